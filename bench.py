@@ -7,9 +7,9 @@ process, before anything here touches the GPU) and exits with the child's code.
 
 A "step" is one pass of the hot path over one z-slab: every rank encodes a 1024x1024x512 uint16 synthetic stack
 (BASELINE.json configs[1]; 1 GiB, already resident in HBM) with ONE C-ABI call.  Weak scaling: per-GPU work is fixed.
-W warm-up steps, then blocks of EXACTLY K steps, each bracketed by barrier + torch.cuda.synchronize() on both sides, MAX
-over ranks per block; blocks are repeated until >= 1 s has been timed and the MEDIAN block is reported (`ms_per_step`,
-`value`; min / max next to it).  value = (N * input bytes * K) / block time, GB = 1e9 bytes.
+W warm-up steps, then ONE block of EXACTLY K timed steps, bracketed by barrier + torch.cuda.synchronize() on both sides, MAX
+over ranks (`ms_per_step` = block time / K, `value`).  --min-seconds S repeats such blocks until >= S s have been timed and
+reports the MEDIAN block (min / max next to it).  --dump-outputs DIR writes the blob of the last timed step as .npy files.  value = (N * input bytes * K) / block time, GB = 1e9 bytes.
 
 N > 1: slabs are independent sqeazy blobs.  `value` is measured with the blobs left on the GPUs that made them (a sharded
 container; only the 8-byte sizes -- its index -- are all_gathered over RCCL per step).  `with_gather` is the same run with
@@ -43,11 +43,9 @@ import time
 
 import numpy as np
 
-# HIP deals streams to hardware queues in creation order, FOUR queues by default: with the default stream in use that leaves three
-# caller streams a queue of their own, and a fourth caller shares one (its kernels never overlap the other's: measured 1250 GB/s
-# with four calls in flight against 1515 with three).  Eight queues, set before the HIP runtime starts: four calls in flight,
-# 1660 GB/s.  A deployment setting like the caller's thread count; the runtime reads it once, at its first call.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
+# HIP deals streams to hardware queues in creation order, four queues by default: with the default stream in use that leaves three
+# caller streams a queue of their own, and a fourth caller shares one (its kernels never overlap the other's).  The queue count is a
+# deployment setting of the HIP runtime; the bench runs with the runtime's default and records it in `config.env`.
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -522,6 +520,30 @@ def gather_stats_delta(g0, g1):
             "gather_ms_per_step": round((g1["seconds"] - g0["seconds"]) / ng * 1e3, 4)}
 
 
+DUMP_SAMPLES = 1 << 21            # --dump-outputs: bytes of the blob sampled at seeded positions
+DUMP_HEAD = 1 << 20               # .. and the blob's first bytes (sqy header + the start of the LZ4 frames)
+
+
+def dump_outputs(out_dir, blob):
+    """--dump-outputs: what a caller of the timed path receives, the compressed blob (a uint8 device tensor), as float32 / float64 .npy
+    files of at most 64 MB together -- its size, its first DUMP_HEAD bytes, DUMP_SAMPLES bytes at positions drawn from a fixed seed
+    (sorted, with the positions next to them) and the sha256 of the whole blob, byte by byte"""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    n = int(blob.numel())
+    idx = np.unique(np.random.default_rng(0x5EA2).integers(0, n, size=min(n, DUMP_SAMPLES)))
+    arrays = {
+        "blob_bytes": np.array([n], np.float64),
+        "blob_head": blob[:DUMP_HEAD].cpu().numpy().astype(np.float32),
+        "blob_sample_index": idx.astype(np.float64),
+        "blob_sample": blob[torch.from_numpy(idx).to(blob.device)].cpu().numpy().astype(np.float32),
+        "blob_sha256": np.frombuffer(hashlib.sha256(blob.cpu().numpy().tobytes()).digest(), np.uint8).astype(np.float32),
+    }
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def spawn_ranks(n, argv):
     """--gpus N without a launcher: start the N ranks as a torchrun child (nothing in this process has touched the GPU yet)"""
     s = socket.socket()
@@ -543,7 +565,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--quick", action="store_true", help="main measurement only (no CPU baseline, host ABI, secondary configs): profiling runs")
-    ap.add_argument("--min-seconds", type=float, default=1.0, help="keep timing blocks of --steps steps until this much has been timed")
+    ap.add_argument("--min-seconds", type=float, default=0.0,
+                    help="keep timing blocks of --steps steps until this much has been timed (default: one block, exactly --steps timed steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0's blob: its size, head, a seeded sample and its sha256) as DIR/<name>.npy")
     ap.add_argument("--frames", type=int, default=SHAPE[0], help="z extent per GPU (default: the BASELINE config)")
     ap.add_argument("--no-gather", action="store_true", help="N>1: skip the second measurement with the RCCL gather to rank 0 inside the step")
     ap.add_argument("--slabs-inflight", type=int, default=SLABS_INFLIGHT)
@@ -551,9 +576,11 @@ def main():
                     help="C-ABI calls in flight per GPU (host threads, one stream + workspace each; the C-ABI is re-entrant like "
                          "the reference's).  1 = strictly one call after the other.  A call is a chain of dependent kernels -- transpose "
                          "(HBM), duplicate search, LZ4 parse (latency-bound, HBM mostly idle), frame gather -- so several calls keep "
-                         "every unit busy (measured in round 3, GPU_MAX_HW_QUEUES=8: 3 -> 1518, 4 -> 1665, 5 -> 1350, 6 -> 1550 GB/s; "
-                         "with the runtime's default of four hardware queues: 3 -> 1515, 4 -> 1250)")
+                         "every unit busy (measured in round 3 with the runtime's default of four hardware queues: 3 -> 1515, 4 -> 1250 GB/s; "
+                         "more calls than queues share them)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     SLABS_INFLIGHT = max(1, args.slabs_inflight)
 
     # (SQY_BENCH_FORCE_SPAWN=1: rehearsal of the self-launch on a one-GPU box)
@@ -641,10 +668,11 @@ def main():
             torch.cuda.synchronize()
 
     def timed_blocks(gather):
-        """blocks of exactly --steps steps, each fenced on both sides, max over ranks per block, until --min-seconds are timed"""
+        """blocks of exactly --steps steps, each fenced on both sides, max over ranks per block: one block, and more until --min-seconds
+        are timed"""
         times, payload = [], 0
         local = []                                          # this rank's own clock per block (N > 1 diagnostics)
-        while sum(times) < args.min_seconds and len(times) < 200:
+        while not times or (sum(times) < args.min_seconds and len(times) < 200):
             fence()
             t0 = time.perf_counter()
             payload = run_steps(args.steps, gather)
@@ -678,6 +706,10 @@ def main():
     sqeazy_amd.profile_enable(False)
     prof = sqeazy_amd.profile_get()
     nblocks = len(times)
+    if args.dump_outputs and rank == 0:
+        # the blob of the last timed step (step K-1 is thread (K-1) % inflight's last), before any other leg reuses its buffer
+        b, off, n = last_blob[(args.steps - 1) % inflight]
+        dump_outputs(args.dump_outputs, outs[(args.steps - 1) % inflight][b][off:off + n])
     # the same leg as an unchanged caller gets it: every option at its default (the transposes of caller streams are not chained)
     default_leg = None
     if world == 1 and not args.quick:
@@ -765,8 +797,8 @@ def main():
             with sqeazy_amd.option(*CHAIN):
                 alt["3_in_flight_DeviceAt"] = alt_point(min(3, inflight), "SQYAMD_PipelineEncode_UI16_DeviceAt")
                 alt["4_in_flight_Device_blob_at_offset_0"] = alt_point(min(4, inflight), "SQYAMD_PipelineEncode_UI16_Device")
-            alt["note"] = ("round 3's headline was 4 in flight / DeviceAt / GPU_MAX_HW_QUEUES=8 as well; round 2's was 3 in flight / _Device; the hardware-queue "
-                           "count is read once by the HIP runtime and cannot be varied inside one process")
+            alt["note"] = ("round 3's headline was 4 in flight / DeviceAt as well, with more hardware queues than the runtime's default; round 2's was "
+                           "3 in flight / _Device; the hardware-queue count is read once by the HIP runtime and cannot be varied inside one process")
         except Exception as e:   # reported, never required
             alt["error"] = repr(e)
     # one call at a time (nothing else in flight), for the record: latency of the call and the kernels' undisturbed durations

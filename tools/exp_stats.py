@@ -5,7 +5,6 @@ own clock ticks (s_memtime), the time and number of its waits for the ring's LDS
 """
 import ctypes, os, sys, threading, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import numpy as np, torch
 import sqeazy_amd
 from sqeazy_amd import synth

@@ -2,7 +2,6 @@
 the number of slab calls the library keeps in flight.   python tools/ns_volume.py [pipeline]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import numpy as np, torch
 import sqeazy_amd
 from sqeazy_amd import synth
