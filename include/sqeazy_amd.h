@@ -76,11 +76,12 @@ SQY_FUNCTION_PREFIX int SQY_Pipeline_Max_Compressed_Length_3D_UI16(const char* p
 
 /* inc/sqeazy.h:219-243, src/sqeazy.cpp:233-268.  true iff the string parses as head filters -> sink -> tail filters
  * (src/sqeazy_pipelines.hpp:31-77) AND every stage is implemented here.  Head filters: diff3x3x1, bitswap1, bitshuffle,
- * raster_reorder, tile_shuffle, frame_shuffle, zcurve_reorder; sinks: pass_through, quantiser (16-bit input; every
+ * raster_reorder, tile_shuffle, frame_shuffle, zcurve_reorder, rmestbkrd, rmbkrd_neighbor5x5x5 (threshold / fraction that std::stoi /
+ * std::stof accept, a finite fraction; {Z, Y, X} shapes only, see DESIGN.md 7 for the shapes refused at encode time); sinks: pass_through, quantiser (16-bit input; every
  * weighting_function with a finite exponent, decode_lut_path), lz4 (accel <= 2, negative = liblz4's acceleration; last stage);
  * tail filters on the sink's `char` stream: diff3x3x1, bitswap1, bitshuffle, lz4, raster_reorder, tile_shuffle, frame_shuffle,
- * zcurve_reorder -- the reference's whole list but the video codecs.  false where the reference says true: the background filters
- * (remove_background, rmbkrd_neighbor5x5x5, rmestbkrd), the video sinks / filters (h264, hevc), lz4 with accel >= 3 (LZ4HC),
+ * zcurve_reorder -- the reference's whole list but the video codecs.  false where the reference says true: remove_background,
+ * the video sinks / filters (h264, hevc), lz4 with accel >= 3 (LZ4HC),
  * stages behind an lz4 sink.  (A geometry the reference leaves undefined for a stage is refused at encode time: error 1.) */
 SQY_FUNCTION_PREFIX bool SQY_Pipeline_Possible_UI16(const char* pipeline_string);
 SQY_FUNCTION_PREFIX bool SQY_Pipeline_Possible_UI8(const char* pipeline_string);
@@ -208,6 +209,9 @@ SQY_FUNCTION_PREFIX void SQYAMD_Release_Workspace(void);
  *   "stored_tail_index"               1 [SQY_NO_STORED_TAIL_INDEX=1 -> 0]  decode of the chunked layout: the stored frames at the end of the LZ4
  *                                     stream (bit planes of noise) are looked for where they must start, the scan for frame headers stops in
  *                                     front of them (0: it reads the whole stream)
+ *   "host_l2_bytes"                   the host CPU's L2 size as the reference reads it (CPUID; 0 .. 2^32-1)  rmestbkrd samples
+ *                                     `Y*X > L2 ? (size_t)(L2 * .75) : Y*X` voxels of its two z faces -- a PARAMETER of the stage's result
+ *                                     (the one option that changes bytes): set it to the value of the host whose blobs are to be matched
  * Set: 0 = done, 1 = unknown name or value out of range.  Get: the value, -1 for an unknown name. */
 SQY_FUNCTION_PREFIX int SQYAMD_Set_Option(const char* name, long value);
 SQY_FUNCTION_PREFIX long SQYAMD_Get_Option(const char* name);

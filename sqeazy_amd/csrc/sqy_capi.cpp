@@ -44,7 +44,7 @@ using sqy::StageKind;
 // ---- run-time options ------------------------------------------------------------------------------
 // Measurement / test switches.  The environment is read ONCE, when the library is loaded (getenv in the middle of a call races with
 // setenv from other host threads); afterwards they change only through SQYAMD_Set_Option (atomics).  None of them changes a byte of
-// any result.
+// any result -- except host_l2_bytes, which stands for a value the reference reads off the host CPU and is a parameter of rmestbkrd.
 long env_flag(const char* name) { const char* v = std::getenv(name); return v && *v && std::strcmp(v, "0") != 0 ? 1 : 0; }
 long env_number(const char* name, long dflt, long lo, long hi)
 {
@@ -70,12 +70,14 @@ struct Options {
     std::atomic<long> noise_digest;                     // frames in place: the transpose leaves the noise digest, the parse proves noise chunks empty from it
     std::atomic<long> transpose_blocks_per_cu;          // frames in place: workgroups of the transposer's grid per CU
     std::atomic<long> stored_tail_index;                // decode, chunked layout: the stored frames at the stream's end are found where they must start, not by the scan
+    std::atomic<long> host_l2_bytes;                    // rmestbkrd: the host CPU's L2 size as the reference's compass reads it (detected; tests set it)
     Options()
         : transpose_chain(env_flag("SQY_NO_TRANSPOSE_CHAIN") ? 0 : 1), transpose_chain_caller_streams(env_flag("SQY_TRANSPOSE_CHAIN_CALLER_STREAMS")),
           block_parallel(env_flag("SQY_NO_BLOCK_PARALLEL") ? 0 : 1), block_parallel_warmup(env_number("SQY_BLOCK_PARALLEL_WARMUP", 65536, 0, kWarmupMax)),
           block_parallel_stats(env_flag("SQY_BLOCK_PARALLEL_STATS")), tail_scan(env_flag("SQY_NO_TAIL_SCAN") ? 0 : 1),
           decode_two_waves(env_flag("SQY_NO_DECODE_TWO_WAVES") ? 0 : 1), noise_digest(env_flag("SQY_NO_NOISE_DIGEST") ? 0 : 1),
-          transpose_blocks_per_cu(env_number("SQY_TRANSPOSE_BLOCKS_PER_CU", 32, 1, 64)), stored_tail_index(env_flag("SQY_NO_STORED_TAIL_INDEX") ? 0 : 1) { sqy::set_bitswap1_blocks_per_cu(transpose_blocks_per_cu.load()); }
+          transpose_blocks_per_cu(env_number("SQY_TRANSPOSE_BLOCKS_PER_CU", 32, 1, 64)), stored_tail_index(env_flag("SQY_NO_STORED_TAIL_INDEX") ? 0 : 1),
+          host_l2_bytes((long)sqy::host_l2_cache_bytes()) { sqy::set_bitswap1_blocks_per_cu(transpose_blocks_per_cu.load()); }
     std::atomic<long>* find(const char* name)
     {
         if (!name) return nullptr;
@@ -89,6 +91,7 @@ struct Options {
         if (!std::strcmp(name, "noise_digest")) return &noise_digest;
         if (!std::strcmp(name, "transpose_blocks_per_cu")) return &transpose_blocks_per_cu;
         if (!std::strcmp(name, "stored_tail_index")) return &stored_tail_index;
+        if (!std::strcmp(name, "host_l2_bytes")) return &host_l2_bytes;
         return nullptr;
     }
 };
@@ -195,11 +198,12 @@ struct Workspace {
     DevBuf spec;              // block-linked frames parsed block-parallel: per block the table it started from and the one it left, the walk lists
     DevBuf diff_side;         // diff3x3x1 in front of a 16-bit bitswap1: the columns the stage can touch (outside the ping/pong rotation)
     DevBuf digest;            // frames in place: the noise digest the transpose leaves for the LZ4 parse (19 KB per 256 KiB chunk)
+    DevBuf bkrd;              // rmestbkrd: the four face histograms and their supports
     void* pinned = nullptr;   // 4 KiB of pinned host memory for small read-backs
     void release_buffers()
     {
         ping.release(); pong.release(); lz4_scratch.release(); csize.release(); frame_off.release();
-        io_src.release(); io_dst.release(); small.release(); plan.release(); dedupe.release(); diff_side.release(); spec.release(); digest.release();
+        io_src.release(); io_dst.release(); small.release(); plan.release(); dedupe.release(); diff_side.release(); spec.release(); digest.release(); bkrd.release();
     }
 };
 
@@ -361,6 +365,32 @@ struct DrainOnExit {
     }
 };
 
+// The background filters' shapes, checked before anything is uploaded or launched (both are head filters: the volume's shape).
+// rmestbkrd reads rows z = 1 and Z-2 (background_scheme_utils.hpp:86); rmbkrd_neighbor5x5x5 takes a row length from an offset its
+// list may not have (sqy::neighbor5_geometry_defined).
+bool background_geometry_ok(const Pipeline& pipe, const std::vector<uint64_t>& dims)
+{
+    for (const Stage& st : pipe.stages) {
+        if (st.kind != StageKind::rmestbkrd && st.kind != StageKind::rmbkrd_neighbor5) continue;
+        if (dims.size() != 3) {
+            std::fprintf(stderr, "[sqeazy]\t %s: shape of rank %zu, the stage takes {Z, Y, X}; refused\n", st.name.c_str(), dims.size());
+            return false;
+        }
+        if (st.kind == StageKind::rmestbkrd && dims[0] < 2) {
+            std::fprintf(stderr, "[sqeazy]\t rmestbkrd: %llu frame(s); the reference reads frames 1 and Z-2 out of bounds; refused\n",
+                         (unsigned long long)dims[0]);
+            return false;
+        }
+        if (st.kind == StageKind::rmbkrd_neighbor5 && !sqy::neighbor5_geometry_defined(dims[0], dims[1], dims[2])) {
+            std::fprintf(stderr, "[sqeazy]\t rmbkrd_neighbor5x5x5: shape %llux%llux%llu takes the reference's row length from an offset it does not "
+                                 "have (X < 5, Y < 5, X = Y = 5, or a single centre row); refused\n",
+                         (unsigned long long)dims[0], (unsigned long long)dims[1], (unsigned long long)dims[2]);
+            return false;
+        }
+    }
+    return true;
+}
+
 bool device_present()
 {
     int n = 0;
@@ -415,6 +445,7 @@ int encode_on_device(Context& cx, const char* pipeline_c, const void* d_src, con
         }
     }
     const uint64_t raw_bytes = len * (uint64_t)elem_size;
+    if (!background_geometry_ok(pipe, dims)) return 1;
 
     Workspace* ws = &cx.ws;
     std::vector<PendingEvent>* pend = &cx.pending;
@@ -578,6 +609,29 @@ int encode_on_device(Context& cx, const char* pipeline_c, const void* d_src, con
                 if (!out) return 1;
                 ProfScope ps("raster_reorder", stream, pend);
                 SQY_HIP(sqy::launch_raster_reorder(cur, out, Z, Y, X, ts, cur_elem, false, stream));
+                cur = out;
+                break;
+            }
+            case StageKind::rmestbkrd: {
+                // remove_estimated_background_scheme::encode (remove_estimated_background_scheme_impl.hpp:71-110); shape checked above
+                const uint64_t portion = sqy::rmestbkrd_face_portion(dims[1] * dims[2], (uint32_t)g_opt.host_l2_bytes.load());
+                if (ws->bkrd.ensure(sqy::rmestbkrd_work_bytes(cur_elem))) return 1;
+                uint8_t* out = next_buf(cur_len * cur_elem);
+                if (!out) return 1;
+                ProfScope ps("rmestbkrd", stream, pend);
+                SQY_HIP(sqy::launch_rmestbkrd(cur, out, dims[0], dims[1], dims[2], portion, cur_elem, ws->bkrd.p, stream));
+                cur = out;
+                break;
+            }
+            case StageKind::rmbkrd_neighbor5: {
+                // flatten_to_neighborhood_scheme::encode (flatten_to_neighborhood_scheme_impl.hpp:90-150): the threshold in the voxel type,
+                // cut_fraction = fraction * (size<Neighborhood>() - 1) in float; shape checked above
+                const float cut = st.nb_fraction * (float)(125u - 1u);
+                uint8_t* out = next_buf(cur_len * cur_elem);
+                if (!out) return 1;
+                ProfScope ps("rmbkrd_neighbor5x5x5", stream, pend);
+                SQY_HIP(sqy::launch_rmbkrd_neighbor5(cur, out, dims[0], dims[1], dims[2], (uint32_t)st.nb_threshold, cut,
+                                                     sqy::neighbor5_z_end(dims[0], dims[2]), cur_elem, stream));
                 cur = out;
                 break;
             }
@@ -1236,6 +1290,7 @@ int encode_from_host(const char* pipeline, const char* src, long* shape, unsigne
     const uint64_t raw = len * (uint64_t)elem_size;
     Pipeline pipe = Pipeline::from_string(pipeline, elem_size);
     pipe.set_n_threads(nthreads);
+    if (!background_geometry_ok(pipe, std::vector<uint64_t>(shape, shape + rank))) return 1;
     // What the caller was told to allocate: SQY_Pipeline_Max_Compressed_Length_* evaluates the bound on a fresh
     // pipeline (n_threads = 1, sqeazy.cpp:144-231).  The reference itself writes past that for pipelines whose
     // header grows while encoding (frame_shuffle's reorder_map on stacks of many small frames); here the
@@ -1363,8 +1418,12 @@ int decode_on_device(Context& cx, const void* d_src_v, uint64_t srclen, void* d_
     bool diff_in_place = false;            // the bit-plane inverse wrote into the volume itself; the diff3x3x1 inverse works there
     const uint32_t* lz4_flag = nullptr;    // the LZ4 decoder's error flag, read when the call ends
     int lz4_flag_stage = 0;
+    // the background filters decode as a copy (remove_estimated_background_scheme_impl.hpp:125-150, flatten_to_neighborhood_scheme_impl.hpp
+    // :152-178): behind `lead` of them at the pipeline's front, stage `lead`'s inverse produces the volume
+    size_t lead = 0;
+    while (lead < pipe.stages.size() && (pipe.stages[lead].kind == StageKind::rmestbkrd || pipe.stages[lead].kind == StageKind::rmbkrd_neighbor5)) ++lead;
     auto out_buf = [&](size_t stage_index, uint64_t bytes) -> uint8_t* {
-        if (stage_index == 0) return static_cast<uint8_t*>(d_dst);               // the first stage's inverse produces the volume
+        if (stage_index <= lead) return static_cast<uint8_t*>(d_dst);            // the first stage's inverse produces the volume
         DevBuf& b = use_ping ? ws->ping : ws->pong;
         use_ping = !use_ping;
         if (b.ensure(std::max<uint64_t>(bytes, 16))) return nullptr;
@@ -1581,7 +1640,7 @@ int decode_on_device(Context& cx, const void* d_src_v, uint64_t srclen, void* d_
                         break;
                     }
                     // (odd sizes: the two stages one after the other; out16 is the quantiser's output buffer below)
-                    if (si - 1 != 0) use_ping = !use_ping;                 // hand the buffer back to the quantiser stage
+                    if (si - 1 > lead) use_ping = !use_ping;               // hand the buffer back to the quantiser stage
                 }
                 // diff3x3x1 as the pipeline's first stage (16-bit, the usual geometry): its inverse can only change the leading columns of
                 // a row, so the planes are transposed straight into the volume and the inverse works there (round 4; before: into a
@@ -1618,6 +1677,9 @@ int decode_on_device(Context& cx, const void* d_src_v, uint64_t srclen, void* d_
             }
             case StageKind::pass_through:
                 break;                                                          // pass_through_scheme_impl.hpp:81-95: bytes are the voxels
+            case StageKind::rmestbkrd:
+            case StageKind::rmbkrd_neighbor5:
+                break;                                                          // a copy: `cur` is the filtered volume (written out at the end)
             case StageKind::zcurve_reorder: {
                 if (h.shape.size() != 3) return stage_error(si);
                 auto t = st.cfg.find("tile_size");
@@ -2192,6 +2254,7 @@ int SQYAMD_Set_Option(const char* name, long value)
     if (!o) return 1;
     if (o == &g_opt.block_parallel_warmup) { if (value < 0 || value > kWarmupMax) return 1; }
     else if (o == &g_opt.transpose_blocks_per_cu) { if (value < 1 || value > 64) return 1; sqy::set_bitswap1_blocks_per_cu(value); }
+    else if (o == &g_opt.host_l2_bytes) { if (value < 0 || value > (long)UINT32_MAX) return 1; }
     else if (value != 0 && value != 1) return 1;
     o->store(value);
     return 0;

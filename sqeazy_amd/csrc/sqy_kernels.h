@@ -159,6 +159,17 @@ hipError_t launch_lz4_frame_gather(const uint8_t* in, uint64_t total, uint32_t c
                                    uint64_t in_stride = 0, bool raw_from_scratch = false);
 
 // quantiser: 65536-bin histogram of u16 voxels (histo is zeroed by the launcher), and out[i] = lut[in[i]]
+// background removal, 1- or 2-byte voxels of a {Z, Y, X} volume
+// rmestbkrd (encoders/remove_estimated_background_scheme_impl.hpp:71-110): four face histograms (frames z = 0 and Z-1: their first
+// `portion` voxels; rows y = 0 and Y-1 of frames 1, Z/2, Z-2), the 99 % support of each, out = in > t ? in - t : 0 with t = (T)min of the
+// supports -- all on the stream, no host round trip.  work: rmestbkrd_work_bytes(elem_size) bytes of the call's own workspace.  Z >= 2
+uint64_t rmestbkrd_work_bytes(int elem_size);
+hipError_t launch_rmestbkrd(const void* in, void* out, uint64_t Z, uint64_t Y, uint64_t X, uint64_t portion, int elem_size, void* work,
+                            hipStream_t stream);
+// rmbkrd_neighbor5x5x5: every voxel of `out` written; centres z in [2, z_end), y in [2, Y-2), x in [2, X-1) with in >= threshold keep
+// their value when (float)(neighbours below threshold) <= cut (= fraction * 124.f), all else 0 (neighbours past the end: not counted)
+hipError_t launch_rmbkrd_neighbor5(const void* in, void* out, uint64_t Z, uint64_t Y, uint64_t X, uint32_t threshold, float cut,
+                                   uint64_t z_end, int elem_size, hipStream_t stream);
 hipError_t launch_histogram_u16(const uint16_t* in, uint64_t len, uint32_t* histo, hipStream_t stream);
 hipError_t launch_quantiser_apply_u16(const uint16_t* in, uint8_t* out, uint64_t len, const uint8_t* lut, hipStream_t stream);
 // .. with the 8-bit bit-plane transpose of the sink's bytes in the same pass (quantiser->bitswap1; `in` 16-byte aligned): out = the 8

@@ -6859,4 +6859,328 @@ hipError_t launch_frame_scatter(const void* in, void* out, uint64_t Z, uint64_t 
     return hipGetLastError();
 }
 
+
+// ------------------------------------------------------------------------------------------------
+// background removal (head filters rmestbkrd and rmbkrd_neighbor5x5x5)
+//
+// rmestbkrd (encoders/remove_estimated_background_scheme_impl.hpp:71-110): the 99 % support of four face histograms
+// (background_scheme_utils.hpp:35-105, hist_impl.hpp:60-90, 355-380), their minimum truncated to the voxel type is subtracted with a
+// clamp at 0 (remove_background_scheme_impl.hpp:73-95).  Three kernels, no host round trip: the faces' histograms (one launch, four
+// histograms in the call's workspace), the support of each (one workgroup per histogram, the threshold stays in device memory),
+// the subtract (a streaming pass that reads the four supports).
+// ------------------------------------------------------------------------------------------------
+// The faces of a microscopy stack are background, a narrow band of values: every workgroup counts into a window of the value range in
+// LDS (16384 bins for 16-bit voxels -- 64 KiB --, all 256 for 8-bit), centred on its first voxel; values outside go to the global
+// histogram directly, the window is added there at the end.  (Global atomics alone: 2.3 ms for the two 1024 x 1024 frames of the
+// bench stack, thousands of waves adding to the same few bins.)
+constexpr uint32_t BKRD_WIN = 16384;
+
+template <typename T>
+__global__ __launch_bounds__(256)
+void bkrd_face_histo_kernel(const T* __restrict__ in, uint64_t Z, uint64_t Y, uint64_t X, uint64_t portion, uint32_t* __restrict__ histo)
+{
+    constexpr uint32_t NB = 1u << (8 * sizeof(T));
+    constexpr uint32_t WIN = NB < BKRD_WIN ? NB : BKRD_WIN;
+    __shared__ uint32_t win[WIN];
+    // blockIdx.y: 0 / 1 the first `portion` voxels of frames z = 0 / Z-1, 2..4 / 5..7 row y = 0 / Y-1 of frames z = 1, Z/2, Z-2
+    const uint32_t seg = blockIdx.y;
+    const uint64_t YX = Y * X;
+    uint64_t base, len;
+    uint32_t face;
+    if (seg < 2) {
+        face = seg;
+        base = seg == 0 ? 0 : (Z - 1) * YX;
+        len = portion;
+    } else {
+        face = seg < 5 ? 2 : 3;
+        const uint32_t k = (seg - 2) % 3;
+        const uint64_t z = k == 0 ? 1 : k == 1 ? Z / 2 : Z - 2;
+        base = z * YX + (face == 2 ? 0 : (Y - 1) * X);
+        len = X;
+    }
+    const uint64_t first = (uint64_t)blockIdx.x * 256;
+    if (first >= len) return;                                           // (uniform: nothing of this segment for the workgroup)
+    uint32_t* h = histo + (uint64_t)face * NB;
+    const uint32_t v0 = in[base + first];
+    const uint32_t wbase = v0 > WIN / 2 ? (v0 - WIN / 2 < NB - WIN ? v0 - WIN / 2 : NB - WIN) : 0;
+    for (uint32_t i = threadIdx.x; i < WIN; i += 256) win[i] = 0;
+    __syncthreads();
+    for (uint64_t i = first + threadIdx.x; i < len; i += (uint64_t)gridDim.x * 256) {
+        const uint32_t key = in[base + i];
+        const uint32_t r = key - wbase;
+        if (r < WIN) atomicAdd(&win[r], 1u); else atomicAdd(&h[key], 1u);
+    }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < WIN; i += 256) {
+        const uint32_t c = win[i];
+        if (c) atomicAdd(&h[wbase + i], c);
+    }
+}
+
+// histogram::calc_support(0.99f) on a histogram filled by add_from_image only (smallest / largest populated bin still 0 and the type's
+// maximum): support_index sums the bins into an int (std::accumulate(.., 0)) held as a double, walks a double running sum and stops at
+// the first bin m with running / total > (double)0.99f (none: m = bins.size(), narrowed to T); then
+// result = m > 0 ? float(uint32(bins[m] * m + bins[m-1] * (m-1))) / float(bins[m-1] + bins[m]) : 0.
+// The running sums are exact integers, so a prefix scan over the workgroup divides the same operands the sequential walk does.
+template <typename T>
+__global__ __launch_bounds__(256)
+void bkrd_support_kernel(const uint32_t* __restrict__ histo, float* __restrict__ supports)
+{
+    constexpr uint32_t NB = 1u << (8 * sizeof(T));
+    constexpr uint32_t PER = NB / 256;
+    __shared__ uint64_t part[256];
+    __shared__ uint32_t first;
+    const uint32_t* h = histo + (uint64_t)blockIdx.x * NB;
+    const uint32_t t = threadIdx.x;
+    uint64_t mine = 0;
+    for (uint32_t k = 0; k < PER; ++k) mine += h[t * PER + k];
+    part[t] = mine;
+    if (t == 0) first = NB;
+    __syncthreads();
+    for (uint32_t d = 1; d < 256; d <<= 1) {                 // inclusive scan of the per-thread sums
+        const uint64_t add = t >= d ? part[t - d] : 0;
+        __syncthreads();
+        part[t] += add;
+        __syncthreads();
+    }
+    const double total = (double)(int32_t)(uint32_t)part[255];
+    const double thr = (double)0.99f;
+    double running = (double)(part[t] - mine);
+    for (uint32_t k = 0; k < PER; ++k) {
+        running += (double)h[t * PER + k];
+        if (running / total > thr) { atomicMin(&first, t * PER + k); break; }
+    }
+    __syncthreads();
+    if (t == 0) {
+        const uint32_t m = first & (NB - 1);                  // (T) of bins.size() when no bin qualifies
+        float result = 0.f;
+        if (m > 0) {
+            const uint32_t num = h[m] * m + h[m - 1] * (m - 1);
+            result = (float)num / (float)(h[m - 1] + h[m]);
+        }
+        supports[blockIdx.x] = result;
+    }
+}
+
+// out = in > t ? in - t : 0 with t = (T)min(supports[0..3]) (remove_background_scheme_impl.hpp:88-90; std::min_element)
+template <typename T>
+__device__ __forceinline__ uint32_t bkrd_threshold(const float* supports)
+{
+    float r = supports[0];
+    for (int i = 1; i < 4; ++i) if (supports[i] < r) r = supports[i];
+    const float top = (float)((1u << (8 * sizeof(T))) - 1);
+    return r >= top ? (uint32_t)top : (uint32_t)r;           // (r is in [0, 2^bits): a weighted mean of two bin indices)
+}
+
+template <typename T>
+__global__ __launch_bounds__(256)
+void bkrd_subtract_kernel(const T* __restrict__ in, T* __restrict__ out, uint64_t len, const float* __restrict__ supports, int vec)
+{
+    const uint32_t t = bkrd_threshold<T>(supports);
+    const uint64_t stride = (uint64_t)gridDim.x * 256;
+    const uint64_t gid = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    uint64_t done = 0;
+    if (vec) {
+        constexpr uint32_t BITS = 8 * sizeof(T), MASK = (1u << BITS) - 1;
+        const uint64_t nvec = len / (16 / sizeof(T));
+        const uint4* src = reinterpret_cast<const uint4*>(in);
+        uint4* dst = reinterpret_cast<uint4*>(out);
+        for (uint64_t i = gid; i < nvec; i += 4 * stride) {
+            uint4 v[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) if (i + u * stride < nvec) v[u] = src[i + u * stride];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                if (i + u * stride >= nvec) continue;
+                uint32_t w[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    uint32_t r = 0;
+#pragma unroll
+                    for (uint32_t s = 0; s < 32; s += BITS) {
+                        const uint32_t e = (w[j] >> s) & MASK;
+                        r |= (e > t ? e - t : 0u) << s;
+                    }
+                    w[j] = r;
+                }
+                dst[i + u * stride] = make_uint4(w[0], w[1], w[2], w[3]);
+            }
+        }
+        done = nvec * (16 / sizeof(T));
+    }
+    for (uint64_t i = done + gid; i < len; i += stride) {
+        const uint32_t e = in[i];
+        out[i] = (T)(e > t ? e - t : 0u);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// rmbkrd_neighbor5x5x5 (flatten_to_neighborhood_scheme_impl.hpp:90-150, neighborhood_utils.hpp:141-240, background_scheme_utils.hpp:232-272)
+// centres z in [2, z_end), y in [2, Y-2), x in [2, X-1); a centre with in >= thr keeps its value when the number n of its 125 flat
+// neighbours c + dz*YX + dy*X + dx (d in [-2, 2], rows wrap) with in < thr satisfies (float)n <= cut; every other voxel is 0, and so is
+// a neighbour at or past the volume's end.
+// n is a box sum of the 0/1 field b = (in < thr) over FLAT offsets, so it separates exactly: 5 taps along stride 1, then X, then Y*X.
+// A workgroup owns a 64 x 16 column of the volume and walks NB5_ZC frames down it: each frame's b box (68 x 20, the flat offsets make
+// the halo of a row the neighbouring row's voxels, exactly as the reference reads them) is loaded once into LDS, summed along x and
+// y into a ring of five planes, and the ring's sum is the count of the frame two planes up.  Sums of 0/1 bytes never carry out of a
+// byte (<= 125), so four columns are summed per 32-bit word.
+// ------------------------------------------------------------------------------------------------
+// a workgroup barrier for LDS only: the global loads of the next frame stay in flight across it (the release fence of __syncthreads
+// waits for every outstanding memory operation)
+__device__ __forceinline__ void lds_barrier()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+}
+
+constexpr int NB5_TX = 64, NB5_TY = 16, NB5_ZC = 64;
+constexpr int NB5_BW = NB5_TX + 4, NB5_BH = NB5_TY + 4;                 // the b box of one frame: 68 x 20 bytes
+constexpr int NB5_BOX = NB5_BW * NB5_BH;                                 // 1360
+constexpr int NB5_PRE = (NB5_BOX + 255) / 256;                          // 6 loads per thread and frame
+
+template <typename T>
+__global__ __launch_bounds__(256)
+void bkrd_neighbor5_kernel(const T* __restrict__ in, T* __restrict__ out, int64_t Z, int64_t Y, int64_t X, uint32_t thr, float cut,
+                           int64_t z_end, uint32_t ntx, uint32_t nty)
+{
+    __shared__ uint32_t bb[NB5_BH][NB5_BW / 4 + 1];                     // b box, bytes (one spare word per row for the shifted reads)
+    __shared__ uint32_t r1[NB5_BH][NB5_TX / 4];                         // 5-tap sums along x
+    __shared__ uint32_t ring[5][NB5_TY][NB5_TX / 4];                    // .. then along y, five frames
+    const uint32_t t = threadIdx.x;
+    uint64_t bid = blockIdx.x;
+    const int64_t x0 = (int64_t)(bid % ntx) * NB5_TX; bid /= ntx;
+    const int64_t y0 = (int64_t)(bid % nty) * NB5_TY; bid /= nty;
+    const int64_t zs = (int64_t)bid * NB5_ZC;
+    const int64_t ze = zs + NB5_ZC < Z ? zs + NB5_ZC : Z;
+    const int64_t YX = Y * X, N = Z * YX;
+    // this thread's output: row j, columns c4 .. c4+3 of the tile
+    const int64_t j = t >> 4, c4 = (t & 15) * 4;
+    const int64_t oy = y0 + j, ox = x0 + c4;
+    const bool tile_has_centres = x0 + NB5_TX > 2 && x0 < X - 1 && y0 + NB5_TY > 2 && y0 < Y - 2 && ze > 2 && zs < z_end;
+    auto store4 = [&](int64_t z, const uint32_t* v) {
+        if (oy >= Y || ox >= X) return;
+        const int64_t o = z * YX + oy * X + ox;
+        if (ox + 3 < X && (o & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & (4 * sizeof(T) - 1)) == 0) {
+            if (sizeof(T) == 2) *reinterpret_cast<uint2*>(out + o) = make_uint2(v[0] | v[1] << 16, v[2] | v[3] << 16);
+            else *reinterpret_cast<uint32_t*>(out + o) = v[0] | v[1] << 8 | v[2] << 16 | v[3] << 24;
+        } else {
+            for (int k = 0; k < 4; ++k) if (ox + k < X) out[o + k] = (T)v[k];
+        }
+    };
+    if (!tile_has_centres) {
+        const uint32_t zero[4] = {0, 0, 0, 0};
+        for (int64_t z = zs; z < ze; ++z) store4(z, zero);
+        return;
+    }
+    uint8_t* bbytes = reinterpret_cast<uint8_t*>(&bb[0][0]);
+    uint32_t pre[NB5_PRE];
+    auto load = [&](int64_t p) {
+#pragma unroll
+        for (int k = 0; k < NB5_PRE; ++k) {
+            const int idx = (int)t + 256 * k;
+            pre[k] = 0xffffffffu;                                            // (>= thr: not counted)
+            if (idx < NB5_BOX) {
+                const int row = idx / NB5_BW, col = idx - row * NB5_BW;
+                const int64_t f = p * YX + (y0 - 2 + row) * X + (x0 - 2 + col);
+                if (f >= 0 && f < N) pre[k] = in[f];
+            }
+        }
+    };
+    load(zs - 2);
+    for (int64_t p = zs - 2; p < ze + 2; ++p) {
+#pragma unroll
+        for (int k = 0; k < NB5_PRE; ++k) {
+            const int idx = (int)t + 256 * k;
+            if (idx < NB5_BOX) {
+                const int row = idx / NB5_BW, col = idx - row * NB5_BW;
+                bbytes[row * (NB5_BW + 4) + col] = pre[k] < thr ? 1 : 0;
+            }
+        }
+        if (p + 1 < ze + 2) load(p + 1);                                     // next frame's loads in flight during the sums
+        lds_barrier();
+        for (int w = (int)t; w < NB5_BH * (NB5_TX / 4); w += 256) {
+            const int row = w >> 4, cw = w & 15;
+            const uint64_t pair = (uint64_t)bb[row][cw] | (uint64_t)bb[row][cw + 1] << 32;
+            r1[row][cw] = (uint32_t)pair + (uint32_t)(pair >> 8) + (uint32_t)(pair >> 16) + (uint32_t)(pair >> 24) + (uint32_t)(pair >> 32);
+        }
+        lds_barrier();
+        const int slot = (int)((p - (zs - 2)) % 5);
+        ring[slot][j][t & 15] = r1[j][t & 15] + r1[j + 1][t & 15] + r1[j + 2][t & 15] + r1[j + 3][t & 15] + r1[j + 4][t & 15];
+        lds_barrier();
+        const int64_t z = p - 2;
+        if (z < zs) continue;
+        const uint32_t n4 = ring[0][j][t & 15] + ring[1][j][t & 15] + ring[2][j][t & 15] + ring[3][j][t & 15] + ring[4][j][t & 15];
+        uint32_t v[4] = {0, 0, 0, 0};
+        if (z >= 2 && z < z_end && oy >= 2 && oy < Y - 2 && oy < Y) {
+            const int64_t o = z * YX + oy * X + ox;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int64_t x = ox + k;
+                if (x < 2 || x >= X - 1) continue;
+                const uint32_t c = in[o + k];
+                const uint32_t n = (n4 >> (8 * k)) & 0xffu;
+                if (c >= thr && !((float)n > cut)) v[k] = c;
+            }
+        }
+        store4(z, v);
+    }
+}
+
+template <typename T>
+static hipError_t launch_rmestbkrd_t(const T* in, T* out, uint64_t Z, uint64_t Y, uint64_t X, uint64_t portion, void* work, hipStream_t stream)
+{
+    constexpr uint64_t NB = 1ull << (8 * sizeof(T));
+    uint32_t* histo = static_cast<uint32_t*>(work);
+    float* supports = reinterpret_cast<float*>(histo + 4 * NB);
+    hipError_t e = hipMemsetAsync(histo, 0, 4 * NB * sizeof(uint32_t), stream);
+    if (e != hipSuccess) return e;
+    const uint64_t most = portion > X ? portion : X;
+    uint64_t bx = (most + 255) / 256;
+    if (bx > 128) bx = 128;                                              // (each workgroup adds its window to the histogram at the end)
+    if (bx == 0) bx = 1;
+    hipLaunchKernelGGL(bkrd_face_histo_kernel<T>, dim3((unsigned)bx, 8), dim3(256), 0, stream, in, Z, Y, X, portion, histo);
+    hipLaunchKernelGGL(bkrd_support_kernel<T>, dim3(4), dim3(256), 0, stream, (const uint32_t*)histo, supports);
+    const uint64_t len = Z * Y * X;
+    const int vec = ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
+    uint64_t blocks = (len / (16 / sizeof(T)) + 1024 - 1) / 1024;      // four 16-byte items per thread
+    const uint64_t cap = (uint64_t)num_cus() * 16;
+    if (blocks > cap) blocks = cap;
+    if (blocks == 0) blocks = 1;
+    hipLaunchKernelGGL(bkrd_subtract_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, stream, in, out, len, (const float*)supports, vec);
+    return hipGetLastError();
+}
+
+uint64_t rmestbkrd_work_bytes(int elem_size)
+{
+    return 4 * (1ull << (8 * elem_size)) * sizeof(uint32_t) + 64;
+}
+
+hipError_t launch_rmestbkrd(const void* in, void* out, uint64_t Z, uint64_t Y, uint64_t X, uint64_t portion, int elem_size, void* work,
+                            hipStream_t stream)
+{
+    if (Z < 2 || Y == 0 || X == 0 || portion > Y * X) return hipErrorInvalidValue;
+    if (elem_size == 2) return launch_rmestbkrd_t(static_cast<const uint16_t*>(in), static_cast<uint16_t*>(out), Z, Y, X, portion, work, stream);
+    if (elem_size == 1) return launch_rmestbkrd_t(static_cast<const uint8_t*>(in), static_cast<uint8_t*>(out), Z, Y, X, portion, work, stream);
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_rmbkrd_neighbor5(const void* in, void* out, uint64_t Z, uint64_t Y, uint64_t X, uint32_t threshold, float cut,
+                                   uint64_t z_end, int elem_size, hipStream_t stream)
+{
+    if (Z == 0 || Y == 0 || X == 0) return hipSuccess;
+    const uint64_t ntx = (X + NB5_TX - 1) / NB5_TX, nty = (Y + NB5_TY - 1) / NB5_TY, ntz = (Z + NB5_ZC - 1) / NB5_ZC;
+    const uint64_t blocks = ntx * nty * ntz;
+    if (blocks > 0x7fffffffull || ntx > 0xffffffffull || nty > 0xffffffffull) return hipErrorInvalidValue;
+    if (elem_size == 2)
+        hipLaunchKernelGGL(bkrd_neighbor5_kernel<uint16_t>, dim3((unsigned)blocks), dim3(256), 0, stream, static_cast<const uint16_t*>(in),
+                           static_cast<uint16_t*>(out), (int64_t)Z, (int64_t)Y, (int64_t)X, threshold, cut, (int64_t)z_end, (uint32_t)ntx, (uint32_t)nty);
+    else if (elem_size == 1)
+        hipLaunchKernelGGL(bkrd_neighbor5_kernel<uint8_t>, dim3((unsigned)blocks), dim3(256), 0, stream, static_cast<const uint8_t*>(in),
+                           static_cast<uint8_t*>(out), (int64_t)Z, (int64_t)Y, (int64_t)X, threshold, cut, (int64_t)z_end, (uint32_t)ntx, (uint32_t)nty);
+    else
+        return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
 } // namespace sqy

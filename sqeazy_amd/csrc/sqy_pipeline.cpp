@@ -6,6 +6,8 @@
 #pragma clang fp contract(off)
 
 #include <algorithm>
+#include <cerrno>
+#include <climits>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -14,6 +16,9 @@
 #include <sstream>
 #include <sys/stat.h>
 #include <thread>
+#if defined(__x86_64__) || defined(__i386__)
+#include <cpuid.h>
+#endif
 
 namespace sqy {
 
@@ -279,6 +284,8 @@ static StageKind kind_of(const std::string& n)
     if (n == "quantiser") return StageKind::quantiser;
     if (n == "lz4") return StageKind::lz4;
     if (n == "pass_through") return StageKind::pass_through;
+    if (n == "rmestbkrd") return StageKind::rmestbkrd;
+    if (n == "rmbkrd_neighbor5x5x5") return StageKind::rmbkrd_neighbor5;
     return StageKind::unsupported;
 }
 
@@ -289,6 +296,9 @@ std::string Stage::config() const
         case StageKind::diff3x3x1: return "";                                    // diff_scheme_impl.hpp:55-59
         case StageKind::lz4: return lz4.config();                                // lz4.hpp:132-141
         case StageKind::pass_through: return "";
+        case StageKind::rmestbkrd: return "";                                    // remove_estimated_background_scheme_impl.hpp:32-40
+        case StageKind::rmbkrd_neighbor5:                                        // flatten_to_neighborhood_scheme_impl.hpp:73-80 (%f)
+            return "threshold=" + std::to_string(nb_threshold) + ",fraction=" + std::to_string(nb_fraction);
         case StageKind::quantiser: {                                             // quantiser_scheme_impl.hpp:102-118
             std::string s;
             size_t count = 0;
@@ -389,6 +399,15 @@ Pipeline Pipeline::from_string(const std::string& s, int elem_size)
         st.kind = kind_of(pr.first);
         st.cfg = parse_minors(pr.second);
         if (st.kind == StageKind::lz4) st.lz4 = Lz4Params(pr.second);
+        if (st.kind == StageKind::rmbkrd_neighbor5) {
+            long t = 1;
+            float f = 0.5f;
+            if (neighbor5_parse(st.cfg, &t, &f)) {
+                // `raw_type threshold = std::stoi(..)`: the int narrowed to the voxel type (modulo 2^8 / 2^16)
+                st.nb_threshold = elem_size == 2 ? (long)(uint16_t)t : elem_size == 1 ? (long)(uint8_t)t : t;
+                st.nb_fraction = f;
+            }
+        }
         if (st.kind == StageKind::raster_reorder && elem_size > 0 && !st.cfg.count("tile_size"))
             st.cfg["tile_size"] = std::to_string(16 / (p.sink_index >= 0 ? 1 : elem_size));   // raster_reorder_scheme_impl.hpp:23 (behind the sink: raster_reorder_scheme<char>)
         if (p.sink_index < 0) {
@@ -452,6 +471,15 @@ bool Pipeline::supported(const std::string& s, int elem_size, std::string* why)
                 break;
             case StageKind::pass_through:
                 break;
+            case StageKind::rmestbkrd:
+                break;                                                           // (head filter only; the shape is checked at encode time)
+            case StageKind::rmbkrd_neighbor5: {
+                long t;
+                float f;
+                if (!neighbor5_parse(st.cfg, &t, &f))
+                    return fail("rmbkrd_neighbor5x5x5: threshold / fraction the reference's std::stoi / std::stof throws on, or a fraction that is not finite");
+                break;
+            }
             default:
                 return fail("stage '" + st.name + "' is not implemented on MI355X");
         }
@@ -477,6 +505,90 @@ bool raster_geometry_defined(uint64_t Z, uint64_t Y, uint64_t X, uint64_t ts, in
     const uint64_t block = 16 / (uint64_t)elem_size;
     if (nrem == 0 && ts % block == 0 && ts != block) return false;       // :160-243: encode_full_simd overwrites the tile row's head
     return true;
+}
+
+// ---- background removal ----
+bool neighbor5_parse(const std::map<std::string, std::string>& cfg, long* threshold, float* fraction)
+{
+    // flatten_to_neighborhood_scheme(const std::string&) (flatten_to_neighborhood_scheme_impl.hpp:44-60): fraction = std::stof,
+    // threshold = std::stoi.  libstdc++ throws when nothing was converted or strtof / strtol report ERANGE (stoi: also outside int)
+    *threshold = 1;
+    *fraction = 0.5f;
+    auto f = cfg.find("fraction");
+    if (f != cfg.end()) {
+        const char* p = f->second.c_str();
+        char* end = nullptr;
+        errno = 0;
+        const float v = std::strtof(p, &end);
+        if (end == p || errno == ERANGE || !std::isfinite(v)) return false;
+        *fraction = v;
+    }
+    auto t = cfg.find("threshold");
+    if (t != cfg.end()) {
+        const char* p = t->second.c_str();
+        char* end = nullptr;
+        errno = 0;
+        const long v = std::strtol(p, &end, 10);
+        if (end == p || errno == ERANGE || v < INT_MIN || v > INT_MAX) return false;
+        *threshold = v;
+    }
+    return true;
+}
+
+uint64_t neighbor5_z_end(uint64_t Z, uint64_t X)
+{
+    // halo::compute_offsets_in_x (neighborhood_utils.hpp:199-235): z runs to non_halo_end(2) = world[2] - 2 = X - 2 (row_major::x == 2),
+    // offsets at or past the volume's end are dropped -- so z < min(X - 2, Z)
+    const uint64_t e = std::min(X >= 2 ? X - 2 : 0, Z);
+    return e < 2 ? 2 : e;
+}
+
+bool neighbor5_geometry_defined(uint64_t Z, uint64_t Y, uint64_t X)
+{
+    if (Z == 0 || X < 5 || Y < 5) return false;          // (X - 4)(Y - 4) <= 1: the one-offset branch, halo_size_x = length - offsets[2]
+    if (X == 5 && Y == 5) return false;
+    const uint64_t n_offsets = (neighbor5_z_end(Z, X) - 2) * (Y - 4);
+    return n_offsets != 1;                               // (one offset: `offsets.size() != 1` fails and offsets[2] is read again)
+}
+
+uint32_t host_l2_cache_bytes()
+{
+#if defined(__x86_64__) || defined(__i386__)
+    // compass bit_view::range(b, e): bits [b, e) -- so range(16, 31) is 15 bits wide
+    auto range = [](uint32_t v, uint32_t b, uint32_t e) -> uint32_t { return (v >> b) & ((1u << (e - b)) - 1u); };
+    unsigned a = 0, b = 0, c = 0, d = 0;
+    __cpuid_count(0, 0, a, b, c, d);
+    char vendor[12];
+    std::memcpy(vendor, &b, 4); std::memcpy(vendor + 4, &d, 4); std::memcpy(vendor + 8, &c, 4);
+    const std::string brand(vendor, 12);
+    std::vector<uint32_t> sizes;
+    if (brand.find("AMD") != std::string::npos) {                  // cache::on_amd (compass.hpp:993-1021)
+        __cpuid_count(0x80000005u, 0, a, b, c, d);
+        if (range(c, 0, 7)) {
+            sizes.push_back(range(c, 24, 31) * 1024u);
+            __cpuid_count(0x80000006u, 0, a, b, c, d);
+            sizes.push_back((range(c, 16, 31) & 0xffffu) * 1024u);
+            sizes.push_back(range(d, 19, 31) * 512u * 1024u);
+        }
+    }
+    if (brand.find("Intel") != std::string::npos) {                // cache::on_intel (compass.hpp:955-990)
+        for (uint32_t l = 0; l < 8; ++l) {
+            __cpuid_count(4, l, a, b, c, d);
+            if (!(a & 2u) || range(a, 5, 8) != l) continue;
+            const uint32_t ways = 1 + range(b, 22, 31), partitions = 1 + range(b, 12, 21), line = 1 + range(b, 0, 11), sets = 1 + c;
+            sizes.push_back(ways * partitions * line * sets);
+        }
+    }
+    return sizes.size() > 1 ? sizes[1] : 0;                         // cache::level(2)
+#else
+    return 0;
+#endif
+}
+
+uint64_t rmestbkrd_face_portion(uint64_t frame_voxels, uint32_t l2_bytes)
+{
+    // background_scheme_utils.hpp:44-45: voxels compared with bytes, (index_type)(L2 * .75)
+    return frame_voxels > (uint64_t)l2_bytes ? (uint64_t)(l2_bytes * .75) : frame_voxels;
 }
 
 int clean_number_of_threads(int n)

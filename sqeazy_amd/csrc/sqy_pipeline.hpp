@@ -27,7 +27,8 @@ std::vector<std::string> split_outside_verbatim(const std::string& s, const std:
 pairs_t parse_pairs(const std::string& pipeline);
 std::map<std::string, std::string> parse_minors(const std::string& cfg);
 
-enum class StageKind { diff3x3x1, bitswap1, bitshuffle, frame_shuffle, raster_reorder, zcurve_reorder, tile_shuffle, quantiser, lz4, pass_through, unsupported };
+enum class StageKind { diff3x3x1, bitswap1, bitshuffle, frame_shuffle, raster_reorder, zcurve_reorder, tile_shuffle, quantiser, lz4, pass_through,
+                       rmestbkrd, rmbkrd_neighbor5, unsupported };
 
 struct Lz4Params {
     int accel = 1;
@@ -65,6 +66,10 @@ struct Stage {
     StageKind kind = StageKind::unsupported;
     std::map<std::string, std::string> cfg;   // parsed (k=v,...) payload; std::map => sorted like the reference's config_map
     Lz4Params lz4;
+    // rmbkrd_neighbor5x5x5 (flatten_to_neighborhood_scheme_impl.hpp:44-80): std::stoi into the voxel type (wrapped to 8 / 16 bits when
+    // from_string knows the voxel size), std::stof
+    long nb_threshold = 1;
+    float nb_fraction = 0.5f;
     std::string config() const;               // re-serialised configuration, as the reference's config()
     std::string full_name() const;            // name or name(config)
 };
@@ -106,6 +111,18 @@ bool zcurve_geometry_defined(uint64_t Z, uint64_t Y, uint64_t X, uint64_t tile_s
 bool tile_shuffle_geometry_defined(uint64_t Z, uint64_t Y, uint64_t X, uint64_t tile_size);
 // metric = (T)(sequential float sum / voxels per tile), sorted ascending, slot i <- first tile whose metric equals sorted[i]
 void tile_shuffle_order(const float* sums, size_t ntiles, size_t per_tile, int elem_size, uint64_t* decode_map, bool signed_char = false);
+// rmbkrd_neighbor5x5x5's parameters as the reference's constructor reads them: false where std::stoi / std::stof would throw, and for a
+// fraction that is not finite.  *threshold is the int std::stoi returns (not yet narrowed to the voxel type)
+bool neighbor5_parse(const std::map<std::string, std::string>& cfg, long* threshold, float* fraction);
+// rmbkrd_neighbor5x5x5 (flatten_to_neighborhood_scheme_impl.hpp:90-150, neighborhood_utils.hpp:141-240): false for the geometries whose row
+// length the reference takes from an element its offset list does not have (X < 5, Y < 5, X = Y = 5, exactly one offset)
+bool neighbor5_geometry_defined(uint64_t Z, uint64_t Y, uint64_t X);
+// centres of the 5x5x5 filter: z in [2, z_end), y in [2, Y - 2), x in [2, X - 1); z_end = max(2, min(X - 2, Z))
+uint64_t neighbor5_z_end(uint64_t Z, uint64_t X);
+// the host CPU's L2 size in bytes as the reference's compass reads it (compass.hpp:950-1035): CPUID leaf 4 on Intel, 0x80000006 on AMD,
+// 0 on any other vendor or architecture.  rmestbkrd samples `frame > L2 ? (size_t)(L2 * .75) : frame` voxels of the z faces
+uint32_t host_l2_cache_bytes();
+uint64_t rmestbkrd_face_portion(uint64_t frame_voxels, uint32_t l2_bytes);
 // bitshuffle: elements per block (bshuf_default_block_size for 0); 0 when the configured size is not a multiple of 8
 uint64_t bitshuffle_block_elems(int elem_size, uint64_t block_size);
 
