@@ -153,6 +153,13 @@ struct ProfScope {
     }
 };
 
+// one launch (an expression of type hipError_t), timed under `name` when profiling is on; `stream` and `pend` are the call's
+#define SQY_TIMED(name, launch)                                                                         \
+    do {                                                                                                \
+        ProfScope ps_(name, stream, pend);                                                              \
+        SQY_HIP(launch);                                                                                \
+    } while (0)
+
 void prof_collect(std::vector<PendingEvent>& pending)
 {
     for (PendingEvent& p : pending) {
@@ -397,6 +404,26 @@ bool device_present()
     return hipGetDeviceCount(&n) == hipSuccess && n > 0;
 }
 
+// Multiplies the extents of a shape up to the first one that is not positive (then 0) or the first partial product of 2^31 or more (then
+// that product).  One encode call takes [1, 2^31) voxels: the reference multiplies the extents into an `int` (dynamic_pipeline.hpp:565).
+uint64_t voxel_count(const long* shape, unsigned rank)
+{
+    uint64_t n = 1;
+    for (unsigned i = 0; i < rank; ++i) {
+        if (shape[i] <= 0) return 0;
+        n *= (uint64_t)shape[i];
+        if (n >= ((uint64_t)1 << 31)) break;
+    }
+    return n;
+}
+
+// frame_shuffle's frame_chunk_size (frame_shuffle_scheme_impl.hpp:86-90); negative reads as 0, which both directions refuse
+uint64_t frame_chunk_size(const Stage& st)
+{
+    auto c = st.cfg.find("frame_chunk_size");
+    return c != st.cfg.end() ? (uint64_t)std::max(std::atoi(c->second.c_str()), 0) : 1;
+}
+
 // ---- encode --------------------------------------------------------------------------------------
 // The body of dynamic_pipeline::encode (dynamic_pipeline.hpp:560-616) on device buffers.
 // dstoffset == nullptr: the blob starts at d_dst.  Otherwise it may start anywhere inside [d_dst, d_dst + dst_capacity) and
@@ -410,6 +437,778 @@ struct FrameQuery {
     long* offsets = nullptr;    // out, relative to the blob start: frames 0, every, 2 every, ..; then the blob length
     int max_entries = 0;
     int count = 0;              // out: frames listed (the end entry comes on top)
+};
+
+// The frame descriptor of sqeazy's LZ4 frames: the FLG and BD bytes and the header checksum byte (lz4frame.c, LZ4F_headerChecksum)
+struct Lz4Descriptor { unsigned char flg, bd; uint32_t hc; };
+Lz4Descriptor lz4_descriptor(int block_id)
+{
+    const unsigned char fd[2] = {0x40, (unsigned char)(block_id << 4)};
+    return {fd[0], fd[1], (sqy::xxh32(fd, 2, 0) >> 8) & 0xff};
+}
+
+// One encode call: where it runs, the stream between the stages, and what the stages hand each other.
+struct EncodeCall {
+    Context& cx;
+    Workspace* ws;
+    std::vector<PendingEvent>* pend;
+    hipStream_t stream;
+    Pipeline pipe;
+    std::vector<uint64_t> dims;
+    uint64_t len;                        // voxels
+    int elem_size;
+    void* d_dst;
+    uint64_t dst_capacity;
+    long* dstoffset;                     // nullptr: the blob starts at d_dst
+    FrameQuery* fq;
+
+    // the stream between stages
+    const uint8_t* cur;
+    int cur_elem;                        // bytes per element
+    uint64_t cur_len;                    // elements
+    bool use_ping = true;
+
+    // left for lz4 by the stages in front of it
+    struct {
+        const uint32_t* piece_hash = nullptr;   // 16-bit bitswap1: hashes of the 1 KiB pieces of the plane stream (duplicate-chunk search)
+        bool inplace = false;                   // frames in place: chunk k of the plane stream sits at d_dst + t0 + 11 + k * in_stride
+        uint64_t t0 = 0, in_stride = 0;
+        uint32_t* digest = nullptr;             // frames in place: the noise digest (sqy_kernels.h: launch_bitswap1_u16), digest_stride words per chunk
+        uint32_t digest_stride = 0;
+        bool dedupe_cleared = false;            // the duplicate search's table and the dense list's counter were zeroed in front of the transpose
+        const uint64_t* frame_map = nullptr;    // frame_shuffle directly in front: frames are read through the map
+        uint64_t frame_bytes = 0;
+    } prep;
+    // left for a 16-bit bitswap1 by diff3x3x1 directly in front of it: only the columns the stage can touch (compact side buffer)
+    struct DiffSide { const uint16_t* p = nullptr; uint32_t w = 0, X = 0; } side;
+    // left for finish() by lz4
+    struct {
+        bool on = false;                        // the payload is LZ4 frames
+        int block_id = 0;
+        uint64_t total = 0, chunk = 0, nchunks = 0, stride = 0;
+        const sqy::Lz4Block* blocks = nullptr;  // block-linked frames (nthreads == 1, or chunks of several LZ4 blocks): the block list in HBM
+        const uint32_t* dup_of = nullptr;       // chunks that are byte-identical to an earlier chunk share its frame
+        uint64_t* tail_info = nullptr;          // frames in place: the run of stored chunks that ends the payload
+        bool inplace_done = false;              // frames in place, finished on the device: where the blob is
+        uint64_t blob_at = 0, blob_bytes = 0, payload_bytes = 0;
+    } lz4;
+
+    EncodeCall(Context& c, hipStream_t s, Pipeline&& p, std::vector<uint64_t>&& d, uint64_t voxels, int elem, const void* src, void* dst,
+               uint64_t capacity, long* offset, FrameQuery* frames)
+        : cx(c), ws(&c.ws), pend(&c.pending), stream(s), pipe(std::move(p)), dims(std::move(d)), len(voxels), elem_size(elem), d_dst(dst),
+          dst_capacity(capacity), dstoffset(offset), fq(frames), cur(static_cast<const uint8_t*>(src)), cur_elem(elem), cur_len(voxels) {}
+
+    uint8_t* next_buf(size_t bytes)
+    {
+        DevBuf& b = use_ping ? ws->ping : ws->pong;
+        use_ping = !use_ping;
+        return b.ensure(bytes) ? nullptr : static_cast<uint8_t*>(b.p);
+    }
+    int produced(const uint8_t* out) { cur = out; return 0; }           // the stage's output is the next stage's input
+    bool is_tail(size_t si) const { return pipe.sink_index >= 0 && (int)si > pipe.sink_index; }
+    // the reference's 3-D schemes refuse other shapes (sqeazy::detail::<scheme>::encode)
+    bool not_3d(const char* scheme) const
+    {
+        if (dims.size() != 3) std::fprintf(stderr, "[sqeazy::detail::%s::encode] received non-3D shape which is currently unsupported!\n", scheme);
+        return dims.size() != 3;
+    }
+    bool followed_by(size_t si, StageKind k) const { return si + 1 < pipe.stages.size() && pipe.stages[si + 1].kind == k; }
+    // the shape a 3-D stage sees: the volume's -- or, behind a sink that did not write one byte per voxel, {1, 1, bytes}
+    // (dynamic_pipeline.hpp:658-666: the tail chain's "sinked_shape")
+    void stage_shape(size_t si, uint64_t& Z, uint64_t& Y, uint64_t& X) const
+    {
+        const bool flat = is_tail(si) && cur_len * (uint64_t)cur_elem != len;
+        Z = flat ? 1 : dims[0]; Y = flat ? 1 : dims[1]; X = flat ? cur_len : dims[2];
+    }
+
+    int bitswap1(size_t si)
+    {
+        // lz4 right behind: leave piece hashes for its duplicate-chunk detection (bit planes of small values repeat)
+        uint32_t* ph = nullptr;
+        uint64_t gap_chunk = 0;
+        if (cur_elem == 2 && followed_by(si, StageKind::lz4)) {
+            const sqy::Lz4Params& lz = pipe.stages[si + 1].lz4;
+            const uint64_t words = sqy::bitswap1_piece_hash_words(cur, cur, cur_len);         // (0 unless whole tiles, 16-byte aligned input)
+            const uint64_t total = cur_len * 2;
+            const uint64_t chunk = lz.bytes_per_chunk(total);
+            const bool chunked = chunk <= lz.block_bytes() && !(pipe.nthreads == 1 && total > chunk);
+            if (words && chunked && chunk % 1024 == 0 && total > chunk) {
+                const uint64_t nch = (total + chunk - 1) / chunk;
+                const uint64_t ph_bytes = (words * 4 + 63) & ~(uint64_t)63;
+                if (ws->dedupe.ensure(ph_bytes + sqy::lz4_dedupe_work_bytes(nch) + ((nch * 4 + 7) & ~(uint64_t)7) + sqy::lz4_holes_map_bytes(nch, (uint32_t)chunk))) return 1;
+                ph = static_cast<uint32_t*>(ws->dedupe.p);
+                prep.piece_hash = ph;
+                // frames in place: lz4 is the last stage, chunks a power of two, the caller takes the blob where it ends up,
+                // and the destination holds frame headers in front of and end marks behind every chunk
+                if (dstoffset && si + 2 == pipe.stages.size() && (chunk & (chunk - 1)) == 0) {
+                    // room in front for the sqy header (its length depends on the payload size: take the longest)
+                    const uint64_t hdr_max = sqy::header_pack(elem_size, false, dims, pipe.name(), (uint64_t)INT_MAX).size() + 2;
+                    uint64_t t0 = hdr_max;
+                    while ((reinterpret_cast<uintptr_t>(d_dst) + t0 + 11) & 15) ++t0;          // body of chunk 0 on a 16-byte boundary
+                    if (t0 + nch * (chunk + 15) <= dst_capacity) {
+                        gap_chunk = chunk;
+                        prep.t0 = t0;
+                        prep.in_stride = chunk + 15;
+                        prep.inplace = true;
+                        // (one small kernel in front of the transpose instead of three fill dispatches between the kernels behind it)
+                        if (ws->plan.ensure((nch + 1) * sizeof(uint32_t))) return 1;
+                        SQY_HIP(sqy::launch_lz4_dedupe_clear(static_cast<uint8_t*>(ws->dedupe.p) + ph_bytes, nch, static_cast<uint32_t*>(ws->plan.p), stream));
+                        prep.dedupe_cleared = true;
+                        // the noise digest (round 6): every plane segment a whole number of chunks, liblz4's plain search behind it
+                        const uint32_t dstride = sqy::lz4_noise_digest_stride((uint32_t)chunk);
+                        if (g_opt.noise_digest.load() && dstride && (cur_len / 8) % chunk == 0 && lz.accel >= 0 &&
+                            !ws->digest.ensure(nch * (uint64_t)dstride * sizeof(uint32_t), true)) {
+                            prep.digest = static_cast<uint32_t*>(ws->digest.p);
+                            prep.digest_stride = dstride;
+                        }
+                    }
+                }
+            }
+        }
+        uint8_t* out = gap_chunk ? static_cast<uint8_t*>(d_dst) + prep.t0 + 11 : next_buf(cur_len * cur_elem);
+        if (!out) return 1;
+        if (!gap_chunk && ph && (reinterpret_cast<uintptr_t>(out) & 15)) { ph = nullptr; prep.piece_hash = nullptr; }
+        // The bit-plane transposes of the calls in flight on one device run one after the other (round 4): a stream waits for the
+        // transpose of the call in front before it starts its own.  Two HBM-bound kernels side by side each run at half speed
+        // and end together; chained, the first call's parse starts a whole transpose earlier (bench, four calls in flight:
+        // +3 %; also chaining the duplicate search behind it: -12 %, measured and not kept).  Only a transpose launched within
+        // the last few milliseconds is waited for.  The chain is an edge between streams: by default only streams this library
+        // owns (the host-pointer entry points, the Slabs workers) are chained -- a stream the CALLER brings may carry work this
+        // library knows nothing about (a backlog, a host function that waits for another of the caller's threads), and a hidden
+        // wait on it would couple calls that are documented as independent (round-4 advice).  A caller whose streams carry
+        // nothing but these calls opts in: SQYAMD_Set_Option("transpose_chain_caller_streams", 1) (bench.py does, and says so).
+        // "transpose_chain" = 0 (or SQY_NO_TRANSPOSE_CHAIN=1 when the library is loaded) switches the chain off altogether.
+        const bool owned = stream != nullptr && stream == cx.stream;
+        int devid = 0;
+        const bool chain = g_opt.transpose_chain.load() && (owned || g_opt.transpose_chain_caller_streams.load()) && gap_chunk &&
+                           hipGetDevice(&devid) == hipSuccess && devid >= 0 && devid < kMaxDev;
+        std::unique_lock<std::mutex> tlock;
+        if (chain) {
+            if (!cx.t_done && hipEventCreateWithFlags(&cx.t_done, hipEventDisableTiming) != hipSuccess) return 1;
+            tlock = std::unique_lock<std::mutex>(g_tchain_mu[devid]);
+            const auto now = std::chrono::steady_clock::now();
+            if (g_tchain_last[devid] && g_tchain_last[devid] != cx.t_done && now - g_tchain_when[devid] < std::chrono::milliseconds(5))
+                SQY_HIP(hipStreamWaitEvent(stream, g_tchain_last[devid], 0));
+            g_tchain_when[devid] = now;
+        }
+        if (cur_elem == 2)
+            SQY_TIMED("bitswap1_u16", sqy::launch_bitswap1_u16(reinterpret_cast<const uint16_t*>(cur), reinterpret_cast<uint16_t*>(out), cur_len, stream, ph,
+                                                               (uint32_t)gap_chunk, side.p, side.w, side.X, gap_chunk ? prep.digest : nullptr, prep.digest_stride));
+        else
+            SQY_TIMED("bitswap1_u8", sqy::launch_bitswap1_u8(cur, out, cur_len, stream));
+        if (chain) {
+            SQY_HIP(hipEventRecord(cx.t_done, stream));
+            g_tchain_last[devid] = cx.t_done;
+            tlock.unlock();
+        }
+        side = DiffSide();                      // (consumed: a later bitswap1 of the pipeline reads its plain input)
+        return produced(out);
+    }
+
+    // raster_reorder and zcurve_reorder: inside a tile the reference's morton_at_ct<log2(tile)> code is row-major, so the tiled raster kernel
+    // is both stages.  (round 5) As a tail filter the stream is the sink's `char` output (sqeazy_pipelines.hpp:64-77 lists the stages for the
+    // tail chain): stage_shape.
+    int reorder(size_t si, bool zcurve)
+    {
+        const char* name = zcurve ? "zcurve_reorder" : "raster_reorder";
+        if (not_3d(zcurve ? "zcurve" : "reorder")) return 1;
+        const Stage& st = pipe.stages[si];
+        auto t = st.cfg.find("tile_size");                 // (raster_reorder: always there, from_string fills in the default)
+        const uint64_t ts = t != st.cfg.end() ? (uint64_t)std::atoi(t->second.c_str()) : (zcurve ? 2 : 0);
+        uint64_t Z, Y, X;
+        stage_shape(si, Z, Y, X);
+        if (zcurve ? !sqy::zcurve_geometry_defined(Z, Y, X, ts) : !sqy::raster_geometry_defined(Z, Y, X, ts, cur_elem)) {
+            std::fprintf(stderr, "[sqeazy]\t %s: the reference's result is undefined for shape %llux%llux%llu at tile_size=%llu (%s); refused\n", name,
+                         (unsigned long long)Z, (unsigned long long)Y, (unsigned long long)X, (unsigned long long)ts,
+                         zcurve ? "tile sizes other than 2..128 powers of two, or a tile that does not divide a power-of-two shape"
+                                : "remainder in some dimensions only, or a tile wider than one 16-byte block");
+            return 1;
+        }
+        uint8_t* out = next_buf(cur_len * cur_elem);
+        if (!out) return 1;
+        SQY_TIMED(name, sqy::launch_raster_reorder(cur, out, Z, Y, X, ts, cur_elem, false, stream));
+        return produced(out);
+    }
+
+    // remove_estimated_background_scheme::encode (remove_estimated_background_scheme_impl.hpp:71-110); shape checked by background_geometry_ok
+    int rmestbkrd()
+    {
+        const uint64_t portion = sqy::rmestbkrd_face_portion(dims[1] * dims[2], (uint32_t)g_opt.host_l2_bytes.load());
+        if (ws->bkrd.ensure(sqy::rmestbkrd_work_bytes(cur_elem))) return 1;
+        uint8_t* out = next_buf(cur_len * cur_elem);
+        if (!out) return 1;
+        SQY_TIMED("rmestbkrd", sqy::launch_rmestbkrd(cur, out, dims[0], dims[1], dims[2], portion, cur_elem, ws->bkrd.p, stream));
+        return produced(out);
+    }
+
+    // flatten_to_neighborhood_scheme::encode (flatten_to_neighborhood_scheme_impl.hpp:90-150): the threshold in the voxel type,
+    // cut_fraction = fraction * (size<Neighborhood>() - 1) in float; shape checked by background_geometry_ok
+    int rmbkrd_neighbor5(size_t si)
+    {
+        const Stage& st = pipe.stages[si];
+        const float cut = st.nb_fraction * (float)(125u - 1u);
+        uint8_t* out = next_buf(cur_len * cur_elem);
+        if (!out) return 1;
+        SQY_TIMED("rmbkrd_neighbor5x5x5", sqy::launch_rmbkrd_neighbor5(cur, out, dims[0], dims[1], dims[2], (uint32_t)st.nb_threshold, cut,
+                                                                       sqy::neighbor5_z_end(dims[0], dims[2]), cur_elem, stream));
+        return produced(out);
+    }
+
+    // pass_through_scheme_impl.hpp:66-79: the sink that only re-types the stream to bytes
+    int pass_through() { cur_len *= (uint64_t)cur_elem; cur_elem = 1; return 0; }
+
+    int bitshuffle(size_t si)
+    {
+        const Stage& st = pipe.stages[si];
+        auto b = st.cfg.find("block_size");
+        const uint64_t be = sqy::bitshuffle_block_elems(cur_elem, b != st.cfg.end() ? (uint64_t)std::atoi(b->second.c_str()) : 0);
+        if (!be) { std::fprintf(stderr, "[sqeazy]\t bitshuffle: block_size must be a multiple of 8\n"); return 1; }
+        uint8_t* out = next_buf(cur_len * cur_elem);
+        if (!out) return 1;
+        SQY_TIMED("bitshuffle", sqy::launch_bitshuffle(cur, out, cur_len, cur_elem, be, false, stream));
+        return produced(out);
+    }
+
+    // frame_shuffle and tile_shuffle: the sequential binary32 sums of `units` runs of `per_unit` elements of `in`, read back, ordered on the
+    // host (order(sums, map)), and the map sent to *d_map (behind the sums in ws->small).  `map` is read by that async copy: the caller keeps
+    // it until the stream has been synchronised.
+    template <class Order>
+    int shuffle_map(const uint8_t* in, uint64_t units, uint64_t per_unit, bool tail, const char* prof, Order order,
+                                std::vector<uint64_t>& map, uint64_t** d_map)
+    {
+        if (ws->small.ensure(std::max<uint64_t>(units * 16, 4096))) return 1;
+        float* d_sums = static_cast<float*>(ws->small.p);
+        *d_map = reinterpret_cast<uint64_t*>(static_cast<uint8_t*>(ws->small.p) + ((units * 4 + 15) & ~(uint64_t)15));
+        const uint64_t fm_bytes = sqy::frame_metric_scratch_bytes(units, per_unit, cur_elem);
+        if (ws->lz4_scratch.ensure(std::max<uint64_t>(fm_bytes, 16))) return 1;      // free until the sink runs
+        SQY_TIMED(prof, sqy::launch_frame_metric(in, units, per_unit, cur_elem, d_sums, stream, ws->lz4_scratch.p, fm_bytes, tail));
+        std::vector<float> sums(units);
+        map.assign(units, 0);
+        SQY_HIP(hipMemcpyAsync(sums.data(), d_sums, units * sizeof(float), hipMemcpyDeviceToHost, stream));
+        SQY_HIP(hipStreamSynchronize(stream));
+        order(sums.data(), map.data());
+        SQY_HIP(hipMemcpyAsync(*d_map, map.data(), units * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+        return 0;
+    }
+
+    int tile_shuffle(size_t si)
+    {
+        if (not_3d("tile_shuffle")) return 1;
+        Stage& st = pipe.stages[si];
+        auto t = st.cfg.find("tile_size");
+        const uint64_t ts = t != st.cfg.end() ? (uint64_t)std::atoi(t->second.c_str()) : 32;
+        // (tail filter: tile_shuffle_scheme<char> on the sink's stream -- the tile sums add SIGNED bytes and the metric is a char)
+        const bool tail = is_tail(si);
+        uint64_t Z, Y, X;
+        stage_shape(si, Z, Y, X);
+        if (!sqy::tile_shuffle_geometry_defined(Z, Y, X, ts)) {
+            std::fprintf(stderr, "[sqeazy]\t tile_shuffle: shape %llux%llux%llu is not a whole multiple of tile_size=%llu; the reference's remainder "
+                                 "path (P^2 median over tiles read past their end, thread-timing dependent map) is not reproduced; refused\n",
+                         (unsigned long long)Z, (unsigned long long)Y, (unsigned long long)X, (unsigned long long)ts);
+            return 1;
+        }
+        const uint64_t per_tile = ts * ts * ts, ntiles = cur_len / per_tile, tile_bytes = per_tile * (uint64_t)cur_elem;
+        // 1. tiles made contiguous (tile-major copy), 2. their sequential binary32 sums, 3. order on the host, 4. tiles appended in that order
+        uint8_t* tiled = next_buf(cur_len * cur_elem);
+        if (!tiled) return 1;
+        SQY_TIMED("tile_gather", sqy::launch_raster_reorder(cur, tiled, Z, Y, X, ts, cur_elem, false, stream));
+        std::vector<uint64_t> map;
+        uint64_t* d_map = nullptr;
+        auto order = [&](const float* sums, uint64_t* m) { sqy::tile_shuffle_order(sums, ntiles, per_tile, cur_elem, m, tail); };
+        if (shuffle_map(tiled, ntiles, per_tile, tail, "tile_metric", order, map, &d_map)) return 1;
+        uint8_t* out = next_buf(cur_len * cur_elem);
+        if (!out) return 1;
+        SQY_TIMED("tile_shuffle", sqy::launch_frame_gather(tiled, out, ntiles, tile_bytes, d_map, stream));
+        SQY_HIP(hipStreamSynchronize(stream));                     // `map` (host) is read by the async copy of shuffle_map
+        st.cfg["reorder_map"] = sqy::to_verbatim(map.data(), ntiles * sizeof(uint64_t));   // tile_shuffle_scheme_impl.hpp:88
+        return produced(out);
+    }
+
+    int diff3x3x1(size_t si)
+    {
+        if (dims.size() != 3) {
+            // diff_scheme_impl.hpp:84-87 returns the output pointer unmoved -> the chain throws
+            // (dynamic_stage_chain.hpp:313-317); no exception may cross this ABI
+            std::fprintf(stderr, "[diff_scheme] unable to process input data that is not 3D\n");
+            return 1;
+        }
+        // as a tail filter the stream is the sink's `char` output, {1, 1, bytes} unless that is one byte per voxel: which the stage cannot take
+        const bool tail = is_tail(si);
+        uint64_t Z, Y, X;
+        stage_shape(si, Z, Y, X);
+        if ((int64_t)(X - 1) * (int64_t)(Y - 2) <= 1 || Y < 3 || X < 2) {
+            std::fprintf(stderr, "[sqeazy]\t diff3x3x1: shape %llux%llux%llu reads out of bounds in the reference; refused\n",
+                         (unsigned long long)Z, (unsigned long long)Y, (unsigned long long)X);
+            return 1;
+        }
+        if (cur_elem == 1 && (Z > 127 || Y > 127 || X > 127)) {
+            std::fprintf(stderr, "[sqeazy]\t diff3x3x1 on 8-bit voxels: extents > 127 overflow the reference's char coordinates; refused\n");
+            return 1;
+        }
+        const uint32_t sw = (!tail && followed_by(si, StageKind::bitswap1) && (reinterpret_cast<uintptr_t>(cur) & 15) == 0)
+                                ? sqy::diff3x3x1_side_width(Z, Y, X, cur_elem) : 0;
+        if (sw) {
+            // a buffer of its own: `cur` stays where it is, so the transpose's output (the next buffer of the
+            // ping/pong rotation) can never be the buffer `cur` lives in
+            if (ws->diff_side.ensure(Z * Y * (uint64_t)sw * 2)) return 1;
+            uint8_t* sbuf = static_cast<uint8_t*>(ws->diff_side.p);
+            SQY_TIMED("diff3x3x1", sqy::launch_diff3x3x1_side(reinterpret_cast<const uint16_t*>(cur), reinterpret_cast<uint16_t*>(sbuf), Z, Y, X, sw, stream));
+            side.p = reinterpret_cast<const uint16_t*>(sbuf);
+            side.w = sw;
+            side.X = (uint32_t)X;
+            return 0;                                                   // (`cur` stays the stage's input: the transpose reads both)
+        }
+        uint8_t* out = next_buf(cur_len * cur_elem);
+        if (!out) return 1;
+        SQY_TIMED("diff3x3x1", sqy::launch_diff3x3x1(cur, out, Z, Y, X, cur_elem, stream, tail));
+        return produced(out);
+    }
+
+    int frame_shuffle(size_t si)
+    {
+        if (not_3d("frame_shuffle")) return 1;
+        Stage& st = pipe.stages[si];
+        // (tail filter: signed bytes; ONE frame {1, 1, bytes} when the sink did not write one byte per voxel)
+        const bool tail = is_tail(si);
+        // frame_chunk_size = N: N consecutive frames are one sort unit (frame_shuffle_utils.hpp:105-133, encode_full) -- the stage
+        // on Z / N "frames" of N * Y * X voxels.  Z % N != 0 takes the reference's encode_with_remainder (Boost's P^2 median
+        // estimate as the metric, :193-260): not reproduced
+        const uint64_t fcs = frame_chunk_size(st);
+        uint64_t Z0, Y, X;
+        stage_shape(si, Z0, Y, X);
+        if (fcs == 0 || Z0 % fcs != 0) {
+            std::fprintf(stderr, "[sqeazy]\t frame_shuffle: %llu frames are no whole multiple of frame_chunk_size=%llu; the reference's remainder path "
+                                 "(a P^2 median estimate as the metric) is not reproduced; refused\n", (unsigned long long)Z0, (unsigned long long)fcs);
+            return 1;
+        }
+        const uint64_t Z = Z0 / fcs, per_frame = Y * X * fcs;
+        std::vector<uint64_t> map;
+        uint64_t* d_map = nullptr;
+        auto order = [&](const float* sums, uint64_t* m) { sqy::frame_shuffle_order(sums, Z, per_frame, m); };
+        if (shuffle_map(cur, Z, per_frame, tail, "frame_metric", order, map, &d_map)) return 1;
+        // when lz4 follows immediately and its chunks tile the frames, the permuted copy is never materialised:
+        // the LZ4 kernels read frame map[f] where the stream has frame f
+        const uint64_t frame_bytes = per_frame * (uint64_t)cur_elem;
+        bool fused = false;
+        if (followed_by(si, StageKind::lz4) && frame_bytes) {
+            const sqy::Lz4Params& lz = pipe.stages[si + 1].lz4;
+            const uint64_t total = cur_len * (uint64_t)cur_elem;
+            const uint64_t chunk = lz.bytes_per_chunk(total);
+            fused = chunk && frame_bytes % chunk == 0 && chunk <= lz.block_bytes() &&
+                    !(pipe.nthreads == 1 && total > chunk);               // (block-linked frames read a gathered copy)
+        }
+        if (fused) {
+            prep.frame_map = d_map;
+            prep.frame_bytes = frame_bytes;
+        } else {
+            uint8_t* out = next_buf(cur_len * cur_elem);
+            if (!out) return 1;
+            SQY_TIMED("frame_gather", sqy::launch_frame_gather(cur, out, Z, frame_bytes, d_map, stream));
+            cur = out;
+        }
+        SQY_HIP(hipStreamSynchronize(stream));                     // `map` (host) is read by the async copy of shuffle_map
+        st.cfg["frame_chunk_size"] = std::to_string(fcs);
+        st.cfg["reorder_map"] = sqy::to_verbatim(map.data(), Z * sizeof(uint64_t));   // frame_shuffle_scheme_impl.hpp:86-90
+        return 0;
+    }
+
+    // quantiser_scheme<uint16_t,char>::encode (quantiser_scheme_impl.hpp:176-226); with a bitswap1 right behind it that stage as well
+    int quantiser(size_t& si)
+    {
+        Stage& st = pipe.stages[si];
+        if (ws->small.ensure(65536 * sizeof(uint32_t) + 65536)) return 1;
+        uint32_t* d_histo = static_cast<uint32_t*>(ws->small.p);
+        uint8_t* d_lut = static_cast<uint8_t*>(ws->small.p) + 65536 * sizeof(uint32_t);
+        SQY_TIMED("histogram_u16", sqy::launch_histogram_u16(reinterpret_cast<const uint16_t*>(cur), cur_len, d_histo, stream));
+        std::vector<uint32_t> histo(65536);
+        std::vector<unsigned char> lut_encode(65536);
+        uint16_t lut_decode[256];
+        SQY_HIP(hipMemcpyAsync(histo.data(), d_histo, 65536 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        SQY_HIP(hipStreamSynchronize(stream));
+        sqy::QuantiserWeighting qw;
+        {
+            auto wf = st.cfg.find("weighting_function");
+            if (wf != st.cfg.end() && !sqy::quantiser_parse_weighting(wf->second, &qw)) return 1;    // (refused by supported() already)
+        }
+        sqy::quantiser_build_luts(histo.data(), 65536, lut_encode.data(), lut_decode, qw);
+        SQY_HIP(hipMemcpyAsync(d_lut, lut_encode.data(), 65536, hipMemcpyHostToDevice, stream));
+        uint8_t* out = next_buf(cur_len);
+        if (!out) return 1;
+        // (round 5) bitswap1 right behind the sink: look-up and 8-bit bit-plane transpose in one pass
+        if (followed_by(si, StageKind::bitswap1) && (reinterpret_cast<uintptr_t>(cur) & 15) == 0) {
+            SQY_TIMED("quantiser_bitswap1_u8", sqy::launch_quantiser_apply_bitswap1_u8(reinterpret_cast<const uint16_t*>(cur), out, cur_len, d_lut, stream));
+            si += 1;                                                   // the bitswap1 stage is done as well
+        } else {
+            SQY_TIMED("quantiser_apply", sqy::launch_quantiser_apply_u16(reinterpret_cast<const uint16_t*>(cur), out, cur_len, d_lut, stream));
+        }
+        SQY_HIP(hipStreamSynchronize(stream));                     // lut_encode (host) is read by the async copy above
+        // quantiser_scheme_impl.hpp:200-204: the decode LUT goes to the file the caller named, else into the header
+        auto lp = st.cfg.find("decode_lut_path");
+        if (lp != st.cfg.end()) {
+            if (!sqy::quantiser_lut_to_file(lp->second, lut_decode, 256)) {
+                // (the reference does not notice and returns a blob nobody can decode; here the encode fails)
+                std::fprintf(stderr, "[sqeazy]\t quantiser: unable to write the decode LUT to %s\n", lp->second.c_str());
+                return 1;
+            }
+        } else
+            st.cfg["decode_lut_string"] = sqy::to_verbatim(lut_decode, sizeof(lut_decode));
+        cur = out;
+        cur_elem = 1;                                              // sink output is `char`
+        return 0;
+    }
+
+    int lz4_stage(size_t si)
+    {
+        const sqy::Lz4Params& lz = pipe.stages[si].lz4;
+        // liblz4's acceleration: LZ4F turns a negative compression level -k into acceleration k + 1 (lz4frame.c, LZ4F_compressBlock),
+        // LZ4_compress_fast_continue caps it at 65537 (lz4.c, LZ4_ACCELERATION_MAX)
+        const uint32_t accel = lz.accel < 0 ? (uint32_t)std::min<int64_t>(1 - (int64_t)lz.accel, 65537) : 1u;
+        lz4.block_id = lz.block_id;
+        lz4.total = cur_len * (uint64_t)cur_elem;
+        lz4.chunk = lz4.total ? lz.bytes_per_chunk(lz4.total) : 1;
+        lz4.nchunks = lz4.total ? (lz4.total + lz4.chunk - 1) / lz4.chunk : 0;
+        const bool serial = pipe.nthreads == 1 && lz4.nchunks > 1;          // lz4.hpp:227-234: one block-linked frame
+        if (!serial && lz4.chunk <= lz.block_bytes()) {
+            if (lz4_chunked(si, accel)) return 1;
+            if (lz4.inplace_done) return 0;
+        } else if (lz4.total) {
+            if (lz4_linked(si, serial, accel)) return 1;
+        }
+        SQY_TIMED("lz4_frame_scan", sqy::launch_lz4_frame_scan(static_cast<uint32_t*>(ws->csize.p), lz4.nchunks, lz4.total, (uint32_t)lz4.chunk,
+                                                               static_cast<uint64_t*>(ws->frame_off.p), stream, lz4.blocks, lz4.dup_of, lz4.tail_info));
+        lz4.on = true;
+        return 0;
+    }
+
+    // chunked layout, one LZ4 block per frame: every chunk is independent.  The duplicate search, the parse and the dense pass behind it --
+    // or, frames in place with a header short enough, everything up to the finished blob (lz4_inplace_finish)
+    int lz4_chunked(size_t si, uint32_t accel)
+    {
+        lz4.stride = (lz4.chunk + 15) & ~(uint64_t)15;
+        if (ws->lz4_scratch.ensure(std::max<uint64_t>(lz4.nchunks * lz4.stride, 16))) return 1;
+        if (ws->csize.ensure(std::max<uint64_t>(lz4.nchunks, 1) * sizeof(uint32_t))) return 1;
+        if (ws->frame_off.ensure((lz4.nchunks + 1 + 4) * sizeof(uint64_t))) return 1;
+        if (prep.inplace) lz4.tail_info = static_cast<uint64_t*>(ws->frame_off.p) + lz4.nchunks + 1;
+        sqy::Lz4DedupeArgs dedupe_args;              // frames in place: the duplicate decision per chunk is made inside the parse kernel
+        bool fused_dedupe = false;
+        if (prep.piece_hash && si > 0 && pipe.stages[si - 1].kind == StageKind::bitswap1) {
+            const uint64_t words = sqy::bitswap1_piece_hash_words(cur, cur, cur_len);     // (same count as when they were made)
+            const uint64_t ph_bytes = (words * 4 + 63) & ~(uint64_t)63;
+            uint8_t* base = static_cast<uint8_t*>(ws->dedupe.p) + ph_bytes;
+            uint32_t* d_dup = reinterpret_cast<uint32_t*>(base + sqy::lz4_dedupe_work_bytes(lz4.nchunks));
+            // frames in place: which 1 KiB pieces of the plane stream the transpose left unwritten (all zero)
+            uint64_t* holes = prep.inplace ? reinterpret_cast<uint64_t*>(reinterpret_cast<uint8_t*>(d_dup) + ((lz4.nchunks * 4 + 7) & ~(uint64_t)7)) : nullptr;
+            ProfScope ps("lz4_dedupe", stream, pend);
+            // frames in place (acceleration 1): only the key table is built here, the decision per chunk (byte compare, hole fill)
+            // is the first thing the chunk's parse wavefront does (lz4_chunk_dedupe)
+            fused_dedupe = prep.inplace && accel == 1;
+            SQY_HIP(sqy::launch_lz4_dedupe(cur, lz4.total, (uint32_t)lz4.chunk, prep.piece_hash, base, d_dup, stream, prep.in_stride, holes,
+                                           prep.dedupe_cleared, fused_dedupe ? &dedupe_args : nullptr));
+            lz4.dup_of = d_dup;
+            if (fused_dedupe && prep.digest) { dedupe_args.digest = prep.digest; dedupe_args.digest_stride = prep.digest_stride; }
+        }
+        if (ws->plan.ensure((lz4.nchunks + 1) * sizeof(uint32_t))) return 1;
+        uint32_t* d_redo = static_cast<uint32_t*>(ws->plan.p);       // chunks the first pass leaves to the dense batches
+        SQY_TIMED("lz4_chunks", sqy::launch_lz4_chunks(cur, lz4.total, (uint32_t)lz4.chunk, static_cast<uint8_t*>(ws->lz4_scratch.p), lz4.stride,
+                                                       static_cast<uint32_t*>(ws->csize.p), lz4.nchunks, stream, prep.frame_map, prep.frame_bytes, d_redo,
+                                                       fused_dedupe ? nullptr : lz4.dup_of, prep.in_stride, accel, prep.dedupe_cleared,
+                                                       fused_dedupe ? &dedupe_args : nullptr));
+        std::string hdr_prefix, hdr_suffix;
+        if (prep.inplace && !(fq && fq->every > 0)) sqy::header_pack_parts(elem_size, false, dims, pipe.name(), &hdr_prefix, &hdr_suffix);
+        if (prep.inplace && !hdr_prefix.empty() && hdr_prefix.size() + hdr_suffix.size() <= sqy::kLz4InplaceHeaderTextMax)
+            return lz4_inplace_finish(d_redo, hdr_prefix, hdr_suffix);
+        SQY_HIP(hipMemcpyAsync(ws->pinned, d_redo, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        SQY_HIP(hipStreamSynchronize(stream));
+        const uint32_t n_redo = *static_cast<uint32_t*>(ws->pinned);
+        return n_redo ? lz4_dense(d_redo, n_redo) : 0;
+    }
+
+    // the chunks the first pass left to the dense batches (d_redo[0] of them)
+    int lz4_dense(uint32_t* d_redo, uint32_t n_redo)
+    {
+        SQY_TIMED("lz4_chunks_dense", sqy::launch_lz4_chunks_dense(cur, lz4.total, (uint32_t)lz4.chunk, static_cast<uint8_t*>(ws->lz4_scratch.p), lz4.stride,
+                                                                   static_cast<uint32_t*>(ws->csize.p), d_redo, n_redo, stream, prep.frame_map, prep.frame_bytes,
+                                                                   prep.in_stride));
+        return 0;
+    }
+
+    // Frames in place, ONE host round trip per call (round 4): frame scan + tail marks, the stored chunks in front of the tail put aside,
+    // the gather and the sqy header are all queued behind the parse right away and take what they need (where the stored tail begins,
+    // the payload size) from device memory; what the host has to know comes back through pinned memory with the one synchronisation.
+    // Only when the parse left chunks to the dense pass (streams of short sequences: seldom on microscopy stacks) do these kernels return
+    // untouched -- they look at the list's counter -- and run again behind the dense pass (status 2).
+    int lz4_inplace_finish(uint32_t* d_redo, const std::string& hdr_prefix, const std::string& hdr_suffix)
+    {
+        const Lz4Descriptor fd = lz4_descriptor(lz4.block_id);
+        uint8_t* outb = static_cast<uint8_t*>(d_dst);
+        volatile uint64_t* record = static_cast<volatile uint64_t*>(ws->pinned);
+        // (round 6) scan, tail marks, gather and header are ONE kernel (lz4_inplace_tail_fused_kernel: no workgroup waits for
+        // another; with calls in flight the five launches it replaces were 0.3 ms of a call's 2.4).  Only when stored chunks
+        // sit in front of the stored tail -- their bodies lie where gathered frames go -- does it hand back (status 4) to the
+        // separate kernels, which put those chunks aside first.
+        const bool fused_tail = lz4.nchunks <= 65536;         // (a workgroup of the fused kernel owns at most 64 chunks)
+        // fused: the one kernel; else the frame scan (scan_too) and the separate kernel
+        auto tail = [&](const uint32_t* guard, bool fused, bool scan_too) -> int {
+            record[0] = 0;
+            if (!fused && scan_too)
+                SQY_TIMED("lz4_frame_scan", sqy::launch_lz4_frame_scan(static_cast<uint32_t*>(ws->csize.p), lz4.nchunks, lz4.total, (uint32_t)lz4.chunk,
+                                                                       static_cast<uint64_t*>(ws->frame_off.p), stream, nullptr, lz4.dup_of, lz4.tail_info, guard,
+                                                                       outb + prep.t0 + 11, prep.in_stride, fd.bd, fd.hc));
+            auto with_args = [&](auto launch) {
+                return launch(outb, prep.t0, prep.in_stride, lz4.total, (uint32_t)lz4.chunk, lz4.nchunks, static_cast<uint8_t*>(ws->lz4_scratch.p), lz4.stride,
+                              static_cast<uint32_t*>(ws->csize.p), static_cast<uint64_t*>(ws->frame_off.p), lz4.dup_of, lz4.tail_info, fd.bd, fd.hc,
+                              hdr_prefix.data(), (uint32_t)hdr_prefix.size(), hdr_suffix.data(), (uint32_t)hdr_suffix.size(), (uint32_t)elem_size, guard,
+                              const_cast<uint64_t*>(record), stream);
+            };
+            SQY_TIMED(fused ? "lz4_inplace_tail" : "lz4_frame_gather",
+                      fused ? with_args(sqy::launch_lz4_inplace_tail_fused) : with_args(sqy::launch_lz4_inplace_tail));
+            return 0;
+        };
+        if (tail(d_redo, fused_tail, true)) return 1;
+        SQY_HIP(hipStreamSynchronize(stream));
+        if (record[0] == 2) {                                  // chunks left to the dense pass: it runs, then the tail again
+            if (lz4_dense(d_redo, (uint32_t)record[6])) return 1;
+            if (tail(nullptr, fused_tail, true)) return 1;
+            SQY_HIP(hipStreamSynchronize(stream));
+        }
+        if (record[0] == 4) {                                  // stored chunks in front of the stored tail: put aside first
+            if (tail(nullptr, false, false)) return 1;
+            SQY_HIP(hipStreamSynchronize(stream));
+        }
+        if (record[0] != 1) {
+            std::fprintf(stderr, "[sqeazy]\t internal error: frames in place did not finish (status %llu)\n", (unsigned long long)record[0]);
+            return 1;
+        }
+        lz4.inplace_done = true;
+        lz4.blob_at = record[1]; lz4.blob_bytes = record[2]; lz4.payload_bytes = record[3];
+        lz4.on = true;
+        return 0;
+    }
+
+    // block-linked frames: the serial layout (nthreads == 1) or chunks that span several LZ4 blocks.  The table of a frame is carried
+    // from block to block (lz4_utils.hpp:99-173): one wavefront walks each frame -- or every block is parsed at once from a guess of that
+    // table that is checked afterwards (lz4_linked_spec)
+    int lz4_linked(size_t si, bool serial, uint32_t accel)
+    {
+        const sqy::Lz4Plan plan = sqy::lz4_plan_blocks(lz4.total, lz4.chunk, pipe.stages[si].lz4.block_bytes(), serial);
+        if (!plan.ok || plan.blocks.empty()) {
+            std::fprintf(stderr, "[sqeazy]\t lz4: block layout not available on MI355X\n");
+            return 1;
+        }
+        const uint64_t nblocks = plan.blocks.size(), nframes = plan.frame_first.size() - 1;
+        const uint64_t blocks_bytes = nblocks * sizeof(sqy::Lz4Block), first_bytes = (nframes + 1) * sizeof(uint32_t);
+        static_assert(sizeof(sqy::Lz4Block) == sizeof(sqy::Lz4BlockPlan) && sizeof(sqy::Lz4Block) == 32, "plan entries are read by the kernels as they are");
+        if (ws->plan.ensure(blocks_bytes + first_bytes)) return 1;
+        sqy::Lz4Block* d_blocks = static_cast<sqy::Lz4Block*>(ws->plan.p);
+        uint32_t* d_first = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(ws->plan.p) + blocks_bytes);
+        SQY_HIP(hipMemcpyAsync(d_blocks, plan.blocks.data(), blocks_bytes, hipMemcpyHostToDevice, stream));
+        SQY_HIP(hipMemcpyAsync(d_first, plan.frame_first.data(), first_bytes, hipMemcpyHostToDevice, stream));
+        lz4.stride = ((uint64_t)plan.max_block + 15) & ~(uint64_t)15;
+        if (ws->lz4_scratch.ensure(std::max<uint64_t>(nblocks * lz4.stride, 16))) return 1;
+        if (ws->csize.ensure(nblocks * sizeof(uint32_t))) return 1;
+        if (ws->frame_off.ensure((nblocks + 1) * sizeof(uint64_t))) return 1;
+        // Few long frames (the serial layout above all): block-parallel.  Every block is parsed by its own wavefront from
+        // a table rebuilt by parsing the >= 64 KiB in front of it, the tables are checked against what the block in
+        // front really left, and what fails the check is parsed again in order (sqy_kernels.h: Lz4SpecArgs).  Twice the
+        // parse work on thousands of wavefronts instead of one: worth it when the frame walks would leave the chip empty.
+        uint64_t longest = 0;
+        for (uint64_t f = 0; f < nframes; ++f) longest = std::max<uint64_t>(longest, plan.frame_first[f + 1] - plan.frame_first[f]);
+        // measurement / test knob: SQY_NO_BLOCK_PARALLEL (the frame walk of rounds 2-3)
+        // (without room for the tables -- 32 KiB per block -- the walk, which needs none)
+        const bool spec_wanted = g_opt.block_parallel.load() != 0 && longest >= 3 && nframes < 1024;
+        const bool spec_room = spec_wanted && !ws->spec.ensure(nblocks * sqy::kLz4SpecTableWords * sizeof(uint32_t) + 3 * nblocks * sizeof(uint32_t), true);
+        if (spec_wanted && !spec_room) {
+            // (round-4 advice) said once, not per call: the result is the same, the rate is not
+            static std::atomic<bool> told{false};
+            if (!told.exchange(true))
+                std::fprintf(stderr, "[sqeazy]\t lz4: no HBM for the block-parallel parse's tables (%llu MiB): block-linked frames are walked by one "
+                                     "wavefront each (same bytes, hundreds of times slower on long frames)\n",
+                             (unsigned long long)((nblocks * sqy::kLz4SpecTableWords * sizeof(uint32_t)) >> 20));
+        }
+        if (spec_room) {
+            if (lz4_linked_spec(plan, d_blocks, accel)) return 1;
+        } else {
+            SQY_TIMED("lz4_linked", sqy::launch_lz4_linked(cur, d_blocks, d_first, nframes, plan.max_block, static_cast<uint8_t*>(ws->lz4_scratch.p),
+                                                           lz4.stride, static_cast<uint32_t*>(ws->csize.p), stream, accel));
+        }
+        SQY_HIP(hipStreamSynchronize(stream));                 // `plan` (host) is read by the async copies above
+        lz4.blocks = d_blocks;
+        lz4.nchunks = nblocks;                                  // scan and gather work per block from here on
+        lz4.chunk = plan.max_block;
+        return 0;
+    }
+
+    // The block-parallel parse of block-linked frames: every block from a guessed table, then verify / redo rounds until every block
+    // started from the table the block in front really left.  Returns with the stream synchronised.
+    int lz4_linked_spec(const sqy::Lz4Plan& plan, const sqy::Lz4Block* d_blocks, uint32_t accel)
+    {
+        const uint64_t nblocks = plan.blocks.size(), nframes = plan.frame_first.size() - 1;
+        const uint64_t list_bytes = nblocks * sizeof(uint32_t);
+        // SQY_BLOCK_PARALLEL_WARMUP = bytes of warm-up in front of a block (default and liblz4's reach: 64 KiB; less makes the guess fail
+        // more often -- the result stays exact, the blocks that fail are parsed again)
+        const uint64_t warmup = (uint64_t)g_opt.block_parallel_warmup.load();
+        std::vector<uint32_t> wfirst(nblocks), wlast(nblocks), ok(nblocks);
+        for (uint64_t f = 0; f < nframes; ++f)
+            for (uint32_t k = plan.frame_first[f]; k < plan.frame_first[f + 1]; ++k) {
+                uint32_t j = k;
+                uint64_t have = 0;
+                while (j > plan.frame_first[f] && have < warmup) { --j; have += plan.blocks[j].n; }
+                wfirst[k] = j; wlast[k] = (uint32_t)k;
+            }
+        sqy::Lz4SpecArgs sa;
+        sa.tables = static_cast<uint32_t*>(ws->spec.p);
+        uint32_t* d_wfirst = sa.tables + nblocks * sqy::kLz4SpecTableWords;
+        uint32_t* d_wlast = d_wfirst + nblocks;
+        uint32_t* d_ok = d_wlast + nblocks;
+        sa.wave_first = d_wfirst; sa.wave_last = d_wlast; sa.mode = 1;
+        SQY_HIP(hipMemcpyAsync(d_wfirst, wfirst.data(), list_bytes, hipMemcpyHostToDevice, stream));
+        SQY_HIP(hipMemcpyAsync(d_wlast, wlast.data(), list_bytes, hipMemcpyHostToDevice, stream));
+        SQY_TIMED("lz4_linked_blocks", sqy::launch_lz4_linked_spec(cur, d_blocks, sa, nblocks, plan.max_block, static_cast<uint8_t*>(ws->lz4_scratch.p),
+                                                                   lz4.stride, static_cast<uint32_t*>(ws->csize.p), stream, accel));
+        for (uint64_t round = 0;; ++round) {
+            SQY_TIMED("lz4_linked_verify", sqy::launch_lz4_linked_verify(d_blocks, nblocks, sa.tables, plan.max_block, d_ok, stream));
+            SQY_HIP(hipMemcpyAsync(ok.data(), d_ok, list_bytes, hipMemcpyDeviceToHost, stream));
+            SQY_HIP(hipStreamSynchronize(stream));
+            // runs of blocks that did not start from the true table: one wavefront each, in order, from the table in front
+            // (round-5 advice) a run is parsed by ONE wavefront, block after block: at most kRunMax blocks of it per launch (the
+            // rest keep failing the check and are taken by the next rounds, each from the table the last one left) -- the top
+            // plane of a quantised stack fails as one run of 511 blocks, seconds of work: sixteen launches of a fraction of a
+            // second instead of one kernel that runs for seconds; and the caller is told, once, what layout to ask for.
+            constexpr uint64_t kRunMax = 32;
+            uint64_t nruns = 0, longest_run = 0;
+            for (uint64_t k = 0; k < nblocks; ++k) {
+                if (ok[k]) continue;
+                uint64_t e = k;
+                while (e + 1 < nblocks && !ok[e + 1] && !(plan.blocks[e + 1].flags & 1u)) ++e;
+                longest_run = std::max(longest_run, e - k + 1);
+                wfirst[nruns] = (uint32_t)k; wlast[nruns] = (uint32_t)std::min(e, k + kRunMax - 1); ++nruns;
+                k = e;
+            }
+            if (longest_run > 4 * kRunMax) {
+                static std::atomic<bool> told{false};
+                if (!told.exchange(true))
+                    std::fprintf(stderr, "[sqeazy]\t lz4: %llu blocks in a row of this block-linked frame (nthreads = 1) can only be parsed one after "
+                                         "the other -- a stream of short sequences, whose table no guess reproduces -- by one wavefront, "
+                                         "~10 ms per block.  The chunked layout (nthreads = 0 or > 1: independent frames, same decoder) "
+                                         "takes milliseconds for the same data.\n", (unsigned long long)longest_run);
+            }
+            if (g_opt.block_parallel_stats.load()) {
+                uint64_t nbad = 0;
+                for (uint64_t r = 0; r < nruns; ++r) nbad += wlast[r] - wfirst[r] + 1;
+                std::fprintf(stderr, "[sqeazy]\t lz4 block-parallel: round %llu, %llu of %llu blocks to parse again in %llu runs",
+                             (unsigned long long)round, (unsigned long long)nbad, (unsigned long long)nblocks, (unsigned long long)nruns);
+                for (uint64_t r = 0; r < nruns && r < 24; ++r) std::fprintf(stderr, "%s%u..%u", r ? ", " : ": blocks ", wfirst[r], wlast[r]);
+                std::fprintf(stderr, "\n");
+            }
+            if (nruns == 0) return 0;
+            if (round > nblocks + 8) {
+                std::fprintf(stderr, "[sqeazy]\t lz4: the block-parallel parse did not settle\n");
+                return 1;
+            }
+            SQY_HIP(hipMemcpyAsync(d_wfirst, wfirst.data(), nruns * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+            SQY_HIP(hipMemcpyAsync(d_wlast, wlast.data(), nruns * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+            sa.mode = 2;
+            ProfScope ps("lz4_linked_redo", stream, pend);
+            SQY_HIP(sqy::launch_lz4_linked_spec(cur, d_blocks, sa, nruns, plan.max_block, static_cast<uint8_t*>(ws->lz4_scratch.p),
+                                                lz4.stride, static_cast<uint32_t*>(ws->csize.p), stream, accel));
+            SQY_HIP(hipStreamSynchronize(stream));             // (wfirst / wlast are reused by the next round)
+        }
+    }
+
+    // The payload's size, the sqy header (written after encoding, as the reference rewrites it: dynamic_pipeline.hpp:599-612), the frame
+    // offsets asked for, and the blob put together in d_dst
+    int finish(long* dstlength)
+    {
+        // ---- payload size ----
+        uint64_t payload_bytes = lz4.payload_bytes, tail_j = 0, tail_head_bytes = 0, tail_raw_head = 0;   // (known when the device finished the blob)
+        if (!lz4.on) {
+            payload_bytes = cur_len * (uint64_t)cur_elem;
+        } else if (lz4.nchunks == 0) {
+            payload_bytes = 7 + 4;                         // empty input: frame header + end mark
+        } else if (prep.inplace && !lz4.inplace_done) {
+            SQY_HIP(hipMemcpyAsync(ws->pinned, lz4.tail_info, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+            SQY_HIP(hipStreamSynchronize(stream));
+            const uint64_t* ti = static_cast<const uint64_t*>(ws->pinned);
+            tail_j = ti[0]; tail_head_bytes = ti[1]; tail_raw_head = ti[2]; payload_bytes = ti[3];
+        } else if (!lz4.inplace_done) {
+            SQY_HIP(hipMemcpyAsync(ws->pinned, static_cast<uint64_t*>(ws->frame_off.p) + lz4.nchunks, sizeof(uint64_t),
+                                   hipMemcpyDeviceToHost, stream));
+            SQY_HIP(hipStreamSynchronize(stream));
+            payload_bytes = *static_cast<uint64_t*>(ws->pinned);
+        }
+        if (lz4.on && payload_bytes > (uint64_t)INT_MAX) {
+            // encode_parallel sums the chunk sizes into an `int` and rejects the result (lz4_utils.hpp:264-273)
+            std::fprintf(stderr, "[sqeazy]\t lz4: %llu payload bytes overflow the reference's int byte count\n",
+                         (unsigned long long)payload_bytes);
+            return 1;
+        }
+        // the blob is complete (the stream synchronised): it lies at d_dst + at
+        auto done = [&](uint64_t at, uint64_t bytes) -> int {
+            if (g_prof_on.load()) prof_collect(*pend);
+            if (dstoffset) *dstoffset = (long)at;
+            *dstlength = (long)bytes;
+            return 0;
+        };
+        if (lz4.inplace_done) return done(lz4.blob_at, lz4.blob_bytes);
+
+        // ---- header ----
+        const std::string hdr = sqy::header_pack(elem_size, false, dims, pipe.name(), payload_bytes);
+        if (fq && fq->every > 0) {
+            if (!lz4.on || lz4.blocks || !fq->offsets) { std::fprintf(stderr, "[sqeazy]\t frame offsets: the payload is not one LZ4 frame per chunk\n"); return 1; }
+            const uint64_t cnt = (lz4.nchunks + (uint64_t)fq->every - 1) / (uint64_t)fq->every;
+            if (cnt + 1 > (uint64_t)std::max(fq->max_entries, 0)) { std::fprintf(stderr, "[sqeazy]\t frame offsets: %llu entries do not fit\n", (unsigned long long)(cnt + 1)); return 1; }
+            std::vector<uint64_t> fo(cnt + 1, 0);
+            if (cnt)
+                SQY_HIP(hipMemcpy2DAsync(fo.data(), sizeof(uint64_t), ws->frame_off.p, (size_t)fq->every * sizeof(uint64_t), sizeof(uint64_t), cnt,
+                                         hipMemcpyDeviceToHost, stream));
+            SQY_HIP(hipStreamSynchronize(stream));
+            for (uint64_t i = 0; i < cnt; ++i) fq->offsets[i] = (long)(fo[i] + hdr.size());
+            fq->offsets[cnt] = (long)(hdr.size() + payload_bytes);
+            fq->count = (int)cnt;
+        }
+        const uint64_t blob_bytes = hdr.size() + payload_bytes;
+        if (blob_bytes > dst_capacity) {
+            std::fprintf(stderr, "[sqeazy]\t destination buffer too small (%llu > %llu bytes)\n", (unsigned long long)blob_bytes,
+                         (unsigned long long)dst_capacity);
+            return 1;
+        }
+        uint8_t* out = static_cast<uint8_t*>(d_dst);
+        const Lz4Descriptor fd = lz4_descriptor(lz4.block_id);
+        if (prep.inplace) {
+            // the run of stored chunks j.. that ends the payload stays where the bit-plane transpose put it; frames 0..j-1 are
+            // gathered so that they end where frame j begins, the header goes in front of them
+            const uint64_t frame_j = prep.t0 + tail_j * prep.in_stride;
+            if (tail_head_bytes + hdr.size() > frame_j) { std::fprintf(stderr, "[sqeazy]\t internal error: frames in place overlap the header\n"); return 1; }
+            const uint64_t payload_at = frame_j - tail_head_bytes, blob_at = payload_at - hdr.size();
+            uint8_t* body0 = out + prep.t0 + 11;
+            SQY_TIMED("lz4_tail_marks", sqy::launch_lz4_tail_marks(body0, prep.in_stride, lz4.total, (uint32_t)lz4.chunk, lz4.nchunks, fd.bd, fd.hc, lz4.tail_info, stream));
+            if (tail_raw_head) {
+                SQY_TIMED("lz4_stash_raw", sqy::launch_lz4_stash_raw(body0, prep.in_stride, lz4.total, (uint32_t)lz4.chunk, static_cast<uint8_t*>(ws->lz4_scratch.p), lz4.stride,
+                                                                     static_cast<uint32_t*>(ws->csize.p), lz4.dup_of, tail_j, stream));
+            }
+            if (tail_j) {
+                SQY_TIMED("lz4_frame_gather", sqy::launch_lz4_frame_gather(body0, lz4.total, (uint32_t)lz4.chunk, static_cast<uint8_t*>(ws->lz4_scratch.p), lz4.stride,
+                                                                           static_cast<uint32_t*>(ws->csize.p), static_cast<uint64_t*>(ws->frame_off.p), out + payload_at, fd.bd, fd.hc,
+                                                                           tail_j, stream, nullptr, 0, nullptr, lz4.dup_of, prep.in_stride, tail_raw_head != 0));
+            }
+            SQY_HIP(hipMemcpyAsync(out + blob_at, hdr.data(), hdr.size(), hipMemcpyHostToDevice, stream));
+            SQY_HIP(hipStreamSynchronize(stream));
+            return done(blob_at, blob_bytes);
+        }
+        SQY_HIP(hipMemcpyAsync(out, hdr.data(), hdr.size(), hipMemcpyHostToDevice, stream));
+        if (lz4.on && lz4.nchunks == 0) {
+            const unsigned char empty[11] = {0x04, 0x22, 0x4D, 0x18, fd.flg, fd.bd, (unsigned char)fd.hc, 0, 0, 0, 0};
+            SQY_HIP(hipMemcpyAsync(out + hdr.size(), empty, sizeof(empty), hipMemcpyHostToDevice, stream));
+        } else if (lz4.on) {
+            SQY_TIMED("lz4_frame_gather", sqy::launch_lz4_frame_gather(cur, lz4.total, (uint32_t)lz4.chunk, static_cast<uint8_t*>(ws->lz4_scratch.p), lz4.stride,
+                                                                       static_cast<uint32_t*>(ws->csize.p), static_cast<uint64_t*>(ws->frame_off.p),
+                                                                       out + hdr.size(), fd.bd, fd.hc, lz4.nchunks, stream, prep.frame_map, prep.frame_bytes, lz4.blocks, lz4.dup_of));
+        } else {
+            SQY_TIMED("payload_copy", hipMemcpyAsync(out + hdr.size(), cur, payload_bytes, hipMemcpyDeviceToDevice, stream));
+        }
+        SQY_HIP(hipStreamSynchronize(stream));
+        return done(0, blob_bytes);
+    }
 };
 
 int encode_on_device(Context& cx, const char* pipeline_c, const void* d_src, const long* shape, unsigned rank, int elem_size,
@@ -431,832 +1230,39 @@ int encode_on_device(Context& cx, const char* pipeline_c, const void* d_src, con
         return 1;
     }
     pipe.set_n_threads(nthreads);
-
-    std::vector<uint64_t> dims(shape, shape + rank);
-    uint64_t len = 1;
-    for (uint64_t d : dims) {
-        if ((long)d <= 0) { std::fprintf(stderr, "[sqeazy]\t non-positive extent in shape\n"); return 1; }
-        len *= d;
-        if (len >= ((uint64_t)1 << 31)) {
-            // the reference multiplies the extents into an `int` (dynamic_pipeline.hpp:565): one call is < 2^31 voxels
-            std::fprintf(stderr, "[sqeazy]\t %llu+ voxels in one call overflow the reference's int voxel count; encode z-slabs\n",
-                         (unsigned long long)len);
-            return 1;
-        }
-    }
-    const uint64_t raw_bytes = len * (uint64_t)elem_size;
-    if (!background_geometry_ok(pipe, dims)) return 1;
-
-    Workspace* ws = &cx.ws;
-    std::vector<PendingEvent>* pend = &cx.pending;
-    DrainOnExit drain{stream, pend, cx.side};
-
-    // ---- walk the stages ----
-    const uint8_t* cur = static_cast<const uint8_t*>(d_src);
-    int cur_elem = elem_size;            // bytes per element of the stream between stages
-    uint64_t cur_len = len;              // elements
-    bool use_ping = true;
-    auto next_buf = [&](size_t bytes) -> uint8_t* {
-        DevBuf& b = use_ping ? ws->ping : ws->pong;
-        use_ping = !use_ping;
-        if (b.ensure(bytes)) return nullptr;
-        return static_cast<uint8_t*>(b.p);
-    };
-
-    // the shape a 3-D stage sees: the volume's -- or, behind a sink that did not write one byte per voxel, {1, 1, bytes}
-    // (dynamic_pipeline.hpp:658-666: the tail chain's "sinked_shape")
-    auto stage_shape = [&](size_t si, uint64_t& Z, uint64_t& Y, uint64_t& X) {
-        const bool tail = pipe.sink_index >= 0 && (int)si > pipe.sink_index;
-        const bool flat = tail && cur_len * (uint64_t)cur_elem != len;
-        Z = flat ? 1 : dims[0]; Y = flat ? 1 : dims[1]; X = flat ? cur_len : dims[2];
-    };
-
-    uint64_t payload_bytes = 0;
-    bool payload_is_lz4 = false;
-    const sqy::Lz4Params* lz4p = nullptr;
-    uint64_t lz4_total = 0, lz4_nchunks = 0, lz4_chunk = 0, lz4_stride = 0;
-    const uint64_t* lz4_frame_map = nullptr;     // frame_shuffle directly in front of lz4: frames are read through the map
-    uint64_t lz4_frame_bytes = 0;
-    const uint32_t* lz4_piece_hash = nullptr;    // left by a 16-bit bitswap1 directly in front of lz4: hashes of the 1 KiB pieces of the plane stream
-    const uint32_t* lz4_dup_of = nullptr;        // chunks that are byte-identical to an earlier chunk share its frame
-    const sqy::Lz4Block* lz4_blocks = nullptr;   // block-linked frames (nthreads == 1, or chunks of several LZ4 blocks): the block list in HBM
-    // frames in place: chunk k of the plane stream sits at d_dst + inplace_t0 + 11 + k * lz4_in_stride
-    bool lz4_inplace = false;
-    uint64_t lz4_in_stride = 0, inplace_t0 = 0;
-    // diff3x3x1 directly in front of a 16-bit bitswap1: only the columns the stage can touch are computed (compact side buffer)
-    const uint16_t* bsw_side = nullptr;
-    uint32_t bsw_side_w = 0, bsw_side_X = 0;
-    uint64_t* lz4_tail_info = nullptr;
-    sqy::Lz4DedupeArgs lz4_dedupe_args;          // frames in place: the duplicate decision per chunk is made inside the parse kernel
-    bool fused_dedupe = false;
-    bool dedupe_cleared = false;                 // the duplicate search's table and the dense list's counter were zeroed in front of the transpose
-    bool inplace_done = false;                   // frames in place, finished on the device: where the blob is
-    uint64_t inplace_blob_at = 0, inplace_blob_bytes = 0, inplace_hdr_bytes = 0;
-    uint64_t* lz4_holes = nullptr;               // frames in place: which 1 KiB pieces of the plane stream the transpose left unwritten (all zero)
-    uint32_t* lz4_digest = nullptr;              // frames in place: the noise digest (sqy_kernels.h: launch_bitswap1_u16), lz4_digest_stride words per chunk
-    uint32_t lz4_digest_stride = 0;
-    static_assert(sizeof(sqy::Lz4Block) == sizeof(sqy::Lz4BlockPlan) && sizeof(sqy::Lz4Block) == 32, "plan entries are read by the kernels as they are");
-
-    size_t skip_stage = ~(size_t)0;             // a stage that the stage in front of it has already done (quantiser + bitswap1 in one pass)
-    for (size_t si = 0; si < pipe.stages.size(); ++si) {
-        if (si == skip_stage) continue;
-
-        Stage& st = pipe.stages[si];
-        switch (st.kind) {
-            case StageKind::bitswap1: {
-                // lz4 right behind: leave piece hashes for its duplicate-chunk detection (bit planes of small values repeat)
-                uint32_t* ph = nullptr;
-                uint64_t gap_chunk = 0;
-                if (cur_elem == 2 && si + 1 < pipe.stages.size() && pipe.stages[si + 1].kind == StageKind::lz4) {
-                    const uint64_t words = sqy::bitswap1_piece_hash_words(cur, cur, cur_len);         // (0 unless whole tiles, 16-byte aligned input)
-                    const uint64_t total = cur_len * 2;
-                    const uint64_t chunk = pipe.stages[si + 1].lz4.bytes_per_chunk(total);
-                    const bool chunked = chunk <= pipe.stages[si + 1].lz4.block_bytes() && !(pipe.nthreads == 1 && total > chunk);
-                    if (words && chunked && chunk % 1024 == 0 && total > chunk) {
-                        const uint64_t nch = (total + chunk - 1) / chunk;
-                        const uint64_t ph_bytes = (words * 4 + 63) & ~(uint64_t)63;
-                        if (ws->dedupe.ensure(ph_bytes + sqy::lz4_dedupe_work_bytes(nch) + ((nch * 4 + 7) & ~(uint64_t)7) + sqy::lz4_holes_map_bytes(nch, (uint32_t)chunk))) return 1;
-                        ph = static_cast<uint32_t*>(ws->dedupe.p);
-                        lz4_piece_hash = ph;
-                        // frames in place: lz4 is the last stage, chunks a power of two, the caller takes the blob where it ends up,
-                        // and the destination holds frame headers in front of and end marks behind every chunk
-                        if (dstoffset && si + 2 == pipe.stages.size() && (chunk & (chunk - 1)) == 0) {
-                            // room in front for the sqy header (its length depends on the payload size: take the longest)
-                            const uint64_t hdr_max = sqy::header_pack(elem_size, false, dims, pipe.name(), (uint64_t)INT_MAX).size() + 2;
-                            uint64_t t0 = hdr_max;
-                            while ((reinterpret_cast<uintptr_t>(d_dst) + t0 + 11) & 15) ++t0;          // body of chunk 0 on a 16-byte boundary
-                            if (t0 + nch * (chunk + 15) <= dst_capacity) {
-                                gap_chunk = chunk;
-                                inplace_t0 = t0;
-                                lz4_in_stride = chunk + 15;
-                                lz4_inplace = true;
-                                // (one small kernel in front of the transpose instead of three fill dispatches between the kernels behind it)
-                                if (ws->plan.ensure((nch + 1) * sizeof(uint32_t))) return 1;
-                                SQY_HIP(sqy::launch_lz4_dedupe_clear(static_cast<uint8_t*>(ws->dedupe.p) + ph_bytes, nch, static_cast<uint32_t*>(ws->plan.p), stream));
-                                dedupe_cleared = true;
-                                // the noise digest (round 6): every plane segment a whole number of chunks, liblz4's plain search behind it
-                                const uint32_t dstride = sqy::lz4_noise_digest_stride((uint32_t)chunk);
-                                if (g_opt.noise_digest.load() && dstride && (cur_len / 8) % chunk == 0 && pipe.stages[si + 1].lz4.accel >= 0 &&
-                                    !ws->digest.ensure(nch * (uint64_t)dstride * sizeof(uint32_t), true)) {
-                                    lz4_digest = static_cast<uint32_t*>(ws->digest.p);
-                                    lz4_digest_stride = dstride;
-                                }
-                            }
-                        }
-                    }
-                }
-                uint8_t* out = gap_chunk ? static_cast<uint8_t*>(d_dst) + inplace_t0 + 11 : next_buf(cur_len * cur_elem);
-                if (!out) return 1;
-                if (!gap_chunk && ph && (reinterpret_cast<uintptr_t>(out) & 15)) { ph = nullptr; lz4_piece_hash = nullptr; }
-                // The bit-plane transposes of the calls in flight on one device run one after the other (round 4): a stream waits for the
-                // transpose of the call in front before it starts its own.  Two HBM-bound kernels side by side each run at half speed
-                // and end together; chained, the first call's parse starts a whole transpose earlier (bench, four calls in flight:
-                // +3 %; also chaining the duplicate search behind it: -12 %, measured and not kept).  Only a transpose launched within
-                // the last few milliseconds is waited for.  The chain is an edge between streams: by default only streams this library
-                // owns (the host-pointer entry points, the Slabs workers) are chained -- a stream the CALLER brings may carry work this
-                // library knows nothing about (a backlog, a host function that waits for another of the caller's threads), and a hidden
-                // wait on it would couple calls that are documented as independent (round-4 advice).  A caller whose streams carry
-                // nothing but these calls opts in: SQYAMD_Set_Option("transpose_chain_caller_streams", 1) (bench.py does, and says so).
-                // "transpose_chain" = 0 (or SQY_NO_TRANSPOSE_CHAIN=1 when the library is loaded) switches the chain off altogether.
-                const bool owned = stream != nullptr && stream == cx.stream;
-                int devid = 0;
-                const bool chain = g_opt.transpose_chain.load() && (owned || g_opt.transpose_chain_caller_streams.load()) && gap_chunk &&
-                                   hipGetDevice(&devid) == hipSuccess && devid >= 0 && devid < kMaxDev;
-                std::unique_lock<std::mutex> tlock;
-                if (chain) {
-                    if (!cx.t_done && hipEventCreateWithFlags(&cx.t_done, hipEventDisableTiming) != hipSuccess) return 1;
-                    tlock = std::unique_lock<std::mutex>(g_tchain_mu[devid]);
-                    const auto now = std::chrono::steady_clock::now();
-                    if (g_tchain_last[devid] && g_tchain_last[devid] != cx.t_done && now - g_tchain_when[devid] < std::chrono::milliseconds(5))
-                        SQY_HIP(hipStreamWaitEvent(stream, g_tchain_last[devid], 0));
-                    g_tchain_when[devid] = now;
-                }
-                {
-                ProfScope ps(cur_elem == 2 ? "bitswap1_u16" : "bitswap1_u8", stream, pend);
-                if (cur_elem == 2)
-                    SQY_HIP(sqy::launch_bitswap1_u16(reinterpret_cast<const uint16_t*>(cur), reinterpret_cast<uint16_t*>(out), cur_len, stream, ph,
-                                                     (uint32_t)gap_chunk, bsw_side, bsw_side_w, bsw_side_X, gap_chunk ? lz4_digest : nullptr,
-                                                     lz4_digest_stride));
-                else
-                    SQY_HIP(sqy::launch_bitswap1_u8(cur, out, cur_len, stream));
-                }
-                if (chain) {
-                    SQY_HIP(hipEventRecord(cx.t_done, stream));
-                    g_tchain_last[devid] = cx.t_done;
-                    tlock.unlock();
-                }
-                bsw_side = nullptr; bsw_side_w = 0; bsw_side_X = 0;       // (consumed: a later bitswap1 of the pipeline reads its plain input)
-                cur = out;
-                break;
-            }
-            case StageKind::raster_reorder: {
-                if (dims.size() != 3) {
-                    std::fprintf(stderr, "[sqeazy::detail::reorder::encode] received non-3D shape which is currently unsupported!\n");
-                    return 1;
-                }
-                const uint64_t ts = (uint64_t)std::atoi(st.cfg["tile_size"].c_str());
-                // (round 5) as a tail filter the stream is the sink's `char` output: the volume's shape when that is one byte per voxel,
-                // else {1, 1, bytes} (dynamic_pipeline.hpp:658-666; sqeazy_pipelines.hpp:64-77 lists the stage for the tail chain)
-                uint64_t Z, Y, X;
-                stage_shape(si, Z, Y, X);
-                if (!sqy::raster_geometry_defined(Z, Y, X, ts, cur_elem)) {
-                    std::fprintf(stderr, "[sqeazy]\t raster_reorder: the reference's result is undefined for shape %llux%llux%llu at tile_size=%llu "
-                                         "(remainder in some dimensions only, or a tile wider than one 16-byte block); refused\n",
-                                 (unsigned long long)Z, (unsigned long long)Y, (unsigned long long)X, (unsigned long long)ts);
-                    return 1;
-                }
-                uint8_t* out = next_buf(cur_len * cur_elem);
-                if (!out) return 1;
-                ProfScope ps("raster_reorder", stream, pend);
-                SQY_HIP(sqy::launch_raster_reorder(cur, out, Z, Y, X, ts, cur_elem, false, stream));
-                cur = out;
-                break;
-            }
-            case StageKind::rmestbkrd: {
-                // remove_estimated_background_scheme::encode (remove_estimated_background_scheme_impl.hpp:71-110); shape checked above
-                const uint64_t portion = sqy::rmestbkrd_face_portion(dims[1] * dims[2], (uint32_t)g_opt.host_l2_bytes.load());
-                if (ws->bkrd.ensure(sqy::rmestbkrd_work_bytes(cur_elem))) return 1;
-                uint8_t* out = next_buf(cur_len * cur_elem);
-                if (!out) return 1;
-                ProfScope ps("rmestbkrd", stream, pend);
-                SQY_HIP(sqy::launch_rmestbkrd(cur, out, dims[0], dims[1], dims[2], portion, cur_elem, ws->bkrd.p, stream));
-                cur = out;
-                break;
-            }
-            case StageKind::rmbkrd_neighbor5: {
-                // flatten_to_neighborhood_scheme::encode (flatten_to_neighborhood_scheme_impl.hpp:90-150): the threshold in the voxel type,
-                // cut_fraction = fraction * (size<Neighborhood>() - 1) in float; shape checked above
-                const float cut = st.nb_fraction * (float)(125u - 1u);
-                uint8_t* out = next_buf(cur_len * cur_elem);
-                if (!out) return 1;
-                ProfScope ps("rmbkrd_neighbor5x5x5", stream, pend);
-                SQY_HIP(sqy::launch_rmbkrd_neighbor5(cur, out, dims[0], dims[1], dims[2], (uint32_t)st.nb_threshold, cut,
-                                                     sqy::neighbor5_z_end(dims[0], dims[2]), cur_elem, stream));
-                cur = out;
-                break;
-            }
-            case StageKind::pass_through: {
-                // pass_through_scheme_impl.hpp:66-79: the sink that only re-types the stream to bytes
-                cur_len *= (uint64_t)cur_elem;
-                cur_elem = 1;
-                break;
-            }
-            case StageKind::zcurve_reorder: {
-                if (dims.size() != 3) {
-                    std::fprintf(stderr, "[sqeazy::detail::zcurve::encode] received non-3D shape which is currently unsupported!\n");
-                    return 1;
-                }
-                auto t = st.cfg.find("tile_size");
-                const uint64_t ts = t != st.cfg.end() ? (uint64_t)std::atoi(t->second.c_str()) : 2;
-                uint64_t Z, Y, X;
-                stage_shape(si, Z, Y, X);                                  // (tail filter: the sink's char stream, see raster_reorder)
-                if (!sqy::zcurve_geometry_defined(Z, Y, X, ts)) {
-                    std::fprintf(stderr, "[sqeazy]\t zcurve_reorder: the reference's result is undefined for shape %llux%llux%llu at tile_size=%llu "
-                                         "(tile sizes other than 2..128 powers of two, or a tile that does not divide a power-of-two shape); refused\n",
-                                 (unsigned long long)Z, (unsigned long long)Y, (unsigned long long)X, (unsigned long long)ts);
-                    return 1;
-                }
-                uint8_t* out = next_buf(cur_len * cur_elem);
-                if (!out) return 1;
-                ProfScope ps("zcurve_reorder", stream, pend);
-                // (inside a tile the reference's morton_at_ct<log2(tile)> code is row-major: the tiled raster kernel is the stage)
-                SQY_HIP(sqy::launch_raster_reorder(cur, out, Z, Y, X, ts, cur_elem, false, stream));
-                cur = out;
-                break;
-            }
-            case StageKind::bitshuffle: {
-                auto b = st.cfg.find("block_size");
-                const uint64_t be = sqy::bitshuffle_block_elems(cur_elem, b != st.cfg.end() ? (uint64_t)std::atoi(b->second.c_str()) : 0);
-                if (!be) { std::fprintf(stderr, "[sqeazy]\t bitshuffle: block_size must be a multiple of 8\n"); return 1; }
-                uint8_t* out = next_buf(cur_len * cur_elem);
-                if (!out) return 1;
-                ProfScope ps("bitshuffle", stream, pend);
-                SQY_HIP(sqy::launch_bitshuffle(cur, out, cur_len, cur_elem, be, false, stream));
-                cur = out;
-                break;
-            }
-            case StageKind::tile_shuffle: {
-                if (dims.size() != 3) {
-                    std::fprintf(stderr, "[sqeazy::detail::tile_shuffle::encode] received non-3D shape which is currently unsupported!\n");
-                    return 1;
-                }
-                auto t = st.cfg.find("tile_size");
-                const uint64_t ts = t != st.cfg.end() ? (uint64_t)std::atoi(t->second.c_str()) : 32;
-                // (tail filter: tile_shuffle_scheme<char> on the sink's stream -- the tile sums add SIGNED bytes and the metric is a char)
-                const bool tail = pipe.sink_index >= 0 && (int)si > pipe.sink_index;
-                uint64_t Z, Y, X;
-                stage_shape(si, Z, Y, X);
-                if (!sqy::tile_shuffle_geometry_defined(Z, Y, X, ts)) {
-                    std::fprintf(stderr, "[sqeazy]\t tile_shuffle: shape %llux%llux%llu is not a whole multiple of tile_size=%llu; the reference's remainder "
-                                         "path (P^2 median over tiles read past their end, thread-timing dependent map) is not reproduced; refused\n",
-                                 (unsigned long long)Z, (unsigned long long)Y, (unsigned long long)X, (unsigned long long)ts);
-                    return 1;
-                }
-                const uint64_t per_tile = ts * ts * ts, ntiles = cur_len / per_tile, tile_bytes = per_tile * (uint64_t)cur_elem;
-                // 1. tiles made contiguous (tile-major copy), 2. their sequential binary32 sums, 3. order on the host, 4. tiles appended in that order
-                uint8_t* tiled = next_buf(cur_len * cur_elem);
-                if (!tiled) return 1;
-                {
-                    ProfScope ps("tile_gather", stream, pend);
-                    SQY_HIP(sqy::launch_raster_reorder(cur, tiled, Z, Y, X, ts, cur_elem, false, stream));
-                }
-                if (ws->small.ensure(std::max<uint64_t>(ntiles * 16, 4096))) return 1;
-                float* d_sums = static_cast<float*>(ws->small.p);
-                uint64_t* d_map = reinterpret_cast<uint64_t*>(static_cast<uint8_t*>(ws->small.p) + ((ntiles * 4 + 15) & ~(uint64_t)15));
-                {
-                    const uint64_t fm_bytes = sqy::frame_metric_scratch_bytes(ntiles, per_tile, cur_elem);
-                    if (ws->lz4_scratch.ensure(std::max<uint64_t>(fm_bytes, 16))) return 1;
-                    ProfScope ps("tile_metric", stream, pend);
-                    SQY_HIP(sqy::launch_frame_metric(tiled, ntiles, per_tile, cur_elem, d_sums, stream, ws->lz4_scratch.p, fm_bytes, tail));
-                }
-                std::vector<float> sums(ntiles);
-                std::vector<uint64_t> map(ntiles);
-                SQY_HIP(hipMemcpyAsync(sums.data(), d_sums, ntiles * sizeof(float), hipMemcpyDeviceToHost, stream));
-                SQY_HIP(hipStreamSynchronize(stream));
-                sqy::tile_shuffle_order(sums.data(), ntiles, per_tile, cur_elem, map.data(), tail);
-                SQY_HIP(hipMemcpyAsync(d_map, map.data(), ntiles * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
-                uint8_t* out = next_buf(cur_len * cur_elem);
-                if (!out) return 1;
-                {
-                    ProfScope ps("tile_shuffle", stream, pend);
-                    SQY_HIP(sqy::launch_frame_gather(tiled, out, ntiles, tile_bytes, d_map, stream));
-                }
-                SQY_HIP(hipStreamSynchronize(stream));                     // `map` (host) is read by the async copy above
-                st.cfg["reorder_map"] = sqy::to_verbatim(map.data(), ntiles * sizeof(uint64_t));   // tile_shuffle_scheme_impl.hpp:88
-                cur = out;
-                break;
-            }
-            case StageKind::diff3x3x1: {
-                if (dims.size() != 3) {
-                    // diff_scheme_impl.hpp:84-87 returns the output pointer unmoved -> the chain throws
-                    // (dynamic_stage_chain.hpp:313-317); no exception may cross this ABI
-                    std::fprintf(stderr, "[diff_scheme] unable to process input data that is not 3D\n");
-                    return 1;
-                }
-                // as a tail filter the stream is the sink's `char` output: the volume's shape when that is one byte per voxel, else
-                // {1, 1, bytes} (dynamic_pipeline.hpp:658-666), which the stage cannot take
-                const bool tail = pipe.sink_index >= 0 && (int)si > pipe.sink_index;
-                const bool flat = tail && cur_len * (uint64_t)cur_elem != len;
-                const uint64_t Z = flat ? 1 : dims[0], Y = flat ? 1 : dims[1], X = flat ? cur_len : dims[2];
-                if ((int64_t)(X - 1) * (int64_t)(Y - 2) <= 1 || Y < 3 || X < 2) {
-                    std::fprintf(stderr, "[sqeazy]\t diff3x3x1: shape %llux%llux%llu reads out of bounds in the reference; refused\n",
-                                 (unsigned long long)Z, (unsigned long long)Y, (unsigned long long)X);
-                    return 1;
-                }
-                if (cur_elem == 1 && (Z > 127 || Y > 127 || X > 127)) {
-                    std::fprintf(stderr, "[sqeazy]\t diff3x3x1 on 8-bit voxels: extents > 127 overflow the reference's char coordinates; refused\n");
-                    return 1;
-                }
-                {
-                    const uint32_t sw = (!tail && si + 1 < pipe.stages.size() && pipe.stages[si + 1].kind == StageKind::bitswap1 &&
-                                         (reinterpret_cast<uintptr_t>(cur) & 15) == 0)
-                                            ? sqy::diff3x3x1_side_width(Z, Y, X, cur_elem) : 0;
-                    if (sw) {
-                        // a buffer of its own: `cur` stays where it is, so the transpose's output (the next buffer of the
-                        // ping/pong rotation) can never be the buffer `cur` lives in
-                        if (ws->diff_side.ensure(Z * Y * (uint64_t)sw * 2)) return 1;
-                        uint8_t* side = static_cast<uint8_t*>(ws->diff_side.p);
-                        ProfScope ps("diff3x3x1", stream, pend);
-                        SQY_HIP(sqy::launch_diff3x3x1_side(reinterpret_cast<const uint16_t*>(cur), reinterpret_cast<uint16_t*>(side), Z, Y, X, sw, stream));
-                        bsw_side = reinterpret_cast<const uint16_t*>(side);
-                        bsw_side_w = sw;
-                        bsw_side_X = (uint32_t)X;
-                        break;                                              // (`cur` stays the stage's input: the transpose reads both)
-                    }
-                }
-                uint8_t* out = next_buf(cur_len * cur_elem);
-                if (!out) return 1;
-                ProfScope ps("diff3x3x1", stream, pend);
-                SQY_HIP(sqy::launch_diff3x3x1(cur, out, Z, Y, X, cur_elem, stream, tail));
-                cur = out;
-                break;
-            }
-            case StageKind::frame_shuffle: {
-                if (dims.size() != 3) {
-                    std::fprintf(stderr, "[sqeazy::detail::frame_shuffle::encode] received non-3D shape which is currently unsupported!\n");
-                    return 1;
-                }
-                // (tail filter: signed bytes; ONE frame {1, 1, bytes} when the sink did not write one byte per voxel)
-                const bool tail = pipe.sink_index >= 0 && (int)si > pipe.sink_index;
-                const bool flat = tail && cur_len * (uint64_t)cur_elem != len;
-                // frame_chunk_size = N: N consecutive frames are one sort unit (frame_shuffle_utils.hpp:105-133, encode_full) -- the stage
-                // on Z / N "frames" of N * Y * X voxels.  Z % N != 0 takes the reference's encode_with_remainder (Boost's P^2 median
-                // estimate as the metric, :193-260): not reproduced
-                uint64_t fcs = 1;
-                {
-                    auto c = st.cfg.find("frame_chunk_size");
-                    if (c != st.cfg.end()) fcs = (uint64_t)std::max(std::atoi(c->second.c_str()), 0);
-                }
-                const uint64_t Z0 = flat ? 1 : dims[0];
-                if (fcs == 0 || Z0 % fcs != 0) {
-                    std::fprintf(stderr, "[sqeazy]\t frame_shuffle: %llu frames are no whole multiple of frame_chunk_size=%llu; the reference's remainder path "
-                                         "(a P^2 median estimate as the metric) is not reproduced; refused\n", (unsigned long long)Z0, (unsigned long long)fcs);
-                    return 1;
-                }
-                const uint64_t Z = Z0 / fcs, per_frame = (flat ? cur_len : dims[1] * dims[2]) * fcs;
-                if (ws->small.ensure(std::max<uint64_t>(Z * 16, 4096))) return 1;
-                float* d_sums = static_cast<float*>(ws->small.p);
-                uint64_t* d_map = reinterpret_cast<uint64_t*>(static_cast<uint8_t*>(ws->small.p) + ((Z * 4 + 15) & ~(uint64_t)15));
-                {
-                    const uint64_t fm_bytes = sqy::frame_metric_scratch_bytes(Z, per_frame, cur_elem);
-                    if (ws->lz4_scratch.ensure(std::max<uint64_t>(fm_bytes, 16))) return 1;      // free until the sink runs
-                    ProfScope ps("frame_metric", stream, pend);
-                    SQY_HIP(sqy::launch_frame_metric(cur, Z, per_frame, cur_elem, d_sums, stream, ws->lz4_scratch.p, fm_bytes, tail));
-                }
-                std::vector<float> sums(Z);
-                std::vector<uint64_t> map(Z);
-                SQY_HIP(hipMemcpyAsync(sums.data(), d_sums, Z * sizeof(float), hipMemcpyDeviceToHost, stream));
-                SQY_HIP(hipStreamSynchronize(stream));
-                sqy::frame_shuffle_order(sums.data(), Z, per_frame, map.data());
-                SQY_HIP(hipMemcpyAsync(d_map, map.data(), Z * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
-                // when lz4 follows immediately and its chunks tile the frames, the permuted copy is never materialised:
-                // the LZ4 kernels read frame map[f] where the stream has frame f
-                const uint64_t frame_bytes = per_frame * (uint64_t)cur_elem;
-                bool fused = false;
-                if (si + 1 < pipe.stages.size() && pipe.stages[si + 1].kind == StageKind::lz4 && frame_bytes) {
-                    const uint64_t total = cur_len * (uint64_t)cur_elem;
-                    const uint64_t chunk = pipe.stages[si + 1].lz4.bytes_per_chunk(total);
-                    fused = chunk && frame_bytes % chunk == 0 && chunk <= pipe.stages[si + 1].lz4.block_bytes() &&
-                            !(pipe.nthreads == 1 && total > chunk);               // (block-linked frames read a gathered copy)
-                }
-                if (fused) {
-                    lz4_frame_map = d_map;
-                    lz4_frame_bytes = frame_bytes;
-                    SQY_HIP(hipStreamSynchronize(stream));                 // `map` (host) is read by the async copy above
-                } else {
-                    uint8_t* out = next_buf(cur_len * cur_elem);
-                    if (!out) return 1;
-                    {
-                        ProfScope ps("frame_gather", stream, pend);
-                        SQY_HIP(sqy::launch_frame_gather(cur, out, Z, frame_bytes, d_map, stream));
-                    }
-                    SQY_HIP(hipStreamSynchronize(stream));                 // `map` (host) is read by the async copy above
-                    cur = out;
-                }
-                st.cfg["frame_chunk_size"] = std::to_string(fcs);
-                st.cfg["reorder_map"] = sqy::to_verbatim(map.data(), Z * sizeof(uint64_t));   // frame_shuffle_scheme_impl.hpp:86-90
-                break;
-            }
-            case StageKind::quantiser: {
-                // quantiser_scheme<uint16_t,char>::encode (quantiser_scheme_impl.hpp:176-226)
-                if (ws->small.ensure(65536 * sizeof(uint32_t) + 65536)) return 1;
-                uint32_t* d_histo = static_cast<uint32_t*>(ws->small.p);
-                uint8_t* d_lut = static_cast<uint8_t*>(ws->small.p) + 65536 * sizeof(uint32_t);
-                {
-                    ProfScope ps("histogram_u16", stream, pend);
-                    SQY_HIP(sqy::launch_histogram_u16(reinterpret_cast<const uint16_t*>(cur), cur_len, d_histo, stream));
-                }
-                std::vector<uint32_t> histo(65536);
-                std::vector<unsigned char> lut_encode(65536);
-                uint16_t lut_decode[256];
-                SQY_HIP(hipMemcpyAsync(histo.data(), d_histo, 65536 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-                SQY_HIP(hipStreamSynchronize(stream));
-                sqy::QuantiserWeighting qw;
-                {
-                    auto wf = st.cfg.find("weighting_function");
-                    if (wf != st.cfg.end() && !sqy::quantiser_parse_weighting(wf->second, &qw)) return 1;    // (refused by supported() already)
-                }
-                sqy::quantiser_build_luts(histo.data(), 65536, lut_encode.data(), lut_decode, qw);
-                SQY_HIP(hipMemcpyAsync(d_lut, lut_encode.data(), 65536, hipMemcpyHostToDevice, stream));
-                uint8_t* out = next_buf(cur_len);
-                if (!out) return 1;
-                // (round 5) bitswap1 right behind the sink: look-up and 8-bit bit-plane transpose in one pass, the stage behind is done too
-                const bool fuse_bitswap = si + 1 < pipe.stages.size() && pipe.stages[si + 1].kind == StageKind::bitswap1 &&
-                                          (reinterpret_cast<uintptr_t>(cur) & 15) == 0;
-                if (fuse_bitswap) {
-                    ProfScope ps("quantiser_bitswap1_u8", stream, pend);
-                    SQY_HIP(sqy::launch_quantiser_apply_bitswap1_u8(reinterpret_cast<const uint16_t*>(cur), out, cur_len, d_lut, stream));
-                    skip_stage = si + 1;
-                } else {
-                    ProfScope ps("quantiser_apply", stream, pend);
-                    SQY_HIP(sqy::launch_quantiser_apply_u16(reinterpret_cast<const uint16_t*>(cur), out, cur_len, d_lut, stream));
-                }
-                SQY_HIP(hipStreamSynchronize(stream));                     // lut_encode (host) is read by the async copy above
-                {
-                    // quantiser_scheme_impl.hpp:200-204: the decode LUT goes to the file the caller named, else into the header
-                    auto lp = st.cfg.find("decode_lut_path");
-                    if (lp != st.cfg.end()) {
-                        if (!sqy::quantiser_lut_to_file(lp->second, lut_decode, 256)) {
-                            // (the reference does not notice and returns a blob nobody can decode; here the encode fails)
-                            std::fprintf(stderr, "[sqeazy]\t quantiser: unable to write the decode LUT to %s\n", lp->second.c_str());
-                            return 1;
-                        }
-                    } else
-                        st.cfg["decode_lut_string"] = sqy::to_verbatim(lut_decode, sizeof(lut_decode));
-                }
-                cur = out;
-                cur_elem = 1;                                              // sink output is `char`
-                break;
-            }
-            case StageKind::lz4: {
-                lz4p = &st.lz4;
-                // liblz4's acceleration: LZ4F turns a negative compression level -k into acceleration k + 1 (lz4frame.c, LZ4F_compressBlock),
-                // LZ4_compress_fast_continue caps it at 65537 (lz4.c, LZ4_ACCELERATION_MAX)
-                const uint32_t lz4_accel = st.lz4.accel < 0 ? (uint32_t)std::min<int64_t>(1 - (int64_t)st.lz4.accel, 65537) : 1u;
-                lz4_total = cur_len * (uint64_t)cur_elem;
-                lz4_chunk = lz4_total ? st.lz4.bytes_per_chunk(lz4_total) : 1;
-                lz4_nchunks = lz4_total ? (lz4_total + lz4_chunk - 1) / lz4_chunk : 0;
-                const bool serial = pipe.nthreads == 1 && lz4_nchunks > 1;          // lz4.hpp:227-234: one block-linked frame
-                if (!serial && lz4_chunk <= st.lz4.block_bytes()) {
-                    // chunked layout, one LZ4 block per frame: every chunk is independent
-                    lz4_stride = (lz4_chunk + 15) & ~(uint64_t)15;
-                    if (ws->lz4_scratch.ensure(std::max<uint64_t>(lz4_nchunks * lz4_stride, 16))) return 1;
-                    if (ws->csize.ensure(std::max<uint64_t>(lz4_nchunks, 1) * sizeof(uint32_t))) return 1;
-                    if (ws->frame_off.ensure((lz4_nchunks + 1 + 4) * sizeof(uint64_t))) return 1;
-                    if (lz4_inplace) lz4_tail_info = static_cast<uint64_t*>(ws->frame_off.p) + lz4_nchunks + 1;
-                    if (lz4_piece_hash && si > 0 && pipe.stages[si - 1].kind == StageKind::bitswap1) {
-                        const uint64_t words = sqy::bitswap1_piece_hash_words(cur, cur, cur_len);     // (same count as when they were made)
-                        const uint64_t ph_bytes = (words * 4 + 63) & ~(uint64_t)63;
-                        uint8_t* base = static_cast<uint8_t*>(ws->dedupe.p) + ph_bytes;
-                        uint32_t* d_dup = reinterpret_cast<uint32_t*>(base + sqy::lz4_dedupe_work_bytes(lz4_nchunks));
-                        if (lz4_inplace) lz4_holes = reinterpret_cast<uint64_t*>(reinterpret_cast<uint8_t*>(d_dup) + ((lz4_nchunks * 4 + 7) & ~(uint64_t)7));
-                        ProfScope ps("lz4_dedupe", stream, pend);
-                        // frames in place (acceleration 1): only the key table is built here, the decision per chunk (byte compare, hole fill)
-                        // is the first thing the chunk's parse wavefront does (lz4_chunk_dedupe)
-                        fused_dedupe = lz4_inplace && lz4_accel == 1;
-                        SQY_HIP(sqy::launch_lz4_dedupe(cur, lz4_total, (uint32_t)lz4_chunk, lz4_piece_hash, base, d_dup, stream, lz4_in_stride, lz4_holes,
-                                                       dedupe_cleared, fused_dedupe ? &lz4_dedupe_args : nullptr));
-                        lz4_dup_of = d_dup;
-                        if (fused_dedupe && lz4_digest) { lz4_dedupe_args.digest = lz4_digest; lz4_dedupe_args.digest_stride = lz4_digest_stride; }
-                    }
-                    if (ws->plan.ensure((lz4_nchunks + 1) * sizeof(uint32_t))) return 1;
-                    uint32_t* d_redo = static_cast<uint32_t*>(ws->plan.p);       // chunks the first pass leaves to the dense batches
-                    {
-                        ProfScope ps("lz4_chunks", stream, pend);
-                        SQY_HIP(sqy::launch_lz4_chunks(cur, lz4_total, (uint32_t)lz4_chunk, static_cast<uint8_t*>(ws->lz4_scratch.p), lz4_stride,
-                                                       static_cast<uint32_t*>(ws->csize.p), lz4_nchunks, stream, lz4_frame_map, lz4_frame_bytes, d_redo,
-                                                       fused_dedupe ? nullptr : lz4_dup_of, lz4_in_stride, lz4_accel, dedupe_cleared,
-                                                       fused_dedupe ? &lz4_dedupe_args : nullptr));
-                    }
-                    auto dense_pass = [&](uint32_t n_redo) -> int {
-                        ProfScope ps("lz4_chunks_dense", stream, pend);
-                        SQY_HIP(sqy::launch_lz4_chunks_dense(cur, lz4_total, (uint32_t)lz4_chunk, static_cast<uint8_t*>(ws->lz4_scratch.p), lz4_stride,
-                                                             static_cast<uint32_t*>(ws->csize.p), d_redo, n_redo, stream, lz4_frame_map, lz4_frame_bytes,
-                                                             lz4_in_stride));
-                        return 0;
-                    };
-                    std::string hdr_prefix, hdr_suffix;
-                    if (lz4_inplace && !(fq && fq->every > 0)) sqy::header_pack_parts(elem_size, false, dims, pipe.name(), &hdr_prefix, &hdr_suffix);
-                    if (lz4_inplace && !hdr_prefix.empty() && hdr_prefix.size() + hdr_suffix.size() <= sqy::kLz4InplaceHeaderTextMax) {
-                        // Frames in place, ONE host round trip per call (round 4): frame scan + tail marks, the stored chunks in front of
-                        // the tail put aside, the gather and the sqy header are all queued behind the parse right away and take what
-                        // they need (where the stored tail begins, the payload size) from device memory; what the host has to know
-                        // comes back through pinned memory with the one synchronisation.  Only when the parse left chunks to the
-                        // dense pass (streams of short sequences: seldom on microscopy stacks) do these kernels return untouched --
-                        // they look at the list's counter -- and run again behind the dense pass.
-                        const unsigned char fd[2] = {0x40, (unsigned char)(st.lz4.block_id << 4)};
-                        const uint32_t hc = (sqy::xxh32(fd, 2, 0) >> 8) & 0xff;
-                        uint8_t* outb = static_cast<uint8_t*>(d_dst);
-                        volatile uint64_t* record = static_cast<volatile uint64_t*>(ws->pinned);
-                        // (round 6) scan, tail marks, gather and header are ONE kernel (lz4_inplace_tail_fused_kernel: no workgroup waits for
-                        // another; with calls in flight the five launches it replaces were 0.3 ms of a call's 2.4).  Only when stored chunks
-                        // sit in front of the stored tail -- their bodies lie where gathered frames go -- does it hand back (status 4) to the
-                        // separate kernels, which put those chunks aside first.
-                        const bool fused_tail = lz4_nchunks <= 65536;         // (a workgroup of the fused kernel owns at most 64 chunks)
-                        auto tail_separate = [&](const uint32_t* guard, bool scan_too) -> int {
-                            record[0] = 0;
-                            if (scan_too) {
-                                ProfScope ps("lz4_frame_scan", stream, pend);
-                                SQY_HIP(sqy::launch_lz4_frame_scan(static_cast<uint32_t*>(ws->csize.p), lz4_nchunks, lz4_total, (uint32_t)lz4_chunk,
-                                                                   static_cast<uint64_t*>(ws->frame_off.p), stream, nullptr, lz4_dup_of, lz4_tail_info, guard,
-                                                                   outb + inplace_t0 + 11, lz4_in_stride, fd[1], hc));
-                            }
-                            ProfScope ps("lz4_frame_gather", stream, pend);
-                            SQY_HIP(sqy::launch_lz4_inplace_tail(outb, inplace_t0, lz4_in_stride, lz4_total, (uint32_t)lz4_chunk, lz4_nchunks,
-                                                                 static_cast<uint8_t*>(ws->lz4_scratch.p), lz4_stride, static_cast<uint32_t*>(ws->csize.p),
-                                                                 static_cast<uint64_t*>(ws->frame_off.p), lz4_dup_of, lz4_tail_info, fd[1], hc,
-                                                                 hdr_prefix.data(), (uint32_t)hdr_prefix.size(), hdr_suffix.data(), (uint32_t)hdr_suffix.size(),
-                                                                 (uint32_t)elem_size, guard, const_cast<uint64_t*>(record), stream));
-                            return 0;
-                        };
-                        auto tail = [&](const uint32_t* guard) -> int {
-                            if (!fused_tail) return tail_separate(guard, true);
-                            record[0] = 0;
-                            ProfScope ps("lz4_inplace_tail", stream, pend);
-                            SQY_HIP(sqy::launch_lz4_inplace_tail_fused(outb, inplace_t0, lz4_in_stride, lz4_total, (uint32_t)lz4_chunk, lz4_nchunks,
-                                                                       static_cast<uint8_t*>(ws->lz4_scratch.p), lz4_stride, static_cast<uint32_t*>(ws->csize.p),
-                                                                       static_cast<uint64_t*>(ws->frame_off.p), lz4_dup_of, lz4_tail_info, fd[1], hc,
-                                                                       hdr_prefix.data(), (uint32_t)hdr_prefix.size(), hdr_suffix.data(),
-                                                                       (uint32_t)hdr_suffix.size(), (uint32_t)elem_size, guard, const_cast<uint64_t*>(record), stream));
-                            return 0;
-                        };
-                        if (tail(d_redo)) return 1;
-                        SQY_HIP(hipStreamSynchronize(stream));
-                        if (record[0] == 2) {
-                            if (dense_pass((uint32_t)record[6])) return 1;
-                            if (tail(nullptr)) return 1;
-                            SQY_HIP(hipStreamSynchronize(stream));
-                        }
-                        if (record[0] == 4) {                                  // stored chunks in front of the stored tail: put aside first
-                            if (tail_separate(nullptr, false)) return 1;
-                            SQY_HIP(hipStreamSynchronize(stream));
-                        }
-                        if (record[0] != 1) {
-                            std::fprintf(stderr, "[sqeazy]\t internal error: frames in place did not finish (status %llu)\n", (unsigned long long)record[0]);
-                            return 1;
-                        }
-                        inplace_done = true;
-                        inplace_blob_at = record[1]; inplace_blob_bytes = record[2]; payload_bytes = record[3];
-                        inplace_hdr_bytes = inplace_blob_bytes - payload_bytes;
-                        payload_is_lz4 = true;
-                        break;
-                    }
-                    SQY_HIP(hipMemcpyAsync(ws->pinned, d_redo, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-                    SQY_HIP(hipStreamSynchronize(stream));
-                    const uint32_t n_redo = *static_cast<uint32_t*>(ws->pinned);
-                    if (n_redo && dense_pass(n_redo)) return 1;
-                } else if (lz4_total) {
-                    // block-linked frames: the serial layout (nthreads == 1) or chunks that span several LZ4 blocks.  The table
-                    // of a frame is carried from block to block (lz4_utils.hpp:99-173): one wavefront walks each frame -- or, below, every
-                    // block is parsed at once from a guess of that table that is checked afterwards
-                    const sqy::Lz4Plan plan = sqy::lz4_plan_blocks(lz4_total, lz4_chunk, st.lz4.block_bytes(), serial);
-                    if (!plan.ok || plan.blocks.empty()) {
-                        std::fprintf(stderr, "[sqeazy]\t lz4: block layout not available on MI355X\n");
-                        return 1;
-                    }
-                    const uint64_t nblocks = plan.blocks.size(), nframes = plan.frame_first.size() - 1;
-                    const uint64_t blocks_bytes = nblocks * sizeof(sqy::Lz4Block), first_bytes = (nframes + 1) * sizeof(uint32_t);
-                    if (ws->plan.ensure(blocks_bytes + first_bytes)) return 1;
-                    sqy::Lz4Block* d_blocks = static_cast<sqy::Lz4Block*>(ws->plan.p);
-                    uint32_t* d_first = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(ws->plan.p) + blocks_bytes);
-                    SQY_HIP(hipMemcpyAsync(d_blocks, plan.blocks.data(), blocks_bytes, hipMemcpyHostToDevice, stream));
-                    SQY_HIP(hipMemcpyAsync(d_first, plan.frame_first.data(), first_bytes, hipMemcpyHostToDevice, stream));
-                    lz4_stride = ((uint64_t)plan.max_block + 15) & ~(uint64_t)15;
-                    if (ws->lz4_scratch.ensure(std::max<uint64_t>(nblocks * lz4_stride, 16))) return 1;
-                    if (ws->csize.ensure(nblocks * sizeof(uint32_t))) return 1;
-                    if (ws->frame_off.ensure((nblocks + 1) * sizeof(uint64_t))) return 1;
-                    // Few long frames (the serial layout above all): block-parallel.  Every block is parsed by its own wavefront from
-                    // a table rebuilt by parsing the >= 64 KiB in front of it, the tables are checked against what the block in
-                    // front really left, and what fails the check is parsed again in order (sqy_kernels.h: Lz4SpecArgs).  Twice the
-                    // parse work on thousands of wavefronts instead of one: worth it when the frame walks would leave the chip empty.
-                    uint64_t longest = 0;
-                    for (uint64_t f = 0; f < nframes; ++f) longest = std::max<uint64_t>(longest, plan.frame_first[f + 1] - plan.frame_first[f]);
-                    // measurement / test knobs: SQY_NO_BLOCK_PARALLEL (the frame walk of rounds 2-3), SQY_BLOCK_PARALLEL_WARMUP = bytes
-                    // of warm-up in front of a block (default and liblz4's reach: 64 KiB; less makes the guess fail more often --
-                    // the result stays exact, the blocks that fail are parsed again)
-                    const bool spec_off = g_opt.block_parallel.load() == 0;
-                    const uint64_t warmup = (uint64_t)g_opt.block_parallel_warmup.load();
-                    const uint64_t list_bytes = nblocks * sizeof(uint32_t);
-                    // (without room for the tables -- 32 KiB per block -- the walk, which needs none)
-                    const bool spec_wanted = !spec_off && longest >= 3 && nframes < 1024;
-                    const bool spec_room = spec_wanted && !ws->spec.ensure(nblocks * sqy::kLz4SpecTableWords * sizeof(uint32_t) + 3 * list_bytes, true);
-                    if (spec_wanted && !spec_room) {
-                        // (round-4 advice) said once, not per call: the result is the same, the rate is not
-                        static std::atomic<bool> told{false};
-                        if (!told.exchange(true))
-                            std::fprintf(stderr, "[sqeazy]\t lz4: no HBM for the block-parallel parse's tables (%llu MiB): block-linked frames are walked by one "
-                                                 "wavefront each (same bytes, hundreds of times slower on long frames)\n",
-                                         (unsigned long long)((nblocks * sqy::kLz4SpecTableWords * sizeof(uint32_t)) >> 20));
-                    }
-                    if (spec_room) {
-                        std::vector<uint32_t> wfirst(nblocks), wlast(nblocks), ok(nblocks);
-                        for (uint64_t f = 0; f < nframes; ++f)
-                            for (uint32_t k = plan.frame_first[f]; k < plan.frame_first[f + 1]; ++k) {
-                                uint32_t j = k;
-                                uint64_t have = 0;
-                                while (j > plan.frame_first[f] && have < warmup) { --j; have += plan.blocks[j].n; }
-                                wfirst[k] = j; wlast[k] = (uint32_t)k;
-                            }
-                        sqy::Lz4SpecArgs sa;
-                        sa.tables = static_cast<uint32_t*>(ws->spec.p);
-                        uint32_t* d_wfirst = sa.tables + nblocks * sqy::kLz4SpecTableWords;
-                        uint32_t* d_wlast = d_wfirst + nblocks;
-                        uint32_t* d_ok = d_wlast + nblocks;
-                        sa.wave_first = d_wfirst; sa.wave_last = d_wlast; sa.mode = 1;
-                        SQY_HIP(hipMemcpyAsync(d_wfirst, wfirst.data(), list_bytes, hipMemcpyHostToDevice, stream));
-                        SQY_HIP(hipMemcpyAsync(d_wlast, wlast.data(), list_bytes, hipMemcpyHostToDevice, stream));
-                        {
-                            ProfScope ps("lz4_linked_blocks", stream, pend);
-                            SQY_HIP(sqy::launch_lz4_linked_spec(cur, d_blocks, sa, nblocks, plan.max_block, static_cast<uint8_t*>(ws->lz4_scratch.p),
-                                                                lz4_stride, static_cast<uint32_t*>(ws->csize.p), stream, lz4_accel));
-                        }
-                        for (uint64_t round = 0;; ++round) {
-                            {
-                                ProfScope ps("lz4_linked_verify", stream, pend);
-                                SQY_HIP(sqy::launch_lz4_linked_verify(d_blocks, nblocks, sa.tables, plan.max_block, d_ok, stream));
-                            }
-                            SQY_HIP(hipMemcpyAsync(ok.data(), d_ok, list_bytes, hipMemcpyDeviceToHost, stream));
-                            SQY_HIP(hipStreamSynchronize(stream));
-                            // runs of blocks that did not start from the true table: one wavefront each, in order, from the table in front
-                            // (round-5 advice) a run is parsed by ONE wavefront, block after block: at most kRunMax blocks of it per launch (the
-                            // rest keep failing the check and are taken by the next rounds, each from the table the last one left) -- the top
-                            // plane of a quantised stack fails as one run of 511 blocks, seconds of work: sixteen launches of a fraction of a
-                            // second instead of one kernel that runs for seconds; and the caller is told, once, what layout to ask for.
-                            constexpr uint64_t kRunMax = 32;
-                            uint64_t nruns = 0, longest_run = 0;
-                            for (uint64_t k = 0; k < nblocks; ++k) {
-                                if (ok[k]) continue;
-                                uint64_t e = k;
-                                while (e + 1 < nblocks && !ok[e + 1] && !(plan.blocks[e + 1].flags & 1u)) ++e;
-                                longest_run = std::max(longest_run, e - k + 1);
-                                wfirst[nruns] = (uint32_t)k; wlast[nruns] = (uint32_t)std::min(e, k + kRunMax - 1); ++nruns;
-                                k = e;
-                            }
-                            if (longest_run > 4 * kRunMax) {
-                                static std::atomic<bool> told{false};
-                                if (!told.exchange(true))
-                                    std::fprintf(stderr, "[sqeazy]\t lz4: %llu blocks in a row of this block-linked frame (nthreads = 1) can only be parsed one after "
-                                                         "the other -- a stream of short sequences, whose table no guess reproduces -- by one wavefront, "
-                                                         "~10 ms per block.  The chunked layout (nthreads = 0 or > 1: independent frames, same decoder) "
-                                                         "takes milliseconds for the same data.\n", (unsigned long long)longest_run);
-                            }
-                            if (g_opt.block_parallel_stats.load()) {
-                                uint64_t nbad = 0;
-                                for (uint64_t r = 0; r < nruns; ++r) nbad += wlast[r] - wfirst[r] + 1;
-                                std::fprintf(stderr, "[sqeazy]\t lz4 block-parallel: round %llu, %llu of %llu blocks to parse again in %llu runs",
-                                             (unsigned long long)round, (unsigned long long)nbad, (unsigned long long)nblocks, (unsigned long long)nruns);
-                                for (uint64_t r = 0; r < nruns && r < 24; ++r) std::fprintf(stderr, "%s%u..%u", r ? ", " : ": blocks ", wfirst[r], wlast[r]);
-                                std::fprintf(stderr, "\n");
-                            }
-                            if (nruns == 0) break;
-                            if (round > nblocks + 8) {
-                                std::fprintf(stderr, "[sqeazy]\t lz4: the block-parallel parse did not settle\n");
-                                return 1;
-                            }
-                            SQY_HIP(hipMemcpyAsync(d_wfirst, wfirst.data(), nruns * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-                            SQY_HIP(hipMemcpyAsync(d_wlast, wlast.data(), nruns * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-                            sa.mode = 2;
-                            ProfScope ps("lz4_linked_redo", stream, pend);
-                            SQY_HIP(sqy::launch_lz4_linked_spec(cur, d_blocks, sa, nruns, plan.max_block, static_cast<uint8_t*>(ws->lz4_scratch.p),
-                                                                lz4_stride, static_cast<uint32_t*>(ws->csize.p), stream, lz4_accel));
-                            SQY_HIP(hipStreamSynchronize(stream));         // (wfirst / wlast are reused by the next round)
-                        }
-                    } else {
-                        ProfScope ps("lz4_linked", stream, pend);
-                        SQY_HIP(sqy::launch_lz4_linked(cur, d_blocks, d_first, nframes, plan.max_block, static_cast<uint8_t*>(ws->lz4_scratch.p),
-                                                       lz4_stride, static_cast<uint32_t*>(ws->csize.p), stream, lz4_accel));
-                    }
-                    SQY_HIP(hipStreamSynchronize(stream));                 // `plan` (host) is read by the async copies above
-                    lz4_blocks = d_blocks;
-                    lz4_nchunks = nblocks;                                  // scan and gather work per block from here on
-                    lz4_chunk = plan.max_block;
-                }
-                {
-                    ProfScope ps("lz4_frame_scan", stream, pend);
-                    SQY_HIP(sqy::launch_lz4_frame_scan(static_cast<uint32_t*>(ws->csize.p), lz4_nchunks, lz4_total, (uint32_t)lz4_chunk,
-                                                       static_cast<uint64_t*>(ws->frame_off.p), stream, lz4_blocks, lz4_dup_of, lz4_tail_info));
-                }
-                payload_is_lz4 = true;
-                break;
-            }
-            default:
-                std::fprintf(stderr, "[sqeazy]\t stage %s is not implemented on MI355X\n", st.name.c_str());
-                return 1;
-        }
-    }
-
-    if (inplace_done) {
-        if (payload_bytes > (uint64_t)INT_MAX) {
-            std::fprintf(stderr, "[sqeazy]\t lz4: %llu payload bytes overflow the reference's int byte count\n", (unsigned long long)payload_bytes);
-            return 1;
-        }
-        if (g_prof_on.load()) prof_collect(cx.pending);
-        *dstoffset = (long)inplace_blob_at;
-        *dstlength = (long)inplace_blob_bytes;
-        (void)inplace_hdr_bytes;
-        return 0;
-    }
-    // ---- payload size ----
-    uint64_t tail_j = 0, tail_head_bytes = 0, tail_raw_head = 0;
-    if (payload_is_lz4) {
-        if (lz4_nchunks == 0) {
-            payload_bytes = 7 + 4;                     // empty input: frame header + end mark
-        } else if (lz4_inplace) {
-            SQY_HIP(hipMemcpyAsync(ws->pinned, lz4_tail_info, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
-            SQY_HIP(hipStreamSynchronize(stream));
-            const uint64_t* ti = static_cast<const uint64_t*>(ws->pinned);
-            tail_j = ti[0]; tail_head_bytes = ti[1]; tail_raw_head = ti[2]; payload_bytes = ti[3];
-        } else {
-            SQY_HIP(hipMemcpyAsync(ws->pinned, static_cast<uint64_t*>(ws->frame_off.p) + lz4_nchunks, sizeof(uint64_t),
-                                   hipMemcpyDeviceToHost, stream));
-            SQY_HIP(hipStreamSynchronize(stream));
-            payload_bytes = *static_cast<uint64_t*>(ws->pinned);
-        }
-        if (payload_bytes > (uint64_t)INT_MAX) {
-            // encode_parallel sums the chunk sizes into an `int` and rejects the result (lz4_utils.hpp:264-273)
-            std::fprintf(stderr, "[sqeazy]\t lz4: %llu payload bytes overflow the reference's int byte count\n",
-                         (unsigned long long)payload_bytes);
-            return 1;
-        }
-    } else {
-        payload_bytes = cur_len * (uint64_t)cur_elem;
-    }
-
-    // ---- header (written after encoding, as the reference rewrites it: dynamic_pipeline.hpp:599-612) ----
-    const std::string hdr = sqy::header_pack(elem_size, false, dims, pipe.name(), payload_bytes);
-    if (fq && fq->every > 0) {
-        if (!payload_is_lz4 || lz4_blocks || !fq->offsets) { std::fprintf(stderr, "[sqeazy]\t frame offsets: the payload is not one LZ4 frame per chunk\n"); return 1; }
-        const uint64_t cnt = (lz4_nchunks + (uint64_t)fq->every - 1) / (uint64_t)fq->every;
-        if (cnt + 1 > (uint64_t)std::max(fq->max_entries, 0)) { std::fprintf(stderr, "[sqeazy]\t frame offsets: %llu entries do not fit\n", (unsigned long long)(cnt + 1)); return 1; }
-        std::vector<uint64_t> fo(cnt + 1, 0);
-        if (cnt)
-            SQY_HIP(hipMemcpy2DAsync(fo.data(), sizeof(uint64_t), ws->frame_off.p, (size_t)fq->every * sizeof(uint64_t), sizeof(uint64_t), cnt,
-                                     hipMemcpyDeviceToHost, stream));
-        SQY_HIP(hipStreamSynchronize(stream));
-        for (uint64_t i = 0; i < cnt; ++i) fq->offsets[i] = (long)(fo[i] + hdr.size());
-        fq->offsets[cnt] = (long)(hdr.size() + payload_bytes);
-        fq->count = (int)cnt;
-    }
-    const uint64_t blob_bytes = hdr.size() + payload_bytes;
-    if (blob_bytes > dst_capacity) {
-        std::fprintf(stderr, "[sqeazy]\t destination buffer too small (%llu > %llu bytes)\n", (unsigned long long)blob_bytes,
-                     (unsigned long long)dst_capacity);
+    const uint64_t len = voxel_count(shape, rank);
+    if (len == 0) { std::fprintf(stderr, "[sqeazy]\t non-positive extent in shape\n"); return 1; }
+    if (len >= ((uint64_t)1 << 31)) {
+        std::fprintf(stderr, "[sqeazy]\t %llu+ voxels in one call overflow the reference's int voxel count; encode z-slabs\n", (unsigned long long)len);
         return 1;
     }
-    uint8_t* out = static_cast<uint8_t*>(d_dst);
-    if (lz4_inplace) {
-        // the run of stored chunks j.. that ends the payload stays where the bit-plane transpose put it; frames 0..j-1 are
-        // gathered so that they end where frame j begins, the header goes in front of them
-        const uint64_t frame_j = inplace_t0 + tail_j * lz4_in_stride;
-        if (tail_head_bytes + hdr.size() > frame_j) { std::fprintf(stderr, "[sqeazy]\t internal error: frames in place overlap the header\n"); return 1; }
-        const uint64_t payload_at = frame_j - tail_head_bytes, blob_at = payload_at - hdr.size();
-        const unsigned char fd[2] = {0x40, (unsigned char)(lz4p->block_id << 4)};
-        const uint32_t hc = (sqy::xxh32(fd, 2, 0) >> 8) & 0xff;
-        uint8_t* body0 = out + inplace_t0 + 11;
-        {
-            ProfScope ps("lz4_tail_marks", stream, pend);
-            SQY_HIP(sqy::launch_lz4_tail_marks(body0, lz4_in_stride, lz4_total, (uint32_t)lz4_chunk, lz4_nchunks, fd[1], hc, lz4_tail_info, stream));
+    std::vector<uint64_t> dims(shape, shape + rank);
+    if (!background_geometry_ok(pipe, dims)) return 1;
+
+    DrainOnExit drain{stream, &cx.pending, cx.side};
+    EncodeCall c(cx, stream, std::move(pipe), std::move(dims), len, elem_size, d_src, d_dst, dst_capacity, dstoffset, fq);
+    for (size_t si = 0; si < c.pipe.stages.size(); ++si) {
+        int rc = 0;
+        switch (c.pipe.stages[si].kind) {
+            case StageKind::bitswap1:          rc = c.bitswap1(si); break;
+            case StageKind::raster_reorder:    rc = c.reorder(si, false); break;
+            case StageKind::zcurve_reorder:    rc = c.reorder(si, true); break;
+            case StageKind::rmestbkrd:         rc = c.rmestbkrd(); break;
+            case StageKind::rmbkrd_neighbor5:  rc = c.rmbkrd_neighbor5(si); break;
+            case StageKind::bitshuffle:        rc = c.bitshuffle(si); break;
+            case StageKind::tile_shuffle:      rc = c.tile_shuffle(si); break;
+            case StageKind::diff3x3x1:         rc = c.diff3x3x1(si); break;
+            case StageKind::frame_shuffle:     rc = c.frame_shuffle(si); break;
+            case StageKind::quantiser:         rc = c.quantiser(si); break;        // (may do the bitswap1 behind it as well)
+            case StageKind::lz4:               rc = c.lz4_stage(si); break;
+            case StageKind::pass_through:      rc = c.pass_through(); break;
+            default:
+                std::fprintf(stderr, "[sqeazy]\t stage %s is not implemented on MI355X\n", c.pipe.stages[si].name.c_str());
+                return 1;
         }
-        if (tail_raw_head) {
-            ProfScope ps("lz4_stash_raw", stream, pend);
-            SQY_HIP(sqy::launch_lz4_stash_raw(body0, lz4_in_stride, lz4_total, (uint32_t)lz4_chunk, static_cast<uint8_t*>(ws->lz4_scratch.p), lz4_stride,
-                                              static_cast<uint32_t*>(ws->csize.p), lz4_dup_of, tail_j, stream));
-        }
-        if (tail_j) {
-            ProfScope ps("lz4_frame_gather", stream, pend);
-            SQY_HIP(sqy::launch_lz4_frame_gather(body0, lz4_total, (uint32_t)lz4_chunk, static_cast<uint8_t*>(ws->lz4_scratch.p), lz4_stride,
-                                                 static_cast<uint32_t*>(ws->csize.p), static_cast<uint64_t*>(ws->frame_off.p), out + payload_at, fd[1], hc,
-                                                 tail_j, stream, nullptr, 0, nullptr, lz4_dup_of, lz4_in_stride, tail_raw_head != 0));
-        }
-        SQY_HIP(hipMemcpyAsync(out + blob_at, hdr.data(), hdr.size(), hipMemcpyHostToDevice, stream));
-        SQY_HIP(hipStreamSynchronize(stream));
-        if (g_prof_on.load()) prof_collect(cx.pending);
-        *dstoffset = (long)blob_at;
-        *dstlength = (long)blob_bytes;
-        return 0;
+        if (rc) return rc;
     }
-    SQY_HIP(hipMemcpyAsync(out, hdr.data(), hdr.size(), hipMemcpyHostToDevice, stream));
-    if (payload_is_lz4) {
-        const unsigned char fd[2] = {0x40, (unsigned char)(lz4p->block_id << 4)};
-        const uint32_t hc = (sqy::xxh32(fd, 2, 0) >> 8) & 0xff;
-        if (lz4_nchunks == 0) {
-            const unsigned char empty[11] = {0x04, 0x22, 0x4D, 0x18, fd[0], fd[1], (unsigned char)hc, 0, 0, 0, 0};
-            SQY_HIP(hipMemcpyAsync(out + hdr.size(), empty, sizeof(empty), hipMemcpyHostToDevice, stream));
-        } else {
-            ProfScope ps("lz4_frame_gather", stream, pend);
-            SQY_HIP(sqy::launch_lz4_frame_gather(cur, lz4_total, (uint32_t)lz4_chunk, static_cast<uint8_t*>(ws->lz4_scratch.p), lz4_stride,
-                                                 static_cast<uint32_t*>(ws->csize.p), static_cast<uint64_t*>(ws->frame_off.p),
-                                                 out + hdr.size(), fd[1], hc, lz4_nchunks, stream, lz4_frame_map, lz4_frame_bytes, lz4_blocks, lz4_dup_of));
-        }
-    } else {
-        ProfScope ps("payload_copy", stream, pend);
-        SQY_HIP(hipMemcpyAsync(out + hdr.size(), cur, payload_bytes, hipMemcpyDeviceToDevice, stream));
-    }
-    SQY_HIP(hipStreamSynchronize(stream));
-    if (g_prof_on.load()) prof_collect(cx.pending);
-    *dstlength = (long)blob_bytes;
-    (void)raw_bytes;
-    return 0;
+    return c.finish(dstlength);
 }
 
 // dst_capacity < 0: the caller followed the reference protocol and allocated SQY_Pipeline_Max_Compressed_Length bytes
@@ -1277,12 +1283,8 @@ int encode_from_host(const char* pipeline, const char* src, long* shape, unsigne
     Workspace* ws = &lease.ctx->ws;
     hipStream_t stream = lease.ctx->own_stream();
     if (!stream) { std::fprintf(stderr, "[sqeazy]\t no HIP stream\n"); return 1; }
-    uint64_t len = 1;
-    for (unsigned i = 0; i < rank; ++i) {
-        if (shape[i] <= 0) return 1;
-        len *= (uint64_t)shape[i];
-        if (len >= ((uint64_t)1 << 31)) break;
-    }
+    const uint64_t len = voxel_count(shape, rank);
+    if (len == 0) return 1;
     if (len >= ((uint64_t)1 << 31)) {
         std::fprintf(stderr, "[sqeazy]\t 2^31 or more voxels in one call overflow the reference's int voxel count; encode z-slabs\n");
         return 1;
@@ -1311,7 +1313,7 @@ int encode_from_host(const char* pipeline, const char* src, long* shape, unsigne
 // ---- decode --------------------------------------------------------------------------------------
 // dynamic_pipeline::decode (dynamic_pipeline.hpp:740-846): tail filters^-1, sink^-1, head filters^-1 in reverse.
 // the quantiser's decode LUT (256 x u16, base64 in the header) into ws->small; synchronous: the host copy does not outlive the call
-int quantiser_lut_to_device(const sqy::Stage& st, Workspace* ws, hipStream_t stream)
+int quantiser_lut_to_device(const sqy::Stage& st, Workspace* ws)
 {
     std::vector<unsigned char> lut;
     auto lp = st.cfg.find("decode_lut_path");
@@ -1324,14 +1326,11 @@ int quantiser_lut_to_device(const sqy::Stage& st, Workspace* ws, hipStream_t str
         }
     } else {
         auto it = st.cfg.find("decode_lut_string");
-        if (it == st.cfg.end() || it->second.size() < 21) { std::fprintf(stderr, "[sqeazy]\t quantiser: no decode_lut_string in the header\n"); return 1; }
-        const std::string b64 = it->second.substr(10, it->second.size() - 21);   // strip <verbatim> ... </verbatim>
-        lut = sqy::base64_decode(b64);
+        if (it == st.cfg.end() || !sqy::from_verbatim(it->second, &lut)) { std::fprintf(stderr, "[sqeazy]\t quantiser: no decode_lut_string in the header\n"); return 1; }
     }
     if (lut.size() != 512) { std::fprintf(stderr, "[sqeazy]\t quantiser: malformed decode LUT\n"); return 1; }
     if (ws->small.ensure(4096)) return 1;
     SQY_HIP(hipMemcpy(ws->small.p, lut.data(), 512, hipMemcpyHostToDevice));
-    (void)stream;
     return 0;
 }
 
@@ -1353,120 +1352,109 @@ bool header_shape_ok(const sqy::HeaderInfo& h, uint64_t srclen, uint64_t* raw_by
     return true;
 }
 
-int decode_on_device(Context& cx, const void* d_src_v, uint64_t srclen, void* d_dst, uint64_t dst_capacity, int want_elem, hipStream_t stream)
-{
-    if (!d_src_v || !d_dst) return 1;
-    const uint8_t* d_src = static_cast<const uint8_t*>(d_src_v);
-    Workspace* ws = &cx.ws;
-    std::vector<PendingEvent>* pend = &cx.pending;
-    DrainOnExit drain{stream, pend, cx.side};
+// Where the frames and blocks of an LZ4 payload are (lz4_frame_rank / lz4_frame_index), in ws->lz4_scratch and ws->csize
+struct Lz4Index {
+    uint64_t chunk = 0, nchunks = 0, block_bytes = 0;
+    uint8_t* blk = nullptr;
+    uint32_t* frame_first = nullptr;
+    uint32_t* counts = nullptr;                  // [0..3] index result, [4] decode error flag
+    uint32_t hc[8] = {0, 0, 100, 0, 0, 0, 0, 0}; // the index result read back: [0] frames, [1] blocks, [2] error code (100: not covered)
+};
+// frame_shuffle's inverse folded into the LZ4 decode: frames go to remap[f] * bytes (zero: the places no map entry names are zeroed first)
+struct Lz4Remap { const uint64_t* map = nullptr; uint64_t bytes = 0; bool zero = false; };
 
-    // header: fetch a prefix of the blob, grow until the delimiter is inside
-    std::vector<char> head;
-    sqy::HeaderInfo h;
-    for (uint64_t want = 1 << 16;; want *= 16) {
-        const uint64_t take = std::min<uint64_t>(want, srclen);
-        head.resize(take);
-        SQY_HIP(hipMemcpyAsync(head.data(), d_src, take, hipMemcpyDeviceToHost, stream));
-        SQY_HIP(hipStreamSynchronize(stream));
-        h = sqy::header_unpack(head.data(), head.data() + take);
-        if (h.valid || take == srclen) break;
-    }
-    if (!h.valid) { std::fprintf(stderr, "[sqeazy]\t unable to find a sqy header in the blob\n"); return 1; }
-    const int elem = h.elem_size();
-    if (elem != want_elem) { std::fprintf(stderr, "[sqeazy]\t blob holds %s voxels\n", h.type.c_str()); return 1; }
-    std::string why;
-    if (!Pipeline::supported(h.pipename, elem, &why)) {
-        std::fprintf(stderr, "[sqeazy]\t%s cannot be build with this version of sqeazy (%s)\n", h.pipename.c_str(), why.c_str());
-        return 1;
-    }
-    Pipeline pipe = Pipeline::from_string(h.pipename);
-    // the header is untrusted input: every extent positive, the voxel count below 2^31 (what one encode call can have
-    // produced), no wrap-around anywhere
-    uint64_t raw_bytes = 0;
-    if (!header_shape_ok(h, srclen, &raw_bytes)) return 1;
-    const uint64_t n = raw_bytes / (uint64_t)elem;
-    if (raw_bytes > dst_capacity) {
-        std::fprintf(stderr, "[sqeazy]\t decode: buffer too small or blob truncated\n");
-        return 1;
-    }
-    // composite return codes of dynamic_pipeline::detail_decode (dynamic_pipeline.hpp:795-846): a failing tail filter
-    // returns its code, a failing sink code + 10, a failing head filter code + 100
-    const int sink_index = pipe.sink_index;
-    auto stage_error = [&](size_t si) -> int {
-        if (sink_index >= 0 && (int)si > sink_index) return 1;
-        if (sink_index >= 0 && (int)si == sink_index) return 1 + 10;
-        return 1 + 100;
-    };
-    // element size of the stream in front of every stage (the quantiser sink turns it into bytes)
+// One decode call: the blob's header, the stream between the inverses, and what they hand each other.
+struct DecodeCall {
+    Context& cx;
+    Workspace* ws;
+    std::vector<PendingEvent>* pend;
+    hipStream_t stream;
+    void* d_dst;
+    const sqy::HeaderInfo& h;
+    Pipeline pipe;
+    uint64_t n;                          // voxels
+    // element size and count of the stream in front of every stage on the ENCODER's side: what its inverse produces
     // (the quantiser maps every voxel to one byte; pass_through re-types the voxels: elem times as many one-byte elements)
-    std::vector<int> elem_before(pipe.stages.size());
-    std::vector<uint64_t> count_before(pipe.stages.size());
-    {
-        int e = elem;
-        uint64_t c = n;
-        for (size_t i = 0; i < pipe.stages.size(); ++i) {
-            elem_before[i] = e;
-            count_before[i] = c;
-            if (pipe.stages[i].kind == StageKind::quantiser) e = 1;
-            if (pipe.stages[i].kind == StageKind::pass_through) { c *= (uint64_t)e; e = 1; }
-        }
-    }
-    const uint8_t* cur = d_src + h.size;
-    uint64_t cur_bytes = h.payload_bytes;
+    std::vector<int> elem_before;
+    std::vector<uint64_t> count_before;
+    // the background filters decode as a copy (remove_estimated_background_scheme_impl.hpp:125-150, flatten_to_neighborhood_scheme_impl.hpp
+    // :152-178): behind `lead` of them at the pipeline's front, stage `lead`'s inverse produces the volume
+    size_t lead = 0;
+
+    // the stream between the inverses
+    const uint8_t* cur;
+    uint64_t cur_bytes;
     bool use_ping = true;
     bool diff_in_place = false;            // the bit-plane inverse wrote into the volume itself; the diff3x3x1 inverse works there
     const uint32_t* lz4_flag = nullptr;    // the LZ4 decoder's error flag, read when the call ends
     int lz4_flag_stage = 0;
-    // the background filters decode as a copy (remove_estimated_background_scheme_impl.hpp:125-150, flatten_to_neighborhood_scheme_impl.hpp
-    // :152-178): behind `lead` of them at the pipeline's front, stage `lead`'s inverse produces the volume
-    size_t lead = 0;
-    while (lead < pipe.stages.size() && (pipe.stages[lead].kind == StageKind::rmestbkrd || pipe.stages[lead].kind == StageKind::rmbkrd_neighbor5)) ++lead;
-    auto out_buf = [&](size_t stage_index, uint64_t bytes) -> uint8_t* {
-        if (stage_index <= lead) return static_cast<uint8_t*>(d_dst);            // the first stage's inverse produces the volume
+    // frame_shuffle's inverse: the reorder map out of the header (alive until the call's last synchronisation), and the places no map
+    // entry names (maps that are no permutation)
+    std::vector<unsigned char> fs_map;
+    std::vector<uint64_t> fs_unnamed;
+
+    DecodeCall(Context& c, hipStream_t s, void* dst, const sqy::HeaderInfo& hi, Pipeline&& p, uint64_t voxels, const uint8_t* payload)
+        : cx(c), ws(&c.ws), pend(&c.pending), stream(s), d_dst(dst), h(hi), pipe(std::move(p)), n(voxels), elem_before(pipe.stages.size()), count_before(pipe.stages.size()), cur(payload), cur_bytes(hi.payload_bytes)
+    {
+        int e = h.elem_size();
+        uint64_t cnt = n;
+        for (size_t i = 0; i < pipe.stages.size(); ++i) {
+            elem_before[i] = e;
+            count_before[i] = cnt;
+            if (pipe.stages[i].kind == StageKind::quantiser) e = 1;
+            if (pipe.stages[i].kind == StageKind::pass_through) { cnt *= (uint64_t)e; e = 1; }
+        }
+        while (lead < pipe.stages.size() && (pipe.stages[lead].kind == StageKind::rmestbkrd || pipe.stages[lead].kind == StageKind::rmbkrd_neighbor5)) ++lead;
+    }
+
+    // composite return codes of dynamic_pipeline::detail_decode (dynamic_pipeline.hpp:795-846): a failing tail filter
+    // returns its code, a failing sink code + 10, a failing head filter code + 100
+    int stage_error(size_t si) const { return is_tail(si) ? 1 : (int)si == pipe.sink_index ? 1 + 10 : 1 + 100; }
+    int produced(const uint8_t* out, uint64_t bytes) { cur = out; cur_bytes = bytes; return 0; }   // the next inverse's input
+    bool is_tail(size_t si) const { return pipe.sink_index >= 0 && (int)si > pipe.sink_index; }
+    bool preceded_by(size_t si, StageKind k) const { return si >= 1 && pipe.stages[si - 1].kind == k; }
+    uint64_t in_bytes(size_t si) const { return count_before[si] * (uint64_t)elem_before[si]; }   // bytes the inverse has to produce
+    uint8_t* work_buf(uint64_t bytes)                                  // the next buffer of the ping/pong rotation
+    {
         DevBuf& b = use_ping ? ws->ping : ws->pong;
         use_ping = !use_ping;
-        if (b.ensure(std::max<uint64_t>(bytes, 16))) return nullptr;
-        return static_cast<uint8_t*>(b.p);
-    };
-
+        return b.ensure(std::max<uint64_t>(bytes, 16)) ? nullptr : static_cast<uint8_t*>(b.p);
+    }
+    // the first stage's inverse produces the volume
+    uint8_t* out_buf(size_t stage_index, uint64_t bytes) { return stage_index <= lead ? static_cast<uint8_t*>(d_dst) : work_buf(bytes); }
     // the shape a 3-D stage saw on the encoder's side (h.shape.size() == 3 checked by the caller): the volume's, or {1, 1, bytes} behind
     // a sink that did not write one byte per voxel (dynamic_pipeline.hpp:658-666)
-    auto stage_shape = [&](size_t si, uint64_t n_in, uint64_t& Z, uint64_t& Y, uint64_t& X) {
-        const bool flat = sink_index >= 0 && (int)si > sink_index && n_in != n;
-        Z = flat ? 1 : h.shape[0]; Y = flat ? 1 : h.shape[1]; X = flat ? n_in : h.shape[2];
-    };
+    void stage_shape(size_t si, uint64_t& Z, uint64_t& Y, uint64_t& X) const
+    {
+        const bool flat = is_tail(si) && count_before[si] != n;
+        Z = flat ? 1 : h.shape[0]; Y = flat ? 1 : h.shape[1]; X = flat ? count_before[si] : h.shape[2];
+    }
 
-    // frame_shuffle's inverse: the reorder map out of the header, checked and sent to the device (ws->small).  Used by the stage itself and
-    // by the LZ4 stage behind it, which decodes its frames straight to their places when it can (round 5).
-    std::vector<unsigned char> fs_map;                                          // (alive until the call's last synchronisation)
-    std::vector<uint64_t> fs_unnamed;                                           // places no map entry names (maps that are no permutation)
     // zeros where nobody writes: the places the map does not name (round 6: not the whole volume -- the C4 stack's map leaves a few of its
     // 1024 places out, and clearing 1 GiB for them was 0.25 of the decode's 0.85 ms)
-    auto zero_unnamed_places = [&](uint8_t* out, uint64_t place_bytes, uint64_t bytes) -> int {
+    int zero_unnamed_places(uint8_t* out, uint64_t place_bytes, uint64_t bytes)
+    {
         // (a memset's launch costs about what 25 MB of it cost the memory)
         if (fs_unnamed.size() * (place_bytes + (25ull << 20)) >= bytes) { SQY_HIP(hipMemsetAsync(out, 0, bytes, stream)); return 0; }
         for (uint64_t v : fs_unnamed) SQY_HIP(hipMemsetAsync(out + v * place_bytes, 0, place_bytes, stream));
         return 0;
-    };
-    auto frame_shuffle_prepare = [&](size_t fi, uint64_t& Z, uint64_t& frame_bytes_dec, bool& permutation) -> int {
+    }
+
+    // frame_shuffle's inverse: the reorder map out of the header, checked and sent to the device (ws->small).  Used by the stage itself and
+    // by the LZ4 stage behind it, which decodes its frames straight to their places when it can (round 5).
+    int frame_shuffle_prepare(size_t fi, uint64_t& Z, uint64_t& frame_bytes_dec, bool& permutation)
+    {
         const Stage& fs = pipe.stages[fi];
-        const uint64_t fs_n = count_before[fi], fs_bytes = fs_n * (uint64_t)elem_before[fi];
         if (h.shape.size() != 3) return 1;
         auto it = fs.cfg.find("reorder_map");
         // (as a tail filter behind a sink that did not write one byte per voxel the stream is ONE frame: {1, 1, bytes})
-        const bool one_frame = sink_index >= 0 && (int)fi > sink_index && fs_n != n;
-        uint64_t fcs = 1;
-        {
-            auto c = fs.cfg.find("frame_chunk_size");
-            if (c != fs.cfg.end()) fcs = (uint64_t)std::max(std::atoi(c->second.c_str()), 0);
-        }
-        const uint64_t Z0 = one_frame ? 1 : h.shape[0];
+        const uint64_t fcs = frame_chunk_size(fs);
+        uint64_t Z0, Y, X;
+        stage_shape(fi, Z0, Y, X);
         if (fcs == 0 || Z0 % fcs != 0) { std::fprintf(stderr, "[sqeazy]\t frame_shuffle: frame_chunk_size does not divide the frames\n"); return 1; }
         Z = Z0 / fcs;
-        frame_bytes_dec = (one_frame ? fs_bytes : h.shape[1] * h.shape[2] * (uint64_t)elem_before[fi]) * fcs;
-        if (it == fs.cfg.end() || it->second.size() < 21) { std::fprintf(stderr, "[sqeazy]\t frame_shuffle: no reorder_map in the header\n"); return 1; }
-        fs_map = sqy::base64_decode(it->second.substr(10, it->second.size() - 21));
+        frame_bytes_dec = Y * X * (uint64_t)elem_before[fi] * fcs;
+        if (it == fs.cfg.end() || !sqy::from_verbatim(it->second, &fs_map)) { std::fprintf(stderr, "[sqeazy]\t frame_shuffle: no reorder_map in the header\n"); return 1; }
         if (fs_map.size() != Z * 8) { std::fprintf(stderr, "[sqeazy]\t frame_shuffle: malformed reorder_map\n"); return 1; }
         std::vector<bool> targeted(Z, false);
         permutation = true;
@@ -1493,328 +1481,360 @@ int decode_on_device(Context& cx, const void* d_src_v, uint64_t srclen, void* d_
         SQY_HIP(hipMemcpyAsync(ws->small.p, fs_map.data(), Z * 8, hipMemcpyHostToDevice, stream));
         SQY_HIP(hipStreamSynchronize(stream));                                   // (pageable source: gone from the host's side before anything can return)
         return 0;
-    };
-
-    for (size_t si = pipe.stages.size(); si-- > 0;) {
-        const Stage& st = pipe.stages[si];
-        const int e_in = elem_before[si];                                       // element size on the ENCODER's input side of this stage
-        const uint64_t n_in = count_before[si];                                 // elements on that side
-        const uint64_t stage_in_bytes = n_in * (uint64_t)e_in;                  // bytes the inverse has to produce
-        switch (st.kind) {
-            case StageKind::lz4: {
-                const uint64_t total = stage_in_bytes;
-                const uint64_t chunk = total ? st.lz4.bytes_per_chunk(total) : 1;
-                const uint64_t block_bytes = st.lz4.block_bytes();
-                const uint64_t nchunks = total ? (total + chunk - 1) / chunk : 0;
-                const uint64_t max_blocks = std::max<uint64_t>(nchunks * ((chunk + block_bytes - 1) / block_bytes), total / block_bytes + 1) + 16;
-                // block list, frame starts, and a table of frame-start candidates (16 B x >= 8 slots per expected frame)
-                const uint64_t idx_bytes = (max_blocks * 16 + (max_blocks + 2) * 4 + 64 + 15) & ~15ull;
-                const uint64_t cand_bytes = sqy::lz4_frame_rank_scratch_bytes(nchunks);
-                if (ws->lz4_scratch.ensure(idx_bytes + cand_bytes)) return 1;
-                uint8_t* blk = static_cast<uint8_t*>(ws->lz4_scratch.p);
-                uint32_t* frame_first = reinterpret_cast<uint32_t*>(blk + max_blocks * 16);
-                void* cand = blk + idx_bytes;
-                if (ws->csize.ensure(64)) return 1;
-                uint32_t* counts = static_cast<uint32_t*>(ws->csize.p);          // [0..3] index result, [4] decode error flag
-                SQY_HIP(hipMemsetAsync(counts, 0, 64, stream));
-                uint32_t hc[8] = {0, 0, 100, 0, 0, 0, 0, 0};
-                if (nchunks > 1) {
-                    // chunked layout expected: rank the frame list in parallel.  The frames at the stream's end that are stored blocks of
-                    // the chunk size are found where they must start, not by the scan (hc[6] of them); should the ranking give up with
-                    // such a tail, the whole stream is scanned before the walk below is tried.
-                    for (int with_tail = g_opt.stored_tail_index.load() ? 1 : 0; with_tail >= 0; --with_tail) {
-                        {
-                            ProfScope ps("lz4_frame_rank", stream, pend);
-                            SQY_HIP(sqy::launch_lz4_frame_rank(cur, cur_bytes, blk, frame_first, max_blocks, counts, nchunks, cand, stream,
-                                                               with_tail ? chunk : 0, with_tail ? total - (nchunks - 1) * chunk : 0));
-                        }
-                        SQY_HIP(hipMemcpyAsync(hc, counts, sizeof(hc), hipMemcpyDeviceToHost, stream));
-                        SQY_HIP(hipStreamSynchronize(stream));
-                        if (hc[2] != 100 || hc[6] == 0) break;
-                        SQY_HIP(hipMemsetAsync(counts, 0, 64, stream));
-                    }
-                }
-                if (hc[2] == 100) {
-                    // one frame, the serial block-linked layout, or anything the parallel ranking does not cover
-                    {
-                        ProfScope ps("lz4_frame_index", stream, pend);
-                        SQY_HIP(sqy::launch_lz4_frame_index(cur, cur_bytes, blk, frame_first, max_blocks, counts, stream));
-                    }
-                    SQY_HIP(hipMemcpyAsync(hc, counts, sizeof(hc), hipMemcpyDeviceToHost, stream));
-                    SQY_HIP(hipStreamSynchronize(stream));
-                }
-                if (hc[2]) { std::fprintf(stderr, "[sqy::lz4] corrupt LZ4 frame stream (code %u)\n", hc[2]); return stage_error(si); }
-                const uint32_t nframes = hc[0];
-                if (nframes > 1 && nframes != nchunks) {
-                    std::fprintf(stderr, "[sqy::lz4] %u frames where %llu chunks were expected\n", nframes, (unsigned long long)nchunks);
-                    return stage_error(si);
-                }
-                if (nframes == 0 && total > 0) {
-                    std::fprintf(stderr, "[sqy::lz4] no LZ4 frame in the payload, %llu bytes expected\n", (unsigned long long)total);
-                    return stage_error(si);
-                }
-                // frame_shuffle right in front (on the encoder's side), the chunked layout, every chunk inside one of its frames: the frames
-                // are decoded straight to where the shuffle's inverse would move them (round 5: one pass over the volume less -- the C4
-                // config's decode 1.49 -> 1.1 ms)
-                const uint64_t* remap = nullptr;
-                uint64_t remap_bytes = 0;
-                bool remap_zero = false;
-                if (si >= 1 && pipe.stages[si - 1].kind == StageKind::frame_shuffle && nframes == nchunks && nframes > 1 && total % chunk == 0 &&
-                    count_before[si - 1] * (uint64_t)elem_before[si - 1] == total && h.shape.size() == 3) {
-                    uint64_t Z = 0, fb = 0;
-                    bool permutation = true;
-                    if (const int rc = frame_shuffle_prepare(si - 1, Z, fb, permutation)) return rc;
-                    // (round-5 advice) a map that names a place twice -- frames of equal metric on the encoder's side, or a crafted blob --:
-                    // several LZ4 frames must not decode into one place at once (the ring kernels read matches that reach behind their
-                    // ring back from there).  The device's copy of such a map has every frame but the last one named for a place struck
-                    // (frame_shuffle_prepare): struck frames are not decoded, the places nobody names are zeroed first.
-                    if (fb && fb % chunk == 0 && Z * fb == total) {
-                        remap = static_cast<const uint64_t*>(ws->small.p);
-                        remap_bytes = fb;
-                        remap_zero = !permutation;
-                    }
-                }
-                uint8_t* out = out_buf(remap ? si - 1 : si, total);
-                if (!out) return 1;
-                if (remap_zero) { if (const int rc = zero_unnamed_places(out, remap_bytes, total)) return rc; }   // (frames nobody names come out as zeros, as behind the stage's own inverse)
-                uint32_t bad = 0;
-                bool decoded = false;
-                // ONE block-linked frame (nthreads = 1 on the encoder's side): every block at once with the history as an unknown, the
-                // references resolved afterwards (sqy_kernels.hip: lz4_blocks_decode_sym_kernel).  A stream that is not a frame of
-                // full blocks, or is damaged, raises the flag: the one-wavefront walk below then decides, as in rounds 2-3.
-                const bool par_wanted = nframes == 1 && g_opt.block_parallel.load() && sqy::lz4_linked_decode_parallel_possible(hc[1], total, block_bytes);
-                const bool par_room = par_wanted && !ws->spec.ensure(((total * sizeof(uint16_t) + 255) & ~(uint64_t)255) + sqy::lz4_linked_decode_scan_scratch_bytes(hc[1]), true);
-                if (par_wanted && !par_room) {
-                    // (round-4 advice) the references need 2 bytes per decoded byte; without them the walk below decodes the frame -- said once
-                    static std::atomic<bool> told{false};
-                    if (!told.exchange(true))
-                        std::fprintf(stderr, "[sqeazy]\t lz4: no HBM for the block-parallel decode's references (%llu MiB): the block-linked frame is decoded "
-                                             "by one wavefront (same bytes, hundreds of times slower)\n", (unsigned long long)((total * sizeof(uint16_t)) >> 20));
-                }
-                if (par_room) {
-                    // (no room for the references: the walk needs none)
-                    hipError_t le;
-                    {
-                        ProfScope ps("lz4_linked_decode", stream, pend);
-                        uint8_t* scan = static_cast<uint8_t*>(ws->spec.p) + ((total * sizeof(uint16_t) + 255) & ~(uint64_t)255);
-                        le = sqy::launch_lz4_linked_decode_parallel(cur, blk, hc[1], out, static_cast<uint16_t*>(ws->spec.p), total, block_bytes,
-                                                                    counts + 4, stream, g_opt.tail_scan.load() ? scan : nullptr);
-                    }
-                    if (le != hipSuccess) (void)hipGetLastError();                    // (e.g. no 128 KiB of LDS for the tails: the walk below)
-                    SQY_HIP(hipMemcpyAsync(&bad, counts + 4, sizeof(bad), hipMemcpyDeviceToHost, stream));
-                    SQY_HIP(hipStreamSynchronize(stream));
-                    decoded = le == hipSuccess && bad == 0;
-                    if (!decoded) SQY_HIP(hipMemsetAsync(counts + 4, 0, sizeof(uint32_t), stream));
-                }
-                if (!decoded) {
-                    {
-                        const bool side_ok = cx.ensure_side();           // (without it the copy simply follows on the same stream)
-                        ProfScope ps("lz4_frames_decode", stream, pend);
-                        SQY_HIP(sqy::launch_lz4_frames_decode(cur, blk, frame_first, nframes, out, total, chunk, block_bytes, hc[3], counts + 4, stream, side_ok ? cx.side : nullptr, cx.fork, cx.join,
-                                                              remap, remap_bytes, g_opt.decode_two_waves.load() && hc[1] == nframes));
-                    }
-                    // (the decoder's verdict is read at the END of the call, with the call's last synchronisation: the stages in between are
-                    // plain data movement and stay inside their buffers whatever the bytes are -- one host round trip less per decode)
-                    lz4_flag = counts + 4;
-                    lz4_flag_stage = (int)si;
-                }
-                cur = out; cur_bytes = total;
-                if (remap) si -= 1;                                        // the frame_shuffle stage is done as well
-                break;
-            }
-            case StageKind::bitswap1: {
-                // quantiser right in front (on the encoder's side): the inverse transpose and the quantiser's look-up in one pass
-                if (e_in == 1 && si >= 1 && pipe.stages[si - 1].kind == StageKind::quantiser && count_before[si - 1] == n_in &&
-                    elem_before[si - 1] == 2) {
-                    if (quantiser_lut_to_device(pipe.stages[si - 1], ws, stream)) return 1;
-                    uint8_t* out16 = out_buf(si - 1, n_in * 2);
-                    if (!out16) return 1;
-                    if (sqy::bitswap1_u8_decode_lut_possible(cur, out16, n_in)) {
-                        {
-                            ProfScope ps("bitswap1_quantiser_decode", stream, pend);
-                            SQY_HIP(sqy::launch_bitswap1_u8_decode_lut(cur, reinterpret_cast<uint16_t*>(out16), n_in,
-                                                                       static_cast<const uint16_t*>(ws->small.p), stream));
-                        }
-                        cur = out16; cur_bytes = n_in * 2;
-                        si -= 1;                                           // the quantiser stage is done as well
-                        break;
-                    }
-                    // (odd sizes: the two stages one after the other; out16 is the quantiser's output buffer below)
-                    if (si - 1 > lead) use_ping = !use_ping;               // hand the buffer back to the quantiser stage
-                }
-                // diff3x3x1 as the pipeline's first stage (16-bit, the usual geometry): its inverse can only change the leading columns of
-                // a row, so the planes are transposed straight into the volume and the inverse works there (round 4; before: into a
-                // work buffer, from which the inverse copied every untouched column -- 0.75 ms of a 2 GiB slab's 1.1)
-                uint8_t* out = nullptr;
-                if (si == 1 && pipe.stages[0].kind == StageKind::diff3x3x1 && e_in == 2 && h.shape.size() == 3 && n_in == n &&
-                    (reinterpret_cast<uintptr_t>(d_dst) & 15) == 0 && sqy::diff3x3x1_decode_chain_columns(h.shape[0], h.shape[1], h.shape[2], 2)) {
-                    out = static_cast<uint8_t*>(d_dst);
-                    diff_in_place = true;
-                } else
-                    out = out_buf(si, stage_in_bytes);
-                if (!out) return 1;
-                ProfScope ps("bitswap1_decode", stream, pend);
-                SQY_HIP(sqy::launch_bitswap1_decode(cur, out, n_in, e_in, stream));
-                cur = out; cur_bytes = stage_in_bytes;
-                break;
-            }
-            case StageKind::raster_reorder: {
-                if (h.shape.size() != 3) return 1;
-                auto t = st.cfg.find("tile_size");
-                const uint64_t ts = t != st.cfg.end() ? (uint64_t)std::atoi(t->second.c_str()) : 0;
-                uint64_t Z, Y, X;
-                stage_shape(si, n_in, Z, Y, X);                              // (tail filter: the sink's char stream)
-                if (!sqy::raster_geometry_defined(Z, Y, X, ts, e_in)) {
-                    std::fprintf(stderr, "[sqeazy]\t raster_reorder: tile_size %llu does not fit the shape\n", (unsigned long long)ts);
-                    return stage_error(si);
-                }
-                uint8_t* out = out_buf(si, stage_in_bytes);
-                if (!out) return 1;
-                ProfScope ps("raster_reorder_decode", stream, pend);
-                SQY_HIP(sqy::launch_raster_reorder(cur, out, Z, Y, X, ts, e_in, true, stream));
-                cur = out; cur_bytes = stage_in_bytes;
-                break;
-            }
-            case StageKind::pass_through:
-                break;                                                          // pass_through_scheme_impl.hpp:81-95: bytes are the voxels
-            case StageKind::rmestbkrd:
-            case StageKind::rmbkrd_neighbor5:
-                break;                                                          // a copy: `cur` is the filtered volume (written out at the end)
-            case StageKind::zcurve_reorder: {
-                if (h.shape.size() != 3) return stage_error(si);
-                auto t = st.cfg.find("tile_size");
-                const uint64_t ts = t != st.cfg.end() ? (uint64_t)std::atoi(t->second.c_str()) : 2;
-                uint64_t Z, Y, X;
-                stage_shape(si, n_in, Z, Y, X);
-                if (!sqy::zcurve_geometry_defined(Z, Y, X, ts)) {
-                    std::fprintf(stderr, "[sqeazy]\t zcurve_reorder: tile_size %llu does not fit the shape\n", (unsigned long long)ts);
-                    return stage_error(si);
-                }
-                uint8_t* out = out_buf(si, stage_in_bytes);
-                if (!out) return 1;
-                ProfScope ps("zcurve_reorder_decode", stream, pend);
-                SQY_HIP(sqy::launch_raster_reorder(cur, out, Z, Y, X, ts, e_in, true, stream));
-                cur = out; cur_bytes = stage_in_bytes;
-                break;
-            }
-            case StageKind::bitshuffle: {
-                const int e_here = (sink_index >= 0 && (int)si > sink_index) ? 1 : e_in;      // tail filters work on the sink's bytes
-                auto b = st.cfg.find("block_size");
-                const uint64_t be = sqy::bitshuffle_block_elems(e_here, b != st.cfg.end() ? (uint64_t)std::atoi(b->second.c_str()) : 0);
-                if (!be) return stage_error(si);
-                uint8_t* out = out_buf(si, stage_in_bytes);
-                if (!out) return 1;
-                ProfScope ps("bitshuffle_decode", stream, pend);
-                SQY_HIP(sqy::launch_bitshuffle(cur, out, stage_in_bytes / (uint64_t)e_here, e_here, be, true, stream));
-                cur = out; cur_bytes = stage_in_bytes;
-                break;
-            }
-            case StageKind::tile_shuffle: {
-                if (h.shape.size() != 3) return stage_error(si);
-                auto t = st.cfg.find("tile_size");
-                const uint64_t ts = t != st.cfg.end() ? (uint64_t)std::atoi(t->second.c_str()) : 32;
-                uint64_t Z, Y, X;
-                stage_shape(si, n_in, Z, Y, X);
-                if (!sqy::tile_shuffle_geometry_defined(Z, Y, X, ts)) {
-                    std::fprintf(stderr, "[sqeazy]\t tile_shuffle: tile_size %llu does not divide the shape\n", (unsigned long long)ts);
-                    return stage_error(si);
-                }
-                auto it = st.cfg.find("reorder_map");
-                const uint64_t per_tile = ts * ts * ts, ntiles = n_in / per_tile, tile_bytes = per_tile * (uint64_t)e_in;
-                if (it == st.cfg.end() || it->second.size() < 21) { std::fprintf(stderr, "[sqeazy]\t tile_shuffle: no reorder_map in the header\n"); return stage_error(si); }
-                const std::vector<unsigned char> mapb = sqy::base64_decode(it->second.substr(10, it->second.size() - 21));
-                if (mapb.size() != ntiles * 8) { std::fprintf(stderr, "[sqeazy]\t tile_shuffle: malformed reorder_map\n"); return stage_error(si); }
-                // tile_shuffle_utils.hpp:473-482: encoded tile i goes to slot map[i], a later i wins, unnamed slots stay zero:
-                // as a gather, slot t takes the LAST i that names it
-                std::vector<uint64_t> src_of(ntiles, ~0ull);
-                for (uint64_t i = 0; i < ntiles; ++i) {
-                    uint64_t v; std::memcpy(&v, mapb.data() + 8 * i, 8);
-                    if (v >= ntiles) { std::fprintf(stderr, "[sqeazy]\t tile_shuffle: reorder_map out of range\n"); return stage_error(si); }
-                    src_of[v] = i;
-                }
-                if (ws->small.ensure(std::max<uint64_t>(ntiles * 8, 4096))) return 1;
-                SQY_HIP(hipMemcpyAsync(ws->small.p, src_of.data(), ntiles * 8, hipMemcpyHostToDevice, stream));
-                DevBuf& tb = use_ping ? ws->ping : ws->pong;                    // tile-major intermediate
-                use_ping = !use_ping;
-                if (tb.ensure(std::max<uint64_t>(stage_in_bytes, 16))) return 1;
-                {
-                    ProfScope ps("tile_unshuffle", stream, pend);
-                    SQY_HIP(sqy::launch_frame_gather(cur, tb.p, ntiles, tile_bytes, static_cast<const uint64_t*>(ws->small.p), stream));
-                }
-                SQY_HIP(hipStreamSynchronize(stream));                          // src_of (host) is read by the async copy above
-                uint8_t* out = out_buf(si, stage_in_bytes);
-                if (!out) return 1;
-                {
-                    ProfScope ps("tile_scatter", stream, pend);
-                    SQY_HIP(sqy::launch_raster_reorder(tb.p, out, Z, Y, X, ts, e_in, true, stream));
-                }
-                cur = out; cur_bytes = stage_in_bytes;
-                break;
-            }
-            case StageKind::diff3x3x1: {
-                if (h.shape.size() != 3) return 1;
-                // as a tail filter (behind the sink) the stream is `char` and has the volume's shape only when the sink wrote one
-                // byte per voxel (dynamic_pipeline.hpp:658-666); anything else the encoder refused
-                const bool tail = sink_index >= 0 && (int)si > sink_index;
-                if (tail && (n_in != n || e_in != 1)) return stage_error(si);
-                uint8_t* out = out_buf(si, stage_in_bytes);
-                if (!out) return 1;
-                if (ws->lz4_scratch.ensure(sqy::diff3x3x1_decode_scratch_bytes(h.shape[2]))) return 1;
-                void* left_tmp = nullptr;
-                if (si == 0 && diff_in_place && cur == out) {              // the bit-plane inverse wrote the volume's own memory (above)
-                    DevBuf& tb = use_ping ? ws->ping : ws->pong;
-                    use_ping = !use_ping;
-                    if (tb.ensure(std::max<uint64_t>(stage_in_bytes, 16))) return 1;
-                    left_tmp = tb.p;
-                }
-                ProfScope ps("diff3x3x1_decode", stream, pend);
-                const bool side_ok = cx.ensure_side();
-                SQY_HIP(sqy::launch_diff3x3x1_decode(cur, out, h.shape[0], h.shape[1], h.shape[2], e_in, ws->lz4_scratch.p, stream, tail,
-                                                     side_ok ? cx.side : nullptr, cx.fork, cx.join, left_tmp));
-                cur = out; cur_bytes = stage_in_bytes;
-                break;
-            }
-            case StageKind::quantiser: {
-                if (quantiser_lut_to_device(st, ws, stream)) return 1;
-                uint8_t* out = out_buf(si, stage_in_bytes);
-                if (!out) return 1;
-                {
-                    ProfScope ps("quantiser_decode", stream, pend);
-                    SQY_HIP(sqy::launch_quantiser_decode(cur, reinterpret_cast<uint16_t*>(out), n, static_cast<const uint16_t*>(ws->small.p), stream));
-                }
-                SQY_HIP(hipStreamSynchronize(stream));
-                cur = out; cur_bytes = stage_in_bytes;
-                break;
-            }
-            case StageKind::frame_shuffle: {
-                uint64_t Z = 0, frame_bytes_dec = 0;
-                bool permutation = true;
-                if (const int rc = frame_shuffle_prepare(si, Z, frame_bytes_dec, permutation)) return rc;
-                uint8_t* out = out_buf(si, stage_in_bytes);
-                if (!out) return 1;
-                // Frames with equal metrics share ONE source frame in the encoder (std::find, frame_shuffle_utils.hpp:158-161): the map then
-                // names a frame twice and others not at all.  The reference's decode leaves the frames nobody names as the output
-                // buffer had them (frame_shuffle_utils.hpp:337-344); here they come out as zeros, not as whatever the
-                // workspace held.
-                if (!permutation) { if (const int rc = zero_unnamed_places(out, frame_bytes_dec, stage_in_bytes)) return rc; }
-                {
-                    ProfScope ps("frame_scatter", stream, pend);
-                    SQY_HIP(sqy::launch_frame_scatter(cur, out, Z, frame_bytes_dec, static_cast<const uint64_t*>(ws->small.p), stream));
-                }
-                cur = out; cur_bytes = stage_in_bytes;
-                break;
-            }
-            default:
-                return 1;
-        }
     }
-    if (cur != d_dst) SQY_HIP(hipMemcpyAsync(d_dst, cur, raw_bytes, hipMemcpyDeviceToDevice, stream));
-    if (lz4_flag) SQY_HIP(hipMemcpyAsync(ws->pinned, lz4_flag, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+
+    // The LZ4 frames' inverse: the frame index, then the frames decoded -- with frame_shuffle in front straight to the places its inverse
+    // would move them to, which then is done as well
+    int lz4(size_t& si)
+    {
+        const uint64_t total = in_bytes(si);
+        Lz4Index ix;
+        if (const int rc = lz4_index(si, total, ix)) return rc;
+        Lz4Remap rm;
+        if (const int rc = lz4_remap(si, total, ix, rm)) return rc;
+        uint8_t* out = out_buf(rm.map ? si - 1 : si, total);
+        if (!out) return 1;
+        if (rm.zero) { if (const int rc = zero_unnamed_places(out, rm.bytes, total)) return rc; }   // (frames nobody names come out as zeros, as behind the stage's own inverse)
+        bool decoded = false;
+        if (lz4_linked_parallel(ix, out, total, &decoded)) return 1;
+        if (!decoded && lz4_frames(si, ix, out, total, rm)) return 1;
+        if (rm.map) si -= 1;                                       // the frame_shuffle stage is done as well
+        return produced(out, total);
+    }
+
+    int lz4_index(size_t si, uint64_t total, Lz4Index& ix)
+    {
+        const Stage& st = pipe.stages[si];
+        ix.chunk = total ? st.lz4.bytes_per_chunk(total) : 1;
+        ix.block_bytes = st.lz4.block_bytes();
+        ix.nchunks = total ? (total + ix.chunk - 1) / ix.chunk : 0;
+        const uint64_t max_blocks = std::max<uint64_t>(ix.nchunks * ((ix.chunk + ix.block_bytes - 1) / ix.block_bytes), total / ix.block_bytes + 1) + 16;
+        // block list, frame starts, and a table of frame-start candidates (16 B x >= 8 slots per expected frame)
+        const uint64_t idx_bytes = (max_blocks * 16 + (max_blocks + 2) * 4 + 64 + 15) & ~15ull;
+        const uint64_t cand_bytes = sqy::lz4_frame_rank_scratch_bytes(ix.nchunks);
+        if (ws->lz4_scratch.ensure(idx_bytes + cand_bytes)) return 1;
+        ix.blk = static_cast<uint8_t*>(ws->lz4_scratch.p);
+        ix.frame_first = reinterpret_cast<uint32_t*>(ix.blk + max_blocks * 16);
+        void* cand = ix.blk + idx_bytes;
+        if (ws->csize.ensure(64)) return 1;
+        ix.counts = static_cast<uint32_t*>(ws->csize.p);
+        SQY_HIP(hipMemsetAsync(ix.counts, 0, 64, stream));
+        if (ix.nchunks > 1) {
+            // chunked layout expected: rank the frame list in parallel.  The frames at the stream's end that are stored blocks of
+            // the chunk size are found where they must start, not by the scan (hc[6] of them); should the ranking give up with
+            // such a tail, the whole stream is scanned before the walk below is tried.
+            for (int with_tail = g_opt.stored_tail_index.load() ? 1 : 0; with_tail >= 0; --with_tail) {
+                SQY_TIMED("lz4_frame_rank", sqy::launch_lz4_frame_rank(cur, cur_bytes, ix.blk, ix.frame_first, max_blocks, ix.counts, ix.nchunks, cand, stream,
+                                                                       with_tail ? ix.chunk : 0, with_tail ? total - (ix.nchunks - 1) * ix.chunk : 0));
+                SQY_HIP(hipMemcpyAsync(ix.hc, ix.counts, sizeof(ix.hc), hipMemcpyDeviceToHost, stream));
+                SQY_HIP(hipStreamSynchronize(stream));
+                if (ix.hc[2] != 100 || ix.hc[6] == 0) break;
+                SQY_HIP(hipMemsetAsync(ix.counts, 0, 64, stream));
+            }
+        }
+        if (ix.hc[2] == 100) {
+            // one frame, the serial block-linked layout, or anything the parallel ranking does not cover
+            SQY_TIMED("lz4_frame_index", sqy::launch_lz4_frame_index(cur, cur_bytes, ix.blk, ix.frame_first, max_blocks, ix.counts, stream));
+            SQY_HIP(hipMemcpyAsync(ix.hc, ix.counts, sizeof(ix.hc), hipMemcpyDeviceToHost, stream));
+            SQY_HIP(hipStreamSynchronize(stream));
+        }
+        if (ix.hc[2]) { std::fprintf(stderr, "[sqy::lz4] corrupt LZ4 frame stream (code %u)\n", ix.hc[2]); return stage_error(si); }
+        const uint32_t nframes = ix.hc[0];
+        if (nframes > 1 && nframes != ix.nchunks) {
+            std::fprintf(stderr, "[sqy::lz4] %u frames where %llu chunks were expected\n", nframes, (unsigned long long)ix.nchunks);
+            return stage_error(si);
+        }
+        if (nframes == 0 && total > 0) {
+            std::fprintf(stderr, "[sqy::lz4] no LZ4 frame in the payload, %llu bytes expected\n", (unsigned long long)total);
+            return stage_error(si);
+        }
+        return 0;
+    }
+
+    // frame_shuffle right in front (on the encoder's side), the chunked layout, every chunk inside one of its frames: the frames
+    // are decoded straight to where the shuffle's inverse would move them (round 5: one pass over the volume less -- the C4
+    // config's decode 1.49 -> 1.1 ms)
+    int lz4_remap(size_t si, uint64_t total, const Lz4Index& ix, Lz4Remap& rm)
+    {
+        const uint32_t nframes = ix.hc[0];
+        if (!(preceded_by(si, StageKind::frame_shuffle) && nframes == ix.nchunks && nframes > 1 && total % ix.chunk == 0 && in_bytes(si - 1) == total &&
+              h.shape.size() == 3))
+            return 0;
+        uint64_t Z = 0, fb = 0;
+        bool permutation = true;
+        if (const int rc = frame_shuffle_prepare(si - 1, Z, fb, permutation)) return rc;
+        // (round-5 advice) a map that names a place twice -- frames of equal metric on the encoder's side, or a crafted blob --:
+        // several LZ4 frames must not decode into one place at once (the ring kernels read matches that reach behind their
+        // ring back from there).  The device's copy of such a map has every frame but the last one named for a place struck
+        // (frame_shuffle_prepare): struck frames are not decoded, the places nobody names are zeroed first.
+        if (fb && fb % ix.chunk == 0 && Z * fb == total) {
+            rm.map = static_cast<const uint64_t*>(ws->small.p);
+            rm.bytes = fb;
+            rm.zero = !permutation;
+        }
+        return 0;
+    }
+
+    // ONE block-linked frame (nthreads = 1 on the encoder's side): every block at once with the history as an unknown, the
+    // references resolved afterwards (sqy_kernels.hip: lz4_blocks_decode_sym_kernel).  A stream that is not a frame of
+    // full blocks, or is damaged, raises the flag: *decoded stays false, and the one-wavefront walk (lz4_frames) decides, as in rounds 2-3.
+    int lz4_linked_parallel(const Lz4Index& ix, uint8_t* out, uint64_t total, bool* decoded)
+    {
+        const bool par_wanted = ix.hc[0] == 1 && g_opt.block_parallel.load() && sqy::lz4_linked_decode_parallel_possible(ix.hc[1], total, ix.block_bytes);
+        const bool par_room = par_wanted && !ws->spec.ensure(((total * sizeof(uint16_t) + 255) & ~(uint64_t)255) + sqy::lz4_linked_decode_scan_scratch_bytes(ix.hc[1]), true);
+        if (par_wanted && !par_room) {
+            // (round-4 advice) the references need 2 bytes per decoded byte; without them the walk decodes the frame -- said once
+            static std::atomic<bool> told{false};
+            if (!told.exchange(true))
+                std::fprintf(stderr, "[sqeazy]\t lz4: no HBM for the block-parallel decode's references (%llu MiB): the block-linked frame is decoded "
+                                     "by one wavefront (same bytes, hundreds of times slower)\n", (unsigned long long)((total * sizeof(uint16_t)) >> 20));
+        }
+        if (!par_room) return 0;                                   // (no room for the references: the walk needs none)
+        hipError_t le;
+        {
+            ProfScope ps("lz4_linked_decode", stream, pend);
+            uint8_t* scan = static_cast<uint8_t*>(ws->spec.p) + ((total * sizeof(uint16_t) + 255) & ~(uint64_t)255);
+            le = sqy::launch_lz4_linked_decode_parallel(cur, ix.blk, ix.hc[1], out, static_cast<uint16_t*>(ws->spec.p), total, ix.block_bytes,
+                                                        ix.counts + 4, stream, g_opt.tail_scan.load() ? scan : nullptr);
+        }
+        if (le != hipSuccess) (void)hipGetLastError();                    // (e.g. no 128 KiB of LDS for the tails: the walk)
+        uint32_t bad = 0;
+        SQY_HIP(hipMemcpyAsync(&bad, ix.counts + 4, sizeof(bad), hipMemcpyDeviceToHost, stream));
+        SQY_HIP(hipStreamSynchronize(stream));
+        *decoded = le == hipSuccess && bad == 0;
+        if (!*decoded) SQY_HIP(hipMemsetAsync(ix.counts + 4, 0, sizeof(uint32_t), stream));
+        return 0;
+    }
+
+    // every frame by its own wavefront(s), the stored ones copied on the side stream
+    int lz4_frames(size_t si, const Lz4Index& ix, uint8_t* out, uint64_t total, const Lz4Remap& rm)
+    {
+        const uint32_t nframes = ix.hc[0];
+        {
+            const bool side_ok = cx.ensure_side();           // (without it the copy simply follows on the same stream)
+            SQY_TIMED("lz4_frames_decode", sqy::launch_lz4_frames_decode(cur, ix.blk, ix.frame_first, nframes, out, total, ix.chunk, ix.block_bytes, ix.hc[3], ix.counts + 4, stream,
+                                                                         side_ok ? cx.side : nullptr, cx.fork, cx.join, rm.map, rm.bytes,
+                                                                         g_opt.decode_two_waves.load() && ix.hc[1] == nframes));
+        }
+        // (the decoder's verdict is read at the END of the call, with the call's last synchronisation: the stages in between are
+        // plain data movement and stay inside their buffers whatever the bytes are -- one host round trip less per decode)
+        lz4_flag = ix.counts + 4;
+        lz4_flag_stage = (int)si;
+        return 0;
+    }
+
+    int bitswap1(size_t& si)
+    {
+        const int e_in = elem_before[si];
+        const uint64_t n_in = count_before[si];
+        // quantiser right in front (on the encoder's side): the inverse transpose and the quantiser's look-up in one pass
+        if (e_in == 1 && preceded_by(si, StageKind::quantiser) && count_before[si - 1] == n_in && elem_before[si - 1] == 2) {
+            if (quantiser_lut_to_device(pipe.stages[si - 1], ws)) return 1;
+            uint8_t* out16 = out_buf(si - 1, n_in * 2);
+            if (!out16) return 1;
+            if (sqy::bitswap1_u8_decode_lut_possible(cur, out16, n_in)) {
+                SQY_TIMED("bitswap1_quantiser_decode", sqy::launch_bitswap1_u8_decode_lut(cur, reinterpret_cast<uint16_t*>(out16), n_in,
+                                                                                          static_cast<const uint16_t*>(ws->small.p), stream));
+                si -= 1;                                           // the quantiser stage is done as well
+                return produced(out16, n_in * 2);
+            }
+            // (odd sizes: the two stages one after the other; out16 is the output buffer of quantiser())
+            if (si - 1 > lead) use_ping = !use_ping;               // hand the buffer back to the quantiser stage
+        }
+        // diff3x3x1 as the pipeline's first stage (16-bit, the usual geometry): its inverse can only change the leading columns of
+        // a row, so the planes are transposed straight into the volume and the inverse works there (round 4; before: into a
+        // work buffer, from which the inverse copied every untouched column -- 0.75 ms of a 2 GiB slab's 1.1)
+        uint8_t* out = nullptr;
+        if (si == 1 && pipe.stages[0].kind == StageKind::diff3x3x1 && e_in == 2 && h.shape.size() == 3 && n_in == n &&
+            (reinterpret_cast<uintptr_t>(d_dst) & 15) == 0 && sqy::diff3x3x1_decode_chain_columns(h.shape[0], h.shape[1], h.shape[2], 2)) {
+            out = static_cast<uint8_t*>(d_dst);
+            diff_in_place = true;
+        } else
+            out = out_buf(si, in_bytes(si));
+        if (!out) return 1;
+        SQY_TIMED("bitswap1_decode", sqy::launch_bitswap1_decode(cur, out, n_in, e_in, stream));
+        return produced(out, in_bytes(si));
+    }
+
+    // raster_reorder and zcurve_reorder (one kernel, see the encoder's side)
+    int reorder(size_t si, bool zcurve)
+    {
+        if (h.shape.size() != 3) return zcurve ? stage_error(si) : 1;
+        const Stage& st = pipe.stages[si];
+        auto t = st.cfg.find("tile_size");
+        const uint64_t ts = t != st.cfg.end() ? (uint64_t)std::atoi(t->second.c_str()) : (zcurve ? 2 : 0);
+        uint64_t Z, Y, X;
+        stage_shape(si, Z, Y, X);                                  // (tail filter: the sink's char stream)
+        if (zcurve ? !sqy::zcurve_geometry_defined(Z, Y, X, ts) : !sqy::raster_geometry_defined(Z, Y, X, ts, elem_before[si])) {
+            std::fprintf(stderr, "[sqeazy]\t %s: tile_size %llu does not fit the shape\n", zcurve ? "zcurve_reorder" : "raster_reorder", (unsigned long long)ts);
+            return stage_error(si);
+        }
+        uint8_t* out = out_buf(si, in_bytes(si));
+        if (!out) return 1;
+        SQY_TIMED(zcurve ? "zcurve_reorder_decode" : "raster_reorder_decode", sqy::launch_raster_reorder(cur, out, Z, Y, X, ts, elem_before[si], true, stream));
+        return produced(out, in_bytes(si));
+    }
+
+    int bitshuffle(size_t si)
+    {
+        const Stage& st = pipe.stages[si];
+        const int e_here = is_tail(si) ? 1 : elem_before[si];     // tail filters work on the sink's bytes
+        auto b = st.cfg.find("block_size");
+        const uint64_t be = sqy::bitshuffle_block_elems(e_here, b != st.cfg.end() ? (uint64_t)std::atoi(b->second.c_str()) : 0);
+        if (!be) return stage_error(si);
+        uint8_t* out = out_buf(si, in_bytes(si));
+        if (!out) return 1;
+        SQY_TIMED("bitshuffle_decode", sqy::launch_bitshuffle(cur, out, in_bytes(si) / (uint64_t)e_here, e_here, be, true, stream));
+        return produced(out, in_bytes(si));
+    }
+
+    int tile_shuffle(size_t si)
+    {
+        if (h.shape.size() != 3) return stage_error(si);
+        const Stage& st = pipe.stages[si];
+        auto t = st.cfg.find("tile_size");
+        const uint64_t ts = t != st.cfg.end() ? (uint64_t)std::atoi(t->second.c_str()) : 32;
+        uint64_t Z, Y, X;
+        stage_shape(si, Z, Y, X);
+        if (!sqy::tile_shuffle_geometry_defined(Z, Y, X, ts)) {
+            std::fprintf(stderr, "[sqeazy]\t tile_shuffle: tile_size %llu does not divide the shape\n", (unsigned long long)ts);
+            return stage_error(si);
+        }
+        auto it = st.cfg.find("reorder_map");
+        const uint64_t stage_in_bytes = in_bytes(si);
+        const uint64_t per_tile = ts * ts * ts, ntiles = count_before[si] / per_tile, tile_bytes = per_tile * (uint64_t)elem_before[si];
+        std::vector<unsigned char> mapb;
+        if (it == st.cfg.end() || !sqy::from_verbatim(it->second, &mapb)) { std::fprintf(stderr, "[sqeazy]\t tile_shuffle: no reorder_map in the header\n"); return stage_error(si); }
+        if (mapb.size() != ntiles * 8) { std::fprintf(stderr, "[sqeazy]\t tile_shuffle: malformed reorder_map\n"); return stage_error(si); }
+        // tile_shuffle_utils.hpp:473-482: encoded tile i goes to slot map[i], a later i wins, unnamed slots stay zero:
+        // as a gather, slot t takes the LAST i that names it
+        std::vector<uint64_t> src_of(ntiles, ~0ull);
+        for (uint64_t i = 0; i < ntiles; ++i) {
+            uint64_t v; std::memcpy(&v, mapb.data() + 8 * i, 8);
+            if (v >= ntiles) { std::fprintf(stderr, "[sqeazy]\t tile_shuffle: reorder_map out of range\n"); return stage_error(si); }
+            src_of[v] = i;
+        }
+        if (ws->small.ensure(std::max<uint64_t>(ntiles * 8, 4096))) return 1;
+        SQY_HIP(hipMemcpyAsync(ws->small.p, src_of.data(), ntiles * 8, hipMemcpyHostToDevice, stream));
+        uint8_t* tb = work_buf(stage_in_bytes);                         // tile-major intermediate
+        if (!tb) return 1;
+        SQY_TIMED("tile_unshuffle", sqy::launch_frame_gather(cur, tb, ntiles, tile_bytes, static_cast<const uint64_t*>(ws->small.p), stream));
+        SQY_HIP(hipStreamSynchronize(stream));                          // src_of (host) is read by the async copy above
+        uint8_t* out = out_buf(si, stage_in_bytes);
+        if (!out) return 1;
+        SQY_TIMED("tile_scatter", sqy::launch_raster_reorder(tb, out, Z, Y, X, ts, elem_before[si], true, stream));
+        return produced(out, stage_in_bytes);
+    }
+
+    int diff3x3x1(size_t si)
+    {
+        if (h.shape.size() != 3) return 1;
+        // as a tail filter (behind the sink) the stream is `char` and has the volume's shape only when the sink wrote one
+        // byte per voxel (dynamic_pipeline.hpp:658-666); anything else the encoder refused
+        const bool tail = is_tail(si);
+        if (tail && (count_before[si] != n || elem_before[si] != 1)) return stage_error(si);
+        uint8_t* out = out_buf(si, in_bytes(si));
+        if (!out) return 1;
+        void* left_tmp = nullptr;
+        if (si == 0 && diff_in_place && cur == out) {              // the bit-plane inverse wrote the volume's own memory (bitswap1)
+            left_tmp = work_buf(in_bytes(si));
+            if (!left_tmp) return 1;
+        }
+        ProfScope ps("diff3x3x1_decode", stream, pend);
+        const bool side_ok = cx.ensure_side();
+        SQY_HIP(sqy::launch_diff3x3x1_decode(cur, out, h.shape[0], h.shape[1], h.shape[2], elem_before[si], ws->lz4_scratch.p, stream, tail,
+                                             side_ok ? cx.side : nullptr, cx.fork, cx.join, left_tmp));
+        return produced(out, in_bytes(si));
+    }
+
+    int quantiser(size_t si)
+    {
+        if (quantiser_lut_to_device(pipe.stages[si], ws)) return 1;
+        uint8_t* out = out_buf(si, in_bytes(si));
+        if (!out) return 1;
+        SQY_TIMED("quantiser_decode", sqy::launch_quantiser_decode(cur, reinterpret_cast<uint16_t*>(out), n, static_cast<const uint16_t*>(ws->small.p), stream));
+        SQY_HIP(hipStreamSynchronize(stream));
+        return produced(out, in_bytes(si));
+    }
+
+    int frame_shuffle(size_t si)
+    {
+        uint64_t Z = 0, frame_bytes_dec = 0;
+        bool permutation = true;
+        if (const int rc = frame_shuffle_prepare(si, Z, frame_bytes_dec, permutation)) return rc;
+        uint8_t* out = out_buf(si, in_bytes(si));
+        if (!out) return 1;
+        // Frames with equal metrics share ONE source frame in the encoder (std::find, frame_shuffle_utils.hpp:158-161): the map then
+        // names a frame twice and others not at all.  The reference's decode leaves the frames nobody names as the output
+        // buffer had them (frame_shuffle_utils.hpp:337-344); here they come out as zeros, not as whatever the
+        // workspace held.
+        if (!permutation) { if (const int rc = zero_unnamed_places(out, frame_bytes_dec, in_bytes(si))) return rc; }
+        SQY_TIMED("frame_scatter", sqy::launch_frame_scatter(cur, out, Z, frame_bytes_dec, static_cast<const uint64_t*>(ws->small.p), stream));
+        return produced(out, in_bytes(si));
+    }
+};
+
+int decode_on_device(Context& cx, const void* d_src_v, uint64_t srclen, void* d_dst, uint64_t dst_capacity, int want_elem, hipStream_t stream)
+{
+    if (!d_src_v || !d_dst) return 1;
+    const uint8_t* d_src = static_cast<const uint8_t*>(d_src_v);
+    DrainOnExit drain{stream, &cx.pending, cx.side};
+    // header: fetch a prefix of the blob, grow until the delimiter is inside
+    std::vector<char> head;
+    sqy::HeaderInfo h;
+    for (uint64_t want = 1 << 16;; want *= 16) {
+        const uint64_t take = std::min<uint64_t>(want, srclen);
+        head.resize(take);
+        SQY_HIP(hipMemcpyAsync(head.data(), d_src, take, hipMemcpyDeviceToHost, stream));
+        SQY_HIP(hipStreamSynchronize(stream));
+        h = sqy::header_unpack(head.data(), head.data() + take);
+        if (h.valid || take == srclen) break;
+    }
+    if (!h.valid) { std::fprintf(stderr, "[sqeazy]\t unable to find a sqy header in the blob\n"); return 1; }
+    const int elem = h.elem_size();
+    if (elem != want_elem) { std::fprintf(stderr, "[sqeazy]\t blob holds %s voxels\n", h.type.c_str()); return 1; }
+    std::string why;
+    if (!Pipeline::supported(h.pipename, elem, &why)) {
+        std::fprintf(stderr, "[sqeazy]\t%s cannot be build with this version of sqeazy (%s)\n", h.pipename.c_str(), why.c_str());
+        return 1;
+    }
+    Pipeline pipe = Pipeline::from_string(h.pipename);
+    // the header is untrusted input: every extent positive, the voxel count below 2^31 (what one encode call can have
+    // produced), no wrap-around anywhere
+    uint64_t raw_bytes = 0;
+    if (!header_shape_ok(h, srclen, &raw_bytes)) return 1;
+    if (raw_bytes > dst_capacity) {
+        std::fprintf(stderr, "[sqeazy]\t decode: buffer too small or blob truncated\n");
+        return 1;
+    }
+
+    DecodeCall c(cx, stream, d_dst, h, std::move(pipe), raw_bytes / (uint64_t)elem, d_src + h.size);
+    for (size_t si = c.pipe.stages.size(); si-- > 0;) {
+        int rc = 0;
+        switch (c.pipe.stages[si].kind) {
+            case StageKind::lz4:               rc = c.lz4(si); break;              // (may do the frame_shuffle in front as well)
+            case StageKind::bitswap1:          rc = c.bitswap1(si); break;         // (may do the quantiser in front as well)
+            case StageKind::raster_reorder:    rc = c.reorder(si, false); break;
+            case StageKind::zcurve_reorder:    rc = c.reorder(si, true); break;
+            case StageKind::bitshuffle:        rc = c.bitshuffle(si); break;
+            case StageKind::tile_shuffle:      rc = c.tile_shuffle(si); break;
+            case StageKind::diff3x3x1:         rc = c.diff3x3x1(si); break;
+            case StageKind::quantiser:         rc = c.quantiser(si); break;
+            case StageKind::frame_shuffle:     rc = c.frame_shuffle(si); break;
+            case StageKind::pass_through:      break;                              // pass_through_scheme_impl.hpp:81-95: bytes are the voxels
+            case StageKind::rmestbkrd:
+            case StageKind::rmbkrd_neighbor5:  break;                              // a copy: `cur` is the filtered volume (written out at the end)
+            default:                           return 1;
+        }
+        if (rc) return rc;
+    }
+    if (c.cur != d_dst) SQY_HIP(hipMemcpyAsync(d_dst, c.cur, raw_bytes, hipMemcpyDeviceToDevice, stream));
+    if (c.lz4_flag) SQY_HIP(hipMemcpyAsync(cx.ws.pinned, c.lz4_flag, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
     SQY_HIP(hipStreamSynchronize(stream));
     if (g_prof_on.load()) prof_collect(cx.pending);
-    if (lz4_flag && *static_cast<const uint32_t*>(ws->pinned)) {
+    if (c.lz4_flag && *static_cast<const uint32_t*>(cx.ws.pinned)) {
         std::fprintf(stderr, "[sqy::lz4] corrupt LZ4 block, or a frame that does not decode to its share of the volume\n");
-        return stage_error((size_t)lz4_flag_stage);
+        return c.stage_error((size_t)c.lz4_flag_stage);
     }
     return 0;
 }
@@ -1841,6 +1861,20 @@ int decode_from_host(const char* src, long srclength, char* dst, int elem_size)
     SQY_HIP(hipStreamSynchronize(stream));
     if (!lease.ctx->stager.copy(ws->io_dst.p, dst, raw, false, dev_id)) { std::fprintf(stderr, "[sqeazy]\t device to host transfer failed\n"); return 1; }
     return 0;
+}
+
+// The body of the device-memory encode entry points: the blob at d_dst (_Device), or where *dstoffset says (at: _DeviceAt), with the
+// offsets of the frames fq asks for (_DeviceAt_Frames: *count of them)
+int encode_device(const char* pipeline, const void* d_src, const long* shape, unsigned rank, int elem_size, void* d_dst, long dst_capacity,
+                  long* dstoffset, long* dstlength, int nthreads, void* hip_stream, bool at, FrameQuery* fq = nullptr, int* count = nullptr)
+{
+    if ((at && !dstoffset) || (fq && (fq->every <= 0 || !fq->offsets || !count))) return 1;
+    ContextLease lease;
+    if (!lease.ctx) { std::fprintf(stderr, "[sqeazy]\t no usable HIP device\n"); return 1; }
+    const int rc = encode_on_device(*lease.ctx, pipeline, d_src, shape, rank, elem_size, d_dst, (uint64_t)std::max(dst_capacity, 0l), dstlength,
+                                    nthreads, static_cast<hipStream_t>(hip_stream), dstoffset, fq);
+    if (fq) *count = fq->count;
+    return rc;
 }
 
 int max_compressed_length(const char* pipeline, long pipeline_length, long* length, int elem_size, uint64_t raw_bytes)
@@ -1997,10 +2031,7 @@ bool SQY_Pipeline_Possible_UI8(const char* s) { return guarded_bool([&]() -> boo
 bool SQY_Pipeline_Possible(const char* s, int sizeofpixel)
 {
     return guarded_bool([&]() -> bool {
-    if (!s) return false;
-    if (sizeofpixel == 2) return Pipeline::supported(s, 2);
-    if (sizeofpixel == 1) return Pipeline::supported(s, 1);
-    return false;
+    return s && (sizeofpixel == 1 || sizeofpixel == 2) && Pipeline::supported(s, sizeofpixel);
     });
 }
 
@@ -2024,10 +2055,7 @@ int SQYAMD_PipelineEncode_UI16_Device(const char* pipeline, const void* d_src, c
                                       long dst_capacity, long* dstlength, int nthreads, void* hip_stream)
 {
     return guarded([&]() -> int {
-    ContextLease lease;
-    if (!lease.ctx) { std::fprintf(stderr, "[sqeazy]\t no usable HIP device\n"); return 1; }
-    return encode_on_device(*lease.ctx, pipeline, d_src, shape, shape_size, 2, d_dst, (uint64_t)std::max(dst_capacity, 0l), dstlength, nthreads,
-                            static_cast<hipStream_t>(hip_stream));
+    return encode_device(pipeline, d_src, shape, shape_size, 2, d_dst, dst_capacity, nullptr, dstlength, nthreads, hip_stream, false);
     });
 }
 
@@ -2035,10 +2063,7 @@ int SQYAMD_PipelineEncode_UI8_Device(const char* pipeline, const void* d_src, co
                                      long dst_capacity, long* dstlength, int nthreads, void* hip_stream)
 {
     return guarded([&]() -> int {
-    ContextLease lease;
-    if (!lease.ctx) { std::fprintf(stderr, "[sqeazy]\t no usable HIP device\n"); return 1; }
-    return encode_on_device(*lease.ctx, pipeline, d_src, shape, shape_size, 1, d_dst, (uint64_t)std::max(dst_capacity, 0l), dstlength, nthreads,
-                            static_cast<hipStream_t>(hip_stream));
+    return encode_device(pipeline, d_src, shape, shape_size, 1, d_dst, dst_capacity, nullptr, dstlength, nthreads, hip_stream, false);
     });
 }
 
@@ -2046,11 +2071,7 @@ int SQYAMD_PipelineEncode_UI16_DeviceAt(const char* pipeline, const void* d_src,
                                         long dst_capacity, long* dstoffset, long* dstlength, int nthreads, void* hip_stream)
 {
     return guarded([&]() -> int {
-    if (!dstoffset) return 1;
-    ContextLease lease;
-    if (!lease.ctx) { std::fprintf(stderr, "[sqeazy]\t no usable HIP device\n"); return 1; }
-    return encode_on_device(*lease.ctx, pipeline, d_src, shape, shape_size, 2, d_dst, (uint64_t)std::max(dst_capacity, 0l), dstlength, nthreads,
-                            static_cast<hipStream_t>(hip_stream), dstoffset);
+    return encode_device(pipeline, d_src, shape, shape_size, 2, d_dst, dst_capacity, dstoffset, dstlength, nthreads, hip_stream, true);
     });
 }
 
@@ -2059,15 +2080,8 @@ int SQYAMD_PipelineEncode_UI16_DeviceAt_Frames(const char* pipeline, const void*
                                                long* frame_offsets, int max_entries, int* count)
 {
     return guarded([&]() -> int {
-    if (!dstoffset || every <= 0 || !frame_offsets || !count) return 1;
-    ContextLease lease;
-    if (!lease.ctx) { std::fprintf(stderr, "[sqeazy]\t no usable HIP device\n"); return 1; }
-    FrameQuery fq;
-    fq.every = every; fq.offsets = frame_offsets; fq.max_entries = max_entries;
-    const int rc = encode_on_device(*lease.ctx, pipeline, d_src, shape, shape_size, 2, d_dst, (uint64_t)std::max(dst_capacity, 0l), dstlength, nthreads,
-                                    static_cast<hipStream_t>(hip_stream), dstoffset, &fq);
-    *count = fq.count;
-    return rc;
+    FrameQuery fq{every, frame_offsets, max_entries, 0};
+    return encode_device(pipeline, d_src, shape, shape_size, 2, d_dst, dst_capacity, dstoffset, dstlength, nthreads, hip_stream, true, &fq, count);
     });
 }
 
@@ -2076,15 +2090,8 @@ int SQYAMD_PipelineEncode_UI8_DeviceAt_Frames(const char* pipeline, const void* 
                                               long* frame_offsets, int max_entries, int* count)
 {
     return guarded([&]() -> int {
-    if (!dstoffset || every <= 0 || !frame_offsets || !count) return 1;
-    ContextLease lease;
-    if (!lease.ctx) { std::fprintf(stderr, "[sqeazy]\t no usable HIP device\n"); return 1; }
-    FrameQuery fq;
-    fq.every = every; fq.offsets = frame_offsets; fq.max_entries = max_entries;
-    const int rc = encode_on_device(*lease.ctx, pipeline, d_src, shape, shape_size, 1, d_dst, (uint64_t)std::max(dst_capacity, 0l), dstlength, nthreads,
-                                    static_cast<hipStream_t>(hip_stream), dstoffset, &fq);
-    *count = fq.count;
-    return rc;
+    FrameQuery fq{every, frame_offsets, max_entries, 0};
+    return encode_device(pipeline, d_src, shape, shape_size, 1, d_dst, dst_capacity, dstoffset, dstlength, nthreads, hip_stream, true, &fq, count);
     });
 }
 
@@ -2092,11 +2099,7 @@ int SQYAMD_PipelineEncode_UI8_DeviceAt(const char* pipeline, const void* d_src, 
                                        long dst_capacity, long* dstoffset, long* dstlength, int nthreads, void* hip_stream)
 {
     return guarded([&]() -> int {
-    if (!dstoffset) return 1;
-    ContextLease lease;
-    if (!lease.ctx) { std::fprintf(stderr, "[sqeazy]\t no usable HIP device\n"); return 1; }
-    return encode_on_device(*lease.ctx, pipeline, d_src, shape, shape_size, 1, d_dst, (uint64_t)std::max(dst_capacity, 0l), dstlength, nthreads,
-                            static_cast<hipStream_t>(hip_stream), dstoffset);
+    return encode_device(pipeline, d_src, shape, shape_size, 1, d_dst, dst_capacity, dstoffset, dstlength, nthreads, hip_stream, true);
     });
 }
 
@@ -2299,13 +2302,9 @@ int SQYAMD_Header_Build(const char* pipeline, int sizeof_voxel, const long* shap
         if (!sqy::Pipeline::supported(pipeline, sizeof_voxel)) return 1;
         const sqy::Pipeline p = sqy::Pipeline::from_string(pipeline, sizeof_voxel);
         std::vector<uint64_t> shp(shape, shape + shape_size);
-        // what one encode call can have produced: < 2^31 voxels, at most INT_MAX payload bytes (decode refuses anything else)
-        uint64_t nvox = 1;
-        for (uint64_t v : shp) {
-            if ((long)v <= 0 || v >= ((uint64_t)1 << 31)) return 1;
-            nvox *= v;
-            if (nvox >= ((uint64_t)1 << 31)) return 1;
-        }
+        // what one encode call can have produced: < 2^31 voxels, every extent too, at most INT_MAX payload bytes (decode refuses anything else)
+        const uint64_t nvox = voxel_count(shape, shape_size);
+        if (nvox == 0 || nvox >= ((uint64_t)1 << 31) || *std::max_element(shp.begin(), shp.end()) >= ((uint64_t)1 << 31)) return 1;
         if (encoded_bytes > (long)INT_MAX) return 1;
         const std::string hdr = sqy::header_pack(sizeof_voxel, false, shp, p.name(), (uint64_t)encoded_bytes);
         const long need = (long)hdr.size();

@@ -226,7 +226,6 @@ hipError_t launch_bitswap1_u8_decode_lut(const uint8_t* in, uint16_t* out, uint6
 hipError_t launch_bitswap1_decode(const void* in, void* out, uint64_t len, int elem_size, hipStream_t stream);
 // one launch per frame over the columns the stage can touch (frame z needs the decoded frame z-1), the other columns one plain copy
 // -- on copy_stream next to the chain when that, fork and join are given.  (scratch: unused since round 3)
-uint64_t diff3x3x1_decode_scratch_bytes(uint64_t X);
 // diff3x3x1_decode_chain_columns: how many leading columns of a row go through that chain in the usual 16-bit geometry (a multiple of 8;
 // 0: another geometry).  left_tmp != nullptr (that geometry, in == out, both 16-byte aligned): the volume is decoded where it lies --
 // the encoded chain columns are first copied to left_tmp (same indices, a buffer of the volume's size), nothing else moves

@@ -6726,9 +6726,6 @@ hipError_t launch_bitswap1_decode(const void* in, void* out, uint64_t len, int e
     return hipGetLastError();
 }
 
-// scratch for the one-launch kernel: 256 strips x 2 edges x 2 frame parities x ceil(X / 3) words, and the abort word
-uint64_t diff3x3x1_decode_scratch_bytes(uint64_t X) { (void)X; return 0; }      // (the frame chain below needs none)
-
 // the usual geometry of the inverse (16-bit, every row's reach inside its row): the columns that go through the chain of launches --
 // the ones the stage can touch and their right-hand neighbour, whole 16-byte vectors; 0: another geometry
 uint64_t diff3x3x1_decode_chain_columns(uint64_t Z, uint64_t Y, uint64_t X, int elem_size)

@@ -981,6 +981,13 @@ std::string to_verbatim(const void* data, size_t bytes)
     return kVerbOpen + base64_encode(static_cast<const unsigned char*>(data), bytes) + kVerbClose;   // string_parsers.hpp:507-534
 }
 
+bool from_verbatim(const std::string& v, std::vector<unsigned char>* out)
+{
+    if (v.size() < 21) return false;
+    *out = base64_decode(v.substr(10, v.size() - 21));
+    return true;
+}
+
 // ---- xxh32 (LZ4 frame descriptor checksum) ----
 static inline uint32_t rotl32(uint32_t x, int r) { return (x << r) | (x >> (32 - r)); }
 static inline uint32_t rd32(const unsigned char* p) { uint32_t v; std::memcpy(&v, p, 4); return v; }

@@ -165,6 +165,9 @@ void frame_shuffle_order(const float* sums, size_t Z, size_t per_frame, uint64_t
 std::string base64_encode(const unsigned char* src, size_t n);
 std::vector<unsigned char> base64_decode(const std::string& s);
 std::string to_verbatim(const void* data, size_t bytes);
+// its inverse: false for a string shorter than the two tags (21 characters); else the 10 and 11 characters at its ends are stripped
+// (not checked) and the rest base64-decoded into *out
+bool from_verbatim(const std::string& v, std::vector<unsigned char>* out);
 
 uint32_t xxh32(const unsigned char* p, size_t len, uint32_t seed);
 

@@ -137,6 +137,12 @@ static void base64(std::mt19937& rng)
         (void)base64_decode(mutate(e, rng));
         const std::string v = to_verbatim(raw.data(), raw.size());
         CHECK(raw.empty() ? v.empty() : v.find("<verbatim>") == 0);
+        std::vector<unsigned char> back;
+        if (!raw.empty()) CHECK(from_verbatim(v, &back) && back == raw);
+        const std::string m = mutate(v, rng);
+        const bool ok = from_verbatim(m, &back);
+        CHECK(ok == (m.size() >= 21));                                       // shorter than the two tags: refused, else decoded
+        CHECK(!from_verbatim(v.substr(0, rng() % 21), &back));
     }
 }
 
