@@ -28,7 +28,7 @@ struct Lz4DedupeArgs {
 // will be cut into -- chunk k (gap_chunk bytes, a power of two) at out + k * (gap_chunk + 15), `out` any alignment; needs
 // len % 8192 == 0
 // side != nullptr (launch_diff3x3x1_side): columns x < side_w of every row of X voxels are read from the compact buffer `side`
-// digest != nullptr (round 6, frames in place only, len / 8 a multiple of gap_chunk): the NOISE DIGEST -- bucket << 16 | tag of the five bytes at
+// digest != nullptr (round 6, frames in place only, len / 8 a multiple of gap_chunk): the NOISE DIGEST -- bucket << 17 | tag of the five bytes at
 // every position liblz4's search probes from probe 961 on when it starts with a chunk and finds nothing, digest_stride
 // (= lz4_noise_digest_stride(gap_chunk)) words per chunk of the plane stream; the LZ4 parse of a chunk takes its batches from there as long
 // as nothing has matched (Lz4DedupeArgs::digest) instead of reading the plane bytes again

@@ -244,7 +244,7 @@ void bitswap1_u16_regs(const uint16_t* __restrict__ in, uint16_t* __restrict__ o
         // Those answers are left HERE, where the bytes are in registers: from probe 961 on (step >= 16: at most one probe per lane's
         // sixteen bytes) lane L works out which probe, if any, starts inside its bytes [x, x + 16) of the chunk, takes the five bytes
         // from there (the next lane's first dword through a DPP shift; the wave's last lane cannot see behind its bytes: such an entry
-        // says "look yourself"), and stores bucket << 16 | tag at digest[chunk][u - 961].  The chunk's parse wave (lz4_chunks_kernel, the
+        // says "look yourself"), and stores bucket << 17 | tag at digest[chunk][u - 961].  The chunk's parse wave (lz4_chunks_kernel, the
         // batches proved empty) takes its batches from there as long as nothing has matched.  Exact by construction: the entries are what
         // the parse computes from the same bytes.  Pieces that are all zero write nothing; a chunk with such a piece is parsed from its bytes.
         uint32_t dg = 0;                       // one register across the planes: bit 31 = a probe starts in my bytes | probe number - 961 << 4 | its byte
@@ -264,7 +264,9 @@ void bitswap1_u16_regs(const uint16_t* __restrict__ in, uint16_t* __restrict__ o
                 if (cand < x + 16u && u >= 961u && u - 961u < digest_stride) dg = 0x80000000u | ((u - 961u) << 4) | (cand - x);
             }
         }
-        const uint32_t dg_tsh = 31u - gap_shift;                            // the parse's tag width for a whole chunk (positions take gap_shift bits)
+        // the parse's tag width for a whole chunk (positions take gap_shift bits).  An entry is bucket << 17 | tag: the bucket is 12 bits, the
+        // tag at most 17 (gap_shift >= 14: chunks of 16 KiB and up, the launch guard's) -- lz4_chunks_kernel unpacks it the same way
+        const uint32_t dg_tsh = 31u - gap_shift;
         // One pass over the planes: the piece's hash, then the piece (round 6: hash and store of a plane next to each other, its four
         // registers are free behind them; two separate loops kept all sixty-four alive across sixteen branches).
         const uint32_t pm = 2u * (uint32_t)lane + 1u;                    // position inside the piece
@@ -302,7 +304,7 @@ void bitswap1_u16_regs(const uint16_t* __restrict__ in, uint16_t* __restrict__ o
                     const uint32_t d1 = dg_q == 0u ? val.y : dg_q == 1u ? val.z : dg_q == 2u ? val.w : nx;
                     const uint32_t lo = __builtin_amdgcn_alignbyte(d1, d0, dg_r);                  // bytes off .. off + 3
                     const uint32_t b5 = d1 >> (8u * dg_r);                                          // byte off + 4 (in its low byte)
-                    uint32_t e = (lz4_hash5_32(lo, b5) << 16) | ((lo * 2654435761u) >> (32u - dg_tsh));
+                    uint32_t e = (lz4_hash5_32(lo, b5) << 17) | ((lo * 2654435761u) >> (32u - dg_tsh));
                     if (lane == 63 && dg_off > 11u) e = 0xffffffffu;                                // its five bytes end in the next tile's piece
                     // (the chunk's row of the digest as a SCALAR base, the lane's entry a 32-bit offset: see the piece's address below)
                     const uint64_t drow = (B >> gap_shift) * (uint64_t)digest_stride * 4u;
@@ -1914,7 +1916,7 @@ void lz4_chunks_kernel(const uint8_t* __restrict__ in, uint64_t total, uint32_t 
                         uint32_t pos, nxt;
                         if (!digest_ok() || !geometry(pos, nxt)) { on = false; continue; }
                         const uint32_t e = dgq[k];
-                        uint32_t h = e >> 16, mytag = e & 0xffffu;
+                        uint32_t h = e >> 17, mytag = e & 0x1ffffu;          // (bitswap1_u16_regs: tags up to 17 bits, 16 KiB chunks)
                         if (ballot(e == 0xffffffffu)) {
                             if (e == 0xffffffffu) {
                                 const uint64_t seq = glb_ld_u64(w.src + pos);
@@ -3349,7 +3351,7 @@ void lz4_frame_tail_kernel(const uint8_t* __restrict__ in, uint64_t n, uint64_t 
     // place k = 1 .. kmax from the end: start(k) = n - (15 + last) - (k - 1) * (15 + chunk)
     auto start_of = [&](uint32_t k) -> int64_t { return (int64_t)n - (int64_t)(15 + last) - (int64_t)(k - 1u) * (int64_t)(15 + chunk); };
     // (every load of a thread's four places in flight at once, at clamped addresses: a place costs one trip to memory, not five)
-    for (uint32_t k0 = 1u; k0 <= kmax && k0 < first_bad; k0 += 4096u) {
+    for (uint32_t k0 = 1u; k0 <= kmax; k0 += 4096u) {
         uint32_t pz[4], mg[4], w1[4], w2[4], em[4];
         bool in_range[4];
 #pragma unroll
@@ -3376,6 +3378,11 @@ void lz4_frame_tail_kernel(const uint8_t* __restrict__ in, uint64_t n, uint64_t 
             if (!ok) atomicMin(&first_bad, k);
         }
         __syncthreads();
+        // every wave decides from its own copy, taken between two barriers: read at the loop's head, first_bad could already hold a value a
+        // faster wave's next pass wrote (k0 + 4096 itself), and the waves would leave the loop after different numbers of barriers
+        const uint32_t fb = first_bad;
+        __syncthreads();
+        if (k0 + 4096u >= fb) break;
     }
     __syncthreads();
     const uint32_t m = first_bad - 1u;

@@ -906,3 +906,30 @@ def test_stored_tail_random_streams(sqy, oracle, options):
             options("stored_tail_index", on)
             rc, back = sqy.decode(blob)
             assert rc == 0 and np.array_equal(back.reshape(-1), data), (case, on, nch, len(parts[-1]))
+
+
+@pytest.mark.parametrize("kb", [1, 4])
+def test_stored_tail_past_one_pass(sqy, oracle, options, kb):
+    """the look at the stored tail checks 4096 places per pass (lz4_frame_tail_kernel): tails of 4095 .. 8193 stored frames, the
+    first compressed frame at place 4096, 4097, 8193 (and 4098, 8194) from the end -- its second and third passes, and the exit
+    when a pass ends exactly at the tail's first frame"""
+    chunk = kb << 10
+    cfg = "(blocksize_kb=%d,framestep_kb=%d)" % (kb, kb)
+    rng = np.random.default_rng(63 + kb)
+    for m in (4095, 4096, 4097, 8192, 8193):
+        last = chunk if m % 2 == 0 else int(rng.integers(1, chunk))
+        head = [rng.integers(0, 256, chunk, dtype=np.uint8), np.zeros(chunk, np.uint8)]     # stored, then compressed at place m + 1
+        data = np.concatenate(head + [rng.integers(0, 256, (m - 1) * chunk + last, dtype=np.uint8)])
+        blob = oracle.pipeline_encode("lz4" + cfg, data.reshape(1, 1, -1), nthreads=2)
+        payload = blob[oracle.header_unpack(blob)["size"]:]
+        tail_start = len(payload) - (15 + last) - (m - 1) * (15 + chunk)
+        field = int.from_bytes(payload[15 + chunk + 7:15 + chunk + 11], "little")         # the zeros' frame: compressed, right in front
+        assert not field & 0x80000000 and 15 + chunk + 15 + field == tail_start
+        assert int.from_bytes(payload[tail_start + 7:tail_start + 11], "little") == 0x80000000 | chunk
+        for on in (1, 0):
+            options("stored_tail_index", on)
+            sqy.profile_reset(); sqy.profile_enable(True)
+            rc, back = sqy.decode(blob)
+            sqy.profile_enable(False)
+            assert rc == 0 and np.array_equal(back.reshape(-1), data), (m, on)
+            assert _rank_launches(sqy) == 1, (m, on)
