@@ -12,21 +12,28 @@ over ranks (`ms_per_step` = block time / K, `value`).  --min-seconds S repeats s
 reports the MEDIAN block (min / max next to it).  --dump-outputs DIR writes the blob of the last timed step as .npy files.  value = (N * input bytes * K) / block time, GB = 1e9 bytes.
 
 N > 1: slabs are independent sqeazy blobs.  `value` is measured with the blobs left on the GPUs that made them (a sharded
-container; only the 8-byte sizes -- its index -- are all_gathered over RCCL per step).  `with_gather` is the same run with
+container; only the 8-byte sizes -- its index -- are all_gathered over RCCL per step).  `with_gather` (--full) is the same run with
 north_star's final RCCL gather of the compressed slabs to rank 0 inside every step, posted from a gather thread so that it
 overlaps the next steps' encodes (double-buffered root ingress).
 
-The JSON line also carries
+A plain run does only what `value` needs: it sets up, warms up, times the steps, writes --dump-outputs and prints the line.
+That line carries
   roofline      the dominant kernel (largest share of device time, HIP events on the launch stream inside the timed
                 region) priced at the path's ALGORITHMIC bytes per call (2 B per voxel read once + payload bytes written
-                once: SURVEY.md 8(d)) against 8 TB/s; `alone_*` = the same with one call at a time; `traffic` = PMC bytes
-                per launch from the committed rocprofv3 passes of THIS library build (profiles/, matched by sha256), else null
+                once: SURVEY.md 8(d)) against 8 TB/s; `traffic` = PMC bytes per launch from the committed rocprofv3 passes
+                of THIS library build (profiles/, matched by sha256), else null
+  build         sha256 and compile flags of libsqeazy_amd.so
+--full runs every other leg after the timed steps and adds what it measured or checked:
+  verified      the last blob of every caller thread hashed against the reference pieces' digest (tests/golden/headline.json)
+  single_call   one call at a time (latency, rate, `roofline.alone_*`); serial_layout: the nthreads = 1 layout and its decode
+  config.default_options, other_operating_points   the timed leg with every option at its default, fewer calls in flight
   cpu_baseline  the reference's own SSE bit-plane gather + liblz4 1.9.3 frames (oracle/_ref) on the host cores, the two
                 C calls alone on the full 1 GiB stack: one thread and all cores
   host_abi      the same stack through the reference-protocol entry point SQY_PipelineEncode_UI16 (host pointers, PCIe)
   config.secondary   device time and roofline fraction of the other BASELINE configs and of north_star's target
                 (2048^3 uint16 as 8 sequential 2048x2048x256 slab calls on this GPU); N = 1 only
-  build         sha256 and compile flags of libsqeazy_amd.so
+  with_gather   N > 1 only (above)
+--quick trims --full to the legs that take seconds (verified, single_call, serial_layout, with_gather): profiling runs.
 """
 import argparse
 import ctypes
@@ -563,14 +570,19 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--quick", action="store_true", help="main measurement only (no CPU baseline, host ABI, secondary configs): profiling runs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, run every other leg (checks against the reference digests, one call at a time, the serial "
+                         "layout, other operating points, CPU baseline, host ABI, the other BASELINE configs, N>1: the gather); "
+                         "off: the timed steps and the line alone")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
+    ap.add_argument("--quick", action="store_true",
+                    help="with --full: no default-options leg, other operating points, CPU baseline, host ABI, secondary configs: profiling runs")
     ap.add_argument("--min-seconds", type=float, default=0.0,
                     help="keep timing blocks of --steps steps until this much has been timed (default: one block, exactly --steps timed steps)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the last timed step computed (rank 0's blob: its size, head, a seeded sample and its sha256) as DIR/<name>.npy")
     ap.add_argument("--frames", type=int, default=SHAPE[0], help="z extent per GPU (default: the BASELINE config)")
-    ap.add_argument("--no-gather", action="store_true", help="N>1: skip the second measurement with the RCCL gather to rank 0 inside the step")
+    ap.add_argument("--no-gather", action="store_true", help="N>1 with --full: skip the second measurement with the RCCL gather to rank 0 inside the step")
     ap.add_argument("--slabs-inflight", type=int, default=SLABS_INFLIGHT)
     ap.add_argument("--inflight", type=int, default=4,
                     help="C-ABI calls in flight per GPU (host threads, one stream + workspace each; the C-ABI is re-entrant like "
@@ -630,7 +642,7 @@ def main():
     # every caller thread owns a stream and two output buffers (the gather of step s may still read one while s+inflight encodes)
     streams = [torch.cuda.Stream(device=dev) for _ in range(inflight)]
     outs = [[torch.empty(cap, dtype=torch.uint8, device=dev) for _ in range(2)] for _ in range(inflight)]
-    gatherer = multi.SlabGatherer(world * cap, dev) if (dist_on and not args.no_gather) else None
+    gatherer = multi.SlabGatherer(world * cap, dev) if (dist_on and args.full and not args.no_gather) else None
     torch.cuda.synchronize()
 
     # the C call of every (thread, buffer), marshalled once: what a C caller's loop looks like (no Python object is built per step)
@@ -706,13 +718,20 @@ def main():
     sqeazy_amd.profile_enable(False)
     prof = sqeazy_amd.profile_get()
     nblocks = len(times)
+    # size and header of a blob of the timed region itself, read before any other leg reuses its buffer
+    timed_blob_bytes, timed_header_bytes = None, None
+    for t in range(inflight):
+        if last_blob[t] is not None:
+            b, off, n = last_blob[t]
+            timed_blob_bytes, timed_header_bytes = n, sqeazy_amd.header_size(outs[t][b][off:off + min(n, 65536)].cpu().numpy().tobytes())
+            break
     if args.dump_outputs and rank == 0:
         # the blob of the last timed step (step K-1 is thread (K-1) % inflight's last), before any other leg reuses its buffer
         b, off, n = last_blob[(args.steps - 1) % inflight]
         dump_outputs(args.dump_outputs, outs[(args.steps - 1) % inflight][b][off:off + n])
     # the same leg as an unchanged caller gets it: every option at its default (the transposes of caller streams are not chained)
     default_leg = None
-    if world == 1 and not args.quick:
+    if args.full and world == 1 and not args.quick:
         fence()
         t0 = time.perf_counter()
         run_steps(args.steps)
@@ -721,33 +740,30 @@ def main():
         default_leg = {"value": round(nbytes * args.steps / dt0 / 1e9, 1), "unit": "GB/s", "ms_per_step": round(dt0 / args.steps * 1e3, 4),
                        "options": {k: sqeazy_amd.get_option(k) for k in ("transpose_chain", "transpose_chain_caller_streams")},
                        "timing": "one block of %d steps" % args.steps}
-    # What was timed is also checked (after the clock stopped): the LAST blob of every caller thread is hashed and compared with the
-    # digest the reference pieces themselves give for this stack (tests/golden/headline.json: reference SSE bit-plane gather + liblz4
-    # 1.9.3 frames, oracle/gen_golden.py --headline; a data file, nothing of oracle/ runs here)
-    digests = []
-    timed_blob_bytes, timed_header_bytes = None, None      # of a blob of the timed region itself, read before any other leg reuses a buffer
-    for t in range(inflight):
-        if last_blob[t] is not None:
-            b, off, n = last_blob[t]
-            raw = outs[t][b][off:off + n].cpu().numpy().tobytes()
-            digests.append(hashlib.sha256(raw).hexdigest())
-            if timed_blob_bytes is None:
-                timed_blob_bytes, timed_header_bytes = n, sqeazy_amd.header_size(raw[:65536])
-            del raw
-    verify = {"verified": False, "blobs_hashed": len(digests), "blob_sha256": digests[0] if digests else None,
-              "threads_agree": len(set(digests)) == 1}
-    try:
-        with open(os.path.join(ROOT, "tests", "golden", "headline.json")) as f:
-            for g in json.load(f)["stacks"]:
-                if tuple(g["shape_zyx"]) == tuple(shape) and g["z_offset"] == rank * shape[0] and g["z_total"] == world * shape[0]:
-                    verify["reference_blob_sha256"] = g["blob_sha256"]
-                    verify["payload_sha256"] = g["payload_sha256"]
-                    verify["against"] = "tests/golden/headline.json (%s): %s" % (g["name"], g["source"])
-                    verify["verified"] = bool(digests) and all(d == g["blob_sha256"] for d in digests)
-    except Exception as e:   # reported, never fatal for the measurement
-        verify["error"] = repr(e)
-    if "against" not in verify:
-        verify["against"] = "no reference digest for this shape (only the BASELINE stack has one); threads compared with each other"
+    # --full: what was timed is also checked (after the clock stopped): the LAST blob of every caller thread is hashed and compared
+    # with the digest the reference pieces themselves give for this stack (tests/golden/headline.json: reference SSE bit-plane gather +
+    # liblz4 1.9.3 frames, oracle/gen_golden.py --headline; a data file, nothing of oracle/ runs here)
+    verify = None
+    if args.full:
+        digests = []
+        for t in range(inflight):
+            if last_blob[t] is not None:
+                b, off, n = last_blob[t]
+                digests.append(hashlib.sha256(outs[t][b][off:off + n].cpu().numpy().tobytes()).hexdigest())
+        verify = {"verified": False, "blobs_hashed": len(digests), "blob_sha256": digests[0] if digests else None,
+                  "threads_agree": len(set(digests)) == 1}
+        try:
+            with open(os.path.join(ROOT, "tests", "golden", "headline.json")) as f:
+                for g in json.load(f)["stacks"]:
+                    if tuple(g["shape_zyx"]) == tuple(shape) and g["z_offset"] == rank * shape[0] and g["z_total"] == world * shape[0]:
+                        verify["reference_blob_sha256"] = g["blob_sha256"]
+                        verify["payload_sha256"] = g["payload_sha256"]
+                        verify["against"] = "tests/golden/headline.json (%s): %s" % (g["name"], g["source"])
+                        verify["verified"] = bool(digests) and all(d == g["blob_sha256"] for d in digests)
+        except Exception as e:   # reported, never fatal for the measurement
+            verify["error"] = repr(e)
+        if "against" not in verify:
+            verify["against"] = "no reference digest for this shape (only the BASELINE stack has one); threads compared with each other"
 
     per_rank = per_rank_report(False)
     gather_times, gather_stats, per_rank_gather = None, None, None
@@ -762,7 +778,7 @@ def main():
     # other operating points of the same step, for comparison with earlier rounds (round-3 advice): fewer calls in flight, and the entry
     # point that leaves the blob at the start of the destination (no frames in place: the payload is gathered)
     alt = {}
-    if world == 1 and not args.quick:
+    if args.full and world == 1 and not args.quick:
         def alt_point(n_inflight, fn_name):
             fn = getattr(sqeazy_amd.lib(), fn_name)
             errs = []
@@ -802,23 +818,25 @@ def main():
         except Exception as e:   # reported, never required
             alt["error"] = repr(e)
     # one call at a time (nothing else in flight), for the record: latency of the call and the kernels' undisturbed durations
-    fence()
-    sqeazy_amd.profile_reset()
-    sqeazy_amd.profile_enable(True)
-    single = []
-    for _ in range(5):
-        tl = time.perf_counter()
-        rc, single_off, _n = sqeazy_amd.encode_device_at(PIPELINE, vol.data_ptr(), shape, np.uint16, outs[0][0].data_ptr(), cap, nthreads=0,
-                                                         stream=streams[0].cuda_stream)
-        torch.cuda.synchronize()
-        single.append((time.perf_counter() - tl) * 1e3)
-    sqeazy_amd.profile_enable(False)
-    prof_alone = sqeazy_amd.profile_get()
-    fence()
+    single, prof_alone = None, {}
+    if args.full:
+        fence()
+        sqeazy_amd.profile_reset()
+        sqeazy_amd.profile_enable(True)
+        single = []
+        for _ in range(5):
+            tl = time.perf_counter()
+            rc, single_off, _n = sqeazy_amd.encode_device_at(PIPELINE, vol.data_ptr(), shape, np.uint16, outs[0][0].data_ptr(), cap, nthreads=0,
+                                                             stream=streams[0].cuda_stream)
+            torch.cuda.synchronize()
+            single.append((time.perf_counter() - tl) * 1e3)
+        sqeazy_amd.profile_enable(False)
+        prof_alone = sqeazy_amd.profile_get()
+        fence()
     # the layout every default caller of the reference asks for (nthreads = 1: one block-linked frame), one call at a time; its blob is
     # hashed against the digest the reference pieces give for that layout (tests/golden/headline.json "serial")
     serial_layout = None
-    if rank == 0:
+    if args.full and rank == 0:
         try:
             sqeazy_amd.profile_reset()
             sqeazy_amd.profile_enable(True)
@@ -873,8 +891,6 @@ def main():
         algo_bytes = nbytes + payload_bytes                  # 2 B/voxel read once + payload written once
         achieved = (algo_bytes / 1e9) / (avg_ms / 1e3) if avg_ms else 0.0
         ident = lib_identity()
-        alone_ms = prof_alone[dom][0] / max(prof_alone[dom][1], 1) if dom in prof_alone else None
-        single_ms = min(single)
         mode = "%d calls in flight" % inflight
         line = {
             "metric": "encode GB/s (input voxels) for bitswap1->lz4 uint16 volume",
@@ -889,31 +905,37 @@ def main():
                 "input_bytes_per_gpu": nbytes, "payload_bytes": payload_bytes, "blob_bytes": payload, "calls_in_flight_per_gpu": inflight,
                 "env": {"GPU_MAX_HW_QUEUES": os.environ.get("GPU_MAX_HW_QUEUES")},
                 "options": options_timed, "options_note": "transpose_chain_caller_streams is OFF by default (include/sqeazy_amd.h): `value` is measured with the "
-                                                         "caller opting in; `default_options` is the same leg without",
-                "default_options": default_leg,
-                "single_call_latency_ms": round(single_ms, 4),
-                "one_call_at_a_time": {"value": round(nbytes / (single_ms / 1e3) / 1e9, 1), "unit": "GB/s",
-                                       "roofline_frac_whole_call": round(algo_bytes / (single_ms / 1e3) / 1e9 / HBM_PEAK_GBS, 5)}},
+                                                         "caller opting in; `default_options` (--full) is the same leg without"},
             "roofline": {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": None,
                          # every kernel of the call together: algorithmic bytes of one step / wall time of one step
                          "whole_step_frac": round((algo_bytes / 1e9) / (dt / args.steps) / HBM_PEAK_GBS, 5),
                          "algorithmic_bytes_per_launch": algo_bytes, "avg_launch_ms": round(avg_ms, 4), "launches_timed": dom_n,
-                         # the same kernel with the GPU to itself (one call at a time, measured right after the timed region)
-                         "alone_launch_ms": round(alone_ms, 4) if alone_ms else None,
-                         "alone_frac": round((algo_bytes / 1e9) / (alone_ms / 1e3) / HBM_PEAK_GBS, 5) if alone_ms else None,
                          "kernels_ms_per_step": {k: round(v[0] / max(v[1], 1), 4) for k, v in prof.items()}},
-            # one call at a time (what the sqy tool, the HDF5 filter and the Java binding do): latency of the call, its rate, and
-            # the whole call's algorithmic bytes against the roofline
-            "single_call": {"ms": round(single_ms, 4), "value": round(nbytes / (single_ms / 1e3) / 1e9, 1), "unit": "GB/s",
-                            "roofline_frac": round(algo_bytes / (single_ms / 1e3) / 1e9 / HBM_PEAK_GBS, 5),
-                            "kernels_ms": {k: round(v[0] / max(v[1], 1), 4) for k, v in prof_alone.items()}},
-            "verified": verify["verified"], "payload_sha256": verify.get("payload_sha256"), "verification": verify,
-            "serial_layout": serial_layout,
-            "other_operating_points": alt,
             "entry_point": "SQYAMD_PipelineEncode_UI16_DeviceAt (device pointers; the blob may start anywhere in the destination: frames in place)",
             "build": ident,
         }
+        if args.full:
+            alone_ms = prof_alone[dom][0] / max(prof_alone[dom][1], 1) if dom in prof_alone else None
+            single_ms = min(single)
+            line["config"].update({
+                "default_options": default_leg,
+                "single_call_latency_ms": round(single_ms, 4),
+                "one_call_at_a_time": {"value": round(nbytes / (single_ms / 1e3) / 1e9, 1), "unit": "GB/s",
+                                       "roofline_frac_whole_call": round(algo_bytes / (single_ms / 1e3) / 1e9 / HBM_PEAK_GBS, 5)}})
+            # the same kernel with the GPU to itself (one call at a time, measured right after the timed region)
+            line["roofline"].update({
+                "alone_launch_ms": round(alone_ms, 4) if alone_ms else None,
+                "alone_frac": round((algo_bytes / 1e9) / (alone_ms / 1e3) / HBM_PEAK_GBS, 5) if alone_ms else None})
+            line.update({
+                # one call at a time (what the sqy tool, the HDF5 filter and the Java binding do): latency of the call, its rate, and
+                # the whole call's algorithmic bytes against the roofline
+                "single_call": {"ms": round(single_ms, 4), "value": round(nbytes / (single_ms / 1e3) / 1e9, 1), "unit": "GB/s",
+                                "roofline_frac": round(algo_bytes / (single_ms / 1e3) / 1e9 / HBM_PEAK_GBS, 5),
+                                "kernels_ms": {k: round(v[0] / max(v[1], 1), 4) for k, v in prof_alone.items()}},
+                "verified": verify["verified"], "payload_sha256": verify.get("payload_sha256"), "verification": verify,
+                "serial_layout": serial_layout,
+                "other_operating_points": alt})
         # launches of every kernel per encode call inside the timed region (1 each on this stack; a dense second pass would count too)
         ncalls = max(nblocks * args.steps, 1)
         tr = measured_traffic(ident["sha256"], dom, {k: v[1] / ncalls for k, v in prof.items()})
@@ -938,7 +960,7 @@ def main():
         if per_rank is not None:
             line["per_rank"] = per_rank
             line["world_size_rccl"] = per_rank["world_size_rccl"]
-        if world == 1 and not args.quick:
+        if args.full and world == 1 and not args.quick:
             vol_host = vol.cpu().numpy()
             if not args.no_cpu_baseline:
                 try:

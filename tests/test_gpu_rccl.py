@@ -103,7 +103,7 @@ def test_bench_self_spawn_and_distributed_path_on_one_gpu():
     env = dict(os.environ)
     env.update({"SQY_BENCH_FORCE_SPAWN": "1", "SQY_BENCH_FORCE_DIST": "1", "HSA_ENABLE_IPC_MODE_LEGACY": "0", "MASTER_ADDR": "127.0.0.1"})
     env.pop("WORLD_SIZE", None); env.pop("RANK", None); env.pop("LOCAL_RANK", None)
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--quick", "--steps", "3", "--warmup", "1", "--min-seconds", "0.05"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--full", "--quick", "--steps", "3", "--warmup", "1", "--min-seconds", "0.05"],
                        env=env, capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -1,12 +1,12 @@
 #!/bin/bash
-# GPU box: plain bench + rocprofv3 kernel trace + the two HBM counter passes, all over the default bench command.
+# On an MI355X: the full bench line, then a rocprofv3 kernel trace and the HBM / wave counter passes over bench.py --full --quick.
 # Outputs under gpurun_out/prof/; condense afterwards (here) with tools/summarize_profile.py <tag>.
 set -o pipefail
 cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 P=gpurun_out/prof
 rm -rf $P; mkdir -p $P      # (delete your local gpurun_out/prof before fetching: gpurun merges, it does not remove stale files)
-B="bench.py"
+B="bench.py --full"
 timeout -k 10 500 python3 $B > $P/bench_plain.log 2>&1 || exit 1
 tail -1 $P/bench_plain.log | cut -c1-400
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $P/trace -- python3 $B --quick > $P/bench_trace.log 2>&1 || exit 1

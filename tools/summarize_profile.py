@@ -68,7 +68,7 @@ for f in newest(os.path.join(src, "trace", "*", "*_kernel_stats.csv")):
         if is_ours(r["Name"]):
             rows.append(r)
 with open(os.path.join(dst, "%s_kernel_stats.csv" % tag), "w") as f:
-    f.write("# rocprofv3 --kernel-trace --stats -- python3 bench.py --quick  (defaults: 30 steps, 5 warm-up, 4 calls in flight)   (sqy:: kernels only)\n")
+    f.write("# rocprofv3 --kernel-trace --stats -- python3 bench.py --full --quick  (defaults: 30 steps, 5 warm-up, 4 calls in flight)   (sqy:: kernels only)\n")
     w = csv.writer(f)
     w.writerow(["Name", "Calls", "TotalDurationNs", "AverageNs", "MinNs", "MaxNs", "StdDev"])
     for r in sorted(rows, key=lambda r: -float(r["TotalDurationNs"])):
@@ -95,7 +95,7 @@ with open(os.path.join(dst, "%s_pmc_hbm.csv" % tag), "w") as f:
 sha_file = os.path.join(src, "library_sha256.txt")
 sha = open(sha_file).read().strip() if os.path.exists(sha_file) else None
 # bench.py reports `roofline.traffic` from this file only when it was collected on the very library build it is running
-json.dump({"library_sha256": sha, "command": "rocprofv3 --pmc FETCH_SIZE|WRITE_SIZE --kernel-trace -- python3 bench.py --quick",
+json.dump({"library_sha256": sha, "command": "rocprofv3 --pmc FETCH_SIZE|WRITE_SIZE --kernel-trace -- python3 bench.py --full --quick",
            "hbm_bytes": "(2 * FETCH_SIZE + WRITE_SIZE) * 1024 per launch, mean over launches", "traffic": traffic},
           open(os.path.join(dst, "%s_pmc_hbm.json" % tag), "w"), indent=1, sort_keys=True)
 # wave-level counters (what the waves wait for), summed over the XCDs' instances of a launch, mean over launches
@@ -111,7 +111,7 @@ for name in ("pmc_sq1", "pmc_sq2", "pmc_sq3"):
 if sq:
     names = sorted({c for k in sq for c in sq[k]})
     with open(os.path.join(dst, "%s_pmc_sq.csv" % tag), "w") as f:
-        f.write("# rocprofv3 --pmc <SQ counters> --kernel-trace -- python3 bench.py --quick (three passes); per launch, mean over launches\n")
+        f.write("# rocprofv3 --pmc <SQ counters> --kernel-trace -- python3 bench.py --full --quick (three passes); per launch, mean over launches\n")
         w = csv.writer(f)
         w.writerow(["kernel"] + names)
         for k in sorted(sq):
