@@ -158,6 +158,23 @@ SQY_FUNCTION_PREFIX int SQYAMD_PipelineEncode_UI8_Cap(const char* pipeline, cons
 SQY_FUNCTION_PREFIX int SQYAMD_Decode_UI16_Device(const void* d_src, long srclength, void* d_dst, long dst_capacity, void* hip_stream);
 SQY_FUNCTION_PREFIX int SQYAMD_Decode_UI8_Device(const void* d_src, long srclength, void* d_dst, long dst_capacity, void* hip_stream);
 
+/* Frames [z0, z0 + nz) of a blob -- the index along shape[0], any rank -- decoded into d_dst: nz * (shape[1] * ... ) voxels,
+ * exactly the bytes SQYAMD_Decode_*_Device writes at d_dst + z0 * frame_bytes.  Nothing outside [d_dst, d_dst + nz * frame_bytes)
+ * is written.  Returns 1 for a bad range, a too-small dst_capacity, a blob of the other voxel type, or a malformed header.  A damaged
+ * frame that the range needs gives SQY_Decode's composite code.
+ * Stream, context and ordering rules are those of SQYAMD_Decode_*_Device (several host threads may call at once).  In the chunked LZ4
+ * layout (nthreads >= 2 at encode time) of `lz4`, `bitswap1->lz4`, `quantiser->bitswap1->lz4` (16-bit) and `frame_shuffle->lz4`, each
+ * optionally behind rmestbkrd / rmbkrd_neighbor5x5x5 heads, only the LZ4 frames the range needs are decoded (a damaged frame OUTSIDE
+ * the range then goes unnoticed: DESIGN.md 7); every other blob is decoded whole into the library's workspace and the range copied
+ * out -- same bytes, the full decode's time. */
+SQY_FUNCTION_PREFIX int SQYAMD_Decode_Frames_UI16_Device(const void* d_src, long srclength, long z0, long nz, void* d_dst, long dst_capacity,
+                                                         void* hip_stream);
+SQY_FUNCTION_PREFIX int SQYAMD_Decode_Frames_UI8_Device(const void* d_src, long srclength, long z0, long nz, void* d_dst, long dst_capacity,
+                                                        void* hip_stream);
+/* host-pointer variants: the blob is staged as in SQY_Decode_*, and only the range comes back */
+SQY_FUNCTION_PREFIX int SQYAMD_Decode_Frames_UI16(const char* src, long srclength, long z0, long nz, char* dst, long dst_capacity);
+SQY_FUNCTION_PREFIX int SQYAMD_Decode_Frames_UI8(const char* src, long srclength, long z0, long nz, char* dst, long dst_capacity);
+
 /* ------------------------------------------------------------------------------------------------
  * Section C -- several GPUs (no reference counterpart: sqeazy is a single process with OpenMP loops)
  *
@@ -212,6 +229,8 @@ SQY_FUNCTION_PREFIX void SQYAMD_Release_Workspace(void);
  *   "host_l2_bytes"                   the host CPU's L2 size as the reference reads it (CPUID; 0 .. 2^32-1)  rmestbkrd samples
  *                                     `Y*X > L2 ? (size_t)(L2 * .75) : Y*X` voxels of its two z faces -- a PARAMETER of the stage's result
  *                                     (the one option that changes bytes): set it to the value of the host whose blobs are to be matched
+ *   "decode_frames_subset"            1 [SQY_NO_DECODE_FRAMES_SUBSET=1 -> 0]  SQYAMD_Decode_Frames_*: only the LZ4 frames the range needs, where
+ *                                     the pipeline allows (0: every blob decoded whole and the range copied out -- same bytes)
  * Set: 0 = done, 1 = unknown name or value out of range.  Get: the value, -1 for an unknown name. */
 SQY_FUNCTION_PREFIX int SQYAMD_Set_Option(const char* name, long value);
 SQY_FUNCTION_PREFIX long SQYAMD_Get_Option(const char* name);

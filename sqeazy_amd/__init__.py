@@ -29,6 +29,7 @@ EXPORTED_SYMBOLS = (
     "SQYAMD_PipelineEncode_Slabs_UI16_Device", "SQYAMD_PipelineEncode_Slabs_UI8_Device",
     "SQYAMD_PipelineEncode_UI16_Cap", "SQYAMD_PipelineEncode_UI8_Cap",
     "SQYAMD_Decode_UI16_Device", "SQYAMD_Decode_UI8_Device",
+    "SQYAMD_Decode_Frames_UI16_Device", "SQYAMD_Decode_Frames_UI8_Device", "SQYAMD_Decode_Frames_UI16", "SQYAMD_Decode_Frames_UI8",
     "SQYAMD_Profile_Enable", "SQYAMD_Profile_Reset", "SQYAMD_Profile_Get",
     "SQYAMD_Release_Workspace", "SQYAMD_Set_Option", "SQYAMD_Get_Option", "SQYAMD_Version", "SQYAMD_Header_Pipeline", "SQYAMD_Header_Build",
     "SQYAMD_Comm_UniqueId", "SQYAMD_Comm_Init", "SQYAMD_Comm_Destroy", "SQYAMD_Gather_Blobs",
@@ -83,6 +84,10 @@ def lib():
             getattr(L, f).argtypes = [ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_int]
         for f in ("SQYAMD_Decode_UI8_Device", "SQYAMD_Decode_UI16_Device"):
             getattr(L, f).argtypes = [ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p]
+        for f in ("SQYAMD_Decode_Frames_UI8_Device", "SQYAMD_Decode_Frames_UI16_Device"):
+            getattr(L, f).argtypes = [ctypes.c_void_p, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p]
+        for f in ("SQYAMD_Decode_Frames_UI8", "SQYAMD_Decode_Frames_UI16"):
+            getattr(L, f).argtypes = [ctypes.c_void_p, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_void_p, ctypes.c_long]
         _lib = L
     return _lib
 
@@ -248,6 +253,28 @@ def decode(blob, nthreads=0):
     src = np.frombuffer(blob, dtype=np.uint8)
     rc = getattr(lib(), "SQY_Decode_" + _suffix(dtype))(src.ctypes.data, ctypes.c_long(len(blob)), out.ctypes.data, ctypes.c_int(nthreads))
     return (rc, None) if rc else (0, out)
+
+
+def decode_frames(blob, z0, nz):
+    """SQYAMD_Decode_Frames_UI8/UI16: frames [z0, z0 + nz) of the blob (along shape[0]); returns (rc, ndarray or None)."""
+    blob = bytes(blob)
+    size = decompressed_sizeof(blob)
+    shape = decompressed_shape(blob)
+    if size not in (1, 2) or not shape:
+        return 1, None
+    dtype = np.uint16 if size == 2 else np.uint8
+    out = np.empty((max(int(nz), 0),) + tuple(shape[1:]), dtype=dtype)
+    src = np.frombuffer(blob, dtype=np.uint8)
+    rc = getattr(lib(), "SQYAMD_Decode_Frames_" + _suffix(dtype))(src.ctypes.data, ctypes.c_long(len(blob)), ctypes.c_long(int(z0)),
+                                                                  ctypes.c_long(int(nz)), out.ctypes.data, ctypes.c_long(out.nbytes))
+    return (rc, None) if rc else (0, out)
+
+
+def decode_frames_device(d_src, srclength, z0, nz, d_dst, dst_capacity, dtype, stream=None):
+    """SQYAMD_Decode_Frames_*_Device on raw device pointers (ints); returns rc."""
+    return getattr(lib(), "SQYAMD_Decode_Frames_%s_Device" % _suffix(dtype))(
+        ctypes.c_void_p(int(d_src)), ctypes.c_long(int(srclength)), ctypes.c_long(int(z0)), ctypes.c_long(int(nz)), ctypes.c_void_p(int(d_dst)),
+        ctypes.c_long(int(dst_capacity)), ctypes.c_void_p(stream or 0))
 
 
 def set_option(name, value):

@@ -71,13 +71,14 @@ struct Options {
     std::atomic<long> transpose_blocks_per_cu;          // frames in place: workgroups of the transposer's grid per CU
     std::atomic<long> stored_tail_index;                // decode, chunked layout: the stored frames at the stream's end are found where they must start, not by the scan
     std::atomic<long> host_l2_bytes;                    // rmestbkrd: the host CPU's L2 size as the reference's compass reads it (detected; tests set it)
+    std::atomic<long> decode_frames_subset;             // frame-range decode: only the LZ4 frames the range needs, where the pipeline allows (0: full decode + copy)
     Options()
         : transpose_chain(env_flag("SQY_NO_TRANSPOSE_CHAIN") ? 0 : 1), transpose_chain_caller_streams(env_flag("SQY_TRANSPOSE_CHAIN_CALLER_STREAMS")),
           block_parallel(env_flag("SQY_NO_BLOCK_PARALLEL") ? 0 : 1), block_parallel_warmup(env_number("SQY_BLOCK_PARALLEL_WARMUP", 65536, 0, kWarmupMax)),
           block_parallel_stats(env_flag("SQY_BLOCK_PARALLEL_STATS")), tail_scan(env_flag("SQY_NO_TAIL_SCAN") ? 0 : 1),
           decode_two_waves(env_flag("SQY_NO_DECODE_TWO_WAVES") ? 0 : 1), noise_digest(env_flag("SQY_NO_NOISE_DIGEST") ? 0 : 1),
           transpose_blocks_per_cu(env_number("SQY_TRANSPOSE_BLOCKS_PER_CU", 32, 1, 64)), stored_tail_index(env_flag("SQY_NO_STORED_TAIL_INDEX") ? 0 : 1),
-          host_l2_bytes((long)sqy::host_l2_cache_bytes()) { sqy::set_bitswap1_blocks_per_cu(transpose_blocks_per_cu.load()); }
+          host_l2_bytes((long)sqy::host_l2_cache_bytes()), decode_frames_subset(env_flag("SQY_NO_DECODE_FRAMES_SUBSET") ? 0 : 1) { sqy::set_bitswap1_blocks_per_cu(transpose_blocks_per_cu.load()); }
     std::atomic<long>* find(const char* name)
     {
         if (!name) return nullptr;
@@ -92,6 +93,7 @@ struct Options {
         if (!std::strcmp(name, "transpose_blocks_per_cu")) return &transpose_blocks_per_cu;
         if (!std::strcmp(name, "stored_tail_index")) return &stored_tail_index;
         if (!std::strcmp(name, "host_l2_bytes")) return &host_l2_bytes;
+        if (!std::strcmp(name, "decode_frames_subset")) return &decode_frames_subset;
         return nullptr;
     }
 };
@@ -206,11 +208,14 @@ struct Workspace {
     DevBuf diff_side;         // diff3x3x1 in front of a 16-bit bitswap1: the columns the stage can touch (outside the ping/pong rotation)
     DevBuf digest;            // frames in place: the noise digest the transpose leaves for the LZ4 parse (19 KB per 256 KiB chunk)
     DevBuf bkrd;              // rmestbkrd: the four face histograms and their supports
+    DevBuf subset;            // frame-range decode: the frame list, the subset's block index, the frame_shuffle map of the range
+    DevBuf range_full;        // frame-range decode of a blob the subset path does not take: the whole volume, the range copied out
     void* pinned = nullptr;   // 4 KiB of pinned host memory for small read-backs
     void release_buffers()
     {
         ping.release(); pong.release(); lz4_scratch.release(); csize.release(); frame_off.release();
         io_src.release(); io_dst.release(); small.release(); plan.release(); dedupe.release(); diff_side.release(); spec.release(); digest.release(); bkrd.release();
+        subset.release(); range_full.release();
     }
 };
 
@@ -1772,16 +1777,155 @@ struct DecodeCall {
         SQY_TIMED("frame_scatter", sqy::launch_frame_scatter(cur, out, Z, frame_bytes_dec, static_cast<const uint64_t*>(ws->small.p), stream));
         return produced(out, in_bytes(si));
     }
+
+    // ---- frame-range decode (SQYAMD_Decode_Frames_*) ----
+    // Frames [z0, z0 + nz) of the volume (fb bytes each) into d_dst, decoding only the LZ4 frames they need.  Taken for the chunked
+    // layout of  [heads ->] lz4 | bitswap1->lz4 | quantiser->bitswap1->lz4 | frame_shuffle->lz4  (the background heads decode as a copy);
+    // *taken = false for anything else, with nothing written to d_dst (the caller decodes the whole blob).  The decoder's verdict is
+    // left in lz4_flag, as by lz4_frames.
+    std::vector<unsigned char> sub_host;   // the tables uploaded to ws->subset (alive until the call's last synchronisation)
+
+    int frames_subset(uint64_t z0, uint64_t nz, uint64_t fb, bool* taken)
+    {
+        *taken = false;
+        const size_t ns = pipe.stages.size();
+        if (ns == 0 || pipe.stages[ns - 1].kind != StageKind::lz4 || lead >= ns) return 0;
+        const size_t li = ns - 1, nfront = li - lead;
+        auto kind = [&](size_t i) { return pipe.stages[i].kind; };
+        enum Form { PLAIN, PLANES, PLANES_LUT, SHUFFLE } form;
+        if (nfront == 0) form = PLAIN;
+        else if (nfront == 1 && kind(lead) == StageKind::bitswap1) form = PLANES;
+        else if (nfront == 1 && kind(lead) == StageKind::frame_shuffle) form = SHUFFLE;
+        else if (nfront == 2 && kind(lead) == StageKind::quantiser && kind(lead + 1) == StageKind::bitswap1) form = PLANES_LUT;
+        else return 0;
+        const int e = h.elem_size();
+        const uint64_t total = in_bytes(li);
+        // the stream in front of lz4 holds the voxels in their order (PLANES_LUT: one quantised byte per voxel)
+        if (total != n * (uint64_t)(form == PLANES_LUT ? 1 : e)) return 0;
+        if (form == PLANES && (elem_before[lead] != e || count_before[lead] != n)) return 0;
+        if (form == PLANES_LUT && (e != 2 || elem_before[lead + 1] != 1 || count_before[lead + 1] != n)) return 0;
+        if (form == SHUFFLE && !(h.shape.size() == 3 && in_bytes(lead) == total)) return 0;
+        Lz4Index ix;
+        if (const int rc = lz4_index(li, total, ix)) return rc;
+        const uint32_t nframes = ix.hc[0];
+        if (nframes < 2 || nframes != ix.nchunks) return 0;          // one frame, or the serial layout: the history runs from the start
+        const uint64_t chunk = ix.chunk;
+
+        std::vector<uint32_t> ids;                                     // the LZ4 frames to decode, ascending
+        std::vector<uint64_t> remap;                                   // SHUFFLE: place (relative to the range's first) of every slot decoded
+        uint64_t out_bytes = 0;
+        uint8_t* sbuf = nullptr;                                       // where the subset decodes to
+        uint64_t pa = 0, pb = 0, fbp = 0;                              // SHUFFLE: places [pa, pb) of fbp bytes cover the range
+        std::vector<uint64_t> coff;                                    // else: offset of frame f in the compacted stream
+        if (form == SHUFFLE) {
+            // the lz4_remap conditions: whole chunks inside whole places
+            if (total % chunk != 0) return 0;
+            uint64_t P = 0;
+            bool permutation = true;
+            if (const int rc = frame_shuffle_prepare(lead, P, fbp, permutation)) return rc;
+            if (!(fbp && fbp % chunk == 0 && P * fbp == total)) return 0;
+            pa = z0 * fb / fbp;
+            pb = ((z0 + nz) * fb + fbp - 1) / fbp;
+            const uint64_t cpf = fbp / chunk;
+            // fs_map has every slot but the last one named for a place struck (~0): the last one wins, as in the full decode
+            for (uint64_t i = 0; i < P; ++i) {
+                uint64_t v;
+                std::memcpy(&v, fs_map.data() + 8 * i, 8);
+                if (v == ~0ull || v < pa || v >= pb) continue;
+                remap.push_back(v - pa);
+                for (uint64_t c = 0; c < cpf; ++c) ids.push_back((uint32_t)(i * cpf + c));
+            }
+            out_bytes = (pb - pa) * fbp;
+        } else {
+            // byte spans of the stream in front of lz4 that the range needs
+            std::vector<std::pair<uint64_t, uint64_t>> spans;
+            const uint64_t vpf = n / h.shape[0], v0 = z0 * vpf, v1 = (z0 + nz) * vpf;
+            if (form == PLAIN)
+                spans.push_back({v0 * (uint64_t)e, v1 * (uint64_t)e});
+            else {
+                const uint64_t we = form == PLANES ? (uint64_t)e : 1, W = 8 * we, seg = n / W, L = seg * W;
+                const uint64_t w0 = std::min(v0 / W, seg), w1 = std::min((v1 + W - 1) / W, seg);
+                if (w0 < w1) for (uint64_t s = 0; s < W; ++s) spans.push_back({(s * seg + w0) * we, (s * seg + w1) * we});
+                if (v1 > L) spans.push_back({std::max(v0, L) * we, v1 * we});
+            }
+            std::vector<char> need(nframes, 0);
+            for (const auto& sp : spans) for (uint64_t f = sp.first / chunk; f <= (sp.second - 1) / chunk; ++f) need[f] = 1;
+            coff.assign(nframes, 0);
+            for (uint32_t f = 0; f < nframes; ++f) {
+                if (!need[f]) continue;
+                coff[f] = out_bytes;
+                ids.push_back(f);
+                out_bytes += std::min<uint64_t>(chunk, total - (uint64_t)f * chunk);
+            }
+        }
+
+        // the tables: ids | subset frame starts | remap | subset block index
+        const uint64_t nsel = ids.size(), mpf = (chunk + ix.block_bytes - 1) / ix.block_bytes;
+        const uint64_t o_ff = (nsel * 4 + 15) & ~15ull, o_map = o_ff + (((nsel + 1) * 4 + 15) & ~15ull), o_blk = o_map + ((remap.size() * 8 + 15) & ~15ull);
+        if (ws->subset.ensure(std::max<uint64_t>(o_blk + nsel * mpf * 16, 16))) return 1;
+        sub_host.assign(o_blk, 0);
+        if (nsel) std::memcpy(sub_host.data(), ids.data(), nsel * 4);
+        if (!remap.empty()) std::memcpy(sub_host.data() + o_map, remap.data(), remap.size() * 8);
+        uint8_t* d_sub = static_cast<uint8_t*>(ws->subset.p);
+        if (o_blk) SQY_HIP(hipMemcpyAsync(d_sub, sub_host.data(), o_blk, hipMemcpyHostToDevice, stream));
+
+        *taken = true;
+        // SHUFFLE with the range on place boundaries (frame_chunk_size 1): straight into d_dst; else through the workspace
+        const bool direct = form == SHUFFLE && pa * fbp == z0 * fb && pb * fbp == (z0 + nz) * fb;
+        sbuf = direct ? static_cast<uint8_t*>(d_dst) : work_buf(out_bytes);
+        if (!sbuf) return 1;
+        if (form == SHUFFLE) {
+            // places of the range that no slot names come out as zeros (frame_shuffle's inverse)
+            std::vector<char> named(pb - pa, 0);
+            for (uint64_t v : remap) named[v] = 1;
+            for (uint64_t k = 0; k < pb - pa;) {
+                if (named[k]) { ++k; continue; }
+                uint64_t k1 = k;
+                while (k1 < pb - pa && !named[k1]) ++k1;
+                SQY_HIP(hipMemsetAsync(sbuf + k * fbp, 0, (k1 - k) * fbp, stream));
+                k = k1;
+            }
+        }
+        if (nsel) {
+            SQY_TIMED("lz4_frames_subset_decode",
+                      sqy::launch_lz4_frames_subset_decode(cur, ix.blk, ix.frame_first, nframes, reinterpret_cast<const uint32_t*>(d_sub), (uint32_t)nsel,
+                                                           (uint32_t)mpf, d_sub + o_blk, reinterpret_cast<uint32_t*>(d_sub + o_ff), sbuf, out_bytes, chunk,
+                                                           ix.block_bytes, ix.hc[3], ix.counts + 4, stream,
+                                                           form == SHUFFLE ? reinterpret_cast<const uint64_t*>(d_sub + o_map) : nullptr, fbp,
+                                                           g_opt.decode_two_waves.load() && ix.hc[1] == nframes));
+            lz4_flag = ix.counts + 4;
+            lz4_flag_stage = (int)li;
+        }
+        auto compact = [&](uint64_t b) { const uint64_t f = b / chunk; return coff[f] + (b - f * chunk); };
+        const uint64_t range_bytes = nz * fb;
+        if (form == SHUFFLE) {
+            if (!direct) SQY_TIMED("frames_range_copy", hipMemcpyAsync(d_dst, sbuf + (z0 * fb - pa * fbp), range_bytes, hipMemcpyDeviceToDevice, stream));
+        } else if (form == PLAIN) {
+            SQY_TIMED("frames_range_copy", hipMemcpyAsync(d_dst, sbuf + compact(z0 * fb), range_bytes, hipMemcpyDeviceToDevice, stream));
+        } else {
+            const uint64_t we = form == PLANES ? (uint64_t)e : 1, W = 8 * we, seg = n / W, L = seg * W;
+            const uint64_t vpf = n / h.shape[0];
+            sqy::Bitswap1Range r{};
+            r.v0 = z0 * vpf; r.v1 = (z0 + nz) * vpf; r.L = L;
+            r.w0 = std::min(r.v0 / W, seg); r.w1 = std::min((r.v1 + W - 1) / W, seg);
+            if (r.w0 < r.w1) for (uint64_t s = 0; s < W; ++s) r.plane[s] = compact((s * seg + r.w0) * we);
+            if (r.v1 > L) r.tail = compact(std::max(r.v0, L) * we);
+            const uint16_t* lut = nullptr;
+            if (form == PLANES_LUT) {
+                if (quantiser_lut_to_device(pipe.stages[lead], ws)) return 1;
+                lut = static_cast<const uint16_t*>(ws->small.p);
+            }
+            SQY_TIMED(lut ? "bitswap1_quantiser_decode_range" : "bitswap1_decode_range",
+                      sqy::launch_bitswap1_decode_range(sbuf, d_dst, r, (int)we, lut, stream));
+        }
+        return 0;
+    }
 };
 
-int decode_on_device(Context& cx, const void* d_src_v, uint64_t srclen, void* d_dst, uint64_t dst_capacity, int want_elem, hipStream_t stream)
+// the header of a blob in device memory: a prefix of the blob fetched, grown until the delimiter is inside
+int fetch_header(const uint8_t* d_src, uint64_t srclen, hipStream_t stream, sqy::HeaderInfo& h)
 {
-    if (!d_src_v || !d_dst) return 1;
-    const uint8_t* d_src = static_cast<const uint8_t*>(d_src_v);
-    DrainOnExit drain{stream, &cx.pending, cx.side};
-    // header: fetch a prefix of the blob, grow until the delimiter is inside
     std::vector<char> head;
-    sqy::HeaderInfo h;
     for (uint64_t want = 1 << 16;; want *= 16) {
         const uint64_t take = std::min<uint64_t>(want, srclen);
         head.resize(take);
@@ -1791,6 +1935,16 @@ int decode_on_device(Context& cx, const void* d_src_v, uint64_t srclen, void* d_
         if (h.valid || take == srclen) break;
     }
     if (!h.valid) { std::fprintf(stderr, "[sqeazy]\t unable to find a sqy header in the blob\n"); return 1; }
+    return 0;
+}
+
+int decode_on_device(Context& cx, const void* d_src_v, uint64_t srclen, void* d_dst, uint64_t dst_capacity, int want_elem, hipStream_t stream)
+{
+    if (!d_src_v || !d_dst) return 1;
+    const uint8_t* d_src = static_cast<const uint8_t*>(d_src_v);
+    DrainOnExit drain{stream, &cx.pending, cx.side};
+    sqy::HeaderInfo h;
+    if (fetch_header(d_src, srclen, stream, h)) return 1;
     const int elem = h.elem_size();
     if (elem != want_elem) { std::fprintf(stderr, "[sqeazy]\t blob holds %s voxels\n", h.type.c_str()); return 1; }
     std::string why;
@@ -1836,6 +1990,92 @@ int decode_on_device(Context& cx, const void* d_src_v, uint64_t srclen, void* d_
         std::fprintf(stderr, "[sqy::lz4] corrupt LZ4 block, or a frame that does not decode to its share of the volume\n");
         return c.stage_error((size_t)c.lz4_flag_stage);
     }
+    return 0;
+}
+
+// Frames [z0, z0 + nz) of the blob (the index along shape[0]) into d_dst: the subset path (DecodeCall::frames_subset) where it applies and
+// the option allows, else the whole blob decoded into the workspace and the range copied out.  Same checks as decode_on_device, plus
+// the range and the capacity for it -- all before anything is written.
+int decode_frames_on_device(Context& cx, const void* d_src_v, uint64_t srclen, long z0, long nz, void* d_dst, uint64_t dst_capacity, int want_elem,
+                            hipStream_t stream)
+{
+    if (!d_src_v || !d_dst) return 1;
+    const uint8_t* d_src = static_cast<const uint8_t*>(d_src_v);
+    std::vector<PendingEvent>* pend = &cx.pending;
+    DrainOnExit drain{stream, &cx.pending, cx.side};
+    sqy::HeaderInfo h;
+    if (fetch_header(d_src, srclen, stream, h)) return 1;
+    const int elem = h.elem_size();
+    if (elem != want_elem) { std::fprintf(stderr, "[sqeazy]\t blob holds %s voxels\n", h.type.c_str()); return 1; }
+    std::string why;
+    if (!Pipeline::supported(h.pipename, elem, &why)) {
+        std::fprintf(stderr, "[sqeazy]\t%s cannot be build with this version of sqeazy (%s)\n", h.pipename.c_str(), why.c_str());
+        return 1;
+    }
+    uint64_t raw_bytes = 0;
+    if (!header_shape_ok(h, srclen, &raw_bytes)) return 1;
+    const uint64_t Z = h.shape[0], fb = raw_bytes / Z;
+    if (z0 < 0 || nz <= 0 || (uint64_t)z0 + (uint64_t)nz > Z) {
+        std::fprintf(stderr, "[sqeazy]\t decode frames: range [%ld, %ld + %ld) outside the blob's %llu frames\n", z0, z0, nz, (unsigned long long)Z);
+        return 1;
+    }
+    const uint64_t range_bytes = (uint64_t)nz * fb;
+    if (range_bytes > dst_capacity) { std::fprintf(stderr, "[sqeazy]\t decode frames: buffer too small\n"); return 1; }
+
+    if (g_opt.decode_frames_subset.load()) {
+        DecodeCall c(cx, stream, d_dst, h, Pipeline::from_string(h.pipename), raw_bytes / (uint64_t)elem, d_src + h.size);
+        bool taken = false;
+        if (const int rc = c.frames_subset((uint64_t)z0, (uint64_t)nz, fb, &taken)) return rc;
+        if (taken) {
+            if (c.lz4_flag) SQY_HIP(hipMemcpyAsync(cx.ws.pinned, c.lz4_flag, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+            SQY_HIP(hipStreamSynchronize(stream));
+            if (g_prof_on.load()) prof_collect(cx.pending);
+            if (c.lz4_flag && *static_cast<const uint32_t*>(cx.ws.pinned)) {
+                std::fprintf(stderr, "[sqy::lz4] corrupt LZ4 block, or a frame that does not decode to its share of the volume\n");
+                return c.stage_error((size_t)c.lz4_flag_stage);
+            }
+            return 0;
+        }
+    }
+    // every other blob: the whole volume, then the range
+    if (cx.ws.range_full.ensure(std::max<uint64_t>(raw_bytes, 16))) return 1;
+    if (const int rc = decode_on_device(cx, d_src_v, srclen, cx.ws.range_full.p, raw_bytes, want_elem, stream)) return rc;
+    SQY_TIMED("frames_range_copy", hipMemcpyAsync(d_dst, static_cast<const uint8_t*>(cx.ws.range_full.p) + (uint64_t)z0 * fb, range_bytes,
+                                                  hipMemcpyDeviceToDevice, stream));
+    SQY_HIP(hipStreamSynchronize(stream));
+    if (g_prof_on.load()) prof_collect(cx.pending);
+    return 0;
+}
+
+// host-pointer frame-range decode: the blob staged as in decode_from_host, only the range comes back
+int decode_frames_from_host(const char* src, long srclength, long z0, long nz, char* dst, long dst_capacity, int elem_size)
+{
+    if (!src || !dst || srclength <= 0) return 1;
+    const sqy::HeaderInfo h = sqy::header_unpack(src, src + srclength);
+    if (!h.valid) { std::fprintf(stderr, "[sqeazy]\t unable to find a sqy header in the blob\n"); return 1; }
+    uint64_t raw = 0;
+    if (!header_shape_ok(h, (uint64_t)srclength, &raw)) return 1;           // untrusted input: before anything is allocated or uploaded
+    if (h.elem_size() != elem_size) { std::fprintf(stderr, "[sqeazy]\t blob holds %s voxels\n", h.type.c_str()); return 1; }
+    const uint64_t Z = h.shape[0], fb = raw / Z;
+    if (z0 < 0 || nz <= 0 || (uint64_t)z0 + (uint64_t)nz > Z || (uint64_t)nz * fb > (uint64_t)std::max(dst_capacity, 0l)) {
+        std::fprintf(stderr, "[sqeazy]\t decode frames: range [%ld, %ld + %ld) outside the blob's %llu frames, or buffer too small\n", z0, z0, nz,
+                     (unsigned long long)Z);
+        return 1;
+    }
+    const uint64_t range_bytes = (uint64_t)nz * fb;
+    if (!device_present()) { std::fprintf(stderr, "[sqeazy]\t no MI355X (HIP device) visible: sqeazy_amd has no CPU path\n"); return 1; }
+    ContextLease lease;
+    if (!lease.ctx) { std::fprintf(stderr, "[sqeazy]\t no usable HIP device\n"); return 1; }
+    Workspace* ws = &lease.ctx->ws;
+    hipStream_t stream = lease.ctx->own_stream();
+    if (!stream) { std::fprintf(stderr, "[sqeazy]\t no HIP stream\n"); return 1; }
+    if (ws->io_src.ensure(std::max<uint64_t>((uint64_t)srclength, 16)) || ws->io_dst.ensure(std::max<uint64_t>(range_bytes, 16))) return 1;
+    int dev_id = 0;
+    SQY_HIP(hipGetDevice(&dev_id));
+    if (!lease.ctx->stager.copy(ws->io_src.p, const_cast<char*>(src), (size_t)srclength, true, dev_id)) { std::fprintf(stderr, "[sqeazy]\t host to device transfer failed\n"); return 1; }
+    const int rc = decode_frames_on_device(*lease.ctx, ws->io_src.p, (uint64_t)srclength, z0, nz, ws->io_dst.p, range_bytes, elem_size, stream);
+    if (rc) return rc;
+    if (!lease.ctx->stager.copy(ws->io_dst.p, dst, range_bytes, false, dev_id)) { std::fprintf(stderr, "[sqeazy]\t device to host transfer failed\n"); return 1; }
     return 0;
 }
 
@@ -2220,6 +2460,36 @@ int SQYAMD_Decode_UI16_Device(const void* d_src, long srclength, void* d_dst, lo
     if (!lease.ctx) { std::fprintf(stderr, "[sqeazy]\t no usable HIP device\n"); return 1; }
     return decode_on_device(*lease.ctx, d_src, (uint64_t)std::max(srclength, 0l), d_dst, (uint64_t)std::max(dst_capacity, 0l), 2, static_cast<hipStream_t>(hip_stream));
     });
+}
+
+int SQYAMD_Decode_Frames_UI16_Device(const void* d_src, long srclength, long z0, long nz, void* d_dst, long dst_capacity, void* hip_stream)
+{
+    return guarded([&]() -> int {
+    ContextLease lease;
+    if (!lease.ctx) { std::fprintf(stderr, "[sqeazy]\t no usable HIP device\n"); return 1; }
+    return decode_frames_on_device(*lease.ctx, d_src, (uint64_t)std::max(srclength, 0l), z0, nz, d_dst, (uint64_t)std::max(dst_capacity, 0l), 2,
+                                   static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+int SQYAMD_Decode_Frames_UI8_Device(const void* d_src, long srclength, long z0, long nz, void* d_dst, long dst_capacity, void* hip_stream)
+{
+    return guarded([&]() -> int {
+    ContextLease lease;
+    if (!lease.ctx) { std::fprintf(stderr, "[sqeazy]\t no usable HIP device\n"); return 1; }
+    return decode_frames_on_device(*lease.ctx, d_src, (uint64_t)std::max(srclength, 0l), z0, nz, d_dst, (uint64_t)std::max(dst_capacity, 0l), 1,
+                                   static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+int SQYAMD_Decode_Frames_UI16(const char* src, long srclength, long z0, long nz, char* dst, long dst_capacity)
+{
+    return guarded([&]() -> int { return decode_frames_from_host(src, srclength, z0, nz, dst, dst_capacity, 2); });
+}
+
+int SQYAMD_Decode_Frames_UI8(const char* src, long srclength, long z0, long nz, char* dst, long dst_capacity)
+{
+    return guarded([&]() -> int { return decode_frames_from_host(src, srclength, z0, nz, dst, dst_capacity, 1); });
 }
 
 int SQYAMD_Decode_UI8_Device(const void* d_src, long srclength, void* d_dst, long dst_capacity, void* hip_stream)

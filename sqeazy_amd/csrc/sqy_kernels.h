@@ -224,6 +224,25 @@ hipError_t launch_lz4_frames_decode(const uint8_t* in, const void* blk, const ui
 bool bitswap1_u8_decode_lut_possible(const void* in, const void* out, uint64_t len);
 hipError_t launch_bitswap1_u8_decode_lut(const uint8_t* in, uint16_t* out, uint64_t len, const uint16_t* lut, hipStream_t stream);
 hipError_t launch_bitswap1_decode(const void* in, void* out, uint64_t len, int elem_size, hipStream_t stream);
+// ---- frame-range decode (SQYAMD_Decode_Frames_*) ----
+// LZ4 frames ids[0..nsel) of a chunked-layout stream (the full index: blk, frame_first of nframes frames), decoded by the kernels of
+// launch_lz4_frames_decode: subset frame i to out + i * frame_stride (ids ascending: the frames' bytes back to back, out_bytes = their
+// sum), or with remap to remap[i * frame_stride / remap_bytes] * remap_bytes + the rest (out_bytes a multiple of remap_bytes).
+// sblk (nsel * max_per_frame * 16 bytes) and sff (nsel + 1 words): the subset's block index, built on the device.  *errflag as there.
+hipError_t launch_lz4_frames_subset_decode(const uint8_t* in, const void* blk, const uint32_t* frame_first, uint32_t nframes,
+                                           const uint32_t* ids, uint32_t nsel, uint32_t max_per_frame, void* sblk, uint32_t* sff,
+                                           uint8_t* out, uint64_t out_bytes, uint64_t frame_stride, uint64_t block_bytes, uint32_t ncompressed,
+                                           uint32_t* errflag, hipStream_t stream, const uint64_t* remap = nullptr, uint64_t remap_bytes = 0,
+                                           bool two_waves = false);
+// inverse bitswap1 of plane words [w0, w1) into voxels [v0, v1) (out[v - v0]; W = 8 * elem_size voxels per word): stored plane segment s
+// of the range starts at in + plane[s] (byte offsets), the voxels [max(v0, L), v1) behind the planes (L = segment words * W) at
+// in + tail.  lut != nullptr (elem_size 1): 16-bit voxels out of the quantiser's decode table (quantiser->bitswap1)
+struct Bitswap1Range {
+    uint64_t plane[16];
+    uint64_t tail;
+    uint64_t w0, w1, v0, v1, L;
+};
+hipError_t launch_bitswap1_decode_range(const uint8_t* in, void* out, const Bitswap1Range& r, int elem_size, const uint16_t* lut, hipStream_t stream);
 // one launch per frame over the columns the stage can touch (frame z needs the decoded frame z-1), the other columns one plain copy
 // -- on copy_stream next to the chain when that, fork and join are given.  (scratch: unused since round 3)
 // diff3x3x1_decode_chain_columns: how many leading columns of a row go through that chain in the usual 16-bit geometry (a multiple of 8;

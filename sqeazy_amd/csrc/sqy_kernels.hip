@@ -16,6 +16,7 @@
 #include <mutex>
 #include <stdint.h>
 #include <cstring>
+#include <type_traits>
 
 #include "sqy_kernels.h"
 
@@ -6730,6 +6731,134 @@ hipError_t launch_bitswap1_decode(const void* in, void* out, uint64_t len, int e
         hipLaunchKernelGGL((bitswap1_decode_kernel<uint16_t>), dim3((unsigned)rb), dim3(256), 0, stream, (const uint16_t*)in, (uint16_t*)out, len, seg, w0);
     } else
         hipLaunchKernelGGL((bitswap1_decode_kernel<uint8_t>), dim3((unsigned)blocks), dim3(256), 0, stream, (const uint8_t*)in, (uint8_t*)out, len, seg, (uint64_t)0);
+    return hipGetLastError();
+}
+
+// ---- frame-range decode (SQYAMD_Decode_Frames_*): a subset of the LZ4 frames, a range of the bit-plane words ----------------------
+// The subset's own block index: frame ids[i]'s blocks of the full index (blk, frame_first) copied to sblk, sff[i] = where they start
+// there, sff[nsel] = the end -- then the decode kernels above run on it unchanged (subset frame i decodes to out + i * frame_stride).
+// One workgroup: a thread counts the blocks of its share of the list, the counts are scanned in LDS, every thread copies its share.
+// A frame with no block or more than max_per_frame (the chunk's blocks: a damaged index) gets none: the decode kernel then reports it.
+__global__ __launch_bounds__(1024)
+void lz4_subset_index_kernel(const uint4* __restrict__ blk, const uint32_t* __restrict__ frame_first, uint32_t nframes,
+                             const uint32_t* __restrict__ ids, uint32_t nsel, uint32_t max_per_frame, uint4* __restrict__ sblk,
+                             uint32_t* __restrict__ sff, uint32_t* __restrict__ errflag)
+{
+    __shared__ uint32_t scan[1024];
+    const uint32_t t = threadIdx.x;
+    const uint32_t per = (nsel + 1023u) / 1024u;
+    const uint32_t i0 = t * per < nsel ? t * per : nsel, i1 = i0 + per < nsel ? i0 + per : nsel;
+    auto blocks_of = [&](uint32_t i) -> uint32_t {
+        const uint32_t f = ids[i];
+        if (f >= nframes) return 0u;
+        const uint32_t nb = frame_first[f + 1] - frame_first[f];
+        return nb <= max_per_frame ? nb : 0u;
+    };
+    uint32_t mine = 0;
+    for (uint32_t i = i0; i < i1; ++i) mine += blocks_of(i);
+    scan[t] = mine;
+    __syncthreads();
+    for (uint32_t d = 1; d < 1024u; d <<= 1) {                      // inclusive scan
+        const uint32_t add = t >= d ? scan[t - d] : 0u;
+        __syncthreads();
+        scan[t] += add;
+        __syncthreads();
+    }
+    uint32_t at = scan[t] - mine;
+    for (uint32_t i = i0; i < i1; ++i) {
+        sff[i] = at;
+        const uint32_t nb = blocks_of(i);
+        if (nb == 0) { atomicExch(errflag, 1u); continue; }
+        const uint32_t b0 = frame_first[ids[i]];
+        for (uint32_t k = 0; k < nb; ++k) sblk[at + k] = blk[b0 + k];
+        at += nb;
+    }
+    if (t == 1023u) sff[nsel] = scan[1023];
+}
+
+hipError_t launch_lz4_frames_subset_decode(const uint8_t* in, const void* blk, const uint32_t* frame_first, uint32_t nframes,
+                                           const uint32_t* ids, uint32_t nsel, uint32_t max_per_frame, void* sblk, uint32_t* sff,
+                                           uint8_t* out, uint64_t out_bytes, uint64_t frame_stride, uint64_t block_bytes, uint32_t ncompressed,
+                                           uint32_t* errflag, hipStream_t stream, const uint64_t* remap, uint64_t remap_bytes, bool two_waves)
+{
+    if (nsel == 0) return hipSuccess;
+    if (max_per_frame == 0 || frame_stride == 0 || (!remap && out_bytes > (uint64_t)nsel * frame_stride)) return hipErrorInvalidValue;
+    if (remap && (remap_bytes == 0 || remap_bytes % frame_stride != 0 || out_bytes % remap_bytes != 0)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(lz4_subset_index_kernel, dim3(1), dim3(1024), 0, stream, (const uint4*)blk, frame_first, nframes, ids, nsel, max_per_frame,
+                       (uint4*)sblk, sff, errflag);
+    // the kernel choice of launch_lz4_frames_decode, on the subset's counts
+    const uint32_t nc = ncompressed < nsel ? ncompressed : nsel;
+    if (two_waves && !(nc > SQY_RING8_MIN && nsel > SQY_RING8_MIN)) {
+        if (nc > 768u && nsel > 768u)
+            hipLaunchKernelGGL(lz4_frames_decode2_kernel<16384>, dim3(nsel), dim3(128), 0, stream, in, (const uint4*)sblk, sff, out,
+                               out_bytes, frame_stride, block_bytes, errflag, remap, remap_bytes);
+        else
+            hipLaunchKernelGGL(lz4_frames_decode2_kernel<65536>, dim3(nsel), dim3(128), 0, stream, in, (const uint4*)sblk, sff, out,
+                               out_bytes, frame_stride, block_bytes, errflag, remap, remap_bytes);
+    } else if (nc > SQY_RING8_MIN && nsel > SQY_RING8_MIN)
+        hipLaunchKernelGGL(lz4_frames_decode_kernel<8192>, dim3(nsel), dim3(64), 0, stream, in, (const uint4*)sblk, sff, out,
+                           out_bytes, frame_stride, block_bytes, errflag, remap, remap_bytes);
+    else if (nc > 768u && nsel > 768u)
+        hipLaunchKernelGGL(lz4_frames_decode_kernel<16384>, dim3(nsel), dim3(64), 0, stream, in, (const uint4*)sblk, sff, out,
+                           out_bytes, frame_stride, block_bytes, errflag, remap, remap_bytes);
+    else
+        hipLaunchKernelGGL(lz4_frames_decode_kernel<65536>, dim3(nsel), dim3(64), 0, stream, in, (const uint4*)sblk, sff, out,
+                           out_bytes, frame_stride, block_bytes, errflag, remap, remap_bytes);
+    const uint32_t slices = (uint32_t)((block_bytes + DEC_COPY_SLICE - 1) / DEC_COPY_SLICE);
+    if (slices == 0 || (uint64_t)nsel * slices > 0x7fffffffull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(lz4_stored_frames_copy_kernel, dim3(nsel * slices), dim3(256), 0, stream, in, (const uint4*)sblk, sff,
+                       out, out_bytes, frame_stride, slices, remap, remap_bytes);
+    return hipGetLastError();
+}
+
+// Inverse bitswap1 of plane words [w0, w1) only (bitswap1_decode_kernel's arithmetic): word i of the range of stored plane segment s is
+// read at in + plane[s] + i * sizeof(T), voxel v of [v0, v1) is written to out[v - v0]; the voxels [max(v0, L), v1) behind the planes
+// (the encoder copies the len % W tail verbatim) come from in + tail.  lut != nullptr (8-bit planes of quantiser->bitswap1): 16-bit
+// values out of the quantiser's decode table.
+template <typename T, bool LUT>
+__global__ __launch_bounds__(256)
+void bitswap1_decode_range_kernel(const uint8_t* __restrict__ in, void* __restrict__ out_v, Bitswap1Range a, const uint16_t* __restrict__ lut)
+{
+    constexpr uint32_t W = sizeof(T) * 8;
+    typedef typename std::conditional<LUT, uint16_t, T>::type O;
+    __shared__ uint16_t sl[LUT ? 256 : 1];
+    if (LUT) { sl[threadIdx.x] = lut[threadIdx.x]; __syncthreads(); }
+    O* __restrict__ out = static_cast<O*>(out_v);
+    const uint64_t nw = a.w1 - a.w0;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < nw; i += (uint64_t)gridDim.x * 256u) {
+        uint32_t plane[W];
+#pragma unroll
+        for (uint32_t b = 0; b < W; ++b) plane[b] = *reinterpret_cast<const T*>(in + a.plane[W - 1 - b] + i * sizeof(T));
+        const uint64_t base = (a.w0 + i) * W;
+#pragma unroll
+        for (uint32_t j = 0; j < W; ++j) {
+            uint32_t v = 0;
+#pragma unroll
+            for (uint32_t b = 0; b < W; ++b) v |= ((plane[b] >> (W - 1 - j)) & 1u) << b;
+            if (base + j >= a.v0 && base + j < a.v1) out[base + j - a.v0] = LUT ? (O)sl[v & 0xffu] : (O)v;
+        }
+    }
+    if (blockIdx.x == 0) {
+        const uint64_t t0 = a.v0 > a.L ? a.v0 : a.L;
+        for (uint64_t v = t0 + threadIdx.x; v < a.v1; v += 256u) {
+            const T x = *reinterpret_cast<const T*>(in + a.tail + (v - t0) * sizeof(T));
+            out[v - a.v0] = LUT ? (O)sl[(uint32_t)x & 0xffu] : (O)x;
+        }
+    }
+}
+
+hipError_t launch_bitswap1_decode_range(const uint8_t* in, void* out, const Bitswap1Range& r, int elem_size, const uint16_t* lut, hipStream_t stream)
+{
+    if (r.v1 <= r.v0 || r.w1 < r.w0 || (elem_size != 1 && elem_size != 2) || (lut && elem_size != 1)) return hipErrorInvalidValue;
+    uint64_t g = (r.w1 - r.w0 + 255) / 256;
+    if (g == 0) g = 1;                                                  // (block 0 also moves the tail)
+    if (g > 8192) g = 8192;
+    if (elem_size == 2)
+        hipLaunchKernelGGL((bitswap1_decode_range_kernel<uint16_t, false>), dim3((unsigned)g), dim3(256), 0, stream, in, out, r, lut);
+    else if (lut)
+        hipLaunchKernelGGL((bitswap1_decode_range_kernel<uint8_t, true>), dim3((unsigned)g), dim3(256), 0, stream, in, out, r, lut);
+    else
+        hipLaunchKernelGGL((bitswap1_decode_range_kernel<uint8_t, false>), dim3((unsigned)g), dim3(256), 0, stream, in, out, r, lut);
     return hipGetLastError();
 }
 
