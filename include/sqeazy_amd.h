@@ -175,6 +175,28 @@ SQY_FUNCTION_PREFIX int SQYAMD_Decode_Frames_UI8_Device(const void* d_src, long 
 SQY_FUNCTION_PREFIX int SQYAMD_Decode_Frames_UI16(const char* src, long srclength, long z0, long nz, char* dst, long dst_capacity);
 SQY_FUNCTION_PREFIX int SQYAMD_Decode_Frames_UI8(const char* src, long srclength, long z0, long nz, char* dst, long dst_capacity);
 
+/* The volume a set of z-slab blobs makes, decoded with one call: the inverse of SQYAMD_PipelineEncode_Slabs_*_Device and the reader of
+ * the multi-GPU container.  Blob i lies at d_src + offsets[i], lengths[i] bytes (host arrays; any alignment).  Every blob is a complete sqeazy
+ * blob of the entry point's voxel type; all have the same rank and the same shape[1..]; their shape[0] may differ.  Slab i's voxels land at
+ * d_dst + (frames[0] + .. + frames[i-1]) * frame_bytes -- exactly the bytes SQYAMD_Decode_*_Device writes for that blob.
+ * frames (host, may be NULL): out, shape[0] of every blob.  Nothing outside [d_dst, d_dst + volume bytes) is written.
+ * Blobs that end in lz4 in the chunked layout (nthreads >= 2 at encode time) are decoded in groups: the frame index of every blob of a group
+ * in one launch, one LZ4 decode launch for all of them, then each blob's remaining inverses into its place.  A group holds blobs while their
+ * LZ4 output stays within 4 GiB (at least one); inflight > 0 also caps the blobs per group (<= 0: only the 4 GiB bound) -- it bounds the
+ * workspace.  Every other blob (the serial layout, no lz4, a single chunk) is decoded on its own, as by SQYAMD_Decode_*_Device; a set may mix both.
+ * Stream, context and ordering rules as SQYAMD_Decode_*_Device.  Return: 0, 1 (bad arguments / headers -- nslabs <= 0, a NULL pointer, an
+ * invalid header, another voxel type, rank or shape[1..], a dst_capacity below the volume -- checked before anything is written), or the
+ * composite code SQY_Decode gives the first damaged blob in slab order. */
+SQY_FUNCTION_PREFIX int SQYAMD_Decode_Slabs_UI16_Device(const void* d_src, const long* offsets, const long* lengths, int nslabs,
+                                                        void* d_dst, long dst_capacity, long* frames, int inflight, void* hip_stream);
+SQY_FUNCTION_PREFIX int SQYAMD_Decode_Slabs_UI8_Device(const void* d_src, const long* offsets, const long* lengths, int nslabs,
+                                                       void* d_dst, long dst_capacity, long* frames, int inflight, void* hip_stream);
+/* host-pointer variants: the blobs staged as in SQY_Decode_*, the volume comes back */
+SQY_FUNCTION_PREFIX int SQYAMD_Decode_Slabs_UI16(const char* src, const long* offsets, const long* lengths, int nslabs,
+                                                 char* dst, long dst_capacity, long* frames);
+SQY_FUNCTION_PREFIX int SQYAMD_Decode_Slabs_UI8(const char* src, const long* offsets, const long* lengths, int nslabs,
+                                                char* dst, long dst_capacity, long* frames);
+
 /* ------------------------------------------------------------------------------------------------
  * Section C -- several GPUs (no reference counterpart: sqeazy is a single process with OpenMP loops)
  *
@@ -231,6 +253,8 @@ SQY_FUNCTION_PREFIX void SQYAMD_Release_Workspace(void);
  *                                     (the one option that changes bytes): set it to the value of the host whose blobs are to be matched
  *   "decode_frames_subset"            1 [SQY_NO_DECODE_FRAMES_SUBSET=1 -> 0]  SQYAMD_Decode_Frames_*: only the LZ4 frames the range needs, where
  *                                     the pipeline allows (0: every blob decoded whole and the range copied out -- same bytes)
+ *   "decode_slabs_joint"              1 [SQY_NO_DECODE_SLABS_JOINT=1 -> 0]  SQYAMD_Decode_Slabs_*: the chunked LZ4 blobs of a group indexed and
+ *                                     decoded by one launch each (0: every blob on its own, as by SQYAMD_Decode_*_Device -- same bytes)
  * Set: 0 = done, 1 = unknown name or value out of range.  Get: the value, -1 for an unknown name. */
 SQY_FUNCTION_PREFIX int SQYAMD_Set_Option(const char* name, long value);
 SQY_FUNCTION_PREFIX long SQYAMD_Get_Option(const char* name);

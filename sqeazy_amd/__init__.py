@@ -30,6 +30,7 @@ EXPORTED_SYMBOLS = (
     "SQYAMD_PipelineEncode_UI16_Cap", "SQYAMD_PipelineEncode_UI8_Cap",
     "SQYAMD_Decode_UI16_Device", "SQYAMD_Decode_UI8_Device",
     "SQYAMD_Decode_Frames_UI16_Device", "SQYAMD_Decode_Frames_UI8_Device", "SQYAMD_Decode_Frames_UI16", "SQYAMD_Decode_Frames_UI8",
+    "SQYAMD_Decode_Slabs_UI16_Device", "SQYAMD_Decode_Slabs_UI8_Device", "SQYAMD_Decode_Slabs_UI16", "SQYAMD_Decode_Slabs_UI8",
     "SQYAMD_Profile_Enable", "SQYAMD_Profile_Reset", "SQYAMD_Profile_Get",
     "SQYAMD_Release_Workspace", "SQYAMD_Set_Option", "SQYAMD_Get_Option", "SQYAMD_Version", "SQYAMD_Header_Pipeline", "SQYAMD_Header_Build",
     "SQYAMD_Comm_UniqueId", "SQYAMD_Comm_Init", "SQYAMD_Comm_Destroy", "SQYAMD_Gather_Blobs",
@@ -88,6 +89,11 @@ def lib():
             getattr(L, f).argtypes = [ctypes.c_void_p, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p]
         for f in ("SQYAMD_Decode_Frames_UI8", "SQYAMD_Decode_Frames_UI16"):
             getattr(L, f).argtypes = [ctypes.c_void_p, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_void_p, ctypes.c_long]
+        for f in ("SQYAMD_Decode_Slabs_UI8_Device", "SQYAMD_Decode_Slabs_UI16_Device"):
+            getattr(L, f).argtypes = [ctypes.c_void_p, c_long_p, c_long_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_long, c_long_p, ctypes.c_int,
+                                      ctypes.c_void_p]
+        for f in ("SQYAMD_Decode_Slabs_UI8", "SQYAMD_Decode_Slabs_UI16"):
+            getattr(L, f).argtypes = [ctypes.c_void_p, c_long_p, c_long_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_long, c_long_p]
         _lib = L
     return _lib
 
@@ -275,6 +281,50 @@ def decode_frames_device(d_src, srclength, z0, nz, d_dst, dst_capacity, dtype, s
     return getattr(lib(), "SQYAMD_Decode_Frames_%s_Device" % _suffix(dtype))(
         ctypes.c_void_p(int(d_src)), ctypes.c_long(int(srclength)), ctypes.c_long(int(z0)), ctypes.c_long(int(nz)), ctypes.c_void_p(int(d_dst)),
         ctypes.c_long(int(dst_capacity)), ctypes.c_void_p(stream or 0))
+
+
+def decode_slabs_device(d_src, offsets, lengths, d_dst, dst_capacity, dtype, inflight=0, stream=None):
+    """SQYAMD_Decode_Slabs_*_Device: blob i at d_src + offsets[i] (lengths[i] bytes), the volume they make to d_dst; returns (rc, frames)."""
+    n = len(offsets)
+    frames = (ctypes.c_long * max(n, 1))()
+    rc = getattr(lib(), "SQYAMD_Decode_Slabs_%s_Device" % _suffix(dtype))(
+        ctypes.c_void_p(int(d_src)), _longs(offsets) if n else None, _longs(lengths) if n else None, ctypes.c_int(n), ctypes.c_void_p(int(d_dst)),
+        ctypes.c_long(int(dst_capacity)), frames, ctypes.c_int(int(inflight)), ctypes.c_void_p(stream or 0))
+    return rc, list(frames[:n])
+
+
+def decode_slabs_packed(buf, offsets, lengths):
+    """SQYAMD_Decode_Slabs_UI8/UI16 on blobs that lie in `buf` (bytes) at offsets[i], lengths[i] bytes; returns (rc, ndarray or None)"""
+    buf = bytes(buf)
+    if not offsets:
+        return 1, None
+    first = buf[offsets[0]:offsets[0] + lengths[0]]
+    size, shape = decompressed_sizeof(first), decompressed_shape(first)
+    if size not in (1, 2) or not shape:
+        return 1, None
+    dtype = np.uint16 if size == 2 else np.uint8
+    Z = 0
+    for o, n in zip(offsets, lengths):
+        s = decompressed_shape(buf[o:o + n])
+        if tuple(s[1:]) != tuple(shape[1:]):
+            return 1, None
+        Z += s[0]
+    out = np.empty((Z,) + tuple(shape[1:]), dtype=dtype)
+    src = np.frombuffer(buf, dtype=np.uint8)
+    frames = (ctypes.c_long * len(offsets))()
+    rc = getattr(lib(), "SQYAMD_Decode_Slabs_" + _suffix(dtype))(src.ctypes.data, _longs(offsets), _longs(lengths), ctypes.c_int(len(offsets)),
+                                                                 out.ctypes.data, ctypes.c_long(out.nbytes), frames)
+    return (rc, None) if rc else (0, out)
+
+
+def decode_slabs(blobs):
+    """SQYAMD_Decode_Slabs_UI8/UI16: z-slab blobs (a list of byte strings), packed back to back; returns (rc, volume ndarray or None)"""
+    blobs = [bytes(b) for b in blobs]
+    offsets, at = [], 0
+    for b in blobs:
+        offsets.append(at)
+        at += len(b)
+    return decode_slabs_packed(b"".join(blobs), offsets, [len(b) for b in blobs])
 
 
 def set_option(name, value):

@@ -72,13 +72,15 @@ struct Options {
     std::atomic<long> stored_tail_index;                // decode, chunked layout: the stored frames at the stream's end are found where they must start, not by the scan
     std::atomic<long> host_l2_bytes;                    // rmestbkrd: the host CPU's L2 size as the reference's compass reads it (detected; tests set it)
     std::atomic<long> decode_frames_subset;             // frame-range decode: only the LZ4 frames the range needs, where the pipeline allows (0: full decode + copy)
+    std::atomic<long> decode_slabs_joint;               // slab-set decode: the chunked LZ4 blobs of a group indexed and decoded by one launch each (0: blob by blob)
     Options()
         : transpose_chain(env_flag("SQY_NO_TRANSPOSE_CHAIN") ? 0 : 1), transpose_chain_caller_streams(env_flag("SQY_TRANSPOSE_CHAIN_CALLER_STREAMS")),
           block_parallel(env_flag("SQY_NO_BLOCK_PARALLEL") ? 0 : 1), block_parallel_warmup(env_number("SQY_BLOCK_PARALLEL_WARMUP", 65536, 0, kWarmupMax)),
           block_parallel_stats(env_flag("SQY_BLOCK_PARALLEL_STATS")), tail_scan(env_flag("SQY_NO_TAIL_SCAN") ? 0 : 1),
           decode_two_waves(env_flag("SQY_NO_DECODE_TWO_WAVES") ? 0 : 1), noise_digest(env_flag("SQY_NO_NOISE_DIGEST") ? 0 : 1),
           transpose_blocks_per_cu(env_number("SQY_TRANSPOSE_BLOCKS_PER_CU", 32, 1, 64)), stored_tail_index(env_flag("SQY_NO_STORED_TAIL_INDEX") ? 0 : 1),
-          host_l2_bytes((long)sqy::host_l2_cache_bytes()), decode_frames_subset(env_flag("SQY_NO_DECODE_FRAMES_SUBSET") ? 0 : 1) { sqy::set_bitswap1_blocks_per_cu(transpose_blocks_per_cu.load()); }
+          host_l2_bytes((long)sqy::host_l2_cache_bytes()), decode_frames_subset(env_flag("SQY_NO_DECODE_FRAMES_SUBSET") ? 0 : 1),
+          decode_slabs_joint(env_flag("SQY_NO_DECODE_SLABS_JOINT") ? 0 : 1) { sqy::set_bitswap1_blocks_per_cu(transpose_blocks_per_cu.load()); }
     std::atomic<long>* find(const char* name)
     {
         if (!name) return nullptr;
@@ -94,6 +96,7 @@ struct Options {
         if (!std::strcmp(name, "stored_tail_index")) return &stored_tail_index;
         if (!std::strcmp(name, "host_l2_bytes")) return &host_l2_bytes;
         if (!std::strcmp(name, "decode_frames_subset")) return &decode_frames_subset;
+        if (!std::strcmp(name, "decode_slabs_joint")) return &decode_slabs_joint;
         return nullptr;
     }
 };
@@ -202,6 +205,27 @@ struct DevBuf {
     void release() { if (p) hipFree(p); p = nullptr; cap = 0; }
 };
 
+// pinned host memory (grow-only), for read-backs of more than the context's 4 KiB
+struct HostBuf {
+    void* p = nullptr;
+    size_t cap = 0;
+    int ensure(size_t bytes)
+    {
+        if (bytes <= cap) return 0;
+        if (p) { hipHostFree(p); p = nullptr; cap = 0; }
+        const size_t want = (bytes + ((size_t)1 << 16) - 1) & ~(((size_t)1 << 16) - 1);
+        if (hipHostMalloc(&p, want, hipHostMallocDefault) != hipSuccess) {
+            std::fprintf(stderr, "[sqeazy]\t unable to allocate %zu bytes of pinned host memory\n", want);
+            (void)hipGetLastError();
+            p = nullptr;
+            return 1;
+        }
+        cap = want;
+        return 0;
+    }
+    void release() { if (p) hipHostFree(p); p = nullptr; cap = 0; }
+};
+
 struct Workspace {
     DevBuf ping, pong, lz4_scratch, csize, frame_off, io_src, io_dst, small, plan, dedupe;
     DevBuf spec;              // block-linked frames parsed block-parallel: per block the table it started from and the one it left, the walk lists
@@ -210,12 +234,16 @@ struct Workspace {
     DevBuf bkrd;              // rmestbkrd: the four face histograms and their supports
     DevBuf subset;            // frame-range decode: the frame list, the subset's block index, the frame_shuffle map of the range
     DevBuf range_full;        // frame-range decode of a blob the subset path does not take: the whole volume, the range copied out
+    DevBuf slabs_index;       // slab-set decode: every blob's frame ranking (scratch, block index, counts) of a group
+    DevBuf slabs_joint;       // .. the group's joint block index, frame output table, part descriptors and frame_shuffle maps
+    DevBuf slabs_out;         // .. the group's LZ4 output (when it does not go straight to the volume)
+    HostBuf slabs_host;       // .. the blobs' header prefixes and the ranking's counts, read back
     void* pinned = nullptr;   // 4 KiB of pinned host memory for small read-backs
     void release_buffers()
     {
         ping.release(); pong.release(); lz4_scratch.release(); csize.release(); frame_off.release();
         io_src.release(); io_dst.release(); small.release(); plan.release(); dedupe.release(); diff_side.release(); spec.release(); digest.release(); bkrd.release();
-        subset.release(); range_full.release();
+        subset.release(); range_full.release(); slabs_index.release(); slabs_joint.release(); slabs_out.release(); slabs_host.release();
     }
 };
 
@@ -1449,6 +1477,15 @@ struct DecodeCall {
     // by the LZ4 stage behind it, which decodes its frames straight to their places when it can (round 5).
     int frame_shuffle_prepare(size_t fi, uint64_t& Z, uint64_t& frame_bytes_dec, bool& permutation)
     {
+        if (const int rc = frame_shuffle_map(fi, Z, frame_bytes_dec, permutation)) return rc;
+        if (ws->small.ensure(std::max<uint64_t>(Z * 8, 4096))) return 1;
+        SQY_HIP(hipMemcpyAsync(ws->small.p, fs_map.data(), Z * 8, hipMemcpyHostToDevice, stream));
+        SQY_HIP(hipStreamSynchronize(stream));                                   // (pageable source: gone from the host's side before anything can return)
+        return 0;
+    }
+    // .. its host part: fs_map (the device's copy, struck slots ~0) and fs_unnamed
+    int frame_shuffle_map(size_t fi, uint64_t& Z, uint64_t& frame_bytes_dec, bool& permutation)
+    {
         const Stage& fs = pipe.stages[fi];
         if (h.shape.size() != 3) return 1;
         auto it = fs.cfg.find("reorder_map");
@@ -1482,9 +1519,6 @@ struct DecodeCall {
                 if (last[v] != i) { const uint64_t none = ~0ull; std::memcpy(fs_map.data() + 8 * i, &none, 8); }
             }
         }
-        if (ws->small.ensure(std::max<uint64_t>(Z * 8, 4096))) return 1;
-        SQY_HIP(hipMemcpyAsync(ws->small.p, fs_map.data(), Z * 8, hipMemcpyHostToDevice, stream));
-        SQY_HIP(hipStreamSynchronize(stream));                                   // (pageable source: gone from the host's side before anything can return)
         return 0;
     }
 
@@ -1938,6 +1972,32 @@ int fetch_header(const uint8_t* d_src, uint64_t srclen, hipStream_t stream, sqy:
     return 0;
 }
 
+// The inverses of stages [0, from) in reverse order, from c.cur on (from = the stage count: the whole pipeline; the slab-set decode starts
+// behind an LZ4 stage that has already run).  The result is c.cur; the caller moves it to d_dst when it is not there.
+int decode_stages(DecodeCall& c, size_t from)
+{
+    for (size_t si = from; si-- > 0;) {
+        int rc = 0;
+        switch (c.pipe.stages[si].kind) {
+            case StageKind::lz4:               rc = c.lz4(si); break;              // (may do the frame_shuffle in front as well)
+            case StageKind::bitswap1:          rc = c.bitswap1(si); break;         // (may do the quantiser in front as well)
+            case StageKind::raster_reorder:    rc = c.reorder(si, false); break;
+            case StageKind::zcurve_reorder:    rc = c.reorder(si, true); break;
+            case StageKind::bitshuffle:        rc = c.bitshuffle(si); break;
+            case StageKind::tile_shuffle:      rc = c.tile_shuffle(si); break;
+            case StageKind::diff3x3x1:         rc = c.diff3x3x1(si); break;
+            case StageKind::quantiser:         rc = c.quantiser(si); break;
+            case StageKind::frame_shuffle:     rc = c.frame_shuffle(si); break;
+            case StageKind::pass_through:      break;                              // pass_through_scheme_impl.hpp:81-95: bytes are the voxels
+            case StageKind::rmestbkrd:
+            case StageKind::rmbkrd_neighbor5:  break;                              // a copy: `cur` is the filtered volume (written out at the end)
+            default:                           return 1;
+        }
+        if (rc) return rc;
+    }
+    return 0;
+}
+
 int decode_on_device(Context& cx, const void* d_src_v, uint64_t srclen, void* d_dst, uint64_t dst_capacity, int want_elem, hipStream_t stream)
 {
     if (!d_src_v || !d_dst) return 1;
@@ -1963,25 +2023,7 @@ int decode_on_device(Context& cx, const void* d_src_v, uint64_t srclen, void* d_
     }
 
     DecodeCall c(cx, stream, d_dst, h, std::move(pipe), raw_bytes / (uint64_t)elem, d_src + h.size);
-    for (size_t si = c.pipe.stages.size(); si-- > 0;) {
-        int rc = 0;
-        switch (c.pipe.stages[si].kind) {
-            case StageKind::lz4:               rc = c.lz4(si); break;              // (may do the frame_shuffle in front as well)
-            case StageKind::bitswap1:          rc = c.bitswap1(si); break;         // (may do the quantiser in front as well)
-            case StageKind::raster_reorder:    rc = c.reorder(si, false); break;
-            case StageKind::zcurve_reorder:    rc = c.reorder(si, true); break;
-            case StageKind::bitshuffle:        rc = c.bitshuffle(si); break;
-            case StageKind::tile_shuffle:      rc = c.tile_shuffle(si); break;
-            case StageKind::diff3x3x1:         rc = c.diff3x3x1(si); break;
-            case StageKind::quantiser:         rc = c.quantiser(si); break;
-            case StageKind::frame_shuffle:     rc = c.frame_shuffle(si); break;
-            case StageKind::pass_through:      break;                              // pass_through_scheme_impl.hpp:81-95: bytes are the voxels
-            case StageKind::rmestbkrd:
-            case StageKind::rmbkrd_neighbor5:  break;                              // a copy: `cur` is the filtered volume (written out at the end)
-            default:                           return 1;
-        }
-        if (rc) return rc;
-    }
+    if (const int rc = decode_stages(c, c.pipe.stages.size())) return rc;
     if (c.cur != d_dst) SQY_HIP(hipMemcpyAsync(d_dst, c.cur, raw_bytes, hipMemcpyDeviceToDevice, stream));
     if (c.lz4_flag) SQY_HIP(hipMemcpyAsync(cx.ws.pinned, c.lz4_flag, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
     SQY_HIP(hipStreamSynchronize(stream));
@@ -2100,6 +2142,311 @@ int decode_from_host(const char* src, long srclength, char* dst, int elem_size)
     if (rc) return rc;
     SQY_HIP(hipStreamSynchronize(stream));
     if (!lease.ctx->stager.copy(ws->io_dst.p, dst, raw, false, dev_id)) { std::fprintf(stderr, "[sqeazy]\t device to host transfer failed\n"); return 1; }
+    return 0;
+}
+
+// ---- z-slab blob sets (SQYAMD_Decode_Slabs_*) ----------------------------------------------------------------------------------
+// Blobs in the chunked LZ4 layout are decoded in groups: the frame ranking of every blob of a group in one launch per kernel, one read-back,
+// one joint block index and one LZ4 decode launch for all of them, then each blob's remaining inverses (bitswap1, diff3x3x1, ..) from the
+// group's LZ4 output into its place.  Every other blob -- and every blob of a group whose decode raised the error flag -- goes through
+// decode_on_device, one at a time.
+constexpr uint64_t kSlabsGroupBytes = 4ull << 30;       // LZ4 output of one group (inflight <= 0)
+constexpr uint64_t kSlabsHeadPrefix = 1ull << 16;       // bytes of every blob fetched for its header at first
+
+struct SlabBlob {
+    const uint8_t* src = nullptr;
+    uint64_t len = 0, src_off = 0;
+    sqy::HeaderInfo h;
+    uint64_t raw = 0, dst_off = 0;
+    // the joint path: the LZ4 stage's input to the decoder (total bytes, chunks), where its output goes
+    std::unique_ptr<DecodeCall> call;
+    size_t li = 0;
+    uint64_t total = 0, chunk = 0, nchunks = 0, block_bytes = 0, max_blocks = 0;
+    uint64_t out_base = 0, map_off = 0, fs_bytes = 0;
+    bool remap = false;
+    int rc = 0;
+};
+
+uint64_t align_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
+
+// The joint path for blobs g[0..m) (slab order).  Blobs it cannot take are appended to `single`; the flag raised: all of g go there.
+int decode_slab_group(Context& cx, const uint8_t* d_src, std::vector<SlabBlob>& blobs, const std::vector<size_t>& g, uint8_t* d_dst,
+                      uint64_t volume_bytes, hipStream_t stream, std::vector<size_t>& single)
+{
+    Workspace* ws = &cx.ws;
+    std::vector<PendingEvent>* pend = &cx.pending;
+    const uint32_t m = (uint32_t)g.size();
+    // 1. every blob's frame ranking: scratch | block index | frame starts per blob, then the counts (16 words each) and the group's flag
+    std::vector<uint64_t> at(m);
+    uint64_t bytes = 0;
+    for (uint32_t k = 0; k < m; ++k) {
+        const SlabBlob& b = blobs[g[k]];
+        at[k] = bytes;
+        bytes += align_up(sqy::lz4_frame_rank_scratch_bytes(b.nchunks), 256) + align_up(b.max_blocks * 16, 256) + align_up((b.max_blocks + 2) * 4, 256);
+    }
+    const uint64_t o_counts = bytes, o_desc = align_up(o_counts + (uint64_t)m * 64 + 64, 256);
+    if (ws->slabs_index.ensure(o_desc + sqy::lz4_frame_rank_batch_desc_bytes(m))) return 1;
+    uint8_t* di = static_cast<uint8_t*>(ws->slabs_index.p);
+    uint32_t* counts = reinterpret_cast<uint32_t*>(di + o_counts);
+    uint32_t* flag = counts + 16 * m;
+    std::vector<sqy::Lz4RankJob> jobs(m);
+    for (uint32_t k = 0; k < m; ++k) {
+        const SlabBlob& b = blobs[g[k]];
+        sqy::Lz4RankJob& j = jobs[k];
+        uint8_t* p = di + at[k];
+        j.scratch = p;
+        p += align_up(sqy::lz4_frame_rank_scratch_bytes(b.nchunks), 256);
+        j.blk = p;
+        j.frame_first = reinterpret_cast<uint32_t*>(p + align_up(b.max_blocks * 16, 256));
+        j.in = b.call->cur;
+        j.n = b.call->cur_bytes;
+        j.max_blocks = b.max_blocks;
+        j.counts = counts + 16 * k;
+        j.expected_frames = b.nchunks;
+        const bool tail = g_opt.stored_tail_index.load() != 0;             // (the stored tail looked for where it must start, as lz4_index does)
+        j.chunk = tail ? b.chunk : 0;
+        j.last = tail ? b.total - (b.nchunks - 1) * b.chunk : 0;
+    }
+    std::vector<unsigned char> hdesc(sqy::lz4_frame_rank_batch_desc_bytes(m));
+    SQY_HIP(hipMemsetAsync(flag, 0, 64, stream));
+    SQY_TIMED("slabs_frame_index", sqy::launch_lz4_frame_rank_batch(jobs.data(), m, di + o_desc, hdesc.data(), stream));
+    if (ws->slabs_host.ensure((size_t)m * 64)) return 1;
+    const uint32_t* hc_all = static_cast<const uint32_t*>(ws->slabs_host.p);
+    SQY_HIP(hipMemcpyAsync(ws->slabs_host.p, counts, (size_t)m * 64, hipMemcpyDeviceToHost, stream));
+    SQY_HIP(hipStreamSynchronize(stream));
+
+    // 2. who stays: ranked without complaint, one frame per chunk (anything else -- code 100, an error, a stored tail the ranking gave up
+    // on -- is decoded on its own, where the single-blob index gets the last word)
+    std::vector<size_t> mem;
+    std::vector<uint32_t> hc3;
+    std::vector<const void*> blk_of;
+    for (uint32_t k = 0; k < m; ++k) {
+        const uint32_t* hc = hc_all + 16 * k;
+        if (hc[2] != 0 || hc[0] != blobs[g[k]].nchunks) { single.push_back(g[k]); continue; }
+        mem.push_back(g[k]);
+        hc3.push_back(hc[3]);
+        blk_of.push_back(jobs[k].blk);
+    }
+    if (mem.empty()) return 0;
+
+    // 3. where each blob's LZ4 output goes: straight into its place in the volume when the LZ4 stage's inverse produces the volume for
+    // every blob of the group (lz4, frame_shuffle->lz4, behind the background heads) and the places are 16-byte aligned, else the workspace
+    std::vector<unsigned char> maps;
+    bool direct = true;
+    for (size_t b : mem) {
+        SlabBlob& s = blobs[b];
+        DecodeCall& c = *s.call;
+        s.remap = false;
+        if (c.preceded_by(s.li, StageKind::frame_shuffle) && s.total % s.chunk == 0 && c.in_bytes(s.li - 1) == s.total && s.h.shape.size() == 3) {
+            uint64_t Z = 0, fb = 0;
+            bool permutation = true;
+            if (c.frame_shuffle_map(s.li - 1, Z, fb, permutation) == 0 && fb && fb % s.chunk == 0 && Z * fb == s.total) {
+                s.remap = true;
+                s.fs_bytes = fb;
+                s.map_off = maps.size();
+                maps.insert(maps.end(), c.fs_map.begin(), c.fs_map.begin() + Z * 8);
+            }
+        }
+        const size_t first_after = s.remap ? s.li - 1 : s.li;           // the stage whose inverse the LZ4 decode completes
+        if (first_after > c.lead || ((reinterpret_cast<uintptr_t>(d_dst) + s.dst_off) & 15) != 0) direct = false;
+    }
+    uint64_t out_bytes = 0;
+    for (size_t b : mem) {
+        SlabBlob& s = blobs[b];
+        if (direct) s.out_base = s.dst_off;
+        else { s.out_base = out_bytes; out_bytes = align_up(out_bytes + s.total, 256); }
+    }
+    if (direct) out_bytes = volume_bytes;
+    uint8_t* out = direct ? d_dst : nullptr;
+    if (!direct) {
+        if (ws->slabs_out.ensure(std::max<uint64_t>(out_bytes, 16))) return 1;
+        out = static_cast<uint8_t*>(ws->slabs_out.p);
+    }
+
+    // 4. the joint index and the one decode launch: parts | maps | joint blk | joint frame starts | frame output table
+    const uint32_t np = (uint32_t)mem.size();
+    uint64_t jn = 0, ncomp = 0;
+    uint32_t maxf = 0;
+    for (uint32_t k = 0; k < np; ++k) { jn += blobs[mem[k]].nchunks; ncomp += hc3[k]; maxf = std::max<uint32_t>(maxf, (uint32_t)blobs[mem[k]].nchunks); }
+    if (jn > 0x7fffffffull) { for (size_t b : mem) single.push_back(b); return 0; }
+    const uint64_t o_maps = align_up(np * sizeof(sqy::Lz4JointPart), 256), o_jblk = align_up(o_maps + maps.size(), 256),
+                   o_jff = o_jblk + jn * 16, o_jout = align_up(o_jff + (jn + 1) * 4, 256);
+    if (ws->slabs_joint.ensure(o_jout + jn * 16)) return 1;
+    uint8_t* dj = static_cast<uint8_t*>(ws->slabs_joint.p);
+    std::vector<unsigned char> up(o_maps + maps.size());
+    for (uint32_t k = 0, jbase = 0; k < np; ++k) {
+        const SlabBlob& s = blobs[mem[k]];
+        sqy::Lz4JointPart pt{};
+        pt.blk = blk_of[k];
+        pt.in_off = (uint64_t)(s.call->cur - d_src);
+        pt.out_base = s.out_base;
+        pt.chunk = s.chunk;
+        pt.total = s.total;
+        pt.remap = s.remap ? reinterpret_cast<const uint64_t*>(dj + o_maps + s.map_off) : nullptr;
+        pt.remap_bytes = s.remap ? s.fs_bytes : 0;
+        pt.jbase = jbase;
+        pt.nframes = (uint32_t)s.nchunks;
+        std::memcpy(up.data() + k * sizeof(pt), &pt, sizeof(pt));
+        jbase += (uint32_t)s.nchunks;
+    }
+    if (!maps.empty()) std::memcpy(up.data() + o_maps, maps.data(), maps.size());
+    SQY_HIP(hipMemcpyAsync(dj, up.data(), up.size(), hipMemcpyHostToDevice, stream));
+    for (size_t b : mem) {                                              // frames nobody names come out as zeros (frame_shuffle's inverse)
+        SlabBlob& s = blobs[b];
+        if (s.remap && !s.call->fs_unnamed.empty())
+            if (const int rc = s.call->zero_unnamed_places(out + s.out_base, s.fs_bytes, s.total)) return rc;
+    }
+    const bool side_ok = cx.ensure_side();
+    SQY_TIMED("slabs_lz4_decode",
+              sqy::launch_lz4_frames_joint_decode(d_src, reinterpret_cast<const sqy::Lz4JointPart*>(dj), np, maxf, dj + o_jblk,
+                                                  reinterpret_cast<uint32_t*>(dj + o_jff), reinterpret_cast<uint64_t*>(dj + o_jout), (uint32_t)jn, out,
+                                                  out_bytes, blobs[mem[0]].block_bytes, (uint32_t)std::min<uint64_t>(ncomp, 0xffffffffull), flag, stream,
+                                                  side_ok ? cx.side : nullptr, cx.fork, cx.join, g_opt.decode_two_waves.load() != 0));
+
+    // 5. every blob's remaining inverses, from its LZ4 output into its place
+    bool first = true;
+    for (size_t b : mem) {
+        SlabBlob& s = blobs[b];
+        DecodeCall& c = *s.call;
+        // (the quantiser's table goes to ws->small by a synchronous copy: the blob before must be done with it)
+        if (!first) for (const Stage& st : c.pipe.stages) if (st.kind == StageKind::quantiser) { SQY_HIP(hipStreamSynchronize(stream)); break; }
+        first = false;
+        c.cur = out + s.out_base;
+        c.cur_bytes = s.total;
+        if (const int rc = decode_stages(c, s.remap ? s.li - 1 : s.li)) { s.rc = rc; continue; }
+        if (c.cur != c.d_dst) SQY_HIP(hipMemcpyAsync(c.d_dst, c.cur, s.raw, hipMemcpyDeviceToDevice, stream));
+    }
+    // 6. the decoder's verdict, one read-back for the group
+    SQY_HIP(hipMemcpyAsync(cx.ws.pinned, flag, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    SQY_HIP(hipStreamSynchronize(stream));
+    if (g_prof_on.load()) prof_collect(cx.pending);
+    if (*static_cast<const uint32_t*>(cx.ws.pinned)) {
+        // a damaged frame somewhere in the group: every blob of it again on its own, which gives each one its exact code
+        for (size_t b : mem) { blobs[b].rc = 0; single.push_back(b); }
+    }
+    return 0;
+}
+
+int decode_slabs_on_device(Context& cx, const void* d_src_v, const long* offsets, const long* lengths, int nslabs, void* d_dst_v, uint64_t dst_capacity,
+                           long* frames, int inflight, int want_elem, hipStream_t stream)
+{
+    if (!d_src_v || !d_dst_v || !offsets || !lengths || nslabs <= 0) { std::fprintf(stderr, "[sqeazy]\t decode slabs: bad arguments\n"); return 1; }
+    const uint8_t* d_src = static_cast<const uint8_t*>(d_src_v);
+    uint8_t* d_dst = static_cast<uint8_t*>(d_dst_v);
+    DrainOnExit drain{stream, &cx.pending, cx.side};
+    std::vector<SlabBlob> blobs((size_t)nslabs);
+    for (int i = 0; i < nslabs; ++i) {
+        if (offsets[i] < 0 || lengths[i] <= 0) { std::fprintf(stderr, "[sqeazy]\t decode slabs: blob %d at %ld, %ld bytes\n", i, offsets[i], lengths[i]); return 1; }
+        blobs[i].src_off = (uint64_t)offsets[i];
+        blobs[i].src = d_src + offsets[i];
+        blobs[i].len = (uint64_t)lengths[i];
+    }
+    // 1. the headers: every blob's prefix with one synchronisation (a header longer than that: fetched on its own), checked before anything
+    // is written
+    if (cx.ws.slabs_host.ensure((size_t)nslabs * kSlabsHeadPrefix)) return 1;
+    char* hp = static_cast<char*>(cx.ws.slabs_host.p);
+    for (int i = 0; i < nslabs; ++i)
+        SQY_HIP(hipMemcpyAsync(hp + (uint64_t)i * kSlabsHeadPrefix, blobs[i].src, std::min(kSlabsHeadPrefix, blobs[i].len), hipMemcpyDeviceToHost, stream));
+    SQY_HIP(hipStreamSynchronize(stream));
+    uint64_t volume = 0;
+    for (int i = 0; i < nslabs; ++i) {
+        SlabBlob& b = blobs[i];
+        const uint64_t take = std::min(kSlabsHeadPrefix, b.len);
+        b.h = sqy::header_unpack(hp + (uint64_t)i * kSlabsHeadPrefix, hp + (uint64_t)i * kSlabsHeadPrefix + take);
+        if (!b.h.valid && take < b.len && fetch_header(b.src, b.len, stream, b.h)) return 1;
+        if (!b.h.valid) { std::fprintf(stderr, "[sqeazy]\t decode slabs: no sqy header in blob %d\n", i); return 1; }
+        if (b.h.elem_size() != want_elem) { std::fprintf(stderr, "[sqeazy]\t decode slabs: blob %d holds %s voxels\n", i, b.h.type.c_str()); return 1; }
+        std::string why;
+        if (!Pipeline::supported(b.h.pipename, want_elem, &why)) {
+            std::fprintf(stderr, "[sqeazy]\t%s cannot be build with this version of sqeazy (%s)\n", b.h.pipename.c_str(), why.c_str());
+            return 1;
+        }
+        if (!header_shape_ok(b.h, b.len, &b.raw)) return 1;
+        const sqy::HeaderInfo& h0 = blobs[0].h;
+        if (b.h.shape.size() != h0.shape.size() || !std::equal(b.h.shape.begin() + 1, b.h.shape.end(), h0.shape.begin() + 1)) {
+            std::fprintf(stderr, "[sqeazy]\t decode slabs: blob %d's shape does not continue blob 0's\n", i);
+            return 1;
+        }
+        b.dst_off = volume;
+        volume += b.raw;
+    }
+    if (volume > dst_capacity) { std::fprintf(stderr, "[sqeazy]\t decode slabs: %llu bytes do not fit the buffer\n", (unsigned long long)volume); return 1; }
+    if (frames) for (int i = 0; i < nslabs; ++i) frames[i] = (long)blobs[i].h.shape[0];
+
+    // 2. who takes the joint path: the last stage lz4, more than one chunk (the ranking then tells the chunked layout from the serial one)
+    std::vector<size_t> joint, single;
+    for (int i = 0; i < nslabs; ++i) {
+        SlabBlob& b = blobs[i];
+        bool ok = g_opt.decode_slabs_joint.load() != 0;
+        if (ok) {
+            b.call.reset(new DecodeCall(cx, stream, d_dst + b.dst_off, b.h, Pipeline::from_string(b.h.pipename), b.raw / (uint64_t)want_elem, b.src + b.h.size));
+            DecodeCall& c = *b.call;
+            const size_t ns = c.pipe.stages.size();
+            ok = ns > 0 && c.pipe.stages[ns - 1].kind == StageKind::lz4;
+            if (ok) {
+                const Stage& st = c.pipe.stages[ns - 1];
+                b.li = ns - 1;
+                b.total = c.in_bytes(b.li);
+                b.chunk = b.total ? st.lz4.bytes_per_chunk(b.total) : 1;
+                b.block_bytes = st.lz4.block_bytes();
+                b.nchunks = b.total ? (b.total + b.chunk - 1) / b.chunk : 0;
+                b.max_blocks = std::max<uint64_t>(b.nchunks * ((b.chunk + b.block_bytes - 1) / b.block_bytes), b.total / b.block_bytes + 1) + 16;
+                ok = b.nchunks > 1 && b.chunk <= b.block_bytes;
+            }
+        }
+        (ok ? joint : single).push_back((size_t)i);
+    }
+    // 3. groups: LZ4 output up to kSlabsGroupBytes (at least one blob), at most `inflight` blobs, one block size
+    std::vector<std::vector<size_t>> groups;
+    uint64_t gbytes = 0;
+    for (size_t b : joint) {
+        const uint64_t need = align_up(blobs[b].total, 256);
+        if (groups.empty() || (gbytes + need > kSlabsGroupBytes) || (inflight > 0 && groups.back().size() >= (size_t)inflight) ||
+            blobs[groups.back()[0]].block_bytes != blobs[b].block_bytes) {
+            groups.emplace_back();
+            gbytes = 0;
+        }
+        groups.back().push_back(b);
+        gbytes += need;
+    }
+    for (const auto& g : groups)
+        if (const int rc = decode_slab_group(cx, d_src, blobs, g, d_dst, volume, stream, single)) return rc;
+    // 4. the others, one at a time
+    for (size_t b : single)
+        blobs[b].rc = decode_on_device(cx, blobs[b].src, blobs[b].len, d_dst + blobs[b].dst_off, blobs[b].raw, want_elem, stream);
+    for (const SlabBlob& b : blobs) if (b.rc) return b.rc;
+    return 0;
+}
+
+// host-pointer slab-set decode: the span of the blobs staged as in decode_from_host, the volume comes back
+int decode_slabs_from_host(const char* src, const long* offsets, const long* lengths, int nslabs, char* dst, long dst_capacity, long* frames,
+                           int elem_size)
+{
+    if (!src || !dst || !offsets || !lengths || nslabs <= 0) { std::fprintf(stderr, "[sqeazy]\t decode slabs: bad arguments\n"); return 1; }
+    uint64_t span = 0, volume = 0;
+    for (int i = 0; i < nslabs; ++i) {                                   // untrusted input: before anything is allocated or uploaded
+        if (offsets[i] < 0 || lengths[i] <= 0) { std::fprintf(stderr, "[sqeazy]\t decode slabs: blob %d at %ld, %ld bytes\n", i, offsets[i], lengths[i]); return 1; }
+        const sqy::HeaderInfo h = sqy::header_unpack(src + offsets[i], src + offsets[i] + lengths[i]);
+        if (!h.valid) { std::fprintf(stderr, "[sqeazy]\t decode slabs: no sqy header in blob %d\n", i); return 1; }
+        uint64_t raw = 0;
+        if (!header_shape_ok(h, (uint64_t)lengths[i], &raw)) return 1;
+        volume += raw;
+        span = std::max<uint64_t>(span, (uint64_t)offsets[i] + (uint64_t)lengths[i]);
+    }
+    if (volume > (uint64_t)std::max(dst_capacity, 0l)) { std::fprintf(stderr, "[sqeazy]\t decode slabs: %llu bytes do not fit the buffer\n", (unsigned long long)volume); return 1; }
+    if (!device_present()) { std::fprintf(stderr, "[sqeazy]\t no MI355X (HIP device) visible: sqeazy_amd has no CPU path\n"); return 1; }
+    ContextLease lease;
+    if (!lease.ctx) { std::fprintf(stderr, "[sqeazy]\t no usable HIP device\n"); return 1; }
+    Workspace* ws = &lease.ctx->ws;
+    hipStream_t stream = lease.ctx->own_stream();
+    if (!stream) { std::fprintf(stderr, "[sqeazy]\t no HIP stream\n"); return 1; }
+    if (ws->io_src.ensure(std::max<uint64_t>(span, 16)) || ws->io_dst.ensure(std::max<uint64_t>(volume, 16))) return 1;
+    int dev_id = 0;
+    SQY_HIP(hipGetDevice(&dev_id));
+    if (!lease.ctx->stager.copy(ws->io_src.p, const_cast<char*>(src), (size_t)span, true, dev_id)) { std::fprintf(stderr, "[sqeazy]\t host to device transfer failed\n"); return 1; }
+    const int rc = decode_slabs_on_device(*lease.ctx, ws->io_src.p, offsets, lengths, nslabs, ws->io_dst.p, volume, frames, 0, elem_size, stream);
+    if (rc) return rc;
+    if (!lease.ctx->stager.copy(ws->io_dst.p, dst, volume, false, dev_id)) { std::fprintf(stderr, "[sqeazy]\t device to host transfer failed\n"); return 1; }
     return 0;
 }
 
@@ -2490,6 +2837,38 @@ int SQYAMD_Decode_Frames_UI16(const char* src, long srclength, long z0, long nz,
 int SQYAMD_Decode_Frames_UI8(const char* src, long srclength, long z0, long nz, char* dst, long dst_capacity)
 {
     return guarded([&]() -> int { return decode_frames_from_host(src, srclength, z0, nz, dst, dst_capacity, 1); });
+}
+
+int SQYAMD_Decode_Slabs_UI16_Device(const void* d_src, const long* offsets, const long* lengths, int nslabs, void* d_dst, long dst_capacity,
+                                    long* frames, int inflight, void* hip_stream)
+{
+    return guarded([&]() -> int {
+    ContextLease lease;
+    if (!lease.ctx) { std::fprintf(stderr, "[sqeazy]\t no usable HIP device\n"); return 1; }
+    return decode_slabs_on_device(*lease.ctx, d_src, offsets, lengths, nslabs, d_dst, (uint64_t)std::max(dst_capacity, 0l), frames, inflight, 2,
+                                  static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+int SQYAMD_Decode_Slabs_UI8_Device(const void* d_src, const long* offsets, const long* lengths, int nslabs, void* d_dst, long dst_capacity,
+                                   long* frames, int inflight, void* hip_stream)
+{
+    return guarded([&]() -> int {
+    ContextLease lease;
+    if (!lease.ctx) { std::fprintf(stderr, "[sqeazy]\t no usable HIP device\n"); return 1; }
+    return decode_slabs_on_device(*lease.ctx, d_src, offsets, lengths, nslabs, d_dst, (uint64_t)std::max(dst_capacity, 0l), frames, inflight, 1,
+                                  static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+int SQYAMD_Decode_Slabs_UI16(const char* src, const long* offsets, const long* lengths, int nslabs, char* dst, long dst_capacity, long* frames)
+{
+    return guarded([&]() -> int { return decode_slabs_from_host(src, offsets, lengths, nslabs, dst, dst_capacity, frames, 2); });
+}
+
+int SQYAMD_Decode_Slabs_UI8(const char* src, const long* offsets, const long* lengths, int nslabs, char* dst, long dst_capacity, long* frames)
+{
+    return guarded([&]() -> int { return decode_slabs_from_host(src, offsets, lengths, nslabs, dst, dst_capacity, frames, 1); });
 }
 
 int SQYAMD_Decode_UI8_Device(const void* d_src, long srclength, void* d_dst, long dst_capacity, void* hip_stream)

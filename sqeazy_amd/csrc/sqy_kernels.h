@@ -203,6 +203,39 @@ hipError_t launch_lz4_frame_rank(const uint8_t* in, uint64_t n, void* blk, uint3
                                  uint32_t* counts, uint64_t expected_frames, void* scratch, hipStream_t stream, uint64_t chunk = 0, uint64_t last = 0);
 // (chunk, last: the bytes every frame but the last / the last frame decodes to -- frames at the stream's end that are STORED blocks of
 //  those sizes are found where they must start instead of by the scan; 0 = scan everything.  counts: 16 words, [6] = frames found so)
+// The ranking of several streams at once (SQYAMD_Decode_Slabs_*): job i is launch_lz4_frame_rank(in, n, blk, frame_first, max_blocks,
+// counts, expected_frames, scratch, .., chunk, last) -- its own scratch (lz4_frame_rank_scratch_bytes), counts (16 words, zeroed here) --,
+// all jobs in one launch per kernel, the single-workgroup tail and rank kernels of the jobs side by side.  d_desc: device memory of
+// lz4_frame_rank_batch_desc_bytes(njobs) bytes; h_desc: host memory of as many, alive until the stream has passed the launch.
+struct Lz4RankJob {
+    const uint8_t* in;
+    uint64_t n;
+    void* blk;
+    uint32_t* frame_first;
+    uint64_t max_blocks;
+    uint32_t* counts;
+    uint64_t expected_frames;
+    void* scratch;
+    uint64_t chunk, last;
+};
+uint64_t lz4_frame_rank_batch_desc_bytes(uint32_t njobs);
+hipError_t launch_lz4_frame_rank_batch(const Lz4RankJob* jobs, uint32_t njobs, void* d_desc, void* h_desc, hipStream_t stream);
+// One LZ4 decode launch over the ranked frames of several streams (SQYAMD_Decode_Slabs_*).  Part p (device array d_parts): nframes
+// single-block frames indexed at blk (offsets relative to its stream, which starts at in + in_off), `total` bytes decoded in frames of
+// `chunk`; frame f goes to out + out_base + f * chunk, or with remap (frame_shuffle in front) to out + out_base + remap[o / remap_bytes] *
+// remap_bytes + o % remap_bytes, o = f * chunk (~0 in remap: struck).  jblk (16 B), jff (4 B + 1) and jout (16 B) per frame of all parts:
+// the joint index the launch builds on the device.  The kernel choice of launch_lz4_frames_decode on the joint counts; *errflag as there.
+struct Lz4JointPart {
+    const void* blk;
+    uint64_t in_off, out_base, chunk, total;
+    const uint64_t* remap;
+    uint64_t remap_bytes;
+    uint32_t jbase, nframes;
+};
+hipError_t launch_lz4_frames_joint_decode(const uint8_t* in, const Lz4JointPart* d_parts, uint32_t nparts, uint32_t max_part_frames, void* jblk,
+                                          uint32_t* jff, uint64_t* jout, uint32_t nframes, uint8_t* out, uint64_t out_bytes, uint64_t block_bytes,
+                                          uint32_t ncompressed, uint32_t* errflag, hipStream_t stream, hipStream_t copy_stream = nullptr,
+                                          hipEvent_t fork = nullptr, hipEvent_t join = nullptr, bool two_waves = false);
 // frame f decodes to out + f*frame_stride; every block decodes to at most block_bytes
 // ONE block-linked frame (the serial layout) decoded block-parallel: every block at once with the history as an unknown (16-bit
 // references in `refs`, out_bytes words), the tails resolved in order by one workgroup, the rest at once.  blk: the frame's blocks

@@ -3285,7 +3285,7 @@ __device__ __forceinline__ uint32_t cand_slot(uint64_t pos, uint32_t mask)
 // layout's ONE block-linked frame (or chunks of several blocks) -- nothing the ranking covers, it would scan the whole payload
 // (0.2-0.3 ms per GiB) only to give up.  *hint = 1 makes the two kernels below return at once; the host then takes the walk, as it does
 // whenever the ranking gives up.
-__global__ void lz4_frame_probe_kernel(const uint8_t* __restrict__ in, uint64_t n, uint32_t* __restrict__ hint)
+__device__ __forceinline__ void frame_probe_body(const uint8_t* __restrict__ in, uint64_t n, uint32_t* __restrict__ hint)
 {
     uint32_t multi = 0;
     if (n >= 19 && ld_u32(in) == 0x184D2204u) {
@@ -3298,6 +3298,7 @@ __global__ void lz4_frame_probe_kernel(const uint8_t* __restrict__ in, uint64_t 
     }
     *hint = multi;
 }
+__global__ void lz4_frame_probe_kernel(const uint8_t* __restrict__ in, uint64_t n, uint32_t* __restrict__ hint) { frame_probe_body(in, n, hint); }
 
 // a window that holds the magic's first two bytes somewhere: the sixteen start positions one by one (a call: it is rare)
 __device__ __noinline__ void frame_cand_record(uint64_t n, FrameSlot* __restrict__ table, uint32_t mask, FrameCand* __restrict__ list, uint32_t cap,
@@ -3339,12 +3340,11 @@ __device__ __noinline__ void frame_cand_record(uint64_t n, FrameSlot* __restrict
 // trust: the ranking still has to reach the first of these from position 0 and the last one's end mark has to sit on the stream's end; a
 // stream built to fool this (stored payloads that hold such headers at those very places) makes the ranking give up, and the host scans
 // again with last = 0 (no tail), then walks.
-__global__ __launch_bounds__(1024)
-void lz4_frame_tail_kernel(const uint8_t* __restrict__ in, uint64_t n, uint64_t chunk, uint64_t last, uint32_t kmax, FrameSlot* __restrict__ table,
-                           uint32_t mask, FrameCand* __restrict__ list, uint32_t cap, uint32_t* __restrict__ ncand,
-                           const uint32_t* __restrict__ hint, uint32_t* __restrict__ tail_frames, unsigned long long* __restrict__ scan_end)
+__device__ __forceinline__ void frame_tail_body(const uint8_t* __restrict__ in, uint64_t n, uint64_t chunk, uint64_t last, uint32_t kmax, FrameSlot* __restrict__ table,
+                                                uint32_t mask, FrameCand* __restrict__ list, uint32_t cap, uint32_t* __restrict__ ncand,
+                                                const uint32_t* __restrict__ hint, uint32_t* __restrict__ tail_frames, unsigned long long* __restrict__ scan_end,
+                                                uint32_t& first_bad)
 {
-    __shared__ uint32_t first_bad;
     const uint32_t tid = threadIdx.x;
     if (tid == 0) { first_bad = kmax + 1u; *scan_end = n; *tail_frames = 0u; }
     __syncthreads();
@@ -3402,18 +3402,26 @@ void lz4_frame_tail_kernel(const uint8_t* __restrict__ in, uint64_t n, uint64_t 
     }
     if (tid == 0) { *scan_end = (unsigned long long)start_of(m); *tail_frames = m; }
 }
+__global__ __launch_bounds__(1024)
+void lz4_frame_tail_kernel(const uint8_t* __restrict__ in, uint64_t n, uint64_t chunk, uint64_t last, uint32_t kmax, FrameSlot* __restrict__ table,
+                           uint32_t mask, FrameCand* __restrict__ list, uint32_t cap, uint32_t* __restrict__ ncand,
+                           const uint32_t* __restrict__ hint, uint32_t* __restrict__ tail_frames, unsigned long long* __restrict__ scan_end)
+{
+    __shared__ uint32_t first_bad;
+    frame_tail_body(in, n, chunk, last, kmax, table, mask, list, cap, ncand, hint, tail_frames, scan_end, first_bad);
+}
 
-__global__ __launch_bounds__(256)
-void lz4_frame_candidates_kernel(const uint8_t* __restrict__ in, uint64_t n_stream, FrameSlot* __restrict__ table, uint32_t mask,
-                                 FrameCand* __restrict__ list, uint32_t cap, uint32_t* __restrict__ ncand, const uint32_t* __restrict__ hint,
-                                 const unsigned long long* __restrict__ scan_end)
+// (bx, gx: this workgroup and the workgroups of the stream's scan -- blockIdx.x and gridDim.x of the single-stream kernel)
+__device__ __forceinline__ void frame_candidates_body(const uint8_t* __restrict__ in, uint64_t n_stream, FrameSlot* __restrict__ table, uint32_t mask,
+                                                      FrameCand* __restrict__ list, uint32_t cap, uint32_t* __restrict__ ncand, const uint32_t* __restrict__ hint,
+                                                      const unsigned long long* __restrict__ scan_end, uint32_t bx, uint32_t gx)
 {
     if (*hint) return;
     // (the stored tail, above: its frames are on the list already; a frame that starts in front of it ends in front of it)
     const uint64_t n = *scan_end < n_stream ? (uint64_t)*scan_end : n_stream;
     // a thread inspects 16 start positions [base, base + 16); it needs the bytes [base - 4, base + 28).  Four such windows per thread and
     // step, all their loads issued before the first is looked at
-    const uint64_t stride = (uint64_t)gridDim.x * 256;
+    const uint64_t stride = (uint64_t)gx * 256;
     auto inspect = [&](uint64_t base, const uint32_t (&w)[9], uint32_t kmax) {
         // the magic's first TWO bytes (04 22) at one of the 16 positions?  The reject has to hold for whole wavefronts: a lone 04 sits in
         // one window of sixteen, i.e. in nearly every wavefront's 64 windows -- a test for that byte alone sends every wave through the
@@ -3455,7 +3463,7 @@ void lz4_frame_candidates_kernel(const uint8_t* __restrict__ in, uint64_t n_stre
         inspect(base, w, kmax);
     };
     const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t gthread = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    const uint64_t gthread = (uint64_t)bx * 256 + threadIdx.x;
     {
         // a wavefront's pieces: 256 vectors in a row each, the grid's wavefronts take them in turn, the NEXT piece's loads are in flight
         // while this one is looked at (a wavefront that loads 64 bytes per lane once and then computes keeps the memory system busy for
@@ -3463,7 +3471,7 @@ void lz4_frame_candidates_kernel(const uint8_t* __restrict__ in, uint64_t n_stre
         // (every load unconditional, at a clamped address: a load under a condition with a default value behind it makes the compiler
         // wait for it on the spot)
         struct Piece { uint4 a[4]; uint4 edge; };
-        const uint64_t npieces = (nal + 255) / 256, nwaves = (uint64_t)gridDim.x * 4;
+        const uint64_t npieces = (nal + 255) / 256, nwaves = (uint64_t)gx * 4;
         const uint4* __restrict__ vec = reinterpret_cast<const uint4*>(in + A);
         auto issue = [&](uint64_t pc, Piece& q) {
             const uint64_t t0 = pc * 256 + (uint64_t)lane * 4;           // this lane's first vector
@@ -3510,9 +3518,16 @@ void lz4_frame_candidates_kernel(const uint8_t* __restrict__ in, uint64_t n_stre
             }
         }
     }
-    if (blockIdx.x == 0 && threadIdx.x == 0 && A) slow_window(0, (uint32_t)(A < n ? A : n));          // start positions [0, A)
+    if (bx == 0 && threadIdx.x == 0 && A) slow_window(0, (uint32_t)(A < n ? A : n));          // start positions [0, A)
     // the ragged end: start positions from the first vector not taken above
     for (uint64_t base = A + nal * 16 + gthread * 16; base < n; base += stride * 16) slow_window(base, 16u);
+}
+__global__ __launch_bounds__(256)
+void lz4_frame_candidates_kernel(const uint8_t* __restrict__ in, uint64_t n_stream, FrameSlot* __restrict__ table, uint32_t mask,
+                                 FrameCand* __restrict__ list, uint32_t cap, uint32_t* __restrict__ ncand, const uint32_t* __restrict__ hint,
+                                 const unsigned long long* __restrict__ scan_end)
+{
+    frame_candidates_body(in, n_stream, table, mask, list, cap, ncand, hint, scan_end, blockIdx.x, gridDim.x);
 }
 
 // one workgroup of 1024 threads; work arrays succ[2][N+2], dist[2][N+2], mark[N+2]: in LDS as 16-bit indices when the candidates fit
@@ -3609,6 +3624,79 @@ void lz4_frame_rank_kernel(const uint8_t* __restrict__ in, uint64_t n, const Fra
     } else {
         frame_rank_body<uint32_t>(in, n, table, mask, list, N, work, work + M, work + 2 * M, work + 3 * M,
                                   reinterpret_cast<uint8_t*>(work + 4 * M), blk, frame_first, max_blocks, counts, &head_s);
+    }
+}
+
+// ---- the frame ranking of several streams at once (SQYAMD_Decode_Slabs_*) ----------------------------------------------------------------
+// One job per stream; blockIdx.y (probe, tail, rank: blockIdx.x) picks the job, and each job runs the single-stream kernels' bodies on its
+// own table, list, work arrays and counts.  The single-workgroup tail and rank kernels of the jobs so run side by side, one workgroup each.
+struct RankJobDev {
+    const uint8_t* in;
+    uint64_t n, chunk, last, max_blocks, slots;
+    FrameSlot* table;
+    FrameCand* list;
+    uint32_t* work;
+    uint32_t* ncand;
+    uint4* blk;
+    uint32_t* frame_first;
+    uint32_t* counts;                    // 16 words: [0..3] the index, [4] (the decoders' flag, unused), [5] hint, [6] tail frames, [8..9] scan end
+    uint32_t cap, kmax, lds_entries, cand_blocks;
+};
+
+// what launch_lz4_frame_rank's memsets do: the table, the candidate count, and the counts the ranking reports in
+__global__ __launch_bounds__(256)
+void lz4_frame_rank_clear_batch_kernel(const RankJobDev* __restrict__ jobs)
+{
+    const RankJobDev& j = jobs[blockIdx.y];
+    uint4* t = reinterpret_cast<uint4*>(j.table);
+    for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < j.slots; i += (uint64_t)gridDim.x * 256u) t[i] = make_uint4(0u, 0u, 0u, 0u);
+    if (blockIdx.x == 0 && threadIdx.x < 16u) j.counts[threadIdx.x] = 0u;
+    if (blockIdx.x == 0 && threadIdx.x == 0) *j.ncand = 0u;
+}
+
+__global__ void lz4_frame_probe_batch_kernel(const RankJobDev* __restrict__ jobs)
+{
+    const RankJobDev& j = jobs[blockIdx.x];
+    frame_probe_body(j.in, j.n, j.counts + 5);
+}
+
+__global__ __launch_bounds__(1024)
+void lz4_frame_tail_batch_kernel(const RankJobDev* __restrict__ jobs)
+{
+    __shared__ uint32_t first_bad;
+    const RankJobDev& j = jobs[blockIdx.x];
+    frame_tail_body(j.in, j.n, j.chunk, j.last, j.kmax, j.table, (uint32_t)(j.slots - 1), j.list, j.cap, j.ncand, j.counts + 5, j.counts + 6,
+                    reinterpret_cast<unsigned long long*>(j.counts + 8), first_bad);
+}
+
+__global__ __launch_bounds__(256)
+void lz4_frame_candidates_batch_kernel(const RankJobDev* __restrict__ jobs)
+{
+    const RankJobDev& j = jobs[blockIdx.y];
+    if (blockIdx.x >= j.cand_blocks) return;
+    frame_candidates_body(j.in, j.n, j.table, (uint32_t)(j.slots - 1), j.list, j.cap, j.ncand, j.counts + 5,
+                          reinterpret_cast<const unsigned long long*>(j.counts + 8), blockIdx.x, j.cand_blocks);
+}
+
+__global__ __launch_bounds__(1024)
+void lz4_frame_rank_batch_kernel(const RankJobDev* __restrict__ jobs)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t rank_lds[];
+    __shared__ uint32_t head_s;
+    const RankJobDev& j = jobs[blockIdx.x];
+    uint32_t* counts = j.counts;
+    if (counts[5]) { if (threadIdx.x == 0) { counts[0] = 0; counts[1] = 0; counts[2] = 100; } return; }
+    const uint32_t N = *j.ncand;
+    if (N == 0 || N > j.cap) { if (threadIdx.x == 0) { counts[0] = 0; counts[1] = 0; counts[2] = 100; } return; }
+    const uint32_t M = N + 2, lds_entries = j.lds_entries, mask = (uint32_t)(j.slots - 1);
+    if (M <= lds_entries && M <= 65535u) {
+        uint16_t* w16 = reinterpret_cast<uint16_t*>(rank_lds);
+        frame_rank_body<uint16_t>(j.in, j.n, j.table, mask, j.list, N, w16, w16 + lds_entries, w16 + 2 * lds_entries, w16 + 3 * lds_entries,
+                                  rank_lds + 8u * lds_entries, j.blk, j.frame_first, j.max_blocks, counts, &head_s);
+    } else {
+        uint32_t* work = j.work;
+        frame_rank_body<uint32_t>(j.in, j.n, j.table, mask, j.list, N, work, work + M, work + 2 * M, work + 3 * M,
+                                  reinterpret_cast<uint8_t*>(work + 4 * M), j.blk, j.frame_first, j.max_blocks, counts, &head_s);
     }
 }
 
@@ -3715,6 +3803,21 @@ __device__ __forceinline__ uint64_t lz4_decode_frame_out(uint64_t o, const uint6
     const uint64_t fi = o / remap_bytes;
     return remap[fi] * remap_bytes + (o - fi * remap_bytes);
 }
+// OFFS (the joint decode of several blobs, SQYAMD_Decode_Slabs_*): `remap` is a table of two words per frame instead -- where frame f's
+// output starts (~0: struck, not decoded) and the bytes it has to deliver; frame_stride is not used.  The single-blob instantiations
+// (OFFS = false) are compiled exactly as before.
+template <bool OFFS>
+__device__ __forceinline__ bool lz4_frame_struck(uint32_t f, uint64_t frame_stride, const uint64_t* __restrict__ remap, uint64_t remap_bytes)
+{
+    if (OFFS) return remap[2u * (uint64_t)f] == ~0ull;
+    return lz4_decode_frame_struck((uint64_t)f * frame_stride, remap, remap_bytes);
+}
+template <bool OFFS>
+__device__ __forceinline__ uint64_t lz4_frame_out(uint32_t f, uint64_t frame_stride, const uint64_t* __restrict__ remap, uint64_t remap_bytes)
+{
+    if (OFFS) return remap[2u * (uint64_t)f];
+    return lz4_decode_frame_out((uint64_t)f * frame_stride, remap, remap_bytes);
+}
 
 // The decode kernels' rings leave for global memory in pieces of DEC_FLUSH_PIECE bytes (flush()), a copy step adds at most DEC_STEP_MAX:
 // up to DEC_FLUSH_PIECE - 1 + DEC_STEP_MAX decoded bytes are in the ring only.  A match that reaches behind the ring reads them back
@@ -3723,7 +3826,7 @@ __device__ __forceinline__ uint64_t lz4_decode_frame_out(uint64_t o, const uint6
 // flushed since -- j + cnt + DEC_FLUSH_PIECE + DEC_STEP_MAX > offset -- waits again (round-5 advice: the guard still said 2048 from the
 // time when pieces were 1 KiB).
 constexpr uint32_t DEC_FLUSH_PIECE = 4096u, DEC_STEP_MAX = 1024u;
-template <uint32_t DEC_RING>
+template <uint32_t DEC_RING, bool OFFS = false>
 __global__ __launch_bounds__(64)
 void lz4_frames_decode_kernel(const uint8_t* __restrict__ in, const uint4* __restrict__ blk, const uint32_t* __restrict__ frame_first,
                               uint8_t* __restrict__ out, uint64_t out_bytes, uint64_t frame_stride, uint64_t block_bytes,
@@ -3739,8 +3842,8 @@ void lz4_frames_decode_kernel(const uint8_t* __restrict__ in, const uint4* __res
     const int lane = threadIdx.x;
     const uint32_t f = blockIdx.x;
     const uint32_t b0 = frame_first[f], b1 = frame_first[f + 1];
-    if (lz4_decode_frame_struck((uint64_t)f * frame_stride, remap, remap_bytes)) return;
-    const uint64_t frame_out = lz4_decode_frame_out((uint64_t)f * frame_stride, remap, remap_bytes);   // frame f decodes to [f*chunk, ...)
+    if (lz4_frame_struck<OFFS>(f, frame_stride, remap, remap_bytes)) return;
+    const uint64_t frame_out = lz4_frame_out<OFFS>(f, frame_stride, remap, remap_bytes);   // frame f decodes to [f*chunk, ...)
     uint32_t pos = 0;                                          // decoded bytes of this frame so far
     uint32_t flushed = 0;                                      // bytes of this frame already written to global memory
     bool bad = false;
@@ -4255,7 +4358,7 @@ void lz4_frames_decode_kernel(const uint8_t* __restrict__ in, const uint4* __res
     // else one chunk (the last frame the remainder) -- short frames must not leave the destination half-written
     {
         const uint64_t room = frame_out < out_bytes ? out_bytes - frame_out : 0;
-        const uint64_t expect = remap ? frame_stride : (gridDim.x == 1 || room < frame_stride) ? room : frame_stride;   // (remap: whole chunks only)
+        const uint64_t expect = OFFS ? remap[2u * (uint64_t)f + 1u] : remap ? frame_stride : (gridDim.x == 1 || room < frame_stride) ? room : frame_stride;   // (remap: whole chunks only)
         if ((uint64_t)pos != expect) bad = true;
     }
     if (bad && lane == 0) atomicExch(errflag, 1u);
@@ -4282,7 +4385,9 @@ void lz4_frames_decode_kernel(const uint8_t* __restrict__ in, const uint4* __res
 constexpr uint32_t DEC2_PIN = 4096;                   // wave 0's own stage of compressed bytes: a ring of two halves (+ 32 bytes of mirror)
 constexpr uint32_t DEC2_UNIT = 64;                    // sequences per unit
 
-// wave 0 of lz4_frames_decode2_kernel (a function of its own: the two roles in one body had the register allocator spill)
+// wave 0 of lz4_frames_decode2_kernel (a function of its own: the two roles in one body had the register allocator spill).  (OFFS: a copy of
+// its own for the table-mode kernels, so that the calls of the single-blob kernels -- and what the compiler makes of them -- stay as they were)
+template <bool OFFS>
 __device__ __noinline__ void lz4_decode2_parse(const uint8_t* __restrict__ src, uint32_t sz, lds_u8* pstage, SQY_LDS uint4* units,
                                                volatile SQY_LDS uint32_t* ctrl, int lane, uint64_t* stats)
 {
@@ -4524,8 +4629,8 @@ __device__ __noinline__ void lz4_decode2_parse(const uint8_t* __restrict__ src, 
     })
 }
 
-// wave 1 of lz4_frames_decode2_kernel
-template <uint32_t DEC_RING>
+// wave 1 of lz4_frames_decode2_kernel (OFFS: as above)
+template <uint32_t DEC_RING, bool OFFS>
 __device__ __noinline__ void lz4_decode2_copy(const uint8_t* __restrict__ src, uint32_t sz, uint8_t* __restrict__ out, uint64_t frame_out, uint64_t out_bytes,
                                               uint64_t block_bytes, uint64_t expect, lds_u8* ring, lds_u8* stage, lds_u8* owner_mark,
                                               SQY_LDS uint4* units, volatile SQY_LDS uint32_t* ctrl, uint32_t* __restrict__ errflag, int lane)
@@ -4830,7 +4935,7 @@ __device__ __noinline__ void lz4_decode2_copy(const uint8_t* __restrict__ src, u
     })
 }
 
-template <uint32_t DEC_RING>
+template <uint32_t DEC_RING, bool OFFS = false>
 __global__ __launch_bounds__(128)
 void lz4_frames_decode2_kernel(const uint8_t* __restrict__ in, const uint4* __restrict__ blk, const uint32_t* __restrict__ frame_first,
                                uint8_t* __restrict__ out, uint64_t out_bytes, uint64_t frame_stride, uint64_t block_bytes,
@@ -4849,12 +4954,12 @@ void lz4_frames_decode2_kernel(const uint8_t* __restrict__ in, const uint4* __re
     const uint32_t role = sgpr(threadIdx.x >> 6);
     const uint32_t f = blockIdx.x;
     const uint32_t b0 = frame_first[f], b1 = frame_first[f + 1];
-    if (lz4_decode_frame_struck((uint64_t)f * frame_stride, remap, remap_bytes)) return;      // (the whole workgroup: f is its frame)
+    if (lz4_frame_struck<OFFS>(f, frame_stride, remap, remap_bytes)) return;      // (the whole workgroup: f is its frame)
     if (threadIdx.x < 8) ctrl[threadIdx.x] = 0;
     __syncthreads();
-    const uint64_t frame_out = lz4_decode_frame_out((uint64_t)f * frame_stride, remap, remap_bytes);
+    const uint64_t frame_out = lz4_frame_out<OFFS>(f, frame_stride, remap, remap_bytes);
     const uint64_t room = frame_out < out_bytes ? out_bytes - frame_out : 0;
-    const uint64_t expect = remap ? frame_stride : (gridDim.x == 1 || room < frame_stride) ? room : frame_stride;
+    const uint64_t expect = OFFS ? remap[2u * (uint64_t)f + 1u] : remap ? frame_stride : (gridDim.x == 1 || room < frame_stride) ? room : frame_stride;
     if (b1 - b0 != 1) {                                       // (the host sends such streams to the other kernel)
         if (threadIdx.x == 0) atomicExch(errflag, 1u);
         return;
@@ -4869,13 +4974,14 @@ void lz4_frames_decode2_kernel(const uint8_t* __restrict__ in, const uint4* __re
     }
     uint64_t* stats = nullptr;
     SQY_DST(if (frame_out + 512 <= out_bytes) stats = reinterpret_cast<uint64_t*>(out + frame_out);)
-    if (role == 0) lz4_decode2_parse(src, sz, pstage, units, ctrl, lane, stats);
-    else lz4_decode2_copy<DEC_RING>(src, sz, out, frame_out, out_bytes, block_bytes, expect, ring, stage, owner_mark, units, ctrl, errflag, lane);
+    if (role == 0) lz4_decode2_parse<OFFS>(src, sz, pstage, units, ctrl, lane, stats);
+    else lz4_decode2_copy<DEC_RING, OFFS>(src, sz, out, frame_out, out_bytes, block_bytes, expect, ring, stage, owner_mark, units, ctrl, errflag, lane);
 }
 
 // stored (uncompressed) blocks of single-block frames: plain copy stream -> output, one workgroup per 32 KiB slice
 constexpr uint32_t DEC_COPY_SLICE = 32768;
 
+template <bool OFFS = false>
 __global__ __launch_bounds__(256)
 void lz4_stored_frames_copy_kernel(const uint8_t* __restrict__ in, const uint4* __restrict__ blk, const uint32_t* __restrict__ frame_first,
                                    uint8_t* __restrict__ out, uint64_t out_bytes, uint64_t frame_stride, uint32_t slices_per_frame,
@@ -4887,8 +4993,8 @@ void lz4_stored_frames_copy_kernel(const uint8_t* __restrict__ in, const uint4* 
     const uint4 e = blk[b0];
     if (!(e.z >> 31)) return;
     const uint32_t sz = e.z & 0x7fffffffu;
-    if (lz4_decode_frame_struck((uint64_t)f * frame_stride, remap, remap_bytes)) return;
-    const uint64_t o = lz4_decode_frame_out((uint64_t)f * frame_stride, remap, remap_bytes);
+    if (lz4_frame_struck<OFFS>(f, frame_stride, remap, remap_bytes)) return;
+    const uint64_t o = lz4_frame_out<OFFS>(f, frame_stride, remap, remap_bytes);
     if (o + sz > out_bytes) return;                              // the decode kernel reports it
     const uint32_t begin = slice * DEC_COPY_SLICE;
     if (begin >= sz) return;
@@ -6583,7 +6689,101 @@ hipError_t launch_lz4_frame_rank(const uint8_t* in, uint64_t n, void* blk, uint3
     return hipGetLastError();
 }
 
+uint64_t lz4_frame_rank_batch_desc_bytes(uint32_t njobs) { return (uint64_t)njobs * sizeof(RankJobDev); }
+
+hipError_t launch_lz4_frame_rank_batch(const Lz4RankJob* jobs, uint32_t njobs, void* d_desc, void* h_desc, hipStream_t stream)
+{
+    if (njobs == 0) return hipSuccess;
+    if (njobs > 65535u) return hipErrorInvalidValue;
+    RankJobDev* hd = static_cast<RankJobDev*>(h_desc);
+    const uint64_t gcap = (uint64_t)num_cus() * 4;
+    const uint64_t per_job = std::max<uint64_t>(gcap / njobs, 64);        // (the jobs' scans share the grid launch_lz4_frame_rank gives one)
+    uint64_t max_slots = 0, max_cand = 1;
+    size_t lds_bytes = 0;
+    for (uint32_t i = 0; i < njobs; ++i) {
+        const Lz4RankJob& a = jobs[i];
+        const uint64_t cap = a.expected_frames * 4 + 1024;                // the layout of lz4_frame_rank_scratch_bytes
+        uint64_t slots = 1024;
+        while (slots < cap * 4) slots *= 2;
+        uint8_t* p = static_cast<uint8_t*>(a.scratch);
+        RankJobDev& d = hd[i];
+        d.in = a.in; d.n = a.n; d.chunk = a.chunk; d.last = a.last; d.max_blocks = a.max_blocks; d.slots = slots;
+        d.table = reinterpret_cast<FrameSlot*>(p);
+        d.list = reinterpret_cast<FrameCand*>(p + slots * sizeof(FrameSlot));
+        d.work = reinterpret_cast<uint32_t*>(p + slots * sizeof(FrameSlot) + cap * sizeof(FrameCand));
+        d.ncand = d.work + 5 * (cap + 2);
+        d.blk = static_cast<uint4*>(a.blk); d.frame_first = a.frame_first; d.counts = a.counts;
+        d.cap = (uint32_t)cap;
+        d.kmax = (uint32_t)std::min<uint64_t>(a.expected_frames, 1u << 20);
+        uint64_t lds_entries = (a.expected_frames + 1024 + 2 + 7) & ~(uint64_t)7;
+        if (lds_entries > 16000) lds_entries = 0;                          // (144 KiB of the CU's 160; as launch_lz4_frame_rank)
+        d.lds_entries = (uint32_t)lds_entries;
+        lds_bytes = std::max<size_t>(lds_bytes, (size_t)lds_entries * 9);
+        uint64_t blocks = ((a.n + 15) / 16 + 1023) / 1024;
+        if (blocks > per_job) blocks = per_job;
+        if (blocks == 0) blocks = 1;
+        d.cand_blocks = (uint32_t)blocks;
+        max_slots = std::max(max_slots, slots);
+        max_cand = std::max(max_cand, blocks);
+    }
+    if (lds_bytes > 48 * 1024) {
+        static std::atomic<size_t> allowed{0};
+        if (allowed.load() < lds_bytes) {
+            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(lz4_frame_rank_batch_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024);
+            if (e != hipSuccess) {                                         // (the work arrays then stay in global memory)
+                (void)hipGetLastError();
+                for (uint32_t i = 0; i < njobs; ++i) hd[i].lds_entries = 0;
+                lds_bytes = 0;
+            } else allowed.store(144 * 1024);
+        }
+    }
+    hipError_t e = hipMemcpyAsync(d_desc, h_desc, lz4_frame_rank_batch_desc_bytes(njobs), hipMemcpyHostToDevice, stream);
+    if (e != hipSuccess) return e;
+    const RankJobDev* dd = static_cast<const RankJobDev*>(d_desc);
+    const uint64_t clear_blocks = std::min<uint64_t>((max_slots + 255) / 256, 1024);
+    hipLaunchKernelGGL(lz4_frame_rank_clear_batch_kernel, dim3((unsigned)clear_blocks, njobs), dim3(256), 0, stream, dd);
+    hipLaunchKernelGGL(lz4_frame_probe_batch_kernel, dim3(njobs), dim3(1), 0, stream, dd);
+    hipLaunchKernelGGL(lz4_frame_tail_batch_kernel, dim3(njobs), dim3(1024), 0, stream, dd);
+    hipLaunchKernelGGL(lz4_frame_candidates_batch_kernel, dim3((unsigned)max_cand, njobs), dim3(256), 0, stream, dd);
+    hipLaunchKernelGGL(lz4_frame_rank_batch_kernel, dim3(njobs), dim3(1024), lds_bytes, stream, dd);
+    return hipGetLastError();
+}
+
 constexpr uint32_t SQY_RING8_MIN = 2560;
+// the decode kernels of launch_lz4_frames_decode and their choice by the frames' counts; OFFS: launch_lz4_frames_joint_decode's table mode
+template <bool OFFS>
+static hipError_t lz4_frames_decode_kernels(const uint8_t* in, const void* blk, const uint32_t* frame_first, uint32_t nframes, uint8_t* out,
+                                            uint64_t out_bytes, uint64_t frame_stride, uint64_t block_bytes, uint32_t ncompressed,
+                                            uint32_t* errflag, hipStream_t stream, hipStream_t cs, const uint64_t* remap, uint64_t remap_bytes, bool two_waves)
+{
+    if (two_waves && !(ncompressed > SQY_RING8_MIN && nframes > SQY_RING8_MIN)) {
+        // (a 32 KiB ring here would serve nine in ten of the matches that reach behind 16 KiB -- a seventh of the bench stack's -- out of
+        // LDS, but only three frames fit a CU then: measured, 0.63 -> 0.73 ms)
+        if (ncompressed > 768u && nframes > 768u)
+            hipLaunchKernelGGL((lz4_frames_decode2_kernel<16384, OFFS>), dim3(nframes), dim3(128), 0, stream, in, (const uint4*)blk, frame_first, out,
+                               out_bytes, frame_stride, block_bytes, errflag, remap, remap_bytes);
+        else
+            hipLaunchKernelGGL((lz4_frames_decode2_kernel<65536, OFFS>), dim3(nframes), dim3(128), 0, stream, in, (const uint4*)blk, frame_first, out,
+                               out_bytes, frame_stride, block_bytes, errflag, remap, remap_bytes);
+    } else
+    if (ncompressed > SQY_RING8_MIN && nframes > SQY_RING8_MIN)
+        hipLaunchKernelGGL((lz4_frames_decode_kernel<8192, OFFS>), dim3(nframes), dim3(64), 0, stream, in, (const uint4*)blk, frame_first, out,
+                           out_bytes, frame_stride, block_bytes, errflag, remap, remap_bytes);
+    else if (ncompressed > 768u && nframes > 768u)
+        hipLaunchKernelGGL((lz4_frames_decode_kernel<16384, OFFS>), dim3(nframes), dim3(64), 0, stream, in, (const uint4*)blk, frame_first, out,
+                           out_bytes, frame_stride, block_bytes, errflag, remap, remap_bytes);
+    else
+        hipLaunchKernelGGL((lz4_frames_decode_kernel<65536, OFFS>), dim3(nframes), dim3(64), 0, stream, in, (const uint4*)blk, frame_first, out,
+                           out_bytes, frame_stride, block_bytes, errflag, remap, remap_bytes);
+    {   // stored blocks of single-block frames (a block never exceeds block_bytes)
+        const uint32_t slices = (uint32_t)((block_bytes + DEC_COPY_SLICE - 1) / DEC_COPY_SLICE);
+        if (slices == 0 || (uint64_t)nframes * slices > 0x7fffffffull) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(lz4_stored_frames_copy_kernel<OFFS>, dim3(nframes * slices), dim3(256), 0, cs, in, (const uint4*)blk, frame_first,
+                           out, out_bytes, frame_stride, slices, remap, remap_bytes);
+    }
+    return hipGetLastError();
+}
+
 hipError_t launch_lz4_frames_decode(const uint8_t* in, const void* blk, const uint32_t* frame_first, uint32_t nframes, uint8_t* out,
                                     uint64_t out_bytes, uint64_t frame_stride, uint64_t block_bytes, uint32_t ncompressed,
                                     uint32_t* errflag, hipStream_t stream, hipStream_t copy_stream, hipEvent_t fork, hipEvent_t join,
@@ -6612,33 +6812,69 @@ hipError_t launch_lz4_frames_decode(const uint8_t* in, const void* blk, const ui
     // sequences are, the other moves the bytes (lz4_frames_decode2_kernel)
     // (not beyond that: the C3 slab's 3584 frames through two waves each, 8 KiB ring, take 7.1 ms against 2.6 -- that range is bound by the
     // instructions issued, and two waves issue more of them)
-    if (two_waves && !(ncompressed > SQY_RING8_MIN && nframes > SQY_RING8_MIN)) {
-        // (a 32 KiB ring here would serve nine in ten of the matches that reach behind 16 KiB -- a seventh of the bench stack's -- out of
-        // LDS, but only three frames fit a CU then: measured, 0.63 -> 0.73 ms)
-        if (ncompressed > 768u && nframes > 768u)
-            hipLaunchKernelGGL(lz4_frames_decode2_kernel<16384>, dim3(nframes), dim3(128), 0, stream, in, (const uint4*)blk, frame_first, out,
-                               out_bytes, frame_stride, block_bytes, errflag, remap, remap_bytes);
-        else
-            hipLaunchKernelGGL(lz4_frames_decode2_kernel<65536>, dim3(nframes), dim3(128), 0, stream, in, (const uint4*)blk, frame_first, out,
-                               out_bytes, frame_stride, block_bytes, errflag, remap, remap_bytes);
-    } else
-    if (ncompressed > SQY_RING8_MIN && nframes > SQY_RING8_MIN)
-        hipLaunchKernelGGL(lz4_frames_decode_kernel<8192>, dim3(nframes), dim3(64), 0, stream, in, (const uint4*)blk, frame_first, out,
-                           out_bytes, frame_stride, block_bytes, errflag, remap, remap_bytes);
-    else if (ncompressed > 768u && nframes > 768u)
-        hipLaunchKernelGGL(lz4_frames_decode_kernel<16384>, dim3(nframes), dim3(64), 0, stream, in, (const uint4*)blk, frame_first, out,
-                           out_bytes, frame_stride, block_bytes, errflag, remap, remap_bytes);
-    else
-        hipLaunchKernelGGL(lz4_frames_decode_kernel<65536>, dim3(nframes), dim3(64), 0, stream, in, (const uint4*)blk, frame_first, out,
-                           out_bytes, frame_stride, block_bytes, errflag, remap, remap_bytes);
-    {   // stored blocks of single-block frames (a block never exceeds block_bytes)
-        const uint32_t slices = (uint32_t)((block_bytes + DEC_COPY_SLICE - 1) / DEC_COPY_SLICE);
-        if (slices == 0 || (uint64_t)nframes * slices > 0x7fffffffull) return hipErrorInvalidValue;
-        hipLaunchKernelGGL(lz4_stored_frames_copy_kernel, dim3(nframes * slices), dim3(256), 0, cs, in, (const uint4*)blk, frame_first,
-                           out, out_bytes, frame_stride, slices, remap, remap_bytes);
+    {
+        const hipError_t e = lz4_frames_decode_kernels<false>(in, blk, frame_first, nframes, out, out_bytes, frame_stride, block_bytes, ncompressed, errflag,
+                                                              stream, cs, remap, remap_bytes, two_waves);
+        if (e != hipSuccess) return e;
     }
     if (side) {
         hipError_t e = hipEventRecord(join, copy_stream);
+        if (e != hipSuccess) return e;
+        e = hipStreamWaitEvent(stream, join, 0);
+        if (e != hipSuccess) return e;
+    }
+    return hipGetLastError();
+}
+
+// ---- several blobs' LZ4 streams in one launch (SQYAMD_Decode_Slabs_*) ----------------------------------------------------------------------
+// The joint block index: part p's frames (its own index, blk with offsets into its stream) get the joint numbers jbase + f, their block
+// offsets are made relative to the joint `in` (+ in_off), and every frame its output offset and size in jout (two words; ~0: struck).
+// Frames of single blocks only (the ranked chunked layout, frame_first[f] = f): jff is the identity.
+__global__ __launch_bounds__(256)
+void lz4_joint_index_kernel(const Lz4JointPart* __restrict__ parts, uint4* __restrict__ jblk, uint32_t* __restrict__ jff, uint64_t* __restrict__ jout)
+{
+    const Lz4JointPart& p = parts[blockIdx.y];
+    const uint32_t f = blockIdx.x * 256u + threadIdx.x;
+    if (f >= p.nframes) return;
+    const uint4 e = static_cast<const uint4*>(p.blk)[f];
+    const uint64_t off = (((uint64_t)e.y << 32) | e.x) + p.in_off;
+    const uint32_t j = p.jbase + f;
+    jblk[j] = make_uint4((uint32_t)off, (uint32_t)(off >> 32), e.z, 0u);
+    jff[j] = j;
+    if (f + 1u == p.nframes) jff[j + 1u] = j + 1u;
+    const uint64_t o = (uint64_t)f * p.chunk;
+    const uint64_t want = p.total - o < p.chunk ? p.total - o : p.chunk;
+    uint64_t at = p.out_base + o;
+    if (p.remap) {
+        const uint64_t fi = o / p.remap_bytes, v = p.remap[fi];
+        at = v == ~0ull ? ~0ull : p.out_base + v * p.remap_bytes + (o - fi * p.remap_bytes);
+    }
+    jout[2u * (uint64_t)j] = at;
+    jout[2u * (uint64_t)j + 1u] = want;
+}
+
+hipError_t launch_lz4_frames_joint_decode(const uint8_t* in, const Lz4JointPart* d_parts, uint32_t nparts, uint32_t max_part_frames, void* jblk,
+                                          uint32_t* jff, uint64_t* jout, uint32_t nframes, uint8_t* out, uint64_t out_bytes, uint64_t block_bytes,
+                                          uint32_t ncompressed, uint32_t* errflag, hipStream_t stream, hipStream_t copy_stream, hipEvent_t fork,
+                                          hipEvent_t join, bool two_waves)
+{
+    if (nframes == 0 || nparts == 0) return hipSuccess;
+    if (nparts > 65535u || block_bytes == 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(lz4_joint_index_kernel, dim3((max_part_frames + 255u) / 256u, nparts), dim3(256), 0, stream, d_parts, (uint4*)jblk, jff, jout);
+    const bool side = copy_stream && copy_stream != stream && fork && join;
+    hipStream_t cs = side ? copy_stream : stream;
+    if (side) {
+        hipError_t e = hipEventRecord(fork, stream);
+        if (e != hipSuccess) return e;
+        e = hipStreamWaitEvent(copy_stream, fork, 0);
+        if (e != hipSuccess) return e;
+    }
+    // (frame_stride is not read in the table mode; the chunk-sized block bound stays block_bytes)
+    hipError_t e = lz4_frames_decode_kernels<true>(in, jblk, jff, nframes, out, out_bytes, block_bytes, block_bytes, ncompressed, errflag, stream, cs,
+                                                   jout, 1, two_waves);
+    if (e != hipSuccess) return e;
+    if (side) {
+        e = hipEventRecord(join, copy_stream);
         if (e != hipSuccess) return e;
         e = hipStreamWaitEvent(stream, join, 0);
         if (e != hipSuccess) return e;
@@ -6806,7 +7042,7 @@ hipError_t launch_lz4_frames_subset_decode(const uint8_t* in, const void* blk, c
                            out_bytes, frame_stride, block_bytes, errflag, remap, remap_bytes);
     const uint32_t slices = (uint32_t)((block_bytes + DEC_COPY_SLICE - 1) / DEC_COPY_SLICE);
     if (slices == 0 || (uint64_t)nsel * slices > 0x7fffffffull) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(lz4_stored_frames_copy_kernel, dim3(nsel * slices), dim3(256), 0, stream, in, (const uint4*)sblk, sff,
+    hipLaunchKernelGGL(lz4_stored_frames_copy_kernel<false>, dim3(nsel * slices), dim3(256), 0, stream, in, (const uint4*)sblk, sff,
                        out, out_bytes, frame_stride, slices, remap, remap_bytes);
     return hipGetLastError();
 }

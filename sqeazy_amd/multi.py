@@ -180,6 +180,27 @@ def unpack_container(buf):
     return out
 
 
+def decode_container(buf, dtype):
+    """the volume of a sharded container (u64 count | u64 sizes | blobs, pack_container) through SQYAMD_Decode_Slabs_*: returns
+    (rc, ndarray or None); rc 1 when the blobs do not hold `dtype` voxels"""
+    import sqeazy_amd
+    buf = bytes(buf)
+    count = int(np.frombuffer(buf[:8], dtype=np.uint64)[0]) if len(buf) >= 8 else 0
+    if count <= 0 or len(buf) < 8 + 8 * count:
+        return 1, None
+    sizes = [int(s) for s in np.frombuffer(buf[8:8 + 8 * count], dtype=np.uint64)]
+    offsets, at = [], 8 + 8 * count
+    for s in sizes:
+        offsets.append(at)
+        at += s
+    if at > len(buf):
+        return 1, None
+    first = buf[offsets[0]:offsets[0] + sizes[0]]
+    if sqeazy_amd.decompressed_sizeof(first) != np.dtype(dtype).itemsize:
+        return 1, None
+    return sqeazy_amd.decode_slabs_packed(buf, offsets, sizes)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # Single-blob mode (SURVEY.md 8(e), "optional"): N ranks produce ONE blob, byte-identical to what one call on the whole
 # volume yields, for `bitswap1->lz4` in the chunked layout.  The whole volume's payload is the 16 (8) bit planes one after
