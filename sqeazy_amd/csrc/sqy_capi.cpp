@@ -1385,9 +1385,18 @@ bool header_shape_ok(const sqy::HeaderInfo& h, uint64_t srclen, uint64_t* raw_by
     return true;
 }
 
+// The last synchronisation of a decode: the LZ4 decoder's error flag (nullptr: no LZ4 decode ran) comes back with it, *raised says what it holds
+int lz4_verdict(Context& cx, const uint32_t* flag, hipStream_t stream, bool* raised)
+{
+    if (flag) SQY_HIP(hipMemcpyAsync(cx.ws.pinned, flag, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    SQY_HIP(hipStreamSynchronize(stream));
+    if (g_prof_on.load()) prof_collect(cx.pending);
+    *raised = flag && *static_cast<const uint32_t*>(cx.ws.pinned);
+    return 0;
+}
+
 // Where the frames and blocks of an LZ4 payload are (lz4_frame_rank / lz4_frame_index), in ws->lz4_scratch and ws->csize
-struct Lz4Index {
-    uint64_t chunk = 0, nchunks = 0, block_bytes = 0;
+struct Lz4Index : sqy::Lz4DecodeGeometry {
     uint8_t* blk = nullptr;
     uint32_t* frame_first = nullptr;
     uint32_t* counts = nullptr;                  // [0..3] index result, [4] decode error flag
@@ -1497,28 +1506,25 @@ struct DecodeCall {
         Z = Z0 / fcs;
         frame_bytes_dec = Y * X * (uint64_t)elem_before[fi] * fcs;
         if (it == fs.cfg.end() || !sqy::from_verbatim(it->second, &fs_map)) { std::fprintf(stderr, "[sqeazy]\t frame_shuffle: no reorder_map in the header\n"); return 1; }
-        if (fs_map.size() != Z * 8) { std::fprintf(stderr, "[sqeazy]\t frame_shuffle: malformed reorder_map\n"); return 1; }
-        std::vector<bool> targeted(Z, false);
-        permutation = true;
-        for (uint64_t i = 0; i < Z; ++i) {
-            uint64_t v; std::memcpy(&v, fs_map.data() + 8 * i, 8);
-            if (v >= Z) { std::fprintf(stderr, "[sqeazy]\t frame_shuffle: reorder_map out of range\n"); return 1; }
-            if (targeted[v]) permutation = false;
-            targeted[v] = true;
+        if (!sqy::frame_shuffle_decode_map(&fs_map, Z, &fs_unnamed, &permutation)) {
+            std::fprintf(stderr, fs_map.size() != Z * 8 ? "[sqeazy]\t frame_shuffle: malformed reorder_map\n" : "[sqeazy]\t frame_shuffle: reorder_map out of range\n");
+            return 1;
         }
-        fs_unnamed.clear();
-        if (!permutation) for (uint64_t v = 0; v < Z; ++v) if (!targeted[v]) fs_unnamed.push_back(v);
-        if (!permutation) {
-            // A map that names a place twice (frames of equal metric on the encoder's side: same bytes -- or a crafted blob: not): the
-            // reference's decode walks the frames in order, the LAST one named for a place stays (frame_shuffle_utils.hpp:337-344).
-            // Same here, whatever order the scatter's workgroups run in: the earlier ones are struck from the device's copy of the map.
-            std::vector<uint64_t> last(Z, ~0ull);
-            for (uint64_t i = 0; i < Z; ++i) { uint64_t v; std::memcpy(&v, fs_map.data() + 8 * i, 8); last[v] = i; }
-            for (uint64_t i = 0; i < Z; ++i) {
-                uint64_t v; std::memcpy(&v, fs_map.data() + 8 * i, 8);
-                if (last[v] != i) { const uint64_t none = ~0ull; std::memcpy(fs_map.data() + 8 * i, &none, 8); }
-            }
-        }
+        return 0;
+    }
+    // frame_shuffle right in front of the LZ4 stage si (on the encoder's side), both on the same `total` bytes of a 3-D volume
+    bool shuffle_in_front(size_t si, uint64_t total) const
+    {
+        return preceded_by(si, StageKind::frame_shuffle) && in_bytes(si - 1) == total && h.shape.size() == 3;
+    }
+    // .. and the chunked layout with every chunk inside one of the shuffle's Z places of fb bytes: *fold, the LZ4 frames can be decoded
+    // straight to where the shuffle's inverse would move them (fs_map; upload: in ws->small as well)
+    int shuffle_fold(size_t si, uint64_t total, const sqy::Lz4DecodeGeometry& g, uint64_t nframes, bool upload, uint64_t& Z, uint64_t& fb, bool& permutation, bool* fold)
+    {
+        *fold = false;
+        if (!(shuffle_in_front(si, total) && sqy::lz4_chunks_whole(nframes, g.nchunks, total, g.chunk))) return 0;
+        if (const int rc = upload ? frame_shuffle_prepare(si - 1, Z, fb, permutation) : frame_shuffle_map(si - 1, Z, fb, permutation)) return rc;
+        *fold = sqy::lz4_folds_into_shuffle(nframes, g.nchunks, total, g.chunk, Z, fb);
         return 0;
     }
 
@@ -1544,10 +1550,8 @@ struct DecodeCall {
     int lz4_index(size_t si, uint64_t total, Lz4Index& ix)
     {
         const Stage& st = pipe.stages[si];
-        ix.chunk = total ? st.lz4.bytes_per_chunk(total) : 1;
-        ix.block_bytes = st.lz4.block_bytes();
-        ix.nchunks = total ? (total + ix.chunk - 1) / ix.chunk : 0;
-        const uint64_t max_blocks = std::max<uint64_t>(ix.nchunks * ((ix.chunk + ix.block_bytes - 1) / ix.block_bytes), total / ix.block_bytes + 1) + 16;
+        static_cast<sqy::Lz4DecodeGeometry&>(ix) = sqy::lz4_decode_geometry(st.lz4, total);
+        const uint64_t max_blocks = ix.max_blocks;
         // block list, frame starts, and a table of frame-start candidates (16 B x >= 8 slots per expected frame)
         const uint64_t idx_bytes = (max_blocks * 16 + (max_blocks + 2) * 4 + 64 + 15) & ~15ull;
         const uint64_t cand_bytes = sqy::lz4_frame_rank_scratch_bytes(ix.nchunks);
@@ -1595,18 +1599,14 @@ struct DecodeCall {
     // config's decode 1.49 -> 1.1 ms)
     int lz4_remap(size_t si, uint64_t total, const Lz4Index& ix, Lz4Remap& rm)
     {
-        const uint32_t nframes = ix.hc[0];
-        if (!(preceded_by(si, StageKind::frame_shuffle) && nframes == ix.nchunks && nframes > 1 && total % ix.chunk == 0 && in_bytes(si - 1) == total &&
-              h.shape.size() == 3))
-            return 0;
         uint64_t Z = 0, fb = 0;
-        bool permutation = true;
-        if (const int rc = frame_shuffle_prepare(si - 1, Z, fb, permutation)) return rc;
+        bool permutation = true, fold = false;
+        if (const int rc = shuffle_fold(si, total, ix, ix.hc[0], true, Z, fb, permutation, &fold)) return rc;
         // (round-5 advice) a map that names a place twice -- frames of equal metric on the encoder's side, or a crafted blob --:
         // several LZ4 frames must not decode into one place at once (the ring kernels read matches that reach behind their
         // ring back from there).  The device's copy of such a map has every frame but the last one named for a place struck
         // (frame_shuffle_prepare): struck frames are not decoded, the places nobody names are zeroed first.
-        if (fb && fb % ix.chunk == 0 && Z * fb == total) {
+        if (fold) {
             rm.map = static_cast<const uint64_t*>(ws->small.p);
             rm.bytes = fb;
             rm.zero = !permutation;
@@ -1812,6 +1812,16 @@ struct DecodeCall {
         return produced(out, in_bytes(si));
     }
 
+    // the call's last synchronisation, and with it the LZ4 decoder's verdict
+    int finish()
+    {
+        bool raised = false;
+        if (const int rc = lz4_verdict(cx, lz4_flag, stream, &raised)) return rc;
+        if (!raised) return 0;
+        std::fprintf(stderr, "[sqy::lz4] corrupt LZ4 block, or a frame that does not decode to its share of the volume\n");
+        return stage_error((size_t)lz4_flag_stage);
+    }
+
     // ---- frame-range decode (SQYAMD_Decode_Frames_*) ----
     // Frames [z0, z0 + nz) of the volume (fb bytes each) into d_dst, decoding only the LZ4 frames they need.  Taken for the chunked
     // layout of  [heads ->] lz4 | bitswap1->lz4 | quantiser->bitswap1->lz4 | frame_shuffle->lz4  (the background heads decode as a copy);
@@ -1826,131 +1836,74 @@ struct DecodeCall {
         if (ns == 0 || pipe.stages[ns - 1].kind != StageKind::lz4 || lead >= ns) return 0;
         const size_t li = ns - 1, nfront = li - lead;
         auto kind = [&](size_t i) { return pipe.stages[i].kind; };
-        enum Form { PLAIN, PLANES, PLANES_LUT, SHUFFLE } form;
-        if (nfront == 0) form = PLAIN;
-        else if (nfront == 1 && kind(lead) == StageKind::bitswap1) form = PLANES;
-        else if (nfront == 1 && kind(lead) == StageKind::frame_shuffle) form = SHUFFLE;
-        else if (nfront == 2 && kind(lead) == StageKind::quantiser && kind(lead + 1) == StageKind::bitswap1) form = PLANES_LUT;
+        typedef sqy::RangeForm Form;
+        Form form;
+        if (nfront == 0) form = Form::plain;
+        else if (nfront == 1 && kind(lead) == StageKind::bitswap1) form = Form::planes;
+        else if (nfront == 1 && kind(lead) == StageKind::frame_shuffle) form = Form::shuffle;
+        else if (nfront == 2 && kind(lead) == StageKind::quantiser && kind(lead + 1) == StageKind::bitswap1) form = Form::planes_lut;
         else return 0;
         const int e = h.elem_size();
         const uint64_t total = in_bytes(li);
-        // the stream in front of lz4 holds the voxels in their order (PLANES_LUT: one quantised byte per voxel)
-        if (total != n * (uint64_t)(form == PLANES_LUT ? 1 : e)) return 0;
-        if (form == PLANES && (elem_before[lead] != e || count_before[lead] != n)) return 0;
-        if (form == PLANES_LUT && (e != 2 || elem_before[lead + 1] != 1 || count_before[lead + 1] != n)) return 0;
-        if (form == SHUFFLE && !(h.shape.size() == 3 && in_bytes(lead) == total)) return 0;
+        // the stream in front of lz4 holds the voxels in their order (planes_lut: one quantised byte per voxel)
+        if (total != n * (uint64_t)(form == Form::planes_lut ? 1 : e)) return 0;
+        if (form == Form::planes && (elem_before[lead] != e || count_before[lead] != n)) return 0;
+        if (form == Form::planes_lut && (e != 2 || elem_before[lead + 1] != 1 || count_before[lead + 1] != n)) return 0;
+        if (form == Form::shuffle && !shuffle_in_front(li, total)) return 0;
         Lz4Index ix;
         if (const int rc = lz4_index(li, total, ix)) return rc;
         const uint32_t nframes = ix.hc[0];
         if (nframes < 2 || nframes != ix.nchunks) return 0;          // one frame, or the serial layout: the history runs from the start
         const uint64_t chunk = ix.chunk;
-
-        std::vector<uint32_t> ids;                                     // the LZ4 frames to decode, ascending
-        std::vector<uint64_t> remap;                                   // SHUFFLE: place (relative to the range's first) of every slot decoded
-        uint64_t out_bytes = 0;
-        uint8_t* sbuf = nullptr;                                       // where the subset decodes to
-        uint64_t pa = 0, pb = 0, fbp = 0;                              // SHUFFLE: places [pa, pb) of fbp bytes cover the range
-        std::vector<uint64_t> coff;                                    // else: offset of frame f in the compacted stream
-        if (form == SHUFFLE) {
-            // the lz4_remap conditions: whole chunks inside whole places
-            if (total % chunk != 0) return 0;
-            uint64_t P = 0;
-            bool permutation = true;
-            if (const int rc = frame_shuffle_prepare(lead, P, fbp, permutation)) return rc;
-            if (!(fbp && fbp % chunk == 0 && P * fbp == total)) return 0;
-            pa = z0 * fb / fbp;
-            pb = ((z0 + nz) * fb + fbp - 1) / fbp;
-            const uint64_t cpf = fbp / chunk;
-            // fs_map has every slot but the last one named for a place struck (~0): the last one wins, as in the full decode
-            for (uint64_t i = 0; i < P; ++i) {
-                uint64_t v;
-                std::memcpy(&v, fs_map.data() + 8 * i, 8);
-                if (v == ~0ull || v < pa || v >= pb) continue;
-                remap.push_back(v - pa);
-                for (uint64_t c = 0; c < cpf; ++c) ids.push_back((uint32_t)(i * cpf + c));
-            }
-            out_bytes = (pb - pa) * fbp;
-        } else {
-            // byte spans of the stream in front of lz4 that the range needs
-            std::vector<std::pair<uint64_t, uint64_t>> spans;
-            const uint64_t vpf = n / h.shape[0], v0 = z0 * vpf, v1 = (z0 + nz) * vpf;
-            if (form == PLAIN)
-                spans.push_back({v0 * (uint64_t)e, v1 * (uint64_t)e});
-            else {
-                const uint64_t we = form == PLANES ? (uint64_t)e : 1, W = 8 * we, seg = n / W, L = seg * W;
-                const uint64_t w0 = std::min(v0 / W, seg), w1 = std::min((v1 + W - 1) / W, seg);
-                if (w0 < w1) for (uint64_t s = 0; s < W; ++s) spans.push_back({(s * seg + w0) * we, (s * seg + w1) * we});
-                if (v1 > L) spans.push_back({std::max(v0, L) * we, v1 * we});
-            }
-            std::vector<char> need(nframes, 0);
-            for (const auto& sp : spans) for (uint64_t f = sp.first / chunk; f <= (sp.second - 1) / chunk; ++f) need[f] = 1;
-            coff.assign(nframes, 0);
-            for (uint32_t f = 0; f < nframes; ++f) {
-                if (!need[f]) continue;
-                coff[f] = out_bytes;
-                ids.push_back(f);
-                out_bytes += std::min<uint64_t>(chunk, total - (uint64_t)f * chunk);
-            }
+        uint64_t P = 0, fbp = 0;                                       // shuffle: P places of fbp bytes
+        if (form == Form::shuffle) {
+            bool permutation = true, fold = false;
+            if (const int rc = shuffle_fold(li, total, ix, nframes, true, P, fbp, permutation, &fold)) return rc;
+            if (!fold) return 0;
         }
+        // the LZ4 frames the range needs and where its bytes lie behind their decode
+        const sqy::FrameRangePlan p = sqy::frame_range_plan(form, n, e, h.shape[0], z0, nz, chunk, total, nframes, fs_map, fbp, P);
+        if (!p.ok) return 0;
 
         // the tables: ids | subset frame starts | remap | subset block index
-        const uint64_t nsel = ids.size(), mpf = (chunk + ix.block_bytes - 1) / ix.block_bytes;
-        const uint64_t o_ff = (nsel * 4 + 15) & ~15ull, o_map = o_ff + (((nsel + 1) * 4 + 15) & ~15ull), o_blk = o_map + ((remap.size() * 8 + 15) & ~15ull);
+        const uint64_t nsel = p.ids.size(), mpf = (chunk + ix.block_bytes - 1) / ix.block_bytes;
+        const uint64_t o_ff = (nsel * 4 + 15) & ~15ull, o_map = o_ff + (((nsel + 1) * 4 + 15) & ~15ull), o_blk = o_map + ((p.remap.size() * 8 + 15) & ~15ull);
         if (ws->subset.ensure(std::max<uint64_t>(o_blk + nsel * mpf * 16, 16))) return 1;
         sub_host.assign(o_blk, 0);
-        if (nsel) std::memcpy(sub_host.data(), ids.data(), nsel * 4);
-        if (!remap.empty()) std::memcpy(sub_host.data() + o_map, remap.data(), remap.size() * 8);
+        if (nsel) std::memcpy(sub_host.data(), p.ids.data(), nsel * 4);
+        if (!p.remap.empty()) std::memcpy(sub_host.data() + o_map, p.remap.data(), p.remap.size() * 8);
         uint8_t* d_sub = static_cast<uint8_t*>(ws->subset.p);
         if (o_blk) SQY_HIP(hipMemcpyAsync(d_sub, sub_host.data(), o_blk, hipMemcpyHostToDevice, stream));
 
         *taken = true;
-        // SHUFFLE with the range on place boundaries (frame_chunk_size 1): straight into d_dst; else through the workspace
-        const bool direct = form == SHUFFLE && pa * fbp == z0 * fb && pb * fbp == (z0 + nz) * fb;
-        sbuf = direct ? static_cast<uint8_t*>(d_dst) : work_buf(out_bytes);
+        // shuffle with the range on place boundaries (frame_chunk_size 1): straight into d_dst; else through the workspace
+        uint8_t* sbuf = p.direct ? static_cast<uint8_t*>(d_dst) : work_buf(p.out_bytes);     // where the subset decodes to
         if (!sbuf) return 1;
-        if (form == SHUFFLE) {
-            // places of the range that no slot names come out as zeros (frame_shuffle's inverse)
-            std::vector<char> named(pb - pa, 0);
-            for (uint64_t v : remap) named[v] = 1;
-            for (uint64_t k = 0; k < pb - pa;) {
-                if (named[k]) { ++k; continue; }
-                uint64_t k1 = k;
-                while (k1 < pb - pa && !named[k1]) ++k1;
-                SQY_HIP(hipMemsetAsync(sbuf + k * fbp, 0, (k1 - k) * fbp, stream));
-                k = k1;
-            }
-        }
+        // places of the range that no slot names come out as zeros (frame_shuffle's inverse)
+        for (const auto& run : p.zero_runs) SQY_HIP(hipMemsetAsync(sbuf + run.first * fbp, 0, (run.second - run.first) * fbp, stream));
         if (nsel) {
             SQY_TIMED("lz4_frames_subset_decode",
                       sqy::launch_lz4_frames_subset_decode(cur, ix.blk, ix.frame_first, nframes, reinterpret_cast<const uint32_t*>(d_sub), (uint32_t)nsel,
-                                                           (uint32_t)mpf, d_sub + o_blk, reinterpret_cast<uint32_t*>(d_sub + o_ff), sbuf, out_bytes, chunk,
+                                                           (uint32_t)mpf, d_sub + o_blk, reinterpret_cast<uint32_t*>(d_sub + o_ff), sbuf, p.out_bytes, chunk,
                                                            ix.block_bytes, ix.hc[3], ix.counts + 4, stream,
-                                                           form == SHUFFLE ? reinterpret_cast<const uint64_t*>(d_sub + o_map) : nullptr, fbp,
+                                                           form == Form::shuffle ? reinterpret_cast<const uint64_t*>(d_sub + o_map) : nullptr, fbp,
                                                            g_opt.decode_two_waves.load() && ix.hc[1] == nframes));
             lz4_flag = ix.counts + 4;
             lz4_flag_stage = (int)li;
         }
-        auto compact = [&](uint64_t b) { const uint64_t f = b / chunk; return coff[f] + (b - f * chunk); };
-        const uint64_t range_bytes = nz * fb;
-        if (form == SHUFFLE) {
-            if (!direct) SQY_TIMED("frames_range_copy", hipMemcpyAsync(d_dst, sbuf + (z0 * fb - pa * fbp), range_bytes, hipMemcpyDeviceToDevice, stream));
-        } else if (form == PLAIN) {
-            SQY_TIMED("frames_range_copy", hipMemcpyAsync(d_dst, sbuf + compact(z0 * fb), range_bytes, hipMemcpyDeviceToDevice, stream));
-        } else {
-            const uint64_t we = form == PLANES ? (uint64_t)e : 1, W = 8 * we, seg = n / W, L = seg * W;
-            const uint64_t vpf = n / h.shape[0];
+        if (form == Form::plain || (form == Form::shuffle && !p.direct)) {
+            SQY_TIMED("frames_range_copy", hipMemcpyAsync(d_dst, sbuf + p.range_at, nz * fb, hipMemcpyDeviceToDevice, stream));
+        } else if (form != Form::shuffle) {
             sqy::Bitswap1Range r{};
-            r.v0 = z0 * vpf; r.v1 = (z0 + nz) * vpf; r.L = L;
-            r.w0 = std::min(r.v0 / W, seg); r.w1 = std::min((r.v1 + W - 1) / W, seg);
-            if (r.w0 < r.w1) for (uint64_t s = 0; s < W; ++s) r.plane[s] = compact((s * seg + r.w0) * we);
-            if (r.v1 > L) r.tail = compact(std::max(r.v0, L) * we);
+            std::copy(p.plane, p.plane + 16, r.plane);
+            r.tail = p.tail; r.w0 = p.w0; r.w1 = p.w1; r.v0 = p.v0; r.v1 = p.v1; r.L = p.L;
             const uint16_t* lut = nullptr;
-            if (form == PLANES_LUT) {
+            if (form == Form::planes_lut) {
                 if (quantiser_lut_to_device(pipe.stages[lead], ws)) return 1;
                 lut = static_cast<const uint16_t*>(ws->small.p);
             }
             SQY_TIMED(lut ? "bitswap1_quantiser_decode_range" : "bitswap1_decode_range",
-                      sqy::launch_bitswap1_decode_range(sbuf, d_dst, r, (int)we, lut, stream));
+                      sqy::launch_bitswap1_decode_range(sbuf, d_dst, r, p.we, lut, stream));
         }
         return 0;
     }
@@ -1998,6 +1951,19 @@ int decode_stages(DecodeCall& c, size_t from)
     return 0;
 }
 
+// Admission of an untrusted blob by its header: the voxel type the entry point was called for (who: how the message names the blob), a
+// pipeline this library implements, and header_shape_ok (every extent positive, fewer than 2^31 voxels, no wrap-around anywhere)
+bool admit_blob(const sqy::HeaderInfo& h, uint64_t srclen, int want_elem, uint64_t* raw_bytes, const char* who = "blob")
+{
+    if (h.elem_size() != want_elem) { std::fprintf(stderr, "[sqeazy]\t %s holds %s voxels\n", who, h.type.c_str()); return false; }
+    std::string why;
+    if (!Pipeline::supported(h.pipename, want_elem, &why)) {
+        std::fprintf(stderr, "[sqeazy]\t%s cannot be build with this version of sqeazy (%s)\n", h.pipename.c_str(), why.c_str());
+        return false;
+    }
+    return header_shape_ok(h, srclen, raw_bytes);
+}
+
 int decode_on_device(Context& cx, const void* d_src_v, uint64_t srclen, void* d_dst, uint64_t dst_capacity, int want_elem, hipStream_t stream)
 {
     if (!d_src_v || !d_dst) return 1;
@@ -2005,34 +1971,17 @@ int decode_on_device(Context& cx, const void* d_src_v, uint64_t srclen, void* d_
     DrainOnExit drain{stream, &cx.pending, cx.side};
     sqy::HeaderInfo h;
     if (fetch_header(d_src, srclen, stream, h)) return 1;
-    const int elem = h.elem_size();
-    if (elem != want_elem) { std::fprintf(stderr, "[sqeazy]\t blob holds %s voxels\n", h.type.c_str()); return 1; }
-    std::string why;
-    if (!Pipeline::supported(h.pipename, elem, &why)) {
-        std::fprintf(stderr, "[sqeazy]\t%s cannot be build with this version of sqeazy (%s)\n", h.pipename.c_str(), why.c_str());
-        return 1;
-    }
-    Pipeline pipe = Pipeline::from_string(h.pipename);
-    // the header is untrusted input: every extent positive, the voxel count below 2^31 (what one encode call can have
-    // produced), no wrap-around anywhere
     uint64_t raw_bytes = 0;
-    if (!header_shape_ok(h, srclen, &raw_bytes)) return 1;
+    if (!admit_blob(h, srclen, want_elem, &raw_bytes)) return 1;
     if (raw_bytes > dst_capacity) {
         std::fprintf(stderr, "[sqeazy]\t decode: buffer too small or blob truncated\n");
         return 1;
     }
 
-    DecodeCall c(cx, stream, d_dst, h, std::move(pipe), raw_bytes / (uint64_t)elem, d_src + h.size);
+    DecodeCall c(cx, stream, d_dst, h, Pipeline::from_string(h.pipename), raw_bytes / (uint64_t)want_elem, d_src + h.size);
     if (const int rc = decode_stages(c, c.pipe.stages.size())) return rc;
     if (c.cur != d_dst) SQY_HIP(hipMemcpyAsync(d_dst, c.cur, raw_bytes, hipMemcpyDeviceToDevice, stream));
-    if (c.lz4_flag) SQY_HIP(hipMemcpyAsync(cx.ws.pinned, c.lz4_flag, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    SQY_HIP(hipStreamSynchronize(stream));
-    if (g_prof_on.load()) prof_collect(cx.pending);
-    if (c.lz4_flag && *static_cast<const uint32_t*>(cx.ws.pinned)) {
-        std::fprintf(stderr, "[sqy::lz4] corrupt LZ4 block, or a frame that does not decode to its share of the volume\n");
-        return c.stage_error((size_t)c.lz4_flag_stage);
-    }
-    return 0;
+    return c.finish();
 }
 
 // Frames [z0, z0 + nz) of the blob (the index along shape[0]) into d_dst: the subset path (DecodeCall::frames_subset) where it applies and
@@ -2047,15 +1996,8 @@ int decode_frames_on_device(Context& cx, const void* d_src_v, uint64_t srclen, l
     DrainOnExit drain{stream, &cx.pending, cx.side};
     sqy::HeaderInfo h;
     if (fetch_header(d_src, srclen, stream, h)) return 1;
-    const int elem = h.elem_size();
-    if (elem != want_elem) { std::fprintf(stderr, "[sqeazy]\t blob holds %s voxels\n", h.type.c_str()); return 1; }
-    std::string why;
-    if (!Pipeline::supported(h.pipename, elem, &why)) {
-        std::fprintf(stderr, "[sqeazy]\t%s cannot be build with this version of sqeazy (%s)\n", h.pipename.c_str(), why.c_str());
-        return 1;
-    }
     uint64_t raw_bytes = 0;
-    if (!header_shape_ok(h, srclen, &raw_bytes)) return 1;
+    if (!admit_blob(h, srclen, want_elem, &raw_bytes)) return 1;
     const uint64_t Z = h.shape[0], fb = raw_bytes / Z;
     if (z0 < 0 || nz <= 0 || (uint64_t)z0 + (uint64_t)nz > Z) {
         std::fprintf(stderr, "[sqeazy]\t decode frames: range [%ld, %ld + %ld) outside the blob's %llu frames\n", z0, z0, nz, (unsigned long long)Z);
@@ -2065,19 +2007,10 @@ int decode_frames_on_device(Context& cx, const void* d_src_v, uint64_t srclen, l
     if (range_bytes > dst_capacity) { std::fprintf(stderr, "[sqeazy]\t decode frames: buffer too small\n"); return 1; }
 
     if (g_opt.decode_frames_subset.load()) {
-        DecodeCall c(cx, stream, d_dst, h, Pipeline::from_string(h.pipename), raw_bytes / (uint64_t)elem, d_src + h.size);
+        DecodeCall c(cx, stream, d_dst, h, Pipeline::from_string(h.pipename), raw_bytes / (uint64_t)want_elem, d_src + h.size);
         bool taken = false;
         if (const int rc = c.frames_subset((uint64_t)z0, (uint64_t)nz, fb, &taken)) return rc;
-        if (taken) {
-            if (c.lz4_flag) SQY_HIP(hipMemcpyAsync(cx.ws.pinned, c.lz4_flag, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-            SQY_HIP(hipStreamSynchronize(stream));
-            if (g_prof_on.load()) prof_collect(cx.pending);
-            if (c.lz4_flag && *static_cast<const uint32_t*>(cx.ws.pinned)) {
-                std::fprintf(stderr, "[sqy::lz4] corrupt LZ4 block, or a frame that does not decode to its share of the volume\n");
-                return c.stage_error((size_t)c.lz4_flag_stage);
-            }
-            return 0;
-        }
+        if (taken) return c.finish();
     }
     // every other blob: the whole volume, then the range
     if (cx.ws.range_full.ensure(std::max<uint64_t>(raw_bytes, 16))) return 1;
@@ -2089,14 +2022,34 @@ int decode_frames_on_device(Context& cx, const void* d_src_v, uint64_t srclen, l
     return 0;
 }
 
-// host-pointer frame-range decode: the blob staged as in decode_from_host, only the range comes back
+// A device-memory decode on host pointers: src_bytes of src staged in the leased context's io_src, call(context, d_src, d_dst, stream), then
+// dst_bytes of its io_dst back to dst.  The callers have checked the (untrusted) headers: nothing is allocated before that.
+template <class F>
+int decode_staged(const char* src, uint64_t src_bytes, char* dst, uint64_t dst_bytes, F&& call)
+{
+    if (!device_present()) { std::fprintf(stderr, "[sqeazy]\t no MI355X (HIP device) visible: sqeazy_amd has no CPU path\n"); return 1; }
+    ContextLease lease;
+    if (!lease.ctx) { std::fprintf(stderr, "[sqeazy]\t no usable HIP device\n"); return 1; }
+    Workspace* ws = &lease.ctx->ws;
+    hipStream_t stream = lease.ctx->own_stream();
+    if (!stream) { std::fprintf(stderr, "[sqeazy]\t no HIP stream\n"); return 1; }
+    if (ws->io_src.ensure(std::max<uint64_t>(src_bytes, 16)) || ws->io_dst.ensure(std::max<uint64_t>(dst_bytes, 16))) return 1;
+    int dev_id = 0;
+    SQY_HIP(hipGetDevice(&dev_id));
+    if (!lease.ctx->stager.copy(ws->io_src.p, const_cast<char*>(src), (size_t)src_bytes, true, dev_id)) { std::fprintf(stderr, "[sqeazy]\t host to device transfer failed\n"); return 1; }
+    if (const int rc = call(*lease.ctx, ws->io_src.p, ws->io_dst.p, stream)) return rc;
+    if (!lease.ctx->stager.copy(ws->io_dst.p, dst, dst_bytes, false, dev_id)) { std::fprintf(stderr, "[sqeazy]\t device to host transfer failed\n"); return 1; }
+    return 0;
+}
+
+// host-pointer frame-range decode: only the range comes back
 int decode_frames_from_host(const char* src, long srclength, long z0, long nz, char* dst, long dst_capacity, int elem_size)
 {
     if (!src || !dst || srclength <= 0) return 1;
     const sqy::HeaderInfo h = sqy::header_unpack(src, src + srclength);
     if (!h.valid) { std::fprintf(stderr, "[sqeazy]\t unable to find a sqy header in the blob\n"); return 1; }
     uint64_t raw = 0;
-    if (!header_shape_ok(h, (uint64_t)srclength, &raw)) return 1;           // untrusted input: before anything is allocated or uploaded
+    if (!header_shape_ok(h, (uint64_t)srclength, &raw)) return 1;
     if (h.elem_size() != elem_size) { std::fprintf(stderr, "[sqeazy]\t blob holds %s voxels\n", h.type.c_str()); return 1; }
     const uint64_t Z = h.shape[0], fb = raw / Z;
     if (z0 < 0 || nz <= 0 || (uint64_t)z0 + (uint64_t)nz > Z || (uint64_t)nz * fb > (uint64_t)std::max(dst_capacity, 0l)) {
@@ -2105,20 +2058,9 @@ int decode_frames_from_host(const char* src, long srclength, long z0, long nz, c
         return 1;
     }
     const uint64_t range_bytes = (uint64_t)nz * fb;
-    if (!device_present()) { std::fprintf(stderr, "[sqeazy]\t no MI355X (HIP device) visible: sqeazy_amd has no CPU path\n"); return 1; }
-    ContextLease lease;
-    if (!lease.ctx) { std::fprintf(stderr, "[sqeazy]\t no usable HIP device\n"); return 1; }
-    Workspace* ws = &lease.ctx->ws;
-    hipStream_t stream = lease.ctx->own_stream();
-    if (!stream) { std::fprintf(stderr, "[sqeazy]\t no HIP stream\n"); return 1; }
-    if (ws->io_src.ensure(std::max<uint64_t>((uint64_t)srclength, 16)) || ws->io_dst.ensure(std::max<uint64_t>(range_bytes, 16))) return 1;
-    int dev_id = 0;
-    SQY_HIP(hipGetDevice(&dev_id));
-    if (!lease.ctx->stager.copy(ws->io_src.p, const_cast<char*>(src), (size_t)srclength, true, dev_id)) { std::fprintf(stderr, "[sqeazy]\t host to device transfer failed\n"); return 1; }
-    const int rc = decode_frames_on_device(*lease.ctx, ws->io_src.p, (uint64_t)srclength, z0, nz, ws->io_dst.p, range_bytes, elem_size, stream);
-    if (rc) return rc;
-    if (!lease.ctx->stager.copy(ws->io_dst.p, dst, range_bytes, false, dev_id)) { std::fprintf(stderr, "[sqeazy]\t device to host transfer failed\n"); return 1; }
-    return 0;
+    return decode_staged(src, (uint64_t)srclength, dst, range_bytes, [&](Context& cx, void* d_src, void* d_dst, hipStream_t stream) {
+        return decode_frames_on_device(cx, d_src, (uint64_t)srclength, z0, nz, d_dst, range_bytes, elem_size, stream);
+    });
 }
 
 int decode_from_host(const char* src, long srclength, char* dst, int elem_size)
@@ -2126,23 +2068,13 @@ int decode_from_host(const char* src, long srclength, char* dst, int elem_size)
     if (!src || !dst || srclength <= 0) return 1;
     const sqy::HeaderInfo h = sqy::header_unpack(src, src + srclength);
     if (!h.valid) { std::fprintf(stderr, "[sqeazy]\t unable to find a sqy header in the blob\n"); return 1; }
-    if (!device_present()) { std::fprintf(stderr, "[sqeazy]\t no MI355X (HIP device) visible: sqeazy_amd has no CPU path\n"); return 1; }
-    ContextLease lease;
-    if (!lease.ctx) { std::fprintf(stderr, "[sqeazy]\t no usable HIP device\n"); return 1; }
-    Workspace* ws = &lease.ctx->ws;
-    hipStream_t stream = lease.ctx->own_stream();
-    if (!stream) { std::fprintf(stderr, "[sqeazy]\t no HIP stream\n"); return 1; }
     uint64_t raw = 0;
-    if (!header_shape_ok(h, (uint64_t)srclength, &raw)) return 1;          // untrusted input: before anything is allocated or uploaded
-    if (ws->io_src.ensure(std::max<uint64_t>((uint64_t)srclength, 16)) || ws->io_dst.ensure(std::max<uint64_t>(raw, 16))) return 1;
-    int dev_id = 0;
-    SQY_HIP(hipGetDevice(&dev_id));
-    if (!lease.ctx->stager.copy(ws->io_src.p, const_cast<char*>(src), (size_t)srclength, true, dev_id)) { std::fprintf(stderr, "[sqeazy]\t host to device transfer failed\n"); return 1; }
-    const int rc = decode_on_device(*lease.ctx, ws->io_src.p, (uint64_t)srclength, ws->io_dst.p, raw, elem_size, stream);
-    if (rc) return rc;
-    SQY_HIP(hipStreamSynchronize(stream));
-    if (!lease.ctx->stager.copy(ws->io_dst.p, dst, raw, false, dev_id)) { std::fprintf(stderr, "[sqeazy]\t device to host transfer failed\n"); return 1; }
-    return 0;
+    if (!header_shape_ok(h, (uint64_t)srclength, &raw)) return 1;
+    return decode_staged(src, (uint64_t)srclength, dst, raw, [&](Context& cx, void* d_src, void* d_dst, hipStream_t stream) -> int {
+        if (const int rc = decode_on_device(cx, d_src, (uint64_t)srclength, d_dst, raw, elem_size, stream)) return rc;
+        SQY_HIP(hipStreamSynchronize(stream));
+        return 0;
+    });
 }
 
 // ---- z-slab blob sets (SQYAMD_Decode_Slabs_*) ----------------------------------------------------------------------------------
@@ -2153,7 +2085,7 @@ int decode_from_host(const char* src, long srclength, char* dst, int elem_size)
 constexpr uint64_t kSlabsGroupBytes = 4ull << 30;       // LZ4 output of one group (inflight <= 0)
 constexpr uint64_t kSlabsHeadPrefix = 1ull << 16;       // bytes of every blob fetched for its header at first
 
-struct SlabBlob {
+struct SlabBlob : sqy::Lz4DecodeGeometry {              // (of the LZ4 stage's input, on the joint path)
     const uint8_t* src = nullptr;
     uint64_t len = 0, src_off = 0;
     sqy::HeaderInfo h;
@@ -2161,7 +2093,7 @@ struct SlabBlob {
     // the joint path: the LZ4 stage's input to the decoder (total bytes, chunks), where its output goes
     std::unique_ptr<DecodeCall> call;
     size_t li = 0;
-    uint64_t total = 0, chunk = 0, nchunks = 0, block_bytes = 0, max_blocks = 0;
+    uint64_t total = 0;
     uint64_t out_base = 0, map_off = 0, fs_bytes = 0;
     bool remap = false;
     int rc = 0;
@@ -2237,15 +2169,12 @@ int decode_slab_group(Context& cx, const uint8_t* d_src, std::vector<SlabBlob>& 
         SlabBlob& s = blobs[b];
         DecodeCall& c = *s.call;
         s.remap = false;
-        if (c.preceded_by(s.li, StageKind::frame_shuffle) && s.total % s.chunk == 0 && c.in_bytes(s.li - 1) == s.total && s.h.shape.size() == 3) {
-            uint64_t Z = 0, fb = 0;
-            bool permutation = true;
-            if (c.frame_shuffle_map(s.li - 1, Z, fb, permutation) == 0 && fb && fb % s.chunk == 0 && Z * fb == s.total) {
-                s.remap = true;
-                s.fs_bytes = fb;
-                s.map_off = maps.size();
-                maps.insert(maps.end(), c.fs_map.begin(), c.fs_map.begin() + Z * 8);
-            }
+        uint64_t Z = 0, fb = 0;
+        bool permutation = true;
+        if (c.shuffle_fold(s.li, s.total, s, s.nchunks, false, Z, fb, permutation, &s.remap) == 0 && s.remap) {
+            s.fs_bytes = fb;
+            s.map_off = maps.size();
+            maps.insert(maps.end(), c.fs_map.begin(), c.fs_map.begin() + Z * 8);
         }
         const size_t first_after = s.remap ? s.li - 1 : s.li;           // the stage whose inverse the LZ4 decode completes
         if (first_after > c.lead || ((reinterpret_cast<uintptr_t>(d_dst) + s.dst_off) & 15) != 0) direct = false;
@@ -2317,10 +2246,9 @@ int decode_slab_group(Context& cx, const uint8_t* d_src, std::vector<SlabBlob>& 
         if (c.cur != c.d_dst) SQY_HIP(hipMemcpyAsync(c.d_dst, c.cur, s.raw, hipMemcpyDeviceToDevice, stream));
     }
     // 6. the decoder's verdict, one read-back for the group
-    SQY_HIP(hipMemcpyAsync(cx.ws.pinned, flag, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    SQY_HIP(hipStreamSynchronize(stream));
-    if (g_prof_on.load()) prof_collect(cx.pending);
-    if (*static_cast<const uint32_t*>(cx.ws.pinned)) {
+    bool raised = false;
+    if (const int rc = lz4_verdict(cx, flag, stream, &raised)) return rc;
+    if (raised) {
         // a damaged frame somewhere in the group: every blob of it again on its own, which gives each one its exact code
         for (size_t b : mem) { blobs[b].rc = 0; single.push_back(b); }
     }
@@ -2355,13 +2283,7 @@ int decode_slabs_on_device(Context& cx, const void* d_src_v, const long* offsets
         b.h = sqy::header_unpack(hp + (uint64_t)i * kSlabsHeadPrefix, hp + (uint64_t)i * kSlabsHeadPrefix + take);
         if (!b.h.valid && take < b.len && fetch_header(b.src, b.len, stream, b.h)) return 1;
         if (!b.h.valid) { std::fprintf(stderr, "[sqeazy]\t decode slabs: no sqy header in blob %d\n", i); return 1; }
-        if (b.h.elem_size() != want_elem) { std::fprintf(stderr, "[sqeazy]\t decode slabs: blob %d holds %s voxels\n", i, b.h.type.c_str()); return 1; }
-        std::string why;
-        if (!Pipeline::supported(b.h.pipename, want_elem, &why)) {
-            std::fprintf(stderr, "[sqeazy]\t%s cannot be build with this version of sqeazy (%s)\n", b.h.pipename.c_str(), why.c_str());
-            return 1;
-        }
-        if (!header_shape_ok(b.h, b.len, &b.raw)) return 1;
+        if (!admit_blob(b.h, b.len, want_elem, &b.raw, ("decode slabs: blob " + std::to_string(i)).c_str())) return 1;
         const sqy::HeaderInfo& h0 = blobs[0].h;
         if (b.h.shape.size() != h0.shape.size() || !std::equal(b.h.shape.begin() + 1, b.h.shape.end(), h0.shape.begin() + 1)) {
             std::fprintf(stderr, "[sqeazy]\t decode slabs: blob %d's shape does not continue blob 0's\n", i);
@@ -2384,13 +2306,9 @@ int decode_slabs_on_device(Context& cx, const void* d_src_v, const long* offsets
             const size_t ns = c.pipe.stages.size();
             ok = ns > 0 && c.pipe.stages[ns - 1].kind == StageKind::lz4;
             if (ok) {
-                const Stage& st = c.pipe.stages[ns - 1];
                 b.li = ns - 1;
                 b.total = c.in_bytes(b.li);
-                b.chunk = b.total ? st.lz4.bytes_per_chunk(b.total) : 1;
-                b.block_bytes = st.lz4.block_bytes();
-                b.nchunks = b.total ? (b.total + b.chunk - 1) / b.chunk : 0;
-                b.max_blocks = std::max<uint64_t>(b.nchunks * ((b.chunk + b.block_bytes - 1) / b.block_bytes), b.total / b.block_bytes + 1) + 16;
+                static_cast<sqy::Lz4DecodeGeometry&>(b) = sqy::lz4_decode_geometry(c.pipe.stages[b.li].lz4, b.total);
                 ok = b.nchunks > 1 && b.chunk <= b.block_bytes;
             }
         }
@@ -2418,7 +2336,7 @@ int decode_slabs_on_device(Context& cx, const void* d_src_v, const long* offsets
     return 0;
 }
 
-// host-pointer slab-set decode: the span of the blobs staged as in decode_from_host, the volume comes back
+// host-pointer slab-set decode: the span of the blobs goes to the device, the volume comes back
 int decode_slabs_from_host(const char* src, const long* offsets, const long* lengths, int nslabs, char* dst, long dst_capacity, long* frames,
                            int elem_size)
 {
@@ -2434,20 +2352,9 @@ int decode_slabs_from_host(const char* src, const long* offsets, const long* len
         span = std::max<uint64_t>(span, (uint64_t)offsets[i] + (uint64_t)lengths[i]);
     }
     if (volume > (uint64_t)std::max(dst_capacity, 0l)) { std::fprintf(stderr, "[sqeazy]\t decode slabs: %llu bytes do not fit the buffer\n", (unsigned long long)volume); return 1; }
-    if (!device_present()) { std::fprintf(stderr, "[sqeazy]\t no MI355X (HIP device) visible: sqeazy_amd has no CPU path\n"); return 1; }
-    ContextLease lease;
-    if (!lease.ctx) { std::fprintf(stderr, "[sqeazy]\t no usable HIP device\n"); return 1; }
-    Workspace* ws = &lease.ctx->ws;
-    hipStream_t stream = lease.ctx->own_stream();
-    if (!stream) { std::fprintf(stderr, "[sqeazy]\t no HIP stream\n"); return 1; }
-    if (ws->io_src.ensure(std::max<uint64_t>(span, 16)) || ws->io_dst.ensure(std::max<uint64_t>(volume, 16))) return 1;
-    int dev_id = 0;
-    SQY_HIP(hipGetDevice(&dev_id));
-    if (!lease.ctx->stager.copy(ws->io_src.p, const_cast<char*>(src), (size_t)span, true, dev_id)) { std::fprintf(stderr, "[sqeazy]\t host to device transfer failed\n"); return 1; }
-    const int rc = decode_slabs_on_device(*lease.ctx, ws->io_src.p, offsets, lengths, nslabs, ws->io_dst.p, volume, frames, 0, elem_size, stream);
-    if (rc) return rc;
-    if (!lease.ctx->stager.copy(ws->io_dst.p, dst, volume, false, dev_id)) { std::fprintf(stderr, "[sqeazy]\t device to host transfer failed\n"); return 1; }
-    return 0;
+    return decode_staged(src, span, dst, volume, [&](Context& cx, void* d_src, void* d_dst, hipStream_t stream) {
+        return decode_slabs_on_device(cx, d_src, offsets, lengths, nslabs, d_dst, volume, frames, 0, elem_size, stream);
+    });
 }
 
 // The body of the device-memory encode entry points: the blob at d_dst (_Device), or where *dstoffset says (at: _DeviceAt), with the

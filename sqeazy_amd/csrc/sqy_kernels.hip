@@ -6751,6 +6751,14 @@ hipError_t launch_lz4_frame_rank_batch(const Lz4RankJob* jobs, uint32_t njobs, v
 
 constexpr uint32_t SQY_RING8_MIN = 2560;
 // the decode kernels of launch_lz4_frames_decode and their choice by the frames' counts; OFFS: launch_lz4_frames_joint_decode's table mode
+// more compressed blocks than the 64 KiB-ring kernel keeps resident (2 per CU) plus half a round: the small ring's four-fold
+// occupancy wins; below that the frames are few and long, and every match served from LDS wins
+// (round 4) more compressed frames than even the 16 KiB-ring kernel keeps resident (8 per CU) plus a quarter: the 8 KiB ring's 13 waves
+// per CU win although more matches reach behind the ring -- the C3 slab's 3584 frames 3.37 -> 2.65 ms (a 4 KiB ring: no better)
+// (round 5) frames of one block, few enough for every one of them to be resident: two wavefronts per frame, one finds out what the
+// sequences are, the other moves the bytes (lz4_frames_decode2_kernel)
+// (not beyond that: the C3 slab's 3584 frames through two waves each, 8 KiB ring, take 7.1 ms against 2.6 -- that range is bound by the
+// instructions issued, and two waves issue more of them)
 template <bool OFFS>
 static hipError_t lz4_frames_decode_kernels(const uint8_t* in, const void* blk, const uint32_t* frame_first, uint32_t nframes, uint8_t* out,
                                             uint64_t out_bytes, uint64_t frame_stride, uint64_t block_bytes, uint32_t ncompressed,
@@ -6784,47 +6792,22 @@ static hipError_t lz4_frames_decode_kernels(const uint8_t* in, const void* blk, 
     return hipGetLastError();
 }
 
-hipError_t launch_lz4_frames_decode(const uint8_t* in, const void* blk, const uint32_t* frame_first, uint32_t nframes, uint8_t* out,
-                                    uint64_t out_bytes, uint64_t frame_stride, uint64_t block_bytes, uint32_t ncompressed,
-                                    uint32_t* errflag, hipStream_t stream, hipStream_t copy_stream, hipEvent_t fork, hipEvent_t join,
-                                    const uint64_t* remap, uint64_t remap_bytes, bool two_waves)
-{
-    if (nframes == 0) return hipSuccess;
-    // (remap: frame f goes to remap[f * stride / remap_bytes] * remap_bytes + the rest -- whole chunks inside whole shuffle frames only)
-    if (remap && (remap_bytes == 0 || frame_stride == 0 || remap_bytes % frame_stride != 0 || out_bytes % remap_bytes != 0 ||
-                  (uint64_t)nframes * frame_stride != out_bytes)) return hipErrorInvalidValue;
-    // the stored frames are copied (HBM-bound) while the compressed ones are decoded (latency-bound, HBM idle): disjoint
-    // outputs, both only read the stream -- on a second stream when the caller has one to spare.  The decode kernel is
-    // launched first: its few long-running waves should get their slots before the copy's many short workgroups fill the CUs.
-    const bool side = copy_stream && copy_stream != stream && fork && join;
-    hipStream_t cs = side ? copy_stream : stream;
-    if (side) {
-        hipError_t e = hipEventRecord(fork, stream);
-        if (e != hipSuccess) return e;
-        e = hipStreamWaitEvent(copy_stream, fork, 0);
-        if (e != hipSuccess) return e;
-    }
-    // more compressed blocks than the 64 KiB-ring kernel keeps resident (2 per CU) plus half a round: the small ring's four-fold
-    // occupancy wins; below that the frames are few and long, and every match served from LDS wins
-    // (round 4) more compressed frames than even the 16 KiB-ring kernel keeps resident (8 per CU) plus a quarter: the 8 KiB ring's 13 waves
-    // per CU win although more matches reach behind the ring -- the C3 slab's 3584 frames 3.37 -> 2.65 ms (a 4 KiB ring: no better)
-    // (round 5) frames of one block, few enough for every one of them to be resident: two wavefronts per frame, one finds out what the
-    // sequences are, the other moves the bytes (lz4_frames_decode2_kernel)
-    // (not beyond that: the C3 slab's 3584 frames through two waves each, 8 KiB ring, take 7.1 ms against 2.6 -- that range is bound by the
-    // instructions issued, and two waves issue more of them)
+// The stored frames are copied (HBM-bound) while the compressed ones are decoded (latency-bound, HBM idle): disjoint outputs, both only
+// read the stream -- on a second stream (cs) when the caller has one to spare, between fork() and join().  The decode kernel is launched
+// first: its few long-running waves should get their slots before the copy's many short workgroups fill the CUs.
+struct SideCopy {
+    hipStream_t stream, cs;
+    hipEvent_t ev_fork, ev_join;
+    SideCopy(hipStream_t s, hipStream_t copy_stream, hipEvent_t f, hipEvent_t j)
+        : stream(s), cs(copy_stream && copy_stream != s && f && j ? copy_stream : s), ev_fork(f), ev_join(j) {}
+    hipError_t fork() const { return cs == stream ? hipSuccess : order(ev_fork, stream, cs); }
+    hipError_t join() const { return cs == stream ? hipSuccess : order(ev_join, cs, stream); }
+    static hipError_t order(hipEvent_t ev, hipStream_t first, hipStream_t then)
     {
-        const hipError_t e = lz4_frames_decode_kernels<false>(in, blk, frame_first, nframes, out, out_bytes, frame_stride, block_bytes, ncompressed, errflag,
-                                                              stream, cs, remap, remap_bytes, two_waves);
-        if (e != hipSuccess) return e;
+        const hipError_t e = hipEventRecord(ev, first);
+        return e != hipSuccess ? e : hipStreamWaitEvent(then, ev, 0);
     }
-    if (side) {
-        hipError_t e = hipEventRecord(join, copy_stream);
-        if (e != hipSuccess) return e;
-        e = hipStreamWaitEvent(stream, join, 0);
-        if (e != hipSuccess) return e;
-    }
-    return hipGetLastError();
-}
+};
 
 // ---- several blobs' LZ4 streams in one launch (SQYAMD_Decode_Slabs_*) ----------------------------------------------------------------------
 // The joint block index: part p's frames (its own index, blk with offsets into its stream) get the joint numbers jbase + f, their block
@@ -6861,24 +6844,12 @@ hipError_t launch_lz4_frames_joint_decode(const uint8_t* in, const Lz4JointPart*
     if (nframes == 0 || nparts == 0) return hipSuccess;
     if (nparts > 65535u || block_bytes == 0) return hipErrorInvalidValue;
     hipLaunchKernelGGL(lz4_joint_index_kernel, dim3((max_part_frames + 255u) / 256u, nparts), dim3(256), 0, stream, d_parts, (uint4*)jblk, jff, jout);
-    const bool side = copy_stream && copy_stream != stream && fork && join;
-    hipStream_t cs = side ? copy_stream : stream;
-    if (side) {
-        hipError_t e = hipEventRecord(fork, stream);
-        if (e != hipSuccess) return e;
-        e = hipStreamWaitEvent(copy_stream, fork, 0);
-        if (e != hipSuccess) return e;
-    }
+    SideCopy sc(stream, copy_stream, fork, join);
+    if (const hipError_t e = sc.fork()) return e;
     // (frame_stride is not read in the table mode; the chunk-sized block bound stays block_bytes)
-    hipError_t e = lz4_frames_decode_kernels<true>(in, jblk, jff, nframes, out, out_bytes, block_bytes, block_bytes, ncompressed, errflag, stream, cs,
-                                                   jout, 1, two_waves);
-    if (e != hipSuccess) return e;
-    if (side) {
-        e = hipEventRecord(join, copy_stream);
-        if (e != hipSuccess) return e;
-        e = hipStreamWaitEvent(stream, join, 0);
-        if (e != hipSuccess) return e;
-    }
+    if (const hipError_t e = lz4_frames_decode_kernels<true>(in, jblk, jff, nframes, out, out_bytes, block_bytes, block_bytes, ncompressed, errflag, stream,
+                                                             sc.cs, jout, 1, two_waves)) return e;
+    if (const hipError_t e = sc.join()) return e;
     return hipGetLastError();
 }
 
@@ -7012,6 +6983,25 @@ void lz4_subset_index_kernel(const uint4* __restrict__ blk, const uint32_t* __re
     if (t == 1023u) sff[nsel] = scan[1023];
 }
 
+// (defined here, not next to the joint launch: the decode kernels' implicit instantiations are emitted in the order their launch code
+// is first seen, and this order leaves every kernel of the code object where it was)
+hipError_t launch_lz4_frames_decode(const uint8_t* in, const void* blk, const uint32_t* frame_first, uint32_t nframes, uint8_t* out,
+                                    uint64_t out_bytes, uint64_t frame_stride, uint64_t block_bytes, uint32_t ncompressed,
+                                    uint32_t* errflag, hipStream_t stream, hipStream_t copy_stream, hipEvent_t fork, hipEvent_t join,
+                                    const uint64_t* remap, uint64_t remap_bytes, bool two_waves)
+{
+    if (nframes == 0) return hipSuccess;
+    // (remap: frame f goes to remap[f * stride / remap_bytes] * remap_bytes + the rest -- whole chunks inside whole shuffle frames only)
+    if (remap && (remap_bytes == 0 || frame_stride == 0 || remap_bytes % frame_stride != 0 || out_bytes % remap_bytes != 0 ||
+                  (uint64_t)nframes * frame_stride != out_bytes)) return hipErrorInvalidValue;
+    SideCopy sc(stream, copy_stream, fork, join);
+    if (const hipError_t e = sc.fork()) return e;
+    if (const hipError_t e = lz4_frames_decode_kernels<false>(in, blk, frame_first, nframes, out, out_bytes, frame_stride, block_bytes, ncompressed, errflag,
+                                                              stream, sc.cs, remap, remap_bytes, two_waves)) return e;
+    if (const hipError_t e = sc.join()) return e;
+    return hipGetLastError();
+}
+
 hipError_t launch_lz4_frames_subset_decode(const uint8_t* in, const void* blk, const uint32_t* frame_first, uint32_t nframes,
                                            const uint32_t* ids, uint32_t nsel, uint32_t max_per_frame, void* sblk, uint32_t* sff,
                                            uint8_t* out, uint64_t out_bytes, uint64_t frame_stride, uint64_t block_bytes, uint32_t ncompressed,
@@ -7023,28 +7013,8 @@ hipError_t launch_lz4_frames_subset_decode(const uint8_t* in, const void* blk, c
     hipLaunchKernelGGL(lz4_subset_index_kernel, dim3(1), dim3(1024), 0, stream, (const uint4*)blk, frame_first, nframes, ids, nsel, max_per_frame,
                        (uint4*)sblk, sff, errflag);
     // the kernel choice of launch_lz4_frames_decode, on the subset's counts
-    const uint32_t nc = ncompressed < nsel ? ncompressed : nsel;
-    if (two_waves && !(nc > SQY_RING8_MIN && nsel > SQY_RING8_MIN)) {
-        if (nc > 768u && nsel > 768u)
-            hipLaunchKernelGGL(lz4_frames_decode2_kernel<16384>, dim3(nsel), dim3(128), 0, stream, in, (const uint4*)sblk, sff, out,
-                               out_bytes, frame_stride, block_bytes, errflag, remap, remap_bytes);
-        else
-            hipLaunchKernelGGL(lz4_frames_decode2_kernel<65536>, dim3(nsel), dim3(128), 0, stream, in, (const uint4*)sblk, sff, out,
-                               out_bytes, frame_stride, block_bytes, errflag, remap, remap_bytes);
-    } else if (nc > SQY_RING8_MIN && nsel > SQY_RING8_MIN)
-        hipLaunchKernelGGL(lz4_frames_decode_kernel<8192>, dim3(nsel), dim3(64), 0, stream, in, (const uint4*)sblk, sff, out,
-                           out_bytes, frame_stride, block_bytes, errflag, remap, remap_bytes);
-    else if (nc > 768u && nsel > 768u)
-        hipLaunchKernelGGL(lz4_frames_decode_kernel<16384>, dim3(nsel), dim3(64), 0, stream, in, (const uint4*)sblk, sff, out,
-                           out_bytes, frame_stride, block_bytes, errflag, remap, remap_bytes);
-    else
-        hipLaunchKernelGGL(lz4_frames_decode_kernel<65536>, dim3(nsel), dim3(64), 0, stream, in, (const uint4*)sblk, sff, out,
-                           out_bytes, frame_stride, block_bytes, errflag, remap, remap_bytes);
-    const uint32_t slices = (uint32_t)((block_bytes + DEC_COPY_SLICE - 1) / DEC_COPY_SLICE);
-    if (slices == 0 || (uint64_t)nsel * slices > 0x7fffffffull) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(lz4_stored_frames_copy_kernel<false>, dim3(nsel * slices), dim3(256), 0, stream, in, (const uint4*)sblk, sff,
-                       out, out_bytes, frame_stride, slices, remap, remap_bytes);
-    return hipGetLastError();
+    return lz4_frames_decode_kernels<false>(in, sblk, sff, nsel, out, out_bytes, frame_stride, block_bytes, ncompressed < nsel ? ncompressed : nsel, errflag,
+                                            stream, stream, remap, remap_bytes, two_waves);
 }
 
 // Inverse bitswap1 of plane words [w0, w1) only (bitswap1_decode_kernel's arithmetic): word i of the range of stored plane segment s is

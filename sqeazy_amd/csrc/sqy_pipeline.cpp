@@ -271,6 +271,124 @@ Lz4Plan lz4_plan_blocks(uint64_t total, uint64_t step, uint64_t block_bytes, boo
     return plan;
 }
 
+// ---- decode planning ----
+Lz4DecodeGeometry lz4_decode_geometry(const Lz4Params& p, uint64_t total)
+{
+    Lz4DecodeGeometry g;
+    g.chunk = total ? p.bytes_per_chunk(total) : 1;
+    g.block_bytes = p.block_bytes();
+    g.nchunks = total ? (total + g.chunk - 1) / g.chunk : 0;
+    g.max_blocks = std::max<uint64_t>(g.nchunks * ((g.chunk + g.block_bytes - 1) / g.block_bytes), total / g.block_bytes + 1) + 16;
+    return g;
+}
+
+bool lz4_chunks_whole(uint64_t nframes, uint64_t nchunks, uint64_t total, uint64_t chunk)
+{
+    return nframes == nchunks && nframes > 1 && chunk && total % chunk == 0;
+}
+
+bool lz4_folds_into_shuffle(uint64_t nframes, uint64_t nchunks, uint64_t total, uint64_t chunk, uint64_t Z, uint64_t fb)
+{
+    return lz4_chunks_whole(nframes, nchunks, total, chunk) && fb && fb % chunk == 0 && Z * fb == total;
+}
+
+bool frame_shuffle_decode_map(std::vector<unsigned char>* map, uint64_t Z, std::vector<uint64_t>* unnamed, bool* permutation)
+{
+    if (map->size() % 8 != 0 || map->size() / 8 != Z) return false;
+    auto slot = [&](uint64_t i) { uint64_t v; std::memcpy(&v, map->data() + 8 * i, 8); return v; };
+    std::vector<uint64_t> last(Z, ~0ull);            // the last slot named for a place
+    *permutation = true;
+    for (uint64_t i = 0; i < Z; ++i) {
+        const uint64_t v = slot(i);
+        if (v >= Z) return false;
+        if (last[v] != ~0ull) *permutation = false;
+        last[v] = i;
+    }
+    unnamed->clear();
+    if (*permutation) return true;
+    // A map that names a place twice (frames of equal metric on the encoder's side: same bytes -- or a crafted blob: not): the last
+    // slot named for a place stays, whatever order the scatter's workgroups run in -- the earlier ones are struck.
+    for (uint64_t v = 0; v < Z; ++v) if (last[v] == ~0ull) unnamed->push_back(v);
+    for (uint64_t i = 0; i < Z; ++i)
+        if (last[slot(i)] != i) { const uint64_t none = ~0ull; std::memcpy(map->data() + 8 * i, &none, 8); }
+    return true;
+}
+
+FrameRangePlan frame_range_plan(RangeForm form, uint64_t n, int elem, uint64_t shape0, uint64_t z0, uint64_t nz, uint64_t chunk, uint64_t total,
+                                uint32_t nframes, const std::vector<unsigned char>& struck_map, uint64_t place_bytes, uint64_t places)
+{
+    FrameRangePlan p;
+    const uint64_t e = (uint64_t)elem;
+    p.we = form == RangeForm::planes ? elem : 1;
+    const uint64_t we = (uint64_t)p.we;
+    // a range inside the volume, the stream the voxels in their order, one frame per chunk
+    if (shape0 == 0 || n == 0 || n % shape0 != 0 || nz == 0 || z0 >= shape0 || nz > shape0 - z0 || (elem != 1 && elem != 2) || chunk == 0 ||
+        total != n * (form == RangeForm::planes_lut ? 1 : e) || (uint64_t)nframes != (total + chunk - 1) / chunk)
+        return p;
+    const uint64_t vpf = n / shape0, fb = vpf * e;
+    p.v0 = z0 * vpf;
+    p.v1 = (z0 + nz) * vpf;
+    if (form == RangeForm::shuffle) {
+        if (!lz4_folds_into_shuffle(nframes, nframes, total, chunk, places, place_bytes) || struck_map.size() != places * 8) return p;
+        p.pa = z0 * fb / place_bytes;
+        p.pb = ((z0 + nz) * fb + place_bytes - 1) / place_bytes;
+        const uint64_t cpf = place_bytes / chunk, np = p.pb - p.pa;
+        std::vector<char> named(np, 0);
+        // (the struck map: the last slot named for a place wins, as in the full decode)
+        for (uint64_t i = 0; i < places; ++i) {
+            uint64_t v;
+            std::memcpy(&v, struck_map.data() + 8 * i, 8);
+            if (v == ~0ull || v < p.pa || v >= p.pb) continue;
+            p.remap.push_back(v - p.pa);
+            named[v - p.pa] = 1;
+            for (uint64_t c = 0; c < cpf; ++c) p.ids.push_back((uint32_t)(i * cpf + c));
+        }
+        for (uint64_t k = 0; k < np;) {
+            if (named[k]) { ++k; continue; }
+            uint64_t k1 = k;
+            while (k1 < np && !named[k1]) ++k1;
+            p.zero_runs.push_back({k, k1});
+            k = k1;
+        }
+        p.out_bytes = np * place_bytes;
+        p.range_at = z0 * fb - p.pa * place_bytes;
+        p.direct = p.range_at == 0 && p.pb * place_bytes == (z0 + nz) * fb;
+        p.ok = true;
+        return p;
+    }
+    // byte spans of the stream in front of lz4 that the range needs
+    std::vector<std::pair<uint64_t, uint64_t>> spans;
+    if (form == RangeForm::plain)
+        spans.push_back({p.v0 * e, p.v1 * e});
+    else {
+        // W = 8 * we plane segments of seg words (we bytes, W voxels each), then the n % W voxels behind them verbatim
+        const uint64_t W = 8 * we, seg = n / W;
+        p.L = seg * W;
+        p.w0 = std::min(p.v0 / W, seg);
+        p.w1 = std::min((p.v1 + W - 1) / W, seg);
+        if (p.w0 < p.w1) for (uint64_t s = 0; s < W; ++s) spans.push_back({(s * seg + p.w0) * we, (s * seg + p.w1) * we});
+        if (p.v1 > p.L) spans.push_back({std::max(p.v0, p.L) * we, p.v1 * we});
+    }
+    std::vector<char> need(nframes, 0);
+    for (const auto& sp : spans) for (uint64_t f = sp.first / chunk; f <= (sp.second - 1) / chunk; ++f) need[f] = 1;
+    p.coff.assign(nframes, 0);
+    for (uint32_t f = 0; f < nframes; ++f) {
+        if (!need[f]) continue;
+        p.coff[f] = p.out_bytes;
+        p.ids.push_back(f);
+        p.out_bytes += std::min<uint64_t>(chunk, total - (uint64_t)f * chunk);
+    }
+    auto compact = [&](uint64_t b) { const uint64_t f = b / chunk; return p.coff[f] + (b - f * chunk); };
+    if (form == RangeForm::plain) p.range_at = compact(spans[0].first);
+    else {
+        // (the spans in their order: the plane segments' words, then the tail)
+        for (size_t s = 0; p.w0 < p.w1 && s < (size_t)(8 * we); ++s) p.plane[s] = compact(spans[s].first);
+        if (p.v1 > p.L) p.tail = compact(spans.back().first);
+    }
+    p.ok = true;
+    return p;
+}
+
 // ---- stages ----
 static StageKind kind_of(const std::string& n)
 {

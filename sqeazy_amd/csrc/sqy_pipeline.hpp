@@ -61,6 +61,44 @@ struct Lz4Plan {
 // serial = false: one frame per `step` bytes, each fed by a single update (encode_parallel -> encode_serial per chunk)
 Lz4Plan lz4_plan_blocks(uint64_t total, uint64_t step, uint64_t block_bytes, bool serial);
 
+// ---- decode planning: host arithmetic on untrusted input (a header's shape, LZ4 parameters and reorder_map, a caller's range) ----
+// What the decoder of one LZ4 stage indexes: `total` bytes in front of the stage in `nchunks` chunks of `chunk` (the last one may be
+// short), at most `max_blocks` LZ4 blocks of up to `block_bytes`
+struct Lz4DecodeGeometry { uint64_t chunk = 1, nchunks = 0, block_bytes = 0, max_blocks = 0; };
+Lz4DecodeGeometry lz4_decode_geometry(const Lz4Params& p, uint64_t total);
+// the chunked layout with every chunk full: one frame per chunk, more than one
+bool lz4_chunks_whole(uint64_t nframes, uint64_t nchunks, uint64_t total, uint64_t chunk);
+// .. and every chunk inside one of frame_shuffle's Z places of fb bytes: the LZ4 frames can be decoded straight to the shuffle's places
+bool lz4_folds_into_shuffle(uint64_t nframes, uint64_t nchunks, uint64_t total, uint64_t chunk, uint64_t Z, uint64_t fb);
+// frame_shuffle's inverse from the decoded reorder_map (Z 64-bit slots: slot i's frame goes to place map[i]).  *map becomes the device's
+// copy: every slot but the LAST one named for a place struck (~0) -- the reference's decode walks the slots in order, the last writer
+// stays (frame_shuffle_utils.hpp:337-344).  *unnamed: the places no slot names, ascending.  false: wrong length, or an entry >= Z
+bool frame_shuffle_decode_map(std::vector<unsigned char>* map, uint64_t Z, std::vector<uint64_t>* unnamed, bool* permutation);
+
+// Frames [z0, z0 + nz) of a volume of n voxels (elem bytes each, shape0 frames) out of the chunked LZ4 layout (nframes frames of `chunk`
+// bytes, `total` in all) in front of which the stream is
+//   plain: the voxels | planes: bitswap1's planes of them | planes_lut: bitswap1's planes of one quantised byte per voxel |
+//   shuffle: frame_shuffle's `places` places of place_bytes (struck_map: frame_shuffle_decode_map's; lz4_folds_into_shuffle holds)
+enum class RangeForm { plain, planes, planes_lut, shuffle };
+struct FrameRangePlan {
+    bool ok = false;                        // false: arguments that name no range of such a stream (nothing else is filled in)
+    std::vector<uint32_t> ids;              // the LZ4 frames to decode: ascending, unique
+    uint64_t out_bytes = 0;                 // what they decode to, back to back (shuffle: places [pa, pb))
+    uint64_t range_at = 0;                  // plain, shuffle: the range's first byte in there
+    std::vector<uint64_t> coff;             // plain, planes: offset of frame f in there (frames of ids only)
+    // planes: sqy::Bitswap1Range's values -- words [w0, w1) of plane segment s at plane[s], voxels [max(v0, L), v1) at tail; we bytes a word
+    uint64_t plane[16] = {}, tail = 0, v0 = 0, v1 = 0, w0 = 0, w1 = 0, L = 0;
+    int we = 1;
+    // shuffle: the place (relative to pa) of every slot decoded, in slot order; direct: the range starts and ends on place boundaries;
+    // zero_runs: the places [first, second) (relative to pa) no slot names
+    std::vector<uint64_t> remap;
+    uint64_t pa = 0, pb = 0;
+    bool direct = false;
+    std::vector<std::pair<uint64_t, uint64_t>> zero_runs;
+};
+FrameRangePlan frame_range_plan(RangeForm form, uint64_t n, int elem, uint64_t shape0, uint64_t z0, uint64_t nz, uint64_t chunk, uint64_t total,
+                                uint32_t nframes, const std::vector<unsigned char>& struck_map = {}, uint64_t place_bytes = 0, uint64_t places = 0);
+
 struct Stage {
     std::string name;
     StageKind kind = StageKind::unsupported;

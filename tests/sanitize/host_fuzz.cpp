@@ -1,11 +1,12 @@
 // Host side of libsqeazy_amd under AddressSanitizer + UndefinedBehaviorSanitizer (CPU only, no HIP): the pipeline grammar, the
 // configuration strings, the sqy header (pack / unpack of untrusted bytes), base64, the LZ4 block planner, the quantiser's host LUTs
-// and file readers, the frame / tile ordering -- everything sqy_pipeline.cpp holds -- driven with valid inputs, systematic
+// and file readers, the frame / tile ordering, the decode planners -- everything sqy_pipeline.cpp holds -- driven with valid inputs, systematic
 // truncations and seeded random mutations.  Built and run by tests/test_host_sanitizers.py:
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all host_fuzz.cpp ../../sqeazy_amd/csrc/sqy_pipeline.cpp
 // Exit code 0 and no sanitizer report = pass.  ("race detection / sanitizers".)
 #include "../../sqeazy_amd/csrc/sqy_pipeline.hpp"
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -251,6 +252,198 @@ static void orderings(std::mt19937& rng)
     CHECK(xxh32(nullptr, 0, 0) == 0x02CC5D05u);
 }
 
+// ---- the decode planners (host arithmetic on untrusted input: a header's LZ4 parameters, shape and reorder_map, a caller's range) ----
+static void lz4_geometry(std::mt19937&)
+{
+    for (const char* cfg : {"", "blocksize_kb=64", "accel=1,blocksize_kb=256,framestep_kb=256,n_chunks_of_input=0", "blocksize_kb=64,framestep_kb=64",
+                            "blocksize_kb=64,framestep_kb=256", "n_chunks_of_input=7", "n_chunks_of_input=3", "blocksize_kb=64,n_chunks_of_input=2",
+                            "framestep_kb=0,n_chunks_of_input=3", "framestep_kb=0", "blocksize_kb=4096,framestep_kb=1024"}) {
+        const Lz4Params p(cfg);
+        const uint64_t c = lz4_decode_geometry(p, 1ull << 30).chunk;
+        for (uint64_t total : {(uint64_t)0, (uint64_t)1, c - 1, c, c + 1, 3 * c, 3 * c + 5, (uint64_t)((3ull << 30) + 12345)}) {
+            const Lz4DecodeGeometry g = lz4_decode_geometry(p, total);
+            CHECK(g.chunk >= 1 && g.block_bytes == p.block_bytes());
+            if (total == 0) { CHECK(g.nchunks == 0 && g.max_blocks >= 1); continue; }
+            CHECK(g.nchunks * g.chunk >= total && total > (g.nchunks - 1) * g.chunk);
+            const Lz4Plan plan = lz4_plan_blocks(total, g.chunk, g.block_bytes, false);
+            if (plan.ok) CHECK(g.max_blocks >= plan.blocks.size());
+        }
+    }
+}
+
+static std::vector<unsigned char> map_bytes(const std::vector<uint64_t>& m)
+{
+    std::vector<unsigned char> b(m.size() * 8);
+    if (!m.empty()) std::memcpy(b.data(), m.data(), b.size());
+    return b;
+}
+
+static void shuffle_maps(std::mt19937& rng)
+{
+    for (int round = 0; round < 4000; ++round) {
+        const uint64_t Z = rng() % 40;
+        std::vector<uint64_t> m(Z);
+        for (uint64_t i = 0; i < Z; ++i) m[i] = i;
+        const unsigned kind = rng() % 4;
+        if (kind == 0) std::shuffle(m.begin(), m.end(), rng);                        // a permutation
+        else for (uint64_t i = 0; i < Z; ++i) if (rng() % 3 == 0) m[i] = rng() % Z;  // repeated places
+        bool bad = false;
+        if (kind == 2 && Z) { m[rng() % Z] = Z + rng() % 3 + (rng() % 2 ? 0 : ~0ull - Z - 3); bad = true; }    // an entry >= Z
+        std::vector<unsigned char> bytes = map_bytes(m);
+        if (kind == 3) { bytes.resize(rng() % (Z * 8 + 20)); bad = bytes.size() != Z * 8; }                    // wrong length
+        std::vector<uint64_t> unnamed = {99};
+        bool permutation = false;
+        const bool ok = frame_shuffle_decode_map(&bytes, Z, &unnamed, &permutation);
+        CHECK(ok == !bad);
+        if (!ok) continue;
+        // the model: walk the slots in order, the last writer of a place wins
+        std::vector<uint64_t> winner(Z, ~0ull);
+        for (uint64_t i = 0; i < Z; ++i) winner[m[i]] = i;
+        std::vector<uint64_t> want_unnamed;
+        for (uint64_t v = 0; v < Z; ++v) if (winner[v] == ~0ull) want_unnamed.push_back(v);
+        CHECK(permutation == want_unnamed.empty());
+        CHECK(unnamed == want_unnamed);
+        for (uint64_t i = 0; i < Z; ++i) {
+            uint64_t v; std::memcpy(&v, bytes.data() + 8 * i, 8);
+            CHECK(v == (winner[m[i]] == i ? m[i] : ~0ull));
+        }
+    }
+}
+
+// one frame-range plan against brute force over the range's voxels; `map`: the shuffle's reorder_map as the header has it
+static void check_range_plan(RangeForm form, uint64_t n, int elem, uint64_t shape0, uint64_t z0, uint64_t nz, uint64_t chunk, const std::vector<uint64_t>& map,
+                             uint64_t place_bytes)
+{
+    const uint64_t e = (uint64_t)elem, we = form == RangeForm::planes ? e : 1, total = n * (form == RangeForm::planes_lut ? 1 : e);
+    const uint32_t nframes = (uint32_t)((total + chunk - 1) / chunk);
+    std::vector<unsigned char> struck = map_bytes(map);
+    std::vector<uint64_t> unnamed;
+    bool permutation = true;
+    if (form == RangeForm::shuffle) CHECK(frame_shuffle_decode_map(&struck, map.size(), &unnamed, &permutation));
+    const FrameRangePlan p = frame_range_plan(form, n, elem, shape0, z0, nz, chunk, total, nframes, struck, place_bytes, map.size());
+    if (nz == 0 || z0 >= shape0 || nz > shape0 - z0) { CHECK(!p.ok); return; }       // (what the drivers refuse before planning)
+    CHECK(p.ok);
+    for (size_t i = 0; i < p.ids.size(); ++i) CHECK(p.ids[i] < nframes && (i == 0 || p.ids[i - 1] < p.ids[i]));
+    std::vector<char> sel(nframes, 0);
+    for (uint32_t f : p.ids) sel[f] = 1;
+    const uint64_t vpf = n / shape0, v0 = z0 * vpf, v1 = (z0 + nz) * vpf, fb = vpf * e;
+    if (form == RangeForm::shuffle) {
+        const uint64_t P = map.size(), np = p.pb - p.pa, cpf = place_bytes / chunk;
+        CHECK(p.pa * place_bytes <= z0 * fb && (z0 + nz) * fb <= p.pb * place_bytes && p.pb <= P && p.out_bytes == np * place_bytes);
+        CHECK(p.range_at + nz * fb <= p.out_bytes && p.direct == (np * place_bytes == nz * fb));
+        CHECK(p.ids.size() == p.remap.size() * cpf);
+        std::vector<int> cover(np, 0);
+        for (uint64_t v : p.remap) { CHECK(v < np); cover[v] += 1; }
+        for (const auto& run : p.zero_runs) { CHECK(run.first < run.second && run.second <= np); for (uint64_t k = run.first; k < run.second; ++k) cover[k] += 2; }
+        std::vector<uint64_t> winner(P, ~0ull);
+        for (uint64_t i = 0; i < P; ++i) winner[map[i]] = i;
+        // every byte of the range: in a place the last slot named for it fills -- that slot's frames are decoded, to that place -- or zeroed
+        for (uint64_t b = v0 * e; b < v1 * e; ++b) {
+            const uint64_t place = b / place_bytes, slot = winner[place];
+            CHECK(place >= p.pa && place < p.pb && cover[place - p.pa] == (slot == ~0ull ? 2 : 1));
+            if (slot == ~0ull) continue;
+            const uint64_t f = (slot * place_bytes + b % place_bytes) / chunk;
+            CHECK(sel[f]);
+            const size_t at = std::lower_bound(p.ids.begin(), p.ids.end(), (uint32_t)f) - p.ids.begin();
+            CHECK(p.remap[at / cpf] == place - p.pa);
+        }
+        for (uint64_t k = 0; k < np; ++k) CHECK(cover[k] == 1 || cover[k] == 2);
+        return;
+    }
+    // the selected frames back to back: where every byte of them came from
+    std::vector<uint64_t> from;
+    for (uint32_t f : p.ids) {
+        CHECK(p.coff[f] == from.size());
+        for (uint64_t b = (uint64_t)f * chunk; b < std::min<uint64_t>(total, ((uint64_t)f + 1) * chunk); ++b) from.push_back(b);
+    }
+    CHECK(p.out_bytes == from.size());
+    if (form == RangeForm::plain) {
+        CHECK(p.range_at + nz * fb <= p.out_bytes);
+        for (uint64_t b = v0 * e; b < v1 * e; ++b) { CHECK(sel[b / chunk]); CHECK(from[p.range_at + (b - v0 * e)] == b); }
+        return;
+    }
+    // the bit-plane layout: W = 8 * we plane segments of n / W words, then the verbatim tail
+    const uint64_t W = 8 * we, seg = n / W, L = seg * W;
+    CHECK(p.we == (int)we && p.v0 == v0 && p.v1 == v1 && p.L == L && p.w0 <= p.w1 && p.w1 <= seg);
+    for (uint64_t v = v0; v < v1; ++v) {
+        if (v >= L) {
+            for (uint64_t k = 0; k < we; ++k) CHECK(sel[(v * we + k) / chunk]);
+            CHECK(p.tail + (v1 - std::max(v0, L)) * we <= p.out_bytes);
+            for (uint64_t k = 0; k < we; ++k) CHECK(from[p.tail + (v - std::max(v0, L)) * we + k] == v * we + k);
+            continue;
+        }
+        const uint64_t w = v / W;
+        CHECK(w >= p.w0 && w < p.w1);
+        for (uint64_t s = 0; s < W; ++s) {
+            CHECK(p.plane[s] + (p.w1 - p.w0) * we <= p.out_bytes);
+            for (uint64_t k = 0; k < we; ++k) {
+                CHECK(sel[((s * seg + w) * we + k) / chunk]);
+                CHECK(from[p.plane[s] + (w - p.w0) * we + k] == (s * seg + w) * we + k);
+            }
+        }
+    }
+}
+
+static void range_plans(std::mt19937& rng)
+{
+    const RangeForm forms[] = {RangeForm::plain, RangeForm::planes, RangeForm::planes_lut, RangeForm::shuffle};
+    for (int round = 0; round < 6000; ++round) {
+        const RangeForm form = forms[round % 4];
+        const int elem = form == RangeForm::planes_lut ? 2 : 1 + (int)(rng() % 2);
+        const uint64_t shape0 = 1 + rng() % 12, vpf = 1 + rng() % 40, n = shape0 * vpf;
+        const uint64_t total = n * (uint64_t)(form == RangeForm::planes_lut ? 1 : elem);
+        // hostile ranges: the volume's ends, single frames, and now and then what the drivers refuse (nz = 0, past the end)
+        uint64_t z0 = rng() % shape0, nz = 1 + rng() % (shape0 - z0);
+        switch (rng() % 8) {
+            case 0: nz = shape0 - z0; break;
+            case 1: z0 = 0; nz = 1; break;
+            case 2: z0 = shape0 - 1; nz = 1; break;
+            case 3: if (rng() % 4 == 0) nz = rng() % 3 ? shape0 - z0 + 1 + rng() % 3 : 0; break;
+            case 4: if (rng() % 4 == 0) { z0 = shape0 + rng() % 2; nz = 1; } break;
+            default: break;
+        }
+        uint64_t chunk = rng() % 3 == 0 ? total + rng() % 3 : 1 + rng() % total;       // (one-chunk streams among them)
+        std::vector<uint64_t> map;
+        uint64_t place_bytes = 0;
+        if (form == RangeForm::shuffle) {
+            // frame_chunk_size consecutive frames are one place; whole chunks inside whole places, more than one chunk
+            uint64_t fcs = 1 + rng() % shape0;
+            while (shape0 % fcs) --fcs;
+            place_bytes = vpf * (uint64_t)elem * fcs;
+            chunk = 1 + rng() % place_bytes;
+            while (place_bytes % chunk) --chunk;
+            if (total / chunk < 2) continue;
+            map.resize(shape0 / fcs);
+            for (uint64_t i = 0; i < map.size(); ++i) map[i] = i;
+            if (rng() % 2) std::shuffle(map.begin(), map.end(), rng);
+            else for (uint64_t& v : map) if (rng() % 3 == 0) v = rng() % map.size();
+        }
+        check_range_plan(form, n, elem, shape0, z0, nz, chunk, map, place_bytes);
+    }
+    // fewer voxels than a plane word holds, a volume that is no whole number of words, one frame, one chunk
+    for (RangeForm form : {RangeForm::planes, RangeForm::planes_lut})
+        for (int elem : {1, 2})
+            for (uint64_t shape0 : {(uint64_t)1, (uint64_t)3, (uint64_t)5})
+                for (uint64_t vpf : {(uint64_t)1, (uint64_t)2, (uint64_t)7, (uint64_t)16})
+                    for (uint64_t z0 = 0; z0 < shape0; ++z0)
+                        for (uint64_t chunk : {(uint64_t)1, (uint64_t)3, (uint64_t)16, (uint64_t)1000}) {
+                            if (form == RangeForm::planes_lut && elem != 2) continue;
+                            check_range_plan(form, shape0 * vpf, elem, shape0, z0, 1, chunk, {}, 0);
+                            check_range_plan(form, shape0 * vpf, elem, shape0, z0, shape0 - z0, chunk, {}, 0);
+                        }
+    // arguments that name no range of such a stream are refused, not followed
+    CHECK(!frame_range_plan(RangeForm::plain, 0, 1, 0, 0, 1, 1, 0, 0).ok);
+    CHECK(!frame_range_plan(RangeForm::plain, 12, 2, 3, 0, 1, 0, 24, 1).ok);                               // no chunk size
+    CHECK(!frame_range_plan(RangeForm::plain, 12, 2, 3, 0, 1, 8, 24, 2).ok);                               // not one frame per chunk
+    CHECK(!frame_range_plan(RangeForm::planes, 12, 2, 3, ~0ull, 2, 8, 24, 3).ok);                          // z0 + nz wraps
+    CHECK(!frame_range_plan(RangeForm::planes, 12, 4, 3, 0, 1, 8, 48, 6).ok);                              // no such voxel type
+    CHECK(!frame_range_plan(RangeForm::shuffle, 12, 2, 3, 0, 1, 8, 24, 3, std::vector<unsigned char>(8), 8, 3).ok);   // a map of the wrong length
+    CHECK(!frame_range_plan(RangeForm::shuffle, 12, 2, 3, 0, 1, 8, 24, 3, std::vector<unsigned char>(24), 12, 2).ok); // chunks across places
+    CHECK(lz4_folds_into_shuffle(3, 3, 24, 8, 3, 8) && !lz4_folds_into_shuffle(1, 1, 24, 24, 1, 24) && !lz4_folds_into_shuffle(3, 3, 24, 8, 3, 0) &&
+          !lz4_folds_into_shuffle(3, 3, 24, 8, 2, 8) && !lz4_chunks_whole(3, 3, 25, 9) && !lz4_chunks_whole(2, 3, 24, 8) && !lz4_chunks_whole(0, 0, 0, 0));
+}
+
+
 int main(int argc, char** argv)
 {
     std::mt19937 rng(argc > 1 ? (unsigned)std::atoi(argv[1]) : 20261004u);
@@ -260,6 +453,9 @@ int main(int argc, char** argv)
     lz4_plans(rng);
     quantiser(rng);
     orderings(rng);
+    lz4_geometry(rng);
+    shuffle_maps(rng);
+    range_plans(rng);
     std::printf("host_fuzz ok: %lu checks\n", g_checks);
     return 0;
 }
