@@ -101,7 +101,10 @@ SQY_FUNCTION_PREFIX int SQY_Decode_UI8(const char* src, long srclength, char* ds
 
 /* d_src / d_dst are device pointers on the current HIP device; dst_capacity is checked (1 when the
  * blob does not fit).  hip_stream is a hipStream_t (NULL = default stream).  The call returns after the
- * blob is complete in d_dst.  All work is queued on hip_stream: whatever made d_src has to be in front of it there (or complete). */
+ * blob is complete in d_dst.  Ordering: the call starts behind everything queued on hip_stream at the time of the call (whatever made
+ * d_src has to be in front of it there, or complete) and is complete on return; work on OTHER streams that touches d_src or d_dst is
+ * the caller's to synchronise.  The work itself runs on hip_stream -- or, for the frames-in-place path of the _DeviceAt entry points
+ * below where the option "stage_lanes" says so, on streams of the library's own. */
 SQY_FUNCTION_PREFIX int SQYAMD_PipelineEncode_UI16_Device(const char* pipeline, const void* d_src, const long* shape,
                                                           unsigned shape_size, void* d_dst, long dst_capacity,
                                                           long* dstlength, int nthreads, void* hip_stream);
@@ -113,7 +116,19 @@ SQY_FUNCTION_PREFIX int SQYAMD_PipelineEncode_UI8_Device(const char* pipeline, c
  * transpose writes the plane stream straight into d_dst as the bodies of the LZ4 frames it will become (one frame per 256 KiB
  * chunk, encoders/lz4_utils.hpp:193-274); the stored frames that end the payload -- the noise planes, 98 % of the payload of a
  * microscopy stack -- then never move, only the compressed frames in front of them are gathered (no second pass over the
- * payload).  dst_capacity as above; every other pipeline returns *dstoffset = 0. */
+ * payload).  dst_capacity as above; every other pipeline returns *dstoffset = 0.
+ * Lanes ("stage_lanes" = 1, or 2 with "transpose_chain_caller_streams" on): a frames-in-place call waits on the CALLING THREAD until everything queued on hip_stream is complete
+ * (it polls; nothing is queued on hip_stream), then runs on the library's lanes of the device -- one stream for the bit-plane
+ * transposes of all such calls, in call order, and "parse_lanes" streams for what follows, dealt to the calls in flight -- and returns
+ * when its blob is complete.  The lanes are 1 + parse_lanes plain non-blocking streams per device, created on first use; with them
+ * it is the library, not the number of streams its callers happen to bring, that decides which kernels of the calls in flight can
+ * run side by side on the hardware queues the process has.  A hip_stream that still has work in flight after 2 ms (a backlog)
+ * delays nobody: that call runs on hip_stream itself, as with "stage_lanes" = 0 (a stage of the call's own in front of the transpose,
+ * diff3x3x1, runs on hip_stream too and is waited for the same way: one host round trip inside the call, and a stage longer than
+ * 2 ms keeps the call on hip_stream).  A call that finds no other call on the lanes first asks the two lanes it would take for an
+ * answer (a marker each, 0.25 ms at most): a lane that does not answer has a kernel of some other stream in front of it in its
+ * hardware queue, and the call stays on hip_stream.  With other calls on the lanes that is not asked, and such a kernel holds up the
+ * calls on the lane it blocks -- the reason for the default of "stage_lanes". */
 SQY_FUNCTION_PREFIX int SQYAMD_PipelineEncode_UI16_DeviceAt(const char* pipeline, const void* d_src, const long* shape,
                                                             unsigned shape_size, void* d_dst, long dst_capacity, long* dstoffset,
                                                             long* dstlength, int nthreads, void* hip_stream);
@@ -235,6 +250,19 @@ SQY_FUNCTION_PREFIX void SQYAMD_Release_Workspace(void);
  *   "transpose_chain_caller_streams"  0 [SQY_TRANSPOSE_CHAIN_CALLER_STREAMS=1]  .. on streams the CALLER brings as well.  This puts a
  *                                     hipStreamWaitEvent between two caller streams: only for callers whose streams carry nothing but
  *                                     these calls (a backlog or a host function on one stream would hold the other up)
+ *   "stage_lanes"                     2 [SQY_STAGE_LANES=<0..2>]  frames-in-place calls of the _DeviceAt / _DeviceAt_Frames entry points run on
+ *                                     the library's lanes (see there), not on the stream the caller passes: 0 never, 1 always, 2 when
+ *                                     "transpose_chain_caller_streams" is on -- the caller's statement that its streams carry nothing but
+ *                                     these calls, which now also means lanes.  (The lanes occupy every hardware queue of the process: a long
+ *                                     kernel of the caller's own on ANY of its streams shares a queue with one lane and holds up the calls
+ *                                     on it; a call on its caller's stream meets that only when the runtime puts the two streams behind one
+ *                                     queue.)  The Slabs workers and the host-pointer entry points keep their own streams and the chain above
+ *   "parse_lanes"                     3 [SQY_PARSE_LANES=<1..8>]  how many parse lanes a device has.  3 + the transpose lane = the four hardware
+ *                                     queues a process gets by default; a fourth parse lane shares a queue with the transpose lane (measured: no
+ *                                     faster than without lanes)
+ *   "lane_calls", "lane_backlog_fallbacks", "lane_blocked_fallbacks"   counters, not switches (Get reads, Set takes 0 only): calls that
+ *                                     ran on the lanes; calls that stayed on their caller's stream because it had a backlog; .. because a
+ *                                     lane did not answer
  *   "block_parallel"                  1 [SQY_NO_BLOCK_PARALLEL=1 -> 0]  block-linked frames (nthreads = 1) encoded / decoded block-parallel
  *   "block_parallel_warmup"           65536 [SQY_BLOCK_PARALLEL_WARMUP=<bytes>, 0 .. 2^30]  stream parsed in front of a block to guess its table
  *   "block_parallel_stats"            0 [SQY_BLOCK_PARALLEL_STATS=1]  print the blocks whose guess failed

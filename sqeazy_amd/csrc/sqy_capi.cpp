@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "sqy_kernels.h"
+#include "sqy_lanes.hpp"
 #include "sqy_pipeline.hpp"
 
 namespace {
@@ -59,6 +60,7 @@ long env_number(const char* name, long dflt, long lo, long hi)
     return (long)x;
 }
 constexpr long kWarmupMax = 1l << 30;
+constexpr long kStageLanesDefault = 2, kParseLanesDefault = 3;      // (measured: DESIGN.md section 5)
 struct Options {
     std::atomic<long> transpose_chain;                  // the bit-plane transposes of calls in flight on LIBRARY-OWNED streams run one after the other
     std::atomic<long> transpose_chain_caller_streams;   // .. on streams the callers bring as well (opt-in: couples those streams, see the bitswap1 stage)
@@ -73,6 +75,11 @@ struct Options {
     std::atomic<long> host_l2_bytes;                    // rmestbkrd: the host CPU's L2 size as the reference's compass reads it (detected; tests set it)
     std::atomic<long> decode_frames_subset;             // frame-range decode: only the LZ4 frames the range needs, where the pipeline allows (0: full decode + copy)
     std::atomic<long> decode_slabs_joint;               // slab-set decode: the chunked LZ4 blobs of a group indexed and decoded by one launch each (0: blob by blob)
+    std::atomic<long> stage_lanes;                      // frames-in-place calls on caller streams run on the library's lanes: 0 never, 1 always, 2 where transpose_chain_caller_streams is on
+    std::atomic<long> parse_lanes;                      // .. how many parse lanes a device has (1-8)
+    // counters (Get reads, Set takes 0 only): calls that ran on the lanes; calls that stayed on their caller's stream because it had a
+    // backlog; .. because an idle lane did not answer (a foreign kernel in front of it in its hardware queue)
+    std::atomic<long> lane_calls{0}, lane_backlog_fallbacks{0}, lane_blocked_fallbacks{0};
     Options()
         : transpose_chain(env_flag("SQY_NO_TRANSPOSE_CHAIN") ? 0 : 1), transpose_chain_caller_streams(env_flag("SQY_TRANSPOSE_CHAIN_CALLER_STREAMS")),
           block_parallel(env_flag("SQY_NO_BLOCK_PARALLEL") ? 0 : 1), block_parallel_warmup(env_number("SQY_BLOCK_PARALLEL_WARMUP", 65536, 0, kWarmupMax)),
@@ -80,7 +87,8 @@ struct Options {
           decode_two_waves(env_flag("SQY_NO_DECODE_TWO_WAVES") ? 0 : 1), noise_digest(env_flag("SQY_NO_NOISE_DIGEST") ? 0 : 1),
           transpose_blocks_per_cu(env_number("SQY_TRANSPOSE_BLOCKS_PER_CU", 32, 1, 64)), stored_tail_index(env_flag("SQY_NO_STORED_TAIL_INDEX") ? 0 : 1),
           host_l2_bytes((long)sqy::host_l2_cache_bytes()), decode_frames_subset(env_flag("SQY_NO_DECODE_FRAMES_SUBSET") ? 0 : 1),
-          decode_slabs_joint(env_flag("SQY_NO_DECODE_SLABS_JOINT") ? 0 : 1) { sqy::set_bitswap1_blocks_per_cu(transpose_blocks_per_cu.load()); }
+          decode_slabs_joint(env_flag("SQY_NO_DECODE_SLABS_JOINT") ? 0 : 1), stage_lanes(env_number("SQY_STAGE_LANES", kStageLanesDefault, 0, 2)),
+          parse_lanes(env_number("SQY_PARSE_LANES", kParseLanesDefault, 1, sqy::LanePicker::kMaxLanes)) { sqy::set_bitswap1_blocks_per_cu(transpose_blocks_per_cu.load()); }
     std::atomic<long>* find(const char* name)
     {
         if (!name) return nullptr;
@@ -97,6 +105,11 @@ struct Options {
         if (!std::strcmp(name, "host_l2_bytes")) return &host_l2_bytes;
         if (!std::strcmp(name, "decode_frames_subset")) return &decode_frames_subset;
         if (!std::strcmp(name, "decode_slabs_joint")) return &decode_slabs_joint;
+        if (!std::strcmp(name, "stage_lanes")) return &stage_lanes;
+        if (!std::strcmp(name, "parse_lanes")) return &parse_lanes;
+        if (!std::strcmp(name, "lane_calls")) return &lane_calls;
+        if (!std::strcmp(name, "lane_backlog_fallbacks")) return &lane_backlog_fallbacks;
+        if (!std::strcmp(name, "lane_blocked_fallbacks")) return &lane_blocked_fallbacks;
         return nullptr;
     }
 };
@@ -324,6 +337,14 @@ struct Context {
     hipStream_t side = nullptr;         // decode: stored frames are copied here while the compressed ones are decoded
     hipEvent_t fork = nullptr, join = nullptr;
     hipEvent_t t_done = nullptr;        // recorded behind this call's bit-plane transpose (the transposes of calls in flight run one after the other)
+    hipEvent_t lane_t = nullptr;        // a call that takes the lanes: recorded behind its transpose on the transpose lane, its parse lane waits for it
+    hipEvent_t lane_p = nullptr;        // .. the liveness marker on its parse lane (lane_t serves as the transpose lane's)
+    bool ensure_lane_event()
+    {
+        if (!lane_p && hipEventCreateWithFlags(&lane_p, hipEventDisableTiming) != hipSuccess) { lane_p = nullptr; return false; }
+        if (!lane_t && hipEventCreateWithFlags(&lane_t, hipEventDisableTiming) != hipSuccess) { lane_t = nullptr; return false; }
+        return true;
+    }
     hipStream_t own_stream()
     {
         if (!stream && hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) != hipSuccess) stream = nullptr;
@@ -349,6 +370,56 @@ constexpr size_t kMaxCtxPerDev = 8;
 std::mutex g_tchain_mu[kMaxDev];
 hipEvent_t g_tchain_last[kMaxDev] = {};
 std::chrono::steady_clock::time_point g_tchain_when[kMaxDev];
+// The lanes of one device (round 7): streams of the library's own on which the frames-in-place calls that callers make on streams of
+// THEIRS run.  The runtime deals streams to the few hardware queues a process gets; kernels of two streams behind one queue never
+// overlap, so with one caller stream per call in flight it is the callers' number of streams, not the work, that decides what runs
+// side by side.  On lanes it is the library's: ONE transpose lane (the clear + bit-plane transpose of every such call, in call order
+// -- the serial order the event chain below expresses between streams, without an event) and `parse_lanes` parse lanes (everything
+// behind the transpose, on the lane with the fewest calls leased).  Created on first use and kept; plain non-blocking streams.
+struct Lanes {
+    std::mutex mu;                      // lane creation, the picker, and the launches onto the transpose lane
+    hipStream_t transpose = nullptr;
+    hipStream_t parse[sqy::LanePicker::kMaxLanes] = {};
+    sqy::LanePicker picker;
+    bool ensure(int lane)
+    {
+        if (!transpose && hipStreamCreateWithFlags(&transpose, hipStreamNonBlocking) != hipSuccess) { transpose = nullptr; return false; }
+        if (!parse[lane] && hipStreamCreateWithFlags(&parse[lane], hipStreamNonBlocking) != hipSuccess) { parse[lane] = nullptr; return false; }
+        return true;
+    }
+};
+Lanes g_lanes[kMaxDev];
+// how long a call polls for its caller's stream to arrive before it stays on that stream (see EncodeCall::take_lanes)
+constexpr std::chrono::microseconds kLaneArrival(2000);
+// how long an idle lane may take to answer a marker before it counts as blocked (an idle queue answers in 10-30 us)
+constexpr std::chrono::microseconds kLaneAnswer(250);
+
+// What one call holds of the lanes: its parse lane's lease (given back on every way out) and what it queued where (for the drain).
+struct LaneLease {
+    Lanes* lanes = nullptr;
+    int lane = -1;
+    hipStream_t transpose = nullptr, parse = nullptr;
+    hipEvent_t t_done = nullptr;        // recorded behind the call's last launch on the transpose lane
+    bool taken() const { return lanes != nullptr; }
+    // waits for what this call queued on the lanes -- not for other calls' transposes behind it on the transpose lane
+    void drain()
+    {
+        if (!lanes) return;
+        if (t_done) (void)hipEventSynchronize(t_done);
+        else (void)hipStreamSynchronize(transpose);
+        (void)hipStreamSynchronize(parse);
+    }
+    ~LaneLease()
+    {
+        if (!lanes) return;
+        std::lock_guard<std::mutex> lock(lanes->mu);
+        lanes->picker.give(lane);
+    }
+    LaneLease() = default;
+    LaneLease(const LaneLease&) = delete;
+    LaneLease& operator=(const LaneLease&) = delete;
+};
+
 std::mutex g_pool_mu;
 std::condition_variable g_pool_cv;
 std::vector<std::unique_ptr<Context>> g_pool[kMaxDev];
@@ -394,9 +465,12 @@ struct DrainOnExit {
     hipStream_t s;
     std::vector<PendingEvent>* pending;
     hipStream_t side = nullptr;         // the context's side stream (decode)
+    LaneLease* lanes = nullptr;         // encode: what the call queued on the library's lanes
     ~DrainOnExit()
     {
-        (void)hipStreamSynchronize(s);
+        // (a call on the lanes saw its caller's stream complete before it took them and has queued nothing there since)
+        if (!lanes || !lanes->taken()) (void)hipStreamSynchronize(s);
+        if (lanes) lanes->drain();
         if (side) (void)hipStreamSynchronize(side);
         if (!pending->empty()) {
             if (g_prof_on.load()) prof_collect(*pending);
@@ -485,7 +559,8 @@ struct EncodeCall {
     Context& cx;
     Workspace* ws;
     std::vector<PendingEvent>* pend;
-    hipStream_t stream;
+    hipStream_t stream;                  // where the next launch goes: the stream the call was made on, or one of the library's lanes
+    LaneLease* lanes;
     Pipeline pipe;
     std::vector<uint64_t> dims;
     uint64_t len;                        // voxels
@@ -527,8 +602,8 @@ struct EncodeCall {
     } lz4;
 
     EncodeCall(Context& c, hipStream_t s, Pipeline&& p, std::vector<uint64_t>&& d, uint64_t voxels, int elem, const void* src, void* dst,
-               uint64_t capacity, long* offset, FrameQuery* frames)
-        : cx(c), ws(&c.ws), pend(&c.pending), stream(s), pipe(std::move(p)), dims(std::move(d)), len(voxels), elem_size(elem), d_dst(dst),
+               uint64_t capacity, long* offset, FrameQuery* frames, LaneLease* lane_lease)
+        : cx(c), ws(&c.ws), pend(&c.pending), stream(s), lanes(lane_lease), pipe(std::move(p)), dims(std::move(d)), len(voxels), elem_size(elem), d_dst(dst),
           dst_capacity(capacity), dstoffset(offset), fq(frames), cur(static_cast<const uint8_t*>(src)), cur_elem(elem), cur_len(voxels) {}
 
     uint8_t* next_buf(size_t bytes)
@@ -554,8 +629,93 @@ struct EncodeCall {
         Z = flat ? 1 : dims[0]; Y = flat ? 1 : dims[1]; X = flat ? cur_len : dims[2];
     }
 
+    // Frames in place on a stream the caller brought: the rest of the call moves onto the library's lanes (option stage_lanes).
+    // The call has to start behind everything queued on the caller's stream S at the time of the call.  A hipStreamWaitEvent on the
+    // transpose lane would say so -- and make every transpose queued behind this one wait for S's backlog as well, the coupling of
+    // callers' streams that transpose_chain_caller_streams is opt-in for.  So the wait is done HERE, on the calling thread (which
+    // blocks until the call is complete anyway): S is polled (hipStreamQuery) until everything on it is complete, then the call
+    // takes its place in the lane and needs no edge on the device at all.  Nothing is queued on S for that -- not even an event:
+    // S may share its hardware queue with a parse lane, and a marker would sit there behind another call's whole parse (measured:
+    // 0.65 instead of 0.60 ms per step).  A stream that has not arrived within kLaneArrival carries a backlog: that call
+    // stays on S, as with stage_lanes = 0 (returns 0 with `stream` unchanged).  On success `lock` holds the device's lane mutex --
+    // launches onto the transpose lane are in call order, and a timed kernel's two events enclose nothing of another call.
+    int take_lanes(std::unique_lock<std::mutex>& lock)
+    {
+        // stage_lanes = 2 (default): only for callers who said that their streams carry nothing but these calls.  The lanes sit on ALL
+        // of the process's hardware queues; a long foreign kernel on any caller stream then shares a queue with one of them and holds
+        // up every call that uses that lane (measured: one call in three, or all of them when it is the transpose lane's queue) --
+        // below the streams, where no poll sees it.  On its own stream a call meets such a kernel only when the runtime happens to
+        // put the two streams behind one queue.
+        const long mode = g_opt.stage_lanes.load();
+        if (!lanes || mode == 0 || (mode == 2 && !g_opt.transpose_chain_caller_streams.load()) || (stream != nullptr && stream == cx.stream)) return 0;
+        int devid = 0;
+        if (hipGetDevice(&devid) != hipSuccess || devid < 0 || devid >= kMaxDev) return 0;
+        if (!cx.ensure_lane_event()) { std::fprintf(stderr, "[sqeazy]\t no HIP event for the lanes\n"); return 1; }
+        const auto deadline = std::chrono::steady_clock::now() + kLaneArrival;
+        for (;;) {
+            const hipError_t e = hipStreamQuery(stream);
+            if (e == hipSuccess) break;
+            (void)hipGetLastError();
+            if (e != hipErrorNotReady) { std::fprintf(stderr, "[sqeazy]\t HIP error %s while waiting for the caller's stream\n", hipGetErrorString(e)); return 1; }
+            if (std::chrono::steady_clock::now() > deadline) { g_opt.lane_backlog_fallbacks += 1; return 0; }
+            std::this_thread::yield();
+        }
+        Lanes& L = g_lanes[devid];
+        lock = std::unique_lock<std::mutex>(L.mu);
+        const int lane = L.picker.take((int)g_opt.parse_lanes.load());
+        if (!L.ensure(lane)) {
+            L.picker.give(lane);
+            std::fprintf(stderr, "[sqeazy]\t no HIP stream for the lanes\n");
+            return 1;
+        }
+        // Liveness.  The lanes share the process's hardware queues with the callers' streams, and a kernel waits for whatever is in
+        // front of it in its QUEUE: a long kernel of the caller's own on some other stream holds up a lane without any stream saying
+        // so.  When this call is the only one on the lanes (every lease but its own given back: nothing of the library's is in
+        // flight there) an idle lane answers a marker at once; one that does not within kLaneAnswer has such a kernel in front, and
+        // the call stays on its caller's stream.  With other calls on the lanes a marker would wait for THEIR kernels: not asked.
+        if (L.picker.total() == 1) {
+            const hipError_t r = hipEventRecord(cx.lane_t, L.transpose);
+            if (r != hipSuccess || hipEventRecord(cx.lane_p, L.parse[lane]) != hipSuccess) { L.picker.give(lane); SQY_HIP(hipErrorUnknown); }
+            lock.unlock();                                  // (calls that arrive now queue behind the markers)
+            const auto answer_by = std::chrono::steady_clock::now() + kLaneAnswer;
+            bool alive = false;
+            for (;;) {
+                const hipError_t et = hipEventQuery(cx.lane_t), ep = et == hipSuccess ? hipEventQuery(cx.lane_p) : et;
+                if (et == hipSuccess && ep == hipSuccess) { alive = true; break; }
+                (void)hipGetLastError();
+                if (std::chrono::steady_clock::now() > answer_by) break;
+                std::this_thread::yield();
+            }
+            lock.lock();
+            if (!alive) {
+                L.picker.give(lane);
+                lock.unlock();
+                g_opt.lane_blocked_fallbacks += 1;
+                return 0;
+            }
+        }
+        g_opt.lane_calls += 1;
+        lanes->lanes = &L;
+        lanes->lane = lane;
+        lanes->transpose = L.transpose;
+        lanes->parse = L.parse[lane];
+        stream = L.transpose;
+        return 0;
+    }
+    // behind the call's last launch on the transpose lane: its parse lane waits for that, and takes the rest of the call
+    int leave_transpose_lane(std::unique_lock<std::mutex>& lock)
+    {
+        SQY_HIP(hipEventRecord(cx.lane_t, stream));
+        lanes->t_done = cx.lane_t;
+        lock.unlock();
+        stream = lanes->parse;
+        SQY_HIP(hipStreamWaitEvent(stream, cx.lane_t, 0));
+        return 0;
+    }
+
     int bitswap1(size_t si)
     {
+        std::unique_lock<std::mutex> lane_lock;             // (held from take_lanes to leave_transpose_lane, or to the first error return)
         // lz4 right behind: leave piece hashes for its duplicate-chunk detection (bit planes of small values repeat)
         uint32_t* ph = nullptr;
         uint64_t gap_chunk = 0;
@@ -585,15 +745,17 @@ struct EncodeCall {
                         prep.inplace = true;
                         // (one small kernel in front of the transpose instead of three fill dispatches between the kernels behind it)
                         if (ws->plan.ensure((nch + 1) * sizeof(uint32_t))) return 1;
-                        SQY_HIP(sqy::launch_lz4_dedupe_clear(static_cast<uint8_t*>(ws->dedupe.p) + ph_bytes, nch, static_cast<uint32_t*>(ws->plan.p), stream));
-                        prep.dedupe_cleared = true;
                         // the noise digest (round 6): every plane segment a whole number of chunks, liblz4's plain search behind it
+                        // (allocated in front of take_lanes: the lane mutex is held for launches only)
                         const uint32_t dstride = sqy::lz4_noise_digest_stride((uint32_t)chunk);
                         if (g_opt.noise_digest.load() && dstride && (cur_len / 8) % chunk == 0 && lz.accel >= 0 &&
                             !ws->digest.ensure(nch * (uint64_t)dstride * sizeof(uint32_t), true)) {
                             prep.digest = static_cast<uint32_t*>(ws->digest.p);
                             prep.digest_stride = dstride;
                         }
+                        if (take_lanes(lane_lock)) return 1;
+                        SQY_HIP(sqy::launch_lz4_dedupe_clear(static_cast<uint8_t*>(ws->dedupe.p) + ph_bytes, nch, static_cast<uint32_t*>(ws->plan.p), stream));
+                        prep.dedupe_cleared = true;
                     }
                 }
             }
@@ -611,9 +773,11 @@ struct EncodeCall {
         // wait on it would couple calls that are documented as independent (round-4 advice).  A caller whose streams carry
         // nothing but these calls opts in: SQYAMD_Set_Option("transpose_chain_caller_streams", 1) (bench.py does, and says so).
         // "transpose_chain" = 0 (or SQY_NO_TRANSPOSE_CHAIN=1 when the library is loaded) switches the chain off altogether.
+        // (round 7) A call on the lanes needs none of this: its transpose is on the transpose lane, behind the one in front.
+        const bool on_lanes = lanes && lanes->taken();
         const bool owned = stream != nullptr && stream == cx.stream;
         int devid = 0;
-        const bool chain = g_opt.transpose_chain.load() && (owned || g_opt.transpose_chain_caller_streams.load()) && gap_chunk &&
+        const bool chain = !on_lanes && g_opt.transpose_chain.load() && (owned || g_opt.transpose_chain_caller_streams.load()) && gap_chunk &&
                            hipGetDevice(&devid) == hipSuccess && devid >= 0 && devid < kMaxDev;
         std::unique_lock<std::mutex> tlock;
         if (chain) {
@@ -634,6 +798,7 @@ struct EncodeCall {
             g_tchain_last[devid] = cx.t_done;
             tlock.unlock();
         }
+        if (on_lanes && leave_transpose_lane(lane_lock)) return 1;
         side = DiffSide();                      // (consumed: a later bitswap1 of the pipeline reads its plain input)
         return produced(out);
     }
@@ -1272,8 +1437,9 @@ int encode_on_device(Context& cx, const char* pipeline_c, const void* d_src, con
     std::vector<uint64_t> dims(shape, shape + rank);
     if (!background_geometry_ok(pipe, dims)) return 1;
 
-    DrainOnExit drain{stream, &cx.pending, cx.side};
-    EncodeCall c(cx, stream, std::move(pipe), std::move(dims), len, elem_size, d_src, d_dst, dst_capacity, dstoffset, fq);
+    LaneLease lanes;                    // (given back after the drain)
+    DrainOnExit drain{stream, &cx.pending, cx.side, &lanes};
+    EncodeCall c(cx, stream, std::move(pipe), std::move(dims), len, elem_size, d_src, d_dst, dst_capacity, dstoffset, fq, &lanes);
     for (size_t si = 0; si < c.pipe.stages.size(); ++si) {
         int rc = 0;
         switch (c.pipe.stages[si].kind) {
@@ -2814,6 +2980,9 @@ int SQYAMD_Set_Option(const char* name, long value)
     if (o == &g_opt.block_parallel_warmup) { if (value < 0 || value > kWarmupMax) return 1; }
     else if (o == &g_opt.transpose_blocks_per_cu) { if (value < 1 || value > 64) return 1; sqy::set_bitswap1_blocks_per_cu(value); }
     else if (o == &g_opt.host_l2_bytes) { if (value < 0 || value > (long)UINT32_MAX) return 1; }
+    else if (o == &g_opt.stage_lanes) { if (value < 0 || value > 2) return 1; }
+    else if (o == &g_opt.lane_calls || o == &g_opt.lane_backlog_fallbacks || o == &g_opt.lane_blocked_fallbacks) { if (value != 0) return 1; }
+    else if (o == &g_opt.parse_lanes) { if (value < 1 || value > sqy::LanePicker::kMaxLanes) return 1; }
     else if (value != 0 && value != 1) return 1;
     o->store(value);
     return 0;
