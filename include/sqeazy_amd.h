@@ -263,6 +263,8 @@ SQY_FUNCTION_PREFIX void SQYAMD_Release_Workspace(void);
  *   "lane_calls", "lane_backlog_fallbacks", "lane_blocked_fallbacks"   counters, not switches (Get reads, Set takes 0 only): calls that
  *                                     ran on the lanes; calls that stayed on their caller's stream because it had a backlog; .. because a
  *                                     lane did not answer
+ *   "call_stamps"                     0  1: every device-memory encode call leaves host time stamps for SQYAMD_Call_Stamps (setting 1 drops
+ *                                     the stamps kept so far); 0: a call pays one relaxed load
  *   "block_parallel"                  1 [SQY_NO_BLOCK_PARALLEL=1 -> 0]  block-linked frames (nthreads = 1) encoded / decoded block-parallel
  *   "block_parallel_warmup"           65536 [SQY_BLOCK_PARALLEL_WARMUP=<bytes>, 0 .. 2^30]  stream parsed in front of a block to guess its table
  *   "block_parallel_stats"            0 [SQY_BLOCK_PARALLEL_STATS=1]  print the blocks whose guess failed
@@ -286,6 +288,17 @@ SQY_FUNCTION_PREFIX void SQYAMD_Release_Workspace(void);
  * Set: 0 = done, 1 = unknown name or value out of range.  Get: the value, -1 for an unknown name. */
 SQY_FUNCTION_PREFIX int SQYAMD_Set_Option(const char* name, long value);
 SQY_FUNCTION_PREFIX long SQYAMD_Get_Option(const char* name);
+
+/* Where the host side of the device-memory encode calls spends its time (option "call_stamps" = 1 while they run).  Copies the
+ * newest max_records records, oldest first, SQYAMD_CALL_STAMP_FIELDS longs each, and returns how many (out == NULL: how many are
+ * kept; the last 8192 calls are).  A record: [0] the call's place in the order of the transpose lane since "lane_calls" was reset
+ * (-1: it did not run on the lanes), [1] its parse lane, [2] a number that stands for the calling thread, then
+ * std::chrono::steady_clock nanoseconds at [3] entry of the C call, [4] lanes taken (the caller's stream polled, the lane mutex
+ * held), [5] clear launched, [6] transpose launched, [7] everything queued on the parse lane, [8] hipStreamSynchronize returned,
+ * [9] just before the C call returns (drained, context given back).
+ * A stamp the call did not pass is 0.  tools/inflight_timeline.py reads them next to a kernel trace of the same run. */
+#define SQYAMD_CALL_STAMP_FIELDS 10
+SQY_FUNCTION_PREFIX long SQYAMD_Call_Stamps(long* out, long max_records);
 
 /* Header helpers for callers that store blobs in containers of their own (the HDF5 filter's cd_values carry a header:
  * inc/sqeazy_h5_filter.hpp:117-121, src/hdf5_utils.hpp:730-738).  The reference does this through its C++ header class

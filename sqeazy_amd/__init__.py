@@ -32,7 +32,7 @@ EXPORTED_SYMBOLS = (
     "SQYAMD_Decode_Frames_UI16_Device", "SQYAMD_Decode_Frames_UI8_Device", "SQYAMD_Decode_Frames_UI16", "SQYAMD_Decode_Frames_UI8",
     "SQYAMD_Decode_Slabs_UI16_Device", "SQYAMD_Decode_Slabs_UI8_Device", "SQYAMD_Decode_Slabs_UI16", "SQYAMD_Decode_Slabs_UI8",
     "SQYAMD_Profile_Enable", "SQYAMD_Profile_Reset", "SQYAMD_Profile_Get",
-    "SQYAMD_Release_Workspace", "SQYAMD_Set_Option", "SQYAMD_Get_Option", "SQYAMD_Version", "SQYAMD_Header_Pipeline", "SQYAMD_Header_Build",
+    "SQYAMD_Release_Workspace", "SQYAMD_Set_Option", "SQYAMD_Get_Option", "SQYAMD_Call_Stamps", "SQYAMD_Version", "SQYAMD_Header_Pipeline", "SQYAMD_Header_Build",
     "SQYAMD_Comm_UniqueId", "SQYAMD_Comm_Init", "SQYAMD_Comm_Destroy", "SQYAMD_Gather_Blobs",
 )
 
@@ -335,6 +335,21 @@ def set_option(name, value):
 
 def get_option(name):
     return int(lib().SQYAMD_Get_Option(name.encode()))
+
+
+CALL_STAMP_FIELDS = ("seq", "lane", "thread", "entry", "lanes_taken", "clear_launched", "transpose_launched", "parse_queued", "sync_returned", "returned")
+
+
+def call_stamps(max_records=8192):
+    """SQYAMD_Call_Stamps: the newest records of the encode calls made under option "call_stamps", oldest first, one dict per call
+    (CALL_STAMP_FIELDS: place on the transpose lane, parse lane, steady-clock nanoseconds; include/sqeazy_amd.h)"""
+    fn = lib().SQYAMD_Call_Stamps
+    fn.restype = ctypes.c_long
+    fn.argtypes = [ctypes.POINTER(ctypes.c_long), ctypes.c_long]
+    nf = len(CALL_STAMP_FIELDS)
+    buf = (ctypes.c_long * (nf * max_records))()
+    n = fn(buf, max_records)
+    return [dict(zip(CALL_STAMP_FIELDS, buf[i * nf:(i + 1) * nf])) for i in range(n)]
 
 
 class option:

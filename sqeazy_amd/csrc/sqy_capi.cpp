@@ -80,6 +80,7 @@ struct Options {
     // counters (Get reads, Set takes 0 only): calls that ran on the lanes; calls that stayed on their caller's stream because it had a
     // backlog; .. because an idle lane did not answer (a foreign kernel in front of it in its hardware queue)
     std::atomic<long> lane_calls{0}, lane_backlog_fallbacks{0}, lane_blocked_fallbacks{0};
+    std::atomic<long> call_stamps{0};                   // host time stamps per encode call (SQYAMD_Call_Stamps); off: a call pays one relaxed load
     Options()
         : transpose_chain(env_flag("SQY_NO_TRANSPOSE_CHAIN") ? 0 : 1), transpose_chain_caller_streams(env_flag("SQY_TRANSPOSE_CHAIN_CALLER_STREAMS")),
           block_parallel(env_flag("SQY_NO_BLOCK_PARALLEL") ? 0 : 1), block_parallel_warmup(env_number("SQY_BLOCK_PARALLEL_WARMUP", 65536, 0, kWarmupMax)),
@@ -110,10 +111,50 @@ struct Options {
         if (!std::strcmp(name, "lane_calls")) return &lane_calls;
         if (!std::strcmp(name, "lane_backlog_fallbacks")) return &lane_backlog_fallbacks;
         if (!std::strcmp(name, "lane_blocked_fallbacks")) return &lane_blocked_fallbacks;
+        if (!std::strcmp(name, "call_stamps")) return &call_stamps;
         return nullptr;
     }
 };
 Options g_opt;
+
+// ---- call stamps ---------------------------------------------------------------------------------
+// Where the host side of an encode call spends its time (option "call_stamps", read back through SQYAMD_Call_Stamps): the steady
+// clock at seven places of the call, the call's place in the order of the transpose lane and the parse lane it took.  Together with
+// a kernel trace of the same run this splits a call's cycle into what the device did and what it waited for
+// (tools/inflight_timeline.py).  The last kStampRing calls are kept.
+struct CallStamps {
+    enum { entry, lanes_taken, clear_launched, transpose_launched, parse_queued, sync_returned, returned, kStamps };
+    long seq = -1;                      // n-th call on the transpose lane since the counters were reset (-1: the call did not take the lanes)
+    long lane = -1;                     // its parse lane
+    long thread = 0;                    // the calling thread (a hash of its id: which calls follow each other)
+    long ns[kStamps] = {};
+    void stamp(int i) { ns[i] = (long)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+};
+constexpr size_t kStampRing = 8192;
+std::mutex g_stamps_mu;
+std::vector<CallStamps> g_stamps;       // a ring once it holds kStampRing records
+size_t g_stamps_next = 0;
+// One call's record: stamped at entry, and put into the ring when it goes out of scope -- declared in front of the call's context
+// lease, so that the last stamp is taken when the context has gone back to the pool.
+struct StampScope {
+    CallStamps rec;
+    const bool on;
+    StampScope() : on(g_opt.call_stamps.load(std::memory_order_relaxed) != 0) 
+    {
+        if (!on) return;
+        rec.stamp(CallStamps::entry);
+        rec.thread = (long)(std::hash<std::thread::id>()(std::this_thread::get_id()) & 0x7fffffff);
+    }
+    CallStamps* get() { return on ? &rec : nullptr; }
+    ~StampScope()
+    {
+        if (!on) return;
+        rec.stamp(CallStamps::returned);
+        std::lock_guard<std::mutex> lock(g_stamps_mu);
+        if (g_stamps.size() < kStampRing) g_stamps.push_back(rec);
+        else { g_stamps[g_stamps_next] = rec; g_stamps_next = (g_stamps_next + 1) % kStampRing; }
+    }
+};
 
 // ---- per-kernel timing -------------------------------------------------------------------------
 struct ProfEntry { std::string name; double ms = 0; long launches = 0; };
@@ -400,11 +441,16 @@ struct LaneLease {
     int lane = -1;
     hipStream_t transpose = nullptr, parse = nullptr;
     hipEvent_t t_done = nullptr;        // recorded behind the call's last launch on the transpose lane
+    bool complete = false;              // the call has seen everything it queued on the lanes finish (EncodeCall::finish)
     bool taken() const { return lanes != nullptr; }
-    // waits for what this call queued on the lanes -- not for other calls' transposes behind it on the transpose lane
+    // waits for what this call queued on the lanes -- not for other calls' transposes behind it on the transpose lane.  A call that
+    // has synchronised with its parse lane behind its last launch has nothing left to wait for, and must not ask the lane again: by
+    // then the NEXT call may have queued its kernels there (the picker sends it to the lane of the call that is about to finish), and
+    // hipStreamSynchronize would wait for that call's whole parse -- one call in four did, 1.6 ms each.
+    // Only the ways out that have not seen the lane finish (errors) wait here.
     void drain()
     {
-        if (!lanes) return;
+        if (!lanes || complete) return;
         if (t_done) (void)hipEventSynchronize(t_done);
         else (void)hipStreamSynchronize(transpose);
         (void)hipStreamSynchronize(parse);
@@ -561,6 +607,7 @@ struct EncodeCall {
     std::vector<PendingEvent>* pend;
     hipStream_t stream;                  // where the next launch goes: the stream the call was made on, or one of the library's lanes
     LaneLease* lanes;
+    CallStamps* stamps;                  // nullptr: not asked for
     Pipeline pipe;
     std::vector<uint64_t> dims;
     uint64_t len;                        // voxels
@@ -602,8 +649,8 @@ struct EncodeCall {
     } lz4;
 
     EncodeCall(Context& c, hipStream_t s, Pipeline&& p, std::vector<uint64_t>&& d, uint64_t voxels, int elem, const void* src, void* dst,
-               uint64_t capacity, long* offset, FrameQuery* frames, LaneLease* lane_lease)
-        : cx(c), ws(&c.ws), pend(&c.pending), stream(s), lanes(lane_lease), pipe(std::move(p)), dims(std::move(d)), len(voxels), elem_size(elem), d_dst(dst),
+               uint64_t capacity, long* offset, FrameQuery* frames, LaneLease* lane_lease, CallStamps* call_stamps)
+        : cx(c), ws(&c.ws), pend(&c.pending), stream(s), lanes(lane_lease), stamps(call_stamps), pipe(std::move(p)), dims(std::move(d)), len(voxels), elem_size(elem), d_dst(dst),
           dst_capacity(capacity), dstoffset(offset), fq(frames), cur(static_cast<const uint8_t*>(src)), cur_elem(elem), cur_len(voxels) {}
 
     uint8_t* next_buf(size_t bytes)
@@ -694,7 +741,8 @@ struct EncodeCall {
                 return 0;
             }
         }
-        g_opt.lane_calls += 1;
+        const long seq = g_opt.lane_calls.fetch_add(1);
+        if (stamps) { stamps->seq = seq; stamps->lane = lane; stamps->stamp(CallStamps::lanes_taken); }
         lanes->lanes = &L;
         lanes->lane = lane;
         lanes->transpose = L.transpose;
@@ -756,6 +804,7 @@ struct EncodeCall {
                         if (take_lanes(lane_lock)) return 1;
                         SQY_HIP(sqy::launch_lz4_dedupe_clear(static_cast<uint8_t*>(ws->dedupe.p) + ph_bytes, nch, static_cast<uint32_t*>(ws->plan.p), stream));
                         prep.dedupe_cleared = true;
+                        if (stamps) stamps->stamp(CallStamps::clear_launched);
                     }
                 }
             }
@@ -798,6 +847,7 @@ struct EncodeCall {
             g_tchain_last[devid] = cx.t_done;
             tlock.unlock();
         }
+        if (stamps) stamps->stamp(CallStamps::transpose_launched);
         if (on_lanes && leave_transpose_lane(lane_lock)) return 1;
         side = DiffSide();                      // (consumed: a later bitswap1 of the pipeline reads its plain input)
         return produced(out);
@@ -1163,7 +1213,9 @@ struct EncodeCall {
             return 0;
         };
         if (tail(d_redo, fused_tail, true)) return 1;
+        if (stamps) stamps->stamp(CallStamps::parse_queued);
         SQY_HIP(hipStreamSynchronize(stream));
+        if (stamps) stamps->stamp(CallStamps::sync_returned);
         if (record[0] == 2) {                                  // chunks left to the dense pass: it runs, then the tail again
             if (lz4_dense(d_redo, (uint32_t)record[6])) return 1;
             if (tail(nullptr, fused_tail, true)) return 1;
@@ -1342,6 +1394,7 @@ struct EncodeCall {
         }
         // the blob is complete (the stream synchronised): it lies at d_dst + at
         auto done = [&](uint64_t at, uint64_t bytes) -> int {
+            if (lanes) lanes->complete = true;
             if (g_prof_on.load()) prof_collect(*pend);
             if (dstoffset) *dstoffset = (long)at;
             *dstlength = (long)bytes;
@@ -1411,7 +1464,7 @@ struct EncodeCall {
 
 int encode_on_device(Context& cx, const char* pipeline_c, const void* d_src, const long* shape, unsigned rank, int elem_size,
                      void* d_dst, uint64_t dst_capacity, long* dstlength, int nthreads, hipStream_t stream, long* dstoffset = nullptr,
-                     FrameQuery* fq = nullptr)
+                     FrameQuery* fq = nullptr, CallStamps* stamps = nullptr)
 {
     if (!pipeline_c || !d_src || !shape || !d_dst || !dstlength) return 1;
     if (dstoffset) *dstoffset = 0;
@@ -1439,7 +1492,7 @@ int encode_on_device(Context& cx, const char* pipeline_c, const void* d_src, con
 
     LaneLease lanes;                    // (given back after the drain)
     DrainOnExit drain{stream, &cx.pending, cx.side, &lanes};
-    EncodeCall c(cx, stream, std::move(pipe), std::move(dims), len, elem_size, d_src, d_dst, dst_capacity, dstoffset, fq, &lanes);
+    EncodeCall c(cx, stream, std::move(pipe), std::move(dims), len, elem_size, d_src, d_dst, dst_capacity, dstoffset, fq, &lanes, stamps);
     for (size_t si = 0; si < c.pipe.stages.size(); ++si) {
         int rc = 0;
         switch (c.pipe.stages[si].kind) {
@@ -2529,10 +2582,11 @@ int encode_device(const char* pipeline, const void* d_src, const long* shape, un
                   long* dstoffset, long* dstlength, int nthreads, void* hip_stream, bool at, FrameQuery* fq = nullptr, int* count = nullptr)
 {
     if ((at && !dstoffset) || (fq && (fq->every <= 0 || !fq->offsets || !count))) return 1;
+    StampScope stamps;                  // (in front of the lease: its last stamp is taken when the context has gone back)
     ContextLease lease;
     if (!lease.ctx) { std::fprintf(stderr, "[sqeazy]\t no usable HIP device\n"); return 1; }
     const int rc = encode_on_device(*lease.ctx, pipeline, d_src, shape, rank, elem_size, d_dst, (uint64_t)std::max(dst_capacity, 0l), dstlength,
-                                    nthreads, static_cast<hipStream_t>(hip_stream), dstoffset, fq);
+                                    nthreads, static_cast<hipStream_t>(hip_stream), dstoffset, fq, stamps.get());
     if (fq) *count = fq->count;
     return rc;
 }
@@ -2983,6 +3037,10 @@ int SQYAMD_Set_Option(const char* name, long value)
     else if (o == &g_opt.stage_lanes) { if (value < 0 || value > 2) return 1; }
     else if (o == &g_opt.lane_calls || o == &g_opt.lane_backlog_fallbacks || o == &g_opt.lane_blocked_fallbacks) { if (value != 0) return 1; }
     else if (o == &g_opt.parse_lanes) { if (value < 1 || value > sqy::LanePicker::kMaxLanes) return 1; }
+    else if (o == &g_opt.call_stamps) {
+        if (value != 0 && value != 1) return 1;
+        if (value) { std::lock_guard<std::mutex> lock(g_stamps_mu); g_stamps.clear(); g_stamps_next = 0; }      // switching on starts a new record
+    }
     else if (value != 0 && value != 1) return 1;
     o->store(value);
     return 0;
@@ -2992,6 +3050,21 @@ long SQYAMD_Get_Option(const char* name)
 {
     std::atomic<long>* o = g_opt.find(name);
     return o ? o->load() : -1;
+}
+
+long SQYAMD_Call_Stamps(long* out, long max_records)
+{
+    std::lock_guard<std::mutex> lock(g_stamps_mu);
+    const size_t have = g_stamps.size();
+    if (!out || max_records <= 0) return (long)have;
+    const size_t n = std::min<size_t>(have, (size_t)max_records), first = (have < kStampRing ? 0 : g_stamps_next) + (have - n);
+    for (size_t i = 0; i < n; ++i) {
+        const CallStamps& r = g_stamps[(first + i) % have];
+        long* o = out + i * SQYAMD_CALL_STAMP_FIELDS;
+        o[0] = r.seq; o[1] = r.lane; o[2] = r.thread;
+        for (int k = 0; k < CallStamps::kStamps; ++k) o[3 + k] = r.ns[k];
+    }
+    return (long)n;
 }
 
 void SQYAMD_Release_Workspace(void)
