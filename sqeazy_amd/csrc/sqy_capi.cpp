@@ -625,9 +625,8 @@ struct EncodeCall {
 
     // left for lz4 by the stages in front of it
     struct {
-        const uint32_t* piece_hash = nullptr;   // 16-bit bitswap1: hashes of the 1 KiB pieces of the plane stream (duplicate-chunk search)
-        bool inplace = false;                   // frames in place: chunk k of the plane stream sits at d_dst + t0 + 11 + k * in_stride
-        uint64_t t0 = 0, in_stride = 0;
+        sqy::Lz4DedupeLayout dedupe;            // 16-bit bitswap1: ws->dedupe holds hashes of the 1 KiB pieces of the plane stream (total != 0)
+        sqy::Lz4InplacePlan place;              // frames in place: chunk k of the plane stream sits at d_dst + body0 + k * in_stride
         uint32_t* digest = nullptr;             // frames in place: the noise digest (sqy_kernels.h: launch_bitswap1_u16), digest_stride words per chunk
         uint32_t digest_stride = 0;
         bool dedupe_cleared = false;            // the duplicate search's table and the dense list's counter were zeroed in front of the transpose
@@ -761,92 +760,96 @@ struct EncodeCall {
         return 0;
     }
 
+    // The bit-plane transposes of the calls in flight on one device run one after the other (round 4): a stream waits for the
+    // transpose of the call in front before it starts its own.  Two HBM-bound kernels side by side each run at half speed
+    // and end together; chained, the first call's parse starts a whole transpose earlier (bench, four calls in flight:
+    // +3 %; also chaining the duplicate search behind it: -12 %, measured and not kept).  Only a transpose launched within
+    // the last few milliseconds is waited for.  The chain is an edge between streams: by default only streams this library
+    // owns (the host-pointer entry points, the Slabs workers) are chained -- a stream the CALLER brings may carry work this
+    // library knows nothing about (a backlog, a host function that waits for another of the caller's threads), and a hidden
+    // wait on it would couple calls that are documented as independent (round-4 advice).  A caller whose streams carry
+    // nothing but these calls opts in: SQYAMD_Set_Option("transpose_chain_caller_streams", 1) (bench.py does, and says so).
+    // "transpose_chain" = 0 (or SQY_NO_TRANSPOSE_CHAIN=1 when the library is loaded) switches the chain off altogether.
+    // (round 7) A call on the lanes needs none of this: its transpose is on the transpose lane, behind the one in front.
+    struct TransposeChain {
+        int devid = -1;                                     // -1: this call's transpose is not chained
+        std::unique_lock<std::mutex> lock;                  // the device's chain, held from the wait to the record
+    };
+    // in front of the transpose's launch: waits for the transpose in front
+    int chain_wait(TransposeChain& tc, bool inplace)
+    {
+        const bool owned = stream != nullptr && stream == cx.stream;
+        int devid = 0;
+        if ((lanes && lanes->taken()) || !g_opt.transpose_chain.load() || !(owned || g_opt.transpose_chain_caller_streams.load()) || !inplace ||
+            hipGetDevice(&devid) != hipSuccess || devid < 0 || devid >= kMaxDev) return 0;
+        if (!cx.t_done && hipEventCreateWithFlags(&cx.t_done, hipEventDisableTiming) != hipSuccess) return 1;
+        tc.lock = std::unique_lock<std::mutex>(g_tchain_mu[devid]);
+        const auto now = std::chrono::steady_clock::now();
+        if (g_tchain_last[devid] && g_tchain_last[devid] != cx.t_done && now - g_tchain_when[devid] < std::chrono::milliseconds(5))
+            SQY_HIP(hipStreamWaitEvent(stream, g_tchain_last[devid], 0));
+        g_tchain_when[devid] = now;
+        tc.devid = devid;
+        return 0;
+    }
+    // behind it: this call's transpose is the one the next call waits for
+    int chain_record(TransposeChain& tc)
+    {
+        if (tc.devid < 0) return 0;
+        SQY_HIP(hipEventRecord(cx.t_done, stream));
+        g_tchain_last[tc.devid] = cx.t_done;
+        tc.lock.unlock();
+        return 0;
+    }
+
+    // A 16-bit bitswap1 with lz4 right behind it leaves piece hashes for the duplicate-chunk search (bit planes of small values repeat)
+    // and, where lz4_inplace_plan says so, writes the plane stream as frames in place.  Planned and allocated here; then the call takes
+    // its lanes and clears the search's table in front of the transpose (one small kernel instead of three fill dispatches between the
+    // kernels behind it).  Every allocation is in front of take_lanes: the lane mutex is held for launches only.
+    int bitswap1_for_lz4(size_t si, std::unique_lock<std::mutex>& lane_lock)
+    {
+        const sqy::Lz4Params& lz = pipe.stages[si + 1].lz4;
+        const sqy::Lz4EncodeLayout lay = sqy::lz4_encode_layout(lz, cur_len * 2, pipe.nthreads);
+        const uint64_t words = sqy::bitswap1_piece_hash_words(cur, cur, cur_len);         // (0 unless whole tiles, 16-byte aligned input)
+        prep.dedupe = sqy::lz4_dedupe_layout(lay, words);
+        if (!prep.dedupe.total) return 0;
+        if (ws->dedupe.ensure(prep.dedupe.total)) return 1;
+        // room in front for the sqy header (its length depends on the payload size: take the longest)
+        const uint64_t hdr_max = sqy::header_pack(elem_size, false, dims, pipe.name(), (uint64_t)INT_MAX).size() + 2;
+        prep.place = sqy::lz4_inplace_plan(lay, words, si + 2 == pipe.stages.size(), dstoffset != nullptr,
+                                           (unsigned)(reinterpret_cast<uintptr_t>(d_dst) & 15), dst_capacity, hdr_max);
+        if (!prep.place.on) return 0;
+        if (ws->plan.ensure((lay.nchunks + 1) * sizeof(uint32_t))) return 1;
+        const uint32_t dstride = sqy::lz4_noise_digest_words(lz, lay, g_opt.noise_digest.load() != 0, cur_len / 8);      // (round 6)
+        if (dstride && !ws->digest.ensure(lay.nchunks * (uint64_t)dstride * sizeof(uint32_t), true)) {
+            prep.digest = static_cast<uint32_t*>(ws->digest.p);
+            prep.digest_stride = dstride;
+        }
+        if (take_lanes(lane_lock)) return 1;
+        SQY_HIP(sqy::launch_lz4_dedupe_clear(ws->dedupe.p, prep.dedupe, static_cast<uint32_t*>(ws->plan.p), stream));
+        prep.dedupe_cleared = true;
+        if (stamps) stamps->stamp(CallStamps::clear_launched);
+        return 0;
+    }
+
     int bitswap1(size_t si)
     {
         std::unique_lock<std::mutex> lane_lock;             // (held from take_lanes to leave_transpose_lane, or to the first error return)
-        // lz4 right behind: leave piece hashes for its duplicate-chunk detection (bit planes of small values repeat)
-        uint32_t* ph = nullptr;
-        uint64_t gap_chunk = 0;
-        if (cur_elem == 2 && followed_by(si, StageKind::lz4)) {
-            const sqy::Lz4Params& lz = pipe.stages[si + 1].lz4;
-            const uint64_t words = sqy::bitswap1_piece_hash_words(cur, cur, cur_len);         // (0 unless whole tiles, 16-byte aligned input)
-            const uint64_t total = cur_len * 2;
-            const uint64_t chunk = lz.bytes_per_chunk(total);
-            const bool chunked = chunk <= lz.block_bytes() && !(pipe.nthreads == 1 && total > chunk);
-            if (words && chunked && chunk % 1024 == 0 && total > chunk) {
-                const uint64_t nch = (total + chunk - 1) / chunk;
-                const uint64_t ph_bytes = (words * 4 + 63) & ~(uint64_t)63;
-                if (ws->dedupe.ensure(ph_bytes + sqy::lz4_dedupe_work_bytes(nch) + ((nch * 4 + 7) & ~(uint64_t)7) + sqy::lz4_holes_map_bytes(nch, (uint32_t)chunk))) return 1;
-                ph = static_cast<uint32_t*>(ws->dedupe.p);
-                prep.piece_hash = ph;
-                // frames in place: lz4 is the last stage, chunks a power of two, the caller takes the blob where it ends up,
-                // and the destination holds frame headers in front of and end marks behind every chunk
-                if (dstoffset && si + 2 == pipe.stages.size() && (chunk & (chunk - 1)) == 0) {
-                    // room in front for the sqy header (its length depends on the payload size: take the longest)
-                    const uint64_t hdr_max = sqy::header_pack(elem_size, false, dims, pipe.name(), (uint64_t)INT_MAX).size() + 2;
-                    uint64_t t0 = hdr_max;
-                    while ((reinterpret_cast<uintptr_t>(d_dst) + t0 + 11) & 15) ++t0;          // body of chunk 0 on a 16-byte boundary
-                    if (t0 + nch * (chunk + 15) <= dst_capacity) {
-                        gap_chunk = chunk;
-                        prep.t0 = t0;
-                        prep.in_stride = chunk + 15;
-                        prep.inplace = true;
-                        // (one small kernel in front of the transpose instead of three fill dispatches between the kernels behind it)
-                        if (ws->plan.ensure((nch + 1) * sizeof(uint32_t))) return 1;
-                        // the noise digest (round 6): every plane segment a whole number of chunks, liblz4's plain search behind it
-                        // (allocated in front of take_lanes: the lane mutex is held for launches only)
-                        const uint32_t dstride = sqy::lz4_noise_digest_stride((uint32_t)chunk);
-                        if (g_opt.noise_digest.load() && dstride && (cur_len / 8) % chunk == 0 && lz.accel >= 0 &&
-                            !ws->digest.ensure(nch * (uint64_t)dstride * sizeof(uint32_t), true)) {
-                            prep.digest = static_cast<uint32_t*>(ws->digest.p);
-                            prep.digest_stride = dstride;
-                        }
-                        if (take_lanes(lane_lock)) return 1;
-                        SQY_HIP(sqy::launch_lz4_dedupe_clear(static_cast<uint8_t*>(ws->dedupe.p) + ph_bytes, nch, static_cast<uint32_t*>(ws->plan.p), stream));
-                        prep.dedupe_cleared = true;
-                        if (stamps) stamps->stamp(CallStamps::clear_launched);
-                    }
-                }
-            }
-        }
-        uint8_t* out = gap_chunk ? static_cast<uint8_t*>(d_dst) + prep.t0 + 11 : next_buf(cur_len * cur_elem);
+        if (cur_elem == 2 && followed_by(si, StageKind::lz4) && bitswap1_for_lz4(si, lane_lock)) return 1;
+        const bool inplace = prep.place.on;
+        uint8_t* out = inplace ? static_cast<uint8_t*>(d_dst) + prep.place.body0 : next_buf(cur_len * cur_elem);
         if (!out) return 1;
-        if (!gap_chunk && ph && (reinterpret_cast<uintptr_t>(out) & 15)) { ph = nullptr; prep.piece_hash = nullptr; }
-        // The bit-plane transposes of the calls in flight on one device run one after the other (round 4): a stream waits for the
-        // transpose of the call in front before it starts its own.  Two HBM-bound kernels side by side each run at half speed
-        // and end together; chained, the first call's parse starts a whole transpose earlier (bench, four calls in flight:
-        // +3 %; also chaining the duplicate search behind it: -12 %, measured and not kept).  Only a transpose launched within
-        // the last few milliseconds is waited for.  The chain is an edge between streams: by default only streams this library
-        // owns (the host-pointer entry points, the Slabs workers) are chained -- a stream the CALLER brings may carry work this
-        // library knows nothing about (a backlog, a host function that waits for another of the caller's threads), and a hidden
-        // wait on it would couple calls that are documented as independent (round-4 advice).  A caller whose streams carry
-        // nothing but these calls opts in: SQYAMD_Set_Option("transpose_chain_caller_streams", 1) (bench.py does, and says so).
-        // "transpose_chain" = 0 (or SQY_NO_TRANSPOSE_CHAIN=1 when the library is loaded) switches the chain off altogether.
-        // (round 7) A call on the lanes needs none of this: its transpose is on the transpose lane, behind the one in front.
+        if (!inplace && (reinterpret_cast<uintptr_t>(out) & 15)) prep.dedupe = sqy::Lz4DedupeLayout();     // (no piece hashes into such a buffer)
+        uint32_t* ph = prep.dedupe.total ? static_cast<uint32_t*>(ws->dedupe.p) : nullptr;
         const bool on_lanes = lanes && lanes->taken();
-        const bool owned = stream != nullptr && stream == cx.stream;
-        int devid = 0;
-        const bool chain = !on_lanes && g_opt.transpose_chain.load() && (owned || g_opt.transpose_chain_caller_streams.load()) && gap_chunk &&
-                           hipGetDevice(&devid) == hipSuccess && devid >= 0 && devid < kMaxDev;
-        std::unique_lock<std::mutex> tlock;
-        if (chain) {
-            if (!cx.t_done && hipEventCreateWithFlags(&cx.t_done, hipEventDisableTiming) != hipSuccess) return 1;
-            tlock = std::unique_lock<std::mutex>(g_tchain_mu[devid]);
-            const auto now = std::chrono::steady_clock::now();
-            if (g_tchain_last[devid] && g_tchain_last[devid] != cx.t_done && now - g_tchain_when[devid] < std::chrono::milliseconds(5))
-                SQY_HIP(hipStreamWaitEvent(stream, g_tchain_last[devid], 0));
-            g_tchain_when[devid] = now;
-        }
+        TransposeChain tc;
+        if (chain_wait(tc, inplace)) return 1;
         if (cur_elem == 2)
             SQY_TIMED("bitswap1_u16", sqy::launch_bitswap1_u16(reinterpret_cast<const uint16_t*>(cur), reinterpret_cast<uint16_t*>(out), cur_len, stream, ph,
-                                                               (uint32_t)gap_chunk, side.p, side.w, side.X, gap_chunk ? prep.digest : nullptr, prep.digest_stride));
+                                                               inplace ? (uint32_t)prep.place.chunk : 0, side.p, side.w, side.X, inplace ? prep.digest : nullptr,
+                                                               prep.digest_stride));
         else
             SQY_TIMED("bitswap1_u8", sqy::launch_bitswap1_u8(cur, out, cur_len, stream));
-        if (chain) {
-            SQY_HIP(hipEventRecord(cx.t_done, stream));
-            g_tchain_last[devid] = cx.t_done;
-            tlock.unlock();
-        }
+        if (chain_record(tc)) return 1;
         if (stamps) stamps->stamp(CallStamps::transpose_launched);
         if (on_lanes && leave_transpose_lane(lane_lock)) return 1;
         side = DiffSide();                      // (consumed: a later bitswap1 of the pipeline reads its plain input)
@@ -1039,11 +1042,8 @@ struct EncodeCall {
         const uint64_t frame_bytes = per_frame * (uint64_t)cur_elem;
         bool fused = false;
         if (followed_by(si, StageKind::lz4) && frame_bytes) {
-            const sqy::Lz4Params& lz = pipe.stages[si + 1].lz4;
-            const uint64_t total = cur_len * (uint64_t)cur_elem;
-            const uint64_t chunk = lz.bytes_per_chunk(total);
-            fused = chunk && frame_bytes % chunk == 0 && chunk <= lz.block_bytes() &&
-                    !(pipe.nthreads == 1 && total > chunk);               // (block-linked frames read a gathered copy)
+            const sqy::Lz4EncodeLayout lay = sqy::lz4_encode_layout(pipe.stages[si + 1].lz4, cur_len * (uint64_t)cur_elem, pipe.nthreads);
+            fused = lay.chunked() && frame_bytes % lay.chunk == 0;        // (block-linked frames read a gathered copy)
         }
         if (fused) {
             prep.frame_map = d_map;
@@ -1108,19 +1108,16 @@ struct EncodeCall {
     int lz4_stage(size_t si)
     {
         const sqy::Lz4Params& lz = pipe.stages[si].lz4;
-        // liblz4's acceleration: LZ4F turns a negative compression level -k into acceleration k + 1 (lz4frame.c, LZ4F_compressBlock),
-        // LZ4_compress_fast_continue caps it at 65537 (lz4.c, LZ4_ACCELERATION_MAX)
-        const uint32_t accel = lz.accel < 0 ? (uint32_t)std::min<int64_t>(1 - (int64_t)lz.accel, 65537) : 1u;
         lz4.block_id = lz.block_id;
         lz4.total = cur_len * (uint64_t)cur_elem;
-        lz4.chunk = lz4.total ? lz.bytes_per_chunk(lz4.total) : 1;
-        lz4.nchunks = lz4.total ? (lz4.total + lz4.chunk - 1) / lz4.chunk : 0;
-        const bool serial = pipe.nthreads == 1 && lz4.nchunks > 1;          // lz4.hpp:227-234: one block-linked frame
-        if (!serial && lz4.chunk <= lz.block_bytes()) {
-            if (lz4_chunked(si, accel)) return 1;
+        const sqy::Lz4EncodeLayout lay = sqy::lz4_encode_layout(lz, lz4.total, pipe.nthreads);
+        lz4.chunk = lay.chunk;
+        lz4.nchunks = lay.nchunks;
+        if (lay.chunked()) {
+            if (lz4_chunked(lay.accel)) return 1;
             if (lz4.inplace_done) return 0;
-        } else if (lz4.total) {
-            if (lz4_linked(si, serial, accel)) return 1;
+        } else if (lz4_linked(si, lay.kind == sqy::Lz4LayoutKind::serial, lay.accel)) {
+            return 1;
         }
         SQY_TIMED("lz4_frame_scan", sqy::launch_lz4_frame_scan(static_cast<uint32_t*>(ws->csize.p), lz4.nchunks, lz4.total, (uint32_t)lz4.chunk,
                                                                static_cast<uint64_t*>(ws->frame_off.p), stream, lz4.blocks, lz4.dup_of, lz4.tail_info));
@@ -1130,40 +1127,35 @@ struct EncodeCall {
 
     // chunked layout, one LZ4 block per frame: every chunk is independent.  The duplicate search, the parse and the dense pass behind it --
     // or, frames in place with a header short enough, everything up to the finished blob (lz4_inplace_finish)
-    int lz4_chunked(size_t si, uint32_t accel)
+    int lz4_chunked(uint32_t accel)
     {
         lz4.stride = (lz4.chunk + 15) & ~(uint64_t)15;
         if (ws->lz4_scratch.ensure(std::max<uint64_t>(lz4.nchunks * lz4.stride, 16))) return 1;
         if (ws->csize.ensure(std::max<uint64_t>(lz4.nchunks, 1) * sizeof(uint32_t))) return 1;
         if (ws->frame_off.ensure((lz4.nchunks + 1 + 4) * sizeof(uint64_t))) return 1;
-        if (prep.inplace) lz4.tail_info = static_cast<uint64_t*>(ws->frame_off.p) + lz4.nchunks + 1;
+        if (prep.place.on) lz4.tail_info = static_cast<uint64_t*>(ws->frame_off.p) + lz4.nchunks + 1;
         sqy::Lz4DedupeArgs dedupe_args;              // frames in place: the duplicate decision per chunk is made inside the parse kernel
         bool fused_dedupe = false;
-        if (prep.piece_hash && si > 0 && pipe.stages[si - 1].kind == StageKind::bitswap1) {
-            const uint64_t words = sqy::bitswap1_piece_hash_words(cur, cur, cur_len);     // (same count as when they were made)
-            const uint64_t ph_bytes = (words * 4 + 63) & ~(uint64_t)63;
-            uint8_t* base = static_cast<uint8_t*>(ws->dedupe.p) + ph_bytes;
-            uint32_t* d_dup = reinterpret_cast<uint32_t*>(base + sqy::lz4_dedupe_work_bytes(lz4.nchunks));
-            // frames in place: which 1 KiB pieces of the plane stream the transpose left unwritten (all zero)
-            uint64_t* holes = prep.inplace ? reinterpret_cast<uint64_t*>(reinterpret_cast<uint8_t*>(d_dup) + ((lz4.nchunks * 4 + 7) & ~(uint64_t)7)) : nullptr;
+        if (prep.dedupe.total) {                     // (left by the bitswap1 directly in front: lz4 is a pipeline's one sink, Pipeline::supported)
             ProfScope ps("lz4_dedupe", stream, pend);
             // frames in place (acceleration 1): only the key table is built here, the decision per chunk (byte compare, hole fill)
-            // is the first thing the chunk's parse wavefront does (lz4_chunk_dedupe)
-            fused_dedupe = prep.inplace && accel == 1;
-            SQY_HIP(sqy::launch_lz4_dedupe(cur, lz4.total, (uint32_t)lz4.chunk, prep.piece_hash, base, d_dup, stream, prep.in_stride, holes,
+            // is the first thing the chunk's parse wavefront does (lz4_chunk_dedupe).  (holes: which 1 KiB pieces of the plane stream the
+            // transpose left unwritten, all zero)
+            fused_dedupe = prep.place.on && accel == 1;
+            SQY_HIP(sqy::launch_lz4_dedupe(cur, lz4.total, (uint32_t)lz4.chunk, ws->dedupe.p, prep.dedupe, stream, prep.place.in_stride, prep.place.on,
                                            prep.dedupe_cleared, fused_dedupe ? &dedupe_args : nullptr));
-            lz4.dup_of = d_dup;
+            lz4.dup_of = reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(ws->dedupe.p) + prep.dedupe.dup_at);
             if (fused_dedupe && prep.digest) { dedupe_args.digest = prep.digest; dedupe_args.digest_stride = prep.digest_stride; }
         }
         if (ws->plan.ensure((lz4.nchunks + 1) * sizeof(uint32_t))) return 1;
         uint32_t* d_redo = static_cast<uint32_t*>(ws->plan.p);       // chunks the first pass leaves to the dense batches
         SQY_TIMED("lz4_chunks", sqy::launch_lz4_chunks(cur, lz4.total, (uint32_t)lz4.chunk, static_cast<uint8_t*>(ws->lz4_scratch.p), lz4.stride,
                                                        static_cast<uint32_t*>(ws->csize.p), lz4.nchunks, stream, prep.frame_map, prep.frame_bytes, d_redo,
-                                                       fused_dedupe ? nullptr : lz4.dup_of, prep.in_stride, accel, prep.dedupe_cleared,
+                                                       fused_dedupe ? nullptr : lz4.dup_of, prep.place.in_stride, accel, prep.dedupe_cleared,
                                                        fused_dedupe ? &dedupe_args : nullptr));
         std::string hdr_prefix, hdr_suffix;
-        if (prep.inplace && !(fq && fq->every > 0)) sqy::header_pack_parts(elem_size, false, dims, pipe.name(), &hdr_prefix, &hdr_suffix);
-        if (prep.inplace && !hdr_prefix.empty() && hdr_prefix.size() + hdr_suffix.size() <= sqy::kLz4InplaceHeaderTextMax)
+        if (prep.place.on && !(fq && fq->every > 0)) sqy::header_pack_parts(elem_size, false, dims, pipe.name(), &hdr_prefix, &hdr_suffix);
+        if (prep.place.on && !hdr_prefix.empty() && hdr_prefix.size() + hdr_suffix.size() <= sqy::kLz4InplaceHeaderTextMax)
             return lz4_inplace_finish(d_redo, hdr_prefix, hdr_suffix);
         SQY_HIP(hipMemcpyAsync(ws->pinned, d_redo, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
         SQY_HIP(hipStreamSynchronize(stream));
@@ -1176,7 +1168,7 @@ struct EncodeCall {
     {
         SQY_TIMED("lz4_chunks_dense", sqy::launch_lz4_chunks_dense(cur, lz4.total, (uint32_t)lz4.chunk, static_cast<uint8_t*>(ws->lz4_scratch.p), lz4.stride,
                                                                    static_cast<uint32_t*>(ws->csize.p), d_redo, n_redo, stream, prep.frame_map, prep.frame_bytes,
-                                                                   prep.in_stride));
+                                                                   prep.place.in_stride));
         return 0;
     }
 
@@ -1201,9 +1193,9 @@ struct EncodeCall {
             if (!fused && scan_too)
                 SQY_TIMED("lz4_frame_scan", sqy::launch_lz4_frame_scan(static_cast<uint32_t*>(ws->csize.p), lz4.nchunks, lz4.total, (uint32_t)lz4.chunk,
                                                                        static_cast<uint64_t*>(ws->frame_off.p), stream, nullptr, lz4.dup_of, lz4.tail_info, guard,
-                                                                       outb + prep.t0 + 11, prep.in_stride, fd.bd, fd.hc));
+                                                                       outb + prep.place.body0, prep.place.in_stride, fd.bd, fd.hc));
             auto with_args = [&](auto launch) {
-                return launch(outb, prep.t0, prep.in_stride, lz4.total, (uint32_t)lz4.chunk, lz4.nchunks, static_cast<uint8_t*>(ws->lz4_scratch.p), lz4.stride,
+                return launch(outb, prep.place.t0, prep.place.in_stride, lz4.total, (uint32_t)lz4.chunk, lz4.nchunks, static_cast<uint8_t*>(ws->lz4_scratch.p), lz4.stride,
                               static_cast<uint32_t*>(ws->csize.p), static_cast<uint64_t*>(ws->frame_off.p), lz4.dup_of, lz4.tail_info, fd.bd, fd.hc,
                               hdr_prefix.data(), (uint32_t)hdr_prefix.size(), hdr_suffix.data(), (uint32_t)hdr_suffix.size(), (uint32_t)elem_size, guard,
                               const_cast<uint64_t*>(record), stream);
@@ -1261,11 +1253,9 @@ struct EncodeCall {
         // a table rebuilt by parsing the >= 64 KiB in front of it, the tables are checked against what the block in
         // front really left, and what fails the check is parsed again in order (sqy_kernels.h: Lz4SpecArgs).  Twice the
         // parse work on thousands of wavefronts instead of one: worth it when the frame walks would leave the chip empty.
-        uint64_t longest = 0;
-        for (uint64_t f = 0; f < nframes; ++f) longest = std::max<uint64_t>(longest, plan.frame_first[f + 1] - plan.frame_first[f]);
         // measurement / test knob: SQY_NO_BLOCK_PARALLEL (the frame walk of rounds 2-3)
         // (without room for the tables -- 32 KiB per block -- the walk, which needs none)
-        const bool spec_wanted = g_opt.block_parallel.load() != 0 && longest >= 3 && nframes < 1024;
+        const bool spec_wanted = g_opt.block_parallel.load() != 0 && sqy::lz4_spec_wanted(plan);
         const bool spec_room = spec_wanted && !ws->spec.ensure(nblocks * sqy::kLz4SpecTableWords * sizeof(uint32_t) + 3 * nblocks * sizeof(uint32_t), true);
         if (spec_wanted && !spec_room) {
             // (round-4 advice) said once, not per call: the result is the same, the rate is not
@@ -1292,19 +1282,12 @@ struct EncodeCall {
     // started from the table the block in front really left.  Returns with the stream synchronised.
     int lz4_linked_spec(const sqy::Lz4Plan& plan, const sqy::Lz4Block* d_blocks, uint32_t accel)
     {
-        const uint64_t nblocks = plan.blocks.size(), nframes = plan.frame_first.size() - 1;
+        const uint64_t nblocks = plan.blocks.size();
         const uint64_t list_bytes = nblocks * sizeof(uint32_t);
         // SQY_BLOCK_PARALLEL_WARMUP = bytes of warm-up in front of a block (default and liblz4's reach: 64 KiB; less makes the guess fail
         // more often -- the result stays exact, the blocks that fail are parsed again)
-        const uint64_t warmup = (uint64_t)g_opt.block_parallel_warmup.load();
-        std::vector<uint32_t> wfirst(nblocks), wlast(nblocks), ok(nblocks);
-        for (uint64_t f = 0; f < nframes; ++f)
-            for (uint32_t k = plan.frame_first[f]; k < plan.frame_first[f + 1]; ++k) {
-                uint32_t j = k;
-                uint64_t have = 0;
-                while (j > plan.frame_first[f] && have < warmup) { --j; have += plan.blocks[j].n; }
-                wfirst[k] = j; wlast[k] = (uint32_t)k;
-            }
+        std::vector<uint32_t> wfirst, wlast, ok(nblocks);
+        sqy::lz4_warmup_windows(plan, (uint64_t)g_opt.block_parallel_warmup.load(), &wfirst, &wlast);
         sqy::Lz4SpecArgs sa;
         sa.tables = static_cast<uint32_t*>(ws->spec.p);
         uint32_t* d_wfirst = sa.tables + nblocks * sqy::kLz4SpecTableWords;
@@ -1325,15 +1308,8 @@ struct EncodeCall {
             // plane of a quantised stack fails as one run of 511 blocks, seconds of work: sixteen launches of a fraction of a
             // second instead of one kernel that runs for seconds; and the caller is told, once, what layout to ask for.
             constexpr uint64_t kRunMax = 32;
-            uint64_t nruns = 0, longest_run = 0;
-            for (uint64_t k = 0; k < nblocks; ++k) {
-                if (ok[k]) continue;
-                uint64_t e = k;
-                while (e + 1 < nblocks && !ok[e + 1] && !(plan.blocks[e + 1].flags & 1u)) ++e;
-                longest_run = std::max(longest_run, e - k + 1);
-                wfirst[nruns] = (uint32_t)k; wlast[nruns] = (uint32_t)std::min(e, k + kRunMax - 1); ++nruns;
-                k = e;
-            }
+            const sqy::Lz4RedoRuns runs = sqy::lz4_redo_runs(plan, ok, kRunMax, &wfirst, &wlast);
+            const uint64_t nruns = runs.nruns, longest_run = runs.longest;
             if (longest_run > 4 * kRunMax) {
                 static std::atomic<bool> told{false};
                 if (!told.exchange(true))
@@ -1365,90 +1341,89 @@ struct EncodeCall {
         }
     }
 
-    // The payload's size, the sqy header (written after encoding, as the reference rewrites it: dynamic_pipeline.hpp:599-612), the frame
-    // offsets asked for, and the blob put together in d_dst
-    int finish(long* dstlength)
+    // frames in place, not finished on the device: what the frame scan left about the run of stored chunks that ends the payload
+    struct StoredTail { uint64_t j = 0, head_bytes = 0, raw_head = 0; };
+
+    // the payload's size (known already when the device finished the blob)
+    int payload_size(uint64_t* payload_bytes, StoredTail* tail)
     {
-        // ---- payload size ----
-        uint64_t payload_bytes = lz4.payload_bytes, tail_j = 0, tail_head_bytes = 0, tail_raw_head = 0;   // (known when the device finished the blob)
+        *payload_bytes = lz4.payload_bytes;
         if (!lz4.on) {
-            payload_bytes = cur_len * (uint64_t)cur_elem;
+            *payload_bytes = cur_len * (uint64_t)cur_elem;
         } else if (lz4.nchunks == 0) {
-            payload_bytes = 7 + 4;                         // empty input: frame header + end mark
-        } else if (prep.inplace && !lz4.inplace_done) {
+            *payload_bytes = 7 + 4;                        // empty input: frame header + end mark
+        } else if (prep.place.on && !lz4.inplace_done) {
             SQY_HIP(hipMemcpyAsync(ws->pinned, lz4.tail_info, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
             SQY_HIP(hipStreamSynchronize(stream));
             const uint64_t* ti = static_cast<const uint64_t*>(ws->pinned);
-            tail_j = ti[0]; tail_head_bytes = ti[1]; tail_raw_head = ti[2]; payload_bytes = ti[3];
+            tail->j = ti[0]; tail->head_bytes = ti[1]; tail->raw_head = ti[2]; *payload_bytes = ti[3];
         } else if (!lz4.inplace_done) {
             SQY_HIP(hipMemcpyAsync(ws->pinned, static_cast<uint64_t*>(ws->frame_off.p) + lz4.nchunks, sizeof(uint64_t),
                                    hipMemcpyDeviceToHost, stream));
             SQY_HIP(hipStreamSynchronize(stream));
-            payload_bytes = *static_cast<uint64_t*>(ws->pinned);
+            *payload_bytes = *static_cast<uint64_t*>(ws->pinned);
         }
-        if (lz4.on && payload_bytes > (uint64_t)INT_MAX) {
+        if (lz4.on && *payload_bytes > (uint64_t)INT_MAX) {
             // encode_parallel sums the chunk sizes into an `int` and rejects the result (lz4_utils.hpp:264-273)
             std::fprintf(stderr, "[sqeazy]\t lz4: %llu payload bytes overflow the reference's int byte count\n",
-                         (unsigned long long)payload_bytes);
+                         (unsigned long long)*payload_bytes);
             return 1;
         }
-        // the blob is complete (the stream synchronised): it lies at d_dst + at
-        auto done = [&](uint64_t at, uint64_t bytes) -> int {
-            if (lanes) lanes->complete = true;
-            if (g_prof_on.load()) prof_collect(*pend);
-            if (dstoffset) *dstoffset = (long)at;
-            *dstlength = (long)bytes;
-            return 0;
-        };
-        if (lz4.inplace_done) return done(lz4.blob_at, lz4.blob_bytes);
+        return 0;
+    }
 
-        // ---- header ----
-        const std::string hdr = sqy::header_pack(elem_size, false, dims, pipe.name(), payload_bytes);
-        if (fq && fq->every > 0) {
-            if (!lz4.on || lz4.blocks || !fq->offsets) { std::fprintf(stderr, "[sqeazy]\t frame offsets: the payload is not one LZ4 frame per chunk\n"); return 1; }
-            const uint64_t cnt = (lz4.nchunks + (uint64_t)fq->every - 1) / (uint64_t)fq->every;
-            if (cnt + 1 > (uint64_t)std::max(fq->max_entries, 0)) { std::fprintf(stderr, "[sqeazy]\t frame offsets: %llu entries do not fit\n", (unsigned long long)(cnt + 1)); return 1; }
-            std::vector<uint64_t> fo(cnt + 1, 0);
-            if (cnt)
-                SQY_HIP(hipMemcpy2DAsync(fo.data(), sizeof(uint64_t), ws->frame_off.p, (size_t)fq->every * sizeof(uint64_t), sizeof(uint64_t), cnt,
-                                         hipMemcpyDeviceToHost, stream));
-            SQY_HIP(hipStreamSynchronize(stream));
-            for (uint64_t i = 0; i < cnt; ++i) fq->offsets[i] = (long)(fo[i] + hdr.size());
-            fq->offsets[cnt] = (long)(hdr.size() + payload_bytes);
-            fq->count = (int)cnt;
-        }
-        const uint64_t blob_bytes = hdr.size() + payload_bytes;
-        if (blob_bytes > dst_capacity) {
-            std::fprintf(stderr, "[sqeazy]\t destination buffer too small (%llu > %llu bytes)\n", (unsigned long long)blob_bytes,
-                         (unsigned long long)dst_capacity);
-            return 1;
-        }
+    // where every fq->every-th LZ4 frame starts in the blob
+    int frame_offsets(uint64_t hdr_bytes, uint64_t payload_bytes)
+    {
+        if (!lz4.on || lz4.blocks || !fq->offsets) { std::fprintf(stderr, "[sqeazy]\t frame offsets: the payload is not one LZ4 frame per chunk\n"); return 1; }
+        const uint64_t cnt = (lz4.nchunks + (uint64_t)fq->every - 1) / (uint64_t)fq->every;
+        if (cnt + 1 > (uint64_t)std::max(fq->max_entries, 0)) { std::fprintf(stderr, "[sqeazy]\t frame offsets: %llu entries do not fit\n", (unsigned long long)(cnt + 1)); return 1; }
+        std::vector<uint64_t> fo(cnt + 1, 0);
+        if (cnt)
+            SQY_HIP(hipMemcpy2DAsync(fo.data(), sizeof(uint64_t), ws->frame_off.p, (size_t)fq->every * sizeof(uint64_t), sizeof(uint64_t), cnt,
+                                     hipMemcpyDeviceToHost, stream));
+        SQY_HIP(hipStreamSynchronize(stream));
+        for (uint64_t i = 0; i < cnt; ++i) fq->offsets[i] = (long)(fo[i] + hdr_bytes);
+        fq->offsets[cnt] = (long)(hdr_bytes + payload_bytes);
+        fq->count = (int)cnt;
+        return 0;
+    }
+
+    // Frames in place, put together from the host (a frame-offset query, or header text too long for lz4_inplace_finish): the run of
+    // stored chunks j.. that ends the payload stays where the bit-plane transpose put it; frames 0..j-1 are gathered so that they end
+    // where frame j begins, the header goes in front of them.  *blob_at: where the blob then begins
+    int assemble_inplace(const std::string& hdr, const StoredTail& tail, uint64_t* blob_at)
+    {
         uint8_t* out = static_cast<uint8_t*>(d_dst);
         const Lz4Descriptor fd = lz4_descriptor(lz4.block_id);
-        if (prep.inplace) {
-            // the run of stored chunks j.. that ends the payload stays where the bit-plane transpose put it; frames 0..j-1 are
-            // gathered so that they end where frame j begins, the header goes in front of them
-            const uint64_t frame_j = prep.t0 + tail_j * prep.in_stride;
-            if (tail_head_bytes + hdr.size() > frame_j) { std::fprintf(stderr, "[sqeazy]\t internal error: frames in place overlap the header\n"); return 1; }
-            const uint64_t payload_at = frame_j - tail_head_bytes, blob_at = payload_at - hdr.size();
-            uint8_t* body0 = out + prep.t0 + 11;
-            SQY_TIMED("lz4_tail_marks", sqy::launch_lz4_tail_marks(body0, prep.in_stride, lz4.total, (uint32_t)lz4.chunk, lz4.nchunks, fd.bd, fd.hc, lz4.tail_info, stream));
-            if (tail_raw_head) {
-                SQY_TIMED("lz4_stash_raw", sqy::launch_lz4_stash_raw(body0, prep.in_stride, lz4.total, (uint32_t)lz4.chunk, static_cast<uint8_t*>(ws->lz4_scratch.p), lz4.stride,
-                                                                     static_cast<uint32_t*>(ws->csize.p), lz4.dup_of, tail_j, stream));
-            }
-            if (tail_j) {
-                SQY_TIMED("lz4_frame_gather", sqy::launch_lz4_frame_gather(body0, lz4.total, (uint32_t)lz4.chunk, static_cast<uint8_t*>(ws->lz4_scratch.p), lz4.stride,
-                                                                           static_cast<uint32_t*>(ws->csize.p), static_cast<uint64_t*>(ws->frame_off.p), out + payload_at, fd.bd, fd.hc,
-                                                                           tail_j, stream, nullptr, 0, nullptr, lz4.dup_of, prep.in_stride, tail_raw_head != 0));
-            }
-            SQY_HIP(hipMemcpyAsync(out + blob_at, hdr.data(), hdr.size(), hipMemcpyHostToDevice, stream));
-            SQY_HIP(hipStreamSynchronize(stream));
-            return done(blob_at, blob_bytes);
+        const uint64_t frame_j = prep.place.t0 + tail.j * prep.place.in_stride;
+        if (tail.head_bytes + hdr.size() > frame_j) { std::fprintf(stderr, "[sqeazy]\t internal error: frames in place overlap the header\n"); return 1; }
+        const uint64_t payload_at = frame_j - tail.head_bytes;
+        *blob_at = payload_at - hdr.size();
+        uint8_t* body0 = out + prep.place.body0;
+        SQY_TIMED("lz4_tail_marks", sqy::launch_lz4_tail_marks(body0, prep.place.in_stride, lz4.total, (uint32_t)lz4.chunk, lz4.nchunks, fd.bd, fd.hc, lz4.tail_info, stream));
+        if (tail.raw_head) {
+            SQY_TIMED("lz4_stash_raw", sqy::launch_lz4_stash_raw(body0, prep.place.in_stride, lz4.total, (uint32_t)lz4.chunk, static_cast<uint8_t*>(ws->lz4_scratch.p), lz4.stride,
+                                                                 static_cast<uint32_t*>(ws->csize.p), lz4.dup_of, tail.j, stream));
         }
+        if (tail.j) {
+            SQY_TIMED("lz4_frame_gather", sqy::launch_lz4_frame_gather(body0, lz4.total, (uint32_t)lz4.chunk, static_cast<uint8_t*>(ws->lz4_scratch.p), lz4.stride,
+                                                                       static_cast<uint32_t*>(ws->csize.p), static_cast<uint64_t*>(ws->frame_off.p), out + payload_at, fd.bd, fd.hc,
+                                                                       tail.j, stream, nullptr, 0, nullptr, lz4.dup_of, prep.place.in_stride, tail.raw_head != 0));
+        }
+        SQY_HIP(hipMemcpyAsync(out + *blob_at, hdr.data(), hdr.size(), hipMemcpyHostToDevice, stream));
+        SQY_HIP(hipStreamSynchronize(stream));
+        return 0;
+    }
+
+    // header and payload from d_dst on
+    int assemble_plain(const std::string& hdr, uint64_t payload_bytes)
+    {
+        uint8_t* out = static_cast<uint8_t*>(d_dst);
+        const Lz4Descriptor fd = lz4_descriptor(lz4.block_id);
         SQY_HIP(hipMemcpyAsync(out, hdr.data(), hdr.size(), hipMemcpyHostToDevice, stream));
         if (lz4.on && lz4.nchunks == 0) {
-            const unsigned char empty[11] = {0x04, 0x22, 0x4D, 0x18, fd.flg, fd.bd, (unsigned char)fd.hc, 0, 0, 0, 0};
+            const unsigned char empty[7 + 4] = {0x04, 0x22, 0x4D, 0x18, fd.flg, fd.bd, (unsigned char)fd.hc, 0, 0, 0, 0};
             SQY_HIP(hipMemcpyAsync(out + hdr.size(), empty, sizeof(empty), hipMemcpyHostToDevice, stream));
         } else if (lz4.on) {
             SQY_TIMED("lz4_frame_gather", sqy::launch_lz4_frame_gather(cur, lz4.total, (uint32_t)lz4.chunk, static_cast<uint8_t*>(ws->lz4_scratch.p), lz4.stride,
@@ -1458,9 +1433,70 @@ struct EncodeCall {
             SQY_TIMED("payload_copy", hipMemcpyAsync(out + hdr.size(), cur, payload_bytes, hipMemcpyDeviceToDevice, stream));
         }
         SQY_HIP(hipStreamSynchronize(stream));
-        return done(0, blob_bytes);
+        return 0;
+    }
+
+    // the blob is complete (the stream synchronised): it lies at d_dst + at
+    int done(uint64_t at, uint64_t bytes, long* dstlength)
+    {
+        if (lanes) lanes->complete = true;
+        if (g_prof_on.load()) prof_collect(*pend);
+        if (dstoffset) *dstoffset = (long)at;
+        *dstlength = (long)bytes;
+        return 0;
+    }
+
+    // The payload's size, the sqy header (written after encoding, as the reference rewrites it: dynamic_pipeline.hpp:599-612), the frame
+    // offsets asked for, and the blob put together in d_dst
+    int finish(long* dstlength)
+    {
+        uint64_t payload_bytes = 0, blob_at = 0;
+        StoredTail tail;
+        if (payload_size(&payload_bytes, &tail)) return 1;
+        if (lz4.inplace_done) return done(lz4.blob_at, lz4.blob_bytes, dstlength);
+        const std::string hdr = sqy::header_pack(elem_size, false, dims, pipe.name(), payload_bytes);
+        if (fq && fq->every > 0 && frame_offsets(hdr.size(), payload_bytes)) return 1;
+        const uint64_t blob_bytes = hdr.size() + payload_bytes;
+        if (blob_bytes > dst_capacity) {
+            std::fprintf(stderr, "[sqeazy]\t destination buffer too small (%llu > %llu bytes)\n", (unsigned long long)blob_bytes,
+                         (unsigned long long)dst_capacity);
+            return 1;
+        }
+        if (prep.place.on ? assemble_inplace(hdr, tail, &blob_at) : assemble_plain(hdr, payload_bytes)) return 1;
+        return done(blob_at, blob_bytes, dstlength);
     }
 };
+
+// A pipeline this library encodes; the reason goes to stderr where the reference would have taken the pipeline
+bool pipeline_admitted(const std::string& pipeline, int elem_size)
+{
+    std::string why;
+    if (Pipeline::supported(pipeline, elem_size, &why)) return true;
+    if (Pipeline::reference_accepts(pipeline)) std::fprintf(stderr, "[sqeazy]\t pipeline %s: %s\n", pipeline.c_str(), why.c_str());
+    return false;
+}
+
+// What every encode call checks before it touches the device: the pipeline, the volume's size against the reference's int counts, the
+// background filters' geometry.  0: *pipe, *dims and *len are the call's
+int admit_encode(const std::string& pipeline, const long* shape, unsigned rank, int elem_size, int nthreads, Pipeline* pipe, std::vector<uint64_t>* dims,
+                 uint64_t* len)
+{
+    if (!pipeline_admitted(pipeline, elem_size)) return 1;
+    *pipe = Pipeline::from_string(pipeline, elem_size);
+    if (pipe->stages.empty()) {
+        std::fprintf(stderr, "[sqeazy]\t received %spipeline of size 0, cannot encode buffer\n", pipe->name().c_str());
+        return 1;
+    }
+    pipe->set_n_threads(nthreads);
+    *len = voxel_count(shape, rank);
+    if (*len == 0) { std::fprintf(stderr, "[sqeazy]\t non-positive extent in shape\n"); return 1; }
+    if (*len >= ((uint64_t)1 << 31)) {
+        std::fprintf(stderr, "[sqeazy]\t %llu+ voxels in one call overflow the reference's int voxel count; encode z-slabs\n", (unsigned long long)*len);
+        return 1;
+    }
+    dims->assign(shape, shape + rank);
+    return background_geometry_ok(*pipe, *dims) ? 0 : 1;
+}
 
 int encode_on_device(Context& cx, const char* pipeline_c, const void* d_src, const long* shape, unsigned rank, int elem_size,
                      void* d_dst, uint64_t dst_capacity, long* dstlength, int nthreads, hipStream_t stream, long* dstoffset = nullptr,
@@ -1468,27 +1504,10 @@ int encode_on_device(Context& cx, const char* pipeline_c, const void* d_src, con
 {
     if (!pipeline_c || !d_src || !shape || !d_dst || !dstlength) return 1;
     if (dstoffset) *dstoffset = 0;
-    const std::string pipeline(pipeline_c);
-    std::string why;
-    if (!Pipeline::supported(pipeline, elem_size, &why)) {
-        if (Pipeline::reference_accepts(pipeline))
-            std::fprintf(stderr, "[sqeazy]\t pipeline %s: %s\n", pipeline.c_str(), why.c_str());
-        return 1;
-    }
-    Pipeline pipe = Pipeline::from_string(pipeline, elem_size);
-    if (pipe.stages.empty()) {
-        std::fprintf(stderr, "[sqeazy]\t received %spipeline of size 0, cannot encode buffer\n", pipe.name().c_str());
-        return 1;
-    }
-    pipe.set_n_threads(nthreads);
-    const uint64_t len = voxel_count(shape, rank);
-    if (len == 0) { std::fprintf(stderr, "[sqeazy]\t non-positive extent in shape\n"); return 1; }
-    if (len >= ((uint64_t)1 << 31)) {
-        std::fprintf(stderr, "[sqeazy]\t %llu+ voxels in one call overflow the reference's int voxel count; encode z-slabs\n", (unsigned long long)len);
-        return 1;
-    }
-    std::vector<uint64_t> dims(shape, shape + rank);
-    if (!background_geometry_ok(pipe, dims)) return 1;
+    Pipeline pipe;
+    std::vector<uint64_t> dims;
+    uint64_t len = 0;
+    if (admit_encode(pipeline_c, shape, rank, elem_size, nthreads, &pipe, &dims, &len)) return 1;
 
     LaneLease lanes;                    // (given back after the drain)
     DrainOnExit drain{stream, &cx.pending, cx.side, &lanes};
@@ -1522,29 +1541,18 @@ int encode_from_host(const char* pipeline, const char* src, long* shape, unsigne
                      long* dstlength, int nthreads, long dst_capacity = -1)
 {
     if (!pipeline || !src || !shape || !dst || !dstlength) return 1;
-    {
-        std::string why;
-        if (!Pipeline::supported(pipeline, elem_size, &why)) {
-            if (Pipeline::reference_accepts(pipeline)) std::fprintf(stderr, "[sqeazy]\t pipeline %s: %s\n", pipeline, why.c_str());
-            return 1;   // sqeazy.cpp:81-82,118-119: invalid pipeline -> 1 before touching any buffer
-        }
-    }
+    if (!pipeline_admitted(pipeline, elem_size)) return 1;   // sqeazy.cpp:81-82,118-119: invalid pipeline -> 1 before touching any buffer
     if (!device_present()) { std::fprintf(stderr, "[sqeazy]\t no MI355X (HIP device) visible: sqeazy_amd has no CPU path\n"); return 1; }
     ContextLease lease;
     if (!lease.ctx) { std::fprintf(stderr, "[sqeazy]\t no usable HIP device\n"); return 1; }
     Workspace* ws = &lease.ctx->ws;
     hipStream_t stream = lease.ctx->own_stream();
     if (!stream) { std::fprintf(stderr, "[sqeazy]\t no HIP stream\n"); return 1; }
-    const uint64_t len = voxel_count(shape, rank);
-    if (len == 0) return 1;
-    if (len >= ((uint64_t)1 << 31)) {
-        std::fprintf(stderr, "[sqeazy]\t 2^31 or more voxels in one call overflow the reference's int voxel count; encode z-slabs\n");
-        return 1;
-    }
+    Pipeline pipe;
+    std::vector<uint64_t> dims;
+    uint64_t len = 0;
+    if (admit_encode(pipeline, shape, rank, elem_size, nthreads, &pipe, &dims, &len)) return 1;      // (in front of the staging buffers)
     const uint64_t raw = len * (uint64_t)elem_size;
-    Pipeline pipe = Pipeline::from_string(pipeline, elem_size);
-    pipe.set_n_threads(nthreads);
-    if (!background_geometry_ok(pipe, std::vector<uint64_t>(shape, shape + rank))) return 1;
     // What the caller was told to allocate: SQY_Pipeline_Max_Compressed_Length_* evaluates the bound on a fresh
     // pipeline (n_threads = 1, sqeazy.cpp:144-231).  The reference itself writes past that for pipelines whose
     // header grows while encoding (frame_shuffle's reorder_map on stacks of many small frames); here the

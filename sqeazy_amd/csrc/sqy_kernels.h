@@ -7,6 +7,8 @@
 
 namespace sqy {
 
+struct Lz4DedupeLayout;          // sqy_pipeline.hpp (as kLz4FrameHead and kLz4FrameGap)
+
 // the duplicate search's tables, handed to launch_lz4_chunks when the decision per chunk is made by the chunk's own parse wavefront
 // (launch_lz4_dedupe(.., fused) fills it in); chunk_key == nullptr: not in use
 struct Lz4DedupeArgs {
@@ -25,7 +27,7 @@ struct Lz4DedupeArgs {
 // piece_hash != nullptr (bitswap1_piece_hash_words(..) words, only offered when that is non-zero): a hash of every 1 KiB piece of
 // plane data is left there for launch_lz4_dedupe
 // gap_chunk != 0 ("frames in place", see launch_lz4_tail_marks): the plane stream is written as the bodies of the LZ4 frames it
-// will be cut into -- chunk k (gap_chunk bytes, a power of two) at out + k * (gap_chunk + 15), `out` any alignment; needs
+// will be cut into -- chunk k (gap_chunk bytes, a power of two) at out + k * (gap_chunk + kLz4FrameGap), `out` any alignment; needs
 // len % 8192 == 0
 // side != nullptr (launch_diff3x3x1_side): columns x < side_w of every row of X voxels are read from the compact buffer `side`
 // digest != nullptr (round 6, frames in place only, len / 8 a multiple of gap_chunk): the NOISE DIGEST -- bucket << 17 | tag of the five bytes at
@@ -36,21 +38,18 @@ hipError_t launch_bitswap1_u16(const uint16_t* in, uint16_t* out, uint64_t len, 
                                uint32_t gap_chunk = 0, const uint16_t* side = nullptr, uint32_t side_w = 0, uint32_t X = 0,
                                uint32_t* digest = nullptr, uint32_t digest_stride = 0);
 void set_bitswap1_blocks_per_cu(long n);      // workgroups (two waves) of the in-place transposer per CU (default 32: as many as fit)
-uint32_t lz4_noise_digest_stride(uint32_t chunk);      // words per chunk, 0 = no digest for this chunk size
 uint64_t bitswap1_piece_hash_words(const void* in, const void* out, uint64_t len);
 // duplicate chunks of a plane stream (chunk a multiple of 1 KiB): dup_of[k] = the earliest chunk with the same bytes (k itself when
-// there is none); the hashes only nominate, a byte compare decides.  work: lz4_dedupe_work_bytes(nchunks) bytes
-uint64_t lz4_dedupe_work_bytes(uint64_t nchunks);
+// there is none); the hashes only nominate, a byte compare decides.  base: the search's workspace, laid out by lz4_dedupe_layout -- the
+// piece hashes are read and dup_of is written there
 // in_stride (all LZ4 launchers; 0 = chunk): chunk k of the stream starts at in + k * in_stride
 // holes (with gap_chunk): launch_bitswap1_u16 leaves the all-zero 1 KiB pieces of the stream UNWRITTEN (their hash is the exact zero
-// marker, 0); launch_lz4_dedupe(.., holes_map: scratch of lz4_holes_map_bytes) compares through the markers and then fills the pieces
+// marker, 0); launch_lz4_dedupe(.., holes: the workspace's holes map is used) compares through the markers and then fills the pieces
 // in (writes into `in`) for every chunk anybody will read -- the bit planes above the data's range are neither written nor read
-hipError_t launch_lz4_dedupe(const uint8_t* in, uint64_t total, uint32_t chunk, const uint32_t* piece_hash, void* work,
-                             uint32_t* dup_of, hipStream_t stream, uint64_t in_stride = 0, uint64_t* holes_map = nullptr,
-                             bool table_is_clear = false, Lz4DedupeArgs* fused = nullptr);
+hipError_t launch_lz4_dedupe(const uint8_t* in, uint64_t total, uint32_t chunk, void* base, const Lz4DedupeLayout& lay, hipStream_t stream,
+                             uint64_t in_stride = 0, bool holes = false, bool table_is_clear = false, Lz4DedupeArgs* fused = nullptr);
 // the search's table emptied and *zero_word = 0 by one small kernel (a call launches it in front of its bit-plane transpose)
-hipError_t launch_lz4_dedupe_clear(void* work, uint64_t nchunks, uint32_t* zero_word, hipStream_t stream);
-uint64_t lz4_holes_map_bytes(uint64_t nchunks, uint32_t chunk);
+hipError_t launch_lz4_dedupe_clear(void* base, const Lz4DedupeLayout& lay, uint32_t* zero_word, hipStream_t stream);
 hipError_t launch_bitswap1_u8(const uint8_t* in, uint8_t* out, uint64_t len, hipStream_t stream);
 
 // diff3x3x1 on a {Z,Y,X} volume of 1- or 2-byte unsigned voxels (encoders/diff_scheme_impl.hpp:78-139)
@@ -142,10 +141,10 @@ hipError_t launch_lz4_inplace_tail(uint8_t* out, uint64_t t0, uint64_t in_stride
                                    const char* hdr_suffix, uint32_t suffix_len, uint32_t elem_size, const uint32_t* guard, uint64_t* record,
                                    hipStream_t stream);
 constexpr uint32_t kLz4InplaceHeaderTextMax = 3000;   // prefix + suffix bytes the finish kernel takes as an argument
-// Frames in place (chunked layout; the stage in front wrote chunk k of the stream at body0 + k * in_stride, in_stride = chunk + 15):
+// Frames in place (chunked layout; the stage in front wrote chunk k of the stream at body0 + k * in_stride, in_stride = chunk + kLz4FrameGap):
 // tail_info (4 words, from the scan) = {j, bytes of frames 0..j-1, stored chunks among them, payload bytes}, j = first chunk of
 // the run of stored chunks that ends the stream.  Those are final where they stand: tail_marks writes header / size field / end
-// mark around them.  The frames in front are gathered (launch_lz4_frame_gather over j chunks) to END at body0 - 11 + j * in_stride;
+// mark around them.  The frames in front are gathered (launch_lz4_frame_gather over j chunks) to END at body0 - kLz4FrameHead + j * in_stride;
 // stored chunks among THEM are first put aside in their scratch slots (stash_raw; gather then with raw_from_scratch).
 hipError_t launch_lz4_tail_marks(uint8_t* body0, uint64_t in_stride, uint64_t total, uint32_t chunk, uint64_t nchunks, uint32_t bd_byte,
                                  uint32_t hc_byte, const uint64_t* tail_info, hipStream_t stream);

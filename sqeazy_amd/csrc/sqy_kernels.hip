@@ -19,6 +19,7 @@
 #include <type_traits>
 
 #include "sqy_kernels.h"
+#include "sqy_pipeline.hpp"
 
 namespace sqy {
 
@@ -5939,22 +5940,6 @@ hipError_t launch_bitswap1_u16(const uint16_t* in, uint16_t* out, uint64_t len, 
     return hipGetLastError();
 }
 
-uint32_t lz4_noise_digest_stride(uint32_t chunk)
-{
-    // probes of a search that starts with the chunk and never finds anything (liblz4's step schedule), from probe 961 on; 0: no digest
-    if (chunk < 16384u || (chunk & (chunk - 1u))) return 0;
-    uint64_t p = 1, st = 1, nb = 64, probes = 0;
-    for (;;) {
-        ++probes;
-        const uint64_t p2 = p + st;
-        st = nb >> 6; ++nb;
-        if (p2 > (uint64_t)chunk - 12 + 1) break;
-        p = p2;
-    }
-    if (probes <= 961) return 0;
-    return (uint32_t)(((probes - 960) + 63) & ~(uint64_t)63);
-}
-
 uint64_t bitswap1_piece_hash_words(const void* in, const void* out, uint64_t len)
 {
     // one 1 KiB piece per plane and tile, four words each; 0 when the tile kernel does not cover the buffer exactly
@@ -5973,31 +5958,31 @@ void lz4_dedupe_clear_kernel(uint64_t* __restrict__ tab_key, uint32_t* __restric
     if (i == 0 && zero_word) *zero_word = 0u;
 }
 
-hipError_t launch_lz4_dedupe_clear(void* work, uint64_t nchunks, uint32_t* zero_word, hipStream_t stream)
+hipError_t launch_lz4_dedupe_clear(void* base, const Lz4DedupeLayout& lay, uint32_t* zero_word, hipStream_t stream)
 {
-    if (nchunks == 0) return hipSuccess;
-    uint32_t tab = 64;
-    while (tab < 2 * nchunks) tab <<= 1;
-    uint64_t* chunk_key = static_cast<uint64_t*>(work);
-    uint64_t* tab_key = chunk_key + nchunks;
-    uint32_t* tab_val = reinterpret_cast<uint32_t*>(tab_key + tab);
+    if (lay.total == 0) return hipSuccess;
+    const uint32_t tab = (uint32_t)lay.table;
+    uint64_t* tab_key = reinterpret_cast<uint64_t*>(static_cast<uint8_t*>(base) + lay.tab_key_at);
+    uint32_t* tab_val = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(base) + lay.tab_val_at);
     hipLaunchKernelGGL(lz4_dedupe_clear_kernel, dim3((tab + 255u) / 256u), dim3(256), 0, stream, tab_key, tab_val, tab, zero_word);
     return hipGetLastError();
 }
 
-hipError_t launch_lz4_dedupe(const uint8_t* in, uint64_t total, uint32_t chunk, const uint32_t* piece_hash, void* work,
-                             uint32_t* dup_of, hipStream_t stream, uint64_t in_stride, uint64_t* holes_map, bool table_is_clear,
-                             Lz4DedupeArgs* fused)
+hipError_t launch_lz4_dedupe(const uint8_t* in, uint64_t total, uint32_t chunk, void* base, const Lz4DedupeLayout& lay, hipStream_t stream,
+                             uint64_t in_stride, bool holes, bool table_is_clear, Lz4DedupeArgs* fused)
 {
     const uint64_t nchunks = (total + chunk - 1) / chunk, nfull = total / chunk;
     if (nchunks == 0) return hipSuccess;
     if (in_stride == 0) in_stride = chunk;
-    if (chunk % 1024 != 0) return hipErrorInvalidValue;
-    uint32_t tab = 64;
-    while (tab < 2 * nchunks) tab <<= 1;
-    uint64_t* chunk_key = static_cast<uint64_t*>(work);
-    uint64_t* tab_key = chunk_key + nchunks;
-    uint32_t* tab_val = reinterpret_cast<uint32_t*>(tab_key + tab);
+    if (chunk % 1024 != 0 || lay.total == 0) return hipErrorInvalidValue;
+    uint8_t* const b = static_cast<uint8_t*>(base);
+    const uint32_t tab = (uint32_t)lay.table;
+    const uint32_t* piece_hash = reinterpret_cast<const uint32_t*>(b);
+    uint64_t* chunk_key = reinterpret_cast<uint64_t*>(b + lay.work_at);
+    uint64_t* tab_key = reinterpret_cast<uint64_t*>(b + lay.tab_key_at);
+    uint32_t* tab_val = reinterpret_cast<uint32_t*>(b + lay.tab_val_at);
+    uint32_t* dup_of = reinterpret_cast<uint32_t*>(b + lay.dup_at);
+    uint64_t* holes_map = holes ? reinterpret_cast<uint64_t*>(b + lay.holes_at) : nullptr;
     hipError_t e = hipSuccess;
     if (!table_is_clear) {
         e = hipMemsetAsync(tab_key, 0, (size_t)tab * 8, stream);
@@ -6019,18 +6004,6 @@ hipError_t launch_lz4_dedupe(const uint8_t* in, uint64_t total, uint32_t chunk, 
     hipLaunchKernelGGL(lz4_dedupe_verify_kernel, dim3((unsigned)nchunks), dim3(DEDUPE_THREADS), 0, stream, in, chunk, in_stride, nfull, nchunks, chunk_key,
                        tab_key, tab_val, tab - 1u, dup_of, piece_hash, holes_map, total);
     return hipGetLastError();
-}
-
-uint64_t lz4_holes_map_bytes(uint64_t nchunks, uint32_t chunk)
-{
-    return nchunks * (1u + ((uint64_t)(chunk >> 10) + 63u) / 64u) * 8u;
-}
-
-uint64_t lz4_dedupe_work_bytes(uint64_t nchunks)
-{
-    uint64_t tab = 64;
-    while (tab < 2 * nchunks) tab <<= 1;
-    return nchunks * 8 + tab * 8 + tab * 4 + 64;
 }
 
 hipError_t launch_quantiser_apply_bitswap1_u8(const uint16_t* in, uint8_t* out, uint64_t len, const uint8_t* lut, hipStream_t stream)
@@ -6450,7 +6423,7 @@ hipError_t launch_lz4_inplace_tail(uint8_t* out, uint64_t t0, uint64_t in_stride
     hp.prefix_len = prefix_len; hp.suffix_len = suffix_len;
     std::memcpy(hp.text, hdr_prefix, prefix_len);
     std::memcpy(hp.text + prefix_len, hdr_suffix, suffix_len);
-    uint8_t* body0 = out + t0 + 11;
+    uint8_t* body0 = out + t0 + kLz4FrameHead;
     const uint32_t slices_stash = (chunk + 32767u) / 32768u, slices = (chunk + GATHER_SLICE - 1) / GATHER_SLICE;
     const uint64_t stash_items = nchunks * slices_stash, gather_items = nchunks * slices;
     hipLaunchKernelGGL(lz4_stash_raw_kernel, dim3((unsigned)(stash_items < 1024 ? stash_items : 1024)), dim3(256), 0, stream, body0, in_stride, total, chunk,

@@ -271,6 +271,105 @@ Lz4Plan lz4_plan_blocks(uint64_t total, uint64_t step, uint64_t block_bytes, boo
     return plan;
 }
 
+// ---- encode planning ----
+Lz4EncodeLayout lz4_encode_layout(const Lz4Params& p, uint64_t total, unsigned nthreads)
+{
+    const Lz4DecodeGeometry g = lz4_decode_geometry(p, total);
+    Lz4EncodeLayout lay;
+    lay.chunk = g.chunk; lay.nchunks = g.nchunks;
+    if (nthreads == 1 && g.nchunks > 1) lay.kind = Lz4LayoutKind::serial;
+    else if (g.chunk > g.block_bytes) lay.kind = Lz4LayoutKind::linked_chunks;
+    if (p.accel < 0) lay.accel = (uint32_t)std::min<int64_t>(1 - (int64_t)p.accel, 65537);
+    return lay;
+}
+
+static uint64_t round_up(uint64_t v, uint64_t to) { return (v + to - 1) / to * to; }
+
+Lz4DedupeLayout lz4_dedupe_layout(const Lz4EncodeLayout& lay, uint64_t piece_hash_words)
+{
+    Lz4DedupeLayout d;
+    if (!piece_hash_words || !lay.chunked() || lay.chunk % 1024 != 0 || lay.nchunks < 2) return d;
+    d.table = 64;
+    while (d.table < 2 * lay.nchunks) d.table <<= 1;
+    d.work_at = round_up(piece_hash_words * 4, 64);
+    d.tab_key_at = d.work_at + lay.nchunks * 8;
+    d.tab_val_at = d.tab_key_at + d.table * 8;
+    d.dup_at = d.tab_val_at + d.table * 4 + 64;
+    d.holes_at = d.dup_at + round_up(lay.nchunks * 4, 8);
+    d.total = d.holes_at + lay.nchunks * (1u + ((lay.chunk >> 10) + 63u) / 64u) * 8u;       // per chunk: a word, and a bit per 1 KiB piece
+    return d;
+}
+
+Lz4InplacePlan lz4_inplace_plan(const Lz4EncodeLayout& lay, uint64_t piece_hash_words, bool lz4_is_last, bool takes_offset, unsigned dst_mod16,
+                                uint64_t capacity, uint64_t header_max)
+{
+    Lz4InplacePlan p;
+    if (!lz4_dedupe_layout(lay, piece_hash_words).total || !lz4_is_last || !takes_offset || (lay.chunk & (lay.chunk - 1))) return p;
+    p.chunk = lay.chunk;
+    p.t0 = header_max;
+    while ((dst_mod16 + p.t0 + kLz4FrameHead) & 15) ++p.t0;         // body of chunk 0 on a 16-byte boundary
+    p.in_stride = lay.chunk + kLz4FrameGap;
+    p.body0 = p.t0 + kLz4FrameHead;
+    p.on = p.t0 + lay.nchunks * p.in_stride <= capacity;
+    return p.on ? p : Lz4InplacePlan();
+}
+
+static uint32_t lz4_noise_digest_stride(uint32_t chunk)
+{
+    if (chunk < 16384u || (chunk & (chunk - 1u))) return 0;
+    uint64_t p = 1, st = 1, nb = 64, probes = 0;
+    for (;;) {
+        ++probes;
+        const uint64_t p2 = p + st;
+        st = nb >> 6; ++nb;
+        if (p2 > (uint64_t)chunk - 12 + 1) break;
+        p = p2;
+    }
+    if (probes <= 961) return 0;
+    return (uint32_t)(((probes - 960) + 63) & ~(uint64_t)63);
+}
+
+uint32_t lz4_noise_digest_words(const Lz4Params& p, const Lz4EncodeLayout& lay, bool option_on, uint64_t segment_bytes)
+{
+    const uint32_t stride = lay.chunk <= 0xffffffffull ? lz4_noise_digest_stride((uint32_t)lay.chunk) : 0;
+    return option_on && stride && segment_bytes % lay.chunk == 0 && p.accel >= 0 ? stride : 0;
+}
+
+bool lz4_spec_wanted(const Lz4Plan& plan)
+{
+    const uint64_t nframes = plan.frame_first.size() - 1;
+    uint64_t longest = 0;
+    for (uint64_t f = 0; f < nframes; ++f) longest = std::max<uint64_t>(longest, plan.frame_first[f + 1] - plan.frame_first[f]);
+    return longest >= 3 && nframes < 1024;
+}
+
+void lz4_warmup_windows(const Lz4Plan& plan, uint64_t warmup, std::vector<uint32_t>* first, std::vector<uint32_t>* last)
+{
+    first->resize(plan.blocks.size()); last->resize(plan.blocks.size());
+    for (size_t f = 0; f + 1 < plan.frame_first.size(); ++f)
+        for (uint32_t k = plan.frame_first[f]; k < plan.frame_first[f + 1]; ++k) {
+            uint32_t j = k;
+            uint64_t have = 0;
+            while (j > plan.frame_first[f] && have < warmup) { --j; have += plan.blocks[j].n; }
+            (*first)[k] = j; (*last)[k] = k;
+        }
+}
+
+Lz4RedoRuns lz4_redo_runs(const Lz4Plan& plan, const std::vector<uint32_t>& ok, uint64_t run_max, std::vector<uint32_t>* first, std::vector<uint32_t>* last)
+{
+    Lz4RedoRuns r;
+    const uint64_t nblocks = ok.size();
+    for (uint64_t k = 0; k < nblocks; ++k) {
+        if (ok[k]) continue;
+        uint64_t e = k;
+        while (e + 1 < nblocks && !ok[e + 1] && !(plan.blocks[e + 1].flags & 1u)) ++e;
+        r.longest = std::max(r.longest, e - k + 1);
+        (*first)[r.nruns] = (uint32_t)k; (*last)[r.nruns] = (uint32_t)std::min(e, k + run_max - 1); ++r.nruns;
+        k = e;
+    }
+    return r;
+}
+
 // ---- decode planning ----
 Lz4DecodeGeometry lz4_decode_geometry(const Lz4Params& p, uint64_t total)
 {

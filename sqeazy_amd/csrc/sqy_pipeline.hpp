@@ -61,6 +61,52 @@ struct Lz4Plan {
 // serial = false: one frame per `step` bytes, each fed by a single update (encode_parallel -> encode_serial per chunk)
 Lz4Plan lz4_plan_blocks(uint64_t total, uint64_t step, uint64_t block_bytes, bool serial);
 
+// ---- encode planning: every layout decision of the LZ4 stage and of the stages that prepare its input, stated once ----
+// How `total` bytes in front of the LZ4 stage become frames (lz4.hpp:227-234), and liblz4's acceleration for them
+//   chunked: one frame of one LZ4 block per chunk, every chunk independent | serial: nthreads == 1 and more than one chunk, ONE block-linked
+//   frame fed a chunk at a time | linked_chunks: one block-linked frame per chunk, chunks of several LZ4 blocks
+enum class Lz4LayoutKind { chunked, serial, linked_chunks };
+struct Lz4EncodeLayout {
+    uint64_t chunk = 1, nchunks = 0;        // (lz4_decode_geometry's)
+    Lz4LayoutKind kind = Lz4LayoutKind::chunked;
+    // LZ4F turns a negative compression level -k into acceleration k + 1 (lz4frame.c, LZ4F_compressBlock),
+    // LZ4_compress_fast_continue caps it at 65537 (lz4.c, LZ4_ACCELERATION_MAX)
+    uint32_t accel = 1;
+    bool chunked() const { return kind == Lz4LayoutKind::chunked; }
+};
+Lz4EncodeLayout lz4_encode_layout(const Lz4Params& p, uint64_t total, unsigned nthreads);
+
+// Frames in place: a 16-bit bitswap1 in front of lz4 writes chunk k of the plane stream into the destination at body0 + k * in_stride,
+// where it is the body of the stored frame it may become -- kLz4FrameHead bytes (frame header 7, block size field 4) in front, the end
+// mark behind: kLz4FrameGap bytes between two chunks.  t0 (>= header_max, the longest sqy header) is where frame 0 begins.
+constexpr uint64_t kLz4FrameHead = 7 + 4, kLz4FrameGap = kLz4FrameHead + 4;
+struct Lz4InplacePlan { bool on = false; uint64_t chunk = 0, t0 = 0, in_stride = 0, body0 = 0; };     // (all 0 when off)
+// on: piece hashes offered and a duplicate search behind them (lz4_dedupe_layout), lz4 the last stage, a power-of-two chunk, a caller who
+// takes the blob where it ends up, and room in the destination (dst_mod16: its address modulo 16 -- body0 lands on a 16-byte boundary)
+Lz4InplacePlan lz4_inplace_plan(const Lz4EncodeLayout& lay, uint64_t piece_hash_words, bool lz4_is_last, bool takes_offset, unsigned dst_mod16,
+                                uint64_t capacity, uint64_t header_max);
+// words per chunk of the noise digest a frames-in-place call gets (probes of a search that starts with the chunk and never finds anything,
+// liblz4's step schedule, from probe 961 on); 0 = none: the option off, a chunk size without one, a plane segment (segment_bytes) that is
+// no whole number of chunks, or not liblz4's plain search behind it (accel < 0)
+uint32_t lz4_noise_digest_words(const Lz4Params& p, const Lz4EncodeLayout& lay, bool option_on, uint64_t segment_bytes);
+
+// The duplicate-chunk search's workspace (one buffer), byte offsets in ascending order, each region ending where the next begins: bitswap1's
+// piece hashes at 0 | work_at: a key per chunk | tab_key_at, tab_val_at: the hash table's keys and values (`table` slots) | dup_at: dup_of |
+// holes_at: the holes map (frames in place: which 1 KiB pieces the transpose left unwritten) | total
+struct Lz4DedupeLayout { uint64_t table = 0, work_at = 0, tab_key_at = 0, tab_val_at = 0, dup_at = 0, holes_at = 0, total = 0; };     // total 0: no search
+// the search runs on piece hashes (piece_hash_words of them, 0: none offered) of a chunked layout of more than one chunk of whole KiB
+Lz4DedupeLayout lz4_dedupe_layout(const Lz4EncodeLayout& lay, uint64_t piece_hash_words);
+
+// The block-parallel parse of block-linked frames (sqy_kernels.h: Lz4SpecArgs).  Worth it for few long frames: the frame walks would
+// leave the chip empty
+bool lz4_spec_wanted(const Lz4Plan& plan);
+// mode 1: block k is parsed behind a warm-up over blocks [first[k], k) of its frame: the fewest that hold `warmup` bytes, or all of them
+void lz4_warmup_windows(const Lz4Plan& plan, uint64_t warmup, std::vector<uint32_t>* first, std::vector<uint32_t>* last);
+// mode 2: every maximal stretch of failed blocks (ok[k] == 0) that lies in one frame gives one run [first[r], last[r]] from its first
+// block, at most run_max blocks long (the rest fail the next check again).  first / last: at least ok.size() entries, nruns are written
+struct Lz4RedoRuns { uint64_t nruns = 0, longest = 0; };      // longest: the longest stretch, uncapped
+Lz4RedoRuns lz4_redo_runs(const Lz4Plan& plan, const std::vector<uint32_t>& ok, uint64_t run_max, std::vector<uint32_t>* first, std::vector<uint32_t>* last);
+
 // ---- decode planning: host arithmetic on untrusted input (a header's shape, LZ4 parameters and reorder_map, a caller's range) ----
 // What the decoder of one LZ4 stage indexes: `total` bytes in front of the stage in `nchunks` chunks of `chunk` (the last one may be
 // short), at most `max_blocks` LZ4 blocks of up to `block_bytes`

@@ -1,6 +1,6 @@
 // Host side of libsqeazy_amd under AddressSanitizer + UndefinedBehaviorSanitizer (CPU only, no HIP): the pipeline grammar, the
 // configuration strings, the sqy header (pack / unpack of untrusted bytes), base64, the LZ4 block planner, the quantiser's host LUTs
-// and file readers, the frame / tile ordering, the decode planners -- everything sqy_pipeline.cpp holds -- driven with valid inputs, systematic
+// and file readers, the frame / tile ordering, the decode and encode planners -- everything sqy_pipeline.cpp holds -- driven with valid inputs, systematic
 // truncations and seeded random mutations.  Built and run by tests/test_host_sanitizers.py:
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all host_fuzz.cpp ../../sqeazy_amd/csrc/sqy_pipeline.cpp
 // Exit code 0 and no sanitizer report = pass.  ("race detection / sanitizers".)
@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <random>
 #include <string>
 #include <vector>
@@ -443,6 +444,184 @@ static void range_plans(std::mt19937& rng)
           !lz4_folds_into_shuffle(3, 3, 24, 8, 2, 8) && !lz4_chunks_whole(3, 3, 25, 9) && !lz4_chunks_whole(2, 3, 24, 8) && !lz4_chunks_whole(0, 0, 0, 0));
 }
 
+// ---- the encode planners (sqy_capi.cpp's EncodeCall asks them; each is checked against a brute-force model of its own) ----
+static Lz4Params random_lz4(std::mt19937& rng)
+{
+    const char* const blocksizes[] = {"64", "256", "1024", "4096"};
+    std::string cfg = std::string("blocksize_kb=") + blocksizes[rng() % 4];
+    switch (rng() % 4) {
+        case 0: break;                                                                   // framestep_kb = 256
+        case 1: cfg += ",framestep_kb=" + std::to_string(1u << (rng() % 14)); break;
+        case 2: cfg += ",framestep_kb=" + std::to_string(1 + rng() % 9000); break;
+        default: cfg += ",framestep_kb=0,n_chunks_of_input=" + std::to_string(rng() % 40); break;
+    }
+    if (rng() % 3 == 0) cfg += ",accel=" + std::to_string((int)(rng() % 200) - 100);
+    return Lz4Params(cfg);
+}
+
+static void encode_layouts(std::mt19937& rng)
+{
+    for (int round = 0; round < 200000; ++round) {
+        const Lz4Params lz = random_lz4(rng);
+        const unsigned nthreads = (unsigned)(rng() % 4);
+        const uint64_t sizes[] = {0, 1, (uint64_t)rng() % 5000, (uint64_t)rng() % (64u << 20), ((uint64_t)rng() % 2048 + 1) << 10, lz.block_bytes() + rng() % 3 - 1,
+                                  lz.bytes_per_chunk(1ull << 40) * (rng() % 5) + rng() % 3 - 1};
+        const uint64_t total = sizes[rng() % 7] & 0xffffffffull;
+        const Lz4EncodeLayout lay = lz4_encode_layout(lz, total, nthreads);
+        const Lz4DecodeGeometry g = lz4_decode_geometry(lz, total);
+        CHECK(lay.chunk == g.chunk && lay.nchunks == g.nchunks && lay.chunk >= 1);
+        {   // EncodeCall::lz4_stage as it was
+            const uint64_t chunk = total ? lz.bytes_per_chunk(total) : 1;
+            const uint64_t nchunks = total ? (total + chunk - 1) / chunk : 0;
+            const bool serial = nthreads == 1 && nchunks > 1;
+            const Lz4LayoutKind want = !serial && chunk <= lz.block_bytes() ? Lz4LayoutKind::chunked : serial ? Lz4LayoutKind::serial : Lz4LayoutKind::linked_chunks;
+            CHECK(lay.chunk == chunk && lay.nchunks == nchunks && lay.kind == want);
+            CHECK(total || lay.chunked());                          // (the linked layouts are never asked for an empty stream)
+        }
+        if (total) {      // (no stage sees an empty stream: a call of zero voxels is refused)
+            // EncodeCall::bitswap1 as it was
+            const uint64_t chunk = lz.bytes_per_chunk(total);
+            const bool chunked = chunk <= lz.block_bytes() && !(nthreads == 1 && total > chunk);
+            CHECK(lay.chunked() == chunked && lay.chunk == chunk);
+            CHECK((lay.nchunks > 1) == (total > chunk) && lay.nchunks == (total + chunk - 1) / chunk);
+            // EncodeCall::frame_shuffle as it was
+            const uint64_t frame_bytes = rng() % 3 ? chunk * (1 + rng() % 3) : 1 + rng() % (2 * chunk);
+            const bool fused = chunk && frame_bytes % chunk == 0 && chunk <= lz.block_bytes() && !(nthreads == 1 && total > chunk);
+            CHECK((lay.chunked() && frame_bytes % lay.chunk == 0) == fused);
+        }
+        CHECK(lay.accel == (lz.accel < 0 ? (uint32_t)(1 - lz.accel) : 1u));
+    }
+    const struct { int accel; uint32_t want; } edges[] = {{0, 1}, {1, 1}, {-1, 2}, {-65535, 65536}, {-65536, 65537}, {-65537, 65537}, {-2147483647 - 1, 65537}, {2147483647, 1}};
+    for (const auto& e : edges) {
+        Lz4Params lz;
+        lz.accel = e.accel;
+        CHECK(lz4_encode_layout(lz, 1u << 20, 0).accel == e.want);
+    }
+}
+
+static void dedupe_and_inplace_plans(std::mt19937& rng)
+{
+    for (int round = 0; round < 200000; ++round) {
+        const Lz4Params lz = random_lz4(rng);
+        const unsigned nthreads = (unsigned)(rng() % 3);
+        const uint64_t total = rng() % 4 ? ((uint64_t)rng() % 4096 + 1) << 13 : (uint64_t)rng() % (32u << 20);      // (bitswap1's tiles: 8192 voxels)
+        const uint64_t words = rng() % 5 ? total / 16384 * 64 : 0;
+        const Lz4EncodeLayout lay = lz4_encode_layout(lz, total, nthreads);
+        const uint64_t nch = lay.nchunks, chunk = lay.chunk;
+        // the duplicate search's workspace: EncodeCall::bitswap1's condition and sum as they were
+        const Lz4DedupeLayout d = lz4_dedupe_layout(lay, words);
+        const bool searched = words && lay.chunked() && chunk % 1024 == 0 && total > chunk;
+        CHECK((d.total != 0) == searched);
+        if (searched) {
+            uint64_t tab = 64;
+            while (tab < 2 * nch) tab <<= 1;
+            CHECK(d.table == tab && (d.table & (d.table - 1)) == 0 && d.table >= 64 && d.table >= 2 * nch);
+            const uint64_t ph_bytes = (words * 4 + 63) & ~(uint64_t)63, work_bytes = nch * 8 + tab * 8 + tab * 4 + 64;
+            const uint64_t dup_bytes = (nch * 4 + 7) & ~(uint64_t)7, holes_bytes = nch * (1u + ((uint64_t)((uint32_t)chunk >> 10) + 63u) / 64u) * 8u;
+            CHECK(d.total == ph_bytes + work_bytes + dup_bytes + holes_bytes);
+            // regions: ascending, disjoint, aligned as they were (64 / 8 / 8), inside the total; each holds what is kept there
+            CHECK(d.work_at >= words * 4 && d.work_at == ph_bytes && d.work_at % 64 == 0);
+            CHECK(d.tab_key_at == d.work_at + nch * 8 && d.tab_val_at == d.tab_key_at + d.table * 8 && d.tab_val_at + d.table * 4 <= d.dup_at);
+            CHECK(d.dup_at == d.work_at + work_bytes && d.dup_at % 8 == 0 && d.dup_at + nch * 4 <= d.holes_at);
+            CHECK(d.holes_at == d.dup_at + dup_bytes && d.holes_at % 8 == 0 && d.holes_at + holes_bytes == d.total && holes_bytes >= nch * (8 + ((chunk >> 10) + 7) / 8));
+        }
+        // frames in place
+        const bool last = rng() % 8 != 0, offset = rng() % 8 != 0;
+        const unsigned mod16 = (unsigned)(rng() % 16);
+        const uint64_t hdr_max = 100 + rng() % 400;
+        uint64_t t0 = hdr_max;
+        while ((mod16 + t0 + 11) % 16) ++t0;
+        const uint64_t need = t0 + nch * (chunk + 15);
+        const uint64_t capacity = rng() % 3 == 0 ? need : rng() % 3 == 0 ? need - 1 : need + (int64_t)(rng() % 4096) - 2048;
+        const Lz4InplacePlan p = lz4_inplace_plan(lay, words, last, offset, mod16, capacity, hdr_max);
+        const bool want = searched && last && offset && (chunk & (chunk - 1)) == 0 && need <= capacity;
+        CHECK(p.on == want);
+        if (p.on) {
+            CHECK(kLz4FrameHead == 11 && kLz4FrameGap == 15);
+            CHECK((mod16 + p.body0) % 16 == 0 && p.body0 == p.t0 + kLz4FrameHead && p.t0 >= hdr_max && p.t0 - hdr_max < 16 && p.t0 == t0);
+            CHECK(p.chunk == chunk && p.in_stride == chunk + kLz4FrameGap && p.t0 + nch * (chunk + kLz4FrameGap) <= capacity);
+            CHECK(!lz4_inplace_plan(lay, words, last, offset, mod16, need - 1, hdr_max).on && lz4_inplace_plan(lay, words, last, offset, mod16, need, hdr_max).on);
+            CHECK(!lz4_inplace_plan(lay, 0, last, offset, mod16, capacity, hdr_max).on && !lz4_inplace_plan(lay, words, false, offset, mod16, capacity, hdr_max).on &&
+                  !lz4_inplace_plan(lay, words, last, false, mod16, capacity, hdr_max).on);
+        } else {
+            CHECK(p.chunk == 0 && p.t0 == 0 && p.in_stride == 0 && p.body0 == 0);
+        }
+        // the noise digest: EncodeCall::bitswap1's test as it was, the stride from the probes of liblz4's step schedule over a chunk (from probe
+        // 961 on, in whole 64-word rows; chunks of 16 KiB and more that are powers of two)
+        const bool option = rng() % 8 != 0;
+        const uint64_t segment = total / 16;
+        static std::map<uint64_t, uint32_t> strides;
+        if (chunk >= 16384 && !(chunk & (chunk - 1)) && !strides.count(chunk)) {
+            uint64_t probes = 0;
+            for (uint64_t pos = 1, step = 1, attempts = 64; ; pos += step, step = attempts++ >> 6) { ++probes; if (pos + step > chunk - 11) break; }
+            strides[chunk] = probes > 961 ? (uint32_t)((probes - 960 + 63) / 64 * 64) : 0u;
+        }
+        const uint32_t stride = strides.count(chunk) ? strides[chunk] : 0u;
+        CHECK(lz4_noise_digest_words(lz, lay, option, segment) == (option && stride && segment % chunk == 0 && lz.accel >= 0 ? stride : 0u));
+    }
+}
+
+static void block_parallel_plans(std::mt19937& rng)
+{
+    const uint64_t blocks[] = {64u << 10, 256u << 10, 1u << 20};
+    for (int round = 0; round < 3000; ++round) {
+        const uint64_t bb = blocks[rng() % 3];
+        const uint64_t total = 1 + (uint64_t)rng() % (24u << 20);
+        const uint64_t step = rng() % 2 ? bb * (1 + rng() % 6) : 1 + (uint64_t)rng() % (4u << 20);
+        const Lz4Plan plan = lz4_plan_blocks(total, step, bb, rng() % 3 == 0);
+        if (!plan.ok || plan.blocks.empty()) continue;
+        const size_t nblocks = plan.blocks.size(), nframes = plan.frame_first.size() - 1;
+        std::vector<uint32_t> frame_of(nblocks);
+        uint64_t longest_frame = 0;
+        for (size_t f = 0; f < nframes; ++f) {
+            for (uint32_t k = plan.frame_first[f]; k < plan.frame_first[f + 1]; ++k) frame_of[k] = (uint32_t)f;
+            longest_frame = std::max<uint64_t>(longest_frame, plan.frame_first[f + 1] - plan.frame_first[f]);
+        }
+        CHECK(lz4_spec_wanted(plan) == (longest_frame >= 3 && nframes < 1024));
+        // warm-up windows: inside the frame, enough bytes or from the frame's first block, and not one block more than that
+        const uint64_t warmups[] = {0, 1, 65536, bb, 1 + (uint64_t)rng() % (3 * bb)};
+        const uint64_t warmup = warmups[rng() % 5];
+        std::vector<uint32_t> first, last;
+        lz4_warmup_windows(plan, warmup, &first, &last);
+        CHECK(first.size() == nblocks && last.size() == nblocks);
+        for (size_t k = 0; k < nblocks; ++k) {
+            const uint32_t f0 = plan.frame_first[frame_of[k]];
+            CHECK(last[k] == k && first[k] <= k && first[k] >= f0);
+            uint64_t have = 0;
+            for (size_t j = first[k]; j < k; ++j) have += plan.blocks[j].n;
+            CHECK(have >= warmup || first[k] == f0);
+            if (first[k] < k) CHECK(have - plan.blocks[first[k]].n < warmup);
+        }
+        // redo runs
+        const uint64_t run_max = 1 + rng() % 40;
+        std::vector<uint32_t> ok(nblocks);
+        const unsigned density = 1 + rng() % 8;
+        for (size_t k = 0; k < nblocks; ++k) ok[k] = round % 50 == 0 ? 1u : (rng() % density != 0 ? 0u : 1u);
+        std::vector<uint32_t> rf(nblocks, ~0u), rl(nblocks, ~0u);
+        const Lz4RedoRuns r = lz4_redo_runs(plan, ok, run_max, &rf, &rl);
+        CHECK(r.nruns <= nblocks);
+        std::vector<unsigned char> starts(nblocks, 0);
+        for (uint64_t i = 0; i < r.nruns; ++i) {
+            CHECK(rf[i] <= rl[i] && rl[i] < nblocks && rl[i] - rf[i] + 1 <= run_max);
+            if (i) CHECK(rf[i] > rl[i - 1]);
+            for (uint32_t k = rf[i]; k <= rl[i]; ++k) { CHECK(!ok[k] && frame_of[k] == frame_of[rf[i]]); if (k > rf[i]) CHECK(!(plan.blocks[k].flags & 1u)); }
+            starts[rf[i]] = 1;
+        }
+        for (uint64_t i = r.nruns; i < nblocks; ++i) CHECK(rf[i] == ~0u && rl[i] == ~0u);
+        // model: the maximal stretches of failed blocks of one frame; each starts exactly one run
+        uint64_t stretches = 0, longest = 0;
+        for (size_t k = 0; k < nblocks; ++k) {
+            if (ok[k] || (k > 0 && !ok[k - 1] && frame_of[k - 1] == frame_of[k])) continue;
+            size_t e = k;
+            while (e + 1 < nblocks && !ok[e + 1] && frame_of[e + 1] == frame_of[k]) ++e;
+            ++stretches; longest = std::max<uint64_t>(longest, e - k + 1);
+            CHECK(starts[k]);
+        }
+        CHECK(r.nruns == stretches && r.longest == longest);
+        if (round % 50 == 0) CHECK(r.nruns == 0 && r.longest == 0);
+    }
+}
+
 
 int main(int argc, char** argv)
 {
@@ -456,6 +635,9 @@ int main(int argc, char** argv)
     lz4_geometry(rng);
     shuffle_maps(rng);
     range_plans(rng);
+    encode_layouts(rng);
+    dedupe_and_inplace_plans(rng);
+    block_parallel_plans(rng);
     std::printf("host_fuzz ok: %lu checks\n", g_checks);
     return 0;
 }
