@@ -163,6 +163,34 @@ SQY_FUNCTION_PREFIX int SQYAMD_PipelineEncode_Slabs_UI16_Device(const char* pipe
 SQY_FUNCTION_PREFIX int SQYAMD_PipelineEncode_Slabs_UI8_Device(const char* pipeline, const void* d_src, const long* shape,
                                                                unsigned shape_size, int nslabs, void* d_dst, long slab_capacity,
                                                                long* offsets, long* lengths, int nthreads, int inflight);
+/* Many small volumes -- tiles, time points, dataset chunks: separately allocated, shapes may differ -- as one blob each with ONE call.
+ * d_srcs: a HOST array of nvolumes device pointers, each aligned at least to the voxel size.  shapes: a host array of nvolumes x
+ * shape_size longs, row i = volume i's {z,y,x}.  Blob i is written inside d_dst[i*slot_capacity, (i+1)*slot_capacity) and nothing
+ * outside a volume's own slot is written; offsets[i] = its start relative to d_dst, lengths[i] = its bytes (host arrays, as for
+ * _Slabs_*_Device).  Blob i is byte for byte what SQYAMD_PipelineEncode_*_Device gives for volume i with the same pipeline and nthreads.
+ * Volumes of `lz4` and `bitswap1->lz4` in the chunked layout (nthreads != 1 or a single chunk) with liblz4's acceleration 1 and at most
+ * "encode_batch_joint_max_bytes" of LZ4 input are encoded in groups ("encode_batch_group_bytes" of LZ4 input each, at least one volume):
+ * per group one launch of every kernel for all its volumes and two host round trips, whatever their number; their blobs start at the
+ * slot's first byte.  Every other volume (other pipelines, the serial or block-linked layout, accel < 0, larger volumes) is encoded as by
+ * _DeviceAt into its slot, in volume order on the same stream; a batch may mix both kinds.
+ * Stream, context, ordering and thread-safety rules are those of SQYAMD_PipelineEncode_*_Device: the work runs behind what is queued
+ * on hip_stream and is complete on return; several host threads may call at once.
+ * Returns 0 or 1.  Bad arguments -- a NULL pointer (also in d_srcs), nvolumes <= 0, shape_size 0, slot_capacity <= 0, a non-positive
+ * extent, a pipeline not admitted for the voxel type, a geometry the single call refuses for any volume, a misaligned source -- return
+ * 1 before anything is written, with offsets and lengths zeroed.  A blob that does not fit its slot makes the call return 1 (offsets and
+ * lengths zeroed); nothing of that volume is written, and no slot's neighbours are touched. */
+SQY_FUNCTION_PREFIX int SQYAMD_PipelineEncode_Batch_UI16_Device(const char* pipeline, const void* const* d_srcs, const long* shapes,
+                                                                unsigned shape_size, int nvolumes, void* d_dst, long slot_capacity,
+                                                                long* offsets, long* lengths, int nthreads, void* hip_stream);
+SQY_FUNCTION_PREFIX int SQYAMD_PipelineEncode_Batch_UI8_Device(const char* pipeline, const void* const* d_srcs, const long* shapes,
+                                                               unsigned shape_size, int nvolumes, void* d_dst, long slot_capacity,
+                                                               long* offsets, long* lengths, int nthreads, void* hip_stream);
+/* host-pointer variants: srcs[i] are host pointers, dst is host memory laid out the same way (only the blobs' bytes are written).  Every
+ * volume is staged up, the device driver called once and the blobs brought back; the staging does not overlap with the encode */
+SQY_FUNCTION_PREFIX int SQYAMD_PipelineEncode_Batch_UI16(const char* pipeline, const char* const* srcs, const long* shapes, unsigned shape_size,
+                                                         int nvolumes, char* dst, long slot_capacity, long* offsets, long* lengths, int nthreads);
+SQY_FUNCTION_PREFIX int SQYAMD_PipelineEncode_Batch_UI8(const char* pipeline, const char* const* srcs, const long* shapes, unsigned shape_size,
+                                                        int nvolumes, char* dst, long slot_capacity, long* offsets, long* lengths, int nthreads);
 /* host-pointer encode with an explicit destination capacity (returns 1 instead of overflowing dst; the
  * reference-protocol entry points above assume dst holds exactly SQY_Pipeline_Max_Compressed_Length_* bytes) */
 SQY_FUNCTION_PREFIX int SQYAMD_PipelineEncode_UI16_Cap(const char* pipeline, const char* src, long* shape, unsigned shape_size,
@@ -285,6 +313,12 @@ SQY_FUNCTION_PREFIX void SQYAMD_Release_Workspace(void);
  *                                     the pipeline allows (0: every blob decoded whole and the range copied out -- same bytes)
  *   "decode_slabs_joint"              1 [SQY_NO_DECODE_SLABS_JOINT=1 -> 0]  SQYAMD_Decode_Slabs_*: the chunked LZ4 blobs of a group indexed and
  *                                     decoded by one launch each (0: every blob on its own, as by SQYAMD_Decode_*_Device -- same bytes)
+ *   "encode_batch_joint"              1 [SQY_NO_ENCODE_BATCH_JOINT=1 -> 0]  SQYAMD_PipelineEncode_Batch_*: the joint-eligible volumes of a group share
+ *                                     one launch of every kernel (0: every volume through the single-call path -- same bytes)
+ *   "encode_batch_group_bytes"        2^30 [SQY_ENCODE_BATCH_GROUP_BYTES=<bytes>, 1 .. 2^32-1]  .. the LZ4 input of one group (a group holds at
+ *                                     least one volume): bounds the workspace -- twice that and the tables
+ *   "encode_batch_joint_max_bytes"    2^27 [SQY_ENCODE_BATCH_JOINT_MAX_BYTES=<bytes>, 0 .. 2^32-1]  .. a volume with more LZ4 input is encoded
+ *                                     on its own, frames in place (the faster path for large stacks; the default is measured: DESIGN.md 5)
  * Set: 0 = done, 1 = unknown name or value out of range.  Get: the value, -1 for an unknown name. */
 SQY_FUNCTION_PREFIX int SQYAMD_Set_Option(const char* name, long value);
 SQY_FUNCTION_PREFIX long SQYAMD_Get_Option(const char* name);

@@ -27,6 +27,7 @@ EXPORTED_SYMBOLS = (
     "SQYAMD_PipelineEncode_UI16_DeviceAt", "SQYAMD_PipelineEncode_UI8_DeviceAt",
     "SQYAMD_PipelineEncode_UI16_DeviceAt_Frames", "SQYAMD_PipelineEncode_UI8_DeviceAt_Frames",
     "SQYAMD_PipelineEncode_Slabs_UI16_Device", "SQYAMD_PipelineEncode_Slabs_UI8_Device",
+    "SQYAMD_PipelineEncode_Batch_UI16_Device", "SQYAMD_PipelineEncode_Batch_UI8_Device", "SQYAMD_PipelineEncode_Batch_UI16", "SQYAMD_PipelineEncode_Batch_UI8",
     "SQYAMD_PipelineEncode_UI16_Cap", "SQYAMD_PipelineEncode_UI8_Cap",
     "SQYAMD_Decode_UI16_Device", "SQYAMD_Decode_UI8_Device",
     "SQYAMD_Decode_Frames_UI16_Device", "SQYAMD_Decode_Frames_UI8_Device", "SQYAMD_Decode_Frames_UI16", "SQYAMD_Decode_Frames_UI8",
@@ -78,6 +79,12 @@ def lib():
         for f in ("SQYAMD_PipelineEncode_Slabs_UI8_Device", "SQYAMD_PipelineEncode_Slabs_UI16_Device"):
             getattr(L, f).argtypes = [ctypes.c_char_p, ctypes.c_void_p, c_long_p, ctypes.c_uint, ctypes.c_int, ctypes.c_void_p, ctypes.c_long,
                                       c_long_p, c_long_p, ctypes.c_int, ctypes.c_int]
+        for f in ("SQYAMD_PipelineEncode_Batch_UI8_Device", "SQYAMD_PipelineEncode_Batch_UI16_Device"):
+            getattr(L, f).argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_void_p), c_long_p, ctypes.c_uint, ctypes.c_int, ctypes.c_void_p, ctypes.c_long,
+                                      c_long_p, c_long_p, ctypes.c_int, ctypes.c_void_p]
+        for f in ("SQYAMD_PipelineEncode_Batch_UI8", "SQYAMD_PipelineEncode_Batch_UI16"):
+            getattr(L, f).argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_void_p), c_long_p, ctypes.c_uint, ctypes.c_int, ctypes.c_void_p, ctypes.c_long,
+                                      c_long_p, c_long_p, ctypes.c_int]
         for f in ("SQYAMD_PipelineEncode_UI8_Cap", "SQYAMD_PipelineEncode_UI16_Cap"):
             getattr(L, f).argtypes = [ctypes.c_char_p, ctypes.c_void_p, c_long_p, ctypes.c_uint, ctypes.c_void_p, ctypes.c_long, c_long_p,
                                       ctypes.c_int]
@@ -213,6 +220,44 @@ def encode_slabs_device(pipeline, d_src, shape, dtype, nslabs, d_dst, slab_capac
         pipeline.encode(), ctypes.c_void_p(int(d_src)), _longs(shape), ctypes.c_uint(len(shape)), ctypes.c_int(nslabs),
         ctypes.c_void_p(int(d_dst)), ctypes.c_long(int(slab_capacity)), offs, lens, ctypes.c_int(nthreads), ctypes.c_int(inflight))
     return rc, list(offs), list(lens)
+
+
+def encode_batch_device(pipeline, d_srcs, shapes, dtype, d_dst, slot_capacity, nthreads=0, stream=None):
+    """SQYAMD_PipelineEncode_Batch_*_Device: volume i ({z,y,x} = shapes[i]) at device pointer d_srcs[i] becomes a blob inside slot i of d_dst
+    (slot_capacity bytes each); returns (rc, offsets, lengths), offsets relative to d_dst."""
+    n = len(d_srcs)
+    rank = len(shapes[0]) if n else 0
+    ptrs = (ctypes.c_void_p * max(n, 1))(*[int(p) for p in d_srcs])
+    flat = _longs([x for s in shapes for x in s]) if n else None
+    offs = (ctypes.c_long * max(n, 1))()
+    lens = (ctypes.c_long * max(n, 1))()
+    rc = getattr(lib(), "SQYAMD_PipelineEncode_Batch_%s_Device" % _suffix(dtype))(
+        pipeline.encode(), ptrs, flat, ctypes.c_uint(rank), ctypes.c_int(n), ctypes.c_void_p(int(d_dst)), ctypes.c_long(int(slot_capacity)), offs, lens,
+        ctypes.c_int(nthreads), ctypes.c_void_p(stream or 0))
+    return rc, list(offs[:n]), list(lens[:n])
+
+
+def encode_batch(pipeline, volumes, nthreads=0):
+    """SQYAMD_PipelineEncode_Batch_UI8/UI16 on host ndarrays of one dtype and rank (shapes may differ); returns the list of blobs (bytes).
+    Raises ValueError when the call returns non-zero."""
+    vols = [np.ascontiguousarray(v) for v in volumes]
+    if not vols:
+        raise ValueError("encode_batch: no volumes")
+    dtype, rank = vols[0].dtype, vols[0].ndim
+    if any(v.dtype != dtype or v.ndim != rank for v in vols):
+        raise TypeError("encode_batch takes volumes of one dtype and rank")
+    n = len(vols)
+    cap = max(max(max_compressed_length(pipeline, v.shape, dtype), 64) for v in vols) if pipeline_possible(pipeline, dtype) else 64
+    dst = np.empty(n * cap, dtype=np.uint8)
+    ptrs = (ctypes.c_void_p * n)(*[v.ctypes.data for v in vols])
+    offs = (ctypes.c_long * n)()
+    lens = (ctypes.c_long * n)()
+    rc = getattr(lib(), "SQYAMD_PipelineEncode_Batch_" + _suffix(dtype))(
+        pipeline.encode(), ptrs, _longs([x for v in vols for x in v.shape]), ctypes.c_uint(rank), ctypes.c_int(n), dst.ctypes.data, ctypes.c_long(cap),
+        offs, lens, ctypes.c_int(nthreads))
+    if rc:
+        raise ValueError("SQYAMD_PipelineEncode_Batch returned %d for %r" % (rc, pipeline))
+    return [dst[offs[i]:offs[i] + lens[i]].tobytes() for i in range(n)]
 
 
 def header_size(blob):

@@ -61,6 +61,8 @@ long env_number(const char* name, long dflt, long lo, long hi)
 }
 constexpr long kWarmupMax = 1l << 30;
 constexpr long kStageLanesDefault = 2, kParseLanesDefault = 3;      // (measured: DESIGN.md section 5)
+constexpr long kBatchBytesMax = (1l << 32) - 1, kBatchGroupBytesDefault = 1l << 30;
+constexpr long kBatchJointMaxDefault = 128l << 20;                 // (the batch encode sweep: the largest size swept)
 struct Options {
     std::atomic<long> transpose_chain;                  // the bit-plane transposes of calls in flight on LIBRARY-OWNED streams run one after the other
     std::atomic<long> transpose_chain_caller_streams;   // .. on streams the callers bring as well (opt-in: couples those streams, see the bitswap1 stage)
@@ -75,6 +77,9 @@ struct Options {
     std::atomic<long> host_l2_bytes;                    // rmestbkrd: the host CPU's L2 size as the reference's compass reads it (detected; tests set it)
     std::atomic<long> decode_frames_subset;             // frame-range decode: only the LZ4 frames the range needs, where the pipeline allows (0: full decode + copy)
     std::atomic<long> decode_slabs_joint;               // slab-set decode: the chunked LZ4 blobs of a group indexed and decoded by one launch each (0: blob by blob)
+    std::atomic<long> encode_batch_joint;               // batch encode: the joint-eligible volumes of a group share one launch of every kernel (0: volume by volume)
+    std::atomic<long> encode_batch_group_bytes;         // .. the LZ4 input one group holds at most (a group holds at least one volume)
+    std::atomic<long> encode_batch_joint_max_bytes;     // .. a volume with more LZ4 input than this is encoded on its own (frames in place)
     std::atomic<long> stage_lanes;                      // frames-in-place calls on caller streams run on the library's lanes: 0 never, 1 always, 2 where transpose_chain_caller_streams is on
     std::atomic<long> parse_lanes;                      // .. how many parse lanes a device has (1-8)
     // counters (Get reads, Set takes 0 only): calls that ran on the lanes; calls that stayed on their caller's stream because it had a
@@ -88,7 +93,9 @@ struct Options {
           decode_two_waves(env_flag("SQY_NO_DECODE_TWO_WAVES") ? 0 : 1), noise_digest(env_flag("SQY_NO_NOISE_DIGEST") ? 0 : 1),
           transpose_blocks_per_cu(env_number("SQY_TRANSPOSE_BLOCKS_PER_CU", 32, 1, 64)), stored_tail_index(env_flag("SQY_NO_STORED_TAIL_INDEX") ? 0 : 1),
           host_l2_bytes((long)sqy::host_l2_cache_bytes()), decode_frames_subset(env_flag("SQY_NO_DECODE_FRAMES_SUBSET") ? 0 : 1),
-          decode_slabs_joint(env_flag("SQY_NO_DECODE_SLABS_JOINT") ? 0 : 1), stage_lanes(env_number("SQY_STAGE_LANES", kStageLanesDefault, 0, 2)),
+          decode_slabs_joint(env_flag("SQY_NO_DECODE_SLABS_JOINT") ? 0 : 1), encode_batch_joint(env_flag("SQY_NO_ENCODE_BATCH_JOINT") ? 0 : 1),
+          encode_batch_group_bytes(env_number("SQY_ENCODE_BATCH_GROUP_BYTES", kBatchGroupBytesDefault, 1, kBatchBytesMax)),
+          encode_batch_joint_max_bytes(env_number("SQY_ENCODE_BATCH_JOINT_MAX_BYTES", kBatchJointMaxDefault, 0, kBatchBytesMax)), stage_lanes(env_number("SQY_STAGE_LANES", kStageLanesDefault, 0, 2)),
           parse_lanes(env_number("SQY_PARSE_LANES", kParseLanesDefault, 1, sqy::LanePicker::kMaxLanes)) { sqy::set_bitswap1_blocks_per_cu(transpose_blocks_per_cu.load()); }
     std::atomic<long>* find(const char* name)
     {
@@ -106,6 +113,9 @@ struct Options {
         if (!std::strcmp(name, "host_l2_bytes")) return &host_l2_bytes;
         if (!std::strcmp(name, "decode_frames_subset")) return &decode_frames_subset;
         if (!std::strcmp(name, "decode_slabs_joint")) return &decode_slabs_joint;
+        if (!std::strcmp(name, "encode_batch_joint")) return &encode_batch_joint;
+        if (!std::strcmp(name, "encode_batch_group_bytes")) return &encode_batch_group_bytes;
+        if (!std::strcmp(name, "encode_batch_joint_max_bytes")) return &encode_batch_joint_max_bytes;
         if (!std::strcmp(name, "stage_lanes")) return &stage_lanes;
         if (!std::strcmp(name, "parse_lanes")) return &parse_lanes;
         if (!std::strcmp(name, "lane_calls")) return &lane_calls;
@@ -292,12 +302,17 @@ struct Workspace {
     DevBuf slabs_joint;       // .. the group's joint block index, frame output table, part descriptors and frame_shuffle maps
     DevBuf slabs_out;         // .. the group's LZ4 output (when it does not go straight to the volume)
     HostBuf slabs_host;       // .. the blobs' header prefixes and the ranking's counts, read back
+    DevBuf batch_stream;      // batch encode: the LZ4 input of a group's volumes (the bit planes), one stream behind the other
+    DevBuf batch_scratch;     // .. a slot of compressed output per entry of the group's joint chunk table
+    DevBuf batch_tables;      // .. the tables a group uploads (chunks, volumes, transposer jobs, header text) and what the kernels hand each other
+    HostBuf batch_host;       // .. the records of every volume, the staging area of the upload
     void* pinned = nullptr;   // 4 KiB of pinned host memory for small read-backs
     void release_buffers()
     {
         ping.release(); pong.release(); lz4_scratch.release(); csize.release(); frame_off.release();
         io_src.release(); io_dst.release(); small.release(); plan.release(); dedupe.release(); diff_side.release(); spec.release(); digest.release(); bkrd.release();
         subset.release(); range_full.release(); slabs_index.release(); slabs_joint.release(); slabs_out.release(); slabs_host.release();
+        batch_stream.release(); batch_scratch.release(); batch_tables.release(); batch_host.release();
     }
 };
 
@@ -1478,8 +1493,8 @@ bool pipeline_admitted(const std::string& pipeline, int elem_size)
 
 // What every encode call checks before it touches the device: the pipeline, the volume's size against the reference's int counts, the
 // background filters' geometry.  0: *pipe, *dims and *len are the call's
-int admit_encode(const std::string& pipeline, const long* shape, unsigned rank, int elem_size, int nthreads, Pipeline* pipe, std::vector<uint64_t>* dims,
-                 uint64_t* len)
+// (in two halves: a batch admits its pipeline once and every volume's shape)
+int admit_pipeline(const std::string& pipeline, int elem_size, int nthreads, Pipeline* pipe)
 {
     if (!pipeline_admitted(pipeline, elem_size)) return 1;
     *pipe = Pipeline::from_string(pipeline, elem_size);
@@ -1488,6 +1503,10 @@ int admit_encode(const std::string& pipeline, const long* shape, unsigned rank, 
         return 1;
     }
     pipe->set_n_threads(nthreads);
+    return 0;
+}
+int admit_shape(const Pipeline* pipe, const long* shape, unsigned rank, std::vector<uint64_t>* dims, uint64_t* len)
+{
     *len = voxel_count(shape, rank);
     if (*len == 0) { std::fprintf(stderr, "[sqeazy]\t non-positive extent in shape\n"); return 1; }
     if (*len >= ((uint64_t)1 << 31)) {
@@ -1496,6 +1515,11 @@ int admit_encode(const std::string& pipeline, const long* shape, unsigned rank, 
     }
     dims->assign(shape, shape + rank);
     return background_geometry_ok(*pipe, *dims) ? 0 : 1;
+}
+int admit_encode(const std::string& pipeline, const long* shape, unsigned rank, int elem_size, int nthreads, Pipeline* pipe, std::vector<uint64_t>* dims,
+                 uint64_t* len)
+{
+    return admit_pipeline(pipeline, elem_size, nthreads, pipe) || admit_shape(pipe, shape, rank, dims, len) ? 1 : 0;
 }
 
 int encode_on_device(Context& cx, const char* pipeline_c, const void* d_src, const long* shape, unsigned rank, int elem_size,
@@ -2599,6 +2623,230 @@ int encode_device(const char* pipeline, const void* d_src, const long* shape, un
     return rc;
 }
 
+// ---- batch encode (SQYAMD_PipelineEncode_Batch_*) -------------------------------------------------
+// Many volumes, one blob each, blob i inside slot i of d_dst.  The volumes lz4_batch_plan calls joint-eligible (pipelines lz4 and
+// bitswap1->lz4, the chunked layout, acceleration 1) go through the kernels group by group -- one launch per kernel for all volumes of a
+// group, two host round trips per group (the dense pass's count, the records) --, every other volume through encode_on_device.
+static_assert(sizeof(sqy::Lz4BatchChunkPlan) == sizeof(sqy::Lz4BatchChunk) && sizeof(sqy::Lz4BatchChunk) == 24, "the joint chunk table's layout");
+
+// What a batch call checks before it touches the device or writes anything: every argument, the pipeline once, every volume's shape
+struct BatchAdmit {
+    Pipeline pipe;
+    std::vector<std::vector<uint64_t>> dims;
+    std::vector<uint64_t> len;              // voxels
+};
+int admit_batch(const char* pipeline, const void* const* srcs, const long* shapes, unsigned rank, int elem_size, int nvolumes, const void* dst,
+                long slot_capacity, long* offsets, long* lengths, int nthreads, BatchAdmit* a)
+{
+    if (!offsets || !lengths) return 1;
+    for (int i = 0; i < nvolumes; ++i) { offsets[i] = 0; lengths[i] = 0; }
+    if (!pipeline || !srcs || !shapes || !dst || rank == 0 || nvolumes <= 0 || slot_capacity <= 0) return 1;
+    if (admit_pipeline(pipeline, elem_size, nthreads, &a->pipe)) return 1;
+    a->dims.resize((size_t)nvolumes);
+    a->len.resize((size_t)nvolumes);
+    for (int i = 0; i < nvolumes; ++i) {
+        if (!srcs[i]) return 1;
+        if (admit_shape(&a->pipe, shapes + (size_t)i * rank, rank, &a->dims[(size_t)i], &a->len[(size_t)i])) return 1;
+    }
+    return 0;
+}
+
+// one group of the plan through the kernels; rc 1 with a message when a blob does not fit its slot (nothing of that volume is written)
+int encode_batch_group(Context& cx, const BatchAdmit& a, const sqy::Lz4BatchGroup& g, bool transpose, int elem_size, const void* const* d_srcs,
+                       uint8_t* d_dst, uint64_t slot_capacity, long* offsets, long* lengths, uint64_t* records, uint8_t* staging, hipStream_t stream)
+{
+    Workspace* ws = &cx.ws;
+    std::vector<PendingEvent>* pend = &cx.pending;
+    const size_t nv = g.vols.size(), nc = g.chunks.size();
+    const std::string pipename = a.pipe.name();
+    // the upload, one copy: chunk table | volume of every entry | volumes | transposer jobs | their tile prefix | header text
+    auto up16 = [](uint64_t v) { return (v + 15) & ~(uint64_t)15; };
+    std::vector<std::string> text(nv);
+    uint64_t text_bytes = 0;
+    for (size_t j = 0; j < nv; ++j) {
+        std::string prefix, suffix;
+        sqy::header_pack_parts(elem_size, false, a.dims[g.vols[j]], pipename, &prefix, &suffix);
+        if (prefix.size() + suffix.size() > 4000) { std::fprintf(stderr, "[sqeazy]\t header text too long for the batch path\n"); return 1; }     // (the staging area's share)
+        text[j] = prefix + '\0' + suffix;                // (split again below: the prefix holds no NUL)
+        text_bytes += prefix.size() + suffix.size();
+    }
+    const uint64_t table_at = 0, volof_at = up16(table_at + nc * sizeof(sqy::Lz4BatchChunk)), vols_at = up16(volof_at + nc * 4),
+                   jobs_at = up16(vols_at + nv * sizeof(sqy::Lz4BatchVolume)), tiles_at = up16(jobs_at + nv * sizeof(sqy::Bitswap1Job)),
+                   text_at = up16(tiles_at + (nv + 1) * 4), upload = up16(text_at + text_bytes);
+    // .. and what the kernels hand each other: csize | redo list | frame offsets | per volume: payload bytes, header bytes and verdict
+    const uint64_t csize_at = upload, redo_at = up16(csize_at + nc * 4), foff_at = up16(redo_at + (nc + 1) * 4), vinfo_at = up16(foff_at + nc * 8),
+                   tables = vinfo_at + nv * 16;
+    if (ws->batch_tables.ensure(tables) || ws->batch_scratch.ensure(std::max<uint64_t>(nc * g.scratch_stride, 16))) return 1;
+    if (transpose && ws->batch_stream.ensure(std::max<uint64_t>(g.stream_bytes, 16))) return 1;
+    uint8_t* const d_tab = static_cast<uint8_t*>(ws->batch_tables.p);
+    uint8_t* const d_stream = transpose ? static_cast<uint8_t*>(ws->batch_stream.p) : nullptr;
+
+    sqy::Lz4BatchChunk* h_table = reinterpret_cast<sqy::Lz4BatchChunk*>(staging + table_at);
+    uint32_t* h_volof = reinterpret_cast<uint32_t*>(staging + volof_at);
+    sqy::Lz4BatchVolume* h_vols = reinterpret_cast<sqy::Lz4BatchVolume*>(staging + vols_at);
+    sqy::Bitswap1Job* h_jobs = reinterpret_cast<sqy::Bitswap1Job*>(staging + jobs_at);
+    uint32_t* h_tiles = reinterpret_cast<uint32_t*>(staging + tiles_at);
+    char* h_text = reinterpret_cast<char*>(staging + text_at);
+    uint64_t text_used = 0;
+    uint32_t ntiles = 0;
+    for (size_t j = 0; j < nv; ++j) {
+        const uint32_t vol = g.vols[j];
+        const size_t cut = text[j].find('\0');
+        const uint32_t prefix_len = (uint32_t)cut, suffix_len = (uint32_t)(text[j].size() - cut - 1);
+        std::memcpy(h_text + text_used, text[j].data(), prefix_len);
+        std::memcpy(h_text + text_used + prefix_len, text[j].data() + cut + 1, suffix_len);
+        h_vols[j] = sqy::Lz4BatchVolume{(uint64_t)vol * slot_capacity, slot_capacity, g.first_chunk[j], g.first_chunk[j + 1] - g.first_chunk[j],
+                                        (uint32_t)text_used, prefix_len, suffix_len, (uint32_t)elem_size, vol, 0};
+        text_used += prefix_len + suffix_len;
+        h_jobs[j] = sqy::Bitswap1Job{d_srcs[vol], d_stream ? d_stream + g.stream_at[j] : nullptr, a.len[vol]};
+        h_tiles[j] = ntiles;
+        ntiles += sqy::batch_bitswap1_tiles(a.len[vol]);
+        for (uint32_t e = g.first_chunk[j]; e < g.first_chunk[j + 1]; ++e) {
+            const sqy::Lz4BatchChunkPlan& c = g.chunks[e];
+            // (plain lz4: the stream IS the volume -- the entry's offset counts from address 0)
+            const uint64_t off = transpose ? c.off : (uint64_t)reinterpret_cast<uintptr_t>(d_srcs[vol]) + (c.off - g.stream_at[j]);
+            h_table[e] = sqy::Lz4BatchChunk{off, c.n, c.vol, c.slot, 0};
+            h_volof[e] = (uint32_t)j;
+        }
+    }
+    h_tiles[nv] = ntiles;
+    SQY_HIP(hipMemcpyAsync(d_tab, staging, upload, hipMemcpyHostToDevice, stream));
+
+    const sqy::Lz4BatchChunk* d_table = reinterpret_cast<const sqy::Lz4BatchChunk*>(d_tab + table_at);
+    const sqy::Lz4BatchVolume* d_vols = reinterpret_cast<const sqy::Lz4BatchVolume*>(d_tab + vols_at);
+    uint32_t* d_csize = reinterpret_cast<uint32_t*>(d_tab + csize_at);
+    uint32_t* d_redo = reinterpret_cast<uint32_t*>(d_tab + redo_at);
+    uint64_t* d_foff = reinterpret_cast<uint64_t*>(d_tab + foff_at);
+    uint64_t* d_vinfo = reinterpret_cast<uint64_t*>(d_tab + vinfo_at);
+    uint8_t* d_scratch = static_cast<uint8_t*>(ws->batch_scratch.p);
+    if (transpose)
+        SQY_TIMED("batch_bitswap1", sqy::launch_bitswap1_batch(reinterpret_cast<const sqy::Bitswap1Job*>(d_tab + jobs_at),
+                                                               reinterpret_cast<const uint32_t*>(d_tab + tiles_at), (uint32_t)nv, ntiles, elem_size, stream));
+    SQY_TIMED("batch_lz4_chunks", sqy::launch_lz4_chunks_table(d_stream, d_table, (uint32_t)nc, d_scratch, g.scratch_stride, d_csize, d_redo, stream));
+    // round trip 1: how many entries the first pass left to the dense batches
+    SQY_HIP(hipMemcpyAsync(ws->pinned, d_redo, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    SQY_HIP(hipStreamSynchronize(stream));
+    const uint32_t n_redo = *static_cast<uint32_t*>(ws->pinned);
+    if (n_redo)
+        SQY_TIMED("batch_lz4_chunks_dense", sqy::launch_lz4_chunks_table_dense(d_stream, d_table, d_scratch, g.scratch_stride, d_csize, d_redo, n_redo, stream));
+    SQY_TIMED("batch_lz4_frame_scan", sqy::launch_lz4_batch_scan(d_table, d_vols, (uint32_t)nv, d_csize, d_foff, d_vinfo, stream));
+    const Lz4Descriptor fd = lz4_descriptor(a.pipe.stages.back().lz4.block_id);
+    SQY_TIMED("batch_lz4_frame_gather", sqy::launch_lz4_batch_gather(d_stream, d_table, (uint32_t)nc, g.max_chunk, d_vols,
+                                                                     reinterpret_cast<const uint32_t*>(d_tab + volof_at), d_scratch, g.scratch_stride, d_csize,
+                                                                     d_foff, d_vinfo, reinterpret_cast<const char*>(d_tab + text_at), d_dst, fd.bd, fd.hc, records, stream));
+    // round trip 2: the records
+    SQY_HIP(hipStreamSynchronize(stream));
+    int rc = 0;
+    for (size_t j = 0; j < nv; ++j) {
+        const uint32_t vol = g.vols[j];
+        const volatile uint64_t* r = records + 3 * (uint64_t)vol;
+        if (r[0] == sqy::kBatchDone) { offsets[vol] = (long)((uint64_t)vol * slot_capacity); lengths[vol] = (long)r[1]; continue; }
+        if (r[0] == sqy::kBatchNoRoom)
+            std::fprintf(stderr, "[sqeazy]\t volume %u: destination slot too small (%llu payload bytes and the header > %llu bytes)\n", vol,
+                         (unsigned long long)r[2], (unsigned long long)slot_capacity);
+        else if (r[0] == sqy::kBatchPayloadTooLong)
+            std::fprintf(stderr, "[sqeazy]\t lz4: %llu payload bytes overflow the reference's int byte count\n", (unsigned long long)r[2]);
+        else
+            std::fprintf(stderr, "[sqeazy]\t internal error: volume %u of the batch was not finished (status %llu)\n", vol, (unsigned long long)r[0]);
+        rc = 1;
+    }
+    return rc;
+}
+
+int encode_batch_on_device(Context& cx, const char* pipeline, const BatchAdmit& a, const void* const* d_srcs, const long* shapes, unsigned rank, int elem_size,
+                           int nvolumes, void* d_dst, uint64_t slot_capacity, long* offsets, long* lengths, int nthreads, hipStream_t stream)
+{
+    for (int i = 0; i < nvolumes; ++i)
+        if (reinterpret_cast<uintptr_t>(d_srcs[i]) % (uintptr_t)elem_size) { std::fprintf(stderr, "[sqeazy]\t volume %d: source not aligned to the voxel size\n", i); return 1; }
+    const std::vector<Stage>& st = a.pipe.stages;
+    const bool transpose = st.size() == 2 && st[0].kind == StageKind::bitswap1 && st[1].kind == StageKind::lz4;
+    const bool joint_pipeline = transpose || (st.size() == 1 && st[0].kind == StageKind::lz4);
+    sqy::Lz4BatchPlan plan;
+    plan.group_of.assign((size_t)nvolumes, -1);
+    if (joint_pipeline && g_opt.encode_batch_joint.load()) {
+        std::vector<uint64_t> totals((size_t)nvolumes);
+        for (int i = 0; i < nvolumes; ++i) totals[(size_t)i] = a.len[(size_t)i] * (uint64_t)elem_size;
+        plan = sqy::lz4_batch_plan(st.back().lz4, totals, a.pipe.nthreads, (uint64_t)g_opt.encode_batch_group_bytes.load(),
+                                   (uint64_t)g_opt.encode_batch_joint_max_bytes.load());
+    }
+    int rc = 0;
+    if (!plan.groups.empty()) {
+        DrainOnExit drain{stream, &cx.pending};
+        // pinned: a record per volume of the batch (3 words), behind them the staging area of the largest group's upload
+        uint64_t staging = 0;
+        for (const sqy::Lz4BatchGroup& g : plan.groups)
+            staging = std::max<uint64_t>(staging, g.chunks.size() * (sizeof(sqy::Lz4BatchChunk) + 4) + g.vols.size() * (sizeof(sqy::Lz4BatchVolume) + sizeof(sqy::Bitswap1Job) + 4 + 4096) + 256);
+        const uint64_t records_bytes = ((uint64_t)nvolumes * 24 + 63) & ~(uint64_t)63;
+        if (cx.ws.batch_host.ensure(records_bytes + staging)) return 1;
+        uint64_t* records = static_cast<uint64_t*>(cx.ws.batch_host.p);
+        std::memset(records, 0, records_bytes);
+        for (const sqy::Lz4BatchGroup& g : plan.groups)
+            if (encode_batch_group(cx, a, g, transpose, elem_size, d_srcs, static_cast<uint8_t*>(d_dst), slot_capacity, offsets, lengths, records,
+                                   static_cast<uint8_t*>(cx.ws.batch_host.p) + records_bytes, stream))
+                rc = 1;
+        if (g_prof_on.load()) prof_collect(cx.pending);
+    }
+    // every other volume: the single-call path into its slot, in volume order (the blob where the call leaves it inside the slot)
+    for (int i = 0; i < nvolumes && rc == 0; ++i) {
+        if (plan.group_of[(size_t)i] >= 0) continue;
+        long at = 0, len = 0;
+        rc = encode_on_device(cx, pipeline, d_srcs[i], shapes + (size_t)i * rank, rank, elem_size, static_cast<uint8_t*>(d_dst) + (uint64_t)i * slot_capacity,
+                              slot_capacity, &len, nthreads, stream, &at);
+        if (rc == 0) { offsets[i] = (long)((uint64_t)i * slot_capacity) + at; lengths[i] = len; }
+    }
+    if (rc) for (int i = 0; i < nvolumes; ++i) { offsets[i] = 0; lengths[i] = 0; }
+    return rc;
+}
+
+int encode_batch_device(const char* pipeline, const void* const* d_srcs, const long* shapes, unsigned rank, int elem_size, int nvolumes, void* d_dst,
+                        long slot_capacity, long* offsets, long* lengths, int nthreads, void* hip_stream)
+{
+    BatchAdmit a;
+    if (admit_batch(pipeline, d_srcs, shapes, rank, elem_size, nvolumes, d_dst, slot_capacity, offsets, lengths, nthreads, &a)) return 1;
+    ContextLease lease;
+    if (!lease.ctx) { std::fprintf(stderr, "[sqeazy]\t no usable HIP device\n"); return 1; }
+    return encode_batch_on_device(*lease.ctx, pipeline, a, d_srcs, shapes, rank, elem_size, nvolumes, d_dst, (uint64_t)slot_capacity, offsets, lengths, nthreads,
+                                  static_cast<hipStream_t>(hip_stream));
+}
+
+// the host-pointer variant (not tuned): every volume staged up, one call of the device driver, the blobs brought back
+int encode_batch_from_host(const char* pipeline, const char* const* srcs, const long* shapes, unsigned rank, int elem_size, int nvolumes, char* dst,
+                           long slot_capacity, long* offsets, long* lengths, int nthreads)
+{
+    BatchAdmit a;
+    if (admit_batch(pipeline, reinterpret_cast<const void* const*>(srcs), shapes, rank, elem_size, nvolumes, dst, slot_capacity, offsets, lengths, nthreads, &a)) return 1;
+    if (!device_present()) { std::fprintf(stderr, "[sqeazy]\t no MI355X (HIP device) visible: sqeazy_amd has no CPU path\n"); return 1; }
+    ContextLease lease;
+    if (!lease.ctx) { std::fprintf(stderr, "[sqeazy]\t no usable HIP device\n"); return 1; }
+    Workspace* ws = &lease.ctx->ws;
+    hipStream_t stream = lease.ctx->own_stream();
+    if (!stream) { std::fprintf(stderr, "[sqeazy]\t no HIP stream\n"); return 1; }
+    std::vector<uint64_t> at((size_t)nvolumes);
+    uint64_t raw = 0;
+    for (int i = 0; i < nvolumes; ++i) { at[(size_t)i] = raw; raw += (a.len[(size_t)i] * (uint64_t)elem_size + 15) & ~(uint64_t)15; }
+    if (ws->io_src.ensure(std::max<uint64_t>(raw, 16)) || ws->io_dst.ensure((uint64_t)nvolumes * (uint64_t)slot_capacity)) return 1;
+    int dev_id = 0;
+    SQY_HIP(hipGetDevice(&dev_id));
+    std::vector<const void*> d_srcs((size_t)nvolumes);
+    for (int i = 0; i < nvolumes; ++i) {
+        d_srcs[(size_t)i] = static_cast<char*>(ws->io_src.p) + at[(size_t)i];
+        if (!lease.ctx->stager.copy(const_cast<void*>(d_srcs[(size_t)i]), const_cast<char*>(srcs[i]), a.len[(size_t)i] * (uint64_t)elem_size, true, dev_id)) {
+            std::fprintf(stderr, "[sqeazy]\t host to device transfer failed\n");
+            return 1;
+        }
+    }
+    const int rc = encode_batch_on_device(*lease.ctx, pipeline, a, d_srcs.data(), shapes, rank, elem_size, nvolumes, ws->io_dst.p, (uint64_t)slot_capacity, offsets,
+                                          lengths, nthreads, stream);
+    if (rc) return rc;
+    for (int i = 0; i < nvolumes; ++i)
+        if (!lease.ctx->stager.copy(static_cast<char*>(ws->io_dst.p) + offsets[i], dst + offsets[i], (size_t)lengths[i], false, dev_id)) {
+            std::fprintf(stderr, "[sqeazy]\t device to host transfer failed\n");
+            for (int k = 0; k < nvolumes; ++k) { offsets[k] = 0; lengths[k] = 0; }
+            return 1;
+        }
+    return 0;
+}
+
 int max_compressed_length(const char* pipeline, long pipeline_length, long* length, int elem_size, uint64_t raw_bytes)
 {
     if (!pipeline || !length || pipeline_length < 0) return 1;
@@ -2919,6 +3167,38 @@ int SQYAMD_PipelineEncode_Slabs_UI8_Device(const char* pipeline, const void* d_s
     });
 }
 
+int SQYAMD_PipelineEncode_Batch_UI16_Device(const char* pipeline, const void* const* d_srcs, const long* shapes, unsigned shape_size, int nvolumes,
+                                            void* d_dst, long slot_capacity, long* offsets, long* lengths, int nthreads, void* hip_stream)
+{
+    return guarded([&]() -> int {
+    return encode_batch_device(pipeline, d_srcs, shapes, shape_size, 2, nvolumes, d_dst, slot_capacity, offsets, lengths, nthreads, hip_stream);
+    });
+}
+
+int SQYAMD_PipelineEncode_Batch_UI8_Device(const char* pipeline, const void* const* d_srcs, const long* shapes, unsigned shape_size, int nvolumes,
+                                           void* d_dst, long slot_capacity, long* offsets, long* lengths, int nthreads, void* hip_stream)
+{
+    return guarded([&]() -> int {
+    return encode_batch_device(pipeline, d_srcs, shapes, shape_size, 1, nvolumes, d_dst, slot_capacity, offsets, lengths, nthreads, hip_stream);
+    });
+}
+
+int SQYAMD_PipelineEncode_Batch_UI16(const char* pipeline, const char* const* srcs, const long* shapes, unsigned shape_size, int nvolumes, char* dst,
+                                     long slot_capacity, long* offsets, long* lengths, int nthreads)
+{
+    return guarded([&]() -> int {
+    return encode_batch_from_host(pipeline, srcs, shapes, shape_size, 2, nvolumes, dst, slot_capacity, offsets, lengths, nthreads);
+    });
+}
+
+int SQYAMD_PipelineEncode_Batch_UI8(const char* pipeline, const char* const* srcs, const long* shapes, unsigned shape_size, int nvolumes, char* dst,
+                                    long slot_capacity, long* offsets, long* lengths, int nthreads)
+{
+    return guarded([&]() -> int {
+    return encode_batch_from_host(pipeline, srcs, shapes, shape_size, 1, nvolumes, dst, slot_capacity, offsets, lengths, nthreads);
+    });
+}
+
 int SQYAMD_PipelineEncode_UI16_Cap(const char* pipeline, const char* src, long* shape, unsigned shape_size, char* dst,
                                    long dst_capacity, long* dstlength, int nthreads)
 {
@@ -3043,6 +3323,8 @@ int SQYAMD_Set_Option(const char* name, long value)
     else if (o == &g_opt.transpose_blocks_per_cu) { if (value < 1 || value > 64) return 1; sqy::set_bitswap1_blocks_per_cu(value); }
     else if (o == &g_opt.host_l2_bytes) { if (value < 0 || value > (long)UINT32_MAX) return 1; }
     else if (o == &g_opt.stage_lanes) { if (value < 0 || value > 2) return 1; }
+    else if (o == &g_opt.encode_batch_group_bytes) { if (value < 1 || value > kBatchBytesMax) return 1; }
+    else if (o == &g_opt.encode_batch_joint_max_bytes) { if (value < 0 || value > kBatchBytesMax) return 1; }
     else if (o == &g_opt.lane_calls || o == &g_opt.lane_backlog_fallbacks || o == &g_opt.lane_blocked_fallbacks) { if (value != 0) return 1; }
     else if (o == &g_opt.parse_lanes) { if (value < 1 || value > sqy::LanePicker::kMaxLanes) return 1; }
     else if (o == &g_opt.call_stamps) {

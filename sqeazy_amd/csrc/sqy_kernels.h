@@ -157,6 +157,35 @@ hipError_t launch_lz4_frame_gather(const uint8_t* in, uint64_t total, uint32_t c
                                    uint64_t frame_bytes = 0, const Lz4Block* blocks = nullptr, const uint32_t* dup_of = nullptr,
                                    uint64_t in_stride = 0, bool raw_from_scratch = false);
 
+// ---- batch encode (SQYAMD_PipelineEncode_Batch_*): the volumes of a group share one launch of every kernel ----
+// bitswap1 of job j: `len` voxels at `in` (any voxel-aligned address) into planes + tail at `out` (16-byte aligned), laid out as
+// launch_bitswap1_u16 / _u8 lay them out.  first_tile: njobs + 1 words, the prefix sums of batch_bitswap1_tiles(len) -- workgroup ->
+// (job, tile) by a binary search over it
+struct Bitswap1Job { const void* in; void* out; uint64_t len; };
+uint32_t batch_bitswap1_tiles(uint64_t len);
+hipError_t launch_bitswap1_batch(const Bitswap1Job* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ntiles, int elem_size, hipStream_t stream);
+// One entry of the joint chunk table (sqy::Lz4BatchChunkPlan, sqy_pipeline.hpp): chunk e is the n bytes at in + off, compressed on its
+// own into scratch + slot * stride, csize[e] (0: stored); redo as for launch_lz4_chunks (nentries + 1 words, the launcher zeroes redo[0])
+struct Lz4BatchChunk { uint64_t off; uint32_t n, vol, slot, pad; };
+hipError_t launch_lz4_chunks_table(const uint8_t* in, const Lz4BatchChunk* d_table, uint32_t nentries, uint8_t* scratch, uint64_t stride, uint32_t* csize,
+                                   uint32_t* redo, hipStream_t stream);
+hipError_t launch_lz4_chunks_table_dense(const uint8_t* in, const Lz4BatchChunk* d_table, uint8_t* scratch, uint64_t stride, uint32_t* csize,
+                                         uint32_t* redo, uint32_t redo_count, hipStream_t stream);
+// Volume v of a group: table entries [first_chunk, first_chunk + nchunks); its blob goes to out + dst_at, at most capacity bytes; the
+// sqy header is text[text_at, +prefix_len) | payload bytes in decimal | text[text_at + prefix_len, +suffix_len), padded in front to a
+// multiple of elem_size; record (3 words of pinned host memory per volume, index `record`): status, blob bytes, payload bytes
+struct Lz4BatchVolume { uint64_t dst_at, capacity; uint32_t first_chunk, nchunks, text_at, prefix_len, suffix_len, elem_size, record, pad; };
+constexpr uint64_t kBatchDone = 1, kBatchNoRoom = 2, kBatchPayloadTooLong = 3;
+// scan (one workgroup per volume): frame_off[e] = where entry e's frame starts behind its volume's header, vinfo[2 v] = payload bytes,
+// vinfo[2 v + 1] = header bytes | status << 32.  gather: every frame behind its volume's header ([04 22 4D 18 | 40 | BD | HC][u32
+// size][data][00 00 00 00]), the header and the record -- nothing at all for a volume whose blob does not fit its capacity
+hipError_t launch_lz4_batch_scan(const Lz4BatchChunk* d_table, const Lz4BatchVolume* d_vols, uint32_t nvols, const uint32_t* csize,
+                                 uint64_t* frame_off, uint64_t* vinfo, hipStream_t stream);
+hipError_t launch_lz4_batch_gather(const uint8_t* in, const Lz4BatchChunk* d_table, uint32_t nentries, uint32_t max_chunk, const Lz4BatchVolume* d_vols,
+                                   const uint32_t* d_vol_of /* per entry: index into d_vols */, const uint8_t* scratch, uint64_t stride,
+                                   const uint32_t* csize, const uint64_t* frame_off, const uint64_t* vinfo, const char* d_text, uint8_t* out,
+                                   uint32_t bd_byte, uint32_t hc_byte, uint64_t* records, hipStream_t stream);
+
 // quantiser: 65536-bin histogram of u16 voxels (histo is zeroed by the launcher), and out[i] = lut[in[i]]
 // background removal, 1- or 2-byte voxels of a {Z, Y, X} volume
 // rmestbkrd (encoders/remove_estimated_background_scheme_impl.hpp:71-110): four face histograms (frames z = 0 and Z-1: their first

@@ -522,6 +522,117 @@ void bitswap1_u8_generic(const uint8_t* __restrict__ in, uint8_t* __restrict__ o
     if (blockIdx.x == 0 && w < len - L) out[L + w] = in[L + w];
 }
 
+// Batch encode: the bit-plane transposes of many volumes with one launch (SQYAMD_PipelineEncode_Batch_*).  Job j's planes and tail
+// are bitswap1_u16_generic's / bitswap1_u8_generic's.  A workgroup is one tile of BSWB_TILE_VOX voxels of one job (first_tile: the
+// jobs' tile counts as prefix sums, searched); a thread owns 128 voxels in a row -- 8 words of 16 or 16 words of 8 -- and with them
+// 16 bytes of every plane: sixteen-byte loads and stores where the job's pointers and plane size allow, word by word where not.
+constexpr uint32_t BSWB_THREAD_VOX = 128, BSWB_TILE_VOX = 256 * BSWB_THREAD_VOX;
+
+template <int ELEM>
+__global__ __launch_bounds__(256)
+void bitswap1_batch_kernel(const Bitswap1Job* __restrict__ jobs, const uint32_t* __restrict__ first_tile, uint32_t njobs)
+{
+    constexpr uint32_t W = 8 * ELEM, WPT = BSWB_THREAD_VOX / W;        // voxels per word, words per thread
+    uint32_t lo = 0, hi = njobs;                                      // first_tile[lo] <= blockIdx.x < first_tile[hi]
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (first_tile[mid] <= blockIdx.x) lo = mid; else hi = mid;
+    }
+    const Bitswap1Job job = jobs[lo];
+    const uint32_t tile = blockIdx.x - first_tile[lo], tid = threadIdx.x;
+    const uint64_t seg = job.len / W, L = seg * W;                    // words per plane; voxels in the planes
+    const uint8_t* __restrict__ in = static_cast<const uint8_t*>(job.in);
+    uint8_t* __restrict__ out = static_cast<uint8_t*>(job.out);
+    if (tile == 0 && tid < job.len - L) {                             // tail voxels [L, len): copied verbatim
+        if (ELEM == 2) reinterpret_cast<uint16_t*>(out)[L + tid] = reinterpret_cast<const uint16_t*>(in)[L + tid];
+        else out[L + tid] = in[L + tid];
+    }
+    const uint64_t w0 = ((uint64_t)tile * 256u + tid) * WPT;
+    if (w0 >= seg) return;
+    const uint64_t plane_bytes = seg * ELEM;
+    const bool wide = w0 + WPT <= seg && ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out) | plane_bytes) & 15u) == 0;
+    if constexpr (ELEM == 2) {
+        // plane 15 - b, word w: bit 15 - j = bit b of voxel 16 w + j
+        auto word_planes = [](const uint32_t* v, uint32_t* acc) {
+#pragma unroll
+            for (int b = 0; b < 16; ++b) {
+                uint32_t a = 0;
+#pragma unroll
+                for (int j = 0; j < 16; ++j) a |= ((v[j] >> b) & 1u) << (15 - j);
+                acc[b] = a;
+            }
+        };
+        if (wide) {
+            uint32_t res[16][4];
+#pragma unroll
+            for (int b = 0; b < 16; ++b) { res[b][0] = 0; res[b][1] = 0; res[b][2] = 0; res[b][3] = 0; }
+            const uint4* src = reinterpret_cast<const uint4*>(in + w0 * 32u);
+#pragma unroll
+            for (uint32_t i = 0; i < WPT; ++i) {
+                const uint4 x = src[2 * i], y = src[2 * i + 1];
+                const uint32_t d[8] = {x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w};
+                uint32_t v[16], acc[16];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) { v[2 * j] = d[j] & 0xffffu; v[2 * j + 1] = d[j] >> 16; }
+                word_planes(v, acc);
+#pragma unroll
+                for (int b = 0; b < 16; ++b) res[b][i >> 1] |= acc[b] << (16u * (i & 1u));
+            }
+#pragma unroll
+            for (int b = 0; b < 16; ++b)
+                *reinterpret_cast<uint4*>(out + (uint64_t)(15 - b) * plane_bytes + w0 * 2u) = make_uint4(res[b][0], res[b][1], res[b][2], res[b][3]);
+        } else {
+            const uint16_t* in16 = reinterpret_cast<const uint16_t*>(in);
+            uint16_t* out16 = reinterpret_cast<uint16_t*>(out);
+            for (uint64_t w = w0; w < w0 + WPT && w < seg; ++w) {
+                uint32_t v[16], acc[16];
+#pragma unroll
+                for (int j = 0; j < 16; ++j) v[j] = in16[w * 16 + j];
+                word_planes(v, acc);
+#pragma unroll
+                for (int b = 0; b < 16; ++b) out16[(uint64_t)(15 - b) * seg + w] = (uint16_t)acc[b];
+            }
+        }
+    } else {
+        // byte b of the result: bit b of the word's eight voxels, voxel j at bit 7 - j (bitswap1_u8_generic)
+        auto word_planes = [](uint64_t x) -> uint64_t {
+            uint64_t t = x, y;
+            y = (t ^ (t >> 7)) & 0x00AA00AA00AA00AAull; t = t ^ y ^ (y << 7);
+            y = (t ^ (t >> 14)) & 0x0000CCCC0000CCCCull; t = t ^ y ^ (y << 14);
+            y = (t ^ (t >> 28)) & 0x00000000F0F0F0F0ull; t = t ^ y ^ (y << 28);
+            const uint32_t r0 = __brev((uint32_t)t), r1 = __brev((uint32_t)(t >> 32));      // (bits reversed in every byte, bytes swapped)
+            return (uint64_t)__builtin_bswap32(r0) | ((uint64_t)__builtin_bswap32(r1) << 32);
+        };
+        if (wide) {
+            uint32_t res[8][4];
+#pragma unroll
+            for (int b = 0; b < 8; ++b) { res[b][0] = 0; res[b][1] = 0; res[b][2] = 0; res[b][3] = 0; }
+            const uint4* src = reinterpret_cast<const uint4*>(in + w0 * 8u);
+#pragma unroll
+            for (uint32_t i = 0; i < WPT; i += 2) {
+                const uint4 x = src[i >> 1];
+                const uint64_t t[2] = {word_planes((uint64_t)x.x | ((uint64_t)x.y << 32)), word_planes((uint64_t)x.z | ((uint64_t)x.w << 32))};
+#pragma unroll
+                for (uint32_t u = 0; u < 2; ++u)
+#pragma unroll
+                    for (int b = 0; b < 8; ++b) res[b][(i + u) >> 2] |= ((uint32_t)(t[u] >> (8 * b)) & 0xffu) << (8u * ((i + u) & 3u));
+            }
+#pragma unroll
+            for (int b = 0; b < 8; ++b)
+                *reinterpret_cast<uint4*>(out + (uint64_t)(7 - b) * plane_bytes + w0) = make_uint4(res[b][0], res[b][1], res[b][2], res[b][3]);
+        } else {
+            for (uint64_t w = w0; w < w0 + WPT && w < seg; ++w) {
+                uint64_t x = 0;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) x |= (uint64_t)in[w * 8 + j] << (8 * j);
+                const uint64_t t = word_planes(x);
+#pragma unroll
+                for (int b = 0; b < 8; ++b) out[(uint64_t)(7 - b) * seg + w] = (uint8_t)(t >> (8 * b));
+            }
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // diff3x3x1.  out = in, except at flat indices idx in  U_{z in [1,min(X,Z)), y in [1,Y-1)}
 // [z*Y*X + y*X + 1, +Z-2)  where out[idx] = in[idx] - (wrapping 9-neighbour sum of plane z-1)/9.
@@ -1160,7 +1271,10 @@ __device__ __forceinline__ uint32_t lz4_linked_tag_shift(uint32_t max_block)
     return 31u - (32u - (uint32_t)__builtin_clz(pmax - 1));
 }
 
-template <bool LINKED, bool DENSE, bool ACCEL = false>
+// TABLE = true (batch encode, LINKED = false, ACCEL = false): chunk e of the launch is entry e of a joint chunk table -- `blocks` points at
+// Lz4BatchChunk entries instead: the entry's n bytes at in + off, the output at scratch + slot * stride, csize[e]; total, chunk and
+// in_stride are not read.  Its own instantiations: the ones without a table keep their code.
+template <bool LINKED, bool DENSE, bool ACCEL = false, bool TABLE = false>
 __global__ __launch_bounds__(64)
 void lz4_chunks_kernel(const uint8_t* __restrict__ in, uint64_t total, uint32_t chunk, uint64_t in_stride,
                        uint8_t* __restrict__ scratch, uint64_t stride, uint32_t* __restrict__ csize,
@@ -1179,7 +1293,7 @@ void lz4_chunks_kernel(const uint8_t* __restrict__ in, uint64_t total, uint32_t 
     __shared__ __attribute__((aligned(16))) uint8_t stage[LZ4_OB];
     const int lane = threadIdx.x;
     if (!LINKED && !DENSE && dup_of && dup_of[blockIdx.x] != blockIdx.x) return;     // byte-identical to an earlier chunk (lz4_dedupe_*): its frame is that chunk's
-    if constexpr (!LINKED && !DENSE && !ACCEL) if (dd.chunk_key) {                     // the same decision, made here (round 4)
+    if constexpr (!LINKED && !DENSE && !ACCEL && !TABLE) if (dd.chunk_key) {                     // the same decision, made here (round 4)
         if (lz4_chunk_dedupe(in, chunk, in_stride, total, blockIdx.x, dd, threadIdx.x)) return;
         // The holes filled above are read back below by this same wavefront (loads and LDS-DMA): its stores have to have left the
         // wave (vmcnt) -- nothing more: nobody has read those addresses since the kernel began, so no cache holds an older copy.
@@ -1219,6 +1333,7 @@ void lz4_chunks_kernel(const uint8_t* __restrict__ in, uint64_t total, uint32_t 
     int64_t low_in = 0, low_dict = 0;                          // catch-up limits, same coordinates
     bool fresh = true;
     const uint8_t* __restrict__ src;
+    uint64_t tab_slot = 0;                                     // TABLE: the entry's scratch slot
     if (LINKED) {
         const Lz4Block bd = blocks[bi];
         n = bd.n;
@@ -1239,12 +1354,19 @@ void lz4_chunks_kernel(const uint8_t* __restrict__ in, uint64_t total, uint32_t 
     } else {
         // frame_shuffle in front of the sink: the stream is the frames of `in` in the order fmap gives (a chunk never straddles
         // two frames, the host checks fbytes % chunk == 0), read in place instead of gathered into a copy first
+        if constexpr (TABLE) {
+            const Lz4BatchChunk e = reinterpret_cast<const Lz4BatchChunk*>(blocks)[blk];
+            src = in + e.off;
+            n = e.n;
+            tab_slot = e.slot;
+        } else {
         const uint64_t lin = blk * chunk;
         // (in_stride: chunk k of the stream starts at in + k * in_stride -- chunk bytes apart, or chunk + 15 when the stage in
         // front wrote the stream as frame bodies in place)
         src = fmap ? in + fmap[lin / fbytes] * fbytes + lin % fbytes : in + blk * in_stride;
         const uint64_t left = total - blk * chunk;
         n = (uint32_t)(left < chunk ? left : chunk);
+        }
     }
     const uint32_t pend = p0 + n;                              // end of the block
     // bytes the backward catch-up may take on the match side (liblz4: match > lowLimit)
@@ -1253,7 +1375,7 @@ void lz4_chunks_kernel(const uint8_t* __restrict__ in, uint64_t total, uint32_t 
         const int64_t r = (int64_t)mt - (mt >= p0 ? low_in : low_dict);
         return r < 0 ? 0u : (r > 0x7fffffff ? 0x7fffffffu : (uint32_t)r);
     };
-    uint8_t* __restrict__ dst = scratch + blk * stride;
+    uint8_t* __restrict__ dst = scratch + (TABLE ? tab_slot : blk) * stride;
 
     Lz4Window w;
     w.src = (glb_u8*)src; w.win = (lds_u8*)ring; w.n = pend; w.whi = p0; w.wlo = p0; w.nif = 0; w.lane16 = (uint32_t)lane * 16u;
@@ -1308,7 +1430,7 @@ void lz4_chunks_kernel(const uint8_t* __restrict__ in, uint64_t total, uint32_t 
     uint32_t dgq_U = 0xffffffffu;
 #pragma unroll
     for (int k = 0; k < DG_AHEAD; ++k) dgq[k] = 0u;
-    if constexpr (!LINKED && !DENSE && !ACCEL) {
+    if constexpr (!LINKED && !DENSE && !ACCEL && !TABLE) {
         if (dd.digest && n == chunk && dd.holes_map &&
             (uint32_t)dd.holes_map[blk * (1u + ((chunk >> 10) + 63u) / 64u)] == 0u) {
             dgp = dd.digest + blk * (uint64_t)dd.digest_stride;
@@ -2600,6 +2722,139 @@ void lz4_inplace_finish_kernel(uint8_t* __restrict__ out, uint64_t t0, uint64_t 
         record[6] = 0;
         record[0] = 1;
     }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Batch encode (SQYAMD_PipelineEncode_Batch_*): frame scan and gather for the volumes of a group, one launch each.
+// ------------------------------------------------------------------------------------------------
+// One workgroup per volume: the frame offsets of its table entries relative to its payload, the payload's size, the header's length
+// (prefix | payload bytes in decimal | suffix, padded to a multiple of the voxel size) and the verdict: kBatchDone, kBatchNoRoom (header
+// + payload do not fit the volume's capacity) or kBatchPayloadTooLong (the reference counts payload bytes in an int)
+__global__ __launch_bounds__(256)
+void lz4_batch_scan_kernel(const Lz4BatchChunk* __restrict__ table, const Lz4BatchVolume* __restrict__ vols, const uint32_t* __restrict__ csize,
+                           uint64_t* __restrict__ frame_off, uint64_t* __restrict__ vinfo)
+{
+    __shared__ uint64_t wsum[4];
+    __shared__ uint64_t carry_s;
+    const Lz4BatchVolume v = vols[blockIdx.x];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    if (tid == 0) carry_s = 0;
+    __syncthreads();
+    for (uint32_t base = 0; base < v.nchunks; base += 256u) {
+        const uint32_t k = base + tid;
+        uint64_t sz = 0;
+        if (k < v.nchunks) {
+            const uint32_t e = v.first_chunk + k, c = csize[e];
+            sz = 7 + 4 + (c ? c : table[e].n) + 4;
+        }
+        uint64_t x = sz;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint64_t y = __shfl_up(x, d);
+            if (lane >= (uint32_t)d) x += y;
+        }
+        if (lane == 63u) wsum[wave] = x;
+        __syncthreads();
+        uint64_t woff = 0;
+        for (uint32_t w = 0; w < wave; ++w) woff += wsum[w];
+        const uint64_t carry = carry_s;
+        if (k < v.nchunks) frame_off[v.first_chunk + k] = carry + woff + x - sz;
+        __syncthreads();
+        if (tid == 255u) carry_s = carry + woff + x;
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const uint64_t payload = carry_s;
+        uint32_t nd = 0;
+        { uint64_t q = payload; do { ++nd; q /= 10; } while (q); }
+        const uint64_t text = (uint64_t)v.prefix_len + nd + v.suffix_len;
+        const uint64_t hdr_len = text + (v.elem_size - text % v.elem_size) % v.elem_size;      // (sqeazy_header.hpp:172-178)
+        const uint64_t status = payload > 0x7fffffffull ? kBatchPayloadTooLong : (hdr_len + payload > v.capacity ? kBatchNoRoom : kBatchDone);
+        vinfo[2 * blockIdx.x] = payload;
+        vinfo[2 * blockIdx.x + 1] = hdr_len | (status << 32);
+    }
+}
+
+// One workgroup per (table entry, 32 KiB slice), as lz4_frame_gather_kernel; the workgroup of a volume's first entry and slice also
+// writes the volume's header (as lz4_inplace_finish_kernel formats it) and its record.  A volume that is not kBatchDone gets its
+// record and not a byte else.
+__global__ __launch_bounds__(256)
+void lz4_batch_gather_kernel(const uint8_t* __restrict__ in, const Lz4BatchChunk* __restrict__ table, const Lz4BatchVolume* __restrict__ vols,
+                             const uint32_t* __restrict__ vol_of, const uint8_t* __restrict__ scratch, uint64_t stride,
+                             const uint32_t* __restrict__ csize, const uint64_t* __restrict__ frame_off, const uint64_t* __restrict__ vinfo,
+                             const char* __restrict__ text, uint8_t* __restrict__ out, uint32_t bd_byte, uint32_t hc_byte, uint32_t slices_per_chunk,
+                             uint64_t* __restrict__ records)
+{
+    const uint32_t e = blockIdx.x / slices_per_chunk, slice = blockIdx.x % slices_per_chunk, tid = threadIdx.x;
+    const Lz4BatchChunk ce = table[e];
+    const uint32_t lv = vol_of[e];
+    const Lz4BatchVolume v = vols[lv];
+    const uint64_t payload = vinfo[2 * lv], hs = vinfo[2 * lv + 1];
+    const uint64_t hdr_len = hs & 0xffffffffull, status = hs >> 32;
+    const bool first = e == v.first_chunk && slice == 0;
+    if (first && tid == 0) {
+        uint64_t* r = records + 3 * (uint64_t)v.record;
+        r[1] = status == kBatchDone ? hdr_len + payload : 0;
+        r[2] = payload;
+        r[0] = status;
+    }
+    if (status != kBatchDone) return;
+    uint8_t* __restrict__ blob = out + v.dst_at;
+    if (first) {
+        uint32_t nd = 0;
+        { uint64_t q = payload; do { ++nd; q /= 10; } while (q); }
+        const uint64_t pad = hdr_len - ((uint64_t)v.prefix_len + nd + v.suffix_len);
+        const char* __restrict__ t = text + v.text_at;
+        for (uint64_t i = tid; i < hdr_len; i += 256) {
+            uint8_t c;
+            if (i < pad) c = ' ';
+            else if (i < pad + v.prefix_len) c = (uint8_t)t[i - pad];
+            else if (i < pad + v.prefix_len + nd) {                                      // the payload's decimal digits, most significant first
+                uint64_t q = payload;
+                for (uint64_t k = i - pad - v.prefix_len + 1; k < nd; ++k) q /= 10;
+                c = (uint8_t)('0' + q % 10);
+            }
+            else c = (uint8_t)t[v.prefix_len + (i - pad - v.prefix_len - nd)];
+            blob[i] = c;
+        }
+    }
+    const uint32_t c = csize[e];
+    const uint32_t body = c ? c : ce.n;
+    const uint8_t* __restrict__ s = c ? scratch + (uint64_t)ce.slot * stride : in + ce.off;
+    uint8_t* __restrict__ d = blob + hdr_len + frame_off[e];
+    if (slice == 0 && tid < 15) {
+        const uint32_t field = c ? c : (ce.n | 0x80000000u);
+        uint8_t b = 0;
+        uint32_t o = tid;
+        switch (tid) {
+            case 0: b = 0x04; break; case 1: b = 0x22; break; case 2: b = 0x4D; break; case 3: b = 0x18; break;
+            case 4: b = 0x40; break; case 5: b = (uint8_t)bd_byte; break; case 6: b = (uint8_t)hc_byte; break;
+            case 7: b = (uint8_t)field; break; case 8: b = (uint8_t)(field >> 8); break;
+            case 9: b = (uint8_t)(field >> 16); break; case 10: b = (uint8_t)(field >> 24); break;
+            default: b = 0; o = 11 + body + (tid - 11); break;                                          // end mark
+        }
+        d[o] = b;
+    }
+    const uint32_t begin = slice * GATHER_SLICE;
+    if (begin >= body) return;
+    const uint32_t end = (begin + GATHER_SLICE < body) ? begin + GATHER_SLICE : body;
+    uint8_t* __restrict__ dd = d + 11 + begin;
+    const uint8_t* __restrict__ ss = s + begin;
+    uint32_t len = end - begin;
+    const uint32_t head0 = (uint32_t)((16 - (reinterpret_cast<uintptr_t>(dd) & 15)) & 15);          // up to the destination's 16-byte boundary
+    const uint32_t head = head0 < len ? head0 : len;
+    if (tid < head) dd[tid] = ss[tid];
+    dd += head; ss += head; len -= head;
+    const uint32_t nvec = len >> 4;
+    for (uint32_t i0 = tid; i0 < nvec; i0 += 1024) {
+        uint4 q[4];
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j) if (i0 + j * 256u < nvec) q[j] = ld_u128(ss + (size_t)(i0 + j * 256u) * 16);
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j) if (i0 + j * 256u < nvec) *reinterpret_cast<uint4*>(dd + (size_t)(i0 + j * 256u) * 16) = q[j];
+    }
+    const uint32_t done = nvec << 4;
+    if (tid < len - done) dd[done + tid] = ss[done + tid];
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -6121,6 +6376,66 @@ hipError_t launch_lz4_chunks_dense(const uint8_t* in, uint64_t total, uint32_t c
     if (in_stride == 0) in_stride = chunk;
     hipLaunchKernelGGL((lz4_chunks_kernel<false, true>), dim3(redo_count), dim3(64), 0, stream, in, total, chunk, in_stride, scratch, stride, csize,
                        frame_map, frame_bytes, (const Lz4Block*)nullptr, (const uint32_t*)nullptr, 0u, redo, (const uint32_t*)nullptr, 1u, Lz4DedupeArgs{} SQY_DIAG_NULL);
+    return hipGetLastError();
+}
+
+hipError_t launch_lz4_chunks_table(const uint8_t* in, const Lz4BatchChunk* d_table, uint32_t nentries, uint8_t* scratch, uint64_t stride, uint32_t* csize,
+                                   uint32_t* redo, hipStream_t stream)
+{
+    if (nentries == 0) return hipSuccess;
+    if (!d_table || !redo) return hipErrorInvalidValue;
+    const hipError_t e = hipMemsetAsync(redo, 0, sizeof(uint32_t), stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((lz4_chunks_kernel<false, false, false, true>), dim3(nentries), dim3(64), 0, stream, in, (uint64_t)0, 0u, (uint64_t)0, scratch, stride, csize,
+                       (const uint64_t*)nullptr, (uint64_t)0, reinterpret_cast<const Lz4Block*>(d_table), (const uint32_t*)nullptr, 0u, redo,
+                       (const uint32_t*)nullptr, 1u, Lz4DedupeArgs{} SQY_DIAG_NULL);
+    return hipGetLastError();
+}
+
+hipError_t launch_lz4_chunks_table_dense(const uint8_t* in, const Lz4BatchChunk* d_table, uint8_t* scratch, uint64_t stride, uint32_t* csize,
+                                         uint32_t* redo, uint32_t redo_count, hipStream_t stream)
+{
+    if (redo_count == 0) return hipSuccess;
+    if (!d_table || !redo) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((lz4_chunks_kernel<false, true, false, true>), dim3(redo_count), dim3(64), 0, stream, in, (uint64_t)0, 0u, (uint64_t)0, scratch, stride, csize,
+                       (const uint64_t*)nullptr, (uint64_t)0, reinterpret_cast<const Lz4Block*>(d_table), (const uint32_t*)nullptr, 0u, redo,
+                       (const uint32_t*)nullptr, 1u, Lz4DedupeArgs{} SQY_DIAG_NULL);
+    return hipGetLastError();
+}
+
+uint32_t batch_bitswap1_tiles(uint64_t len)
+{
+    const uint64_t t = (len + BSWB_TILE_VOX - 1) / BSWB_TILE_VOX;
+    return (uint32_t)(t ? t : 1);
+}
+
+hipError_t launch_bitswap1_batch(const Bitswap1Job* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ntiles, int elem_size, hipStream_t stream)
+{
+    if (njobs == 0 || ntiles == 0) return hipSuccess;
+    if (elem_size == 2) hipLaunchKernelGGL(bitswap1_batch_kernel<2>, dim3(ntiles), dim3(256), 0, stream, d_jobs, d_first_tile, njobs);
+    else if (elem_size == 1) hipLaunchKernelGGL(bitswap1_batch_kernel<1>, dim3(ntiles), dim3(256), 0, stream, d_jobs, d_first_tile, njobs);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+hipError_t launch_lz4_batch_scan(const Lz4BatchChunk* d_table, const Lz4BatchVolume* d_vols, uint32_t nvols, const uint32_t* csize,
+                                 uint64_t* frame_off, uint64_t* vinfo, hipStream_t stream)
+{
+    if (nvols == 0) return hipSuccess;
+    hipLaunchKernelGGL(lz4_batch_scan_kernel, dim3(nvols), dim3(256), 0, stream, d_table, d_vols, csize, frame_off, vinfo);
+    return hipGetLastError();
+}
+
+hipError_t launch_lz4_batch_gather(const uint8_t* in, const Lz4BatchChunk* d_table, uint32_t nentries, uint32_t max_chunk, const Lz4BatchVolume* d_vols,
+                                   const uint32_t* d_vol_of, const uint8_t* scratch, uint64_t stride, const uint32_t* csize, const uint64_t* frame_off,
+                                   const uint64_t* vinfo, const char* d_text, uint8_t* out, uint32_t bd_byte, uint32_t hc_byte, uint64_t* records,
+                                   hipStream_t stream)
+{
+    if (nentries == 0) return hipSuccess;
+    const uint32_t slices = max_chunk ? (max_chunk + GATHER_SLICE - 1) / GATHER_SLICE : 1u;
+    if ((uint64_t)nentries * slices > 0x7fffffffull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(lz4_batch_gather_kernel, dim3(nentries * slices), dim3(256), 0, stream, in, d_table, d_vols, d_vol_of, scratch, stride, csize, frame_off,
+                       vinfo, d_text, out, bd_byte, hc_byte, slices, records);
     return hipGetLastError();
 }
 

@@ -285,6 +285,44 @@ Lz4EncodeLayout lz4_encode_layout(const Lz4Params& p, uint64_t total, unsigned n
 
 static uint64_t round_up(uint64_t v, uint64_t to) { return (v + to - 1) / to * to; }
 
+Lz4BatchPlan lz4_batch_plan(const Lz4Params& p, const std::vector<uint64_t>& totals, unsigned nthreads, uint64_t group_bytes, uint64_t joint_max)
+{
+    Lz4BatchPlan plan;
+    plan.group_of.assign(totals.size(), -1);
+    uint64_t group_sum = 0;
+    for (size_t i = 0; i < totals.size(); ++i) {
+        const uint64_t total = totals[i];
+        const Lz4EncodeLayout lay = lz4_encode_layout(p, total, nthreads);
+        // (a table entry counts its bytes and its slot in 32 bits: chunks of the chunked layout are at most an LZ4 block of 4 MiB)
+        if (total == 0 || !lay.chunked() || lay.accel != 1 || total > joint_max || lay.nchunks == 0 || lay.chunk > UINT32_MAX) continue;
+        if (plan.groups.empty() || (group_sum && group_sum + total > group_bytes) ||
+            plan.groups.back().chunks.size() + lay.nchunks > (uint64_t)UINT32_MAX / 2) {
+            plan.groups.emplace_back();
+            plan.groups.back().first_chunk.push_back(0);
+            group_sum = 0;
+        }
+        Lz4BatchGroup& g = plan.groups.back();
+        const uint64_t at = round_up(g.stream_bytes, 16);
+        g.vols.push_back((uint32_t)i);
+        g.stream_at.push_back(at);
+        for (uint64_t k = 0; k < lay.nchunks; ++k) {
+            Lz4BatchChunkPlan c;
+            c.off = at + k * lay.chunk;
+            c.n = (uint32_t)std::min<uint64_t>(lay.chunk, total - k * lay.chunk);
+            c.vol = (uint32_t)i;
+            c.slot = (uint32_t)g.chunks.size();
+            g.chunks.push_back(c);
+            g.max_chunk = std::max(g.max_chunk, c.n);
+        }
+        g.first_chunk.push_back((uint32_t)g.chunks.size());
+        g.stream_bytes = at + total;
+        g.scratch_stride = round_up(g.max_chunk, 16);
+        group_sum += total;
+        plan.group_of[i] = (int32_t)(plan.groups.size() - 1);
+    }
+    return plan;
+}
+
 Lz4DedupeLayout lz4_dedupe_layout(const Lz4EncodeLayout& lay, uint64_t piece_hash_words)
 {
     Lz4DedupeLayout d;

@@ -76,6 +76,36 @@ struct Lz4EncodeLayout {
 };
 Lz4EncodeLayout lz4_encode_layout(const Lz4Params& p, uint64_t total, unsigned nthreads);
 
+// ---- batch encode (SQYAMD_PipelineEncode_Batch_*): many volumes, one launch per kernel ----
+// One entry of a group's joint chunk table; same layout as sqy::Lz4BatchChunk (sqy_kernels.h), which the kernels read.
+struct Lz4BatchChunkPlan {
+    uint64_t off;            // where the chunk starts in the group's stream workspace
+    uint32_t n;              // bytes (the last chunk of a volume may be short, wherever it sits in the table)
+    uint32_t vol;            // the volume it belongs to (index into the batch)
+    uint32_t slot;           // its scratch slot: compressed bytes at scratch + slot * scratch_stride
+    uint32_t pad = 0;
+};
+// The volumes that share one launch of every kernel.  Volume vols[j]'s LZ4 input (its stream) lies at stream_at[j] of the stream
+// workspace (16-byte aligned, stream_bytes in all) and is cut into the table entries [first_chunk[j], first_chunk[j + 1]).
+struct Lz4BatchGroup {
+    std::vector<uint32_t> vols;                 // ascending
+    std::vector<uint64_t> stream_at;
+    std::vector<uint32_t> first_chunk;          // vols.size() + 1 entries
+    std::vector<Lz4BatchChunkPlan> chunks;      // the joint chunk table, volume by volume, stream order inside a volume
+    uint64_t stream_bytes = 0;
+    uint64_t scratch_stride = 0;                // the largest chunk, rounded up to 16 bytes
+    uint32_t max_chunk = 0;
+};
+struct Lz4BatchPlan {
+    std::vector<int32_t> group_of;              // per volume: its group, -1: not joint-eligible (the single-call path takes it)
+    std::vector<Lz4BatchGroup> groups;
+};
+// totals[i]: the bytes in front of the LZ4 stage for volume i (> 0: empty volumes are refused before planning).  A volume is
+// joint-eligible when its layout (lz4_encode_layout) is `chunked` with acceleration 1 and totals[i] <= joint_max.  Eligible volumes are
+// dealt to groups in order; a group is closed when the next volume would take its streams past group_bytes (a group holds at least
+// one volume, so a volume larger than the bound gets a group of its own).
+Lz4BatchPlan lz4_batch_plan(const Lz4Params& p, const std::vector<uint64_t>& totals, unsigned nthreads, uint64_t group_bytes, uint64_t joint_max);
+
 // Frames in place: a 16-bit bitswap1 in front of lz4 writes chunk k of the plane stream into the destination at body0 + k * in_stride,
 // where it is the body of the stored frame it may become -- kLz4FrameHead bytes (frame header 7, block size field 4) in front, the end
 // mark behind: kLz4FrameGap bytes between two chunks.  t0 (>= header_max, the longest sqy header) is where frame 0 begins.
