@@ -354,18 +354,40 @@ def accel():
     print("wrote", os.path.join(GOLD, "accel.json"), "with", len(A["cases"]), "cases")
 
 
+def lz4_planted():
+    """tests/golden/lz4_planted.json: the planted streams of tests/lz4_planted.py -- per case its length and sha256 and the size and sha256 of the
+    oracle's block (no bytes); asserts oracle == liblz4 on the way where the reference driver is built"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import lz4_planted as P
+    L = {"_meta": {"generator": "oracle/gen_golden.py --lz4-planted", "block": "sqy_oracle.lz4_block_compress(data, cap=lz4_planted.block_cap(n))",
+                   "liblz4": "1.9.3 (LZ4_versionNumber 10903)" if ref.available() else "not compared"}, "cases": {}}
+    for c in P.cases():
+        d = c["data"]
+        blk = o.lz4_block_compress(d, cap=P.block_cap(len(d)))
+        if ref.available() and len(d) >= 13:
+            assert blk == ref.lz4_block(np.frombuffer(d, np.uint8), cap=P.block_cap(len(d))), c["name"]
+        L["cases"][c["name"]] = {"n": len(d), "sha256": sha(d), "block_bytes": len(blk), "block_sha256": sha(blk)}
+    with open(os.path.join(GOLD, "lz4_planted.json"), "w") as f:
+        json.dump(L, f, indent=1, sort_keys=True)
+    print("wrote", os.path.join(GOLD, "lz4_planted.json"), "with", len(L["cases"]), "cases")
+
+
 if __name__ == "__main__":
     if "--accel" in sys.argv:
         accel()
+    elif "--lz4-planted" in sys.argv:
+        lz4_planted()
     elif "--headline-slabs" in sys.argv:
         headline_slabs()
     elif "--headline-serial" in sys.argv:
         headline_serial()
     elif "--headline" in sys.argv:
+        lz4_planted()
         headline()
         headline_serial()
     else:
         main()
         accel()
+        lz4_planted()
         headline()
         headline_serial()
