@@ -8,9 +8,11 @@ Sources of truth
   * LZ4 bytes      liblz4.so.1.9.3 driven with sqeazy's call sequence (oracle/ref_driver.cpp cites
                    encoders/lz4.hpp:103-113, lz4_utils.hpp:99-274)
   * bitswap1 u16   the reference's own SSE gather, sqeazy::detail::simd_segment_broadcast
-                   (encoders/sse_utils.hpp:1365-1433), compiled in place from /root/reference
-  * everything the reference cannot produce here (needs Boost: scalar bitswap, diff3x3x1, quantiser, frame_shuffle,
-    header) is NOT in this file's "reference" section; those stages are pinned by the reference's own KATs restated in
+                   (encoders/sse_utils.hpp:1365-1433), compiled in place from the reference tree
+  * filter stages  diff3x3x1, rmestbkrd, rmbkrd_neighbor5x5x5, zcurve_reorder, raster_reorder, scalar bitswap1 and the histogram: the
+                   reference's own templates compiled in place (oracle/ref_driver.cpp) -> tests/golden/ref_stages.json (--stages)
+  * what the reference cannot produce here (needs Boost proper: quantiser LUT, frame_shuffle, tile_shuffle, header) is NOT in this
+    file's "reference" section; those stages are pinned by the reference's own KATs restated in
     tests/test_oracle_reference_kats.py and carry "oracle" hashes here only as regression anchors.
 
 Output
@@ -28,6 +30,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from oracle import ref, sqy_oracle as o   # noqa: E402
 from sqeazy_amd import synth             # noqa: E402
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import bkrd_restate as R                                            # noqa: E402
+from ref_stage_inputs import stage_input, stage_volume, stage_tile, case_id  # noqa: E402,F401  (the tests import them from here or there)
 
 GOLD = os.path.join(ROOT, "tests", "golden")
 
@@ -357,7 +362,6 @@ def accel():
 def lz4_planted():
     """tests/golden/lz4_planted.json: the planted streams of tests/lz4_planted.py -- per case its length and sha256 and the size and sha256 of the
     oracle's block (no bytes); asserts oracle == liblz4 on the way where the reference driver is built"""
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
     import lz4_planted as P
     L = {"_meta": {"generator": "oracle/gen_golden.py --lz4-planted", "block": "sqy_oracle.lz4_block_compress(data, cap=lz4_planted.block_cap(n))",
                    "liblz4": "1.9.3 (LZ4_versionNumber 10903)" if ref.available() else "not compared"}, "cases": {}}
@@ -372,8 +376,247 @@ def lz4_planted():
     print("wrote", os.path.join(GOLD, "lz4_planted.json"), "with", len(L["cases"]), "cases")
 
 
+# ------------------------------------------------------------------------------------------------------------------------------------
+# Filter stages against the reference's own templates (oracle/ref_driver.cpp): ONE table of cases, tests/golden/ref_stages.json
+# ------------------------------------------------------------------------------------------------------------------------------------
+def _rows(stage, dtypes, shapes, kinds, seed0, params=None, **flags):
+    out = []
+    for dt in dtypes:
+        for shape in shapes:
+            for kind in kinds:
+                r = {"stage": stage, "dtype": dt, "shape": list(shape), "kind": kind, "seed": seed0 + len(out), "params": dict(params or {})}
+                r.update(flags)
+                out.append(r)
+    return out
+
+
+# why a row is `undefined` (the reference is not run on it) or `serial_only` (run with one thread only); rows carry the key
+REASONS = {
+    "race": "scalar_bitplane_reorder_encode (bitplane_reorder_scalar.hpp:46-70) updates an output word shared by 8 * sizeof(T) consecutive inputs "
+            "with a read-modify-write from whichever threads hold them: only the one-thread run is defined",
+    "sse_fault": "the SSE branch (bitswap_scheme_impl.hpp:106-120) loads with _mm_load_si128 (sse_utils.hpp:1194, :1273): it faults on this address",
+    "neighbour_oob": "count_neighbors_if (background_scheme_utils.hpp:248-268) reads neighbours behind the end of the volume",
+}
+RACE, SSE_FAULT, NB_OOB = "race", "sse_fault", "neighbour_oob"
+
+# zcurve_reorder: the shapes and tiles of tests/test_gpu_new_stages.py::test_zcurve_reorder
+ZCURVE = [((8, 8, 8), 2), ((8, 8, 8), 4), ((8, 8, 8), 8), ((8, 16, 8), 2), ((7, 16, 7), 2), ((5, 3, 9), 2), ((64, 128, 256), 16), ((33, 70, 129), 4),
+          ((128, 128, 128), 128), ((12, 12, 12), 8)]
+# raster_reorder: those of tests/test_gpu_parity.py::test_raster_reorder (tile None: 16 / sizeof(T))
+RASTER = [((32, 64, 96), None), ((16, 32, 48), None), ((33, 64, 97), 5), ((7, 13, 21), 5), ((32, 64, 96), 4), ((33, 66, 99), 4)]
+# rmbkrd_neighbor5x5x5: extents from {1, 2, 4, 5, 6, 9}
+NB_SHAPES = [(9, 9, 5), (9, 6, 5), (9, 5, 6), (6, 6, 5), (9, 9, 6), (6, 9, 5), (9, 6, 6), (9, 9, 9), (6, 6, 6), (5, 6, 9), (4, 9, 9), (2, 6, 6), (6, 5, 9),
+             (1, 9, 9), (9, 9, 4), (9, 4, 9), (9, 5, 5), (9, 9, 1), (9, 2, 9), (1, 1, 1), (2, 5, 6), (9, 9, 2)]
+
+
+def neighbor5_reads_in_bounds(shape):
+    """True when every neighbour of every voxel flatten_to_neighborhood_scheme::encode visits lies inside the volume
+    (offsets of neighborhood_utils.hpp:199-238 for cube_neighborhood<5> on the shape as given, rows of X - 3 voxels)"""
+    Z, Y, X = shape
+    last = -1
+    for z in range(2, X - 2):
+        for y in range(2, Y - 2):
+            off = z * Y * X + y * X + 2
+            if off < Z * Y * X:
+                last = max(last, off + X - 4)
+    return last < 0 or last + 2 * Y * X + 2 * X + 2 < Z * Y * X
+
+
+def stage_table():
+    T = []
+    # ---- diff3x3x1 ----
+    dshapes = [(2, 3, 5), (5, 3, 2), (3, 3, 3), (2, 3, 2), (1, 8, 8), (8, 1, 8), (8, 8, 1), (4, 6, 10), (10, 6, 4), (40, 5, 4), (9, 10, 12)]
+    T += _rows("diff3x3x1", ["uint16", "uint8", "char"], dshapes, ["random"], 100)
+    T += _rows("diff3x3x1", ["uint16"], [(130, 16, 512), (3, 700, 128)], ["random"], 200)
+    T += _rows("diff3x3x1", ["uint16", "uint8"], [(4, 6, 10), (9, 10, 12)], ["max", "ramp"], 300)
+    T += _rows("diff3x3x1", ["uint8", "char"], [(3, 4, 127), (127, 4, 3), (3, 4, 128), (128, 4, 3), (3, 128, 4)], ["random"], 400)
+    T += _rows("diff3x3x1", ["char"], [(4, 6, 10), (9, 10, 12), (10, 6, 4)], ["pm128"], 500)
+    # ---- rmestbkrd ----
+    T += _rows("rmestbkrd", ["uint16", "uint8"], [(2, 4, 4), (3, 5, 7), (16, 32, 32)], ["zero", "max", "two_level", "gamma", "equal_faces"], 600)
+    T += _rows("rmestbkrd", ["uint16", "uint8"], [(1, 4, 4)], ["gamma"], 700)
+    # ---- rmbkrd_neighbor5x5x5 ----
+    nb = []
+    for i, shape in enumerate(NB_SHAPES):
+        for dt in ("uint16", "uint8"):
+            # values 0..79: a level of 18 (16) puts 28 (25) of the 124 neighbours below it on average, a level of 36 puts 56: most walked
+            # voxels stay under the cuts of fraction 0.25 (31) and 0.5 (62), some do not.  Levels 0 and 1 and fraction 1 keep every
+            # walked voxel at or above the level, the largest level skips every voxel.  near_wrap: 4 in 13 lie below the wrapped level
+            # (38 neighbours, cut 62); a level that saturated instead of wrapping would skip every voxel.
+            combos = [(18, 0.25), (1, 1.0), (0, 0.0), (36, 0.5)] if i % 2 == 0 else \
+                     [(40, 1.0), (1, 0.25), (65535 if dt == "uint16" else 255, 0.0), (16, 0.25)]
+            if not R.neighbor5_defined(shape) or not neighbor5_reads_in_bounds(shape):
+                combos = combos[:1]                             # refused by the product, or undefined in the reference: the shape says it all
+            for t, f in combos:
+                nb += _rows("rmbkrd_neighbor5x5x5", [dt], [shape], ["low80"], 800 + len(nb), {"threshold": t, "fraction": f})
+            if len(combos) > 1:
+                nb += _rows("rmbkrd_neighbor5x5x5", [dt], [shape], ["near_wrap"], 800 + len(nb), {"threshold": 70000, "fraction": 0.5})
+    for r in nb:
+        if not neighbor5_reads_in_bounds(r["shape"]):
+            r["undefined"] = NB_OOB
+    T += nb
+    # ---- zcurve_reorder / raster_reorder ----
+    for k, (shape, ts) in enumerate(ZCURVE):
+        T += _rows("zcurve_reorder", ["uint16", "uint8"], [shape], ["random"], 2000 + 2 * k, {"tile_size": ts})
+    for k, (shape, ts) in enumerate(RASTER):
+        T += _rows("raster_reorder", ["uint16", "uint8"], [shape], ["random"], 2100 + 2 * k, {"tile_size": ts})
+    # ---- bitswap1: (1, 1, len), source `offset_bytes` behind an aligned address ----
+    for dt in ("uint16", "uint8"):
+        for n in (1, 7, 8, 9, 127, 128, 129, 4096 + 13):
+            for off in (0, 2):
+                r = _rows("bitswap1", [dt], [(1, 1, n)], ["random"], 2200 + len(T), {"offset_bytes": off})[0]
+                sse = dt == "uint16" and n % 128 == 0
+                if sse and off % 16:
+                    r["undefined"] = SSE_FAULT
+                elif not sse:
+                    r["serial_only"] = RACE
+                T.append(r)
+    # ---- histogram statistics (hist_impl.hpp) ----
+    T += _rows("histogram", ["uint16", "uint8"], [(1, 1, 5000), (1, 1, 1), (3, 5, 7)], ["gamma", "two_level", "zero", "max", "random"], 2400)
+    for i, r in enumerate(T):
+        r["id"] = case_id(r, i)
+    return T
+
+
+def oracle_stage(row, vol):
+    """the ORACLE's output of a case: (bytes, extra numbers); raises ValueError where the oracle refuses the case"""
+    st, p = row["stage"], row["params"]
+    if st == "diff3x3x1":
+        return o.diff3x3x1_encode(vol, char=row["dtype"] == "char").tobytes(), {}
+    if st == "rmestbkrd":
+        if vol.shape[0] < 2:
+            raise ValueError("rmestbkrd: fewer than two frames")
+        sup = [float(R.support(h)) for h in R.face_histograms(vol, 1 << 30)]
+        return R.rmestbkrd(vol, 1 << 30).tobytes(), {"supports": sup, "threshold": R.rmestbkrd_threshold(vol, 1 << 30)}
+    if st == "rmbkrd_neighbor5x5x5":
+        if not R.neighbor5_defined(vol.shape):
+            raise ValueError("rmbkrd_neighbor5x5x5: undefined shape")
+        t, f = R.neighbor5_params("threshold=%d,fraction=%r" % (p["threshold"], p["fraction"]), vol.dtype)
+        return R.neighbor5(vol, t, f).tobytes(), {}
+    if st == "zcurve_reorder":
+        return o.zcurve_reorder(vol, p["tile_size"]).tobytes(), {}
+    if st == "raster_reorder":
+        return o.raster_reorder(vol, stage_tile(row)).tobytes(), {}
+    if st == "bitswap1":
+        return o.bitswap1_encode(vol).tobytes(), {}
+    if st == "histogram":
+        bins = o.histogram(vol)
+        return bins.tobytes(), {"support": float(R.support(bins))}
+    raise KeyError(st)
+
+
+def reference_stage(row, vol, nthreads=1):
+    """the REFERENCE's output of a case through oracle/_ref: (bytes, extra numbers); raises ref.Refused"""
+    st, p = row["stage"], row["params"]
+    if st == "diff3x3x1":
+        return ref.diff3x3x1(vol, char=row["dtype"] == "char", nthreads=nthreads).tobytes(), {}
+    if st == "rmestbkrd":
+        out, sup, thr = ref.rmestbkrd(vol, nthreads)
+        return out.tobytes(), {"supports": [float(s) for s in sup], "threshold": thr}
+    if st == "rmbkrd_neighbor5x5x5":
+        return ref.rmbkrd_neighbor5x5x5(vol, p["threshold"], p["fraction"], nthreads).tobytes(), {}
+    if st == "zcurve_reorder":
+        return ref.zcurve_reorder(vol, p["tile_size"], nthreads=nthreads).tobytes(), {}
+    if st == "raster_reorder":
+        return ref.raster_reorder(vol, stage_tile(row), nthreads=nthreads).tobytes(), {}
+    if st == "bitswap1":
+        return ref.bitswap1(vol, nthreads=nthreads, offset_bytes=p["offset_bytes"]).tobytes(), {}
+    if st == "histogram":
+        bins, stats = ref.hist_stats(vol)
+        return bins.tobytes(), {"support": stats["support"]}          # the oracle restates the bins and the support, nothing else
+    raise KeyError(st)
+
+
+def reference_stage_decode(row, enc):
+    """the reference's decode of its own output, one thread (diff3x3x1's decode reads planes other threads still write)"""
+    st, p = row["stage"], row["params"]
+    if st == "diff3x3x1":
+        return ref.diff3x3x1(enc, char=row["dtype"] == "char", decode=True)
+    if st == "zcurve_reorder":
+        return ref.zcurve_reorder(enc, p["tile_size"], decode=True)
+    if st == "raster_reorder":
+        return ref.raster_reorder(enc, stage_tile(row), decode=True)
+    if st == "bitswap1":
+        return ref.bitswap1(enc, decode=True).reshape(enc.shape)
+    return None
+
+
+def stage_refused(row, vol):
+    """a case the product refuses: the oracle raises on it (the reference reads out of bounds or throws there; it is not run)"""
+    try:
+        oracle_stage(row, vol)
+        return False
+    except ValueError:
+        return True
+
+
+def _lean(c):
+    """a case as the golden file holds it: without its id and empty params (ref_stage_inputs.load_cases puts them back)"""
+    return {k: v for k, v in c.items() if k != "id" and not (k == "params" and not v)}
+
+
+def stages():
+    """tests/golden/ref_stages.json: for every row of stage_table() the byte count and sha256 of what the REFERENCE's own templates give
+    (oracle/ref_driver.cpp), the estimator's supports and threshold as numbers; nthreads 1 and 3 asserted equal unless the row is
+    `serial_only`; rows marked `undefined` and refused rows are not run"""
+    assert ref.stages_available(), "oracle/_ref/libsqy_ref.so missing or stale: run `make -C oracle` where the reference tree exists"
+    rows = stage_table()
+    l2 = int(ref.cache_l2_bytes())
+    G = {"_meta": {"generator": "oracle/gen_golden.py --stages", "source": "the reference's utility headers compiled in place (oracle/ref_driver.cpp)",
+                   "host_l2_bytes": l2, "reasons": REASONS, "inputs": "tests/ref_stage_inputs.py: stage_input(kind, dtype, shape, seed)",
+                   "refused": "the PRODUCT's policy (shapes on which the reference reads out of bounds or throws), taken from the oracle, which "
+                              "restates that policy; the reference is not run on these rows and says nothing about them",
+                   "histogram": "sha256 of the uint32 bins, and calc_support(0.99f); no other statistic is pinned"}, "cases": []}
+    for row in rows:
+        vol = stage_volume(row)
+        e = dict(row)
+        e["input_sha256"] = sha(vol.tobytes())[:12]
+        if stage_refused(row, vol):
+            e["refused"] = True
+        elif "undefined" not in row:
+            if row["stage"] == "rmestbkrd":
+                assert vol.shape[1] * vol.shape[2] <= l2, "the face portion must not depend on this machine's L2"
+            out, extra = reference_stage(row, vol, 1)
+            if "serial_only" not in row:
+                out3, extra3 = reference_stage(row, vol, 3)
+                assert out == out3 and extra == extra3, ("the reference disagrees with itself across thread counts", row["id"])
+            arr = np.frombuffer(out, vol.dtype)
+            back = reference_stage_decode(row, arr.reshape(vol.shape)) if row["stage"] != "histogram" else None
+            if back is not None:
+                assert np.array_equal(back.reshape(vol.shape), vol), ("the reference's decode does not restore the input", row["id"])
+            e.update(extra)
+            e["bytes"], e["sha256"] = len(out), sha(out)
+        G["cases"].append(e)
+    with open(os.path.join(GOLD, "ref_stages.json"), "w") as f:                   # compact, one case per line
+        f.write('{"_meta": %s,\n"cases": [\n%s\n]}\n' % (json.dumps(G["_meta"], sort_keys=True),
+                                                        ",\n".join(json.dumps(_lean(c), sort_keys=True, separators=(",", ":")) for c in G["cases"])))
+    n = len(G["cases"])
+    print("wrote ref_stages.json:", n, "cases,", sum("refused" in c for c in G["cases"]), "refused,", sum("undefined" in c for c in G["cases"]), "undefined")
+
+
+def dump_stage_cases(path):
+    """inputs of every case the reference is run on, for tests/sanitize/ref_stages_san.cpp: cases.txt (one line per case:
+    id stage dtype z y x p0 p1 offset_bytes serial_only) and <index>.bin"""
+    os.makedirs(path, exist_ok=True)
+    lines = []
+    for row in stage_table():
+        vol = stage_volume(row)
+        if "undefined" in row or stage_refused(row, vol):
+            continue
+        p = row["params"]
+        p0 = stage_tile(row) if "reorder" in row["stage"] else p.get("threshold", 0)
+        k = len(lines)
+        vol.tofile(os.path.join(path, "%d.bin" % k))
+        lines.append("%s %s %s %d %d %d %d %r %d %d" % (row["id"], row["stage"], row["dtype"], vol.shape[0], vol.shape[1], vol.shape[2], p0,
+                                                       float(p.get("fraction", 0.0)), p.get("offset_bytes", 0), int("serial_only" in row)))
+    with open(os.path.join(path, "cases.txt"), "w") as f:
+        f.write("\n".join(lines) + "\n")
+    return len(lines)
+
+
 if __name__ == "__main__":
-    if "--accel" in sys.argv:
+    if "--stages" in sys.argv:
+        stages()
+    elif "--accel" in sys.argv:
         accel()
     elif "--lz4-planted" in sys.argv:
         lz4_planted()
@@ -387,6 +630,7 @@ if __name__ == "__main__":
         headline_serial()
     else:
         main()
+        stages()
         accel()
         lz4_planted()
         headline()

@@ -22,6 +22,7 @@ def lib():
     if not _TRIED:
         _TRIED = True
         path = os.path.join(_HERE, "_ref", "libsqy_ref.so")
+        _rebuild_if_stale(path)
         try:
             L = ctypes.CDLL(path)
             for f in ("ref_lz4f_compress_bound", "ref_lz4_encode_serial", "ref_lz4_encode_parallel", "ref_lz4_decode_frames"):
@@ -32,26 +33,180 @@ def lib():
     return _LIB
 
 
+def _rebuild_if_stale(path):
+    """a library from an older driver (no stage entry points in its symbol table) is rebuilt before it is loaded, where the reference
+    tree is there to build it from; where it is not, the old one is kept and serves what it can (sqy_oracle.lib() rebuilds alike)"""
+    try:
+        with open(path, "rb") as f:
+            data = f.read()
+    except OSError:
+        return
+    if all(name.encode() in data for name in STAGE_ENTRY_POINTS):
+        return
+    try:
+        if reference_tree():
+            import subprocess
+            subprocess.call(["make", "-s", "-C", _HERE, "ref"], stdout=subprocess.DEVNULL)
+    except Exception:                                   # no make, no compiler: keep what is there
+        pass
+
+
 def available():
     return lib() is not None
+
+
+STAGE_ENTRY_POINTS = ("ref_diff3x3x1", "ref_diff3x3x1_offsets", "ref_rmestbkrd", "ref_cache_l2_bytes", "ref_rmbkrd_neighbor5x5x5",
+                      "ref_zcurve_reorder", "ref_raster_reorder", "ref_bitswap1", "ref_hist_stats")
+
+
+def stages_available():
+    """True when the library loads AND holds the filter-stage entry points: a prebuilt oracle/_ref from an older driver, kept where the
+    reference tree is absent and nothing can be rebuilt, has only the LZ4 and SSE ones"""
+    L = lib()
+    return L is not None and all(hasattr(L, f) for f in STAGE_ENTRY_POINTS)
+
+
+def _make(target):
+    import subprocess
+    return subprocess.check_output(["make", "-s", "--no-print-directory", "-C", _HERE, target], text=True).strip()
+
+
+def reference_tree():
+    """the reference's source directory oracle/Makefile builds from, or None where it does not exist (then oracle/_ref cannot be rebuilt)"""
+    path = _make("ref-tree")
+    return path if os.path.isdir(path) else None
 
 
 def lz4_version():
     return lib().ref_lz4_version()
 
 
+_DT = {np.dtype(np.uint8): 0, np.dtype(np.uint16): 1}
+_szp = ctypes.POINTER(ctypes.c_size_t)
+
+
+class Refused(ValueError):
+    """the reference threw, or its own checks returned without doing the work"""
+
+
+def _aligned(n, dtype, offset_bytes=0):
+    """n elements of dtype that start `offset_bytes` behind a 64-byte boundary"""
+    dtype = np.dtype(dtype)
+    buf = np.zeros(n * dtype.itemsize + 128, dtype=np.uint8)
+    at = (-buf.ctypes.data % 64) + offset_bytes
+    return buf[at:at + n * dtype.itemsize].view(dtype)
+
+
+def _io(a, char=False, offset_bytes=0):
+    a = np.ascontiguousarray(a)
+    src = _aligned(a.size, a.dtype, offset_bytes)
+    src[:] = a.reshape(-1)
+    dst = _aligned(a.size, a.dtype)
+    return a, src, dst, (2 if char else _DT[a.dtype])
+
+
+def _shape3(shape):
+    return (ctypes.c_size_t * 3)(*[int(d) for d in shape])
+
+
+def _done(rc, what):
+    if rc:
+        raise Refused("%s: the reference %s" % (what, "threw" if rc == 2 else "did not do the work (%d)" % rc))
+
+
+def diff3x3x1(a, char=False, decode=False, nthreads=1):
+    a, src, dst, dt = _io(a, char)
+    _done(lib().ref_diff3x3x1(dt, ctypes.c_void_p(src.ctypes.data), ctypes.c_void_p(dst.ctypes.data), _shape3(a.shape),
+                              int(decode), int(nthreads)), "diff3x3x1")
+    return dst.reshape(a.shape).copy()
+
+
+def diff3x3x1_offsets(shape):
+    L = lib()
+    L.ref_diff3x3x1_offsets.restype = ctypes.c_long
+    hx = ctypes.c_size_t(0)
+    n = L.ref_diff3x3x1_offsets(_shape3(shape), None, ctypes.c_size_t(0), ctypes.byref(hx))
+    if n < 0:
+        raise Refused("diff3x3x1 offsets: the reference threw")
+    out = np.zeros(max(n, 1), dtype=np.uint64)
+    L.ref_diff3x3x1_offsets(_shape3(shape), out.ctypes.data_as(_szp), ctypes.c_size_t(n), ctypes.byref(hx))
+    return out[:n], hx.value
+
+
+def cache_l2_bytes():
+    L = lib()
+    L.ref_cache_l2_bytes.restype = ctypes.c_uint
+    return L.ref_cache_l2_bytes()
+
+
+def rmestbkrd(a, nthreads=1):
+    """(encoded volume, the four face supports as float32, threshold)"""
+    a, src, dst, dt = _io(a)
+    sup = np.zeros(4, np.float32)
+    thr = ctypes.c_double(0)
+    _done(lib().ref_rmestbkrd(dt, ctypes.c_void_p(src.ctypes.data), ctypes.c_void_p(dst.ctypes.data), _shape3(a.shape), int(nthreads),
+                              sup.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), ctypes.byref(thr)), "rmestbkrd")
+    return dst.reshape(a.shape).copy(), sup, int(thr.value)
+
+
+def rmbkrd_neighbor5x5x5(a, threshold, fraction, nthreads=1):
+    """voxels the reference does not write are 0 here (the output buffer starts zeroed)"""
+    a, src, dst, dt = _io(a)
+    _done(lib().ref_rmbkrd_neighbor5x5x5(dt, ctypes.c_void_p(src.ctypes.data), ctypes.c_void_p(dst.ctypes.data), _shape3(a.shape),
+                                         ctypes.c_long(int(threshold)), ctypes.c_float(float(fraction)), int(nthreads)), "rmbkrd_neighbor5x5x5")
+    return dst.reshape(a.shape).copy()
+
+
+def _reorder(fn, a, tile, decode, nthreads):
+    a, src, dst, dt = _io(a)
+    _done(fn(dt, ctypes.c_void_p(src.ctypes.data), ctypes.c_void_p(dst.ctypes.data), _shape3(a.shape), ctypes.c_size_t(int(tile)),
+             int(decode), int(nthreads)), "reorder")
+    return dst.reshape(a.shape).copy()
+
+
+def zcurve_reorder(a, tile, decode=False, nthreads=1):
+    return _reorder(lib().ref_zcurve_reorder, a, tile, decode, nthreads)
+
+
+def raster_reorder(a, tile, decode=False, nthreads=1):
+    return _reorder(lib().ref_raster_reorder, a, tile, decode, nthreads)
+
+
+def bitswap1(a, decode=False, nthreads=1, offset_bytes=0):
+    """bitswap_scheme<T,1> on a flat array of any length whose first element sits `offset_bytes` behind a 64-byte boundary"""
+    a, src, dst, dt = _io(np.ascontiguousarray(a).reshape(-1), offset_bytes=offset_bytes)
+    if dt == 1 and not decode and a.size % 128 == 0 and offset_bytes % 16:
+        raise Refused("the reference's SSE branch loads with _mm_load_si128: it faults on this address")
+    _done(lib().ref_bitswap1(dt, ctypes.c_void_p(src.ctypes.data), ctypes.c_void_p(dst.ctypes.data), ctypes.c_size_t(a.size),
+                             int(decode), int(nthreads)), "bitswap1")
+    return dst.copy()
+
+
+HIST_STATS = ("smallest_populated_bin", "largest_populated_bin", "integral", "mean", "mean_variation", "median", "median_variation",
+              "mode", "entropy", "support")
+
+
+def hist_stats(a):
+    """(bins as uint32, {name: value}) of sqeazy::histogram<T>(begin, end) and calc_support(0.99f)"""
+    a = np.ascontiguousarray(a).reshape(-1)
+    bins = np.zeros(1 << (8 * a.dtype.itemsize), np.uint32)
+    st = np.zeros(len(HIST_STATS), np.float64)
+    _done(lib().ref_hist_stats(_DT[a.dtype], ctypes.c_void_p(a.ctypes.data), ctypes.c_size_t(a.size),
+                               bins.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), st.ctypes.data_as(ctypes.POINTER(ctypes.c_double))), "histogram")
+    return bins, dict(zip(HIST_STATS, st.tolist()))
+
+
 def bitswap1_encode_u16(a, nthreads=1):
-    """reference simd_segment_broadcast; needs len % 128 == 0 and 16-byte alignment."""
+    """bitswap_scheme<uint16_t,1>::encode on 16-byte aligned input.  Goes through the entry point every build of the driver has had:
+    one built before the stage entry points existed takes only lengths that are a multiple of 128 (the SSE branch)."""
     flat = np.ascontiguousarray(a, dtype=np.uint16).reshape(-1)
-    buf = np.zeros(flat.size + 8, dtype=np.uint16)
-    off = (-buf.ctypes.data % 16) // 2
-    src = buf[off:off + flat.size]
+    src = _aligned(flat.size, np.uint16)
     src[:] = flat
     out = np.zeros(flat.size, dtype=np.uint16)
     rc = lib().ref_bitswap1_encode_u16(src.ctypes.data_as(_u16p), out.ctypes.data_as(_u16p),
                                        ctypes.c_size_t(flat.size), ctypes.c_int(nthreads))
     if rc:
-        raise ValueError("reference would take its scalar branch (not buildable here)")
+        raise ValueError("this build of the reference driver does not take its scalar branch")
     return out
 
 

@@ -1,22 +1,28 @@
 /*
  * ref_driver.cpp -- thin driver around the parts of the REAL reference that build in this image
- * without any stand-in header or library (TEST INFRASTRUCTURE ONLY; built into oracle/_ref/,
- * which is git-ignored; never linked into the product).
+ * (TEST INFRASTRUCTURE ONLY; built into oracle/_ref/, which is git-ignored; never linked into the product).
+ * The reference tree is included in place through -I, never quoted.
  *
- *  (1) the reference's own SSE bit-plane gather, included in place from
- *      /root/reference/src/cpp/src/encoders/sse_utils.hpp (needs only <emmintrin.h>&co + OpenMP):
- *      sqeazy::detail::simd_segment_broadcast (sse_utils.hpp:1365-1433), entered exactly as
- *      sse_bitplane_reorder_encode<1> does (bitplane_reorder_sse.hpp:281-311).
+ *  (1) the reference's utility headers, which hold all of the arithmetic of its filter stages.  They
+ *      use Boost for two things only (enable_if_c / is_integral, and Boost.Align); oracle/boost_standin/
+ *      maps those names onto <type_traits> and posix_memalign, and oracle/Makefile pre-includes the
+ *      standard headers Boost used to drag in.  Compiled unmodified: traits.hpp, neighborhood_utils.hpp,
+ *      diff_scheme_utils.hpp, sqeazy_common.hpp, sqeazy_algorithms.hpp, hist_impl.hpp,
+ *      encoders/{histogram_utils, background_scheme_utils, zcurve_reorder_utils, morton,
+ *      raster_reorder_utils, scalar_utils, bitplane_reorder_scalar, bitplane_reorder_sse, sse_utils}.hpp.
+ *      The *_scheme_impl.hpp classes around them need the dynamic-stage machinery (Boost proper) and do
+ *      not build; they are thin, and the entry points below restate their few lines of CALL SEQUENCE
+ *      (cited at each one) while the reference's own templates do the arithmetic.
  *  (2) liblz4 1.9.3 -- the third-party library that holds ALL of the reference's LZ4 arithmetic
  *      (the reference only calls its Frame API).  It is installed in this image
  *      (/usr/lib/x86_64-linux-gnu/liblz4.so.1.9.3, headers /opt/conda/include).  The functions
  *      below drive it with the call sequence and preferences of the reference's call sites:
  *      encoders/lz4.hpp:103-113 (prefs), encoders/lz4_utils.hpp:99-173 (encode_serial),
- *      :193-274 (encode_parallel).  lz4_utils.hpp itself cannot be compiled here (it includes
- *      sqeazy_common.hpp -> Boost.Align, absent from the image), so that sequencing is restated.
+ *      :193-274 (encode_parallel).
  *
- * Everything else in the reference's hot path needs Boost and is therefore unbuildable here
- * (see DESIGN.md).
+ * Still restated only (oracle/sqy_oracle.*): the quantiser's Lloyd-Max LUT (quantiser_utils.hpp needs
+ * Boost.StringAlgo through string_parsers.hpp), frame_shuffle and tile_shuffle (Boost.Accumulators),
+ * bitshuffle (its library is not in the reference tree) and the sqy header (Boost.PropertyTree).
  */
 #include <cstddef>
 #include <cstdint>
@@ -29,24 +35,292 @@
 #include <climits>
 #include <omp.h>
 
-#include "encoders/sse_utils.hpp" /* from /root/reference/src/cpp/src via -I */
+/* from the reference's src/cpp/src via -I */
+#include "traits.hpp"
+#include "sqeazy_common.hpp"
+#include "neighborhood_utils.hpp"
+#include "diff_scheme_utils.hpp"
+#include "sqeazy_algorithms.hpp"
+#include "hist_impl.hpp"
+#include "encoders/histogram_utils.hpp"
+#include "encoders/background_scheme_utils.hpp"
+#include "encoders/morton.hpp"
+#include "encoders/zcurve_reorder_utils.hpp"
+#include "encoders/raster_reorder_utils.hpp"
+#include "encoders/scalar_utils.hpp"
+#include "encoders/bitplane_reorder_scalar.hpp"
+#include "encoders/sse_utils.hpp"
+#include "encoders/bitplane_reorder_sse.hpp"
 
 #include "lz4.h"
 #include "lz4frame.h"
+
+namespace {
+
+typedef std::vector<std::size_t> shape_t;
+
+inline std::size_t voxels(const std::size_t* zyx) { return zyx[0] * zyx[1] * zyx[2]; }
+
+/* The rows a halo-based stage walks: where each row starts and how many voxels it runs. */
+struct rows_t {
+    std::vector<std::size_t> start;
+    std::size_t run;
+};
+
+/* Geometry of diff3x3x1 as encoders/diff_scheme_impl.hpp:92-103 (encode) and :154-164 (decode) ask for it: a
+ * sqeazy::halo<last_plane_neighborhood<3>> over (width, height, depth), its compute_offsets_in_x, the run taken from
+ * axis 0, and the whole rest of the volume as one run when there is a single start. */
+typedef sqeazy::last_plane_neighborhood<3> plane3x3;
+
+rows_t diff_rows(const std::size_t* zyx)
+{
+    rows_t r;
+    sqeazy::halo<plane3x3, std::size_t> h(zyx[2], zyx[1], zyx[0]);
+    h.compute_offsets_in_x(r.start);
+    r.run = h.non_halo_end(0) - h.non_halo_begin(0);
+    if (r.start.size() == 1) r.run = voxels(zyx) - r.start[0];
+    return r;
+}
+
+/* diff3x3x1, both directions.  What decides the arithmetic (diff_scheme_impl.hpp:15-24): the sum of the nine voxels
+ * comes from sqeazy::naive_sum<> in the voxel type T, is widened to add_unsigned<twice_as_wide<T>>, divided by
+ * num_traversed_pixels<>, and the result is stored through remove_unsigned<T>.
+ *   encode (:89-135): dst starts as a copy of src; every walked voxel becomes src - mean(src)
+ *   decode (:151-190): dst starts as a copy of src; every walked voxel becomes src + mean(dst), in walk order */
+template <typename T, bool Decode>
+int diff_walk(const T* src, T* dst, const std::size_t* zyx, int nthreads)
+{
+    typedef typename sqeazy::remove_unsigned<T>::type signed_t;
+    typedef typename sqeazy::add_unsigned<typename sqeazy::twice_as_wide<T>::type>::type wide_t;
+    const std::size_t n = voxels(zyx);
+    std::memcpy(dst, src, n * sizeof(T));
+    const rows_t rows = diff_rows(zyx);
+    const unsigned nine = sqeazy::num_traversed_pixels<plane3x3>();
+    const T* summed = Decode ? dst : src;
+    const signed_t* src_signed = reinterpret_cast<const signed_t*>(src);
+    signed_t* dst_signed = reinterpret_cast<signed_t*>(dst);
+    const long nrows = (long)rows.start.size();
+#pragma omp parallel for num_threads(nthreads)
+    for (long r = 0; r < nrows; ++r) {
+        for (std::size_t k = 0; k < rows.run; ++k) {
+            const std::size_t at = rows.start[r] + k;
+            const wide_t sum = sqeazy::naive_sum<plane3x3>(summed, at, zyx[2], zyx[1], zyx[0]);
+            if (Decode)
+                dst[at] = static_cast<T>(src_signed[at] + sum / nine);
+            else
+                dst_signed[at] = static_cast<signed_t>(src[at] - sum / nine);
+        }
+    }
+    return 0;
+}
+
+/* rmestbkrd (encoders/remove_estimated_background_scheme_impl.hpp:73-103): the four face supports from
+ * sqeazy::extract_darkest_face_supports at 0.99f, their minimum as the level, and the level handed to
+ * remove_background_scheme<T>, whose constructor narrows the float to T (remove_background_scheme_impl.hpp:41-44)
+ * and whose encode (:87-89) keeps what lies above the level, less the level, and zeroes the rest.  That last loop
+ * has no template behind it in the reference; it is the one line of arithmetic stated here. */
+template <typename T>
+int rmestbkrd_encode(const T* in, T* out, const std::size_t* zyx, int nthreads, float* supports4, double* threshold)
+{
+    const shape_t shape(zyx, zyx + 3);
+    const std::vector<float> faces = sqeazy::extract_darkest_face_supports(in, shape, 0.99f, nthreads);
+    float lowest = faces[0];
+    for (std::size_t f = 0; f < faces.size(); ++f) {
+        if (supports4 && f < 4) supports4[f] = faces[f];
+        if (faces[f] < lowest) lowest = faces[f];
+    }
+    const T level = lowest;
+    if (threshold) *threshold = (double)level;
+    if (!out) return 0;
+    const long n = (long)voxels(zyx);
+#pragma omp parallel for num_threads(nthreads)
+    for (long i = 0; i < n; ++i) out[i] = in[i] > level ? in[i] - level : 0;
+    return 0;
+}
+
+/* rmbkrd_neighbor5x5x5 (encoders/flatten_to_neighborhood_scheme_impl.hpp:94-149): a sqeazy::halo<cube_neighborhood<5>>
+ * built from the shape in the order it comes (:98), rows of non_halo_end(2) - non_halo_begin(2) + 1 voxels (:106).  A
+ * walked voxel below the level is left alone; any other is kept or zeroed by whether sqeazy::count_neighbors_if<>
+ * finds more neighbours below the level than fraction * (size<>() - 1), compared as float (:112, :142).  Voxels that
+ * are not walked, or are left alone, keep what `out` held on entry.
+ * With a single row start the reference takes the run from an element its list does not have (:101): returns 3. */
+template <typename T>
+int neighbor5_encode(const T* in, T* out, const std::size_t* zyx, long threshold, float fraction, int nthreads)
+{
+    typedef sqeazy::cube_neighborhood<5> cube5;
+    const shape_t shape(zyx, zyx + 3);
+    const T level = threshold;                     /* the constructor's narrowing of std::stoi's int (:58-60) */
+    rows_t rows;
+    sqeazy::halo<cube5, std::size_t> h(shape.begin(), shape.end());
+    h.compute_offsets_in_x(rows.start);
+    if (rows.start.size() == 1) return 3;
+    rows.run = h.non_halo_end(sqeazy::row_major::x) - h.non_halo_begin(sqeazy::row_major::x) + 1;
+    const float most = fraction * (sqeazy::size<cube5>() - 1);
+    const auto below = [level](T v) { return v < level; };
+    const long nrows = (long)rows.start.size();
+#pragma omp parallel for num_threads(nthreads)
+    for (long r = 0; r < nrows; ++r) {
+        for (std::size_t k = 0; k < rows.run; ++k) {
+            const std::size_t at = rows.start[r] + k;
+            if (below(in[at])) continue;
+            const unsigned dark = sqeazy::count_neighbors_if<cube5>(in + at, shape, below);
+            out[at] = dark > most ? T(0) : in[at];
+        }
+    }
+    return 0;
+}
+
+/* zcurve_reorder (encoders/zcurve_reorder_scheme_impl.hpp:43-61, :85-115): a detail::zcurve of the tile size, and
+ * its encode or decode over the whole volume; done when it reports the end of the output. */
+template <typename T>
+int zcurve_run(const T* in, T* out, const std::size_t* zyx, std::size_t tile, int decode, int nthreads)
+{
+    const shape_t shape(zyx, zyx + 3);
+    const std::size_t n = voxels(zyx);
+    const sqeazy::detail::zcurve curve(tile);
+    const T* stop = decode ? curve.decode(in, in + n, out, shape, nthreads) : curve.encode(in, in + n, out, shape, nthreads);
+    return stop == out + n ? 0 : 1;
+}
+
+/* raster_reorder (encoders/raster_reorder_scheme_impl.hpp:105-143): the same with a detail::reorder. */
+template <typename T>
+int raster_run(const T* in, T* out, const std::size_t* zyx, std::size_t tile, int decode, int nthreads)
+{
+    const shape_t shape(zyx, zyx + 3);
+    const std::size_t n = voxels(zyx);
+    const sqeazy::detail::reorder tiles(tile);
+    const T* stop = decode ? tiles.decode(in, in + n, out, shape, nthreads) : tiles.encode(in, in + n, out, shape, nthreads);
+    return stop == out + n ? 0 : 1;
+}
+
+/* bitswap1 encode (encoders/bitswap_scheme_impl.hpp:97-145): the elements behind the last whole group of
+ * 8 * sizeof(T) are copied as they are; the groups go through sse_bitplane_reorder_encode<1> when T is wider than a
+ * byte and sse_valid_length<1,T> accepts the WHOLE length, else through scalar_bitplane_reorder_encode<1>.
+ * (platform::use_vectorisation and compass' run-time SSE4 test, the other two conditions of :106-110, hold wherever
+ * this driver is built: the Makefile passes -msse4.1.)  The SSE gather loads with _mm_load_si128: the caller keeps
+ * 16-byte alignment wherever that branch is taken. */
+template <typename T>
+int bitswap1_encode(const T* in, T* out, std::size_t n, int nthreads)
+{
+    const std::size_t group = sizeof(T) * CHAR_BIT;
+    const std::size_t whole = n - n % group;
+    std::memcpy(out + whole, in + whole, (n - whole) * sizeof(T));
+    const bool sse = sizeof(T) > 1 && sqeazy::detail::sse_valid_length<1, T>(n);
+    const int failed = sse ? sqeazy::detail::sse_bitplane_reorder_encode<1>(in, out, whole, nthreads)
+                           : sqeazy::detail::scalar_bitplane_reorder_encode<1>(in, out, whole, nthreads);
+    return failed ? 1 : 0;
+}
+
+/* bitswap1 decode (encoders/bitswap_scheme_impl.hpp:181-197): the same tail, then always
+ * scalar_bitplane_reorder_decode<1> with its default of one thread */
+template <typename T>
+int bitswap1_decode(const T* in, T* out, std::size_t n)
+{
+    const std::size_t group = sizeof(T) * CHAR_BIT;
+    const std::size_t whole = n - n % group;
+    std::memcpy(out + whole, in + whole, (n - whole) * sizeof(T));
+    return sqeazy::detail::scalar_bitplane_reorder_decode<1>(in, out, whole) ? 1 : 0;
+}
+
+/* sqeazy::histogram<T>(begin, end) (hist_impl.hpp:162-185 -> fill_from_image -> fill_stats, :216-243) and
+ * calc_support(0.99f) (:359-381), the call of extract_darkest_face_supports.
+ * stats: smallest / largest populated bin, integral, mean, mean variation, median, median variation, mode,
+ * entropy, support. */
+template <typename T>
+int hist_stats(const T* in, std::size_t n, std::uint32_t* bins, double* stats)
+{
+    if (!n) return 1;
+    sqeazy::histogram<T> h(in, in + n);
+    std::copy(h.bins.begin(), h.bins.end(), bins);
+    stats[0] = h.smallest_populated_bin();
+    stats[1] = h.largest_populated_bin();
+    stats[2] = (double)h.integral();
+    stats[3] = h.mean();
+    stats[4] = h.mean_variation();
+    stats[5] = h.median();
+    stats[6] = h.median_variation();
+    stats[7] = h.mode();
+    stats[8] = h.entropy();
+    stats[9] = h.calc_support(0.99f);
+    return 0;
+}
+
+} /* namespace */
 
 extern "C" {
 
 int ref_lz4_version() { return LZ4_versionNumber(); }
 
-/* bitswap_scheme<uint16_t,1>::encode, SSE branch (bitswap_scheme_impl.hpp:97-145): requires
- * len % 128 == 0 and a 16-byte aligned input; returns 1 when the reference would have taken the
- * scalar branch instead (which needs Boost to compile and is not available here). */
+/* ---- filter stages: the reference's own templates behind the call sequence of its scheme classes ------------
+ * dtype: 0 = uint8, 1 = uint16, 2 = char (the tail-filter form behind a sink).  Every entry point returns 0 on
+ * success and 2 when the reference threw (e.g. std::length_error from a reserve() of a wrapped size). */
+#define REF_GUARD(expr) try { return (expr); } catch (...) { return 2; }
+
+/* the offsets and halo_size_x of diff_scheme::encode (diff_scheme_impl.hpp:92-103); returns the number of offsets */
+long ref_diff3x3x1_offsets(const size_t* shape, size_t* out, size_t cap, size_t* halo_size_x)
+{
+    try {
+        const rows_t rows = diff_rows(shape);
+        if (halo_size_x) *halo_size_x = rows.run;
+        for (size_t i = 0; i < rows.start.size() && i < cap; ++i) out[i] = rows.start[i];
+        return (long)rows.start.size();
+    } catch (...) { return -2; }
+}
+
+int ref_diff3x3x1(int dtype, const void* in, void* out, const size_t* shape, int decode, int nthreads)
+{
+    REF_GUARD(dtype == 1 ? (decode ? diff_walk<uint16_t, true>((const uint16_t*)in, (uint16_t*)out, shape, nthreads) : diff_walk<uint16_t, false>((const uint16_t*)in, (uint16_t*)out, shape, nthreads))
+            : dtype == 0 ? (decode ? diff_walk<uint8_t, true>((const uint8_t*)in, (uint8_t*)out, shape, nthreads) : diff_walk<uint8_t, false>((const uint8_t*)in, (uint8_t*)out, shape, nthreads))
+                         : (decode ? diff_walk<char, true>((const char*)in, (char*)out, shape, nthreads) : diff_walk<char, false>((const char*)in, (char*)out, shape, nthreads)))
+}
+
+/* out may be null: supports and threshold only */
+int ref_rmestbkrd(int dtype, const void* in, void* out, const size_t* shape, int nthreads, float* supports4, double* threshold)
+{
+    REF_GUARD(dtype == 1 ? rmestbkrd_encode((const uint16_t*)in, (uint16_t*)out, shape, nthreads, supports4, threshold)
+                         : rmestbkrd_encode((const uint8_t*)in, (uint8_t*)out, shape, nthreads, supports4, threshold))
+}
+
+/* the L2 size extract_darkest_face_supports compares a frame with (background_scheme_utils.hpp:44-45) */
+unsigned ref_cache_l2_bytes() { return compass::runtime::size::cache::level(2); }
+
+int ref_rmbkrd_neighbor5x5x5(int dtype, const void* in, void* out, const size_t* shape, long threshold, float fraction, int nthreads)
+{
+    REF_GUARD(dtype == 1 ? neighbor5_encode((const uint16_t*)in, (uint16_t*)out, shape, threshold, fraction, nthreads)
+                         : neighbor5_encode((const uint8_t*)in, (uint8_t*)out, shape, threshold, fraction, nthreads))
+}
+
+int ref_zcurve_reorder(int dtype, const void* in, void* out, const size_t* shape, size_t tile, int decode, int nthreads)
+{
+    REF_GUARD(dtype == 1 ? zcurve_run((const uint16_t*)in, (uint16_t*)out, shape, tile, decode, nthreads)
+                         : zcurve_run((const uint8_t*)in, (uint8_t*)out, shape, tile, decode, nthreads))
+}
+
+int ref_raster_reorder(int dtype, const void* in, void* out, const size_t* shape, size_t tile, int decode, int nthreads)
+{
+    REF_GUARD(dtype == 1 ? raster_run((const uint16_t*)in, (uint16_t*)out, shape, tile, decode, nthreads)
+                         : raster_run((const uint8_t*)in, (uint8_t*)out, shape, tile, decode, nthreads))
+}
+
+/* any length, any alignment except where the reference's SSE branch is taken (uint16, len % 128 == 0): 16 bytes there */
+int ref_bitswap1(int dtype, const void* in, void* out, size_t len, int decode, int nthreads)
+{
+    REF_GUARD(dtype == 1 ? (decode ? bitswap1_decode((const uint16_t*)in, (uint16_t*)out, len) : bitswap1_encode((const uint16_t*)in, (uint16_t*)out, len, nthreads))
+                         : (decode ? bitswap1_decode((const uint8_t*)in, (uint8_t*)out, len) : bitswap1_encode((const uint8_t*)in, (uint8_t*)out, len, nthreads)))
+}
+
+/* bitswap_scheme<uint16_t,1>::encode as before this entry point was generalised: 1 when the SSE branch's
+ * aligned loads would fault on `in` */
 int ref_bitswap1_encode_u16(const uint16_t* in, uint16_t* out, size_t len, int nthreads)
 {
-    if (len % 128 != 0 || len == 0) return 1;
-    if ((reinterpret_cast<uintptr_t>(in) & 15u) != 0) return 1;
-    sqeazy::detail::simd_segment_broadcast(in, in + len, out, nthreads);
-    return 0;
+    if (len % 128 == 0 && (reinterpret_cast<uintptr_t>(in) & 15u) != 0) return 1;
+    return ref_bitswap1(1, in, out, len, 0, nthreads);
+}
+
+/* bins: 256 or 65536 counters; stats: 10 doubles (see hist_stats) */
+int ref_hist_stats(int dtype, const void* in, size_t n, uint32_t* bins, double* stats)
+{
+    REF_GUARD(dtype == 1 ? hist_stats((const uint16_t*)in, n, bins, stats) : hist_stats((const uint8_t*)in, n, bins, stats))
 }
 
 static LZ4F_preferences_t make_prefs(int accel, int blocksize_id)
