@@ -240,6 +240,34 @@ SQY_FUNCTION_PREFIX int SQYAMD_Decode_Slabs_UI16(const char* src, const long* of
 SQY_FUNCTION_PREFIX int SQYAMD_Decode_Slabs_UI8(const char* src, const long* offsets, const long* lengths, int nslabs,
                                                 char* dst, long dst_capacity, long* frames);
 
+/* Many independent blobs -- tiles, time points, dataset chunks of any shape and pipeline -- decoded with ONE call, each into an allocation
+ * of its own: the way back from SQYAMD_PipelineEncode_Batch_*, whose offsets and lengths can be passed straight through.  Blob i lies at
+ * d_src + offsets[i], lengths[i] bytes (host arrays; any alignment) and is a complete sqeazy blob of the entry point's voxel type; rank,
+ * shape and pipeline may differ from blob to blob.  d_dsts: a HOST array of nblobs device pointers, each aligned at least to the voxel
+ * size, destination i dst_capacities[i] bytes long (host array).  decoded_bytes (host, may be NULL): out, every blob's decoded length.
+ * Blob i's voxels are byte for byte what SQYAMD_Decode_*_Device writes for it; nothing outside [d_dsts[i], d_dsts[i] + decoded length)
+ * is written.  Overlapping destinations are the caller's error and are not checked.
+ * Blobs that end in lz4 with chunks of one LZ4 block (the chunked layout, or a single chunk) are decoded in groups ("decode_batch_group_bytes"
+ * of LZ4 output each, at least one blob, one LZ4 block size): per group one frame-ranking launch, one LZ4 decode launch into the workspace,
+ * one inverse-transpose launch for all its `bitswap1->lz4` blobs and one copy launch for all its `lz4` blobs, two host round trips; other
+ * lz4-terminated pipelines run their remaining inverses blob by blob.  Every other blob (no lz4, the serial layout, chunks of several
+ * blocks) is decoded as by SQYAMD_Decode_*_Device, in blob order on the same stream; a batch may mix both kinds.
+ * Stream, context, ordering and thread-safety rules as SQYAMD_Decode_*_Device: the work runs behind what is queued on hip_stream and is
+ * complete on return; several host threads may call at once.  Return (as SQYAMD_Decode_Slabs_*): 0, 1 (bad arguments / headers -- nblobs
+ * <= 0, a NULL pointer, also inside d_dsts, a negative offset, a length <= 0, an invalid header, another voxel type, a capacity below the
+ * decoded length, a misaligned destination -- all checked before anything is written, decoded_bytes zeroed), or the composite code
+ * SQY_Decode gives the first damaged blob in blob order, returned after every blob has been decoded: the good ones are in place. */
+SQY_FUNCTION_PREFIX int SQYAMD_Decode_Batch_UI16_Device(const void* d_src, const long* offsets, const long* lengths, int nblobs,
+                                                        void* const* d_dsts, const long* dst_capacities, long* decoded_bytes, void* hip_stream);
+SQY_FUNCTION_PREFIX int SQYAMD_Decode_Batch_UI8_Device(const void* d_src, const long* offsets, const long* lengths, int nblobs,
+                                                       void* const* d_dsts, const long* dst_capacities, long* decoded_bytes, void* hip_stream);
+/* host-pointer variants: blobs in host memory at src + offsets[i], dsts[i] host pointers (any alignment); arguments and headers are checked
+ * on the host before any device is looked for */
+SQY_FUNCTION_PREFIX int SQYAMD_Decode_Batch_UI16(const char* src, const long* offsets, const long* lengths, int nblobs,
+                                                 char* const* dsts, const long* dst_capacities, long* decoded_bytes);
+SQY_FUNCTION_PREFIX int SQYAMD_Decode_Batch_UI8(const char* src, const long* offsets, const long* lengths, int nblobs,
+                                                char* const* dsts, const long* dst_capacities, long* decoded_bytes);
+
 /* ------------------------------------------------------------------------------------------------
  * Section C -- several GPUs (no reference counterpart: sqeazy is a single process with OpenMP loops)
  *
@@ -313,6 +341,10 @@ SQY_FUNCTION_PREFIX void SQYAMD_Release_Workspace(void);
  *                                     the pipeline allows (0: every blob decoded whole and the range copied out -- same bytes)
  *   "decode_slabs_joint"              1 [SQY_NO_DECODE_SLABS_JOINT=1 -> 0]  SQYAMD_Decode_Slabs_*: the chunked LZ4 blobs of a group indexed and
  *                                     decoded by one launch each (0: every blob on its own, as by SQYAMD_Decode_*_Device -- same bytes)
+ *   "decode_batch_joint"              1 [SQY_NO_DECODE_BATCH_JOINT=1 -> 0]  SQYAMD_Decode_Batch_*: the joint-eligible blobs of a group ranked, decoded and
+ *                                     transposed back by one launch each (0: every blob on its own, as by SQYAMD_Decode_*_Device -- same bytes)
+ *   "decode_batch_group_bytes"        2^32 [SQY_DECODE_BATCH_GROUP_BYTES=<bytes>, 1 .. 2^32]  .. the LZ4 output of one group (a group holds at
+ *                                     least one blob): bounds the workspace
  *   "encode_batch_joint"              1 [SQY_NO_ENCODE_BATCH_JOINT=1 -> 0]  SQYAMD_PipelineEncode_Batch_*: the joint-eligible volumes of a group share
  *                                     one launch of every kernel (0: every volume through the single-call path -- same bytes)
  *   "encode_batch_group_bytes"        2^30 [SQY_ENCODE_BATCH_GROUP_BYTES=<bytes>, 1 .. 2^32-1]  .. the LZ4 input of one group (a group holds at

@@ -32,6 +32,7 @@ EXPORTED_SYMBOLS = (
     "SQYAMD_Decode_UI16_Device", "SQYAMD_Decode_UI8_Device",
     "SQYAMD_Decode_Frames_UI16_Device", "SQYAMD_Decode_Frames_UI8_Device", "SQYAMD_Decode_Frames_UI16", "SQYAMD_Decode_Frames_UI8",
     "SQYAMD_Decode_Slabs_UI16_Device", "SQYAMD_Decode_Slabs_UI8_Device", "SQYAMD_Decode_Slabs_UI16", "SQYAMD_Decode_Slabs_UI8",
+    "SQYAMD_Decode_Batch_UI16_Device", "SQYAMD_Decode_Batch_UI8_Device", "SQYAMD_Decode_Batch_UI16", "SQYAMD_Decode_Batch_UI8",
     "SQYAMD_Profile_Enable", "SQYAMD_Profile_Reset", "SQYAMD_Profile_Get",
     "SQYAMD_Release_Workspace", "SQYAMD_Set_Option", "SQYAMD_Get_Option", "SQYAMD_Call_Stamps", "SQYAMD_Version", "SQYAMD_Header_Pipeline", "SQYAMD_Header_Build",
     "SQYAMD_Comm_UniqueId", "SQYAMD_Comm_Init", "SQYAMD_Comm_Destroy", "SQYAMD_Gather_Blobs",
@@ -101,6 +102,10 @@ def lib():
                                       ctypes.c_void_p]
         for f in ("SQYAMD_Decode_Slabs_UI8", "SQYAMD_Decode_Slabs_UI16"):
             getattr(L, f).argtypes = [ctypes.c_void_p, c_long_p, c_long_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_long, c_long_p]
+        for f in ("SQYAMD_Decode_Batch_UI8_Device", "SQYAMD_Decode_Batch_UI16_Device"):
+            getattr(L, f).argtypes = [ctypes.c_void_p, c_long_p, c_long_p, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), c_long_p, c_long_p, ctypes.c_void_p]
+        for f in ("SQYAMD_Decode_Batch_UI8", "SQYAMD_Decode_Batch_UI16"):
+            getattr(L, f).argtypes = [ctypes.c_void_p, c_long_p, c_long_p, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), c_long_p, c_long_p]
         _lib = L
     return _lib
 
@@ -370,6 +375,49 @@ def decode_slabs(blobs):
         offsets.append(at)
         at += len(b)
     return decode_slabs_packed(b"".join(blobs), offsets, [len(b) for b in blobs])
+
+
+def decode_batch_device(d_src, offsets, lengths, d_dsts, dst_capacities, dtype, stream=None):
+    """SQYAMD_Decode_Batch_*_Device: blob i at d_src + offsets[i] (lengths[i] bytes) into the device pointer d_dsts[i] (dst_capacities[i] bytes);
+    returns (rc, decoded_bytes).  The offsets and lengths of encode_batch_device can be passed straight through."""
+    n = len(offsets)
+    ptrs = (ctypes.c_void_p * max(n, 1))(*[int(p) for p in d_dsts])
+    decoded = (ctypes.c_long * max(n, 1))()
+    rc = getattr(lib(), "SQYAMD_Decode_Batch_%s_Device" % _suffix(dtype))(
+        ctypes.c_void_p(int(d_src)), _longs(offsets) if n else None, _longs(lengths) if n else None, ctypes.c_int(n), ptrs,
+        _longs(dst_capacities) if n else None, decoded, ctypes.c_void_p(stream or 0))
+    return rc, list(decoded[:n])
+
+
+def decode_batch(blobs):
+    """SQYAMD_Decode_Batch_UI8/UI16 on blobs of one voxel type (a list of byte strings; shapes and pipelines may differ): the counterpart of
+    encode_batch.  Returns the list of volumes (ndarrays); raises ValueError when the call returns non-zero."""
+    blobs = [bytes(b) for b in blobs]
+    if not blobs:
+        raise ValueError("decode_batch: no blobs")
+    size = decompressed_sizeof(blobs[0])
+    if size not in (1, 2):
+        raise ValueError("decode_batch: blob 0 holds no 8- or 16-bit voxels")
+    dtype = np.uint16 if size == 2 else np.uint8
+    outs = []
+    for i, b in enumerate(blobs):
+        shape = decompressed_shape(b)
+        if decompressed_sizeof(b) != size or not shape:
+            raise ValueError("decode_batch: blob %d has another voxel type or no shape" % i)
+        outs.append(np.empty(shape, dtype=dtype))
+    offsets, at = [], 0
+    for b in blobs:
+        offsets.append(at)
+        at += len(b)
+    src = np.frombuffer(b"".join(blobs), dtype=np.uint8)
+    n = len(blobs)
+    ptrs = (ctypes.c_void_p * n)(*[o.ctypes.data for o in outs])
+    decoded = (ctypes.c_long * n)()
+    rc = getattr(lib(), "SQYAMD_Decode_Batch_" + _suffix(dtype))(src.ctypes.data, _longs(offsets), _longs([len(b) for b in blobs]), ctypes.c_int(n), ptrs,
+                                                                 _longs([o.nbytes for o in outs]), decoded)
+    if rc:
+        raise ValueError("SQYAMD_Decode_Batch returned %d" % rc)
+    return outs
 
 
 def set_option(name, value):

@@ -63,6 +63,7 @@ constexpr long kWarmupMax = 1l << 30;
 constexpr long kStageLanesDefault = 2, kParseLanesDefault = 3;      // (measured: DESIGN.md section 5)
 constexpr long kBatchBytesMax = (1l << 32) - 1, kBatchGroupBytesDefault = 1l << 30;
 constexpr long kBatchJointMaxDefault = 128l << 20;                 // (the batch encode sweep: the largest size swept)
+constexpr uint64_t kSlabsGroupBytes = 4ull << 30;                  // slab-set and batch decode: LZ4 output of one group (slabs: inflight <= 0; batch: the option's default and maximum)
 struct Options {
     std::atomic<long> transpose_chain;                  // the bit-plane transposes of calls in flight on LIBRARY-OWNED streams run one after the other
     std::atomic<long> transpose_chain_caller_streams;   // .. on streams the callers bring as well (opt-in: couples those streams, see the bitswap1 stage)
@@ -77,6 +78,8 @@ struct Options {
     std::atomic<long> host_l2_bytes;                    // rmestbkrd: the host CPU's L2 size as the reference's compass reads it (detected; tests set it)
     std::atomic<long> decode_frames_subset;             // frame-range decode: only the LZ4 frames the range needs, where the pipeline allows (0: full decode + copy)
     std::atomic<long> decode_slabs_joint;               // slab-set decode: the chunked LZ4 blobs of a group indexed and decoded by one launch each (0: blob by blob)
+    std::atomic<long> decode_batch_joint;               // batch decode: the joint-eligible blobs of a group indexed, decoded and transposed back by one launch each (0: blob by blob)
+    std::atomic<long> decode_batch_group_bytes;         // .. the LZ4 output one group holds at most (a group holds at least one blob)
     std::atomic<long> encode_batch_joint;               // batch encode: the joint-eligible volumes of a group share one launch of every kernel (0: volume by volume)
     std::atomic<long> encode_batch_group_bytes;         // .. the LZ4 input one group holds at most (a group holds at least one volume)
     std::atomic<long> encode_batch_joint_max_bytes;     // .. a volume with more LZ4 input than this is encoded on its own (frames in place)
@@ -93,7 +96,8 @@ struct Options {
           decode_two_waves(env_flag("SQY_NO_DECODE_TWO_WAVES") ? 0 : 1), noise_digest(env_flag("SQY_NO_NOISE_DIGEST") ? 0 : 1),
           transpose_blocks_per_cu(env_number("SQY_TRANSPOSE_BLOCKS_PER_CU", 32, 1, 64)), stored_tail_index(env_flag("SQY_NO_STORED_TAIL_INDEX") ? 0 : 1),
           host_l2_bytes((long)sqy::host_l2_cache_bytes()), decode_frames_subset(env_flag("SQY_NO_DECODE_FRAMES_SUBSET") ? 0 : 1),
-          decode_slabs_joint(env_flag("SQY_NO_DECODE_SLABS_JOINT") ? 0 : 1), encode_batch_joint(env_flag("SQY_NO_ENCODE_BATCH_JOINT") ? 0 : 1),
+          decode_slabs_joint(env_flag("SQY_NO_DECODE_SLABS_JOINT") ? 0 : 1), decode_batch_joint(env_flag("SQY_NO_DECODE_BATCH_JOINT") ? 0 : 1),
+          decode_batch_group_bytes(env_number("SQY_DECODE_BATCH_GROUP_BYTES", (long)kSlabsGroupBytes, 1, (long)kSlabsGroupBytes)), encode_batch_joint(env_flag("SQY_NO_ENCODE_BATCH_JOINT") ? 0 : 1),
           encode_batch_group_bytes(env_number("SQY_ENCODE_BATCH_GROUP_BYTES", kBatchGroupBytesDefault, 1, kBatchBytesMax)),
           encode_batch_joint_max_bytes(env_number("SQY_ENCODE_BATCH_JOINT_MAX_BYTES", kBatchJointMaxDefault, 0, kBatchBytesMax)), stage_lanes(env_number("SQY_STAGE_LANES", kStageLanesDefault, 0, 2)),
           parse_lanes(env_number("SQY_PARSE_LANES", kParseLanesDefault, 1, sqy::LanePicker::kMaxLanes)) { sqy::set_bitswap1_blocks_per_cu(transpose_blocks_per_cu.load()); }
@@ -113,6 +117,8 @@ struct Options {
         if (!std::strcmp(name, "host_l2_bytes")) return &host_l2_bytes;
         if (!std::strcmp(name, "decode_frames_subset")) return &decode_frames_subset;
         if (!std::strcmp(name, "decode_slabs_joint")) return &decode_slabs_joint;
+        if (!std::strcmp(name, "decode_batch_joint")) return &decode_batch_joint;
+        if (!std::strcmp(name, "decode_batch_group_bytes")) return &decode_batch_group_bytes;
         if (!std::strcmp(name, "encode_batch_joint")) return &encode_batch_joint;
         if (!std::strcmp(name, "encode_batch_group_bytes")) return &encode_batch_group_bytes;
         if (!std::strcmp(name, "encode_batch_joint_max_bytes")) return &encode_batch_joint_max_bytes;
@@ -2333,7 +2339,6 @@ int decode_from_host(const char* src, long srclength, char* dst, int elem_size)
 // one joint block index and one LZ4 decode launch for all of them, then each blob's remaining inverses (bitswap1, diff3x3x1, ..) from the
 // group's LZ4 output into its place.  Every other blob -- and every blob of a group whose decode raised the error flag -- goes through
 // decode_on_device, one at a time.
-constexpr uint64_t kSlabsGroupBytes = 4ull << 30;       // LZ4 output of one group (inflight <= 0)
 constexpr uint64_t kSlabsHeadPrefix = 1ull << 16;       // bytes of every blob fetched for its header at first
 
 struct SlabBlob : sqy::Lz4DecodeGeometry {              // (of the LZ4 stage's input, on the joint path)
@@ -2352,9 +2357,21 @@ struct SlabBlob : sqy::Lz4DecodeGeometry {              // (of the LZ4 stage's i
 
 uint64_t align_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
 
+// What SQYAMD_Decode_Batch_* makes of a group (decode_slab_group's `batch`; nullptr: a slab set).  Every destination is an allocation of its
+// own, so the group's LZ4 output always goes to the workspace, laid out by the plan (SlabBlob::out_base is the plan's out_at), and behind
+// the LZ4 decode the `bitswap1->lz4` blobs share one launch of the batched inverse transposer and the `lz4` blobs one of the batched copy
+// (the plan's tile tables).  Every other pipeline runs its remaining inverses blob by blob, as in a slab set.
+struct BatchGroup {
+    const std::vector<sqy::DecodeBatchBlob>* plan_in;   // what the plan was made from: made again, with the dropped blobs named, when the ranking refuses one
+    uint64_t group_bytes;
+    size_t group;                                       // this group's index in the plan
+    const sqy::DecodeBatchGroup* g;
+    int elem_size;
+};
+
 // The joint path for blobs g[0..m) (slab order).  Blobs it cannot take are appended to `single`; the flag raised: all of g go there.
 int decode_slab_group(Context& cx, const uint8_t* d_src, std::vector<SlabBlob>& blobs, const std::vector<size_t>& g, uint8_t* d_dst,
-                      uint64_t volume_bytes, hipStream_t stream, std::vector<size_t>& single)
+                      uint64_t volume_bytes, hipStream_t stream, std::vector<size_t>& single, const BatchGroup* batch = nullptr)
 {
     Workspace* ws = &cx.ws;
     std::vector<PendingEvent>* pend = &cx.pending;
@@ -2392,7 +2409,7 @@ int decode_slab_group(Context& cx, const uint8_t* d_src, std::vector<SlabBlob>& 
     }
     std::vector<unsigned char> hdesc(sqy::lz4_frame_rank_batch_desc_bytes(m));
     SQY_HIP(hipMemsetAsync(flag, 0, 64, stream));
-    SQY_TIMED("slabs_frame_index", sqy::launch_lz4_frame_rank_batch(jobs.data(), m, di + o_desc, hdesc.data(), stream));
+    SQY_TIMED(batch ? "batch_frame_index" : "slabs_frame_index", sqy::launch_lz4_frame_rank_batch(jobs.data(), m, di + o_desc, hdesc.data(), stream));
     if (ws->slabs_host.ensure((size_t)m * 64)) return 1;
     const uint32_t* hc_all = static_cast<const uint32_t*>(ws->slabs_host.p);
     SQY_HIP(hipMemcpyAsync(ws->slabs_host.p, counts, (size_t)m * 64, hipMemcpyDeviceToHost, stream));
@@ -2415,7 +2432,7 @@ int decode_slab_group(Context& cx, const uint8_t* d_src, std::vector<SlabBlob>& 
     // 3. where each blob's LZ4 output goes: straight into its place in the volume when the LZ4 stage's inverse produces the volume for
     // every blob of the group (lz4, frame_shuffle->lz4, behind the background heads) and the places are 16-byte aligned, else the workspace
     std::vector<unsigned char> maps;
-    bool direct = true;
+    bool direct = batch == nullptr;
     for (size_t b : mem) {
         SlabBlob& s = blobs[b];
         DecodeCall& c = *s.call;
@@ -2434,9 +2451,10 @@ int decode_slab_group(Context& cx, const uint8_t* d_src, std::vector<SlabBlob>& 
     for (size_t b : mem) {
         SlabBlob& s = blobs[b];
         if (direct) s.out_base = s.dst_off;
-        else { s.out_base = out_bytes; out_bytes = align_up(out_bytes + s.total, 256); }
+        else if (!batch) { s.out_base = out_bytes; out_bytes = align_up(out_bytes + s.total, 256); }
     }
     if (direct) out_bytes = volume_bytes;
+    if (batch) out_bytes = batch->g->out_bytes;
     uint8_t* out = direct ? d_dst : nullptr;
     if (!direct) {
         if (ws->slabs_out.ensure(std::max<uint64_t>(out_bytes, 16))) return 1;
@@ -2451,7 +2469,9 @@ int decode_slab_group(Context& cx, const uint8_t* d_src, std::vector<SlabBlob>& 
     if (jn > 0x7fffffffull) { for (size_t b : mem) single.push_back(b); return 0; }
     const uint64_t o_maps = align_up(np * sizeof(sqy::Lz4JointPart), 256), o_jblk = align_up(o_maps + maps.size(), 256),
                    o_jff = o_jblk + jn * 16, o_jout = align_up(o_jff + (jn + 1) * 4, 256);
-    if (ws->slabs_joint.ensure(o_jout + jn * 16)) return 1;
+    // (batch: behind them the job lists and tile tables of the two launches that follow the LZ4 decode)
+    const uint64_t o_jobs = align_up(o_jout + jn * 16, 256), jobs_bytes = batch ? 2 * align_up((uint64_t)np * sizeof(sqy::Bitswap1Job) + ((uint64_t)np + 1) * 4, 256) : 0;
+    if (ws->slabs_joint.ensure(batch ? o_jobs + jobs_bytes : o_jout + jn * 16)) return 1;
     uint8_t* dj = static_cast<uint8_t*>(ws->slabs_joint.p);
     std::vector<unsigned char> up(o_maps + maps.size());
     for (uint32_t k = 0, jbase = 0; k < np; ++k) {
@@ -2477,7 +2497,7 @@ int decode_slab_group(Context& cx, const uint8_t* d_src, std::vector<SlabBlob>& 
             if (const int rc = s.call->zero_unnamed_places(out + s.out_base, s.fs_bytes, s.total)) return rc;
     }
     const bool side_ok = cx.ensure_side();
-    SQY_TIMED("slabs_lz4_decode",
+    SQY_TIMED(batch ? "batch_lz4_decode" : "slabs_lz4_decode",
               sqy::launch_lz4_frames_joint_decode(d_src, reinterpret_cast<const sqy::Lz4JointPart*>(dj), np, maxf, dj + o_jblk,
                                                   reinterpret_cast<uint32_t*>(dj + o_jff), reinterpret_cast<uint64_t*>(dj + o_jout), (uint32_t)jn, out,
                                                   out_bytes, blobs[mem[0]].block_bytes, (uint32_t)std::min<uint64_t>(ncomp, 0xffffffffull), flag, stream,
@@ -2485,9 +2505,42 @@ int decode_slab_group(Context& cx, const uint8_t* d_src, std::vector<SlabBlob>& 
 
     // 5. every blob's remaining inverses, from its LZ4 output into its place
     bool first = true;
+    std::vector<unsigned char> job_tables;                              // (alive until the verdict's synchronisation)
+    if (batch) {
+        // the `bitswap1->lz4` blobs: ONE inverse-transpose launch from the workspace into their destinations; the `lz4` blobs: ONE copy launch
+        const sqy::DecodeBatchGroup* pg = batch->g;
+        sqy::DecodeBatchPlan again;
+        if (mem.size() != g.size()) {
+            std::vector<uint8_t> dropped(blobs.size(), 0);
+            for (size_t b : g) dropped[b] = 1;
+            for (size_t b : mem) dropped[b] = 0;
+            again = sqy::decode_batch_plan(*batch->plan_in, batch->group_bytes, &dropped);
+            pg = &again.groups[batch->group];
+        }
+        job_tables.assign(jobs_bytes, 0);
+        uint64_t at = 0;
+        for (const sqy::DecodeBatchTiles* t : {&pg->planes, &pg->plain}) {
+            const uint32_t nj = (uint32_t)t->jobs.size();
+            if (!nj) continue;
+            const uint64_t tiles_at = at + (uint64_t)nj * sizeof(sqy::Bitswap1Job);
+            for (uint32_t j = 0; j < nj; ++j) {
+                const SlabBlob& s = blobs[t->jobs[j]];
+                const sqy::Bitswap1Job job{out + s.out_base, s.call->d_dst, (*batch->plan_in)[t->jobs[j]].len};
+                std::memcpy(job_tables.data() + at + j * sizeof(job), &job, sizeof(job));
+            }
+            std::memcpy(job_tables.data() + tiles_at, t->first_tile.data(), ((size_t)nj + 1) * 4);
+            SQY_HIP(hipMemcpyAsync(dj + o_jobs + at, job_tables.data() + at, tiles_at - at + ((size_t)nj + 1) * 4, hipMemcpyHostToDevice, stream));
+            const sqy::Bitswap1Job* d_jobs = reinterpret_cast<const sqy::Bitswap1Job*>(dj + o_jobs + at);
+            const uint32_t* d_tiles = reinterpret_cast<const uint32_t*>(dj + o_jobs + tiles_at);
+            if (t == &pg->planes) SQY_TIMED("batch_bitswap1_decode", sqy::launch_bitswap1_decode_batch(d_jobs, d_tiles, nj, t->ntiles, batch->elem_size, stream));
+            else SQY_TIMED("batch_copy", sqy::launch_batch_copy(d_jobs, d_tiles, nj, t->ntiles, stream));
+            at = align_up(tiles_at + ((uint64_t)nj + 1) * 4, 256);
+        }
+    }
     for (size_t b : mem) {
         SlabBlob& s = blobs[b];
         DecodeCall& c = *s.call;
+        if (batch && (*batch->plan_in)[b].form != sqy::DecodeBatchForm::stages) continue;       // (done above)
         // (the quantiser's table goes to ws->small by a synchronous copy: the blob before must be done with it)
         if (!first) for (const Stage& st : c.pipe.stages) if (st.kind == StageKind::quantiser) { SQY_HIP(hipStreamSynchronize(stream)); break; }
         first = false;
@@ -2506,6 +2559,45 @@ int decode_slab_group(Context& cx, const uint8_t* d_src, std::vector<SlabBlob>& 
     return 0;
 }
 
+// The headers of a blob set (blobs[i].src, .len given): every blob's prefix with one synchronisation (a header longer than that: fetched on
+// its own), each admitted for the entry point's voxel type and then shown to check(i) (false: refused) -- all before anything is written.
+// who: how the messages name the entry point.
+template <class F>
+int fetch_blob_headers(Context& cx, std::vector<SlabBlob>& blobs, int want_elem, hipStream_t stream, const char* who, F&& check)
+{
+    const int n = (int)blobs.size();
+    if (cx.ws.slabs_host.ensure((size_t)n * kSlabsHeadPrefix)) return 1;
+    char* hp = static_cast<char*>(cx.ws.slabs_host.p);
+    for (int i = 0; i < n; ++i)
+        SQY_HIP(hipMemcpyAsync(hp + (uint64_t)i * kSlabsHeadPrefix, blobs[i].src, std::min(kSlabsHeadPrefix, blobs[i].len), hipMemcpyDeviceToHost, stream));
+    SQY_HIP(hipStreamSynchronize(stream));
+    for (int i = 0; i < n; ++i) {
+        SlabBlob& b = blobs[i];
+        const uint64_t take = std::min(kSlabsHeadPrefix, b.len);
+        b.h = sqy::header_unpack(hp + (uint64_t)i * kSlabsHeadPrefix, hp + (uint64_t)i * kSlabsHeadPrefix + take);
+        if (!b.h.valid && take < b.len && fetch_header(b.src, b.len, stream, b.h)) return 1;
+        if (!b.h.valid) { std::fprintf(stderr, "[sqeazy]\t %s: no sqy header in blob %d\n", who, i); return 1; }
+        if (!admit_blob(b.h, b.len, want_elem, &b.raw, (std::string(who) + ": blob " + std::to_string(i)).c_str())) return 1;
+        if (!check(i)) return 1;
+    }
+    return 0;
+}
+
+// Whether blob b may take the joint path, with its DecodeCall (destination dst) made: the last stage lz4 and chunks of one LZ4 block.  More
+// than one chunk for a slab set (the ranking then tells the chunked layout from the serial one); a batch also takes ONE chunk -- a
+// single-chunk stream is the same bytes in both layouts.
+bool joint_candidate(Context& cx, SlabBlob& b, void* dst, int want_elem, hipStream_t stream, uint64_t min_chunks)
+{
+    b.call.reset(new DecodeCall(cx, stream, dst, b.h, Pipeline::from_string(b.h.pipename), b.raw / (uint64_t)want_elem, b.src + b.h.size));
+    DecodeCall& c = *b.call;
+    const size_t ns = c.pipe.stages.size();
+    if (ns == 0 || c.pipe.stages[ns - 1].kind != StageKind::lz4) return false;
+    b.li = ns - 1;
+    b.total = c.in_bytes(b.li);
+    static_cast<sqy::Lz4DecodeGeometry&>(b) = sqy::lz4_decode_geometry(c.pipe.stages[b.li].lz4, b.total);
+    return b.nchunks >= min_chunks && b.chunk <= b.block_bytes;
+}
+
 int decode_slabs_on_device(Context& cx, const void* d_src_v, const long* offsets, const long* lengths, int nslabs, void* d_dst_v, uint64_t dst_capacity,
                            long* frames, int inflight, int want_elem, hipStream_t stream)
 {
@@ -2522,27 +2614,18 @@ int decode_slabs_on_device(Context& cx, const void* d_src_v, const long* offsets
     }
     // 1. the headers: every blob's prefix with one synchronisation (a header longer than that: fetched on its own), checked before anything
     // is written
-    if (cx.ws.slabs_host.ensure((size_t)nslabs * kSlabsHeadPrefix)) return 1;
-    char* hp = static_cast<char*>(cx.ws.slabs_host.p);
-    for (int i = 0; i < nslabs; ++i)
-        SQY_HIP(hipMemcpyAsync(hp + (uint64_t)i * kSlabsHeadPrefix, blobs[i].src, std::min(kSlabsHeadPrefix, blobs[i].len), hipMemcpyDeviceToHost, stream));
-    SQY_HIP(hipStreamSynchronize(stream));
     uint64_t volume = 0;
-    for (int i = 0; i < nslabs; ++i) {
-        SlabBlob& b = blobs[i];
-        const uint64_t take = std::min(kSlabsHeadPrefix, b.len);
-        b.h = sqy::header_unpack(hp + (uint64_t)i * kSlabsHeadPrefix, hp + (uint64_t)i * kSlabsHeadPrefix + take);
-        if (!b.h.valid && take < b.len && fetch_header(b.src, b.len, stream, b.h)) return 1;
-        if (!b.h.valid) { std::fprintf(stderr, "[sqeazy]\t decode slabs: no sqy header in blob %d\n", i); return 1; }
-        if (!admit_blob(b.h, b.len, want_elem, &b.raw, ("decode slabs: blob " + std::to_string(i)).c_str())) return 1;
-        const sqy::HeaderInfo& h0 = blobs[0].h;
-        if (b.h.shape.size() != h0.shape.size() || !std::equal(b.h.shape.begin() + 1, b.h.shape.end(), h0.shape.begin() + 1)) {
-            std::fprintf(stderr, "[sqeazy]\t decode slabs: blob %d's shape does not continue blob 0's\n", i);
-            return 1;
-        }
-        b.dst_off = volume;
-        volume += b.raw;
-    }
+    if (fetch_blob_headers(cx, blobs, want_elem, stream, "decode slabs", [&](int i) {
+            SlabBlob& b = blobs[i];
+            const sqy::HeaderInfo& h0 = blobs[0].h;
+            if (b.h.shape.size() != h0.shape.size() || !std::equal(b.h.shape.begin() + 1, b.h.shape.end(), h0.shape.begin() + 1)) {
+                std::fprintf(stderr, "[sqeazy]\t decode slabs: blob %d's shape does not continue blob 0's\n", i);
+                return false;
+            }
+            b.dst_off = volume;
+            volume += b.raw;
+            return true;
+        })) return 1;
     if (volume > dst_capacity) { std::fprintf(stderr, "[sqeazy]\t decode slabs: %llu bytes do not fit the buffer\n", (unsigned long long)volume); return 1; }
     if (frames) for (int i = 0; i < nslabs; ++i) frames[i] = (long)blobs[i].h.shape[0];
 
@@ -2550,19 +2633,7 @@ int decode_slabs_on_device(Context& cx, const void* d_src_v, const long* offsets
     std::vector<size_t> joint, single;
     for (int i = 0; i < nslabs; ++i) {
         SlabBlob& b = blobs[i];
-        bool ok = g_opt.decode_slabs_joint.load() != 0;
-        if (ok) {
-            b.call.reset(new DecodeCall(cx, stream, d_dst + b.dst_off, b.h, Pipeline::from_string(b.h.pipename), b.raw / (uint64_t)want_elem, b.src + b.h.size));
-            DecodeCall& c = *b.call;
-            const size_t ns = c.pipe.stages.size();
-            ok = ns > 0 && c.pipe.stages[ns - 1].kind == StageKind::lz4;
-            if (ok) {
-                b.li = ns - 1;
-                b.total = c.in_bytes(b.li);
-                static_cast<sqy::Lz4DecodeGeometry&>(b) = sqy::lz4_decode_geometry(c.pipe.stages[b.li].lz4, b.total);
-                ok = b.nchunks > 1 && b.chunk <= b.block_bytes;
-            }
-        }
+        const bool ok = g_opt.decode_slabs_joint.load() != 0 && joint_candidate(cx, b, d_dst + b.dst_off, want_elem, stream, 2);
         (ok ? joint : single).push_back((size_t)i);
     }
     // 3. groups: LZ4 output up to kSlabsGroupBytes (at least one blob), at most `inflight` blobs, one block size
@@ -2606,6 +2677,134 @@ int decode_slabs_from_host(const char* src, const long* offsets, const long* len
     return decode_staged(src, span, dst, volume, [&](Context& cx, void* d_src, void* d_dst, hipStream_t stream) {
         return decode_slabs_on_device(cx, d_src, offsets, lengths, nslabs, d_dst, volume, frames, 0, elem_size, stream);
     });
+}
+
+// ---- batch decode (SQYAMD_Decode_Batch_*) -------------------------------------------------------------------------------------
+// Independent blobs -- any shape, any pipeline, each destination an allocation of its own --, the way back from a batch encode.  The
+// joint-eligible ones (the last stage lz4, chunks of one LZ4 block; ONE chunk will do) go through decode_slab_group in the groups
+// sqy::decode_batch_plan deals them to: per group one frame ranking, one read-back of its counts, one joint index and LZ4 decode into the
+// workspace, one inverse-transpose launch for all `bitswap1->lz4` blobs, one copy launch for all `lz4` blobs, one verdict read-back.
+// Every other blob, and what a group hands back, goes through decode_on_device in blob order.
+struct BatchDecodeArgs { const long* offsets; const long* lengths; int nblobs; void* const* dsts; const long* capacities; long* decoded; };
+
+// the arguments alone, before any device is looked for; decoded_bytes zeroed where it can be
+int admit_decode_batch(const void* src, const BatchDecodeArgs& a)
+{
+    if (a.decoded && a.nblobs > 0) for (int i = 0; i < a.nblobs; ++i) a.decoded[i] = 0;
+    if (!src || !a.offsets || !a.lengths || !a.dsts || !a.capacities || a.nblobs <= 0) { std::fprintf(stderr, "[sqeazy]\t decode batch: bad arguments\n"); return 1; }
+    for (int i = 0; i < a.nblobs; ++i)
+        if (a.offsets[i] < 0 || a.lengths[i] <= 0 || !a.dsts[i]) {
+            std::fprintf(stderr, "[sqeazy]\t decode batch: blob %d at %ld, %ld bytes%s\n", i, a.offsets[i], a.lengths[i], a.dsts[i] ? "" : ", no destination");
+            return 1;
+        }
+    return 0;
+}
+
+// what a blob's header has to say before anything is written: it fits its destination, which is aligned to the voxel size
+bool batch_blob_fits(int i, uint64_t raw, const void* dst, long capacity, int elem_size)
+{
+    if (raw > (uint64_t)std::max(capacity, 0l)) { std::fprintf(stderr, "[sqeazy]\t decode batch: blob %d's %llu bytes do not fit its buffer\n", i, (unsigned long long)raw); return false; }
+    if (reinterpret_cast<uintptr_t>(dst) % (uintptr_t)elem_size) { std::fprintf(stderr, "[sqeazy]\t decode batch: destination %d not aligned to the voxel size\n", i); return false; }
+    return true;
+}
+
+int decode_batch_on_device(Context& cx, const void* d_src_v, const BatchDecodeArgs& a, int want_elem, hipStream_t stream)
+{
+    const uint8_t* d_src = static_cast<const uint8_t*>(d_src_v);
+    DrainOnExit drain{stream, &cx.pending, cx.side};
+    const size_t n = (size_t)a.nblobs;
+    std::vector<SlabBlob> blobs(n);
+    for (size_t i = 0; i < n; ++i) {
+        blobs[i].src_off = (uint64_t)a.offsets[i];
+        blobs[i].src = d_src + a.offsets[i];
+        blobs[i].len = (uint64_t)a.lengths[i];
+    }
+    // 1. the headers, checked before anything is written
+    if (fetch_blob_headers(cx, blobs, want_elem, stream, "decode batch", [&](int i) { return batch_blob_fits(i, blobs[i].raw, a.dsts[i], a.capacities[i], want_elem); }))
+        return 1;
+    if (a.decoded) for (size_t i = 0; i < n; ++i) a.decoded[i] = (long)blobs[i].raw;
+
+    // 2. who takes the joint path and in which group (the plan: host-only, sqy_pipeline.cpp)
+    std::vector<sqy::DecodeBatchBlob> plan_in(n);
+    std::vector<size_t> single;
+    const bool joint_on = g_opt.decode_batch_joint.load() != 0;
+    for (size_t i = 0; i < n && joint_on; ++i) {
+        SlabBlob& b = blobs[i];
+        sqy::DecodeBatchBlob& p = plan_in[i];
+        p.eligible = joint_candidate(cx, b, a.dsts[i], want_elem, stream, 1);
+        if (!p.eligible) continue;
+        const DecodeCall& c = *b.call;
+        const std::vector<Stage>& st = c.pipe.stages;
+        p.total = b.total;
+        p.block_bytes = b.block_bytes;
+        if (st.size() == 1) { p.form = sqy::DecodeBatchForm::plain; p.len = b.total; }
+        else if (st.size() == 2 && st[0].kind == StageKind::bitswap1 && c.elem_before[0] == want_elem && c.count_before[0] == c.n && b.total == b.raw) {
+            p.form = sqy::DecodeBatchForm::planes;
+            p.len = c.n;
+        }
+    }
+    const uint64_t group_bytes = (uint64_t)g_opt.decode_batch_group_bytes.load();
+    const sqy::DecodeBatchPlan plan = sqy::decode_batch_plan(plan_in, group_bytes);
+    for (size_t i = 0; i < n; ++i) if (plan.group_of[i] < 0) single.push_back(i);
+    for (size_t gi = 0; gi < plan.groups.size(); ++gi) {
+        const sqy::DecodeBatchGroup& g = plan.groups[gi];
+        std::vector<size_t> members(g.blobs.begin(), g.blobs.end());
+        for (size_t k = 0; k < members.size(); ++k) blobs[members[k]].out_base = g.out_at[k];
+        const BatchGroup bg{&plan_in, group_bytes, gi, &g, want_elem};
+        if (const int rc = decode_slab_group(cx, d_src, blobs, members, nullptr, 0, stream, single, &bg)) return rc;
+    }
+    // 3. the others, one at a time, in blob order
+    std::sort(single.begin(), single.end());
+    for (size_t b : single)
+        blobs[b].rc = decode_on_device(cx, blobs[b].src, blobs[b].len, a.dsts[b], blobs[b].raw, want_elem, stream);
+    for (const SlabBlob& b : blobs) if (b.rc) return b.rc;
+    return 0;
+}
+
+int decode_batch_device(const void* d_src, const BatchDecodeArgs& a, int elem_size, void* hip_stream)
+{
+    if (admit_decode_batch(d_src, a)) return 1;
+    ContextLease lease;
+    if (!lease.ctx) { std::fprintf(stderr, "[sqeazy]\t no usable HIP device\n"); return 1; }
+    return decode_batch_on_device(*lease.ctx, d_src, a, elem_size, static_cast<hipStream_t>(hip_stream));
+}
+
+// the host-pointer variant (not tuned): the span of the blobs staged up, one call of the device driver, every volume brought back
+int decode_batch_from_host(const char* src, const BatchDecodeArgs& a, int elem_size)
+{
+    if (admit_decode_batch(src, a)) return 1;
+    const size_t n = (size_t)a.nblobs;
+    std::vector<uint64_t> raw(n), at(n);
+    uint64_t span = 0, out_bytes = 0;
+    for (size_t i = 0; i < n; ++i) {                                      // untrusted input: before anything is allocated or uploaded
+        const sqy::HeaderInfo h = sqy::header_unpack(src + a.offsets[i], src + a.offsets[i] + a.lengths[i]);
+        if (!h.valid) { std::fprintf(stderr, "[sqeazy]\t decode batch: no sqy header in blob %d\n", (int)i); return 1; }
+        if (!admit_blob(h, (uint64_t)a.lengths[i], elem_size, &raw[i], ("decode batch: blob " + std::to_string(i)).c_str())) return 1;
+        if (raw[i] > (uint64_t)std::max(a.capacities[i], 0l)) { std::fprintf(stderr, "[sqeazy]\t decode batch: blob %d's %llu bytes do not fit its buffer\n", (int)i, (unsigned long long)raw[i]); return 1; }
+        span = std::max<uint64_t>(span, (uint64_t)a.offsets[i] + (uint64_t)a.lengths[i]);
+        at[i] = out_bytes;
+        out_bytes += align_up(raw[i], 256);
+    }
+    if (!device_present()) { std::fprintf(stderr, "[sqeazy]\t no MI355X (HIP device) visible: sqeazy_amd has no CPU path\n"); return 1; }
+    ContextLease lease;
+    if (!lease.ctx) { std::fprintf(stderr, "[sqeazy]\t no usable HIP device\n"); return 1; }
+    Workspace* ws = &lease.ctx->ws;
+    hipStream_t stream = lease.ctx->own_stream();
+    if (!stream) { std::fprintf(stderr, "[sqeazy]\t no HIP stream\n"); return 1; }
+    if (ws->io_src.ensure(std::max<uint64_t>(span, 16)) || ws->io_dst.ensure(std::max<uint64_t>(out_bytes, 16))) return 1;
+    int dev_id = 0;
+    SQY_HIP(hipGetDevice(&dev_id));
+    if (!lease.ctx->stager.copy(ws->io_src.p, const_cast<char*>(src), (size_t)span, true, dev_id)) { std::fprintf(stderr, "[sqeazy]\t host to device transfer failed\n"); return 1; }
+    std::vector<void*> d_dsts(n);
+    std::vector<long> caps(n);
+    for (size_t i = 0; i < n; ++i) { d_dsts[i] = static_cast<char*>(ws->io_dst.p) + at[i]; caps[i] = (long)raw[i]; }
+    const BatchDecodeArgs d{a.offsets, a.lengths, a.nblobs, d_dsts.data(), caps.data(), a.decoded};
+    const int rc = decode_batch_on_device(*lease.ctx, ws->io_src.p, d, elem_size, stream);
+    SQY_HIP(hipStreamSynchronize(stream));
+    // (a damaged blob's code comes back behind the good ones, which are in place: they go home as well)
+    for (size_t i = 0; i < n; ++i)
+        if (!lease.ctx->stager.copy(d_dsts[i], static_cast<char*>(a.dsts[i]), (size_t)raw[i], false, dev_id)) { std::fprintf(stderr, "[sqeazy]\t device to host transfer failed\n"); return 1; }
+    return rc;
 }
 
 // The body of the device-memory encode entry points: the blob at d_dst (_Device), or where *dstoffset says (at: _DeviceAt), with the
@@ -3286,6 +3485,32 @@ int SQYAMD_Decode_Slabs_UI8(const char* src, const long* offsets, const long* le
     return guarded([&]() -> int { return decode_slabs_from_host(src, offsets, lengths, nslabs, dst, dst_capacity, frames, 1); });
 }
 
+int SQYAMD_Decode_Batch_UI16_Device(const void* d_src, const long* offsets, const long* lengths, int nblobs, void* const* d_dsts, const long* dst_capacities,
+                                    long* decoded_bytes, void* hip_stream)
+{
+    return guarded([&]() -> int { return decode_batch_device(d_src, BatchDecodeArgs{offsets, lengths, nblobs, d_dsts, dst_capacities, decoded_bytes}, 2, hip_stream); });
+}
+
+int SQYAMD_Decode_Batch_UI8_Device(const void* d_src, const long* offsets, const long* lengths, int nblobs, void* const* d_dsts, const long* dst_capacities,
+                                   long* decoded_bytes, void* hip_stream)
+{
+    return guarded([&]() -> int { return decode_batch_device(d_src, BatchDecodeArgs{offsets, lengths, nblobs, d_dsts, dst_capacities, decoded_bytes}, 1, hip_stream); });
+}
+
+int SQYAMD_Decode_Batch_UI16(const char* src, const long* offsets, const long* lengths, int nblobs, char* const* dsts, const long* dst_capacities, long* decoded_bytes)
+{
+    return guarded([&]() -> int {
+        return decode_batch_from_host(src, BatchDecodeArgs{offsets, lengths, nblobs, reinterpret_cast<void* const*>(dsts), dst_capacities, decoded_bytes}, 2);
+    });
+}
+
+int SQYAMD_Decode_Batch_UI8(const char* src, const long* offsets, const long* lengths, int nblobs, char* const* dsts, const long* dst_capacities, long* decoded_bytes)
+{
+    return guarded([&]() -> int {
+        return decode_batch_from_host(src, BatchDecodeArgs{offsets, lengths, nblobs, reinterpret_cast<void* const*>(dsts), dst_capacities, decoded_bytes}, 1);
+    });
+}
+
 int SQYAMD_Decode_UI8_Device(const void* d_src, long srclength, void* d_dst, long dst_capacity, void* hip_stream)
 {
     return guarded([&]() -> int {
@@ -3324,6 +3549,7 @@ int SQYAMD_Set_Option(const char* name, long value)
     else if (o == &g_opt.host_l2_bytes) { if (value < 0 || value > (long)UINT32_MAX) return 1; }
     else if (o == &g_opt.stage_lanes) { if (value < 0 || value > 2) return 1; }
     else if (o == &g_opt.encode_batch_group_bytes) { if (value < 1 || value > kBatchBytesMax) return 1; }
+    else if (o == &g_opt.decode_batch_group_bytes) { if (value < 1 || value > (long)kSlabsGroupBytes) return 1; }
     else if (o == &g_opt.encode_batch_joint_max_bytes) { if (value < 0 || value > kBatchBytesMax) return 1; }
     else if (o == &g_opt.lane_calls || o == &g_opt.lane_backlog_fallbacks || o == &g_opt.lane_blocked_fallbacks) { if (value != 0) return 1; }
     else if (o == &g_opt.parse_lanes) { if (value < 1 || value > sqy::LanePicker::kMaxLanes) return 1; }

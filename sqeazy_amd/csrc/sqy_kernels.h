@@ -304,6 +304,13 @@ struct Bitswap1Range {
     uint64_t w0, w1, v0, v1, L;
 };
 hipError_t launch_bitswap1_decode_range(const uint8_t* in, void* out, const Bitswap1Range& r, int elem_size, const uint16_t* lut, hipStream_t stream);
+// ---- batch decode (SQYAMD_Decode_Batch_*): the blobs of a group share one launch of every kernel ----
+// The inverse of launch_bitswap1_batch on the same tables: job j's planes + tail at `in` (16-byte aligned) become its `len` voxels at
+// `out` (any voxel-aligned address; sixteen-byte stores where it and the plane size allow, word by word where not).  first_tile: njobs + 1
+// words, the prefix sums of batch_bitswap1_tiles(len) (sqy::decode_batch_plan makes them)
+hipError_t launch_bitswap1_decode_batch(const Bitswap1Job* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ntiles, int elem_size, hipStream_t stream);
+// plain copies on the same kind of table: job j's `len` BYTES from `in` to `out`, first_tile the prefix sums of batch_bitswap1_tiles(bytes)
+hipError_t launch_batch_copy(const Bitswap1Job* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ntiles, hipStream_t stream);
 // one launch per frame over the columns the stage can touch (frame z needs the decoded frame z-1), the other columns one plain copy
 // -- on copy_stream next to the chain when that, fork and join are given.  (scratch: unused since round 3)
 // diff3x3x1_decode_chain_columns: how many leading columns of a row go through that chain in the usual 16-bit geometry (a multiple of 8;

@@ -6042,6 +6042,155 @@ void bitswap1_decode_u16_regs(const uint16_t* __restrict__ in, uint16_t* __restr
     }
 }
 
+// Batch decode: the inverse bit-plane transposes of many blobs with one launch (SQYAMD_Decode_Batch_*), the inverse of
+// bitswap1_batch_kernel on the same job and tile tables -- job j's planes and tail at `in` (16-byte aligned: the group's LZ4 output),
+// its `len` voxels to `out` (any voxel-aligned address).  A workgroup is one tile of BSWB_TILE_VOX voxels of one job, a thread owns 16
+// bytes of every plane (one 16-byte load per plane, W of them a plane apart) and with them 128 voxels in a row: sixteen-byte stores
+// where the job's pointers and plane size allow, word by word (bitswap1_decode_kernel's loop) where not.  The arithmetic is
+// bitswap1_decode_kernel's: plane W - 1 - b carries bit b, voxel j of a word at bit W - 1 - j; the len % W voxels behind the planes
+// are copied by tile 0.  The registers: pl[16][4] and one transpose of sixteen words at a time, no LDS.
+static_assert(BSWB_TILE_VOX == kBatchTileVoxels, "the host-only planners count tiles of this size");
+template <int ELEM>
+__global__ __launch_bounds__(256)
+void bitswap1_decode_batch_kernel(const Bitswap1Job* __restrict__ jobs, const uint32_t* __restrict__ first_tile, uint32_t njobs)
+{
+    constexpr uint32_t W = 8 * ELEM, WPT = BSWB_THREAD_VOX / W;        // voxels per word, words per thread
+    uint32_t lo = 0, hi = njobs;                                      // first_tile[lo] <= blockIdx.x < first_tile[hi]
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (first_tile[mid] <= blockIdx.x) lo = mid; else hi = mid;
+    }
+    const Bitswap1Job job = jobs[lo];
+    const uint32_t tile = blockIdx.x - first_tile[lo], tid = threadIdx.x;
+    const uint64_t seg = job.len / W, L = seg * W;                    // words per plane; voxels in the planes
+    const uint8_t* __restrict__ in = static_cast<const uint8_t*>(job.in);
+    uint8_t* __restrict__ out = static_cast<uint8_t*>(job.out);
+    if (tile == 0 && tid < job.len - L) {                             // tail voxels [L, len): copied verbatim
+        if (ELEM == 2) reinterpret_cast<uint16_t*>(out)[L + tid] = reinterpret_cast<const uint16_t*>(in)[L + tid];
+        else out[L + tid] = in[L + tid];
+    }
+    const uint64_t w0 = ((uint64_t)tile * 256u + tid) * WPT;
+    if (w0 >= seg) return;
+    const uint64_t plane_bytes = seg * ELEM;
+    const bool wide = w0 + WPT <= seg && ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out) | plane_bytes) & 15u) == 0;
+    if constexpr (ELEM == 2) {
+        if (wide) {
+            uint32_t pl[16][4];                                       // pl[b] = eight words of the plane that carries bit b
+#pragma unroll
+            for (int b = 0; b < 16; ++b) {
+                const uint4 t = *reinterpret_cast<const uint4*>(in + (uint64_t)(15 - b) * plane_bytes + w0 * 2u);
+                pl[b][0] = t.x; pl[b][1] = t.y; pl[b][2] = t.z; pl[b][3] = t.w;
+            }
+            uint4* dst = reinterpret_cast<uint4*>(out + w0 * 32u);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {                             // words w0 + 2 q (group A, low halves) and w0 + 2 q + 1 (group B)
+                uint32_t r[16];
+#pragma unroll
+                for (int b = 0; b < 16; ++b) r[b] = pl[b][q];
+                transpose16x16_pairs(r);                              // r[i] = voxel 15 - i of group A | of group B << 16
+                uint32_t ga[8], gb[8];
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    ga[k] = __builtin_amdgcn_perm(r[14 - 2 * k], r[15 - 2 * k], 0x05040100u);
+                    gb[k] = __builtin_amdgcn_perm(r[14 - 2 * k], r[15 - 2 * k], 0x07060302u);
+                }
+                dst[4 * q] = make_uint4(ga[0], ga[1], ga[2], ga[3]);
+                dst[4 * q + 1] = make_uint4(ga[4], ga[5], ga[6], ga[7]);
+                dst[4 * q + 2] = make_uint4(gb[0], gb[1], gb[2], gb[3]);
+                dst[4 * q + 3] = make_uint4(gb[4], gb[5], gb[6], gb[7]);
+            }
+        } else {
+            const uint16_t* in16 = reinterpret_cast<const uint16_t*>(in);
+            uint16_t* out16 = reinterpret_cast<uint16_t*>(out);
+            for (uint64_t w = w0; w < w0 + WPT && w < seg; ++w) {
+                uint32_t plane[16];
+#pragma unroll
+                for (uint32_t b = 0; b < 16; ++b) plane[b] = in16[(uint64_t)(15 - b) * seg + w];
+#pragma unroll
+                for (uint32_t j = 0; j < 16; ++j) {
+                    uint32_t v = 0;
+#pragma unroll
+                    for (uint32_t b = 0; b < 16; ++b) v |= ((plane[b] >> (15 - j)) & 1u) << b;
+                    out16[w * 16 + j] = (uint16_t)v;
+                }
+            }
+        }
+    } else {
+        if (wide) {
+            uint32_t pw[8][4];                                        // pw[b] = 16 bytes of the plane that carries bit b
+#pragma unroll
+            for (int b = 0; b < 8; ++b) {
+                const uint4 t = *reinterpret_cast<const uint4*>(in + (uint64_t)(7 - b) * plane_bytes + w0);
+                pw[b][0] = t.x; pw[b][1] = t.y; pw[b][2] = t.z; pw[b][3] = t.w;
+            }
+            uint4* dst = reinterpret_cast<uint4*>(out + w0 * 8u);
+#pragma unroll
+            for (int g = 0; g < 16; g += 2) {
+                uint32_t d[4];
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {
+                    // byte b of (hi:lo) = plane byte of bit b (voxel j at bit 7 - j), gathered and transposed as
+                    // bitswap1_u8_decode_lut_kernel does it: afterwards byte i of hi:lo = voxel 7 - i
+                    constexpr uint32_t Z = 0x0c;                      // v_perm selector: a zero byte
+                    const uint32_t c = (uint32_t)((g + u) & 3), wdx = (uint32_t)((g + u) >> 2);
+                    const uint32_t s01 = c | ((4u + c) << 8) | (Z << 16) | (Z << 24), s23 = Z | (Z << 8) | (c << 16) | ((4u + c) << 24);
+                    uint32_t lo_ = __builtin_amdgcn_perm(pw[1][wdx], pw[0][wdx], s01) | __builtin_amdgcn_perm(pw[3][wdx], pw[2][wdx], s23);
+                    uint32_t hi_ = __builtin_amdgcn_perm(pw[5][wdx], pw[4][wdx], s01) | __builtin_amdgcn_perm(pw[7][wdx], pw[6][wdx], s23);
+                    uint32_t y;
+                    y = (lo_ ^ (lo_ >> 7)) & 0x00AA00AAu; lo_ ^= y ^ (y << 7);
+                    y = (hi_ ^ (hi_ >> 7)) & 0x00AA00AAu; hi_ ^= y ^ (y << 7);
+                    y = (lo_ ^ (lo_ >> 14)) & 0x0000CCCCu; lo_ ^= y ^ (y << 14);
+                    y = (hi_ ^ (hi_ >> 14)) & 0x0000CCCCu; hi_ ^= y ^ (y << 14);
+                    y = (lo_ ^ (hi_ << 4)) & 0xF0F0F0F0u; lo_ ^= y; hi_ ^= y >> 4;
+                    d[2 * u] = __builtin_bswap32(hi_);                // voxels 0..3 of the word
+                    d[2 * u + 1] = __builtin_bswap32(lo_);            // voxels 4..7
+                }
+                dst[g >> 1] = make_uint4(d[0], d[1], d[2], d[3]);
+            }
+        } else {
+            for (uint64_t w = w0; w < w0 + WPT && w < seg; ++w) {
+                uint32_t plane[8];
+#pragma unroll
+                for (uint32_t b = 0; b < 8; ++b) plane[b] = in[(uint64_t)(7 - b) * seg + w];
+#pragma unroll
+                for (uint32_t j = 0; j < 8; ++j) {
+                    uint32_t v = 0;
+#pragma unroll
+                    for (uint32_t b = 0; b < 8; ++b) v |= ((plane[b] >> (7 - j)) & 1u) << b;
+                    out[w * 8 + j] = (uint8_t)v;
+                }
+            }
+        }
+    }
+}
+
+// Batch decode, plain `lz4` blobs: job j's `len` BYTES from `in` to `out`, on the tile table of the transposer (a tile = BSWB_TILE_VOX
+// bytes): sixteen bytes per thread and step where both pointers allow, byte by byte where not
+__global__ __launch_bounds__(256)
+void batch_copy_kernel(const Bitswap1Job* __restrict__ jobs, const uint32_t* __restrict__ first_tile, uint32_t njobs)
+{
+    uint32_t lo = 0, hi = njobs;
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (first_tile[mid] <= blockIdx.x) lo = mid; else hi = mid;
+    }
+    const Bitswap1Job job = jobs[lo];
+    const uint64_t base = (uint64_t)(blockIdx.x - first_tile[lo]) * BSWB_TILE_VOX;
+    if (base >= job.len) return;
+    const uint64_t end = job.len - base < BSWB_TILE_VOX ? job.len : base + BSWB_TILE_VOX;
+    const uint8_t* __restrict__ in = static_cast<const uint8_t*>(job.in);
+    uint8_t* __restrict__ out = static_cast<uint8_t*>(job.out);
+    if (((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15u) == 0) {
+#pragma unroll
+        for (uint32_t i = 0; i < BSWB_TILE_VOX / 4096u; ++i) {
+            const uint64_t o = base + ((uint64_t)i * 256u + threadIdx.x) * 16u;
+            if (o + 16u <= end) *reinterpret_cast<uint4*>(out + o) = *reinterpret_cast<const uint4*>(in + o);
+            else for (uint64_t k = o; k < end; ++k) out[k] = in[k];
+        }
+    } else
+        for (uint64_t o = base + threadIdx.x; o < end; o += 256u) out[o] = in[o];
+}
+
 // inverse diff3x3x1, voxels [r0, r1) of frame z (everything before them must be final): diff_scheme_impl.hpp:143-194.
 // The reference decodes in raster order and reads its own output: a rewritten voxel needs the 3x3 neighbourhood one frame back,
 // i.e. indices idx - frame - X - 1 .. idx - frame + X + 1.  Those lie in frame z-1 -- except for the last X + 1 voxels of a
@@ -7353,6 +7502,22 @@ hipError_t launch_bitswap1_decode_range(const uint8_t* in, void* out, const Bits
         hipLaunchKernelGGL((bitswap1_decode_range_kernel<uint8_t, true>), dim3((unsigned)g), dim3(256), 0, stream, in, out, r, lut);
     else
         hipLaunchKernelGGL((bitswap1_decode_range_kernel<uint8_t, false>), dim3((unsigned)g), dim3(256), 0, stream, in, out, r, lut);
+    return hipGetLastError();
+}
+
+hipError_t launch_bitswap1_decode_batch(const Bitswap1Job* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ntiles, int elem_size, hipStream_t stream)
+{
+    if (njobs == 0 || ntiles == 0) return hipSuccess;
+    if (elem_size == 2) hipLaunchKernelGGL(bitswap1_decode_batch_kernel<2>, dim3(ntiles), dim3(256), 0, stream, d_jobs, d_first_tile, njobs);
+    else if (elem_size == 1) hipLaunchKernelGGL(bitswap1_decode_batch_kernel<1>, dim3(ntiles), dim3(256), 0, stream, d_jobs, d_first_tile, njobs);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+hipError_t launch_batch_copy(const Bitswap1Job* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ntiles, hipStream_t stream)
+{
+    if (njobs == 0 || ntiles == 0) return hipSuccess;
+    hipLaunchKernelGGL(batch_copy_kernel, dim3(ntiles), dim3(256), 0, stream, d_jobs, d_first_tile, njobs);
     return hipGetLastError();
 }
 

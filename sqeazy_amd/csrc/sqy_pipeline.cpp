@@ -323,6 +323,42 @@ Lz4BatchPlan lz4_batch_plan(const Lz4Params& p, const std::vector<uint64_t>& tot
     return plan;
 }
 
+DecodeBatchPlan decode_batch_plan(const std::vector<DecodeBatchBlob>& blobs, uint64_t group_bytes, const std::vector<uint8_t>* dropped)
+{
+    DecodeBatchPlan plan;
+    plan.group_of.assign(blobs.size(), -1);
+    auto tiles_of = [](uint64_t len) { return std::max<uint64_t>((len + kBatchTileVoxels - 1) / kBatchTileVoxels, 1); };
+    uint64_t group_tiles = 0;
+    for (size_t i = 0; i < blobs.size(); ++i) {
+        const DecodeBatchBlob& b = blobs[i];
+        if (!b.eligible || i > (size_t)UINT32_MAX) continue;
+        const uint64_t need = round_up(b.total, 256), tiles = tiles_of(b.len);
+        // (a launch's grid counts its tiles in 31 bits)
+        if (plan.groups.empty() || plan.groups.back().out_bytes + need > group_bytes || plan.groups.back().block_bytes != b.block_bytes ||
+            group_tiles + tiles > (uint64_t)INT32_MAX) {
+            plan.groups.emplace_back();
+            plan.groups.back().block_bytes = b.block_bytes;
+            group_tiles = 0;
+        }
+        DecodeBatchGroup& g = plan.groups.back();
+        g.blobs.push_back((uint32_t)i);
+        g.out_at.push_back(g.out_bytes);
+        g.out_bytes += need;
+        group_tiles += tiles;
+        plan.group_of[i] = (int32_t)(plan.groups.size() - 1);
+        if (b.form == DecodeBatchForm::stages || (dropped && i < dropped->size() && (*dropped)[i])) continue;
+        DecodeBatchTiles& t = b.form == DecodeBatchForm::planes ? g.planes : g.plain;
+        t.jobs.push_back((uint32_t)i);
+        t.first_tile.push_back(t.ntiles);
+        t.ntiles += (uint32_t)tiles;
+    }
+    for (DecodeBatchGroup& g : plan.groups) {
+        g.planes.first_tile.push_back(g.planes.ntiles);
+        g.plain.first_tile.push_back(g.plain.ntiles);
+    }
+    return plan;
+}
+
 Lz4DedupeLayout lz4_dedupe_layout(const Lz4EncodeLayout& lay, uint64_t piece_hash_words)
 {
     Lz4DedupeLayout d;

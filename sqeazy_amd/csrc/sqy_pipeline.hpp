@@ -106,6 +106,34 @@ struct Lz4BatchPlan {
 // one volume, so a volume larger than the bound gets a group of its own).
 Lz4BatchPlan lz4_batch_plan(const Lz4Params& p, const std::vector<uint64_t>& totals, unsigned nthreads, uint64_t group_bytes, uint64_t joint_max);
 
+// ---- batch decode (SQYAMD_Decode_Batch_*): many blobs, one launch per kernel ----
+// What the planner knows of blob i: the bytes its LZ4 stage decodes to, the LZ4 block size, whether it may take the joint path at all
+// (the last stage lz4, chunk <= block_bytes), and what follows the LZ4 decode --
+//   stages: its remaining inverses, blob by blob | planes: `bitswap1->lz4`, one job of the batched inverse transposer (len voxels) |
+//   plain: `lz4`, one job of the batched copy (len = total bytes)
+enum class DecodeBatchForm : uint8_t { stages, planes, plain };
+struct DecodeBatchBlob { uint64_t total = 0, block_bytes = 0, len = 0; bool eligible = false; DecodeBatchForm form = DecodeBatchForm::stages; };
+constexpr uint64_t kBatchTileVoxels = 256 * 128;        // a workgroup of the batched transposers and of the batched copy: 256 threads x 128 voxels
+// A launch's job list and tile table: jobs[j] is a blob, its tiles are [first_tile[j], first_tile[j + 1]) (max(1, ceil(len / tile)) each)
+struct DecodeBatchTiles { std::vector<uint32_t> jobs, first_tile; uint32_t ntiles = 0; };
+// The blobs that share one launch of every kernel: blob blobs[j]'s LZ4 output lies at out_at[j] of the group's workspace (256-byte
+// aligned, out_bytes in all); planes / plain: the tables of the two batched launches behind the LZ4 decode
+struct DecodeBatchGroup {
+    std::vector<uint32_t> blobs;                // ascending
+    std::vector<uint64_t> out_at;
+    uint64_t out_bytes = 0, block_bytes = 0;
+    DecodeBatchTiles planes, plain;
+};
+struct DecodeBatchPlan {
+    std::vector<int32_t> group_of;              // per blob: its group, -1: not joint-eligible (the single-call path takes it)
+    std::vector<DecodeBatchGroup> groups;
+};
+// Eligible blobs are dealt to groups in order; a group is closed when the next blob would take its LZ4 output (every blob's rounded up
+// to 256 bytes) past group_bytes or has another block size.  A group holds at least one blob, so a blob larger than the bound gets a
+// group of its own.  dropped (optional, one flag per blob): blobs the frame ranking refused -- they keep their place in the group and
+// in the workspace but get no job in the tile tables.
+DecodeBatchPlan decode_batch_plan(const std::vector<DecodeBatchBlob>& blobs, uint64_t group_bytes, const std::vector<uint8_t>* dropped = nullptr);
+
 // Frames in place: a 16-bit bitswap1 in front of lz4 writes chunk k of the plane stream into the destination at body0 + k * in_stride,
 // where it is the body of the stored frame it may become -- kLz4FrameHead bytes (frame header 7, block size field 4) in front, the end
 // mark behind: kLz4FrameGap bytes between two chunks.  t0 (>= header_max, the longest sqy header) is where frame 0 begins.
