@@ -249,7 +249,12 @@ SQY_FUNCTION_PREFIX int SQYAMD_Decode_Slabs_UI8(const char* src, const long* off
  * is written.  Overlapping destinations are the caller's error and are not checked.
  * Blobs that end in lz4 with chunks of one LZ4 block (the chunked layout, or a single chunk) are decoded in groups ("decode_batch_group_bytes"
  * of LZ4 output each, at least one blob, one LZ4 block size): per group one frame-ranking launch, one LZ4 decode launch into the workspace,
- * one inverse-transpose launch for all its `bitswap1->lz4` blobs and one copy launch for all its `lz4` blobs, two host round trips; other
+ * one inverse-transpose launch for all its `bitswap1->lz4` blobs and one copy launch for all its `lz4` blobs, two host round trips.  16-bit
+ * blobs only: one launch of the inverse transpose with the look-up for all its `quantiser->bitswap1->lz4` blobs (the decode table from the
+ * header, or from decode_lut_path, as the single call reads it), and for all its `diff3x3x1->bitswap1->lz4` and `diff3x3x1->lz4` blobs whose
+ * geometry lets the single call decode several frames per launch (every row's reach inside the row, X a multiple of 8, at most 320
+ * columns that can change, a destination on the 16-byte grid) one launch per 8 frames of the deepest of them plus one -- the residual
+ * volumes of `diff3x3x1->bitswap1->lz4` blobs take as much workspace again, which counts against "decode_batch_group_bytes".  Other
  * lz4-terminated pipelines run their remaining inverses blob by blob.  Every other blob (no lz4, the serial layout, chunks of several
  * blocks) is decoded as by SQYAMD_Decode_*_Device, in blob order on the same stream; a batch may mix both kinds.
  * Stream, context, ordering and thread-safety rules as SQYAMD_Decode_*_Device: the work runs behind what is queued on hip_stream and is
@@ -343,8 +348,8 @@ SQY_FUNCTION_PREFIX void SQYAMD_Release_Workspace(void);
  *                                     decoded by one launch each (0: every blob on its own, as by SQYAMD_Decode_*_Device -- same bytes)
  *   "decode_batch_joint"              1 [SQY_NO_DECODE_BATCH_JOINT=1 -> 0]  SQYAMD_Decode_Batch_*: the joint-eligible blobs of a group ranked, decoded and
  *                                     transposed back by one launch each (0: every blob on its own, as by SQYAMD_Decode_*_Device -- same bytes)
- *   "decode_batch_group_bytes"        2^32 [SQY_DECODE_BATCH_GROUP_BYTES=<bytes>, 1 .. 2^32]  .. the LZ4 output of one group (a group holds at
- *                                     least one blob): bounds the workspace
+ *   "decode_batch_group_bytes"        2^32 [SQY_DECODE_BATCH_GROUP_BYTES=<bytes>, 1 .. 2^32]  .. the LZ4 output of one group, and the residual
+ *                                     volumes of its `diff3x3x1->bitswap1->lz4` blobs (a group holds at least one blob): bounds the workspace
  *   "encode_batch_joint"              1 [SQY_NO_ENCODE_BATCH_JOINT=1 -> 0]  SQYAMD_PipelineEncode_Batch_*: the joint-eligible volumes of a group share
  *                                     one launch of every kernel (0: every volume through the single-call path -- same bytes)
  *   "encode_batch_group_bytes"        2^30 [SQY_ENCODE_BATCH_GROUP_BYTES=<bytes>, 1 .. 2^32-1]  .. the LZ4 input of one group (a group holds at

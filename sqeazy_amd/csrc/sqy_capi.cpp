@@ -1602,23 +1602,30 @@ int encode_from_host(const char* pipeline, const char* src, long* shape, unsigne
 
 // ---- decode --------------------------------------------------------------------------------------
 // dynamic_pipeline::decode (dynamic_pipeline.hpp:740-846): tail filters^-1, sink^-1, head filters^-1 in reverse.
-// the quantiser's decode LUT (256 x u16, base64 in the header) into ws->small; synchronous: the host copy does not outlive the call
-int quantiser_lut_to_device(const sqy::Stage& st, Workspace* ws)
+// the quantiser's decode LUT (256 x u16): from the file the configuration names, else base64 out of the header.  say: with the messages
+bool quantiser_lut_on_host(const sqy::Stage& st, std::vector<unsigned char>* lut, bool say = true)
 {
-    std::vector<unsigned char> lut;
     auto lp = st.cfg.find("decode_lut_path");
     if (lp != st.cfg.end()) {
         // quantiser_scheme_impl.hpp:83-85: a path in the configuration wins over a LUT string
-        lut.resize(512);
-        if (!sqy::quantiser_lut_from_file(lp->second, reinterpret_cast<uint16_t*>(lut.data()), 256)) {
-            std::fprintf(stderr, "lut from %s cannot be loaded, decoding skipped\n", lp->second.c_str());               // quantiser_utils.hpp:559-562
-            return 1;
+        lut->resize(512);
+        if (!sqy::quantiser_lut_from_file(lp->second, reinterpret_cast<uint16_t*>(lut->data()), 256)) {
+            if (say) std::fprintf(stderr, "lut from %s cannot be loaded, decoding skipped\n", lp->second.c_str());       // quantiser_utils.hpp:559-562
+            return false;
         }
     } else {
         auto it = st.cfg.find("decode_lut_string");
-        if (it == st.cfg.end() || !sqy::from_verbatim(it->second, &lut)) { std::fprintf(stderr, "[sqeazy]\t quantiser: no decode_lut_string in the header\n"); return 1; }
+        if (it == st.cfg.end() || !sqy::from_verbatim(it->second, lut)) { if (say) std::fprintf(stderr, "[sqeazy]\t quantiser: no decode_lut_string in the header\n"); return false; }
     }
-    if (lut.size() != 512) { std::fprintf(stderr, "[sqeazy]\t quantiser: malformed decode LUT\n"); return 1; }
+    if (lut->size() != 512) { if (say) std::fprintf(stderr, "[sqeazy]\t quantiser: malformed decode LUT\n"); return false; }
+    return true;
+}
+
+// .. into ws->small; synchronous: the host copy does not outlive the call
+int quantiser_lut_to_device(const sqy::Stage& st, Workspace* ws)
+{
+    std::vector<unsigned char> lut;
+    if (!quantiser_lut_on_host(st, &lut)) return 1;
     if (ws->small.ensure(4096)) return 1;
     SQY_HIP(hipMemcpy(ws->small.p, lut.data(), 512, hipMemcpyHostToDevice));
     return 0;
@@ -2353,6 +2360,7 @@ struct SlabBlob : sqy::Lz4DecodeGeometry {              // (of the LZ4 stage's i
     uint64_t out_base = 0, map_off = 0, fs_bytes = 0;
     bool remap = false;
     int rc = 0;
+    std::vector<unsigned char> lut;                     // a batch's `quantiser->bitswap1->lz4` blob on the joint path: its decode table
 };
 
 uint64_t align_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
@@ -2360,7 +2368,10 @@ uint64_t align_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
 // What SQYAMD_Decode_Batch_* makes of a group (decode_slab_group's `batch`; nullptr: a slab set).  Every destination is an allocation of its
 // own, so the group's LZ4 output always goes to the workspace, laid out by the plan (SlabBlob::out_base is the plan's out_at), and behind
 // the LZ4 decode the `bitswap1->lz4` blobs share one launch of the batched inverse transposer and the `lz4` blobs one of the batched copy
-// (the plan's tile tables).  Every other pipeline runs its remaining inverses blob by blob, as in a slab set.
+// (the plan's tile tables); the `quantiser->bitswap1->lz4` blobs one of the transposer with the look-up, their tables uploaded with the job
+// tables; the 16-bit `diff3x3x1->bitswap1->lz4` and `diff3x3x1->lz4` blobs in the chain geometry one launch per chain step for all of them
+// (launch_diff3x3x1_decode_batch_copy, _step), the former's inverse transposes in the `bitswap1->lz4` blobs' launch, into the workspace.  Every other
+// pipeline runs its remaining inverses blob by blob, as in a slab set.
 struct BatchGroup {
     const std::vector<sqy::DecodeBatchBlob>* plan_in;   // what the plan was made from: made again, with the dropped blobs named, when the ranking refuses one
     uint64_t group_bytes;
@@ -2469,8 +2480,36 @@ int decode_slab_group(Context& cx, const uint8_t* d_src, std::vector<SlabBlob>& 
     if (jn > 0x7fffffffull) { for (size_t b : mem) single.push_back(b); return 0; }
     const uint64_t o_maps = align_up(np * sizeof(sqy::Lz4JointPart), 256), o_jblk = align_up(o_maps + maps.size(), 256),
                    o_jff = o_jblk + jn * 16, o_jout = align_up(o_jff + (jn + 1) * 4, 256);
-    // (batch: behind them the job lists and tile tables of the two launches that follow the LZ4 decode)
-    const uint64_t o_jobs = align_up(o_jout + jn * 16, 256), jobs_bytes = batch ? 2 * align_up((uint64_t)np * sizeof(sqy::Bitswap1Job) + ((uint64_t)np + 1) * 4, 256) : 0;
+    // (batch: behind them what the launches that follow the LZ4 decode read -- job lists, tile and strip tables, the quantiser blobs' LUTs --,
+    // one region of 256-byte aligned parts, uploaded at once; the plan made again without the blobs the ranking refused)
+    const sqy::DecodeBatchGroup* pg = batch ? batch->g : nullptr;
+    sqy::DecodeBatchPlan again;
+    if (batch && mem.size() != g.size()) {
+        std::vector<uint8_t> dropped(blobs.size(), 0);
+        for (size_t b : g) dropped[b] = 1;
+        for (size_t b : mem) dropped[b] = 0;
+        again = sqy::decode_batch_plan(*batch->plan_in, batch->group_bytes, &dropped);
+        pg = &again.groups[batch->group];
+    }
+    struct TablePart { uint64_t jobs_at = 0, tiles_at = 0, extra_at = 0; };           // (extra: the LUTs | the diff jobs' tile table)
+    TablePart part[4];                                                                // planes, plain, quantised, diff
+    uint64_t jobs_bytes = 0;
+    if (batch) {
+        const sqy::DecodeBatchTiles* tt[3] = {&pg->planes, &pg->plain, &pg->quantised};
+        for (int k = 0; k < 3; ++k) {
+            const uint64_t nj = tt[k]->jobs.size();
+            part[k].jobs_at = jobs_bytes;
+            part[k].tiles_at = part[k].jobs_at + nj * sizeof(sqy::Bitswap1Job);
+            part[k].extra_at = align_up(part[k].tiles_at + (nj + 1) * 4, 256);
+            jobs_bytes = k == 2 ? part[k].extra_at + nj * 512 : part[k].extra_at;
+        }
+        const uint64_t nd = pg->diff.jobs.size();
+        part[3].jobs_at = align_up(jobs_bytes, 256);
+        part[3].tiles_at = part[3].jobs_at + nd * sizeof(sqy::DiffBatchJob);             // (first_strip)
+        part[3].extra_at = part[3].tiles_at + (nd + 1) * 4;                              // (first_tile)
+        jobs_bytes = align_up(part[3].extra_at + (nd + 1) * 4, 256);
+    }
+    const uint64_t o_jobs = align_up(o_jout + jn * 16, 256);
     if (ws->slabs_joint.ensure(batch ? o_jobs + jobs_bytes : o_jout + jn * 16)) return 1;
     uint8_t* dj = static_cast<uint8_t*>(ws->slabs_joint.p);
     std::vector<unsigned char> up(o_maps + maps.size());
@@ -2507,34 +2546,52 @@ int decode_slab_group(Context& cx, const uint8_t* d_src, std::vector<SlabBlob>& 
     bool first = true;
     std::vector<unsigned char> job_tables;                              // (alive until the verdict's synchronisation)
     if (batch) {
-        // the `bitswap1->lz4` blobs: ONE inverse-transpose launch from the workspace into their destinations; the `lz4` blobs: ONE copy launch
-        const sqy::DecodeBatchGroup* pg = batch->g;
-        sqy::DecodeBatchPlan again;
-        if (mem.size() != g.size()) {
-            std::vector<uint8_t> dropped(blobs.size(), 0);
-            for (size_t b : g) dropped[b] = 1;
-            for (size_t b : mem) dropped[b] = 0;
-            again = sqy::decode_batch_plan(*batch->plan_in, batch->group_bytes, &dropped);
-            pg = &again.groups[batch->group];
-        }
+        // the `bitswap1->lz4` blobs: ONE inverse-transpose launch from the workspace into their destinations -- and into the workspace for the
+        // `diff3x3x1->bitswap1->lz4` blobs --; the `lz4` blobs: ONE copy launch; the `quantiser->bitswap1->lz4` blobs: ONE launch of the
+        // transposer with the look-up; the diff blobs: ONE launch per chain step
         job_tables.assign(jobs_bytes, 0);
-        uint64_t at = 0;
-        for (const sqy::DecodeBatchTiles* t : {&pg->planes, &pg->plain}) {
-            const uint32_t nj = (uint32_t)t->jobs.size();
-            if (!nj) continue;
-            const uint64_t tiles_at = at + (uint64_t)nj * sizeof(sqy::Bitswap1Job);
+        const sqy::DecodeBatchDiff& df = pg->diff;
+        auto form_of = [&](uint32_t b) { return (*batch->plan_in)[b].form; };
+        std::vector<uint64_t> res_of(blobs.size(), 0);                  // a diff blob's residual volume in the workspace
+        for (size_t j = 0; j < df.jobs.size(); ++j) res_of[df.jobs[j]] = df.res_at[j];
+        const sqy::DecodeBatchTiles* tt[3] = {&pg->planes, &pg->plain, &pg->quantised};
+        for (int k = 0; k < 3; ++k) {
+            const uint32_t nj = (uint32_t)tt[k]->jobs.size();
             for (uint32_t j = 0; j < nj; ++j) {
-                const SlabBlob& s = blobs[t->jobs[j]];
-                const sqy::Bitswap1Job job{out + s.out_base, s.call->d_dst, (*batch->plan_in)[t->jobs[j]].len};
-                std::memcpy(job_tables.data() + at + j * sizeof(job), &job, sizeof(job));
+                const uint32_t b = tt[k]->jobs[j];
+                const SlabBlob& s = blobs[b];
+                void* to = form_of(b) == sqy::DecodeBatchForm::diff_planes ? static_cast<void*>(out + res_of[b]) : s.call->d_dst;
+                const sqy::Bitswap1Job job{out + s.out_base, to, (*batch->plan_in)[b].len};
+                std::memcpy(job_tables.data() + part[k].jobs_at + j * sizeof(job), &job, sizeof(job));
+                if (k == 2) std::memcpy(job_tables.data() + part[k].extra_at + (size_t)j * 512, s.lut.data(), 512);
             }
-            std::memcpy(job_tables.data() + tiles_at, t->first_tile.data(), ((size_t)nj + 1) * 4);
-            SQY_HIP(hipMemcpyAsync(dj + o_jobs + at, job_tables.data() + at, tiles_at - at + ((size_t)nj + 1) * 4, hipMemcpyHostToDevice, stream));
-            const sqy::Bitswap1Job* d_jobs = reinterpret_cast<const sqy::Bitswap1Job*>(dj + o_jobs + at);
-            const uint32_t* d_tiles = reinterpret_cast<const uint32_t*>(dj + o_jobs + tiles_at);
-            if (t == &pg->planes) SQY_TIMED("batch_bitswap1_decode", sqy::launch_bitswap1_decode_batch(d_jobs, d_tiles, nj, t->ntiles, batch->elem_size, stream));
-            else SQY_TIMED("batch_copy", sqy::launch_batch_copy(d_jobs, d_tiles, nj, t->ntiles, stream));
-            at = align_up(tiles_at + ((uint64_t)nj + 1) * 4, 256);
+            std::memcpy(job_tables.data() + part[k].tiles_at, tt[k]->first_tile.data(), ((size_t)nj + 1) * 4);
+        }
+        const uint32_t nd = (uint32_t)df.jobs.size();
+        for (uint32_t j = 0; j < nd; ++j) {
+            const SlabBlob& s = blobs[df.jobs[j]];
+            const sqy::DecodeBatchBlob& p = (*batch->plan_in)[df.jobs[j]];
+            const sqy::DiffBatchJob job{out + df.res_at[j], s.call->d_dst, p.Z, p.Y, p.X, p.chain_columns};
+            std::memcpy(job_tables.data() + part[3].jobs_at + j * sizeof(job), &job, sizeof(job));
+        }
+        std::memcpy(job_tables.data() + part[3].tiles_at, df.first_strip.data(), ((size_t)nd + 1) * 4);
+        std::memcpy(job_tables.data() + part[3].extra_at, df.first_tile.data(), ((size_t)nd + 1) * 4);
+        uint8_t* dt = dj + o_jobs;
+        if (jobs_bytes) SQY_HIP(hipMemcpyAsync(dt, job_tables.data(), jobs_bytes, hipMemcpyHostToDevice, stream));
+        auto jobs_at = [&](int k) { return reinterpret_cast<const sqy::Bitswap1Job*>(dt + part[k].jobs_at); };
+        auto tiles_at = [&](int k) { return reinterpret_cast<const uint32_t*>(dt + part[k].tiles_at); };
+        if (pg->planes.ntiles)
+            SQY_TIMED("batch_bitswap1_decode", sqy::launch_bitswap1_decode_batch(jobs_at(0), tiles_at(0), (uint32_t)pg->planes.jobs.size(), pg->planes.ntiles, batch->elem_size, stream));
+        if (pg->plain.ntiles) SQY_TIMED("batch_copy", sqy::launch_batch_copy(jobs_at(1), tiles_at(1), (uint32_t)pg->plain.jobs.size(), pg->plain.ntiles, stream));
+        if (pg->quantised.ntiles)
+            SQY_TIMED("batch_quantiser_decode", sqy::launch_bitswap1_quantiser_decode_batch(jobs_at(2), tiles_at(2), reinterpret_cast<const uint16_t*>(dt + part[2].extra_at),
+                                                                                             (uint32_t)pg->quantised.jobs.size(), pg->quantised.ntiles, stream));
+        if (nd) {
+            // (every launch timed on its own: the profile counts the launches, 1 + steps whatever the number of blobs)
+            const sqy::DiffBatchJob* d_diff = reinterpret_cast<const sqy::DiffBatchJob*>(dt + part[3].jobs_at);
+            SQY_TIMED("batch_diff3x3x1_decode", sqy::launch_diff3x3x1_decode_batch_copy(d_diff, reinterpret_cast<const uint32_t*>(dt + part[3].extra_at), nd, df.ntiles, stream));
+            for (uint32_t step = 0; step < df.steps; ++step)
+                SQY_TIMED("batch_diff3x3x1_decode", sqy::launch_diff3x3x1_decode_batch_step(d_diff, tiles_at(3), nd, df.nstrips, step, df.max_columns, stream));
         }
     }
     for (size_t b : mem) {
@@ -2683,7 +2740,8 @@ int decode_slabs_from_host(const char* src, const long* offsets, const long* len
 // Independent blobs -- any shape, any pipeline, each destination an allocation of its own --, the way back from a batch encode.  The
 // joint-eligible ones (the last stage lz4, chunks of one LZ4 block; ONE chunk will do) go through decode_slab_group in the groups
 // sqy::decode_batch_plan deals them to: per group one frame ranking, one read-back of its counts, one joint index and LZ4 decode into the
-// workspace, one inverse-transpose launch for all `bitswap1->lz4` blobs, one copy launch for all `lz4` blobs, one verdict read-back.
+// workspace, one inverse-transpose launch for all `bitswap1->lz4` blobs, one copy launch for all `lz4` blobs, one launch with the look-up
+// for all `quantiser->bitswap1->lz4` blobs, one launch per chain step for all 16-bit diff3x3x1 blobs in the chain geometry, one verdict read-back.
 // Every other blob, and what a group hands back, goes through decode_on_device in blob order.
 struct BatchDecodeArgs { const long* offsets; const long* lengths; int nblobs; void* const* dsts; const long* capacities; long* decoded; };
 
@@ -2706,6 +2764,32 @@ bool batch_blob_fits(int i, uint64_t raw, const void* dst, long capacity, int el
     if (raw > (uint64_t)std::max(capacity, 0l)) { std::fprintf(stderr, "[sqeazy]\t decode batch: blob %d's %llu bytes do not fit its buffer\n", i, (unsigned long long)raw); return false; }
     if (reinterpret_cast<uintptr_t>(dst) % (uintptr_t)elem_size) { std::fprintf(stderr, "[sqeazy]\t decode batch: destination %d not aligned to the voxel size\n", i); return false; }
     return true;
+}
+
+// The joint forms behind a filter stage, of 16-bit blobs (p.form stays `stages` for everything else):
+//   quantiser->bitswap1->lz4: the LZ4 output is the 8-bit plane stream of the n quantised voxels; the decode table as the single call reads
+//   it (a table that cannot be had: `stages`, where that call says so)
+//   diff3x3x1->bitswap1->lz4, diff3x3x1->lz4: the geometry of launch_diff3x3x1_decode's chain of several frames per launch, a destination
+//   on the 16-byte grid
+void batch_stage_form(SlabBlob& b, const void* dst, int want_elem, sqy::DecodeBatchBlob& p)
+{
+    const DecodeCall& c = *b.call;
+    const std::vector<Stage>& st = c.pipe.stages;
+    if (want_elem != 2 || st.size() < 2 || st.size() > 3 || c.count_before[st.size() - 1] != c.n) return;
+    if (st.size() == 3 && st[1].kind != StageKind::bitswap1) return;
+    if (st[0].kind == StageKind::quantiser) {
+        if (st.size() != 3 || c.elem_before[0] != 2 || c.elem_before[1] != 1 || b.total != c.n || !quantiser_lut_on_host(st[0], &b.lut, false)) return;
+        p.form = sqy::DecodeBatchForm::quantised;
+        p.len = c.n;
+    } else if (st[0].kind == StageKind::diff3x3x1) {
+        if (c.elem_before[st.size() - 1] != 2 || b.total != b.raw || b.h.shape.size() != 3 || (reinterpret_cast<uintptr_t>(dst) & 15) != 0) return;
+        const uint64_t w = sqy::diff3x3x1_decode_chain_columns(b.h.shape[0], b.h.shape[1], b.h.shape[2], 2);
+        if (!w || !sqy::diff3x3x1_decode_frames_fit(w)) return;
+        p.form = st.size() == 3 ? sqy::DecodeBatchForm::diff_planes : sqy::DecodeBatchForm::diff_plain;
+        p.len = c.n;
+        p.Z = (uint32_t)b.h.shape[0]; p.Y = (uint32_t)b.h.shape[1]; p.X = (uint32_t)b.h.shape[2];
+        p.chain_columns = (uint32_t)w;
+    }
 }
 
 int decode_batch_on_device(Context& cx, const void* d_src_v, const BatchDecodeArgs& a, int want_elem, hipStream_t stream)
@@ -2741,7 +2825,8 @@ int decode_batch_on_device(Context& cx, const void* d_src_v, const BatchDecodeAr
         else if (st.size() == 2 && st[0].kind == StageKind::bitswap1 && c.elem_before[0] == want_elem && c.count_before[0] == c.n && b.total == b.raw) {
             p.form = sqy::DecodeBatchForm::planes;
             p.len = c.n;
-        }
+        } else
+            batch_stage_form(b, a.dsts[i], want_elem, p);
     }
     const uint64_t group_bytes = (uint64_t)g_opt.decode_batch_group_bytes.load();
     const sqy::DecodeBatchPlan plan = sqy::decode_batch_plan(plan_in, group_bytes);

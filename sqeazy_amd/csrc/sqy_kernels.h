@@ -311,6 +311,21 @@ hipError_t launch_bitswap1_decode_range(const uint8_t* in, void* out, const Bits
 hipError_t launch_bitswap1_decode_batch(const Bitswap1Job* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ntiles, int elem_size, hipStream_t stream);
 // plain copies on the same kind of table: job j's `len` BYTES from `in` to `out`, first_tile the prefix sums of batch_bitswap1_tiles(bytes)
 hipError_t launch_batch_copy(const Bitswap1Job* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ntiles, hipStream_t stream);
+// `quantiser->bitswap1->lz4` blobs on the same kind of table: job j's 8 planes + tail of `len` quantised voxels at `in` (16-byte aligned) become
+// `len` 16-bit voxels at `out` (any voxel-aligned address) through the decode table d_luts[256 j .. 256 j + 256)
+hipError_t launch_bitswap1_quantiser_decode_batch(const Bitswap1Job* d_jobs, const uint32_t* d_first_tile, const uint16_t* d_luts, uint32_t njobs, uint32_t ntiles,
+                                                  hipStream_t stream);
+// The diff3x3x1 inverses of many 16-bit volumes in the chain geometry (diff3x3x1_decode_chain_columns != 0, diff3x3x1_decode_frames_fit of
+// it): job j's residual volume of Z x Y x X voxels at `in`, the decoded one to `out` (both 16-byte aligned, apart), w its chain columns.
+// _copy: one launch for frame 0, the frames that cannot change and the columns right of the chain of all jobs (d_first_tile: the prefix sums
+// of batch_bitswap1_tiles(Z Y X)).  _step, behind it, for step = 0, 1, ..: one launch that decodes frames [1 + 8 step, 9 + 8 step) of every
+// job that has them, a workgroup per strip of 32 rows (d_first_strip: the prefix sums of ceil(Y / 32)); max_columns: the largest w of the
+// table.  (sqy::decode_batch_plan makes the tables and counts the steps)
+struct DiffBatchJob { const void* in; void* out; uint32_t Z, Y, X, w; };
+bool diff3x3x1_decode_frames_fit(uint64_t w);
+hipError_t launch_diff3x3x1_decode_batch_copy(const DiffBatchJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ntiles, hipStream_t stream);
+hipError_t launch_diff3x3x1_decode_batch_step(const DiffBatchJob* d_jobs, const uint32_t* d_first_strip, uint32_t njobs, uint32_t nstrips, uint32_t step,
+                                              uint32_t max_columns, hipStream_t stream);
 // one launch per frame over the columns the stage can touch (frame z needs the decoded frame z-1), the other columns one plain copy
 // -- on copy_stream next to the chain when that, fork and join are given.  (scratch: unused since round 3)
 // diff3x3x1_decode_chain_columns: how many leading columns of a row go through that chain in the usual 16-bit geometry (a multiple of 8;

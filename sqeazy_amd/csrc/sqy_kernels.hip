@@ -772,14 +772,13 @@ constexpr uint32_t DDK_K = 8, DDK_R = 32, DDK_ROWS = DDK_R + 2 * DDK_K;
 
 constexpr uint32_t DDK_THREADS = 1024, DDK_ITEMS = 2;          // an image is at most DDK_ITEMS * DDK_THREADS (row, vector) items (launcher)
 
-__global__ __launch_bounds__(DDK_THREADS)
-void diff3x3x1_u16_decode_frames_kernel(const uint16_t* __restrict__ in, uint16_t* __restrict__ out, uint32_t Y, uint32_t X, uint32_t hx,
-                                        uint32_t zlim, uint32_t w, uint32_t z0, uint32_t nframes)
+// (the strip whose first row is y0, by one workgroup: the kernel below, and the batch decode's, which finds its strip in a job table)
+__device__ __forceinline__ void diff3x3x1_u16_decode_strip(const uint16_t* __restrict__ in, uint16_t* __restrict__ out, uint32_t Y, uint32_t X, uint32_t hx,
+                                                           uint32_t zlim, uint32_t w, uint32_t z0, uint32_t nframes, const int32_t y0)
 {
     extern __shared__ __attribute__((aligned(16))) uint16_t ddk_lds[];   // 2 images of DDK_ROWS rows
     const uint32_t pitch = w + 16u;                            // voxels per LDS row: [8 .. 8 + w) = columns 0 .. w-1, [8 + w] = column w (16-byte aligned rows)
     uint16_t* img[2] = {ddk_lds, ddk_lds + (size_t)DDK_ROWS * pitch};
-    const int32_t y0 = (int32_t)(blockIdx.x * DDK_R);
     const uint64_t frame = (uint64_t)Y * X;
     const uint32_t vpr = w / 8u;                               // 8-voxel vectors per row; item vpr of a row is the single column w
     // A thread owns the same (image row, vector) items in every frame: image row i <-> volume row y0 - K + i.  The encoded voxels of
@@ -873,6 +872,65 @@ void diff3x3x1_u16_decode_frames_kernel(const uint16_t* __restrict__ in, uint16_
 #pragma unroll
         for (uint32_t k = 0; k < DDK_ITEMS; ++k) cin[k] = nin[k];
     }
+}
+
+__global__ __launch_bounds__(DDK_THREADS)
+void diff3x3x1_u16_decode_frames_kernel(const uint16_t* __restrict__ in, uint16_t* __restrict__ out, uint32_t Y, uint32_t X, uint32_t hx,
+                                        uint32_t zlim, uint32_t w, uint32_t z0, uint32_t nframes)
+{
+    diff3x3x1_u16_decode_strip(in, out, Y, X, hx, zlim, w, z0, nframes, (int32_t)(blockIdx.x * DDK_R));
+}
+
+// Batch decode (SQYAMD_Decode_Batch_*): the diff3x3x1 inverses of many 16-bit volumes in the chain geometry, driven by a job table.  Job j:
+// its residual volume at `in`, the decoded one to `out` (both 16-byte aligned), Z x Y x X voxels, w = diff3x3x1_decode_chain_columns.
+// Two kernels, no workgroup waits for another (see quantiser_decode_kernel):
+//   _copy_kernel: everything the chain does not produce -- frame 0, the frames z >= zlim that cannot change, columns [w, X) of the frames
+//   in between -- for ALL jobs in one launch; a workgroup is one tile of BSWB_TILE_VOX voxels of one job (first_tile), 16 bytes a thread
+//   and step.
+//   _kernel: step s of the chain, frames [1 + s K, 1 + (s + 1) K) of every job that has them, one launch: a workgroup finds its job and
+//   its strip of DDK_R rows by a binary search over first_strip and runs diff3x3x1_u16_decode_strip on it (a job whose chain is over: out).
+// The launcher sizes the LDS for the widest chain of the table.
+__device__ __forceinline__ uint32_t batch_job_of(const uint32_t* __restrict__ first, uint32_t njobs, uint32_t block)
+{
+    uint32_t lo = 0, hi = njobs;                                      // first[lo] <= block < first[hi]
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (first[mid] <= block) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(256)
+void diff3x3x1_decode_batch_copy_kernel(const DiffBatchJob* __restrict__ jobs, const uint32_t* __restrict__ first_tile, uint32_t njobs)
+{
+    const uint32_t j = batch_job_of(first_tile, njobs, blockIdx.x);
+    const DiffBatchJob job = jobs[j];
+    const uint32_t tile = blockIdx.x - first_tile[j];
+    const uint32_t vpr = job.X / 8u, wv = job.w / 8u, zlim = job.X < job.Z ? job.X : job.Z;          // 16-byte vectors per row, of the chain
+    const uint64_t fv = (uint64_t)job.Y * vpr, nvec = (uint64_t)job.Z * fv;
+    const uint4* __restrict__ in = static_cast<const uint4*>(job.in);
+    uint4* __restrict__ out = static_cast<uint4*>(job.out);
+#pragma unroll 4
+    for (uint32_t i = 0; i < BSWB_THREAD_VOX / 8u; ++i) {
+        const uint64_t v = (uint64_t)tile * (BSWB_TILE_VOX / 8u) + i * 256u + threadIdx.x;
+        if (v >= nvec) break;
+        const uint32_t z = (uint32_t)(v / fv), xv = (uint32_t)((v - (uint64_t)z * fv) % vpr);
+        if (z >= 1u && z < zlim && xv < wv) continue;                 // (the chain's)
+        out[v] = in[v];
+    }
+}
+
+__global__ __launch_bounds__(DDK_THREADS)
+void diff3x3x1_decode_batch_kernel(const DiffBatchJob* __restrict__ jobs, const uint32_t* __restrict__ first_strip, uint32_t njobs, uint32_t step)
+{
+    const uint32_t j = batch_job_of(first_strip, njobs, blockIdx.x);
+    const DiffBatchJob job = jobs[j];
+    const uint32_t strip = blockIdx.x - first_strip[j];
+    const uint32_t zlim = job.X < job.Z ? job.X : job.Z, z0 = 1u + step * DDK_K;
+    if (z0 >= zlim) return;                                           // (the whole workgroup: Z >= 2 below)
+    const uint32_t nframes = zlim - z0 < DDK_K ? zlim - z0 : DDK_K;
+    diff3x3x1_u16_decode_strip(static_cast<const uint16_t*>(job.in), static_cast<uint16_t*>(job.out), job.Y, job.X, job.Z - 2u, zlim, job.w, z0, nframes,
+                               (int32_t)(strip * DDK_R));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -6164,6 +6222,69 @@ void bitswap1_decode_batch_kernel(const Bitswap1Job* __restrict__ jobs, const ui
     }
 }
 
+// Batch decode, `quantiser->bitswap1->lz4` blobs: the 8-bit instantiation above with the quantiser's look-up put back (what
+// bitswap1_u8_decode_lut_kernel is to the single call).  Job j's 8 planes + tail of `len` quantised voxels at `in` become `len` 16-bit
+// voxels at `out` through its decode table luts[256 j .. 256 j + 256), which the workgroup stages in LDS first.  Sixteen-byte stores where
+// the job's pointers and plane size allow, word by word where not; the len % 8 voxels behind the planes are tile 0's.
+__global__ __launch_bounds__(256)
+void bitswap1_quantiser_decode_batch_kernel(const Bitswap1Job* __restrict__ jobs, const uint32_t* __restrict__ first_tile, const uint16_t* __restrict__ luts,
+                                            uint32_t njobs)
+{
+    __shared__ uint16_t sl[256];
+    const uint32_t j = batch_job_of(first_tile, njobs, blockIdx.x);
+    const uint32_t tid = threadIdx.x;
+    sl[tid] = luts[(size_t)j * 256u + tid];
+    __syncthreads();
+    const Bitswap1Job job = jobs[j];
+    const uint32_t tile = blockIdx.x - first_tile[j];
+    const uint64_t seg = job.len / 8u, L = seg * 8u;                  // bytes per plane; voxels in the planes
+    const uint8_t* __restrict__ in = static_cast<const uint8_t*>(job.in);
+    uint16_t* __restrict__ out = static_cast<uint16_t*>(job.out);
+    if (tile == 0 && tid < job.len - L) out[L + tid] = sl[in[L + tid]];          // tail voxels [L, len)
+    const uint64_t w0 = ((uint64_t)tile * 256u + tid) * (BSWB_THREAD_VOX / 8u);
+    if (w0 >= seg) return;
+    const bool wide = w0 + BSWB_THREAD_VOX / 8u <= seg && ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out) | seg) & 15u) == 0;
+    if (wide) {
+        uint32_t pw[8][4];                                            // pw[b] = 16 bytes of the plane that carries bit b
+#pragma unroll
+        for (int b = 0; b < 8; ++b) {
+            const uint4 t = *reinterpret_cast<const uint4*>(in + (uint64_t)(7 - b) * seg + w0);
+            pw[b][0] = t.x; pw[b][1] = t.y; pw[b][2] = t.z; pw[b][3] = t.w;
+        }
+        uint4* dst = reinterpret_cast<uint4*>(out + w0 * 8u);
+#pragma unroll
+        for (int g = 0; g < 16; ++g) {
+            // gathered and transposed as bitswap1_u8_decode_lut_kernel does it: afterwards byte i of hi:lo = voxel 7 - i of byte g
+            constexpr uint32_t Z = 0x0c;                              // v_perm selector: a zero byte
+            const uint32_t c = (uint32_t)(g & 3), wdx = (uint32_t)(g >> 2);
+            const uint32_t s01 = c | ((4u + c) << 8) | (Z << 16) | (Z << 24), s23 = Z | (Z << 8) | (c << 16) | ((4u + c) << 24);
+            uint32_t lo = __builtin_amdgcn_perm(pw[1][wdx], pw[0][wdx], s01) | __builtin_amdgcn_perm(pw[3][wdx], pw[2][wdx], s23);
+            uint32_t hi = __builtin_amdgcn_perm(pw[5][wdx], pw[4][wdx], s01) | __builtin_amdgcn_perm(pw[7][wdx], pw[6][wdx], s23);
+            uint32_t y;
+            y = (lo ^ (lo >> 7)) & 0x00AA00AAu; lo ^= y ^ (y << 7);
+            y = (hi ^ (hi >> 7)) & 0x00AA00AAu; hi ^= y ^ (y << 7);
+            y = (lo ^ (lo >> 14)) & 0x0000CCCCu; lo ^= y ^ (y << 14);
+            y = (hi ^ (hi >> 14)) & 0x0000CCCCu; hi ^= y ^ (y << 14);
+            y = (lo ^ (hi << 4)) & 0xF0F0F0F0u; lo ^= y; hi ^= y >> 4;
+            dst[g] = make_uint4((uint32_t)sl[hi >> 24] | ((uint32_t)sl[(hi >> 16) & 0xffu] << 16), (uint32_t)sl[(hi >> 8) & 0xffu] | ((uint32_t)sl[hi & 0xffu] << 16),
+                                (uint32_t)sl[lo >> 24] | ((uint32_t)sl[(lo >> 16) & 0xffu] << 16), (uint32_t)sl[(lo >> 8) & 0xffu] | ((uint32_t)sl[lo & 0xffu] << 16));
+        }
+    } else {
+        for (uint64_t w = w0; w < w0 + BSWB_THREAD_VOX / 8u && w < seg; ++w) {
+            uint32_t plane[8];
+#pragma unroll
+            for (uint32_t b = 0; b < 8; ++b) plane[b] = in[(uint64_t)(7 - b) * seg + w];
+#pragma unroll
+            for (uint32_t q = 0; q < 8; ++q) {
+                uint32_t v = 0;
+#pragma unroll
+                for (uint32_t b = 0; b < 8; ++b) v |= ((plane[b] >> (7 - q)) & 1u) << b;
+                out[w * 8 + q] = sl[v];
+            }
+        }
+    }
+}
+
 // Batch decode, plain `lz4` blobs: job j's `len` BYTES from `in` to `out`, on the tile table of the transposer (a tile = BSWB_TILE_VOX
 // bytes): sixteen bytes per thread and step where both pointers allow, byte by byte where not
 __global__ __launch_bounds__(256)
@@ -7521,6 +7642,38 @@ hipError_t launch_batch_copy(const Bitswap1Job* d_jobs, const uint32_t* d_first_
     return hipGetLastError();
 }
 
+hipError_t launch_bitswap1_quantiser_decode_batch(const Bitswap1Job* d_jobs, const uint32_t* d_first_tile, const uint16_t* d_luts, uint32_t njobs, uint32_t ntiles,
+                                                  hipStream_t stream)
+{
+    if (njobs == 0 || ntiles == 0) return hipSuccess;
+    hipLaunchKernelGGL(bitswap1_quantiser_decode_batch_kernel, dim3(ntiles), dim3(256), 0, stream, d_jobs, d_first_tile, d_luts, njobs);
+    return hipGetLastError();
+}
+
+// the two LDS images of `w` chain columns fit, and a workgroup's threads cover an image (diff3x3x1_u16_decode_strip)
+bool diff3x3x1_decode_frames_fit(uint64_t w)
+{
+    return 2 * (uint64_t)DDK_ROWS * (w + 16) * sizeof(uint16_t) <= (64u << 10) && (uint64_t)DDK_ROWS * (w / 8 + 1) <= (uint64_t)DDK_ITEMS * DDK_THREADS;
+}
+
+static_assert(DDK_R == kDiffStripRows && DDK_K == kDiffChainFrames, "the host-only planner counts strips and chain steps of this size");
+hipError_t launch_diff3x3x1_decode_batch_copy(const DiffBatchJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ntiles, hipStream_t stream)
+{
+    if (njobs == 0 || ntiles == 0) return hipSuccess;
+    hipLaunchKernelGGL(diff3x3x1_decode_batch_copy_kernel, dim3(ntiles), dim3(256), 0, stream, d_jobs, d_first_tile, njobs);
+    return hipGetLastError();
+}
+
+hipError_t launch_diff3x3x1_decode_batch_step(const DiffBatchJob* d_jobs, const uint32_t* d_first_strip, uint32_t njobs, uint32_t nstrips, uint32_t step,
+                                              uint32_t max_columns, hipStream_t stream)
+{
+    if (njobs == 0 || nstrips == 0) return hipSuccess;
+    if (!diff3x3x1_decode_frames_fit(max_columns)) return hipErrorInvalidValue;
+    const size_t lds = 2 * (size_t)DDK_ROWS * (max_columns + 16) * sizeof(uint16_t);
+    hipLaunchKernelGGL(diff3x3x1_decode_batch_kernel, dim3(nstrips), dim3(DDK_THREADS), lds, stream, d_jobs, d_first_strip, njobs, step);
+    return hipGetLastError();
+}
+
 // the usual geometry of the inverse (16-bit, every row's reach inside its row): the columns that go through the chain of launches --
 // the ones the stage can touch and their right-hand neighbour, whole 16-byte vectors; 0: another geometry
 uint64_t diff3x3x1_decode_chain_columns(uint64_t Z, uint64_t Y, uint64_t X, int elem_size)
@@ -7588,7 +7741,7 @@ hipError_t launch_diff3x3x1_decode(const void* in, void* out, uint64_t Z, uint64
         // frames 1 .. zlim-1: K frames per launch, strips of R rows that recompute the halo rows they need of their neighbours
         // (diff3x3x1_u16_decode_frames_kernel); narrow stripes of columns only -- the two LDS images must fit
         const size_t ddk_lds = 2 * (size_t)DDK_ROWS * (w + 16) * sizeof(uint16_t);
-        if (ddk_lds <= (64u << 10) && (uint64_t)DDK_ROWS * (w / 8 + 1) <= (uint64_t)DDK_ITEMS * DDK_THREADS) {
+        if (diff3x3x1_decode_frames_fit(w)) {
             for (uint64_t z = 1; z < zlim; z += DDK_K) {
                 const uint32_t nf = (uint32_t)(zlim - z < DDK_K ? zlim - z : DDK_K);
                 hipLaunchKernelGGL(diff3x3x1_u16_decode_frames_kernel, dim3((unsigned)((Y + DDK_R - 1) / DDK_R)), dim3(DDK_THREADS), ddk_lds, stream, (const uint16_t*)in,

@@ -328,14 +328,22 @@ DecodeBatchPlan decode_batch_plan(const std::vector<DecodeBatchBlob>& blobs, uin
     DecodeBatchPlan plan;
     plan.group_of.assign(blobs.size(), -1);
     auto tiles_of = [](uint64_t len) { return std::max<uint64_t>((len + kBatchTileVoxels - 1) / kBatchTileVoxels, 1); };
+    auto add_tiles = [](DecodeBatchTiles& t, size_t i, uint64_t tiles) {
+        t.jobs.push_back((uint32_t)i);
+        t.first_tile.push_back(t.ntiles);
+        t.ntiles += (uint32_t)tiles;
+    };
     uint64_t group_tiles = 0;
     for (size_t i = 0; i < blobs.size(); ++i) {
         const DecodeBatchBlob& b = blobs[i];
         if (!b.eligible || i > (size_t)UINT32_MAX) continue;
-        const uint64_t need = round_up(b.total, 256), tiles = tiles_of(b.len);
-        // (a launch's grid counts its tiles in 31 bits)
+        const bool diff = b.form == DecodeBatchForm::diff_planes || b.form == DecodeBatchForm::diff_plain;
+        const uint64_t lz4_out = round_up(b.total, 256), need = b.form == DecodeBatchForm::diff_planes ? 2 * lz4_out : lz4_out;
+        const uint64_t strips = diff ? ((uint64_t)b.Y + kDiffStripRows - 1) / kDiffStripRows : 0;
+        // (a launch's grid counts its tiles in 31 bits; a diff blob has tiles in up to two tables and its strips)
+        const uint64_t tiles = tiles_of(b.len), entries = diff ? 2 * tiles + strips : tiles;
         if (plan.groups.empty() || plan.groups.back().out_bytes + need > group_bytes || plan.groups.back().block_bytes != b.block_bytes ||
-            group_tiles + tiles > (uint64_t)INT32_MAX) {
+            group_tiles + entries > (uint64_t)INT32_MAX) {
             plan.groups.emplace_back();
             plan.groups.back().block_bytes = b.block_bytes;
             group_tiles = 0;
@@ -343,18 +351,33 @@ DecodeBatchPlan decode_batch_plan(const std::vector<DecodeBatchBlob>& blobs, uin
         DecodeBatchGroup& g = plan.groups.back();
         g.blobs.push_back((uint32_t)i);
         g.out_at.push_back(g.out_bytes);
+        const uint64_t at = g.out_bytes;
         g.out_bytes += need;
-        group_tiles += tiles;
+        group_tiles += entries;
         plan.group_of[i] = (int32_t)(plan.groups.size() - 1);
         if (b.form == DecodeBatchForm::stages || (dropped && i < dropped->size() && (*dropped)[i])) continue;
-        DecodeBatchTiles& t = b.form == DecodeBatchForm::planes ? g.planes : g.plain;
-        t.jobs.push_back((uint32_t)i);
-        t.first_tile.push_back(t.ntiles);
-        t.ntiles += (uint32_t)tiles;
+        if (!diff) {
+            add_tiles(b.form == DecodeBatchForm::planes ? g.planes : b.form == DecodeBatchForm::quantised ? g.quantised : g.plain, i, tiles);
+            continue;
+        }
+        if (b.form == DecodeBatchForm::diff_planes) add_tiles(g.planes, i, tiles);
+        DecodeBatchDiff& d = g.diff;
+        d.jobs.push_back((uint32_t)i);
+        d.res_at.push_back(b.form == DecodeBatchForm::diff_planes ? at + lz4_out : at);
+        d.first_strip.push_back(d.nstrips);
+        d.nstrips += (uint32_t)strips;
+        d.first_tile.push_back(d.ntiles);
+        d.ntiles += (uint32_t)tiles;
+        const uint64_t zlim = std::min<uint64_t>(b.X, b.Z);                 // frames 1 .. zlim - 1 go through the chain
+        if (zlim > 1) d.steps = std::max(d.steps, (uint32_t)((zlim - 1 + kDiffChainFrames - 1) / kDiffChainFrames));
+        d.max_columns = std::max(d.max_columns, b.chain_columns);
     }
     for (DecodeBatchGroup& g : plan.groups) {
         g.planes.first_tile.push_back(g.planes.ntiles);
         g.plain.first_tile.push_back(g.plain.ntiles);
+        g.quantised.first_tile.push_back(g.quantised.ntiles);
+        g.diff.first_strip.push_back(g.diff.nstrips);
+        g.diff.first_tile.push_back(g.diff.ntiles);
     }
     return plan;
 }

@@ -110,28 +110,50 @@ Lz4BatchPlan lz4_batch_plan(const Lz4Params& p, const std::vector<uint64_t>& tot
 // What the planner knows of blob i: the bytes its LZ4 stage decodes to, the LZ4 block size, whether it may take the joint path at all
 // (the last stage lz4, chunk <= block_bytes), and what follows the LZ4 decode --
 //   stages: its remaining inverses, blob by blob | planes: `bitswap1->lz4`, one job of the batched inverse transposer (len voxels) |
-//   plain: `lz4`, one job of the batched copy (len = total bytes)
-enum class DecodeBatchForm : uint8_t { stages, planes, plain };
-struct DecodeBatchBlob { uint64_t total = 0, block_bytes = 0, len = 0; bool eligible = false; DecodeBatchForm form = DecodeBatchForm::stages; };
+//   plain: `lz4`, one job of the batched copy (len = total bytes) |
+//   quantised: `quantiser->bitswap1->lz4`, one job of the batched inverse transposer with the look-up (len voxels, total = len bytes) |
+//   diff_planes, diff_plain: `diff3x3x1->bitswap1->lz4`, `diff3x3x1->lz4` of 16-bit voxels in the chain geometry (Z x Y x X = len voxels,
+//   chain_columns of a row through the chain): one job of the batched diff inverse; diff_planes: one of the inverse transposer in front
+enum class DecodeBatchForm : uint8_t { stages, planes, plain, quantised, diff_planes, diff_plain };
+struct DecodeBatchBlob {
+    uint64_t total = 0, block_bytes = 0, len = 0;
+    bool eligible = false;
+    DecodeBatchForm form = DecodeBatchForm::stages;
+    uint32_t Z = 0, Y = 0, X = 0, chain_columns = 0;    // the diff forms only
+};
 constexpr uint64_t kBatchTileVoxels = 256 * 128;        // a workgroup of the batched transposers and of the batched copy: 256 threads x 128 voxels
+// the batched diff inverse: a workgroup decodes up to kDiffChainFrames frames of a strip of kDiffStripRows rows (the kernels' DDK_K, DDK_R)
+constexpr uint32_t kDiffStripRows = 32, kDiffChainFrames = 8;
 // A launch's job list and tile table: jobs[j] is a blob, its tiles are [first_tile[j], first_tile[j + 1]) (max(1, ceil(len / tile)) each)
 struct DecodeBatchTiles { std::vector<uint32_t> jobs, first_tile; uint32_t ntiles = 0; };
+// The diff blobs of a group (both forms).  Job j's residual volume lies at res_at[j] of the workspace: its LZ4 output (diff_plain), or a
+// region of its own behind that, where the inverse transposer puts it (diff_planes).  The chain launches: job j's strips are
+// [first_strip[j], first_strip[j + 1]) (ceil(Y / kDiffStripRows) each), step s covers frames [1 + s K, 1 + (s + 1) K) of every job that
+// has them (frames 1 .. min(X, Z) - 1 go through the chain), `steps` of them.  The launch for everything else -- frame 0, the frames that
+// cannot change, the columns right of the chain -- has tiles of kBatchTileVoxels voxels: first_tile.  max_columns: the widest chain.
+struct DecodeBatchDiff {
+    std::vector<uint32_t> jobs, first_strip, first_tile;
+    std::vector<uint64_t> res_at;
+    uint32_t nstrips = 0, ntiles = 0, steps = 0, max_columns = 0;
+};
 // The blobs that share one launch of every kernel: blob blobs[j]'s LZ4 output lies at out_at[j] of the group's workspace (256-byte
-// aligned, out_bytes in all); planes / plain: the tables of the two batched launches behind the LZ4 decode
+// aligned, out_bytes in all -- a diff_planes blob's residual volume behind its LZ4 output included); planes (the planes blobs, and the
+// diff_planes ones, whose voxels go to the workspace), plain, quantised: the tables of the batched launches behind the LZ4 decode; diff
 struct DecodeBatchGroup {
     std::vector<uint32_t> blobs;                // ascending
     std::vector<uint64_t> out_at;
     uint64_t out_bytes = 0, block_bytes = 0;
-    DecodeBatchTiles planes, plain;
+    DecodeBatchTiles planes, plain, quantised;
+    DecodeBatchDiff diff;
 };
 struct DecodeBatchPlan {
     std::vector<int32_t> group_of;              // per blob: its group, -1: not joint-eligible (the single-call path takes it)
     std::vector<DecodeBatchGroup> groups;
 };
-// Eligible blobs are dealt to groups in order; a group is closed when the next blob would take its LZ4 output (every blob's rounded up
-// to 256 bytes) past group_bytes or has another block size.  A group holds at least one blob, so a blob larger than the bound gets a
-// group of its own.  dropped (optional, one flag per blob): blobs the frame ranking refused -- they keep their place in the group and
-// in the workspace but get no job in the tile tables.
+// Eligible blobs are dealt to groups in order; a group is closed when the next blob would take its workspace (every blob's LZ4 output
+// rounded up to 256 bytes, as much again for a diff_planes blob) past group_bytes or has another block size.  A group holds at least one
+// blob, so a blob larger than the bound gets a group of its own.  dropped (optional, one flag per blob): blobs the frame ranking refused
+// -- they keep their place in the group and in the workspace but get no job in any table.
 DecodeBatchPlan decode_batch_plan(const std::vector<DecodeBatchBlob>& blobs, uint64_t group_bytes, const std::vector<uint8_t>* dropped = nullptr);
 
 // Frames in place: a 16-bit bitswap1 in front of lz4 writes chunk k of the plane stream into the destination at body0 + k * in_stride,

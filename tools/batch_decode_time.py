@@ -8,8 +8,10 @@ whose offsets and lengths are passed straight through:
   batch0   -- SQYAMD_Decode_Batch_UI16_Device with decode_batch_joint = 0 (every blob on its own inside the call)
   batch    -- .. as it comes
 Configurations (those of tools/batch_encode_time.py): a = 64 x 16x512x512 bitswap1->lz4, b = 256 x 16x128x128 bitswap1->lz4,
-c = 256 x 16x128x128 lz4, d = 8 x 64x1024x1024 bitswap1->lz4.  Every column's volumes are checked against the source.  One JSON line per
-configuration, then the kernels of one profiled `batch` call (SQYAMD_Profile_Get) on a line of their own."""
+c = 256 x 16x128x128 lz4, d = 8 x 64x1024x1024 bitswap1->lz4; the two BASELINE pipelines whose inverses behind the LZ4 decode are joint as
+well: e = 256 x 16x128x128 and g = 64 x 16x512x512 diff3x3x1->bitswap1->lz4, f = 256 x 16x128x128 and h = 64 x 16x512x512
+quantiser->bitswap1->lz4.  Every column's volumes are checked against the source (the lossy quantiser: against the `loop` column's).  One JSON
+line per configuration, then the kernels of one profiled `batch` call (SQYAMD_Profile_Get) on a line of their own."""
 import json
 import os
 import sys
@@ -23,7 +25,9 @@ from sqeazy_amd import synth  # noqa: E402
 
 K = int(sys.argv[1]) if len(sys.argv) > 1 else 5
 CONFIGS = {"a": ("bitswap1->lz4", (16, 512, 512), 64), "b": ("bitswap1->lz4", (16, 128, 128), 256), "c": ("lz4", (16, 128, 128), 256),
-           "d": ("bitswap1->lz4", (64, 1024, 1024), 8)}
+           "d": ("bitswap1->lz4", (64, 1024, 1024), 8),
+           "e": ("diff3x3x1->bitswap1->lz4", (16, 128, 128), 256), "f": ("quantiser->bitswap1->lz4", (16, 128, 128), 256),
+           "g": ("diff3x3x1->bitswap1->lz4", (16, 512, 512), 64), "h": ("quantiser->bitswap1->lz4", (16, 512, 512), 64)}
 WANT = sys.argv[2:] or sorted(CONFIGS)
 COLUMNS = ("loop", "slabs", "batch0", "batch")
 
@@ -70,6 +74,7 @@ def run(name, pipeline, shape, n, dev, stream):
 
     fns = {"loop": loop, "slabs": slabs, "batch0": batch0, "batch": batch}
     flat = vol.reshape(n, -1)
+    lossy = "quantiser" in pipeline
     for c in COLUMNS:                                                   # warm-up, and every column's volumes against the source
         joined.fill_(0)
         for t in apart:
@@ -77,6 +82,8 @@ def run(name, pipeline, shape, n, dev, stream):
         fns[c]()
         torch.cuda.synchronize()
         got = joined.reshape(n, -1) if c in ("loop", "slabs") else torch.stack(apart)
+        if lossy and c == "loop":
+            flat = got.clone()                                          # (what the single call makes of every blob)
         assert torch.equal(got, flat), (name, c)
     ms = {c: [] for c in COLUMNS}
     for _ in range(K):
