@@ -168,11 +168,14 @@ SQY_FUNCTION_PREFIX int SQYAMD_PipelineEncode_Slabs_UI8_Device(const char* pipel
  * shape_size longs, row i = volume i's {z,y,x}.  Blob i is written inside d_dst[i*slot_capacity, (i+1)*slot_capacity) and nothing
  * outside a volume's own slot is written; offsets[i] = its start relative to d_dst, lengths[i] = its bytes (host arrays, as for
  * _Slabs_*_Device).  Blob i is byte for byte what SQYAMD_PipelineEncode_*_Device gives for volume i with the same pipeline and nthreads.
- * Volumes of `lz4` and `bitswap1->lz4` in the chunked layout (nthreads != 1 or a single chunk) with liblz4's acceleration 1 and at most
- * "encode_batch_joint_max_bytes" of LZ4 input are encoded in groups ("encode_batch_group_bytes" of LZ4 input each, at least one volume):
+ * Volumes of `lz4`, `bitswap1->lz4` and -- 16-bit voxels, the quantiser with its default weighting (no weighting_function) and its decode
+ * LUT in the header (no decode_lut_path) -- `quantiser->bitswap1->lz4` in the chunked layout (nthreads != 1 or a single chunk) with
+ * liblz4's acceleration 1 and at most "encode_batch_joint_max_bytes" of LZ4 input (a byte per voxel behind the quantiser) are encoded in
+ * groups ("encode_batch_group_bytes" of LZ4 input each -- a quantised volume also counts its tables, 320.5 KiB --, at least one volume):
  * per group one launch of every kernel for all its volumes and two host round trips, whatever their number; their blobs start at the
- * slot's first byte.  Every other volume (other pipelines, the serial or block-linked layout, accel < 0, larger volumes) is encoded as by
- * _DeviceAt into its slot, in volume order on the same stream; a batch may mix both kinds.
+ * slot's first byte.  The quantiser's histograms and look-up tables are made on the GPU for the whole group; the tables are exactly the
+ * single call's.  Every other volume (other pipelines, other weightings, a LUT file, the serial or block-linked layout, accel < 0, larger
+ * volumes) is encoded as by _DeviceAt into its slot, in volume order on the same stream; a batch may mix both kinds.
  * Stream, context, ordering and thread-safety rules are those of SQYAMD_PipelineEncode_*_Device: the work runs behind what is queued
  * on hip_stream and is complete on return; several host threads may call at once.
  * Returns 0 or 1.  Bad arguments -- a NULL pointer (also in d_srcs), nvolumes <= 0, shape_size 0, slot_capacity <= 0, a non-positive

@@ -311,6 +311,7 @@ struct Workspace {
     DevBuf batch_stream;      // batch encode: the LZ4 input of a group's volumes (the bit planes), one stream behind the other
     DevBuf batch_scratch;     // .. a slot of compressed output per entry of the group's joint chunk table
     DevBuf batch_tables;      // .. the tables a group uploads (chunks, volumes, transposer jobs, header text) and what the kernels hand each other
+    DevBuf batch_quant;       // .. quantiser->bitswap1->lz4: every volume's histogram, then every encode LUT, then every decode LUT
     HostBuf batch_host;       // .. the records of every volume, the staging area of the upload
     void* pinned = nullptr;   // 4 KiB of pinned host memory for small read-backs
     void release_buffers()
@@ -318,7 +319,7 @@ struct Workspace {
         ping.release(); pong.release(); lz4_scratch.release(); csize.release(); frame_off.release();
         io_src.release(); io_dst.release(); small.release(); plan.release(); dedupe.release(); diff_side.release(); spec.release(); digest.release(); bkrd.release();
         subset.release(); range_full.release(); slabs_index.release(); slabs_joint.release(); slabs_out.release(); slabs_host.release();
-        batch_stream.release(); batch_scratch.release(); batch_tables.release(); batch_host.release();
+        batch_stream.release(); batch_scratch.release(); batch_tables.release(); batch_quant.release(); batch_host.release();
     }
 };
 
@@ -2908,9 +2909,11 @@ int encode_device(const char* pipeline, const void* d_src, const long* shape, un
 }
 
 // ---- batch encode (SQYAMD_PipelineEncode_Batch_*) -------------------------------------------------
-// Many volumes, one blob each, blob i inside slot i of d_dst.  The volumes lz4_batch_plan calls joint-eligible (pipelines lz4 and
-// bitswap1->lz4, the chunked layout, acceleration 1) go through the kernels group by group -- one launch per kernel for all volumes of a
-// group, two host round trips per group (the dense pass's count, the records) --, every other volume through encode_on_device.
+// Many volumes, one blob each, blob i inside slot i of d_dst.  The volumes the planner calls joint-eligible (sqy::encode_batch_form: the
+// pipelines lz4, bitswap1->lz4 and quantiser->bitswap1->lz4 with the default weighting and the LUT in the header; sqy::lz4_batch_plan:
+// the chunked layout, acceleration 1) go through the kernels group by group -- one launch per kernel for all volumes of a group, two
+// host round trips per group (the dense pass's count and, quantised, the decode LUTs for the headers; the records) --, every other
+// volume through encode_on_device.
 static_assert(sizeof(sqy::Lz4BatchChunkPlan) == sizeof(sqy::Lz4BatchChunk) && sizeof(sqy::Lz4BatchChunk) == 24, "the joint chunk table's layout");
 
 // What a batch call checks before it touches the device or writes anything: every argument, the pipeline once, every volume's shape
@@ -2936,32 +2939,44 @@ int admit_batch(const char* pipeline, const void* const* srcs, const long* shape
 }
 
 // one group of the plan through the kernels; rc 1 with a message when a blob does not fit its slot (nothing of that volume is written)
-int encode_batch_group(Context& cx, const BatchAdmit& a, const sqy::Lz4BatchGroup& g, bool transpose, int elem_size, const void* const* d_srcs,
+constexpr uint64_t kBatchHeaderTextMax = 4000;      // prefix + suffix of one volume's header (the staging area's share: 4096 bytes a volume)
+
+int encode_batch_group(Context& cx, const BatchAdmit& a, const sqy::Lz4BatchGroup& g, sqy::EncodeBatchForm form, int elem_size, const void* const* d_srcs,
                        uint8_t* d_dst, uint64_t slot_capacity, long* offsets, long* lengths, uint64_t* records, uint8_t* staging, hipStream_t stream)
 {
     Workspace* ws = &cx.ws;
     std::vector<PendingEvent>* pend = &cx.pending;
     const size_t nv = g.vols.size(), nc = g.chunks.size();
-    const std::string pipename = a.pipe.name();
-    // the upload, one copy: chunk table | volume of every entry | volumes | transposer jobs | their tile prefix | header text
+    const bool quantised = form == sqy::EncodeBatchForm::quantiser_bitswap1_lz4, transpose = quantised || form == sqy::EncodeBatchForm::bitswap1_lz4;
+    // the upload: chunk table | volume of every entry | transposer jobs | their tile prefix -- and, in a copy of their own behind round
+    // trip 1 when the header text is known only then (quantised: every volume's name carries its decode LUT) -- | volumes | header text
     auto up16 = [](uint64_t v) { return (v + 15) & ~(uint64_t)15; };
     std::vector<std::string> text(nv);
     uint64_t text_bytes = 0;
-    for (size_t j = 0; j < nv; ++j) {
+    auto pack_text = [&](size_t j, const std::string& pipename) {
         std::string prefix, suffix;
         sqy::header_pack_parts(elem_size, false, a.dims[g.vols[j]], pipename, &prefix, &suffix);
-        if (prefix.size() + suffix.size() > 4000) { std::fprintf(stderr, "[sqeazy]\t header text too long for the batch path\n"); return 1; }     // (the staging area's share)
+        if (prefix.size() + suffix.size() > kBatchHeaderTextMax) {
+            std::fprintf(stderr, "[sqeazy]\t volume %u: header text too long for the batch path\n", g.vols[j]);
+            return 1;
+        }
         text[j] = prefix + '\0' + suffix;                // (split again below: the prefix holds no NUL)
         text_bytes += prefix.size() + suffix.size();
+        return 0;
+    };
+    if (!quantised) {
+        const std::string pipename = a.pipe.name();
+        for (size_t j = 0; j < nv; ++j) if (pack_text(j, pipename)) return 1;
     }
-    const uint64_t table_at = 0, volof_at = up16(table_at + nc * sizeof(sqy::Lz4BatchChunk)), vols_at = up16(volof_at + nc * 4),
-                   jobs_at = up16(vols_at + nv * sizeof(sqy::Lz4BatchVolume)), tiles_at = up16(jobs_at + nv * sizeof(sqy::Bitswap1Job)),
-                   text_at = up16(tiles_at + (nv + 1) * 4), upload = up16(text_at + text_bytes);
+    const uint64_t table_at = 0, volof_at = up16(table_at + nc * sizeof(sqy::Lz4BatchChunk)), jobs_at = up16(volof_at + nc * 4),
+                   tiles_at = up16(jobs_at + nv * sizeof(sqy::Bitswap1Job)), vols_at = up16(tiles_at + (nv + 1) * 4),
+                   text_at = up16(vols_at + nv * sizeof(sqy::Lz4BatchVolume)), upload = up16(text_at + (quantised ? nv * kBatchHeaderTextMax : text_bytes));
     // .. and what the kernels hand each other: csize | redo list | frame offsets | per volume: payload bytes, header bytes and verdict
     const uint64_t csize_at = upload, redo_at = up16(csize_at + nc * 4), foff_at = up16(redo_at + (nc + 1) * 4), vinfo_at = up16(foff_at + nc * 8),
                    tables = vinfo_at + nv * 16;
     if (ws->batch_tables.ensure(tables) || ws->batch_scratch.ensure(std::max<uint64_t>(nc * g.scratch_stride, 16))) return 1;
     if (transpose && ws->batch_stream.ensure(std::max<uint64_t>(g.stream_bytes, 16))) return 1;
+    if (quantised && ws->batch_quant.ensure(nv * sqy::kQuantiserBatchTableBytes)) return 1;
     uint8_t* const d_tab = static_cast<uint8_t*>(ws->batch_tables.p);
     uint8_t* const d_stream = transpose ? static_cast<uint8_t*>(ws->batch_stream.p) : nullptr;
 
@@ -2973,15 +2988,22 @@ int encode_batch_group(Context& cx, const BatchAdmit& a, const sqy::Lz4BatchGrou
     char* h_text = reinterpret_cast<char*>(staging + text_at);
     uint64_t text_used = 0;
     uint32_t ntiles = 0;
+    // the volume table and the header text, once every volume's text is there
+    auto fill_volumes = [&]() {
+        for (size_t j = 0; j < nv; ++j) {
+            const uint32_t vol = g.vols[j];
+            const size_t cut = text[j].find('\0');
+            const uint32_t prefix_len = (uint32_t)cut, suffix_len = (uint32_t)(text[j].size() - cut - 1);
+            std::memcpy(h_text + text_used, text[j].data(), prefix_len);
+            std::memcpy(h_text + text_used + prefix_len, text[j].data() + cut + 1, suffix_len);
+            h_vols[j] = sqy::Lz4BatchVolume{(uint64_t)vol * slot_capacity, slot_capacity, g.first_chunk[j], g.first_chunk[j + 1] - g.first_chunk[j],
+                                            (uint32_t)text_used, prefix_len, suffix_len, (uint32_t)elem_size, vol, 0};
+            text_used += prefix_len + suffix_len;
+        }
+    };
+    if (!quantised) fill_volumes();
     for (size_t j = 0; j < nv; ++j) {
         const uint32_t vol = g.vols[j];
-        const size_t cut = text[j].find('\0');
-        const uint32_t prefix_len = (uint32_t)cut, suffix_len = (uint32_t)(text[j].size() - cut - 1);
-        std::memcpy(h_text + text_used, text[j].data(), prefix_len);
-        std::memcpy(h_text + text_used + prefix_len, text[j].data() + cut + 1, suffix_len);
-        h_vols[j] = sqy::Lz4BatchVolume{(uint64_t)vol * slot_capacity, slot_capacity, g.first_chunk[j], g.first_chunk[j + 1] - g.first_chunk[j],
-                                        (uint32_t)text_used, prefix_len, suffix_len, (uint32_t)elem_size, vol, 0};
-        text_used += prefix_len + suffix_len;
         h_jobs[j] = sqy::Bitswap1Job{d_srcs[vol], d_stream ? d_stream + g.stream_at[j] : nullptr, a.len[vol]};
         h_tiles[j] = ntiles;
         ntiles += sqy::batch_bitswap1_tiles(a.len[vol]);
@@ -2994,7 +3016,7 @@ int encode_batch_group(Context& cx, const BatchAdmit& a, const sqy::Lz4BatchGrou
         }
     }
     h_tiles[nv] = ntiles;
-    SQY_HIP(hipMemcpyAsync(d_tab, staging, upload, hipMemcpyHostToDevice, stream));
+    SQY_HIP(hipMemcpyAsync(d_tab, staging, quantised ? vols_at : up16(text_at + text_bytes), hipMemcpyHostToDevice, stream));
 
     const sqy::Lz4BatchChunk* d_table = reinterpret_cast<const sqy::Lz4BatchChunk*>(d_tab + table_at);
     const sqy::Lz4BatchVolume* d_vols = reinterpret_cast<const sqy::Lz4BatchVolume*>(d_tab + vols_at);
@@ -3003,14 +3025,35 @@ int encode_batch_group(Context& cx, const BatchAdmit& a, const sqy::Lz4BatchGrou
     uint64_t* d_foff = reinterpret_cast<uint64_t*>(d_tab + foff_at);
     uint64_t* d_vinfo = reinterpret_cast<uint64_t*>(d_tab + vinfo_at);
     uint8_t* d_scratch = static_cast<uint8_t*>(ws->batch_scratch.p);
-    if (transpose)
-        SQY_TIMED("batch_bitswap1", sqy::launch_bitswap1_batch(reinterpret_cast<const sqy::Bitswap1Job*>(d_tab + jobs_at),
-                                                               reinterpret_cast<const uint32_t*>(d_tab + tiles_at), (uint32_t)nv, ntiles, elem_size, stream));
+    const sqy::Bitswap1Job* d_jobs = reinterpret_cast<const sqy::Bitswap1Job*>(d_tab + jobs_at);
+    const uint32_t* d_tiles = reinterpret_cast<const uint32_t*>(d_tab + tiles_at);
+    // (quantised) the group's histograms | encode LUTs | decode LUTs, volume j's at index j of each
+    uint32_t* const d_histos = static_cast<uint32_t*>(ws->batch_quant.p);
+    uint8_t* const d_luts = quantised ? static_cast<uint8_t*>(ws->batch_quant.p) + nv * sqy::kQuantiserBatchHistoBytes : nullptr;
+    uint16_t* const d_decode = quantised ? reinterpret_cast<uint16_t*>(d_luts + nv * sqy::kQuantiserBatchLutBytes) : nullptr;
+    uint16_t* const h_decode = reinterpret_cast<uint16_t*>(staging + upload);          // (pinned, behind the staging area of the upload)
+    if (quantised) {
+        SQY_TIMED("batch_quantiser_histogram", sqy::launch_batch_quantiser_histogram(d_jobs, d_tiles, (uint32_t)nv, ntiles, d_histos, stream));
+        SQY_TIMED("batch_quantiser_lut", sqy::launch_batch_quantiser_lut(d_histos, (uint32_t)nv, d_luts, d_decode, stream));
+        SQY_TIMED("batch_quantiser_bitswap1", sqy::launch_batch_quantiser_bitswap1(d_jobs, d_tiles, (uint32_t)nv, ntiles, d_luts, stream));
+    } else if (transpose)
+        SQY_TIMED("batch_bitswap1", sqy::launch_bitswap1_batch(d_jobs, d_tiles, (uint32_t)nv, ntiles, elem_size, stream));
     SQY_TIMED("batch_lz4_chunks", sqy::launch_lz4_chunks_table(d_stream, d_table, (uint32_t)nc, d_scratch, g.scratch_stride, d_csize, d_redo, stream));
-    // round trip 1: how many entries the first pass left to the dense batches
+    // round trip 1: how many entries the first pass left to the dense batches -- and, quantised, the decode LUTs the headers carry
+    if (quantised) SQY_HIP(hipMemcpyAsync(h_decode, d_decode, nv * sqy::kQuantiserBatchDecodeBytes, hipMemcpyDeviceToHost, stream));
     SQY_HIP(hipMemcpyAsync(ws->pinned, d_redo, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
     SQY_HIP(hipStreamSynchronize(stream));
     const uint32_t n_redo = *static_cast<uint32_t*>(ws->pinned);
+    if (quantised) {
+        // every volume's own pipeline name (quantiser_scheme_impl.hpp:200-204: the decode LUT goes into the header), its header text, the upload
+        Pipeline named = a.pipe;
+        for (size_t j = 0; j < nv; ++j) {
+            named.stages[0].cfg["decode_lut_string"] = sqy::to_verbatim(h_decode + j * 256, sqy::kQuantiserBatchDecodeBytes);
+            if (pack_text(j, named.name())) return 1;
+        }
+        fill_volumes();
+        SQY_HIP(hipMemcpyAsync(d_tab + vols_at, staging + vols_at, up16(text_at + text_bytes) - vols_at, hipMemcpyHostToDevice, stream));
+    }
     if (n_redo)
         SQY_TIMED("batch_lz4_chunks_dense", sqy::launch_lz4_chunks_table_dense(d_stream, d_table, d_scratch, g.scratch_stride, d_csize, d_redo, n_redo, stream));
     SQY_TIMED("batch_lz4_frame_scan", sqy::launch_lz4_batch_scan(d_table, d_vols, (uint32_t)nv, d_csize, d_foff, d_vinfo, stream));
@@ -3042,16 +3085,14 @@ int encode_batch_on_device(Context& cx, const char* pipeline, const BatchAdmit& 
 {
     for (int i = 0; i < nvolumes; ++i)
         if (reinterpret_cast<uintptr_t>(d_srcs[i]) % (uintptr_t)elem_size) { std::fprintf(stderr, "[sqeazy]\t volume %d: source not aligned to the voxel size\n", i); return 1; }
-    const std::vector<Stage>& st = a.pipe.stages;
-    const bool transpose = st.size() == 2 && st[0].kind == StageKind::bitswap1 && st[1].kind == StageKind::lz4;
-    const bool joint_pipeline = transpose || (st.size() == 1 && st[0].kind == StageKind::lz4);
+    const sqy::EncodeBatchForm form = g_opt.encode_batch_joint.load() ? sqy::encode_batch_form(a.pipe, elem_size) : sqy::EncodeBatchForm::none;
     sqy::Lz4BatchPlan plan;
     plan.group_of.assign((size_t)nvolumes, -1);
-    if (joint_pipeline && g_opt.encode_batch_joint.load()) {
+    if (form != sqy::EncodeBatchForm::none) {
         std::vector<uint64_t> totals((size_t)nvolumes);
-        for (int i = 0; i < nvolumes; ++i) totals[(size_t)i] = a.len[(size_t)i] * (uint64_t)elem_size;
-        plan = sqy::lz4_batch_plan(st.back().lz4, totals, a.pipe.nthreads, (uint64_t)g_opt.encode_batch_group_bytes.load(),
-                                   (uint64_t)g_opt.encode_batch_joint_max_bytes.load());
+        for (int i = 0; i < nvolumes; ++i) totals[(size_t)i] = sqy::encode_batch_stream_bytes(form, a.len[(size_t)i], elem_size);
+        plan = sqy::lz4_batch_plan(a.pipe.stages.back().lz4, totals, a.pipe.nthreads, (uint64_t)g_opt.encode_batch_group_bytes.load(),
+                                   (uint64_t)g_opt.encode_batch_joint_max_bytes.load(), sqy::encode_batch_extra_bytes(form));
     }
     int rc = 0;
     if (!plan.groups.empty()) {
@@ -3059,13 +3100,13 @@ int encode_batch_on_device(Context& cx, const char* pipeline, const BatchAdmit& 
         // pinned: a record per volume of the batch (3 words), behind them the staging area of the largest group's upload
         uint64_t staging = 0;
         for (const sqy::Lz4BatchGroup& g : plan.groups)
-            staging = std::max<uint64_t>(staging, g.chunks.size() * (sizeof(sqy::Lz4BatchChunk) + 4) + g.vols.size() * (sizeof(sqy::Lz4BatchVolume) + sizeof(sqy::Bitswap1Job) + 4 + 4096) + 256);
+            staging = std::max<uint64_t>(staging, g.chunks.size() * (sizeof(sqy::Lz4BatchChunk) + 4) + g.vols.size() * (sizeof(sqy::Lz4BatchVolume) + sizeof(sqy::Bitswap1Job) + 4 + 4096 + sqy::kQuantiserBatchDecodeBytes) + 256);
         const uint64_t records_bytes = ((uint64_t)nvolumes * 24 + 63) & ~(uint64_t)63;
         if (cx.ws.batch_host.ensure(records_bytes + staging)) return 1;
         uint64_t* records = static_cast<uint64_t*>(cx.ws.batch_host.p);
         std::memset(records, 0, records_bytes);
         for (const sqy::Lz4BatchGroup& g : plan.groups)
-            if (encode_batch_group(cx, a, g, transpose, elem_size, d_srcs, static_cast<uint8_t*>(d_dst), slot_capacity, offsets, lengths, records,
+            if (encode_batch_group(cx, a, g, form, elem_size, d_srcs, static_cast<uint8_t*>(d_dst), slot_capacity, offsets, lengths, records,
                                    static_cast<uint8_t*>(cx.ws.batch_host.p) + records_bytes, stream))
                 rc = 1;
         if (g_prof_on.load()) prof_collect(cx.pending);

@@ -164,6 +164,15 @@ hipError_t launch_lz4_frame_gather(const uint8_t* in, uint64_t total, uint32_t c
 struct Bitswap1Job { const void* in; void* out; uint64_t len; };
 uint32_t batch_bitswap1_tiles(uint64_t len);
 hipError_t launch_bitswap1_batch(const Bitswap1Job* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ntiles, int elem_size, hipStream_t stream);
+// quantiser->bitswap1->lz4 on the same tables (16-bit voxels): the 65536-bin histogram of job j at d_histos + 65536 j (zeroed by the
+// launcher); its encode LUT (65536 bytes at d_luts_encode + 65536 j) and decode LUT (256 values at d_luts_decode + 256 j) -- exactly
+// sqy::quantiser_build_luts' for the default weighting, one workgroup per histogram, no host involved; look-up and 8-bit bit-plane
+// transpose in one pass into job j's `out` (launch_quantiser_apply_bitswap1_u8's layout)
+hipError_t launch_batch_quantiser_histogram(const Bitswap1Job* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ntiles, uint32_t* d_histos,
+                                            hipStream_t stream);
+hipError_t launch_batch_quantiser_lut(const uint32_t* d_histos, uint32_t njobs, uint8_t* d_luts_encode, uint16_t* d_luts_decode, hipStream_t stream);
+hipError_t launch_batch_quantiser_bitswap1(const Bitswap1Job* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ntiles, const uint8_t* d_luts_encode,
+                                           hipStream_t stream);
 // One entry of the joint chunk table (sqy::Lz4BatchChunkPlan, sqy_pipeline.hpp): chunk e is the n bytes at in + off, compressed on its
 // own into scratch + slot * stride, csize[e] (0: stored); redo as for launch_lz4_chunks (nentries + 1 words, the launcher zeroes redo[0])
 struct Lz4BatchChunk { uint64_t off; uint32_t n, vol, slot, pad; };

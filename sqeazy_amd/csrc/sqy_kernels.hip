@@ -20,6 +20,7 @@
 
 #include "sqy_kernels.h"
 #include "sqy_pipeline.hpp"
+#include "sqy_quantiser_lut.hpp"
 
 namespace sqy {
 
@@ -8125,6 +8126,260 @@ hipError_t launch_rmbkrd_neighbor5(const void* in, void* out, uint64_t Z, uint64
                            static_cast<uint8_t*>(out), (int64_t)Z, (int64_t)Y, (int64_t)X, threshold, cut, (int64_t)z_end, (uint32_t)ntx, (uint32_t)nty);
     else
         return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// Batch encode of quantiser->bitswap1->lz4 volumes (SQYAMD_PipelineEncode_Batch_*): histograms, LUTs, look-up + transpose of all volumes
+// of a group, one launch each, on bitswap1_batch_kernel's job table (job j: `len` 16-bit voxels at `in`, any voxel-aligned address; its
+// planes + tail to `out`, 16-byte aligned) and tile prefix sums (a workgroup = one tile of BSWB_TILE_VOX voxels of one job).
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t batch_find_job(const uint32_t* __restrict__ first_tile, uint32_t njobs)
+{
+    uint32_t lo = 0, hi = njobs;                                      // first_tile[lo] <= blockIdx.x < first_tile[hi]
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (first_tile[mid] <= blockIdx.x) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// The 65536-bin histogram of job j at histos + 65536 j (zeroed in front of the launch).  histogram_u16_kernel's LDS window per tile: a
+// private 16384-bin quarter of the value range (voted from the tile's first voxels) counted with LDS atomics, the rest and the flush with
+// global ones.  Sixteen-byte loads where the job's pointer allows, voxel by voxel where not.
+__global__ __launch_bounds__(256)
+void batch_quantiser_histogram_kernel(const Bitswap1Job* __restrict__ jobs, const uint32_t* __restrict__ first_tile, uint32_t njobs,
+                                      uint32_t* __restrict__ histos)
+{
+    extern __shared__ uint32_t hwin[];      // HIST_WIN_BINS counters
+    __shared__ uint32_t votes[4];
+    const uint32_t j = batch_find_job(first_tile, njobs), tile = blockIdx.x - first_tile[j], tid = threadIdx.x;
+    const Bitswap1Job job = jobs[j];
+    const uint64_t v_begin = (uint64_t)tile * BSWB_TILE_VOX;
+    if (v_begin >= job.len) return;                                   // (uniform; a job has at least one voxel)
+    const uint32_t n = (uint32_t)(job.len - v_begin < BSWB_TILE_VOX ? job.len - v_begin : BSWB_TILE_VOX);     // voxels of this tile
+    const uint16_t* __restrict__ in = static_cast<const uint16_t*>(job.in) + v_begin;
+    uint32_t* __restrict__ histo = histos + (uint64_t)j * 65536u;
+    for (uint32_t i = tid; i < (uint32_t)HIST_WIN_BINS / 4u; i += 256) reinterpret_cast<uint4*>(hwin)[i] = make_uint4(0, 0, 0, 0);
+    if (tid < 4) votes[tid] = 0;
+    __syncthreads();
+    const bool wide = (reinterpret_cast<uintptr_t>(in) & 15u) == 0;   // (a tile starts 64 KiB multiples behind the job's pointer)
+    const uint32_t probe = wide ? tid * 8u : tid;
+    if (probe < n) atomicAdd(&votes[in[probe] >> 14], 1u);
+    __syncthreads();
+    uint32_t best = 0;
+#pragma unroll
+    for (uint32_t q = 1; q < 4; ++q) if (votes[q] > votes[best]) best = q;
+    const uint32_t wbase = best * HIST_WIN_BINS;
+    auto count = [&](uint32_t a) {
+        const uint32_t r = a - wbase;
+        if (r < (uint32_t)HIST_WIN_BINS) atomicAdd(&hwin[r], 1u); else atomicAdd(&histo[a], 1u);
+    };
+    if (wide) {
+        const uint32_t nvec = n / 8u;                                 // 8 voxels per 16-byte load
+        const uint4* src = reinterpret_cast<const uint4*>(in);
+        for (uint32_t vb = tid; vb < nvec; vb += 1024) {              // four loads in flight per thread
+            uint4 xs[4];
+#pragma unroll
+            for (uint32_t u = 0; u < 4; ++u) if (vb + u * 256u < nvec) xs[u] = src[vb + u * 256u];
+#pragma unroll
+            for (uint32_t u = 0; u < 4; ++u) {
+                if (vb + u * 256u >= nvec) continue;
+                const uint32_t w[4] = {xs[u].x, xs[u].y, xs[u].z, xs[u].w};
+#pragma unroll
+                for (int k = 0; k < 4; ++k) { count(w[k] & 0xffffu); count(w[k] >> 16); }
+            }
+        }
+        if (nvec * 8u + tid < n) count(in[nvec * 8u + tid]);          // (at most 7 voxels)
+    } else {
+        for (uint32_t i = tid; i < n; i += 1024) {
+            uint32_t xs[4];
+#pragma unroll
+            for (uint32_t u = 0; u < 4; ++u) if (i + u * 256u < n) xs[u] = in[i + u * 256u];
+#pragma unroll
+            for (uint32_t u = 0; u < 4; ++u) if (i + u * 256u < n) count(xs[u]);
+        }
+    }
+    __syncthreads();
+    for (uint32_t i = tid; i < (uint32_t)HIST_WIN_BINS; i += 256) {
+        const uint32_t c = hwin[i];
+        if (c) atomicAdd(&histo[wbase + i], c);
+    }
+}
+
+// One workgroup per histogram: encode LUT (65536 bytes) and decode LUT (256 x uint16) of the default weighting, sqy::quantiser_lut_default
+// (sqy_quantiser_lut.hpp -- the source the host test compiles as well).  All four wavefronts read the histogram once: the total, the
+// number of occupied bins and a bit per bin "has a count" in LDS.  Wavefront 0 then walks: lane k holds bin k of the current 64, the chain
+// runs wave-uniform, blocks without a count cost no load (the next block's counts are asked for while the current one is walked), and the
+// encode LUT leaves in 64-byte stores.
+constexpr uint32_t QLUT_THREADS = 256;
+struct QlutWaveBlocks {
+    const uint32_t* __restrict__ histo;
+    uint8_t* __restrict__ lut_encode;
+    const uint32_t* occ_bits;               // LDS: bit (i & 31) of word i >> 5 = bin i has a count
+    double total_;
+    uint32_t levels_, lane, base, c, c_next, code;
+    __device__ uint64_t occupied(uint32_t b) const { return (uint64_t)occ_bits[2 * b] | ((uint64_t)occ_bits[2 * b + 1] << 32); }
+    __device__ double total() const { return total_; }
+    __device__ uint32_t levels() const { return levels_; }
+    __device__ void prefetch(uint32_t b) { c_next = (b < kQlutBlocks && occupied(b) != 0) ? histo[b * kQlutBlockBins + lane] : 0u; }
+    __device__ uint64_t enter(uint32_t b)
+    {
+        base = b * kQlutBlockBins;
+        c = c_next;
+        prefetch(b + 1);
+        return occupied(b);
+    }
+    __device__ uint32_t count(uint32_t k) const { return (uint32_t)__builtin_amdgcn_readlane((int)c, (int)k); }
+    __device__ void codes_begin(uint32_t v) { code = v; }
+    __device__ void codes_from(uint32_t k, uint32_t v) { if (lane >= k) code = v; }
+    __device__ void codes_write() { lut_encode[base + lane] = (uint8_t)code; }
+};
+
+__global__ __launch_bounds__(QLUT_THREADS)
+void batch_quantiser_lut_kernel(const uint32_t* __restrict__ histos, uint8_t* __restrict__ luts_encode, uint16_t* __restrict__ luts_decode)
+{
+    __shared__ uint32_t occ_bits[kQlutBins / 32];
+    __shared__ double s_total[QLUT_THREADS / 64];
+    __shared__ uint32_t s_levels[QLUT_THREADS / 64];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t* __restrict__ histo = histos + (uint64_t)blockIdx.x * kQlutBins;
+    for (uint32_t i = tid; i < kQlutBins / 32; i += QLUT_THREADS) occ_bits[i] = 0;
+    __syncthreads();
+    // (the terms are integers below 2^32, the sum stays below 2^48: a double adds them exactly in any order)
+    double total = 0.;
+    uint32_t levels = 0;
+    const uint4* src = reinterpret_cast<const uint4*>(histo);
+    for (uint32_t q0 = tid; q0 < kQlutBins / 4; q0 += QLUT_THREADS * 8) {      // eight loads in flight per thread
+        uint4 xs[8];
+#pragma unroll
+        for (uint32_t u = 0; u < 8; ++u) xs[u] = src[q0 + u * QLUT_THREADS];
+#pragma unroll
+        for (uint32_t u = 0; u < 8; ++u) {
+            const uint32_t q = q0 + u * QLUT_THREADS;                          // bins 4 q .. 4 q + 3
+            const uint32_t w[4] = {xs[u].x, xs[u].y, xs[u].z, xs[u].w};
+            uint32_t bits = 0;
+#pragma unroll
+            for (uint32_t k = 0; k < 4; ++k) {
+                const float importance = qlut_importance(w[k]);
+                total = total + (double)importance;
+                if (importance != 0.f) bits |= 1u << k;
+            }
+            levels += __popc(bits);
+            if (bits) atomicOr(&occ_bits[q >> 3], bits << ((q & 7u) * 4u));
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) { total += __shfl_xor(total, off); levels += __shfl_xor(levels, off); }
+    if ((tid & 63u) == 0) { s_total[tid >> 6] = total; s_levels[tid >> 6] = levels; }
+    __syncthreads();
+    if (tid >= 64) return;                                                     // (no barrier behind this point)
+    QlutWaveBlocks io;
+    io.histo = histo;
+    io.lut_encode = luts_encode + (uint64_t)blockIdx.x * kQlutBins;
+    io.occ_bits = occ_bits;
+    io.total_ = 0.;
+    io.levels_ = 0;
+    for (uint32_t w = 0; w < QLUT_THREADS / 64; ++w) { io.total_ += s_total[w]; io.levels_ += s_levels[w]; }
+    io.lane = tid;
+    io.base = 0; io.c = 0; io.code = 0;
+    io.prefetch(0);
+    quantiser_lut_default(io, luts_decode + (uint64_t)blockIdx.x * kQlutLevels);
+}
+
+// byte b of the result: bit b of the word's eight codes, code j at bit 7 - j (bitswap1_u8_generic)
+__device__ __forceinline__ uint64_t bswb_code_planes(uint64_t x)
+{
+    uint64_t t = x, y;
+    y = (t ^ (t >> 7)) & 0x00AA00AA00AA00AAull; t = t ^ y ^ (y << 7);
+    y = (t ^ (t >> 14)) & 0x0000CCCC0000CCCCull; t = t ^ y ^ (y << 14);
+    y = (t ^ (t >> 28)) & 0x00000000F0F0F0F0ull; t = t ^ y ^ (y << 28);
+    const uint32_t r0 = __brev((uint32_t)t), r1 = __brev((uint32_t)(t >> 32));      // (bits reversed in every byte, bytes swapped)
+    return (uint64_t)__builtin_bswap32(r0) | ((uint64_t)__builtin_bswap32(r1) << 32);
+}
+
+// Look-up and 8-bit bit-plane transpose in one pass: bitswap1_batch_kernel<1>'s thread layout (a thread owns 128 voxels in a row: 256
+// source bytes, 16 words of 8 codes, 16 bytes of each of the 8 planes) with job j's encode LUT (luts + 65536 j) staged in LDS in front.
+// Job j's output is quantiser_apply_bitswap1_u8_kernel's: 8 plane segments of len / 8 bytes, MSB plane first, then the len % 8 tail codes.
+__global__ __launch_bounds__(256)
+void batch_quantiser_bitswap1_kernel(const Bitswap1Job* __restrict__ jobs, const uint32_t* __restrict__ first_tile, uint32_t njobs,
+                                     const uint8_t* __restrict__ luts)
+{
+    extern __shared__ uint8_t slut[];
+    constexpr uint32_t WPT = BSWB_THREAD_VOX / 8;                     // words per thread
+    const uint32_t j = batch_find_job(first_tile, njobs), tile = blockIdx.x - first_tile[j], tid = threadIdx.x;
+    const Bitswap1Job job = jobs[j];
+    const uint4* __restrict__ lut = reinterpret_cast<const uint4*>(luts + (uint64_t)j * 65536u);
+    for (uint32_t i = tid; i < 65536u / 16u; i += 256) reinterpret_cast<uint4*>(slut)[i] = lut[i];
+    __syncthreads();
+    const uint64_t seg = job.len / 8, L = seg * 8;                    // bytes per plane; voxels in the planes
+    const uint16_t* __restrict__ in = static_cast<const uint16_t*>(job.in);
+    uint8_t* __restrict__ out = static_cast<uint8_t*>(job.out);
+    if (tile == 0 && tid < job.len - L) out[L + tid] = slut[in[L + tid]];      // tail voxels [L, len): their codes
+    const uint64_t w0 = ((uint64_t)tile * 256u + tid) * WPT;
+    if (w0 >= seg) return;
+    const bool wide_in = (reinterpret_cast<uintptr_t>(in) & 15u) == 0;
+    const bool wide_out = w0 + WPT <= seg && ((reinterpret_cast<uintptr_t>(out) | seg) & 15u) == 0;
+    // byte i of the result = the code of voxel 8 w + i
+    auto codes = [&](uint64_t w) -> uint64_t {
+        uint32_t v[8];
+        if (wide_in) {
+            const uint4 x = *reinterpret_cast<const uint4*>(in + w * 8u);
+            v[0] = x.x & 0xffffu; v[1] = x.x >> 16; v[2] = x.y & 0xffffu; v[3] = x.y >> 16;
+            v[4] = x.z & 0xffffu; v[5] = x.z >> 16; v[6] = x.w & 0xffffu; v[7] = x.w >> 16;
+        } else {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) v[i] = in[w * 8u + i];
+        }
+        uint64_t t = 0;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) t |= (uint64_t)slut[v[i]] << (8 * i);
+        return t;
+    };
+    if (wide_out) {
+        uint32_t res[8][4];
+#pragma unroll
+        for (int b = 0; b < 8; ++b) { res[b][0] = 0; res[b][1] = 0; res[b][2] = 0; res[b][3] = 0; }
+#pragma unroll
+        for (uint32_t i = 0; i < WPT; ++i) {
+            const uint64_t t = bswb_code_planes(codes(w0 + i));
+#pragma unroll
+            for (int b = 0; b < 8; ++b) res[b][i >> 2] |= ((uint32_t)(t >> (8 * b)) & 0xffu) << (8u * (i & 3u));
+        }
+#pragma unroll
+        for (int b = 0; b < 8; ++b)
+            *reinterpret_cast<uint4*>(out + (uint64_t)(7 - b) * seg + w0) = make_uint4(res[b][0], res[b][1], res[b][2], res[b][3]);
+    } else {
+        for (uint64_t w = w0; w < w0 + WPT && w < seg; ++w) {
+            const uint64_t t = bswb_code_planes(codes(w));
+#pragma unroll
+            for (int b = 0; b < 8; ++b) out[(uint64_t)(7 - b) * seg + w] = (uint8_t)(t >> (8 * b));
+        }
+    }
+}
+
+hipError_t launch_batch_quantiser_histogram(const Bitswap1Job* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ntiles, uint32_t* d_histos,
+                                            hipStream_t stream)
+{
+    if (njobs == 0 || ntiles == 0) return hipSuccess;
+    hipError_t e = hipMemsetAsync(d_histos, 0, (size_t)njobs * 65536u * sizeof(uint32_t), stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(batch_quantiser_histogram_kernel, dim3(ntiles), dim3(256), HIST_WIN_BINS * sizeof(uint32_t), stream, d_jobs, d_first_tile, njobs, d_histos);
+    return hipGetLastError();
+}
+
+hipError_t launch_batch_quantiser_lut(const uint32_t* d_histos, uint32_t njobs, uint8_t* d_luts_encode, uint16_t* d_luts_decode, hipStream_t stream)
+{
+    if (njobs == 0) return hipSuccess;
+    hipLaunchKernelGGL(batch_quantiser_lut_kernel, dim3(njobs), dim3(QLUT_THREADS), 0, stream, d_histos, d_luts_encode, d_luts_decode);
+    return hipGetLastError();
+}
+
+hipError_t launch_batch_quantiser_bitswap1(const Bitswap1Job* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ntiles, const uint8_t* d_luts_encode,
+                                           hipStream_t stream)
+{
+    if (njobs == 0 || ntiles == 0) return hipSuccess;
+    hipLaunchKernelGGL(batch_quantiser_bitswap1_kernel, dim3(ntiles), dim3(256), 65536, stream, d_jobs, d_first_tile, njobs, d_luts_encode);
     return hipGetLastError();
 }
 

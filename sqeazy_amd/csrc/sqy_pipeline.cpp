@@ -285,7 +285,27 @@ Lz4EncodeLayout lz4_encode_layout(const Lz4Params& p, uint64_t total, unsigned n
 
 static uint64_t round_up(uint64_t v, uint64_t to) { return (v + to - 1) / to * to; }
 
-Lz4BatchPlan lz4_batch_plan(const Lz4Params& p, const std::vector<uint64_t>& totals, unsigned nthreads, uint64_t group_bytes, uint64_t joint_max)
+EncodeBatchForm encode_batch_form(const Pipeline& pipe, int elem_size)
+{
+    const std::vector<Stage>& st = pipe.stages;
+    if (st.empty() || st.back().kind != StageKind::lz4) return EncodeBatchForm::none;
+    if (st.size() == 1) return EncodeBatchForm::lz4;
+    if (st.size() == 2 && st[0].kind == StageKind::bitswap1) return EncodeBatchForm::bitswap1_lz4;
+    if (st.size() == 3 && st[0].kind == StageKind::quantiser && st[1].kind == StageKind::bitswap1 && elem_size == 2 &&
+        !st[0].cfg.count("weighting_function") && !st[0].cfg.count("decode_lut_path"))
+        return EncodeBatchForm::quantiser_bitswap1_lz4;
+    return EncodeBatchForm::none;
+}
+
+uint64_t encode_batch_stream_bytes(EncodeBatchForm form, uint64_t voxels, int elem_size)
+{
+    return form == EncodeBatchForm::quantiser_bitswap1_lz4 ? voxels : voxels * (uint64_t)elem_size;
+}
+
+uint64_t encode_batch_extra_bytes(EncodeBatchForm form) { return form == EncodeBatchForm::quantiser_bitswap1_lz4 ? kQuantiserBatchTableBytes : 0; }
+
+Lz4BatchPlan lz4_batch_plan(const Lz4Params& p, const std::vector<uint64_t>& totals, unsigned nthreads, uint64_t group_bytes, uint64_t joint_max,
+                            uint64_t extra_bytes)
 {
     Lz4BatchPlan plan;
     plan.group_of.assign(totals.size(), -1);
@@ -295,7 +315,7 @@ Lz4BatchPlan lz4_batch_plan(const Lz4Params& p, const std::vector<uint64_t>& tot
         const Lz4EncodeLayout lay = lz4_encode_layout(p, total, nthreads);
         // (a table entry counts its bytes and its slot in 32 bits: chunks of the chunked layout are at most an LZ4 block of 4 MiB)
         if (total == 0 || !lay.chunked() || lay.accel != 1 || total > joint_max || lay.nchunks == 0 || lay.chunk > UINT32_MAX) continue;
-        if (plan.groups.empty() || (group_sum && group_sum + total > group_bytes) ||
+        if (plan.groups.empty() || (group_sum && group_sum + total + extra_bytes > group_bytes) ||
             plan.groups.back().chunks.size() + lay.nchunks > (uint64_t)UINT32_MAX / 2) {
             plan.groups.emplace_back();
             plan.groups.back().first_chunk.push_back(0);
@@ -317,7 +337,7 @@ Lz4BatchPlan lz4_batch_plan(const Lz4Params& p, const std::vector<uint64_t>& tot
         g.first_chunk.push_back((uint32_t)g.chunks.size());
         g.stream_bytes = at + total;
         g.scratch_stride = round_up(g.max_chunk, 16);
-        group_sum += total;
+        group_sum += total + extra_bytes;
         plan.group_of[i] = (int32_t)(plan.groups.size() - 1);
     }
     return plan;

@@ -103,8 +103,23 @@ struct Lz4BatchPlan {
 // totals[i]: the bytes in front of the LZ4 stage for volume i (> 0: empty volumes are refused before planning).  A volume is
 // joint-eligible when its layout (lz4_encode_layout) is `chunked` with acceleration 1 and totals[i] <= joint_max.  Eligible volumes are
 // dealt to groups in order; a group is closed when the next volume would take its streams past group_bytes (a group holds at least
-// one volume, so a volume larger than the bound gets a group of its own).
-Lz4BatchPlan lz4_batch_plan(const Lz4Params& p, const std::vector<uint64_t>& totals, unsigned nthreads, uint64_t group_bytes, uint64_t joint_max);
+// one volume, so a volume larger than the bound gets a group of its own).  extra_bytes: workspace every eligible volume takes besides
+// its stream (the quantised form's tables); it counts against group_bytes with the stream, not against joint_max.
+Lz4BatchPlan lz4_batch_plan(const Lz4Params& p, const std::vector<uint64_t>& totals, unsigned nthreads, uint64_t group_bytes, uint64_t joint_max,
+                            uint64_t extra_bytes = 0);
+// Which joint form a pipeline takes in a batch -- the stages in front of the LZ4 stage that the group's kernels do for all volumes at once:
+//   none: every volume through the single-call path | lz4: the stream is the volume | bitswap1_lz4: the batched transposer |
+//   quantiser_bitswap1_lz4: 16-bit voxels, the quantiser with the default weighting (no weighting_function) and the decode LUT in the
+//   header (no decode_lut_path) -- histograms, LUTs, look-up and transpose batched, one byte per voxel in front of the LZ4 stage
+enum class EncodeBatchForm : uint8_t { none, lz4, bitswap1_lz4, quantiser_bitswap1_lz4 };
+struct Pipeline;
+EncodeBatchForm encode_batch_form(const Pipeline& pipe, int elem_size);
+// the quantised form's tables per volume: histogram (65536 x 4 bytes), encode LUT (65536 bytes), decode LUT (256 x 2 bytes)
+constexpr uint64_t kQuantiserBatchHistoBytes = 65536 * 4, kQuantiserBatchLutBytes = 65536, kQuantiserBatchDecodeBytes = 256 * 2,
+                   kQuantiserBatchTableBytes = kQuantiserBatchHistoBytes + kQuantiserBatchLutBytes + kQuantiserBatchDecodeBytes;
+// the bytes in front of the LZ4 stage for a volume of `voxels` voxels, and what lz4_batch_plan takes as extra_bytes
+uint64_t encode_batch_stream_bytes(EncodeBatchForm form, uint64_t voxels, int elem_size);
+uint64_t encode_batch_extra_bytes(EncodeBatchForm form);
 
 // ---- batch decode (SQYAMD_Decode_Batch_*): many blobs, one launch per kernel ----
 // What the planner knows of blob i: the bytes its LZ4 stage decodes to, the LZ4 block size, whether it may take the joint path at all

@@ -7,7 +7,10 @@ repetition by repetition inside one process, u16 volumes from synth.stack_torch:
   batch0   -- SQYAMD_PipelineEncode_Batch_UI16_Device with encode_batch_joint = 0 (every volume on its own inside the call)
   batch    -- .. as it comes
 Configurations: a = 64 x 16x512x512 bitswap1->lz4 (the encode mirror of tools/slabs_decode_time.py's d), b = 256 x 16x128x128 bitswap1->lz4,
-c = 256 x 16x128x128 lz4, d = 8 x 64x1024x1024 bitswap1->lz4.  `sweep`: bitswap1->lz4 volumes of 128 KiB .. 128 MiB (z x 256 x 256, as many
+c = 256 x 16x128x128 lz4, d = 8 x 64x1024x1024 bitswap1->lz4; quantiser->bitswap1->lz4 (columns loop, batch0, batch -- the slabs of slabs3
+get other LUTs than the volumes, so their blobs are not comparable): e = 256 x 16x128x128, f = 64 x 16x512x512, g = 4 x 16x128x128.  For
+these the baseline is batch0 -- every volume through the single-call path inside the call, what the call did before the joint form --
+and the row ends with the per-kernel device times of one profiled batch call (SQYAMD_Profile_*).  `sweep`: bitswap1->lz4 volumes of 128 KiB .. 128 MiB (z x 256 x 256, as many
 as make 1 GiB, at most 256), loop against batch with every volume on the joint path -- the largest size at which batch is not slower than
 loop in any of the k pairs is the default of "encode_batch_joint_max_bytes".  Every blob is checked against the loop's.  One JSON line per row."""
 import json
@@ -23,7 +26,8 @@ from sqeazy_amd import synth  # noqa: E402
 
 K = int(sys.argv[1]) if len(sys.argv) > 1 else 5
 CONFIGS = {"a": ("bitswap1->lz4", (16, 512, 512), 64), "b": ("bitswap1->lz4", (16, 128, 128), 256), "c": ("lz4", (16, 128, 128), 256),
-           "d": ("bitswap1->lz4", (64, 1024, 1024), 8)}
+           "d": ("bitswap1->lz4", (64, 1024, 1024), 8), "e": ("quantiser->bitswap1->lz4", (16, 128, 128), 256),
+           "f": ("quantiser->bitswap1->lz4", (16, 512, 512), 64), "g": ("quantiser->bitswap1->lz4", (16, 128, 128), 4)}
 WANT = sys.argv[2:] or sorted(CONFIGS)
 
 
@@ -98,6 +102,20 @@ def run(name, pipeline, shape, n, columns, dev, stream, joint_max=None):
         row["batch_wins_every_pair"] = all(b < x for b, x in zip(ms["batch"], base))
         row["baseline_over_batch"] = [round(x / b, 2) for b, x in zip(ms["batch"], base)]
         row["loop_spread"] = [min(ms["loop"]), max(ms["loop"])]
+    if "batch" in ms and "batch0" in ms:
+        row["batch0_over_batch"] = [round(x / b, 2) for b, x in zip(ms["batch"], ms["batch0"])]
+        row["batch_faster_than_batch0_every_pair"] = all(b < x for b, x in zip(ms["batch"], ms["batch0"]))
+        row["batch_not_slower_than_batch0_any_pair"] = all(b <= x for b, x in zip(ms["batch"], ms["batch0"]))
+    if pipeline.startswith("quantiser"):
+        sqeazy_amd.profile_reset()
+        sqeazy_amd.profile_enable(True)
+        try:
+            batch()
+            torch.cuda.synchronize()
+        finally:
+            sqeazy_amd.profile_enable(False)
+        row["batch_kernel_ms"] = {k: [round(v[0], 3), v[1]] for k, v in sorted(sqeazy_amd.profile_get().items())}
+        sqeazy_amd.profile_reset()
     print(json.dumps(row), flush=True)
     del vol, out
     torch.cuda.empty_cache()
@@ -119,7 +137,7 @@ def main():
             print(json.dumps({"sweep": "encode_batch_joint_max_bytes", "largest_size_not_slower_in_any_pair": best}), flush=True)
         else:
             pipeline, shape, n = CONFIGS[name]
-            run(name, pipeline, shape, n, ("loop", "slabs3", "batch0", "batch"), dev, stream)
+            run(name, pipeline, shape, n, ("loop", "batch0", "batch") if pipeline.startswith("quantiser") else ("loop", "slabs3", "batch0", "batch"), dev, stream)
 
 
 if __name__ == "__main__":
