@@ -11,7 +11,10 @@ Sources of truth
                    (encoders/sse_utils.hpp:1365-1433), compiled in place from the reference tree
   * filter stages  diff3x3x1, rmestbkrd, rmbkrd_neighbor5x5x5, zcurve_reorder, raster_reorder, scalar bitswap1 and the histogram: the
                    reference's own templates compiled in place (oracle/ref_driver.cpp) -> tests/golden/ref_stages.json (--stages)
-  * what the reference cannot produce here (needs Boost proper: quantiser LUT, frame_shuffle, tile_shuffle, header) is NOT in this
+  * quantiser LUTs the reference's own sqeazy::quantiser<uint16_t, uint8_t> compiled in place (oracle/ref_driver.cpp, with the
+                   string_parsers.hpp of oracle/ref_shim/) on the volumes of tests/quantiser_cases.py -> tests/golden/quantiser_luts.json
+                   (--quantiser): digests of both tables
+  * what the reference cannot produce here (needs Boost proper: frame_shuffle, tile_shuffle, header) is NOT in this
     file's "reference" section; those stages are pinned by the reference's own KATs restated in
     tests/test_oracle_reference_kats.py and carry "oracle" hashes here only as regression anchors.
 
@@ -593,9 +596,14 @@ def stages():
     print("wrote ref_stages.json:", n, "cases,", sum("refused" in c for c in G["cases"]), "refused,", sum("undefined" in c for c in G["cases"]), "undefined")
 
 
+# the volumes of tests/quantiser_cases.py the sanitized driver runs the reference's quantiser on: the Lloyd walk where binary32 rounds, and
+# the walk's first case with the top bin occupied
+QUANTISER_SAN_CASES = ("uniform_60000", "levels_257_top")
+
+
 def dump_stage_cases(path):
     """inputs of every case the reference is run on, for tests/sanitize/ref_stages_san.cpp: cases.txt (one line per case:
-    id stage dtype z y x p0 p1 offset_bytes serial_only) and <index>.bin"""
+    id stage dtype z y x p0 p1 offset_bytes serial_only) and <index>.bin; quantiser.txt (name, voxels) and quantiser_<index>.bin"""
     os.makedirs(path, exist_ok=True)
     lines = []
     for row in stage_table():
@@ -610,12 +618,56 @@ def dump_stage_cases(path):
                                                        float(p.get("fraction", 0.0)), p.get("offset_bytes", 0), int("serial_only" in row)))
     with open(os.path.join(path, "cases.txt"), "w") as f:
         f.write("\n".join(lines) + "\n")
+    import quantiser_cases as Q
+    with open(os.path.join(path, "quantiser.txt"), "w") as f:
+        for k, name in enumerate(QUANTISER_SAN_CASES):
+            Q.volume(name).tofile(os.path.join(path, "quantiser_%d.bin" % k))
+            f.write("%s %d\n" % (name, Q.volume(name).size))
     return len(lines)
+
+
+# the weightings the quantiser goldens hold besides the default: one of each of the reference's two functors
+QUANTISER_WEIGHTERS = ("power_of_1_2", "offset_power_of_2_3")
+
+
+def quantiser_weightings(name):
+    """the weightings a case of tests/quantiser_cases.py is recorded and compared with"""
+    import quantiser_cases as Q
+    return ("none",) + (QUANTISER_WEIGHTERS if Q.FAMILY[name] in (Q.ROUNDING, Q.BOUNDARY) else ())
+
+
+def quantiser():
+    """tests/golden/quantiser_luts.json: for every volume of tests/quantiser_cases.py the sha256 of the encode LUT (65536 bytes) and of the
+    decode LUT (256 little-endian uint16) that the REFERENCE's quantiser builds from the voxels, one and three threads asserted equal, the
+    oracle asserted equal on the way.  Digests only."""
+    import quantiser_cases as Q
+    assert ref.quantiser_available(), "oracle/_ref/libsqy_ref.so missing or stale: run `make -C oracle` where the reference tree exists"
+    out = {"_meta": {"generator": "oracle/gen_golden.py --quantiser", "cases": "tests/quantiser_cases.py: volume(name)",
+                     "source": "sqeazy::quantiser<uint16_t, uint8_t>::setup_com compiled in place (oracle/ref_driver.cpp)",
+                     "digests": "[sha256 of lut_encode, uint8[65536]; sha256 of lut_decode, uint16[256] little-endian] per weighting_function"},
+           "cases": {}}
+    for name in Q.NAMES:
+        vol = Q.volume(name)
+        e = {"voxels_sha256": sha(vol.tobytes())[:12], "luts": {}}
+        for w in quantiser_weightings(name):
+            enc, dec = ref.quantiser_luts(vol, w, 1)
+            enc3, dec3 = ref.quantiser_luts(vol, w, 3)
+            assert np.array_equal(enc, enc3) and np.array_equal(dec, dec3), ("the reference disagrees with itself across thread counts", name, w)
+            oenc, odec = o.quantiser_build_luts(o.histogram(vol), w)
+            assert np.array_equal(enc, oenc) and np.array_equal(dec, odec), ("the oracle differs from the reference", name, w)
+            e["luts"][w] = [sha(enc.tobytes()), sha(dec.astype("<u2").tobytes())]
+        out["cases"][name] = e
+    with open(os.path.join(GOLD, "quantiser_luts.json"), "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print("wrote quantiser_luts.json:", len(out["cases"]), "cases")
 
 
 if __name__ == "__main__":
     if "--stages" in sys.argv:
         stages()
+    elif "--quantiser" in sys.argv:
+        quantiser()
     elif "--accel" in sys.argv:
         accel()
     elif "--lz4-planted" in sys.argv:
@@ -631,6 +683,7 @@ if __name__ == "__main__":
     else:
         main()
         stages()
+        quantiser()
         accel()
         lz4_planted()
         headline()

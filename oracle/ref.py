@@ -1,5 +1,6 @@
 """Loader for oracle/_ref/libsqy_ref.so -- the driver around the REAL reference pieces that build in
-this image (reference SSE bit-plane gather + the image's liblz4 1.9.3).  TEST INFRASTRUCTURE ONLY.
+this image (the reference's filter-stage templates, its SSE bit-plane gather and its quantiser + the image's
+liblz4 1.9.3).  TEST INFRASTRUCTURE ONLY.
 
 The library is built by oracle/Makefile from /root/reference when that tree is present; on the GPU box
 only the prebuilt file (shipped with the snapshot) can be used.  `available()` says whether it loads.
@@ -41,7 +42,7 @@ def _rebuild_if_stale(path):
             data = f.read()
     except OSError:
         return
-    if all(name.encode() in data for name in STAGE_ENTRY_POINTS):
+    if all(name.encode() in data for name in STAGE_ENTRY_POINTS + QUANTISER_ENTRY_POINTS):
         return
     try:
         if reference_tree():
@@ -64,6 +65,16 @@ def stages_available():
     reference tree is absent and nothing can be rebuilt, has only the LZ4 and SSE ones"""
     L = lib()
     return L is not None and all(hasattr(L, f) for f in STAGE_ENTRY_POINTS)
+
+
+QUANTISER_ENTRY_POINTS = ("ref_quantiser_luts", "ref_quantiser_encode")
+
+
+def quantiser_available():
+    """True when the library also holds the reference's quantiser: a prebuilt oracle/_ref from a driver before those entry points has the
+    other stages only"""
+    L = lib()
+    return L is not None and all(hasattr(L, f) for f in QUANTISER_ENTRY_POINTS)
 
 
 def _make(target):
@@ -194,6 +205,34 @@ def hist_stats(a):
     _done(lib().ref_hist_stats(_DT[a.dtype], ctypes.c_void_p(a.ctypes.data), ctypes.c_size_t(a.size),
                                bins.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), st.ctypes.data_as(ctypes.POINTER(ctypes.c_double))), "histogram")
     return bins, dict(zip(HIST_STATS, st.tolist()))
+
+
+def _weighting(weighting):
+    from oracle import sqy_oracle
+    return sqy_oracle.quantiser_weighting(weighting)        # the text -> (mode, numerator, denominator), as the scheme reads it
+
+
+def quantiser_luts(a, weighting="none", nthreads=1):
+    """(lut_encode uint8[65536], lut_decode uint16[256]) of sqeazy::quantiser<uint16_t, uint8_t> after setup_com on the voxels"""
+    flat = np.ascontiguousarray(a, dtype=np.uint16).reshape(-1)
+    enc = np.zeros(65536, np.uint8)
+    dec = np.zeros(256, np.uint16)
+    mode, num, den = _weighting(weighting)
+    _done(lib().ref_quantiser_luts(flat.ctypes.data_as(_u16p), ctypes.c_size_t(flat.size), mode, num, den, int(nthreads),
+                                   enc.ctypes.data_as(_u8p), dec.ctypes.data_as(_u16p)), "quantiser")
+    return enc, dec
+
+
+def quantiser_encode(a, weighting="none", nthreads=1):
+    """(codes uint8 of a.shape, lut_decode uint16[256]): quantiser_scheme::encode on the voxels"""
+    a = np.ascontiguousarray(a, dtype=np.uint16)
+    flat = a.reshape(-1)
+    codes = np.zeros(flat.size, np.uint8)
+    dec = np.zeros(256, np.uint16)
+    mode, num, den = _weighting(weighting)
+    _done(lib().ref_quantiser_encode(flat.ctypes.data_as(_u16p), ctypes.c_size_t(flat.size), mode, num, den, int(nthreads),
+                                     codes.ctypes.data_as(_u8p), dec.ctypes.data_as(_u16p)), "quantiser")
+    return codes.reshape(a.shape), dec
 
 
 def bitswap1_encode_u16(a, nthreads=1):

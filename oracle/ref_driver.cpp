@@ -9,7 +9,11 @@
  *      standard headers Boost used to drag in.  Compiled unmodified: traits.hpp, neighborhood_utils.hpp,
  *      diff_scheme_utils.hpp, sqeazy_common.hpp, sqeazy_algorithms.hpp, hist_impl.hpp,
  *      encoders/{histogram_utils, background_scheme_utils, zcurve_reorder_utils, morton,
- *      raster_reorder_utils, scalar_utils, bitplane_reorder_scalar, bitplane_reorder_sse, sse_utils}.hpp.
+ *      raster_reorder_utils, scalar_utils, bitplane_reorder_scalar, bitplane_reorder_sse, sse_utils,
+ *      quantiser_utils, quantiser_weighters}.hpp and header_utils.hpp.  quantiser_utils.hpp includes
+ *      "string_parsers.hpp" (Boost.StringAlgo) for its two LUT-as-string helpers; oracle/ref_shim/ holds a header
+ *      of that name, our own, that declares the two templates those helpers name, and the Makefile puts it on the
+ *      include path in front of the reference tree.  The driver never calls the helpers.
  *      The *_scheme_impl.hpp classes around them need the dynamic-stage machinery (Boost proper) and do
  *      not build; they are thin, and the entry points below restate their few lines of CALL SEQUENCE
  *      (cited at each one) while the reference's own templates do the arithmetic.
@@ -20,9 +24,9 @@
  *      encoders/lz4.hpp:103-113 (prefs), encoders/lz4_utils.hpp:99-173 (encode_serial),
  *      :193-274 (encode_parallel).
  *
- * Still restated only (oracle/sqy_oracle.*): the quantiser's Lloyd-Max LUT (quantiser_utils.hpp needs
- * Boost.StringAlgo through string_parsers.hpp), frame_shuffle and tile_shuffle (Boost.Accumulators),
- * bitshuffle (its library is not in the reference tree) and the sqy header (Boost.PropertyTree).
+ * Still restated only (oracle/sqy_oracle.*): frame_shuffle and tile_shuffle (Boost.Accumulators), bitshuffle (its
+ * library is not in the reference tree), the sqy header (Boost.PropertyTree) and with it the text form of the
+ * quantiser's decode LUT.  The quantiser's LUTs themselves are the reference's (ref_quantiser_* below).
  */
 #include <cstddef>
 #include <cstdint>
@@ -51,6 +55,7 @@
 #include "encoders/bitplane_reorder_scalar.hpp"
 #include "encoders/sse_utils.hpp"
 #include "encoders/bitplane_reorder_sse.hpp"
+#include "encoders/quantiser_utils.hpp"         /* its "string_parsers.hpp" is oracle/ref_shim/'s */
 
 #include "lz4.h"
 #include "lz4frame.h"
@@ -245,6 +250,43 @@ int hist_stats(const T* in, std::size_t n, std::uint32_t* bins, double* stats)
     return 0;
 }
 
+/* quantiser (encoders/quantiser_scheme_impl.hpp:176-226): the scheme holds a default-constructed sqeazy::quantiser (:64, :72), hands it
+ * its thread count (:94) and calls setup_com on the voxels -- without a functor when the weighting string contains "none" (:186-187), else
+ * with weighters::offset_power_of(a, b) when it contains "offset" and weighters::power_of(a, b) when not (:189-196).  The codes are
+ * std::transform, or its OpenMP loop, of applyLUT over lut_encode_ (:206-223).  Histogram, weights, importance, the level count, the
+ * linear mapping and the Lloyd walk all run inside the reference's quantiser (quantiser_utils.hpp:386-418, :227-306).
+ * mode: 0 none, 1 power_of, 2 offset_power_of.  codes may be null: LUTs only. */
+typedef sqeazy::quantiser<std::uint16_t, std::uint8_t> quantiser16;
+
+int quantiser_run(const std::uint16_t* in, std::size_t n, int mode, int a, int b, int nthreads, std::uint8_t* lut_encode,
+                  std::uint16_t* lut_decode, std::uint8_t* codes)
+{
+    if (!in || !n || mode < 0 || mode > 2) return 1;
+    quantiser16 shrinker;
+    shrinker.set_n_threads(nthreads);
+    if (mode == 0)
+        shrinker.setup_com(in, in + n);
+    else if (mode == 2) {
+        sqeazy::weighters::offset_power_of w(a, b);
+        shrinker.setup_com(in, in + n, w);
+    } else {
+        sqeazy::weighters::power_of w(a, b);
+        shrinker.setup_com(in, in + n, w);
+    }
+    if (lut_encode) std::copy(shrinker.lut_encode_.begin(), shrinker.lut_encode_.end(), lut_encode);
+    if (lut_decode) std::copy(shrinker.lut_decode_.begin(), shrinker.lut_decode_.end(), lut_decode);
+    if (!codes) return 0;
+    sqeazy::applyLUT<std::uint16_t, std::uint8_t> lutApplyer(shrinker.lut_encode_);
+    if (nthreads == 1)
+        std::transform(in, in + n, codes, lutApplyer);
+    else {
+        const long len = (long)n;
+#pragma omp parallel for shared(codes) firstprivate(len, in, lutApplyer) num_threads(nthreads)
+        for (long idx = 0; idx < len; idx++) codes[idx] = lutApplyer(in[idx]);
+    }
+    return 0;
+}
+
 } /* namespace */
 
 extern "C" {
@@ -321,6 +363,18 @@ int ref_bitswap1_encode_u16(const uint16_t* in, uint16_t* out, size_t len, int n
 int ref_hist_stats(int dtype, const void* in, size_t n, uint32_t* bins, double* stats)
 {
     REF_GUARD(dtype == 1 ? hist_stats((const uint16_t*)in, n, bins, stats) : hist_stats((const uint8_t*)in, n, bins, stats))
+}
+
+/* quantiser<uint16_t, uint8_t>: lut_encode 65536 entries, lut_decode 256; mode / a / b as quantiser_run takes them */
+int ref_quantiser_luts(const uint16_t* in, size_t n, int mode, int a, int b, int nthreads, uint8_t* lut_encode, uint16_t* lut_decode)
+{
+    REF_GUARD(quantiser_run(in, n, mode, a, b, nthreads, lut_encode, lut_decode, nullptr))
+}
+
+/* the scheme's encode: n codes and the decode LUT that goes into the header */
+int ref_quantiser_encode(const uint16_t* in, size_t n, int mode, int a, int b, int nthreads, uint8_t* codes, uint16_t* lut_decode)
+{
+    REF_GUARD(quantiser_run(in, n, mode, a, b, nthreads, nullptr, lut_decode, codes))
 }
 
 static LZ4F_preferences_t make_prefs(int accel, int blocksize_id)

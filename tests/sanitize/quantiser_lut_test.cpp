@@ -2,11 +2,16 @@
 // sqy::quantiser_build_luts with the default weighting: both tables, all 65536 + 256 entries, on constructed histograms and on 1000
 // seeded random ones.  tests/test_host_encode_batch_stages.py builds and runs this with g++, sanitizers on.  Prints "quantiser_lut ok"
 // and returns 0; else the case (the seed), the table and the first differing entry, and returns 1.
+// With a directory as its argument it also reads the histograms of tests/quantiser_cases.py from it (names.txt, <index>.histo as 65536
+// uint32, <index>.enc as 65536 bytes, <index>.dec as 256 uint16: the oracle's tables, which tests/test_oracle_reference_quantiser.py
+// holds to the reference's own quantiser) and compares BOTH host routines with those tables; prints "quantiser_lut table ok".
 #include "../../sqeazy_amd/csrc/sqy_pipeline.hpp"
 #include "../../sqeazy_amd/csrc/sqy_quantiser_lut.hpp"
 
 #include <cstdio>
+#include <fstream>
 #include <random>
+#include <string>
 #include <vector>
 
 namespace {
@@ -34,6 +39,54 @@ int compare(const char* what, long seed, const std::vector<uint32_t>& histo)
     return 0;
 }
 
+template <class T>
+bool read_file(const std::string& path, std::vector<T>& into, size_t count)
+{
+    into.assign(count, T());
+    std::ifstream f(path, std::ios::binary);
+    f.read(reinterpret_cast<char*>(into.data()), (std::streamsize)(count * sizeof(T)));
+    return (size_t)f.gcount() == count * sizeof(T);
+}
+
+// 0 when both host routines give the tables the directory holds for every histogram in it
+int table(const std::string& dir)
+{
+    std::ifstream names(dir + "/names.txt");
+    std::string name;
+    int k = 0;
+    for (; std::getline(names, name); ++k) {
+        std::vector<uint32_t> histo;
+        std::vector<unsigned char> enc_want;
+        std::vector<uint16_t> dec_want;
+        const std::string stem = dir + "/" + std::to_string(k);
+        if (!read_file(stem + ".histo", histo, N) || !read_file(stem + ".enc", enc_want, N) || !read_file(stem + ".dec", dec_want, 256)) {
+            std::fprintf(stderr, "%s: cannot read the case's files\n", name.c_str());
+            return 1;
+        }
+        for (int routine = 0; routine < 2; ++routine) {
+            const char* who = routine ? "quantiser_lut_default_host" : "quantiser_build_luts";
+            std::vector<unsigned char> enc(N, 0x55);
+            uint16_t dec[256];
+            for (int i = 0; i < 256; ++i) dec[i] = 0x5555;
+            if (routine) sqy::quantiser_lut_default_host(histo.data(), enc.data(), dec);
+            else sqy::quantiser_build_luts(histo.data(), N, enc.data(), dec);
+            for (size_t i = 0; i < N; ++i)
+                if (enc[i] != enc_want[i]) {
+                    std::fprintf(stderr, "%s: %s: lut_encode[%zu] = %u, the oracle has %u\n", name.c_str(), who, i, (unsigned)enc[i], (unsigned)enc_want[i]);
+                    return 1;
+                }
+            for (size_t i = 0; i < 256; ++i)
+                if (dec[i] != dec_want[i]) {
+                    std::fprintf(stderr, "%s: %s: lut_decode[%zu] = %u, the oracle has %u\n", name.c_str(), who, i, (unsigned)dec[i], (unsigned)dec_want[i]);
+                    return 1;
+                }
+        }
+    }
+    if (!k) { std::fprintf(stderr, "no histograms in %s\n", dir.c_str()); return 1; }
+    std::printf("quantiser_lut table ok (%d histograms)\n", k);
+    return 0;
+}
+
 std::vector<uint32_t> zeros() { return std::vector<uint32_t>(N, 0); }
 
 // `levels` occupied bins spread over [lo, hi], counts 1 .. max_count
@@ -53,8 +106,9 @@ std::vector<uint32_t> spread(std::mt19937_64& rng, uint32_t lo, uint32_t hi, uin
 }
 }
 
-int main()
+int main(int argc, char** argv)
 {
+    if (argc > 1) return table(argv[1]);
     int bad = 0;
     bad += compare("all zero", -1, zeros());
     for (uint32_t at : {0u, 65535u, 31000u, 63u, 64u}) {

@@ -2,6 +2,9 @@
 // UndefinedBehaviorSanitizer, on the CPU.  tests/test_oracle_reference_stages_san.py writes the table's inputs with
 // oracle.gen_golden.dump_stage_cases (cases.txt + <index>.bin) and runs this on the directory: every case the goldens were taken from
 // runs with 1 and 3 threads (1 only where the table says so), the two outputs must be equal, and the lossless stages must decode back.
+// The same directory holds two volumes of tests/quantiser_cases.py (quantiser.txt: name and voxel count per line, quantiser_<index>.bin):
+// the reference's quantiser builds its LUTs from them and encodes them, with the default weighting and both weighting functors, 1 and 3
+// threads; the tables must not depend on the thread count and every code must be the encode LUT's entry of its voxel.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -20,6 +23,8 @@ int ref_zcurve_reorder(int dtype, const void* in, void* out, const size_t* shape
 int ref_raster_reorder(int dtype, const void* in, void* out, const size_t* shape, size_t tile, int decode, int nthreads);
 int ref_bitswap1(int dtype, const void* in, void* out, size_t len, int decode, int nthreads);
 int ref_hist_stats(int dtype, const void* in, size_t n, uint32_t* bins, double* stats);
+int ref_quantiser_luts(const uint16_t* in, size_t n, int mode, int a, int b, int nthreads, uint8_t* lut_encode, uint16_t* lut_decode);
+int ref_quantiser_encode(const uint16_t* in, size_t n, int mode, int a, int b, int nthreads, uint8_t* codes, uint16_t* lut_decode);
 }
 
 namespace {
@@ -57,6 +62,23 @@ int run(const std::string& stage, int dt, const void* in, void* out, const size_
     if (stage == "raster_reorder") return ref_raster_reorder(dt, in, out, shape, (size_t)p0, decode, nthreads);
     if (stage == "bitswap1") return ref_bitswap1(dt, in, out, len, decode, nthreads);
     return -1;
+}
+
+// 0, or what went wrong with one volume under one weighting (mode 0: none, 1: power_of_a_b, 2: offset_power_of_a_b)
+int quantiser_case(const uint16_t* vox, size_t n, int mode, int a, int b)
+{
+    buffer enc1(65536, 0), enc3(65536, 0), dec1(512, 0), dec3(512, 0), dec_e(512, 0), codes1(n, 0), codes3(n, 0);
+    uint16_t* d1 = reinterpret_cast<uint16_t*>(dec1.data());
+    uint16_t* d3 = reinterpret_cast<uint16_t*>(dec3.data());
+    uint16_t* de = reinterpret_cast<uint16_t*>(dec_e.data());
+    if (ref_quantiser_luts(vox, n, mode, a, b, 1, enc1.data(), d1)) return 20;
+    if (ref_quantiser_luts(vox, n, mode, a, b, 3, enc3.data(), d3)) return 21;
+    if (std::memcmp(enc1.data(), enc3.data(), 65536) || std::memcmp(d1, d3, 512)) return 22;
+    if (ref_quantiser_encode(vox, n, mode, a, b, 1, codes1.data(), de) || std::memcmp(d1, de, 512)) return 23;
+    if (ref_quantiser_encode(vox, n, mode, a, b, 3, codes3.data(), de) || std::memcmp(d1, de, 512)) return 24;
+    for (size_t i = 0; i < n; ++i)
+        if (codes1.data()[i] != enc1.data()[vox[i]] || codes3.data()[i] != codes1.data()[i]) return 25;
+    return 0;
 }
 
 }  // namespace
@@ -104,5 +126,24 @@ int main(int argc, char** argv)
         if (rc) { std::printf("FAILED %s rc=%d\n", id.c_str(), rc); ++bad; }
     }
     std::printf("ref_stages_san: %d cases, %d failed\n", k, bad);
+    std::ifstream qtable(dir + "/quantiser.txt");
+    int q = 0, qbad = 0;
+    for (; std::getline(qtable, line); ++q) {
+        std::istringstream is(line);
+        std::string name;
+        size_t n;
+        if (!(is >> name >> n) || !n) return 5;
+        buffer vox(n * 2, 0);
+        std::ifstream f(dir + "/quantiser_" + std::to_string(q) + ".bin", std::ios::binary);
+        f.read(reinterpret_cast<char*>(vox.data()), (std::streamsize)(n * 2));
+        if ((size_t)f.gcount() != n * 2) return 6;
+        const int weightings[3][3] = {{0, 1, 1}, {1, 1, 2}, {2, 2, 3}};
+        for (const auto& w : weightings) {
+            const int rc = quantiser_case(reinterpret_cast<const uint16_t*>(vox.data()), n, w[0], w[1], w[2]);
+            if (rc) { std::printf("FAILED quantiser %s mode=%d rc=%d\n", name.c_str(), w[0], rc); ++qbad; }
+        }
+    }
+    std::printf("ref_stages_san: %d quantiser volumes, %d failed\n", q, qbad);
+    bad += qbad;
     return bad ? 1 : 0;
 }

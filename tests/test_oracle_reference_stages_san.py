@@ -1,6 +1,7 @@
 """The reference driver over the whole stage case table under AddressSanitizer + UndefinedBehaviorSanitizer, on the CPU: a stand-alone
 program (tests/sanitize/ref_stages_san.cpp + oracle/ref_driver.cpp, built here with g++) that runs every case the goldens of
-tests/golden/ref_stages.json were taken from, with 1 and 3 threads.  A case on which the reference reads or writes out of bounds is
+tests/golden/ref_stages.json were taken from, with 1 and 3 threads, and the reference's quantiser on two volumes of
+tests/quantiser_cases.py (LUTs and codes, the default weighting and both weighting functors).  A case on which the reference reads or writes out of bounds is
 marked `undefined` in the table of oracle/gen_golden.py and is not among them.  Needs the reference tree: the program is built from it here.
 
 UBSan's `shift` check is off, for two habits of the reference that it reports on every run and that change no result here:
@@ -41,3 +42,4 @@ def test_reference_driver_over_the_table_under_asan_ubsan(tmp_path):
     assert r.returncode not in (97, 98) and r.returncode >= 0, (r.returncode, r.stderr[-3000:])
     assert "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-3000:]
     assert r.returncode == 0 and ("ref_stages_san: %d cases, 0 failed" % n) in r.stdout, (r.stdout[-2000:], r.stderr[-2000:])
+    assert ("ref_stages_san: %d quantiser volumes, 0 failed" % len(gen_golden.QUANTISER_SAN_CASES)) in r.stdout, r.stdout[-2000:]
