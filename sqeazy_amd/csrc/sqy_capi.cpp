@@ -2342,23 +2342,24 @@ int decode_from_host(const char* src, long srclength, char* dst, int elem_size)
     });
 }
 
-// ---- z-slab blob sets (SQYAMD_Decode_Slabs_*) ----------------------------------------------------------------------------------
-// Blobs in the chunked LZ4 layout are decoded in groups: the frame ranking of every blob of a group in one launch per kernel, one read-back,
-// one joint block index and one LZ4 decode launch for all of them, then each blob's remaining inverses (bitswap1, diff3x3x1, ..) from the
-// group's LZ4 output into its place.  Every other blob -- and every blob of a group whose decode raised the error flag -- goes through
-// decode_on_device, one at a time.
+// ---- z-slab blob sets (SQYAMD_Decode_Slabs_*) and batches (SQYAMD_Decode_Batch_*): a group on the joint path -----------------
+// Blobs in the chunked LZ4 layout are decoded in groups.  What both callers share, one function per step: the frame ranking of every blob
+// of a group in one launch per kernel and one read-back (group_rank), one joint block index and one LZ4 decode launch for all of them
+// (group_lz4_decode), a blob's remaining inverses from the group's LZ4 output into its place (group_remaining_stages), one verdict
+// read-back (group_verdict).  The caller (decode_slabs_group, decode_batch_group) says where the LZ4 output goes, what follows the decode
+// and under which names the launches are profiled.  Every other blob -- and every blob of a group whose decode raised the error flag --
+// goes through decode_on_device, one at a time.  The tables' layouts: sqy::decode_rank_layout, decode_joint_layout (sqy_pipeline.cpp).
 constexpr uint64_t kSlabsHeadPrefix = 1ull << 16;       // bytes of every blob fetched for its header at first
 
 struct SlabBlob : sqy::Lz4DecodeGeometry {              // (of the LZ4 stage's input, on the joint path)
     const uint8_t* src = nullptr;
-    uint64_t len = 0, src_off = 0;
+    uint64_t len = 0;
     sqy::HeaderInfo h;
     uint64_t raw = 0, dst_off = 0;
     // the joint path: the LZ4 stage's input to the decoder (total bytes, chunks), where its output goes
     std::unique_ptr<DecodeCall> call;
     size_t li = 0;
-    uint64_t total = 0;
-    uint64_t out_base = 0, map_off = 0, fs_bytes = 0;
+    uint64_t total = 0, out_base = 0, map_off = 0, fs_bytes = 0;
     bool remap = false;
     int rc = 0;
     std::vector<unsigned char> lut;                     // a batch's `quantiser->bitswap1->lz4` blob on the joint path: its decode table
@@ -2366,255 +2367,274 @@ struct SlabBlob : sqy::Lz4DecodeGeometry {              // (of the LZ4 stage's i
 
 uint64_t align_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
 
-// What SQYAMD_Decode_Batch_* makes of a group (decode_slab_group's `batch`; nullptr: a slab set).  Every destination is an allocation of its
-// own, so the group's LZ4 output always goes to the workspace, laid out by the plan (SlabBlob::out_base is the plan's out_at), and behind
-// the LZ4 decode the `bitswap1->lz4` blobs share one launch of the batched inverse transposer and the `lz4` blobs one of the batched copy
-// (the plan's tile tables); the `quantiser->bitswap1->lz4` blobs one of the transposer with the look-up, their tables uploaded with the job
-// tables; the 16-bit `diff3x3x1->bitswap1->lz4` and `diff3x3x1->lz4` blobs in the chain geometry one launch per chain step for all of them
-// (launch_diff3x3x1_decode_batch_copy, _step), the former's inverse transposes in the `bitswap1->lz4` blobs' launch, into the workspace.  Every other
-// pipeline runs its remaining inverses blob by blob, as in a slab set.
-struct BatchGroup {
-    const std::vector<sqy::DecodeBatchBlob>* plan_in;   // what the plan was made from: made again, with the dropped blobs named, when the ranking refuses one
-    uint64_t group_bytes;
-    size_t group;                                       // this group's index in the plan
-    const sqy::DecodeBatchGroup* g;
-    int elem_size;
+struct GroupNames { const char *frame_index, *lz4_decode; };                // the profile names of a group's two shared launches
+constexpr GroupNames kSlabsNames{"slabs_frame_index", "slabs_lz4_decode"}, kBatchNames{"batch_frame_index", "batch_lz4_decode"};
+
+// A group on its way through the steps
+struct JointGroup {
+    Context& cx;
+    const uint8_t* d_src;
+    std::vector<SlabBlob>& blobs;
+    hipStream_t stream;
+    GroupNames names;
+    // group_rank: who stays (slab order) and each one's block index, the maps of those with SlabBlob::remap; their frames in all, the compressed
+    // ones, the most of one blob; the error flag
+    std::vector<size_t> mem;
+    std::vector<const void*> blk_of;
+    std::vector<unsigned char> maps;
+    uint64_t nframes = 0, ncompressed = 0, max_frames = 0;
+    uint32_t* flag = nullptr;
+    std::vector<unsigned char> up;          // group_lz4_decode: the pageable source of its upload, alive until group_verdict's synchronisation
+    uint8_t* out = nullptr;                 // the caller: where the LZ4 output goes -- blob b's at out + blobs[b].out_base, out_bytes in all
+    uint64_t out_bytes = 0;
 };
 
-// The joint path for blobs g[0..m) (slab order).  Blobs it cannot take are appended to `single`; the flag raised: all of g go there.
-int decode_slab_group(Context& cx, const uint8_t* d_src, std::vector<SlabBlob>& blobs, const std::vector<size_t>& g, uint8_t* d_dst,
-                      uint64_t volume_bytes, hipStream_t stream, std::vector<size_t>& single, const BatchGroup* batch = nullptr)
+// The frame ranking of blobs g[0..m) and its read-back.  Who stays (G.mem): ranked without complaint, one frame per chunk -- with them
+// whether their frame_shuffle folds into the decode (SlabBlob::remap, fs_bytes; G.maps).  Anything else -- code 100, an error, a stored tail
+// the ranking gave up on -- is appended to `single`, where the single-blob index gets the last word; so is everybody when the frames are
+// more than the joint index counts.
+int group_rank(JointGroup& G, const std::vector<size_t>& g, std::vector<size_t>& single)
 {
-    Workspace* ws = &cx.ws;
-    std::vector<PendingEvent>* pend = &cx.pending;
+    Workspace* ws = &G.cx.ws;
+    std::vector<PendingEvent>* pend = &G.cx.pending;
+    hipStream_t stream = G.stream;
     const uint32_t m = (uint32_t)g.size();
-    // 1. every blob's frame ranking: scratch | block index | frame starts per blob, then the counts (16 words each) and the group's flag
-    std::vector<uint64_t> at(m);
-    uint64_t bytes = 0;
-    for (uint32_t k = 0; k < m; ++k) {
-        const SlabBlob& b = blobs[g[k]];
-        at[k] = bytes;
-        bytes += align_up(sqy::lz4_frame_rank_scratch_bytes(b.nchunks), 256) + align_up(b.max_blocks * 16, 256) + align_up((b.max_blocks + 2) * 4, 256);
-    }
-    const uint64_t o_counts = bytes, o_desc = align_up(o_counts + (uint64_t)m * 64 + 64, 256);
-    if (ws->slabs_index.ensure(o_desc + sqy::lz4_frame_rank_batch_desc_bytes(m))) return 1;
+    std::vector<sqy::DecodeRankBlob> sizes(m);
+    for (uint32_t k = 0; k < m; ++k) sizes[k] = sqy::DecodeRankBlob{sqy::lz4_frame_rank_scratch_bytes(G.blobs[g[k]].nchunks), G.blobs[g[k]].max_blocks};
+    const sqy::DecodeRankLayout L = sqy::decode_rank_layout(sizes, sqy::lz4_frame_rank_batch_desc_bytes(m));
+    if (ws->slabs_index.ensure(L.total)) return 1;
     uint8_t* di = static_cast<uint8_t*>(ws->slabs_index.p);
-    uint32_t* counts = reinterpret_cast<uint32_t*>(di + o_counts);
-    uint32_t* flag = counts + 16 * m;
+    uint32_t* counts = reinterpret_cast<uint32_t*>(di + L.counts_at);
+    G.flag = reinterpret_cast<uint32_t*>(di + L.flag_at);
+    const bool tail = g_opt.stored_tail_index.load() != 0;                 // (the stored tail looked for where it must start, as lz4_index does)
     std::vector<sqy::Lz4RankJob> jobs(m);
     for (uint32_t k = 0; k < m; ++k) {
-        const SlabBlob& b = blobs[g[k]];
+        const SlabBlob& b = G.blobs[g[k]];
         sqy::Lz4RankJob& j = jobs[k];
-        uint8_t* p = di + at[k];
-        j.scratch = p;
-        p += align_up(sqy::lz4_frame_rank_scratch_bytes(b.nchunks), 256);
-        j.blk = p;
-        j.frame_first = reinterpret_cast<uint32_t*>(p + align_up(b.max_blocks * 16, 256));
-        j.in = b.call->cur;
-        j.n = b.call->cur_bytes;
-        j.max_blocks = b.max_blocks;
-        j.counts = counts + 16 * k;
-        j.expected_frames = b.nchunks;
-        const bool tail = g_opt.stored_tail_index.load() != 0;             // (the stored tail looked for where it must start, as lz4_index does)
-        j.chunk = tail ? b.chunk : 0;
-        j.last = tail ? b.total - (b.nchunks - 1) * b.chunk : 0;
+        j.in = b.call->cur; j.n = b.call->cur_bytes;
+        j.scratch = di + L.blobs[k].scratch_at; j.blk = di + L.blobs[k].blk_at;
+        j.frame_first = reinterpret_cast<uint32_t*>(di + L.blobs[k].frame_first_at);
+        j.max_blocks = b.max_blocks; j.expected_frames = b.nchunks; j.counts = counts + 16 * k;
+        j.chunk = tail ? b.chunk : 0; j.last = tail ? b.total - (b.nchunks - 1) * b.chunk : 0;
     }
     std::vector<unsigned char> hdesc(sqy::lz4_frame_rank_batch_desc_bytes(m));
-    SQY_HIP(hipMemsetAsync(flag, 0, 64, stream));
-    SQY_TIMED(batch ? "batch_frame_index" : "slabs_frame_index", sqy::launch_lz4_frame_rank_batch(jobs.data(), m, di + o_desc, hdesc.data(), stream));
+    SQY_HIP(hipMemsetAsync(G.flag, 0, 64, stream));
+    SQY_TIMED(G.names.frame_index, sqy::launch_lz4_frame_rank_batch(jobs.data(), m, di + L.desc_at, hdesc.data(), stream));
     if (ws->slabs_host.ensure((size_t)m * 64)) return 1;
     const uint32_t* hc_all = static_cast<const uint32_t*>(ws->slabs_host.p);
     SQY_HIP(hipMemcpyAsync(ws->slabs_host.p, counts, (size_t)m * 64, hipMemcpyDeviceToHost, stream));
     SQY_HIP(hipStreamSynchronize(stream));
-
-    // 2. who stays: ranked without complaint, one frame per chunk (anything else -- code 100, an error, a stored tail the ranking gave up
-    // on -- is decoded on its own, where the single-blob index gets the last word)
-    std::vector<size_t> mem;
-    std::vector<uint32_t> hc3;
-    std::vector<const void*> blk_of;
     for (uint32_t k = 0; k < m; ++k) {
         const uint32_t* hc = hc_all + 16 * k;
-        if (hc[2] != 0 || hc[0] != blobs[g[k]].nchunks) { single.push_back(g[k]); continue; }
-        mem.push_back(g[k]);
-        hc3.push_back(hc[3]);
-        blk_of.push_back(jobs[k].blk);
-    }
-    if (mem.empty()) return 0;
-
-    // 3. where each blob's LZ4 output goes: straight into its place in the volume when the LZ4 stage's inverse produces the volume for
-    // every blob of the group (lz4, frame_shuffle->lz4, behind the background heads) and the places are 16-byte aligned, else the workspace
-    std::vector<unsigned char> maps;
-    bool direct = batch == nullptr;
-    for (size_t b : mem) {
-        SlabBlob& s = blobs[b];
-        DecodeCall& c = *s.call;
+        SlabBlob& s = G.blobs[g[k]];
+        if (hc[2] != 0 || hc[0] != s.nchunks) { single.push_back(g[k]); continue; }
+        G.mem.push_back(g[k]);
+        G.blk_of.push_back(jobs[k].blk);
+        G.nframes += s.nchunks; G.ncompressed += hc[3]; G.max_frames = std::max(G.max_frames, s.nchunks);
         s.remap = false;
         uint64_t Z = 0, fb = 0;
         bool permutation = true;
-        if (c.shuffle_fold(s.li, s.total, s, s.nchunks, false, Z, fb, permutation, &s.remap) == 0 && s.remap) {
+        if (s.call->shuffle_fold(s.li, s.total, s, s.nchunks, false, Z, fb, permutation, &s.remap) == 0 && s.remap) {
             s.fs_bytes = fb;
-            s.map_off = maps.size();
-            maps.insert(maps.end(), c.fs_map.begin(), c.fs_map.begin() + Z * 8);
+            s.map_off = G.maps.size();
+            G.maps.insert(G.maps.end(), s.call->fs_map.begin(), s.call->fs_map.begin() + Z * 8);
         }
-        const size_t first_after = s.remap ? s.li - 1 : s.li;           // the stage whose inverse the LZ4 decode completes
-        if (first_after > c.lead || ((reinterpret_cast<uintptr_t>(d_dst) + s.dst_off) & 15) != 0) direct = false;
     }
-    uint64_t out_bytes = 0;
-    for (size_t b : mem) {
-        SlabBlob& s = blobs[b];
-        if (direct) s.out_base = s.dst_off;
-        else if (!batch) { s.out_base = out_bytes; out_bytes = align_up(out_bytes + s.total, 256); }
-    }
-    if (direct) out_bytes = volume_bytes;
-    if (batch) out_bytes = batch->g->out_bytes;
-    uint8_t* out = direct ? d_dst : nullptr;
-    if (!direct) {
-        if (ws->slabs_out.ensure(std::max<uint64_t>(out_bytes, 16))) return 1;
-        out = static_cast<uint8_t*>(ws->slabs_out.p);
-    }
+    if (G.nframes > 0x7fffffffull) { single.insert(single.end(), G.mem.begin(), G.mem.end()); G.mem.clear(); }
+    return 0;
+}
 
-    // 4. the joint index and the one decode launch: parts | maps | joint blk | joint frame starts | frame output table
-    const uint32_t np = (uint32_t)mem.size();
-    uint64_t jn = 0, ncomp = 0;
-    uint32_t maxf = 0;
-    for (uint32_t k = 0; k < np; ++k) { jn += blobs[mem[k]].nchunks; ncomp += hc3[k]; maxf = std::max<uint32_t>(maxf, (uint32_t)blobs[mem[k]].nchunks); }
-    if (jn > 0x7fffffffull) { for (size_t b : mem) single.push_back(b); return 0; }
-    const uint64_t o_maps = align_up(np * sizeof(sqy::Lz4JointPart), 256), o_jblk = align_up(o_maps + maps.size(), 256),
-                   o_jff = o_jblk + jn * 16, o_jout = align_up(o_jff + (jn + 1) * 4, 256);
-    // (batch: behind them what the launches that follow the LZ4 decode read -- job lists, tile and strip tables, the quantiser blobs' LUTs --,
-    // one region of 256-byte aligned parts, uploaded at once; the plan made again without the blobs the ranking refused)
-    const sqy::DecodeBatchGroup* pg = batch ? batch->g : nullptr;
-    sqy::DecodeBatchPlan again;
-    if (batch && mem.size() != g.size()) {
-        std::vector<uint8_t> dropped(blobs.size(), 0);
-        for (size_t b : g) dropped[b] = 1;
-        for (size_t b : mem) dropped[b] = 0;
-        again = sqy::decode_batch_plan(*batch->plan_in, batch->group_bytes, &dropped);
-        pg = &again.groups[batch->group];
-    }
-    struct TablePart { uint64_t jobs_at = 0, tiles_at = 0, extra_at = 0; };           // (extra: the LUTs | the diff jobs' tile table)
-    TablePart part[4];                                                                // planes, plain, quantised, diff
-    uint64_t jobs_bytes = 0;
-    if (batch) {
-        const sqy::DecodeBatchTiles* tt[3] = {&pg->planes, &pg->plain, &pg->quantised};
-        for (int k = 0; k < 3; ++k) {
-            const uint64_t nj = tt[k]->jobs.size();
-            part[k].jobs_at = jobs_bytes;
-            part[k].tiles_at = part[k].jobs_at + nj * sizeof(sqy::Bitswap1Job);
-            part[k].extra_at = align_up(part[k].tiles_at + (nj + 1) * 4, 256);
-            jobs_bytes = k == 2 ? part[k].extra_at + nj * 512 : part[k].extra_at;
-        }
-        const uint64_t nd = pg->diff.jobs.size();
-        part[3].jobs_at = align_up(jobs_bytes, 256);
-        part[3].tiles_at = part[3].jobs_at + nd * sizeof(sqy::DiffBatchJob);             // (first_strip)
-        part[3].extra_at = part[3].tiles_at + (nd + 1) * 4;                              // (first_tile)
-        jobs_bytes = align_up(part[3].extra_at + (nd + 1) * 4, 256);
-    }
-    const uint64_t o_jobs = align_up(o_jout + jn * 16, 256);
-    if (ws->slabs_joint.ensure(batch ? o_jobs + jobs_bytes : o_jout + jn * 16)) return 1;
-    uint8_t* dj = static_cast<uint8_t*>(ws->slabs_joint.p);
-    std::vector<unsigned char> up(o_maps + maps.size());
+// The joint index -- a part per blob and the maps from the host, the rest built by the launch -- and the one LZ4 decode launch into G.out
+int group_lz4_decode(JointGroup& G, const sqy::DecodeJointLayout& L)
+{
+    std::vector<PendingEvent>* pend = &G.cx.pending;
+    hipStream_t stream = G.stream;
+    if (G.cx.ws.slabs_joint.ensure(L.total)) return 1;
+    uint8_t* dj = static_cast<uint8_t*>(G.cx.ws.slabs_joint.p);
+    const uint32_t np = (uint32_t)G.mem.size();
+    G.up.assign(L.upload_bytes, 0);
     for (uint32_t k = 0, jbase = 0; k < np; ++k) {
-        const SlabBlob& s = blobs[mem[k]];
+        const SlabBlob& s = G.blobs[G.mem[k]];
         sqy::Lz4JointPart pt{};
-        pt.blk = blk_of[k];
-        pt.in_off = (uint64_t)(s.call->cur - d_src);
-        pt.out_base = s.out_base;
-        pt.chunk = s.chunk;
-        pt.total = s.total;
-        pt.remap = s.remap ? reinterpret_cast<const uint64_t*>(dj + o_maps + s.map_off) : nullptr;
+        pt.blk = G.blk_of[k]; pt.in_off = (uint64_t)(s.call->cur - G.d_src);
+        pt.out_base = s.out_base; pt.chunk = s.chunk; pt.total = s.total;
+        pt.remap = s.remap ? reinterpret_cast<const uint64_t*>(dj + L.maps_at + s.map_off) : nullptr;
         pt.remap_bytes = s.remap ? s.fs_bytes : 0;
-        pt.jbase = jbase;
-        pt.nframes = (uint32_t)s.nchunks;
-        std::memcpy(up.data() + k * sizeof(pt), &pt, sizeof(pt));
-        jbase += (uint32_t)s.nchunks;
+        pt.jbase = jbase; pt.nframes = (uint32_t)s.nchunks;
+        std::memcpy(G.up.data() + L.parts_at + k * sizeof(pt), &pt, sizeof(pt));
+        jbase += pt.nframes;
     }
-    if (!maps.empty()) std::memcpy(up.data() + o_maps, maps.data(), maps.size());
-    SQY_HIP(hipMemcpyAsync(dj, up.data(), up.size(), hipMemcpyHostToDevice, stream));
-    for (size_t b : mem) {                                              // frames nobody names come out as zeros (frame_shuffle's inverse)
-        SlabBlob& s = blobs[b];
+    if (!G.maps.empty()) std::memcpy(G.up.data() + L.maps_at, G.maps.data(), G.maps.size());
+    SQY_HIP(hipMemcpyAsync(dj, G.up.data(), G.up.size(), hipMemcpyHostToDevice, stream));
+    for (size_t b : G.mem) {                                            // frames nobody names come out as zeros (frame_shuffle's inverse)
+        SlabBlob& s = G.blobs[b];
         if (s.remap && !s.call->fs_unnamed.empty())
-            if (const int rc = s.call->zero_unnamed_places(out + s.out_base, s.fs_bytes, s.total)) return rc;
+            if (const int rc = s.call->zero_unnamed_places(G.out + s.out_base, s.fs_bytes, s.total)) return rc;
     }
-    const bool side_ok = cx.ensure_side();
-    SQY_TIMED(batch ? "batch_lz4_decode" : "slabs_lz4_decode",
-              sqy::launch_lz4_frames_joint_decode(d_src, reinterpret_cast<const sqy::Lz4JointPart*>(dj), np, maxf, dj + o_jblk,
-                                                  reinterpret_cast<uint32_t*>(dj + o_jff), reinterpret_cast<uint64_t*>(dj + o_jout), (uint32_t)jn, out,
-                                                  out_bytes, blobs[mem[0]].block_bytes, (uint32_t)std::min<uint64_t>(ncomp, 0xffffffffull), flag, stream,
-                                                  side_ok ? cx.side : nullptr, cx.fork, cx.join, g_opt.decode_two_waves.load() != 0));
+    const bool side_ok = G.cx.ensure_side();
+    SQY_TIMED(G.names.lz4_decode,
+              sqy::launch_lz4_frames_joint_decode(G.d_src, reinterpret_cast<const sqy::Lz4JointPart*>(dj + L.parts_at), np, (uint32_t)G.max_frames, dj + L.jblk_at,
+                                                  reinterpret_cast<uint32_t*>(dj + L.jff_at), reinterpret_cast<uint64_t*>(dj + L.jout_at), (uint32_t)G.nframes,
+                                                  G.out, G.out_bytes, G.blobs[G.mem[0]].block_bytes, (uint32_t)std::min<uint64_t>(G.ncompressed, 0xffffffffull), G.flag,
+                                                  stream, side_ok ? G.cx.side : nullptr, G.cx.fork, G.cx.join, g_opt.decode_two_waves.load() != 0));
+    return 0;
+}
 
-    // 5. every blob's remaining inverses, from its LZ4 output into its place
+// The remaining inverses of the blobs `who`, blob by blob, from the group's LZ4 output into their places
+int group_remaining_stages(JointGroup& G, const std::vector<size_t>& who)
+{
     bool first = true;
-    std::vector<unsigned char> job_tables;                              // (alive until the verdict's synchronisation)
-    if (batch) {
-        // the `bitswap1->lz4` blobs: ONE inverse-transpose launch from the workspace into their destinations -- and into the workspace for the
-        // `diff3x3x1->bitswap1->lz4` blobs --; the `lz4` blobs: ONE copy launch; the `quantiser->bitswap1->lz4` blobs: ONE launch of the
-        // transposer with the look-up; the diff blobs: ONE launch per chain step
-        job_tables.assign(jobs_bytes, 0);
-        const sqy::DecodeBatchDiff& df = pg->diff;
-        auto form_of = [&](uint32_t b) { return (*batch->plan_in)[b].form; };
-        std::vector<uint64_t> res_of(blobs.size(), 0);                  // a diff blob's residual volume in the workspace
-        for (size_t j = 0; j < df.jobs.size(); ++j) res_of[df.jobs[j]] = df.res_at[j];
-        const sqy::DecodeBatchTiles* tt[3] = {&pg->planes, &pg->plain, &pg->quantised};
-        for (int k = 0; k < 3; ++k) {
-            const uint32_t nj = (uint32_t)tt[k]->jobs.size();
-            for (uint32_t j = 0; j < nj; ++j) {
-                const uint32_t b = tt[k]->jobs[j];
-                const SlabBlob& s = blobs[b];
-                void* to = form_of(b) == sqy::DecodeBatchForm::diff_planes ? static_cast<void*>(out + res_of[b]) : s.call->d_dst;
-                const sqy::Bitswap1Job job{out + s.out_base, to, (*batch->plan_in)[b].len};
-                std::memcpy(job_tables.data() + part[k].jobs_at + j * sizeof(job), &job, sizeof(job));
-                if (k == 2) std::memcpy(job_tables.data() + part[k].extra_at + (size_t)j * 512, s.lut.data(), 512);
-            }
-            std::memcpy(job_tables.data() + part[k].tiles_at, tt[k]->first_tile.data(), ((size_t)nj + 1) * 4);
-        }
-        const uint32_t nd = (uint32_t)df.jobs.size();
-        for (uint32_t j = 0; j < nd; ++j) {
-            const SlabBlob& s = blobs[df.jobs[j]];
-            const sqy::DecodeBatchBlob& p = (*batch->plan_in)[df.jobs[j]];
-            const sqy::DiffBatchJob job{out + df.res_at[j], s.call->d_dst, p.Z, p.Y, p.X, p.chain_columns};
-            std::memcpy(job_tables.data() + part[3].jobs_at + j * sizeof(job), &job, sizeof(job));
-        }
-        std::memcpy(job_tables.data() + part[3].tiles_at, df.first_strip.data(), ((size_t)nd + 1) * 4);
-        std::memcpy(job_tables.data() + part[3].extra_at, df.first_tile.data(), ((size_t)nd + 1) * 4);
-        uint8_t* dt = dj + o_jobs;
-        if (jobs_bytes) SQY_HIP(hipMemcpyAsync(dt, job_tables.data(), jobs_bytes, hipMemcpyHostToDevice, stream));
-        auto jobs_at = [&](int k) { return reinterpret_cast<const sqy::Bitswap1Job*>(dt + part[k].jobs_at); };
-        auto tiles_at = [&](int k) { return reinterpret_cast<const uint32_t*>(dt + part[k].tiles_at); };
-        if (pg->planes.ntiles)
-            SQY_TIMED("batch_bitswap1_decode", sqy::launch_bitswap1_decode_batch(jobs_at(0), tiles_at(0), (uint32_t)pg->planes.jobs.size(), pg->planes.ntiles, batch->elem_size, stream));
-        if (pg->plain.ntiles) SQY_TIMED("batch_copy", sqy::launch_batch_copy(jobs_at(1), tiles_at(1), (uint32_t)pg->plain.jobs.size(), pg->plain.ntiles, stream));
-        if (pg->quantised.ntiles)
-            SQY_TIMED("batch_quantiser_decode", sqy::launch_bitswap1_quantiser_decode_batch(jobs_at(2), tiles_at(2), reinterpret_cast<const uint16_t*>(dt + part[2].extra_at),
-                                                                                             (uint32_t)pg->quantised.jobs.size(), pg->quantised.ntiles, stream));
-        if (nd) {
-            // (every launch timed on its own: the profile counts the launches, 1 + steps whatever the number of blobs)
-            const sqy::DiffBatchJob* d_diff = reinterpret_cast<const sqy::DiffBatchJob*>(dt + part[3].jobs_at);
-            SQY_TIMED("batch_diff3x3x1_decode", sqy::launch_diff3x3x1_decode_batch_copy(d_diff, reinterpret_cast<const uint32_t*>(dt + part[3].extra_at), nd, df.ntiles, stream));
-            for (uint32_t step = 0; step < df.steps; ++step)
-                SQY_TIMED("batch_diff3x3x1_decode", sqy::launch_diff3x3x1_decode_batch_step(d_diff, tiles_at(3), nd, df.nstrips, step, df.max_columns, stream));
-        }
-    }
-    for (size_t b : mem) {
-        SlabBlob& s = blobs[b];
+    for (size_t b : who) {
+        SlabBlob& s = G.blobs[b];
         DecodeCall& c = *s.call;
-        if (batch && (*batch->plan_in)[b].form != sqy::DecodeBatchForm::stages) continue;       // (done above)
         // (the quantiser's table goes to ws->small by a synchronous copy: the blob before must be done with it)
-        if (!first) for (const Stage& st : c.pipe.stages) if (st.kind == StageKind::quantiser) { SQY_HIP(hipStreamSynchronize(stream)); break; }
+        if (!first) for (const Stage& st : c.pipe.stages) if (st.kind == StageKind::quantiser) { SQY_HIP(hipStreamSynchronize(G.stream)); break; }
         first = false;
-        c.cur = out + s.out_base;
+        c.cur = G.out + s.out_base;
         c.cur_bytes = s.total;
         if (const int rc = decode_stages(c, s.remap ? s.li - 1 : s.li)) { s.rc = rc; continue; }
-        if (c.cur != c.d_dst) SQY_HIP(hipMemcpyAsync(c.d_dst, c.cur, s.raw, hipMemcpyDeviceToDevice, stream));
-    }
-    // 6. the decoder's verdict, one read-back for the group
-    bool raised = false;
-    if (const int rc = lz4_verdict(cx, flag, stream, &raised)) return rc;
-    if (raised) {
-        // a damaged frame somewhere in the group: every blob of it again on its own, which gives each one its exact code
-        for (size_t b : mem) { blobs[b].rc = 0; single.push_back(b); }
+        if (c.cur != c.d_dst) SQY_HIP(hipMemcpyAsync(c.d_dst, c.cur, s.raw, hipMemcpyDeviceToDevice, G.stream));
     }
     return 0;
+}
+
+// The decoder's verdict, one read-back for the group.  The flag raised -- a damaged frame somewhere in the group --: every blob of it again
+// on its own (appended to `single`), which gives each one its exact code
+int group_verdict(JointGroup& G, std::vector<size_t>& single)
+{
+    bool raised = false;
+    if (const int rc = lz4_verdict(G.cx, G.flag, G.stream, &raised)) return rc;
+    if (raised) for (size_t b : G.mem) { G.blobs[b].rc = 0; single.push_back(b); }
+    return 0;
+}
+
+// The joint path for slabs g[0..m) of a slab set (slab order).  Blobs it cannot take are appended to `single`; the flag raised: all of g go
+// there.  The LZ4 output goes straight into each blob's place in the volume when the LZ4 stage's inverse produces the volume for every
+// blob of the group (lz4, frame_shuffle->lz4, behind the background heads) and the places are 16-byte aligned, else to the workspace,
+// packed here; every blob's remaining inverses (bitswap1, diff3x3x1, ..) follow the decode.
+int decode_slabs_group(Context& cx, const uint8_t* d_src, std::vector<SlabBlob>& blobs, const std::vector<size_t>& g, uint8_t* d_dst,
+                       uint64_t volume_bytes, hipStream_t stream, std::vector<size_t>& single)
+{
+    JointGroup G{cx, d_src, blobs, stream, kSlabsNames};
+    if (const int rc = group_rank(G, g, single)) return rc;
+    if (G.mem.empty()) return 0;
+    bool direct = true;
+    for (size_t b : G.mem) {
+        const SlabBlob& s = blobs[b];
+        const size_t first_after = s.remap ? s.li - 1 : s.li;           // the stage whose inverse the LZ4 decode completes
+        if (first_after > s.call->lead || ((reinterpret_cast<uintptr_t>(d_dst) + s.dst_off) & 15) != 0) direct = false;
+    }
+    if (direct) {
+        for (size_t b : G.mem) blobs[b].out_base = blobs[b].dst_off;
+        G.out = d_dst;
+        G.out_bytes = volume_bytes;
+    } else {
+        for (size_t b : G.mem) { blobs[b].out_base = G.out_bytes; G.out_bytes = align_up(G.out_bytes + blobs[b].total, 256); }
+        if (cx.ws.slabs_out.ensure(std::max<uint64_t>(G.out_bytes, 16))) return 1;
+        G.out = static_cast<uint8_t*>(cx.ws.slabs_out.p);
+    }
+    if (const int rc = group_lz4_decode(G, sqy::decode_joint_layout(G.mem.size(), G.maps.size(), G.nframes))) return rc;
+    if (const int rc = group_remaining_stages(G, G.mem)) return rc;
+    return group_verdict(G, single);
+}
+
+// What follows the LZ4 decode in a batch group (pg: its plan, sqy::decode_batch_plan's).  The tables of the launches -- job lists, tile and
+// strip tables, the quantised blobs' LUTs -- in one upload (`tables`: host memory for it, alive until the verdict's synchronisation), then
+// the `bitswap1->lz4` blobs: ONE inverse-transpose launch from the workspace into their destinations -- and into the workspace for the
+// `diff3x3x1->bitswap1->lz4` blobs --; the `lz4` blobs: ONE copy launch; the `quantiser->bitswap1->lz4` blobs: ONE launch of the transposer
+// with the look-up; the 16-bit diff3x3x1 blobs in the chain geometry: ONE launch per chain step (launch_diff3x3x1_decode_batch_copy, _step)
+int batch_group_tail(JointGroup& G, const sqy::DecodeJointLayout& L, const sqy::DecodeBatchGroup& pg, const std::vector<sqy::DecodeBatchBlob>& plan_in, int elem_size,
+                     std::vector<unsigned char>& tables)
+{
+    std::vector<PendingEvent>* pend = &G.cx.pending;
+    hipStream_t stream = G.stream;
+    tables.assign(L.jobs_bytes, 0);
+    auto host = [&](uint64_t at) { return tables.data() + (at - L.jobs_upload_at); };
+    const sqy::DecodeBatchDiff& df = pg.diff;
+    std::vector<uint64_t> res_of(G.blobs.size(), 0);                    // a diff blob's residual volume in the workspace
+    for (size_t j = 0; j < df.jobs.size(); ++j) res_of[df.jobs[j]] = df.res_at[j];
+    const sqy::DecodeBatchTiles* tt[3] = {&pg.planes, &pg.plain, &pg.quantised};
+    const sqy::DecodeJointLayout::Family* ff[3] = {&L.planes, &L.plain, &L.quantised};
+    for (int k = 0; k < 3; ++k) {
+        const size_t nj = tt[k]->jobs.size();
+        for (size_t j = 0; j < nj; ++j) {
+            const uint32_t b = tt[k]->jobs[j];
+            const SlabBlob& s = G.blobs[b];
+            void* to = plan_in[b].form == sqy::DecodeBatchForm::diff_planes ? static_cast<void*>(G.out + res_of[b]) : s.call->d_dst;
+            const sqy::Bitswap1Job job{G.out + s.out_base, to, plan_in[b].len};
+            std::memcpy(host(ff[k]->jobs_at) + j * sizeof(job), &job, sizeof(job));
+            if (tt[k] == &pg.quantised) std::memcpy(host(ff[k]->extra_at) + j * 512, s.lut.data(), 512);
+        }
+        std::memcpy(host(ff[k]->tiles_at), tt[k]->first_tile.data(), (nj + 1) * 4);
+    }
+    const uint32_t nd = (uint32_t)df.jobs.size();
+    for (uint32_t j = 0; j < nd; ++j) {
+        const sqy::DecodeBatchBlob& p = plan_in[df.jobs[j]];
+        const sqy::DiffBatchJob job{G.out + df.res_at[j], G.blobs[df.jobs[j]].call->d_dst, p.Z, p.Y, p.X, p.chain_columns};
+        std::memcpy(host(L.diff.jobs_at) + j * sizeof(job), &job, sizeof(job));
+    }
+    std::memcpy(host(L.diff.tiles_at), df.first_strip.data(), ((size_t)nd + 1) * 4);
+    std::memcpy(host(L.diff.extra_at), df.first_tile.data(), ((size_t)nd + 1) * 4);
+    uint8_t* dj = static_cast<uint8_t*>(G.cx.ws.slabs_joint.p);
+    if (L.jobs_bytes) SQY_HIP(hipMemcpyAsync(dj + L.jobs_upload_at, tables.data(), L.jobs_bytes, hipMemcpyHostToDevice, stream));
+    auto jobs = [&](const sqy::DecodeJointLayout::Family& f) { return reinterpret_cast<const sqy::Bitswap1Job*>(dj + f.jobs_at); };
+    auto words = [&](uint64_t at) { return reinterpret_cast<const uint32_t*>(dj + at); };
+    if (pg.planes.ntiles)
+        SQY_TIMED("batch_bitswap1_decode", sqy::launch_bitswap1_decode_batch(jobs(L.planes), words(L.planes.tiles_at), (uint32_t)pg.planes.jobs.size(), pg.planes.ntiles, elem_size, stream));
+    if (pg.plain.ntiles) SQY_TIMED("batch_copy", sqy::launch_batch_copy(jobs(L.plain), words(L.plain.tiles_at), (uint32_t)pg.plain.jobs.size(), pg.plain.ntiles, stream));
+    if (pg.quantised.ntiles)
+        SQY_TIMED("batch_quantiser_decode", sqy::launch_bitswap1_quantiser_decode_batch(jobs(L.quantised), words(L.quantised.tiles_at), reinterpret_cast<const uint16_t*>(dj + L.quantised.extra_at),
+                                                                                         (uint32_t)pg.quantised.jobs.size(), pg.quantised.ntiles, stream));
+    if (nd) {
+        // (every launch timed on its own: the profile counts the launches, 1 + steps whatever the number of blobs)
+        const sqy::DiffBatchJob* d_diff = reinterpret_cast<const sqy::DiffBatchJob*>(dj + L.diff.jobs_at);
+        SQY_TIMED("batch_diff3x3x1_decode", sqy::launch_diff3x3x1_decode_batch_copy(d_diff, words(L.diff.extra_at), nd, df.ntiles, stream));
+        for (uint32_t step = 0; step < df.steps; ++step)
+            SQY_TIMED("batch_diff3x3x1_decode", sqy::launch_diff3x3x1_decode_batch_step(d_diff, words(L.diff.tiles_at), nd, df.nstrips, step, df.max_columns, stream));
+    }
+    return 0;
+}
+
+// The joint path for group gi of a batch's plan (made from plan_in under the bound group_bytes).  Blobs it cannot take are appended to
+// `single`; the flag raised: all of the group go there.  Every destination is an allocation of its own, so the LZ4 output always goes to
+// the workspace, where the plan says (out_at); the pipelines without a batched launch run their remaining inverses as in a slab set.
+int decode_batch_group(Context& cx, const uint8_t* d_src, std::vector<SlabBlob>& blobs, const std::vector<sqy::DecodeBatchBlob>& plan_in, uint64_t group_bytes,
+                       const sqy::DecodeBatchPlan& plan, size_t gi, int elem_size, hipStream_t stream, std::vector<size_t>& single)
+{
+    const sqy::DecodeBatchGroup* pg = &plan.groups[gi];
+    const std::vector<size_t> g(pg->blobs.begin(), pg->blobs.end());
+    for (size_t k = 0; k < g.size(); ++k) blobs[g[k]].out_base = pg->out_at[k];
+    JointGroup G{cx, d_src, blobs, stream, kBatchNames};
+    if (const int rc = group_rank(G, g, single)) return rc;
+    if (G.mem.empty()) return 0;
+    // the plan made again without the blobs the ranking refused: they keep their place in the workspace and have no job in any table
+    sqy::DecodeBatchPlan again;
+    if (G.mem.size() != g.size()) {
+        std::vector<uint8_t> dropped(blobs.size(), 0);
+        for (size_t b : g) dropped[b] = 1;
+        for (size_t b : G.mem) dropped[b] = 0;
+        again = sqy::decode_batch_plan(plan_in, group_bytes, &dropped);
+        pg = &again.groups[gi];
+    }
+    G.out_bytes = pg->out_bytes;
+    if (cx.ws.slabs_out.ensure(std::max<uint64_t>(G.out_bytes, 16))) return 1;
+    G.out = static_cast<uint8_t*>(cx.ws.slabs_out.p);
+    const sqy::DecodeJointLayout L = sqy::decode_joint_layout(G.mem.size(), G.maps.size(), G.nframes, pg);
+    if (const int rc = group_lz4_decode(G, L)) return rc;
+    std::vector<unsigned char> tables;
+    if (const int rc = batch_group_tail(G, L, *pg, plan_in, elem_size, tables)) return rc;
+    std::vector<size_t> rest;                                           // everything else: blob by blob, as in a slab set
+    for (size_t b : G.mem) if (plan_in[b].form == sqy::DecodeBatchForm::stages) rest.push_back(b);
+    if (const int rc = group_remaining_stages(G, rest)) return rc;
+    return group_verdict(G, single);
+}
+
+// An entry of a caller's blob table: an offset from 0 on, a byte or more, a destination where the entry point (`who` in the message) takes them
+bool blob_entry_ok(const char* who, int i, long offset, long length, bool has_dst = true)
+{
+    if (offset >= 0 && length > 0 && has_dst) return true;
+    std::fprintf(stderr, "[sqeazy]\t %s: blob %d at %ld, %ld bytes%s\n", who, i, offset, length, has_dst ? "" : ", no destination");
+    return false;
 }
 
 // The headers of a blob set (blobs[i].src, .len given): every blob's prefix with one synchronisation (a header longer than that: fetched on
@@ -2665,8 +2685,7 @@ int decode_slabs_on_device(Context& cx, const void* d_src_v, const long* offsets
     DrainOnExit drain{stream, &cx.pending, cx.side};
     std::vector<SlabBlob> blobs((size_t)nslabs);
     for (int i = 0; i < nslabs; ++i) {
-        if (offsets[i] < 0 || lengths[i] <= 0) { std::fprintf(stderr, "[sqeazy]\t decode slabs: blob %d at %ld, %ld bytes\n", i, offsets[i], lengths[i]); return 1; }
-        blobs[i].src_off = (uint64_t)offsets[i];
+        if (!blob_entry_ok("decode slabs", i, offsets[i], lengths[i])) return 1;
         blobs[i].src = d_src + offsets[i];
         blobs[i].len = (uint64_t)lengths[i];
     }
@@ -2694,21 +2713,13 @@ int decode_slabs_on_device(Context& cx, const void* d_src_v, const long* offsets
         const bool ok = g_opt.decode_slabs_joint.load() != 0 && joint_candidate(cx, b, d_dst + b.dst_off, want_elem, stream, 2);
         (ok ? joint : single).push_back((size_t)i);
     }
-    // 3. groups: LZ4 output up to kSlabsGroupBytes (at least one blob), at most `inflight` blobs, one block size
-    std::vector<std::vector<size_t>> groups;
-    uint64_t gbytes = 0;
-    for (size_t b : joint) {
-        const uint64_t need = align_up(blobs[b].total, 256);
-        if (groups.empty() || (gbytes + need > kSlabsGroupBytes) || (inflight > 0 && groups.back().size() >= (size_t)inflight) ||
-            blobs[groups.back()[0]].block_bytes != blobs[b].block_bytes) {
-            groups.emplace_back();
-            gbytes = 0;
-        }
-        groups.back().push_back(b);
-        gbytes += need;
+    // 3. groups: LZ4 output up to kSlabsGroupBytes (at least one blob), at most `inflight` blobs, one block size (sqy_pipeline.cpp)
+    std::vector<sqy::SlabJointBlob> sizes;
+    for (size_t b : joint) sizes.push_back(sqy::SlabJointBlob{blobs[b].total, blobs[b].block_bytes});
+    for (std::vector<size_t>& g : sqy::decode_slab_groups(sizes, kSlabsGroupBytes, inflight)) {
+        for (size_t& j : g) j = joint[j];
+        if (const int rc = decode_slabs_group(cx, d_src, blobs, g, d_dst, volume, stream, single)) return rc;
     }
-    for (const auto& g : groups)
-        if (const int rc = decode_slab_group(cx, d_src, blobs, g, d_dst, volume, stream, single)) return rc;
     // 4. the others, one at a time
     for (size_t b : single)
         blobs[b].rc = decode_on_device(cx, blobs[b].src, blobs[b].len, d_dst + blobs[b].dst_off, blobs[b].raw, want_elem, stream);
@@ -2723,7 +2734,7 @@ int decode_slabs_from_host(const char* src, const long* offsets, const long* len
     if (!src || !dst || !offsets || !lengths || nslabs <= 0) { std::fprintf(stderr, "[sqeazy]\t decode slabs: bad arguments\n"); return 1; }
     uint64_t span = 0, volume = 0;
     for (int i = 0; i < nslabs; ++i) {                                   // untrusted input: before anything is allocated or uploaded
-        if (offsets[i] < 0 || lengths[i] <= 0) { std::fprintf(stderr, "[sqeazy]\t decode slabs: blob %d at %ld, %ld bytes\n", i, offsets[i], lengths[i]); return 1; }
+        if (!blob_entry_ok("decode slabs", i, offsets[i], lengths[i])) return 1;
         const sqy::HeaderInfo h = sqy::header_unpack(src + offsets[i], src + offsets[i] + lengths[i]);
         if (!h.valid) { std::fprintf(stderr, "[sqeazy]\t decode slabs: no sqy header in blob %d\n", i); return 1; }
         uint64_t raw = 0;
@@ -2739,11 +2750,10 @@ int decode_slabs_from_host(const char* src, const long* offsets, const long* len
 
 // ---- batch decode (SQYAMD_Decode_Batch_*) -------------------------------------------------------------------------------------
 // Independent blobs -- any shape, any pipeline, each destination an allocation of its own --, the way back from a batch encode.  The
-// joint-eligible ones (the last stage lz4, chunks of one LZ4 block; ONE chunk will do) go through decode_slab_group in the groups
+// joint-eligible ones (the last stage lz4, chunks of one LZ4 block; ONE chunk will do) go through decode_batch_group in the groups
 // sqy::decode_batch_plan deals them to: per group one frame ranking, one read-back of its counts, one joint index and LZ4 decode into the
-// workspace, one inverse-transpose launch for all `bitswap1->lz4` blobs, one copy launch for all `lz4` blobs, one launch with the look-up
-// for all `quantiser->bitswap1->lz4` blobs, one launch per chain step for all 16-bit diff3x3x1 blobs in the chain geometry, one verdict read-back.
-// Every other blob, and what a group hands back, goes through decode_on_device in blob order.
+// workspace, batch_group_tail's launches, one verdict read-back.  Every other blob, and what a group hands back, goes through
+// decode_on_device in blob order.
 struct BatchDecodeArgs { const long* offsets; const long* lengths; int nblobs; void* const* dsts; const long* capacities; long* decoded; };
 
 // the arguments alone, before any device is looked for; decoded_bytes zeroed where it can be
@@ -2752,10 +2762,7 @@ int admit_decode_batch(const void* src, const BatchDecodeArgs& a)
     if (a.decoded && a.nblobs > 0) for (int i = 0; i < a.nblobs; ++i) a.decoded[i] = 0;
     if (!src || !a.offsets || !a.lengths || !a.dsts || !a.capacities || a.nblobs <= 0) { std::fprintf(stderr, "[sqeazy]\t decode batch: bad arguments\n"); return 1; }
     for (int i = 0; i < a.nblobs; ++i)
-        if (a.offsets[i] < 0 || a.lengths[i] <= 0 || !a.dsts[i]) {
-            std::fprintf(stderr, "[sqeazy]\t decode batch: blob %d at %ld, %ld bytes%s\n", i, a.offsets[i], a.lengths[i], a.dsts[i] ? "" : ", no destination");
-            return 1;
-        }
+        if (!blob_entry_ok("decode batch", i, a.offsets[i], a.lengths[i], a.dsts[i] != nullptr)) return 1;
     return 0;
 }
 
@@ -2800,7 +2807,6 @@ int decode_batch_on_device(Context& cx, const void* d_src_v, const BatchDecodeAr
     const size_t n = (size_t)a.nblobs;
     std::vector<SlabBlob> blobs(n);
     for (size_t i = 0; i < n; ++i) {
-        blobs[i].src_off = (uint64_t)a.offsets[i];
         blobs[i].src = d_src + a.offsets[i];
         blobs[i].len = (uint64_t)a.lengths[i];
     }
@@ -2832,13 +2838,8 @@ int decode_batch_on_device(Context& cx, const void* d_src_v, const BatchDecodeAr
     const uint64_t group_bytes = (uint64_t)g_opt.decode_batch_group_bytes.load();
     const sqy::DecodeBatchPlan plan = sqy::decode_batch_plan(plan_in, group_bytes);
     for (size_t i = 0; i < n; ++i) if (plan.group_of[i] < 0) single.push_back(i);
-    for (size_t gi = 0; gi < plan.groups.size(); ++gi) {
-        const sqy::DecodeBatchGroup& g = plan.groups[gi];
-        std::vector<size_t> members(g.blobs.begin(), g.blobs.end());
-        for (size_t k = 0; k < members.size(); ++k) blobs[members[k]].out_base = g.out_at[k];
-        const BatchGroup bg{&plan_in, group_bytes, gi, &g, want_elem};
-        if (const int rc = decode_slab_group(cx, d_src, blobs, members, nullptr, 0, stream, single, &bg)) return rc;
-    }
+    for (size_t gi = 0; gi < plan.groups.size(); ++gi)
+        if (const int rc = decode_batch_group(cx, d_src, blobs, plan_in, group_bytes, plan, gi, want_elem, stream, single)) return rc;
     // 3. the others, one at a time, in blob order
     std::sort(single.begin(), single.end());
     for (size_t b : single)
@@ -2915,6 +2916,9 @@ int encode_device(const char* pipeline, const void* d_src, const long* shape, un
 // host round trips per group (the dense pass's count and, quantised, the decode LUTs for the headers; the records) --, every other
 // volume through encode_on_device.
 static_assert(sizeof(sqy::Lz4BatchChunkPlan) == sizeof(sqy::Lz4BatchChunk) && sizeof(sqy::Lz4BatchChunk) == 24, "the joint chunk table's layout");
+// what the host-only layouts of the batch and slab-set tables (sqy_pipeline.hpp) take the kernels' structs to be
+static_assert(sizeof(sqy::Bitswap1Job) == sqy::kBitswap1JobBytes && sizeof(sqy::DiffBatchJob) == sqy::kDiffBatchJobBytes && sizeof(sqy::Lz4JointPart) == sqy::kLz4JointPartBytes &&
+              sizeof(sqy::Lz4BatchChunk) == sqy::kLz4BatchChunkBytes && sizeof(sqy::Lz4BatchVolume) == sqy::kLz4BatchVolumeBytes, "the table layouts' element sizes");
 
 // What a batch call checks before it touches the device or writes anything: every argument, the pipeline once, every volume's shape
 struct BatchAdmit {
@@ -2938,9 +2942,8 @@ int admit_batch(const char* pipeline, const void* const* srcs, const long* shape
     return 0;
 }
 
-// one group of the plan through the kernels; rc 1 with a message when a blob does not fit its slot (nothing of that volume is written)
-constexpr uint64_t kBatchHeaderTextMax = 4000;      // prefix + suffix of one volume's header (the staging area's share: 4096 bytes a volume)
-
+// one group of the plan through the kernels; rc 1 with a message when a blob does not fit its slot (nothing of that volume is written).
+// staging: pinned, sqy::encode_batch_layout's staging_bytes for the group at its worst-case text
 int encode_batch_group(Context& cx, const BatchAdmit& a, const sqy::Lz4BatchGroup& g, sqy::EncodeBatchForm form, int elem_size, const void* const* d_srcs,
                        uint8_t* d_dst, uint64_t slot_capacity, long* offsets, long* lengths, uint64_t* records, uint8_t* staging, hipStream_t stream)
 {
@@ -2948,15 +2951,13 @@ int encode_batch_group(Context& cx, const BatchAdmit& a, const sqy::Lz4BatchGrou
     std::vector<PendingEvent>* pend = &cx.pending;
     const size_t nv = g.vols.size(), nc = g.chunks.size();
     const bool quantised = form == sqy::EncodeBatchForm::quantiser_bitswap1_lz4, transpose = quantised || form == sqy::EncodeBatchForm::bitswap1_lz4;
-    // the upload: chunk table | volume of every entry | transposer jobs | their tile prefix -- and, in a copy of their own behind round
-    // trip 1 when the header text is known only then (quantised: every volume's name carries its decode LUT) -- | volumes | header text
-    auto up16 = [](uint64_t v) { return (v + 15) & ~(uint64_t)15; };
+    // the header text: known now, or only behind round trip 1 (quantised: every volume's name carries its decode LUT)
     std::vector<std::string> text(nv);
     uint64_t text_bytes = 0;
     auto pack_text = [&](size_t j, const std::string& pipename) {
         std::string prefix, suffix;
         sqy::header_pack_parts(elem_size, false, a.dims[g.vols[j]], pipename, &prefix, &suffix);
-        if (prefix.size() + suffix.size() > kBatchHeaderTextMax) {
+        if (prefix.size() + suffix.size() > sqy::kBatchHeaderTextMax) {
             std::fprintf(stderr, "[sqeazy]\t volume %u: header text too long for the batch path\n", g.vols[j]);
             return 1;
         }
@@ -2968,24 +2969,21 @@ int encode_batch_group(Context& cx, const BatchAdmit& a, const sqy::Lz4BatchGrou
         const std::string pipename = a.pipe.name();
         for (size_t j = 0; j < nv; ++j) if (pack_text(j, pipename)) return 1;
     }
-    const uint64_t table_at = 0, volof_at = up16(table_at + nc * sizeof(sqy::Lz4BatchChunk)), jobs_at = up16(volof_at + nc * 4),
-                   tiles_at = up16(jobs_at + nv * sizeof(sqy::Bitswap1Job)), vols_at = up16(tiles_at + (nv + 1) * 4),
-                   text_at = up16(vols_at + nv * sizeof(sqy::Lz4BatchVolume)), upload = up16(text_at + (quantised ? nv * kBatchHeaderTextMax : text_bytes));
-    // .. and what the kernels hand each other: csize | redo list | frame offsets | per volume: payload bytes, header bytes and verdict
-    const uint64_t csize_at = upload, redo_at = up16(csize_at + nc * 4), foff_at = up16(redo_at + (nc + 1) * 4), vinfo_at = up16(foff_at + nc * 8),
-                   tables = vinfo_at + nv * 16;
-    if (ws->batch_tables.ensure(tables) || ws->batch_scratch.ensure(std::max<uint64_t>(nc * g.scratch_stride, 16))) return 1;
+    // the tables (sqy::encode_batch_layout): what the host uploads -- the volumes and the header text in a copy of their own behind round
+    // trip 1 when the text is known only then --, and behind it what the kernels hand each other
+    const sqy::EncodeBatchLayout L = sqy::encode_batch_layout(nc, nv, quantised, quantised ? nv * sqy::kBatchHeaderTextMax : text_bytes);
+    if (ws->batch_tables.ensure(L.tables) || ws->batch_scratch.ensure(std::max<uint64_t>(nc * g.scratch_stride, 16))) return 1;
     if (transpose && ws->batch_stream.ensure(std::max<uint64_t>(g.stream_bytes, 16))) return 1;
     if (quantised && ws->batch_quant.ensure(nv * sqy::kQuantiserBatchTableBytes)) return 1;
     uint8_t* const d_tab = static_cast<uint8_t*>(ws->batch_tables.p);
     uint8_t* const d_stream = transpose ? static_cast<uint8_t*>(ws->batch_stream.p) : nullptr;
 
-    sqy::Lz4BatchChunk* h_table = reinterpret_cast<sqy::Lz4BatchChunk*>(staging + table_at);
-    uint32_t* h_volof = reinterpret_cast<uint32_t*>(staging + volof_at);
-    sqy::Lz4BatchVolume* h_vols = reinterpret_cast<sqy::Lz4BatchVolume*>(staging + vols_at);
-    sqy::Bitswap1Job* h_jobs = reinterpret_cast<sqy::Bitswap1Job*>(staging + jobs_at);
-    uint32_t* h_tiles = reinterpret_cast<uint32_t*>(staging + tiles_at);
-    char* h_text = reinterpret_cast<char*>(staging + text_at);
+    sqy::Lz4BatchChunk* h_table = reinterpret_cast<sqy::Lz4BatchChunk*>(staging + L.table_at);
+    uint32_t* h_volof = reinterpret_cast<uint32_t*>(staging + L.volof_at);
+    sqy::Lz4BatchVolume* h_vols = reinterpret_cast<sqy::Lz4BatchVolume*>(staging + L.vols_at);
+    sqy::Bitswap1Job* h_jobs = reinterpret_cast<sqy::Bitswap1Job*>(staging + L.jobs_at);
+    uint32_t* h_tiles = reinterpret_cast<uint32_t*>(staging + L.tiles_at);
+    char* h_text = reinterpret_cast<char*>(staging + L.text_at);
     uint64_t text_used = 0;
     uint32_t ntiles = 0;
     // the volume table and the header text, once every volume's text is there
@@ -3016,22 +3014,22 @@ int encode_batch_group(Context& cx, const BatchAdmit& a, const sqy::Lz4BatchGrou
         }
     }
     h_tiles[nv] = ntiles;
-    SQY_HIP(hipMemcpyAsync(d_tab, staging, quantised ? vols_at : up16(text_at + text_bytes), hipMemcpyHostToDevice, stream));
+    SQY_HIP(hipMemcpyAsync(d_tab, staging, quantised ? L.vols_at : L.upload, hipMemcpyHostToDevice, stream));
 
-    const sqy::Lz4BatchChunk* d_table = reinterpret_cast<const sqy::Lz4BatchChunk*>(d_tab + table_at);
-    const sqy::Lz4BatchVolume* d_vols = reinterpret_cast<const sqy::Lz4BatchVolume*>(d_tab + vols_at);
-    uint32_t* d_csize = reinterpret_cast<uint32_t*>(d_tab + csize_at);
-    uint32_t* d_redo = reinterpret_cast<uint32_t*>(d_tab + redo_at);
-    uint64_t* d_foff = reinterpret_cast<uint64_t*>(d_tab + foff_at);
-    uint64_t* d_vinfo = reinterpret_cast<uint64_t*>(d_tab + vinfo_at);
+    const sqy::Lz4BatchChunk* d_table = reinterpret_cast<const sqy::Lz4BatchChunk*>(d_tab + L.table_at);
+    const sqy::Lz4BatchVolume* d_vols = reinterpret_cast<const sqy::Lz4BatchVolume*>(d_tab + L.vols_at);
+    uint32_t* d_csize = reinterpret_cast<uint32_t*>(d_tab + L.csize_at);
+    uint32_t* d_redo = reinterpret_cast<uint32_t*>(d_tab + L.redo_at);
+    uint64_t* d_foff = reinterpret_cast<uint64_t*>(d_tab + L.foff_at);
+    uint64_t* d_vinfo = reinterpret_cast<uint64_t*>(d_tab + L.vinfo_at);
     uint8_t* d_scratch = static_cast<uint8_t*>(ws->batch_scratch.p);
-    const sqy::Bitswap1Job* d_jobs = reinterpret_cast<const sqy::Bitswap1Job*>(d_tab + jobs_at);
-    const uint32_t* d_tiles = reinterpret_cast<const uint32_t*>(d_tab + tiles_at);
+    const sqy::Bitswap1Job* d_jobs = reinterpret_cast<const sqy::Bitswap1Job*>(d_tab + L.jobs_at);
+    const uint32_t* d_tiles = reinterpret_cast<const uint32_t*>(d_tab + L.tiles_at);
     // (quantised) the group's histograms | encode LUTs | decode LUTs, volume j's at index j of each
     uint32_t* const d_histos = static_cast<uint32_t*>(ws->batch_quant.p);
     uint8_t* const d_luts = quantised ? static_cast<uint8_t*>(ws->batch_quant.p) + nv * sqy::kQuantiserBatchHistoBytes : nullptr;
     uint16_t* const d_decode = quantised ? reinterpret_cast<uint16_t*>(d_luts + nv * sqy::kQuantiserBatchLutBytes) : nullptr;
-    uint16_t* const h_decode = reinterpret_cast<uint16_t*>(staging + upload);          // (pinned, behind the staging area of the upload)
+    uint16_t* const h_decode = reinterpret_cast<uint16_t*>(staging + L.decode_at);     // (pinned, behind the staging area of the upload)
     if (quantised) {
         SQY_TIMED("batch_quantiser_histogram", sqy::launch_batch_quantiser_histogram(d_jobs, d_tiles, (uint32_t)nv, ntiles, d_histos, stream));
         SQY_TIMED("batch_quantiser_lut", sqy::launch_batch_quantiser_lut(d_histos, (uint32_t)nv, d_luts, d_decode, stream));
@@ -3052,15 +3050,15 @@ int encode_batch_group(Context& cx, const BatchAdmit& a, const sqy::Lz4BatchGrou
             if (pack_text(j, named.name())) return 1;
         }
         fill_volumes();
-        SQY_HIP(hipMemcpyAsync(d_tab + vols_at, staging + vols_at, up16(text_at + text_bytes) - vols_at, hipMemcpyHostToDevice, stream));
+        SQY_HIP(hipMemcpyAsync(d_tab + L.vols_at, staging + L.vols_at, sqy::encode_batch_layout(nc, nv, quantised, text_bytes).upload - L.vols_at, hipMemcpyHostToDevice, stream));
     }
     if (n_redo)
         SQY_TIMED("batch_lz4_chunks_dense", sqy::launch_lz4_chunks_table_dense(d_stream, d_table, d_scratch, g.scratch_stride, d_csize, d_redo, n_redo, stream));
     SQY_TIMED("batch_lz4_frame_scan", sqy::launch_lz4_batch_scan(d_table, d_vols, (uint32_t)nv, d_csize, d_foff, d_vinfo, stream));
     const Lz4Descriptor fd = lz4_descriptor(a.pipe.stages.back().lz4.block_id);
     SQY_TIMED("batch_lz4_frame_gather", sqy::launch_lz4_batch_gather(d_stream, d_table, (uint32_t)nc, g.max_chunk, d_vols,
-                                                                     reinterpret_cast<const uint32_t*>(d_tab + volof_at), d_scratch, g.scratch_stride, d_csize,
-                                                                     d_foff, d_vinfo, reinterpret_cast<const char*>(d_tab + text_at), d_dst, fd.bd, fd.hc, records, stream));
+                                                                     reinterpret_cast<const uint32_t*>(d_tab + L.volof_at), d_scratch, g.scratch_stride, d_csize,
+                                                                     d_foff, d_vinfo, reinterpret_cast<const char*>(d_tab + L.text_at), d_dst, fd.bd, fd.hc, records, stream));
     // round trip 2: the records
     SQY_HIP(hipStreamSynchronize(stream));
     int rc = 0;
@@ -3097,10 +3095,11 @@ int encode_batch_on_device(Context& cx, const char* pipeline, const BatchAdmit& 
     int rc = 0;
     if (!plan.groups.empty()) {
         DrainOnExit drain{stream, &cx.pending};
-        // pinned: a record per volume of the batch (3 words), behind them the staging area of the largest group's upload
+        // pinned: a record per volume of the batch (3 words), behind them the staging area of the group that needs the largest one
+        const bool quantised = form == sqy::EncodeBatchForm::quantiser_bitswap1_lz4;
         uint64_t staging = 0;
         for (const sqy::Lz4BatchGroup& g : plan.groups)
-            staging = std::max<uint64_t>(staging, g.chunks.size() * (sizeof(sqy::Lz4BatchChunk) + 4) + g.vols.size() * (sizeof(sqy::Lz4BatchVolume) + sizeof(sqy::Bitswap1Job) + 4 + 4096 + sqy::kQuantiserBatchDecodeBytes) + 256);
+            staging = std::max(staging, sqy::encode_batch_layout(g.chunks.size(), g.vols.size(), quantised, g.vols.size() * sqy::kBatchHeaderTextMax).staging_bytes);
         const uint64_t records_bytes = ((uint64_t)nvolumes * 24 + 63) & ~(uint64_t)63;
         if (cx.ws.batch_host.ensure(records_bytes + staging)) return 1;
         uint64_t* records = static_cast<uint64_t*>(cx.ws.batch_host.p);

@@ -402,6 +402,102 @@ DecodeBatchPlan decode_batch_plan(const std::vector<DecodeBatchBlob>& blobs, uin
     return plan;
 }
 
+std::vector<std::vector<size_t>> decode_slab_groups(const std::vector<SlabJointBlob>& joint, uint64_t group_bytes, int inflight)
+{
+    std::vector<std::vector<size_t>> groups;
+    uint64_t gbytes = 0;
+    for (size_t j = 0; j < joint.size(); ++j) {
+        const uint64_t need = round_up(joint[j].total, 256);
+        if (groups.empty() || gbytes + need > group_bytes || (inflight > 0 && groups.back().size() >= (size_t)inflight) ||
+            joint[groups.back()[0]].block_bytes != joint[j].block_bytes) {
+            groups.emplace_back();
+            gbytes = 0;
+        }
+        groups.back().push_back(j);
+        gbytes += need;
+    }
+    return groups;
+}
+
+// a region of `bytes` behind *end, its start rounded up to `align`: where it starts
+static uint64_t append(uint64_t* end, uint64_t bytes, uint64_t align)
+{
+    const uint64_t at = round_up(*end, align);
+    *end = at + bytes;
+    return at;
+}
+
+DecodeRankLayout decode_rank_layout(const std::vector<DecodeRankBlob>& blobs, uint64_t desc_bytes)
+{
+    DecodeRankLayout l;
+    uint64_t end = 0;
+    for (const DecodeRankBlob& b : blobs) {
+        DecodeRankLayout::Blob at;
+        at.scratch_at = append(&end, b.scratch_bytes, kDecodeTableAlign);
+        at.blk_at = append(&end, b.max_blocks * kLz4BlockIndexBytes, kDecodeTableAlign);
+        at.frame_first_at = append(&end, (b.max_blocks + 2) * 4, kDecodeTableAlign);
+        l.blobs.push_back(at);
+    }
+    l.counts_at = append(&end, blobs.size() * 64, kDecodeTableAlign);
+    l.flag_at = append(&end, 64, 64);
+    l.desc_at = append(&end, desc_bytes, kDecodeTableAlign);
+    l.total = end;
+    return l;
+}
+
+DecodeJointLayout decode_joint_layout(uint64_t nparts, uint64_t map_bytes, uint64_t nframes, const DecodeBatchGroup* batch)
+{
+    DecodeJointLayout l;
+    uint64_t end = 0;
+    l.parts_at = append(&end, nparts * kLz4JointPartBytes, kDecodeTableAlign);
+    l.maps_at = append(&end, map_bytes, kDecodeTableAlign);
+    l.upload_bytes = end;
+    l.jblk_at = append(&end, nframes * kLz4BlockIndexBytes, kDecodeTableAlign);
+    l.jff_at = append(&end, (nframes + 1) * 4, 4);
+    l.jout_at = append(&end, nframes * kLz4BlockIndexBytes, kDecodeTableAlign);
+    l.jobs_upload_at = end;
+    if (batch) {
+        DecodeJointLayout::Family* const family[4] = {&l.planes, &l.plain, &l.quantised, &l.diff};
+        const uint64_t njobs[4] = {batch->planes.jobs.size(), batch->plain.jobs.size(), batch->quantised.jobs.size(), batch->diff.jobs.size()};
+        for (int k = 0; k < 4; ++k) {
+            DecodeJointLayout::Family& f = *family[k];
+            const bool diff = family[k] == &l.diff, quantised = family[k] == &l.quantised;
+            const uint64_t tiles_bytes = (njobs[k] + 1) * 4;
+            f.jobs_at = append(&end, njobs[k] * (diff ? kDiffBatchJobBytes : kBitswap1JobBytes), kDecodeTableAlign);
+            f.tiles_at = append(&end, tiles_bytes, 4);
+            // (the diff family's second table follows its first; the LUTs, and the empty region of the other families, start a new line)
+            f.extra_at = diff ? append(&end, tiles_bytes, 4) : append(&end, quantised ? njobs[k] * 512 : 0, kDecodeTableAlign);
+        }
+        l.jobs_upload_at = l.planes.jobs_at;
+    }
+    l.jobs_bytes = end - l.jobs_upload_at;
+    l.total = end;
+    return l;
+}
+
+EncodeBatchLayout encode_batch_layout(uint64_t nchunks, uint64_t nvols, bool quantised, uint64_t text_bytes)
+{
+    EncodeBatchLayout l;
+    uint64_t end = 0;
+    const uint64_t a = kEncodeTableAlign;
+    l.table_at = append(&end, nchunks * kLz4BatchChunkBytes, a);
+    l.volof_at = append(&end, nchunks * 4, a);
+    l.jobs_at = append(&end, nvols * kBitswap1JobBytes, a);
+    l.tiles_at = append(&end, (nvols + 1) * 4, a);
+    l.vols_at = append(&end, nvols * kLz4BatchVolumeBytes, a);
+    l.text_at = append(&end, text_bytes, a);
+    l.upload = round_up(end, a);
+    uint64_t staging = l.upload;
+    l.decode_at = append(&staging, quantised ? nvols * kQuantiserBatchDecodeBytes : 0, a);
+    l.staging_bytes = staging;
+    l.csize_at = append(&end, nchunks * 4, a);
+    l.redo_at = append(&end, (nchunks + 1) * 4, a);
+    l.foff_at = append(&end, nchunks * 8, a);
+    l.vinfo_at = append(&end, nvols * 16, a);
+    l.tables = end;
+    return l;
+}
+
 Lz4DedupeLayout lz4_dedupe_layout(const Lz4EncodeLayout& lay, uint64_t piece_hash_words)
 {
     Lz4DedupeLayout d;

@@ -171,6 +171,58 @@ struct DecodeBatchPlan {
 // -- they keep their place in the group and in the workspace but get no job in any table.
 DecodeBatchPlan decode_batch_plan(const std::vector<DecodeBatchBlob>& blobs, uint64_t group_bytes, const std::vector<uint8_t>* dropped = nullptr);
 
+// The slab set's groups (SQYAMD_Decode_Slabs_*): joint blob j decodes `total` bytes in LZ4 blocks of block_bytes.  The blobs are dealt to
+// groups in order; a group is closed when the next blob would take its LZ4 output (every blob's rounded up to 256 bytes) past group_bytes,
+// when it holds `inflight` blobs (inflight <= 0: no bound on the count), or when the next blob has another block size.  A group holds at
+// least one blob.  The groups hold indices into `joint`.
+struct SlabJointBlob { uint64_t total = 0, block_bytes = 0; };
+std::vector<std::vector<size_t>> decode_slab_groups(const std::vector<SlabJointBlob>& joint, uint64_t group_bytes, int inflight);
+
+// ---- device tables of the batch and slab-set drivers: byte offsets into ONE buffer each, in ascending order, each region ending where the
+// next begins (but for the padding in front of an aligned one), `total` the end of the last region.  The element sizes are those of the
+// kernels' structs (sqy_kernels.h), which sqy_capi.cpp pins with static_asserts ----
+constexpr uint64_t kBitswap1JobBytes = 24, kDiffBatchJobBytes = 32, kLz4JointPartBytes = 64, kLz4BatchChunkBytes = 24, kLz4BatchVolumeBytes = 48;
+constexpr uint64_t kLz4BlockIndexBytes = 16;            // an entry of a block index (blk, jblk) and of the frame output table (jout)
+constexpr uint64_t kDecodeTableAlign = 256, kEncodeTableAlign = 16;
+
+// The ranking workspace of a decode group (Workspace::slabs_index).  Per blob, 256-byte aligned each: the ranking's scratch (scratch_bytes:
+// lz4_frame_rank_scratch_bytes of its chunks) | its block index (max_blocks entries) | its frame starts (max_blocks + 2 words); then
+// counts_at: 16 words per blob | flag_at: the group's error flag (64 bytes) | desc_at: launch_lz4_frame_rank_batch's descriptors
+struct DecodeRankBlob { uint64_t scratch_bytes = 0, max_blocks = 0; };
+struct DecodeRankLayout {
+    struct Blob { uint64_t scratch_at = 0, blk_at = 0, frame_first_at = 0; };
+    std::vector<Blob> blobs;
+    uint64_t counts_at = 0, flag_at = 0, desc_at = 0, total = 0;
+};
+DecodeRankLayout decode_rank_layout(const std::vector<DecodeRankBlob>& blobs, uint64_t desc_bytes);
+
+// The joint decode tables of a group (Workspace::slabs_joint): parts_at: an Lz4JointPart per blob | maps_at: the frame_shuffle maps | jblk_at,
+// jff_at, jout_at: the joint index of `nframes` frames (16 bytes, a word + 1, 16 bytes per frame).  The first upload_bytes are the host's
+// (parts and maps), the rest is built on the device.  A batch (batch != nullptr) has behind them what the launches that follow the LZ4
+// decode read, one upload of jobs_bytes at jobs_upload_at; per job family its job array at jobs_at (Bitswap1Job, the diff family's
+// DiffBatchJob), njobs + 1 words of prefix sums at tiles_at (first_tile; diff: first_strip) and at extra_at
+//   quantised: a decode LUT of 512 bytes per job | diff: its second prefix table (first_tile) | planes, plain: nothing
+struct DecodeJointLayout {
+    uint64_t parts_at = 0, maps_at = 0, jblk_at = 0, jff_at = 0, jout_at = 0, upload_bytes = 0;
+    struct Family { uint64_t jobs_at = 0, tiles_at = 0, extra_at = 0; } planes, plain, quantised, diff;      // (as DecodeBatchGroup names them)
+    uint64_t jobs_upload_at = 0, jobs_bytes = 0, total = 0;
+};
+DecodeJointLayout decode_joint_layout(uint64_t nparts, uint64_t map_bytes, uint64_t nframes, const DecodeBatchGroup* batch = nullptr);
+
+// The tables of an encode batch group, 16-byte aligned each.  What the host writes, in the pinned staging area and in Workspace::batch_tables
+// alike: table_at: the chunk table | volof_at: a word per chunk | jobs_at: a Bitswap1Job per volume | tiles_at: nvols + 1 words | vols_at:
+// an Lz4BatchVolume each | text_at: text_bytes of header text -- `upload` bytes in all.  Behind them in batch_tables what the kernels hand
+// each other: csize_at, redo_at (nchunks + 1 words), foff_at (8 bytes a chunk), vinfo_at (16 bytes a volume); `tables` bytes in all.  Behind
+// them in the staging area, at decode_at, a quantised group's decode LUTs come back (512 bytes a volume); staging_bytes in all.  A
+// quantised group knows its text only after its first round trip: it is laid out for the worst case, kBatchHeaderTextMax bytes a volume.
+constexpr uint64_t kBatchHeaderTextMax = 4000;          // prefix + suffix of one volume's header
+struct EncodeBatchLayout {
+    uint64_t table_at = 0, volof_at = 0, jobs_at = 0, tiles_at = 0, vols_at = 0, text_at = 0, upload = 0;
+    uint64_t csize_at = 0, redo_at = 0, foff_at = 0, vinfo_at = 0, tables = 0;
+    uint64_t decode_at = 0, staging_bytes = 0;
+};
+EncodeBatchLayout encode_batch_layout(uint64_t nchunks, uint64_t nvols, bool quantised, uint64_t text_bytes);
+
 // Frames in place: a 16-bit bitswap1 in front of lz4 writes chunk k of the plane stream into the destination at body0 + k * in_stride,
 // where it is the body of the stored frame it may become -- kLz4FrameHead bytes (frame header 7, block size field 4) in front, the end
 // mark behind: kLz4FrameGap bytes between two chunks.  t0 (>= header_max, the longest sqy header) is where frame 0 begins.

@@ -190,6 +190,29 @@ def test_mixed_batch(sqy, oracle):
     assert not any(k.startswith(SINGLE_QUANT + ("diff3x3x1_decode",)) for k in prof), prof
 
 
+def test_one_group_of_every_family_with_a_blob_the_ranking_refuses(sqy, oracle):
+    """ONE group (one block size) with jobs in all four tables -- planes, plain, quantised, both diff forms -- and in their midst a blob in
+    the serial layout (nthreads = 1): one LZ4 frame where the geometry has three chunks, so the frame ranking refuses it, the group's plan is
+    made again with that member dropped, and the blob goes through the single path.  Every output: the oracle's decode of the same blob."""
+    pipes = [("bitswap1->lz4", 2, (4, 16, 32)), ("lz4", 2, (5, 20, 40)), (QUANT, 2, (6, 24, 40)), (DIFF_PLANES, 2, (4, 16, 32)),
+             ("bitswap1->lz4(n_chunks_of_input=3)", 1, (6, 24, 40)), (DIFF_PLAIN, 2, (5, 20, 40)), ("bitswap1->lz4(n_chunks_of_input=3)", 2, (6, 24, 40))]
+    pairs = [_blob(oracle, p, ("stack", s, 820 + i), lambda: synth.stack(s, np.uint16, seed=820 + i), nthreads=t) for i, (p, t, s) in enumerate(pipes)]
+    magic = bytes([0x04, 0x22, 0x4D, 0x18])
+    assert pairs[4][1].count(magic) == 1 and pairs[6][1].count(magic) == 3      # the serial layout, and the same pipeline chunked
+    res, prof = _profiled(sqy, lambda: _decode(sqy, pairs))
+    _check(sqy, pairs, res, lossless=False)
+    for i, (v, b) in enumerate(pairs):
+        assert res[5][i] == np.ascontiguousarray(oracle.pipeline_decode(b)).tobytes(), "blob %d differs from the oracle's decode" % i
+    for name in ("batch_frame_index", "batch_lz4_decode", "batch_bitswap1_decode", "batch_quantiser_decode", "batch_copy"):
+        assert prof[name][1] == 1, (name, prof)                              # one group, one launch each
+    assert prof["batch_diff3x3x1_decode"][1] == 1 + 1, prof                  # both diff blobs: at most 5 frames, one chain step
+    # the single path: the refused blob (its own index and LZ4 decode, its inverse transpose), nobody else
+    assert "lz4_frame_rank" in prof or "lz4_frame_index" in prof, prof
+    assert "lz4_frames_decode" in prof or "lz4_linked_decode" in prof, prof
+    assert prof["bitswap1_decode"][1] == 1, prof
+    assert not any(k.startswith(SINGLE_QUANT + ("diff3x3x1_decode",)) for k in prof), prof
+
+
 def test_groups_and_the_switch(sqy, oracle, options):
     pairs = _chain_set(oracle, DIFF_PLANES) + _quant_set(oracle)
     want = _decode(sqy, pairs)[5]
