@@ -3173,7 +3173,8 @@ void frame_metric_i8_kernel(const int8_t* __restrict__ in, uint64_t Z, uint64_t 
 // (FmBlock::lane_map).  A wave splits a 4 KiB block over its 64 lanes, each lane adds its 64 bytes to both stand-ins, the 64 lane maps
 // are composed in lane order by a tree (FmBlock::block_map).  Blocks that may cross into the next binade (at most a dozen per frame)
 // are added by the lanes one after the other, starting from the real sum.  Below 2^24 everything is exact.
-// Checked against numpy's sequential float32 cumsum (tests) and, end to end, against the oracle's C loop.
+// Checked against numpy's sequential float32 cumsum and the oracle's C loop, to the ulp, on frames built for every branch below
+// (tests/frame_metric_cases.py, tests/test_frame_metric_host.py, tests/test_gpu_frame_metric.py).
 // building blocks of the exact evaluation, one 4 KiB block of a frame per wavefront step
 template <typename T>
 struct FmBlock {

@@ -47,15 +47,23 @@ def main(stage_lanes, opt_in):
     for _ in range(3):
         call(out_b, sb)
     alone = [call(out_b, sb)[0] for _ in range(9)]
-    # the spin kernel: at least 100 alone-times and 50 ms, calibrated here (the counter's rate is the device's business)
+    # the spin kernel: at least 100 alone-times and 50 ms, calibrated here (the counter's rate is the device's business).  The first
+    # launch of the spin kernel loads its code object, and any one launch can meet a stall of the host: a time that holds something
+    # else than the kernel would end the calibration with a kernel far too short.  So one launch before any is timed, and a length
+    # counts as long enough only by the shorter of two timings
     cycles, spin = 1 << 22, 0.0
     with torch.cuda.stream(sa):
+        torch.cuda._sleep(1)
+        sa.synchronize()
         for _ in range(12):
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            torch.cuda._sleep(cycles)
-            sa.synchronize()
-            spin = time.perf_counter() - t0
+            timed = []
+            for _ in range(2):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                torch.cuda._sleep(cycles)
+                sa.synchronize()
+                timed.append(time.perf_counter() - t0)
+            spin = min(timed)
             if spin >= max(100 * float(np.median(alone)), 0.05):
                 break
             cycles *= 4
