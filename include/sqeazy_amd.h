@@ -188,6 +188,23 @@ SQY_FUNCTION_PREFIX int SQYAMD_PipelineEncode_Batch_UI16_Device(const char* pipe
 SQY_FUNCTION_PREFIX int SQYAMD_PipelineEncode_Batch_UI8_Device(const char* pipeline, const void* const* d_srcs, const long* shapes,
                                                                unsigned shape_size, int nvolumes, void* d_dst, long slot_capacity,
                                                                long* offsets, long* lengths, int nthreads, void* hip_stream);
+/* _Batch_*_Device for views: volume i is a strided view of a larger resident allocation -- a tile of a dataset, a region of interest, a
+ * padded or pitched volume -- encoded where it lies, without a dense copy of the caller's.  strides: a HOST array of nvolumes x shape_size
+ * longs in VOXELS, row i = view i's strides, outermost dimension first.  The rules, all checked on the host before the device is touched
+ * or anything is written (1, offsets and lengths zeroed): shape_size is 1, 2 or 3; the innermost stride is 1; every stride is positive and
+ * stride[k] >= shape[k+1] * stride[k+1] (a view never overlaps itself); d_srcs[i] is aligned to the voxel size.  Only the view's voxels
+ * are read.  strides == NULL: every view is dense and the call IS SQYAMD_PipelineEncode_Batch_*_Device (same kernels); the same holds for
+ * any view whose strides are the dense ones.  Blob i is byte for byte what SQYAMD_PipelineEncode_*_Device gives for a dense copy of view
+ * i; slots, offsets, lengths, capacity, errors, stream, context, ordering and thread safety are _Batch_*_Device's.
+ * `bitswap1->lz4`: the group's transposer gathers its voxels from the views (no copy at all); `lz4`: one launch packs the group's views
+ * into its stream workspace; every other pipeline: one launch packs the group's views into a workspace that counts against
+ * "encode_batch_group_bytes", then as _Batch_*_Device.  "batch_strided_fused" = 0: packed copies for every pipeline. */
+SQY_FUNCTION_PREFIX int SQYAMD_PipelineEncode_BatchStrided_UI16_Device(const char* pipeline, const void* const* d_srcs, const long* shapes,
+                                                                       const long* strides, unsigned shape_size, int nvolumes, void* d_dst,
+                                                                       long slot_capacity, long* offsets, long* lengths, int nthreads, void* hip_stream);
+SQY_FUNCTION_PREFIX int SQYAMD_PipelineEncode_BatchStrided_UI8_Device(const char* pipeline, const void* const* d_srcs, const long* shapes,
+                                                                      const long* strides, unsigned shape_size, int nvolumes, void* d_dst,
+                                                                      long slot_capacity, long* offsets, long* lengths, int nthreads, void* hip_stream);
 /* host-pointer variants: srcs[i] are host pointers, dst is host memory laid out the same way (only the blobs' bytes are written).  Every
  * volume is staged up, the device driver called once and the blobs brought back; the staging does not overlap with the encode */
 SQY_FUNCTION_PREFIX int SQYAMD_PipelineEncode_Batch_UI16(const char* pipeline, const char* const* srcs, const long* shapes, unsigned shape_size,
@@ -269,6 +286,20 @@ SQY_FUNCTION_PREFIX int SQYAMD_Decode_Batch_UI16_Device(const void* d_src, const
                                                         void* const* d_dsts, const long* dst_capacities, long* decoded_bytes, void* hip_stream);
 SQY_FUNCTION_PREFIX int SQYAMD_Decode_Batch_UI8_Device(const void* d_src, const long* offsets, const long* lengths, int nblobs,
                                                        void* const* d_dsts, const long* dst_capacities, long* decoded_bytes, void* hip_stream);
+/* _Batch_*_Device into views: blob i is decoded into the strided view d_dsts[i] of dst_shapes row i (shape_size longs) and dst_strides row
+ * i (voxels; the rules of SQYAMD_PipelineEncode_BatchStrided_*, checked on the host before anything is written; NULL: dense views, the
+ * call is _Batch_*_Device with the shapes checked).  The blob's header shape must equal its dst_shapes row, rank included (else 1 before
+ * anything is written).  Exactly the view's voxels are written: the voxels in the gaps between its rows and frames are not touched.  Two
+ * views of one call that overlap are the caller's error.  `bitswap1->lz4` and `lz4` blobs on the joint path are written into their views
+ * by the group's last launch; every other blob is decoded into a workspace place, and ONE launch at the end of the call unpacks them all
+ * ("batch_strided_fused" = 0: every blob).  Return codes, stream, context, ordering and thread safety as _Batch_*_Device; the offsets and
+ * lengths of SQYAMD_PipelineEncode_BatchStrided_* can be passed straight through. */
+SQY_FUNCTION_PREFIX int SQYAMD_Decode_BatchStrided_UI16_Device(const void* d_src, const long* offsets, const long* lengths, int nblobs,
+                                                               void* const* d_dsts, const long* dst_shapes, const long* dst_strides,
+                                                               unsigned shape_size, long* decoded_bytes, void* hip_stream);
+SQY_FUNCTION_PREFIX int SQYAMD_Decode_BatchStrided_UI8_Device(const void* d_src, const long* offsets, const long* lengths, int nblobs,
+                                                              void* const* d_dsts, const long* dst_shapes, const long* dst_strides,
+                                                              unsigned shape_size, long* decoded_bytes, void* hip_stream);
 /* host-pointer variants: blobs in host memory at src + offsets[i], dsts[i] host pointers (any alignment); arguments and headers are checked
  * on the host before any device is looked for */
 SQY_FUNCTION_PREFIX int SQYAMD_Decode_Batch_UI16(const char* src, const long* offsets, const long* lengths, int nblobs,
@@ -359,6 +390,9 @@ SQY_FUNCTION_PREFIX void SQYAMD_Release_Workspace(void);
  *                                     least one volume): bounds the workspace -- twice that and the tables
  *   "encode_batch_joint_max_bytes"    2^27 [SQY_ENCODE_BATCH_JOINT_MAX_BYTES=<bytes>, 0 .. 2^32-1]  .. a volume with more LZ4 input is encoded
  *                                     on its own, frames in place (the faster path for large stacks; the default is measured: DESIGN.md 5)
+ *   "batch_strided_fused"             1 [SQY_NO_BATCH_STRIDED_FUSED=1 -> 0]  SQYAMD_*_BatchStrided_*: the bitswap1 transposers gather from and scatter
+ *                                     into the views, `lz4` packs into the stream and unpacks from the LZ4 output (0: packed copies for every
+ *                                     pipeline -- same bytes)
  * Set: 0 = done, 1 = unknown name or value out of range.  Get: the value, -1 for an unknown name. */
 SQY_FUNCTION_PREFIX int SQYAMD_Set_Option(const char* name, long value);
 SQY_FUNCTION_PREFIX long SQYAMD_Get_Option(const char* name);

@@ -28,6 +28,8 @@ EXPORTED_SYMBOLS = (
     "SQYAMD_PipelineEncode_UI16_DeviceAt_Frames", "SQYAMD_PipelineEncode_UI8_DeviceAt_Frames",
     "SQYAMD_PipelineEncode_Slabs_UI16_Device", "SQYAMD_PipelineEncode_Slabs_UI8_Device",
     "SQYAMD_PipelineEncode_Batch_UI16_Device", "SQYAMD_PipelineEncode_Batch_UI8_Device", "SQYAMD_PipelineEncode_Batch_UI16", "SQYAMD_PipelineEncode_Batch_UI8",
+    "SQYAMD_PipelineEncode_BatchStrided_UI16_Device", "SQYAMD_PipelineEncode_BatchStrided_UI8_Device",
+    "SQYAMD_Decode_BatchStrided_UI16_Device", "SQYAMD_Decode_BatchStrided_UI8_Device",
     "SQYAMD_PipelineEncode_UI16_Cap", "SQYAMD_PipelineEncode_UI8_Cap",
     "SQYAMD_Decode_UI16_Device", "SQYAMD_Decode_UI8_Device",
     "SQYAMD_Decode_Frames_UI16_Device", "SQYAMD_Decode_Frames_UI8_Device", "SQYAMD_Decode_Frames_UI16", "SQYAMD_Decode_Frames_UI8",
@@ -83,6 +85,12 @@ def lib():
         for f in ("SQYAMD_PipelineEncode_Batch_UI8_Device", "SQYAMD_PipelineEncode_Batch_UI16_Device"):
             getattr(L, f).argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_void_p), c_long_p, ctypes.c_uint, ctypes.c_int, ctypes.c_void_p, ctypes.c_long,
                                       c_long_p, c_long_p, ctypes.c_int, ctypes.c_void_p]
+        for f in ("SQYAMD_PipelineEncode_BatchStrided_UI8_Device", "SQYAMD_PipelineEncode_BatchStrided_UI16_Device"):
+            getattr(L, f).argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_void_p), c_long_p, c_long_p, ctypes.c_uint, ctypes.c_int, ctypes.c_void_p,
+                                      ctypes.c_long, c_long_p, c_long_p, ctypes.c_int, ctypes.c_void_p]
+        for f in ("SQYAMD_Decode_BatchStrided_UI8_Device", "SQYAMD_Decode_BatchStrided_UI16_Device"):
+            getattr(L, f).argtypes = [ctypes.c_void_p, c_long_p, c_long_p, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), c_long_p, c_long_p, ctypes.c_uint,
+                                      c_long_p, ctypes.c_void_p]
         for f in ("SQYAMD_PipelineEncode_Batch_UI8", "SQYAMD_PipelineEncode_Batch_UI16"):
             getattr(L, f).argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_void_p), c_long_p, ctypes.c_uint, ctypes.c_int, ctypes.c_void_p, ctypes.c_long,
                                       c_long_p, c_long_p, ctypes.c_int]
@@ -242,6 +250,43 @@ def encode_batch_device(pipeline, d_srcs, shapes, dtype, d_dst, slot_capacity, n
     return rc, list(offs[:n]), list(lens[:n])
 
 
+def encode_batch_strided_device(pipeline, d_srcs, shapes, strides, dtype, d_dst, slot_capacity, nthreads=0, stream=None):
+    """SQYAMD_PipelineEncode_BatchStrided_*_Device: encode_batch_device for views -- volume i is the strided view at device pointer d_srcs[i]
+    with shape shapes[i] and strides[i] in VOXELS (outermost first, the innermost 1; strides None: dense volumes).  Returns (rc, offsets,
+    lengths), offsets relative to d_dst."""
+    n = len(d_srcs)
+    rank = len(shapes[0]) if n else 0
+    ptrs = (ctypes.c_void_p * max(n, 1))(*[int(p) for p in d_srcs])
+    flat = _longs([x for s in shapes for x in s]) if n else None
+    flat_strides = _longs([x for s in strides for x in s]) if n and strides is not None else None
+    offs = (ctypes.c_long * max(n, 1))()
+    lens = (ctypes.c_long * max(n, 1))()
+    rc = getattr(lib(), "SQYAMD_PipelineEncode_BatchStrided_%s_Device" % _suffix(dtype))(
+        pipeline.encode(), ptrs, flat, flat_strides, ctypes.c_uint(rank), ctypes.c_int(n), ctypes.c_void_p(int(d_dst)), ctypes.c_long(int(slot_capacity)),
+        offs, lens, ctypes.c_int(nthreads), ctypes.c_void_p(stream or 0))
+    return rc, list(offs[:n]), list(lens[:n])
+
+
+def tile_views(base_ptr, shape, tile, itemsize):
+    """The regular grid of tiles of a dense volume of `shape` at device pointer base_ptr (itemsize bytes a voxel), as views for
+    encode_batch_strided_device / decode_batch_strided_device: returns (ptrs, shapes, strides), tiles in row-major grid order, the tiles
+    at the high ends smaller where `tile` does not divide `shape`.  Strides are in voxels."""
+    shape, tile = [int(x) for x in shape], [int(x) for x in tile]
+    if len(shape) != len(tile) or not 1 <= len(shape) <= 3 or min(shape + tile) < 1:
+        raise ValueError("tile_views: shape and tile of one rank (1 to 3), positive extents")
+    strides = [1] * len(shape)
+    for k in range(len(shape) - 2, -1, -1):
+        strides[k] = strides[k + 1] * shape[k + 1]
+    ptrs, shapes = [], []
+    starts = [[]]
+    for k in range(len(shape)):
+        starts = [s + [o] for s in starts for o in range(0, shape[k], tile[k])]
+    for s in starts:
+        ptrs.append(int(base_ptr) + sum(o * st for o, st in zip(s, strides)) * int(itemsize))
+        shapes.append(tuple(min(t, d - o) for o, t, d in zip(s, tile, shape)))
+    return ptrs, shapes, [tuple(strides)] * len(ptrs)
+
+
 def encode_batch(pipeline, volumes, nthreads=0):
     """SQYAMD_PipelineEncode_Batch_UI8/UI16 on host ndarrays of one dtype and rank (shapes may differ); returns the list of blobs (bytes).
     Raises ValueError when the call returns non-zero."""
@@ -386,6 +431,21 @@ def decode_batch_device(d_src, offsets, lengths, d_dsts, dst_capacities, dtype, 
     rc = getattr(lib(), "SQYAMD_Decode_Batch_%s_Device" % _suffix(dtype))(
         ctypes.c_void_p(int(d_src)), _longs(offsets) if n else None, _longs(lengths) if n else None, ctypes.c_int(n), ptrs,
         _longs(dst_capacities) if n else None, decoded, ctypes.c_void_p(stream or 0))
+    return rc, list(decoded[:n])
+
+
+def decode_batch_strided_device(d_src, offsets, lengths, d_dsts, shapes, strides, dtype, stream=None):
+    """SQYAMD_Decode_BatchStrided_*_Device: blob i at d_src + offsets[i] (lengths[i] bytes) into the strided view at device pointer d_dsts[i]
+    with shape shapes[i] (the blob's own) and strides[i] in voxels (None: dense); only the view's voxels are written.  Returns (rc,
+    decoded_bytes).  The offsets and lengths of encode_batch_strided_device can be passed straight through."""
+    n = len(offsets)
+    rank = len(shapes[0]) if n else 0
+    ptrs = (ctypes.c_void_p * max(n, 1))(*[int(p) for p in d_dsts])
+    decoded = (ctypes.c_long * max(n, 1))()
+    rc = getattr(lib(), "SQYAMD_Decode_BatchStrided_%s_Device" % _suffix(dtype))(
+        ctypes.c_void_p(int(d_src)), _longs(offsets) if n else None, _longs(lengths) if n else None, ctypes.c_int(n), ptrs,
+        _longs([x for s in shapes for x in s]) if n else None, _longs([x for s in strides for x in s]) if n and strides is not None else None,
+        ctypes.c_uint(rank), decoded, ctypes.c_void_p(stream or 0))
     return rc, list(decoded[:n])
 
 

@@ -83,6 +83,7 @@ struct Options {
     std::atomic<long> encode_batch_joint;               // batch encode: the joint-eligible volumes of a group share one launch of every kernel (0: volume by volume)
     std::atomic<long> encode_batch_group_bytes;         // .. the LZ4 input one group holds at most (a group holds at least one volume)
     std::atomic<long> encode_batch_joint_max_bytes;     // .. a volume with more LZ4 input than this is encoded on its own (frames in place)
+    std::atomic<long> batch_strided_fused;              // strided views: the transposers gather from / scatter into the view, `lz4` packs into the stream and unpacks from the LZ4 output (0: packed copies everywhere)
     std::atomic<long> stage_lanes;                      // frames-in-place calls on caller streams run on the library's lanes: 0 never, 1 always, 2 where transpose_chain_caller_streams is on
     std::atomic<long> parse_lanes;                      // .. how many parse lanes a device has (1-8)
     // counters (Get reads, Set takes 0 only): calls that ran on the lanes; calls that stayed on their caller's stream because it had a
@@ -99,7 +100,8 @@ struct Options {
           decode_slabs_joint(env_flag("SQY_NO_DECODE_SLABS_JOINT") ? 0 : 1), decode_batch_joint(env_flag("SQY_NO_DECODE_BATCH_JOINT") ? 0 : 1),
           decode_batch_group_bytes(env_number("SQY_DECODE_BATCH_GROUP_BYTES", (long)kSlabsGroupBytes, 1, (long)kSlabsGroupBytes)), encode_batch_joint(env_flag("SQY_NO_ENCODE_BATCH_JOINT") ? 0 : 1),
           encode_batch_group_bytes(env_number("SQY_ENCODE_BATCH_GROUP_BYTES", kBatchGroupBytesDefault, 1, kBatchBytesMax)),
-          encode_batch_joint_max_bytes(env_number("SQY_ENCODE_BATCH_JOINT_MAX_BYTES", kBatchJointMaxDefault, 0, kBatchBytesMax)), stage_lanes(env_number("SQY_STAGE_LANES", kStageLanesDefault, 0, 2)),
+          encode_batch_joint_max_bytes(env_number("SQY_ENCODE_BATCH_JOINT_MAX_BYTES", kBatchJointMaxDefault, 0, kBatchBytesMax)),
+          batch_strided_fused(env_flag("SQY_NO_BATCH_STRIDED_FUSED") ? 0 : 1), stage_lanes(env_number("SQY_STAGE_LANES", kStageLanesDefault, 0, 2)),
           parse_lanes(env_number("SQY_PARSE_LANES", kParseLanesDefault, 1, sqy::LanePicker::kMaxLanes)) { sqy::set_bitswap1_blocks_per_cu(transpose_blocks_per_cu.load()); }
     std::atomic<long>* find(const char* name)
     {
@@ -122,6 +124,7 @@ struct Options {
         if (!std::strcmp(name, "encode_batch_joint")) return &encode_batch_joint;
         if (!std::strcmp(name, "encode_batch_group_bytes")) return &encode_batch_group_bytes;
         if (!std::strcmp(name, "encode_batch_joint_max_bytes")) return &encode_batch_joint_max_bytes;
+        if (!std::strcmp(name, "batch_strided_fused")) return &batch_strided_fused;
         if (!std::strcmp(name, "stage_lanes")) return &stage_lanes;
         if (!std::strcmp(name, "parse_lanes")) return &parse_lanes;
         if (!std::strcmp(name, "lane_calls")) return &lane_calls;
@@ -313,6 +316,9 @@ struct Workspace {
     DevBuf batch_tables;      // .. the tables a group uploads (chunks, volumes, transposer jobs, header text) and what the kernels hand each other
     DevBuf batch_quant;       // .. quantiser->bitswap1->lz4: every volume's histogram, then every encode LUT, then every decode LUT
     HostBuf batch_host;       // .. the records of every volume, the staging area of the upload
+    DevBuf batch_pack;        // strided views: the packed copies of a group's views (encode), the dense places of a call's views (decode)
+    DevBuf batch_pack_one;    // .. decode: the dense place of a view whose blob is decoded on its own
+    DevBuf batch_views[3];    // .. the job and tile tables of the view launches: pack / unpack, the strided transposer, the strided copy
     void* pinned = nullptr;   // 4 KiB of pinned host memory for small read-backs
     void release_buffers()
     {
@@ -320,6 +326,7 @@ struct Workspace {
         io_src.release(); io_dst.release(); small.release(); plan.release(); dedupe.release(); diff_side.release(); spec.release(); digest.release(); bkrd.release();
         subset.release(); range_full.release(); slabs_index.release(); slabs_joint.release(); slabs_out.release(); slabs_host.release();
         batch_stream.release(); batch_scratch.release(); batch_tables.release(); batch_quant.release(); batch_host.release();
+        batch_pack.release(); batch_pack_one.release(); for (DevBuf& b : batch_views) b.release();
     }
 };
 
@@ -2342,6 +2349,84 @@ int decode_from_host(const char* src, long srclength, char* dst, int elem_size)
     });
 }
 
+// ---- strided views (SQYAMD_PipelineEncode_BatchStrided_*, SQYAMD_Decode_BatchStrided_*) ---------------------------------------------------
+// A view is admitted on the host (sqy::admit_view: the stride rules, folded) before the device is touched.  A dense view is the Batch
+// entry points' volume.  For the others, layer one: packed copies -- one batch_pack launch per encode group into Workspace::batch_pack in
+// front of the Batch drivers, one batch_unpack launch per decode call behind them.  Layer two (the option batch_strided_fused): the
+// bitswap1 transposers gather from and scatter into the view, `lz4` packs into the stream and unpacks from the LZ4 output.
+static_assert(sizeof(sqy::BatchViewJob) == sqy::kBatchViewJobBytes, "the view job's layout");
+
+// The jobs of one view launch and their tile table (tiles of sqy::kBatchTileVoxels voxels).  `host` is the upload's source (pageable): it
+// must outlive the copy, so a launch that has been queued is waited for before its tables go -- on every way out of the scope that owns
+// it, the error returns included (behind a call's own synchronisation the wait finds the stream idle)
+struct ViewLaunch {
+    enum Kind { pack, unpack, bitswap1, bitswap1_decode, copy_to_view };
+    std::vector<sqy::BatchViewJob> jobs;
+    std::vector<uint32_t> first_tile;
+    uint32_t ntiles = 0;
+    std::vector<unsigned char> host;
+    hipStream_t queued_on = nullptr;
+    bool queued = false;
+    ViewLaunch() = default;
+    ViewLaunch(const ViewLaunch&) = delete;
+    ViewLaunch& operator=(const ViewLaunch&) = delete;
+    ~ViewLaunch() { wait(); }
+    void wait() { if (queued) (void)hipStreamSynchronize(queued_on); queued = false; }
+    void clear() { wait(); jobs.clear(); first_tile.clear(); ntiles = 0; host.clear(); }
+    void add(const void* view, const void* dense, const sqy::BatchView& v)
+    {
+        jobs.push_back(sqy::BatchViewJob{const_cast<void*>(view), const_cast<void*>(dense), v.Z, v.Y, v.X, v.sz, v.sy});
+        first_tile.push_back(ntiles);
+        ntiles += sqy::batch_bitswap1_tiles(v.Z * v.Y * v.X);
+    }
+};
+// the tables to Workspace::batch_views[slot], the launch behind them under its profile name; no jobs: nothing
+int launch_views(Context& cx, hipStream_t stream, ViewLaunch& l, ViewLaunch::Kind kind, int slot, int elem_size)
+{
+    if (l.jobs.empty()) return 0;
+    std::vector<PendingEvent>* pend = &cx.pending;
+    const size_t nj = l.jobs.size(), jobs_bytes = nj * sizeof(sqy::BatchViewJob), tiles_at = (jobs_bytes + 15) & ~(size_t)15;
+    l.first_tile.push_back(l.ntiles);
+    l.host.assign(tiles_at + (nj + 1) * 4, 0);
+    std::memcpy(l.host.data(), l.jobs.data(), jobs_bytes);
+    std::memcpy(l.host.data() + tiles_at, l.first_tile.data(), (nj + 1) * 4);
+    DevBuf& buf = cx.ws.batch_views[slot];
+    if (buf.ensure(l.host.size())) return 1;
+    l.queued_on = stream;
+    l.queued = true;
+    SQY_HIP(hipMemcpyAsync(buf.p, l.host.data(), l.host.size(), hipMemcpyHostToDevice, stream));
+    const sqy::BatchViewJob* d_jobs = static_cast<const sqy::BatchViewJob*>(buf.p);
+    const uint32_t* d_tiles = reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(buf.p) + tiles_at);
+    switch (kind) {
+    case ViewLaunch::pack: SQY_TIMED("batch_pack", sqy::launch_batch_view_copy(d_jobs, d_tiles, (uint32_t)nj, l.ntiles, elem_size, false, stream)); break;
+    case ViewLaunch::unpack: SQY_TIMED("batch_unpack", sqy::launch_batch_view_copy(d_jobs, d_tiles, (uint32_t)nj, l.ntiles, elem_size, true, stream)); break;
+    case ViewLaunch::bitswap1: SQY_TIMED("batch_bitswap1_strided", sqy::launch_bitswap1_batch_strided(d_jobs, d_tiles, (uint32_t)nj, l.ntiles, elem_size, stream)); break;
+    case ViewLaunch::bitswap1_decode:
+        SQY_TIMED("batch_bitswap1_decode_strided", sqy::launch_bitswap1_decode_batch_strided(d_jobs, d_tiles, (uint32_t)nj, l.ntiles, elem_size, stream));
+        break;
+    case ViewLaunch::copy_to_view:      // (batch decode, plain `lz4` blobs: the copy out of the LZ4 output is the unpack)
+        SQY_TIMED("batch_copy_strided", sqy::launch_batch_view_copy(d_jobs, d_tiles, (uint32_t)nj, l.ntiles, elem_size, true, stream));
+        break;
+    }
+    return 0;
+}
+// The caller's view table on the host, before the device is touched: views[i] admitted from row i of shapes and strides (strides nullptr:
+// every view dense), ptrs[i] aligned to the voxel size.  1 with a message: a view that breaks a rule
+int admit_views(const char* who, const void* const* ptrs, const long* shapes, const long* strides, unsigned rank, int n, int elem_size, std::vector<sqy::BatchView>* views)
+{
+    if (rank == 0 || rank > 3) { std::fprintf(stderr, "[sqeazy]\t %s: views have 1 to 3 dimensions, not %u\n", who, rank); return 1; }
+    views->resize((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        if (!ptrs[i]) return 1;
+        if (reinterpret_cast<uintptr_t>(ptrs[i]) % (uintptr_t)elem_size) { std::fprintf(stderr, "[sqeazy]\t %s: view %d not aligned to the voxel size\n", who, i); return 1; }
+        if (!sqy::admit_view(shapes + (size_t)i * rank, strides ? strides + (size_t)i * rank : nullptr, rank, &(*views)[(size_t)i])) {
+            std::fprintf(stderr, "[sqeazy]\t %s: view %d: the innermost stride must be 1, every stride positive and no smaller than the extent times the stride of the next dimension\n", who, i);
+            return 1;
+        }
+    }
+    return 0;
+}
+
 // ---- z-slab blob sets (SQYAMD_Decode_Slabs_*) and batches (SQYAMD_Decode_Batch_*): a group on the joint path -----------------
 // Blobs in the chunked LZ4 layout are decoded in groups.  What both callers share, one function per step: the frame ranking of every blob
 // of a group in one launch per kernel and one read-back (group_rank), one joint block index and one LZ4 decode launch for all of them
@@ -2543,8 +2628,15 @@ int decode_slabs_group(Context& cx, const uint8_t* d_src, std::vector<SlabBlob>&
 // the `bitswap1->lz4` blobs: ONE inverse-transpose launch from the workspace into their destinations -- and into the workspace for the
 // `diff3x3x1->bitswap1->lz4` blobs --; the `lz4` blobs: ONE copy launch; the `quantiser->bitswap1->lz4` blobs: ONE launch of the transposer
 // with the look-up; the 16-bit diff3x3x1 blobs in the chain geometry: ONE launch per chain step (launch_diff3x3x1_decode_batch_copy, _step)
+// A batch of views (sv != nullptr): the planes and plain blobs whose destination is a view that takes the voxels directly leave the dense
+// launches' tables for sv->scatter and sv->copy (alive as `tables` is) -- one batch_bitswap1_decode_strided, one batch_copy_strided launch
+struct StridedDecode {
+    const std::vector<sqy::BatchView>* views = nullptr;
+    std::vector<uint8_t> direct;            // per blob: 1 = the joint path's last launch writes into the view
+    ViewLaunch scatter, copy;
+};
 int batch_group_tail(JointGroup& G, const sqy::DecodeJointLayout& L, const sqy::DecodeBatchGroup& pg, const std::vector<sqy::DecodeBatchBlob>& plan_in, int elem_size,
-                     std::vector<unsigned char>& tables)
+                     std::vector<unsigned char>& tables, StridedDecode* sv = nullptr)
 {
     std::vector<PendingEvent>* pend = &G.cx.pending;
     hipStream_t stream = G.stream;
@@ -2555,17 +2647,28 @@ int batch_group_tail(JointGroup& G, const sqy::DecodeJointLayout& L, const sqy::
     for (size_t j = 0; j < df.jobs.size(); ++j) res_of[df.jobs[j]] = df.res_at[j];
     const sqy::DecodeBatchTiles* tt[3] = {&pg.planes, &pg.plain, &pg.quantised};
     const sqy::DecodeJointLayout::Family* ff[3] = {&L.planes, &L.plain, &L.quantised};
+    size_t dense_jobs[3] = {0, 0, 0};                                   // what stays in the dense launches' tables
+    uint32_t dense_tiles[3] = {0, 0, 0};
     for (int k = 0; k < 3; ++k) {
         const size_t nj = tt[k]->jobs.size();
+        std::vector<uint32_t> first_tile;
         for (size_t j = 0; j < nj; ++j) {
             const uint32_t b = tt[k]->jobs[j];
             const SlabBlob& s = G.blobs[b];
+            if (sv && sv->direct[b] == 1 && plan_in[b].form != sqy::DecodeBatchForm::diff_planes) {
+                (k == 0 ? sv->scatter : sv->copy).add(s.call->d_dst, G.out + s.out_base, (*sv->views)[b]);
+                continue;
+            }
             void* to = plan_in[b].form == sqy::DecodeBatchForm::diff_planes ? static_cast<void*>(G.out + res_of[b]) : s.call->d_dst;
             const sqy::Bitswap1Job job{G.out + s.out_base, to, plan_in[b].len};
-            std::memcpy(host(ff[k]->jobs_at) + j * sizeof(job), &job, sizeof(job));
-            if (tt[k] == &pg.quantised) std::memcpy(host(ff[k]->extra_at) + j * 512, s.lut.data(), 512);
+            std::memcpy(host(ff[k]->jobs_at) + dense_jobs[k] * sizeof(job), &job, sizeof(job));
+            if (tt[k] == &pg.quantised) std::memcpy(host(ff[k]->extra_at) + dense_jobs[k] * 512, s.lut.data(), 512);
+            first_tile.push_back(dense_tiles[k]);
+            dense_tiles[k] += tt[k]->first_tile[j + 1] - tt[k]->first_tile[j];
+            ++dense_jobs[k];
         }
-        std::memcpy(host(ff[k]->tiles_at), tt[k]->first_tile.data(), (nj + 1) * 4);
+        first_tile.push_back(dense_tiles[k]);
+        std::memcpy(host(ff[k]->tiles_at), first_tile.data(), first_tile.size() * 4);
     }
     const uint32_t nd = (uint32_t)df.jobs.size();
     for (uint32_t j = 0; j < nd; ++j) {
@@ -2579,12 +2682,14 @@ int batch_group_tail(JointGroup& G, const sqy::DecodeJointLayout& L, const sqy::
     if (L.jobs_bytes) SQY_HIP(hipMemcpyAsync(dj + L.jobs_upload_at, tables.data(), L.jobs_bytes, hipMemcpyHostToDevice, stream));
     auto jobs = [&](const sqy::DecodeJointLayout::Family& f) { return reinterpret_cast<const sqy::Bitswap1Job*>(dj + f.jobs_at); };
     auto words = [&](uint64_t at) { return reinterpret_cast<const uint32_t*>(dj + at); };
-    if (pg.planes.ntiles)
-        SQY_TIMED("batch_bitswap1_decode", sqy::launch_bitswap1_decode_batch(jobs(L.planes), words(L.planes.tiles_at), (uint32_t)pg.planes.jobs.size(), pg.planes.ntiles, elem_size, stream));
-    if (pg.plain.ntiles) SQY_TIMED("batch_copy", sqy::launch_batch_copy(jobs(L.plain), words(L.plain.tiles_at), (uint32_t)pg.plain.jobs.size(), pg.plain.ntiles, stream));
-    if (pg.quantised.ntiles)
+    if (dense_tiles[0])
+        SQY_TIMED("batch_bitswap1_decode", sqy::launch_bitswap1_decode_batch(jobs(L.planes), words(L.planes.tiles_at), (uint32_t)dense_jobs[0], dense_tiles[0], elem_size, stream));
+    if (dense_tiles[1]) SQY_TIMED("batch_copy", sqy::launch_batch_copy(jobs(L.plain), words(L.plain.tiles_at), (uint32_t)dense_jobs[1], dense_tiles[1], stream));
+    if (dense_tiles[2])
         SQY_TIMED("batch_quantiser_decode", sqy::launch_bitswap1_quantiser_decode_batch(jobs(L.quantised), words(L.quantised.tiles_at), reinterpret_cast<const uint16_t*>(dj + L.quantised.extra_at),
-                                                                                         (uint32_t)pg.quantised.jobs.size(), pg.quantised.ntiles, stream));
+                                                                                         (uint32_t)dense_jobs[2], dense_tiles[2], stream));
+    if (sv && (launch_views(G.cx, stream, sv->scatter, ViewLaunch::bitswap1_decode, 1, elem_size) || launch_views(G.cx, stream, sv->copy, ViewLaunch::copy_to_view, 2, elem_size)))
+        return 1;
     if (nd) {
         // (every launch timed on its own: the profile counts the launches, 1 + steps whatever the number of blobs)
         const sqy::DiffBatchJob* d_diff = reinterpret_cast<const sqy::DiffBatchJob*>(dj + L.diff.jobs_at);
@@ -2599,8 +2704,9 @@ int batch_group_tail(JointGroup& G, const sqy::DecodeJointLayout& L, const sqy::
 // `single`; the flag raised: all of the group go there.  Every destination is an allocation of its own, so the LZ4 output always goes to
 // the workspace, where the plan says (out_at); the pipelines without a batched launch run their remaining inverses as in a slab set.
 int decode_batch_group(Context& cx, const uint8_t* d_src, std::vector<SlabBlob>& blobs, const std::vector<sqy::DecodeBatchBlob>& plan_in, uint64_t group_bytes,
-                       const sqy::DecodeBatchPlan& plan, size_t gi, int elem_size, hipStream_t stream, std::vector<size_t>& single)
+                       const sqy::DecodeBatchPlan& plan, size_t gi, int elem_size, hipStream_t stream, std::vector<size_t>& single, StridedDecode* sv = nullptr)
 {
+    if (sv) { sv->scatter.clear(); sv->copy.clear(); }                  // (the group before has been synchronised)
     const sqy::DecodeBatchGroup* pg = &plan.groups[gi];
     const std::vector<size_t> g(pg->blobs.begin(), pg->blobs.end());
     for (size_t k = 0; k < g.size(); ++k) blobs[g[k]].out_base = pg->out_at[k];
@@ -2622,7 +2728,7 @@ int decode_batch_group(Context& cx, const uint8_t* d_src, std::vector<SlabBlob>&
     const sqy::DecodeJointLayout L = sqy::decode_joint_layout(G.mem.size(), G.maps.size(), G.nframes, pg);
     if (const int rc = group_lz4_decode(G, L)) return rc;
     std::vector<unsigned char> tables;
-    if (const int rc = batch_group_tail(G, L, *pg, plan_in, elem_size, tables)) return rc;
+    if (const int rc = batch_group_tail(G, L, *pg, plan_in, elem_size, tables, sv)) return rc;
     std::vector<size_t> rest;                                           // everything else: blob by blob, as in a slab set
     for (size_t b : G.mem) if (plan_in[b].form == sqy::DecodeBatchForm::stages) rest.push_back(b);
     if (const int rc = group_remaining_stages(G, rest)) return rc;
@@ -2800,9 +2906,14 @@ void batch_stage_form(SlabBlob& b, const void* dst, int want_elem, sqy::DecodeBa
     }
 }
 
-int decode_batch_on_device(Context& cx, const void* d_src_v, const BatchDecodeArgs& a, int want_elem, hipStream_t stream)
+// views (SQYAMD_Decode_BatchStrided_*): blob i's header shape must be row i of shapes (rank dimensions); a.dsts[i] is view i
+int decode_batch_on_device(Context& cx, const void* d_src_v, const BatchDecodeArgs& a, int want_elem, hipStream_t stream,
+                           const std::vector<sqy::BatchView>* views = nullptr, const long* shapes = nullptr, unsigned rank = 0)
 {
     const uint8_t* d_src = static_cast<const uint8_t*>(d_src_v);
+    StridedDecode sv;
+    sv.views = views;
+    ViewLaunch unpacks;                                                 // (in front of the drain: alive until it has synchronised)
     DrainOnExit drain{stream, &cx.pending, cx.side};
     const size_t n = (size_t)a.nblobs;
     std::vector<SlabBlob> blobs(n);
@@ -2811,18 +2922,51 @@ int decode_batch_on_device(Context& cx, const void* d_src_v, const BatchDecodeAr
         blobs[i].len = (uint64_t)a.lengths[i];
     }
     // 1. the headers, checked before anything is written
-    if (fetch_blob_headers(cx, blobs, want_elem, stream, "decode batch", [&](int i) { return batch_blob_fits(i, blobs[i].raw, a.dsts[i], a.capacities[i], want_elem); }))
+    if (fetch_blob_headers(cx, blobs, want_elem, stream, "decode batch", [&](int i) {
+            if (views) {
+                const std::vector<uint64_t>& hs = blobs[i].h.shape;
+                bool same = hs.size() == rank;
+                for (unsigned k = 0; same && k < rank; ++k) same = hs[k] == (uint64_t)shapes[(size_t)i * rank + k];
+                if (!same) { std::fprintf(stderr, "[sqeazy]\t decode batch: blob %d's shape is not its view's\n", i); return false; }
+            }
+            return batch_blob_fits(i, blobs[i].raw, a.dsts[i], a.capacities[i], want_elem);
+        }))
         return 1;
     if (a.decoded) for (size_t i = 0; i < n; ++i) a.decoded[i] = (long)blobs[i].raw;
+    const bool joint_on = g_opt.decode_batch_joint.load() != 0;
+    // where blob i's voxels go as a dense volume: its destination -- or, for a view that is no dense allocation, a place in
+    // Workspace::batch_pack, unpacked by ONE launch at the end of the call; unless (batch_strided_fused) its pipeline is one whose last
+    // launch on the joint path can write into the view: `bitswap1->lz4`, `lz4`
+    std::vector<void*> dst_of(a.dsts, a.dsts + n);
+    bool strided = false;
+    if (views) {
+        const bool fused = joint_on && g_opt.batch_strided_fused.load() != 0;
+        sv.direct.assign(n, 0);
+        std::vector<uint64_t> place(n, 0);
+        uint64_t bytes = 0;
+        for (size_t i = 0; i < n; ++i) {
+            if ((*views)[i].dense) continue;
+            strided = true;
+            const std::vector<Stage> st = Pipeline::from_string(blobs[i].h.pipename).stages;
+            if (fused && !st.empty() && st.back().kind == StageKind::lz4 && (st.size() == 1 || (st.size() == 2 && st[0].kind == StageKind::bitswap1))) sv.direct[i] = 1;
+            else { place[i] = bytes; bytes += align_up(blobs[i].raw, 256); }
+        }
+        if (bytes && cx.ws.batch_pack.ensure(bytes)) return 1;
+        for (size_t i = 0; i < n; ++i)
+            if (!(*views)[i].dense && !sv.direct[i]) {
+                dst_of[i] = static_cast<uint8_t*>(cx.ws.batch_pack.p) + place[i];
+                unpacks.add(a.dsts[i], dst_of[i], (*views)[i]);
+            }
+    }
+    StridedDecode* const svp = strided ? &sv : nullptr;
 
     // 2. who takes the joint path and in which group (the plan: host-only, sqy_pipeline.cpp)
     std::vector<sqy::DecodeBatchBlob> plan_in(n);
     std::vector<size_t> single;
-    const bool joint_on = g_opt.decode_batch_joint.load() != 0;
     for (size_t i = 0; i < n && joint_on; ++i) {
         SlabBlob& b = blobs[i];
         sqy::DecodeBatchBlob& p = plan_in[i];
-        p.eligible = joint_candidate(cx, b, a.dsts[i], want_elem, stream, 1);
+        p.eligible = joint_candidate(cx, b, dst_of[i], want_elem, stream, 1);
         if (!p.eligible) continue;
         const DecodeCall& c = *b.call;
         const std::vector<Stage>& st = c.pipe.stages;
@@ -2833,19 +2977,57 @@ int decode_batch_on_device(Context& cx, const void* d_src_v, const BatchDecodeAr
             p.form = sqy::DecodeBatchForm::planes;
             p.len = c.n;
         } else
-            batch_stage_form(b, a.dsts[i], want_elem, p);
+            batch_stage_form(b, dst_of[i], want_elem, p);
+        // (a view that was to take its voxels directly and has no such form after all: on its own, below)
+        if (svp && sv.direct[i] && p.form != sqy::DecodeBatchForm::planes && p.form != sqy::DecodeBatchForm::plain) p.eligible = false;
     }
     const uint64_t group_bytes = (uint64_t)g_opt.decode_batch_group_bytes.load();
     const sqy::DecodeBatchPlan plan = sqy::decode_batch_plan(plan_in, group_bytes);
     for (size_t i = 0; i < n; ++i) if (plan.group_of[i] < 0) single.push_back(i);
     for (size_t gi = 0; gi < plan.groups.size(); ++gi)
-        if (const int rc = decode_batch_group(cx, d_src, blobs, plan_in, group_bytes, plan, gi, want_elem, stream, single)) return rc;
+        if (const int rc = decode_batch_group(cx, d_src, blobs, plan_in, group_bytes, plan, gi, want_elem, stream, single, svp)) return rc;
     // 3. the others, one at a time, in blob order
     std::sort(single.begin(), single.end());
-    for (size_t b : single)
-        blobs[b].rc = decode_on_device(cx, blobs[b].src, blobs[b].len, a.dsts[b], blobs[b].raw, want_elem, stream);
+    for (size_t b : single) {
+        if (!svp || !sv.direct[b]) {
+            blobs[b].rc = decode_on_device(cx, blobs[b].src, blobs[b].len, dst_of[b], blobs[b].raw, want_elem, stream);
+            continue;
+        }
+        // a view without a place in the workspace: decoded into one of its own, unpacked
+        if (cx.ws.batch_pack_one.ensure(blobs[b].raw)) return 1;
+        blobs[b].rc = decode_on_device(cx, blobs[b].src, blobs[b].len, cx.ws.batch_pack_one.p, blobs[b].raw, want_elem, stream);
+        if (blobs[b].rc) continue;
+        ViewLaunch one;
+        one.add(a.dsts[b], cx.ws.batch_pack_one.p, (*views)[b]);
+        if (launch_views(cx, stream, one, ViewLaunch::unpack, 0, want_elem)) return 1;
+        SQY_HIP(hipStreamSynchronize(stream));                          // (the launch's tables are this scope's)
+    }
+    // 4. the views with a place in the workspace: ONE unpack launch
+    if (svp && launch_views(cx, stream, unpacks, ViewLaunch::unpack, 0, want_elem)) return 1;
     for (const SlabBlob& b : blobs) if (b.rc) return b.rc;
     return 0;
+}
+
+// SQYAMD_Decode_BatchStrided_*: the arguments and every view on the host, then the batch driver with the views
+int decode_batch_strided_device(const void* d_src, const long* offsets, const long* lengths, int nblobs, void* const* d_dsts, const long* dst_shapes,
+                                const long* dst_strides, unsigned rank, long* decoded, int elem_size, void* hip_stream)
+{
+    if (decoded && nblobs > 0) for (int i = 0; i < nblobs; ++i) decoded[i] = 0;
+    if (!d_src || !offsets || !lengths || !d_dsts || !dst_shapes || nblobs <= 0) { std::fprintf(stderr, "[sqeazy]\t decode batch: bad arguments\n"); return 1; }
+    std::vector<sqy::BatchView> views;
+    if (admit_views("decode batch", d_dsts, dst_shapes, dst_strides, rank, nblobs, elem_size, &views)) return 1;
+    std::vector<long> caps((size_t)nblobs);
+    for (int i = 0; i < nblobs; ++i) {
+        const sqy::BatchView& v = views[(size_t)i];
+        const uint64_t bytes = v.Z * v.Y * v.X * (uint64_t)elem_size;
+        if (bytes > (uint64_t)LONG_MAX) return 1;
+        caps[(size_t)i] = (long)bytes;
+    }
+    const BatchDecodeArgs a{offsets, lengths, nblobs, d_dsts, caps.data(), decoded};
+    if (admit_decode_batch(d_src, a)) return 1;
+    ContextLease lease;
+    if (!lease.ctx) { std::fprintf(stderr, "[sqeazy]\t no usable HIP device\n"); return 1; }
+    return decode_batch_on_device(*lease.ctx, d_src, a, elem_size, static_cast<hipStream_t>(hip_stream), &views, dst_shapes, rank);
 }
 
 int decode_batch_device(const void* d_src, const BatchDecodeArgs& a, int elem_size, void* hip_stream)
@@ -2944,8 +3126,11 @@ int admit_batch(const char* pipeline, const void* const* srcs, const long* shape
 
 // one group of the plan through the kernels; rc 1 with a message when a blob does not fit its slot (nothing of that volume is written).
 // staging: pinned, sqy::encode_batch_layout's staging_bytes for the group at its worst-case text
+// views (nullptr: every volume dense) with how[vol], sqy ViewRead: how a volume that is no dense allocation is read
+enum ViewRead : uint8_t { in_place = 0, gathered, packed_to_stream, packed };
 int encode_batch_group(Context& cx, const BatchAdmit& a, const sqy::Lz4BatchGroup& g, sqy::EncodeBatchForm form, int elem_size, const void* const* d_srcs,
-                       uint8_t* d_dst, uint64_t slot_capacity, long* offsets, long* lengths, uint64_t* records, uint8_t* staging, hipStream_t stream)
+                       uint8_t* d_dst, uint64_t slot_capacity, long* offsets, long* lengths, uint64_t* records, uint8_t* staging, hipStream_t stream,
+                       const std::vector<sqy::BatchView>* views = nullptr, const std::vector<uint8_t>* how = nullptr)
 {
     Workspace* ws = &cx.ws;
     std::vector<PendingEvent>* pend = &cx.pending;
@@ -2973,10 +3158,21 @@ int encode_batch_group(Context& cx, const BatchAdmit& a, const sqy::Lz4BatchGrou
     // trip 1 when the text is known only then --, and behind it what the kernels hand each other
     const sqy::EncodeBatchLayout L = sqy::encode_batch_layout(nc, nv, quantised, quantised ? nv * sqy::kBatchHeaderTextMax : text_bytes);
     if (ws->batch_tables.ensure(L.tables) || ws->batch_scratch.ensure(std::max<uint64_t>(nc * g.scratch_stride, 16))) return 1;
-    if (transpose && ws->batch_stream.ensure(std::max<uint64_t>(g.stream_bytes, 16))) return 1;
+    // the views of the group that are no dense allocations: the packed copies' places in Workspace::batch_pack (16-byte aligned)
+    auto read_of = [&](uint32_t vol) { return how ? (ViewRead)(*how)[vol] : in_place; };
+    std::vector<uint64_t> place(nv, 0);
+    uint64_t pack_bytes = 0;
+    bool to_stream = false;
+    for (size_t j = 0; j < nv; ++j) {
+        if (read_of(g.vols[j]) == packed) { place[j] = pack_bytes; pack_bytes += (a.len[g.vols[j]] * (uint64_t)elem_size + 15) & ~(uint64_t)15; }
+        to_stream = to_stream || read_of(g.vols[j]) == packed_to_stream;
+    }
+    if (pack_bytes && ws->batch_pack.ensure(pack_bytes)) return 1;
+    if ((transpose || to_stream) && ws->batch_stream.ensure(std::max<uint64_t>(g.stream_bytes, 16))) return 1;
     if (quantised && ws->batch_quant.ensure(nv * sqy::kQuantiserBatchTableBytes)) return 1;
     uint8_t* const d_tab = static_cast<uint8_t*>(ws->batch_tables.p);
     uint8_t* const d_stream = transpose ? static_cast<uint8_t*>(ws->batch_stream.p) : nullptr;
+    ViewLaunch packs, gathers;
 
     sqy::Lz4BatchChunk* h_table = reinterpret_cast<sqy::Lz4BatchChunk*>(staging + L.table_at);
     uint32_t* h_volof = reinterpret_cast<uint32_t*>(staging + L.volof_at);
@@ -3000,20 +3196,35 @@ int encode_batch_group(Context& cx, const BatchAdmit& a, const sqy::Lz4BatchGrou
         }
     };
     if (!quantised) fill_volumes();
+    size_t njobs = 0;                                                   // the jobs of the dense transposer: every volume but the gathered views
     for (size_t j = 0; j < nv; ++j) {
         const uint32_t vol = g.vols[j];
-        h_jobs[j] = sqy::Bitswap1Job{d_srcs[vol], d_stream ? d_stream + g.stream_at[j] : nullptr, a.len[vol]};
-        h_tiles[j] = ntiles;
-        ntiles += sqy::batch_bitswap1_tiles(a.len[vol]);
+        const ViewRead read = read_of(vol);
+        // where the volume's voxels are dense: its own allocation, its packed copy -- or (plain lz4, packed_to_stream) its stream
+        const void* src = d_srcs[vol];
+        if (read == packed) {
+            src = static_cast<uint8_t*>(ws->batch_pack.p) + place[j];
+            packs.add(d_srcs[vol], src, (*views)[vol]);
+        } else if (read == packed_to_stream) {
+            src = static_cast<uint8_t*>(ws->batch_stream.p) + g.stream_at[j];
+            packs.add(d_srcs[vol], src, (*views)[vol]);
+        }
+        if (read == gathered)
+            gathers.add(d_srcs[vol], d_stream + g.stream_at[j], (*views)[vol]);
+        else {
+            h_jobs[njobs] = sqy::Bitswap1Job{src, d_stream ? d_stream + g.stream_at[j] : nullptr, a.len[vol]};
+            h_tiles[njobs++] = ntiles;
+            ntiles += sqy::batch_bitswap1_tiles(a.len[vol]);
+        }
         for (uint32_t e = g.first_chunk[j]; e < g.first_chunk[j + 1]; ++e) {
             const sqy::Lz4BatchChunkPlan& c = g.chunks[e];
             // (plain lz4: the stream IS the volume -- the entry's offset counts from address 0)
-            const uint64_t off = transpose ? c.off : (uint64_t)reinterpret_cast<uintptr_t>(d_srcs[vol]) + (c.off - g.stream_at[j]);
+            const uint64_t off = transpose ? c.off : (uint64_t)reinterpret_cast<uintptr_t>(src) + (c.off - g.stream_at[j]);
             h_table[e] = sqy::Lz4BatchChunk{off, c.n, c.vol, c.slot, 0};
             h_volof[e] = (uint32_t)j;
         }
     }
-    h_tiles[nv] = ntiles;
+    h_tiles[njobs] = ntiles;
     SQY_HIP(hipMemcpyAsync(d_tab, staging, quantised ? L.vols_at : L.upload, hipMemcpyHostToDevice, stream));
 
     const sqy::Lz4BatchChunk* d_table = reinterpret_cast<const sqy::Lz4BatchChunk*>(d_tab + L.table_at);
@@ -3030,12 +3241,15 @@ int encode_batch_group(Context& cx, const BatchAdmit& a, const sqy::Lz4BatchGrou
     uint8_t* const d_luts = quantised ? static_cast<uint8_t*>(ws->batch_quant.p) + nv * sqy::kQuantiserBatchHistoBytes : nullptr;
     uint16_t* const d_decode = quantised ? reinterpret_cast<uint16_t*>(d_luts + nv * sqy::kQuantiserBatchLutBytes) : nullptr;
     uint16_t* const h_decode = reinterpret_cast<uint16_t*>(staging + L.decode_at);     // (pinned, behind the staging area of the upload)
+    if (launch_views(cx, stream, packs, ViewLaunch::pack, 0, elem_size)) return 1;
     if (quantised) {
         SQY_TIMED("batch_quantiser_histogram", sqy::launch_batch_quantiser_histogram(d_jobs, d_tiles, (uint32_t)nv, ntiles, d_histos, stream));
         SQY_TIMED("batch_quantiser_lut", sqy::launch_batch_quantiser_lut(d_histos, (uint32_t)nv, d_luts, d_decode, stream));
         SQY_TIMED("batch_quantiser_bitswap1", sqy::launch_batch_quantiser_bitswap1(d_jobs, d_tiles, (uint32_t)nv, ntiles, d_luts, stream));
-    } else if (transpose)
-        SQY_TIMED("batch_bitswap1", sqy::launch_bitswap1_batch(d_jobs, d_tiles, (uint32_t)nv, ntiles, elem_size, stream));
+    } else if (transpose) {
+        if (njobs) SQY_TIMED("batch_bitswap1", sqy::launch_bitswap1_batch(d_jobs, d_tiles, (uint32_t)njobs, ntiles, elem_size, stream));
+        if (launch_views(cx, stream, gathers, ViewLaunch::bitswap1, 1, elem_size)) return 1;
+    }
     SQY_TIMED("batch_lz4_chunks", sqy::launch_lz4_chunks_table(d_stream, d_table, (uint32_t)nc, d_scratch, g.scratch_stride, d_csize, d_redo, stream));
     // round trip 1: how many entries the first pass left to the dense batches -- and, quantised, the decode LUTs the headers carry
     if (quantised) SQY_HIP(hipMemcpyAsync(h_decode, d_decode, nv * sqy::kQuantiserBatchDecodeBytes, hipMemcpyDeviceToHost, stream));
@@ -3079,18 +3293,34 @@ int encode_batch_group(Context& cx, const BatchAdmit& a, const sqy::Lz4BatchGrou
 }
 
 int encode_batch_on_device(Context& cx, const char* pipeline, const BatchAdmit& a, const void* const* d_srcs, const long* shapes, unsigned rank, int elem_size,
-                           int nvolumes, void* d_dst, uint64_t slot_capacity, long* offsets, long* lengths, int nthreads, hipStream_t stream)
+                           int nvolumes, void* d_dst, uint64_t slot_capacity, long* offsets, long* lengths, int nthreads, hipStream_t stream,
+                           const std::vector<sqy::BatchView>* views = nullptr)
 {
     for (int i = 0; i < nvolumes; ++i)
         if (reinterpret_cast<uintptr_t>(d_srcs[i]) % (uintptr_t)elem_size) { std::fprintf(stderr, "[sqeazy]\t volume %d: source not aligned to the voxel size\n", i); return 1; }
     const sqy::EncodeBatchForm form = g_opt.encode_batch_joint.load() ? sqy::encode_batch_form(a.pipe, elem_size) : sqy::EncodeBatchForm::none;
     sqy::Lz4BatchPlan plan;
     plan.group_of.assign((size_t)nvolumes, -1);
+    // the views that are no dense allocations: gathered by the transposer, packed into the stream (plain lz4), or packed into the
+    // group's workspace -- whose bytes count against the group bound
+    std::vector<uint8_t> how((size_t)nvolumes, in_place);
+    std::vector<uint64_t> pack_bytes((size_t)nvolumes, 0);
+    bool strided = false;
+    if (views) {
+        const bool fused = g_opt.batch_strided_fused.load() != 0;
+        for (size_t i = 0; i < (size_t)nvolumes; ++i) {
+            if ((*views)[i].dense) continue;
+            strided = true;
+            how[i] = fused && form == sqy::EncodeBatchForm::bitswap1_lz4 ? gathered : fused && form == sqy::EncodeBatchForm::lz4 ? packed_to_stream : packed;
+            if (how[i] == packed) pack_bytes[i] = (a.len[i] * (uint64_t)elem_size + 15) & ~(uint64_t)15;
+        }
+    }
     if (form != sqy::EncodeBatchForm::none) {
         std::vector<uint64_t> totals((size_t)nvolumes);
         for (int i = 0; i < nvolumes; ++i) totals[(size_t)i] = sqy::encode_batch_stream_bytes(form, a.len[(size_t)i], elem_size);
-        plan = sqy::lz4_batch_plan(a.pipe.stages.back().lz4, totals, a.pipe.nthreads, (uint64_t)g_opt.encode_batch_group_bytes.load(),
-                                   (uint64_t)g_opt.encode_batch_joint_max_bytes.load(), sqy::encode_batch_extra_bytes(form));
+        plan = sqy::lz4_batch_plan_views(a.pipe.stages.back().lz4, totals, strided ? pack_bytes : std::vector<uint64_t>(), a.pipe.nthreads,
+                                         (uint64_t)g_opt.encode_batch_group_bytes.load(), (uint64_t)g_opt.encode_batch_joint_max_bytes.load(),
+                                         sqy::encode_batch_extra_bytes(form));
     }
     int rc = 0;
     if (!plan.groups.empty()) {
@@ -3106,7 +3336,7 @@ int encode_batch_on_device(Context& cx, const char* pipeline, const BatchAdmit& 
         std::memset(records, 0, records_bytes);
         for (const sqy::Lz4BatchGroup& g : plan.groups)
             if (encode_batch_group(cx, a, g, form, elem_size, d_srcs, static_cast<uint8_t*>(d_dst), slot_capacity, offsets, lengths, records,
-                                   static_cast<uint8_t*>(cx.ws.batch_host.p) + records_bytes, stream))
+                                   static_cast<uint8_t*>(cx.ws.batch_host.p) + records_bytes, stream, strided ? views : nullptr, strided ? &how : nullptr))
                 rc = 1;
         if (g_prof_on.load()) prof_collect(cx.pending);
     }
@@ -3114,7 +3344,16 @@ int encode_batch_on_device(Context& cx, const char* pipeline, const BatchAdmit& 
     for (int i = 0; i < nvolumes && rc == 0; ++i) {
         if (plan.group_of[(size_t)i] >= 0) continue;
         long at = 0, len = 0;
-        rc = encode_on_device(cx, pipeline, d_srcs[i], shapes + (size_t)i * rank, rank, elem_size, static_cast<uint8_t*>(d_dst) + (uint64_t)i * slot_capacity,
+        const void* src = d_srcs[i];
+        if (how[(size_t)i] != in_place) {                               // a view outside the joint forms: from its packed copy
+            if (cx.ws.batch_pack.ensure(a.len[(size_t)i] * (uint64_t)elem_size)) { rc = 1; break; }
+            src = cx.ws.batch_pack.p;
+            ViewLaunch one;
+            one.add(d_srcs[i], src, (*views)[(size_t)i]);
+            DrainOnExit drain{stream, &cx.pending};                     // (the launch's tables are this scope's)
+            if (launch_views(cx, stream, one, ViewLaunch::pack, 0, elem_size)) { rc = 1; break; }
+        }
+        rc = encode_on_device(cx, pipeline, src, shapes + (size_t)i * rank, rank, elem_size, static_cast<uint8_t*>(d_dst) + (uint64_t)i * slot_capacity,
                               slot_capacity, &len, nthreads, stream, &at);
         if (rc == 0) { offsets[i] = (long)((uint64_t)i * slot_capacity) + at; lengths[i] = len; }
     }
@@ -3131,6 +3370,20 @@ int encode_batch_device(const char* pipeline, const void* const* d_srcs, const l
     if (!lease.ctx) { std::fprintf(stderr, "[sqeazy]\t no usable HIP device\n"); return 1; }
     return encode_batch_on_device(*lease.ctx, pipeline, a, d_srcs, shapes, rank, elem_size, nvolumes, d_dst, (uint64_t)slot_capacity, offsets, lengths, nthreads,
                                   static_cast<hipStream_t>(hip_stream));
+}
+
+// SQYAMD_PipelineEncode_BatchStrided_*: the Batch call's checks, then every view on the host; strides == nullptr: the Batch call
+int encode_batch_strided_device(const char* pipeline, const void* const* d_srcs, const long* shapes, const long* strides, unsigned rank, int elem_size, int nvolumes,
+                                void* d_dst, long slot_capacity, long* offsets, long* lengths, int nthreads, void* hip_stream)
+{
+    BatchAdmit a;
+    if (admit_batch(pipeline, d_srcs, shapes, rank, elem_size, nvolumes, d_dst, slot_capacity, offsets, lengths, nthreads, &a)) return 1;
+    std::vector<sqy::BatchView> views;
+    if (admit_views("encode batch", d_srcs, shapes, strides, rank, nvolumes, elem_size, &views)) return 1;
+    ContextLease lease;
+    if (!lease.ctx) { std::fprintf(stderr, "[sqeazy]\t no usable HIP device\n"); return 1; }
+    return encode_batch_on_device(*lease.ctx, pipeline, a, d_srcs, shapes, rank, elem_size, nvolumes, d_dst, (uint64_t)slot_capacity, offsets, lengths, nthreads,
+                                  static_cast<hipStream_t>(hip_stream), strides ? &views : nullptr);
 }
 
 // the host-pointer variant (not tuned): every volume staged up, one call of the device driver, the blobs brought back
@@ -3507,6 +3760,22 @@ int SQYAMD_PipelineEncode_Batch_UI8_Device(const char* pipeline, const void* con
     });
 }
 
+int SQYAMD_PipelineEncode_BatchStrided_UI16_Device(const char* pipeline, const void* const* d_srcs, const long* shapes, const long* strides, unsigned shape_size,
+                                                   int nvolumes, void* d_dst, long slot_capacity, long* offsets, long* lengths, int nthreads, void* hip_stream)
+{
+    return guarded([&]() -> int {
+        return encode_batch_strided_device(pipeline, d_srcs, shapes, strides, shape_size, 2, nvolumes, d_dst, slot_capacity, offsets, lengths, nthreads, hip_stream);
+    });
+}
+
+int SQYAMD_PipelineEncode_BatchStrided_UI8_Device(const char* pipeline, const void* const* d_srcs, const long* shapes, const long* strides, unsigned shape_size,
+                                                  int nvolumes, void* d_dst, long slot_capacity, long* offsets, long* lengths, int nthreads, void* hip_stream)
+{
+    return guarded([&]() -> int {
+        return encode_batch_strided_device(pipeline, d_srcs, shapes, strides, shape_size, 1, nvolumes, d_dst, slot_capacity, offsets, lengths, nthreads, hip_stream);
+    });
+}
+
 int SQYAMD_PipelineEncode_Batch_UI16(const char* pipeline, const char* const* srcs, const long* shapes, unsigned shape_size, int nvolumes, char* dst,
                                      long slot_capacity, long* offsets, long* lengths, int nthreads)
 {
@@ -3620,6 +3889,18 @@ int SQYAMD_Decode_Batch_UI8_Device(const void* d_src, const long* offsets, const
                                    long* decoded_bytes, void* hip_stream)
 {
     return guarded([&]() -> int { return decode_batch_device(d_src, BatchDecodeArgs{offsets, lengths, nblobs, d_dsts, dst_capacities, decoded_bytes}, 1, hip_stream); });
+}
+
+int SQYAMD_Decode_BatchStrided_UI16_Device(const void* d_src, const long* offsets, const long* lengths, int nblobs, void* const* d_dsts, const long* dst_shapes,
+                                           const long* dst_strides, unsigned shape_size, long* decoded_bytes, void* hip_stream)
+{
+    return guarded([&]() -> int { return decode_batch_strided_device(d_src, offsets, lengths, nblobs, d_dsts, dst_shapes, dst_strides, shape_size, decoded_bytes, 2, hip_stream); });
+}
+
+int SQYAMD_Decode_BatchStrided_UI8_Device(const void* d_src, const long* offsets, const long* lengths, int nblobs, void* const* d_dsts, const long* dst_shapes,
+                                          const long* dst_strides, unsigned shape_size, long* decoded_bytes, void* hip_stream)
+{
+    return guarded([&]() -> int { return decode_batch_strided_device(d_src, offsets, lengths, nblobs, d_dsts, dst_shapes, dst_strides, shape_size, decoded_bytes, 1, hip_stream); });
 }
 
 int SQYAMD_Decode_Batch_UI16(const char* src, const long* offsets, const long* lengths, int nblobs, char* const* dsts, const long* dst_capacities, long* decoded_bytes)

@@ -173,6 +173,19 @@ hipError_t launch_batch_quantiser_histogram(const Bitswap1Job* d_jobs, const uin
 hipError_t launch_batch_quantiser_lut(const uint32_t* d_histos, uint32_t njobs, uint8_t* d_luts_encode, uint16_t* d_luts_decode, hipStream_t stream);
 hipError_t launch_batch_quantiser_bitswap1(const Bitswap1Job* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ntiles, const uint8_t* d_luts_encode,
                                            hipStream_t stream);
+// ---- strided views (SQYAMD_*_BatchStrided_*): job j is a view of Z x Y x X voxels at `view` (voxel-aligned; rows sy, frames sz voxels
+// apart, sqy::BatchView) and its dense form at `dense`.  first_tile as above, over batch_bitswap1_tiles(Z Y X).  Nothing outside the
+// view's voxels is read or written on the view's side.
+struct BatchViewJob { void* view; void* dense; uint64_t Z, Y, X, sz, sy; };
+// the copy between the two: to_view = false packs the view into `dense` (any voxel-aligned address), true unpacks `dense` into the view
+hipError_t launch_batch_view_copy(const BatchViewJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ntiles, int elem_size, bool to_view,
+                                  hipStream_t stream);
+// launch_bitswap1_batch with the voxels gathered from the view: planes + tail to `dense` (16-byte aligned), no packed copy in between
+hipError_t launch_bitswap1_batch_strided(const BatchViewJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ntiles, int elem_size, hipStream_t stream);
+// launch_bitswap1_decode_batch with the voxels scattered into the view: planes + tail at `dense` (16-byte aligned)
+hipError_t launch_bitswap1_decode_batch_strided(const BatchViewJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ntiles, int elem_size,
+                                                hipStream_t stream);
+
 // One entry of the joint chunk table (sqy::Lz4BatchChunkPlan, sqy_pipeline.hpp): chunk e is the n bytes at in + off, compressed on its
 // own into scratch + slot * stride, csize[e] (0: stored); redo as for launch_lz4_chunks (nentries + 1 words, the launcher zeroes redo[0])
 struct Lz4BatchChunk { uint64_t off; uint32_t n, vol, slot, pad; };

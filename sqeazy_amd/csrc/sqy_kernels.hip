@@ -21,6 +21,7 @@
 #include "sqy_kernels.h"
 #include "sqy_pipeline.hpp"
 #include "sqy_quantiser_lut.hpp"
+#include "sqy_batch_view.hpp"
 
 namespace sqy {
 
@@ -7625,6 +7626,336 @@ hipError_t launch_bitswap1_decode_range(const uint8_t* in, void* out, const Bits
         hipLaunchKernelGGL((bitswap1_decode_range_kernel<uint8_t, true>), dim3((unsigned)g), dim3(256), 0, stream, in, out, r, lut);
     else
         hipLaunchKernelGGL((bitswap1_decode_range_kernel<uint8_t, false>), dim3((unsigned)g), dim3(256), 0, stream, in, out, r, lut);
+    return hipGetLastError();
+}
+
+// ---- strided views (SQYAMD_PipelineEncode_BatchStrided_*, SQYAMD_Decode_BatchStrided_*) --------------------------------------------------
+// Job j is a view of Z x Y x X voxels cut out of a larger allocation (rows sy, frames sz voxels apart) and its dense form.  All three
+// kernels have bitswap1_batch_kernel's geometry: a workgroup is one tile of BSWB_TILE_VOX voxels of one job, a thread owns 128 voxels
+// in a row of the dense order.  It finds its first voxel in the view with sqy::view_walk_start (two divisions) and goes on from row to
+// row with view_walk_advance.  The view is touched sixteen bytes at a time where a piece of sixteen bytes lies in one row and on the
+// 16-byte grid, voxel by voxel where not -- and never outside the view's voxels: the gaps between rows and frames belong to the caller.
+template <int ELEM>
+__device__ __forceinline__ uint32_t view_voxel_load(const uint8_t* view, uint64_t off)
+{
+    if constexpr (ELEM == 2) return reinterpret_cast<const uint16_t*>(view)[off];
+    else return view[off];
+}
+template <int ELEM>
+__device__ __forceinline__ void view_voxel_store(uint8_t* view, uint64_t off, uint32_t v)
+{
+    if constexpr (ELEM == 2) reinterpret_cast<uint16_t*>(view)[off] = (uint16_t)v;
+    else view[off] = (uint8_t)v;
+}
+
+// the next n voxels of the dense order (n <= 16 / ELEM), packed as they lie in a dense copy; the bytes behind them are zero
+template <int ELEM>
+__device__ __forceinline__ uint4 view_gather16(const uint8_t* __restrict__ view, const ViewGeometry& g, ViewWalk& w, uint32_t n)
+{
+    constexpr uint32_t G = 16 / ELEM;
+    const uint8_t* p = view + w.off * ELEM;
+    if (n == G && w.left >= G && (reinterpret_cast<uintptr_t>(p) & 15u) == 0) {
+        const uint4 r = *reinterpret_cast<const uint4*>(p);
+        view_walk_advance(g, &w, G);
+        return r;
+    }
+    uint32_t d[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (uint32_t k = 0; k < G; ++k)
+        if (k < n) {
+            d[k * ELEM / 4] |= view_voxel_load<ELEM>(view, w.off) << (8u * ((k * ELEM) & 3u));
+            view_walk_advance(g, &w, 1);
+        }
+    return make_uint4(d[0], d[1], d[2], d[3]);
+}
+// its inverse: the first n voxels packed in v go to the next n places of the dense order
+template <int ELEM>
+__device__ __forceinline__ void view_scatter16(uint8_t* __restrict__ view, const ViewGeometry& g, ViewWalk& w, uint4 v, uint32_t n)
+{
+    constexpr uint32_t G = 16 / ELEM;
+    uint8_t* p = view + w.off * ELEM;
+    if (n == G && w.left >= G && (reinterpret_cast<uintptr_t>(p) & 15u) == 0) {
+        *reinterpret_cast<uint4*>(p) = v;
+        view_walk_advance(g, &w, G);
+        return;
+    }
+    const uint32_t d[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (uint32_t k = 0; k < G; ++k)
+        if (k < n) {
+            view_voxel_store<ELEM>(view, w.off, d[k * ELEM / 4] >> (8u * ((k * ELEM) & 3u)));
+            view_walk_advance(g, &w, 1);
+        }
+}
+
+__device__ __forceinline__ uint32_t batch_job_of_tile(const uint32_t* __restrict__ first_tile, uint32_t njobs)
+{
+    uint32_t lo = 0, hi = njobs;                                      // first_tile[lo] <= blockIdx.x < first_tile[hi]
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (first_tile[mid] <= blockIdx.x) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// pack (TO_VIEW = false: view -> dense) and unpack (TO_VIEW = true: dense -> view).  A pure copy, so the lanes interleave: a tile is cut
+// into pieces of sixteen bytes of the dense order, piece p of the tile goes to thread p % 256 -- the 64 lanes of one load or store touch
+// 1 KiB in a row on the dense side, and on the view's side wherever rows are longer than a piece.  Every piece finds its place with a
+// walk of its own (two 32-bit divisions); it moves as sixteen bytes where it lies in one row and on the 16-byte grid on both sides,
+// voxel by voxel where not.
+template <int ELEM, bool TO_VIEW>
+__global__ __launch_bounds__(256)
+void batch_view_copy_kernel(const BatchViewJob* __restrict__ jobs, const uint32_t* __restrict__ first_tile, uint32_t njobs)
+{
+    constexpr uint32_t G = 16 / ELEM, PIECES = BSWB_TILE_VOX / G / 256u;      // voxels per piece, pieces per thread
+    const uint32_t j = batch_job_of_tile(first_tile, njobs);
+    const BatchViewJob job = jobs[j];
+    const uint64_t len = job.Z * job.Y * job.X;
+    const uint64_t base = (uint64_t)(blockIdx.x - first_tile[j]) * BSWB_TILE_VOX;
+    const ViewGeometry g{job.Y, job.X, job.sz, job.sy};
+    uint8_t* view = static_cast<uint8_t*>(job.view);
+    uint8_t* dense = static_cast<uint8_t*>(job.dense);
+    for (uint32_t k = 0; k < PIECES; ++k) {
+        const uint64_t i0 = base + ((uint64_t)k * 256u + threadIdx.x) * G;
+        if (i0 >= len) return;
+        const uint32_t n = (uint32_t)(len - i0 < G ? len - i0 : G);
+        ViewWalk w = view_walk_start(g, i0);
+        uint8_t* pv = view + w.off * ELEM;
+        uint8_t* pd = dense + i0 * ELEM;
+        if (n == G && w.left >= G && ((reinterpret_cast<uintptr_t>(pv) | reinterpret_cast<uintptr_t>(pd)) & 15u) == 0) {
+            if (TO_VIEW) *reinterpret_cast<uint4*>(pv) = *reinterpret_cast<const uint4*>(pd);
+            else *reinterpret_cast<uint4*>(pd) = *reinterpret_cast<const uint4*>(pv);
+            continue;
+        }
+        for (uint32_t v = 0; v < n; ++v) {
+            if (TO_VIEW) view_voxel_store<ELEM>(view, w.off, view_voxel_load<ELEM>(pd, v));
+            else view_voxel_store<ELEM>(pd, v, view_voxel_load<ELEM>(view, w.off));
+            view_walk_advance(g, &w, 1);
+        }
+    }
+}
+
+// bitswap1_batch_kernel with the 128 voxels of a thread gathered from the view: the arithmetic, the planes and the tail are its own
+template <int ELEM>
+__global__ __launch_bounds__(256)
+void bitswap1_batch_strided_kernel(const BatchViewJob* __restrict__ jobs, const uint32_t* __restrict__ first_tile, uint32_t njobs)
+{
+    constexpr uint32_t W = 8 * ELEM, WPT = BSWB_THREAD_VOX / W;        // voxels per word, words per thread
+    const uint32_t j = batch_job_of_tile(first_tile, njobs);
+    const BatchViewJob job = jobs[j];
+    const uint32_t tile = blockIdx.x - first_tile[j], tid = threadIdx.x;
+    const uint64_t len = job.Z * job.Y * job.X, seg = len / W, L = seg * W;
+    const ViewGeometry g{job.Y, job.X, job.sz, job.sy};
+    const uint8_t* __restrict__ in = static_cast<const uint8_t*>(job.view);
+    uint8_t* __restrict__ out = static_cast<uint8_t*>(job.dense);
+    if (tile == 0 && tid < len - L)                                   // tail voxels [L, len): copied verbatim
+        view_voxel_store<ELEM>(out, L + tid, view_voxel_load<ELEM>(in, view_walk_start(g, L + tid).off));
+    const uint64_t w0 = ((uint64_t)tile * 256u + tid) * WPT;
+    if (w0 >= seg) return;
+    const uint32_t nw = (uint32_t)(seg - w0 < WPT ? seg - w0 : WPT);  // this thread's words
+    const uint64_t plane_bytes = seg * ELEM;
+    const bool wide = nw == WPT && ((reinterpret_cast<uintptr_t>(out) | plane_bytes) & 15u) == 0;
+    ViewWalk w = view_walk_start(g, w0 * W);
+    if constexpr (ELEM == 2) {
+        uint32_t res[16][4];                                          // res[b]: the thread's eight words of the plane that carries bit b
+#pragma unroll
+        for (int b = 0; b < 16; ++b) { res[b][0] = 0; res[b][1] = 0; res[b][2] = 0; res[b][3] = 0; }
+#pragma unroll
+        for (uint32_t i = 0; i < WPT; ++i) {
+            if (i >= nw) break;
+            const uint4 x = view_gather16<2>(in, g, w, 8), y = view_gather16<2>(in, g, w, 8);
+            const uint32_t d[8] = {x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w};
+            uint32_t v[16];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) { v[2 * k] = d[k] & 0xffffu; v[2 * k + 1] = d[k] >> 16; }
+            // plane 15 - b, word w: bit 15 - k = bit b of voxel 16 w + k
+#pragma unroll
+            for (int b = 0; b < 16; ++b) {
+                uint32_t a = 0;
+#pragma unroll
+                for (int k = 0; k < 16; ++k) a |= ((v[k] >> b) & 1u) << (15 - k);
+                res[b][i >> 1] |= a << (16u * (i & 1u));
+            }
+        }
+        if (wide) {
+#pragma unroll
+            for (int b = 0; b < 16; ++b)
+                *reinterpret_cast<uint4*>(out + (uint64_t)(15 - b) * plane_bytes + w0 * 2u) = make_uint4(res[b][0], res[b][1], res[b][2], res[b][3]);
+        } else {
+            uint16_t* out16 = reinterpret_cast<uint16_t*>(out);
+#pragma unroll
+            for (uint32_t i = 0; i < WPT; ++i)
+                if (i < nw)
+#pragma unroll
+                    for (int b = 0; b < 16; ++b) out16[(uint64_t)(15 - b) * seg + w0 + i] = (uint16_t)(res[b][i >> 1] >> (16u * (i & 1u)));
+        }
+    } else {
+        // byte b of the result: bit b of the word's eight voxels, voxel k at bit 7 - k (bitswap1_u8_generic)
+        auto word_planes = [](uint64_t x) -> uint64_t {
+            uint64_t t = x, y;
+            y = (t ^ (t >> 7)) & 0x00AA00AA00AA00AAull; t = t ^ y ^ (y << 7);
+            y = (t ^ (t >> 14)) & 0x0000CCCC0000CCCCull; t = t ^ y ^ (y << 14);
+            y = (t ^ (t >> 28)) & 0x00000000F0F0F0F0ull; t = t ^ y ^ (y << 28);
+            const uint32_t r0 = __brev((uint32_t)t), r1 = __brev((uint32_t)(t >> 32));      // (bits reversed in every byte, bytes swapped)
+            return (uint64_t)__builtin_bswap32(r0) | ((uint64_t)__builtin_bswap32(r1) << 32);
+        };
+        uint32_t res[8][4];
+#pragma unroll
+        for (int b = 0; b < 8; ++b) { res[b][0] = 0; res[b][1] = 0; res[b][2] = 0; res[b][3] = 0; }
+#pragma unroll
+        for (uint32_t i = 0; i < WPT; i += 2) {
+            if (i >= nw) break;
+            const uint4 x = view_gather16<1>(in, g, w, nw - i >= 2u ? 16u : 8u);      // (a last odd word: its eight voxels, zeros behind them)
+            const uint64_t t[2] = {word_planes((uint64_t)x.x | ((uint64_t)x.y << 32)), word_planes((uint64_t)x.z | ((uint64_t)x.w << 32))};
+#pragma unroll
+            for (uint32_t u = 0; u < 2; ++u)
+#pragma unroll
+                for (int b = 0; b < 8; ++b) res[b][(i + u) >> 2] |= ((uint32_t)(t[u] >> (8 * b)) & 0xffu) << (8u * ((i + u) & 3u));
+        }
+        if (wide) {
+#pragma unroll
+            for (int b = 0; b < 8; ++b)
+                *reinterpret_cast<uint4*>(out + (uint64_t)(7 - b) * plane_bytes + w0) = make_uint4(res[b][0], res[b][1], res[b][2], res[b][3]);
+        } else {
+#pragma unroll
+            for (uint32_t i = 0; i < WPT; ++i)
+                if (i < nw)
+#pragma unroll
+                    for (int b = 0; b < 8; ++b) out[(uint64_t)(7 - b) * seg + w0 + i] = (uint8_t)(res[b][i >> 2] >> (8u * (i & 3u)));
+        }
+    }
+}
+
+// bitswap1_decode_batch_kernel with the 128 voxels of a thread scattered into the view: the arithmetic is its own
+template <int ELEM>
+__global__ __launch_bounds__(256)
+void bitswap1_decode_batch_strided_kernel(const BatchViewJob* __restrict__ jobs, const uint32_t* __restrict__ first_tile, uint32_t njobs)
+{
+    constexpr uint32_t W = 8 * ELEM, WPT = BSWB_THREAD_VOX / W;        // voxels per word, words per thread
+    const uint32_t j = batch_job_of_tile(first_tile, njobs);
+    const BatchViewJob job = jobs[j];
+    const uint32_t tile = blockIdx.x - first_tile[j], tid = threadIdx.x;
+    const uint64_t len = job.Z * job.Y * job.X, seg = len / W, L = seg * W;
+    const ViewGeometry g{job.Y, job.X, job.sz, job.sy};
+    const uint8_t* __restrict__ in = static_cast<const uint8_t*>(job.dense);
+    uint8_t* __restrict__ out = static_cast<uint8_t*>(job.view);
+    if (tile == 0 && tid < len - L)                                   // tail voxels [L, len): copied verbatim
+        view_voxel_store<ELEM>(out, view_walk_start(g, L + tid).off, view_voxel_load<ELEM>(in, L + tid));
+    const uint64_t w0 = ((uint64_t)tile * 256u + tid) * WPT;
+    if (w0 >= seg) return;
+    const uint32_t nw = (uint32_t)(seg - w0 < WPT ? seg - w0 : WPT);  // this thread's words
+    const uint64_t plane_bytes = seg * ELEM;
+    const bool wide = nw == WPT && ((reinterpret_cast<uintptr_t>(in) | plane_bytes) & 15u) == 0;
+    ViewWalk w = view_walk_start(g, w0 * W);
+    if constexpr (ELEM == 2) {
+        uint32_t pl[16][4];                                           // pl[b] = eight words of the plane that carries bit b
+        if (wide) {
+#pragma unroll
+            for (int b = 0; b < 16; ++b) {
+                const uint4 t = *reinterpret_cast<const uint4*>(in + (uint64_t)(15 - b) * plane_bytes + w0 * 2u);
+                pl[b][0] = t.x; pl[b][1] = t.y; pl[b][2] = t.z; pl[b][3] = t.w;
+            }
+        } else {
+            const uint16_t* in16 = reinterpret_cast<const uint16_t*>(in);
+#pragma unroll
+            for (int b = 0; b < 16; ++b) { pl[b][0] = 0; pl[b][1] = 0; pl[b][2] = 0; pl[b][3] = 0; }
+#pragma unroll
+            for (uint32_t i = 0; i < WPT; ++i)
+                if (i < nw)
+#pragma unroll
+                    for (int b = 0; b < 16; ++b) pl[b][i >> 1] |= (uint32_t)in16[(uint64_t)(15 - b) * seg + w0 + i] << (16u * (i & 1u));
+        }
+#pragma unroll
+        for (uint32_t q = 0; q < 4; ++q) {                            // words w0 + 2 q (group A, low halves) and w0 + 2 q + 1 (group B)
+            if (2 * q >= nw) break;
+            uint32_t r[16];
+#pragma unroll
+            for (int b = 0; b < 16; ++b) r[b] = pl[b][q];
+            transpose16x16_pairs(r);                                  // r[i] = voxel 15 - i of group A | of group B << 16
+            uint32_t ga[8], gb[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                ga[k] = __builtin_amdgcn_perm(r[14 - 2 * k], r[15 - 2 * k], 0x05040100u);
+                gb[k] = __builtin_amdgcn_perm(r[14 - 2 * k], r[15 - 2 * k], 0x07060302u);
+            }
+            view_scatter16<2>(out, g, w, make_uint4(ga[0], ga[1], ga[2], ga[3]), 8);
+            view_scatter16<2>(out, g, w, make_uint4(ga[4], ga[5], ga[6], ga[7]), 8);
+            if (2 * q + 1 >= nw) break;
+            view_scatter16<2>(out, g, w, make_uint4(gb[0], gb[1], gb[2], gb[3]), 8);
+            view_scatter16<2>(out, g, w, make_uint4(gb[4], gb[5], gb[6], gb[7]), 8);
+        }
+    } else {
+        uint32_t pw[8][4];                                            // pw[b] = 16 bytes of the plane that carries bit b
+        if (wide) {
+#pragma unroll
+            for (int b = 0; b < 8; ++b) {
+                const uint4 t = *reinterpret_cast<const uint4*>(in + (uint64_t)(7 - b) * plane_bytes + w0);
+                pw[b][0] = t.x; pw[b][1] = t.y; pw[b][2] = t.z; pw[b][3] = t.w;
+            }
+        } else {
+#pragma unroll
+            for (int b = 0; b < 8; ++b) { pw[b][0] = 0; pw[b][1] = 0; pw[b][2] = 0; pw[b][3] = 0; }
+#pragma unroll
+            for (uint32_t i = 0; i < WPT; ++i)
+                if (i < nw)
+#pragma unroll
+                    for (int b = 0; b < 8; ++b) pw[b][i >> 2] |= (uint32_t)in[(uint64_t)(7 - b) * seg + w0 + i] << (8u * (i & 3u));
+        }
+#pragma unroll
+        for (uint32_t gq = 0; gq < 16; gq += 2) {
+            if (gq >= nw) break;
+            uint32_t d[4];
+#pragma unroll
+            for (uint32_t u = 0; u < 2; ++u) {
+                // byte b of (hi:lo) = plane byte of bit b (voxel k at bit 7 - k), gathered and transposed as
+                // bitswap1_decode_batch_kernel does it: afterwards byte i of hi:lo = voxel 7 - i
+                constexpr uint32_t Zs = 0x0c;                         // v_perm selector: a zero byte
+                const uint32_t c = (gq + u) & 3u, wdx = (gq + u) >> 2;
+                const uint32_t s01 = c | ((4u + c) << 8) | (Zs << 16) | (Zs << 24), s23 = Zs | (Zs << 8) | (c << 16) | ((4u + c) << 24);
+                uint32_t lo_ = __builtin_amdgcn_perm(pw[1][wdx], pw[0][wdx], s01) | __builtin_amdgcn_perm(pw[3][wdx], pw[2][wdx], s23);
+                uint32_t hi_ = __builtin_amdgcn_perm(pw[5][wdx], pw[4][wdx], s01) | __builtin_amdgcn_perm(pw[7][wdx], pw[6][wdx], s23);
+                uint32_t y;
+                y = (lo_ ^ (lo_ >> 7)) & 0x00AA00AAu; lo_ ^= y ^ (y << 7);
+                y = (hi_ ^ (hi_ >> 7)) & 0x00AA00AAu; hi_ ^= y ^ (y << 7);
+                y = (lo_ ^ (lo_ >> 14)) & 0x0000CCCCu; lo_ ^= y ^ (y << 14);
+                y = (hi_ ^ (hi_ >> 14)) & 0x0000CCCCu; hi_ ^= y ^ (y << 14);
+                y = (lo_ ^ (hi_ << 4)) & 0xF0F0F0F0u; lo_ ^= y; hi_ ^= y >> 4;
+                d[2 * u] = __builtin_bswap32(hi_);                    // voxels 0..3 of the word
+                d[2 * u + 1] = __builtin_bswap32(lo_);                // voxels 4..7
+            }
+            view_scatter16<1>(out, g, w, make_uint4(d[0], d[1], d[2], d[3]), nw - gq >= 2u ? 16u : 8u);
+        }
+    }
+}
+
+hipError_t launch_batch_view_copy(const BatchViewJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ntiles, int elem_size, bool to_view,
+                                  hipStream_t stream)
+{
+    if (njobs == 0 || ntiles == 0) return hipSuccess;
+    if (elem_size == 2 && to_view) hipLaunchKernelGGL((batch_view_copy_kernel<2, true>), dim3(ntiles), dim3(256), 0, stream, d_jobs, d_first_tile, njobs);
+    else if (elem_size == 2) hipLaunchKernelGGL((batch_view_copy_kernel<2, false>), dim3(ntiles), dim3(256), 0, stream, d_jobs, d_first_tile, njobs);
+    else if (elem_size == 1 && to_view) hipLaunchKernelGGL((batch_view_copy_kernel<1, true>), dim3(ntiles), dim3(256), 0, stream, d_jobs, d_first_tile, njobs);
+    else if (elem_size == 1) hipLaunchKernelGGL((batch_view_copy_kernel<1, false>), dim3(ntiles), dim3(256), 0, stream, d_jobs, d_first_tile, njobs);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+hipError_t launch_bitswap1_batch_strided(const BatchViewJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ntiles, int elem_size, hipStream_t stream)
+{
+    if (njobs == 0 || ntiles == 0) return hipSuccess;
+    if (elem_size == 2) hipLaunchKernelGGL(bitswap1_batch_strided_kernel<2>, dim3(ntiles), dim3(256), 0, stream, d_jobs, d_first_tile, njobs);
+    else if (elem_size == 1) hipLaunchKernelGGL(bitswap1_batch_strided_kernel<1>, dim3(ntiles), dim3(256), 0, stream, d_jobs, d_first_tile, njobs);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+hipError_t launch_bitswap1_decode_batch_strided(const BatchViewJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ntiles, int elem_size,
+                                                hipStream_t stream)
+{
+    if (njobs == 0 || ntiles == 0) return hipSuccess;
+    if (elem_size == 2) hipLaunchKernelGGL(bitswap1_decode_batch_strided_kernel<2>, dim3(ntiles), dim3(256), 0, stream, d_jobs, d_first_tile, njobs);
+    else if (elem_size == 1) hipLaunchKernelGGL(bitswap1_decode_batch_strided_kernel<1>, dim3(ntiles), dim3(256), 0, stream, d_jobs, d_first_tile, njobs);
+    else return hipErrorInvalidValue;
     return hipGetLastError();
 }
 

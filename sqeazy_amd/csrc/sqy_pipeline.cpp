@@ -307,11 +307,54 @@ uint64_t encode_batch_extra_bytes(EncodeBatchForm form) { return form == EncodeB
 Lz4BatchPlan lz4_batch_plan(const Lz4Params& p, const std::vector<uint64_t>& totals, unsigned nthreads, uint64_t group_bytes, uint64_t joint_max,
                             uint64_t extra_bytes)
 {
+    return lz4_batch_plan_views(p, totals, std::vector<uint64_t>(), nthreads, group_bytes, joint_max, extra_bytes);
+}
+
+bool admit_view(const long* shape, const long* strides, unsigned rank, BatchView* view)
+{
+    if (!shape || !view || rank == 0 || rank > 3) return false;
+    constexpr uint64_t kReachMax = (uint64_t)1 << 62;
+    uint64_t d[3] = {1, 1, 1}, s[3] = {0, 0, 1};
+    for (unsigned k = 0; k < rank; ++k) {
+        if (shape[k] < 1 || (strides && strides[k] < 1)) return false;
+        d[3 - rank + k] = (uint64_t)shape[k];
+    }
+    if (d[2] >= kReachMax || d[1] >= kReachMax / d[2] || d[0] >= kReachMax / (d[1] * d[2])) return false;
+    s[1] = d[2];
+    s[0] = d[1] * d[2];
+    if (strides) {
+        if (strides[rank - 1] != 1) return false;
+        for (unsigned k = 0; k < rank; ++k) s[3 - rank + k] = (uint64_t)strides[k];
+        // the padded dimensions in front: the dense strides over what follows them
+        for (int k = 2 - (int)rank; k >= 0; --k) {
+            if (s[k + 1] >= kReachMax / d[k + 1]) return false;
+            s[k] = d[k + 1] * s[k + 1];
+        }
+        for (int k = 1; k >= 0; --k) {
+            if (s[k + 1] >= kReachMax / d[k + 1]) return false;               // (the reach of dimension k + 1 in 64 bits)
+            if (s[k] < d[k + 1] * s[k + 1]) return false;
+        }
+        if (s[0] >= kReachMax / d[0]) return false;
+    }
+    BatchView v{d[0], d[1], d[2], s[0], s[1], false};
+    if (v.sy == v.X) { v.X *= v.Y; v.Y = 1; v.sy = v.X; }                   // rows without a gap: one row per frame
+    if (v.Y == 1) { v.Y = v.Z; v.Z = 1; v.sy = v.sz; v.sz = v.Y * v.sy; }   // .. the frames are the rows
+    else if (v.sz == v.Y * v.sy) { v.Y *= v.Z; v.Z = 1; v.sz = v.Y * v.sy; }
+    if (v.sy == v.X || v.Y == 1) { v.X *= v.Y; v.Y = 1; v.sy = v.X; v.sz = v.X; }
+    if (v.Z == 1) v.sz = v.Y * v.sy;                                        // (one frame: no frame pitch to speak of)
+    v.dense = v.Z == 1 && v.Y == 1;
+    *view = v;
+    return true;
+}
+
+Lz4BatchPlan lz4_batch_plan_views(const Lz4Params& p, const std::vector<uint64_t>& totals, const std::vector<uint64_t>& pack_bytes, unsigned nthreads,
+                                  uint64_t group_bytes, uint64_t joint_max, uint64_t extra_bytes_all)
+{
     Lz4BatchPlan plan;
     plan.group_of.assign(totals.size(), -1);
     uint64_t group_sum = 0;
     for (size_t i = 0; i < totals.size(); ++i) {
-        const uint64_t total = totals[i];
+        const uint64_t total = totals[i], extra_bytes = extra_bytes_all + (i < pack_bytes.size() ? pack_bytes[i] : 0);
         const Lz4EncodeLayout lay = lz4_encode_layout(p, total, nthreads);
         // (a table entry counts its bytes and its slot in 32 bits: chunks of the chunked layout are at most an LZ4 block of 4 MiB)
         if (total == 0 || !lay.chunked() || lay.accel != 1 || total > joint_max || lay.nchunks == 0 || lay.chunk > UINT32_MAX) continue;

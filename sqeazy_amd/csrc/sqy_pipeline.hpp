@@ -121,6 +121,23 @@ constexpr uint64_t kQuantiserBatchHistoBytes = 65536 * 4, kQuantiserBatchLutByte
 uint64_t encode_batch_stream_bytes(EncodeBatchForm form, uint64_t voxels, int elem_size);
 uint64_t encode_batch_extra_bytes(EncodeBatchForm form);
 
+// ---- strided views (SQYAMD_PipelineEncode_BatchStrided_*, SQYAMD_Decode_BatchStrided_*): a volume cut out of a larger allocation ----
+// Z x Y x X voxels, x innermost with stride 1, rows sy voxels apart, frames sz voxels apart.  dense: sy = X and sz = Y X, the view is one
+// run of Z Y X voxels (Z = Y = 1 then: a dense view is folded into one row)
+struct BatchView { uint64_t Z, Y, X, sz, sy; bool dense; };
+// A caller's view of `rank` dimensions (1 .. 3, outermost first; ranks 1 and 2 are padded with leading 1s), strides in voxels, nullptr: the
+// dense ones.  false: rank 0 or above 3, an extent below 1, an innermost stride other than 1, a stride below 1, a dimension that overlaps
+// the next one's reach (stride[k] < shape[k + 1] * stride[k + 1]), or a reach (shape x stride) past 2^62 voxels.  The view is folded where
+// the strides allow: rows that follow each other without a gap (sy = X) become one row, frames without a gap (sz = Y sy) one frame -- so
+// a tile that spans whole rows of its parent has fewer, longer rows.
+bool admit_view(const long* shape, const long* strides, unsigned rank, BatchView* view);
+// lz4_batch_plan for views: pack_bytes[i] is what volume i's packed copy takes in the group's workspace (0: read in place); it counts
+// against group_bytes with the stream and extra_bytes.  All zeros: lz4_batch_plan's result.
+Lz4BatchPlan lz4_batch_plan_views(const Lz4Params& p, const std::vector<uint64_t>& totals, const std::vector<uint64_t>& pack_bytes, unsigned nthreads,
+                                  uint64_t group_bytes, uint64_t joint_max, uint64_t extra_bytes = 0);
+// a view job of the pack, unpack and strided transposer launches (sqy::BatchViewJob, sqy_kernels.h)
+constexpr uint64_t kBatchViewJobBytes = 56;
+
 // ---- batch decode (SQYAMD_Decode_Batch_*): many blobs, one launch per kernel ----
 // What the planner knows of blob i: the bytes its LZ4 stage decodes to, the LZ4 block size, whether it may take the joint path at all
 // (the last stage lz4, chunk <= block_bytes), and what follows the LZ4 decode --
