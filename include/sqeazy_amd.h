@@ -360,6 +360,9 @@ SQY_FUNCTION_PREFIX void SQYAMD_Release_Workspace(void);
  *                                     lane did not answer
  *   "call_stamps"                     0  1: every device-memory encode call leaves host time stamps for SQYAMD_Call_Stamps (setting 1 drops
  *                                     the stamps kept so far); 0: a call pays one relaxed load
+ *   "dedupe_report"                   0  1: every chunked encode call that ran the duplicate-chunk search keeps the search's keys and decisions
+ *                                     for SQYAMD_Dedupe_Report (one small copy and one more synchronisation at the call's end; setting 1 drops
+ *                                     the record kept so far); 0: a call pays one relaxed load
  *   "block_parallel"                  1 [SQY_NO_BLOCK_PARALLEL=1 -> 0]  block-linked frames (nthreads = 1) encoded / decoded block-parallel
  *   "block_parallel_warmup"           65536 [SQY_BLOCK_PARALLEL_WARMUP=<bytes>, 0 .. 2^30]  stream parsed in front of a block to guess its table
  *   "block_parallel_stats"            0 [SQY_BLOCK_PARALLEL_STATS=1]  print the blocks whose guess failed
@@ -407,6 +410,14 @@ SQY_FUNCTION_PREFIX long SQYAMD_Get_Option(const char* name);
  * A stamp the call did not pass is 0.  tools/inflight_timeline.py reads them next to a kernel trace of the same run. */
 #define SQYAMD_CALL_STAMP_FIELDS 10
 SQY_FUNCTION_PREFIX long SQYAMD_Call_Stamps(long* out, long max_records);
+
+/* What the duplicate-chunk search decided in the newest chunked encode call that ran it while option "dedupe_report" was 1 (a 16-bit
+ * bitswap1 directly in front of lz4, more than one chunk).  Returns that call's number of chunks, 0 when there is no record.  Copies
+ * at most max entries each of: keys[k], the 64-bit key of FULL chunk k (1: every byte zero; a ragged last chunk has none, so one entry
+ * less than chunks is written then), and dup_of[k], k itself or the earlier chunk whose frame chunk k shares.  Either pointer may be NULL;
+ * with max <= 0 nothing is written.  A test diagnostic: the keys are hashes anyone can collide (tests/dedupe_collisions.py does), equal
+ * keys only nominate, a byte compare decides -- and a wrong or a missed decision is visible here where the blob may hide it. */
+SQY_FUNCTION_PREFIX long SQYAMD_Dedupe_Report(unsigned long long* keys, unsigned* dup_of, long max);
 
 /* Header helpers for callers that store blobs in containers of their own (the HDF5 filter's cd_values carry a header:
  * inc/sqeazy_h5_filter.hpp:117-121, src/hdf5_utils.hpp:730-738).  The reference does this through its C++ header class

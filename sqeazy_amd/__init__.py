@@ -36,7 +36,7 @@ EXPORTED_SYMBOLS = (
     "SQYAMD_Decode_Slabs_UI16_Device", "SQYAMD_Decode_Slabs_UI8_Device", "SQYAMD_Decode_Slabs_UI16", "SQYAMD_Decode_Slabs_UI8",
     "SQYAMD_Decode_Batch_UI16_Device", "SQYAMD_Decode_Batch_UI8_Device", "SQYAMD_Decode_Batch_UI16", "SQYAMD_Decode_Batch_UI8",
     "SQYAMD_Profile_Enable", "SQYAMD_Profile_Reset", "SQYAMD_Profile_Get",
-    "SQYAMD_Release_Workspace", "SQYAMD_Set_Option", "SQYAMD_Get_Option", "SQYAMD_Call_Stamps", "SQYAMD_Version", "SQYAMD_Header_Pipeline", "SQYAMD_Header_Build",
+    "SQYAMD_Release_Workspace", "SQYAMD_Set_Option", "SQYAMD_Get_Option", "SQYAMD_Call_Stamps", "SQYAMD_Dedupe_Report", "SQYAMD_Version", "SQYAMD_Header_Pipeline", "SQYAMD_Header_Build",
     "SQYAMD_Comm_UniqueId", "SQYAMD_Comm_Init", "SQYAMD_Comm_Destroy", "SQYAMD_Gather_Blobs",
 )
 
@@ -503,6 +503,19 @@ def call_stamps(max_records=8192):
     buf = (ctypes.c_long * (nf * max_records))()
     n = fn(buf, max_records)
     return [dict(zip(CALL_STAMP_FIELDS, buf[i * nf:(i + 1) * nf])) for i in range(n)]
+
+
+def dedupe_report():
+    """SQYAMD_Dedupe_Report: (keys, dup_of) of the newest chunked encode call that ran the duplicate-chunk search under option
+    "dedupe_report" -- uint64 keys of the full chunks, uint32 dup_of of all chunks; two empty arrays when there is no record"""
+    fn = lib().SQYAMD_Dedupe_Report
+    fn.restype = ctypes.c_long
+    fn.argtypes = [ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_uint), ctypes.c_long]
+    n = fn(None, None, 0)
+    keys, dup_of = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint32)
+    if n:
+        n = min(n, fn(keys.ctypes.data_as(ctypes.POINTER(ctypes.c_ulonglong)), dup_of.ctypes.data_as(ctypes.POINTER(ctypes.c_uint)), n))
+    return keys[:n], dup_of[:n]
 
 
 class option:

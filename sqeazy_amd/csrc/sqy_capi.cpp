@@ -90,6 +90,7 @@ struct Options {
     // backlog; .. because an idle lane did not answer (a foreign kernel in front of it in its hardware queue)
     std::atomic<long> lane_calls{0}, lane_backlog_fallbacks{0}, lane_blocked_fallbacks{0};
     std::atomic<long> call_stamps{0};                   // host time stamps per encode call (SQYAMD_Call_Stamps); off: a call pays one relaxed load
+    std::atomic<long> dedupe_report{0};                 // the duplicate search's keys and decisions of the newest call (SQYAMD_Dedupe_Report); off: one relaxed load
     Options()
         : transpose_chain(env_flag("SQY_NO_TRANSPOSE_CHAIN") ? 0 : 1), transpose_chain_caller_streams(env_flag("SQY_TRANSPOSE_CHAIN_CALLER_STREAMS")),
           block_parallel(env_flag("SQY_NO_BLOCK_PARALLEL") ? 0 : 1), block_parallel_warmup(env_number("SQY_BLOCK_PARALLEL_WARMUP", 65536, 0, kWarmupMax)),
@@ -131,6 +132,7 @@ struct Options {
         if (!std::strcmp(name, "lane_backlog_fallbacks")) return &lane_backlog_fallbacks;
         if (!std::strcmp(name, "lane_blocked_fallbacks")) return &lane_blocked_fallbacks;
         if (!std::strcmp(name, "call_stamps")) return &call_stamps;
+        if (!std::strcmp(name, "dedupe_report")) return &dedupe_report;
         return nullptr;
     }
 };
@@ -174,6 +176,18 @@ struct StampScope {
         else { g_stamps[g_stamps_next] = rec; g_stamps_next = (g_stamps_next + 1) % kStampRing; }
     }
 };
+
+// ---- dedupe report -------------------------------------------------------------------------------
+// What the duplicate-chunk search of the newest chunked encode call decided (option "dedupe_report", read back through
+// SQYAMD_Dedupe_Report): the key of every full chunk and dup_of of every chunk, as the kernels left them in the call's workspace.
+// A missed duplicate does not show in the blob (equal chunks compress to equal frames) and a key is only worth testing against
+// when it is the kernels' own: tests/dedupe_collisions.py.
+struct DedupeReport {
+    std::vector<uint64_t> keys;         // one per FULL chunk
+    std::vector<uint32_t> dup_of;       // one per chunk (a ragged last chunk is its own)
+};
+std::mutex g_dedupe_report_mu;
+DedupeReport g_dedupe_report;
 
 // ---- per-kernel timing -------------------------------------------------------------------------
 struct ProfEntry { std::string name; double ms = 0; long launches = 0; };
@@ -1465,9 +1479,27 @@ struct EncodeCall {
         return 0;
     }
 
+    // option dedupe_report: the search's keys and decisions, copied out of the workspace behind the call's last synchronisation
+    int report_dedupe()
+    {
+        if (!lz4.dup_of || !prep.dedupe.total || lz4.blocks) return 0;       // (no search in this call: the record kept stays)
+        DedupeReport rep;
+        rep.keys.resize(lz4.total / lz4.chunk);
+        rep.dup_of.resize(lz4.nchunks);
+        if (!rep.keys.empty())
+            SQY_HIP(hipMemcpyAsync(rep.keys.data(), static_cast<const uint8_t*>(ws->dedupe.p) + prep.dedupe.work_at, rep.keys.size() * sizeof(uint64_t),
+                                   hipMemcpyDeviceToHost, stream));
+        SQY_HIP(hipMemcpyAsync(rep.dup_of.data(), lz4.dup_of, rep.dup_of.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        SQY_HIP(hipStreamSynchronize(stream));
+        std::lock_guard<std::mutex> lock(g_dedupe_report_mu);
+        g_dedupe_report = std::move(rep);
+        return 0;
+    }
+
     // the blob is complete (the stream synchronised): it lies at d_dst + at
     int done(uint64_t at, uint64_t bytes, long* dstlength)
     {
+        if (g_opt.dedupe_report.load(std::memory_order_relaxed) != 0 && report_dedupe()) return 1;
         if (lanes) lanes->complete = true;
         if (g_prof_on.load()) prof_collect(*pend);
         if (dstoffset) *dstoffset = (long)at;
@@ -3963,6 +3995,10 @@ int SQYAMD_Set_Option(const char* name, long value)
         if (value != 0 && value != 1) return 1;
         if (value) { std::lock_guard<std::mutex> lock(g_stamps_mu); g_stamps.clear(); g_stamps_next = 0; }      // switching on starts a new record
     }
+    else if (o == &g_opt.dedupe_report) {
+        if (value != 0 && value != 1) return 1;
+        if (value) { std::lock_guard<std::mutex> lock(g_dedupe_report_mu); g_dedupe_report = DedupeReport(); }  // switching on drops the record kept
+    }
     else if (value != 0 && value != 1) return 1;
     o->store(value);
     return 0;
@@ -3987,6 +4023,15 @@ long SQYAMD_Call_Stamps(long* out, long max_records)
         for (int k = 0; k < CallStamps::kStamps; ++k) o[3 + k] = r.ns[k];
     }
     return (long)n;
+}
+
+long SQYAMD_Dedupe_Report(unsigned long long* keys, unsigned* dup_of, long max)
+{
+    std::lock_guard<std::mutex> lock(g_dedupe_report_mu);
+    const DedupeReport& r = g_dedupe_report;
+    if (max > 0 && keys) for (size_t i = 0; i < std::min<size_t>(r.keys.size(), (size_t)max); ++i) keys[i] = r.keys[i];
+    if (max > 0 && dup_of) for (size_t i = 0; i < std::min<size_t>(r.dup_of.size(), (size_t)max); ++i) dup_of[i] = r.dup_of[i];
+    return (long)r.dup_of.size();
 }
 
 void SQYAMD_Release_Workspace(void)
