@@ -300,6 +300,26 @@ SQY_FUNCTION_PREFIX int SQYAMD_Decode_BatchStrided_UI16_Device(const void* d_src
 SQY_FUNCTION_PREFIX int SQYAMD_Decode_BatchStrided_UI8_Device(const void* d_src, const long* offsets, const long* lengths, int nblobs,
                                                               void* const* d_dsts, const long* dst_shapes, const long* dst_strides,
                                                               unsigned shape_size, long* decoded_bytes, void* hip_stream);
+/* _BatchStrided_*_Device for a box of every blob -- the read of a box [origin, origin + extent) out of a tiled store, whose border cuts
+ * through tiles: the window of blob i begins at its voxel src_origins row i (shape_size longs, outermost first, host array; NULL: all
+ * zeros) and has the extent dst_shapes row i, which is also the shape of the view d_dsts[i] / dst_strides row i (the view rules of
+ * _BatchStrided_*; NULL strides: dense views).  Checked before anything is written (else 1, decoded_bytes zeroed): everything
+ * _BatchStrided_* checks but the equality of shapes; the header's rank equals shape_size; every origin >= 0, every extent >= 1,
+ * origin + extent <= the header's shape in every dimension (a sum that overflows is beyond it).  Exactly the window's voxels are written,
+ * to exactly the view's voxel places; decoded_bytes[i] = window voxels x voxel size.  Every blob's LZ4 stream is decoded whole; what
+ * follows is cropped: `bitswap1->lz4` blobs on the joint path go through an inverse transposer that stores only the window's voxels,
+ * `lz4` blobs' windows are copied straight out of the LZ4 output; every other blob is decoded dense into a workspace place and ONE launch
+ * at the end of the call copies the windows out ("batch_window_fused" = 0: every blob).  A blob whose window is all of it is a view of
+ * _BatchStrided_*, and a call of such blobs only IS that call: the same launches.  Return codes (a damaged blob: the composite code
+ * after every blob has been handled, the good windows in place), stream, context, ordering and thread safety as _Batch_*_Device. */
+SQY_FUNCTION_PREFIX int SQYAMD_Decode_BatchWindow_UI16_Device(const void* d_src, const long* offsets, const long* lengths, int nblobs,
+                                                              const long* src_origins, void* const* d_dsts, const long* dst_shapes,
+                                                              const long* dst_strides, unsigned shape_size, long* decoded_bytes,
+                                                              void* hip_stream);
+SQY_FUNCTION_PREFIX int SQYAMD_Decode_BatchWindow_UI8_Device(const void* d_src, const long* offsets, const long* lengths, int nblobs,
+                                                             const long* src_origins, void* const* d_dsts, const long* dst_shapes,
+                                                             const long* dst_strides, unsigned shape_size, long* decoded_bytes,
+                                                             void* hip_stream);
 /* host-pointer variants: blobs in host memory at src + offsets[i], dsts[i] host pointers (any alignment); arguments and headers are checked
  * on the host before any device is looked for */
 SQY_FUNCTION_PREFIX int SQYAMD_Decode_Batch_UI16(const char* src, const long* offsets, const long* lengths, int nblobs,
@@ -396,6 +416,9 @@ SQY_FUNCTION_PREFIX void SQYAMD_Release_Workspace(void);
  *   "batch_strided_fused"             1 [SQY_NO_BATCH_STRIDED_FUSED=1 -> 0]  SQYAMD_*_BatchStrided_*: the bitswap1 transposers gather from and scatter
  *                                     into the views, `lz4` packs into the stream and unpacks from the LZ4 output (0: packed copies for every
  *                                     pipeline -- same bytes)
+ *   "batch_window_fused"              1 [SQY_NO_BATCH_WINDOW_FUSED=1 -> 0]  SQYAMD_Decode_BatchWindow_*: the inverse transposer stores only the window's
+ *                                     voxels, `lz4` windows are copied out of the LZ4 output (0: every blob decoded dense into the workspace, one
+ *                                     window copy at the end of the call -- same bytes)
  * Set: 0 = done, 1 = unknown name or value out of range.  Get: the value, -1 for an unknown name. */
 SQY_FUNCTION_PREFIX int SQYAMD_Set_Option(const char* name, long value);
 SQY_FUNCTION_PREFIX long SQYAMD_Get_Option(const char* name);

@@ -30,6 +30,7 @@ EXPORTED_SYMBOLS = (
     "SQYAMD_PipelineEncode_Batch_UI16_Device", "SQYAMD_PipelineEncode_Batch_UI8_Device", "SQYAMD_PipelineEncode_Batch_UI16", "SQYAMD_PipelineEncode_Batch_UI8",
     "SQYAMD_PipelineEncode_BatchStrided_UI16_Device", "SQYAMD_PipelineEncode_BatchStrided_UI8_Device",
     "SQYAMD_Decode_BatchStrided_UI16_Device", "SQYAMD_Decode_BatchStrided_UI8_Device",
+    "SQYAMD_Decode_BatchWindow_UI16_Device", "SQYAMD_Decode_BatchWindow_UI8_Device",
     "SQYAMD_PipelineEncode_UI16_Cap", "SQYAMD_PipelineEncode_UI8_Cap",
     "SQYAMD_Decode_UI16_Device", "SQYAMD_Decode_UI8_Device",
     "SQYAMD_Decode_Frames_UI16_Device", "SQYAMD_Decode_Frames_UI8_Device", "SQYAMD_Decode_Frames_UI16", "SQYAMD_Decode_Frames_UI8",
@@ -91,6 +92,9 @@ def lib():
         for f in ("SQYAMD_Decode_BatchStrided_UI8_Device", "SQYAMD_Decode_BatchStrided_UI16_Device"):
             getattr(L, f).argtypes = [ctypes.c_void_p, c_long_p, c_long_p, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), c_long_p, c_long_p, ctypes.c_uint,
                                       c_long_p, ctypes.c_void_p]
+        for f in ("SQYAMD_Decode_BatchWindow_UI8_Device", "SQYAMD_Decode_BatchWindow_UI16_Device"):
+            getattr(L, f).argtypes = [ctypes.c_void_p, c_long_p, c_long_p, ctypes.c_int, c_long_p, ctypes.POINTER(ctypes.c_void_p), c_long_p, c_long_p,
+                                      ctypes.c_uint, c_long_p, ctypes.c_void_p]
         for f in ("SQYAMD_PipelineEncode_Batch_UI8", "SQYAMD_PipelineEncode_Batch_UI16"):
             getattr(L, f).argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_void_p), c_long_p, ctypes.c_uint, ctypes.c_int, ctypes.c_void_p, ctypes.c_long,
                                       c_long_p, c_long_p, ctypes.c_int]
@@ -447,6 +451,59 @@ def decode_batch_strided_device(d_src, offsets, lengths, d_dsts, shapes, strides
         _longs([x for s in shapes for x in s]) if n else None, _longs([x for s in strides for x in s]) if n and strides is not None else None,
         ctypes.c_uint(rank), decoded, ctypes.c_void_p(stream or 0))
     return rc, list(decoded[:n])
+
+
+def decode_batch_window_device(d_src, offsets, lengths, origins, d_dsts, shapes, strides, dtype, stream=None):
+    """SQYAMD_Decode_BatchWindow_*_Device: of blob i at d_src + offsets[i] (lengths[i] bytes) the window that begins at its voxel origins[i]
+    (None: every window at its blob's first voxel) and has the extent shapes[i], into the strided view at device pointer d_dsts[i] with
+    that shape and strides[i] in voxels (None: dense); only the view's voxels are written.  Returns (rc, decoded_bytes)."""
+    n = len(offsets)
+    rank = len(shapes[0]) if n else 0
+    ptrs = (ctypes.c_void_p * max(n, 1))(*[p if p is None else int(p) for p in d_dsts])
+    decoded = (ctypes.c_long * max(n, 1))()
+    rc = getattr(lib(), "SQYAMD_Decode_BatchWindow_%s_Device" % _suffix(dtype))(
+        ctypes.c_void_p(int(d_src)), _longs(offsets) if n else None, _longs(lengths) if n else None, ctypes.c_int(n),
+        _longs([x for o in origins for x in o]) if n and origins is not None else None, ptrs, _longs([x for s in shapes for x in s]) if n else None,
+        _longs([x for s in strides for x in s]) if n and strides is not None else None, ctypes.c_uint(rank), decoded, ctypes.c_void_p(stream or 0))
+    return rc, list(decoded[:n])
+
+
+def box_windows(shape, tile, box_origin, box_extent, dst_ptr, dst_strides, itemsize):
+    """The read of the box [box_origin, box_origin + box_extent) of a parent of `shape` that is stored as the blobs of tile_views(.., shape,
+    tile, ..) in that grid order, as the arguments of decode_batch_window_device: returns (tile_indices, origins, ptrs, shapes, strides) --
+    the tiles the box intersects in ascending index order and for each one the window inside the tile (origin, shape) and the view that
+    takes it inside a box buffer whose first voxel is at device pointer dst_ptr (ptr; strides = dst_strides, in voxels; None: a dense box).
+    Pure Python.  ValueError: ranks that differ, a rank outside 1 to 3, a non-positive extent, a box outside the parent."""
+    shape, tile, o, e = ([int(x) for x in v] for v in (shape, tile, box_origin, box_extent))
+    rank = len(shape)
+    if not 1 <= rank <= 3 or any(len(v) != rank for v in (tile, o, e)) or (dst_strides is not None and len(dst_strides) != rank):
+        raise ValueError("box_windows: shape, tile, box and strides of one rank (1 to 3)")
+    if min(shape + tile + e) < 1:
+        raise ValueError("box_windows: positive extents")
+    if any(o[k] < 0 or o[k] + e[k] > shape[k] for k in range(rank)):
+        raise ValueError("box_windows: the box lies outside the parent")
+    if dst_strides is None:
+        strides = [1] * rank
+        for k in range(rank - 2, -1, -1):
+            strides[k] = strides[k + 1] * e[k + 1]
+    else:
+        strides = [int(x) for x in dst_strides]
+    grid = [(shape[k] + tile[k] - 1) // tile[k] for k in range(rank)]
+    cells = [[]]                                                    # the grid cells the box reaches, row-major: ascending tile index
+    for k in range(rank):
+        cells = [c + [t] for c in cells for t in range(o[k] // tile[k], (o[k] + e[k] - 1) // tile[k] + 1)]
+    indices, origins, ptrs, shapes = [], [], [], []
+    for c in cells:
+        index = 0
+        for k in range(rank):
+            index = index * grid[k] + c[k]
+        lo = [max(o[k], c[k] * tile[k]) for k in range(rank)]       # the part of the box in this tile, parent coordinates
+        hi = [min(o[k] + e[k], (c[k] + 1) * tile[k]) for k in range(rank)]
+        indices.append(index)
+        origins.append(tuple(lo[k] - c[k] * tile[k] for k in range(rank)))
+        shapes.append(tuple(hi[k] - lo[k] for k in range(rank)))
+        ptrs.append(int(dst_ptr) + sum((lo[k] - o[k]) * strides[k] for k in range(rank)) * int(itemsize))
+    return indices, origins, ptrs, shapes, [tuple(strides)] * len(indices)
 
 
 def decode_batch(blobs):

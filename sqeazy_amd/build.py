@@ -12,7 +12,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libsqeazy_amd.so")
 SOURCES = ["sqy_kernels.hip", "sqy_pipeline.cpp", "sqy_capi.cpp", "sqy_rccl.cpp"]
-HEADERS = ["sqy_kernels.h", "sqy_pipeline.hpp", "sqy_lanes.hpp", "sqy_quantiser_lut.hpp", "sqy_batch_view.hpp", os.path.join("..", "..", "include", "sqeazy_amd.h")]
+HEADERS = ["sqy_kernels.h", "sqy_pipeline.hpp", "sqy_lanes.hpp", "sqy_quantiser_lut.hpp", "sqy_batch_view.hpp", "sqy_batch_window.hpp", os.path.join("..", "..", "include", "sqeazy_amd.h")]
 ARCH = "gfx950"
 # the one and only configuration of libsqeazy_amd.so; kernel experiments live in tools/ and build their own binaries
 # (tried: -mllvm -amdgpu-sched-strategy=max-ilp -- the LZ4 parse kernels alone 3 % faster, the bench with three calls in flight 1.5 % slower)

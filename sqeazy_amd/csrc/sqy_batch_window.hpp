@@ -1,0 +1,90 @@
+// sqy_batch_window.hpp -- the clip of a window (SQYAMD_Decode_BatchWindow_*), written once for two callers under sqy_batch_view.hpp's
+// rule: the kernels that store only a window's voxels (sqy_kernels.hip) and plain host C++ (no HIP header needed:
+// tests/sanitize/batch_window_test.cpp holds it against a triple loop for every window of small blobs).
+//
+// A blob is bZ x bY x bX voxels in dense order i = (z bY + y) bX + x.  A window is the box [oz, oz + Z) x [oy, oy + Y) x [ox, ox + X) of
+// it; its voxel (z, y, x) goes to offset (z - oz) sz + (y - oy) sy + (x - ox) of the destination view.  The clip takes a run [i0, i0 + n)
+// of the blob's dense order and yields the sub-runs that lie inside the window -- each one within a row, so consecutive on both sides --
+// with two divisions at its start and none afterwards: what lies outside is stepped over with multiplications.
+#ifndef SQY_BATCH_WINDOW_HPP_
+#define SQY_BATCH_WINDOW_HPP_
+
+#include "sqy_batch_view.hpp"
+
+namespace sqy {
+
+// the blob's rows and the window in it (the blob's bZ is not needed: the run ends where the caller says), the destination view's pitches
+struct WindowGeometry { uint64_t bY, bX, oz, oy, ox, Z, Y, X, sz, sy; };
+
+struct WindowClip {
+    uint64_t z, y, x;        // the blob coordinates of the voxel at `pos`
+    uint64_t pos, n;         // where the clip stands in the run, the run's length
+};
+
+// a sub-run: `len` voxels from offset `run_off` of the run go to offset `dst_off` of the destination view
+struct WindowPiece { uint64_t run_off, dst_off, len; };
+
+// the clip of the run [i0, i0 + n) (i0 + n <= bZ bY bX)
+SQY_VIEW_HD inline WindowClip window_clip_start(const WindowGeometry& g, uint64_t i0, uint64_t n)
+{
+    uint64_t row, z;
+    if (((i0 | g.bX | g.bY) >> 32) == 0) {
+        row = (uint32_t)i0 / (uint32_t)g.bX;
+        z = (uint32_t)row / (uint32_t)g.bY;
+    } else {
+        row = i0 / g.bX;
+        z = row / g.bY;
+    }
+    return WindowClip{z, row - z * g.bY, i0 - row * g.bX, 0, n};
+}
+
+// The next sub-run inside the window, false when the run has none left.  Every turn of the loop either yields or steps over at least one
+// voxel that lies outside, whole rows and frames at a time.
+SQY_VIEW_HD inline bool window_clip_next(const WindowGeometry& g, WindowClip* c, WindowPiece* out)
+{
+    while (c->pos < c->n) {
+        if (c->z >= g.oz + g.Z) break;                                  // behind the window's last frame: nothing more
+        if (c->z < g.oz) {                                              // to the window's first frame
+            c->pos += (g.oz - c->z) * g.bY * g.bX - (c->y * g.bX + c->x);
+            c->z = g.oz; c->y = 0; c->x = 0;
+        } else if (c->y < g.oy) {                                       // to its first row in this frame
+            c->pos += (g.oy - c->y) * g.bX - c->x;
+            c->y = g.oy; c->x = 0;
+        } else if (c->y >= g.oy + g.Y) {                                // to the next frame
+            c->pos += (g.bY - c->y) * g.bX - c->x;
+            ++c->z; c->y = 0; c->x = 0;
+        } else if (c->x < g.ox) {                                       // to its first column in this row
+            c->pos += g.ox - c->x;
+            c->x = g.ox;
+        } else if (c->x >= g.ox + g.X) {                                // to the next row
+            c->pos += g.bX - c->x;
+            c->x = 0;
+            if (++c->y == g.bY) { c->y = 0; ++c->z; }
+        } else {
+            const uint64_t in_row = g.ox + g.X - c->x, in_run = c->n - c->pos, len = in_row < in_run ? in_row : in_run;
+            out->run_off = c->pos;
+            out->dst_off = (c->z - g.oz) * g.sz + (c->y - g.oy) * g.sy + (c->x - g.ox);
+            out->len = len;
+            c->pos += len;
+            c->x += len;
+            if (c->x == g.bX) {
+                c->x = 0;
+                if (++c->y == g.bY) { c->y = 0; ++c->z; }
+            }
+            return true;
+        }
+    }
+    c->pos = c->n;
+    return false;
+}
+
+// The tiles of `tile` voxels of the blob's dense order that hold a voxel of the window's frames [oz, oz + Z): the first one and their
+// count (the transposer's grid holds no others)
+SQY_VIEW_HD inline uint64_t window_first_tile(const WindowGeometry& g, uint64_t tile) { return g.oz * g.bY * g.bX / tile; }
+SQY_VIEW_HD inline uint64_t window_tile_count(const WindowGeometry& g, uint64_t tile)
+{
+    return ((g.oz + g.Z) * g.bY * g.bX - 1) / tile - window_first_tile(g, tile) + 1;
+}
+
+} // namespace sqy
+#endif

@@ -22,6 +22,7 @@
 #include <thread>
 #include <vector>
 
+#include "sqy_batch_window.hpp"
 #include "sqy_kernels.h"
 #include "sqy_lanes.hpp"
 #include "sqy_pipeline.hpp"
@@ -84,6 +85,7 @@ struct Options {
     std::atomic<long> encode_batch_group_bytes;         // .. the LZ4 input one group holds at most (a group holds at least one volume)
     std::atomic<long> encode_batch_joint_max_bytes;     // .. a volume with more LZ4 input than this is encoded on its own (frames in place)
     std::atomic<long> batch_strided_fused;              // strided views: the transposers gather from / scatter into the view, `lz4` packs into the stream and unpacks from the LZ4 output (0: packed copies everywhere)
+    std::atomic<long> batch_window_fused;               // windows: the inverse transposer stores only the window's voxels, `lz4` windows are copied out of the LZ4 output (0: every blob decoded dense, one window copy)
     std::atomic<long> stage_lanes;                      // frames-in-place calls on caller streams run on the library's lanes: 0 never, 1 always, 2 where transpose_chain_caller_streams is on
     std::atomic<long> parse_lanes;                      // .. how many parse lanes a device has (1-8)
     // counters (Get reads, Set takes 0 only): calls that ran on the lanes; calls that stayed on their caller's stream because it had a
@@ -102,7 +104,7 @@ struct Options {
           decode_batch_group_bytes(env_number("SQY_DECODE_BATCH_GROUP_BYTES", (long)kSlabsGroupBytes, 1, (long)kSlabsGroupBytes)), encode_batch_joint(env_flag("SQY_NO_ENCODE_BATCH_JOINT") ? 0 : 1),
           encode_batch_group_bytes(env_number("SQY_ENCODE_BATCH_GROUP_BYTES", kBatchGroupBytesDefault, 1, kBatchBytesMax)),
           encode_batch_joint_max_bytes(env_number("SQY_ENCODE_BATCH_JOINT_MAX_BYTES", kBatchJointMaxDefault, 0, kBatchBytesMax)),
-          batch_strided_fused(env_flag("SQY_NO_BATCH_STRIDED_FUSED") ? 0 : 1), stage_lanes(env_number("SQY_STAGE_LANES", kStageLanesDefault, 0, 2)),
+          batch_strided_fused(env_flag("SQY_NO_BATCH_STRIDED_FUSED") ? 0 : 1), batch_window_fused(env_flag("SQY_NO_BATCH_WINDOW_FUSED") ? 0 : 1), stage_lanes(env_number("SQY_STAGE_LANES", kStageLanesDefault, 0, 2)),
           parse_lanes(env_number("SQY_PARSE_LANES", kParseLanesDefault, 1, sqy::LanePicker::kMaxLanes)) { sqy::set_bitswap1_blocks_per_cu(transpose_blocks_per_cu.load()); }
     std::atomic<long>* find(const char* name)
     {
@@ -126,6 +128,7 @@ struct Options {
         if (!std::strcmp(name, "encode_batch_group_bytes")) return &encode_batch_group_bytes;
         if (!std::strcmp(name, "encode_batch_joint_max_bytes")) return &encode_batch_joint_max_bytes;
         if (!std::strcmp(name, "batch_strided_fused")) return &batch_strided_fused;
+        if (!std::strcmp(name, "batch_window_fused")) return &batch_window_fused;
         if (!std::strcmp(name, "stage_lanes")) return &stage_lanes;
         if (!std::strcmp(name, "parse_lanes")) return &parse_lanes;
         if (!std::strcmp(name, "lane_calls")) return &lane_calls;
@@ -333,6 +336,7 @@ struct Workspace {
     DevBuf batch_pack;        // strided views: the packed copies of a group's views (encode), the dense places of a call's views (decode)
     DevBuf batch_pack_one;    // .. decode: the dense place of a view whose blob is decoded on its own
     DevBuf batch_views[3];    // .. the job and tile tables of the view launches: pack / unpack, the strided transposer, the strided copy
+    DevBuf batch_windows[3];  // .. and of the window launches: the window copy, the windowed transposer, the copy out of the LZ4 output
     void* pinned = nullptr;   // 4 KiB of pinned host memory for small read-backs
     void release_buffers()
     {
@@ -340,7 +344,7 @@ struct Workspace {
         io_src.release(); io_dst.release(); small.release(); plan.release(); dedupe.release(); diff_side.release(); spec.release(); digest.release(); bkrd.release();
         subset.release(); range_full.release(); slabs_index.release(); slabs_joint.release(); slabs_out.release(); slabs_host.release();
         batch_stream.release(); batch_scratch.release(); batch_tables.release(); batch_quant.release(); batch_host.release();
-        batch_pack.release(); batch_pack_one.release(); for (DevBuf& b : batch_views) b.release();
+        batch_pack.release(); batch_pack_one.release(); for (DevBuf& b : batch_views) b.release(); for (DevBuf& b : batch_windows) b.release();
     }
 };
 
@@ -2459,6 +2463,79 @@ int admit_views(const char* who, const void* const* ptrs, const long* shapes, co
     return 0;
 }
 
+// ---- windows (SQYAMD_Decode_BatchWindow_*) ----------------------------------------------------------------------------------------------------
+// A window is admitted on the host (sqy::admit_window) against its blob's header before anything is written.  Layer one: the blob is
+// decoded dense into a place of Workspace::batch_pack, ONE batch_window_copy launch at the end of the call copies every window out.
+// Layer two (the option batch_window_fused): on the joint path the `bitswap1->lz4` blobs' inverse transposer stores only the window's
+// voxels, the `lz4` blobs' windows are copied straight out of the LZ4 output.
+static_assert(sizeof(sqy::BatchWindowJob) == sqy::kBatchWindowJobBytes, "the window job's layout");
+
+// a window's view as the caller gave it, padded to three dimensions and NOT folded (admit_view folds; the window's rows must stay rows)
+struct WindowView { uint64_t sz, sy; };
+WindowView window_view(const sqy::BatchWindow& w, const long* strides, unsigned rank)
+{
+    uint64_t s[3] = {w.Y * w.X, w.X, 1};
+    if (strides) {
+        for (unsigned k = 0; k < rank; ++k) s[3 - rank + k] = (uint64_t)strides[k];
+        for (int k = 2 - (int)rank; k >= 0; --k) s[k] = (k == 1 ? w.X : w.Y) * s[k + 1];      // (extent 1 there: never stepped over)
+    }
+    return WindowView{s[0], s[1]};
+}
+
+// ViewLaunch for window jobs (sqy::batch_window_layout); the same rule for `host`
+struct WindowLaunch {
+    enum Kind { copy, bitswap1_decode, copy_from_lz4 };
+    std::vector<sqy::BatchWindowJob> jobs;
+    std::vector<uint32_t> first_tile;
+    uint32_t ntiles = 0;
+    std::vector<unsigned char> host;
+    hipStream_t queued_on = nullptr;
+    bool queued = false;
+    WindowLaunch() = default;
+    WindowLaunch(const WindowLaunch&) = delete;
+    WindowLaunch& operator=(const WindowLaunch&) = delete;
+    ~WindowLaunch() { wait(); }
+    void wait() { if (queued) (void)hipStreamSynchronize(queued_on); queued = false; }
+    void clear() { wait(); jobs.clear(); first_tile.clear(); ntiles = 0; host.clear(); }
+    // blob_tiles: the job is the windowed transposer's (the blob's tiles that reach into the window's frames), else the copy's (the
+    // window's own tiles)
+    void add(const void* view, const void* dense, const sqy::BatchWindow& w, const WindowView& v, bool blob_tiles)
+    {
+        const sqy::WindowGeometry g{w.bY, w.bX, w.oz, w.oy, w.ox, w.Z, w.Y, w.X, v.sz, v.sy};
+        const uint64_t tile0 = blob_tiles ? sqy::window_first_tile(g, sqy::kBatchTileVoxels) : 0;
+        jobs.push_back(sqy::BatchWindowJob{const_cast<void*>(view), dense, w.Z, w.Y, w.X, v.sz, v.sy, w.bZ, w.bY, w.bX, w.oz, w.oy, w.ox, tile0});
+        first_tile.push_back(ntiles);
+        ntiles += blob_tiles ? (uint32_t)sqy::window_tile_count(g, sqy::kBatchTileVoxels) : sqy::batch_bitswap1_tiles(w.Z * w.Y * w.X);
+    }
+};
+// the tables to Workspace::batch_windows[kind], the launch behind them under its profile name; no jobs: nothing
+int launch_windows(Context& cx, hipStream_t stream, WindowLaunch& l, WindowLaunch::Kind kind, int elem_size)
+{
+    if (l.jobs.empty()) return 0;
+    std::vector<PendingEvent>* pend = &cx.pending;
+    const size_t nj = l.jobs.size();
+    const sqy::BatchWindowLayout lay = sqy::batch_window_layout(nj);
+    l.first_tile.push_back(l.ntiles);
+    l.host.assign(lay.total, 0);
+    std::memcpy(l.host.data(), l.jobs.data(), nj * sizeof(sqy::BatchWindowJob));
+    std::memcpy(l.host.data() + lay.tiles_at, l.first_tile.data(), (nj + 1) * 4);
+    DevBuf& buf = cx.ws.batch_windows[(int)kind];
+    if (buf.ensure(l.host.size())) return 1;
+    l.queued_on = stream;
+    l.queued = true;
+    SQY_HIP(hipMemcpyAsync(buf.p, l.host.data(), l.host.size(), hipMemcpyHostToDevice, stream));
+    const sqy::BatchWindowJob* d_jobs = static_cast<const sqy::BatchWindowJob*>(buf.p);
+    const uint32_t* d_tiles = reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(buf.p) + lay.tiles_at);
+    switch (kind) {
+    case WindowLaunch::copy: SQY_TIMED("batch_window_copy", sqy::launch_batch_window_copy(d_jobs, d_tiles, (uint32_t)nj, l.ntiles, elem_size, stream)); break;
+    case WindowLaunch::bitswap1_decode:
+        SQY_TIMED("batch_bitswap1_decode_window", sqy::launch_bitswap1_decode_batch_window(d_jobs, d_tiles, (uint32_t)nj, l.ntiles, elem_size, stream));
+        break;
+    case WindowLaunch::copy_from_lz4: SQY_TIMED("batch_copy_window", sqy::launch_batch_window_copy(d_jobs, d_tiles, (uint32_t)nj, l.ntiles, elem_size, stream)); break;
+    }
+    return 0;
+}
+
 // ---- z-slab blob sets (SQYAMD_Decode_Slabs_*) and batches (SQYAMD_Decode_Batch_*): a group on the joint path -----------------
 // Blobs in the chunked LZ4 layout are decoded in groups.  What both callers share, one function per step: the frame ranking of every blob
 // of a group in one launch per kernel and one read-back (group_rank), one joint block index and one LZ4 decode launch for all of them
@@ -2664,8 +2741,13 @@ int decode_slabs_group(Context& cx, const uint8_t* d_src, std::vector<SlabBlob>&
 // launches' tables for sv->scatter and sv->copy (alive as `tables` is) -- one batch_bitswap1_decode_strided, one batch_copy_strided launch
 struct StridedDecode {
     const std::vector<sqy::BatchView>* views = nullptr;
-    std::vector<uint8_t> direct;            // per blob: 1 = the joint path's last launch writes into the view
+    std::vector<uint8_t> direct;            // per blob: 1 = the joint path's last launch writes into the view, 2 = .. the window's voxels into it
     ViewLaunch scatter, copy;
+    // windows (SQYAMD_Decode_BatchWindow_*): blob b's window and its unfolded view, for direct[b] == 2 -- one batch_bitswap1_decode_window,
+    // one batch_copy_window launch
+    const std::vector<sqy::BatchWindow>* wins = nullptr;
+    std::vector<WindowView> wviews;
+    WindowLaunch wscatter, wcopy;
 };
 int batch_group_tail(JointGroup& G, const sqy::DecodeJointLayout& L, const sqy::DecodeBatchGroup& pg, const std::vector<sqy::DecodeBatchBlob>& plan_in, int elem_size,
                      std::vector<unsigned char>& tables, StridedDecode* sv = nullptr)
@@ -2689,6 +2771,10 @@ int batch_group_tail(JointGroup& G, const sqy::DecodeJointLayout& L, const sqy::
             const SlabBlob& s = G.blobs[b];
             if (sv && sv->direct[b] == 1 && plan_in[b].form != sqy::DecodeBatchForm::diff_planes) {
                 (k == 0 ? sv->scatter : sv->copy).add(s.call->d_dst, G.out + s.out_base, (*sv->views)[b]);
+                continue;
+            }
+            if (sv && sv->direct[b] == 2 && plan_in[b].form != sqy::DecodeBatchForm::diff_planes) {
+                (k == 0 ? sv->wscatter : sv->wcopy).add(s.call->d_dst, G.out + s.out_base, (*sv->wins)[b], sv->wviews[b], k == 0);
                 continue;
             }
             void* to = plan_in[b].form == sqy::DecodeBatchForm::diff_planes ? static_cast<void*>(G.out + res_of[b]) : s.call->d_dst;
@@ -2722,6 +2808,8 @@ int batch_group_tail(JointGroup& G, const sqy::DecodeJointLayout& L, const sqy::
                                                                                          (uint32_t)dense_jobs[2], dense_tiles[2], stream));
     if (sv && (launch_views(G.cx, stream, sv->scatter, ViewLaunch::bitswap1_decode, 1, elem_size) || launch_views(G.cx, stream, sv->copy, ViewLaunch::copy_to_view, 2, elem_size)))
         return 1;
+    if (sv && (launch_windows(G.cx, stream, sv->wscatter, WindowLaunch::bitswap1_decode, elem_size) || launch_windows(G.cx, stream, sv->wcopy, WindowLaunch::copy_from_lz4, elem_size)))
+        return 1;
     if (nd) {
         // (every launch timed on its own: the profile counts the launches, 1 + steps whatever the number of blobs)
         const sqy::DiffBatchJob* d_diff = reinterpret_cast<const sqy::DiffBatchJob*>(dj + L.diff.jobs_at);
@@ -2738,7 +2826,7 @@ int batch_group_tail(JointGroup& G, const sqy::DecodeJointLayout& L, const sqy::
 int decode_batch_group(Context& cx, const uint8_t* d_src, std::vector<SlabBlob>& blobs, const std::vector<sqy::DecodeBatchBlob>& plan_in, uint64_t group_bytes,
                        const sqy::DecodeBatchPlan& plan, size_t gi, int elem_size, hipStream_t stream, std::vector<size_t>& single, StridedDecode* sv = nullptr)
 {
-    if (sv) { sv->scatter.clear(); sv->copy.clear(); }                  // (the group before has been synchronised)
+    if (sv) { sv->scatter.clear(); sv->copy.clear(); sv->wscatter.clear(); sv->wcopy.clear(); }     // (the group before has been synchronised)
     const sqy::DecodeBatchGroup* pg = &plan.groups[gi];
     const std::vector<size_t> g(pg->blobs.begin(), pg->blobs.end());
     for (size_t k = 0; k < g.size(); ++k) blobs[g[k]].out_base = pg->out_at[k];
@@ -2939,13 +3027,18 @@ void batch_stage_form(SlabBlob& b, const void* dst, int want_elem, sqy::DecodeBa
 }
 
 // views (SQYAMD_Decode_BatchStrided_*): blob i's header shape must be row i of shapes (rank dimensions); a.dsts[i] is view i
+// windows (SQYAMD_Decode_BatchWindow_*, wa != nullptr): row i of shapes is the extent of a window of blob i that begins at row i of
+// wa->origins; a blob whose window is all of it is a view as above, and a call of such blobs only takes every path it takes there
+struct WindowArgs { const long* origins; const long* strides; };
 int decode_batch_on_device(Context& cx, const void* d_src_v, const BatchDecodeArgs& a, int want_elem, hipStream_t stream,
-                           const std::vector<sqy::BatchView>* views = nullptr, const long* shapes = nullptr, unsigned rank = 0)
+                           const std::vector<sqy::BatchView>* views = nullptr, const long* shapes = nullptr, unsigned rank = 0, const WindowArgs* wa = nullptr)
 {
     const uint8_t* d_src = static_cast<const uint8_t*>(d_src_v);
     StridedDecode sv;
     sv.views = views;
     ViewLaunch unpacks;                                                 // (in front of the drain: alive until it has synchronised)
+    WindowLaunch wcopies;
+    std::vector<sqy::BatchWindow> wins(wa ? (size_t)a.nblobs : 0);
     DrainOnExit drain{stream, &cx.pending, cx.side};
     const size_t n = (size_t)a.nblobs;
     std::vector<SlabBlob> blobs(n);
@@ -2955,6 +3048,11 @@ int decode_batch_on_device(Context& cx, const void* d_src_v, const BatchDecodeAr
     }
     // 1. the headers, checked before anything is written
     if (fetch_blob_headers(cx, blobs, want_elem, stream, "decode batch", [&](int i) {
+            if (wa) {                                                   // (the view was admitted for the window's extent, aligned to the voxel size)
+                if (sqy::admit_window(blobs[i].h.shape, wa->origins ? wa->origins + (size_t)i * rank : nullptr, shapes + (size_t)i * rank, rank, &wins[(size_t)i])) return true;
+                std::fprintf(stderr, "[sqeazy]\t decode batch: blob %d's window does not lie inside its shape\n", i);
+                return false;
+            }
             if (views) {
                 const std::vector<uint64_t>& hs = blobs[i].h.shape;
                 bool same = hs.size() == rank;
@@ -2964,7 +3062,12 @@ int decode_batch_on_device(Context& cx, const void* d_src_v, const BatchDecodeAr
             return batch_blob_fits(i, blobs[i].raw, a.dsts[i], a.capacities[i], want_elem);
         }))
         return 1;
-    if (a.decoded) for (size_t i = 0; i < n; ++i) a.decoded[i] = (long)blobs[i].raw;
+    // the blobs whose window is a part of them; none: a call of views
+    std::vector<uint8_t> windowed(n, 0);
+    bool any_window = false;
+    for (size_t i = 0; i < wins.size(); ++i) if (!wins[i].whole) { windowed[i] = 1; any_window = true; }
+    if (a.decoded)
+        for (size_t i = 0; i < n; ++i) a.decoded[i] = windowed[i] ? (long)(wins[i].Z * wins[i].Y * wins[i].X * (uint64_t)want_elem) : (long)blobs[i].raw;
     const bool joint_on = g_opt.decode_batch_joint.load() != 0;
     // where blob i's voxels go as a dense volume: its destination -- or, for a view that is no dense allocation, a place in
     // Workspace::batch_pack, unpacked by ONE launch at the end of the call; unless (batch_strided_fused) its pipeline is one whose last
@@ -2972,22 +3075,29 @@ int decode_batch_on_device(Context& cx, const void* d_src_v, const BatchDecodeAr
     std::vector<void*> dst_of(a.dsts, a.dsts + n);
     bool strided = false;
     if (views) {
-        const bool fused = joint_on && g_opt.batch_strided_fused.load() != 0;
+        const bool fused = joint_on && g_opt.batch_strided_fused.load() != 0, wfused = joint_on && g_opt.batch_window_fused.load() != 0;
         sv.direct.assign(n, 0);
+        if (any_window) {
+            sv.wins = &wins;
+            sv.wviews.resize(n);
+            for (size_t i = 0; i < n; ++i) sv.wviews[i] = window_view(wins[i], wa->strides ? wa->strides + i * rank : nullptr, rank);
+        }
         std::vector<uint64_t> place(n, 0);
         uint64_t bytes = 0;
         for (size_t i = 0; i < n; ++i) {
-            if ((*views)[i].dense) continue;
+            if (!windowed[i] && (*views)[i].dense) continue;
             strided = true;
             const std::vector<Stage> st = Pipeline::from_string(blobs[i].h.pipename).stages;
-            if (fused && !st.empty() && st.back().kind == StageKind::lz4 && (st.size() == 1 || (st.size() == 2 && st[0].kind == StageKind::bitswap1))) sv.direct[i] = 1;
+            if ((windowed[i] ? wfused : fused) && !st.empty() && st.back().kind == StageKind::lz4 && (st.size() == 1 || (st.size() == 2 && st[0].kind == StageKind::bitswap1)))
+                sv.direct[i] = windowed[i] ? 2 : 1;
             else { place[i] = bytes; bytes += align_up(blobs[i].raw, 256); }
         }
         if (bytes && cx.ws.batch_pack.ensure(bytes)) return 1;
         for (size_t i = 0; i < n; ++i)
-            if (!(*views)[i].dense && !sv.direct[i]) {
+            if ((windowed[i] || !(*views)[i].dense) && !sv.direct[i]) {
                 dst_of[i] = static_cast<uint8_t*>(cx.ws.batch_pack.p) + place[i];
-                unpacks.add(a.dsts[i], dst_of[i], (*views)[i]);
+                if (windowed[i]) wcopies.add(a.dsts[i], dst_of[i], wins[i], sv.wviews[i], false);
+                else unpacks.add(a.dsts[i], dst_of[i], (*views)[i]);
             }
     }
     StridedDecode* const svp = strided ? &sv : nullptr;
@@ -3030,12 +3140,14 @@ int decode_batch_on_device(Context& cx, const void* d_src_v, const BatchDecodeAr
         blobs[b].rc = decode_on_device(cx, blobs[b].src, blobs[b].len, cx.ws.batch_pack_one.p, blobs[b].raw, want_elem, stream);
         if (blobs[b].rc) continue;
         ViewLaunch one;
-        one.add(a.dsts[b], cx.ws.batch_pack_one.p, (*views)[b]);
-        if (launch_views(cx, stream, one, ViewLaunch::unpack, 0, want_elem)) return 1;
+        WindowLaunch wone;
+        if (windowed[b]) wone.add(a.dsts[b], cx.ws.batch_pack_one.p, wins[b], sv.wviews[b], false);
+        else one.add(a.dsts[b], cx.ws.batch_pack_one.p, (*views)[b]);
+        if (launch_views(cx, stream, one, ViewLaunch::unpack, 0, want_elem) || launch_windows(cx, stream, wone, WindowLaunch::copy, want_elem)) return 1;
         SQY_HIP(hipStreamSynchronize(stream));                          // (the launch's tables are this scope's)
     }
-    // 4. the views with a place in the workspace: ONE unpack launch
-    if (svp && launch_views(cx, stream, unpacks, ViewLaunch::unpack, 0, want_elem)) return 1;
+    // 4. the views with a place in the workspace: ONE unpack launch; the windows with one: ONE window copy
+    if (svp && (launch_views(cx, stream, unpacks, ViewLaunch::unpack, 0, want_elem) || launch_windows(cx, stream, wcopies, WindowLaunch::copy, want_elem))) return 1;
     for (const SlabBlob& b : blobs) if (b.rc) return b.rc;
     return 0;
 }
@@ -3060,6 +3172,24 @@ int decode_batch_strided_device(const void* d_src, const long* offsets, const lo
     ContextLease lease;
     if (!lease.ctx) { std::fprintf(stderr, "[sqeazy]\t no usable HIP device\n"); return 1; }
     return decode_batch_on_device(*lease.ctx, d_src, a, elem_size, static_cast<hipStream_t>(hip_stream), &views, dst_shapes, rank);
+}
+
+// SQYAMD_Decode_BatchWindow_*: the arguments and every view (of the window's extent) on the host, then the batch driver with the views and
+// the windows' origins -- it admits each window against its blob's header before anything is written
+int decode_batch_window_device(const void* d_src, const long* offsets, const long* lengths, int nblobs, const long* src_origins, void* const* d_dsts,
+                               const long* dst_shapes, const long* dst_strides, unsigned rank, long* decoded, int elem_size, void* hip_stream)
+{
+    if (decoded && nblobs > 0) for (int i = 0; i < nblobs; ++i) decoded[i] = 0;
+    if (!d_src || !offsets || !lengths || !d_dsts || !dst_shapes || nblobs <= 0) { std::fprintf(stderr, "[sqeazy]\t decode batch: bad arguments\n"); return 1; }
+    std::vector<sqy::BatchView> views;
+    if (admit_views("decode batch", d_dsts, dst_shapes, dst_strides, rank, nblobs, elem_size, &views)) return 1;
+    const std::vector<long> caps((size_t)nblobs, LONG_MAX);             // (a window's bytes are its view's: nothing to fit)
+    const BatchDecodeArgs a{offsets, lengths, nblobs, d_dsts, caps.data(), decoded};
+    if (admit_decode_batch(d_src, a)) return 1;
+    ContextLease lease;
+    if (!lease.ctx) { std::fprintf(stderr, "[sqeazy]\t no usable HIP device\n"); return 1; }
+    const WindowArgs wa{src_origins, dst_strides};
+    return decode_batch_on_device(*lease.ctx, d_src, a, elem_size, static_cast<hipStream_t>(hip_stream), &views, dst_shapes, rank, &wa);
 }
 
 int decode_batch_device(const void* d_src, const BatchDecodeArgs& a, int elem_size, void* hip_stream)
@@ -3933,6 +4063,22 @@ int SQYAMD_Decode_BatchStrided_UI8_Device(const void* d_src, const long* offsets
                                           const long* dst_strides, unsigned shape_size, long* decoded_bytes, void* hip_stream)
 {
     return guarded([&]() -> int { return decode_batch_strided_device(d_src, offsets, lengths, nblobs, d_dsts, dst_shapes, dst_strides, shape_size, decoded_bytes, 1, hip_stream); });
+}
+
+int SQYAMD_Decode_BatchWindow_UI16_Device(const void* d_src, const long* offsets, const long* lengths, int nblobs, const long* src_origins, void* const* d_dsts,
+                                          const long* dst_shapes, const long* dst_strides, unsigned shape_size, long* decoded_bytes, void* hip_stream)
+{
+    return guarded([&]() -> int {
+        return decode_batch_window_device(d_src, offsets, lengths, nblobs, src_origins, d_dsts, dst_shapes, dst_strides, shape_size, decoded_bytes, 2, hip_stream);
+    });
+}
+
+int SQYAMD_Decode_BatchWindow_UI8_Device(const void* d_src, const long* offsets, const long* lengths, int nblobs, const long* src_origins, void* const* d_dsts,
+                                         const long* dst_shapes, const long* dst_strides, unsigned shape_size, long* decoded_bytes, void* hip_stream)
+{
+    return guarded([&]() -> int {
+        return decode_batch_window_device(d_src, offsets, lengths, nblobs, src_origins, d_dsts, dst_shapes, dst_strides, shape_size, decoded_bytes, 1, hip_stream);
+    });
 }
 
 int SQYAMD_Decode_Batch_UI16(const char* src, const long* offsets, const long* lengths, int nblobs, char* const* dsts, const long* dst_capacities, long* decoded_bytes)

@@ -185,6 +185,18 @@ hipError_t launch_bitswap1_batch_strided(const BatchViewJob* d_jobs, const uint3
 // launch_bitswap1_decode_batch with the voxels scattered into the view: planes + tail at `dense` (16-byte aligned)
 hipError_t launch_bitswap1_decode_batch_strided(const BatchViewJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ntiles, int elem_size,
                                                 hipStream_t stream);
+// ---- windows (SQYAMD_Decode_BatchWindow_*): job j is the box [oz, oz + Z) x [oy, oy + Y) x [ox, ox + X) of a blob of bZ x bY x bX voxels
+// (sqy::BatchWindow) and the view of Z x Y x X voxels at `view` that takes it (voxel-aligned; rows sy, frames sz voxels apart).  Nothing
+// but the view's voxels is written.
+struct BatchWindowJob { void* view; const void* dense; uint64_t Z, Y, X, sz, sy, bZ, bY, bX, oz, oy, ox, tile0; };
+// the copy out of the blob's dense volume at `dense` (any voxel-aligned address).  first_tile: the prefix sums of
+// batch_bitswap1_tiles(Z Y X), the WINDOW's voxels; tile0 is not read
+hipError_t launch_batch_window_copy(const BatchWindowJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ntiles, int elem_size, hipStream_t stream);
+// launch_bitswap1_decode_batch_strided with only the window's voxels stored: planes + tail of the whole blob at `dense` (16-byte aligned).
+// Job j's workgroups are the tiles [tile0, tile0 + count) of the BLOB's dense order that hold its frames [oz, oz + Z)
+// (sqy::window_first_tile, window_tile_count); first_tile: the prefix sums of those counts
+hipError_t launch_bitswap1_decode_batch_window(const BatchWindowJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ntiles, int elem_size,
+                                               hipStream_t stream);
 
 // One entry of the joint chunk table (sqy::Lz4BatchChunkPlan, sqy_pipeline.hpp): chunk e is the n bytes at in + off, compressed on its
 // own into scratch + slot * stride, csize[e] (0: stored); redo as for launch_lz4_chunks (nentries + 1 words, the launcher zeroes redo[0])

@@ -22,6 +22,7 @@
 #include "sqy_pipeline.hpp"
 #include "sqy_quantiser_lut.hpp"
 #include "sqy_batch_view.hpp"
+#include "sqy_batch_window.hpp"
 
 namespace sqy {
 
@@ -7926,6 +7927,198 @@ void bitswap1_decode_batch_strided_kernel(const BatchViewJob* __restrict__ jobs,
             view_scatter16<1>(out, g, w, make_uint4(d[0], d[1], d[2], d[3]), nw - gq >= 2u ? 16u : 8u);
         }
     }
+}
+
+// ---- windows (SQYAMD_Decode_BatchWindow_*) -------------------------------------------------------------------------------------------------
+// Job j is a box of a blob and the view of the box's shape that takes it (BatchWindowJob).  Only the box's voxels are stored, each to its
+// place in the view; what the view's rows and frames leave between them belongs to the caller.
+
+// batch_view_copy_kernel between two views of the window's shape: the source is the window inside the blob's dense volume (its base moved
+// to the window's first voxel, rows bX, frames bY bX voxels apart), the destination the caller's view.  Tiles and pieces are those of the
+// WINDOW's dense order; a piece has the same voxels left in its row on both sides.
+template <int ELEM>
+__global__ __launch_bounds__(256)
+void batch_window_copy_kernel(const BatchWindowJob* __restrict__ jobs, const uint32_t* __restrict__ first_tile, uint32_t njobs)
+{
+    constexpr uint32_t G = 16 / ELEM, PIECES = BSWB_TILE_VOX / G / 256u;      // voxels per piece, pieces per thread
+    const uint32_t j = batch_job_of_tile(first_tile, njobs);
+    const BatchWindowJob job = jobs[j];
+    const uint64_t len = job.Z * job.Y * job.X;
+    const uint64_t base = (uint64_t)(blockIdx.x - first_tile[j]) * BSWB_TILE_VOX;
+    const ViewGeometry gs{job.Y, job.X, job.bY * job.bX, job.bX}, gd{job.Y, job.X, job.sz, job.sy};
+    const uint8_t* src = static_cast<const uint8_t*>(job.dense) + ((job.oz * job.bY + job.oy) * job.bX + job.ox) * ELEM;
+    uint8_t* view = static_cast<uint8_t*>(job.view);
+    for (uint32_t k = 0; k < PIECES; ++k) {
+        const uint64_t i0 = base + ((uint64_t)k * 256u + threadIdx.x) * G;
+        if (i0 >= len) return;
+        const uint32_t n = (uint32_t)(len - i0 < G ? len - i0 : G);
+        ViewWalk ws = view_walk_start(gs, i0), wd = view_walk_start(gd, i0);
+        const uint8_t* ps = src + ws.off * ELEM;
+        uint8_t* pd = view + wd.off * ELEM;
+        if (n == G && wd.left >= G && ((reinterpret_cast<uintptr_t>(ps) | reinterpret_cast<uintptr_t>(pd)) & 15u) == 0) {
+            *reinterpret_cast<uint4*>(pd) = *reinterpret_cast<const uint4*>(ps);
+            continue;
+        }
+        for (uint32_t v = 0; v < n; ++v) {
+            view_voxel_store<ELEM>(view, wd.off, view_voxel_load<ELEM>(src, ws.off));
+            view_walk_advance(gs, &ws, 1);
+            view_walk_advance(gd, &wd, 1);
+        }
+    }
+}
+
+// view_scatter16 behind the clip: the piece v holds the n voxels (n <= 16 / ELEM) at offset p of the thread's run; those inside the
+// current sub-run `cur` -- and the ones behind it that the piece reaches, have: there is one -- go to the view.  Sixteen bytes where the
+// full piece lies in one sub-run (so in one row) and lands on the 16-byte grid, voxel by voxel where not.  Pieces come in ascending p.
+template <int ELEM>
+__device__ __forceinline__ void window_scatter16(uint8_t* __restrict__ view, const WindowGeometry& g, WindowClip& c, WindowPiece& cur, bool& have, uint4 v, uint32_t p,
+                                                 uint32_t n)
+{
+    constexpr uint32_t G = 16 / ELEM;
+    const uint32_t d[4] = {v.x, v.y, v.z, v.w};
+    while (have && cur.run_off < (uint64_t)p + n) {
+        const uint64_t end = cur.run_off + cur.len;                  // (> p: a sub-run that ends in front of the piece has been left)
+        const uint32_t lo = cur.run_off > p ? (uint32_t)(cur.run_off - p) : 0u, hi = end < (uint64_t)p + n ? (uint32_t)(end - p) : n;
+        const uint64_t off = cur.dst_off + ((uint64_t)p + lo - cur.run_off);          // where voxel lo of the piece goes
+        uint8_t* q = view + off * ELEM;
+        if (lo == 0 && hi == G && (reinterpret_cast<uintptr_t>(q) & 15u) == 0)
+            *reinterpret_cast<uint4*>(q) = v;
+        else {
+#pragma unroll
+            for (uint32_t k = 0; k < G; ++k)
+                if (k >= lo && k < hi) view_voxel_store<ELEM>(view, off + (k - lo), d[k * ELEM / 4] >> (8u * ((k * ELEM) & 3u)));
+        }
+        if (end > (uint64_t)p + n) break;                             // the sub-run goes on in the next piece
+        have = window_clip_next(g, &c, &cur);
+    }
+}
+
+// bitswap1_decode_batch_strided_kernel behind the clip: a thread owns 128 voxels in a row of the BLOB's dense order, clips that run
+// against the window first and is gone before it has loaded a plane word when nothing of it lies inside; the arithmetic is that
+// kernel's.  The grid holds the blob's tiles from job.tile0 on that reach into the window's frames.
+template <int ELEM>
+__global__ __launch_bounds__(256)
+void bitswap1_decode_batch_window_kernel(const BatchWindowJob* __restrict__ jobs, const uint32_t* __restrict__ first_tile, uint32_t njobs)
+{
+    constexpr uint32_t W = 8 * ELEM, WPT = BSWB_THREAD_VOX / W;        // voxels per word, words per thread
+    const uint32_t j = batch_job_of_tile(first_tile, njobs);
+    const BatchWindowJob job = jobs[j];
+    const uint32_t own = blockIdx.x - first_tile[j], tid = threadIdx.x;
+    const uint64_t tile = job.tile0 + own;
+    const uint64_t len = job.bZ * job.bY * job.bX, seg = len / W, L = seg * W;
+    const WindowGeometry g{job.bY, job.bX, job.oz, job.oy, job.ox, job.Z, job.Y, job.X, job.sz, job.sy};
+    const uint8_t* __restrict__ in = static_cast<const uint8_t*>(job.dense);
+    uint8_t* __restrict__ out = static_cast<uint8_t*>(job.view);
+    WindowPiece cur;
+    if (own == 0 && tid < len - L) {                                  // tail voxels [L, len): copied verbatim, those of the window
+        WindowClip ct = window_clip_start(g, L + tid, 1);
+        if (window_clip_next(g, &ct, &cur)) view_voxel_store<ELEM>(out, cur.dst_off, view_voxel_load<ELEM>(in, L + tid));
+    }
+    const uint64_t w0 = (tile * 256u + tid) * WPT;
+    if (w0 >= seg) return;
+    const uint32_t nw = (uint32_t)(seg - w0 < WPT ? seg - w0 : WPT);  // this thread's words
+    WindowClip c = window_clip_start(g, w0 * W, (uint64_t)nw * W);
+    bool have = window_clip_next(g, &c, &cur);
+    if (!have) return;                                                // nothing of the run inside the window: no plane word is loaded
+    const uint64_t plane_bytes = seg * ELEM;
+    const bool wide = nw == WPT && ((reinterpret_cast<uintptr_t>(in) | plane_bytes) & 15u) == 0;
+    if constexpr (ELEM == 2) {
+        uint32_t pl[16][4];                                           // pl[b] = eight words of the plane that carries bit b
+        if (wide) {
+#pragma unroll
+            for (int b = 0; b < 16; ++b) {
+                const uint4 t = *reinterpret_cast<const uint4*>(in + (uint64_t)(15 - b) * plane_bytes + w0 * 2u);
+                pl[b][0] = t.x; pl[b][1] = t.y; pl[b][2] = t.z; pl[b][3] = t.w;
+            }
+        } else {
+            const uint16_t* in16 = reinterpret_cast<const uint16_t*>(in);
+#pragma unroll
+            for (int b = 0; b < 16; ++b) { pl[b][0] = 0; pl[b][1] = 0; pl[b][2] = 0; pl[b][3] = 0; }
+#pragma unroll
+            for (uint32_t i = 0; i < WPT; ++i)
+                if (i < nw)
+#pragma unroll
+                    for (int b = 0; b < 16; ++b) pl[b][i >> 1] |= (uint32_t)in16[(uint64_t)(15 - b) * seg + w0 + i] << (16u * (i & 1u));
+        }
+#pragma unroll
+        for (uint32_t q = 0; q < 4; ++q) {                            // words w0 + 2 q (group A, low halves) and w0 + 2 q + 1 (group B)
+            if (2 * q >= nw || !have) break;
+            uint32_t r[16];
+#pragma unroll
+            for (int b = 0; b < 16; ++b) r[b] = pl[b][q];
+            transpose16x16_pairs(r);                                  // r[i] = voxel 15 - i of group A | of group B << 16
+            uint32_t ga[8], gb[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                ga[k] = __builtin_amdgcn_perm(r[14 - 2 * k], r[15 - 2 * k], 0x05040100u);
+                gb[k] = __builtin_amdgcn_perm(r[14 - 2 * k], r[15 - 2 * k], 0x07060302u);
+            }
+            window_scatter16<2>(out, g, c, cur, have, make_uint4(ga[0], ga[1], ga[2], ga[3]), 32u * q, 8);
+            window_scatter16<2>(out, g, c, cur, have, make_uint4(ga[4], ga[5], ga[6], ga[7]), 32u * q + 8u, 8);
+            if (2 * q + 1 >= nw) break;
+            window_scatter16<2>(out, g, c, cur, have, make_uint4(gb[0], gb[1], gb[2], gb[3]), 32u * q + 16u, 8);
+            window_scatter16<2>(out, g, c, cur, have, make_uint4(gb[4], gb[5], gb[6], gb[7]), 32u * q + 24u, 8);
+        }
+    } else {
+        uint32_t pw[8][4];                                            // pw[b] = 16 bytes of the plane that carries bit b
+        if (wide) {
+#pragma unroll
+            for (int b = 0; b < 8; ++b) {
+                const uint4 t = *reinterpret_cast<const uint4*>(in + (uint64_t)(7 - b) * plane_bytes + w0);
+                pw[b][0] = t.x; pw[b][1] = t.y; pw[b][2] = t.z; pw[b][3] = t.w;
+            }
+        } else {
+#pragma unroll
+            for (int b = 0; b < 8; ++b) { pw[b][0] = 0; pw[b][1] = 0; pw[b][2] = 0; pw[b][3] = 0; }
+#pragma unroll
+            for (uint32_t i = 0; i < WPT; ++i)
+                if (i < nw)
+#pragma unroll
+                    for (int b = 0; b < 8; ++b) pw[b][i >> 2] |= (uint32_t)in[(uint64_t)(7 - b) * seg + w0 + i] << (8u * (i & 3u));
+        }
+#pragma unroll
+        for (uint32_t gq = 0; gq < 16; gq += 2) {
+            if (gq >= nw || !have) break;
+            uint32_t d[4];
+#pragma unroll
+            for (uint32_t u = 0; u < 2; ++u) {
+                // (bitswap1_decode_batch_strided_kernel's gather and transpose: afterwards byte i of hi:lo = voxel 7 - i)
+                constexpr uint32_t Zs = 0x0c;                         // v_perm selector: a zero byte
+                const uint32_t cc = (gq + u) & 3u, wdx = (gq + u) >> 2;
+                const uint32_t s01 = cc | ((4u + cc) << 8) | (Zs << 16) | (Zs << 24), s23 = Zs | (Zs << 8) | (cc << 16) | ((4u + cc) << 24);
+                uint32_t lo_ = __builtin_amdgcn_perm(pw[1][wdx], pw[0][wdx], s01) | __builtin_amdgcn_perm(pw[3][wdx], pw[2][wdx], s23);
+                uint32_t hi_ = __builtin_amdgcn_perm(pw[5][wdx], pw[4][wdx], s01) | __builtin_amdgcn_perm(pw[7][wdx], pw[6][wdx], s23);
+                uint32_t y;
+                y = (lo_ ^ (lo_ >> 7)) & 0x00AA00AAu; lo_ ^= y ^ (y << 7);
+                y = (hi_ ^ (hi_ >> 7)) & 0x00AA00AAu; hi_ ^= y ^ (y << 7);
+                y = (lo_ ^ (lo_ >> 14)) & 0x0000CCCCu; lo_ ^= y ^ (y << 14);
+                y = (hi_ ^ (hi_ >> 14)) & 0x0000CCCCu; hi_ ^= y ^ (y << 14);
+                y = (lo_ ^ (hi_ << 4)) & 0xF0F0F0F0u; lo_ ^= y; hi_ ^= y >> 4;
+                d[2 * u] = __builtin_bswap32(hi_);                    // voxels 0..3 of the word
+                d[2 * u + 1] = __builtin_bswap32(lo_);                // voxels 4..7
+            }
+            window_scatter16<1>(out, g, c, cur, have, make_uint4(d[0], d[1], d[2], d[3]), 8u * gq, nw - gq >= 2u ? 16u : 8u);
+        }
+    }
+}
+
+hipError_t launch_batch_window_copy(const BatchWindowJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ntiles, int elem_size, hipStream_t stream)
+{
+    if (njobs == 0 || ntiles == 0) return hipSuccess;
+    if (elem_size == 2) hipLaunchKernelGGL(batch_window_copy_kernel<2>, dim3(ntiles), dim3(256), 0, stream, d_jobs, d_first_tile, njobs);
+    else if (elem_size == 1) hipLaunchKernelGGL(batch_window_copy_kernel<1>, dim3(ntiles), dim3(256), 0, stream, d_jobs, d_first_tile, njobs);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+hipError_t launch_bitswap1_decode_batch_window(const BatchWindowJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ntiles, int elem_size,
+                                               hipStream_t stream)
+{
+    if (njobs == 0 || ntiles == 0) return hipSuccess;
+    if (elem_size == 2) hipLaunchKernelGGL(bitswap1_decode_batch_window_kernel<2>, dim3(ntiles), dim3(256), 0, stream, d_jobs, d_first_tile, njobs);
+    else if (elem_size == 1) hipLaunchKernelGGL(bitswap1_decode_batch_window_kernel<1>, dim3(ntiles), dim3(256), 0, stream, d_jobs, d_first_tile, njobs);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
 }
 
 hipError_t launch_batch_view_copy(const BatchViewJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ntiles, int elem_size, bool to_view,

@@ -347,6 +347,33 @@ bool admit_view(const long* shape, const long* strides, unsigned rank, BatchView
     return true;
 }
 
+bool admit_window(const std::vector<uint64_t>& header_shape, const long* origin, const long* extent, unsigned rank, BatchWindow* out)
+{
+    if (!extent || !out || rank == 0 || rank > 3 || header_shape.size() != rank) return false;
+    uint64_t b[3] = {1, 1, 1}, o[3] = {0, 0, 0}, e[3] = {1, 1, 1};
+    bool whole = true;
+    for (unsigned k = 0; k < rank; ++k) {
+        const long og = origin ? origin[k] : 0;
+        if (og < 0 || extent[k] < 1) return false;
+        // (both below 2^63: their sum cannot wrap in 64 unsigned bits)
+        if ((uint64_t)og + (uint64_t)extent[k] > header_shape[k]) return false;
+        b[3 - rank + k] = header_shape[k];
+        o[3 - rank + k] = (uint64_t)og;
+        e[3 - rank + k] = (uint64_t)extent[k];
+        whole = whole && og == 0 && (uint64_t)extent[k] == header_shape[k];
+    }
+    *out = BatchWindow{b[0], b[1], b[2], o[0], o[1], o[2], e[0], e[1], e[2], whole};
+    return true;
+}
+
+BatchWindowLayout batch_window_layout(uint64_t njobs)
+{
+    BatchWindowLayout l;
+    l.tiles_at = round_up(njobs * kBatchWindowJobBytes, 16);
+    l.total = l.tiles_at + (njobs + 1) * 4;
+    return l;
+}
+
 Lz4BatchPlan lz4_batch_plan_views(const Lz4Params& p, const std::vector<uint64_t>& totals, const std::vector<uint64_t>& pack_bytes, unsigned nthreads,
                                   uint64_t group_bytes, uint64_t joint_max, uint64_t extra_bytes_all)
 {

@@ -138,6 +138,20 @@ Lz4BatchPlan lz4_batch_plan_views(const Lz4Params& p, const std::vector<uint64_t
 // a view job of the pack, unpack and strided transposer launches (sqy::BatchViewJob, sqy_kernels.h)
 constexpr uint64_t kBatchViewJobBytes = 56;
 
+// ---- windows (SQYAMD_Decode_BatchWindow_*): a box of a blob decoded into a view of the box's shape ----
+// The blob's shape bZ x bY x bX, the window's first voxel (oz, oy, ox) in it and its extent Z x Y x X, all padded to three dimensions with
+// leading 1s (origins: 0s).  whole: the window is the blob
+struct BatchWindow { uint64_t bZ, bY, bX, oz, oy, ox, Z, Y, X; bool whole; };
+// A caller's window of `rank` dimensions (outermost first) inside a blob whose header gives header_shape; origin nullptr: all zeros.
+// false: rank 0 or above 3, a header of another rank, an origin below 0, an extent below 1, or origin + extent past the header's shape
+// (a sum that overflows `long` is past it)
+bool admit_window(const std::vector<uint64_t>& header_shape, const long* origin, const long* extent, unsigned rank, BatchWindow* out);
+// a window job of the window copy and the windowed transposer (sqy::BatchWindowJob, sqy_kernels.h)
+constexpr uint64_t kBatchWindowJobBytes = 112;
+// The tables of one window launch, one upload: njobs jobs at 0 | tiles_at (16-byte aligned): njobs + 1 words of prefix sums | total
+struct BatchWindowLayout { uint64_t tiles_at = 0, total = 0; };
+BatchWindowLayout batch_window_layout(uint64_t njobs);
+
 // ---- batch decode (SQYAMD_Decode_Batch_*): many blobs, one launch per kernel ----
 // What the planner knows of blob i: the bytes its LZ4 stage decodes to, the LZ4 block size, whether it may take the joint path at all
 // (the last stage lz4, chunk <= block_bytes), and what follows the LZ4 decode --
