@@ -205,6 +205,40 @@ SQY_FUNCTION_PREFIX int SQYAMD_PipelineEncode_BatchStrided_UI16_Device(const cha
 SQY_FUNCTION_PREFIX int SQYAMD_PipelineEncode_BatchStrided_UI8_Device(const char* pipeline, const void* const* d_srcs, const long* shapes,
                                                                       const long* strides, unsigned shape_size, int nvolumes, void* d_dst,
                                                                       long slot_capacity, long* offsets, long* lengths, int nthreads, void* hip_stream);
+/* _BatchStrided_*_Device into ONE packed buffer: the blobs back to back in d_dst with an index of (offset, length) -- a shard of a chunked
+ * store, a container file, one device-to-host copy of exactly the compressed bytes -- instead of a slot of max_compressed_length each.
+ * d_srcs, shapes, strides (NULL: dense volumes), pipeline, nthreads, stream, context, ordering and thread safety are
+ * _BatchStrided_*_Device's, and so is the admission: on the host, before the device is touched.  Blob i is byte for byte what
+ * SQYAMD_PipelineEncode_*_Device gives for a dense copy of volume i.
+ * Placement: the blobs lie in volume order, offsets[0] = 0, offsets[i+1] = round_up(offsets[i] + lengths[i], align), *total =
+ * offsets[n-1] + lengths[n-1]; all of it in 64 unsigned bits.  align is a power of two, 1 <= align <= 65536 (anything else: 1 before
+ * anything is written).  Offsets are relative to d_dst, which needs no alignment.  The call writes the blobs' bytes and nothing else: no
+ * byte in front of d_dst, none at or behind d_dst + dst_capacity, no gap byte between two blobs.
+ * Capacity: when the packed blobs do not fit dst_capacity the call returns 1 with offsets and lengths zeroed and *total = the capacity
+ * a retry needs -- every volume is still compressed, so the figure is exact.  Blobs that lie wholly inside the capacity may have been
+ * written, nothing else is.  Every other failure -- bad arguments (those of _BatchStrided_*_Device, total == NULL, dst_capacity <= 0, a
+ * bad align), a refused geometry, a payload that overflows the reference's int -- returns 1 with offsets, lengths and *total zeroed.  A
+ * caller who wants no retry passes the sum of round_up(SQY_Pipeline_Max_Compressed_Length_3D of volume i, align).
+ * The joint-eligible volumes (see _Batch_*_Device) take the group's launches plus one placement scan (one workgroup) between the frame
+ * scan and the gather, which then writes every blob at its place; the number of host round trips is unchanged.  Every other volume is
+ * encoded first, into a workspace slot of its max_compressed_length, and copied to its place at the end: volume order holds in a mixed
+ * call too.  The way back is SQYAMD_Decode_Batch*_Device with the same offsets and lengths. */
+SQY_FUNCTION_PREFIX int SQYAMD_PipelineEncode_BatchPacked_UI16_Device(const char* pipeline, const void* const* d_srcs, const long* shapes,
+                                                                      const long* strides, unsigned shape_size, int nvolumes, void* d_dst,
+                                                                      long dst_capacity, long align, long* offsets, long* lengths, long* total,
+                                                                      int nthreads, void* hip_stream);
+SQY_FUNCTION_PREFIX int SQYAMD_PipelineEncode_BatchPacked_UI8_Device(const char* pipeline, const void* const* d_srcs, const long* shapes,
+                                                                     const long* strides, unsigned shape_size, int nvolumes, void* d_dst,
+                                                                     long dst_capacity, long align, long* offsets, long* lengths, long* total,
+                                                                     int nthreads, void* hip_stream);
+/* host-pointer variants (not tuned): every volume staged up, the device driver called once, ONE copy of *total bytes brought back to dst
+ * -- the blobs and, for align > 1, the gap bytes between them, which are zeros.  Capacity and errors as above. */
+SQY_FUNCTION_PREFIX int SQYAMD_PipelineEncode_BatchPacked_UI16(const char* pipeline, const char* const* srcs, const long* shapes, unsigned shape_size,
+                                                               int nvolumes, char* dst, long dst_capacity, long align, long* offsets, long* lengths,
+                                                               long* total, int nthreads);
+SQY_FUNCTION_PREFIX int SQYAMD_PipelineEncode_BatchPacked_UI8(const char* pipeline, const char* const* srcs, const long* shapes, unsigned shape_size,
+                                                              int nvolumes, char* dst, long dst_capacity, long align, long* offsets, long* lengths,
+                                                              long* total, int nthreads);
 /* host-pointer variants: srcs[i] are host pointers, dst is host memory laid out the same way (only the blobs' bytes are written).  Every
  * volume is staged up, the device driver called once and the blobs brought back; the staging does not overlap with the encode */
 SQY_FUNCTION_PREFIX int SQYAMD_PipelineEncode_Batch_UI16(const char* pipeline, const char* const* srcs, const long* shapes, unsigned shape_size,

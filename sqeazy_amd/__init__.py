@@ -29,6 +29,8 @@ EXPORTED_SYMBOLS = (
     "SQYAMD_PipelineEncode_Slabs_UI16_Device", "SQYAMD_PipelineEncode_Slabs_UI8_Device",
     "SQYAMD_PipelineEncode_Batch_UI16_Device", "SQYAMD_PipelineEncode_Batch_UI8_Device", "SQYAMD_PipelineEncode_Batch_UI16", "SQYAMD_PipelineEncode_Batch_UI8",
     "SQYAMD_PipelineEncode_BatchStrided_UI16_Device", "SQYAMD_PipelineEncode_BatchStrided_UI8_Device",
+    "SQYAMD_PipelineEncode_BatchPacked_UI16_Device", "SQYAMD_PipelineEncode_BatchPacked_UI8_Device",
+    "SQYAMD_PipelineEncode_BatchPacked_UI16", "SQYAMD_PipelineEncode_BatchPacked_UI8",
     "SQYAMD_Decode_BatchStrided_UI16_Device", "SQYAMD_Decode_BatchStrided_UI8_Device",
     "SQYAMD_Decode_BatchWindow_UI16_Device", "SQYAMD_Decode_BatchWindow_UI8_Device",
     "SQYAMD_PipelineEncode_UI16_Cap", "SQYAMD_PipelineEncode_UI8_Cap",
@@ -89,6 +91,12 @@ def lib():
         for f in ("SQYAMD_PipelineEncode_BatchStrided_UI8_Device", "SQYAMD_PipelineEncode_BatchStrided_UI16_Device"):
             getattr(L, f).argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_void_p), c_long_p, c_long_p, ctypes.c_uint, ctypes.c_int, ctypes.c_void_p,
                                       ctypes.c_long, c_long_p, c_long_p, ctypes.c_int, ctypes.c_void_p]
+        for f in ("SQYAMD_PipelineEncode_BatchPacked_UI8_Device", "SQYAMD_PipelineEncode_BatchPacked_UI16_Device"):
+            getattr(L, f).argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_void_p), c_long_p, c_long_p, ctypes.c_uint, ctypes.c_int, ctypes.c_void_p,
+                                      ctypes.c_long, ctypes.c_long, c_long_p, c_long_p, c_long_p, ctypes.c_int, ctypes.c_void_p]
+        for f in ("SQYAMD_PipelineEncode_BatchPacked_UI8", "SQYAMD_PipelineEncode_BatchPacked_UI16"):
+            getattr(L, f).argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_void_p), c_long_p, ctypes.c_uint, ctypes.c_int, ctypes.c_void_p, ctypes.c_long,
+                                      ctypes.c_long, c_long_p, c_long_p, c_long_p, ctypes.c_int]
         for f in ("SQYAMD_Decode_BatchStrided_UI8_Device", "SQYAMD_Decode_BatchStrided_UI16_Device"):
             getattr(L, f).argtypes = [ctypes.c_void_p, c_long_p, c_long_p, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), c_long_p, c_long_p, ctypes.c_uint,
                                       c_long_p, ctypes.c_void_p]
@@ -271,6 +279,25 @@ def encode_batch_strided_device(pipeline, d_srcs, shapes, strides, dtype, d_dst,
     return rc, list(offs[:n]), list(lens[:n])
 
 
+def encode_batch_packed_device(pipeline, d_srcs, shapes, strides, dtype, d_dst, dst_capacity, align=1, nthreads=0, stream=None):
+    """SQYAMD_PipelineEncode_BatchPacked_*_Device: encode_batch_strided_device (strides None: dense volumes) with the blobs back to back in
+    the dst_capacity bytes at d_dst -- offsets[0] = 0, offsets[i + 1] = offsets[i] + lengths[i] rounded up to align (a power of two up to
+    65536), total = offsets[-1] + lengths[-1].  Returns (rc, offsets, lengths, total); rc 1 with zeroed tables and total > 0: the blobs do
+    not fit, total is the capacity a retry needs."""
+    n = len(d_srcs)
+    rank = len(shapes[0]) if n else 0
+    ptrs = (ctypes.c_void_p * max(n, 1))(*[int(p) for p in d_srcs])
+    flat = _longs([x for s in shapes for x in s]) if n else None
+    flat_strides = _longs([x for s in strides for x in s]) if n and strides is not None else None
+    offs = (ctypes.c_long * max(n, 1))()
+    lens = (ctypes.c_long * max(n, 1))()
+    total = ctypes.c_long(0)
+    rc = getattr(lib(), "SQYAMD_PipelineEncode_BatchPacked_%s_Device" % _suffix(dtype))(
+        pipeline.encode(), ptrs, flat, flat_strides, ctypes.c_uint(rank), ctypes.c_int(n), ctypes.c_void_p(int(d_dst)), ctypes.c_long(int(dst_capacity)),
+        ctypes.c_long(int(align)), offs, lens, ctypes.byref(total), ctypes.c_int(nthreads), ctypes.c_void_p(stream or 0))
+    return rc, list(offs[:n]), list(lens[:n]), total.value
+
+
 def tile_views(base_ptr, shape, tile, itemsize):
     """The regular grid of tiles of a dense volume of `shape` at device pointer base_ptr (itemsize bytes a voxel), as views for
     encode_batch_strided_device / decode_batch_strided_device: returns (ptrs, shapes, strides), tiles in row-major grid order, the tiles
@@ -312,6 +339,33 @@ def encode_batch(pipeline, volumes, nthreads=0):
     if rc:
         raise ValueError("SQYAMD_PipelineEncode_Batch returned %d for %r" % (rc, pipeline))
     return [dst[offs[i]:offs[i] + lens[i]].tobytes() for i in range(n)]
+
+
+def encode_batch_packed(pipeline, volumes, align=1, nthreads=0):
+    """SQYAMD_PipelineEncode_BatchPacked_UI8/UI16 on host ndarrays of one dtype and rank (shapes may differ); returns (buffer, offsets, lengths):
+    the blobs back to back in `buffer` (bytes, exactly the call's total; for align > 1 zeros between the blobs), blob i =
+    buffer[offsets[i]:offsets[i] + lengths[i]].  Raises ValueError when the call returns non-zero."""
+    vols = [np.ascontiguousarray(v) for v in volumes]
+    if not vols:
+        raise ValueError("encode_batch_packed: no volumes")
+    dtype, rank = vols[0].dtype, vols[0].ndim
+    if any(v.dtype != dtype or v.ndim != rank for v in vols):
+        raise TypeError("encode_batch_packed takes volumes of one dtype and rank")
+    n, align = len(vols), int(align)
+    # (the capacity that needs no retry; a bad align is the call's to refuse)
+    step = align if align >= 1 else 1
+    cap = sum(-(-max(max_compressed_length(pipeline, v.shape, dtype), 64) // step) * step for v in vols) if pipeline_possible(pipeline, dtype) else 64
+    dst = np.empty(cap, dtype=np.uint8)
+    ptrs = (ctypes.c_void_p * n)(*[v.ctypes.data for v in vols])
+    offs = (ctypes.c_long * n)()
+    lens = (ctypes.c_long * n)()
+    total = ctypes.c_long(0)
+    rc = getattr(lib(), "SQYAMD_PipelineEncode_BatchPacked_" + _suffix(dtype))(
+        pipeline.encode(), ptrs, _longs([x for v in vols for x in v.shape]), ctypes.c_uint(rank), ctypes.c_int(n), dst.ctypes.data, ctypes.c_long(cap),
+        ctypes.c_long(align), offs, lens, ctypes.byref(total), ctypes.c_int(nthreads))
+    if rc:
+        raise ValueError("SQYAMD_PipelineEncode_BatchPacked returned %d for %r" % (rc, pipeline))
+    return dst[:total.value].tobytes(), list(offs), list(lens)
 
 
 def header_size(blob):

@@ -337,6 +337,8 @@ struct Workspace {
     DevBuf batch_pack_one;    // .. decode: the dense place of a view whose blob is decoded on its own
     DevBuf batch_views[3];    // .. the job and tile tables of the view launches: pack / unpack, the strided transposer, the strided copy
     DevBuf batch_windows[3];  // .. and of the window launches: the window copy, the windowed transposer, the copy out of the LZ4 output
+    DevBuf batch_places;      // packed batch encode: the places a group's placement scan leaves for the gather, behind them its gap table
+    DevBuf batch_packed;      // .. a slot of max_compressed_length for every volume outside the joint forms, copied to its place at the end
     void* pinned = nullptr;   // 4 KiB of pinned host memory for small read-backs
     void release_buffers()
     {
@@ -345,6 +347,7 @@ struct Workspace {
         subset.release(); range_full.release(); slabs_index.release(); slabs_joint.release(); slabs_out.release(); slabs_host.release();
         batch_stream.release(); batch_scratch.release(); batch_tables.release(); batch_quant.release(); batch_host.release();
         batch_pack.release(); batch_pack_one.release(); for (DevBuf& b : batch_views) b.release(); for (DevBuf& b : batch_windows) b.release();
+        batch_places.release(); batch_packed.release();
     }
 };
 
@@ -3290,9 +3293,14 @@ int admit_batch(const char* pipeline, const void* const* srcs, const long* shape
 // staging: pinned, sqy::encode_batch_layout's staging_bytes for the group at its worst-case text
 // views (nullptr: every volume dense) with how[vol], sqy ViewRead: how a volume that is no dense allocation is read
 enum ViewRead : uint8_t { in_place = 0, gathered, packed_to_stream, packed };
+// the packed layout (SQYAMD_PipelineEncode_BatchPacked_*) for one group: it begins at `base` of d_dst (a multiple of align), gaps[j]
+// (pinned, a word per volume of the group) is what the volumes outside the group take in front of its volume j, no blob may end behind
+// `capacity`.  The group leaves every volume's blob length in lens[vol] and whether it was written in placed[vol]; offsets and lengths
+// are the caller's to fill.  nullptr: the slot layout
+struct PackedGroup { uint64_t align, base, capacity; const uint64_t* gaps; uint64_t* lens; uint8_t* placed; };
 int encode_batch_group(Context& cx, const BatchAdmit& a, const sqy::Lz4BatchGroup& g, sqy::EncodeBatchForm form, int elem_size, const void* const* d_srcs,
                        uint8_t* d_dst, uint64_t slot_capacity, long* offsets, long* lengths, uint64_t* records, uint8_t* staging, hipStream_t stream,
-                       const std::vector<sqy::BatchView>* views = nullptr, const std::vector<uint8_t>* how = nullptr)
+                       const std::vector<sqy::BatchView>* views = nullptr, const std::vector<uint8_t>* how = nullptr, const PackedGroup* pk = nullptr)
 {
     Workspace* ws = &cx.ws;
     std::vector<PendingEvent>* pend = &cx.pending;
@@ -3320,6 +3328,9 @@ int encode_batch_group(Context& cx, const BatchAdmit& a, const sqy::Lz4BatchGrou
     // trip 1 when the text is known only then --, and behind it what the kernels hand each other
     const sqy::EncodeBatchLayout L = sqy::encode_batch_layout(nc, nv, quantised, quantised ? nv * sqy::kBatchHeaderTextMax : text_bytes);
     if (ws->batch_tables.ensure(L.tables) || ws->batch_scratch.ensure(std::max<uint64_t>(nc * g.scratch_stride, 16))) return 1;
+    if (pk && ws->batch_places.ensure(2 * nv * sizeof(uint64_t))) return 1;
+    uint64_t* const d_place = pk ? static_cast<uint64_t*>(ws->batch_places.p) : nullptr;
+    uint64_t* const d_gap = pk && std::any_of(pk->gaps, pk->gaps + nv, [](uint64_t x) { return x != 0; }) ? d_place + nv : nullptr;   // (no gap: no upload)
     // the views of the group that are no dense allocations: the packed copies' places in Workspace::batch_pack (16-byte aligned)
     auto read_of = [&](uint32_t vol) { return how ? (ViewRead)(*how)[vol] : in_place; };
     std::vector<uint64_t> place(nv, 0);
@@ -3352,7 +3363,8 @@ int encode_batch_group(Context& cx, const BatchAdmit& a, const sqy::Lz4BatchGrou
             const uint32_t prefix_len = (uint32_t)cut, suffix_len = (uint32_t)(text[j].size() - cut - 1);
             std::memcpy(h_text + text_used, text[j].data(), prefix_len);
             std::memcpy(h_text + text_used + prefix_len, text[j].data() + cut + 1, suffix_len);
-            h_vols[j] = sqy::Lz4BatchVolume{(uint64_t)vol * slot_capacity, slot_capacity, g.first_chunk[j], g.first_chunk[j + 1] - g.first_chunk[j],
+            // (packed: the place comes from the placement scan, which also holds the blob against the capacity)
+            h_vols[j] = sqy::Lz4BatchVolume{pk ? 0 : (uint64_t)vol * slot_capacity, pk ? ~(uint64_t)0 : slot_capacity, g.first_chunk[j], g.first_chunk[j + 1] - g.first_chunk[j],
                                             (uint32_t)text_used, prefix_len, suffix_len, (uint32_t)elem_size, vol, 0};
             text_used += prefix_len + suffix_len;
         }
@@ -3388,6 +3400,7 @@ int encode_batch_group(Context& cx, const BatchAdmit& a, const sqy::Lz4BatchGrou
     }
     h_tiles[njobs] = ntiles;
     SQY_HIP(hipMemcpyAsync(d_tab, staging, quantised ? L.vols_at : L.upload, hipMemcpyHostToDevice, stream));
+    if (d_gap) SQY_HIP(hipMemcpyAsync(d_gap, pk->gaps, nv * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
 
     const sqy::Lz4BatchChunk* d_table = reinterpret_cast<const sqy::Lz4BatchChunk*>(d_tab + L.table_at);
     const sqy::Lz4BatchVolume* d_vols = reinterpret_cast<const sqy::Lz4BatchVolume*>(d_tab + L.vols_at);
@@ -3431,16 +3444,23 @@ int encode_batch_group(Context& cx, const BatchAdmit& a, const sqy::Lz4BatchGrou
     if (n_redo)
         SQY_TIMED("batch_lz4_chunks_dense", sqy::launch_lz4_chunks_table_dense(d_stream, d_table, d_scratch, g.scratch_stride, d_csize, d_redo, n_redo, stream));
     SQY_TIMED("batch_lz4_frame_scan", sqy::launch_lz4_batch_scan(d_table, d_vols, (uint32_t)nv, d_csize, d_foff, d_vinfo, stream));
+    if (pk) SQY_TIMED("batch_lz4_place", sqy::launch_lz4_batch_place(d_vinfo, d_gap, (uint32_t)nv, pk->align, pk->base, pk->capacity, d_place, stream));
     const Lz4Descriptor fd = lz4_descriptor(a.pipe.stages.back().lz4.block_id);
     SQY_TIMED("batch_lz4_frame_gather", sqy::launch_lz4_batch_gather(d_stream, d_table, (uint32_t)nc, g.max_chunk, d_vols,
                                                                      reinterpret_cast<const uint32_t*>(d_tab + L.volof_at), d_scratch, g.scratch_stride, d_csize,
-                                                                     d_foff, d_vinfo, reinterpret_cast<const char*>(d_tab + L.text_at), d_dst, fd.bd, fd.hc, records, stream));
+                                                                     d_foff, d_vinfo, reinterpret_cast<const char*>(d_tab + L.text_at), d_dst, fd.bd, fd.hc, records, stream,
+                                                                     d_place));
     // round trip 2: the records
     SQY_HIP(hipStreamSynchronize(stream));
     int rc = 0;
     for (size_t j = 0; j < nv; ++j) {
         const uint32_t vol = g.vols[j];
         const volatile uint64_t* r = records + 3 * (uint64_t)vol;
+        if (pk && (r[0] == sqy::kBatchDone || r[0] == sqy::kBatchNoRoom)) {     // (no room: the call goes on, for the capacity a retry needs)
+            pk->lens[vol] = r[1];
+            pk->placed[vol] = r[0] == sqy::kBatchDone;
+            continue;
+        }
         if (r[0] == sqy::kBatchDone) { offsets[vol] = (long)((uint64_t)vol * slot_capacity); lengths[vol] = (long)r[1]; continue; }
         if (r[0] == sqy::kBatchNoRoom)
             std::fprintf(stderr, "[sqeazy]\t volume %u: destination slot too small (%llu payload bytes and the header > %llu bytes)\n", vol,
@@ -3454,9 +3474,12 @@ int encode_batch_group(Context& cx, const BatchAdmit& a, const sqy::Lz4BatchGrou
     return rc;
 }
 
+// dense_to (SQYAMD_PipelineEncode_BatchPacked_*; nullptr: the slot layout): the blobs back to back in d_dst by sqy::packed_places' rule --
+// slot_capacity is then the capacity of all of d_dst, and *total what the blobs take (or, rc 1 and the blobs do not fit, what they would take)
+struct PackedArgs { uint64_t align; long* total; };
 int encode_batch_on_device(Context& cx, const char* pipeline, const BatchAdmit& a, const void* const* d_srcs, const long* shapes, unsigned rank, int elem_size,
                            int nvolumes, void* d_dst, uint64_t slot_capacity, long* offsets, long* lengths, int nthreads, hipStream_t stream,
-                           const std::vector<sqy::BatchView>* views = nullptr)
+                           const std::vector<sqy::BatchView>* views = nullptr, const PackedArgs* dense_to = nullptr)
 {
     for (int i = 0; i < nvolumes; ++i)
         if (reinterpret_cast<uintptr_t>(d_srcs[i]) % (uintptr_t)elem_size) { std::fprintf(stderr, "[sqeazy]\t volume %d: source not aligned to the voxel size\n", i); return 1; }
@@ -3484,43 +3507,119 @@ int encode_batch_on_device(Context& cx, const char* pipeline, const BatchAdmit& 
                                          (uint64_t)g_opt.encode_batch_group_bytes.load(), (uint64_t)g_opt.encode_batch_joint_max_bytes.load(),
                                          sqy::encode_batch_extra_bytes(form));
     }
+    const size_t n = (size_t)nvolumes;
     int rc = 0;
-    if (!plan.groups.empty()) {
+    // the packed layout's state: every blob's length, whether a group wrote it, and for a volume outside the joint forms where its blob
+    // waits in Workspace::batch_packed
+    std::vector<uint64_t> lens, waits_at;
+    std::vector<uint8_t> placed;
+    uint64_t* gaps = nullptr;                                           // (pinned, behind the staging area: the group at hand's)
+    // the groups, in order; the packed layout hands each where it begins and what lies between its members
+    auto run_groups = [&]() -> int {
+        if (plan.groups.empty()) return 0;
         DrainOnExit drain{stream, &cx.pending};
         // pinned: a record per volume of the batch (3 words), behind them the staging area of the group that needs the largest one
         const bool quantised = form == sqy::EncodeBatchForm::quantiser_bitswap1_lz4;
-        uint64_t staging = 0;
-        for (const sqy::Lz4BatchGroup& g : plan.groups)
+        uint64_t staging = 0, most_vols = 0;
+        for (const sqy::Lz4BatchGroup& g : plan.groups) {
             staging = std::max(staging, sqy::encode_batch_layout(g.chunks.size(), g.vols.size(), quantised, g.vols.size() * sqy::kBatchHeaderTextMax).staging_bytes);
+            most_vols = std::max<uint64_t>(most_vols, g.vols.size());
+        }
+        staging = (staging + 15) & ~(uint64_t)15;
         const uint64_t records_bytes = ((uint64_t)nvolumes * 24 + 63) & ~(uint64_t)63;
-        if (cx.ws.batch_host.ensure(records_bytes + staging)) return 1;
+        if (cx.ws.batch_host.ensure(records_bytes + staging + (dense_to ? most_vols * sizeof(uint64_t) : 0))) return 1;
         uint64_t* records = static_cast<uint64_t*>(cx.ws.batch_host.p);
         std::memset(records, 0, records_bytes);
-        for (const sqy::Lz4BatchGroup& g : plan.groups)
+        gaps = reinterpret_cast<uint64_t*>(static_cast<uint8_t*>(cx.ws.batch_host.p) + records_bytes + staging);
+        int grc = 0;
+        for (const sqy::Lz4BatchGroup& g : plan.groups) {
+            PackedGroup pk{};
+            if (dense_to) {
+                // every volume in front of the group is known by now: the others, and the groups before it (the plan deals volumes in order)
+                const uint32_t v0 = g.vols[0];
+                const sqy::PackedPlaces before = sqy::packed_places(std::vector<uint64_t>(lens.begin(), lens.begin() + v0), std::vector<uint64_t>(), dense_to->align, 0, slot_capacity);
+                if (!before.ok) return 1;
+                pk = PackedGroup{dense_to->align, v0 ? align_up(before.end, dense_to->align) : 0, slot_capacity, gaps, lens.data(), placed.data()};
+                for (size_t j = 0; j < g.vols.size(); ++j) {
+                    gaps[j] = 0;
+                    for (uint32_t k = j ? g.vols[j - 1] + 1 : v0; k < g.vols[j]; ++k) gaps[j] += align_up(lens[k], dense_to->align);
+                }
+            }
             if (encode_batch_group(cx, a, g, form, elem_size, d_srcs, static_cast<uint8_t*>(d_dst), slot_capacity, offsets, lengths, records,
-                                   static_cast<uint8_t*>(cx.ws.batch_host.p) + records_bytes, stream, strided ? views : nullptr, strided ? &how : nullptr))
-                rc = 1;
+                                   static_cast<uint8_t*>(cx.ws.batch_host.p) + records_bytes, stream, strided ? views : nullptr, strided ? &how : nullptr,
+                                   dense_to ? &pk : nullptr)) {
+                grc = 1;
+                if (dense_to) break;                                      // (the groups behind it would not know where they begin)
+            }
+        }
         if (g_prof_on.load()) prof_collect(cx.pending);
-    }
-    // every other volume: the single-call path into its slot, in volume order (the blob where the call leaves it inside the slot)
-    for (int i = 0; i < nvolumes && rc == 0; ++i) {
-        if (plan.group_of[(size_t)i] >= 0) continue;
-        long at = 0, len = 0;
+        return grc;
+    };
+    // every other volume: the single-call path into `cap` bytes at dst (the blob where the call leaves it: *at, *len)
+    auto run_single = [&](int i, uint8_t* dst, uint64_t cap, long* at, long* len) -> int {
         const void* src = d_srcs[i];
         if (how[(size_t)i] != in_place) {                               // a view outside the joint forms: from its packed copy
-            if (cx.ws.batch_pack.ensure(a.len[(size_t)i] * (uint64_t)elem_size)) { rc = 1; break; }
+            if (cx.ws.batch_pack.ensure(a.len[(size_t)i] * (uint64_t)elem_size)) return 1;
             src = cx.ws.batch_pack.p;
             ViewLaunch one;
             one.add(d_srcs[i], src, (*views)[(size_t)i]);
             DrainOnExit drain{stream, &cx.pending};                     // (the launch's tables are this scope's)
-            if (launch_views(cx, stream, one, ViewLaunch::pack, 0, elem_size)) { rc = 1; break; }
+            if (launch_views(cx, stream, one, ViewLaunch::pack, 0, elem_size)) return 1;
         }
-        rc = encode_on_device(cx, pipeline, src, shapes + (size_t)i * rank, rank, elem_size, static_cast<uint8_t*>(d_dst) + (uint64_t)i * slot_capacity,
-                              slot_capacity, &len, nthreads, stream, &at);
-        if (rc == 0) { offsets[i] = (long)((uint64_t)i * slot_capacity) + at; lengths[i] = len; }
+        return encode_on_device(cx, pipeline, src, shapes + (size_t)i * rank, rank, elem_size, dst, cap, len, nthreads, stream, at);
+    };
+    if (!dense_to) {
+        rc = run_groups();
+        // .. into its slot, in volume order
+        for (int i = 0; i < nvolumes && rc == 0; ++i) {
+            if (plan.group_of[(size_t)i] >= 0) continue;
+            long at = 0, len = 0;
+            rc = run_single(i, static_cast<uint8_t*>(d_dst) + (uint64_t)i * slot_capacity, slot_capacity, &at, &len);
+            if (rc == 0) { offsets[i] = (long)((uint64_t)i * slot_capacity) + at; lengths[i] = len; }
+        }
+        if (rc) for (int i = 0; i < nvolumes; ++i) { offsets[i] = 0; lengths[i] = 0; }
+        return rc;
     }
-    if (rc) for (int i = 0; i < nvolumes; ++i) { offsets[i] = 0; lengths[i] = 0; }
-    return rc;
+    // The packed layout.  A volume outside the joint forms uses its whole slot and leaves the blob anywhere in it, so these go first, each
+    // into a workspace slot of its own: the host then knows their sizes, the groups get them as gaps, and the blobs are copied to their
+    // places at the end.  (offsets, lengths and *total are zero here: admit_batch_packed)
+    lens.assign(n, 0);
+    waits_at.assign(n, 0);
+    placed.assign(n, 0);
+    uint64_t waiting = 0;
+    std::vector<uint64_t> slot_at(n, 0), slot_cap(n, 0);
+    for (size_t i = 0; i < n; ++i) {
+        if (plan.group_of[i] >= 0) continue;
+        slot_at[i] = waiting;
+        slot_cap[i] = a.pipe.max_encoded_size(a.len[i] * (uint64_t)elem_size, elem_size);
+        waiting += align_up(slot_cap[i], 256);
+    }
+    if (waiting && cx.ws.batch_packed.ensure(waiting)) return 1;
+    for (int i = 0; i < nvolumes; ++i) {
+        if (plan.group_of[(size_t)i] >= 0) continue;
+        long at = 0, len = 0;
+        if (run_single(i, static_cast<uint8_t*>(cx.ws.batch_packed.p) + slot_at[(size_t)i], slot_cap[(size_t)i], &at, &len)) return 1;
+        waits_at[(size_t)i] = slot_at[(size_t)i] + (uint64_t)at;
+        lens[(size_t)i] = (uint64_t)len;
+    }
+    if (run_groups()) return 1;
+    const sqy::PackedPlaces places = sqy::packed_places(lens, std::vector<uint64_t>(), dense_to->align, 0, slot_capacity);
+    if (!places.ok) { std::fprintf(stderr, "[sqeazy]\t encode batch: the packed blobs pass 2^63 bytes\n"); return 1; }
+    if (places.first_unfit < n) {
+        std::fprintf(stderr, "[sqeazy]\t encode batch: the packed blobs take %llu bytes, the destination holds %llu (volume %zu is the first that does not fit)\n",
+                     (unsigned long long)places.end, (unsigned long long)slot_capacity, places.first_unfit);
+        *dense_to->total = (long)places.end;
+        return 1;
+    }
+    for (size_t i = 0; i < n; ++i)
+        if (plan.group_of[i] >= 0 && !placed[i]) { std::fprintf(stderr, "[sqeazy]\t internal error: volume %zu of the batch was not placed\n", i); return 1; }
+    for (size_t i = 0; i < n; ++i)
+        if (plan.group_of[i] < 0)
+            SQY_HIP(hipMemcpyAsync(static_cast<uint8_t*>(d_dst) + places.at[i], static_cast<uint8_t*>(cx.ws.batch_packed.p) + waits_at[i], lens[i], hipMemcpyDeviceToDevice, stream));
+    if (waiting) SQY_HIP(hipStreamSynchronize(stream));
+    for (size_t i = 0; i < n; ++i) { offsets[i] = (long)places.at[i]; lengths[i] = (long)lens[i]; }
+    *dense_to->total = (long)places.end;
+    return 0;
 }
 
 int encode_batch_device(const char* pipeline, const void* const* d_srcs, const long* shapes, unsigned rank, int elem_size, int nvolumes, void* d_dst,
@@ -3583,6 +3682,84 @@ int encode_batch_from_host(const char* pipeline, const char* const* srcs, const 
             for (int k = 0; k < nvolumes; ++k) { offsets[k] = 0; lengths[k] = 0; }
             return 1;
         }
+    return 0;
+}
+
+// SQYAMD_PipelineEncode_BatchPacked_*: the Batch call's checks with the capacity of all of dst, then total and align -- on the host,
+// before the device is touched; offsets, lengths and *total are zeroed whatever comes of it
+int admit_batch_packed(const char* pipeline, const void* const* srcs, const long* shapes, unsigned rank, int elem_size, int nvolumes, const void* dst,
+                       long dst_capacity, long align, long* offsets, long* lengths, long* total, int nthreads, BatchAdmit* a)
+{
+    if (total) *total = 0;
+    if (admit_batch(pipeline, srcs, shapes, rank, elem_size, nvolumes, dst, dst_capacity, offsets, lengths, nthreads, a)) return 1;
+    if (!total) return 1;
+    if (align < 1 || align > (long)sqy::kPackedAlignMax || (align & (align - 1))) {
+        std::fprintf(stderr, "[sqeazy]\t encode batch: align %ld is no power of two from 1 to %llu\n", align, (unsigned long long)sqy::kPackedAlignMax);
+        return 1;
+    }
+    return 0;
+}
+
+int encode_batch_packed_device(const char* pipeline, const void* const* d_srcs, const long* shapes, const long* strides, unsigned rank, int elem_size, int nvolumes,
+                               void* d_dst, long dst_capacity, long align, long* offsets, long* lengths, long* total, int nthreads, void* hip_stream)
+{
+    BatchAdmit a;
+    if (admit_batch_packed(pipeline, d_srcs, shapes, rank, elem_size, nvolumes, d_dst, dst_capacity, align, offsets, lengths, total, nthreads, &a)) return 1;
+    std::vector<sqy::BatchView> views;
+    if (admit_views("encode batch", d_srcs, shapes, strides, rank, nvolumes, elem_size, &views)) return 1;
+    ContextLease lease;
+    if (!lease.ctx) { std::fprintf(stderr, "[sqeazy]\t no usable HIP device\n"); return 1; }
+    const PackedArgs packed{(uint64_t)align, total};
+    return encode_batch_on_device(*lease.ctx, pipeline, a, d_srcs, shapes, rank, elem_size, nvolumes, d_dst, (uint64_t)dst_capacity, offsets, lengths, nthreads,
+                                  static_cast<hipStream_t>(hip_stream), strides ? &views : nullptr, &packed);
+}
+
+// the host-pointer variant (not tuned): every volume staged up, one call of the device driver, ONE copy of *total bytes back
+int encode_batch_packed_from_host(const char* pipeline, const char* const* srcs, const long* shapes, unsigned rank, int elem_size, int nvolumes, char* dst,
+                                  long dst_capacity, long align, long* offsets, long* lengths, long* total, int nthreads)
+{
+    BatchAdmit a;
+    if (admit_batch_packed(pipeline, reinterpret_cast<const void* const*>(srcs), shapes, rank, elem_size, nvolumes, dst, dst_capacity, align, offsets, lengths, total,
+                           nthreads, &a))
+        return 1;
+    if (!device_present()) { std::fprintf(stderr, "[sqeazy]\t no MI355X (HIP device) visible: sqeazy_amd has no CPU path\n"); return 1; }
+    ContextLease lease;
+    if (!lease.ctx) { std::fprintf(stderr, "[sqeazy]\t no usable HIP device\n"); return 1; }
+    Workspace* ws = &lease.ctx->ws;
+    hipStream_t stream = lease.ctx->own_stream();
+    if (!stream) { std::fprintf(stderr, "[sqeazy]\t no HIP stream\n"); return 1; }
+    std::vector<uint64_t> at((size_t)nvolumes);
+    // the device buffer: the caller's capacity, but no more than what needs no retry
+    uint64_t raw = 0, enough = 0;
+    for (int i = 0; i < nvolumes; ++i) {
+        at[(size_t)i] = raw;
+        raw += (a.len[(size_t)i] * (uint64_t)elem_size + 15) & ~(uint64_t)15;
+        enough += align_up(a.pipe.max_encoded_size(a.len[(size_t)i] * (uint64_t)elem_size, elem_size), (uint64_t)align);
+    }
+    const uint64_t capacity = std::min<uint64_t>((uint64_t)dst_capacity, enough);
+    if (ws->io_src.ensure(std::max<uint64_t>(raw, 16)) || ws->io_dst.ensure(std::max<uint64_t>(capacity, 16))) return 1;
+    int dev_id = 0;
+    SQY_HIP(hipGetDevice(&dev_id));
+    std::vector<const void*> d_srcs((size_t)nvolumes);
+    for (int i = 0; i < nvolumes; ++i) {
+        d_srcs[(size_t)i] = static_cast<char*>(ws->io_src.p) + at[(size_t)i];
+        if (!lease.ctx->stager.copy(const_cast<void*>(d_srcs[(size_t)i]), const_cast<char*>(srcs[i]), a.len[(size_t)i] * (uint64_t)elem_size, true, dev_id)) {
+            std::fprintf(stderr, "[sqeazy]\t host to device transfer failed\n");
+            return 1;
+        }
+    }
+    // (align > 1: the gap bytes come back with the blobs -- zeros, not what the workspace held)
+    if (align > 1) SQY_HIP(hipMemsetAsync(ws->io_dst.p, 0, capacity, stream));
+    const PackedArgs packed{(uint64_t)align, total};
+    const int rc = encode_batch_on_device(*lease.ctx, pipeline, a, d_srcs.data(), shapes, rank, elem_size, nvolumes, ws->io_dst.p, capacity, offsets, lengths, nthreads,
+                                          stream, nullptr, &packed);
+    if (rc) return rc;
+    if (!lease.ctx->stager.copy(ws->io_dst.p, dst, (size_t)*total, false, dev_id)) {
+        std::fprintf(stderr, "[sqeazy]\t device to host transfer failed\n");
+        for (int k = 0; k < nvolumes; ++k) { offsets[k] = 0; lengths[k] = 0; }
+        *total = 0;
+        return 1;
+    }
     return 0;
 }
 
@@ -3935,6 +4112,42 @@ int SQYAMD_PipelineEncode_BatchStrided_UI8_Device(const char* pipeline, const vo
 {
     return guarded([&]() -> int {
         return encode_batch_strided_device(pipeline, d_srcs, shapes, strides, shape_size, 1, nvolumes, d_dst, slot_capacity, offsets, lengths, nthreads, hip_stream);
+    });
+}
+
+int SQYAMD_PipelineEncode_BatchPacked_UI16_Device(const char* pipeline, const void* const* d_srcs, const long* shapes, const long* strides, unsigned shape_size,
+                                                  int nvolumes, void* d_dst, long dst_capacity, long align, long* offsets, long* lengths, long* total, int nthreads,
+                                                  void* hip_stream)
+{
+    return guarded([&]() -> int {
+        return encode_batch_packed_device(pipeline, d_srcs, shapes, strides, shape_size, 2, nvolumes, d_dst, dst_capacity, align, offsets, lengths, total, nthreads,
+                                          hip_stream);
+    });
+}
+
+int SQYAMD_PipelineEncode_BatchPacked_UI8_Device(const char* pipeline, const void* const* d_srcs, const long* shapes, const long* strides, unsigned shape_size,
+                                                 int nvolumes, void* d_dst, long dst_capacity, long align, long* offsets, long* lengths, long* total, int nthreads,
+                                                 void* hip_stream)
+{
+    return guarded([&]() -> int {
+        return encode_batch_packed_device(pipeline, d_srcs, shapes, strides, shape_size, 1, nvolumes, d_dst, dst_capacity, align, offsets, lengths, total, nthreads,
+                                          hip_stream);
+    });
+}
+
+int SQYAMD_PipelineEncode_BatchPacked_UI16(const char* pipeline, const char* const* srcs, const long* shapes, unsigned shape_size, int nvolumes, char* dst,
+                                           long dst_capacity, long align, long* offsets, long* lengths, long* total, int nthreads)
+{
+    return guarded([&]() -> int {
+        return encode_batch_packed_from_host(pipeline, srcs, shapes, shape_size, 2, nvolumes, dst, dst_capacity, align, offsets, lengths, total, nthreads);
+    });
+}
+
+int SQYAMD_PipelineEncode_BatchPacked_UI8(const char* pipeline, const char* const* srcs, const long* shapes, unsigned shape_size, int nvolumes, char* dst,
+                                          long dst_capacity, long align, long* offsets, long* lengths, long* total, int nthreads)
+{
+    return guarded([&]() -> int {
+        return encode_batch_packed_from_host(pipeline, srcs, shapes, shape_size, 1, nvolumes, dst, dst_capacity, align, offsets, lengths, total, nthreads);
     });
 }
 

@@ -218,7 +218,14 @@ hipError_t launch_lz4_batch_scan(const Lz4BatchChunk* d_table, const Lz4BatchVol
 hipError_t launch_lz4_batch_gather(const uint8_t* in, const Lz4BatchChunk* d_table, uint32_t nentries, uint32_t max_chunk, const Lz4BatchVolume* d_vols,
                                    const uint32_t* d_vol_of /* per entry: index into d_vols */, const uint8_t* scratch, uint64_t stride,
                                    const uint32_t* csize, const uint64_t* frame_off, const uint64_t* vinfo, const char* d_text, uint8_t* out,
-                                   uint32_t bd_byte, uint32_t hc_byte, uint64_t* records, hipStream_t stream);
+                                   uint32_t bd_byte, uint32_t hc_byte, uint64_t* records, hipStream_t stream, const uint64_t* d_place = nullptr);
+// The packed layout (SQYAMD_PipelineEncode_BatchPacked_*), between the scan and the gather, one workgroup: d_place[j] = where volume j of
+// the group lies relative to `out` by sqy::packed_places' rule (base: where the group begins, a multiple of align; d_gap[j]: what volumes
+// outside the group take in front of volume j, nullptr: all zero; align a power of two), and a kBatchDone volume that ends behind `capacity` becomes
+// kBatchNoRoom in vinfo.  The gather with d_place writes blob j at out + d_place[j] (dst_at is not read; the scan is given capacity ~0)
+// and leaves a kBatchNoRoom volume's blob length in its record.
+hipError_t launch_lz4_batch_place(uint64_t* vinfo, const uint64_t* d_gap, uint32_t nvols, uint64_t align, uint64_t base, uint64_t capacity, uint64_t* d_place,
+                                  hipStream_t stream);
 
 // quantiser: 65536-bin histogram of u16 voxels (histo is zeroed by the launcher), and out[i] = lut[in[i]]
 // background removal, 1- or 2-byte voxels of a {Z, Y, X} volume

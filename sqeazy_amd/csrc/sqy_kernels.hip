@@ -2836,15 +2836,65 @@ void lz4_batch_scan_kernel(const Lz4BatchChunk* __restrict__ table, const Lz4Bat
     }
 }
 
+// The placement scan of the packed layout (SQYAMD_PipelineEncode_BatchPacked_*), ONE workgroup between the frame scan and the gather:
+// volume j of the group lies at place[j] = base + sum over k <= j of gap[k] + sum over k < j of round_up(hdr_len[k] + payload[k], align)
+// -- sqy::packed_places' rule; base: where the group begins, a multiple of align; gap[j]: what the volumes outside the group take in front
+// of volume j, gap == nullptr: nothing anywhere --, scanned in 64 bits in chunks of 256 with a carry, as lz4_batch_scan_kernel scans a volume's frames.  A kBatchDone volume
+// that ends behind `capacity` becomes kBatchNoRoom (the status half of vinfo): the gather writes nothing of it; it still advances the
+// offset, so the places behind it say what a retry needs.  (No sum wraps: a blob is below 2^33 bytes, a group has fewer than 2^31 volumes
+// and the host keeps base and the gaps below 2^62.)
+__global__ __launch_bounds__(256)
+void lz4_batch_place_kernel(uint64_t* __restrict__ vinfo, const uint64_t* __restrict__ gap, uint32_t nvols, uint64_t align, uint64_t base,
+                            uint64_t capacity, uint64_t* __restrict__ place)
+{
+    __shared__ uint64_t wsum[4];
+    __shared__ uint64_t carry_s;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint64_t mask = align - 1;
+    if (tid == 0) carry_s = base;
+    __syncthreads();
+    for (uint32_t first = 0; first < nvols; first += 256u) {
+        const uint32_t j = first + tid;
+        uint64_t hs = 0, len = 0, room = 0, step = 0;
+        if (j < nvols) {
+            hs = vinfo[2 * j + 1];
+            len = (hs & 0xffffffffull) + vinfo[2 * j];
+            room = (len + mask) & ~mask;
+            step = (gap ? gap[j] : 0) + room;
+        }
+        uint64_t x = step;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint64_t y = __shfl_up(x, d);
+            if (lane >= (uint32_t)d) x += y;
+        }
+        if (lane == 63u) wsum[wave] = x;
+        __syncthreads();
+        uint64_t woff = 0;
+        for (uint32_t w = 0; w < wave; ++w) woff += wsum[w];
+        const uint64_t carry = carry_s;
+        if (j < nvols) {
+            const uint64_t at = carry + woff + x - room;
+            place[j] = at;
+            if ((hs >> 32) == kBatchDone && at + len > capacity) vinfo[2 * j + 1] = (hs & 0xffffffffull) | (kBatchNoRoom << 32);
+        }
+        __syncthreads();
+        if (tid == 255u) carry_s = carry + woff + x;
+        __syncthreads();
+    }
+}
+
 // One workgroup per (table entry, 32 KiB slice), as lz4_frame_gather_kernel; the workgroup of a volume's first entry and slice also
 // writes the volume's header (as lz4_inplace_finish_kernel formats it) and its record.  A volume that is not kBatchDone gets its
-// record and not a byte else.
-__global__ __launch_bounds__(256)
-void lz4_batch_gather_kernel(const uint8_t* __restrict__ in, const Lz4BatchChunk* __restrict__ table, const Lz4BatchVolume* __restrict__ vols,
-                             const uint32_t* __restrict__ vol_of, const uint8_t* __restrict__ scratch, uint64_t stride,
-                             const uint32_t* __restrict__ csize, const uint64_t* __restrict__ frame_off, const uint64_t* __restrict__ vinfo,
-                             const char* __restrict__ text, uint8_t* __restrict__ out, uint32_t bd_byte, uint32_t hc_byte, uint32_t slices_per_chunk,
-                             uint64_t* __restrict__ records)
+// record and not a byte else.  kPacked: the blob lies at out + place[its index in the group] (lz4_batch_place_kernel), not at its dst_at,
+// and a kBatchNoRoom volume's record carries the blob's length -- the host sums up what a retry needs.
+template <bool kPacked>
+__device__ __forceinline__
+void lz4_batch_gather_body(const uint8_t* __restrict__ in, const Lz4BatchChunk* __restrict__ table, const Lz4BatchVolume* __restrict__ vols,
+                           const uint32_t* __restrict__ vol_of, const uint8_t* __restrict__ scratch, uint64_t stride,
+                           const uint32_t* __restrict__ csize, const uint64_t* __restrict__ frame_off, const uint64_t* __restrict__ vinfo,
+                           const char* __restrict__ text, uint8_t* __restrict__ out, uint32_t bd_byte, uint32_t hc_byte, uint32_t slices_per_chunk,
+                           uint64_t* __restrict__ records, const uint64_t* __restrict__ place)
 {
     const uint32_t e = blockIdx.x / slices_per_chunk, slice = blockIdx.x % slices_per_chunk, tid = threadIdx.x;
     const Lz4BatchChunk ce = table[e];
@@ -2855,12 +2905,12 @@ void lz4_batch_gather_kernel(const uint8_t* __restrict__ in, const Lz4BatchChunk
     const bool first = e == v.first_chunk && slice == 0;
     if (first && tid == 0) {
         uint64_t* r = records + 3 * (uint64_t)v.record;
-        r[1] = status == kBatchDone ? hdr_len + payload : 0;
+        r[1] = status == kBatchDone || (kPacked && status == kBatchNoRoom) ? hdr_len + payload : 0;
         r[2] = payload;
         r[0] = status;
     }
     if (status != kBatchDone) return;
-    uint8_t* __restrict__ blob = out + v.dst_at;
+    uint8_t* __restrict__ blob = out + (kPacked ? place[lv] : v.dst_at);
     if (first) {
         uint32_t nd = 0;
         { uint64_t q = payload; do { ++nd; q /= 10; } while (q); }
@@ -2916,6 +2966,26 @@ void lz4_batch_gather_kernel(const uint8_t* __restrict__ in, const Lz4BatchChunk
     }
     const uint32_t done = nvec << 4;
     if (tid < len - done) dd[done + tid] = ss[done + tid];
+}
+
+__global__ __launch_bounds__(256)
+void lz4_batch_gather_kernel(const uint8_t* __restrict__ in, const Lz4BatchChunk* __restrict__ table, const Lz4BatchVolume* __restrict__ vols,
+                             const uint32_t* __restrict__ vol_of, const uint8_t* __restrict__ scratch, uint64_t stride,
+                             const uint32_t* __restrict__ csize, const uint64_t* __restrict__ frame_off, const uint64_t* __restrict__ vinfo,
+                             const char* __restrict__ text, uint8_t* __restrict__ out, uint32_t bd_byte, uint32_t hc_byte, uint32_t slices_per_chunk,
+                             uint64_t* __restrict__ records)
+{
+    lz4_batch_gather_body<false>(in, table, vols, vol_of, scratch, stride, csize, frame_off, vinfo, text, out, bd_byte, hc_byte, slices_per_chunk, records, nullptr);
+}
+
+__global__ __launch_bounds__(256)
+void lz4_batch_gather_packed_kernel(const uint8_t* __restrict__ in, const Lz4BatchChunk* __restrict__ table, const Lz4BatchVolume* __restrict__ vols,
+                                    const uint32_t* __restrict__ vol_of, const uint8_t* __restrict__ scratch, uint64_t stride,
+                                    const uint32_t* __restrict__ csize, const uint64_t* __restrict__ frame_off, const uint64_t* __restrict__ vinfo,
+                                    const char* __restrict__ text, uint8_t* __restrict__ out, uint32_t bd_byte, uint32_t hc_byte, uint32_t slices_per_chunk,
+                                    uint64_t* __restrict__ records, const uint64_t* __restrict__ place)
+{
+    lz4_batch_gather_body<true>(in, table, vols, vol_of, scratch, stride, csize, frame_off, vinfo, text, out, bd_byte, hc_byte, slices_per_chunk, records, place);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -6703,13 +6773,26 @@ hipError_t launch_lz4_batch_scan(const Lz4BatchChunk* d_table, const Lz4BatchVol
 hipError_t launch_lz4_batch_gather(const uint8_t* in, const Lz4BatchChunk* d_table, uint32_t nentries, uint32_t max_chunk, const Lz4BatchVolume* d_vols,
                                    const uint32_t* d_vol_of, const uint8_t* scratch, uint64_t stride, const uint32_t* csize, const uint64_t* frame_off,
                                    const uint64_t* vinfo, const char* d_text, uint8_t* out, uint32_t bd_byte, uint32_t hc_byte, uint64_t* records,
-                                   hipStream_t stream)
+                                   hipStream_t stream, const uint64_t* d_place)
 {
     if (nentries == 0) return hipSuccess;
     const uint32_t slices = max_chunk ? (max_chunk + GATHER_SLICE - 1) / GATHER_SLICE : 1u;
     if ((uint64_t)nentries * slices > 0x7fffffffull) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(lz4_batch_gather_kernel, dim3(nentries * slices), dim3(256), 0, stream, in, d_table, d_vols, d_vol_of, scratch, stride, csize, frame_off,
-                       vinfo, d_text, out, bd_byte, hc_byte, slices, records);
+    if (d_place)
+        hipLaunchKernelGGL(lz4_batch_gather_packed_kernel, dim3(nentries * slices), dim3(256), 0, stream, in, d_table, d_vols, d_vol_of, scratch, stride, csize,
+                           frame_off, vinfo, d_text, out, bd_byte, hc_byte, slices, records, d_place);
+    else
+        hipLaunchKernelGGL(lz4_batch_gather_kernel, dim3(nentries * slices), dim3(256), 0, stream, in, d_table, d_vols, d_vol_of, scratch, stride, csize, frame_off,
+                           vinfo, d_text, out, bd_byte, hc_byte, slices, records);
+    return hipGetLastError();
+}
+
+hipError_t launch_lz4_batch_place(uint64_t* vinfo, const uint64_t* d_gap, uint32_t nvols, uint64_t align, uint64_t base, uint64_t capacity, uint64_t* d_place,
+                                  hipStream_t stream)
+{
+    if (nvols == 0) return hipSuccess;
+    if (align == 0 || (align & (align - 1))) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(lz4_batch_place_kernel, dim3(1), dim3(256), 0, stream, vinfo, d_gap, nvols, align, base, capacity, d_place);
     return hipGetLastError();
 }
 

@@ -310,6 +310,30 @@ Lz4BatchPlan lz4_batch_plan(const Lz4Params& p, const std::vector<uint64_t>& tot
     return lz4_batch_plan_views(p, totals, std::vector<uint64_t>(), nthreads, group_bytes, joint_max, extra_bytes);
 }
 
+PackedPlaces packed_places(const std::vector<uint64_t>& lengths, const std::vector<uint64_t>& gaps, uint64_t align, uint64_t base, uint64_t capacity)
+{
+    constexpr uint64_t lim = (uint64_t)1 << 63;                            // every place and every end stays below it
+    const size_t n = lengths.size();
+    if (align == 0 || align > kPackedAlignMax || (align & (align - 1)) || (!gaps.empty() && gaps.size() != n) || base >= lim) return PackedPlaces();
+    PackedPlaces p;
+    p.at.resize(n);
+    p.first_unfit = n;
+    uint64_t cur = base;
+    p.end = base;
+    for (size_t j = 0; j < n; ++j) {
+        const uint64_t gap = gaps.empty() ? 0 : gaps[j];
+        if (gap >= lim - cur || lengths[j] >= lim - (cur + gap)) return PackedPlaces();
+        p.at[j] = cur + gap;
+        p.end = p.at[j] + lengths[j];
+        if (p.end > capacity && p.first_unfit == n) p.first_unfit = j;
+        if (j + 1 == n) break;
+        if (p.end > lim - align) return PackedPlaces();                   // (the rounded end as well)
+        cur = (p.end + align - 1) & ~(align - 1);
+    }
+    p.ok = true;
+    return p;
+}
+
 bool admit_view(const long* shape, const long* strides, unsigned rank, BatchView* view)
 {
     if (!shape || !view || rank == 0 || rank > 3) return false;

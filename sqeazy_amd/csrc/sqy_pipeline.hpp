@@ -121,6 +121,18 @@ constexpr uint64_t kQuantiserBatchHistoBytes = 65536 * 4, kQuantiserBatchLutByte
 uint64_t encode_batch_stream_bytes(EncodeBatchForm form, uint64_t voxels, int elem_size);
 uint64_t encode_batch_extra_bytes(EncodeBatchForm form);
 
+// ---- packed batch encode (SQYAMD_PipelineEncode_BatchPacked_*): the blobs back to back in one buffer ----
+// The placement rule, stated once (lz4_batch_place_kernel computes the same numbers for the volumes of a group).  Volume j of lengths[j]
+// bytes lies at at[j]: the first one at base + gaps[0], every later one at the end of the one before it rounded up to `align`, plus
+// gaps[j] -- the room in front of volume j that others take (a multiple of align where the caller wants at[j] aligned; gaps empty: none).
+// end: where the last volume ends (not rounded; base for no volume) -- what a capacity must be for every volume to fit.  first_unfit: the
+// first volume with at[j] + lengths[j] > capacity, lengths.size() when all fit; volumes behind it are placed as if it had fitted.  All
+// arithmetic in 64 unsigned bits.  ok = false (at empty, end 0, first_unfit 0): align no power of two in [1, kPackedAlignMax], a gap table
+// of another size than lengths, or a place, end or rounded end above 2^63 - 1 -- refused, never wrapped.
+constexpr uint64_t kPackedAlignMax = 65536;
+struct PackedPlaces { std::vector<uint64_t> at; uint64_t end = 0; size_t first_unfit = 0; bool ok = false; };
+PackedPlaces packed_places(const std::vector<uint64_t>& lengths, const std::vector<uint64_t>& gaps, uint64_t align, uint64_t base, uint64_t capacity);
+
 // ---- strided views (SQYAMD_PipelineEncode_BatchStrided_*, SQYAMD_Decode_BatchStrided_*): a volume cut out of a larger allocation ----
 // Z x Y x X voxels, x innermost with stride 1, rows sy voxels apart, frames sz voxels apart.  dense: sy = X and sz = Y X, the view is one
 // run of Z Y X voxels (Z = Y = 1 then: a dense view is folded into one row)
