@@ -14,9 +14,12 @@ Sources of truth
   * quantiser LUTs the reference's own sqeazy::quantiser<uint16_t, uint8_t> compiled in place (oracle/ref_driver.cpp, with the
                    string_parsers.hpp of oracle/ref_shim/) on the volumes of tests/quantiser_cases.py -> tests/golden/quantiser_luts.json
                    (--quantiser): digests of both tables
-  * what the reference cannot produce here (needs Boost proper: frame_shuffle, tile_shuffle, header) is NOT in this
-    file's "reference" section; those stages are pinned by the reference's own KATs restated in
-    tests/test_oracle_reference_kats.py and carry "oracle" hashes here only as regression anchors.
+  * shuffles       frame_shuffle and tile_shuffle on whole units: the reference's own detail::frame_shuffle / detail::tile_shuffle compiled
+                   in place (oracle/ref_driver.cpp, with the Boost.Accumulators stand-in of oracle/boost_standin/, which only their median
+                   path names) -> tests/golden/ref_shuffles.json (--shuffles): output digests, decode_maps, decode digests
+  * what the reference cannot produce here (needs Boost proper: the sqy header; the remainder / median path of the two shuffles, which
+    oracle and product refuse) is NOT in this file's "reference" section; whole pipelines through frame_shuffle carry "oracle" hashes in
+    golden.json as regression anchors, and the header is pinned by the reference's own KATs restated in tests/test_oracle_reference_kats.py.
 
 Output
   tests/golden/golden.json     {case: {input: generator spec, stage: {sha256, bytes, source}}}
@@ -36,6 +39,7 @@ from sqeazy_amd import synth             # noqa: E402
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import bkrd_restate as R                                            # noqa: E402
 from ref_stage_inputs import stage_input, stage_volume, stage_tile, case_id  # noqa: E402,F401  (the tests import them from here or there)
+from ref_stage_inputs import shuffle_volume, shuffle_param, shuffle_whole, shuffle_case_id  # noqa: E402,F401
 
 GOLD = os.path.join(ROOT, "tests", "golden")
 
@@ -603,7 +607,8 @@ QUANTISER_SAN_CASES = ("uniform_60000", "levels_257_top")
 
 def dump_stage_cases(path):
     """inputs of every case the reference is run on, for tests/sanitize/ref_stages_san.cpp: cases.txt (one line per case:
-    id stage dtype z y x p0 p1 offset_bytes serial_only) and <index>.bin; quantiser.txt (name, voxels) and quantiser_<index>.bin"""
+    id stage dtype z y x p0 p1 offset_bytes serial_only) and <index>.bin, the rows of shuffle_table() behind those of stage_table();
+    quantiser.txt (name, voxels) and quantiser_<index>.bin"""
     os.makedirs(path, exist_ok=True)
     lines = []
     for row in stage_table():
@@ -616,6 +621,13 @@ def dump_stage_cases(path):
         vol.tofile(os.path.join(path, "%d.bin" % k))
         lines.append("%s %s %s %d %d %d %d %r %d %d" % (row["id"], row["stage"], row["dtype"], vol.shape[0], vol.shape[1], vol.shape[2], p0,
                                                        float(p.get("fraction", 0.0)), p.get("offset_bytes", 0), int("serial_only" in row)))
+    # the rows of ref_shuffles.json, refused ones included: p0 is frame_chunk_size / tile_size, p1 is 1.0 where the driver has to answer
+    # "remainder" without running the reference
+    for row in shuffle_table():
+        vol = shuffle_volume(row)
+        vol.tofile(os.path.join(path, "%d.bin" % len(lines)))
+        lines.append("%s %s %s %d %d %d %d %r 0 0" % (row["id"], row["stage"], row["dtype"], vol.shape[0], vol.shape[1], vol.shape[2], shuffle_param(row),
+                                                      0.0 if shuffle_whole(row) else 1.0))
     with open(os.path.join(path, "cases.txt"), "w") as f:
         f.write("\n".join(lines) + "\n")
     import quantiser_cases as Q
@@ -663,9 +675,205 @@ def quantiser():
     print("wrote quantiser_luts.json:", len(out["cases"]), "cases")
 
 
+# ------------------------------------------------------------------------------------------------------------------------------------
+# frame_shuffle and tile_shuffle against the reference's own templates (oracle/ref_driver.cpp): tests/golden/ref_shuffles.json
+# ------------------------------------------------------------------------------------------------------------------------------------
+def shuffle_table():
+    """the smallest shapes that still take each branch; every volume at most 64 KiB"""
+    T = []
+
+    def add(stage, dtype, shape, kind, p):
+        r = {"stage": stage, "dtype": dtype, "shape": list(shape), "kind": kind, "seed": 3000 + len(T)}
+        r["frame_chunk_size" if stage == "frame_shuffle" else "tile_size"] = p
+        r["id"] = shuffle_case_id(r, len(T))
+        T.append(r)
+
+    # ---- frame_shuffle: frames of 1 voxel, of 5 x 37 (no whole 16-byte vectors), of whole vectors; chunks of 1, 2, 3 and Z (one unit) ----
+    for dt in ("uint16", "uint8"):
+        add("frame_shuffle", dt, (1, 1, 1), "random", 1)
+        add("frame_shuffle", dt, (7, 1, 1), "random", 1)
+        add("frame_shuffle", dt, (40, 1, 1), "ramp", 1)
+        add("frame_shuffle", dt, (40, 1, 1), "descending", 2)
+        for chunk in (1, 2):
+            add("frame_shuffle", dt, (40, 5, 37), "random", chunk)
+        add("frame_shuffle", dt, (39, 5, 37), "random", 3)
+        add("frame_shuffle", dt, (12, 5, 37), "random", 12)
+        for kind in ("random", "ramp", "descending"):
+            add("frame_shuffle", dt, (12, 8, 16), kind, 1)
+        for chunk in (2, 3, 12):
+            add("frame_shuffle", dt, (12, 8, 16), "descending", chunk)
+        add("frame_shuffle", dt, (9, 8, 16), "all_equal", 1)
+        add("frame_shuffle", dt, (9, 8, 16), "all_equal", 3)
+        add("frame_shuffle", dt, (10, 8, 16), "two_groups", 1)
+        add("frame_shuffle", dt, (20, 8, 16), "two_groups", 2)
+        add("frame_shuffle", dt, (8, 5, 37), "permuted", 1)
+        add("frame_shuffle", dt, (16, 8, 16), "permuted", 2)
+        big = (4, 64, 128) if dt == "uint16" else (4, 128, 128)          # 64 KiB: four frames of 4 blocks, or one unit of 16
+        add("frame_shuffle", dt, big, "random", 1)
+        add("frame_shuffle", dt, big, "descending", 2)
+        add("frame_shuffle", dt, big, "random", 4)
+    for kind in ("pm128", "neg_means", "extremes", "random", "permuted", "all_equal", "two_groups"):
+        add("frame_shuffle", "char", (12, 5, 37), kind, 1)
+        add("frame_shuffle", "char", (12, 8, 16), kind, 2)
+    add("frame_shuffle", "char", (15, 16, 16), "neg_means", 3)
+    add("frame_shuffle", "char", (7, 1, 1), "pm128", 1)
+    add("frame_shuffle", "char", (4, 128, 128), "neg_means", 1)
+    add("frame_shuffle", "char", (4, 128, 128), "extremes", 1)
+    add("frame_shuffle", "char", (4, 128, 128), "pm128", 4)
+    # refused: Z is no multiple of the chunk
+    for dt in ("uint16", "uint8", "char"):
+        add("frame_shuffle", dt, (7, 8, 16), "random", 2)
+        add("frame_shuffle", dt, (10, 8, 16), "random", 3)
+        add("frame_shuffle", dt, (3, 4, 4), "random", 5)
+    # ---- tile_shuffle: tiles of 2, 4, 5, 8 and 16; tile counts that differ per axis; a single tile ----
+    for dt in ("uint16", "uint8", "char"):
+        for shape, ts in (((4, 6, 8), 2), ((4, 12, 8), 4), ((5, 10, 15), 5), ((8, 16, 24), 8), ((16, 16, 32), 16)):
+            add("tile_shuffle", dt, shape, "random", ts)
+        for ts in (2, 5, 16):
+            add("tile_shuffle", dt, (ts, ts, ts), "random", ts)
+        add("tile_shuffle", dt, (8, 16, 24), "ramp", 8)
+        add("tile_shuffle", dt, (8, 8, 12), "all_equal", 4)
+        add("tile_shuffle", dt, (8, 8, 12), "permuted", 4)
+        add("tile_shuffle", dt, (8, 12, 8), "two_groups", 4)
+    for dt in ("uint16", "uint8"):
+        add("tile_shuffle", dt, (8, 12, 8), "descending", 4)
+        for shape, ts in (((4, 6, 8), 2), ((10, 10, 15), 5), ((8, 16, 24), 8), ((16, 32, 32), 16)):
+            add("tile_shuffle", dt, shape, "fraction", ts)
+    add("tile_shuffle", "uint16", (16, 32, 64), "random", 16)              # 64 KiB: eight tiles of two blocks
+    add("tile_shuffle", "uint16", (32, 16, 32), "descending", 16)
+    for shape, ts in (((4, 6, 8), 2), ((5, 10, 20), 5), ((8, 16, 24), 8), ((16, 32, 32), 16)):
+        add("tile_shuffle", "uint8", shape, "integer_edge", ts)
+    for kind in ("pm128", "neg_means", "extremes", "trunc_zero"):
+        for shape, ts in (((4, 6, 8), 2), ((5, 10, 20), 5), ((8, 16, 24), 8), ((16, 32, 32), 16)):
+            add("tile_shuffle", "char", shape, kind, ts)
+    # refused: an axis that is no multiple of the tile, or shorter than it
+    for dt in ("uint16", "uint8", "char"):
+        add("tile_shuffle", dt, (8, 8, 9), "random", 4)
+        add("tile_shuffle", dt, (6, 8, 8), "random", 4)
+        add("tile_shuffle", dt, (8, 10, 8), "random", 4)
+        add("tile_shuffle", dt, (2, 8, 8), "random", 4)
+        add("tile_shuffle", dt, (16, 16, 8), "random", 16)
+    return T
+
+
+def shuffle_fns(row):
+    """(oracle encode, oracle decode, reference encode, reference decode) of a row, all on the uint8 / uint16 array the case travels in"""
+    char, p = row["dtype"] == "char", shuffle_param(row)
+    if row["stage"] == "frame_shuffle":
+        return (lambda v: o.frame_shuffle_encode(v, char=char, chunk=p), lambda e, m: o.frame_shuffle_decode(e, m, p),
+                lambda v, nt: ref.frame_shuffle_encode(v, p, char, nt), lambda e, m: ref.frame_shuffle_decode(e, m, p, char))
+    return (lambda v: o.tile_shuffle_encode(v, p, char=char), lambda e, m: o.tile_shuffle_decode(e, m, p),
+            lambda v, nt: ref.tile_shuffle_encode(v, p, char, nt), lambda e, m: ref.tile_shuffle_decode(e, m, p, char))
+
+
+def oracle_shuffle(row, vol):
+    """the ORACLE's (output, decode_map, zero-filled decode of that output from that map); ValueError where the oracle refuses the shape"""
+    enc, dec, _, _ = shuffle_fns(row)
+    try:
+        out, dmap = enc(vol)
+    except NotImplementedError as e:                                        # frame_shuffle's word for a remainder
+        raise ValueError(str(e))
+    return out, dmap, dec(out, dmap)
+
+
+def reference_shuffle(row, vol, nthreads=1):
+    """the REFERENCE's, through oracle/_ref; ref.Remainder, with nothing of the reference run, where the shape has a remainder"""
+    _, _, enc, dec = shuffle_fns(row)
+    out, dmap = enc(vol, nthreads)
+    return out, dmap, dec(out, dmap)
+
+
+def is_permutation(dmap):
+    return sorted(int(m) for m in dmap) == list(range(len(dmap)))
+
+
+def frame_metric_reference(b, nthreads=1):
+    """the live reference on a built case of tests/frame_metric_cases.py: (output, decode_map); the char and chunk forms as the case's kind says"""
+    import frame_metric_cases as F
+    c = b.case
+    if c.kind == F.TILE:
+        return ref.tile_shuffle_encode(b.volume, c.tile, nthreads=nthreads)
+    return ref.frame_shuffle_encode(b.volume, 2 if c.kind == F.CHUNK else 1, c.kind == F.TAIL, nthreads)
+
+
+def frame_metric_oracle(b):
+    import frame_metric_cases as F
+    c = b.case
+    if c.kind == F.TILE:
+        return o.tile_shuffle_encode(b.volume, c.tile)
+    return o.frame_shuffle_encode(b.volume, char=c.kind == F.TAIL, chunk=2 if c.kind == F.CHUNK else 1)
+
+
+def shuffles():
+    """tests/golden/ref_shuffles.json: for every row of shuffle_table() what the REFERENCE's own detail::frame_shuffle / detail::tile_shuffle
+    give (oracle/ref_driver.cpp): byte count and sha256 of the output, the decode_map as a list, the sha256 of the zero-filled decode of
+    that output from that map; nthreads 1 and 4 asserted equal, the oracle asserted equal on the way.  Rows whose shape has a remainder are
+    `refused` and the reference is not run on them.  And, by name, the decode_map the reference gives for every case of
+    tests/frame_metric_cases.py, asserted equal to the case's expected_map."""
+    import frame_metric_cases as F
+    assert ref.shuffles_available(), "oracle/_ref/libsqy_ref.so missing or stale: run `make -C oracle` where the reference tree exists"
+    G = {"_meta": {"generator": "oracle/gen_golden.py --shuffles",
+                   "source": "sqeazy::detail::frame_shuffle and sqeazy::detail::tile_shuffle compiled in place (oracle/ref_driver.cpp)",
+                   "inputs": "tests/ref_stage_inputs.py: shuffle_volume(case); dtype char travels as the uint8 array of the same bytes",
+                   "decode_sha256": "the reference's decode of its own output from its own map into a ZERO-FILLED buffer (the driver's choice: the "
+                                    "reference leaves slots that no map entry names as they were); the input itself where the map is a permutation",
+                   "refused": "shapes with a remainder (Z % frame_chunk_size, an axis % tile_size, an axis shorter than the tile): the reference would "
+                              "take its median path; it is not run on these rows and says nothing about them",
+                   "frame_metric_cases": "tests/frame_metric_cases.py by name: the decode_map the reference gives for the built volume"},
+         "cases": [], "frame_metric_cases": {}}
+    for row in shuffle_table():
+        vol = shuffle_volume(row)
+        assert vol.nbytes <= 64 << 10, row["id"]
+        e = dict(row)
+        e["input_sha256"] = sha(vol.tobytes())[:12]
+        if not shuffle_whole(row):
+            for fn in (oracle_shuffle, reference_shuffle):
+                try:
+                    fn(row, vol)
+                    raise AssertionError(("a shape with a remainder was not refused", row["id"], fn.__name__))
+                except (ValueError, ref.Remainder):
+                    pass
+            e["refused"] = True
+        else:
+            out, dmap, back = reference_shuffle(row, vol, 1)
+            out4, dmap4, back4 = reference_shuffle(row, vol, 4)
+            assert np.array_equal(out, out4) and np.array_equal(dmap, dmap4) and np.array_equal(back, back4), (
+                "the reference disagrees with itself across thread counts", row["id"])
+            oout, omap, oback = oracle_shuffle(row, vol)
+            assert np.array_equal(out, oout) and np.array_equal(dmap, omap) and np.array_equal(back, oback), ("the oracle differs from the reference", row["id"])
+            if is_permutation(dmap):
+                assert np.array_equal(back, vol), ("the reference's decode does not restore the input", row["id"])
+            e["bytes"], e["sha256"] = out.nbytes, sha(out.tobytes())
+            e["map"] = [int(m) for m in dmap]
+            e["decode_sha256"] = sha(back.tobytes())
+        G["cases"].append(e)
+    for name in F.NAMES:
+        b = F.built(name)
+        out, dmap = frame_metric_reference(b, 1)
+        out4, dmap4 = frame_metric_reference(b, 4)
+        oout, omap = frame_metric_oracle(b)
+        assert np.array_equal(dmap, dmap4) and np.array_equal(out, out4), ("the reference disagrees with itself across thread counts", name)
+        assert np.array_equal(dmap, b.expected_map), ("the case's expected_map is not the reference's", name, dmap.tolist(), b.expected_map.tolist())
+        assert np.array_equal(dmap, omap) and np.array_equal(out, oout), ("the oracle differs from the reference", name)
+        G["frame_metric_cases"][name] = [int(m) for m in dmap]
+        del b, out, out4, oout
+    with open(os.path.join(GOLD, "ref_shuffles.json"), "w") as f:                 # compact, one case per line
+        f.write('{"_meta": %s,\n"cases": [\n%s\n],\n"frame_metric_cases": %s}\n' % (
+            json.dumps(G["_meta"], sort_keys=True),
+            ",\n".join(json.dumps({k: v for k, v in c.items() if k != "id"}, sort_keys=True, separators=(",", ":")) for c in G["cases"]),
+            json.dumps(G["frame_metric_cases"], sort_keys=True, separators=(",", ":"))))
+    live = [c for c in G["cases"] if "refused" not in c]
+    print("wrote ref_shuffles.json:", len(G["cases"]), "cases,", len(G["cases"]) - len(live), "refused,",
+          sum(not is_permutation(c["map"]) for c in live), "with a map that is no permutation;", len(G["frame_metric_cases"]), "maps of frame_metric_cases")
+    for stage in ("frame_shuffle", "tile_shuffle"):
+        print(" ", stage, {dt: sum(c["stage"] == stage and c["dtype"] == dt for c in G["cases"]) for dt in ("uint16", "uint8", "char")})
+
+
 if __name__ == "__main__":
     if "--stages" in sys.argv:
         stages()
+    elif "--shuffles" in sys.argv:
+        shuffles()
     elif "--quantiser" in sys.argv:
         quantiser()
     elif "--accel" in sys.argv:
@@ -683,6 +891,7 @@ if __name__ == "__main__":
     else:
         main()
         stages()
+        shuffles()
         quantiser()
         accel()
         lz4_planted()

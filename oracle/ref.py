@@ -1,6 +1,6 @@
 """Loader for oracle/_ref/libsqy_ref.so -- the driver around the REAL reference pieces that build in
-this image (the reference's filter-stage templates, its SSE bit-plane gather and its quantiser + the image's
-liblz4 1.9.3).  TEST INFRASTRUCTURE ONLY.
+this image (the reference's filter-stage templates, its SSE bit-plane gather, its quantiser and its frame_shuffle /
+tile_shuffle + the image's liblz4 1.9.3).  TEST INFRASTRUCTURE ONLY.
 
 The library is built by oracle/Makefile from /root/reference when that tree is present; on the GPU box
 only the prebuilt file (shipped with the snapshot) can be used.  `available()` says whether it loads.
@@ -42,7 +42,7 @@ def _rebuild_if_stale(path):
             data = f.read()
     except OSError:
         return
-    if all(name.encode() in data for name in STAGE_ENTRY_POINTS + QUANTISER_ENTRY_POINTS):
+    if all(name.encode() in data for name in STAGE_ENTRY_POINTS + QUANTISER_ENTRY_POINTS + SHUFFLE_ENTRY_POINTS):
         return
     try:
         if reference_tree():
@@ -75,6 +75,16 @@ def quantiser_available():
     other stages only"""
     L = lib()
     return L is not None and all(hasattr(L, f) for f in QUANTISER_ENTRY_POINTS)
+
+
+SHUFFLE_ENTRY_POINTS = ("ref_frame_shuffle_encode", "ref_frame_shuffle_decode", "ref_tile_shuffle_encode", "ref_tile_shuffle_decode")
+
+
+def shuffles_available():
+    """True when the library also holds the reference's frame_shuffle and tile_shuffle (a prebuilt oracle/_ref from a driver before those
+    entry points does not)"""
+    L = lib()
+    return L is not None and all(hasattr(L, f) for f in SHUFFLE_ENTRY_POINTS)
 
 
 def _make(target):
@@ -233,6 +243,64 @@ def quantiser_encode(a, weighting="none", nthreads=1):
     _done(lib().ref_quantiser_encode(flat.ctypes.data_as(_u16p), ctypes.c_size_t(flat.size), mode, num, den, int(nthreads),
                                      codes.ctypes.data_as(_u8p), dec.ctypes.data_as(_u16p)), "quantiser")
     return codes.reshape(a.shape), dec
+
+
+class Remainder(Refused):
+    """frame_shuffle / tile_shuffle: the shape is no whole number of units.  The reference would take its median path
+    (encode_with_remainder), which this build does not have; the driver answers before the reference is called"""
+
+
+def _shuffle_done(rc, what):
+    if rc == 4:
+        raise Remainder("%s: the shape has a remainder; the reference's median path is not run" % what)
+    if rc == 5:
+        raise Refused("%s: the map does not fit the shape" % what)
+    _done(rc, what)
+
+
+def _units(shape, chunk=None, tile=None):
+    z, y, x = (int(d) for d in shape)
+    return z // chunk if tile is None else (z // tile) * (y // tile) * (x // tile)
+
+
+def _shuffle_encode(fn, what, a, param, units, char, nthreads):
+    a, src, dst, dt = _io(a, char)
+    dmap = np.zeros(max(units, 1), dtype=np.uint64)
+    _shuffle_done(fn(dt, ctypes.c_void_p(src.ctypes.data), ctypes.c_void_p(dst.ctypes.data), _shape3(a.shape), ctypes.c_size_t(int(param)),
+                     int(nthreads), dmap.ctypes.data_as(_szp), ctypes.c_size_t(units)), what)
+    return dst.reshape(a.shape).copy(), dmap[:units]
+
+
+def _shuffle_decode(fn, what, a, dmap, param, char, nthreads):
+    a, src, dst, dt = _io(a, char)
+    dst[:] = 0xA5 if a.dtype.itemsize == 1 else 0xA5A5     # the driver zero-fills: what is here must not show in the result
+    dmap = np.ascontiguousarray(dmap, dtype=np.uint64)
+    _shuffle_done(fn(dt, ctypes.c_void_p(src.ctypes.data), ctypes.c_void_p(dst.ctypes.data), _shape3(a.shape), ctypes.c_size_t(int(param)),
+                     dmap.ctypes.data_as(_szp), ctypes.c_size_t(dmap.size), int(nthreads)), what)
+    return dst.reshape(a.shape).copy()
+
+
+def frame_shuffle_encode(a, chunk=1, char=False, nthreads=1):
+    """(output of a.shape, decode_map as uint64) of sqeazy::detail::frame_shuffle(frame_chunk_size).encode; raises Remainder, without
+    running the reference, where Z is no multiple of the chunk"""
+    return _shuffle_encode(lib().ref_frame_shuffle_encode, "frame_shuffle", a, chunk, _units(np.shape(a), chunk=max(int(chunk), 1)), char, nthreads)
+
+
+def frame_shuffle_decode(a, dmap, chunk=1, char=False, nthreads=1):
+    """sqeazy::detail::frame_shuffle(frame_chunk_size, map).decode into a ZERO-FILLED output (the driver's choice: the reference leaves
+    slots that no map entry names as the buffer had them)"""
+    return _shuffle_decode(lib().ref_frame_shuffle_decode, "frame_shuffle", a, dmap, chunk, char, nthreads)
+
+
+def tile_shuffle_encode(a, tile_size, char=False, nthreads=1):
+    """(output of a.shape, decode_map as uint64) of sqeazy::detail::tile_shuffle(tile_size).encode; raises Remainder, without running
+    the reference, where an axis is no multiple of the tile"""
+    return _shuffle_encode(lib().ref_tile_shuffle_encode, "tile_shuffle", a, tile_size, _units(np.shape(a), tile=max(int(tile_size), 1)), char, nthreads)
+
+
+def tile_shuffle_decode(a, dmap, tile_size, char=False, nthreads=1):
+    """sqeazy::detail::tile_shuffle(tile_size, map).decode into a zero-filled output"""
+    return _shuffle_decode(lib().ref_tile_shuffle_decode, "tile_shuffle", a, dmap, tile_size, char, nthreads)
 
 
 def bitswap1_encode_u16(a, nthreads=1):

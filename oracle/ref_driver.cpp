@@ -10,7 +10,12 @@
  *      diff_scheme_utils.hpp, sqeazy_common.hpp, sqeazy_algorithms.hpp, hist_impl.hpp,
  *      encoders/{histogram_utils, background_scheme_utils, zcurve_reorder_utils, morton,
  *      raster_reorder_utils, scalar_utils, bitplane_reorder_scalar, bitplane_reorder_sse, sse_utils,
- *      quantiser_utils, quantiser_weighters}.hpp and header_utils.hpp.  quantiser_utils.hpp includes
+ *      quantiser_utils, quantiser_weighters, frame_shuffle_utils, tile_shuffle_utils}.hpp and header_utils.hpp.
+ *      The two shuffle headers include Boost.Accumulators for ONE thing, the median of encode_with_remainder (shapes that are no
+ *      whole number of units).  boost_standin/boost/accumulators/ declares the names they mention, with bodies that stop the
+ *      program; the entry points below return REF_REMAINDER for such shapes before the reference is called, so those bodies are
+ *      never reached.  Everything else in the two headers -- encode_full: std::accumulate in float, sum / n, std::sort,
+ *      std::find -- is plain C++ and runs as the reference wrote it.  quantiser_utils.hpp includes
  *      "string_parsers.hpp" (Boost.StringAlgo) for its two LUT-as-string helpers; oracle/ref_shim/ holds a header
  *      of that name, our own, that declares the two templates those helpers name, and the Makefile puts it on the
  *      include path in front of the reference tree.  The driver never calls the helpers.
@@ -24,9 +29,11 @@
  *      encoders/lz4.hpp:103-113 (prefs), encoders/lz4_utils.hpp:99-173 (encode_serial),
  *      :193-274 (encode_parallel).
  *
- * Still restated only (oracle/sqy_oracle.*): frame_shuffle and tile_shuffle (Boost.Accumulators), bitshuffle (its
- * library is not in the reference tree), the sqy header (Boost.PropertyTree) and with it the text form of the
- * quantiser's decode LUT.  The quantiser's LUTs themselves are the reference's (ref_quantiser_* below).
+ * Still restated only (oracle/sqy_oracle.*): bitshuffle (its library is not in the reference tree), the sqy header
+ * (Boost.PropertyTree) and with it the text form of the quantiser's decode LUT and of the shuffles' reorder_map, and the
+ * remainder / median path of frame_shuffle and tile_shuffle (refused by oracle and product, never run here).  The quantiser's
+ * LUTs themselves are the reference's (ref_quantiser_* below), and so are the metric, the order and the decode_map of
+ * frame_shuffle and tile_shuffle on whole units (ref_frame_shuffle_* / ref_tile_shuffle_* below).
  */
 #include <cstddef>
 #include <cstdint>
@@ -56,6 +63,8 @@
 #include "encoders/sse_utils.hpp"
 #include "encoders/bitplane_reorder_sse.hpp"
 #include "encoders/quantiser_utils.hpp"         /* its "string_parsers.hpp" is oracle/ref_shim/'s */
+#include "encoders/frame_shuffle_utils.hpp"     /* their <boost/accumulators/...> are oracle/boost_standin/'s */
+#include "encoders/tile_shuffle_utils.hpp"
 
 #include "lz4.h"
 #include "lz4frame.h"
@@ -287,6 +296,109 @@ int quantiser_run(const std::uint16_t* in, std::size_t n, int mode, int a, int b
     return 0;
 }
 
+/* frame_shuffle and tile_shuffle.  What the entry points answer besides 0, 1 (the reference did not reach the end of its output) and 2
+ * (it threw): */
+enum {
+    REF_REMAINDER = 4,     /* the shape is no whole number of units: the reference would take encode_with_remainder, the median path.  Worked
+                              out HERE, before anything of the reference runs: the stand-in median behind that path must stay unreachable */
+    REF_BAD_MAP = 5        /* decode: the map has another length than the shape has units, or names a unit the shape does not have (the
+                              reference would read or write behind its buffers); encode: the caller's map has no room */
+};
+
+inline bool frame_remainder(const std::size_t* zyx, std::size_t chunk) { return zyx[0] % chunk != 0; }
+
+inline bool tile_remainder(const std::size_t* zyx, std::size_t tile)
+{
+    for (int d = 0; d < 3; ++d)
+        if (zyx[d] < tile || zyx[d] % tile) return true;       /* an axis shorter than the tile is all remainder */
+    return false;
+}
+
+inline std::size_t frame_units(const std::size_t* zyx, std::size_t chunk) { return zyx[0] / chunk; }
+inline std::size_t tile_units(const std::size_t* zyx, std::size_t tile) { return (zyx[0] / tile) * (zyx[1] / tile) * (zyx[2] / tile); }
+
+inline bool map_fits(const std::size_t* map, std::size_t n_map, std::size_t units)
+{
+    if (n_map != units) return false;
+    for (std::size_t i = 0; i < n_map; ++i)
+        if (map[i] >= units) return false;
+    return true;
+}
+
+/* frame_shuffle_scheme::encode (encoders/frame_shuffle_scheme_impl.hpp:74-93): a detail::frame_shuffle of frame_chunk_size, its encode
+ * over the whole volume with the scheme's thread count, and its decode_map, which the scheme then writes into its config as text (:89;
+ * that text form stays with the oracle).  The metric (float std::accumulate over a unit, divided by the size_t voxel count), std::sort and
+ * std::find all run inside the reference (frame_shuffle_utils.hpp:92-172). */
+template <typename T>
+int frame_shuffle_encode(const T* in, T* out, const std::size_t* zyx, std::size_t chunk, int nthreads, std::size_t* map, std::size_t map_cap)
+{
+    if (!chunk || !voxels(zyx)) return 1;
+    if (frame_remainder(zyx, chunk)) return REF_REMAINDER;
+    if (map_cap < frame_units(zyx, chunk)) return REF_BAD_MAP;
+    const shape_t shape(zyx, zyx + 3);
+    const std::size_t n = voxels(zyx);
+    sqeazy::detail::frame_shuffle frames_of(chunk);
+    const T* stop = frames_of.encode(in, in + n, out, shape, nthreads);
+    if (frames_of.decode_map.size() != frame_units(zyx, chunk)) return 1;
+    std::copy(frames_of.decode_map.begin(), frames_of.decode_map.end(), map);
+    return stop == out + n ? 0 : 1;
+}
+
+/* frame_shuffle_scheme::decode (:95-120): a detail::frame_shuffle of frame_chunk_size and the map read back from the config, its decode
+ * over the whole volume; SUCCESS when it reports the end of the output.
+ * THE DRIVER'S CHOICE, NOT THE REFERENCE'S: `out` is zero-filled first.  The reference copies unit i to slot decode_map[i] and touches
+ * nothing else (frame_shuffle_utils.hpp:337-344), so a slot that no map entry names -- every map of an encode with equal metrics has
+ * such slots -- keeps whatever the caller's buffer held.  Oracle and product make those slots zero; zero-filling here makes the
+ * reference's result a function of payload and map alone, so that the three can be compared. */
+template <typename T>
+int frame_shuffle_decode(const T* in, T* out, const std::size_t* zyx, std::size_t chunk, const std::size_t* map, std::size_t n_map, int nthreads)
+{
+    if (!chunk || !voxels(zyx)) return 1;
+    if (frame_remainder(zyx, chunk)) return REF_REMAINDER;
+    if (!map_fits(map, n_map, frame_units(zyx, chunk))) return REF_BAD_MAP;
+    const shape_t shape(zyx, zyx + 3);
+    const std::size_t n = voxels(zyx);
+    std::memset(out, 0, n * sizeof(T));
+    const sqeazy::detail::frame_shuffle frames_of(chunk, std::vector<std::size_t>(map, map + n_map));
+    const T* stop = frames_of.decode(in, in + n, out, shape, nthreads);
+    return stop == out + n ? 0 : 1;
+}
+
+/* tile_shuffle_scheme::encode (encoders/tile_shuffle_scheme_impl.hpp:74-93): the same with a detail::tile_shuffle of tile_size.  The
+ * tiles, the float std::accumulate over each, the quotient stored INTO THE VOXEL TYPE, std::sort and std::find are the reference's
+ * (tile_shuffle_utils.hpp:104-213). */
+template <typename T>
+int tile_shuffle_encode(const T* in, T* out, const std::size_t* zyx, std::size_t tile, int nthreads, std::size_t* map, std::size_t map_cap)
+{
+    if (!tile || !voxels(zyx)) return 1;
+    if (tile_remainder(zyx, tile)) return REF_REMAINDER;
+    if (map_cap < tile_units(zyx, tile)) return REF_BAD_MAP;
+    const shape_t shape(zyx, zyx + 3);
+    const std::size_t n = voxels(zyx);
+    sqeazy::detail::tile_shuffle tiles_of(tile);
+    const T* stop = tiles_of.encode(in, in + n, out, shape, nthreads);
+    if (tiles_of.decode_map.size() != tile_units(zyx, tile)) return 1;
+    std::copy(tiles_of.decode_map.begin(), tiles_of.decode_map.end(), map);
+    return stop == out + n ? 0 : 1;
+}
+
+/* tile_shuffle_scheme::decode (:95-120).  The zero fill is again THE DRIVER'S CHOICE, kept for symmetry with frame_shuffle: this decode
+ * of the reference writes every voxel of the output from tiles that start out as zeros (tile_shuffle_utils.hpp:466, :529-557), so here a
+ * slot nobody names is zero in the reference too. */
+template <typename T>
+int tile_shuffle_decode(const T* in, T* out, const std::size_t* zyx, std::size_t tile, const std::size_t* map, std::size_t n_map, int nthreads)
+{
+    if (!tile || !voxels(zyx)) return 1;
+    if (tile_remainder(zyx, tile)) return REF_REMAINDER;
+    if (!map_fits(map, n_map, tile_units(zyx, tile))) return REF_BAD_MAP;
+    const shape_t shape(zyx, zyx + 3);
+    const std::size_t n = voxels(zyx);
+    std::memset(out, 0, n * sizeof(T));
+    const sqeazy::detail::tile_shuffle tiles_of(tile, std::vector<std::size_t>(map, map + n_map));
+    const T* stop = tiles_of.decode(in, in + n, out, shape, nthreads);
+    return stop == out + n ? 0 : 1;
+}
+
 } /* namespace */
 
 extern "C" {
@@ -375,6 +487,34 @@ int ref_quantiser_luts(const uint16_t* in, size_t n, int mode, int a, int b, int
 int ref_quantiser_encode(const uint16_t* in, size_t n, int mode, int a, int b, int nthreads, uint8_t* codes, uint16_t* lut_decode)
 {
     REF_GUARD(quantiser_run(in, n, mode, a, b, nthreads, nullptr, lut_decode, codes))
+}
+
+/* frame_shuffle / tile_shuffle on whole units.  dtype as above (2: the `char` form behind a sink).  `map` takes the decode_map, one size_t
+ * per unit (Z / frame_chunk_size, or the tiles of the volume); 4 for a shape with a remainder -- the reference is not run on it --, 5 for a
+ * map that does not fit the shape. */
+#define REF_BY_DTYPE(fn, ...) REF_GUARD(dtype == 1 ? fn((const uint16_t*)in, (uint16_t*)out, __VA_ARGS__) \
+                                      : dtype == 0 ? fn((const uint8_t*)in, (uint8_t*)out, __VA_ARGS__)   \
+                                                   : fn((const char*)in, (char*)out, __VA_ARGS__))
+
+int ref_frame_shuffle_encode(int dtype, const void* in, void* out, const size_t* shape, size_t frame_chunk_size, int nthreads, size_t* map, size_t map_cap)
+{
+    REF_BY_DTYPE(frame_shuffle_encode, shape, frame_chunk_size, nthreads, map, map_cap)
+}
+
+/* `out` is zero-filled before the reference writes to it: see frame_shuffle_decode above */
+int ref_frame_shuffle_decode(int dtype, const void* in, void* out, const size_t* shape, size_t frame_chunk_size, const size_t* map, size_t n_map, int nthreads)
+{
+    REF_BY_DTYPE(frame_shuffle_decode, shape, frame_chunk_size, map, n_map, nthreads)
+}
+
+int ref_tile_shuffle_encode(int dtype, const void* in, void* out, const size_t* shape, size_t tile_size, int nthreads, size_t* map, size_t map_cap)
+{
+    REF_BY_DTYPE(tile_shuffle_encode, shape, tile_size, nthreads, map, map_cap)
+}
+
+int ref_tile_shuffle_decode(int dtype, const void* in, void* out, const size_t* shape, size_t tile_size, const size_t* map, size_t n_map, int nthreads)
+{
+    REF_BY_DTYPE(tile_shuffle_decode, shape, tile_size, map, n_map, nthreads)
 }
 
 static LZ4F_preferences_t make_prefs(int accel, int blocksize_id)

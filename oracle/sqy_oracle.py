@@ -468,6 +468,9 @@ def tile_shuffle_encode(a, tile_size=32, char=False):
     order of the sorted metrics, slot i taking the FIRST tile whose metric equals sorted[i] (tiles with equal metrics all map
     to the first of them).  Shapes with a remainder take the reference's encode_with_remainder (Boost P^2 median over tiles
     read past their end, a thread-timing dependent map): not restated.  returns (volume-shaped output, decode_map)
+    Pinned: on whole tiles this is held against the reference's own detail::tile_shuffle compiled in place (oracle/ref.py
+    tile_shuffle_encode; tests/test_oracle_reference_shuffles.py, tests/golden/ref_shuffles.json), as frame_shuffle_encode and the
+    two decodes are against theirs.
     char=True: the tail filter form, tile_shuffle_scheme<char> on the sink's stream -- the sum adds SIGNED bytes and the metric is a
     (signed) char: `in_value_t` is char in :176-190, the float quotient converts to it by truncation and std::sort orders chars."""
     a = np.ascontiguousarray(a)
@@ -569,6 +572,20 @@ def frame_shuffle_encode(a, char=False, chunk=1):
     if rc:
         raise MemoryError
     return out, dmap
+
+
+def frame_shuffle_decode(a, dmap, chunk=1):
+    """detail::frame_shuffle::decode_with_remainder (frame_shuffle_utils.hpp:313-358) on whole units: encoded unit i goes to slot
+    decode_map[i], in the order of i (a later i wins).  Frames with equal metrics: the map names one unit several times and others not at
+    all -- those the reference leaves as its output buffer had them (:337-344); here, and in the product, they are zeros."""
+    a = np.ascontiguousarray(a)
+    if a.ndim != 3 or chunk < 1 or a.shape[0] % chunk:
+        raise ValueError("frame_shuffle: frame_chunk_size does not divide the frames")
+    units = a.reshape(a.shape[0] // chunk, -1)                             # frame_chunk_size frames per sort unit
+    out = np.zeros_like(units)
+    for i, t in enumerate(np.asarray(dmap).astype(np.int64).tolist()):
+        out[t] = units[i]
+    return out.reshape(a.shape)
 
 
 def base64_encode(raw):
@@ -981,14 +998,7 @@ def pipeline_decode(blob):
                 v = tail_view(cur)
             else:
                 v = np.ascontiguousarray(cur).view(dtype).reshape(h["shape"])
-            # (frames with equal metrics: the map names one frame several times and others not at all -- those the reference leaves as
-            # its output buffer had them, frame_shuffle_utils.hpp:337-344; here, and in the product, they are zeros)
-            if v.shape[0] % s.chunk:
-                raise ValueError("frame_shuffle: frame_chunk_size does not divide the frames")
-            units = v.reshape(v.shape[0] // s.chunk, -1)                       # frame_chunk_size frames per sort unit
-            out = np.zeros_like(units)
-            out[dmap.astype(np.int64)] = units
-            cur = out.reshape(v.shape)
+            cur = frame_shuffle_decode(v, dmap, s.chunk)
         else:
             raise NotImplementedError(s.name)
     return np.ascontiguousarray(cur).view(dtype).reshape(h["shape"])

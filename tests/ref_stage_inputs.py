@@ -1,5 +1,6 @@
-"""Inputs of the stage cases of tests/golden/ref_stages.json, regenerated from their seeds.  numpy only: the GPU test that holds the
-product against the reference's goldens imports this and nothing of the oracle."""
+"""Inputs of the stage cases of tests/golden/ref_stages.json and of the frame_shuffle / tile_shuffle cases of
+tests/golden/ref_shuffles.json, regenerated from their seeds.  numpy only: the GPU tests that hold the product against the reference's
+goldens import this and nothing of the oracle."""
 import numpy as np
 
 
@@ -52,6 +53,127 @@ def stage_tile(case):
     """tile_size of a reorder case; None in the table means the stage's default, 16 / sizeof(T)"""
     ts = case["params"].get("tile_size")
     return ts if ts else 16 // np.dtype(np_dtype(case["dtype"])).itemsize
+
+
+# ---- frame_shuffle / tile_shuffle: tests/golden/ref_shuffles.json ---------------------------------------------------------------------
+# A volume is built unit by unit -- a unit is what the stage sorts: frame_chunk_size frames, or one tile -- so that a kind can say what
+# the units' metrics do.  Values are made as int64 inside the voxel type's range; dtype "char" (the tail-filter form) is signed and travels
+# as the uint8 array of the same bytes.
+TWO24 = 1 << 24
+
+
+def tiles_to_volume(tiles, shape, ts):
+    """tiles (ntiles, ts^3) in (z, y, x) tile order, row-major inside a tile -> the volume they are cut from"""
+    z, y, x = shape
+    return np.ascontiguousarray(tiles.reshape(z // ts, y // ts, x // ts, ts, ts, ts).transpose(0, 3, 1, 4, 2, 5).reshape(shape))
+
+
+def _with_sum(rng, per, total, lo, hi):
+    """`per` small values in [lo, hi] that add up to `total` (|total| <= per): zeros, |total| ones of its sign, and a few +2 / -2 pairs"""
+    v = np.zeros(per, np.int64)
+    at = rng.permutation(per)
+    v[at[:abs(total)]] = 1 if total > 0 else -1
+    free = at[abs(total):]
+    pairs = min(len(free) // 2, 3)
+    if lo <= -2 and hi >= 2:
+        v[free[:pairs]] = 2
+        v[free[pairs:2 * pairs]] = -2
+    assert int(v.sum()) == total
+    return v
+
+
+def shuffle_units(kind, dtype, units, per, seed):
+    """(units, per) int64 values of a kind; dtype is the case's name for it ("uint16", "uint8", "char")"""
+    rng = np.random.default_rng(seed)
+    lo, hi = (-128, 127) if dtype == "char" else (0, int(np.iinfo(np_dtype(dtype)).max))
+    span = hi - lo + 1
+    if kind == "random":                                   # full range
+        return rng.integers(lo, hi + 1, (units, per))
+    if kind == "ramp":
+        return lo + (np.arange(units * per) % span).reshape(units, per)
+    if kind == "descending":                               # every unit's values lie below those of the unit in front of it
+        w = max(span // units, 1)
+        base = np.maximum(hi + 1 - w * (1 + np.arange(units)), lo)
+        return base[:, None] + rng.integers(0, w, (units, per))
+    if kind == "all_equal":                                # one unit, repeated: every metric ties, the map is all zeros
+        return np.tile(rng.integers(lo, hi + 1, per), (units, 1))
+    if kind == "two_groups":                               # A B A B ...: B lies below A, so the map is all 1s, then all 0s
+        a, b = rng.integers(lo + span // 2, hi + 1, per), rng.integers(lo, lo + span // 2, per)
+        return np.stack([a if u % 2 == 0 else b for u in range(units)])
+    if kind == "permuted":                                 # even units: the same voxels in another order, sums below 2^24 -- equal in metric
+        top = min(hi, max(TWO24 // per - 1, 1))            # whatever the order of the additions, and different in content
+        base = rng.integers(max(lo, -top), top + 1, per)
+        return np.stack([rng.permutation(base) if u % 2 == 0 else rng.integers(max(lo, -top), top + 1, per) for u in range(units)])
+    if kind == "pm128":                                    # bytes around +-128 when read as `char`: 120 .. 127 and -128 .. -120
+        return (rng.integers(120, 137, (units, per)) + 128) % 256 - 128
+    if kind == "neg_means":                                # signed: every unit's mean is negative, the means differ
+        return np.stack([rng.integers(-128, -(u * 5 % 60), per) for u in range(units)])
+    if kind == "extremes":                                 # signed: means of exactly -128, 127 and 0, each more than once, and noise
+        rows = [np.full(per, -128), np.full(per, 127), np.zeros(per, np.int64), None]
+        return np.stack([rows[u % 4] if rows[u % 4] is not None else rng.integers(-128, 128, per) for u in range(units)])
+    if kind == "fraction":                                 # tiles: means m + j / per with m one of two integers: they differ in the fraction only,
+        out = np.empty((units, per), np.int64)             # truncate to m or m + 1, and every tile takes the first of its group
+        for u in range(units):
+            out[u] = 100 + (u % 3 == 2)
+            out[u, rng.permutation(per)[:(u * 7 + 1) % per]] += 1
+        return out
+    if kind == "integer_edge":                             # tiles: even units sum to m * per - 1 (truncates to m - 1), odd ones to m * per; m grows
+        out = np.empty((units, per), np.int64)             # by one per pair, so an even unit ties with the odd unit in front of it
+        for u in range(units):
+            m = 50 + u // 2
+            out[u] = m
+            at = rng.permutation(per)
+            pairs = per // 4
+            out[u, at[:pairs]] += 1
+            out[u, at[pairs:2 * pairs]] -= 1
+            if u % 2 == 0:
+                out[u, at[-1]] -= 1
+        return out
+    if kind == "trunc_zero":                               # signed tiles: sums in (-per, 0), 0, in (0, per) -- all truncate toward zero and tie --
+        out = np.empty((units, per), np.int64)             # and sums of exactly -per and per, which do not
+        for u in range(units):
+            k = 1 + (u * 3) % (per - 1)
+            out[u] = (_with_sum(rng, per, -k, lo, hi), np.zeros(per, np.int64), _with_sum(rng, per, k, lo, hi), np.full(per, -1), np.full(per, 1))[u % 5]
+        return out
+    raise KeyError(kind)
+
+
+def shuffle_param(case):
+    return case["frame_chunk_size"] if case["stage"] == "frame_shuffle" else case["tile_size"]
+
+
+def shuffle_whole(case):
+    """True when the shape is a whole number of units: every other shape is refused"""
+    z, y, x = case["shape"]
+    p = shuffle_param(case)
+    return z % p == 0 if case["stage"] == "frame_shuffle" else all(d >= p and d % p == 0 for d in (z, y, x))
+
+
+def shuffle_volume(case):
+    """the volume of a case of ref_shuffles.json.  A shape with a remainder is built frame by frame: it has no units"""
+    shape = tuple(case["shape"])
+    z, y, x = shape
+    p = shuffle_param(case)
+    if case["stage"] == "tile_shuffle" and shuffle_whole(case):
+        v = tiles_to_volume(shuffle_units(case["kind"], case["dtype"], (z // p) * (y // p) * (x // p), p ** 3, case["seed"]), shape, p)
+    else:
+        chunk = p if shuffle_whole(case) else 1
+        v = shuffle_units(case["kind"], case["dtype"], z // chunk, chunk * y * x, case["seed"]).reshape(shape)
+    return v.astype(np.int8).view(np.uint8) if case["dtype"] == "char" else v.astype(np_dtype(case["dtype"]))
+
+
+def shuffle_case_id(case, index):
+    return "%s-%s-%s-%s-p%d-%03d" % (case["stage"], case["dtype"], "x".join(str(d) for d in case["shape"]), case["kind"], shuffle_param(case), index)
+
+
+def load_shuffle_cases(path):
+    """(_meta, cases, expected maps of tests/frame_metric_cases.py by name) of tests/golden/ref_shuffles.json"""
+    import json
+    with open(path) as f:
+        gold = json.load(f)
+    for i, c in enumerate(gold["cases"]):
+        c["id"] = shuffle_case_id(c, i)
+    return gold["_meta"], gold["cases"], gold["frame_metric_cases"]
 
 
 def case_id(case, index):

@@ -2,6 +2,7 @@
 // UndefinedBehaviorSanitizer, on the CPU.  tests/test_oracle_reference_stages_san.py writes the table's inputs with
 // oracle.gen_golden.dump_stage_cases (cases.txt + <index>.bin) and runs this on the directory: every case the goldens were taken from
 // runs with 1 and 3 threads (1 only where the table says so), the two outputs must be equal, and the lossless stages must decode back.
+// Behind them come the cases of tests/golden/ref_shuffles.json (frame_shuffle, tile_shuffle; see shuffle_case below), in the same format.
 // The same directory holds two volumes of tests/quantiser_cases.py (quantiser.txt: name and voxel count per line, quantiser_<index>.bin):
 // the reference's quantiser builds its LUTs from them and encodes them, with the default weighting and both weighting functors, 1 and 3
 // threads; the tables must not depend on the thread count and every code must be the encode LUT's entry of its voxel.
@@ -25,6 +26,10 @@ int ref_bitswap1(int dtype, const void* in, void* out, size_t len, int decode, i
 int ref_hist_stats(int dtype, const void* in, size_t n, uint32_t* bins, double* stats);
 int ref_quantiser_luts(const uint16_t* in, size_t n, int mode, int a, int b, int nthreads, uint8_t* lut_encode, uint16_t* lut_decode);
 int ref_quantiser_encode(const uint16_t* in, size_t n, int mode, int a, int b, int nthreads, uint8_t* codes, uint16_t* lut_decode);
+int ref_frame_shuffle_encode(int dtype, const void* in, void* out, const size_t* shape, size_t frame_chunk_size, int nthreads, size_t* map, size_t map_cap);
+int ref_frame_shuffle_decode(int dtype, const void* in, void* out, const size_t* shape, size_t frame_chunk_size, const size_t* map, size_t n_map, int nthreads);
+int ref_tile_shuffle_encode(int dtype, const void* in, void* out, const size_t* shape, size_t tile_size, int nthreads, size_t* map, size_t map_cap);
+int ref_tile_shuffle_decode(int dtype, const void* in, void* out, const size_t* shape, size_t tile_size, const size_t* map, size_t n_map, int nthreads);
 }
 
 namespace {
@@ -62,6 +67,34 @@ int run(const std::string& stage, int dt, const void* in, void* out, const size_
     if (stage == "raster_reorder") return ref_raster_reorder(dt, in, out, shape, (size_t)p0, decode, nthreads);
     if (stage == "bitswap1") return ref_bitswap1(dt, in, out, len, decode, nthreads);
     return -1;
+}
+
+// frame_shuffle / tile_shuffle, a case of tests/golden/ref_shuffles.json: p is frame_chunk_size or tile_size.  A case the table calls
+// refused must be answered with 4 (remainder) -- the stand-in median behind the reference's remainder path stops the program, so getting
+// here at all says it was not reached.  Every other case is encoded with 1 and 3 threads, output and map must be equal, and the decode
+// from that map must restore the input where the map is a permutation.  The map's buffer holds exactly one entry per unit.
+int shuffle_case(bool frames, int dt, const void* in, const size_t* shape, size_t bytes, size_t p, bool refused)
+{
+    const size_t units = !p ? 0 : frames ? shape[0] / p : (shape[0] / p) * (shape[1] / p) * (shape[2] / p);
+    buffer out1(bytes, 0), out3(bytes, 0), back(bytes, 0), map1(units * sizeof(size_t), 0), map3(units * sizeof(size_t), 0);
+    size_t* m1 = reinterpret_cast<size_t*>(map1.data());
+    size_t* m3 = reinterpret_cast<size_t*>(map3.data());
+    const auto encode = frames ? ref_frame_shuffle_encode : ref_tile_shuffle_encode;
+    const auto decode = frames ? ref_frame_shuffle_decode : ref_tile_shuffle_decode;
+    int rc = encode(dt, in, out1.data(), shape, p, 1, m1, units);
+    if (refused) return rc == 4 && encode(dt, in, out3.data(), shape, p, 3, m3, units) == 4 ? 0 : 30;
+    if (rc) return rc;
+    if ((rc = encode(dt, in, out3.data(), shape, p, 3, m3, units))) return rc;
+    if (std::memcmp(out1.data(), out3.data(), bytes) || std::memcmp(m1, m3, units * sizeof(size_t))) return 10;
+    std::memset(back.data(), 0xA5, bytes);                     // the driver zero-fills what the map does not name
+    if ((rc = decode(dt, out1.data(), back.data(), shape, p, m1, units, 1))) return rc;
+    std::vector<char> named(units, 0);
+    size_t distinct = 0;
+    for (size_t i = 0; i < units; ++i)
+        if (m1[i] >= units) return 31;
+        else if (!named[m1[i]]) { named[m1[i]] = 1; ++distinct; }
+    if (distinct == units && std::memcmp(back.data(), in, bytes)) return 11;
+    return 0;
 }
 
 // 0, or what went wrong with one volume under one weighting (mode 0: none, 1: power_of_a_b, 2: offset_power_of_a_b)
@@ -109,6 +142,11 @@ int main(int argc, char** argv)
             std::vector<uint32_t> bins(dt == 1 ? 65536 : 256);
             double stats[10];
             if (ref_hist_stats(dt, in.data(), len, bins.data(), stats)) { std::printf("FAILED %s\n", id.c_str()); ++bad; }
+            continue;
+        }
+        if (stage == "frame_shuffle" || stage == "tile_shuffle") {
+            const int rc = shuffle_case(stage == "frame_shuffle", dt, in.data(), shape, bytes, (size_t)p0, p1 != 0.0);
+            if (rc) { std::printf("FAILED %s rc=%d\n", id.c_str(), rc); ++bad; }
             continue;
         }
         buffer out1(bytes, 0), out3(bytes, 0), back(bytes, 0);

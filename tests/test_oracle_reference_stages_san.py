@@ -1,6 +1,7 @@
 """The reference driver over the whole stage case table under AddressSanitizer + UndefinedBehaviorSanitizer, on the CPU: a stand-alone
 program (tests/sanitize/ref_stages_san.cpp + oracle/ref_driver.cpp, built here with g++) that runs every case the goldens of
-tests/golden/ref_stages.json were taken from, with 1 and 3 threads, and the reference's quantiser on two volumes of
+tests/golden/ref_stages.json and tests/golden/ref_shuffles.json were taken from, with 1 and 3 threads (the refused shuffle shapes too: the
+driver must answer them without reaching the stand-in median), and the reference's quantiser on two volumes of
 tests/quantiser_cases.py (LUTs and codes, the default weighting and both weighting functors).  A case on which the reference reads or writes out of bounds is
 marked `undefined` in the table of oracle/gen_golden.py and is not among them.  Needs the reference tree: the program is built from it here.
 
