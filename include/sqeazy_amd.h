@@ -354,6 +354,39 @@ SQY_FUNCTION_PREFIX int SQYAMD_Decode_BatchWindow_UI8_Device(const void* d_src, 
                                                              const long* src_origins, void* const* d_dsts, const long* dst_shapes,
                                                              const long* dst_strides, unsigned shape_size, long* decoded_bytes,
                                                              void* hip_stream);
+/* The write of a box into a tiled store, whose border cuts through tiles: every tile under the box is read, modified and written again
+ * with ONE call.  Old blob i lies at d_src + src_offsets[i], src_lengths[i] bytes (host arrays; any alignment): a complete sqeazy blob of
+ * the entry point's voxel type, any pipeline, any layout.  Window i is the box [origins row i, + win_shapes row i) of that blob's volume
+ * (shape_size longs a row, outermost first, host arrays; origins NULL: all zeros); its new voxels are read from the view d_wins[i] /
+ * win_strides row i (d_wins: a HOST array of device pointers; strides in voxels, the view rules of _BatchStrided_*; NULL: dense views).
+ * Only the view's voxels are read.  New blob i is BYTE FOR BYTE what SQYAMD_PipelineEncode_*_Device(pipeline, .., nthreads) gives for the
+ * volume V_i = what SQYAMD_Decode_*_Device gives for old blob i, with the window's voxels replaced by the view's.  It is written into slot
+ * i of d_dst; slot layout, offsets, lengths and the capacity rule are exactly SQYAMD_PipelineEncode_Batch_*_Device's.  `pipeline` is the
+ * new blobs' pipeline and may differ from an old blob's.  A lossy old blob (quantiser) is RE-QUANTISED from its decoded voxels: that is
+ * the definition above, so voxels outside the window may change again.  The same old blob may be named several times in one call; each
+ * result is the old blob with its own window only.  Overlap of d_dst with the old blobs or the views is the caller's error.
+ * Checked before anything is written (else 1, offsets and lengths zeroed): everything _Batch_*_Device checks for the encode side; every
+ * blob entry (offset >= 0, length > 0); the view rules; the windows, against each blob's header: its rank equals shape_size, every
+ * origin >= 0, every extent >= 1, origin + extent <= the header's shape in every dimension (a sum that overflows is beyond it); the
+ * header's voxel type; the single call's geometry refusals for the blob's shape under `pipeline`.  Whatever needs no header is checked
+ * before a device is looked for.  A damaged old blob: SQY_Decode's composite code of the first damaged blob in blob order, offsets and
+ * lengths zeroed, nothing written to d_dst.  A blob that does not fit its slot: 1, the tables zeroed, as in the batch encode.  In every
+ * failure nothing is written outside [d_dst, d_dst + nblobs * slot_capacity).
+ * How: every old blob is decoded dense into a place of the workspace (the batch decode's groups), ONE launch pastes every window into
+ * its place, the batch encode reads the places (its groups and single-call fallbacks) -- a call holds a dense copy of every blob at
+ * once.  A `bitswap1->lz4` old blob on the batch decode's joint path that is written as joint-eligible `bitswap1->lz4` is never
+ * transposed back: its LZ4-decoded bit planes are patched with the window's voxels by one launch per encode group; such planes and
+ * the volumes of old `lz4` blobs are LZ4-decoded straight into their places where a decode group holds nothing else
+ * ("batch_update_fused" = 0: the dense way for every blob -- same bytes).  Stream, context, ordering and thread safety as
+ * _Batch_*_Device: the work runs behind what is queued on hip_stream and is complete on return; safe from several host threads. */
+SQY_FUNCTION_PREFIX int SQYAMD_Update_BatchWindow_UI16_Device(const char* pipeline, const void* d_src, const long* src_offsets, const long* src_lengths,
+                                                              int nblobs, const long* origins, const void* const* d_wins, const long* win_shapes,
+                                                              const long* win_strides, unsigned shape_size, void* d_dst, long slot_capacity, long* offsets,
+                                                              long* lengths, int nthreads, void* hip_stream);
+SQY_FUNCTION_PREFIX int SQYAMD_Update_BatchWindow_UI8_Device(const char* pipeline, const void* d_src, const long* src_offsets, const long* src_lengths,
+                                                             int nblobs, const long* origins, const void* const* d_wins, const long* win_shapes,
+                                                             const long* win_strides, unsigned shape_size, void* d_dst, long slot_capacity, long* offsets,
+                                                             long* lengths, int nthreads, void* hip_stream);
 /* host-pointer variants: blobs in host memory at src + offsets[i], dsts[i] host pointers (any alignment); arguments and headers are checked
  * on the host before any device is looked for */
 SQY_FUNCTION_PREFIX int SQYAMD_Decode_Batch_UI16(const char* src, const long* offsets, const long* lengths, int nblobs,
@@ -453,6 +486,10 @@ SQY_FUNCTION_PREFIX void SQYAMD_Release_Workspace(void);
  *   "batch_window_fused"              1 [SQY_NO_BATCH_WINDOW_FUSED=1 -> 0]  SQYAMD_Decode_BatchWindow_*: the inverse transposer stores only the window's
  *                                     voxels, `lz4` windows are copied out of the LZ4 output (0: every blob decoded dense into the workspace, one
  *                                     window copy at the end of the call -- same bytes)
+ *   "batch_update_fused"              1 [SQY_NO_BATCH_UPDATE_FUSED=1 -> 0]  SQYAMD_Update_BatchWindow_*: `bitswap1->lz4` blobs written as `bitswap1->lz4`
+ *                                     keep their bit planes, the window is patched into them; these and `lz4` blobs are LZ4-decoded straight
+ *                                     into their workspace places (0: every blob decoded dense into the workspace by the batch decode's
+ *                                     launches, one window paste, the batch encode -- same bytes)
  * Set: 0 = done, 1 = unknown name or value out of range.  Get: the value, -1 for an unknown name. */
 SQY_FUNCTION_PREFIX int SQYAMD_Set_Option(const char* name, long value);
 SQY_FUNCTION_PREFIX long SQYAMD_Get_Option(const char* name);

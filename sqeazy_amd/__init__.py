@@ -33,6 +33,7 @@ EXPORTED_SYMBOLS = (
     "SQYAMD_PipelineEncode_BatchPacked_UI16", "SQYAMD_PipelineEncode_BatchPacked_UI8",
     "SQYAMD_Decode_BatchStrided_UI16_Device", "SQYAMD_Decode_BatchStrided_UI8_Device",
     "SQYAMD_Decode_BatchWindow_UI16_Device", "SQYAMD_Decode_BatchWindow_UI8_Device",
+    "SQYAMD_Update_BatchWindow_UI16_Device", "SQYAMD_Update_BatchWindow_UI8_Device",
     "SQYAMD_PipelineEncode_UI16_Cap", "SQYAMD_PipelineEncode_UI8_Cap",
     "SQYAMD_Decode_UI16_Device", "SQYAMD_Decode_UI8_Device",
     "SQYAMD_Decode_Frames_UI16_Device", "SQYAMD_Decode_Frames_UI8_Device", "SQYAMD_Decode_Frames_UI16", "SQYAMD_Decode_Frames_UI8",
@@ -103,6 +104,9 @@ def lib():
         for f in ("SQYAMD_Decode_BatchWindow_UI8_Device", "SQYAMD_Decode_BatchWindow_UI16_Device"):
             getattr(L, f).argtypes = [ctypes.c_void_p, c_long_p, c_long_p, ctypes.c_int, c_long_p, ctypes.POINTER(ctypes.c_void_p), c_long_p, c_long_p,
                                       ctypes.c_uint, c_long_p, ctypes.c_void_p]
+        for f in ("SQYAMD_Update_BatchWindow_UI8_Device", "SQYAMD_Update_BatchWindow_UI16_Device"):
+            getattr(L, f).argtypes = [ctypes.c_char_p, ctypes.c_void_p, c_long_p, c_long_p, ctypes.c_int, c_long_p, ctypes.POINTER(ctypes.c_void_p), c_long_p, c_long_p,
+                                      ctypes.c_uint, ctypes.c_void_p, ctypes.c_long, c_long_p, c_long_p, ctypes.c_int, ctypes.c_void_p]
         for f in ("SQYAMD_PipelineEncode_Batch_UI8", "SQYAMD_PipelineEncode_Batch_UI16"):
             getattr(L, f).argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_void_p), c_long_p, ctypes.c_uint, ctypes.c_int, ctypes.c_void_p, ctypes.c_long,
                                       c_long_p, c_long_p, ctypes.c_int]
@@ -522,11 +526,30 @@ def decode_batch_window_device(d_src, offsets, lengths, origins, d_dsts, shapes,
     return rc, list(decoded[:n])
 
 
+def update_batch_window_device(pipeline, d_src, offsets, lengths, origins, d_wins, shapes, strides, dtype, d_dst, slot_capacity, nthreads=0, stream=None):
+    """SQYAMD_Update_BatchWindow_*_Device: old blob i at d_src + offsets[i] (lengths[i] bytes) is decoded, the window that begins at its voxel
+    origins[i] (None: at its first voxel) and has the extent shapes[i] is replaced by the strided view at device pointer d_wins[i] with
+    that shape and strides[i] in voxels (None: dense), and the result encoded with `pipeline` into slot i of d_dst (slot_capacity bytes
+    each) -- byte for byte the single call's blob.  Returns (rc, offsets, lengths), offsets relative to d_dst."""
+    n = len(offsets)
+    rank = len(shapes[0]) if n else 0
+    ptrs = (ctypes.c_void_p * max(n, 1))(*[p if p is None else int(p) for p in d_wins])
+    offs = (ctypes.c_long * max(n, 1))()
+    lens = (ctypes.c_long * max(n, 1))()
+    rc = getattr(lib(), "SQYAMD_Update_BatchWindow_%s_Device" % _suffix(dtype))(
+        pipeline.encode(), ctypes.c_void_p(int(d_src)), _longs(offsets) if n else None, _longs(lengths) if n else None, ctypes.c_int(n),
+        _longs([x for o in origins for x in o]) if n and origins is not None else None, ptrs, _longs([x for s in shapes for x in s]) if n else None,
+        _longs([x for s in strides for x in s]) if n and strides is not None else None, ctypes.c_uint(rank), ctypes.c_void_p(int(d_dst)),
+        ctypes.c_long(int(slot_capacity)), offs, lens, ctypes.c_int(nthreads), ctypes.c_void_p(stream or 0))
+    return rc, list(offs[:n]), list(lens[:n])
+
+
 def box_windows(shape, tile, box_origin, box_extent, dst_ptr, dst_strides, itemsize):
     """The read of the box [box_origin, box_origin + box_extent) of a parent of `shape` that is stored as the blobs of tile_views(.., shape,
     tile, ..) in that grid order, as the arguments of decode_batch_window_device: returns (tile_indices, origins, ptrs, shapes, strides) --
     the tiles the box intersects in ascending index order and for each one the window inside the tile (origin, shape) and the view that
     takes it inside a box buffer whose first voxel is at device pointer dst_ptr (ptr; strides = dst_strides, in voxels; None: a dense box).
+    The same table serves update_batch_window_device, the write of the box: the views then hold the tiles' new voxels.
     Pure Python.  ValueError: ranks that differ, a rank outside 1 to 3, a non-positive extent, a box outside the parent."""
     shape, tile, o, e = ([int(x) for x in v] for v in (shape, tile, box_origin, box_extent))
     rank = len(shape)

@@ -86,5 +86,29 @@ SQY_VIEW_HD inline uint64_t window_tile_count(const WindowGeometry& g, uint64_t 
     return ((g.oz + g.Z) * g.bY * g.bX - 1) / tile - window_first_tile(g, tile) + 1;
 }
 
+// ---- the update of a window in the bit-plane layout (SQYAMD_Update_BatchWindow_*) ----
+// A voxel has the same bit position in every plane: with W voxels to a plane word (16 for 16-bit voxels, 8 for 8-bit ones), plane
+// W - 1 - b, word w, bit W - 1 - k is bit b of voxel W w + k.  A run of 128 voxels that begins at a word is 16 bytes of every plane -- four
+// 32-bit words m[0..3] as they lie in memory, plane word i of the run at bit W i of them --, and ONE mask says which of those bits a
+// window replaces, whatever the plane.
+
+// the bits of the voxels [off, off + len) of the run (off + len <= 128), or-ed into m
+SQY_VIEW_HD inline void window_run_mask(uint32_t W, uint32_t off, uint32_t len, uint32_t m[4])
+{
+    for (uint32_t w = off / W; w * W < off + len; ++w) {
+        const uint32_t lo = off > w * W ? off - w * W : 0, hi = off + len < (w + 1) * W ? off + len - w * W : W;
+        // voxels [lo, hi) of word w: its bits [W - hi, W - lo)
+        const uint32_t bits = ((1u << (hi - lo)) - 1u) << (W - hi), at = w * W;             // (hi - lo <= W <= 16)
+        m[at >> 5] |= bits << (at & 31u);
+    }
+}
+
+// a piece of a plane (a plane word, or several side by side) with the window's bits replaced; `mask` is the same piece of the run's mask
+template <class T>
+SQY_VIEW_HD inline T window_merge_word(T old_bits, T new_bits, T mask)
+{
+    return (T)((old_bits & (T)~mask) | (new_bits & mask));
+}
+
 } // namespace sqy
 #endif

@@ -86,6 +86,7 @@ struct Options {
     std::atomic<long> encode_batch_joint_max_bytes;     // .. a volume with more LZ4 input than this is encoded on its own (frames in place)
     std::atomic<long> batch_strided_fused;              // strided views: the transposers gather from / scatter into the view, `lz4` packs into the stream and unpacks from the LZ4 output (0: packed copies everywhere)
     std::atomic<long> batch_window_fused;               // windows: the inverse transposer stores only the window's voxels, `lz4` windows are copied out of the LZ4 output (0: every blob decoded dense, one window copy)
+    std::atomic<long> batch_update_fused;               // window updates: `bitswap1->lz4` blobs written as `bitswap1->lz4` keep their planes, the window is patched into them; kept planes and `lz4` blobs are LZ4-decoded straight into their places (0: every blob decoded dense by the batch decode's launches, one paste)
     std::atomic<long> stage_lanes;                      // frames-in-place calls on caller streams run on the library's lanes: 0 never, 1 always, 2 where transpose_chain_caller_streams is on
     std::atomic<long> parse_lanes;                      // .. how many parse lanes a device has (1-8)
     // counters (Get reads, Set takes 0 only): calls that ran on the lanes; calls that stayed on their caller's stream because it had a
@@ -104,7 +105,8 @@ struct Options {
           decode_batch_group_bytes(env_number("SQY_DECODE_BATCH_GROUP_BYTES", (long)kSlabsGroupBytes, 1, (long)kSlabsGroupBytes)), encode_batch_joint(env_flag("SQY_NO_ENCODE_BATCH_JOINT") ? 0 : 1),
           encode_batch_group_bytes(env_number("SQY_ENCODE_BATCH_GROUP_BYTES", kBatchGroupBytesDefault, 1, kBatchBytesMax)),
           encode_batch_joint_max_bytes(env_number("SQY_ENCODE_BATCH_JOINT_MAX_BYTES", kBatchJointMaxDefault, 0, kBatchBytesMax)),
-          batch_strided_fused(env_flag("SQY_NO_BATCH_STRIDED_FUSED") ? 0 : 1), batch_window_fused(env_flag("SQY_NO_BATCH_WINDOW_FUSED") ? 0 : 1), stage_lanes(env_number("SQY_STAGE_LANES", kStageLanesDefault, 0, 2)),
+          batch_strided_fused(env_flag("SQY_NO_BATCH_STRIDED_FUSED") ? 0 : 1), batch_window_fused(env_flag("SQY_NO_BATCH_WINDOW_FUSED") ? 0 : 1),
+          batch_update_fused(env_flag("SQY_NO_BATCH_UPDATE_FUSED") ? 0 : 1), stage_lanes(env_number("SQY_STAGE_LANES", kStageLanesDefault, 0, 2)),
           parse_lanes(env_number("SQY_PARSE_LANES", kParseLanesDefault, 1, sqy::LanePicker::kMaxLanes)) { sqy::set_bitswap1_blocks_per_cu(transpose_blocks_per_cu.load()); }
     std::atomic<long>* find(const char* name)
     {
@@ -129,6 +131,7 @@ struct Options {
         if (!std::strcmp(name, "encode_batch_joint_max_bytes")) return &encode_batch_joint_max_bytes;
         if (!std::strcmp(name, "batch_strided_fused")) return &batch_strided_fused;
         if (!std::strcmp(name, "batch_window_fused")) return &batch_window_fused;
+        if (!std::strcmp(name, "batch_update_fused")) return &batch_update_fused;
         if (!std::strcmp(name, "stage_lanes")) return &stage_lanes;
         if (!std::strcmp(name, "parse_lanes")) return &parse_lanes;
         if (!std::strcmp(name, "lane_calls")) return &lane_calls;
@@ -336,7 +339,9 @@ struct Workspace {
     DevBuf batch_pack;        // strided views: the packed copies of a group's views (encode), the dense places of a call's views (decode)
     DevBuf batch_pack_one;    // .. decode: the dense place of a view whose blob is decoded on its own
     DevBuf batch_views[3];    // .. the job and tile tables of the view launches: pack / unpack, the strided transposer, the strided copy
-    DevBuf batch_windows[3];  // .. and of the window launches: the window copy, the windowed transposer, the copy out of the LZ4 output
+    DevBuf batch_windows[4];  // .. and of the window launches: the window copy, the windowed transposer, the copy out of the LZ4 output, the paste
+    DevBuf batch_update;      // window updates: every old blob's place (decoded dense, or its plane stream), on the 256-byte grid
+    DevBuf batch_patch_jobs;  // .. the job and tile tables of a group's patch launch
     DevBuf batch_places;      // packed batch encode: the places a group's placement scan leaves for the gather, behind them its gap table
     DevBuf batch_packed;      // .. a slot of max_compressed_length for every volume outside the joint forms, copied to its place at the end
     void* pinned = nullptr;   // 4 KiB of pinned host memory for small read-backs
@@ -347,6 +352,7 @@ struct Workspace {
         subset.release(); range_full.release(); slabs_index.release(); slabs_joint.release(); slabs_out.release(); slabs_host.release();
         batch_stream.release(); batch_scratch.release(); batch_tables.release(); batch_quant.release(); batch_host.release();
         batch_pack.release(); batch_pack_one.release(); for (DevBuf& b : batch_views) b.release(); for (DevBuf& b : batch_windows) b.release();
+        batch_update.release(); batch_patch_jobs.release();
         batch_places.release(); batch_packed.release();
     }
 };
@@ -2485,21 +2491,41 @@ WindowView window_view(const sqy::BatchWindow& w, const long* strides, unsigned 
     return WindowView{s[0], s[1]};
 }
 
-// ViewLaunch for window jobs (sqy::batch_window_layout); the same rule for `host`
-struct WindowLaunch {
-    enum Kind { copy, bitswap1_decode, copy_from_lz4 };
-    std::vector<sqy::BatchWindowJob> jobs;
+// ViewLaunch for jobs in the window launches' layout (sqy::batch_window_layout); the same rule for `host`
+template <class Job>
+struct TiledJobs {
+    std::vector<Job> jobs;
     std::vector<uint32_t> first_tile;
     uint32_t ntiles = 0;
     std::vector<unsigned char> host;
     hipStream_t queued_on = nullptr;
     bool queued = false;
-    WindowLaunch() = default;
-    WindowLaunch(const WindowLaunch&) = delete;
-    WindowLaunch& operator=(const WindowLaunch&) = delete;
-    ~WindowLaunch() { wait(); }
+    TiledJobs() = default;
+    TiledJobs(const TiledJobs&) = delete;
+    TiledJobs& operator=(const TiledJobs&) = delete;
+    ~TiledJobs() { wait(); }
     void wait() { if (queued) (void)hipStreamSynchronize(queued_on); queued = false; }
     void clear() { wait(); jobs.clear(); first_tile.clear(); ntiles = 0; host.clear(); }
+    // the tables to buf: the jobs at its start, *d_tiles the prefix sums behind them
+    int upload(hipStream_t stream, DevBuf& buf, const uint32_t** d_tiles)
+    {
+        const size_t nj = jobs.size();
+        const sqy::BatchWindowLayout lay = sqy::batch_window_layout(nj);
+        first_tile.push_back(ntiles);
+        host.assign(lay.total, 0);
+        std::memcpy(host.data(), jobs.data(), nj * sizeof(Job));
+        std::memcpy(host.data() + lay.tiles_at, first_tile.data(), (nj + 1) * 4);
+        if (buf.ensure(host.size())) return 1;
+        queued_on = stream;
+        queued = true;
+        SQY_HIP(hipMemcpyAsync(buf.p, host.data(), host.size(), hipMemcpyHostToDevice, stream));
+        *d_tiles = reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(buf.p) + lay.tiles_at);
+        return 0;
+    }
+};
+struct WindowLaunch : TiledJobs<sqy::BatchWindowJob> {
+    // paste (SQYAMD_Update_BatchWindow_*): the copy the other way round, the job's `dense` is written
+    enum Kind { copy, bitswap1_decode, copy_from_lz4, paste };
     // blob_tiles: the job is the windowed transposer's (the blob's tiles that reach into the window's frames), else the copy's (the
     // window's own tiles)
     void add(const void* view, const void* dense, const sqy::BatchWindow& w, const WindowView& v, bool blob_tiles)
@@ -2516,26 +2542,40 @@ int launch_windows(Context& cx, hipStream_t stream, WindowLaunch& l, WindowLaunc
 {
     if (l.jobs.empty()) return 0;
     std::vector<PendingEvent>* pend = &cx.pending;
-    const size_t nj = l.jobs.size();
-    const sqy::BatchWindowLayout lay = sqy::batch_window_layout(nj);
-    l.first_tile.push_back(l.ntiles);
-    l.host.assign(lay.total, 0);
-    std::memcpy(l.host.data(), l.jobs.data(), nj * sizeof(sqy::BatchWindowJob));
-    std::memcpy(l.host.data() + lay.tiles_at, l.first_tile.data(), (nj + 1) * 4);
+    const uint32_t nj = (uint32_t)l.jobs.size();
     DevBuf& buf = cx.ws.batch_windows[(int)kind];
-    if (buf.ensure(l.host.size())) return 1;
-    l.queued_on = stream;
-    l.queued = true;
-    SQY_HIP(hipMemcpyAsync(buf.p, l.host.data(), l.host.size(), hipMemcpyHostToDevice, stream));
+    const uint32_t* d_tiles = nullptr;
+    if (l.upload(stream, buf, &d_tiles)) return 1;
     const sqy::BatchWindowJob* d_jobs = static_cast<const sqy::BatchWindowJob*>(buf.p);
-    const uint32_t* d_tiles = reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(buf.p) + lay.tiles_at);
     switch (kind) {
-    case WindowLaunch::copy: SQY_TIMED("batch_window_copy", sqy::launch_batch_window_copy(d_jobs, d_tiles, (uint32_t)nj, l.ntiles, elem_size, stream)); break;
+    case WindowLaunch::copy: SQY_TIMED("batch_window_copy", sqy::launch_batch_window_copy(d_jobs, d_tiles, nj, l.ntiles, elem_size, stream)); break;
     case WindowLaunch::bitswap1_decode:
-        SQY_TIMED("batch_bitswap1_decode_window", sqy::launch_bitswap1_decode_batch_window(d_jobs, d_tiles, (uint32_t)nj, l.ntiles, elem_size, stream));
+        SQY_TIMED("batch_bitswap1_decode_window", sqy::launch_bitswap1_decode_batch_window(d_jobs, d_tiles, nj, l.ntiles, elem_size, stream));
         break;
-    case WindowLaunch::copy_from_lz4: SQY_TIMED("batch_copy_window", sqy::launch_batch_window_copy(d_jobs, d_tiles, (uint32_t)nj, l.ntiles, elem_size, stream)); break;
+    case WindowLaunch::copy_from_lz4: SQY_TIMED("batch_copy_window", sqy::launch_batch_window_copy(d_jobs, d_tiles, nj, l.ntiles, elem_size, stream)); break;
+    case WindowLaunch::paste: SQY_TIMED("batch_window_paste", sqy::launch_batch_window_paste(d_jobs, d_tiles, nj, l.ntiles, elem_size, stream)); break;
     }
+    return 0;
+}
+
+// the patch launch of a window update's encode group (layer two): old plane stream + the window's view -> the group's stream
+static_assert(sizeof(sqy::BatchPatchJob) == sqy::kBatchPatchJobBytes, "the patch job's layout");
+struct PatchLaunch : TiledJobs<sqy::BatchPatchJob> {
+    void add(const void* view, const void* old_stream, void* new_stream, const sqy::BatchWindow& w, const WindowView& v)
+    {
+        jobs.push_back(sqy::BatchPatchJob{view, old_stream, new_stream, w.Z, w.Y, w.X, v.sz, v.sy, w.bZ, w.bY, w.bX, w.oz, w.oy, w.ox});
+        first_tile.push_back(ntiles);
+        ntiles += sqy::batch_bitswap1_tiles(w.bZ * w.bY * w.bX);
+    }
+};
+int launch_patches(Context& cx, hipStream_t stream, PatchLaunch& l, int elem_size)
+{
+    if (l.jobs.empty()) return 0;
+    std::vector<PendingEvent>* pend = &cx.pending;
+    const uint32_t* d_tiles = nullptr;
+    if (l.upload(stream, cx.ws.batch_patch_jobs, &d_tiles)) return 1;
+    SQY_TIMED("batch_bitswap1_patch", sqy::launch_bitswap1_batch_patch(static_cast<const sqy::BatchPatchJob*>(cx.ws.batch_patch_jobs.p), d_tiles, (uint32_t)l.jobs.size(), l.ntiles,
+                                                                       elem_size, stream));
     return 0;
 }
 
@@ -2823,11 +2863,28 @@ int batch_group_tail(JointGroup& G, const sqy::DecodeJointLayout& L, const sqy::
     return 0;
 }
 
+// a window update's decode (SQYAMD_Update_BatchWindow_*, ud != nullptr): the headers have been fetched and checked (*ud->fetched, moved
+// from); a `bitswap1->lz4` blob b with (*ud->keep_planes)[b] is planned as DecodeBatchForm::plain -- its LZ4 output, the plane stream, is
+// what its destination gets -- and ud->patched[b] says whether it came out that way (sqy::update_blob_patched)
+// into_place[b]: blob b's LZ4 output is what its place holds; a group of such blobs only is decoded straight into the places (all in ONE
+// buffer: `places`, place_at[b] of places_bytes), with no launch behind the LZ4 decode (sqy::update_group_into_places)
+struct UpdateDecode {
+    const std::vector<uint8_t>* keep_planes;
+    std::vector<uint8_t> patched;
+    std::vector<SlabBlob>* fetched;
+    bool fused_on;
+    uint8_t* places;
+    const std::vector<uint64_t>* place_at;
+    uint64_t places_bytes;
+    std::vector<uint8_t> into_place;
+};
+
 // The joint path for group gi of a batch's plan (made from plan_in under the bound group_bytes).  Blobs it cannot take are appended to
 // `single`; the flag raised: all of the group go there.  Every destination is an allocation of its own, so the LZ4 output always goes to
 // the workspace, where the plan says (out_at); the pipelines without a batched launch run their remaining inverses as in a slab set.
 int decode_batch_group(Context& cx, const uint8_t* d_src, std::vector<SlabBlob>& blobs, const std::vector<sqy::DecodeBatchBlob>& plan_in, uint64_t group_bytes,
-                       const sqy::DecodeBatchPlan& plan, size_t gi, int elem_size, hipStream_t stream, std::vector<size_t>& single, StridedDecode* sv = nullptr)
+                       const sqy::DecodeBatchPlan& plan, size_t gi, int elem_size, hipStream_t stream, std::vector<size_t>& single, StridedDecode* sv = nullptr,
+                       const UpdateDecode* ud = nullptr)
 {
     if (sv) { sv->scatter.clear(); sv->copy.clear(); sv->wscatter.clear(); sv->wcopy.clear(); }     // (the group before has been synchronised)
     const sqy::DecodeBatchGroup* pg = &plan.groups[gi];
@@ -2845,13 +2902,22 @@ int decode_batch_group(Context& cx, const uint8_t* d_src, std::vector<SlabBlob>&
         again = sqy::decode_batch_plan(plan_in, group_bytes, &dropped);
         pg = &again.groups[gi];
     }
-    G.out_bytes = pg->out_bytes;
-    if (cx.ws.slabs_out.ensure(std::max<uint64_t>(G.out_bytes, 16))) return 1;
-    G.out = static_cast<uint8_t*>(cx.ws.slabs_out.p);
+    // a window update's group whose LZ4 outputs all are what their places hold: straight into the places, nothing behind the LZ4 decode
+    const bool into_places = ud && sqy::update_group_into_places(std::vector<uint32_t>(G.mem.begin(), G.mem.end()), ud->into_place);
+    if (into_places) {
+        for (size_t b : G.mem) blobs[b].out_base = (*ud->place_at)[b];
+        G.out_bytes = ud->places_bytes;
+        G.out = ud->places;
+    } else {
+        G.out_bytes = pg->out_bytes;
+        if (cx.ws.slabs_out.ensure(std::max<uint64_t>(G.out_bytes, 16))) return 1;
+        G.out = static_cast<uint8_t*>(cx.ws.slabs_out.p);
+    }
     const sqy::DecodeJointLayout L = sqy::decode_joint_layout(G.mem.size(), G.maps.size(), G.nframes, pg);
     if (const int rc = group_lz4_decode(G, L)) return rc;
     std::vector<unsigned char> tables;
-    if (const int rc = batch_group_tail(G, L, *pg, plan_in, elem_size, tables, sv)) return rc;
+    if (!into_places)
+        if (const int rc = batch_group_tail(G, L, *pg, plan_in, elem_size, tables, sv)) return rc;
     std::vector<size_t> rest;                                           // everything else: blob by blob, as in a slab set
     for (size_t b : G.mem) if (plan_in[b].form == sqy::DecodeBatchForm::stages) rest.push_back(b);
     if (const int rc = group_remaining_stages(G, rest)) return rc;
@@ -3034,7 +3100,8 @@ void batch_stage_form(SlabBlob& b, const void* dst, int want_elem, sqy::DecodeBa
 // wa->origins; a blob whose window is all of it is a view as above, and a call of such blobs only takes every path it takes there
 struct WindowArgs { const long* origins; const long* strides; };
 int decode_batch_on_device(Context& cx, const void* d_src_v, const BatchDecodeArgs& a, int want_elem, hipStream_t stream,
-                           const std::vector<sqy::BatchView>* views = nullptr, const long* shapes = nullptr, unsigned rank = 0, const WindowArgs* wa = nullptr)
+                           const std::vector<sqy::BatchView>* views = nullptr, const long* shapes = nullptr, unsigned rank = 0, const WindowArgs* wa = nullptr,
+                           UpdateDecode* ud = nullptr)
 {
     const uint8_t* d_src = static_cast<const uint8_t*>(d_src_v);
     StridedDecode sv;
@@ -3049,8 +3116,9 @@ int decode_batch_on_device(Context& cx, const void* d_src_v, const BatchDecodeAr
         blobs[i].src = d_src + a.offsets[i];
         blobs[i].len = (uint64_t)a.lengths[i];
     }
+    if (ud) blobs = std::move(*ud->fetched);
     // 1. the headers, checked before anything is written
-    if (fetch_blob_headers(cx, blobs, want_elem, stream, "decode batch", [&](int i) {
+    if (!ud && fetch_blob_headers(cx, blobs, want_elem, stream, "decode batch", [&](int i) {
             if (wa) {                                                   // (the view was admitted for the window's extent, aligned to the voxel size)
                 if (sqy::admit_window(blobs[i].h.shape, wa->origins ? wa->origins + (size_t)i * rank : nullptr, shapes + (size_t)i * rank, rank, &wins[(size_t)i])) return true;
                 std::fprintf(stderr, "[sqeazy]\t decode batch: blob %d's window does not lie inside its shape\n", i);
@@ -3123,6 +3191,10 @@ int decode_batch_on_device(Context& cx, const void* d_src_v, const BatchDecodeAr
             p.len = c.n;
         } else
             batch_stage_form(b, dst_of[i], want_elem, p);
+        if (ud) {
+            if ((ud->patched[i] = sqy::update_blob_patched((*ud->keep_planes)[i] != 0, p.form, true))) { p.form = sqy::DecodeBatchForm::plain; p.len = b.total; }
+            ud->into_place[i] = sqy::update_lz4_into_place(ud->fused_on, p.form);
+        }
         // (a view that was to take its voxels directly and has no such form after all: on its own, below)
         if (svp && sv.direct[i] && p.form != sqy::DecodeBatchForm::planes && p.form != sqy::DecodeBatchForm::plain) p.eligible = false;
     }
@@ -3130,10 +3202,11 @@ int decode_batch_on_device(Context& cx, const void* d_src_v, const BatchDecodeAr
     const sqy::DecodeBatchPlan plan = sqy::decode_batch_plan(plan_in, group_bytes);
     for (size_t i = 0; i < n; ++i) if (plan.group_of[i] < 0) single.push_back(i);
     for (size_t gi = 0; gi < plan.groups.size(); ++gi)
-        if (const int rc = decode_batch_group(cx, d_src, blobs, plan_in, group_bytes, plan, gi, want_elem, stream, single, svp)) return rc;
+        if (const int rc = decode_batch_group(cx, d_src, blobs, plan_in, group_bytes, plan, gi, want_elem, stream, single, svp, ud)) return rc;
     // 3. the others, one at a time, in blob order
     std::sort(single.begin(), single.end());
     for (size_t b : single) {
+        if (ud) ud->patched[b] = sqy::update_blob_patched((*ud->keep_planes)[b] != 0, sqy::DecodeBatchForm::planes, false);    // (decoded dense after all)
         if (!svp || !sv.direct[b]) {
             blobs[b].rc = decode_on_device(cx, blobs[b].src, blobs[b].len, dst_of[b], blobs[b].raw, want_elem, stream);
             continue;
@@ -3292,7 +3365,10 @@ int admit_batch(const char* pipeline, const void* const* srcs, const long* shape
 // one group of the plan through the kernels; rc 1 with a message when a blob does not fit its slot (nothing of that volume is written).
 // staging: pinned, sqy::encode_batch_layout's staging_bytes for the group at its worst-case text
 // views (nullptr: every volume dense) with how[vol], sqy ViewRead: how a volume that is no dense allocation is read
-enum ViewRead : uint8_t { in_place = 0, gathered, packed_to_stream, packed };
+// patched (SQYAMD_Update_BatchWindow_*): d_srcs[vol] is the volume's OLD plane stream; the group's patch launch makes the new one from it
+// and the window's view, in the transposer job's stead as `gathered` does
+enum ViewRead : uint8_t { in_place = 0, gathered, packed_to_stream, packed, patched };
+struct UpdateEncode { const std::vector<uint8_t>* is_patched; const void* const* views; const std::vector<sqy::BatchWindow>* wins; const std::vector<WindowView>* wviews; };
 // the packed layout (SQYAMD_PipelineEncode_BatchPacked_*) for one group: it begins at `base` of d_dst (a multiple of align), gaps[j]
 // (pinned, a word per volume of the group) is what the volumes outside the group take in front of its volume j, no blob may end behind
 // `capacity`.  The group leaves every volume's blob length in lens[vol] and whether it was written in placed[vol]; offsets and lengths
@@ -3300,7 +3376,8 @@ enum ViewRead : uint8_t { in_place = 0, gathered, packed_to_stream, packed };
 struct PackedGroup { uint64_t align, base, capacity; const uint64_t* gaps; uint64_t* lens; uint8_t* placed; };
 int encode_batch_group(Context& cx, const BatchAdmit& a, const sqy::Lz4BatchGroup& g, sqy::EncodeBatchForm form, int elem_size, const void* const* d_srcs,
                        uint8_t* d_dst, uint64_t slot_capacity, long* offsets, long* lengths, uint64_t* records, uint8_t* staging, hipStream_t stream,
-                       const std::vector<sqy::BatchView>* views = nullptr, const std::vector<uint8_t>* how = nullptr, const PackedGroup* pk = nullptr)
+                       const std::vector<sqy::BatchView>* views = nullptr, const std::vector<uint8_t>* how = nullptr, const PackedGroup* pk = nullptr,
+                       const UpdateEncode* up = nullptr)
 {
     Workspace* ws = &cx.ws;
     std::vector<PendingEvent>* pend = &cx.pending;
@@ -3346,6 +3423,7 @@ int encode_batch_group(Context& cx, const BatchAdmit& a, const sqy::Lz4BatchGrou
     uint8_t* const d_tab = static_cast<uint8_t*>(ws->batch_tables.p);
     uint8_t* const d_stream = transpose ? static_cast<uint8_t*>(ws->batch_stream.p) : nullptr;
     ViewLaunch packs, gathers;
+    PatchLaunch patches;
 
     sqy::Lz4BatchChunk* h_table = reinterpret_cast<sqy::Lz4BatchChunk*>(staging + L.table_at);
     uint32_t* h_volof = reinterpret_cast<uint32_t*>(staging + L.volof_at);
@@ -3385,6 +3463,8 @@ int encode_batch_group(Context& cx, const BatchAdmit& a, const sqy::Lz4BatchGrou
         }
         if (read == gathered)
             gathers.add(d_srcs[vol], d_stream + g.stream_at[j], (*views)[vol]);
+        else if (read == patched)
+            patches.add(up->views[vol], d_srcs[vol], d_stream + g.stream_at[j], (*up->wins)[vol], (*up->wviews)[vol]);
         else {
             h_jobs[njobs] = sqy::Bitswap1Job{src, d_stream ? d_stream + g.stream_at[j] : nullptr, a.len[vol]};
             h_tiles[njobs++] = ntiles;
@@ -3423,7 +3503,7 @@ int encode_batch_group(Context& cx, const BatchAdmit& a, const sqy::Lz4BatchGrou
         SQY_TIMED("batch_quantiser_bitswap1", sqy::launch_batch_quantiser_bitswap1(d_jobs, d_tiles, (uint32_t)nv, ntiles, d_luts, stream));
     } else if (transpose) {
         if (njobs) SQY_TIMED("batch_bitswap1", sqy::launch_bitswap1_batch(d_jobs, d_tiles, (uint32_t)njobs, ntiles, elem_size, stream));
-        if (launch_views(cx, stream, gathers, ViewLaunch::bitswap1, 1, elem_size)) return 1;
+        if (launch_views(cx, stream, gathers, ViewLaunch::bitswap1, 1, elem_size) || launch_patches(cx, stream, patches, elem_size)) return 1;
     }
     SQY_TIMED("batch_lz4_chunks", sqy::launch_lz4_chunks_table(d_stream, d_table, (uint32_t)nc, d_scratch, g.scratch_stride, d_csize, d_redo, stream));
     // round trip 1: how many entries the first pass left to the dense batches -- and, quantised, the decode LUTs the headers carry
@@ -3474,12 +3554,21 @@ int encode_batch_group(Context& cx, const BatchAdmit& a, const sqy::Lz4BatchGrou
     return rc;
 }
 
+// the groups of a batch under the options in force (pack_bytes: lz4_batch_plan_views'; empty: none)
+sqy::Lz4BatchPlan encode_batch_plan(const BatchAdmit& a, sqy::EncodeBatchForm form, int elem_size, const std::vector<uint64_t>& pack_bytes)
+{
+    std::vector<uint64_t> totals(a.len.size());
+    for (size_t i = 0; i < a.len.size(); ++i) totals[i] = sqy::encode_batch_stream_bytes(form, a.len[i], elem_size);
+    return sqy::lz4_batch_plan_views(a.pipe.stages.back().lz4, totals, pack_bytes, a.pipe.nthreads, (uint64_t)g_opt.encode_batch_group_bytes.load(),
+                                     (uint64_t)g_opt.encode_batch_joint_max_bytes.load(), sqy::encode_batch_extra_bytes(form));
+}
+
 // dense_to (SQYAMD_PipelineEncode_BatchPacked_*; nullptr: the slot layout): the blobs back to back in d_dst by sqy::packed_places' rule --
 // slot_capacity is then the capacity of all of d_dst, and *total what the blobs take (or, rc 1 and the blobs do not fit, what they would take)
 struct PackedArgs { uint64_t align; long* total; };
 int encode_batch_on_device(Context& cx, const char* pipeline, const BatchAdmit& a, const void* const* d_srcs, const long* shapes, unsigned rank, int elem_size,
                            int nvolumes, void* d_dst, uint64_t slot_capacity, long* offsets, long* lengths, int nthreads, hipStream_t stream,
-                           const std::vector<sqy::BatchView>* views = nullptr, const PackedArgs* dense_to = nullptr)
+                           const std::vector<sqy::BatchView>* views = nullptr, const PackedArgs* dense_to = nullptr, const UpdateEncode* up = nullptr)
 {
     for (int i = 0; i < nvolumes; ++i)
         if (reinterpret_cast<uintptr_t>(d_srcs[i]) % (uintptr_t)elem_size) { std::fprintf(stderr, "[sqeazy]\t volume %d: source not aligned to the voxel size\n", i); return 1; }
@@ -3500,13 +3589,15 @@ int encode_batch_on_device(Context& cx, const char* pipeline, const BatchAdmit& 
             if (how[i] == packed) pack_bytes[i] = (a.len[i] * (uint64_t)elem_size + 15) & ~(uint64_t)15;
         }
     }
-    if (form != sqy::EncodeBatchForm::none) {
-        std::vector<uint64_t> totals((size_t)nvolumes);
-        for (int i = 0; i < nvolumes; ++i) totals[(size_t)i] = sqy::encode_batch_stream_bytes(form, a.len[(size_t)i], elem_size);
-        plan = sqy::lz4_batch_plan_views(a.pipe.stages.back().lz4, totals, strided ? pack_bytes : std::vector<uint64_t>(), a.pipe.nthreads,
-                                         (uint64_t)g_opt.encode_batch_group_bytes.load(), (uint64_t)g_opt.encode_batch_joint_max_bytes.load(),
-                                         sqy::encode_batch_extra_bytes(form));
-    }
+    if (up)
+        for (size_t i = 0; i < (size_t)nvolumes; ++i)
+            if ((*up->is_patched)[i]) { how[i] = patched; strided = true; }
+    if (form != sqy::EncodeBatchForm::none) plan = encode_batch_plan(a, form, elem_size, strided ? pack_bytes : std::vector<uint64_t>());
+    for (size_t i = 0; i < (size_t)nvolumes; ++i)
+        if (how[i] == patched && (form != sqy::EncodeBatchForm::bitswap1_lz4 || plan.group_of[i] < 0)) {
+            std::fprintf(stderr, "[sqeazy]\t internal error: volume %zu kept its planes and has no group to patch them\n", i);
+            return 1;
+        }
     const size_t n = (size_t)nvolumes;
     int rc = 0;
     // the packed layout's state: every blob's length, whether a group wrote it, and for a volume outside the joint forms where its blob
@@ -3547,7 +3638,7 @@ int encode_batch_on_device(Context& cx, const char* pipeline, const BatchAdmit& 
             }
             if (encode_batch_group(cx, a, g, form, elem_size, d_srcs, static_cast<uint8_t*>(d_dst), slot_capacity, offsets, lengths, records,
                                    static_cast<uint8_t*>(cx.ws.batch_host.p) + records_bytes, stream, strided ? views : nullptr, strided ? &how : nullptr,
-                                   dense_to ? &pk : nullptr)) {
+                                   dense_to ? &pk : nullptr, up)) {
                 grc = 1;
                 if (dense_to) break;                                      // (the groups behind it would not know where they begin)
             }
@@ -3645,6 +3736,99 @@ int encode_batch_strided_device(const char* pipeline, const void* const* d_srcs,
     if (!lease.ctx) { std::fprintf(stderr, "[sqeazy]\t no usable HIP device\n"); return 1; }
     return encode_batch_on_device(*lease.ctx, pipeline, a, d_srcs, shapes, rank, elem_size, nvolumes, d_dst, (uint64_t)slot_capacity, offsets, lengths, nthreads,
                                   static_cast<hipStream_t>(hip_stream), strides ? &views : nullptr);
+}
+
+// ---- window update (SQYAMD_Update_BatchWindow_*) ------------------------------------------------------------------------------
+// New blob i = the single call's blob for (old blob i decoded, its window's voxels replaced by view i's), into slot i.  The batch decode
+// driver puts every old blob into its place of Workspace::batch_update (sqy::update_batch_plan), ONE paste launch writes the windows into
+// the places that hold voxels, the batch encode driver reads the places as its sources.  The places that hold planes (layer two,
+// sqy::update_blob_patched) are read by the encode groups' patch launches together with the views.  Nothing is written to d_dst before
+// every old blob has been decoded: a damaged one leaves it untouched.
+int update_batch_on_device(Context& cx, const char* pipeline, BatchAdmit& a, const void* d_src, const long* src_offsets, const long* src_lengths, int nblobs,
+                           const long* origins, const void* const* d_wins, const long* win_shapes, const long* win_strides, unsigned rank, int elem_size, void* d_dst,
+                           uint64_t slot_capacity, long* offsets, long* lengths, int nthreads, hipStream_t stream)
+{
+    const size_t n = (size_t)nblobs;
+    std::vector<SlabBlob> blobs(n);
+    for (size_t i = 0; i < n; ++i) {
+        blobs[i].src = static_cast<const uint8_t*>(d_src) + src_offsets[i];
+        blobs[i].len = (uint64_t)src_lengths[i];
+    }
+    // 1. the headers: the voxel type, the window inside the shape, the shape under the new pipeline -- before anything is written
+    std::vector<sqy::BatchWindow> wins(n);
+    std::vector<long> shapes(n * rank);
+    a.dims.resize(n);
+    a.len.resize(n);
+    {
+        DrainOnExit drain{stream, &cx.pending, cx.side};
+        if (fetch_blob_headers(cx, blobs, elem_size, stream, "update batch", [&](int i) {
+                if (!sqy::admit_window(blobs[i].h.shape, origins ? origins + (size_t)i * rank : nullptr, win_shapes + (size_t)i * rank, rank, &wins[(size_t)i])) {
+                    std::fprintf(stderr, "[sqeazy]\t update batch: blob %d's window does not lie inside its shape\n", i);
+                    return false;
+                }
+                for (unsigned k = 0; k < rank; ++k) shapes[(size_t)i * rank + k] = (long)blobs[i].h.shape[k];
+                return admit_shape(&a.pipe, shapes.data() + (size_t)i * rank, rank, &a.dims[(size_t)i], &a.len[(size_t)i]) == 0;
+            }))
+            return 1;
+    }
+    // 2. the plan (host-only, sqy_pipeline.cpp): which blobs keep their planes, every blob's place
+    const bool fused_on = g_opt.batch_update_fused.load() != 0 && g_opt.decode_batch_joint.load() != 0 && g_opt.encode_batch_joint.load() != 0;
+    const sqy::EncodeBatchForm form = g_opt.encode_batch_joint.load() ? sqy::encode_batch_form(a.pipe, elem_size) : sqy::EncodeBatchForm::none;
+    std::vector<int32_t> group_of(n, -1);
+    if (form != sqy::EncodeBatchForm::none) group_of = encode_batch_plan(a, form, elem_size, std::vector<uint64_t>()).group_of;
+    std::vector<uint64_t> raw(n);
+    for (size_t i = 0; i < n; ++i) raw[i] = blobs[i].raw;
+    const sqy::UpdateBatchPlan plan = sqy::update_batch_plan(raw, form, group_of, fused_on);
+    if (cx.ws.batch_update.ensure(std::max<uint64_t>(plan.bytes, 16))) return 1;
+    std::vector<void*> places(n);
+    std::vector<long> caps(n);
+    for (size_t i = 0; i < n; ++i) { places[i] = static_cast<uint8_t*>(cx.ws.batch_update.p) + plan.place_at[i]; caps[i] = (long)raw[i]; }
+    // 3. the old blobs, through the batch decode driver
+    UpdateDecode ud{&plan.keep_planes, std::vector<uint8_t>(n, 0), &blobs, fused_on, static_cast<uint8_t*>(cx.ws.batch_update.p), &plan.place_at, plan.bytes,
+                    std::vector<uint8_t>(n, 0)};
+    const BatchDecodeArgs d{src_offsets, src_lengths, nblobs, places.data(), caps.data(), nullptr};
+    if (const int rc = decode_batch_on_device(cx, d_src, d, elem_size, stream, nullptr, nullptr, 0, nullptr, &ud)) return rc;
+    // 4. the windows into the places that hold voxels: ONE launch
+    std::vector<WindowView> wviews(n);
+    WindowLaunch pastes;
+    for (size_t i = 0; i < n; ++i) {
+        wviews[i] = window_view(wins[i], win_strides ? win_strides + i * rank : nullptr, rank);
+        if (!ud.patched[i]) pastes.add(d_wins[i], places[i], wins[i], wviews[i], false);
+    }
+    {
+        DrainOnExit drain{stream, &cx.pending, cx.side};
+        if (launch_windows(cx, stream, pastes, WindowLaunch::paste, elem_size)) return 1;
+        pastes.wait();
+    }
+    // 5. the new blobs, through the batch encode driver
+    const UpdateEncode ue{&ud.patched, d_wins, &wins, &wviews};
+    return encode_batch_on_device(cx, pipeline, a, places.data(), shapes.data(), rank, elem_size, nblobs, d_dst, slot_capacity, offsets, lengths, nthreads, stream, nullptr,
+                                  nullptr, &ue);
+}
+
+// what needs no header, before a device is looked for; then the driver
+int update_batch_window_device(const char* pipeline, const void* d_src, const long* src_offsets, const long* src_lengths, int nblobs, const long* origins,
+                               const void* const* d_wins, const long* win_shapes, const long* win_strides, unsigned rank, int elem_size, void* d_dst, long slot_capacity,
+                               long* offsets, long* lengths, int nthreads, void* hip_stream)
+{
+    if (!offsets || !lengths) return 1;
+    for (int i = 0; i < nblobs; ++i) { offsets[i] = 0; lengths[i] = 0; }
+    if (!pipeline || !d_src || !src_offsets || !src_lengths || !d_wins || !win_shapes || !d_dst || nblobs <= 0 || slot_capacity <= 0) {
+        std::fprintf(stderr, "[sqeazy]\t update batch: bad arguments\n");
+        return 1;
+    }
+    BatchAdmit a;
+    if (admit_pipeline(pipeline, elem_size, nthreads, &a.pipe)) return 1;
+    for (int i = 0; i < nblobs; ++i)
+        if (!blob_entry_ok("update batch", i, src_offsets[i], src_lengths[i], d_wins[i] != nullptr)) return 1;
+    std::vector<sqy::BatchView> views;
+    if (admit_views("update batch", d_wins, win_shapes, win_strides, rank, nblobs, elem_size, &views)) return 1;
+    for (size_t k = 0; origins && k < (size_t)nblobs * rank; ++k)
+        if (origins[k] < 0) { std::fprintf(stderr, "[sqeazy]\t update batch: window %zu begins in front of its blob\n", k / rank); return 1; }
+    ContextLease lease;
+    if (!lease.ctx) { std::fprintf(stderr, "[sqeazy]\t no usable HIP device\n"); return 1; }
+    return update_batch_on_device(*lease.ctx, pipeline, a, d_src, src_offsets, src_lengths, nblobs, origins, d_wins, win_shapes, win_strides, rank, elem_size, d_dst,
+                                  (uint64_t)slot_capacity, offsets, lengths, nthreads, static_cast<hipStream_t>(hip_stream));
 }
 
 // the host-pointer variant (not tuned): every volume staged up, one call of the device driver, the blobs brought back
@@ -4291,6 +4475,26 @@ int SQYAMD_Decode_BatchWindow_UI8_Device(const void* d_src, const long* offsets,
 {
     return guarded([&]() -> int {
         return decode_batch_window_device(d_src, offsets, lengths, nblobs, src_origins, d_dsts, dst_shapes, dst_strides, shape_size, decoded_bytes, 1, hip_stream);
+    });
+}
+
+int SQYAMD_Update_BatchWindow_UI16_Device(const char* pipeline, const void* d_src, const long* src_offsets, const long* src_lengths, int nblobs, const long* origins,
+                                          const void* const* d_wins, const long* win_shapes, const long* win_strides, unsigned shape_size, void* d_dst, long slot_capacity,
+                                          long* offsets, long* lengths, int nthreads, void* hip_stream)
+{
+    return guarded([&]() -> int {
+        return update_batch_window_device(pipeline, d_src, src_offsets, src_lengths, nblobs, origins, d_wins, win_shapes, win_strides, shape_size, 2, d_dst, slot_capacity,
+                                          offsets, lengths, nthreads, hip_stream);
+    });
+}
+
+int SQYAMD_Update_BatchWindow_UI8_Device(const char* pipeline, const void* d_src, const long* src_offsets, const long* src_lengths, int nblobs, const long* origins,
+                                         const void* const* d_wins, const long* win_shapes, const long* win_strides, unsigned shape_size, void* d_dst, long slot_capacity,
+                                         long* offsets, long* lengths, int nthreads, void* hip_stream)
+{
+    return guarded([&]() -> int {
+        return update_batch_window_device(pipeline, d_src, src_offsets, src_lengths, nblobs, origins, d_wins, win_shapes, win_strides, shape_size, 1, d_dst, slot_capacity,
+                                          offsets, lengths, nthreads, hip_stream);
     });
 }
 

@@ -197,6 +197,16 @@ hipError_t launch_batch_window_copy(const BatchWindowJob* d_jobs, const uint32_t
 // (sqy::window_first_tile, window_tile_count); first_tile: the prefix sums of those counts
 hipError_t launch_bitswap1_decode_batch_window(const BatchWindowJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ntiles, int elem_size,
                                                hipStream_t stream);
+// ---- the update of a window (SQYAMD_Update_BatchWindow_*) ----
+// launch_batch_window_copy the other way round: the view's voxels are read and stored into the window inside the dense volume at `dense`
+// (written, whatever the job's type says); nothing else of it is touched
+hipError_t launch_batch_window_paste(const BatchWindowJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ntiles, int elem_size, hipStream_t stream);
+// Job j: the plane stream (planes + tail, launch_bitswap1_batch's layout) of a blob of bZ x bY x bX voxels at old_stream, the window of a
+// BatchWindowJob in it and the view that holds the window's new voxels.  new_stream (no overlap with old_stream) takes the plane stream of
+// the blob with the window's voxels replaced.  The streams at any voxel-aligned address (sixteen bytes at a time where both and the plane
+// size are on the 16-byte grid); first_tile: the prefix sums of batch_bitswap1_tiles(bZ bY bX)
+struct BatchPatchJob { const void* view; const void* old_stream; void* new_stream; uint64_t Z, Y, X, sz, sy, bZ, bY, bX, oz, oy, ox; };
+hipError_t launch_bitswap1_batch_patch(const BatchPatchJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ntiles, int elem_size, hipStream_t stream);
 
 // One entry of the joint chunk table (sqy::Lz4BatchChunkPlan, sqy_pipeline.hpp): chunk e is the n bytes at in + off, compressed on its
 // own into scratch + slot * stride, csize[e] (0: stored); redo as for launch_lz4_chunks (nentries + 1 words, the launcher zeroes redo[0])

@@ -8050,6 +8050,39 @@ void batch_window_copy_kernel(const BatchWindowJob* __restrict__ jobs, const uin
     }
 }
 
+// batch_window_copy_kernel the other way round (SQYAMD_Update_BatchWindow_*): the source is the caller's view, the destination the window
+// inside the blob's dense volume.  The same tiles, pieces and interleaving; a kernel of its own, so that one keeps its code.
+template <int ELEM>
+__global__ __launch_bounds__(256)
+void batch_window_paste_kernel(const BatchWindowJob* __restrict__ jobs, const uint32_t* __restrict__ first_tile, uint32_t njobs)
+{
+    constexpr uint32_t G = 16 / ELEM, PIECES = BSWB_TILE_VOX / G / 256u;      // voxels per piece, pieces per thread
+    const uint32_t j = batch_job_of_tile(first_tile, njobs);
+    const BatchWindowJob job = jobs[j];
+    const uint64_t len = job.Z * job.Y * job.X;
+    const uint64_t base = (uint64_t)(blockIdx.x - first_tile[j]) * BSWB_TILE_VOX;
+    const ViewGeometry gs{job.Y, job.X, job.sz, job.sy}, gd{job.Y, job.X, job.bY * job.bX, job.bX};
+    const uint8_t* view = static_cast<const uint8_t*>(job.view);
+    uint8_t* dst = static_cast<uint8_t*>(const_cast<void*>(job.dense)) + ((job.oz * job.bY + job.oy) * job.bX + job.ox) * ELEM;
+    for (uint32_t k = 0; k < PIECES; ++k) {
+        const uint64_t i0 = base + ((uint64_t)k * 256u + threadIdx.x) * G;
+        if (i0 >= len) return;
+        const uint32_t n = (uint32_t)(len - i0 < G ? len - i0 : G);
+        ViewWalk ws = view_walk_start(gs, i0), wd = view_walk_start(gd, i0);
+        const uint8_t* ps = view + ws.off * ELEM;
+        uint8_t* pd = dst + wd.off * ELEM;
+        if (n == G && wd.left >= G && ((reinterpret_cast<uintptr_t>(ps) | reinterpret_cast<uintptr_t>(pd)) & 15u) == 0) {
+            *reinterpret_cast<uint4*>(pd) = *reinterpret_cast<const uint4*>(ps);
+            continue;
+        }
+        for (uint32_t v = 0; v < n; ++v) {
+            view_voxel_store<ELEM>(dst, wd.off, view_voxel_load<ELEM>(view, ws.off));
+            view_walk_advance(gs, &ws, 1);
+            view_walk_advance(gd, &wd, 1);
+        }
+    }
+}
+
 // view_scatter16 behind the clip: the piece v holds the n voxels (n <= 16 / ELEM) at offset p of the thread's run; those inside the
 // current sub-run `cur` -- and the ones behind it that the piece reaches, have: there is one -- go to the view.  Sixteen bytes where the
 // full piece lies in one sub-run (so in one row) and lands on the 16-byte grid, voxel by voxel where not.  Pieces come in ascending p.
@@ -8185,11 +8218,190 @@ void bitswap1_decode_batch_window_kernel(const BatchWindowJob* __restrict__ jobs
     }
 }
 
+// ---- the update of a window (SQYAMD_Update_BatchWindow_*) ----------------------------------------------------------------------------------
+// window_scatter16's mirror image: the n voxels (n <= 16 / ELEM) at offset p of the thread's run, packed as they lie in a dense copy; those
+// inside the window come from the view, the others are zero.  Pieces come in ascending p.
+template <int ELEM>
+__device__ __forceinline__ uint4 window_gather16(const uint8_t* __restrict__ view, const WindowGeometry& g, WindowClip& c, WindowPiece& cur, bool& have, uint32_t p,
+                                                 uint32_t n)
+{
+    constexpr uint32_t G = 16 / ELEM;
+    uint32_t d[4] = {0, 0, 0, 0};
+    while (have && cur.run_off < (uint64_t)p + n) {
+        const uint64_t end = cur.run_off + cur.len;                  // (> p: a sub-run that ends in front of the piece has been left)
+        const uint32_t lo = cur.run_off > p ? (uint32_t)(cur.run_off - p) : 0u, hi = end < (uint64_t)p + n ? (uint32_t)(end - p) : n;
+        const uint64_t off = cur.dst_off + ((uint64_t)p + lo - cur.run_off);          // where voxel lo of the piece lies
+        const uint8_t* q = view + off * ELEM;
+        if (lo == 0 && hi == G && (reinterpret_cast<uintptr_t>(q) & 15u) == 0) {
+            const uint4 r = *reinterpret_cast<const uint4*>(q);
+            d[0] = r.x; d[1] = r.y; d[2] = r.z; d[3] = r.w;
+        } else {
+#pragma unroll
+            for (uint32_t k = 0; k < G; ++k)
+                if (k >= lo && k < hi) d[k * ELEM / 4] |= view_voxel_load<ELEM>(view, off + (k - lo)) << (8u * ((k * ELEM) & 3u));
+        }
+        if (end > (uint64_t)p + n) break;                             // the sub-run goes on in the next piece
+        have = window_clip_next(g, &c, &cur);
+    }
+    return make_uint4(d[0], d[1], d[2], d[3]);
+}
+
+// The bit planes of a blob with a window's voxels replaced, without the old voxels ever being transposed back: old plane stream + the
+// window's view -> new plane stream (out of place).  bitswap1_batch_kernel's geometry over the BLOB's dense order: a workgroup is one tile
+// of BSWB_TILE_VOX voxels, a thread owns 128 voxels in a row, which is 16 bytes of every plane.  It clips its run first (the clip and the
+// mask: sqy_batch_window.hpp).  Nothing inside the window: its 16 bytes of every plane are copied, no voxel is loaded.  All inside: the
+// voxels are gathered from the view and transposed as bitswap1_batch_strided_kernel does it, no old plane is loaded.  Partly inside:
+// the sub-runs' voxels with zeros elsewhere are transposed and every plane is stored as (old & ~mask) | new.
+template <int ELEM>
+__global__ __launch_bounds__(256)
+void bitswap1_batch_patch_kernel(const BatchPatchJob* __restrict__ jobs, const uint32_t* __restrict__ first_tile, uint32_t njobs)
+{
+    constexpr uint32_t W = 8 * ELEM, WPT = BSWB_THREAD_VOX / W;        // voxels per word (= planes), words per thread
+    typedef typename std::conditional<ELEM == 2, uint16_t, uint8_t>::type word_t;
+    const uint32_t j = batch_job_of_tile(first_tile, njobs);
+    const BatchPatchJob job = jobs[j];
+    const uint32_t tile = blockIdx.x - first_tile[j], tid = threadIdx.x;
+    const uint64_t len = job.bZ * job.bY * job.bX, seg = len / W, L = seg * W;
+    const WindowGeometry g{job.bY, job.bX, job.oz, job.oy, job.ox, job.Z, job.Y, job.X, job.sz, job.sy};
+    const uint8_t* __restrict__ view = static_cast<const uint8_t*>(job.view);
+    const uint8_t* __restrict__ old = static_cast<const uint8_t*>(job.old_stream);
+    uint8_t* __restrict__ out = static_cast<uint8_t*>(job.new_stream);
+    WindowPiece cur;
+    if (tile == 0 && tid < len - L) {                                 // tail voxels [L, len): verbatim, the window's where it has one
+        WindowClip ct = window_clip_start(g, L + tid, 1);
+        const uint32_t v = window_clip_next(g, &ct, &cur) ? view_voxel_load<ELEM>(view, cur.dst_off) : view_voxel_load<ELEM>(old, L + tid);
+        view_voxel_store<ELEM>(out, L + tid, v);
+    }
+    const uint64_t w0 = ((uint64_t)tile * 256u + tid) * WPT;
+    if (w0 >= seg) return;
+    const uint32_t nw = (uint32_t)(seg - w0 < WPT ? seg - w0 : WPT);  // this thread's words
+    const uint64_t plane_bytes = seg * ELEM;
+    const bool wide = nw == WPT && ((reinterpret_cast<uintptr_t>(old) | reinterpret_cast<uintptr_t>(out) | plane_bytes) & 15u) == 0;
+    const WindowClip c0 = window_clip_start(g, w0 * W, (uint64_t)nw * W);
+    WindowClip c = c0;
+    uint32_t mask[4] = {0, 0, 0, 0}, inside = 0;
+    while (window_clip_next(g, &c, &cur)) {
+        window_run_mask(W, (uint32_t)cur.run_off, (uint32_t)cur.len, mask);
+        inside += (uint32_t)cur.len;
+    }
+    if (inside == 0) {                                                // the old planes as they are
+        if (wide) {
+#pragma unroll
+            for (uint32_t b = 0; b < W; ++b)
+                *reinterpret_cast<uint4*>(out + b * plane_bytes + w0 * ELEM) = *reinterpret_cast<const uint4*>(old + b * plane_bytes + w0 * ELEM);
+        } else {
+            for (uint32_t i = 0; i < nw; ++i)
+#pragma unroll
+                for (uint32_t b = 0; b < W; ++b)
+                    reinterpret_cast<word_t*>(out)[b * seg + w0 + i] = reinterpret_cast<const word_t*>(old)[b * seg + w0 + i];
+        }
+        return;
+    }
+    const bool all = inside == nw * W;
+    uint32_t res[W][4];                                               // res[b]: the thread's 16 bytes of the plane that carries bit b
+#pragma unroll
+    for (uint32_t b = 0; b < W; ++b) { res[b][0] = 0; res[b][1] = 0; res[b][2] = 0; res[b][3] = 0; }
+    // the transposer of bitswap1_batch_strided_kernel over pieces of sixteen bytes: next(p, n) = the n voxels at offset p of the run
+    auto transpose = [&](auto&& next) {
+        if constexpr (ELEM == 2) {
+#pragma unroll
+            for (uint32_t i = 0; i < WPT; ++i) {
+                if (i >= nw) break;
+                const uint4 x = next(16u * i, 8u), y = next(16u * i + 8u, 8u);
+                const uint32_t d[8] = {x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w};
+                uint32_t v[16];
+#pragma unroll
+                for (int k = 0; k < 8; ++k) { v[2 * k] = d[k] & 0xffffu; v[2 * k + 1] = d[k] >> 16; }
+                // plane 15 - b, word w: bit 15 - k = bit b of voxel 16 w + k
+#pragma unroll
+                for (int b = 0; b < 16; ++b) {
+                    uint32_t a = 0;
+#pragma unroll
+                    for (int k = 0; k < 16; ++k) a |= ((v[k] >> b) & 1u) << (15 - k);
+                    res[b][i >> 1] |= a << (16u * (i & 1u));
+                }
+            }
+        } else {
+            // byte b of the result: bit b of the word's eight voxels, voxel k at bit 7 - k (bitswap1_u8_generic)
+            auto word_planes = [](uint64_t x) -> uint64_t {
+                uint64_t t = x, y;
+                y = (t ^ (t >> 7)) & 0x00AA00AA00AA00AAull; t = t ^ y ^ (y << 7);
+                y = (t ^ (t >> 14)) & 0x0000CCCC0000CCCCull; t = t ^ y ^ (y << 14);
+                y = (t ^ (t >> 28)) & 0x00000000F0F0F0F0ull; t = t ^ y ^ (y << 28);
+                const uint32_t r0 = __brev((uint32_t)t), r1 = __brev((uint32_t)(t >> 32));      // (bits reversed in every byte, bytes swapped)
+                return (uint64_t)__builtin_bswap32(r0) | ((uint64_t)__builtin_bswap32(r1) << 32);
+            };
+#pragma unroll
+            for (uint32_t i = 0; i < WPT; i += 2) {
+                if (i >= nw) break;
+                const uint4 x = next(8u * i, nw - i >= 2u ? 16u : 8u);                          // (a last odd word: its eight voxels, zeros behind them)
+                const uint64_t t[2] = {word_planes((uint64_t)x.x | ((uint64_t)x.y << 32)), word_planes((uint64_t)x.z | ((uint64_t)x.w << 32))};
+#pragma unroll
+                for (uint32_t u = 0; u < 2; ++u)
+#pragma unroll
+                    for (int b = 0; b < 8; ++b) res[b][(i + u) >> 2] |= ((uint32_t)(t[u] >> (8 * b)) & 0xffu) << (8u * ((i + u) & 3u));
+            }
+        }
+    };
+    if (all) {
+        // (a run that lies inside the window whole is a run of the window's dense order as well: the view's walk)
+        const ViewGeometry gv{job.Y, job.X, job.sz, job.sy};
+        ViewWalk w = view_walk_start(gv, ((c0.z - job.oz) * job.Y + (c0.y - job.oy)) * job.X + (c0.x - job.ox));
+        transpose([&](uint32_t, uint32_t n) { return view_gather16<ELEM>(view, gv, w, n); });
+    } else {
+        c = c0;
+        bool have = window_clip_next(g, &c, &cur);
+        transpose([&](uint32_t p, uint32_t n) { return window_gather16<ELEM>(view, g, c, cur, have, p, n); });
+    }
+    if (wide) {
+#pragma unroll
+        for (uint32_t b = 0; b < W; ++b) {
+            const uint64_t at = (uint64_t)(W - 1 - b) * plane_bytes + w0 * ELEM;
+            uint4 r = make_uint4(res[b][0], res[b][1], res[b][2], res[b][3]);
+            if (!all) {
+                const uint4 o = *reinterpret_cast<const uint4*>(old + at);
+                r = make_uint4(window_merge_word(o.x, r.x, mask[0]), window_merge_word(o.y, r.y, mask[1]), window_merge_word(o.z, r.z, mask[2]),
+                               window_merge_word(o.w, r.w, mask[3]));
+            }
+            *reinterpret_cast<uint4*>(out + at) = r;
+        }
+    } else {
+        constexpr uint32_t PER = 4 / ELEM;                            // plane words in 32 bits
+#pragma unroll
+        for (uint32_t i = 0; i < WPT; ++i)
+            if (i < nw)
+#pragma unroll
+            for (uint32_t b = 0; b < W; ++b) {
+                const uint64_t at = (uint64_t)(W - 1 - b) * seg + w0 + i;
+                const word_t m = (word_t)(mask[i / PER] >> (W * (i % PER))), r = (word_t)(res[b][i / PER] >> (W * (i % PER)));
+                reinterpret_cast<word_t*>(out)[at] = all ? r : window_merge_word(reinterpret_cast<const word_t*>(old)[at], r, m);
+            }
+    }
+}
+
+hipError_t launch_bitswap1_batch_patch(const BatchPatchJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ntiles, int elem_size, hipStream_t stream)
+{
+    if (njobs == 0 || ntiles == 0) return hipSuccess;
+    if (elem_size == 2) hipLaunchKernelGGL(bitswap1_batch_patch_kernel<2>, dim3(ntiles), dim3(256), 0, stream, d_jobs, d_first_tile, njobs);
+    else if (elem_size == 1) hipLaunchKernelGGL(bitswap1_batch_patch_kernel<1>, dim3(ntiles), dim3(256), 0, stream, d_jobs, d_first_tile, njobs);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
 hipError_t launch_batch_window_copy(const BatchWindowJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ntiles, int elem_size, hipStream_t stream)
 {
     if (njobs == 0 || ntiles == 0) return hipSuccess;
     if (elem_size == 2) hipLaunchKernelGGL(batch_window_copy_kernel<2>, dim3(ntiles), dim3(256), 0, stream, d_jobs, d_first_tile, njobs);
     else if (elem_size == 1) hipLaunchKernelGGL(batch_window_copy_kernel<1>, dim3(ntiles), dim3(256), 0, stream, d_jobs, d_first_tile, njobs);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+hipError_t launch_batch_window_paste(const BatchWindowJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ntiles, int elem_size, hipStream_t stream)
+{
+    if (njobs == 0 || ntiles == 0) return hipSuccess;
+    if (elem_size == 2) hipLaunchKernelGGL(batch_window_paste_kernel<2>, dim3(ntiles), dim3(256), 0, stream, d_jobs, d_first_tile, njobs);
+    else if (elem_size == 1) hipLaunchKernelGGL(batch_window_paste_kernel<1>, dim3(ntiles), dim3(256), 0, stream, d_jobs, d_first_tile, njobs);
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }

@@ -398,6 +398,20 @@ BatchWindowLayout batch_window_layout(uint64_t njobs)
     return l;
 }
 
+UpdateBatchPlan update_batch_plan(const std::vector<uint64_t>& raw_bytes, EncodeBatchForm new_form, const std::vector<int32_t>& encode_group_of, bool fused_on)
+{
+    UpdateBatchPlan u;
+    const size_t n = raw_bytes.size();
+    u.keep_planes.assign(n, 0);
+    u.place_at.assign(n, 0);
+    for (size_t i = 0; i < n; ++i) {
+        u.keep_planes[i] = fused_on && new_form == EncodeBatchForm::bitswap1_lz4 && i < encode_group_of.size() && encode_group_of[i] >= 0;
+        u.place_at[i] = u.bytes;
+        u.bytes += round_up(raw_bytes[i], 256);
+    }
+    return u;
+}
+
 Lz4BatchPlan lz4_batch_plan_views(const Lz4Params& p, const std::vector<uint64_t>& totals, const std::vector<uint64_t>& pack_bytes, unsigned nthreads,
                                   uint64_t group_bytes, uint64_t joint_max, uint64_t extra_bytes_all)
 {

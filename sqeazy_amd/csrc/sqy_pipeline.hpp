@@ -214,6 +214,38 @@ struct DecodeBatchPlan {
 // -- they keep their place in the group and in the workspace but get no job in any table.
 DecodeBatchPlan decode_batch_plan(const std::vector<DecodeBatchBlob>& blobs, uint64_t group_bytes, const std::vector<uint8_t>* dropped = nullptr);
 
+// ---- window update (SQYAMD_Update_BatchWindow_*): old blob + a window's new voxels -> new blob ----
+// Every old blob gets a place in ONE workspace buffer, place_at[i] on the 256-byte grid, raw_bytes[i] long (`bytes` in all): its voxels
+// decoded dense -- or, for a blob that takes the fused way, its LZ4 output, the plane stream of just as many bytes.
+// keep_planes[i]: the batch decode is asked to stop behind blob i's LZ4 stage IF it finds the blob to be DecodeBatchForm::planes on its
+// joint path.  That is asked where the new blob can be made from patched planes: the option (fused_on: batch_update_fused and both
+// joint options), the new pipeline in the form bitswap1_lz4, and the volume in a group of the encode's plan (encode_group_of[i] >= 0).
+struct UpdateBatchPlan {
+    std::vector<uint8_t> keep_planes;
+    std::vector<uint64_t> place_at;
+    uint64_t bytes = 0;
+};
+UpdateBatchPlan update_batch_plan(const std::vector<uint64_t>& raw_bytes, EncodeBatchForm new_form, const std::vector<int32_t>& encode_group_of, bool fused_on);
+// What became of blob i: patched (its place holds the old plane stream, the encode group's patch launch reads it and the window's view)
+// only if the decode was asked, found the planes form and kept the blob on the joint path to the end; otherwise its place holds the
+// voxels, the call's ONE paste launch writes the window into them and the encode reads them as a dense volume
+inline bool update_blob_patched(bool keep_planes, DecodeBatchForm old_form, bool decoded_jointly)
+{
+    return keep_planes && old_form == DecodeBatchForm::planes && decoded_jointly;
+}
+// Whether blob i's LZ4 output is what its place holds -- planned_form: the form the batch decode plans it in, `plain` for an `lz4` blob
+// (the volume) and for a blob that keeps its planes (the plane stream).  A decode group whose members ALL are such blobs decodes straight
+// into the places, which lie in one buffer, and launches nothing behind its LZ4 decode; any other group keeps the workspace and its
+// launches, a batched copy for such members (the rule of a slab set's group).  fused_on as above: off, no group does.
+inline bool update_lz4_into_place(bool fused_on, DecodeBatchForm planned_form) { return fused_on && planned_form == DecodeBatchForm::plain; }
+inline bool update_group_into_places(const std::vector<uint32_t>& members, const std::vector<uint8_t>& lz4_into_place)
+{
+    for (uint32_t b : members) if (!lz4_into_place[b]) return false;
+    return !members.empty();
+}
+// a job of the patch launch (sqy::BatchPatchJob, sqy_kernels.h); its tables have the window launches' layout (batch_window_layout)
+constexpr uint64_t kBatchPatchJobBytes = 112;
+
 // The slab set's groups (SQYAMD_Decode_Slabs_*): joint blob j decodes `total` bytes in LZ4 blocks of block_bytes.  The blobs are dealt to
 // groups in order; a group is closed when the next blob would take its LZ4 output (every blob's rounded up to 256 bytes) past group_bytes,
 // when it holds `inflight` blobs (inflight <= 0: no bound on the count), or when the next blob has another block size.  A group holds at
