@@ -354,6 +354,43 @@ SQY_FUNCTION_PREFIX int SQYAMD_Decode_BatchWindow_UI8_Device(const void* d_src, 
                                                              const long* src_origins, void* const* d_dsts, const long* dst_shapes,
                                                              const long* dst_strides, unsigned shape_size, long* decoded_bytes,
                                                              void* hip_stream);
+/* The check of a box of a tiled store against resident voxels: _Decode_BatchWindow_*_Device with the views READ and nothing written --
+ * no decoded copy is kept.  The arguments are that call's; d_views[i] / view_strides row i is the view of view_shapes row i that window i
+ * of blob i is compared with.  stats: a HOST array of nblobs rows of SQYAMD_COMPARE_FIELDS values.  With a = voxel k of window i as
+ * SQYAMD_Decode_*_Device decodes it and b = voxel k of view i (the "original" side of the reference's `sqy compare` metrics), row i holds
+ * the exact unsigned integers below -- a blob has fewer than 2^31 voxels, so SUM_SQ < 2^31 x 65535^2 < 2^63 and nothing wraps; no
+ * floating-point value exists on the device and the order of summation cannot show. */
+#define SQYAMD_COMPARE_FIELDS 8
+#define SQYAMD_COMPARE_VOXELS 0   /* voxels of the window */
+#define SQYAMD_COMPARE_NDIFF 1    /* number of k with a != b */
+#define SQYAMD_COMPARE_SUM_ABS 2  /* sum |a - b| */
+#define SQYAMD_COMPARE_SUM_SQ 3   /* sum (a - b)^2 */
+#define SQYAMD_COMPARE_MAX_ABS 4  /* max |a - b| */
+#define SQYAMD_COMPARE_VIEW_SUM 5 /* sum b */
+#define SQYAMD_COMPARE_VIEW_MIN 6 /* min b */
+#define SQYAMD_COMPARE_VIEW_MAX 7 /* max b */
+/* Checked before anything runs (else 1, stats zeroed; stats == NULL: 1): exactly what _Decode_BatchWindow_* checks -- the blob entries,
+ * the view rules, each window against its blob's header, the header's voxel type --; whatever needs no header (a negative origin
+ * included) is checked before a device is looked for.  Views may overlap or coincide, one view may serve several blobs and the same blob
+ * may be named several times: nothing is written.  Nothing is written to device memory outside the library's workspace: d_src and the
+ * views keep their bytes.  A damaged blob: SQY_Decode's composite code of the first damaged blob in blob order, returned after every blob
+ * has been handled; the damaged blob's row is all ones (every field ~0), the other rows are right.
+ * How: the windowed decode's groups and launches with a reduction where the stores were.  The device holds one 64-byte record per blob in
+ * the workspace, made ready on the stream (zeros, VIEW_MIN all ones) and brought back by ONE copy behind the call's last launch; the host
+ * fills VOXELS.  `bitswap1->lz4` blobs on the joint path go through an inverse transposer that compares the window's voxels with the
+ * view's where the windowed decode stores them, `lz4` blobs' windows are compared in the LZ4 output; every other blob is decoded dense
+ * into a workspace place and ONE launch at the end of the call compares them all ("batch_compare_fused" = 0: every blob -- the same
+ * statistics).  A thread sums its 128 voxels (SUM_SQ in 64 bits), a workgroup reduces across lanes and through LDS, and one set of 64-bit
+ * integer atomics per workgroup of 32768 voxels goes into the record.  Stream, context, ordering and thread safety as _Batch_*_Device:
+ * the work runs behind what is queued on hip_stream and is complete on return; safe from several host threads. */
+SQY_FUNCTION_PREFIX int SQYAMD_Compare_BatchWindow_UI16_Device(const void* d_src, const long* offsets, const long* lengths, int nblobs,
+                                                               const long* src_origins, const void* const* d_views, const long* view_shapes,
+                                                               const long* view_strides, unsigned shape_size, unsigned long long* stats,
+                                                               void* hip_stream);
+SQY_FUNCTION_PREFIX int SQYAMD_Compare_BatchWindow_UI8_Device(const void* d_src, const long* offsets, const long* lengths, int nblobs,
+                                                              const long* src_origins, const void* const* d_views, const long* view_shapes,
+                                                              const long* view_strides, unsigned shape_size, unsigned long long* stats,
+                                                              void* hip_stream);
 /* The write of a box into a tiled store, whose border cuts through tiles: every tile under the box is read, modified and written again
  * with ONE call.  Old blob i lies at d_src + src_offsets[i], src_lengths[i] bytes (host arrays; any alignment): a complete sqeazy blob of
  * the entry point's voxel type, any pipeline, any layout.  Window i is the box [origins row i, + win_shapes row i) of that blob's volume
@@ -490,6 +527,9 @@ SQY_FUNCTION_PREFIX void SQYAMD_Release_Workspace(void);
  *                                     keep their bit planes, the window is patched into them; these and `lz4` blobs are LZ4-decoded straight
  *                                     into their workspace places (0: every blob decoded dense into the workspace by the batch decode's
  *                                     launches, one window paste, the batch encode -- same bytes)
+ *   "batch_compare_fused"             1 [SQY_NO_BATCH_COMPARE_FUSED=1 -> 0]  SQYAMD_Compare_BatchWindow_*: the inverse transposer compares the window's
+ *                                     voxels with the view's, `lz4` windows are compared in the LZ4 output (0: every blob decoded dense into the
+ *                                     workspace, one compare launch at the end of the call -- same statistics)
  * Set: 0 = done, 1 = unknown name or value out of range.  Get: the value, -1 for an unknown name. */
 SQY_FUNCTION_PREFIX int SQYAMD_Set_Option(const char* name, long value);
 SQY_FUNCTION_PREFIX long SQYAMD_Get_Option(const char* name);

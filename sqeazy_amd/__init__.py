@@ -34,6 +34,7 @@ EXPORTED_SYMBOLS = (
     "SQYAMD_Decode_BatchStrided_UI16_Device", "SQYAMD_Decode_BatchStrided_UI8_Device",
     "SQYAMD_Decode_BatchWindow_UI16_Device", "SQYAMD_Decode_BatchWindow_UI8_Device",
     "SQYAMD_Update_BatchWindow_UI16_Device", "SQYAMD_Update_BatchWindow_UI8_Device",
+    "SQYAMD_Compare_BatchWindow_UI16_Device", "SQYAMD_Compare_BatchWindow_UI8_Device",
     "SQYAMD_PipelineEncode_UI16_Cap", "SQYAMD_PipelineEncode_UI8_Cap",
     "SQYAMD_Decode_UI16_Device", "SQYAMD_Decode_UI8_Device",
     "SQYAMD_Decode_Frames_UI16_Device", "SQYAMD_Decode_Frames_UI8_Device", "SQYAMD_Decode_Frames_UI16", "SQYAMD_Decode_Frames_UI8",
@@ -104,6 +105,9 @@ def lib():
         for f in ("SQYAMD_Decode_BatchWindow_UI8_Device", "SQYAMD_Decode_BatchWindow_UI16_Device"):
             getattr(L, f).argtypes = [ctypes.c_void_p, c_long_p, c_long_p, ctypes.c_int, c_long_p, ctypes.POINTER(ctypes.c_void_p), c_long_p, c_long_p,
                                       ctypes.c_uint, c_long_p, ctypes.c_void_p]
+        for f in ("SQYAMD_Compare_BatchWindow_UI8_Device", "SQYAMD_Compare_BatchWindow_UI16_Device"):
+            getattr(L, f).argtypes = [ctypes.c_void_p, c_long_p, c_long_p, ctypes.c_int, c_long_p, ctypes.POINTER(ctypes.c_void_p), c_long_p, c_long_p,
+                                      ctypes.c_uint, ctypes.POINTER(ctypes.c_ulonglong), ctypes.c_void_p]
         for f in ("SQYAMD_Update_BatchWindow_UI8_Device", "SQYAMD_Update_BatchWindow_UI16_Device"):
             getattr(L, f).argtypes = [ctypes.c_char_p, ctypes.c_void_p, c_long_p, c_long_p, ctypes.c_int, c_long_p, ctypes.POINTER(ctypes.c_void_p), c_long_p, c_long_p,
                                       ctypes.c_uint, ctypes.c_void_p, ctypes.c_long, c_long_p, c_long_p, ctypes.c_int, ctypes.c_void_p]
@@ -524,6 +528,40 @@ def decode_batch_window_device(d_src, offsets, lengths, origins, d_dsts, shapes,
         _longs([x for o in origins for x in o]) if n and origins is not None else None, ptrs, _longs([x for s in shapes for x in s]) if n else None,
         _longs([x for s in strides for x in s]) if n and strides is not None else None, ctypes.c_uint(rank), decoded, ctypes.c_void_p(stream or 0))
     return rc, list(decoded[:n])
+
+
+COMPARE_FIELDS = ("voxels", "ndiff", "sum_abs", "sum_sq", "max_abs", "view_sum", "view_min", "view_max")      # SQYAMD_COMPARE_* in index order
+
+
+def compare_batch_window_device(d_src, offsets, lengths, origins, d_views, shapes, strides, dtype, stream=None):
+    """SQYAMD_Compare_BatchWindow_*_Device: the window of blob i of decode_batch_window_device compared with the strided view at device
+    pointer d_views[i] (shape shapes[i], strides[i] in voxels; None: dense); the views are read, nothing is written.  Returns (rc, stats):
+    stats an (n, 8) uint64 array, row i the exact integers COMPARE_FIELDS of window i (a: the decoded voxel, b: the view's).  box_windows
+    makes the table."""
+    n = len(offsets)
+    rank = len(shapes[0]) if n else 0
+    ptrs = (ctypes.c_void_p * max(n, 1))(*[p if p is None else int(p) for p in d_views])
+    stats = np.zeros((n, len(COMPARE_FIELDS)), dtype=np.uint64)
+    rc = getattr(lib(), "SQYAMD_Compare_BatchWindow_%s_Device" % _suffix(dtype))(
+        ctypes.c_void_p(int(d_src)), _longs(offsets) if n else None, _longs(lengths) if n else None, ctypes.c_int(n),
+        _longs([x for o in origins for x in o]) if n and origins is not None else None, ptrs, _longs([x for s in shapes for x in s]) if n else None,
+        _longs([x for s in strides for x in s]) if n and strides is not None else None, ctypes.c_uint(rank),
+        stats.ctypes.data_as(ctypes.POINTER(ctypes.c_ulonglong)) if n else None, ctypes.c_void_p(stream or 0))
+    return rc, stats
+
+
+def compare_metrics(row, dtype):
+    """The metrics of the reference's `sqy compare` from one row of compare_batch_window_device's stats, the view being the original side:
+    mse = sum_sq / voxels, rms = sqrt(mse), nrmse = rms / (view_max - view_min), mnmse = rms / (view_sum / voxels), l1norm = sum_abs,
+    l2norm = sum_sq, psnr = 20 log10(type max) - 10 log10(mse), drange = view_max - view_min.  float64 on the exact integers; a zero
+    denominator or a zero mse gives inf / nan as numpy does."""
+    f = dict(zip(COMPARE_FIELDS, (np.float64(int(x)) for x in row)))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mse = f["sum_sq"] / f["voxels"]
+        rms = np.sqrt(mse)
+        drange = f["view_max"] - f["view_min"]
+        return {"mse": mse, "rms": rms, "nrmse": rms / drange, "mnmse": rms / (f["view_sum"] / f["voxels"]), "l1norm": f["sum_abs"], "l2norm": f["sum_sq"],
+                "psnr": np.float64(20.0) * np.log10(np.float64(np.iinfo(np.dtype(dtype)).max)) - np.float64(10.0) * np.log10(mse), "drange": drange}
 
 
 def update_batch_window_device(pipeline, d_src, offsets, lengths, origins, d_wins, shapes, strides, dtype, d_dst, slot_capacity, nthreads=0, stream=None):

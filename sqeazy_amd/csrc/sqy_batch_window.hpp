@@ -6,6 +6,8 @@
 // it; its voxel (z, y, x) goes to offset (z - oz) sz + (y - oy) sy + (x - ox) of the destination view.  The clip takes a run [i0, i0 + n)
 // of the blob's dense order and yields the sub-runs that lie inside the window -- each one within a row, so consecutive on both sides --
 // with two divisions at its start and none afterwards: what lies outside is stepped over with multiplications.
+// Behind the clip: the mask and the merge of a window's update in the bit-plane layout (SQYAMD_Update_BatchWindow_*), and the sums of a
+// window's compare with a view (SQYAMD_Compare_BatchWindow_*; tests/sanitize/batch_compare_test.cpp holds them against a triple loop).
 #ifndef SQY_BATCH_WINDOW_HPP_
 #define SQY_BATCH_WINDOW_HPP_
 
@@ -108,6 +110,86 @@ template <class T>
 SQY_VIEW_HD inline T window_merge_word(T old_bits, T new_bits, T mask)
 {
     return (T)((old_bits & (T)~mask) | (new_bits & mask));
+}
+
+// ---- the compare of a window with a view of its shape (SQYAMD_Compare_BatchWindow_*) ----
+// What a thread gathers over its voxels: a = the blob's decoded voxel, b = the view's.  A thread owns at most 128 voxels, so every sum
+// but sum_sq fits 32 bits there (128 x 65535 < 2^23); 128 x 65535^2 does not.  The neutral element: compare_sums_neutral().
+struct CompareSums {
+    uint64_t sum_sq;                 // sum (a - b)^2
+    uint32_t n;                      // voxels compared
+    uint32_t ndiff, sum_abs, max_abs;            // a != b; sum |a - b|; max |a - b|
+    uint32_t view_sum, view_min, view_max;       // of b
+};
+SQY_VIEW_HD inline CompareSums compare_sums_neutral() { return CompareSums{0, 0, 0, 0, 0, 0, 0xffffffffu, 0}; }
+
+SQY_VIEW_HD inline void compare_voxel(CompareSums* s, uint32_t a, uint32_t b)
+{
+    const uint32_t d = a > b ? a - b : b - a;
+    ++s->n;
+    s->ndiff += d != 0u;
+    s->sum_abs += d;
+    s->sum_sq += (uint64_t)(d * d);                                     // (d <= 65535: the square fits 32 bits)
+    s->max_abs = d > s->max_abs ? d : s->max_abs;
+    s->view_sum += b;
+    s->view_min = b < s->view_min ? b : s->view_min;
+    s->view_max = b > s->view_max ? b : s->view_max;
+}
+
+// sixteen bytes as they lie in memory, on the 16-byte grid
+struct alignas(16) WindowBytes16 { uint32_t w[4]; };
+
+template <int ELEM>
+SQY_VIEW_HD inline uint32_t window_voxel_load(const uint8_t* base, uint64_t off)
+{
+    if constexpr (ELEM == 2) return reinterpret_cast<const uint16_t*>(base)[off];
+    else return base[off];
+}
+
+// voxels [lo, hi) of two pieces of sixteen bytes, each packed as in a dense copy (hi <= 16 / ELEM)
+template <int ELEM>
+SQY_VIEW_HD inline void compare_piece(CompareSums* s, const uint32_t a[4], const uint32_t b[4], uint32_t lo, uint32_t hi)
+{
+    constexpr uint32_t G = 16 / ELEM, M = ELEM == 2 ? 0xffffu : 0xffu;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (uint32_t k = 0; k < G; ++k)
+        if (k >= lo && k < hi) {
+            const uint32_t sh = 8u * ((k * ELEM) & 3u);
+            compare_voxel(s, (a[k * ELEM / 4] >> sh) & M, (b[k * ELEM / 4] >> sh) & M);
+        }
+}
+
+// The windowed transposer's scatter with loads where its stores were: the piece `a` holds the n decoded voxels (n <= 16 / ELEM) at offset p
+// of the thread's run; those inside the current sub-run `cur` -- and the ones behind it that the piece reaches, have: there is one -- are
+// compared with the view's voxels of the same places.  The view is read sixteen bytes at a time where the full piece lies in one sub-run
+// (so in one row) and on the view's 16-byte grid, voxel by voxel where not; nothing else of it is read.  Pieces come in ascending p.
+template <int ELEM>
+SQY_VIEW_HD inline void window_compare16(const uint8_t* view, const WindowGeometry& g, WindowClip& c, WindowPiece& cur, bool& have, const uint32_t a[4], uint32_t p, uint32_t n,
+                                         CompareSums* s)
+{
+    constexpr uint32_t G = 16 / ELEM;
+    while (have && cur.run_off < (uint64_t)p + n) {
+        const uint64_t end = cur.run_off + cur.len;                  // (> p: a sub-run that ends in front of the piece has been left)
+        const uint32_t lo = cur.run_off > p ? (uint32_t)(cur.run_off - p) : 0u, hi = end < (uint64_t)p + n ? (uint32_t)(end - p) : n;
+        const uint64_t off = cur.dst_off + ((uint64_t)p + lo - cur.run_off);          // where voxel lo of the piece lies in the view
+        const uint8_t* q = view + off * ELEM;
+        uint32_t b[4] = {0, 0, 0, 0};
+        if (lo == 0 && hi == G && (reinterpret_cast<uintptr_t>(q) & 15u) == 0) {
+            const WindowBytes16 r = *reinterpret_cast<const WindowBytes16*>(q);
+            b[0] = r.w[0]; b[1] = r.w[1]; b[2] = r.w[2]; b[3] = r.w[3];
+        } else {
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+            for (uint32_t k = 0; k < G; ++k)
+                if (k >= lo && k < hi) b[k * ELEM / 4] |= window_voxel_load<ELEM>(view, off + (k - lo)) << (8u * ((k * ELEM) & 3u));
+        }
+        compare_piece<ELEM>(s, a, b, lo, hi);
+        if (end > (uint64_t)p + n) break;                             // the sub-run goes on in the next piece
+        have = window_clip_next(g, &c, &cur);
+    }
 }
 
 } // namespace sqy

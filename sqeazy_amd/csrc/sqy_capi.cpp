@@ -87,6 +87,7 @@ struct Options {
     std::atomic<long> batch_strided_fused;              // strided views: the transposers gather from / scatter into the view, `lz4` packs into the stream and unpacks from the LZ4 output (0: packed copies everywhere)
     std::atomic<long> batch_window_fused;               // windows: the inverse transposer stores only the window's voxels, `lz4` windows are copied out of the LZ4 output (0: every blob decoded dense, one window copy)
     std::atomic<long> batch_update_fused;               // window updates: `bitswap1->lz4` blobs written as `bitswap1->lz4` keep their planes, the window is patched into them; kept planes and `lz4` blobs are LZ4-decoded straight into their places (0: every blob decoded dense by the batch decode's launches, one paste)
+    std::atomic<long> batch_compare_fused;              // window compares: the inverse transposer compares the window's voxels with the view's where it would store them, `lz4` windows are compared in the LZ4 output (0: every blob decoded dense, one compare launch)
     std::atomic<long> stage_lanes;                      // frames-in-place calls on caller streams run on the library's lanes: 0 never, 1 always, 2 where transpose_chain_caller_streams is on
     std::atomic<long> parse_lanes;                      // .. how many parse lanes a device has (1-8)
     // counters (Get reads, Set takes 0 only): calls that ran on the lanes; calls that stayed on their caller's stream because it had a
@@ -106,7 +107,7 @@ struct Options {
           encode_batch_group_bytes(env_number("SQY_ENCODE_BATCH_GROUP_BYTES", kBatchGroupBytesDefault, 1, kBatchBytesMax)),
           encode_batch_joint_max_bytes(env_number("SQY_ENCODE_BATCH_JOINT_MAX_BYTES", kBatchJointMaxDefault, 0, kBatchBytesMax)),
           batch_strided_fused(env_flag("SQY_NO_BATCH_STRIDED_FUSED") ? 0 : 1), batch_window_fused(env_flag("SQY_NO_BATCH_WINDOW_FUSED") ? 0 : 1),
-          batch_update_fused(env_flag("SQY_NO_BATCH_UPDATE_FUSED") ? 0 : 1), stage_lanes(env_number("SQY_STAGE_LANES", kStageLanesDefault, 0, 2)),
+          batch_update_fused(env_flag("SQY_NO_BATCH_UPDATE_FUSED") ? 0 : 1), batch_compare_fused(env_flag("SQY_NO_BATCH_COMPARE_FUSED") ? 0 : 1), stage_lanes(env_number("SQY_STAGE_LANES", kStageLanesDefault, 0, 2)),
           parse_lanes(env_number("SQY_PARSE_LANES", kParseLanesDefault, 1, sqy::LanePicker::kMaxLanes)) { sqy::set_bitswap1_blocks_per_cu(transpose_blocks_per_cu.load()); }
     std::atomic<long>* find(const char* name)
     {
@@ -132,6 +133,7 @@ struct Options {
         if (!std::strcmp(name, "batch_strided_fused")) return &batch_strided_fused;
         if (!std::strcmp(name, "batch_window_fused")) return &batch_window_fused;
         if (!std::strcmp(name, "batch_update_fused")) return &batch_update_fused;
+        if (!std::strcmp(name, "batch_compare_fused")) return &batch_compare_fused;
         if (!std::strcmp(name, "stage_lanes")) return &stage_lanes;
         if (!std::strcmp(name, "parse_lanes")) return &parse_lanes;
         if (!std::strcmp(name, "lane_calls")) return &lane_calls;
@@ -340,6 +342,8 @@ struct Workspace {
     DevBuf batch_pack_one;    // .. decode: the dense place of a view whose blob is decoded on its own
     DevBuf batch_views[3];    // .. the job and tile tables of the view launches: pack / unpack, the strided transposer, the strided copy
     DevBuf batch_windows[4];  // .. and of the window launches: the window copy, the windowed transposer, the copy out of the LZ4 output, the paste
+    DevBuf batch_compares[3]; // window compares: the job and tile tables of the compare launch, the comparing transposer, the compare in the LZ4 output
+    DevBuf batch_records;     // .. a record of eight 64-bit words per blob
     DevBuf batch_update;      // window updates: every old blob's place (decoded dense, or its plane stream), on the 256-byte grid
     DevBuf batch_patch_jobs;  // .. the job and tile tables of a group's patch launch
     DevBuf batch_places;      // packed batch encode: the places a group's placement scan leaves for the gather, behind them its gap table
@@ -352,7 +356,8 @@ struct Workspace {
         subset.release(); range_full.release(); slabs_index.release(); slabs_joint.release(); slabs_out.release(); slabs_host.release();
         batch_stream.release(); batch_scratch.release(); batch_tables.release(); batch_quant.release(); batch_host.release();
         batch_pack.release(); batch_pack_one.release(); for (DevBuf& b : batch_views) b.release(); for (DevBuf& b : batch_windows) b.release();
-        batch_update.release(); batch_patch_jobs.release();
+        for (DevBuf& b : batch_compares) b.release();
+        batch_records.release(); batch_update.release(); batch_patch_jobs.release();
         batch_places.release(); batch_packed.release();
     }
 };
@@ -2510,7 +2515,7 @@ struct TiledJobs {
     int upload(hipStream_t stream, DevBuf& buf, const uint32_t** d_tiles)
     {
         const size_t nj = jobs.size();
-        const sqy::BatchWindowLayout lay = sqy::batch_window_layout(nj);
+        const sqy::BatchWindowLayout lay = sqy::batch_window_layout(nj, sizeof(Job));
         first_tile.push_back(ntiles);
         host.assign(lay.total, 0);
         std::memcpy(host.data(), jobs.data(), nj * sizeof(Job));
@@ -2554,6 +2559,44 @@ int launch_windows(Context& cx, hipStream_t stream, WindowLaunch& l, WindowLaunc
         break;
     case WindowLaunch::copy_from_lz4: SQY_TIMED("batch_copy_window", sqy::launch_batch_window_copy(d_jobs, d_tiles, nj, l.ntiles, elem_size, stream)); break;
     case WindowLaunch::paste: SQY_TIMED("batch_window_paste", sqy::launch_batch_window_paste(d_jobs, d_tiles, nj, l.ntiles, elem_size, stream)); break;
+    }
+    return 0;
+}
+
+// ---- the compare of a window with its view (SQYAMD_Compare_BatchWindow_*) ----
+// The windowed decode's driver with loads where its stores were: the same groups, plan and window jobs, each job with its record (eight
+// 64-bit words in Workspace::batch_records).  Layer one: the blob decoded dense into a place of Workspace::batch_pack, ONE
+// batch_window_compare launch at the end of the call.  Layer two (the option batch_compare_fused): on the joint path the `bitswap1->lz4`
+// blobs' inverse transposer compares instead of storing, the `lz4` blobs' windows are compared in the LZ4 output.
+static_assert(sizeof(sqy::BatchCompareJob) == sqy::kBatchCompareJobBytes, "the compare job's layout");
+struct CompareLaunch : TiledJobs<sqy::BatchCompareJob> {
+    enum Kind { compare, bitswap1_decode, compare_in_lz4 };
+    // blob_tiles: as WindowLaunch::add
+    void add(const void* view, const void* dense, const sqy::BatchWindow& w, const WindowView& v, bool blob_tiles, unsigned long long* record)
+    {
+        const sqy::WindowGeometry g{w.bY, w.bX, w.oz, w.oy, w.ox, w.Z, w.Y, w.X, v.sz, v.sy};
+        const uint64_t tile0 = blob_tiles ? sqy::window_first_tile(g, sqy::kBatchTileVoxels) : 0;
+        jobs.push_back(sqy::BatchCompareJob{view, dense, w.Z, w.Y, w.X, v.sz, v.sy, w.bZ, w.bY, w.bX, w.oz, w.oy, w.ox, tile0, record, 0});
+        first_tile.push_back(ntiles);
+        ntiles += blob_tiles ? (uint32_t)sqy::window_tile_count(g, sqy::kBatchTileVoxels) : sqy::batch_bitswap1_tiles(w.Z * w.Y * w.X);
+    }
+};
+// the tables to Workspace::batch_compares[kind], the launch behind them under its profile name; no jobs: nothing
+int launch_compares(Context& cx, hipStream_t stream, CompareLaunch& l, CompareLaunch::Kind kind, int elem_size)
+{
+    if (l.jobs.empty()) return 0;
+    std::vector<PendingEvent>* pend = &cx.pending;
+    const uint32_t nj = (uint32_t)l.jobs.size();
+    DevBuf& buf = cx.ws.batch_compares[(int)kind];
+    const uint32_t* d_tiles = nullptr;
+    if (l.upload(stream, buf, &d_tiles)) return 1;
+    const sqy::BatchCompareJob* d_jobs = static_cast<const sqy::BatchCompareJob*>(buf.p);
+    switch (kind) {
+    case CompareLaunch::compare: SQY_TIMED("batch_window_compare", sqy::launch_batch_window_compare(d_jobs, d_tiles, nj, l.ntiles, elem_size, stream)); break;
+    case CompareLaunch::bitswap1_decode:
+        SQY_TIMED("batch_bitswap1_decode_window_compare", sqy::launch_bitswap1_decode_batch_window_compare(d_jobs, d_tiles, nj, l.ntiles, elem_size, stream));
+        break;
+    case CompareLaunch::compare_in_lz4: SQY_TIMED("batch_compare_window", sqy::launch_batch_window_compare(d_jobs, d_tiles, nj, l.ntiles, elem_size, stream)); break;
     }
     return 0;
 }
@@ -2791,6 +2834,10 @@ struct StridedDecode {
     const std::vector<sqy::BatchWindow>* wins = nullptr;
     std::vector<WindowView> wviews;
     WindowLaunch wscatter, wcopy;
+    // compares (SQYAMD_Compare_BatchWindow_*, records != nullptr): blob b's record at records + 8 b; the windows of direct[b] == 2 are
+    // compared, not stored -- one batch_bitswap1_decode_window_compare, one batch_compare_window launch
+    unsigned long long* records = nullptr;
+    CompareLaunch cscatter, ccopy;
 };
 int batch_group_tail(JointGroup& G, const sqy::DecodeJointLayout& L, const sqy::DecodeBatchGroup& pg, const std::vector<sqy::DecodeBatchBlob>& plan_in, int elem_size,
                      std::vector<unsigned char>& tables, StridedDecode* sv = nullptr)
@@ -2814,6 +2861,10 @@ int batch_group_tail(JointGroup& G, const sqy::DecodeJointLayout& L, const sqy::
             const SlabBlob& s = G.blobs[b];
             if (sv && sv->direct[b] == 1 && plan_in[b].form != sqy::DecodeBatchForm::diff_planes) {
                 (k == 0 ? sv->scatter : sv->copy).add(s.call->d_dst, G.out + s.out_base, (*sv->views)[b]);
+                continue;
+            }
+            if (sv && sv->direct[b] == 2 && sv->records && plan_in[b].form != sqy::DecodeBatchForm::diff_planes) {
+                (k == 0 ? sv->cscatter : sv->ccopy).add(s.call->d_dst, G.out + s.out_base, (*sv->wins)[b], sv->wviews[b], k == 0, sv->records + sqy::kCompareFields * b);
                 continue;
             }
             if (sv && sv->direct[b] == 2 && plan_in[b].form != sqy::DecodeBatchForm::diff_planes) {
@@ -2853,6 +2904,8 @@ int batch_group_tail(JointGroup& G, const sqy::DecodeJointLayout& L, const sqy::
         return 1;
     if (sv && (launch_windows(G.cx, stream, sv->wscatter, WindowLaunch::bitswap1_decode, elem_size) || launch_windows(G.cx, stream, sv->wcopy, WindowLaunch::copy_from_lz4, elem_size)))
         return 1;
+    if (sv && (launch_compares(G.cx, stream, sv->cscatter, CompareLaunch::bitswap1_decode, elem_size) || launch_compares(G.cx, stream, sv->ccopy, CompareLaunch::compare_in_lz4, elem_size)))
+        return 1;
     if (nd) {
         // (every launch timed on its own: the profile counts the launches, 1 + steps whatever the number of blobs)
         const sqy::DiffBatchJob* d_diff = reinterpret_cast<const sqy::DiffBatchJob*>(dj + L.diff.jobs_at);
@@ -2886,7 +2939,7 @@ int decode_batch_group(Context& cx, const uint8_t* d_src, std::vector<SlabBlob>&
                        const sqy::DecodeBatchPlan& plan, size_t gi, int elem_size, hipStream_t stream, std::vector<size_t>& single, StridedDecode* sv = nullptr,
                        const UpdateDecode* ud = nullptr)
 {
-    if (sv) { sv->scatter.clear(); sv->copy.clear(); sv->wscatter.clear(); sv->wcopy.clear(); }     // (the group before has been synchronised)
+    if (sv) { sv->scatter.clear(); sv->copy.clear(); sv->wscatter.clear(); sv->wcopy.clear(); sv->cscatter.clear(); sv->ccopy.clear(); }     // (the group before has been synchronised)
     const sqy::DecodeBatchGroup* pg = &plan.groups[gi];
     const std::vector<size_t> g(pg->blobs.begin(), pg->blobs.end());
     for (size_t k = 0; k < g.size(); ++k) blobs[g[k]].out_base = pg->out_at[k];
@@ -3098,7 +3151,10 @@ void batch_stage_form(SlabBlob& b, const void* dst, int want_elem, sqy::DecodeBa
 // views (SQYAMD_Decode_BatchStrided_*): blob i's header shape must be row i of shapes (rank dimensions); a.dsts[i] is view i
 // windows (SQYAMD_Decode_BatchWindow_*, wa != nullptr): row i of shapes is the extent of a window of blob i that begins at row i of
 // wa->origins; a blob whose window is all of it is a view as above, and a call of such blobs only takes every path it takes there
-struct WindowArgs { const long* origins; const long* strides; };
+// compares (SQYAMD_Compare_BatchWindow_*, wa->compare != nullptr): a.dsts[i] is only read; every blob is a window, the whole ones too.  What
+// the driver leaves for its caller when it has handled every blob (done): each blob's code and its window's voxels
+struct CompareOut { unsigned long long* d_records; std::vector<int> rc; std::vector<uint64_t> voxels; bool done = false; };
+struct WindowArgs { const long* origins; const long* strides; CompareOut* compare = nullptr; };
 int decode_batch_on_device(Context& cx, const void* d_src_v, const BatchDecodeArgs& a, int want_elem, hipStream_t stream,
                            const std::vector<sqy::BatchView>* views = nullptr, const long* shapes = nullptr, unsigned rank = 0, const WindowArgs* wa = nullptr,
                            UpdateDecode* ud = nullptr)
@@ -3108,6 +3164,9 @@ int decode_batch_on_device(Context& cx, const void* d_src_v, const BatchDecodeAr
     sv.views = views;
     ViewLaunch unpacks;                                                 // (in front of the drain: alive until it has synchronised)
     WindowLaunch wcopies;
+    CompareLaunch ccopies;
+    CompareOut* const cmp = wa ? wa->compare : nullptr;
+    sv.records = cmp ? cmp->d_records : nullptr;
     std::vector<sqy::BatchWindow> wins(wa ? (size_t)a.nblobs : 0);
     DrainOnExit drain{stream, &cx.pending, cx.side};
     const size_t n = (size_t)a.nblobs;
@@ -3136,7 +3195,11 @@ int decode_batch_on_device(Context& cx, const void* d_src_v, const BatchDecodeAr
     // the blobs whose window is a part of them; none: a call of views
     std::vector<uint8_t> windowed(n, 0);
     bool any_window = false;
-    for (size_t i = 0; i < wins.size(); ++i) if (!wins[i].whole) { windowed[i] = 1; any_window = true; }
+    for (size_t i = 0; i < wins.size(); ++i) if (cmp || !wins[i].whole) { windowed[i] = 1; any_window = true; }
+    if (cmp) {                                                          // the records: zeros, VIEW_MIN all ones -- on the stream, behind the admission
+        std::vector<PendingEvent>* pend = &cx.pending;
+        SQY_TIMED("batch_compare_init", sqy::launch_batch_compare_init(cmp->d_records, (uint32_t)n, stream));
+    }
     if (a.decoded)
         for (size_t i = 0; i < n; ++i) a.decoded[i] = windowed[i] ? (long)(wins[i].Z * wins[i].Y * wins[i].X * (uint64_t)want_elem) : (long)blobs[i].raw;
     const bool joint_on = g_opt.decode_batch_joint.load() != 0;
@@ -3146,7 +3209,7 @@ int decode_batch_on_device(Context& cx, const void* d_src_v, const BatchDecodeAr
     std::vector<void*> dst_of(a.dsts, a.dsts + n);
     bool strided = false;
     if (views) {
-        const bool fused = joint_on && g_opt.batch_strided_fused.load() != 0, wfused = joint_on && g_opt.batch_window_fused.load() != 0;
+        const bool fused = joint_on && g_opt.batch_strided_fused.load() != 0, wfused = joint_on && (cmp ? g_opt.batch_compare_fused.load() : g_opt.batch_window_fused.load()) != 0;
         sv.direct.assign(n, 0);
         if (any_window) {
             sv.wins = &wins;
@@ -3167,7 +3230,8 @@ int decode_batch_on_device(Context& cx, const void* d_src_v, const BatchDecodeAr
         for (size_t i = 0; i < n; ++i)
             if ((windowed[i] || !(*views)[i].dense) && !sv.direct[i]) {
                 dst_of[i] = static_cast<uint8_t*>(cx.ws.batch_pack.p) + place[i];
-                if (windowed[i]) wcopies.add(a.dsts[i], dst_of[i], wins[i], sv.wviews[i], false);
+                if (cmp) ccopies.add(a.dsts[i], dst_of[i], wins[i], sv.wviews[i], false, cmp->d_records + sqy::kCompareFields * i);
+                else if (windowed[i]) wcopies.add(a.dsts[i], dst_of[i], wins[i], sv.wviews[i], false);
                 else unpacks.add(a.dsts[i], dst_of[i], (*views)[i]);
             }
     }
@@ -3217,13 +3281,26 @@ int decode_batch_on_device(Context& cx, const void* d_src_v, const BatchDecodeAr
         if (blobs[b].rc) continue;
         ViewLaunch one;
         WindowLaunch wone;
-        if (windowed[b]) wone.add(a.dsts[b], cx.ws.batch_pack_one.p, wins[b], sv.wviews[b], false);
+        CompareLaunch cone;
+        if (cmp) {                                                      // (a group that was given up may have added into the record: made ready again)
+            std::vector<PendingEvent>* pend = &cx.pending;
+            SQY_TIMED("batch_compare_init", sqy::launch_batch_compare_init(cmp->d_records + sqy::kCompareFields * b, 1, stream));
+            cone.add(a.dsts[b], cx.ws.batch_pack_one.p, wins[b], sv.wviews[b], false, cmp->d_records + sqy::kCompareFields * b);
+        } else if (windowed[b]) wone.add(a.dsts[b], cx.ws.batch_pack_one.p, wins[b], sv.wviews[b], false);
         else one.add(a.dsts[b], cx.ws.batch_pack_one.p, (*views)[b]);
-        if (launch_views(cx, stream, one, ViewLaunch::unpack, 0, want_elem) || launch_windows(cx, stream, wone, WindowLaunch::copy, want_elem)) return 1;
+        if (launch_views(cx, stream, one, ViewLaunch::unpack, 0, want_elem) || launch_windows(cx, stream, wone, WindowLaunch::copy, want_elem) ||
+            launch_compares(cx, stream, cone, CompareLaunch::compare, want_elem))
+            return 1;
         SQY_HIP(hipStreamSynchronize(stream));                          // (the launch's tables are this scope's)
     }
     // 4. the views with a place in the workspace: ONE unpack launch; the windows with one: ONE window copy
-    if (svp && (launch_views(cx, stream, unpacks, ViewLaunch::unpack, 0, want_elem) || launch_windows(cx, stream, wcopies, WindowLaunch::copy, want_elem))) return 1;
+    if (svp && (launch_views(cx, stream, unpacks, ViewLaunch::unpack, 0, want_elem) || launch_windows(cx, stream, wcopies, WindowLaunch::copy, want_elem) ||
+                launch_compares(cx, stream, ccopies, CompareLaunch::compare, want_elem)))
+        return 1;
+    if (cmp) {
+        for (size_t i = 0; i < n; ++i) { cmp->rc[i] = blobs[i].rc; cmp->voxels[i] = wins[i].Z * wins[i].Y * wins[i].X; }
+        cmp->done = true;
+    }
     for (const SlabBlob& b : blobs) if (b.rc) return b.rc;
     return 0;
 }
@@ -3266,6 +3343,44 @@ int decode_batch_window_device(const void* d_src, const long* offsets, const lon
     if (!lease.ctx) { std::fprintf(stderr, "[sqeazy]\t no usable HIP device\n"); return 1; }
     const WindowArgs wa{src_origins, dst_strides};
     return decode_batch_on_device(*lease.ctx, d_src, a, elem_size, static_cast<hipStream_t>(hip_stream), &views, dst_shapes, rank, &wa);
+}
+
+// SQYAMD_Compare_BatchWindow_*: decode_batch_window_device's admission (and the origins' sign, which needs no header), the batch driver
+// with a record per blob, ONE copy of the records behind its last launch.  stats: nblobs rows of sqy::kCompareFields words, zeroed on
+// every failure; the row of a damaged blob all ones
+int compare_batch_window_device(const void* d_src, const long* offsets, const long* lengths, int nblobs, const long* src_origins, const void* const* d_views,
+                                const long* view_shapes, const long* view_strides, unsigned rank, unsigned long long* stats, int elem_size, void* hip_stream)
+{
+    const size_t words = nblobs > 0 ? (size_t)nblobs * sqy::kCompareFields : 0;
+    if (stats) std::fill(stats, stats + words, 0ull);
+    if (!d_src || !offsets || !lengths || !d_views || !view_shapes || !stats || nblobs <= 0) { std::fprintf(stderr, "[sqeazy]\t compare batch: bad arguments\n"); return 1; }
+    std::vector<sqy::BatchView> views;
+    if (admit_views("compare batch", d_views, view_shapes, view_strides, rank, nblobs, elem_size, &views)) return 1;
+    for (size_t k = 0; src_origins && k < (size_t)nblobs * rank; ++k)
+        if (src_origins[k] < 0) { std::fprintf(stderr, "[sqeazy]\t compare batch: window %zu begins in front of its blob\n", k / rank); return 1; }
+    const std::vector<long> caps((size_t)nblobs, LONG_MAX);             // (a window's bytes are its view's: nothing to fit)
+    const BatchDecodeArgs a{offsets, lengths, nblobs, const_cast<void* const*>(d_views), caps.data(), nullptr};      // (read only: WindowArgs::compare)
+    if (admit_decode_batch(d_src, a)) return 1;
+    ContextLease lease;
+    if (!lease.ctx) { std::fprintf(stderr, "[sqeazy]\t no usable HIP device\n"); return 1; }
+    Context& cx = *lease.ctx;
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    if (cx.ws.batch_records.ensure(words * 8)) return 1;
+    unsigned long long* d_records = static_cast<unsigned long long*>(cx.ws.batch_records.p);
+    CompareOut out{d_records, std::vector<int>((size_t)nblobs, 0), std::vector<uint64_t>((size_t)nblobs, 0)};
+    const WindowArgs wa{src_origins, view_strides, &out};
+    const int rc = decode_batch_on_device(cx, d_src, a, elem_size, stream, &views, view_shapes, rank, &wa);
+    if (!out.done) return rc ? rc : 1;
+    std::vector<unsigned long long> host(words);
+    SQY_HIP(hipMemcpyAsync(host.data(), d_records, words * 8, hipMemcpyDeviceToHost, stream));
+    SQY_HIP(hipStreamSynchronize(stream));
+    for (size_t i = 0; i < (size_t)nblobs; ++i) {
+        unsigned long long* row = stats + i * sqy::kCompareFields;
+        if (out.rc[i]) { std::fill(row, row + sqy::kCompareFields, ~0ull); continue; }
+        std::copy(host.begin() + i * sqy::kCompareFields, host.begin() + (i + 1) * sqy::kCompareFields, row);
+        row[0] = out.voxels[i];
+    }
+    return rc;
 }
 
 int decode_batch_device(const void* d_src, const BatchDecodeArgs& a, int elem_size, void* hip_stream)
@@ -4475,6 +4590,22 @@ int SQYAMD_Decode_BatchWindow_UI8_Device(const void* d_src, const long* offsets,
 {
     return guarded([&]() -> int {
         return decode_batch_window_device(d_src, offsets, lengths, nblobs, src_origins, d_dsts, dst_shapes, dst_strides, shape_size, decoded_bytes, 1, hip_stream);
+    });
+}
+
+int SQYAMD_Compare_BatchWindow_UI16_Device(const void* d_src, const long* offsets, const long* lengths, int nblobs, const long* src_origins, const void* const* d_views,
+                                           const long* view_shapes, const long* view_strides, unsigned shape_size, unsigned long long* stats, void* hip_stream)
+{
+    return guarded([&]() -> int {
+        return compare_batch_window_device(d_src, offsets, lengths, nblobs, src_origins, d_views, view_shapes, view_strides, shape_size, stats, 2, hip_stream);
+    });
+}
+
+int SQYAMD_Compare_BatchWindow_UI8_Device(const void* d_src, const long* offsets, const long* lengths, int nblobs, const long* src_origins, const void* const* d_views,
+                                          const long* view_shapes, const long* view_strides, unsigned shape_size, unsigned long long* stats, void* hip_stream)
+{
+    return guarded([&]() -> int {
+        return compare_batch_window_device(d_src, offsets, lengths, nblobs, src_origins, d_views, view_shapes, view_strides, shape_size, stats, 1, hip_stream);
     });
 }
 

@@ -197,6 +197,17 @@ hipError_t launch_batch_window_copy(const BatchWindowJob* d_jobs, const uint32_t
 // (sqy::window_first_tile, window_tile_count); first_tile: the prefix sums of those counts
 hipError_t launch_bitswap1_decode_batch_window(const BatchWindowJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ntiles, int elem_size,
                                                hipStream_t stream);
+// ---- the compare of a window with its view (SQYAMD_Compare_BatchWindow_*) ----
+// A BatchWindowJob whose view is only read, and the job's record: eight 64-bit words in device memory (the header's SQYAMD_COMPARE_*
+// indices; word 0 is the host's).  Every workgroup that holds a voxel of the window adds its sums into the record with ONE set of integer
+// atomics; nothing else is written.  The records are made ready by launch_batch_compare_init: zeros, VIEW_MIN all ones.
+struct BatchCompareJob { const void* view; const void* dense; uint64_t Z, Y, X, sz, sy, bZ, bY, bX, oz, oy, ox, tile0; unsigned long long* record; uint64_t pad; };
+hipError_t launch_batch_compare_init(unsigned long long* d_records, uint32_t nrecords, hipStream_t stream);
+// launch_batch_window_copy's walk with both sides loaded: `dense` is the blob's dense volume (any voxel-aligned address); tile0 is not read
+hipError_t launch_batch_window_compare(const BatchCompareJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ntiles, int elem_size, hipStream_t stream);
+// launch_bitswap1_decode_batch_window's geometry and tables: planes + tail of the whole blob at `dense` (16-byte aligned)
+hipError_t launch_bitswap1_decode_batch_window_compare(const BatchCompareJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ntiles, int elem_size,
+                                                       hipStream_t stream);
 // ---- the update of a window (SQYAMD_Update_BatchWindow_*) ----
 // launch_batch_window_copy the other way round: the view's voxels are read and stored into the window inside the dense volume at `dense`
 // (written, whatever the job's type says); nothing else of it is touched

@@ -8218,6 +8218,214 @@ void bitswap1_decode_batch_window_kernel(const BatchWindowJob* __restrict__ jobs
     }
 }
 
+// ---- the compare of a window with its view (SQYAMD_Compare_BatchWindow_*) ------------------------------------------------------------------
+// The windowed decode's reads with a reduction where its stores were.  A thread gathers sqy::CompareSums over its 128 voxels (the text of
+// sqy_batch_window.hpp, which a sanitized host test runs too), the workgroup reduces them -- across the wavefront with cross-lane moves,
+// across its four wavefronts through LDS -- and ONE set of 64-bit integer atomics per workgroup goes into the job's record.  Integer
+// atomics: the result does not depend on the order in which workgroups finish.  Nothing but the records is written.
+__global__ __launch_bounds__(256)
+void batch_compare_init_kernel(unsigned long long* __restrict__ records, uint32_t nwords)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i < nwords) records[i] = (i & 7u) == 6u ? ~0ull : 0ull;        // zeros, VIEW_MIN all ones
+}
+
+// EVERY thread of the workgroup comes here, the ones without a voxel with the neutral element: nobody has returned in front of the
+// cross-lane steps or the barrier.  A workgroup without a voxel of the window issues no atomic.
+__device__ __forceinline__ void compare_publish(const CompareSums& s, unsigned long long* __restrict__ record)
+{
+    __shared__ unsigned long long part[4][8];
+    // widened before they leave the thread; in the record's order (word 0: the voxels, kept for the `any` test only)
+    unsigned long long v[8] = {s.n, s.ndiff, s.sum_abs, s.sum_sq, s.max_abs, s.view_sum, s.view_min, s.view_max};
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const unsigned long long o = __shfl_xor(v[k], d);
+            v[k] = k == 4 || k == 7 ? (o > v[k] ? o : v[k]) : k == 6 ? (o < v[k] ? o : v[k]) : v[k] + o;
+        }
+    }
+    const uint32_t tid = threadIdx.x;
+    if ((tid & 63u) == 0)
+#pragma unroll
+        for (int k = 0; k < 8; ++k) part[tid >> 6][k] = v[k];
+    __syncthreads();
+    if (tid >= 8u) return;
+    if (part[0][0] + part[1][0] + part[2][0] + part[3][0] == 0) return;
+    const unsigned long long a = part[0][tid], b = part[1][tid], c = part[2][tid], e = part[3][tid];
+    if (tid == 4u || tid == 7u) {
+        const unsigned long long ab = a > b ? a : b, ce = c > e ? c : e;
+        atomicMax(record + tid, ab > ce ? ab : ce);
+    } else if (tid == 6u) {
+        const unsigned long long ab = a < b ? a : b, ce = c < e ? c : e;
+        atomicMin(record + tid, ab < ce ? ab : ce);
+    } else if (tid != 0u)
+        atomicAdd(record + tid, a + b + c + e);
+}
+
+// batch_window_copy_kernel's walk with both sides loaded and nothing stored: tiles and pieces are those of the WINDOW's dense order, one
+// walk per side -- the window inside the blob's dense volume at job.dense, the caller's view.
+template <int ELEM>
+__global__ __launch_bounds__(256)
+void batch_window_compare_kernel(const BatchCompareJob* __restrict__ jobs, const uint32_t* __restrict__ first_tile, uint32_t njobs)
+{
+    constexpr uint32_t G = 16 / ELEM, PIECES = BSWB_TILE_VOX / G / 256u;      // voxels per piece, pieces per thread (128 voxels)
+    const uint32_t j = batch_job_of_tile(first_tile, njobs);
+    const BatchCompareJob job = jobs[j];
+    const uint64_t len = job.Z * job.Y * job.X;
+    const uint64_t base = (uint64_t)(blockIdx.x - first_tile[j]) * BSWB_TILE_VOX;
+    const ViewGeometry gs{job.Y, job.X, job.bY * job.bX, job.bX}, gv{job.Y, job.X, job.sz, job.sy};
+    const uint8_t* __restrict__ src = static_cast<const uint8_t*>(job.dense) + ((job.oz * job.bY + job.oy) * job.bX + job.ox) * ELEM;
+    const uint8_t* __restrict__ view = static_cast<const uint8_t*>(job.view);
+    CompareSums s = compare_sums_neutral();
+    for (uint32_t k = 0; k < PIECES; ++k) {
+        const uint64_t i0 = base + ((uint64_t)k * 256u + threadIdx.x) * G;
+        if (i0 >= len) break;
+        const uint32_t n = (uint32_t)(len - i0 < G ? len - i0 : G);
+        ViewWalk ws = view_walk_start(gs, i0), wv = view_walk_start(gv, i0);
+        const uint4 x = view_gather16<ELEM>(src, gs, ws, n), y = view_gather16<ELEM>(view, gv, wv, n);
+        const uint32_t a[4] = {x.x, x.y, x.z, x.w}, b[4] = {y.x, y.y, y.z, y.w};
+        compare_piece<ELEM>(&s, a, b, 0u, n);
+    }
+    compare_publish(s, job.record);
+}
+
+// bitswap1_decode_batch_window_kernel with window_compare16 where it scatters: the same grid, clip, plane loads and transposes; a thread
+// whose run holds nothing of the window loads no plane word and joins the reduction with the neutral element.
+template <int ELEM>
+__global__ __launch_bounds__(256)
+void bitswap1_decode_batch_window_compare_kernel(const BatchCompareJob* __restrict__ jobs, const uint32_t* __restrict__ first_tile, uint32_t njobs)
+{
+    constexpr uint32_t W = 8 * ELEM, WPT = BSWB_THREAD_VOX / W;        // voxels per word, words per thread
+    const uint32_t j = batch_job_of_tile(first_tile, njobs);
+    const BatchCompareJob job = jobs[j];
+    const uint32_t own = blockIdx.x - first_tile[j], tid = threadIdx.x;
+    const uint64_t tile = job.tile0 + own;
+    const uint64_t len = job.bZ * job.bY * job.bX, seg = len / W, L = seg * W;
+    const WindowGeometry g{job.bY, job.bX, job.oz, job.oy, job.ox, job.Z, job.Y, job.X, job.sz, job.sy};
+    const uint8_t* __restrict__ in = static_cast<const uint8_t*>(job.dense);
+    const uint8_t* __restrict__ view = static_cast<const uint8_t*>(job.view);
+    CompareSums s = compare_sums_neutral();
+    WindowPiece cur;
+    if (own == 0 && tid < len - L) {                                  // tail voxels [L, len): verbatim in the stream, those of the window
+        WindowClip ct = window_clip_start(g, L + tid, 1);
+        if (window_clip_next(g, &ct, &cur)) compare_voxel(&s, view_voxel_load<ELEM>(in, L + tid), view_voxel_load<ELEM>(view, cur.dst_off));
+    }
+    const uint64_t w0 = (tile * 256u + tid) * WPT;
+    const uint32_t nw = w0 >= seg ? 0u : (uint32_t)(seg - w0 < WPT ? seg - w0 : WPT);      // this thread's words
+    WindowClip c = window_clip_start(g, nw ? w0 * W : 0, (uint64_t)nw * W);
+    bool have = nw != 0 && window_clip_next(g, &c, &cur);
+    if (have) {                                                       // (else: nothing of the run inside the window, no plane word is loaded)
+        const uint64_t plane_bytes = seg * ELEM;
+        const bool wide = nw == WPT && ((reinterpret_cast<uintptr_t>(in) | plane_bytes) & 15u) == 0;
+        if constexpr (ELEM == 2) {
+            uint32_t pl[16][4];                                       // pl[b] = eight words of the plane that carries bit b
+            if (wide) {
+#pragma unroll
+                for (int b = 0; b < 16; ++b) {
+                    const uint4 t = *reinterpret_cast<const uint4*>(in + (uint64_t)(15 - b) * plane_bytes + w0 * 2u);
+                    pl[b][0] = t.x; pl[b][1] = t.y; pl[b][2] = t.z; pl[b][3] = t.w;
+                }
+            } else {
+                const uint16_t* in16 = reinterpret_cast<const uint16_t*>(in);
+#pragma unroll
+                for (int b = 0; b < 16; ++b) { pl[b][0] = 0; pl[b][1] = 0; pl[b][2] = 0; pl[b][3] = 0; }
+#pragma unroll
+                for (uint32_t i = 0; i < WPT; ++i)
+                    if (i < nw)
+#pragma unroll
+                        for (int b = 0; b < 16; ++b) pl[b][i >> 1] |= (uint32_t)in16[(uint64_t)(15 - b) * seg + w0 + i] << (16u * (i & 1u));
+            }
+#pragma unroll
+            for (uint32_t q = 0; q < 4; ++q) {                        // words w0 + 2 q (group A, low halves) and w0 + 2 q + 1 (group B)
+                if (2 * q >= nw || !have) break;
+                uint32_t r[16];
+#pragma unroll
+                for (int b = 0; b < 16; ++b) r[b] = pl[b][q];
+                transpose16x16_pairs(r);                              // r[i] = voxel 15 - i of group A | of group B << 16
+                uint32_t ga[8], gb[8];
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    ga[k] = __builtin_amdgcn_perm(r[14 - 2 * k], r[15 - 2 * k], 0x05040100u);
+                    gb[k] = __builtin_amdgcn_perm(r[14 - 2 * k], r[15 - 2 * k], 0x07060302u);
+                }
+                window_compare16<2>(view, g, c, cur, have, ga, 32u * q, 8, &s);
+                window_compare16<2>(view, g, c, cur, have, ga + 4, 32u * q + 8u, 8, &s);
+                if (2 * q + 1 >= nw) break;
+                window_compare16<2>(view, g, c, cur, have, gb, 32u * q + 16u, 8, &s);
+                window_compare16<2>(view, g, c, cur, have, gb + 4, 32u * q + 24u, 8, &s);
+            }
+        } else {
+            uint32_t pw[8][4];                                        // pw[b] = 16 bytes of the plane that carries bit b
+            if (wide) {
+#pragma unroll
+                for (int b = 0; b < 8; ++b) {
+                    const uint4 t = *reinterpret_cast<const uint4*>(in + (uint64_t)(7 - b) * plane_bytes + w0);
+                    pw[b][0] = t.x; pw[b][1] = t.y; pw[b][2] = t.z; pw[b][3] = t.w;
+                }
+            } else {
+#pragma unroll
+                for (int b = 0; b < 8; ++b) { pw[b][0] = 0; pw[b][1] = 0; pw[b][2] = 0; pw[b][3] = 0; }
+#pragma unroll
+                for (uint32_t i = 0; i < WPT; ++i)
+                    if (i < nw)
+#pragma unroll
+                        for (int b = 0; b < 8; ++b) pw[b][i >> 2] |= (uint32_t)in[(uint64_t)(7 - b) * seg + w0 + i] << (8u * (i & 3u));
+            }
+#pragma unroll
+            for (uint32_t gq = 0; gq < 16; gq += 2) {
+                if (gq >= nw || !have) break;
+                uint32_t d[4];
+#pragma unroll
+                for (uint32_t u = 0; u < 2; ++u) {
+                    // (bitswap1_decode_batch_strided_kernel's gather and transpose: afterwards byte i of hi:lo = voxel 7 - i)
+                    constexpr uint32_t Zs = 0x0c;                     // v_perm selector: a zero byte
+                    const uint32_t cc = (gq + u) & 3u, wdx = (gq + u) >> 2;
+                    const uint32_t s01 = cc | ((4u + cc) << 8) | (Zs << 16) | (Zs << 24), s23 = Zs | (Zs << 8) | (cc << 16) | ((4u + cc) << 24);
+                    uint32_t lo_ = __builtin_amdgcn_perm(pw[1][wdx], pw[0][wdx], s01) | __builtin_amdgcn_perm(pw[3][wdx], pw[2][wdx], s23);
+                    uint32_t hi_ = __builtin_amdgcn_perm(pw[5][wdx], pw[4][wdx], s01) | __builtin_amdgcn_perm(pw[7][wdx], pw[6][wdx], s23);
+                    uint32_t y;
+                    y = (lo_ ^ (lo_ >> 7)) & 0x00AA00AAu; lo_ ^= y ^ (y << 7);
+                    y = (hi_ ^ (hi_ >> 7)) & 0x00AA00AAu; hi_ ^= y ^ (y << 7);
+                    y = (lo_ ^ (lo_ >> 14)) & 0x0000CCCCu; lo_ ^= y ^ (y << 14);
+                    y = (hi_ ^ (hi_ >> 14)) & 0x0000CCCCu; hi_ ^= y ^ (y << 14);
+                    y = (lo_ ^ (hi_ << 4)) & 0xF0F0F0F0u; lo_ ^= y; hi_ ^= y >> 4;
+                    d[2 * u] = __builtin_bswap32(hi_);                // voxels 0..3 of the word
+                    d[2 * u + 1] = __builtin_bswap32(lo_);            // voxels 4..7
+                }
+                window_compare16<1>(view, g, c, cur, have, d, 8u * gq, nw - gq >= 2u ? 16u : 8u, &s);
+            }
+        }
+    }
+    compare_publish(s, job.record);
+}
+
+hipError_t launch_batch_compare_init(unsigned long long* d_records, uint32_t nrecords, hipStream_t stream)
+{
+    if (nrecords == 0) return hipSuccess;
+    hipLaunchKernelGGL(batch_compare_init_kernel, dim3((nrecords * 8u + 255u) / 256u), dim3(256), 0, stream, d_records, nrecords * 8u);
+    return hipGetLastError();
+}
+
+hipError_t launch_batch_window_compare(const BatchCompareJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ntiles, int elem_size, hipStream_t stream)
+{
+    if (njobs == 0 || ntiles == 0) return hipSuccess;
+    if (elem_size == 2) hipLaunchKernelGGL(batch_window_compare_kernel<2>, dim3(ntiles), dim3(256), 0, stream, d_jobs, d_first_tile, njobs);
+    else if (elem_size == 1) hipLaunchKernelGGL(batch_window_compare_kernel<1>, dim3(ntiles), dim3(256), 0, stream, d_jobs, d_first_tile, njobs);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+hipError_t launch_bitswap1_decode_batch_window_compare(const BatchCompareJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ntiles, int elem_size,
+                                                       hipStream_t stream)
+{
+    if (njobs == 0 || ntiles == 0) return hipSuccess;
+    if (elem_size == 2) hipLaunchKernelGGL(bitswap1_decode_batch_window_compare_kernel<2>, dim3(ntiles), dim3(256), 0, stream, d_jobs, d_first_tile, njobs);
+    else if (elem_size == 1) hipLaunchKernelGGL(bitswap1_decode_batch_window_compare_kernel<1>, dim3(ntiles), dim3(256), 0, stream, d_jobs, d_first_tile, njobs);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
 // ---- the update of a window (SQYAMD_Update_BatchWindow_*) ----------------------------------------------------------------------------------
 // window_scatter16's mirror image: the n voxels (n <= 16 / ELEM) at offset p of the thread's run, packed as they lie in a dense copy; those
 // inside the window come from the view, the others are zero.  Pieces come in ascending p.

@@ -390,10 +390,10 @@ bool admit_window(const std::vector<uint64_t>& header_shape, const long* origin,
     return true;
 }
 
-BatchWindowLayout batch_window_layout(uint64_t njobs)
+BatchWindowLayout batch_window_layout(uint64_t njobs, uint64_t job_bytes)
 {
     BatchWindowLayout l;
-    l.tiles_at = round_up(njobs * kBatchWindowJobBytes, 16);
+    l.tiles_at = round_up(njobs * job_bytes, 16);
     l.total = l.tiles_at + (njobs + 1) * 4;
     return l;
 }

@@ -162,7 +162,12 @@ bool admit_window(const std::vector<uint64_t>& header_shape, const long* origin,
 constexpr uint64_t kBatchWindowJobBytes = 112;
 // The tables of one window launch, one upload: njobs jobs at 0 | tiles_at (16-byte aligned): njobs + 1 words of prefix sums | total
 struct BatchWindowLayout { uint64_t tiles_at = 0, total = 0; };
-BatchWindowLayout batch_window_layout(uint64_t njobs);
+BatchWindowLayout batch_window_layout(uint64_t njobs, uint64_t job_bytes = kBatchWindowJobBytes);
+// ---- the compare of a window with its view (SQYAMD_Compare_BatchWindow_*) ----
+// a job of the compare launches (sqy::BatchCompareJob, sqy_kernels.h: a window job and its record); the tables have the window launches'
+// layout with jobs of this size.  A record: kCompareFields 64-bit words per blob, records side by side in one workspace buffer
+constexpr uint64_t kBatchCompareJobBytes = 128;
+constexpr uint64_t kCompareFields = 8, kCompareViewMin = 6;
 
 // ---- batch decode (SQYAMD_Decode_Batch_*): many blobs, one launch per kernel ----
 // What the planner knows of blob i: the bytes its LZ4 stage decodes to, the LZ4 block size, whether it may take the joint path at all
