@@ -495,8 +495,10 @@ SQY_FUNCTION_PREFIX void SQYAMD_Release_Workspace(void);
  *   "noise_digest"                    1 [SQY_NO_NOISE_DIGEST=1 -> 0]  frames in place: the bit-plane transpose leaves bucket and tag of every position
  *                                     liblz4's search probes in a chunk of noise; the LZ4 parse proves such chunks incompressible from them
  *                                     instead of reading the plane stream again (0: it reads)
- *   "transpose_blocks_per_cu"         32 [SQY_TRANSPOSE_BLOCKS_PER_CU=<1..64>]  frames in place: workgroups (two wavefronts) of the transposer's grid
- *                                     per CU (32: as many as fit; fewer leave room for the small kernels of other calls in flight -- measured: slower)
+ *   "transpose_tiles_per_wave"        1 [SQY_TRANSPOSE_TILES_PER_WAVE=<1..64>]  frames in place: tiles of 8192 voxels one wavefront of the transposer
+ *                                     takes, one after the other; its grid is tiles / (2 x this) workgroups of two wavefronts (a measurement
+ *                                     switch, same bytes at every value: longer waves keep the kernels of other calls in flight waiting for a
+ *                                     slot -- measured: slower.  Replaces "transpose_blocks_per_cu", which capped the grid per CU)
  *   "stored_tail_index"               1 [SQY_NO_STORED_TAIL_INDEX=1 -> 0]  decode of the chunked layout: the stored frames at the end of the LZ4
  *                                     stream (bit planes of noise) are looked for where they must start, the scan for frame headers stops in
  *                                     front of them (0: it reads the whole stream)

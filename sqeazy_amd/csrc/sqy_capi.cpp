@@ -74,7 +74,7 @@ struct Options {
     std::atomic<long> tail_scan;                        // serial-layout decode: the walk over the tails as a scan
     std::atomic<long> decode_two_waves;                 // chunked-layout decode: two wavefronts per frame (one parses, one copies)
     std::atomic<long> noise_digest;                     // frames in place: the transpose leaves the noise digest, the parse proves noise chunks empty from it
-    std::atomic<long> transpose_blocks_per_cu;          // frames in place: workgroups of the transposer's grid per CU
+    std::atomic<long> transpose_tiles_per_wave;         // frames in place: tiles one wavefront of the transposer takes (sizes its grid)
     std::atomic<long> stored_tail_index;                // decode, chunked layout: the stored frames at the stream's end are found where they must start, not by the scan
     std::atomic<long> host_l2_bytes;                    // rmestbkrd: the host CPU's L2 size as the reference's compass reads it (detected; tests set it)
     std::atomic<long> decode_frames_subset;             // frame-range decode: only the LZ4 frames the range needs, where the pipeline allows (0: full decode + copy)
@@ -100,7 +100,7 @@ struct Options {
           block_parallel(env_flag("SQY_NO_BLOCK_PARALLEL") ? 0 : 1), block_parallel_warmup(env_number("SQY_BLOCK_PARALLEL_WARMUP", 65536, 0, kWarmupMax)),
           block_parallel_stats(env_flag("SQY_BLOCK_PARALLEL_STATS")), tail_scan(env_flag("SQY_NO_TAIL_SCAN") ? 0 : 1),
           decode_two_waves(env_flag("SQY_NO_DECODE_TWO_WAVES") ? 0 : 1), noise_digest(env_flag("SQY_NO_NOISE_DIGEST") ? 0 : 1),
-          transpose_blocks_per_cu(env_number("SQY_TRANSPOSE_BLOCKS_PER_CU", 32, 1, 64)), stored_tail_index(env_flag("SQY_NO_STORED_TAIL_INDEX") ? 0 : 1),
+          transpose_tiles_per_wave(env_number("SQY_TRANSPOSE_TILES_PER_WAVE", sqy::kBitswap1TilesPerWave, 1, 64)), stored_tail_index(env_flag("SQY_NO_STORED_TAIL_INDEX") ? 0 : 1),
           host_l2_bytes((long)sqy::host_l2_cache_bytes()), decode_frames_subset(env_flag("SQY_NO_DECODE_FRAMES_SUBSET") ? 0 : 1),
           decode_slabs_joint(env_flag("SQY_NO_DECODE_SLABS_JOINT") ? 0 : 1), decode_batch_joint(env_flag("SQY_NO_DECODE_BATCH_JOINT") ? 0 : 1),
           decode_batch_group_bytes(env_number("SQY_DECODE_BATCH_GROUP_BYTES", (long)kSlabsGroupBytes, 1, (long)kSlabsGroupBytes)), encode_batch_joint(env_flag("SQY_NO_ENCODE_BATCH_JOINT") ? 0 : 1),
@@ -108,7 +108,7 @@ struct Options {
           encode_batch_joint_max_bytes(env_number("SQY_ENCODE_BATCH_JOINT_MAX_BYTES", kBatchJointMaxDefault, 0, kBatchBytesMax)),
           batch_strided_fused(env_flag("SQY_NO_BATCH_STRIDED_FUSED") ? 0 : 1), batch_window_fused(env_flag("SQY_NO_BATCH_WINDOW_FUSED") ? 0 : 1),
           batch_update_fused(env_flag("SQY_NO_BATCH_UPDATE_FUSED") ? 0 : 1), batch_compare_fused(env_flag("SQY_NO_BATCH_COMPARE_FUSED") ? 0 : 1), stage_lanes(env_number("SQY_STAGE_LANES", kStageLanesDefault, 0, 2)),
-          parse_lanes(env_number("SQY_PARSE_LANES", kParseLanesDefault, 1, sqy::LanePicker::kMaxLanes)) { sqy::set_bitswap1_blocks_per_cu(transpose_blocks_per_cu.load()); }
+          parse_lanes(env_number("SQY_PARSE_LANES", kParseLanesDefault, 1, sqy::LanePicker::kMaxLanes)) { sqy::set_bitswap1_tiles_per_wave(transpose_tiles_per_wave.load()); }
     std::atomic<long>* find(const char* name)
     {
         if (!name) return nullptr;
@@ -120,7 +120,7 @@ struct Options {
         if (!std::strcmp(name, "tail_scan")) return &tail_scan;
         if (!std::strcmp(name, "decode_two_waves")) return &decode_two_waves;
         if (!std::strcmp(name, "noise_digest")) return &noise_digest;
-        if (!std::strcmp(name, "transpose_blocks_per_cu")) return &transpose_blocks_per_cu;
+        if (!std::strcmp(name, "transpose_tiles_per_wave")) return &transpose_tiles_per_wave;
         if (!std::strcmp(name, "stored_tail_index")) return &stored_tail_index;
         if (!std::strcmp(name, "host_l2_bytes")) return &host_l2_bytes;
         if (!std::strcmp(name, "decode_frames_subset")) return &decode_frames_subset;
@@ -260,18 +260,24 @@ struct ProfScope {
         SQY_HIP(launch);                                                                                \
     } while (0)
 
+void prof_add(const char* name, double ms)
+{
+    std::lock_guard<std::mutex> lock(g_prof_mu);
+    size_t i = 0;
+    for (; i < g_prof.size(); ++i) if (g_prof[i].name == name) break;
+    if (i == g_prof.size()) g_prof.push_back(ProfEntry{name, 0, 0});
+    g_prof[i].ms += ms;
+    g_prof[i].launches += 1;
+}
+
+// a launch that is counted, not timed (no events next to a kernel of a few microseconds in front of a call's transpose)
+void prof_count(const char* name) { if (g_prof_on.load()) prof_add(name, 0); }
+
 void prof_collect(std::vector<PendingEvent>& pending)
 {
     for (PendingEvent& p : pending) {
         float ms = 0;
-        if (hipEventSynchronize(p.b) == hipSuccess && hipEventElapsedTime(&ms, p.a, p.b) == hipSuccess) {
-            std::lock_guard<std::mutex> lock(g_prof_mu);
-            size_t i = 0;
-            for (; i < g_prof.size(); ++i) if (g_prof[i].name == p.name) break;
-            if (i == g_prof.size()) g_prof.push_back(ProfEntry{p.name, 0, 0});
-            g_prof[i].ms += ms;
-            g_prof[i].launches += 1;
-        }
+        if (hipEventSynchronize(p.b) == hipSuccess && hipEventElapsedTime(&ms, p.a, p.b) == hipSuccess) prof_add(p.name, ms);
         ev_give(p.a);
         ev_give(p.b);
     }
@@ -690,7 +696,9 @@ struct EncodeCall {
         sqy::Lz4InplacePlan place;              // frames in place: chunk k of the plane stream sits at d_dst + body0 + k * in_stride
         uint32_t* digest = nullptr;             // frames in place: the noise digest (sqy_kernels.h: launch_bitswap1_u16), digest_stride words per chunk
         uint32_t digest_stride = 0;
-        bool dedupe_cleared = false;            // the duplicate search's table and the dense list's counter were zeroed in front of the transpose
+        sqy::Lz4TableClearPlan clear;           // frames in place: who empties the duplicate search's table and the dense list's counter
+        bool dedupe_cleared = false;            // .. a launch that does so is queued (the clear kernel, or the transposer's): lz4 launches no fills
+                                                // (set behind that launch's success only, and gone with the call: no context keeps it)
         const uint64_t* frame_map = nullptr;    // frame_shuffle directly in front: frames are read through the map
         uint64_t frame_bytes = 0;
     } prep;
@@ -886,9 +894,14 @@ struct EncodeCall {
             prep.digest_stride = dstride;
         }
         if (take_lanes(lane_lock)) return 1;
-        SQY_HIP(sqy::launch_lz4_dedupe_clear(ws->dedupe.p, prep.dedupe, static_cast<uint32_t*>(ws->plan.p), stream));
-        prep.dedupe_cleared = true;
-        if (stamps) stamps->stamp(CallStamps::clear_launched);
+        // who empties the search's table: on the lanes the transposer's own launch (bitswap1 hands it prep.clear), else the clear kernel
+        prep.clear = sqy::lz4_table_clear_plan(prep.dedupe, true, lanes && lanes->taken());
+        if (prep.clear.who == sqy::Lz4TableClearPlan::kernel) {
+            SQY_HIP(sqy::launch_lz4_dedupe_clear(ws->dedupe.p, prep.dedupe, static_cast<uint32_t*>(ws->plan.p), stream));
+            prof_count("lz4_dedupe_clear");
+            prep.dedupe_cleared = true;
+        }
+        if (stamps) stamps->stamp(CallStamps::clear_launched);            // (on the lanes: the place of the launch that is no longer there)
         return 0;
     }
 
@@ -904,11 +917,19 @@ struct EncodeCall {
         const bool on_lanes = lanes && lanes->taken();
         TransposeChain tc;
         if (chain_wait(tc, inplace)) return 1;
-        if (cur_elem == 2)
+        if (cur_elem == 2) {
+            sqy::Bitswap1Clear clr;
+            if (inplace && prep.clear.who == sqy::Lz4TableClearPlan::transposer) {
+                clr.table = static_cast<uint8_t*>(ws->dedupe.p) + prep.clear.table_at;
+                clr.key_bytes = prep.clear.key_bytes;
+                clr.bytes = prep.clear.bytes;
+                clr.zero_word = static_cast<uint32_t*>(ws->plan.p);
+            }
             SQY_TIMED("bitswap1_u16", sqy::launch_bitswap1_u16(reinterpret_cast<const uint16_t*>(cur), reinterpret_cast<uint16_t*>(out), cur_len, stream, ph,
                                                                inplace ? (uint32_t)prep.place.chunk : 0, side.p, side.w, side.X, inplace ? prep.digest : nullptr,
-                                                               prep.digest_stride));
-        else
+                                                               prep.digest_stride, &clr));
+            if (clr.bytes) prep.dedupe_cleared = true;
+        } else
             SQY_TIMED("bitswap1_u8", sqy::launch_bitswap1_u8(cur, out, cur_len, stream));
         if (chain_record(tc)) return 1;
         if (stamps) stamps->stamp(CallStamps::transpose_launched);
@@ -4677,7 +4698,7 @@ int SQYAMD_Set_Option(const char* name, long value)
     std::atomic<long>* o = g_opt.find(name);
     if (!o) return 1;
     if (o == &g_opt.block_parallel_warmup) { if (value < 0 || value > kWarmupMax) return 1; }
-    else if (o == &g_opt.transpose_blocks_per_cu) { if (value < 1 || value > 64) return 1; sqy::set_bitswap1_blocks_per_cu(value); }
+    else if (o == &g_opt.transpose_tiles_per_wave) { if (value < 1 || value > 64) return 1; sqy::set_bitswap1_tiles_per_wave(value); }
     else if (o == &g_opt.host_l2_bytes) { if (value < 0 || value > (long)UINT32_MAX) return 1; }
     else if (o == &g_opt.stage_lanes) { if (value < 0 || value > 2) return 1; }
     else if (o == &g_opt.encode_batch_group_bytes) { if (value < 1 || value > kBatchBytesMax) return 1; }

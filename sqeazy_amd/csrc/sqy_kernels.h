@@ -34,10 +34,23 @@ struct Lz4DedupeArgs {
 // every position liblz4's search probes from probe 961 on when it starts with a chunk and finds nothing, digest_stride
 // (= lz4_noise_digest_stride(gap_chunk)) words per chunk of the plane stream; the LZ4 parse of a chunk takes its batches from there as long
 // as nothing has matched (Lz4DedupeArgs::digest) instead of reading the plane bytes again
+// clear (frames in place only; bytes == 0: nothing): the launch also empties the duplicate search's table -- `key_bytes` bytes of keys (0)
+// and, right behind them, bytes - key_bytes bytes of values (~0) at `table` (8-byte aligned, bytes a multiple of 16: what
+// lz4_dedupe_layout lays out), and *zero_word = 0 -- so that no launch_lz4_dedupe_clear is needed in front of it (sqy_pipeline.hpp:
+// lz4_table_clear_plan decides who clears).  Complete for any len; the first reader is a kernel behind this one.
+struct Bitswap1Clear {
+    uint8_t* table = nullptr;
+    uint32_t key_bytes = 0, bytes = 0;
+    uint32_t* zero_word = nullptr;
+};
 hipError_t launch_bitswap1_u16(const uint16_t* in, uint16_t* out, uint64_t len, hipStream_t stream, uint32_t* piece_hash = nullptr,
                                uint32_t gap_chunk = 0, const uint16_t* side = nullptr, uint32_t side_w = 0, uint32_t X = 0,
-                               uint32_t* digest = nullptr, uint32_t digest_stride = 0);
-void set_bitswap1_blocks_per_cu(long n);      // workgroups (two waves) of the in-place transposer per CU (default 32: as many as fit)
+                               uint32_t* digest = nullptr, uint32_t digest_stride = 0, const Bitswap1Clear* clear = nullptr);
+// frames in place: the transposer's grid is tiles / (2 waves x tiles per wave) workgroups -- how many tiles of 8192 voxels one of its
+// wavefronts takes, one after the other (a measurement switch; the default is what profiles/transpose_grid.txt measured: the shorter
+// the waves, the sooner the other calls' parse and small kernels find a slot)
+constexpr long kBitswap1TilesPerWave = 1;
+void set_bitswap1_tiles_per_wave(long n);
 uint64_t bitswap1_piece_hash_words(const void* in, const void* out, uint64_t len);
 // duplicate chunks of a plane stream (chunk a multiple of 1 KiB): dup_of[k] = the earliest chunk with the same bytes (k itself when
 // there is none); the hashes only nominate, a byte compare decides.  base: the search's workspace, laid out by lz4_dedupe_layout -- the

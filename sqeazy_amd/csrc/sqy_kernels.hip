@@ -205,8 +205,28 @@ template <bool GAP>
 __global__ __launch_bounds__(256)       // (launched in blocks of 128; bounds of 128 let the compiler take 173 registers instead of 127)
 void bitswap1_u16_regs(const uint16_t* __restrict__ in, uint16_t* __restrict__ out, uint64_t n_tiles, uint64_t seg_words,
                        uint32_t* __restrict__ piece_hash, uint32_t gap_shift, const uint16_t* __restrict__ side, uint32_t side_w, uint32_t X,
-                       uint32_t* __restrict__ digest, uint32_t digest_stride)
+                       uint32_t* __restrict__ digest, uint32_t digest_stride, const Bitswap1Clear clr)
 {
+    // GAP, clr.bytes != 0: this launch also empties the duplicate search's table (keys 0, values ~0, one more word 0: what
+    // lz4_dedupe_clear_kernel does) -- the launch in front of the transposer, on the one lane every call's transpose goes through, is
+    // then not needed.  One 16-byte store per thread of the launch's first workgroups (the loop only matters for grids smaller than the
+    // table: a volume of a few tiles); nobody reads the table before this kernel has ended, so nothing waits for anything here.  The
+    // table starts behind a key per chunk, 8 bytes each: up to 8 bytes in front of the first 16-byte boundary and behind the last.
+    if (GAP && clr.bytes) {
+        const Lz4TableClearStores st = lz4_table_clear_stores(reinterpret_cast<uintptr_t>(clr.table), clr.bytes);
+        const uint64_t nthr = (uint64_t)gridDim.x * blockDim.x;
+        for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < st.nvec; i += nthr) {
+            const uint32_t off = st.head + ((uint32_t)i << 4);
+            const v4u fill = {lz4_table_clear_dword(off, clr.key_bytes), lz4_table_clear_dword(off + 4u, clr.key_bytes),
+                              lz4_table_clear_dword(off + 8u, clr.key_bytes), lz4_table_clear_dword(off + 12u, clr.key_bytes)};
+            *reinterpret_cast<v4u*>(clr.table + off) = fill;
+        }
+        if (blockIdx.x == 0 && threadIdx.x == 0) {
+            if (st.head) *reinterpret_cast<uint64_t*>(clr.table) = 0ull;                                       // (keys: key_bytes >= 16)
+            if (st.tail_at < clr.bytes) *reinterpret_cast<uint64_t*>(clr.table + st.tail_at) = ~0ull;          // (values: bytes >= key_bytes + 16)
+            if (clr.zero_word) *clr.zero_word = 0u;
+        }
+    }
     const int lane = threadIdx.x & 63;
     // (the wave number through readfirstlane: tile and every piece address below are then scalar, the lane part a 32-bit offset)
     const uint32_t wpb = blockDim.x >> 6;
@@ -6485,12 +6505,13 @@ static inline int num_cus()
     return cus;
 }
 
-std::atomic<long> g_bsw_blocks_per_cu{32};       // (measurement switch: SQYAMD_Set_Option("transpose_blocks_per_cu"))
-void set_bitswap1_blocks_per_cu(long n) { g_bsw_blocks_per_cu.store(n); }
+std::atomic<long> g_bsw_tiles_per_wave{kBitswap1TilesPerWave};       // (measurement switch: SQYAMD_Set_Option("transpose_tiles_per_wave"))
+void set_bitswap1_tiles_per_wave(long n) { g_bsw_tiles_per_wave.store(n); }
 
 hipError_t launch_bitswap1_u16(const uint16_t* in, uint16_t* out, uint64_t len, hipStream_t stream, uint32_t* piece_hash, uint32_t gap_chunk,
-                               const uint16_t* side, uint32_t side_w, uint32_t X, uint32_t* digest, uint32_t digest_stride)
+                               const uint16_t* side, uint32_t side_w, uint32_t X, uint32_t* digest, uint32_t digest_stride, const Bitswap1Clear* clear)
 {
+    if (clear && clear->bytes && (!gap_chunk || len == 0)) return hipErrorInvalidValue;      // (only the in-place transposer clears)
     if (len == 0) return hipSuccess;
     if (side && (X == 0 || X % 128u != 0 || side_w % 128u != 0 || side_w > X || len % X != 0 || (reinterpret_cast<uintptr_t>(side) & 15) ||
                  len % BSW_TILE_VOX != 0 || (reinterpret_cast<uintptr_t>(in) & 15) || (!gap_chunk && (reinterpret_cast<uintptr_t>(out) & 15))))
@@ -6502,12 +6523,25 @@ hipError_t launch_bitswap1_u16(const uint16_t* in, uint16_t* out, uint64_t len, 
             return hipErrorInvalidValue;
         // (round 6, measured: fewer resident blocks -- 8 .. 2 per CU instead of as many as fit -- let the small kernels of the other calls in
         // flight start sooner, and cost the transposes and with them the step 3 .. 12 %)
-        const uint64_t n_tiles = len / BSW_TILE_VOX, want = (n_tiles + 1) / 2, cap = (uint64_t)num_cus() * (g_bsw_blocks_per_cu.load() > 0 ? (uint64_t)g_bsw_blocks_per_cu.load() : 32u);    // (blocks of two waves: see below)
+        // (round 9) The grid follows from a fixed number of tiles per wave, not from a cap per CU: a wave's lifetime is then the same for
+        // every volume, and the waves of other calls' kernels find a slot as often as one of these short waves ends (measured, four calls in
+        // flight, 8 / 4 / 2 / 1 tiles per wave: the other calls' parses 1.26 / 1.23 / 1.19 / 1.15 ms, this kernel the same at every setting:
+        // profiles/transpose_grid.txt).  The kernel's loop stays (any grid is correct); it runs tiles-per-wave times.
+        const uint64_t n_tiles = len / BSW_TILE_VOX;
+        const long tpw_opt = g_bsw_tiles_per_wave.load();
+        const uint64_t tpw = tpw_opt > 0 ? (uint64_t)tpw_opt : (uint64_t)kBitswap1TilesPerWave;
+        const uint64_t grid = (n_tiles + 2 * tpw - 1) / (2 * tpw);                        // (blocks of two waves: see below)
+        if (grid > 0x7fffffffull) return hipErrorInvalidValue;
         // (the noise digest: only when every plane segment is a whole number of chunks -- a lane's place inside its chunk is then the same
         // in all sixteen planes -- and the chunk long enough for the search to reach step 16)
         if (digest && ((len / 8) % gap_chunk != 0 || gap_chunk < 16384u || digest_stride == 0)) return hipErrorInvalidValue;
-        hipLaunchKernelGGL(bitswap1_u16_regs<true>, dim3((unsigned)(want < cap ? want : cap)), dim3(128), 0, stream, in, out, n_tiles, len / 16,
-                           piece_hash, (uint32_t)__builtin_ctz(gap_chunk), side, side_w, X, digest, digest_stride);
+        // (the duplicate search's table emptied by this launch: the region is what lz4_dedupe_layout lays out, keys then values, 8-byte aligned)
+        const Bitswap1Clear clr = clear ? *clear : Bitswap1Clear();
+        if (clr.bytes && (!clr.table || (reinterpret_cast<uintptr_t>(clr.table) & 7) || (clr.bytes & 15) || (clr.key_bytes & 7) || clr.key_bytes < 16 ||
+                          clr.key_bytes + 16 > clr.bytes))
+            return hipErrorInvalidValue;
+        hipLaunchKernelGGL(bitswap1_u16_regs<true>, dim3((unsigned)grid), dim3(128), 0, stream, in, out, n_tiles, len / 16,
+                           piece_hash, (uint32_t)__builtin_ctz(gap_chunk), side, side_w, X, digest, digest_stride, clr);
         return hipGetLastError();
     }
     const uint64_t seg_words = len / 16;
@@ -6526,7 +6560,7 @@ hipError_t launch_bitswap1_u16(const uint16_t* in, uint16_t* out, uint64_t len, 
         const uint64_t cap = (uint64_t)num_cus() * 32;
         const unsigned grid = (unsigned)(want < cap ? want : cap);
         hipLaunchKernelGGL(bitswap1_u16_regs<false>, dim3(grid), dim3(128), 0, stream, in, out, n_tiles, seg_words, piece_hash, 0u, side, side_w, X,
-                           (uint32_t*)nullptr, 0u);
+                           (uint32_t*)nullptr, 0u, Bitswap1Clear());
     }
     const uint64_t first_word = n_tiles * (BSW_TILE_VOX / 16);
     const uint64_t rest_words = seg_words - first_word;

@@ -621,6 +621,20 @@ Lz4DedupeLayout lz4_dedupe_layout(const Lz4EncodeLayout& lay, uint64_t piece_has
     return d;
 }
 
+Lz4TableClearPlan lz4_table_clear_plan(const Lz4DedupeLayout& d, bool frames_in_place, bool on_lanes)
+{
+    Lz4TableClearPlan p;
+    if (!d.total || !frames_in_place) return p;
+    p.who = Lz4TableClearPlan::kernel;
+    const uint64_t key_bytes = d.table * 8, bytes = d.table * 12;
+    if (!on_lanes || d.tab_val_at != d.tab_key_at + key_bytes || (d.tab_key_at & 7) || (bytes & 15) || key_bytes < 16 || bytes > 0xffffffffull) return p;
+    p.who = Lz4TableClearPlan::transposer;
+    p.table_at = d.tab_key_at;
+    p.key_bytes = (uint32_t)key_bytes;
+    p.bytes = (uint32_t)bytes;
+    return p;
+}
+
 Lz4InplacePlan lz4_inplace_plan(const Lz4EncodeLayout& lay, uint64_t piece_hash_words, bool lz4_is_last, bool takes_offset, unsigned dst_mod16,
                                 uint64_t capacity, uint64_t header_max)
 {

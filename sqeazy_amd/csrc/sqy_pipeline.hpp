@@ -323,6 +323,38 @@ uint32_t lz4_noise_digest_words(const Lz4Params& p, const Lz4EncodeLayout& lay, 
 struct Lz4DedupeLayout { uint64_t table = 0, work_at = 0, tab_key_at = 0, tab_val_at = 0, dup_at = 0, holes_at = 0, total = 0; };     // total 0: no search
 // the search runs on piece hashes (piece_hash_words of them, 0: none offered) of a chunked layout of more than one chunk of whole KiB
 Lz4DedupeLayout lz4_dedupe_layout(const Lz4EncodeLayout& lay, uint64_t piece_hash_words);
+// Who empties the search's table (keys 0, values ~0) and the dense list's counter of a single-volume encode call, in front of the key table:
+//   fills       no frames in place: launch_lz4_dedupe's two fill dispatches behind the transpose
+//   kernel      frames in place: launch_lz4_dedupe_clear in front of the transpose
+//   transposer  frames in place on the library's lanes: the transposer's own launch (Bitswap1Clear: table_at = tab_key_at, key_bytes and
+//               bytes of the keys and of keys + values) -- the clear launch would sit on the one lane every call's transpose goes through.
+//               A call that stays on its caller's stream keeps the kernel, and so does a table the transposer's stores do not fit
+//               (never one that lz4_dedupe_layout laid out: 64 slots and more, 8-byte aligned, values right behind the keys)
+struct Lz4TableClearPlan {
+    enum Who { fills, kernel, transposer } who = fills;
+    uint64_t table_at = 0;
+    uint32_t key_bytes = 0, bytes = 0;
+};
+Lz4TableClearPlan lz4_table_clear_plan(const Lz4DedupeLayout& d, bool frames_in_place, bool on_lanes);
+// The transposer's stores of that clear (the kernel and tests/sanitize/table_clear_test.cpp call these two).  The table starts behind a
+// key per chunk, 8 bytes each, so it may begin and end 8 bytes off a 16-byte boundary: `head` bytes (0 or 8) in front of the first whole
+// 16-byte vector, nvec vectors at head + 16 i, and what is left from tail_at on (== bytes: nothing), head and tail as one 8-byte store each.
+#if defined(__HIP__) || defined(__HIPCC__)
+#define SQY_PIPE_HD __host__ __device__
+#else
+#define SQY_PIPE_HD
+#endif
+struct Lz4TableClearStores { uint32_t head, nvec, tail_at; };
+SQY_PIPE_HD inline Lz4TableClearStores lz4_table_clear_stores(uint64_t table_address, uint32_t bytes)
+{
+    Lz4TableClearStores s;
+    s.head = (16u - (uint32_t)(table_address & 15u)) & 15u;
+    s.nvec = (bytes - s.head) >> 4;
+    s.tail_at = s.head + (s.nvec << 4);
+    return s;
+}
+// the dword at byte `off` of the table: a key's half (0) or a value (~0)
+SQY_PIPE_HD inline uint32_t lz4_table_clear_dword(uint32_t off, uint32_t key_bytes) { return off < key_bytes ? 0u : 0xffffffffu; }
 
 // The block-parallel parse of block-linked frames (sqy_kernels.h: Lz4SpecArgs).  Worth it for few long frames: the frame walks would
 // leave the chip empty

@@ -3,9 +3,11 @@ and, with the library's call stamps of the same run (tools/cycle_stamps.py), whe
 
     python tools/inflight_timeline.py <kernel_trace.csv> [stamps.json]
 
-On the lanes the kernels of one call sit on two queues (clear + transpose on the transpose lane, the rest on the call's parse lane),
-so a call is put together from the stamps: record `seq` is the call's place on the transpose lane (the n-th clear and transpose
-there), `lane` its parse lane (the calls of one lane, in seq order, are the key tables of one queue in start order).  The cycle of a
+On the lanes the kernels of one call sit on two queues (the transpose -- with a clear in front of it in traces of libraries whose
+transposer does not empty the duplicate search's table itself -- on the transpose lane, the rest on the call's parse lane), so a call is
+put together from the stamps: record `seq` is the call's place on the transpose lane (the n-th transpose there), `lane` its parse lane
+(the calls of one lane, in seq order, are the key tables of one queue in start order).  Without clears in the trace "clear" below
+reads "the call's first kernel": the transpose.  The cycle of a
 call -- from its entry to the same thread's next entry -- is then split into
 
   d  entry -> first launch (d1: the poll of the caller's stream and the lane mutex, d2: lanes taken -> clear launched)
@@ -106,10 +108,13 @@ def calls_from_stamps(rows, st):
     byk = collections.defaultdict(list)
     for r in rows:
         byk[r[2]].append(r)
-    # the transpose lane's queue: where the last n clears are
-    tq = collections.Counter(r[3] for r in byk["clear"][-n:]).most_common(1)[0][0]
-    clears = [r for r in byk["clear"] if r[3] == tq][-n:]
+    # the transpose lane's queue: where the last n transposes are
+    tq = collections.Counter(r[3] for r in byk["transp"][-n:]).most_common(1)[0][0]
     transps = [r for r in byk["transp"] if r[3] == tq][-n:]
+    clears = [r for r in byk["clear"] if r[3] == tq][-n:]
+    if not clears:
+        print("  no clear on the transpose lane: a call's first kernel is its transpose")
+        clears = [(t[0], t[0], "clear", t[3]) for t in transps]
     if len(clears) < n or len(transps) < n:
         print("the trace holds %d clears and %d transposes on queue %d, the stamps %d calls: no attribution" % (len(clears), len(transps), tq, n))
         return None
