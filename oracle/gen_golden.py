@@ -414,6 +414,9 @@ RASTER = [((32, 64, 96), None), ((16, 32, 48), None), ((33, 64, 97), 5), ((7, 13
 # rmbkrd_neighbor5x5x5: extents from {1, 2, 4, 5, 6, 9}
 NB_SHAPES = [(9, 9, 5), (9, 6, 5), (9, 5, 6), (6, 6, 5), (9, 9, 6), (6, 9, 5), (9, 6, 6), (9, 9, 9), (6, 6, 6), (5, 6, 9), (4, 9, 9), (2, 6, 6), (6, 5, 9),
              (1, 9, 9), (9, 9, 4), (9, 4, 9), (9, 5, 5), (9, 9, 1), (9, 2, 9), (1, 1, 1), (2, 5, 6), (9, 9, 2)]
+# .. and volumes of more than one tile of the product's kernel: the smallest with centres at z = 64..67; x and y tiles with centres on both
+# sides of the seam; a third chunk that lies wholly behind z_end = 68; three z chunks, three x tiles, two y tiles, z_end = 132 in the last chunk
+NB_SEAM_SHAPES = [(72, 6, 70), (70, 20, 68), (129, 18, 70), (136, 18, 134)]
 
 
 def neighbor5_reads_in_bounds(shape):
@@ -479,6 +482,18 @@ def stage_table():
                 T.append(r)
     # ---- histogram statistics (hist_impl.hpp) ----
     T += _rows("histogram", ["uint16", "uint8"], [(1, 1, 5000), (1, 1, 1), (3, 5, 7)], ["gamma", "two_level", "zero", "max", "random"], 2400)
+    # ---- rmbkrd_neighbor5x5x5 across the seams of the product's tiles (64 x 16 columns, chunks of 64 frames); appended, so that the rows
+    # above keep their ids.  The reference reads in bounds on all four (asserted), so none is `undefined` ----
+    seams = []
+    for shape in NB_SEAM_SHAPES:
+        assert R.neighbor5_defined(shape) and neighbor5_reads_in_bounds(shape), shape
+        for dt in ("uint16", "uint8"):
+            for t, f in ((36, 0.5), (18, 0.25)):
+                seams += _rows("rmbkrd_neighbor5x5x5", [dt], [shape], ["low80"], 5000 + len(seams), {"threshold": t, "fraction": f})
+            seams += _rows("rmbkrd_neighbor5x5x5", [dt], [shape], ["planted"], 5000 + len(seams), {"threshold": 100, "fraction": 0.0})
+    T += seams
+    # ---- rmestbkrd on faces that leave the histogram kernel's window, and a face of more than 32768 voxels ----
+    T += _rows("rmestbkrd", ["uint16"], [(4, 40, 520), (3, 130, 260)], ["spread"], 5100)
     for i, r in enumerate(T):
         r["id"] = case_id(r, i)
     return T

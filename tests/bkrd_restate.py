@@ -63,6 +63,25 @@ def neighbor5_counts(vol, threshold):
     return box5(box5(box5(e, 1), X), YX)[off:off + N].reshape(Z, Y, X)
 
 
+def neighbor5_counts_direct(vol, threshold):
+    """the same count by its definition, with no box sum: the 125 flat offsets dz*Y*X + dy*X + dx added one by one (each a shifted
+    slice of the whole volume); a neighbour outside [0, N) is not counted.  Independent of neighbor5_counts, which separates the sum the
+    way the kernel does."""
+    vol = np.ascontiguousarray(vol)
+    Z, Y, X = vol.shape
+    b = (vol.reshape(-1) < threshold).astype(np.uint8)
+    N = b.size
+    n = np.zeros(N, np.uint8)                              # at most 125
+    for dz in range(-2, 3):
+        for dy in range(-2, 3):
+            for dx in range(-2, 3):
+                d = dz * Y * X + dy * X + dx
+                lo, hi = max(0, -d), min(N, N - d)         # the voxels c with 0 <= c + d < N
+                if lo < hi:
+                    n[lo:hi] += b[lo + d:hi + d]
+    return n.reshape(Z, Y, X).astype(np.int16)
+
+
 def neighbor5_centres(shape):
     Z, Y, X = shape
     z, y, x = np.ogrid[:Z, :Y, :X]

@@ -42,7 +42,105 @@ def stage_input(kind, dtype, shape, seed):
     if kind == "near_wrap":                                # around 70000 mod 2^bits (4464 / 112): 4 in 13 below it
         lo = (70000 % (top + 1)) - 40
         return rng.integers(lo, lo + 130, shape).astype(dtype)
+    if kind == "planted":                                  # 200 everywhere, single voxels and pairs of 10 next to the tile seams
+        v = np.full(n, min(200, top), dtype)
+        singles, pairs = planted_sites(shape, seed)
+        Z, Y, X = shape
+        for z, y, x in singles + [s for p in pairs for s in p]:
+            v[(z * Y + y) * X + x] = 10
+        return v.reshape(shape)
+    if kind == "spread":
+        return spread(dtype, shape, rng)
     raise KeyError(kind)
+
+
+# ---- planted: rmbkrd_neighbor5x5x5 at the seams of its kernel's tiles ---------------------------------------------------------------------
+# bkrd_neighbor5_kernel cuts the volume into columns of 64 (x) by 16 (y) voxels and walks them in chunks of 64 frames: a count that is not
+# carried from one tile or chunk into the next shows at the centres within two voxels of a seam
+PLANTED_SEAMS = {"z": (64, 128), "y": (16,), "x": (64, 128)}
+
+
+def _near(seams, extent):
+    """s - 3 .. s + 2 for every seam s: 61..66 and 125..130, or 13..18 (the voxels that exist); every voxel of an axis too short for a seam"""
+    c = [s + d for s in seams for d in range(-3, 3) if s + d < extent]
+    return c if c else list(range(extent))
+
+
+def planted_sites(shape, seed):
+    """(singles, pairs) of (z, y, x): voxels whose coordinates all come from _near(), taken in the seed's order as long as the 125 flat
+    neighbours of one share no voxel with those of another -- a centre then counts at most one single.  Every second site tries to become
+    a pair: a partner one or two voxels away (towards the seams as the seed has it), whose neighbours it shares; a centre near a pair
+    counts one or two."""
+    Z, Y, X = shape
+    YX = Y * X
+    rng = np.random.default_rng(seed)
+    cand = [(z, y, x) for z in _near(PLANTED_SEAMS["z"], Z) for y in _near(PLANTED_SEAMS["y"], Y) for x in _near(PLANTED_SEAMS["x"], X)]
+    inside = set(cand)
+    # two voxels share a neighbour exactly when their flat distance is a difference of two of the 125 offsets
+    shared = {dz * YX + dy * X + dx for dz in range(-4, 5) for dy in range(-4, 5) for dx in range(-4, 5)}
+    flat = lambda s: (s[0] * Y + s[1]) * X + s[2]
+    steps = [(1, 0, 0), (0, 0, 1), (0, 1, 0), (1, 0, 1), (2, 0, 0), (0, 0, 2), (1, 1, 1), (2, 0, 2)]
+    taken, singles, pairs = [], [], []
+    free = lambda s: all(flat(s) - t not in shared for t in taken)
+    for k in rng.permutation(len(cand)):
+        s = cand[k]
+        if not free(s):
+            continue
+        mate = None
+        if (len(singles) + len(pairs)) % 2 == 1:
+            for j in rng.permutation(len(steps)):
+                m = tuple(a + b for a, b in zip(s, steps[j]))
+                if m in inside and free(m):
+                    mate = m
+                    break
+        if mate is None:
+            singles.append(s)
+            taken.append(flat(s))
+        else:
+            pairs.append((s, mate))
+            taken += [flat(s), flat(mate)]
+    return singles, pairs
+
+
+# ---- spread: rmestbkrd's face histograms away from one narrow band ------------------------------------------------------------------------
+# bkrd_face_histo_kernel counts every 256 voxels of a face into a window of 16384 bins around the first of them: these first values sit at
+# the window's switch (8192 / 8193), in the open (40000) and at its clamp (57343 / 57344 / 65535)
+SPREAD_STARTS = (8192, 8193, 40000, 57343, 57344, 65535)
+
+
+def spread(dtype, shape, rng):
+    """the interior over the whole range; every face the estimator samples cut into segments of 256 voxels: segment k starts with
+    SPREAD_STARTS[k % 6] exactly (8-bit: that value >> 8), holds values within 4000 (15) of it and, where the range has room, two voxels
+    more than 8192 below and two more than 8192 above it.  The rows y = Y-1 take the first three starts only, so that their support --
+    the smallest of the four -- lies in the middle of the range."""
+    Z, Y, X = shape
+    top = int(np.iinfo(dtype).max)
+    wide = top > 255
+    v = rng.integers(0, top + 1, shape).astype(np.int64)
+    flat = v.reshape(-1)
+
+    def fill(base, length, starts, k0):
+        for k, a in enumerate(range(0, length, 256)):
+            L = min(256, length - a)
+            s = starts[(k0 + k) % len(starts)] >> (0 if wide else 8)
+            seg = s + rng.integers(-4000, 4001, L) // (1 if wide else 256)
+            seg = np.where(seg > top, 2 * top - seg, np.abs(seg))                    # folded back into the range, not piled up at its ends
+            seg[0] = s
+            if wide and L >= 8:
+                at = 1 + rng.permutation(L - 1)[:4]
+                if s - 8193 >= 0:
+                    seg[at[:2]] = rng.integers(0, s - 8192, 2)
+                if s + 8193 <= top:
+                    seg[at[2:]] = rng.integers(s + 8193, top + 1, 2)
+            flat[base + a:base + a + L] = seg
+
+    fill(0, Y * X, SPREAD_STARTS, 0)
+    fill((Z - 1) * Y * X, Y * X, SPREAD_STARTS, 3)
+    for i, z in enumerate((1, Z // 2, Z - 2)):
+        if 0 < z < Z - 1:
+            fill(z * Y * X, X, SPREAD_STARTS, 2 * i + 1)
+            fill(z * Y * X + (Y - 1) * X, X, SPREAD_STARTS[:3], i)
+    return v.astype(dtype)
 
 
 def stage_volume(case):

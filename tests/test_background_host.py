@@ -141,3 +141,130 @@ def test_restatement_matches_the_reference_loops(shape):
     vol = rng.integers(0, 10, shape).astype(np.uint16)
     for t, f in ((5, 0.5), (3, 0.25), (8, 0.75), (5, 0.0)):
         assert np.array_equal(R.neighbor5(vol, t, np.float32(f)), _neighbor5_loops(vol, t, f)), (shape, t, f)
+
+
+# ---- the constructions of tests/bkrd_seam_cases.py, held to what they claim (tests/test_gpu_background_seams.py runs them) ----------------
+import bkrd_seam_cases as S                                                   # noqa: E402
+from ref_stage_inputs import PLANTED_SEAMS, SPREAD_STARTS, planted_sites, stage_input  # noqa: E402
+
+SEAM_SHAPES = [(72, 6, 70), (70, 20, 68), (129, 18, 70), (136, 18, 134)]
+
+
+@pytest.mark.parametrize("shape", SEAM_SHAPES + S.CHUNK_END_SHAPES)
+def test_direct_count_equals_the_box_sums(shape):
+    """the 125 offsets added one by one against the separated sum the kernel shares with the restatement: equal at every voxel, the
+    centres among them, on volumes of more than one tile and chunk"""
+    centres = R.neighbor5_centres(shape)
+    assert centres[64:].any() or shape in ((70, 6, 66),)                       # centres behind the first chunk (but for the zero-fill shape)
+    for vol, t in ((stage_input("low80", np.uint16, shape, 1), 36), (stage_input("low80", np.uint8, shape, 2), 18),
+                   (stage_input("planted", np.uint16, shape, 3), 100)):
+        direct, box = R.neighbor5_counts_direct(vol, t), R.neighbor5_counts(vol, t)
+        assert np.array_equal(direct[centres], box[centres]) and np.array_equal(direct, box), (shape, t)
+        assert np.array_equal(S.neighbor5_direct(vol, t, 0.25)[0], R.neighbor5(vol, t, 0.25)), (shape, t)
+
+
+def test_low80_cuts_every_chunk_of_the_largest_shape():
+    """(136, 18, 134), fraction 0.5: each of the three z chunks has thousands of centres on both sides of the cut at threshold 40, and
+    hundreds (the last chunk has four planes of centres) at the goldens' 36"""
+    shape = (136, 18, 134)
+    vol = stage_input("low80", np.uint16, shape, 5)
+    for t in (40, 36):
+        want, n = S.neighbor5_direct(vol, t, 0.5)
+        at = R.neighbor5_centres(shape) & (vol >= t)
+        for zs in (0, 64, 128):
+            chunk = np.zeros(shape, bool)
+            chunk[zs:zs + 64] = True
+            least = 1000 if t == 40 else 400
+            assert (at & chunk & (want != 0)).sum() > least and (at & chunk & (want == 0)).sum() > least, (t, zs)
+
+
+@pytest.mark.parametrize("shape,seeds", S.PLANTED)
+def test_planted_volumes_reach_every_seam(shape, seeds):
+    Z, Y, X = shape
+    seen = {f: set() for f in S.PLANTED_FRACTIONS}
+    for seed in seeds:
+        singles, pairs = planted_sites(shape, seed)
+        for z, y, x in S.planted_voxels(shape, seed):                          # coordinates within 3 of a seam, in every axis
+            assert min(abs(z + .5 - s) for s in PLANTED_SEAMS["z"]) < 3 and abs(y + .5 - 16) < 3 and min(abs(x + .5 - s) for s in PLANTED_SEAMS["x"]) < 3
+        vol = stage_input("planted", np.uint16, shape, seed)
+        assert (vol == 10).sum() == len(singles) + 2 * len(pairs)
+        n = R.neighbor5_counts_direct(vol, S.PLANTED_THRESHOLD)
+        assert n.max() == (2 if pairs else 1)                                    # neighbourhoods of different sites are disjoint
+        lone = stage_input("planted", np.uint16, shape, seed)
+        for p in pairs:
+            lone[p[1]] = 200
+        assert R.neighbor5_counts_direct(lone, S.PLANTED_THRESHOLD).max() == 1
+        for f in S.PLANTED_FRACTIONS:
+            seen[f] |= S.seam_outcomes(vol, seed, f)
+    wanted = S.seam_outcomes_wanted(shape)
+    assert {(a, s) for a, s, _, _ in wanted} >= ({("z", 64), ("x", 64), ("y", 16)} | ({("z", 128), ("x", 128)} if Z > 130 else set()))
+    for f in S.PLANTED_FRACTIONS:
+        assert seen[f] >= wanted, (f, sorted(wanted - seen[f]))
+
+
+def test_planted_names_the_voxel_of_a_count_lost_between_chunks():
+    """a model of the kernel's chunk walk whose ring starts empty at zs (frames zs-2 and zs-1 not loaded): the first voxel the planted
+    test would name lies in the first plane of the second chunk"""
+    shape, seed = (136, 18, 134), 0
+    vol = stage_input("planted", np.uint16, shape, seed)
+    want, n = S.neighbor5_direct(vol, S.PLANTED_THRESHOLD, 0.0)
+    b = (vol < S.PLANTED_THRESHOLD).astype(np.int16)
+    got = want.copy()
+    for zs in (64, 128):                                                          # what the two lost planes would have added
+        lost = np.zeros(shape, np.int16)
+        for z in (zs, zs + 1):
+            for p in range(z - 2, zs):
+                only = np.zeros(shape, np.int16)
+                only[p] = b[p]
+                lost[z] += R.neighbor5_counts_direct(200 - 190 * only, S.PLANTED_THRESHOLD)[z]
+        broken = n - lost
+        keep = R.neighbor5_centres(shape) & (vol >= S.PLANTED_THRESHOLD) & ~(broken > 0)
+        got[zs:zs + 2] = np.where(keep, vol, 0)[zs:zs + 2]
+    diff = S.first_difference(got, want, n)
+    assert diff is not None and diff[0] == 64 and diff[3:] == (200, 0, 1), diff
+
+
+def test_spread_volumes_leave_the_window():
+    vol = S.spread_volume(S.WINDOW_SHAPE, np.uint16)
+    segs = S.face_segments(vol, S.L2_ALL)
+    bases = {S.window_base(int(seg[0])) for _, _, seg in segs}
+    assert bases >= {0, 1, 40000 - 8192, 57343 - 8192, 65536 - S.WIN}                # the switch, open bases, the clamp
+    assert {int(seg[0]) for _, _, seg in segs} == set(SPREAD_STARTS)
+    for (_, piece, seg), (_, piece2, seg2) in zip(segs, segs[1:]):
+        if piece == piece2:
+            assert seg[0] != seg2[0]                                                   # neighbours overlap in global bins, from different bases
+    for _, _, seg in segs:
+        if len(seg) < 8:
+            continue
+        v0, wb = int(seg[0]), S.window_base(int(seg[0]))
+        assert ((seg >= wb) & (seg < wb + S.WIN)).sum() >= len(seg) // 2
+        assert (seg < wb).any() == (v0 > 8192) and (seg >= wb + S.WIN).any() == (v0 + 8193 < 65536), v0
+    assert sum(len(seg) for face, _, seg in segs if face == 2) == 3 * 520 and 520 > 2 * 256
+    # the second pass of the 128 workgroups, on data like the above
+    for shape, l2, portion in [(S.STRIDE_SHAPE, S.L2_ALL, 33800)] + [(S.PORTION_SHAPE, l2, p) for p, l2 in S.PORTION_L2.items()]:
+        assert R.face_portion(shape[1] * shape[2], l2) == portion > 128 * 256 - 1
+    for shape in (S.WINDOW_SHAPE, S.STRIDE_SHAPE, S.PORTION_SHAPE):
+        for dtype in (np.uint16, np.uint8):
+            v = S.spread_volume(shape, dtype)
+            sup = [float(R.support(h)) for h in R.face_histograms(v, S.L2_ALL)]
+            assert len(set(sup)) == 4 and min(sup) == sup[3], sup                      # four supports, the last decides
+            out = R.rmestbkrd(v, S.L2_ALL)
+            assert 0.2 < (out != 0).mean() < 0.8
+
+
+@pytest.mark.parametrize("dtype", [np.uint16, np.uint8])
+def test_support_volumes_stop_where_they_mean_to(dtype):
+    cases = S.support_cases(dtype)
+    stops = set()
+    for lo, hi, k in cases:
+        vol = S.support_volume(dtype, lo, hi, k)
+        m, t = S.support_crossing(lo, hi, k), S.support_threshold(lo, hi, k)
+        for h in R.face_histograms(vol, S.L2_ALL):
+            assert int(h[lo]) + int(h[hi]) == h.sum() and int(h[hi]) in ((10, 3) if k == 10 else (9, 2))
+            running = np.cumsum(h, dtype=np.uint64).astype(np.float64) / float(h.sum())
+            assert int(np.nonzero(running > np.float64(np.float32(0.99)))[0][0]) == m, (lo, hi, k)
+        assert R.rmestbkrd_threshold(vol, S.L2_ALL) == t, (lo, hi, k)
+        inner = vol[1:-1, 1:-1]
+        assert all((inner == x).any() for x in (t - 1, t, t + 1) if 0 <= x <= np.iinfo(dtype).max)
+        stops.add(m)
+    assert stops >= set(S.SUPPORT_BINS[dtype])

@@ -142,6 +142,15 @@ def _admitted(sqy, pipeline, views, dtype):
     return out
 
 
+def _settle():
+    """what torch queued on its own stream for the buffers of a call -- the parents' copies, the canary fill -- is complete before the call
+    is made: the library orders a call behind hip_stream only, "work on OTHER streams that touches d_src or d_dst is the caller's to
+    synchronise" (include/sqeazy_amd.h).  Without this a fill that waits in a hardware queue behind another thread's kernels can land on
+    top of the blobs a call on a stream of its own has just written"""
+    import torch
+    torch.cuda.current_stream(_dev()).synchronize()
+
+
 def _encode(sqy, pipeline, views, dtype, strided=True, joint=True, stream=None, keep=False):
     """the strided call on the views of fresh device parents, slots of canaries: (rc, blobs) -- or, keep = True, (rc, (buffer, offsets,
     lengths)) to pass straight through.  The canaries around the slots hold, the parents are unchanged; on the joint path a slot holds its
@@ -151,6 +160,7 @@ def _encode(sqy, pipeline, views, dtype, strided=True, joint=True, stream=None, 
     n = len(views)
     slot = max(sqy.max_compressed_length(pipeline, v.shape, dtype) for v in views) + 13          # (no multiple of 16)
     buf = torch.full((2 * GAP + slot * n,), CANARY, dtype=torch.uint8, device=_dev())
+    _settle()
     rc, offs, lens = sqy.encode_batch_strided_device(pipeline, [P.ptr(v) for v in views], [v.shape for v in views],
                                                      [v.strides for v in views] if strided else None, dtype, buf.data_ptr() + GAP, slot, stream=stream)
     got = P.read()
@@ -261,6 +271,7 @@ DECODE_CASES = [("bitswap1->lz4", np.uint16), ("bitswap1->lz4", np.uint8), ("bit
 def _decode(sqy, buf, offs, lens, views, dtype, stream=None):
     """the strided decode into pattern-filled parents: (rc, decoded, the parents' bytes, the Parents)"""
     P = Parents(dtype, data=False)
+    _settle()
     rc, decoded = sqy.decode_batch_strided_device(buf.data_ptr(), offs, lens, [P.ptr(v) for v in views], [v.shape for v in views], [v.strides for v in views],
                                                   dtype, stream=stream)
     return rc, decoded, P.read(), P

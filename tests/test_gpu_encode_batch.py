@@ -65,6 +65,7 @@ def _batch(sqy, pipeline, vols, dev, nthreads=0, cap=None, src_shift=0, stream=N
         cap = max(sqy.max_compressed_length(pipeline, v.shape, dtype) for v in vols) + 13          # (no multiple of 16)
     slot = cap
     buf = torch.full((2 * GAP + slot * len(vols),), CANARY, dtype=torch.uint8, device=dev)
+    torch.cuda.current_stream(dev).synchronize()         # the sources and the fill are torch's stream's: the caller's to complete (sqeazy_amd.h)
     rc, offs, lens = sqy.encode_batch_device(pipeline, [r.data_ptr() + src_shift for r in srcs], [v.shape for v in vols], dtype, buf.data_ptr() + GAP, slot,
                                              nthreads=nthreads, stream=stream)
     torch.cuda.synchronize()
