@@ -272,6 +272,30 @@ SQY_FUNCTION_PREFIX int SQYAMD_Decode_Frames_UI8_Device(const void* d_src, long 
 SQY_FUNCTION_PREFIX int SQYAMD_Decode_Frames_UI16(const char* src, long srclength, long z0, long nz, char* dst, long dst_capacity);
 SQY_FUNCTION_PREFIX int SQYAMD_Decode_Frames_UI8(const char* src, long srclength, long z0, long nz, char* dst, long dst_capacity);
 
+/* A box of ONE blob decoded into a view of the box's shape: voxel k of the view (dst_shape, `rank` extents, outermost first) is voxel
+ * origin + k of the volume SQYAMD_Decode_*_Device gives for the blob.  Exactly the box's voxels are written: the gaps between the view's
+ * rows and frames and everything around the view keep their bytes.  dst_strides: the view's strides in voxels under the rules of
+ * SQYAMD_Decode_BatchStrided_* (innermost 1, no dimension overlaps the next one's reach), NULL: dense.  d_dst is aligned to the voxel size.
+ * Checked before anything is written, every refusal returns 1: NULL pointers, a negative origin, rank 0 or above 3, srclength <= 0 (these
+ * before a device is looked for), the view rules, a blob of the other voxel type, a rank that is not the header's, an extent below 1,
+ * origin + extent past the header's shape (a sum that overflows `long` is past it).  A damaged LZ4 frame that the box needs gives
+ * SQY_Decode's composite code; the view may then hold anything.
+ * Stream, context, ordering and thread-safety rules are those of SQYAMD_Decode_Frames_*_Device.  For the blobs of that call's subset path
+ * only the LZ4 frames the box's range [origin[0], origin[0] + extent[0]) needs are decoded (a damaged frame OUTSIDE that range then goes
+ * unnoticed: DESIGN.md 7), and the inverse bit-plane transposer stores the box's voxels straight into the view; every other blob is
+ * decoded whole into the library's workspace and the box copied out -- same bytes, the full decode's time ("decode_box_subset" = 0:
+ * every blob). */
+SQY_FUNCTION_PREFIX int SQYAMD_Decode_Box_UI16_Device(const void* d_src, long srclength, const long* origin, void* d_dst, const long* dst_shape,
+                                                      const long* dst_strides, unsigned rank, void* hip_stream);
+SQY_FUNCTION_PREFIX int SQYAMD_Decode_Box_UI8_Device(const void* d_src, long srclength, const long* origin, void* d_dst, const long* dst_shape,
+                                                     const long* dst_strides, unsigned rank, void* hip_stream);
+/* host-pointer variants: the blob is staged as in SQY_Decode_*, the box comes back dense (extent[0] * .. voxels; 1 where dst_capacity,
+ * in bytes, is less) */
+SQY_FUNCTION_PREFIX int SQYAMD_Decode_Box_UI16(const char* src, long srclength, const long* origin, const long* extent, unsigned rank, char* dst,
+                                               long dst_capacity);
+SQY_FUNCTION_PREFIX int SQYAMD_Decode_Box_UI8(const char* src, long srclength, const long* origin, const long* extent, unsigned rank, char* dst,
+                                              long dst_capacity);
+
 /* The volume a set of z-slab blobs makes, decoded with one call: the inverse of SQYAMD_PipelineEncode_Slabs_*_Device and the reader of
  * the multi-GPU container.  Blob i lies at d_src + offsets[i], lengths[i] bytes (host arrays; any alignment).  Every blob is a complete sqeazy
  * blob of the entry point's voxel type; all have the same rank and the same shape[1..]; their shape[0] may differ.  Slab i's voxels land at
@@ -507,6 +531,8 @@ SQY_FUNCTION_PREFIX void SQYAMD_Release_Workspace(void);
  *                                     (the one option that changes bytes): set it to the value of the host whose blobs are to be matched
  *   "decode_frames_subset"            1 [SQY_NO_DECODE_FRAMES_SUBSET=1 -> 0]  SQYAMD_Decode_Frames_*: only the LZ4 frames the range needs, where
  *                                     the pipeline allows (0: every blob decoded whole and the range copied out -- same bytes)
+ *   "decode_box_subset"               1 [SQY_NO_DECODE_BOX_SUBSET=1 -> 0]  SQYAMD_Decode_Box_*: only the LZ4 frames the box's z-range needs, where
+ *                                     the pipeline allows (0: every blob decoded whole and the box copied out -- same bytes)
  *   "decode_slabs_joint"              1 [SQY_NO_DECODE_SLABS_JOINT=1 -> 0]  SQYAMD_Decode_Slabs_*: the chunked LZ4 blobs of a group indexed and
  *                                     decoded by one launch each (0: every blob on its own, as by SQYAMD_Decode_*_Device -- same bytes)
  *   "decode_batch_joint"              1 [SQY_NO_DECODE_BATCH_JOINT=1 -> 0]  SQYAMD_Decode_Batch_*: the joint-eligible blobs of a group ranked, decoded and

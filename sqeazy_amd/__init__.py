@@ -38,6 +38,7 @@ EXPORTED_SYMBOLS = (
     "SQYAMD_PipelineEncode_UI16_Cap", "SQYAMD_PipelineEncode_UI8_Cap",
     "SQYAMD_Decode_UI16_Device", "SQYAMD_Decode_UI8_Device",
     "SQYAMD_Decode_Frames_UI16_Device", "SQYAMD_Decode_Frames_UI8_Device", "SQYAMD_Decode_Frames_UI16", "SQYAMD_Decode_Frames_UI8",
+    "SQYAMD_Decode_Box_UI16_Device", "SQYAMD_Decode_Box_UI8_Device", "SQYAMD_Decode_Box_UI16", "SQYAMD_Decode_Box_UI8",
     "SQYAMD_Decode_Slabs_UI16_Device", "SQYAMD_Decode_Slabs_UI8_Device", "SQYAMD_Decode_Slabs_UI16", "SQYAMD_Decode_Slabs_UI8",
     "SQYAMD_Decode_Batch_UI16_Device", "SQYAMD_Decode_Batch_UI8_Device", "SQYAMD_Decode_Batch_UI16", "SQYAMD_Decode_Batch_UI8",
     "SQYAMD_Profile_Enable", "SQYAMD_Profile_Reset", "SQYAMD_Profile_Get",
@@ -125,6 +126,10 @@ def lib():
             getattr(L, f).argtypes = [ctypes.c_void_p, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p]
         for f in ("SQYAMD_Decode_Frames_UI8", "SQYAMD_Decode_Frames_UI16"):
             getattr(L, f).argtypes = [ctypes.c_void_p, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_void_p, ctypes.c_long]
+        for f in ("SQYAMD_Decode_Box_UI8_Device", "SQYAMD_Decode_Box_UI16_Device"):
+            getattr(L, f).argtypes = [ctypes.c_void_p, ctypes.c_long, c_long_p, ctypes.c_void_p, c_long_p, c_long_p, ctypes.c_uint, ctypes.c_void_p]
+        for f in ("SQYAMD_Decode_Box_UI8", "SQYAMD_Decode_Box_UI16"):
+            getattr(L, f).argtypes = [ctypes.c_void_p, ctypes.c_long, c_long_p, c_long_p, ctypes.c_uint, ctypes.c_void_p, ctypes.c_long]
         for f in ("SQYAMD_Decode_Slabs_UI8_Device", "SQYAMD_Decode_Slabs_UI16_Device"):
             getattr(L, f).argtypes = [ctypes.c_void_p, c_long_p, c_long_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_long, c_long_p, ctypes.c_int,
                                       ctypes.c_void_p]
@@ -442,6 +447,29 @@ def decode_frames_device(d_src, srclength, z0, nz, d_dst, dst_capacity, dtype, s
     return getattr(lib(), "SQYAMD_Decode_Frames_%s_Device" % _suffix(dtype))(
         ctypes.c_void_p(int(d_src)), ctypes.c_long(int(srclength)), ctypes.c_long(int(z0)), ctypes.c_long(int(nz)), ctypes.c_void_p(int(d_dst)),
         ctypes.c_long(int(dst_capacity)), ctypes.c_void_p(stream or 0))
+
+
+def decode_box(blob, origin, extent):
+    """SQYAMD_Decode_Box_UI8/UI16: the box [origin, origin + extent) of the blob's volume; returns (rc, ndarray of shape extent or None)."""
+    blob = bytes(blob)
+    size = decompressed_sizeof(blob)
+    if size not in (1, 2) or not decompressed_shape(blob):
+        return 1, None
+    dtype = np.uint16 if size == 2 else np.uint8
+    out = np.empty(tuple(max(int(e), 0) for e in extent), dtype=dtype)
+    src = np.frombuffer(blob, dtype=np.uint8)
+    rc = getattr(lib(), "SQYAMD_Decode_Box_" + _suffix(dtype))(src.ctypes.data, ctypes.c_long(len(blob)), _longs(origin), _longs(extent), ctypes.c_uint(len(extent)),
+                                                               out.ctypes.data, ctypes.c_long(out.nbytes))
+    return (rc, None) if rc else (0, out)
+
+
+def decode_box_device(d_src, srclength, origin, d_dst, shape, strides, dtype, stream=None):
+    """SQYAMD_Decode_Box_*_Device on raw device pointers (ints): the box of extent `shape` that begins at voxel `origin` of the blob, into the
+    view at d_dst with that shape and `strides` in voxels (None: dense); only the view's voxels are written.  Returns rc."""
+    return getattr(lib(), "SQYAMD_Decode_Box_%s_Device" % _suffix(dtype))(
+        ctypes.c_void_p(None if d_src is None else int(d_src)), ctypes.c_long(int(srclength)), None if origin is None else _longs(origin),
+        ctypes.c_void_p(None if d_dst is None else int(d_dst)), None if shape is None else _longs(shape), None if strides is None else _longs(strides),
+        ctypes.c_uint(len(shape) if shape is not None else len(origin or ())), ctypes.c_void_p(stream or 0))
 
 
 def decode_slabs_device(d_src, offsets, lengths, d_dst, dst_capacity, dtype, inflight=0, stream=None):

@@ -88,6 +88,25 @@ SQY_VIEW_HD inline uint64_t window_tile_count(const WindowGeometry& g, uint64_t 
     return ((g.oz + g.Z) * g.bY * g.bX - 1) / tile - window_first_tile(g, tile) + 1;
 }
 
+// ---- the box of one large blob (SQYAMD_Decode_Box_*): the windowed transposer over a RANGE [w0, w1) of the plane words ----
+// Its grid runs over ABSOLUTE words: thread t owns the words [t wpt, (t + 1) wpt) n [w0, w1), so the 16 bytes it reads of a plane lie on
+// the 16-byte grid of the original stream wherever the range begins.  The run it clips begins at its own first voxel, t wpt W, and ends
+// behind its last owned word: the words in front of w0 hold voxels in front of the box's first frame (w0 W <= the box's first voxel),
+// which the clip steps over like any others outside -- they are never loaded and never stored.
+struct RangeRun {
+    uint64_t first;          // the thread's first word, t wpt
+    uint32_t lo, hi;         // it owns the words first + [lo, hi) (lo == hi: none)
+};
+SQY_VIEW_HD inline uint64_t range_first_thread(uint64_t w0, uint32_t wpt) { return w0 / wpt; }
+SQY_VIEW_HD inline uint64_t range_thread_count(uint64_t w0, uint64_t w1, uint32_t wpt) { return w1 > w0 ? (w1 - 1) / wpt - w0 / wpt + 1 : 0; }
+SQY_VIEW_HD inline RangeRun range_run(uint64_t t, uint32_t wpt, uint64_t w0, uint64_t w1)
+{
+    const uint64_t first = t * wpt;
+    const uint32_t lo = w0 > first ? (w0 - first < wpt ? (uint32_t)(w0 - first) : wpt) : 0u;
+    const uint32_t hi = w1 > first ? (w1 - first < wpt ? (uint32_t)(w1 - first) : wpt) : 0u;
+    return RangeRun{first, lo, hi > lo ? hi : lo};
+}
+
 // ---- the update of a window in the bit-plane layout (SQYAMD_Update_BatchWindow_*) ----
 // A voxel has the same bit position in every plane: with W voxels to a plane word (16 for 16-bit voxels, 8 for 8-bit ones), plane
 // W - 1 - b, word w, bit W - 1 - k is bit b of voxel W w + k.  A run of 128 voxels that begins at a word is 16 bytes of every plane -- four

@@ -78,6 +78,7 @@ struct Options {
     std::atomic<long> stored_tail_index;                // decode, chunked layout: the stored frames at the stream's end are found where they must start, not by the scan
     std::atomic<long> host_l2_bytes;                    // rmestbkrd: the host CPU's L2 size as the reference's compass reads it (detected; tests set it)
     std::atomic<long> decode_frames_subset;             // frame-range decode: only the LZ4 frames the range needs, where the pipeline allows (0: full decode + copy)
+    std::atomic<long> decode_box_subset;                // box decode: only the LZ4 frames the box's z-range needs, where the pipeline allows (0: full decode + window copy)
     std::atomic<long> decode_slabs_joint;               // slab-set decode: the chunked LZ4 blobs of a group indexed and decoded by one launch each (0: blob by blob)
     std::atomic<long> decode_batch_joint;               // batch decode: the joint-eligible blobs of a group indexed, decoded and transposed back by one launch each (0: blob by blob)
     std::atomic<long> decode_batch_group_bytes;         // .. the LZ4 output one group holds at most (a group holds at least one blob)
@@ -102,6 +103,7 @@ struct Options {
           decode_two_waves(env_flag("SQY_NO_DECODE_TWO_WAVES") ? 0 : 1), noise_digest(env_flag("SQY_NO_NOISE_DIGEST") ? 0 : 1),
           transpose_tiles_per_wave(env_number("SQY_TRANSPOSE_TILES_PER_WAVE", sqy::kBitswap1TilesPerWave, 1, 64)), stored_tail_index(env_flag("SQY_NO_STORED_TAIL_INDEX") ? 0 : 1),
           host_l2_bytes((long)sqy::host_l2_cache_bytes()), decode_frames_subset(env_flag("SQY_NO_DECODE_FRAMES_SUBSET") ? 0 : 1),
+          decode_box_subset(env_flag("SQY_NO_DECODE_BOX_SUBSET") ? 0 : 1),
           decode_slabs_joint(env_flag("SQY_NO_DECODE_SLABS_JOINT") ? 0 : 1), decode_batch_joint(env_flag("SQY_NO_DECODE_BATCH_JOINT") ? 0 : 1),
           decode_batch_group_bytes(env_number("SQY_DECODE_BATCH_GROUP_BYTES", (long)kSlabsGroupBytes, 1, (long)kSlabsGroupBytes)), encode_batch_joint(env_flag("SQY_NO_ENCODE_BATCH_JOINT") ? 0 : 1),
           encode_batch_group_bytes(env_number("SQY_ENCODE_BATCH_GROUP_BYTES", kBatchGroupBytesDefault, 1, kBatchBytesMax)),
@@ -124,6 +126,7 @@ struct Options {
         if (!std::strcmp(name, "stored_tail_index")) return &stored_tail_index;
         if (!std::strcmp(name, "host_l2_bytes")) return &host_l2_bytes;
         if (!std::strcmp(name, "decode_frames_subset")) return &decode_frames_subset;
+        if (!std::strcmp(name, "decode_box_subset")) return &decode_box_subset;
         if (!std::strcmp(name, "decode_slabs_joint")) return &decode_slabs_joint;
         if (!std::strcmp(name, "decode_batch_joint")) return &decode_batch_joint;
         if (!std::strcmp(name, "decode_batch_group_bytes")) return &decode_batch_group_bytes;
@@ -335,6 +338,7 @@ struct Workspace {
     DevBuf bkrd;              // rmestbkrd: the four face histograms and their supports
     DevBuf subset;            // frame-range decode: the frame list, the subset's block index, the frame_shuffle map of the range
     DevBuf range_full;        // frame-range decode of a blob the subset path does not take: the whole volume, the range copied out
+    DevBuf box_window;        // box decode: the job and tile table of the window copy (one job)
     DevBuf slabs_index;       // slab-set decode: every blob's frame ranking (scratch, block index, counts) of a group
     DevBuf slabs_joint;       // .. the group's joint block index, frame output table, part descriptors and frame_shuffle maps
     DevBuf slabs_out;         // .. the group's LZ4 output (when it does not go straight to the volume)
@@ -359,7 +363,7 @@ struct Workspace {
     {
         ping.release(); pong.release(); lz4_scratch.release(); csize.release(); frame_off.release();
         io_src.release(); io_dst.release(); small.release(); plan.release(); dedupe.release(); diff_side.release(); spec.release(); digest.release(); bkrd.release();
-        subset.release(); range_full.release(); slabs_index.release(); slabs_joint.release(); slabs_out.release(); slabs_host.release();
+        subset.release(); range_full.release(); box_window.release(); slabs_index.release(); slabs_joint.release(); slabs_out.release(); slabs_host.release();
         batch_stream.release(); batch_scratch.release(); batch_tables.release(); batch_quant.release(); batch_host.release();
         batch_pack.release(); batch_pack_one.release(); for (DevBuf& b : batch_views) b.release(); for (DevBuf& b : batch_windows) b.release();
         for (DevBuf& b : batch_compares) b.release();
@@ -2165,14 +2169,18 @@ struct DecodeCall {
         return stage_error((size_t)lz4_flag_stage);
     }
 
-    // ---- frame-range decode (SQYAMD_Decode_Frames_*) ----
-    // Frames [z0, z0 + nz) of the volume (fb bytes each) into d_dst, decoding only the LZ4 frames they need.  Taken for the chunked
-    // layout of  [heads ->] lz4 | bitswap1->lz4 | quantiser->bitswap1->lz4 | frame_shuffle->lz4  (the background heads decode as a copy);
-    // *taken = false for anything else, with nothing written to d_dst (the caller decodes the whole blob).  The decoder's verdict is
-    // left in lz4_flag, as by lz4_frames.
+    // ---- frame-range decode (SQYAMD_Decode_Frames_*, SQYAMD_Decode_Box_*) ----
+    // The LZ4 frames that frames [z0, z0 + nz) of the volume need, decoded into range_buf.  Taken for the chunked layout of
+    // [heads ->] lz4 | bitswap1->lz4 | quantiser->bitswap1->lz4 | frame_shuffle->lz4  (the background heads decode as a copy);
+    // *taken = false for anything else, with nothing written (the caller decodes the whole blob).  The decoder's verdict is left in
+    // lz4_flag, as by lz4_frames.  What follows is the caller's: frames_range_out (the frames, dense, into d_dst) or box_range_out (a box of
+    // them into a view).  direct_ok: a shuffle range on place boundaries may be decoded straight into d_dst (range_buf == d_dst then)
     std::vector<unsigned char> sub_host;   // the tables uploaded to ws->subset (alive until the call's last synchronisation)
+    sqy::RangeForm range_form = sqy::RangeForm::plain;
+    sqy::FrameRangePlan range_plan;        // (direct: only where direct_ok)
+    uint8_t* range_buf = nullptr;
 
-    int frames_subset(uint64_t z0, uint64_t nz, uint64_t fb, bool* taken)
+    int frames_subset(uint64_t z0, uint64_t nz, bool direct_ok, bool* taken)
     {
         *taken = false;
         const size_t ns = pipe.stages.size();
@@ -2205,7 +2213,10 @@ struct DecodeCall {
             if (!fold) return 0;
         }
         // the LZ4 frames the range needs and where its bytes lie behind their decode
-        const sqy::FrameRangePlan p = sqy::frame_range_plan(form, n, e, h.shape[0], z0, nz, chunk, total, nframes, fs_map, fbp, P);
+        range_plan = sqy::frame_range_plan(form, n, e, h.shape[0], z0, nz, chunk, total, nframes, fs_map, fbp, P);
+        range_form = form;
+        range_plan.direct = range_plan.direct && direct_ok;
+        const sqy::FrameRangePlan& p = range_plan;
         if (!p.ok) return 0;
 
         // the tables: ids | subset frame starts | remap | subset block index
@@ -2234,19 +2245,38 @@ struct DecodeCall {
             lz4_flag = ix.counts + 4;
             lz4_flag_stage = (int)li;
         }
-        if (form == Form::plain || (form == Form::shuffle && !p.direct)) {
-            SQY_TIMED("frames_range_copy", hipMemcpyAsync(d_dst, sbuf + p.range_at, nz * fb, hipMemcpyDeviceToDevice, stream));
-        } else if (form != Form::shuffle) {
-            sqy::Bitswap1Range r{};
-            std::copy(p.plane, p.plane + 16, r.plane);
-            r.tail = p.tail; r.w0 = p.w0; r.w1 = p.w1; r.v0 = p.v0; r.v1 = p.v1; r.L = p.L;
+        range_buf = sbuf;
+        return 0;
+    }
+
+    // the planes of range_plan for the range transposers, the quantiser's decode table on the device where the form has one
+    int range_planes(sqy::Bitswap1Range* r, const uint16_t** lut)
+    {
+        const sqy::FrameRangePlan& p = range_plan;
+        *r = sqy::Bitswap1Range{};
+        std::copy(p.plane, p.plane + 16, r->plane);
+        r->tail = p.tail; r->w0 = p.w0; r->w1 = p.w1; r->v0 = p.v0; r->v1 = p.v1; r->L = p.L;
+        *lut = nullptr;
+        if (range_form == sqy::RangeForm::planes_lut) {
+            if (quantiser_lut_to_device(pipe.stages[lead], ws)) return 1;
+            *lut = static_cast<const uint16_t*>(ws->small.p);
+        }
+        return 0;
+    }
+
+    // SQYAMD_Decode_Frames_*' last launch behind frames_subset: the nz frames of fb bytes, dense, into d_dst
+    int frames_range_out(uint64_t nz, uint64_t fb)
+    {
+        typedef sqy::RangeForm Form;
+        const sqy::FrameRangePlan& p = range_plan;
+        if (range_form == Form::plain || (range_form == Form::shuffle && !p.direct)) {
+            SQY_TIMED("frames_range_copy", hipMemcpyAsync(d_dst, range_buf + p.range_at, nz * fb, hipMemcpyDeviceToDevice, stream));
+        } else if (range_form != Form::shuffle) {
+            sqy::Bitswap1Range r;
             const uint16_t* lut = nullptr;
-            if (form == Form::planes_lut) {
-                if (quantiser_lut_to_device(pipe.stages[lead], ws)) return 1;
-                lut = static_cast<const uint16_t*>(ws->small.p);
-            }
+            if (range_planes(&r, &lut)) return 1;
             SQY_TIMED(lut ? "bitswap1_quantiser_decode_range" : "bitswap1_decode_range",
-                      sqy::launch_bitswap1_decode_range(sbuf, d_dst, r, p.we, lut, stream));
+                      sqy::launch_bitswap1_decode_range(range_buf, d_dst, r, p.we, lut, stream));
         }
         return 0;
     }
@@ -2352,8 +2382,11 @@ int decode_frames_on_device(Context& cx, const void* d_src_v, uint64_t srclen, l
     if (g_opt.decode_frames_subset.load()) {
         DecodeCall c(cx, stream, d_dst, h, Pipeline::from_string(h.pipename), raw_bytes / (uint64_t)want_elem, d_src + h.size);
         bool taken = false;
-        if (const int rc = c.frames_subset((uint64_t)z0, (uint64_t)nz, fb, &taken)) return rc;
-        if (taken) return c.finish();
+        if (const int rc = c.frames_subset((uint64_t)z0, (uint64_t)nz, true, &taken)) return rc;
+        if (taken) {
+            if (const int rc = c.frames_range_out((uint64_t)nz, fb)) return rc;
+            return c.finish();
+        }
     }
     // every other blob: the whole volume, then the range
     if (cx.ws.range_full.ensure(std::max<uint64_t>(raw_bytes, 16))) return 1;
@@ -2582,6 +2615,122 @@ int launch_windows(Context& cx, hipStream_t stream, WindowLaunch& l, WindowLaunc
     case WindowLaunch::paste: SQY_TIMED("batch_window_paste", sqy::launch_batch_window_paste(d_jobs, d_tiles, nj, l.ntiles, elem_size, stream)); break;
     }
     return 0;
+}
+
+// ---- a box of one large blob (SQYAMD_Decode_Box_*) ------------------------------------------------------------------------------
+// The frame-range decode's pruning joined with the windows' clip: sqy::decode_box_path says what runs.  On the subset paths the LZ4 frames
+// the box's z-range needs are decoded into the workspace (DecodeCall::frames_subset, as for SQYAMD_Decode_Frames_*), then ONE launch
+// stores the box's voxels into the view; every other blob is decoded whole into Workspace::range_full and one window copy cuts the box out.
+
+// one window copy under the name "box_window_copy": the box w of the dense volume at `dense` into the view (l: alive until the stream has
+// been waited for)
+int launch_box_copy(Context& cx, hipStream_t stream, WindowLaunch& l, void* view, const void* dense, const sqy::BatchWindow& w, const WindowView& v, int elem_size)
+{
+    std::vector<PendingEvent>* pend = &cx.pending;
+    l.add(view, dense, w, v, false);
+    const uint32_t* d_tiles = nullptr;
+    if (l.upload(stream, cx.ws.box_window, &d_tiles)) return 1;
+    SQY_TIMED("box_window_copy", sqy::launch_batch_window_copy(static_cast<const sqy::BatchWindowJob*>(cx.ws.box_window.p), d_tiles, 1, l.ntiles, elem_size, stream));
+    return 0;
+}
+
+// SQYAMD_Decode_Box_*'s last launch behind DecodeCall::frames_subset: the box w of the frames in c.range_buf into the view at c.d_dst
+int box_range_out(DecodeCall& c, WindowLaunch& l, const sqy::BatchWindow& w, const WindowView& v, unsigned rank)
+{
+    hipStream_t stream = c.stream;
+    std::vector<PendingEvent>* pend = c.pend;
+    const sqy::FrameRangePlan& p = c.range_plan;
+    const int e = c.h.elem_size();
+    if (sqy::decode_box_path(true, c.range_form, true) == sqy::BoxPath::subset_transposer) {
+        sqy::Bitswap1Range r;
+        const uint16_t* lut = nullptr;
+        if (c.range_planes(&r, &lut)) return 1;
+        const sqy::BatchWindowJob box{c.d_dst, c.range_buf, w.Z, w.Y, w.X, v.sz, v.sy, w.bZ, w.bY, w.bX, w.oz, w.oy, w.ox, 0};
+        SQY_TIMED(lut ? "bitswap1_quantiser_decode_box" : "bitswap1_decode_box", sqy::launch_bitswap1_decode_range_window(c.range_buf, r, box, p.we, lut, stream));
+        return 0;
+    }
+    // plain, shuffle: the range in the workspace is a blob of the box's frames, the box begins at its first one
+    sqy::BatchWindow in_range = w;
+    if (rank == 3) { in_range.bZ = w.Z; in_range.oz = 0; }             // (the frames are the header's first dimension:
+    else if (rank == 2) { in_range.bY = w.Y; in_range.oy = 0; }        //  of a header of rank 2 the rows,
+    else { in_range.bX = w.X; in_range.ox = 0; }                       //  of rank 1 the voxels)
+    return launch_box_copy(c.cx, stream, l, c.d_dst, c.range_buf + p.range_at, in_range, v, e);
+}
+
+// The box [origin, origin + extent) of the blob into the view at d_dst.  Same checks as decode_on_device, plus the window against the
+// header (the view has been admitted by the caller) -- all before anything is written.
+int decode_box_on_device(Context& cx, const void* d_src_v, uint64_t srclen, const long* origin, const long* extent, const long* strides, unsigned rank, void* d_dst,
+                         int want_elem, hipStream_t stream)
+{
+    const uint8_t* d_src = static_cast<const uint8_t*>(d_src_v);
+    DrainOnExit drain{stream, &cx.pending, cx.side};
+    sqy::HeaderInfo h;
+    if (fetch_header(d_src, srclen, stream, h)) return 1;
+    uint64_t raw_bytes = 0;
+    if (!admit_blob(h, srclen, want_elem, &raw_bytes)) return 1;
+    sqy::BatchWindow w;
+    if (!sqy::admit_window(h.shape, origin, extent, rank, &w)) {
+        std::fprintf(stderr, "[sqeazy]\t decode box: the box does not lie inside the blob's shape, or has another rank\n");
+        return 1;
+    }
+    const WindowView v = window_view(w, strides, rank);
+    WindowLaunch l;                                                     // (waits for the stream before its tables go)
+    if (g_opt.decode_box_subset.load()) {
+        DecodeCall c(cx, stream, d_dst, h, Pipeline::from_string(h.pipename), raw_bytes / (uint64_t)want_elem, d_src + h.size);
+        bool taken = false;
+        if (const int rc = c.frames_subset((uint64_t)origin[0], (uint64_t)extent[0], false, &taken)) return rc;
+        if (taken) {
+            if (const int rc = box_range_out(c, l, w, v, rank)) return rc;
+            return c.finish();
+        }
+    }
+    // sqy::BoxPath::whole_copy: the whole volume, then the box
+    if (cx.ws.range_full.ensure(std::max<uint64_t>(raw_bytes, 16))) return 1;
+    if (const int rc = decode_on_device(cx, d_src_v, srclen, cx.ws.range_full.p, raw_bytes, want_elem, stream)) return rc;
+    if (const int rc = launch_box_copy(cx, stream, l, d_dst, cx.ws.range_full.p, w, v, want_elem)) return rc;
+    SQY_HIP(hipStreamSynchronize(stream));
+    if (g_prof_on.load()) prof_collect(cx.pending);
+    return 0;
+}
+
+// what SQYAMD_Decode_Box_* checks without a header, before a device is looked for
+bool box_arguments_ok(const void* src, long srclength, const long* origin, const void* dst, const long* extent, unsigned rank)
+{
+    if (!src || !dst || !origin || !extent || srclength <= 0 || rank == 0 || rank > 3) return false;
+    for (unsigned k = 0; k < rank; ++k) if (origin[k] < 0) return false;
+    return true;
+}
+
+int decode_box_device(const void* d_src, long srclength, const long* origin, void* d_dst, const long* dst_shape, const long* dst_strides, unsigned rank, int elem_size,
+                      void* hip_stream)
+{
+    if (!box_arguments_ok(d_src, srclength, origin, d_dst, dst_shape, rank)) { std::fprintf(stderr, "[sqeazy]\t decode box: bad arguments\n"); return 1; }
+    std::vector<sqy::BatchView> views;
+    const void* const ptrs[1] = {d_dst};
+    if (admit_views("decode box", ptrs, dst_shape, dst_strides, rank, 1, elem_size, &views)) return 1;
+    ContextLease lease;
+    if (!lease.ctx) { std::fprintf(stderr, "[sqeazy]\t no usable HIP device\n"); return 1; }
+    return decode_box_on_device(*lease.ctx, d_src, (uint64_t)srclength, origin, dst_shape, dst_strides, rank, d_dst, elem_size, static_cast<hipStream_t>(hip_stream));
+}
+
+// host pointers: the header and the box are checked here, before anything is staged; the box comes back dense
+int decode_box_from_host(const char* src, long srclength, const long* origin, const long* extent, unsigned rank, char* dst, long dst_capacity, int elem_size)
+{
+    if (!box_arguments_ok(src, srclength, origin, dst, extent, rank)) { std::fprintf(stderr, "[sqeazy]\t decode box: bad arguments\n"); return 1; }
+    const sqy::HeaderInfo h = sqy::header_unpack(src, src + srclength);
+    if (!h.valid) { std::fprintf(stderr, "[sqeazy]\t unable to find a sqy header in the blob\n"); return 1; }
+    uint64_t raw = 0;
+    if (!header_shape_ok(h, (uint64_t)srclength, &raw)) return 1;
+    if (h.elem_size() != elem_size) { std::fprintf(stderr, "[sqeazy]\t blob holds %s voxels\n", h.type.c_str()); return 1; }
+    sqy::BatchWindow w;
+    if (!sqy::admit_window(h.shape, origin, extent, rank, &w) || w.Z * w.Y * w.X * (uint64_t)elem_size > (uint64_t)std::max(dst_capacity, 0l)) {
+        std::fprintf(stderr, "[sqeazy]\t decode box: the box does not lie inside the blob's shape, or buffer too small\n");
+        return 1;
+    }
+    const uint64_t box_bytes = w.Z * w.Y * w.X * (uint64_t)elem_size;
+    return decode_staged(src, (uint64_t)srclength, dst, box_bytes, [&](Context& cx, void* d_src, void* d_dst, hipStream_t stream) {
+        return decode_box_on_device(cx, d_src, (uint64_t)srclength, origin, extent, nullptr, rank, d_dst, elem_size, stream);
+    });
 }
 
 // ---- the compare of a window with its view (SQYAMD_Compare_BatchWindow_*) ----
@@ -4540,6 +4689,28 @@ int SQYAMD_Decode_Frames_UI16(const char* src, long srclength, long z0, long nz,
 int SQYAMD_Decode_Frames_UI8(const char* src, long srclength, long z0, long nz, char* dst, long dst_capacity)
 {
     return guarded([&]() -> int { return decode_frames_from_host(src, srclength, z0, nz, dst, dst_capacity, 1); });
+}
+
+int SQYAMD_Decode_Box_UI16_Device(const void* d_src, long srclength, const long* origin, void* d_dst, const long* dst_shape, const long* dst_strides, unsigned rank,
+                                  void* hip_stream)
+{
+    return guarded([&]() -> int { return decode_box_device(d_src, srclength, origin, d_dst, dst_shape, dst_strides, rank, 2, hip_stream); });
+}
+
+int SQYAMD_Decode_Box_UI8_Device(const void* d_src, long srclength, const long* origin, void* d_dst, const long* dst_shape, const long* dst_strides, unsigned rank,
+                                 void* hip_stream)
+{
+    return guarded([&]() -> int { return decode_box_device(d_src, srclength, origin, d_dst, dst_shape, dst_strides, rank, 1, hip_stream); });
+}
+
+int SQYAMD_Decode_Box_UI16(const char* src, long srclength, const long* origin, const long* extent, unsigned rank, char* dst, long dst_capacity)
+{
+    return guarded([&]() -> int { return decode_box_from_host(src, srclength, origin, extent, rank, dst, dst_capacity, 2); });
+}
+
+int SQYAMD_Decode_Box_UI8(const char* src, long srclength, const long* origin, const long* extent, unsigned rank, char* dst, long dst_capacity)
+{
+    return guarded([&]() -> int { return decode_box_from_host(src, srclength, origin, extent, rank, dst, dst_capacity, 1); });
 }
 
 int SQYAMD_Decode_Slabs_UI16_Device(const void* d_src, const long* offsets, const long* lengths, int nslabs, void* d_dst, long dst_capacity,

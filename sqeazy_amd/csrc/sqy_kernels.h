@@ -379,6 +379,14 @@ struct Bitswap1Range {
     uint64_t w0, w1, v0, v1, L;
 };
 hipError_t launch_bitswap1_decode_range(const uint8_t* in, void* out, const Bitswap1Range& r, int elem_size, const uint16_t* lut, hipStream_t stream);
+// ---- the box of one large blob (SQYAMD_Decode_Box_*) ----
+// launch_bitswap1_decode_range with only a box's voxels stored, each to its place in a view: the windowed transposer's clip and scatter
+// (launch_bitswap1_decode_batch_window) on the range's addressing.  box: the blob's shape, the box in it and the view that takes it
+// (`dense` and tile0 are not read); the range must hold the box, its first voxel at or behind v0 and its last in front of v1 (refused
+// otherwise: the voxels outside [v0, v1) count as outside the box).  Sixteen-byte plane loads
+// where in + plane[s] - w0 elem_size is on the 16-byte grid for every s, word by word where not.  Nothing but the view's voxels is written.
+hipError_t launch_bitswap1_decode_range_window(const uint8_t* in, const Bitswap1Range& r, const BatchWindowJob& box, int elem_size, const uint16_t* lut,
+                                               hipStream_t stream);
 // ---- batch decode (SQYAMD_Decode_Batch_*): the blobs of a group share one launch of every kernel ----
 // The inverse of launch_bitswap1_batch on the same tables: job j's planes + tail at `in` (16-byte aligned) become its `len` voxels at
 // `out` (any voxel-aligned address; sixteen-byte stores where it and the plane size allow, word by word where not).  first_tile: njobs + 1

@@ -8252,6 +8252,139 @@ void bitswap1_decode_batch_window_kernel(const BatchWindowJob* __restrict__ jobs
     }
 }
 
+// ---- the box of one large blob (SQYAMD_Decode_Box_*) ----------------------------------------------------------------------------------------
+// bitswap1_decode_batch_window_kernel over a RANGE of the plane words, behind the pruned LZ4 decode: its clip, plane loads, transposes and
+// scatter, with Bitswap1Range's addressing -- word w of [w0, w1) of stored plane segment s is read at in + plane[s] + (w - w0) ELEM, the
+// voxels [max(v0, L), v1) behind the planes at in + tail.  The grid runs over ABSOLUTE words (sqy::range_run): thread t0 + i owns the words
+// [t WPT, (t + 1) WPT) n [w0, w1), so its 16 bytes of a plane lie on the 16-byte grid of the original stream; sixteen-byte loads where all W
+// of those addresses are on the grid in the workspace too and the thread owns all its words, word by word where not (the range's first and
+// last thread; streams whose segment or chunk size is no multiple of 16).  A thread clips its run against the box first and is gone before
+// it has loaded a plane word when nothing of it lies inside.  LUT (ELEM 1): the 8-bit planes of quantiser->bitswap1, 16-bit voxels out of
+// the decode table, staged in LDS as in bitswap1_quantiser_decode_batch_kernel; a word's eight voxels leave as one piece of 16 bytes.
+template <int ELEM, bool LUT>
+__global__ __launch_bounds__(256)
+void bitswap1_decode_range_window_kernel(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, Bitswap1Range a, WindowGeometry g, uint64_t t0,
+                                         const uint16_t* __restrict__ lut)
+{
+    static_assert(!LUT || ELEM == 1, "the look-up follows 8-bit planes");
+    constexpr uint32_t W = 8 * ELEM, WPT = BSWB_THREAD_VOX / W;        // voxels per word, words per thread
+    constexpr int OUT = LUT ? 2 : ELEM;                                // bytes of a voxel in the view
+    __shared__ uint16_t sl[LUT ? 256 : 1];
+    const uint32_t tid = threadIdx.x;
+    if constexpr (LUT) { sl[tid] = lut[tid]; __syncthreads(); }
+    WindowPiece cur;
+    const uint64_t tail0 = a.v0 > a.L ? a.v0 : a.L;
+    if (blockIdx.x == 0 && tail0 + tid < a.v1) {                      // tail voxels: verbatim (or looked up), those of the box
+        WindowClip ct = window_clip_start(g, tail0 + tid, 1);
+        if (window_clip_next(g, &ct, &cur)) {
+            const uint32_t x = view_voxel_load<ELEM>(in + a.tail, tid);
+            view_voxel_store<OUT>(out, cur.dst_off, LUT ? (uint32_t)sl[x & 0xffu] : x);
+        }
+    }
+    const RangeRun run = range_run(t0 + (uint64_t)blockIdx.x * 256u + tid, WPT, a.w0, a.w1);
+    if (run.lo == run.hi) return;
+    WindowClip c = window_clip_start(g, run.first * W, (uint64_t)run.hi * W);
+    bool have = window_clip_next(g, &c, &cur);
+    if (!have) return;                                                // nothing of the run inside the box: no plane word is loaded
+    const uint64_t at = (run.first - a.w0) * ELEM;                    // the thread's 16 bytes behind plane[s] (in front of it: a first thread's words not owned, never read)
+    bool wide = run.lo == 0 && run.hi == WPT;
+    if (wide) {
+        uint32_t off_grid = 0;                                        // (uniform: first ELEM is a multiple of 16)
+#pragma unroll
+        for (uint32_t s = 0; s < W; ++s) off_grid |= (uint32_t)(reinterpret_cast<uintptr_t>(in) + a.plane[s] + at);
+        wide = (off_grid & 15u) == 0;
+    }
+    if constexpr (ELEM == 2) {
+        uint32_t pl[16][4];                                           // pl[b] = eight words of the plane that carries bit b
+        if (wide) {
+#pragma unroll
+            for (int b = 0; b < 16; ++b) {
+                const uint4 t = *reinterpret_cast<const uint4*>(in + a.plane[15 - b] + at);
+                pl[b][0] = t.x; pl[b][1] = t.y; pl[b][2] = t.z; pl[b][3] = t.w;
+            }
+        } else {
+#pragma unroll
+            for (int b = 0; b < 16; ++b) { pl[b][0] = 0; pl[b][1] = 0; pl[b][2] = 0; pl[b][3] = 0; }
+#pragma unroll
+            for (uint32_t i = 0; i < WPT; ++i)
+                if (i >= run.lo && i < run.hi)
+#pragma unroll
+                    for (int b = 0; b < 16; ++b)
+                        pl[b][i >> 1] |= (uint32_t)*reinterpret_cast<const uint16_t*>(in + a.plane[15 - b] + at + 2u * i) << (16u * (i & 1u));
+        }
+#pragma unroll
+        for (uint32_t q = 0; q < 4; ++q) {                            // words first + 2 q (group A, low halves) and first + 2 q + 1 (group B)
+            if (2 * q >= run.hi || !have) break;
+            uint32_t r[16];
+#pragma unroll
+            for (int b = 0; b < 16; ++b) r[b] = pl[b][q];
+            transpose16x16_pairs(r);                                  // r[i] = voxel 15 - i of group A | of group B << 16
+            uint32_t ga[8], gb[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                ga[k] = __builtin_amdgcn_perm(r[14 - 2 * k], r[15 - 2 * k], 0x05040100u);
+                gb[k] = __builtin_amdgcn_perm(r[14 - 2 * k], r[15 - 2 * k], 0x07060302u);
+            }
+            window_scatter16<2>(out, g, c, cur, have, make_uint4(ga[0], ga[1], ga[2], ga[3]), 32u * q, 8);
+            window_scatter16<2>(out, g, c, cur, have, make_uint4(ga[4], ga[5], ga[6], ga[7]), 32u * q + 8u, 8);
+            if (2 * q + 1 >= run.hi) break;
+            window_scatter16<2>(out, g, c, cur, have, make_uint4(gb[0], gb[1], gb[2], gb[3]), 32u * q + 16u, 8);
+            window_scatter16<2>(out, g, c, cur, have, make_uint4(gb[4], gb[5], gb[6], gb[7]), 32u * q + 24u, 8);
+        }
+    } else {
+        uint32_t pw[8][4];                                            // pw[b] = 16 bytes of the plane that carries bit b
+        if (wide) {
+#pragma unroll
+            for (int b = 0; b < 8; ++b) {
+                const uint4 t = *reinterpret_cast<const uint4*>(in + a.plane[7 - b] + at);
+                pw[b][0] = t.x; pw[b][1] = t.y; pw[b][2] = t.z; pw[b][3] = t.w;
+            }
+        } else {
+#pragma unroll
+            for (int b = 0; b < 8; ++b) { pw[b][0] = 0; pw[b][1] = 0; pw[b][2] = 0; pw[b][3] = 0; }
+#pragma unroll
+            for (uint32_t i = 0; i < WPT; ++i)
+                if (i >= run.lo && i < run.hi)
+#pragma unroll
+                    for (int b = 0; b < 8; ++b) pw[b][i >> 2] |= (uint32_t)in[a.plane[7 - b] + at + i] << (8u * (i & 3u));
+        }
+#pragma unroll
+        for (uint32_t gq = 0; gq < 16; gq += 2) {
+            if (gq >= run.hi || !have) break;
+            uint32_t d[4];
+#pragma unroll
+            for (uint32_t u = 0; u < 2; ++u) {
+                // (bitswap1_decode_batch_strided_kernel's gather and transpose: afterwards byte i of hi:lo = voxel 7 - i)
+                constexpr uint32_t Zs = 0x0c;                         // v_perm selector: a zero byte
+                const uint32_t cc = (gq + u) & 3u, wdx = (gq + u) >> 2;
+                const uint32_t s01 = cc | ((4u + cc) << 8) | (Zs << 16) | (Zs << 24), s23 = Zs | (Zs << 8) | (cc << 16) | ((4u + cc) << 24);
+                uint32_t lo_ = __builtin_amdgcn_perm(pw[1][wdx], pw[0][wdx], s01) | __builtin_amdgcn_perm(pw[3][wdx], pw[2][wdx], s23);
+                uint32_t hi_ = __builtin_amdgcn_perm(pw[5][wdx], pw[4][wdx], s01) | __builtin_amdgcn_perm(pw[7][wdx], pw[6][wdx], s23);
+                uint32_t y;
+                y = (lo_ ^ (lo_ >> 7)) & 0x00AA00AAu; lo_ ^= y ^ (y << 7);
+                y = (hi_ ^ (hi_ >> 7)) & 0x00AA00AAu; hi_ ^= y ^ (y << 7);
+                y = (lo_ ^ (lo_ >> 14)) & 0x0000CCCCu; lo_ ^= y ^ (y << 14);
+                y = (hi_ ^ (hi_ >> 14)) & 0x0000CCCCu; hi_ ^= y ^ (y << 14);
+                y = (lo_ ^ (hi_ << 4)) & 0xF0F0F0F0u; lo_ ^= y; hi_ ^= y >> 4;
+                d[2 * u] = __builtin_bswap32(hi_);                    // voxels 0..3 of the word
+                d[2 * u + 1] = __builtin_bswap32(lo_);                // voxels 4..7
+            }
+            if constexpr (LUT) {
+#pragma unroll
+                for (uint32_t u = 0; u < 2; ++u) {                    // word gq + u: eight 16-bit voxels, one piece
+                    if (gq + u >= run.hi) break;
+                    const uint32_t h4 = d[2 * u], l4 = d[2 * u + 1];  // (voxel k of four at byte k)
+                    window_scatter16<2>(out, g, c, cur, have,
+                                        make_uint4((uint32_t)sl[h4 & 0xffu] | ((uint32_t)sl[(h4 >> 8) & 0xffu] << 16), (uint32_t)sl[(h4 >> 16) & 0xffu] | ((uint32_t)sl[h4 >> 24] << 16),
+                                                   (uint32_t)sl[l4 & 0xffu] | ((uint32_t)sl[(l4 >> 8) & 0xffu] << 16), (uint32_t)sl[(l4 >> 16) & 0xffu] | ((uint32_t)sl[l4 >> 24] << 16)),
+                                        8u * (gq + u), 8);
+                }
+            } else
+                window_scatter16<1>(out, g, c, cur, have, make_uint4(d[0], d[1], d[2], d[3]), 8u * gq, run.hi - gq >= 2u ? 16u : 8u);
+        }
+    }
+}
+
 // ---- the compare of a window with its view (SQYAMD_Compare_BatchWindow_*) ------------------------------------------------------------------
 // The windowed decode's reads with a reduction where its stores were.  A thread gathers sqy::CompareSums over its 128 voxels (the text of
 // sqy_batch_window.hpp, which a sanitized host test runs too), the workgroup reduces them -- across the wavefront with cross-lane moves,
@@ -8655,6 +8788,25 @@ hipError_t launch_bitswap1_decode_batch_window(const BatchWindowJob* d_jobs, con
     if (elem_size == 2) hipLaunchKernelGGL(bitswap1_decode_batch_window_kernel<2>, dim3(ntiles), dim3(256), 0, stream, d_jobs, d_first_tile, njobs);
     else if (elem_size == 1) hipLaunchKernelGGL(bitswap1_decode_batch_window_kernel<1>, dim3(ntiles), dim3(256), 0, stream, d_jobs, d_first_tile, njobs);
     else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+hipError_t launch_bitswap1_decode_range_window(const uint8_t* in, const Bitswap1Range& r, const BatchWindowJob& box, int elem_size, const uint16_t* lut,
+                                               hipStream_t stream)
+{
+    if (r.v1 <= r.v0 || r.w1 < r.w0 || (elem_size != 1 && elem_size != 2) || (lut && elem_size != 1) || !box.view) return hipErrorInvalidValue;
+    // the range holds the box: none of its voxels lies outside the words and the tail the kernel reads
+    if (box.Z == 0 || box.Y == 0 || box.X == 0 || ((box.oz * box.bY + box.oy) * box.bX + box.ox) < r.v0 ||
+        ((box.oz + box.Z - 1) * box.bY + box.oy + box.Y - 1) * box.bX + box.ox + box.X > r.v1) return hipErrorInvalidValue;
+    const uint32_t wpt = BSWB_THREAD_VOX / (8u * (uint32_t)elem_size);
+    const uint64_t t0 = range_first_thread(r.w0, wpt), groups = (range_thread_count(r.w0, r.w1, wpt) + 255) / 256;
+    if (groups > 0x7fffffffull) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)(groups ? groups : 1));                  // (block 0 also moves the tail)
+    const WindowGeometry g{box.bY, box.bX, box.oz, box.oy, box.ox, box.Z, box.Y, box.X, box.sz, box.sy};
+    uint8_t* out = static_cast<uint8_t*>(box.view);
+    if (elem_size == 2) hipLaunchKernelGGL((bitswap1_decode_range_window_kernel<2, false>), grid, dim3(256), 0, stream, in, out, r, g, t0, lut);
+    else if (lut) hipLaunchKernelGGL((bitswap1_decode_range_window_kernel<1, true>), grid, dim3(256), 0, stream, in, out, r, g, t0, lut);
+    else hipLaunchKernelGGL((bitswap1_decode_range_window_kernel<1, false>), grid, dim3(256), 0, stream, in, out, r, g, t0, lut);
     return hipGetLastError();
 }
 

@@ -823,6 +823,12 @@ FrameRangePlan frame_range_plan(RangeForm form, uint64_t n, int elem, uint64_t s
     return p;
 }
 
+BoxPath decode_box_path(bool subset_form, RangeForm form, bool option_on)
+{
+    if (!subset_form || !option_on) return BoxPath::whole_copy;
+    return form == RangeForm::planes || form == RangeForm::planes_lut ? BoxPath::subset_transposer : BoxPath::subset_copy;
+}
+
 // ---- stages ----
 static StageKind kind_of(const std::string& n)
 {

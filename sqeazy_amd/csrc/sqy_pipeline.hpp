@@ -404,6 +404,15 @@ struct FrameRangePlan {
 FrameRangePlan frame_range_plan(RangeForm form, uint64_t n, int elem, uint64_t shape0, uint64_t z0, uint64_t nz, uint64_t chunk, uint64_t total,
                                 uint32_t nframes, const std::vector<unsigned char>& struck_map = {}, uint64_t place_bytes = 0, uint64_t places = 0);
 
+// A box of one large blob (SQYAMD_Decode_Box_*): what runs for it.  subset_form: the blob is one the frame-range plan takes (the chunked
+// layout of a RangeForm pipeline with more than one LZ4 frame -- where DecodeCall::frames_subset says `taken`), then `form` is its form;
+// option_on: decode_box_subset.
+//   subset_transposer  the LZ4 frames the box's z-range needs, then the windowed range transposer (planes, planes_lut)
+//   subset_copy        .. then one window copy out of the range in the workspace (plain, shuffle)
+//   whole_copy         the whole blob decoded into the workspace, one window copy (every other blob; the option off)
+enum class BoxPath { subset_transposer, subset_copy, whole_copy };
+BoxPath decode_box_path(bool subset_form, RangeForm form, bool option_on);
+
 struct Stage {
     std::string name;
     StageKind kind = StageKind::unsupported;
