@@ -38,6 +38,7 @@ from oracle import ref, sqy_oracle as o   # noqa: E402
 from sqeazy_amd import synth             # noqa: E402
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import bkrd_restate as R                                            # noqa: E402
+import diff_seam_cases as D                                         # noqa: E402
 from ref_stage_inputs import stage_input, stage_volume, stage_tile, case_id  # noqa: E402,F401  (the tests import them from here or there)
 from ref_stage_inputs import shuffle_volume, shuffle_param, shuffle_whole, shuffle_case_id  # noqa: E402,F401
 
@@ -494,6 +495,9 @@ def stage_table():
     T += seams
     # ---- rmestbkrd on faces that leave the histogram kernel's window, and a face of more than 32768 voxels ----
     T += _rows("rmestbkrd", ["uint16"], [(4, 40, 520), (3, 130, 260)], ["spread"], 5100)
+    # ---- diff3x3x1 at the seams of the product's kernels: the encode cases of tests/diff_seam_cases.py, same seeds ----
+    T += _rows("diff3x3x1", ["uint16"], D.ENCODE_SHAPES, ["random"], D.ENCODE_SEED0)
+    T += _rows("diff3x3x1", ["uint16"], D.MAX_SHAPES, ["max"], D.MAX_SEED0)
     for i, r in enumerate(T):
         r["id"] = case_id(r, i)
     return T

@@ -264,7 +264,10 @@ def test_diff_decode_rows_that_spill(sqy, oracle, shape, dtype):
                                          ((16, 4, 128), np.uint16), ((5, 600, 8), np.uint16), ((24, 300, 24), np.uint16), ((31, 513, 192), np.uint16), ((50, 40, 2048), np.uint16), ((128, 3, 128), np.uint16),
                                          ((2, 64, 64), np.uint16), ((7, 2100, 64), np.uint16), ((64, 256, 64), np.uint16), ((33, 1030, 256), np.uint16)])
 def test_diff_decode_one_launch_kernel(sqy, oracle, shape, dtype):
-    """16-bit, Z <= X, X a multiple of 8: the strip kernel (one launch, neighbour strips hand their edge rows over)"""
+    """16-bit, Z <= X, X a multiple of 8: the chain geometry of launch_diff3x3x1_decode -- diff3x3x1_u16_decode_frames_kernel, 8 frames per
+    launch, strips of 32 rows that recompute the halo rows they need of their neighbours (nothing is handed over), behind the inverse
+    transpose, in the destination itself where that lies on a 16-byte boundary (left_tmp).  Chains up to w = 128 columns here; the wider ones, the second item slot and the kernel's other seams:
+    tests/test_gpu_diff_seams.py"""
     rng = np.random.default_rng(sum(shape))
     vol = rng.integers(0, 65536 if dtype == np.uint16 else 256, shape).astype(dtype)
     blob = oracle.pipeline_encode("diff3x3x1->bitswap1->lz4", vol)
@@ -307,8 +310,9 @@ def test_decode_batches_with_dependencies_inside_a_step(sqy, oracle, seed, pipel
 
 @pytest.mark.parametrize("shape", [(2, 5000, 64), (3, 300, 4096), (5, 40, 8192), (64, 2049, 64), (17, 1023, 520), (8, 257, 8), (100, 33, 104)])
 def test_diff_decode_one_launch_kernel_strip_geometries(sqy, oracle, shape):
-    """strips of 1..20 rows, the last one short, rows from 16 bytes to 8 KiB; X = 8192 exceeds the exchange words a thread
-    takes and uses the per-frame kernels"""
+    """the chain geometry without a transpose in front (the copy of columns [w, X) on the second stream): strips of 32 rows with the last
+    one short (Y = 5000, 2049, 1023, 257, 33), rows from 16 bytes to 16 KiB, chains of 8 .. 104 columns.  Every shape here fits
+    diff3x3x1_decode_frames_fit; the per-frame chain behind it (w >= 328) is reached in tests/test_gpu_diff_seams.py"""
     rng = np.random.default_rng(sum(shape))
     vol = rng.integers(0, 65536, shape).astype(np.uint16)
     blob = oracle.pipeline_encode("diff3x3x1->lz4", vol)
