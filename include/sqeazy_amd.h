@@ -296,6 +296,26 @@ SQY_FUNCTION_PREFIX int SQYAMD_Decode_Box_UI16(const char* src, long srclength, 
 SQY_FUNCTION_PREFIX int SQYAMD_Decode_Box_UI8(const char* src, long srclength, const long* origin, const long* extent, unsigned rank, char* dst,
                                               long dst_capacity);
 
+/* MANY boxes of ONE blob in one call: box i is [origins + i rank, .. + dst_shapes + i rank) (count rows of `rank` longs each), its view at
+ * d_dsts[i] with the strides dst_strides + i rank (NULL: every view dense) -- each box as by SQYAMD_Decode_Box_*_Device, the same bytes.
+ * The header is fetched once, the LZ4 frames that the boxes' z-ranges need are united and decoded once by one launch, and ONE launch stores
+ * the voxels of all boxes; blobs off the subset path are decoded whole ONCE and one window copy cuts all boxes out.  Boxes may overlap in
+ * the blob; views that overlap each other are the caller's error, as in SQYAMD_Decode_BatchStrided_*.
+ * Everything is checked before a byte is written, every refusal returns 1 with every destination untouched: the rules of
+ * SQYAMD_Decode_Box_* for every box, count < 1, a NULL entry of d_dsts, more workgroups than one launch takes.  A damaged LZ4 frame that
+ * SOME box needs gives SQY_Decode's composite code for the call; the views may then hold anything, nothing outside them is written.  A
+ * damaged frame that no box needs goes unnoticed.  ("decode_boxes_joint" = 0: admitted as above, then SQYAMD_Decode_Box_* box by box.) */
+SQY_FUNCTION_PREFIX int SQYAMD_Decode_Boxes_UI16_Device(const void* d_src, long srclength, long count, const long* origins, void* const* d_dsts,
+                                                        const long* dst_shapes, const long* dst_strides, unsigned rank, void* hip_stream);
+SQY_FUNCTION_PREFIX int SQYAMD_Decode_Boxes_UI8_Device(const void* d_src, long srclength, long count, const long* origins, void* const* d_dsts,
+                                                       const long* dst_shapes, const long* dst_strides, unsigned rank, void* hip_stream);
+/* host-pointer variants: the blob is staged ONCE, the boxes come back dense and back to back in box order (box i starts at the summed bytes
+ * of boxes 0 .. i-1; 1 where dst_capacity, in bytes, is less than the sum of all) */
+SQY_FUNCTION_PREFIX int SQYAMD_Decode_Boxes_UI16(const char* src, long srclength, long count, const long* origins, const long* extents, unsigned rank,
+                                                 char* dst, long dst_capacity);
+SQY_FUNCTION_PREFIX int SQYAMD_Decode_Boxes_UI8(const char* src, long srclength, long count, const long* origins, const long* extents, unsigned rank,
+                                                char* dst, long dst_capacity);
+
 /* The volume a set of z-slab blobs makes, decoded with one call: the inverse of SQYAMD_PipelineEncode_Slabs_*_Device and the reader of
  * the multi-GPU container.  Blob i lies at d_src + offsets[i], lengths[i] bytes (host arrays; any alignment).  Every blob is a complete sqeazy
  * blob of the entry point's voxel type; all have the same rank and the same shape[1..]; their shape[0] may differ.  Slab i's voxels land at
@@ -533,6 +553,8 @@ SQY_FUNCTION_PREFIX void SQYAMD_Release_Workspace(void);
  *                                     the pipeline allows (0: every blob decoded whole and the range copied out -- same bytes)
  *   "decode_box_subset"               1 [SQY_NO_DECODE_BOX_SUBSET=1 -> 0]  SQYAMD_Decode_Box_*: only the LZ4 frames the box's z-range needs, where
  *                                     the pipeline allows (0: every blob decoded whole and the box copied out -- same bytes)
+ *   "decode_boxes_joint"              1 [SQY_NO_DECODE_BOXES_JOINT=1 -> 0]  SQYAMD_Decode_Boxes_*: the boxes' LZ4 frames united and decoded once, one
+ *                                     output launch for all boxes (0: every box on its own, as by SQYAMD_Decode_Box_* -- same bytes)
  *   "decode_slabs_joint"              1 [SQY_NO_DECODE_SLABS_JOINT=1 -> 0]  SQYAMD_Decode_Slabs_*: the chunked LZ4 blobs of a group indexed and
  *                                     decoded by one launch each (0: every blob on its own, as by SQYAMD_Decode_*_Device -- same bytes)
  *   "decode_batch_joint"              1 [SQY_NO_DECODE_BATCH_JOINT=1 -> 0]  SQYAMD_Decode_Batch_*: the joint-eligible blobs of a group ranked, decoded and

@@ -39,6 +39,7 @@ EXPORTED_SYMBOLS = (
     "SQYAMD_Decode_UI16_Device", "SQYAMD_Decode_UI8_Device",
     "SQYAMD_Decode_Frames_UI16_Device", "SQYAMD_Decode_Frames_UI8_Device", "SQYAMD_Decode_Frames_UI16", "SQYAMD_Decode_Frames_UI8",
     "SQYAMD_Decode_Box_UI16_Device", "SQYAMD_Decode_Box_UI8_Device", "SQYAMD_Decode_Box_UI16", "SQYAMD_Decode_Box_UI8",
+    "SQYAMD_Decode_Boxes_UI16_Device", "SQYAMD_Decode_Boxes_UI8_Device", "SQYAMD_Decode_Boxes_UI16", "SQYAMD_Decode_Boxes_UI8",
     "SQYAMD_Decode_Slabs_UI16_Device", "SQYAMD_Decode_Slabs_UI8_Device", "SQYAMD_Decode_Slabs_UI16", "SQYAMD_Decode_Slabs_UI8",
     "SQYAMD_Decode_Batch_UI16_Device", "SQYAMD_Decode_Batch_UI8_Device", "SQYAMD_Decode_Batch_UI16", "SQYAMD_Decode_Batch_UI8",
     "SQYAMD_Profile_Enable", "SQYAMD_Profile_Reset", "SQYAMD_Profile_Get",
@@ -130,6 +131,11 @@ def lib():
             getattr(L, f).argtypes = [ctypes.c_void_p, ctypes.c_long, c_long_p, ctypes.c_void_p, c_long_p, c_long_p, ctypes.c_uint, ctypes.c_void_p]
         for f in ("SQYAMD_Decode_Box_UI8", "SQYAMD_Decode_Box_UI16"):
             getattr(L, f).argtypes = [ctypes.c_void_p, ctypes.c_long, c_long_p, c_long_p, ctypes.c_uint, ctypes.c_void_p, ctypes.c_long]
+        for f in ("SQYAMD_Decode_Boxes_UI8_Device", "SQYAMD_Decode_Boxes_UI16_Device"):
+            getattr(L, f).argtypes = [ctypes.c_void_p, ctypes.c_long, ctypes.c_long, c_long_p, ctypes.POINTER(ctypes.c_void_p), c_long_p, c_long_p, ctypes.c_uint,
+                                      ctypes.c_void_p]
+        for f in ("SQYAMD_Decode_Boxes_UI8", "SQYAMD_Decode_Boxes_UI16"):
+            getattr(L, f).argtypes = [ctypes.c_void_p, ctypes.c_long, ctypes.c_long, c_long_p, c_long_p, ctypes.c_uint, ctypes.c_void_p, ctypes.c_long]
         for f in ("SQYAMD_Decode_Slabs_UI8_Device", "SQYAMD_Decode_Slabs_UI16_Device"):
             getattr(L, f).argtypes = [ctypes.c_void_p, c_long_p, c_long_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_long, c_long_p, ctypes.c_int,
                                       ctypes.c_void_p]
@@ -470,6 +476,44 @@ def decode_box_device(d_src, srclength, origin, d_dst, shape, strides, dtype, st
         ctypes.c_void_p(None if d_src is None else int(d_src)), ctypes.c_long(int(srclength)), None if origin is None else _longs(origin),
         ctypes.c_void_p(None if d_dst is None else int(d_dst)), None if shape is None else _longs(shape), None if strides is None else _longs(strides),
         ctypes.c_uint(len(shape) if shape is not None else len(origin or ())), ctypes.c_void_p(stream or 0))
+
+
+def _long_rows(rows):
+    """rows of longs, row after row (None stays None)"""
+    return None if rows is None else _longs([int(v) for row in rows for v in row])
+
+
+def decode_boxes(blob, origins, extents):
+    """SQYAMD_Decode_Boxes_UI8/UI16: the boxes [origins[i], origins[i] + extents[i]) of the blob's volume with one call; returns
+    (rc, [ndarray of shape extents[i], ..] or None)."""
+    blob = bytes(blob)
+    size = decompressed_sizeof(blob)
+    if size not in (1, 2) or not decompressed_shape(blob) or len(origins) != len(extents) or not len(extents):
+        return 1, None
+    dtype = np.uint16 if size == 2 else np.uint8
+    rank = len(extents[0])
+    shapes = [tuple(max(int(e), 0) for e in ext) for ext in extents]
+    counts = [int(np.prod(sh, dtype=np.int64)) for sh in shapes]
+    out = np.empty(sum(counts), dtype=dtype)
+    src = np.frombuffer(blob, dtype=np.uint8)
+    rc = getattr(lib(), "SQYAMD_Decode_Boxes_" + _suffix(dtype))(src.ctypes.data, ctypes.c_long(len(blob)), ctypes.c_long(len(extents)), _long_rows(origins),
+                                                                 _long_rows(extents), ctypes.c_uint(rank), out.ctypes.data, ctypes.c_long(out.nbytes))
+    if rc:
+        return rc, None
+    ends = np.cumsum(counts)
+    return 0, [out[e - c:e].reshape(sh) for e, c, sh in zip(ends, counts, shapes)]
+
+
+def decode_boxes_device(d_src, srclength, origins, d_dsts, shapes, strides, dtype, stream=None, count=None):
+    """SQYAMD_Decode_Boxes_*_Device on raw device pointers (ints): box i of extent shapes[i] that begins at voxel origins[i] of the blob, into
+    the view at d_dsts[i] with that shape and strides[i] in voxels (strides None: every view dense); only the views' voxels are written.
+    count: the number of boxes (default: as many as there are shapes).  Returns rc."""
+    n = len(shapes) if shapes is not None else len(origins or ())
+    first = (shapes or origins or [()])[0] if n else ()
+    ptrs = None if d_dsts is None else (ctypes.c_void_p * max(len(d_dsts), 1))(*[None if p is None else int(p) for p in d_dsts])
+    return getattr(lib(), "SQYAMD_Decode_Boxes_%s_Device" % _suffix(dtype))(
+        ctypes.c_void_p(None if d_src is None else int(d_src)), ctypes.c_long(int(srclength)), ctypes.c_long(n if count is None else int(count)), _long_rows(origins),
+        ptrs, _long_rows(shapes), _long_rows(strides), ctypes.c_uint(len(first)), ctypes.c_void_p(stream or 0))
 
 
 def decode_slabs_device(d_src, offsets, lengths, d_dst, dst_capacity, dtype, inflight=0, stream=None):

@@ -107,6 +107,25 @@ SQY_VIEW_HD inline RangeRun range_run(uint64_t t, uint32_t wpt, uint64_t w0, uin
     return RangeRun{first, lo, hi > lo ? hi : lo};
 }
 
+// Many boxes of one blob in one launch (SQYAMD_Decode_Boxes_*): job j owns range_job_groups workgroups of 256 threads -- its threads in
+// order, at least one workgroup (the job's first one also moves the tail voxels) -- and workgroup `own` of a job is the single-box
+// grid's block `own`: its thread tid is range_first_thread + own 256 + tid.  first_tile holds the prefix sums of the groups.
+SQY_VIEW_HD inline uint64_t range_job_groups(uint64_t w0, uint64_t w1, uint32_t wpt)
+{
+    const uint64_t g = (range_thread_count(w0, w1, wpt) + 255) / 256;
+    return g ? g : 1;
+}
+// the job of workgroup `group`: first_tile[lo] <= group < first_tile[lo + 1] (the kernels' batch_job_of_tile; njobs >= 1)
+SQY_VIEW_HD inline uint32_t range_job_of_group(const uint32_t* first_tile, uint32_t njobs, uint32_t group)
+{
+    uint32_t lo = 0, hi = njobs;
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (first_tile[mid] <= group) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
 // ---- the update of a window in the bit-plane layout (SQYAMD_Update_BatchWindow_*) ----
 // A voxel has the same bit position in every plane: with W voxels to a plane word (16 for 16-bit voxels, 8 for 8-bit ones), plane
 // W - 1 - b, word w, bit W - 1 - k is bit b of voxel W w + k.  A run of 128 voxels that begins at a word is 16 bytes of every plane -- four

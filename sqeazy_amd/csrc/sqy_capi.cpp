@@ -79,6 +79,7 @@ struct Options {
     std::atomic<long> host_l2_bytes;                    // rmestbkrd: the host CPU's L2 size as the reference's compass reads it (detected; tests set it)
     std::atomic<long> decode_frames_subset;             // frame-range decode: only the LZ4 frames the range needs, where the pipeline allows (0: full decode + copy)
     std::atomic<long> decode_box_subset;                // box decode: only the LZ4 frames the box's z-range needs, where the pipeline allows (0: full decode + window copy)
+    std::atomic<long> decode_boxes_joint;               // many boxes of one blob: the frames united, one output launch for all boxes (0: the single-box driver box by box)
     std::atomic<long> decode_slabs_joint;               // slab-set decode: the chunked LZ4 blobs of a group indexed and decoded by one launch each (0: blob by blob)
     std::atomic<long> decode_batch_joint;               // batch decode: the joint-eligible blobs of a group indexed, decoded and transposed back by one launch each (0: blob by blob)
     std::atomic<long> decode_batch_group_bytes;         // .. the LZ4 output one group holds at most (a group holds at least one blob)
@@ -103,7 +104,7 @@ struct Options {
           decode_two_waves(env_flag("SQY_NO_DECODE_TWO_WAVES") ? 0 : 1), noise_digest(env_flag("SQY_NO_NOISE_DIGEST") ? 0 : 1),
           transpose_tiles_per_wave(env_number("SQY_TRANSPOSE_TILES_PER_WAVE", sqy::kBitswap1TilesPerWave, 1, 64)), stored_tail_index(env_flag("SQY_NO_STORED_TAIL_INDEX") ? 0 : 1),
           host_l2_bytes((long)sqy::host_l2_cache_bytes()), decode_frames_subset(env_flag("SQY_NO_DECODE_FRAMES_SUBSET") ? 0 : 1),
-          decode_box_subset(env_flag("SQY_NO_DECODE_BOX_SUBSET") ? 0 : 1),
+          decode_box_subset(env_flag("SQY_NO_DECODE_BOX_SUBSET") ? 0 : 1), decode_boxes_joint(env_flag("SQY_NO_DECODE_BOXES_JOINT") ? 0 : 1),
           decode_slabs_joint(env_flag("SQY_NO_DECODE_SLABS_JOINT") ? 0 : 1), decode_batch_joint(env_flag("SQY_NO_DECODE_BATCH_JOINT") ? 0 : 1),
           decode_batch_group_bytes(env_number("SQY_DECODE_BATCH_GROUP_BYTES", (long)kSlabsGroupBytes, 1, (long)kSlabsGroupBytes)), encode_batch_joint(env_flag("SQY_NO_ENCODE_BATCH_JOINT") ? 0 : 1),
           encode_batch_group_bytes(env_number("SQY_ENCODE_BATCH_GROUP_BYTES", kBatchGroupBytesDefault, 1, kBatchBytesMax)),
@@ -127,6 +128,7 @@ struct Options {
         if (!std::strcmp(name, "host_l2_bytes")) return &host_l2_bytes;
         if (!std::strcmp(name, "decode_frames_subset")) return &decode_frames_subset;
         if (!std::strcmp(name, "decode_box_subset")) return &decode_box_subset;
+        if (!std::strcmp(name, "decode_boxes_joint")) return &decode_boxes_joint;
         if (!std::strcmp(name, "decode_slabs_joint")) return &decode_slabs_joint;
         if (!std::strcmp(name, "decode_batch_joint")) return &decode_batch_joint;
         if (!std::strcmp(name, "decode_batch_group_bytes")) return &decode_batch_group_bytes;
@@ -339,6 +341,7 @@ struct Workspace {
     DevBuf subset;            // frame-range decode: the frame list, the subset's block index, the frame_shuffle map of the range
     DevBuf range_full;        // frame-range decode of a blob the subset path does not take: the whole volume, the range copied out
     DevBuf box_window;        // box decode: the job and tile table of the window copy (one job)
+    DevBuf boxes_jobs;        // decode of many boxes of one blob: the job and tile table of its one output launch
     DevBuf slabs_index;       // slab-set decode: every blob's frame ranking (scratch, block index, counts) of a group
     DevBuf slabs_joint;       // .. the group's joint block index, frame output table, part descriptors and frame_shuffle maps
     DevBuf slabs_out;         // .. the group's LZ4 output (when it does not go straight to the volume)
@@ -363,7 +366,7 @@ struct Workspace {
     {
         ping.release(); pong.release(); lz4_scratch.release(); csize.release(); frame_off.release();
         io_src.release(); io_dst.release(); small.release(); plan.release(); dedupe.release(); diff_side.release(); spec.release(); digest.release(); bkrd.release();
-        subset.release(); range_full.release(); box_window.release(); slabs_index.release(); slabs_joint.release(); slabs_out.release(); slabs_host.release();
+        subset.release(); range_full.release(); box_window.release(); boxes_jobs.release(); slabs_index.release(); slabs_joint.release(); slabs_out.release(); slabs_host.release();
         batch_stream.release(); batch_scratch.release(); batch_tables.release(); batch_quant.release(); batch_host.release();
         batch_pack.release(); batch_pack_one.release(); for (DevBuf& b : batch_views) b.release(); for (DevBuf& b : batch_windows) b.release();
         for (DevBuf& b : batch_compares) b.release();
@@ -2182,6 +2185,17 @@ struct DecodeCall {
 
     int frames_subset(uint64_t z0, uint64_t nz, bool direct_ok, bool* taken)
     {
+        if (const int rc = frames_subset(std::vector<std::pair<uint64_t, uint64_t>>{{z0, nz}}, direct_ok, taken)) return rc;
+        range_plan = sqy::frame_range_plan_of(ranges_plan, 0);
+        range_plan.direct = range_plan.direct && direct_ok;
+        return 0;
+    }
+
+    // the same for a set of ranges (z0, nz) (SQYAMD_Decode_Boxes_*): one table upload, one LZ4 launch over the united frames into one
+    // buffer; ranges_plan says where each range lies in there.  direct_ok: one range only
+    sqy::FrameRangesPlan ranges_plan;
+    int frames_subset(const std::vector<std::pair<uint64_t, uint64_t>>& ranges, bool direct_ok, bool* taken)
+    {
         *taken = false;
         const size_t ns = pipe.stages.size();
         if (ns == 0 || pipe.stages[ns - 1].kind != StageKind::lz4 || lead >= ns) return 0;
@@ -2213,11 +2227,11 @@ struct DecodeCall {
             if (!fold) return 0;
         }
         // the LZ4 frames the range needs and where its bytes lie behind their decode
-        range_plan = sqy::frame_range_plan(form, n, e, h.shape[0], z0, nz, chunk, total, nframes, fs_map, fbp, P);
+        ranges_plan = sqy::frame_ranges_plan(form, n, e, h.shape[0], ranges, chunk, total, nframes, fs_map, fbp, P);
         range_form = form;
-        range_plan.direct = range_plan.direct && direct_ok;
-        const sqy::FrameRangePlan& p = range_plan;
+        const sqy::FrameRangesPlan& p = ranges_plan;
         if (!p.ok) return 0;
+        const bool direct = direct_ok && ranges.size() == 1 && p.boxes[0].direct;
 
         // the tables: ids | subset frame starts | remap | subset block index
         const uint64_t nsel = p.ids.size(), mpf = (chunk + ix.block_bytes - 1) / ix.block_bytes;
@@ -2231,7 +2245,7 @@ struct DecodeCall {
 
         *taken = true;
         // shuffle with the range on place boundaries (frame_chunk_size 1): straight into d_dst; else through the workspace
-        uint8_t* sbuf = p.direct ? static_cast<uint8_t*>(d_dst) : work_buf(p.out_bytes);     // where the subset decodes to
+        uint8_t* sbuf = direct ? static_cast<uint8_t*>(d_dst) : work_buf(p.out_bytes);       // where the subset decodes to
         if (!sbuf) return 1;
         // places of the range that no slot names come out as zeros (frame_shuffle's inverse)
         for (const auto& run : p.zero_runs) SQY_HIP(hipMemsetAsync(sbuf + run.first * fbp, 0, (run.second - run.first) * fbp, stream));
@@ -2256,6 +2270,10 @@ struct DecodeCall {
         *r = sqy::Bitswap1Range{};
         std::copy(p.plane, p.plane + 16, r->plane);
         r->tail = p.tail; r->w0 = p.w0; r->w1 = p.w1; r->v0 = p.v0; r->v1 = p.v1; r->L = p.L;
+        return range_lut(lut);
+    }
+    int range_lut(const uint16_t** lut)
+    {
         *lut = nullptr;
         if (range_form == sqy::RangeForm::planes_lut) {
             if (quantiser_lut_to_device(pipe.stages[lead], ws)) return 1;
@@ -2730,6 +2748,170 @@ int decode_box_from_host(const char* src, long srclength, const long* origin, co
     const uint64_t box_bytes = w.Z * w.Y * w.X * (uint64_t)elem_size;
     return decode_staged(src, (uint64_t)srclength, dst, box_bytes, [&](Context& cx, void* d_src, void* d_dst, hipStream_t stream) {
         return decode_box_on_device(cx, d_src, (uint64_t)srclength, origin, extent, nullptr, rank, d_dst, elem_size, stream);
+    });
+}
+
+// ---- many boxes of one large blob (SQYAMD_Decode_Boxes_*) ------------------------------------------------------------------------
+// SQYAMD_Decode_Box_*'s driver for a table of boxes: ONE header fetch, frame index, pruned LZ4 launch over the frames of all boxes' z-ranges
+// united (DecodeCall::frames_subset on the ranges) and ONE output launch for all boxes; sqy::decode_boxes_path says what runs.
+static_assert(sizeof(sqy::Bitswap1BoxJob) % 16 == 0, "the box job's layout");
+
+// the boxes' last launch behind DecodeCall::frames_subset: box i (ws[i], its view vs[i] at dsts[i]) out of the united frames in c.range_buf
+int boxes_range_out(DecodeCall& c, WindowLaunch& l, TiledJobs<sqy::Bitswap1BoxJob>& tj, const std::vector<sqy::BatchWindow>& ws, const std::vector<WindowView>& vs,
+                    void* const* dsts, unsigned rank)
+{
+    hipStream_t stream = c.stream;
+    std::vector<PendingEvent>* pend = c.pend;
+    const sqy::FrameRangesPlan& p = c.ranges_plan;
+    const size_t count = ws.size();
+    if (p.boxes.size() != count) return 1;
+    const uint32_t* d_tiles = nullptr;
+    if (sqy::decode_boxes_path(true, c.range_form, true, true) == sqy::BoxesPath::subset_transposer) {
+        const uint16_t* lut = nullptr;
+        if (c.range_lut(&lut)) return 1;
+        const uint32_t wpt = 128u / (8u * (uint32_t)p.we);
+        for (size_t i = 0; i < count; ++i) {
+            const sqy::BatchWindow& w = ws[i];
+            const sqy::FrameRangesBox& b = p.boxes[i];
+            sqy::Bitswap1BoxJob j;
+            j.view = dsts[i];
+            j.g = sqy::WindowGeometry{w.bY, w.bX, w.oz, w.oy, w.ox, w.Z, w.Y, w.X, vs[i].sz, vs[i].sy};
+            std::copy(b.plane, b.plane + 16, j.r.plane);
+            j.r.tail = b.tail; j.r.w0 = b.w0; j.r.w1 = b.w1; j.r.v0 = b.v0; j.r.v1 = b.v1; j.r.L = b.L;
+            j.t0 = sqy::range_first_thread(b.w0, wpt);
+            if (!sqy::bitswap1_box_job_ok(j)) return 1;
+            tj.jobs.push_back(j);
+            tj.first_tile.push_back(tj.ntiles);
+            tj.ntiles += (uint32_t)sqy::range_job_groups(b.w0, b.w1, wpt);
+        }
+        if (tj.upload(stream, c.cx.ws.boxes_jobs, &d_tiles)) return 1;
+        SQY_TIMED(lut ? "bitswap1_quantiser_decode_boxes" : "bitswap1_decode_boxes",
+                  sqy::launch_bitswap1_decode_range_windows(c.range_buf, static_cast<const sqy::Bitswap1BoxJob*>(c.cx.ws.boxes_jobs.p), d_tiles, (uint32_t)count, tj.ntiles,
+                                                            p.we, lut, stream));
+        return 0;
+    }
+    // plain, shuffle: box i's range in the workspace is a blob of its frames, the box begins at its first one
+    for (size_t i = 0; i < count; ++i) {
+        sqy::BatchWindow in_range = ws[i];
+        if (rank == 3) { in_range.bZ = in_range.Z; in_range.oz = 0; }
+        else if (rank == 2) { in_range.bY = in_range.Y; in_range.oy = 0; }
+        else { in_range.bX = in_range.X; in_range.ox = 0; }
+        l.add(dsts[i], c.range_buf + p.boxes[i].range_at, in_range, vs[i], false);
+    }
+    if (l.upload(stream, c.cx.ws.boxes_jobs, &d_tiles)) return 1;
+    SQY_TIMED("boxes_window_copy", sqy::launch_batch_window_copy(static_cast<const sqy::BatchWindowJob*>(c.cx.ws.boxes_jobs.p), d_tiles, (uint32_t)count, l.ntiles,
+                                                                  c.h.elem_size(), stream));
+    return 0;
+}
+
+// Box i = [origins + i rank, .. + extents + i rank) of the blob into the view at d_dsts[i] (strides + i rank, or dense).  The checks of
+// decode_box_on_device for every box, and the launches' sizes -- all before anything is written.
+int decode_boxes_on_device(Context& cx, const void* d_src_v, uint64_t srclen, size_t count, const long* origins, void* const* d_dsts, const long* extents,
+                           const long* strides, unsigned rank, int want_elem, hipStream_t stream)
+{
+    const uint8_t* d_src = static_cast<const uint8_t*>(d_src_v);
+    std::vector<PendingEvent>* pend = &cx.pending;
+    DrainOnExit drain{stream, &cx.pending, cx.side};
+    sqy::HeaderInfo h;
+    if (fetch_header(d_src, srclen, stream, h)) return 1;
+    uint64_t raw_bytes = 0;
+    if (!admit_blob(h, srclen, want_elem, &raw_bytes)) return 1;
+    std::vector<sqy::BatchWindow> ws(count);
+    std::vector<WindowView> vs(count);
+    std::vector<std::pair<uint64_t, uint64_t>> ranges(count);
+    const uint64_t frame_voxels = raw_bytes / (uint64_t)want_elem / h.shape[0];
+    uint64_t copy_tiles = 0, range_groups = 0;               // what the one output launch may hold, whichever it is
+    for (size_t i = 0; i < count; ++i) {
+        const long* o = origins + i * rank;
+        const long* e = extents + i * rank;
+        if (!sqy::admit_window(h.shape, o, e, rank, &ws[i])) {
+            std::fprintf(stderr, "[sqeazy]\t decode boxes: box %zu does not lie inside the blob's shape, or has another rank\n", i);
+            return 1;
+        }
+        vs[i] = window_view(ws[i], strides ? strides + i * rank : nullptr, rank);
+        ranges[i] = {(uint64_t)o[0], (uint64_t)e[0]};
+        copy_tiles += sqy::batch_bitswap1_tiles(ws[i].Z * ws[i].Y * ws[i].X);
+        range_groups += (uint64_t)e[0] * frame_voxels / sqy::kBatchTileVoxels + 2;      // (at least range_job_groups of the box's words)
+    }
+    if (std::max(copy_tiles, range_groups) > 0x7fffffffull) {
+        std::fprintf(stderr, "[sqeazy]\t decode boxes: too many workgroups for one launch\n");
+        return 1;
+    }
+    if (sqy::decode_boxes_path(false, sqy::RangeForm::plain, false, g_opt.decode_boxes_joint.load() != 0) == sqy::BoxesPath::box_by_box) {
+        for (size_t i = 0; i < count; ++i)
+            if (const int rc = decode_box_on_device(cx, d_src_v, srclen, origins + i * rank, extents + i * rank, strides ? strides + i * rank : nullptr, rank, d_dsts[i],
+                                                    want_elem, stream))
+                return rc;
+        return 0;
+    }
+    WindowLaunch l;                                                     // (both wait for the stream before their tables go)
+    TiledJobs<sqy::Bitswap1BoxJob> tj;
+    if (g_opt.decode_box_subset.load()) {
+        DecodeCall c(cx, stream, d_dsts[0], h, Pipeline::from_string(h.pipename), raw_bytes / (uint64_t)want_elem, d_src + h.size);
+        bool taken = false;
+        if (const int rc = c.frames_subset(ranges, false, &taken)) return rc;
+        if (taken) {
+            if (const int rc = boxes_range_out(c, l, tj, ws, vs, d_dsts, rank)) return rc;
+            return c.finish();
+        }
+    }
+    // sqy::BoxesPath::whole_copy: the whole volume ONCE, then all boxes in one launch
+    if (cx.ws.range_full.ensure(std::max<uint64_t>(raw_bytes, 16))) return 1;
+    if (const int rc = decode_on_device(cx, d_src_v, srclen, cx.ws.range_full.p, raw_bytes, want_elem, stream)) return rc;
+    for (size_t i = 0; i < count; ++i) l.add(d_dsts[i], cx.ws.range_full.p, ws[i], vs[i], false);
+    const uint32_t* d_tiles = nullptr;
+    if (l.upload(stream, cx.ws.boxes_jobs, &d_tiles)) return 1;
+    SQY_TIMED("boxes_window_copy", sqy::launch_batch_window_copy(static_cast<const sqy::BatchWindowJob*>(cx.ws.boxes_jobs.p), d_tiles, (uint32_t)count, l.ntiles, want_elem,
+                                                                  stream));
+    SQY_HIP(hipStreamSynchronize(stream));
+    if (g_prof_on.load()) prof_collect(cx.pending);
+    return 0;
+}
+
+// what SQYAMD_Decode_Boxes_* checks without a header, before a device is looked for: box_arguments_ok for every box
+bool boxes_arguments_ok(const void* src, long srclength, long count, const long* origins, const void* const* dsts, const long* extents, unsigned rank)
+{
+    if (!src || srclength <= 0 || count < 1 || count > INT_MAX || !origins || !extents || rank == 0 || rank > 3) return false;
+    for (long i = 0; i < count; ++i)
+        if (!box_arguments_ok(src, srclength, origins + (size_t)i * rank, dsts ? dsts[i] : src, extents + (size_t)i * rank, rank)) return false;
+    return true;
+}
+
+int decode_boxes_device(const void* d_src, long srclength, long count, const long* origins, void* const* d_dsts, const long* dst_shapes, const long* dst_strides,
+                        unsigned rank, int elem_size, void* hip_stream)
+{
+    if (!d_dsts || !boxes_arguments_ok(d_src, srclength, count, origins, d_dsts, dst_shapes, rank)) { std::fprintf(stderr, "[sqeazy]\t decode boxes: bad arguments\n"); return 1; }
+    std::vector<sqy::BatchView> views;
+    if (admit_views("decode boxes", d_dsts, dst_shapes, dst_strides, rank, (int)count, elem_size, &views)) return 1;
+    ContextLease lease;
+    if (!lease.ctx) { std::fprintf(stderr, "[sqeazy]\t no usable HIP device\n"); return 1; }
+    return decode_boxes_on_device(*lease.ctx, d_src, (uint64_t)srclength, (size_t)count, origins, d_dsts, dst_shapes, dst_strides, rank, elem_size,
+                                  static_cast<hipStream_t>(hip_stream));
+}
+
+// host pointers: the header and every box are checked here, before anything is staged; the boxes come back dense, back to back in box order
+int decode_boxes_from_host(const char* src, long srclength, long count, const long* origins, const long* extents, unsigned rank, char* dst, long dst_capacity, int elem_size)
+{
+    if (!dst || !boxes_arguments_ok(src, srclength, count, origins, nullptr, extents, rank)) { std::fprintf(stderr, "[sqeazy]\t decode boxes: bad arguments\n"); return 1; }
+    const sqy::HeaderInfo h = sqy::header_unpack(src, src + srclength);
+    if (!h.valid) { std::fprintf(stderr, "[sqeazy]\t unable to find a sqy header in the blob\n"); return 1; }
+    uint64_t raw = 0;
+    if (!header_shape_ok(h, (uint64_t)srclength, &raw)) return 1;
+    if (h.elem_size() != elem_size) { std::fprintf(stderr, "[sqeazy]\t blob holds %s voxels\n", h.type.c_str()); return 1; }
+    std::vector<uint64_t> at((size_t)count + 1, 0);                    // (a box is no larger than the volume, count fits an int: no wrap)
+    for (long i = 0; i < count; ++i) {
+        sqy::BatchWindow w;
+        if (!sqy::admit_window(h.shape, origins + (size_t)i * rank, extents + (size_t)i * rank, rank, &w)) {
+            std::fprintf(stderr, "[sqeazy]\t decode boxes: box %ld does not lie inside the blob's shape\n", i);
+            return 1;
+        }
+        at[(size_t)i + 1] = at[(size_t)i] + w.Z * w.Y * w.X * (uint64_t)elem_size;
+    }
+    if (at.back() > (uint64_t)std::max(dst_capacity, 0l)) { std::fprintf(stderr, "[sqeazy]\t decode boxes: buffer too small\n"); return 1; }
+    return decode_staged(src, (uint64_t)srclength, dst, at.back(), [&](Context& cx, void* d_src, void* d_dst, hipStream_t stream) {
+        std::vector<void*> ptrs((size_t)count);
+        for (long i = 0; i < count; ++i) ptrs[(size_t)i] = static_cast<uint8_t*>(d_dst) + at[(size_t)i];
+        return decode_boxes_on_device(cx, d_src, (uint64_t)srclength, (size_t)count, origins, ptrs.data(), extents, nullptr, rank, elem_size, stream);
     });
 }
 
@@ -4711,6 +4893,28 @@ int SQYAMD_Decode_Box_UI16(const char* src, long srclength, const long* origin, 
 int SQYAMD_Decode_Box_UI8(const char* src, long srclength, const long* origin, const long* extent, unsigned rank, char* dst, long dst_capacity)
 {
     return guarded([&]() -> int { return decode_box_from_host(src, srclength, origin, extent, rank, dst, dst_capacity, 1); });
+}
+
+int SQYAMD_Decode_Boxes_UI16_Device(const void* d_src, long srclength, long count, const long* origins, void* const* d_dsts, const long* dst_shapes,
+                                    const long* dst_strides, unsigned rank, void* hip_stream)
+{
+    return guarded([&]() -> int { return decode_boxes_device(d_src, srclength, count, origins, d_dsts, dst_shapes, dst_strides, rank, 2, hip_stream); });
+}
+
+int SQYAMD_Decode_Boxes_UI8_Device(const void* d_src, long srclength, long count, const long* origins, void* const* d_dsts, const long* dst_shapes,
+                                   const long* dst_strides, unsigned rank, void* hip_stream)
+{
+    return guarded([&]() -> int { return decode_boxes_device(d_src, srclength, count, origins, d_dsts, dst_shapes, dst_strides, rank, 1, hip_stream); });
+}
+
+int SQYAMD_Decode_Boxes_UI16(const char* src, long srclength, long count, const long* origins, const long* extents, unsigned rank, char* dst, long dst_capacity)
+{
+    return guarded([&]() -> int { return decode_boxes_from_host(src, srclength, count, origins, extents, rank, dst, dst_capacity, 2); });
+}
+
+int SQYAMD_Decode_Boxes_UI8(const char* src, long srclength, long count, const long* origins, const long* extents, unsigned rank, char* dst, long dst_capacity)
+{
+    return guarded([&]() -> int { return decode_boxes_from_host(src, srclength, count, origins, extents, rank, dst, dst_capacity, 1); });
 }
 
 int SQYAMD_Decode_Slabs_UI16_Device(const void* d_src, const long* offsets, const long* lengths, int nslabs, void* d_dst, long dst_capacity,

@@ -5,6 +5,8 @@
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
 
+#include "sqy_batch_window.hpp"
+
 namespace sqy {
 
 struct Lz4DedupeLayout;          // sqy_pipeline.hpp (as kLz4FrameHead and kLz4FrameGap)
@@ -387,6 +389,21 @@ hipError_t launch_bitswap1_decode_range(const uint8_t* in, void* out, const Bits
 // where in + plane[s] - w0 elem_size is on the 16-byte grid for every s, word by word where not.  Nothing but the view's voxels is written.
 hipError_t launch_bitswap1_decode_range_window(const uint8_t* in, const Bitswap1Range& r, const BatchWindowJob& box, int elem_size, const uint16_t* lut,
                                                hipStream_t stream);
+// ---- many boxes of one large blob (SQYAMD_Decode_Boxes_*) ----
+// launch_bitswap1_decode_range_window for a table of boxes in ONE launch: job j stores the voxels of its box (g: the blob's rows, the box
+// and the view's pitches, as sqy::WindowGeometry; view: its base) out of the range r, whose offsets point into the ONE buffer `in` that
+// holds the united LZ4 frames of all boxes; t0 = sqy::range_first_thread(r.w0, words per thread).  d_first_tile: njobs + 1 words, the
+// prefix sums of sqy::range_job_groups(r.w0, r.w1, words per thread); ngroups their sum.  Every job must pass bitswap1_box_job_ok (the
+// range holds the box).  Nothing but the views' voxels is written.
+struct Bitswap1BoxJob {
+    void* view;
+    WindowGeometry g;
+    Bitswap1Range r;
+    uint64_t t0;
+};
+bool bitswap1_box_job_ok(const Bitswap1BoxJob& j);
+hipError_t launch_bitswap1_decode_range_windows(const uint8_t* in, const Bitswap1BoxJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ngroups,
+                                                int elem_size, const uint16_t* lut, hipStream_t stream);
 // ---- batch decode (SQYAMD_Decode_Batch_*): the blobs of a group share one launch of every kernel ----
 // The inverse of launch_bitswap1_batch on the same tables: job j's planes + tail at `in` (16-byte aligned) become its `len` voxels at
 // `out` (any voxel-aligned address; sixteen-byte stores where it and the plane size allow, word by word where not).  first_tile: njobs + 1

@@ -8261,27 +8261,26 @@ void bitswap1_decode_batch_window_kernel(const BatchWindowJob* __restrict__ jobs
 // last thread; streams whose segment or chunk size is no multiple of 16).  A thread clips its run against the box first and is gone before
 // it has loaded a plane word when nothing of it lies inside.  LUT (ELEM 1): the 8-bit planes of quantiser->bitswap1, 16-bit voxels out of
 // the decode table, staged in LDS as in bitswap1_quantiser_decode_batch_kernel; a word's eight voxels leave as one piece of 16 bytes.
+// The body is range_window_body: workgroup `group` of the grid whose first thread is t0 of the ABSOLUTE grid (group 0 also moves the
+// tail); sl: the decode table in LDS (LUT).  bitswap1_decode_range_windows_kernel (SQYAMD_Decode_Boxes_*) runs the same body for many boxes.
 template <int ELEM, bool LUT>
-__global__ __launch_bounds__(256)
-void bitswap1_decode_range_window_kernel(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, Bitswap1Range a, WindowGeometry g, uint64_t t0,
-                                         const uint16_t* __restrict__ lut)
+__device__ __forceinline__ void range_window_body(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, const Bitswap1Range& a, const WindowGeometry& g, uint64_t t0,
+                                                  uint32_t group, const uint16_t* sl)
 {
     static_assert(!LUT || ELEM == 1, "the look-up follows 8-bit planes");
     constexpr uint32_t W = 8 * ELEM, WPT = BSWB_THREAD_VOX / W;        // voxels per word, words per thread
     constexpr int OUT = LUT ? 2 : ELEM;                                // bytes of a voxel in the view
-    __shared__ uint16_t sl[LUT ? 256 : 1];
     const uint32_t tid = threadIdx.x;
-    if constexpr (LUT) { sl[tid] = lut[tid]; __syncthreads(); }
     WindowPiece cur;
     const uint64_t tail0 = a.v0 > a.L ? a.v0 : a.L;
-    if (blockIdx.x == 0 && tail0 + tid < a.v1) {                      // tail voxels: verbatim (or looked up), those of the box
+    if (group == 0 && tail0 + tid < a.v1) {                          // tail voxels: verbatim (or looked up), those of the box
         WindowClip ct = window_clip_start(g, tail0 + tid, 1);
         if (window_clip_next(g, &ct, &cur)) {
             const uint32_t x = view_voxel_load<ELEM>(in + a.tail, tid);
             view_voxel_store<OUT>(out, cur.dst_off, LUT ? (uint32_t)sl[x & 0xffu] : x);
         }
     }
-    const RangeRun run = range_run(t0 + (uint64_t)blockIdx.x * 256u + tid, WPT, a.w0, a.w1);
+    const RangeRun run = range_run(t0 + (uint64_t)group * 256u + tid, WPT, a.w0, a.w1);
     if (run.lo == run.hi) return;
     WindowClip c = window_clip_start(g, run.first * W, (uint64_t)run.hi * W);
     bool have = window_clip_next(g, &c, &cur);
@@ -8383,6 +8382,34 @@ void bitswap1_decode_range_window_kernel(const uint8_t* __restrict__ in, uint8_t
                 window_scatter16<1>(out, g, c, cur, have, make_uint4(d[0], d[1], d[2], d[3]), 8u * gq, run.hi - gq >= 2u ? 16u : 8u);
         }
     }
+}
+
+template <int ELEM, bool LUT>
+__global__ __launch_bounds__(256)
+void bitswap1_decode_range_window_kernel(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, Bitswap1Range a, WindowGeometry g, uint64_t t0,
+                                         const uint16_t* __restrict__ lut)
+{
+    __shared__ uint16_t sl[LUT ? 256 : 1];
+    if constexpr (LUT) { sl[threadIdx.x] = lut[threadIdx.x]; __syncthreads(); }
+    range_window_body<ELEM, LUT>(in, out, a, g, t0, blockIdx.x, sl);
+}
+
+// ---- many boxes of one large blob (SQYAMD_Decode_Boxes_*) --------------------------------------------------------------------------------
+// bitswap1_decode_range_window_kernel driven by a job table in device memory: every box has its own view, geometry, range addressing (into
+// ONE compaction of the united LZ4 frames, at `in`) and first thread t0.  Job j owns first_tile[j + 1] - first_tile[j] =
+// sqy::range_job_groups(w0, w1, WPT) workgroups, found by batch_job_of_tile's binary search; its first workgroup also moves its tail
+// voxels.  The job is uniform per workgroup: it is read through a uniform index, so its fields live in scalar registers.
+template <int ELEM, bool LUT>
+__global__ __launch_bounds__(256)
+void bitswap1_decode_range_windows_kernel(const uint8_t* __restrict__ in, const Bitswap1BoxJob* __restrict__ jobs, const uint32_t* __restrict__ first_tile, uint32_t njobs,
+                                          const uint16_t* __restrict__ lut)
+{
+    __shared__ uint16_t sl[LUT ? 256 : 1];
+    if constexpr (LUT) { sl[threadIdx.x] = lut[threadIdx.x]; __syncthreads(); }
+    const uint32_t j = batch_job_of_tile(first_tile, njobs);
+    const Bitswap1BoxJob* __restrict__ job = jobs + j;
+    const uint32_t own = blockIdx.x - first_tile[j];
+    range_window_body<ELEM, LUT>(in, static_cast<uint8_t*>(job->view), job->r, job->g, job->t0, own, sl);
 }
 
 // ---- the compare of a window with its view (SQYAMD_Compare_BatchWindow_*) ------------------------------------------------------------------
@@ -8808,6 +8835,26 @@ hipError_t launch_bitswap1_decode_range_window(const uint8_t* in, const Bitswap1
     else if (lut) hipLaunchKernelGGL((bitswap1_decode_range_window_kernel<1, true>), grid, dim3(256), 0, stream, in, out, r, g, t0, lut);
     else hipLaunchKernelGGL((bitswap1_decode_range_window_kernel<1, false>), grid, dim3(256), 0, stream, in, out, r, g, t0, lut);
     return hipGetLastError();
+}
+
+hipError_t launch_bitswap1_decode_range_windows(const uint8_t* in, const Bitswap1BoxJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ngroups,
+                                                int elem_size, const uint16_t* lut, hipStream_t stream)
+{
+    if (njobs == 0 || ngroups < njobs || (elem_size != 1 && elem_size != 2) || (lut && elem_size != 1)) return hipErrorInvalidValue;
+    const dim3 grid(ngroups);
+    if (elem_size == 2) hipLaunchKernelGGL((bitswap1_decode_range_windows_kernel<2, false>), grid, dim3(256), 0, stream, in, d_jobs, d_first_tile, njobs, lut);
+    else if (lut) hipLaunchKernelGGL((bitswap1_decode_range_windows_kernel<1, true>), grid, dim3(256), 0, stream, in, d_jobs, d_first_tile, njobs, lut);
+    else hipLaunchKernelGGL((bitswap1_decode_range_windows_kernel<1, false>), grid, dim3(256), 0, stream, in, d_jobs, d_first_tile, njobs, lut);
+    return hipGetLastError();
+}
+
+// what launch_bitswap1_decode_range_window checks of its box, for a job of the table
+bool bitswap1_box_job_ok(const Bitswap1BoxJob& j)
+{
+    const Bitswap1Range& r = j.r;
+    const WindowGeometry& g = j.g;
+    if (r.v1 <= r.v0 || r.w1 < r.w0 || !j.view || g.Z == 0 || g.Y == 0 || g.X == 0) return false;
+    return ((g.oz * g.bY + g.oy) * g.bX + g.ox) >= r.v0 && ((g.oz + g.Z - 1) * g.bY + g.oy + g.Y - 1) * g.bX + g.ox + g.X <= r.v1;
 }
 
 hipError_t launch_batch_view_copy(const BatchViewJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ntiles, int elem_size, bool to_view,

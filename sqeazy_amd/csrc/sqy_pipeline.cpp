@@ -748,33 +748,47 @@ bool frame_shuffle_decode_map(std::vector<unsigned char>* map, uint64_t Z, std::
     return true;
 }
 
-FrameRangePlan frame_range_plan(RangeForm form, uint64_t n, int elem, uint64_t shape0, uint64_t z0, uint64_t nz, uint64_t chunk, uint64_t total,
-                                uint32_t nframes, const std::vector<unsigned char>& struck_map, uint64_t place_bytes, uint64_t places)
+FrameRangesPlan frame_ranges_plan(RangeForm form, uint64_t n, int elem, uint64_t shape0, const std::vector<std::pair<uint64_t, uint64_t>>& ranges, uint64_t chunk,
+                                  uint64_t total, uint32_t nframes, const std::vector<unsigned char>& struck_map, uint64_t place_bytes, uint64_t places)
 {
-    FrameRangePlan p;
+    FrameRangesPlan p;
     const uint64_t e = (uint64_t)elem;
     p.we = form == RangeForm::planes ? elem : 1;
     const uint64_t we = (uint64_t)p.we;
-    // a range inside the volume, the stream the voxels in their order, one frame per chunk
-    if (shape0 == 0 || n == 0 || n % shape0 != 0 || nz == 0 || z0 >= shape0 || nz > shape0 - z0 || (elem != 1 && elem != 2) || chunk == 0 ||
+    // ranges inside the volume, the stream the voxels in their order, one frame per chunk
+    if (shape0 == 0 || n == 0 || n % shape0 != 0 || ranges.empty() || (elem != 1 && elem != 2) || chunk == 0 ||
         total != n * (form == RangeForm::planes_lut ? 1 : e) || (uint64_t)nframes != (total + chunk - 1) / chunk)
         return p;
+    for (const auto& r : ranges)
+        if (r.second == 0 || r.first >= shape0 || r.second > shape0 - r.first) return p;
     const uint64_t vpf = n / shape0, fb = vpf * e;
-    p.v0 = z0 * vpf;
-    p.v1 = (z0 + nz) * vpf;
+    std::vector<FrameRangesBox> boxes(ranges.size());
+    for (size_t i = 0; i < ranges.size(); ++i) {
+        boxes[i].v0 = ranges[i].first * vpf;
+        boxes[i].v1 = (ranges[i].first + ranges[i].second) * vpf;
+    }
     if (form == RangeForm::shuffle) {
         if (!lz4_folds_into_shuffle(nframes, nframes, total, chunk, places, place_bytes) || struck_map.size() != places * 8) return p;
-        p.pa = z0 * fb / place_bytes;
-        p.pb = ((z0 + nz) * fb + place_bytes - 1) / place_bytes;
-        const uint64_t cpf = place_bytes / chunk, np = p.pb - p.pa;
+        // the places some range needs, compacted in ascending order: cplace[v] is place v's index in there
+        std::vector<char> wanted(places, 0);
+        for (size_t i = 0; i < ranges.size(); ++i) {
+            FrameRangesBox& b = boxes[i];
+            b.pa = ranges[i].first * fb / place_bytes;
+            b.pb = ((ranges[i].first + ranges[i].second) * fb + place_bytes - 1) / place_bytes;
+            for (uint64_t v = b.pa; v < b.pb; ++v) wanted[v] = 1;
+        }
+        std::vector<uint64_t> cplace(places, 0);
+        uint64_t np = 0;
+        for (uint64_t v = 0; v < places; ++v) if (wanted[v]) cplace[v] = np++;
+        const uint64_t cpf = place_bytes / chunk;
         std::vector<char> named(np, 0);
         // (the struck map: the last slot named for a place wins, as in the full decode)
         for (uint64_t i = 0; i < places; ++i) {
             uint64_t v;
             std::memcpy(&v, struck_map.data() + 8 * i, 8);
-            if (v == ~0ull || v < p.pa || v >= p.pb) continue;
-            p.remap.push_back(v - p.pa);
-            named[v - p.pa] = 1;
+            if (v == ~0ull || v >= places || !wanted[v]) continue;
+            p.remap.push_back(cplace[v]);
+            named[cplace[v]] = 1;
             for (uint64_t c = 0; c < cpf; ++c) p.ids.push_back((uint32_t)(i * cpf + c));
         }
         for (uint64_t k = 0; k < np;) {
@@ -785,26 +799,35 @@ FrameRangePlan frame_range_plan(RangeForm form, uint64_t n, int elem, uint64_t s
             k = k1;
         }
         p.out_bytes = np * place_bytes;
-        p.range_at = z0 * fb - p.pa * place_bytes;
-        p.direct = p.range_at == 0 && p.pb * place_bytes == (z0 + nz) * fb;
+        for (size_t i = 0; i < ranges.size(); ++i) {
+            FrameRangesBox& b = boxes[i];
+            // (a range's own places are consecutive in the compaction: all of [pa, pb) are wanted)
+            const uint64_t z0 = ranges[i].first, nz = ranges[i].second, in_place = z0 * fb - b.pa * place_bytes;
+            b.range_at = cplace[b.pa] * place_bytes + in_place;
+            b.direct = b.range_at == 0 && in_place == 0 && b.pb * place_bytes == (z0 + nz) * fb;
+        }
+        p.boxes.swap(boxes);
         p.ok = true;
         return p;
     }
-    // byte spans of the stream in front of lz4 that the range needs
-    std::vector<std::pair<uint64_t, uint64_t>> spans;
-    if (form == RangeForm::plain)
-        spans.push_back({p.v0 * e, p.v1 * e});
-    else {
-        // W = 8 * we plane segments of seg words (we bytes, W voxels each), then the n % W voxels behind them verbatim
-        const uint64_t W = 8 * we, seg = n / W;
-        p.L = seg * W;
-        p.w0 = std::min(p.v0 / W, seg);
-        p.w1 = std::min((p.v1 + W - 1) / W, seg);
-        if (p.w0 < p.w1) for (uint64_t s = 0; s < W; ++s) spans.push_back({(s * seg + p.w0) * we, (s * seg + p.w1) * we});
-        if (p.v1 > p.L) spans.push_back({std::max(p.v0, p.L) * we, p.v1 * we});
-    }
+    // byte spans of the stream in front of lz4 that each range needs (planes: the plane segments' words in their order, then the tail)
+    std::vector<std::vector<std::pair<uint64_t, uint64_t>>> spans(ranges.size());
     std::vector<char> need(nframes, 0);
-    for (const auto& sp : spans) for (uint64_t f = sp.first / chunk; f <= (sp.second - 1) / chunk; ++f) need[f] = 1;
+    for (size_t i = 0; i < ranges.size(); ++i) {
+        FrameRangesBox& b = boxes[i];
+        if (form == RangeForm::plain)
+            spans[i].push_back({b.v0 * e, b.v1 * e});
+        else {
+            // W = 8 * we plane segments of seg words (we bytes, W voxels each), then the n % W voxels behind them verbatim
+            const uint64_t W = 8 * we, seg = n / W;
+            b.L = seg * W;
+            b.w0 = std::min(b.v0 / W, seg);
+            b.w1 = std::min((b.v1 + W - 1) / W, seg);
+            if (b.w0 < b.w1) for (uint64_t s = 0; s < W; ++s) spans[i].push_back({(s * seg + b.w0) * we, (s * seg + b.w1) * we});
+            if (b.v1 > b.L) spans[i].push_back({std::max(b.v0, b.L) * we, b.v1 * we});
+        }
+        for (const auto& sp : spans[i]) for (uint64_t f = sp.first / chunk; f <= (sp.second - 1) / chunk; ++f) need[f] = 1;
+    }
     p.coff.assign(nframes, 0);
     for (uint32_t f = 0; f < nframes; ++f) {
         if (!need[f]) continue;
@@ -812,21 +835,57 @@ FrameRangePlan frame_range_plan(RangeForm form, uint64_t n, int elem, uint64_t s
         p.ids.push_back(f);
         p.out_bytes += std::min<uint64_t>(chunk, total - (uint64_t)f * chunk);
     }
+    // A span is contiguous in the stream and every frame that covers it is selected: it is contiguous in the compaction too, whatever
+    // frames of other ranges lie between two spans, and the address of its first byte is the address of all of it
     auto compact = [&](uint64_t b) { const uint64_t f = b / chunk; return p.coff[f] + (b - f * chunk); };
-    if (form == RangeForm::plain) p.range_at = compact(spans[0].first);
-    else {
-        // (the spans in their order: the plane segments' words, then the tail)
-        for (size_t s = 0; p.w0 < p.w1 && s < (size_t)(8 * we); ++s) p.plane[s] = compact(spans[s].first);
-        if (p.v1 > p.L) p.tail = compact(spans.back().first);
+    for (size_t i = 0; i < ranges.size(); ++i) {
+        FrameRangesBox& b = boxes[i];
+        if (form == RangeForm::plain) b.range_at = compact(spans[i][0].first);
+        else {
+            for (size_t s = 0; b.w0 < b.w1 && s < (size_t)(8 * we); ++s) b.plane[s] = compact(spans[i][s].first);
+            if (b.v1 > b.L) b.tail = compact(spans[i].back().first);
+        }
     }
+    p.boxes.swap(boxes);
     p.ok = true;
     return p;
+}
+
+FrameRangePlan frame_range_plan_of(const FrameRangesPlan& u, size_t box)
+{
+    FrameRangePlan p;
+    p.we = u.we;
+    if (!u.ok || box >= u.boxes.size()) return p;
+    const FrameRangesBox& b = u.boxes[box];
+    p.ok = true;
+    p.ids = u.ids; p.out_bytes = u.out_bytes; p.coff = u.coff; p.remap = u.remap; p.zero_runs = u.zero_runs;
+    p.range_at = b.range_at;
+    std::copy(b.plane, b.plane + 16, p.plane);
+    p.tail = b.tail; p.v0 = b.v0; p.v1 = b.v1; p.w0 = b.w0; p.w1 = b.w1; p.L = b.L;
+    p.pa = b.pa; p.pb = b.pb; p.direct = b.direct;
+    return p;
+}
+
+FrameRangePlan frame_range_plan(RangeForm form, uint64_t n, int elem, uint64_t shape0, uint64_t z0, uint64_t nz, uint64_t chunk, uint64_t total,
+                                uint32_t nframes, const std::vector<unsigned char>& struck_map, uint64_t place_bytes, uint64_t places)
+{
+    return frame_range_plan_of(frame_ranges_plan(form, n, elem, shape0, {{z0, nz}}, chunk, total, nframes, struck_map, place_bytes, places), 0);
 }
 
 BoxPath decode_box_path(bool subset_form, RangeForm form, bool option_on)
 {
     if (!subset_form || !option_on) return BoxPath::whole_copy;
     return form == RangeForm::planes || form == RangeForm::planes_lut ? BoxPath::subset_transposer : BoxPath::subset_copy;
+}
+
+BoxesPath decode_boxes_path(bool subset_form, RangeForm form, bool subset_option, bool joint_option)
+{
+    if (!joint_option) return BoxesPath::box_by_box;
+    switch (decode_box_path(subset_form, form, subset_option)) {
+    case BoxPath::subset_transposer: return BoxesPath::subset_transposer;
+    case BoxPath::subset_copy: return BoxesPath::subset_copy;
+    default: return BoxesPath::whole_copy;
+    }
 }
 
 // ---- stages ----

@@ -403,6 +403,30 @@ struct FrameRangePlan {
 };
 FrameRangePlan frame_range_plan(RangeForm form, uint64_t n, int elem, uint64_t shape0, uint64_t z0, uint64_t nz, uint64_t chunk, uint64_t total,
                                 uint32_t nframes, const std::vector<unsigned char>& struck_map = {}, uint64_t place_bytes = 0, uint64_t places = 0);
+// The same for a SET of ranges (z0, nz) of one blob (SQYAMD_Decode_Boxes_*): the LZ4 frames united -- each once, ascending -- and, per
+// range, where its bytes lie in the united frames' compaction.  A range's span of a plane segment (of the voxels, for plain) is
+// contiguous in the stream and all frames that cover it are selected, so it is contiguous in the compaction as well, whatever frames of
+// other ranges lie in between.  shuffle: the places of all ranges, compacted in ascending place order (a range's own places stay
+// consecutive); remap and zero_runs name compacted places.  frame_range_plan is the case of one range: frame_range_plan_of(plan, 0)
+struct FrameRangesBox {
+    uint64_t range_at = 0;                  // plain, shuffle: the range's first byte in the compaction
+    uint64_t plane[16] = {}, tail = 0, v0 = 0, v1 = 0, w0 = 0, w1 = 0, L = 0;      // planes: as FrameRangePlan's
+    uint64_t pa = 0, pb = 0;                // shuffle: the range's places
+    bool direct = false;                    // shuffle: the compaction IS the range
+};
+struct FrameRangesPlan {
+    bool ok = false;
+    std::vector<uint32_t> ids;
+    uint64_t out_bytes = 0;
+    std::vector<uint64_t> coff;
+    int we = 1;
+    std::vector<uint64_t> remap;
+    std::vector<std::pair<uint64_t, uint64_t>> zero_runs;
+    std::vector<FrameRangesBox> boxes;      // one per range, in the caller's order
+};
+FrameRangesPlan frame_ranges_plan(RangeForm form, uint64_t n, int elem, uint64_t shape0, const std::vector<std::pair<uint64_t, uint64_t>>& ranges, uint64_t chunk,
+                                  uint64_t total, uint32_t nframes, const std::vector<unsigned char>& struck_map = {}, uint64_t place_bytes = 0, uint64_t places = 0);
+FrameRangePlan frame_range_plan_of(const FrameRangesPlan& u, size_t box);
 
 // A box of one large blob (SQYAMD_Decode_Box_*): what runs for it.  subset_form: the blob is one the frame-range plan takes (the chunked
 // layout of a RangeForm pipeline with more than one LZ4 frame -- where DecodeCall::frames_subset says `taken`), then `form` is its form;
@@ -412,6 +436,13 @@ FrameRangePlan frame_range_plan(RangeForm form, uint64_t n, int elem, uint64_t s
 //   whole_copy         the whole blob decoded into the workspace, one window copy (every other blob; the option off)
 enum class BoxPath { subset_transposer, subset_copy, whole_copy };
 BoxPath decode_box_path(bool subset_form, RangeForm form, bool option_on);
+// Many boxes of one blob (SQYAMD_Decode_Boxes_*).  joint_option: decode_boxes_joint; the rest as for decode_box_path.
+//   box_by_box         the option off: everything admitted up front, then the single-box driver box by box
+//   subset_transposer  the LZ4 frames of all boxes' z-ranges united, then ONE launch of the job-table range transposer
+//   subset_copy        .. then ONE window copy with a job per box out of the compaction
+//   whole_copy         the whole blob decoded ONCE into the workspace, ONE window copy with a job per box
+enum class BoxesPath { box_by_box, subset_transposer, subset_copy, whole_copy };
+BoxesPath decode_boxes_path(bool subset_form, RangeForm form, bool subset_option, bool joint_option);
 
 struct Stage {
     std::string name;
