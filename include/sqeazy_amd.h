@@ -468,6 +468,33 @@ SQY_FUNCTION_PREFIX int SQYAMD_Update_BatchWindow_UI8_Device(const char* pipelin
                                                              int nblobs, const long* origins, const void* const* d_wins, const long* win_shapes,
                                                              const long* win_strides, unsigned shape_size, void* d_dst, long slot_capacity, long* offsets,
                                                              long* lengths, int nthreads, void* hip_stream);
+/* A box written into ONE large blob: old blob + a box's new voxels -> new blob.  Let V = what SQYAMD_Decode_*_Device gives for the old
+ * blob d_src[0, srclength), and V' = V with the box [origin, origin + view_shape) (`rank` longs each, outermost first) replaced by the
+ * voxels of the view at d_view / view_strides (strides in voxels, the view rules of _BatchStrided_*; NULL: dense; only the view's voxels
+ * are read).  The new blob, d_dst[0, *dstlength), decodes to V' under `pipeline`; whenever the old blob is what
+ * SQYAMD_PipelineEncode_*_Device(pipeline, V, nthreads) gives, the new blob is BYTE FOR BYTE what that call gives for V'.  A lossy old
+ * blob (quantiser) is re-quantised from its decoded voxels, as in SQYAMD_Update_BatchWindow_*.
+ * Admission, all before a byte is written; every refusal returns 1 with *dstlength = 0.  Before a device is looked for: NULL pointers,
+ * rank 0 or above 3, srclength <= 0, dst_capacity <= 0, a negative origin, a pipeline not admitted for the voxel type.  Then the view
+ * rules.  Then, against the header: the voxel type, the header's rank, origin + extent inside the shape (extents >= 1; a sum that
+ * overflows is beyond it), the single call's geometry refusals for the blob's shape under `pipeline`.  d_dst overlapping d_src or the view
+ * is the caller's error.
+ * Errors: a damaged LZ4 frame that is needed gives SQY_Decode's composite code with d_dst untouched.  A new blob that does not fit
+ * dst_capacity returns 1 with *dstlength set to the exact bytes a retry needs, and nothing at or behind d_dst + dst_capacity is
+ * written; SQY_Pipeline_Max_Compressed_Length_* of the shape is always enough.
+ * How: where `pipeline` equals the old blob's pipeline stage for stage, is `lz4` or `bitswap1->lz4`, and both are the
+ * chunked LZ4 layout with acceleration 1 and more than one chunk, only the LZ4 frames that the box's range [origin[0], origin[0] +
+ * view_shape[0]) needs are decoded, patched where they lie, compressed again and spliced between the old frames -- which are copied from
+ * the old blob VERBATIM, whoever wrote them: a damaged frame outside the range goes unnoticed and is carried over, as
+ * SQYAMD_Decode_Box_* leaves it unnoticed.  Every other blob is decoded whole into the library's workspace, the box pasted, and the
+ * volume encoded as by the single call -- same bytes wherever both apply ("update_box_subset" = 0: every blob).
+ * Stream, context, ordering and thread safety are SQYAMD_Decode_Box_*_Device's. */
+SQY_FUNCTION_PREFIX int SQYAMD_Update_Box_UI16_Device(const char* pipeline, const void* d_src, long srclength, const long* origin, const void* d_view,
+                                                      const long* view_shape, const long* view_strides, unsigned rank, void* d_dst, long dst_capacity,
+                                                      long* dstlength, int nthreads, void* hip_stream);
+SQY_FUNCTION_PREFIX int SQYAMD_Update_Box_UI8_Device(const char* pipeline, const void* d_src, long srclength, const long* origin, const void* d_view,
+                                                     const long* view_shape, const long* view_strides, unsigned rank, void* d_dst, long dst_capacity,
+                                                     long* dstlength, int nthreads, void* hip_stream);
 /* host-pointer variants: blobs in host memory at src + offsets[i], dsts[i] host pointers (any alignment); arguments and headers are checked
  * on the host before any device is looked for */
 SQY_FUNCTION_PREFIX int SQYAMD_Decode_Batch_UI16(const char* src, const long* offsets, const long* lengths, int nblobs,

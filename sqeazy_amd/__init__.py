@@ -33,7 +33,7 @@ EXPORTED_SYMBOLS = (
     "SQYAMD_PipelineEncode_BatchPacked_UI16", "SQYAMD_PipelineEncode_BatchPacked_UI8",
     "SQYAMD_Decode_BatchStrided_UI16_Device", "SQYAMD_Decode_BatchStrided_UI8_Device",
     "SQYAMD_Decode_BatchWindow_UI16_Device", "SQYAMD_Decode_BatchWindow_UI8_Device",
-    "SQYAMD_Update_BatchWindow_UI16_Device", "SQYAMD_Update_BatchWindow_UI8_Device",
+    "SQYAMD_Update_BatchWindow_UI16_Device", "SQYAMD_Update_BatchWindow_UI8_Device", "SQYAMD_Update_Box_UI16_Device", "SQYAMD_Update_Box_UI8_Device",
     "SQYAMD_Compare_BatchWindow_UI16_Device", "SQYAMD_Compare_BatchWindow_UI8_Device",
     "SQYAMD_PipelineEncode_UI16_Cap", "SQYAMD_PipelineEncode_UI8_Cap",
     "SQYAMD_Decode_UI16_Device", "SQYAMD_Decode_UI8_Device",
@@ -113,6 +113,9 @@ def lib():
         for f in ("SQYAMD_Update_BatchWindow_UI8_Device", "SQYAMD_Update_BatchWindow_UI16_Device"):
             getattr(L, f).argtypes = [ctypes.c_char_p, ctypes.c_void_p, c_long_p, c_long_p, ctypes.c_int, c_long_p, ctypes.POINTER(ctypes.c_void_p), c_long_p, c_long_p,
                                       ctypes.c_uint, ctypes.c_void_p, ctypes.c_long, c_long_p, c_long_p, ctypes.c_int, ctypes.c_void_p]
+        for f in ("SQYAMD_Update_Box_UI8_Device", "SQYAMD_Update_Box_UI16_Device"):
+            getattr(L, f).argtypes = [ctypes.c_char_p, ctypes.c_void_p, ctypes.c_long, c_long_p, ctypes.c_void_p, c_long_p, c_long_p, ctypes.c_uint, ctypes.c_void_p,
+                                      ctypes.c_long, c_long_p, ctypes.c_int, ctypes.c_void_p]
         for f in ("SQYAMD_PipelineEncode_Batch_UI8", "SQYAMD_PipelineEncode_Batch_UI16"):
             getattr(L, f).argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_void_p), c_long_p, ctypes.c_uint, ctypes.c_int, ctypes.c_void_p, ctypes.c_long,
                                       c_long_p, c_long_p, ctypes.c_int]
@@ -652,6 +655,20 @@ def update_batch_window_device(pipeline, d_src, offsets, lengths, origins, d_win
         _longs([x for s in strides for x in s]) if n and strides is not None else None, ctypes.c_uint(rank), ctypes.c_void_p(int(d_dst)),
         ctypes.c_long(int(slot_capacity)), offs, lens, ctypes.c_int(nthreads), ctypes.c_void_p(stream or 0))
     return rc, list(offs[:n]), list(lens[:n])
+
+
+def update_box_device(pipeline, d_src, srclength, origin, d_view, shape, strides, dtype, d_dst, dst_capacity, nthreads=0, stream=None):
+    """SQYAMD_Update_Box_*_Device on raw device pointers (ints): the old blob at d_src (srclength bytes) with the box of extent `shape` that
+    begins at voxel `origin` replaced by the view at d_view with that shape and `strides` in voxels (None: dense), encoded with `pipeline`
+    into d_dst (dst_capacity bytes) -- byte for byte the single call's blob of the pasted volume.  Returns (rc, dstlength); rc 1 with a
+    dstlength above 0: the bytes a retry needs."""
+    n = ctypes.c_long(0)
+    rc = getattr(lib(), "SQYAMD_Update_Box_%s_Device" % _suffix(dtype))(
+        None if pipeline is None else pipeline.encode(), ctypes.c_void_p(None if d_src is None else int(d_src)), ctypes.c_long(int(srclength)),
+        None if origin is None else _longs(origin), ctypes.c_void_p(None if d_view is None else int(d_view)), None if shape is None else _longs(shape),
+        None if strides is None else _longs(strides), ctypes.c_uint(len(shape) if shape is not None else len(origin or ())),
+        ctypes.c_void_p(None if d_dst is None else int(d_dst)), ctypes.c_long(int(dst_capacity)), ctypes.byref(n), ctypes.c_int(nthreads), ctypes.c_void_p(stream or 0))
+    return rc, n.value
 
 
 def box_windows(shape, tile, box_origin, box_extent, dst_ptr, dst_strides, itemsize):

@@ -80,6 +80,7 @@ struct Options {
     std::atomic<long> decode_frames_subset;             // frame-range decode: only the LZ4 frames the range needs, where the pipeline allows (0: full decode + copy)
     std::atomic<long> decode_box_subset;                // box decode: only the LZ4 frames the box's z-range needs, where the pipeline allows (0: full decode + window copy)
     std::atomic<long> decode_boxes_joint;               // many boxes of one blob: the frames united, one output launch for all boxes (0: the single-box driver box by box)
+    std::atomic<long> update_box_subset;                // box update of one blob: only the LZ4 frames the box's z-range needs are decoded, patched, parsed again and spliced between the old ones, where sqy::update_box_path allows (0: whole decode, one paste, the single call's encode)
     std::atomic<long> decode_slabs_joint;               // slab-set decode: the chunked LZ4 blobs of a group indexed and decoded by one launch each (0: blob by blob)
     std::atomic<long> decode_batch_joint;               // batch decode: the joint-eligible blobs of a group indexed, decoded and transposed back by one launch each (0: blob by blob)
     std::atomic<long> decode_batch_group_bytes;         // .. the LZ4 output one group holds at most (a group holds at least one blob)
@@ -105,6 +106,7 @@ struct Options {
           transpose_tiles_per_wave(env_number("SQY_TRANSPOSE_TILES_PER_WAVE", sqy::kBitswap1TilesPerWave, 1, 64)), stored_tail_index(env_flag("SQY_NO_STORED_TAIL_INDEX") ? 0 : 1),
           host_l2_bytes((long)sqy::host_l2_cache_bytes()), decode_frames_subset(env_flag("SQY_NO_DECODE_FRAMES_SUBSET") ? 0 : 1),
           decode_box_subset(env_flag("SQY_NO_DECODE_BOX_SUBSET") ? 0 : 1), decode_boxes_joint(env_flag("SQY_NO_DECODE_BOXES_JOINT") ? 0 : 1),
+          update_box_subset(env_flag("SQY_NO_UPDATE_BOX_SUBSET") ? 0 : 1),
           decode_slabs_joint(env_flag("SQY_NO_DECODE_SLABS_JOINT") ? 0 : 1), decode_batch_joint(env_flag("SQY_NO_DECODE_BATCH_JOINT") ? 0 : 1),
           decode_batch_group_bytes(env_number("SQY_DECODE_BATCH_GROUP_BYTES", (long)kSlabsGroupBytes, 1, (long)kSlabsGroupBytes)), encode_batch_joint(env_flag("SQY_NO_ENCODE_BATCH_JOINT") ? 0 : 1),
           encode_batch_group_bytes(env_number("SQY_ENCODE_BATCH_GROUP_BYTES", kBatchGroupBytesDefault, 1, kBatchBytesMax)),
@@ -129,6 +131,7 @@ struct Options {
         if (!std::strcmp(name, "decode_frames_subset")) return &decode_frames_subset;
         if (!std::strcmp(name, "decode_box_subset")) return &decode_box_subset;
         if (!std::strcmp(name, "decode_boxes_joint")) return &decode_boxes_joint;
+        if (!std::strcmp(name, "update_box_subset")) return &update_box_subset;
         if (!std::strcmp(name, "decode_slabs_joint")) return &decode_slabs_joint;
         if (!std::strcmp(name, "decode_batch_joint")) return &decode_batch_joint;
         if (!std::strcmp(name, "decode_batch_group_bytes")) return &decode_batch_group_bytes;
@@ -341,6 +344,7 @@ struct Workspace {
     DevBuf subset;            // frame-range decode: the frame list, the subset's block index, the frame_shuffle map of the range
     DevBuf range_full;        // frame-range decode of a blob the subset path does not take: the whole volume, the range copied out
     DevBuf box_window;        // box decode: the job and tile table of the window copy (one job)
+    DevBuf update_box;        // box update, the whole path: the single call's new blob before it is held against the caller's capacity and copied out
     DevBuf boxes_jobs;        // decode of many boxes of one blob: the job and tile table of its one output launch
     DevBuf slabs_index;       // slab-set decode: every blob's frame ranking (scratch, block index, counts) of a group
     DevBuf slabs_joint;       // .. the group's joint block index, frame output table, part descriptors and frame_shuffle maps
@@ -366,7 +370,7 @@ struct Workspace {
     {
         ping.release(); pong.release(); lz4_scratch.release(); csize.release(); frame_off.release();
         io_src.release(); io_dst.release(); small.release(); plan.release(); dedupe.release(); diff_side.release(); spec.release(); digest.release(); bkrd.release();
-        subset.release(); range_full.release(); box_window.release(); boxes_jobs.release(); slabs_index.release(); slabs_joint.release(); slabs_out.release(); slabs_host.release();
+        subset.release(); range_full.release(); box_window.release(); update_box.release(); boxes_jobs.release(); slabs_index.release(); slabs_joint.release(); slabs_out.release(); slabs_host.release();
         batch_stream.release(); batch_scratch.release(); batch_tables.release(); batch_quant.release(); batch_host.release();
         batch_pack.release(); batch_pack_one.release(); for (DevBuf& b : batch_views) b.release(); for (DevBuf& b : batch_windows) b.release();
         for (DevBuf& b : batch_compares) b.release();
@@ -2194,6 +2198,7 @@ struct DecodeCall {
     // the same for a set of ranges (z0, nz) (SQYAMD_Decode_Boxes_*): one table upload, one LZ4 launch over the united frames into one
     // buffer; ranges_plan says where each range lies in there.  direct_ok: one range only
     sqy::FrameRangesPlan ranges_plan;
+    Lz4Index range_ix;                      // the frame index the subset was taken from (valid where *taken)
     int frames_subset(const std::vector<std::pair<uint64_t, uint64_t>>& ranges, bool direct_ok, bool* taken)
     {
         *taken = false;
@@ -2244,6 +2249,7 @@ struct DecodeCall {
         if (o_blk) SQY_HIP(hipMemcpyAsync(d_sub, sub_host.data(), o_blk, hipMemcpyHostToDevice, stream));
 
         *taken = true;
+        range_ix = ix;
         // shuffle with the range on place boundaries (frame_chunk_size 1): straight into d_dst; else through the workspace
         uint8_t* sbuf = direct ? static_cast<uint8_t*>(d_dst) : work_buf(p.out_bytes);       // where the subset decodes to
         if (!sbuf) return 1;
@@ -4298,6 +4304,278 @@ int update_batch_window_device(const char* pipeline, const void* d_src, const lo
                                   (uint64_t)slot_capacity, offsets, lengths, nthreads, static_cast<hipStream_t>(hip_stream));
 }
 
+// ---- a box written into one large blob (SQYAMD_Update_Box_*) --------------------------------------------------------------------
+// New blob = the single call's blob for (old blob decoded, the box's voxels replaced by the view's).  sqy::update_box_path says what runs.
+// subset_patch: the LZ4 frames the box's z-range needs are decoded into the workspace (DecodeCall::frames_subset, as for
+// SQYAMD_Decode_Box_*), the box is patched into that compaction where it lies, its chunks are parsed again by the batch encode's parse,
+// and two launches splice the new frames between the old ones, which are copied from the old blob as they stand.  whole: the blob decoded
+// into Workspace::range_full, one paste launch, the single call's encode.  Nothing is written to d_dst before the old frames that are
+// needed have been decoded and found sound.
+struct UpdateBoxCall {
+    Context& cx;
+    hipStream_t stream;
+    const char* pipeline_text;
+    const Pipeline& pipe;                    // `pipeline`, parsed, its thread count set
+    const uint8_t* d_src;
+    uint64_t srclen;
+    const sqy::HeaderInfo& h;
+    uint64_t raw_bytes;
+    const sqy::BatchWindow& w;
+    const WindowView& v;
+    uint64_t z0, nz;                         // the box's range along the header's first dimension
+    unsigned rank;
+    const void* d_view;
+    int elem;
+    void* d_dst;
+    uint64_t capacity;
+    long* dstlength;
+    int nthreads;
+};
+
+// the tables of the subset path's parse and splice in Workspace::batch_tables, 16-byte aligned each.  What the host writes: table_at: an
+// Lz4BatchChunk per selected chunk | slot_at: a word per frame of the blob | text_at: the header's prefix and suffix -- `upload` bytes.
+// Behind them what the kernels hand each other: csize_at, redo_at (nsel + 1 words), foff_at (nframes + 1 offsets), info_at (2 words)
+struct SpliceTables {
+    uint64_t table_at = 0, slot_at = 0, text_at = 0, upload = 0, csize_at = 0, redo_at = 0, foff_at = 0, info_at = 0, total = 0;
+    std::vector<unsigned char> host;
+    hipStream_t queued_on = nullptr;
+    bool queued = false;
+    SpliceTables(uint64_t nsel, uint64_t nframes, uint64_t text_bytes)
+    {
+        auto up = [](uint64_t x) { return (x + 15) & ~(uint64_t)15; };
+        slot_at = up(nsel * sizeof(sqy::Lz4BatchChunk));
+        text_at = slot_at + up(nframes * 4);
+        upload = csize_at = text_at + up(text_bytes);
+        redo_at = csize_at + up(nsel * 4);
+        foff_at = redo_at + up((nsel + 1) * 4);
+        info_at = foff_at + up((nframes + 1) * 8);
+        total = info_at + 16;
+        host.assign(upload, 0);
+    }
+    SpliceTables(const SpliceTables&) = delete;
+    SpliceTables& operator=(const SpliceTables&) = delete;
+    ~SpliceTables() { if (queued) (void)hipStreamSynchronize(queued_on); }
+};
+
+// subset path, stage 2: the box into the compaction at c.range_buf, in place
+int update_box_patch(DecodeCall& c, const UpdateBoxCall& u, WindowLaunch& l)
+{
+    hipStream_t stream = c.stream;
+    std::vector<PendingEvent>* pend = c.pend;
+    const sqy::FrameRangePlan& p = c.range_plan;
+    if (c.range_form == sqy::RangeForm::planes) {
+        sqy::Bitswap1Range r;
+        const uint16_t* lut = nullptr;
+        if (c.range_planes(&r, &lut)) return 1;
+        const sqy::BatchWindowJob box{const_cast<void*>(u.d_view), nullptr, u.w.Z, u.w.Y, u.w.X, u.v.sz, u.v.sy, u.w.bZ, u.w.bY, u.w.bX, u.w.oz, u.w.oy, u.w.ox, 0};
+        if (!sqy::bitswap1_range_patch_ok(r, box, p.we)) { std::fprintf(stderr, "[sqeazy]\t internal error: the frame range does not hold the box\n"); return 1; }
+        SQY_TIMED("bitswap1_range_patch", sqy::launch_bitswap1_range_patch(c.range_buf, r, box, p.we, stream));
+        return 0;
+    }
+    // plain: the range in the workspace is a blob of the box's frames, the box begins at its first one (box_range_out's rule)
+    sqy::BatchWindow in_range = u.w;
+    if (u.rank == 3) { in_range.bZ = u.w.Z; in_range.oz = 0; }
+    else if (u.rank == 2) { in_range.bY = u.w.Y; in_range.oy = 0; }
+    else { in_range.bX = u.w.X; in_range.ox = 0; }
+    l.add(u.d_view, c.range_buf + p.range_at, in_range, u.v, false);
+    const uint32_t* d_tiles = nullptr;
+    if (l.upload(stream, c.cx.ws.box_window, &d_tiles)) return 1;
+    SQY_TIMED("box_window_paste", sqy::launch_batch_window_paste(static_cast<const sqy::BatchWindowJob*>(c.cx.ws.box_window.p), d_tiles, 1, l.ntiles, u.elem, stream));
+    return 0;
+}
+
+// subset path, stage 3: the selected chunks parsed again (the batch encode's parse over a table of them); the host round trip between
+// its two passes brings the LZ4 decoder's verdict on the old frames with it -- a damaged one ends the call here, d_dst untouched
+int update_box_parse(DecodeCall& c, SpliceTables& T, uint64_t chunk, uint64_t stride)
+{
+    hipStream_t stream = c.stream;
+    std::vector<PendingEvent>* pend = c.pend;
+    Workspace* ws = c.ws;
+    const sqy::FrameRangePlan& p = c.range_plan;
+    const uint32_t nsel = (uint32_t)p.ids.size();
+    const uint64_t total = c.in_bytes(c.pipe.stages.size() - 1);
+    sqy::Lz4BatchChunk* h_table = reinterpret_cast<sqy::Lz4BatchChunk*>(T.host.data() + T.table_at);
+    for (uint32_t k = 0; k < nsel; ++k) {
+        const uint64_t f = p.ids[k];
+        h_table[k] = sqy::Lz4BatchChunk{p.coff[f], (uint32_t)std::min<uint64_t>(chunk, total - f * chunk), 0, k, 0};
+    }
+    if (ws->batch_tables.ensure(T.total) || ws->batch_scratch.ensure(std::max<uint64_t>((uint64_t)nsel * stride, 16))) return 1;
+    uint8_t* d_tab = static_cast<uint8_t*>(ws->batch_tables.p);
+    T.queued_on = stream;
+    T.queued = true;
+    SQY_HIP(hipMemcpyAsync(d_tab, T.host.data(), T.upload, hipMemcpyHostToDevice, stream));
+    const sqy::Lz4BatchChunk* d_table = reinterpret_cast<const sqy::Lz4BatchChunk*>(d_tab + T.table_at);
+    uint32_t* d_csize = reinterpret_cast<uint32_t*>(d_tab + T.csize_at);
+    uint32_t* d_redo = reinterpret_cast<uint32_t*>(d_tab + T.redo_at);
+    uint8_t* d_scratch = static_cast<uint8_t*>(ws->batch_scratch.p);
+    SQY_TIMED("lz4_chunks_table", sqy::launch_lz4_chunks_table(c.range_buf, d_table, nsel, d_scratch, stride, d_csize, d_redo, stream));
+    uint32_t* h_redo = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(ws->pinned) + 16);
+    SQY_HIP(hipMemcpyAsync(h_redo, d_redo, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    if (const int rc = c.finish()) return rc;                           // (synchronises; the verdict)
+    const uint32_t n_redo = *h_redo;
+    if (n_redo) SQY_TIMED("lz4_chunks_table_dense", sqy::launch_lz4_chunks_table_dense(c.range_buf, d_table, d_scratch, stride, d_csize, d_redo, n_redo, stream));
+    return 0;
+}
+
+// subset path, stages 4 and 5: the splice into d_dst, and the one read-back of its record
+int update_box_splice(DecodeCall& c, const UpdateBoxCall& u, const SpliceTables& T, const sqy::Lz4SpliceJob& job, uint64_t stride)
+{
+    hipStream_t stream = c.stream;
+    std::vector<PendingEvent>* pend = c.pend;
+    Workspace* ws = c.ws;
+    uint8_t* d_tab = static_cast<uint8_t*>(ws->batch_tables.p);
+    uint64_t* d_foff = reinterpret_cast<uint64_t*>(d_tab + T.foff_at);
+    uint64_t* d_info = reinterpret_cast<uint64_t*>(d_tab + T.info_at);
+    volatile uint64_t* record = reinterpret_cast<volatile uint64_t*>(static_cast<uint8_t*>(ws->pinned) + 64);
+    record[0] = 0; record[1] = 0; record[2] = 0;
+    const Lz4Descriptor fd = lz4_descriptor(u.pipe.stages.back().lz4.block_id);
+    SQY_TIMED("lz4_splice_scan", sqy::launch_lz4_splice_scan(job, u.capacity, d_foff, d_info, stream));
+    SQY_TIMED("lz4_splice_gather", sqy::launch_lz4_splice_gather(job, c.cur, c.range_buf, static_cast<const uint8_t*>(ws->batch_scratch.p), stride, d_foff, d_info,
+                                                                 reinterpret_cast<const char*>(d_tab + T.text_at), static_cast<uint8_t*>(u.d_dst), fd.bd, fd.hc,
+                                                                 const_cast<uint64_t*>(record), stream));
+    SQY_HIP(hipStreamSynchronize(stream));
+    if (g_prof_on.load()) prof_collect(*pend);
+    if (record[0] == sqy::kSpliceDone) { *u.dstlength = (long)record[1]; return 0; }
+    if (record[0] == sqy::kSpliceNoRoom) {
+        std::fprintf(stderr, "[sqeazy]\t update box: destination buffer too small (%llu > %llu bytes)\n", (unsigned long long)record[1], (unsigned long long)u.capacity);
+        *u.dstlength = (long)record[1];
+    } else if (record[0] == sqy::kSplicePayloadTooLong)
+        std::fprintf(stderr, "[sqeazy]\t lz4: %llu payload bytes overflow the reference's int byte count\n", (unsigned long long)record[2]);
+    else
+        std::fprintf(stderr, "[sqeazy]\t update box: the old blob's frame index does not fit its payload (status %llu)\n", (unsigned long long)record[0]);
+    return 1;
+}
+
+// every other blob: whole decode, one paste, the single call's encode -- into the workspace first, so that a blob that does not fit leaves
+// d_dst untouched and its exact length known
+int update_box_whole(const UpdateBoxCall& u)
+{
+    Context& cx = u.cx;
+    hipStream_t stream = u.stream;
+    if (cx.ws.range_full.ensure(std::max<uint64_t>(u.raw_bytes, 16))) return 1;
+    if (const int rc = decode_on_device(cx, u.d_src, u.srclen, cx.ws.range_full.p, u.raw_bytes, u.elem, stream)) return rc;
+    {
+        DrainOnExit drain{stream, &cx.pending, cx.side};
+        WindowLaunch paste;
+        paste.add(u.d_view, cx.ws.range_full.p, u.w, u.v, false);
+        if (launch_windows(cx, stream, paste, WindowLaunch::paste, u.elem)) return 1;
+        paste.wait();
+    }
+    Pipeline fresh = Pipeline::from_string(u.pipeline_text, u.elem);
+    const uint64_t bound = std::max(fresh.max_encoded_size(u.raw_bytes, u.elem), u.pipe.max_encoded_size(u.raw_bytes, u.elem));
+    if (cx.ws.update_box.ensure(std::max<uint64_t>(bound, 16))) return 1;
+    std::vector<long> shape(u.h.shape.begin(), u.h.shape.end());
+    long len = 0, at = 0;
+    if (const int rc = encode_on_device(cx, u.pipeline_text, cx.ws.range_full.p, shape.data(), u.rank, u.elem, cx.ws.update_box.p, bound, &len, u.nthreads, stream, &at)) return rc;
+    if ((uint64_t)len > u.capacity) {
+        std::fprintf(stderr, "[sqeazy]\t update box: destination buffer too small (%ld > %llu bytes)\n", len, (unsigned long long)u.capacity);
+        *u.dstlength = len;
+        return 1;
+    }
+    SQY_HIP(hipMemcpyAsync(u.d_dst, static_cast<const uint8_t*>(cx.ws.update_box.p) + at, (size_t)len, hipMemcpyDeviceToDevice, stream));
+    SQY_HIP(hipStreamSynchronize(stream));
+    *u.dstlength = len;
+    return 0;
+}
+
+// the subset path where sqy::update_box_path allows it; *taken = false: nothing was written, the caller takes the whole path
+int update_box_subset(const UpdateBoxCall& u, bool* taken)
+{
+    *taken = false;
+    Context& cx = u.cx;
+    hipStream_t stream = u.stream;
+    const uint64_t n = u.raw_bytes / (uint64_t)u.elem;
+    sqy::UpdateBoxFacts facts;
+    facts.option_on = g_opt.update_box_subset.load() != 0;
+    Pipeline held = Pipeline::from_string(u.h.pipename, u.elem);
+    facts.same_stages = sqy::pipelines_same_stages(u.pipe, held);
+    facts.form_ok = sqy::update_box_form_ok(u.pipe);
+    if (!facts.option_on || !facts.same_stages || !facts.form_ok) return 0;
+    facts.layout = sqy::lz4_encode_layout(u.pipe.stages.back().lz4, u.raw_bytes, u.pipe.nthreads);
+    // (before the old blob is touched: what its index must show for the path to hold)
+    facts.subset_taken = true; facts.frames = facts.blocks = facts.layout.nchunks; facts.frame_chunk = facts.layout.chunk;
+    if (sqy::update_box_path(facts) != sqy::UpdateBoxPath::subset_patch) return 0;
+
+    DrainOnExit drain{stream, &cx.pending, cx.side};
+    WindowLaunch l;                                                     // (waits for the stream before its tables go)
+    DecodeCall c(cx, stream, nullptr, u.h, std::move(held), n, u.d_src + u.h.size);
+    // 1. the frame index and the frames of the box's z-range, each a whole chunk of the compaction
+    bool subset = false;
+    if (const int rc = c.frames_subset(u.z0, u.nz, false, &subset)) return rc;
+    facts.subset_taken = subset && (c.range_form == sqy::RangeForm::plain || c.range_form == sqy::RangeForm::planes);
+    facts.frames = c.range_ix.hc[0]; facts.blocks = c.range_ix.hc[1]; facts.frame_chunk = c.range_ix.chunk;
+    if (sqy::update_box_path(facts) != sqy::UpdateBoxPath::subset_patch) return 0;      // (a subset decode already launched is drained; the whole path decides)
+    const sqy::FrameRangePlan& p = c.range_plan;
+    const uint64_t chunk = facts.layout.chunk, nframes = facts.frames, nsel = p.ids.size();
+    const uint64_t stride = (chunk + 15) & ~(uint64_t)15;
+    std::string prefix, suffix;
+    sqy::header_pack_parts(u.elem, false, u.h.shape, u.pipe.name(), &prefix, &suffix);
+    SpliceTables T(nsel, nframes, prefix.size() + suffix.size());
+    std::vector<uint32_t> slot_of(nframes, sqy::kSpliceOldFrame);
+    for (uint64_t k = 0; k < nsel; ++k) slot_of[p.ids[k]] = (uint32_t)k;
+    if (nsel == 0 || chunk > 0x7fffffffull || !sqy::lz4_splice_ok(slot_of, nsel)) { std::fprintf(stderr, "[sqeazy]\t internal error: update box: no frame table\n"); return 1; }
+    std::memcpy(T.host.data() + T.slot_at, slot_of.data(), nframes * 4);
+    std::memcpy(T.host.data() + T.text_at, prefix.data(), prefix.size());
+    std::memcpy(T.host.data() + T.text_at + prefix.size(), suffix.data(), suffix.size());
+    *taken = true;
+    // 2. the box into the compaction
+    if (const int rc = update_box_patch(c, u, l)) return rc;
+    // 3. the selected chunks parsed again; the old frames' verdict
+    if (const int rc = update_box_parse(c, T, chunk, stride)) return rc;
+    // 4., 5. the splice and its record
+    const uint8_t* d_tab = static_cast<const uint8_t*>(cx.ws.batch_tables.p);
+    const sqy::Lz4SpliceJob job{c.range_ix.blk, reinterpret_cast<const uint32_t*>(d_tab + T.slot_at), reinterpret_cast<const sqy::Lz4BatchChunk*>(d_tab + T.table_at),
+                                reinterpret_cast<const uint32_t*>(d_tab + T.csize_at), c.cur_bytes, (uint32_t)nframes,
+                                (uint32_t)(std::max<uint64_t>(chunk, c.range_ix.block_bytes) + sqy::kLz4FrameGap), (uint32_t)prefix.size(), (uint32_t)suffix.size(),
+                                (uint32_t)u.elem};
+    if (!sqy::lz4_splice_job_ok(job)) { std::fprintf(stderr, "[sqeazy]\t update box: more frames than one launch takes\n"); return 1; }
+    return update_box_splice(c, u, T, job, stride);
+}
+
+// what needs no header, before a device is looked for; the view rules; then, against the header: the voxel type, the rank and the box,
+// the single call's refusals for the blob's shape under `pipeline` -- all before a byte is written
+int update_box_device(const char* pipeline, const void* d_src, long srclength, const long* origin, const void* d_view, const long* view_shape, const long* view_strides,
+                      unsigned rank, int elem_size, void* d_dst, long dst_capacity, long* dstlength, int nthreads, void* hip_stream)
+{
+    if (!dstlength) return 1;
+    *dstlength = 0;
+    if (!pipeline || !box_arguments_ok(d_src, srclength, origin, d_dst, view_shape, rank) || !d_view || dst_capacity <= 0) {
+        std::fprintf(stderr, "[sqeazy]\t update box: bad arguments\n");
+        return 1;
+    }
+    Pipeline pipe;
+    if (admit_pipeline(pipeline, elem_size, nthreads, &pipe)) return 1;
+    std::vector<sqy::BatchView> views;
+    const void* const ptrs[1] = {d_view};
+    if (admit_views("update box", ptrs, view_shape, view_strides, rank, 1, elem_size, &views)) return 1;
+    ContextLease lease;
+    if (!lease.ctx) { std::fprintf(stderr, "[sqeazy]\t no usable HIP device\n"); return 1; }
+    Context& cx = *lease.ctx;
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    const uint8_t* src = static_cast<const uint8_t*>(d_src);
+    sqy::HeaderInfo h;
+    uint64_t raw_bytes = 0;
+    sqy::BatchWindow w;
+    {
+        DrainOnExit drain{stream, &cx.pending, cx.side};
+        if (fetch_header(src, (uint64_t)srclength, stream, h)) return 1;
+        if (!admit_blob(h, (uint64_t)srclength, elem_size, &raw_bytes)) return 1;
+        if (!sqy::admit_window(h.shape, origin, view_shape, rank, &w)) {
+            std::fprintf(stderr, "[sqeazy]\t update box: the box does not lie inside the blob's shape, or has another rank\n");
+            return 1;
+        }
+        std::vector<long> shape(h.shape.begin(), h.shape.end());
+        std::vector<uint64_t> dims;
+        uint64_t len = 0;
+        if (admit_shape(&pipe, shape.data(), rank, &dims, &len)) return 1;
+    }
+    const WindowView v = window_view(w, view_strides, rank);
+    const UpdateBoxCall u{cx, stream, pipeline, pipe, src, (uint64_t)srclength, h, raw_bytes, w, v, (uint64_t)origin[0], (uint64_t)view_shape[0], rank, d_view, elem_size, d_dst, (uint64_t)dst_capacity, dstlength, nthreads};
+    bool taken = false;
+    if (const int rc = update_box_subset(u, &taken)) return rc;
+    return taken ? 0 : update_box_whole(u);
+}
+
 // the host-pointer variant (not tuned): every volume staged up, one call of the device driver, the blobs brought back
 int encode_batch_from_host(const char* pipeline, const char* const* srcs, const long* shapes, unsigned rank, int elem_size, int nvolumes, char* dst,
                            long slot_capacity, long* offsets, long* lengths, int nthreads)
@@ -5022,6 +5300,22 @@ int SQYAMD_Update_BatchWindow_UI8_Device(const char* pipeline, const void* d_src
     return guarded([&]() -> int {
         return update_batch_window_device(pipeline, d_src, src_offsets, src_lengths, nblobs, origins, d_wins, win_shapes, win_strides, shape_size, 1, d_dst, slot_capacity,
                                           offsets, lengths, nthreads, hip_stream);
+    });
+}
+
+int SQYAMD_Update_Box_UI16_Device(const char* pipeline, const void* d_src, long srclength, const long* origin, const void* d_view, const long* view_shape,
+                                  const long* view_strides, unsigned rank, void* d_dst, long dst_capacity, long* dstlength, int nthreads, void* hip_stream)
+{
+    return guarded([&]() -> int {
+        return update_box_device(pipeline, d_src, srclength, origin, d_view, view_shape, view_strides, rank, 2, d_dst, dst_capacity, dstlength, nthreads, hip_stream);
+    });
+}
+
+int SQYAMD_Update_Box_UI8_Device(const char* pipeline, const void* d_src, long srclength, const long* origin, const void* d_view, const long* view_shape,
+                                 const long* view_strides, unsigned rank, void* d_dst, long dst_capacity, long* dstlength, int nthreads, void* hip_stream)
+{
+    return guarded([&]() -> int {
+        return update_box_device(pipeline, d_src, srclength, origin, d_view, view_shape, view_strides, rank, 1, d_dst, dst_capacity, dstlength, nthreads, hip_stream);
     });
 }
 

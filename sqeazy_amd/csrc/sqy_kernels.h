@@ -263,6 +263,31 @@ hipError_t launch_lz4_batch_gather(const uint8_t* in, const Lz4BatchChunk* d_tab
 hipError_t launch_lz4_batch_place(uint64_t* vinfo, const uint64_t* d_gap, uint32_t nvols, uint64_t align, uint64_t base, uint64_t capacity, uint64_t* d_place,
                                   hipStream_t stream);
 
+// ---- the splice of old LZ4 frames and new ones into one blob (SQYAMD_Update_Box_*) ----
+// The new blob has the old blob's nframes single-block frames.  Frame f is carried over from the old payload `src` (slot_of[f] =
+// sqy::kSpliceOldFrame; blk: the old payload's frame index, launch_lz4_frame_rank's, one block per frame) or replaced by entry k =
+// slot_of[f] of the chunk table that launch_lz4_chunks_table parsed (csize[k], its scratch slot, or the chunk's own bytes at in + off where
+// it is stored).  src_payload: the old payload's bytes; max_frame: the longest frame the gather copies (chunk or block bytes +
+// kLz4FrameGap; a longer old frame is kSpliceBadIndex); the header is text[0, prefix_len) | payload bytes in decimal | text[prefix_len,
+// + suffix_len), padded in front to a multiple of elem_size.  All arithmetic: sqy_pipeline.hpp's lz4_splice_* functions.
+struct Lz4SpliceJob {
+    const void* blk;
+    const uint32_t* slot_of;
+    const Lz4BatchChunk* table;
+    const uint32_t* csize;
+    uint64_t src_payload;
+    uint32_t nframes, max_frame, prefix_len, suffix_len, elem_size;
+};
+bool lz4_splice_job_ok(const Lz4SpliceJob& j);
+// scan (one workgroup): frame_off[f] = where frame f begins behind the header (nframes + 1 entries), info[0] = payload bytes, info[1] =
+// header bytes | status << 32 (sqy::kSpliceDone .. kSpliceBadIndex; kSpliceNoRoom: header + payload > capacity)
+hipError_t launch_lz4_splice_scan(const Lz4SpliceJob& j, uint64_t capacity, uint64_t* frame_off, uint64_t* info, hipStream_t stream);
+// gather: the header and every frame at out (any byte address; `src` too -- sixteen-byte stores from out's grid on, bytes in front and
+// behind), and the record (3 words of pinned host memory: status, blob bytes -- for kSpliceNoRoom what a retry needs --, payload bytes).
+// Nothing but the record is written unless the status is kSpliceDone; then exactly the blob's bytes are.
+hipError_t launch_lz4_splice_gather(const Lz4SpliceJob& j, const uint8_t* src, const uint8_t* in, const uint8_t* scratch, uint64_t stride, const uint64_t* frame_off,
+                                    const uint64_t* info, const char* d_text, uint8_t* out, uint32_t bd_byte, uint32_t hc_byte, uint64_t* record, hipStream_t stream);
+
 // quantiser: 65536-bin histogram of u16 voxels (histo is zeroed by the launcher), and out[i] = lut[in[i]]
 // background removal, 1- or 2-byte voxels of a {Z, Y, X} volume
 // rmestbkrd (encoders/remove_estimated_background_scheme_impl.hpp:71-110): four face histograms (frames z = 0 and Z-1: their first
@@ -404,6 +429,13 @@ struct Bitswap1BoxJob {
 bool bitswap1_box_job_ok(const Bitswap1BoxJob& j);
 hipError_t launch_bitswap1_decode_range_windows(const uint8_t* in, const Bitswap1BoxJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ngroups,
                                                 int elem_size, const uint16_t* lut, hipStream_t stream);
+// ---- a box written into one large blob (SQYAMD_Update_Box_*) ----
+// launch_bitswap1_decode_range_window the other way round, in place: the box's voxels are read from the view (box.view; `dense` and tile0
+// are not read) and merged into the plane words [w0, w1) and the tail of the range r inside the compaction at buf (launch_bitswap1_batch_patch's
+// mask and merge).  The range must hold the box (bitswap1_range_patch_ok; refused otherwise).  A thread touches only the words of its own
+// 128-voxel run, and only where the box has a voxel in them; nothing else of buf and nothing of the view is written.
+bool bitswap1_range_patch_ok(const Bitswap1Range& r, const BatchWindowJob& box, int elem_size);
+hipError_t launch_bitswap1_range_patch(uint8_t* buf, const Bitswap1Range& r, const BatchWindowJob& box, int elem_size, hipStream_t stream);
 // ---- batch decode (SQYAMD_Decode_Batch_*): the blobs of a group share one launch of every kernel ----
 // The inverse of launch_bitswap1_batch on the same tables: job j's planes + tail at `in` (16-byte aligned) become its `len` voxels at
 // `out` (any voxel-aligned address; sixteen-byte stores where it and the plane size allow, word by word where not).  first_tile: njobs + 1

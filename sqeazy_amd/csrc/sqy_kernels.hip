@@ -3009,6 +3009,154 @@ void lz4_batch_gather_packed_kernel(const uint8_t* __restrict__ in, const Lz4Bat
 }
 
 // ------------------------------------------------------------------------------------------------
+// The splice of old LZ4 frames and new ones into one blob (SQYAMD_Update_Box_*): lz4_batch_scan_kernel and lz4_batch_gather_kernel for ONE
+// volume whose frames are either parsed again (slot_of[f] = its entry k of the chunk table: csize[k], table[k]) or carried over from the
+// old payload `src` as the frame index blk names them.  All sizes by sqy_pipeline.hpp's lz4_splice_* functions.
+// ------------------------------------------------------------------------------------------------
+// ONE workgroup: frame_off[f] = where frame f begins behind the header (nframes + 1 entries), info[0] = payload bytes, info[1] = header
+// bytes | status << 32 (kSpliceDone, kSpliceNoRoom, kSplicePayloadTooLong, kSpliceBadIndex: an old frame outside the old payload)
+__global__ __launch_bounds__(256)
+void lz4_splice_scan_kernel(const uint4* __restrict__ blk, const uint32_t* __restrict__ slot_of, uint32_t nframes, const Lz4BatchChunk* __restrict__ table,
+                            const uint32_t* __restrict__ csize, uint64_t src_payload, uint32_t max_frame, uint32_t prefix_len, uint32_t suffix_len,
+                            uint32_t elem_size, uint64_t capacity, uint64_t* __restrict__ frame_off, uint64_t* __restrict__ info)
+{
+    __shared__ uint64_t wsum[4];
+    __shared__ uint64_t carry_s;
+    __shared__ uint32_t bad_s;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    if (tid == 0) { carry_s = 0; bad_s = 0; }
+    __syncthreads();
+    for (uint32_t base = 0; base < nframes; base += 256u) {
+        const uint32_t f = base + tid;
+        uint64_t sz = 0;
+        if (f < nframes) {
+            const uint32_t k = slot_of[f];
+            if (k == kSpliceOldFrame) {
+                const uint4 b = blk[f];
+                const uint64_t off = (uint64_t)b.x | ((uint64_t)b.y << 32);
+                sz = lz4_splice_old_frame_bytes(b.z);
+                if (!lz4_splice_old_frame_ok(off, b.z, src_payload) || sz > max_frame) atomicOr(&bad_s, 1u);      // (max_frame: what the gather's slices cover)
+            } else
+                sz = lz4_splice_new_frame_bytes(csize[k], table[k].n);
+        }
+        uint64_t x = sz;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint64_t y = __shfl_up(x, d);
+            if (lane >= (uint32_t)d) x += y;
+        }
+        if (lane == 63u) wsum[wave] = x;
+        __syncthreads();
+        uint64_t woff = 0;
+        for (uint32_t w = 0; w < wave; ++w) woff += wsum[w];
+        const uint64_t carry = carry_s;
+        if (f < nframes) frame_off[f] = carry + woff + x - sz;
+        __syncthreads();
+        if (tid == 255u) carry_s = carry + woff + x;
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const uint64_t payload = carry_s;
+        const uint64_t hdr_len = lz4_splice_header_bytes(prefix_len, suffix_len, payload, elem_size);
+        const uint64_t status = bad_s ? kSpliceBadIndex : lz4_splice_status(hdr_len, payload, capacity);
+        frame_off[nframes] = payload;
+        info[0] = payload;
+        info[1] = hdr_len | (status << 32);
+    }
+}
+
+// n bytes from s to d, both at any byte address: bytes up to d's 16-byte boundary, 16-byte stores from there (the loads as s lies), the
+// bytes left over; the whole workgroup
+__device__ __forceinline__ void splice_copy(uint8_t* __restrict__ dd, const uint8_t* __restrict__ ss, uint32_t len, uint32_t tid)
+{
+    const uint32_t head0 = (uint32_t)((16 - (reinterpret_cast<uintptr_t>(dd) & 15)) & 15);
+    const uint32_t head = head0 < len ? head0 : len;
+    if (tid < head) dd[tid] = ss[tid];
+    dd += head; ss += head; len -= head;
+    const uint32_t nvec = len >> 4;
+    for (uint32_t i0 = tid; i0 < nvec; i0 += 1024) {
+        uint4 q[4];
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j) if (i0 + j * 256u < nvec) q[j] = ld_u128(ss + (size_t)(i0 + j * 256u) * 16);
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j) if (i0 + j * 256u < nvec) *reinterpret_cast<uint4*>(dd + (size_t)(i0 + j * 256u) * 16) = q[j];
+    }
+    const uint32_t done = nvec << 4;
+    if (tid < len - done) dd[done + tid] = ss[done + tid];
+}
+
+// One workgroup per (frame, 32 KiB slice): the first one also writes the header (as lz4_batch_gather_kernel formats a volume's) and the
+// record (3 words of pinned host memory: status, blob bytes -- for kSpliceNoRoom what a retry needs --, payload bytes).  A blob that is
+// not kSpliceDone gets its record and not a byte else.  An old frame is copied as it stands from src + its span; a new one gets frame
+// header, size field and end mark around csize[k] bytes from its scratch slot, or around the chunk's own bytes where it is stored.
+__global__ __launch_bounds__(256)
+void lz4_splice_gather_kernel(const uint8_t* __restrict__ src, const uint4* __restrict__ blk, const uint32_t* __restrict__ slot_of, const uint8_t* __restrict__ in,
+                              const Lz4BatchChunk* __restrict__ table, const uint8_t* __restrict__ scratch, uint64_t stride, const uint32_t* __restrict__ csize,
+                              const uint64_t* __restrict__ frame_off, const uint64_t* __restrict__ info, const char* __restrict__ text, uint32_t prefix_len,
+                              uint32_t suffix_len, uint8_t* __restrict__ out, uint32_t bd_byte, uint32_t hc_byte, uint32_t slices_per_frame,
+                              uint64_t* __restrict__ record)
+{
+    const uint32_t f = blockIdx.x / slices_per_frame, slice = blockIdx.x % slices_per_frame, tid = threadIdx.x;
+    const uint64_t payload = info[0], hs = info[1];
+    const uint64_t hdr_len = hs & 0xffffffffull, status = hs >> 32;
+    const bool first = blockIdx.x == 0;
+    if (first && tid == 0) {
+        record[1] = status == kSpliceDone || status == kSpliceNoRoom ? hdr_len + payload : 0;
+        record[2] = payload;
+        record[0] = status;
+    }
+    if (status != kSpliceDone) return;
+    if (first) {
+        const uint32_t nd = decimal_digits(payload);
+        const uint64_t pad = hdr_len - ((uint64_t)prefix_len + nd + suffix_len);
+        for (uint64_t i = tid; i < hdr_len; i += 256) {
+            uint8_t c;
+            if (i < pad) c = ' ';
+            else if (i < pad + prefix_len) c = (uint8_t)text[i - pad];
+            else if (i < pad + prefix_len + nd) {                                        // the payload's decimal digits, most significant first
+                uint64_t q = payload;
+                for (uint64_t k = i - pad - prefix_len + 1; k < nd; ++k) q /= 10;
+                c = (uint8_t)('0' + q % 10);
+            }
+            else c = (uint8_t)text[prefix_len + (i - pad - prefix_len - nd)];
+            out[i] = c;
+        }
+    }
+    uint8_t* __restrict__ d = out + hdr_len + frame_off[f];
+    const uint32_t k = slot_of[f];
+    const uint8_t* __restrict__ s;
+    uint32_t body;
+    if (k == kSpliceOldFrame) {                                        // the whole old frame, marks and all
+        const uint4 b = blk[f];
+        s = src + (((uint64_t)b.x | ((uint64_t)b.y << 32)) - kLz4FrameHead);
+        body = (uint32_t)lz4_splice_old_frame_bytes(b.z);
+    } else {
+        const Lz4BatchChunk ce = table[k];
+        const uint32_t c = csize[k];
+        body = c ? c : ce.n;
+        s = c ? scratch + (uint64_t)ce.slot * stride : in + ce.off;
+        if (slice == 0 && tid < 15) {
+            const uint32_t field = c ? c : (ce.n | 0x80000000u);
+            uint8_t v = 0;
+            uint32_t o = tid;
+            switch (tid) {
+                case 0: v = 0x04; break; case 1: v = 0x22; break; case 2: v = 0x4D; break; case 3: v = 0x18; break;
+                case 4: v = 0x40; break; case 5: v = (uint8_t)bd_byte; break; case 6: v = (uint8_t)hc_byte; break;
+                case 7: v = (uint8_t)field; break; case 8: v = (uint8_t)(field >> 8); break;
+                case 9: v = (uint8_t)(field >> 16); break; case 10: v = (uint8_t)(field >> 24); break;
+                default: v = 0; o = 11 + body + (tid - 11); break;                                          // end mark
+            }
+            d[o] = v;
+        }
+        d += kLz4FrameHead;
+    }
+    const uint32_t begin = slice * GATHER_SLICE;
+    if (begin >= body) return;
+    const uint32_t end = (begin + GATHER_SLICE < body) ? begin + GATHER_SLICE : body;
+    splice_copy(d + begin, s + begin, end - begin, tid);
+}
+
+// ------------------------------------------------------------------------------------------------
 // quantiser (encoders/quantiser_scheme_impl.hpp:176-226): 65536-bin histogram, then LUT apply.
 //
 // Histogram: every workgroup keeps a private 16384-bin window of the value range in LDS (64 KiB) and
@@ -6830,6 +6978,30 @@ hipError_t launch_lz4_batch_place(uint64_t* vinfo, const uint64_t* d_gap, uint32
     return hipGetLastError();
 }
 
+bool lz4_splice_job_ok(const Lz4SpliceJob& j)
+{
+    if (!j.blk || !j.slot_of || !j.table || !j.csize || j.nframes == 0 || j.max_frame <= kLz4FrameGap || (j.elem_size != 1 && j.elem_size != 2)) return false;
+    return (uint64_t)j.nframes * ((j.max_frame + GATHER_SLICE - 1) / GATHER_SLICE) <= 0x7fffffffull;
+}
+
+hipError_t launch_lz4_splice_scan(const Lz4SpliceJob& j, uint64_t capacity, uint64_t* frame_off, uint64_t* info, hipStream_t stream)
+{
+    if (!lz4_splice_job_ok(j) || !frame_off || !info) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(lz4_splice_scan_kernel, dim3(1), dim3(256), 0, stream, static_cast<const uint4*>(j.blk), j.slot_of, j.nframes, j.table, j.csize, j.src_payload,
+                       j.max_frame, j.prefix_len, j.suffix_len, j.elem_size, capacity, frame_off, info);
+    return hipGetLastError();
+}
+
+hipError_t launch_lz4_splice_gather(const Lz4SpliceJob& j, const uint8_t* src, const uint8_t* in, const uint8_t* scratch, uint64_t stride, const uint64_t* frame_off,
+                                    const uint64_t* info, const char* d_text, uint8_t* out, uint32_t bd_byte, uint32_t hc_byte, uint64_t* record, hipStream_t stream)
+{
+    if (!lz4_splice_job_ok(j) || !src || !in || !scratch || !frame_off || !info || !d_text || !out || !record) return hipErrorInvalidValue;
+    const uint32_t slices = (j.max_frame + GATHER_SLICE - 1) / GATHER_SLICE;
+    hipLaunchKernelGGL(lz4_splice_gather_kernel, dim3(j.nframes * slices), dim3(256), 0, stream, src, static_cast<const uint4*>(j.blk), j.slot_of, in, j.table, scratch,
+                       stride, j.csize, frame_off, info, d_text, j.prefix_len, j.suffix_len, out, bd_byte, hc_byte, slices, record);
+    return hipGetLastError();
+}
+
 hipError_t launch_lz4_linked(const uint8_t* in, const Lz4Block* blocks, const uint32_t* frame_first, uint64_t nframes,
                              uint32_t max_block, uint8_t* scratch, uint64_t stride, uint32_t* csize, hipStream_t stream, uint32_t acceleration)
 {
@@ -8648,6 +8820,53 @@ __device__ __forceinline__ uint4 window_gather16(const uint8_t* __restrict__ vie
     return make_uint4(d[0], d[1], d[2], d[3]);
 }
 
+// The transposer of bitswap1_batch_strided_kernel over pieces of sixteen bytes, for the patch kernels: next(p, n) = the n voxels at offset p
+// of the thread's run of nw words; res[b] (zeroed by the caller) takes the thread's 16 bytes of the plane that carries bit b.
+template <int ELEM, class Next>
+__device__ __forceinline__ void window_patch_transpose(uint32_t (&res)[8 * ELEM][4], uint32_t nw, Next&& next)
+{
+    constexpr uint32_t W = 8 * ELEM, WPT = BSWB_THREAD_VOX / W;
+    if constexpr (ELEM == 2) {
+#pragma unroll
+        for (uint32_t i = 0; i < WPT; ++i) {
+            if (i >= nw) break;
+            const uint4 x = next(16u * i, 8u), y = next(16u * i + 8u, 8u);
+            const uint32_t d[8] = {x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w};
+            uint32_t v[16];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) { v[2 * k] = d[k] & 0xffffu; v[2 * k + 1] = d[k] >> 16; }
+            // plane 15 - b, word w: bit 15 - k = bit b of voxel 16 w + k
+#pragma unroll
+            for (int b = 0; b < 16; ++b) {
+                uint32_t a = 0;
+#pragma unroll
+                for (int k = 0; k < 16; ++k) a |= ((v[k] >> b) & 1u) << (15 - k);
+                res[b][i >> 1] |= a << (16u * (i & 1u));
+            }
+        }
+    } else {
+        // byte b of the result: bit b of the word's eight voxels, voxel k at bit 7 - k (bitswap1_u8_generic)
+        auto word_planes = [](uint64_t x) -> uint64_t {
+            uint64_t t = x, y;
+            y = (t ^ (t >> 7)) & 0x00AA00AA00AA00AAull; t = t ^ y ^ (y << 7);
+            y = (t ^ (t >> 14)) & 0x0000CCCC0000CCCCull; t = t ^ y ^ (y << 14);
+            y = (t ^ (t >> 28)) & 0x00000000F0F0F0F0ull; t = t ^ y ^ (y << 28);
+            const uint32_t r0 = __brev((uint32_t)t), r1 = __brev((uint32_t)(t >> 32));      // (bits reversed in every byte, bytes swapped)
+            return (uint64_t)__builtin_bswap32(r0) | ((uint64_t)__builtin_bswap32(r1) << 32);
+        };
+#pragma unroll
+        for (uint32_t i = 0; i < WPT; i += 2) {
+            if (i >= nw) break;
+            const uint4 x = next(8u * i, nw - i >= 2u ? 16u : 8u);                          // (a last odd word: its eight voxels, zeros behind them)
+            const uint64_t t[2] = {word_planes((uint64_t)x.x | ((uint64_t)x.y << 32)), word_planes((uint64_t)x.z | ((uint64_t)x.w << 32))};
+#pragma unroll
+            for (uint32_t u = 0; u < 2; ++u)
+#pragma unroll
+                for (int b = 0; b < 8; ++b) res[b][(i + u) >> 2] |= ((uint32_t)(t[u] >> (8 * b)) & 0xffu) << (8u * ((i + u) & 3u));
+        }
+    }
+}
+
 // The bit planes of a blob with a window's voxels replaced, without the old voxels ever being transposed back: old plane stream + the
 // window's view -> new plane stream (out of place).  bitswap1_batch_kernel's geometry over the BLOB's dense order: a workgroup is one tile
 // of BSWB_TILE_VOX voxels, a thread owns 128 voxels in a row, which is 16 bytes of every plane.  It clips its run first (the clip and the
@@ -8703,48 +8922,7 @@ void bitswap1_batch_patch_kernel(const BatchPatchJob* __restrict__ jobs, const u
     uint32_t res[W][4];                                               // res[b]: the thread's 16 bytes of the plane that carries bit b
 #pragma unroll
     for (uint32_t b = 0; b < W; ++b) { res[b][0] = 0; res[b][1] = 0; res[b][2] = 0; res[b][3] = 0; }
-    // the transposer of bitswap1_batch_strided_kernel over pieces of sixteen bytes: next(p, n) = the n voxels at offset p of the run
-    auto transpose = [&](auto&& next) {
-        if constexpr (ELEM == 2) {
-#pragma unroll
-            for (uint32_t i = 0; i < WPT; ++i) {
-                if (i >= nw) break;
-                const uint4 x = next(16u * i, 8u), y = next(16u * i + 8u, 8u);
-                const uint32_t d[8] = {x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w};
-                uint32_t v[16];
-#pragma unroll
-                for (int k = 0; k < 8; ++k) { v[2 * k] = d[k] & 0xffffu; v[2 * k + 1] = d[k] >> 16; }
-                // plane 15 - b, word w: bit 15 - k = bit b of voxel 16 w + k
-#pragma unroll
-                for (int b = 0; b < 16; ++b) {
-                    uint32_t a = 0;
-#pragma unroll
-                    for (int k = 0; k < 16; ++k) a |= ((v[k] >> b) & 1u) << (15 - k);
-                    res[b][i >> 1] |= a << (16u * (i & 1u));
-                }
-            }
-        } else {
-            // byte b of the result: bit b of the word's eight voxels, voxel k at bit 7 - k (bitswap1_u8_generic)
-            auto word_planes = [](uint64_t x) -> uint64_t {
-                uint64_t t = x, y;
-                y = (t ^ (t >> 7)) & 0x00AA00AA00AA00AAull; t = t ^ y ^ (y << 7);
-                y = (t ^ (t >> 14)) & 0x0000CCCC0000CCCCull; t = t ^ y ^ (y << 14);
-                y = (t ^ (t >> 28)) & 0x00000000F0F0F0F0ull; t = t ^ y ^ (y << 28);
-                const uint32_t r0 = __brev((uint32_t)t), r1 = __brev((uint32_t)(t >> 32));      // (bits reversed in every byte, bytes swapped)
-                return (uint64_t)__builtin_bswap32(r0) | ((uint64_t)__builtin_bswap32(r1) << 32);
-            };
-#pragma unroll
-            for (uint32_t i = 0; i < WPT; i += 2) {
-                if (i >= nw) break;
-                const uint4 x = next(8u * i, nw - i >= 2u ? 16u : 8u);                          // (a last odd word: its eight voxels, zeros behind them)
-                const uint64_t t[2] = {word_planes((uint64_t)x.x | ((uint64_t)x.y << 32)), word_planes((uint64_t)x.z | ((uint64_t)x.w << 32))};
-#pragma unroll
-                for (uint32_t u = 0; u < 2; ++u)
-#pragma unroll
-                    for (int b = 0; b < 8; ++b) res[b][(i + u) >> 2] |= ((uint32_t)(t[u] >> (8 * b)) & 0xffu) << (8u * ((i + u) & 3u));
-            }
-        }
-    };
+    auto transpose = [&](auto&& next) { window_patch_transpose<ELEM>(res, nw, next); };
     if (all) {
         // (a run that lies inside the window whole is a run of the window's dense order as well: the view's walk)
         const ViewGeometry gv{job.Y, job.X, job.sz, job.sy};
@@ -8787,6 +8965,107 @@ hipError_t launch_bitswap1_batch_patch(const BatchPatchJob* d_jobs, const uint32
     if (elem_size == 2) hipLaunchKernelGGL(bitswap1_batch_patch_kernel<2>, dim3(ntiles), dim3(256), 0, stream, d_jobs, d_first_tile, njobs);
     else if (elem_size == 1) hipLaunchKernelGGL(bitswap1_batch_patch_kernel<1>, dim3(ntiles), dim3(256), 0, stream, d_jobs, d_first_tile, njobs);
     else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+// ---- a box written into one large blob (SQYAMD_Update_Box_*) ---------------------------------------------------------------------------------
+// bitswap1_batch_patch_kernel's merge on bitswap1_decode_range_window_kernel's geometry: the plane words [w0, w1) of a compaction of LZ4
+// frames (Bitswap1Range's addressing: word w of stored plane segment s at buf + plane[s] + (w - w0) ELEM, the voxels [max(v0, L), v1) at
+// buf + tail) get the box's voxels out of the view, IN PLACE.  The grid runs over absolute words (sqy::range_run); a thread clips its run of
+// 128 voxels against the box before anything is loaded and is gone when nothing of it lies inside -- it loads and stores nothing.  The
+// others transpose the view's voxels in registers (zeros outside the box), build the run's 128-bit mask and store every plane as
+// (old & ~mask) | new, or just the new bits where the whole run lies inside: sixteen bytes at a time where buf + plane[s] - w0 ELEM is on the
+// 16-byte grid for every s and the thread owns all its words, word by word where not.  Tail voxels are stored directly.  A thread reads
+// and writes only the words of its own run (and group 0's first threads their own tail voxel), so patching in place is safe: no thread
+// reads what another one writes.
+template <int ELEM>
+__global__ __launch_bounds__(256)
+void bitswap1_range_patch_kernel(uint8_t* __restrict__ buf, const uint8_t* __restrict__ view, Bitswap1Range a, WindowGeometry g, uint64_t t0)
+{
+    constexpr uint32_t W = 8 * ELEM, WPT = BSWB_THREAD_VOX / W;        // voxels per word (= planes), words per thread
+    typedef typename std::conditional<ELEM == 2, uint16_t, uint8_t>::type word_t;
+    const uint32_t tid = threadIdx.x;
+    WindowPiece cur;
+    const uint64_t tail0 = a.v0 > a.L ? a.v0 : a.L;
+    if (blockIdx.x == 0 && tail0 + tid < a.v1) {                     // tail voxels: verbatim, the box's where it has one
+        WindowClip ct = window_clip_start(g, tail0 + tid, 1);
+        if (window_clip_next(g, &ct, &cur)) view_voxel_store<ELEM>(buf + a.tail, tid, view_voxel_load<ELEM>(view, cur.dst_off));
+    }
+    const RangeRun run = range_run(t0 + (uint64_t)blockIdx.x * 256u + tid, WPT, a.w0, a.w1);
+    if (run.lo == run.hi) return;
+    const WindowClip c0 = window_clip_start(g, run.first * W, (uint64_t)run.hi * W);
+    WindowClip c = c0;
+    uint32_t mask[4] = {0, 0, 0, 0}, inside = 0;
+    while (window_clip_next(g, &c, &cur)) {
+        window_run_mask(W, (uint32_t)cur.run_off, (uint32_t)cur.len, mask);
+        inside += (uint32_t)cur.len;
+    }
+    if (inside == 0) return;                                          // nothing of the run inside the box: no word is loaded or stored
+    const uint64_t at = (run.first - a.w0) * ELEM;                    // the thread's 16 bytes behind plane[s] (in front of it: a first thread's words not owned, never touched)
+    bool wide = run.lo == 0 && run.hi == WPT;
+    if (wide) {
+        uint32_t off_grid = 0;
+#pragma unroll
+        for (uint32_t s = 0; s < W; ++s) off_grid |= (uint32_t)(reinterpret_cast<uintptr_t>(buf) + a.plane[s] + at);
+        wide = (off_grid & 15u) == 0;
+    }
+    const bool all = inside == WPT * W;                               // (then the thread owns all its words: the box lies inside the range)
+    uint32_t res[W][4];                                               // res[b]: the thread's 16 bytes of the plane that carries bit b
+#pragma unroll
+    for (uint32_t b = 0; b < W; ++b) { res[b][0] = 0; res[b][1] = 0; res[b][2] = 0; res[b][3] = 0; }
+    c = c0;
+    bool have = window_clip_next(g, &c, &cur);
+    window_patch_transpose<ELEM>(res, run.hi, [&](uint32_t p, uint32_t n) { return window_gather16<ELEM>(view, g, c, cur, have, p, n); });
+    if (wide) {
+#pragma unroll
+        for (uint32_t b = 0; b < W; ++b) {
+            uint8_t* q = buf + a.plane[W - 1 - b] + at;
+            uint4 r = make_uint4(res[b][0], res[b][1], res[b][2], res[b][3]);
+            if (!all) {
+                const uint4 o = *reinterpret_cast<const uint4*>(q);
+                r = make_uint4(window_merge_word(o.x, r.x, mask[0]), window_merge_word(o.y, r.y, mask[1]), window_merge_word(o.z, r.z, mask[2]),
+                               window_merge_word(o.w, r.w, mask[3]));
+            }
+            *reinterpret_cast<uint4*>(q) = r;
+        }
+    } else {
+        constexpr uint32_t PER = 4 / ELEM;                            // plane words in 32 bits
+#pragma unroll
+        for (uint32_t i = 0; i < WPT; ++i)
+            if (i >= run.lo && i < run.hi) {
+                const word_t m = (word_t)(mask[i / PER] >> (W * (i % PER)));
+                if (m == 0) continue;                                 // (no voxel of the box in this word)
+#pragma unroll
+                for (uint32_t b = 0; b < W; ++b) {
+                    word_t* q = reinterpret_cast<word_t*>(buf + a.plane[W - 1 - b] + at + (uint64_t)i * ELEM);
+                    const word_t r = (word_t)(res[b][i / PER] >> (W * (i % PER)));
+                    *q = window_merge_word(*q, r, m);
+                }
+            }
+    }
+}
+
+bool bitswap1_range_patch_ok(const Bitswap1Range& r, const BatchWindowJob& box, int elem_size)
+{
+    if (r.v1 <= r.v0 || r.w1 < r.w0 || (elem_size != 1 && elem_size != 2) || !box.view) return false;
+    // the range holds the box: none of its voxels lies outside the words and the tail the kernel touches
+    if (box.Z == 0 || box.Y == 0 || box.X == 0 || box.bY == 0 || box.bX == 0 || box.oy + box.Y > box.bY || box.ox + box.X > box.bX ||
+        ((box.oz * box.bY + box.oy) * box.bX + box.ox) < r.v0 || ((box.oz + box.Z - 1) * box.bY + box.oy + box.Y - 1) * box.bX + box.ox + box.X > r.v1)
+        return false;
+    const uint32_t wpt = BSWB_THREAD_VOX / (8u * (uint32_t)elem_size);
+    return (range_thread_count(r.w0, r.w1, wpt) + 255) / 256 <= 0x7fffffffull;
+}
+
+hipError_t launch_bitswap1_range_patch(uint8_t* buf, const Bitswap1Range& r, const BatchWindowJob& box, int elem_size, hipStream_t stream)
+{
+    if (!buf || !bitswap1_range_patch_ok(r, box, elem_size)) return hipErrorInvalidValue;
+    const uint32_t wpt = BSWB_THREAD_VOX / (8u * (uint32_t)elem_size);
+    const uint64_t t0 = range_first_thread(r.w0, wpt), groups = (range_thread_count(r.w0, r.w1, wpt) + 255) / 256;
+    const dim3 grid((unsigned)(groups ? groups : 1));                  // (block 0 also moves the tail)
+    const WindowGeometry g{box.bY, box.bX, box.oz, box.oy, box.ox, box.Z, box.Y, box.X, box.sz, box.sy};
+    const uint8_t* view = static_cast<const uint8_t*>(box.view);
+    if (elem_size == 2) hipLaunchKernelGGL(bitswap1_range_patch_kernel<2>, grid, dim3(256), 0, stream, buf, view, r, g, t0);
+    else hipLaunchKernelGGL(bitswap1_range_patch_kernel<1>, grid, dim3(256), 0, stream, buf, view, r, g, t0);
     return hipGetLastError();
 }
 

@@ -888,6 +888,71 @@ BoxesPath decode_boxes_path(bool subset_form, RangeForm form, bool subset_option
     }
 }
 
+// ---- a box written into one large blob (SQYAMD_Update_Box_*) ----
+UpdateBoxPath update_box_path(const UpdateBoxFacts& f)
+{
+    const bool pipeline_ok = f.option_on && f.same_stages && f.form_ok;
+    const bool layout_ok = f.layout.chunked() && f.layout.accel == 1 && f.layout.nchunks > 1;
+    const bool blob_ok = f.subset_taken && f.frames == f.layout.nchunks && f.blocks == f.frames && f.frame_chunk == f.layout.chunk;
+    return pipeline_ok && layout_ok && blob_ok ? UpdateBoxPath::subset_patch : UpdateBoxPath::whole;
+}
+
+bool pipelines_same_stages(const Pipeline& a, const Pipeline& b)
+{
+    if (a.stages.size() != b.stages.size() || a.sink_index != b.sink_index) return false;
+    for (size_t i = 0; i < a.stages.size(); ++i) {
+        const Stage &x = a.stages[i], &y = b.stages[i];
+        if (x.kind != y.kind || x.name != y.name) return false;
+        if (x.kind == StageKind::lz4 ? x.lz4.config() != y.lz4.config() || x.lz4.block_id != y.lz4.block_id : x.config() != y.config()) return false;
+    }
+    return true;
+}
+
+bool update_box_form_ok(const Pipeline& p)
+{
+    const size_t ns = p.stages.size();
+    if (ns == 0 || ns > 2 || p.stages[ns - 1].kind != StageKind::lz4) return false;
+    return ns == 1 || p.stages[0].kind == StageKind::bitswap1;
+}
+
+bool lz4_splice_ok(const std::vector<uint32_t>& slot_of, size_t nselected)
+{
+    if (slot_of.empty() || slot_of.size() > 0x7fffffffull || nselected > slot_of.size()) return false;
+    uint32_t next = 0;
+    for (uint32_t s : slot_of) {
+        if (s == kSpliceOldFrame) continue;
+        if (s != next) return false;
+        ++next;
+    }
+    return next == nselected;
+}
+
+Lz4SplicePlan lz4_splice_plan(const std::vector<uint64_t>& old_off, const std::vector<uint32_t>& old_size, const std::vector<uint32_t>& slot_of,
+                              const std::vector<uint32_t>& csize, const std::vector<uint32_t>& n, uint64_t src_payload, uint32_t prefix_len, uint32_t suffix_len,
+                              uint32_t elem_size, uint64_t capacity)
+{
+    Lz4SplicePlan p;
+    const size_t nf = slot_of.size();
+    p.status = kSpliceBadIndex;
+    if (old_off.size() != nf || old_size.size() != nf || csize.size() != n.size() || !lz4_splice_ok(slot_of, n.size()) || elem_size == 0) return p;
+    p.frame_off.assign(nf + 1, 0);
+    bool bad = false;
+    for (size_t f = 0; f < nf; ++f) {
+        const uint32_t k = slot_of[f];
+        uint64_t sz;
+        if (k == kSpliceOldFrame) {
+            bad = bad || !lz4_splice_old_frame_ok(old_off[f], old_size[f], src_payload);
+            sz = lz4_splice_old_frame_bytes(old_size[f]);
+        } else
+            sz = lz4_splice_new_frame_bytes(csize[k], n[k]);
+        p.frame_off[f + 1] = p.frame_off[f] + sz;
+    }
+    p.payload = p.frame_off[nf];
+    p.header_bytes = lz4_splice_header_bytes(prefix_len, suffix_len, p.payload, elem_size);
+    p.status = bad ? kSpliceBadIndex : lz4_splice_status(p.header_bytes, p.payload, capacity);
+    return p;
+}
+
 // ---- stages ----
 static StageKind kind_of(const std::string& n)
 {

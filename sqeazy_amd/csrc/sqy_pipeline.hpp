@@ -356,6 +356,65 @@ SQY_PIPE_HD inline Lz4TableClearStores lz4_table_clear_stores(uint64_t table_add
 // the dword at byte `off` of the table: a key's half (0) or a value (~0)
 SQY_PIPE_HD inline uint32_t lz4_table_clear_dword(uint32_t off, uint32_t key_bytes) { return off < key_bytes ? 0u : 0xffffffffu; }
 
+// ---- a box written into one large blob (SQYAMD_Update_Box_*): the splice of old LZ4 frames and new ones into one blob ----
+// Frame f of the new blob is either REPLACED -- chunk k = slot_of[f] of the selection parsed again: csize[k] compressed bytes, 0 when
+// the chunk's n bytes are stored, as lz4_batch_gather writes a frame -- or the OLD frame, copied as it stands: the frame index names its
+// one block (data offset in the payload, size field with the raw bit), the frame's span is [data offset - kLz4FrameHead, data offset +
+// size + 4).  The kernels (lz4_splice_scan_kernel, lz4_splice_gather_kernel) and the host (lz4_splice_plan,
+// tests/sanitize/update_box_test.cpp) compute every number with the functions below.
+constexpr uint32_t kSpliceOldFrame = 0xffffffffu;       // slot_of[f] of a frame that is carried over
+constexpr uint64_t kSpliceDone = 1, kSpliceNoRoom = 2, kSplicePayloadTooLong = 3, kSpliceBadIndex = 4;
+SQY_PIPE_HD inline uint64_t lz4_splice_new_frame_bytes(uint32_t csize, uint32_t n) { return kLz4FrameHead + (csize ? csize : n) + 4; }
+SQY_PIPE_HD inline uint64_t lz4_splice_old_frame_bytes(uint32_t size_field) { return kLz4FrameHead + (size_field & 0x7fffffffu) + 4; }
+// an old frame's span lies inside the old payload of src_payload bytes
+SQY_PIPE_HD inline bool lz4_splice_old_frame_ok(uint64_t data_off, uint32_t size_field, uint64_t src_payload)
+{
+    return data_off >= kLz4FrameHead && data_off <= src_payload && (uint64_t)(size_field & 0x7fffffffu) + 4 <= src_payload - data_off;
+}
+SQY_PIPE_HD inline uint32_t decimal_digits(uint64_t v) { uint32_t nd = 0; do { ++nd; v /= 10; } while (v); return nd; }
+// the sqy header's length: prefix | payload bytes in decimal | suffix, padded in front to a multiple of the voxel size (sqeazy_header.hpp:172-178)
+SQY_PIPE_HD inline uint64_t lz4_splice_header_bytes(uint32_t prefix_len, uint32_t suffix_len, uint64_t payload, uint32_t elem_size)
+{
+    const uint64_t text = (uint64_t)prefix_len + decimal_digits(payload) + suffix_len;
+    return text + (elem_size - text % elem_size) % elem_size;
+}
+SQY_PIPE_HD inline uint64_t lz4_splice_status(uint64_t header_bytes, uint64_t payload, uint64_t capacity)
+{
+    return payload > 0x7fffffffull ? kSplicePayloadTooLong : (header_bytes + payload > capacity ? kSpliceNoRoom : kSpliceDone);
+}
+// The plan on the host: frame_off[f] = where frame f begins behind the header (nframes + 1 entries, the last one the payload's length),
+// the header's length and the verdict.  old_off / old_size: the frame index' data offset and size field per frame; slot_of as above;
+// csize / n: per selected chunk.  kSpliceBadIndex: an old frame whose span does not lie inside src_payload, or a slot out of range
+struct Lz4SplicePlan { std::vector<uint64_t> frame_off; uint64_t payload = 0, header_bytes = 0, status = 0; };
+Lz4SplicePlan lz4_splice_plan(const std::vector<uint64_t>& old_off, const std::vector<uint32_t>& old_size, const std::vector<uint32_t>& slot_of,
+                              const std::vector<uint32_t>& csize, const std::vector<uint32_t>& n, uint64_t src_payload, uint32_t prefix_len, uint32_t suffix_len,
+                              uint32_t elem_size, uint64_t capacity);
+// The launches' job geometry, checked on the host before any of them: at least one frame, every selected chunk 0 .. nselected - 1 named
+// by exactly one frame, in ascending order
+bool lz4_splice_ok(const std::vector<uint32_t>& slot_of, size_t nselected);
+
+// What runs for SQYAMD_Update_Box_*, stated once.
+//   subset_patch  only the LZ4 frames the box's z-range needs are decoded, patched where they lie, parsed again and spliced between
+//                 the old frames, which are copied verbatim
+//   whole         the whole blob decoded, one paste launch, the single call's encode
+// subset_patch needs ALL of: the option update_box_subset; `pipeline`, parsed, equal to the header's stage for stage (names and the lz4
+// parameters); the form `lz4` or `bitswap1->lz4` with no head filter in front (the quantiser's table and frame_shuffle's order depend on
+// the whole volume); lz4_encode_layout of the new blob `chunked` with acceleration 1 and more than one chunk; and the old blob taken by
+// DecodeCall::frames_subset with one single-block frame per chunk of that same size.
+enum class UpdateBoxPath { subset_patch, whole };
+struct UpdateBoxFacts {
+    bool option_on = false;                 // update_box_subset
+    bool same_stages = false;               // pipelines_same_stages(asked, held)
+    bool form_ok = false;                   // update_box_form_ok(asked)
+    Lz4EncodeLayout layout;                 // lz4_encode_layout(asked's lz4 parameters, total, nthreads)
+    bool subset_taken = false;              // frames_subset took the old blob ..
+    uint64_t frames = 0, blocks = 0, frame_chunk = 0;      // .. and indexed that many frames and blocks, cut at frame_chunk bytes
+};
+UpdateBoxPath update_box_path(const UpdateBoxFacts& f);
+struct Pipeline;
+bool pipelines_same_stages(const Pipeline& a, const Pipeline& b);
+bool update_box_form_ok(const Pipeline& p);
+
 // The block-parallel parse of block-linked frames (sqy_kernels.h: Lz4SpecArgs).  Worth it for few long frames: the frame walks would
 // leave the chip empty
 bool lz4_spec_wanted(const Lz4Plan& plan);
