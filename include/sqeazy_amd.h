@@ -435,6 +435,36 @@ SQY_FUNCTION_PREFIX int SQYAMD_Compare_BatchWindow_UI8_Device(const void* d_src,
                                                               const long* src_origins, const void* const* d_views, const long* view_shapes,
                                                               const long* view_strides, unsigned shape_size, unsigned long long* stats,
                                                               void* hip_stream);
+/* The same check for a stack stored as ONE blob: MANY boxes of one blob compared with resident voxels in one call, nothing written.  Box i
+ * is [origins + i rank, .. + view_shapes + i rank) of the volume SQYAMD_Decode_*_Device gives for the blob (count rows of `rank` longs
+ * each); it is compared with the view at d_views[i] (view_strides + i rank, NULL: every view dense) under the view rules of
+ * SQYAMD_Decode_Boxes_*_Device.  count = 1 is the single box.  stats: a HOST array of count rows of SQYAMD_COMPARE_FIELDS values, the
+ * fields and their meaning exactly SQYAMD_Compare_BatchWindow_*'s (a = the decoded voxel -- behind the quantiser's look-up the 16-bit
+ * voxel out of the table --, b = the view's voxel; exact unsigned 64-bit integers).
+ * Checked before anything runs on the device (else 1, stats zeroed; stats == NULL: 1): exactly what SQYAMD_Decode_Boxes_* checks -- the
+ * arguments, the view rules, every box against the one header, the voxel type, more workgroups than one launch takes --; whatever needs
+ * no header is checked before a device is looked for.  Views may overlap, coincide or be shared and a box may be named twice: nothing is
+ * written.  Nothing is written to device memory outside the library's workspace: d_src and the views keep their bytes.  A damaged LZ4
+ * frame that SOME box's z-range needs gives SQY_Decode's composite code for the call with EVERY row all ones (the frames are decoded
+ * united: the call does not say whose frame it was); a damaged frame that no box needs goes unnoticed, as in SQYAMD_Decode_Boxes_*.
+ * How: one header fetch, the LZ4 frames the boxes' z-ranges need united and decoded by one launch, one 64-byte record per box made ready on
+ * the stream, ONE output launch -- for `bitswap1->lz4` and `quantiser->bitswap1->lz4` the range transposer of SQYAMD_Decode_Boxes_* with
+ * a compare where it stores, for `lz4` and `frame_shuffle->lz4` one window compare in the compaction -- and ONE copy of the records behind
+ * it; the host fills VOXELS.  Every other blob is decoded whole ONCE into the workspace and one window compare takes all boxes
+ * ("compare_boxes_subset" = 0: every blob -- the same statistics).  Stream, context, ordering and thread safety as
+ * SQYAMD_Decode_Boxes_*_Device. */
+SQY_FUNCTION_PREFIX int SQYAMD_Compare_Boxes_UI16_Device(const void* d_src, long srclength, long count, const long* origins, const void* const* d_views,
+                                                         const long* view_shapes, const long* view_strides, unsigned rank, unsigned long long* stats,
+                                                         void* hip_stream);
+SQY_FUNCTION_PREFIX int SQYAMD_Compare_Boxes_UI8_Device(const void* d_src, long srclength, long count, const long* origins, const void* const* d_views,
+                                                        const long* view_shapes, const long* view_strides, unsigned rank, unsigned long long* stats,
+                                                        void* hip_stream);
+/* host-pointer variants: the blob is staged ONCE; views holds the boxes' voxels dense and back to back in box order (1 where views_bytes is
+ * not exactly their sum) */
+SQY_FUNCTION_PREFIX int SQYAMD_Compare_Boxes_UI16(const char* src, long srclength, long count, const long* origins, const long* extents, unsigned rank,
+                                                  const char* views, long views_bytes, unsigned long long* stats);
+SQY_FUNCTION_PREFIX int SQYAMD_Compare_Boxes_UI8(const char* src, long srclength, long count, const long* origins, const long* extents, unsigned rank,
+                                                 const char* views, long views_bytes, unsigned long long* stats);
 /* The write of a box into a tiled store, whose border cuts through tiles: every tile under the box is read, modified and written again
  * with ONE call.  Old blob i lies at d_src + src_offsets[i], src_lengths[i] bytes (host arrays; any alignment): a complete sqeazy blob of
  * the entry point's voxel type, any pipeline, any layout.  Window i is the box [origins row i, + win_shapes row i) of that blob's volume
@@ -582,6 +612,9 @@ SQY_FUNCTION_PREFIX void SQYAMD_Release_Workspace(void);
  *                                     the pipeline allows (0: every blob decoded whole and the box copied out -- same bytes)
  *   "decode_boxes_joint"              1 [SQY_NO_DECODE_BOXES_JOINT=1 -> 0]  SQYAMD_Decode_Boxes_*: the boxes' LZ4 frames united and decoded once, one
  *                                     output launch for all boxes (0: every box on its own, as by SQYAMD_Decode_Box_* -- same bytes)
+ *   "compare_boxes_subset"            1 [SQY_NO_COMPARE_BOXES_SUBSET=1 -> 0]  SQYAMD_Compare_Boxes_*: only the LZ4 frames the boxes' z-ranges need, the
+ *                                     comparing range transposer or one compare in the compaction, where the pipeline allows (0: every blob
+ *                                     decoded whole once and one window compare -- same statistics)
  *   "decode_slabs_joint"              1 [SQY_NO_DECODE_SLABS_JOINT=1 -> 0]  SQYAMD_Decode_Slabs_*: the chunked LZ4 blobs of a group indexed and
  *                                     decoded by one launch each (0: every blob on its own, as by SQYAMD_Decode_*_Device -- same bytes)
  *   "decode_batch_joint"              1 [SQY_NO_DECODE_BATCH_JOINT=1 -> 0]  SQYAMD_Decode_Batch_*: the joint-eligible blobs of a group ranked, decoded and

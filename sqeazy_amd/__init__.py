@@ -40,6 +40,7 @@ EXPORTED_SYMBOLS = (
     "SQYAMD_Decode_Frames_UI16_Device", "SQYAMD_Decode_Frames_UI8_Device", "SQYAMD_Decode_Frames_UI16", "SQYAMD_Decode_Frames_UI8",
     "SQYAMD_Decode_Box_UI16_Device", "SQYAMD_Decode_Box_UI8_Device", "SQYAMD_Decode_Box_UI16", "SQYAMD_Decode_Box_UI8",
     "SQYAMD_Decode_Boxes_UI16_Device", "SQYAMD_Decode_Boxes_UI8_Device", "SQYAMD_Decode_Boxes_UI16", "SQYAMD_Decode_Boxes_UI8",
+    "SQYAMD_Compare_Boxes_UI16_Device", "SQYAMD_Compare_Boxes_UI8_Device", "SQYAMD_Compare_Boxes_UI16", "SQYAMD_Compare_Boxes_UI8",
     "SQYAMD_Decode_Slabs_UI16_Device", "SQYAMD_Decode_Slabs_UI8_Device", "SQYAMD_Decode_Slabs_UI16", "SQYAMD_Decode_Slabs_UI8",
     "SQYAMD_Decode_Batch_UI16_Device", "SQYAMD_Decode_Batch_UI8_Device", "SQYAMD_Decode_Batch_UI16", "SQYAMD_Decode_Batch_UI8",
     "SQYAMD_Profile_Enable", "SQYAMD_Profile_Reset", "SQYAMD_Profile_Get",
@@ -139,6 +140,12 @@ def lib():
                                       ctypes.c_void_p]
         for f in ("SQYAMD_Decode_Boxes_UI8", "SQYAMD_Decode_Boxes_UI16"):
             getattr(L, f).argtypes = [ctypes.c_void_p, ctypes.c_long, ctypes.c_long, c_long_p, c_long_p, ctypes.c_uint, ctypes.c_void_p, ctypes.c_long]
+        for f in ("SQYAMD_Compare_Boxes_UI8_Device", "SQYAMD_Compare_Boxes_UI16_Device"):
+            getattr(L, f).argtypes = [ctypes.c_void_p, ctypes.c_long, ctypes.c_long, c_long_p, ctypes.POINTER(ctypes.c_void_p), c_long_p, c_long_p, ctypes.c_uint,
+                                      ctypes.POINTER(ctypes.c_ulonglong), ctypes.c_void_p]
+        for f in ("SQYAMD_Compare_Boxes_UI8", "SQYAMD_Compare_Boxes_UI16"):
+            getattr(L, f).argtypes = [ctypes.c_void_p, ctypes.c_long, ctypes.c_long, c_long_p, c_long_p, ctypes.c_uint, ctypes.c_void_p, ctypes.c_long,
+                                      ctypes.POINTER(ctypes.c_ulonglong)]
         for f in ("SQYAMD_Decode_Slabs_UI8_Device", "SQYAMD_Decode_Slabs_UI16_Device"):
             getattr(L, f).argtypes = [ctypes.c_void_p, c_long_p, c_long_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_long, c_long_p, ctypes.c_int,
                                       ctypes.c_void_p]
@@ -637,6 +644,41 @@ def compare_metrics(row, dtype):
         drange = f["view_max"] - f["view_min"]
         return {"mse": mse, "rms": rms, "nrmse": rms / drange, "mnmse": rms / (f["view_sum"] / f["voxels"]), "l1norm": f["sum_abs"], "l2norm": f["sum_sq"],
                 "psnr": np.float64(20.0) * np.log10(np.float64(np.iinfo(np.dtype(dtype)).max)) - np.float64(10.0) * np.log10(mse), "drange": drange}
+
+
+def compare_boxes_device(d_src, srclength, origins, d_views, shapes, strides, dtype, stream=None, count=None):
+    """SQYAMD_Compare_Boxes_*_Device on raw device pointers (ints): box i of extent shapes[i] that begins at voxel origins[i] of the ONE blob
+    at d_src, compared with the view at d_views[i] with that shape and strides[i] in voxels (strides None: every view dense); the views are
+    read, nothing is written.  count: the number of boxes (default: as many as there are shapes).  Returns (rc, stats): stats a (count, 8)
+    uint64 array, row i the exact integers COMPARE_FIELDS of box i (a: the decoded voxel, b: the view's); compare_metrics takes a row."""
+    n = len(shapes) if shapes is not None else len(origins or ())
+    first = (shapes or origins or [()])[0] if n else ()
+    ptrs = None if d_views is None else (ctypes.c_void_p * max(len(d_views), 1))(*[None if p is None else int(p) for p in d_views])
+    k = n if count is None else int(count)
+    stats = np.zeros((k if 0 < k < 2 ** 31 else 0, len(COMPARE_FIELDS)), dtype=np.uint64)      # (no rows: stats NULL, which the call refuses)
+    rc = getattr(lib(), "SQYAMD_Compare_Boxes_%s_Device" % _suffix(dtype))(
+        ctypes.c_void_p(None if d_src is None else int(d_src)), ctypes.c_long(int(srclength)), ctypes.c_long(n if count is None else int(count)), _long_rows(origins),
+        ptrs, _long_rows(shapes), _long_rows(strides), ctypes.c_uint(len(first)),
+        stats.ctypes.data_as(ctypes.POINTER(ctypes.c_ulonglong)) if stats.size else None, ctypes.c_void_p(stream or 0))
+    return rc, stats
+
+
+def compare_boxes(blob, origins, views):
+    """SQYAMD_Compare_Boxes_UI8/UI16: the boxes of the blob's volume that begin at origins[i] and have the shape of the ndarray views[i],
+    compared with those arrays with one call; returns (rc, stats) as compare_boxes_device."""
+    blob = bytes(blob)
+    size = decompressed_sizeof(blob)
+    n = len(views)
+    stats = np.zeros((n, len(COMPARE_FIELDS)), dtype=np.uint64)
+    if size not in (1, 2) or not decompressed_shape(blob) or len(origins) != n or not n:
+        return 1, stats
+    dtype = np.uint16 if size == 2 else np.uint8
+    dense = np.concatenate([np.ascontiguousarray(v, dtype=dtype).reshape(-1) for v in views])
+    src = np.frombuffer(blob, dtype=np.uint8)
+    rc = getattr(lib(), "SQYAMD_Compare_Boxes_" + _suffix(dtype))(
+        src.ctypes.data, ctypes.c_long(len(blob)), ctypes.c_long(n), _long_rows(origins), _long_rows([np.shape(v) for v in views]), ctypes.c_uint(np.ndim(views[0])),
+        dense.ctypes.data, ctypes.c_long(dense.nbytes), stats.ctypes.data_as(ctypes.POINTER(ctypes.c_ulonglong)))
+    return rc, stats
 
 
 def update_batch_window_device(pipeline, d_src, offsets, lengths, origins, d_wins, shapes, strides, dtype, d_dst, slot_capacity, nthreads=0, stream=None):

@@ -7,7 +7,8 @@
 // of the blob's dense order and yields the sub-runs that lie inside the window -- each one within a row, so consecutive on both sides --
 // with two divisions at its start and none afterwards: what lies outside is stepped over with multiplications.
 // Behind the clip: the mask and the merge of a window's update in the bit-plane layout (SQYAMD_Update_BatchWindow_*), and the sums of a
-// window's compare with a view (SQYAMD_Compare_BatchWindow_*; tests/sanitize/batch_compare_test.cpp holds them against a triple loop).
+// window's compare with a view (SQYAMD_Compare_BatchWindow_*; tests/sanitize/batch_compare_test.cpp holds them against a triple loop;
+// SQYAMD_Compare_Boxes_* gathers the same sums over the range transposer's runs: tests/sanitize/compare_boxes_test.cpp).
 #ifndef SQY_BATCH_WINDOW_HPP_
 #define SQY_BATCH_WINDOW_HPP_
 

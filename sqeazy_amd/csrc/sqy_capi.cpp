@@ -80,6 +80,7 @@ struct Options {
     std::atomic<long> decode_frames_subset;             // frame-range decode: only the LZ4 frames the range needs, where the pipeline allows (0: full decode + copy)
     std::atomic<long> decode_box_subset;                // box decode: only the LZ4 frames the box's z-range needs, where the pipeline allows (0: full decode + window copy)
     std::atomic<long> decode_boxes_joint;               // many boxes of one blob: the frames united, one output launch for all boxes (0: the single-box driver box by box)
+    std::atomic<long> compare_boxes_subset;             // compare of many boxes of one blob: only the LZ4 frames the boxes' z-ranges need, the comparing range transposer or one compare in the compaction, where sqy::compare_boxes_path allows (0: the blob decoded whole once, one window compare)
     std::atomic<long> update_box_subset;                // box update of one blob: only the LZ4 frames the box's z-range needs are decoded, patched, parsed again and spliced between the old ones, where sqy::update_box_path allows (0: whole decode, one paste, the single call's encode)
     std::atomic<long> decode_slabs_joint;               // slab-set decode: the chunked LZ4 blobs of a group indexed and decoded by one launch each (0: blob by blob)
     std::atomic<long> decode_batch_joint;               // batch decode: the joint-eligible blobs of a group indexed, decoded and transposed back by one launch each (0: blob by blob)
@@ -106,7 +107,7 @@ struct Options {
           transpose_tiles_per_wave(env_number("SQY_TRANSPOSE_TILES_PER_WAVE", sqy::kBitswap1TilesPerWave, 1, 64)), stored_tail_index(env_flag("SQY_NO_STORED_TAIL_INDEX") ? 0 : 1),
           host_l2_bytes((long)sqy::host_l2_cache_bytes()), decode_frames_subset(env_flag("SQY_NO_DECODE_FRAMES_SUBSET") ? 0 : 1),
           decode_box_subset(env_flag("SQY_NO_DECODE_BOX_SUBSET") ? 0 : 1), decode_boxes_joint(env_flag("SQY_NO_DECODE_BOXES_JOINT") ? 0 : 1),
-          update_box_subset(env_flag("SQY_NO_UPDATE_BOX_SUBSET") ? 0 : 1),
+          compare_boxes_subset(env_flag("SQY_NO_COMPARE_BOXES_SUBSET") ? 0 : 1), update_box_subset(env_flag("SQY_NO_UPDATE_BOX_SUBSET") ? 0 : 1),
           decode_slabs_joint(env_flag("SQY_NO_DECODE_SLABS_JOINT") ? 0 : 1), decode_batch_joint(env_flag("SQY_NO_DECODE_BATCH_JOINT") ? 0 : 1),
           decode_batch_group_bytes(env_number("SQY_DECODE_BATCH_GROUP_BYTES", (long)kSlabsGroupBytes, 1, (long)kSlabsGroupBytes)), encode_batch_joint(env_flag("SQY_NO_ENCODE_BATCH_JOINT") ? 0 : 1),
           encode_batch_group_bytes(env_number("SQY_ENCODE_BATCH_GROUP_BYTES", kBatchGroupBytesDefault, 1, kBatchBytesMax)),
@@ -131,6 +132,7 @@ struct Options {
         if (!std::strcmp(name, "decode_frames_subset")) return &decode_frames_subset;
         if (!std::strcmp(name, "decode_box_subset")) return &decode_box_subset;
         if (!std::strcmp(name, "decode_boxes_joint")) return &decode_boxes_joint;
+        if (!std::strcmp(name, "compare_boxes_subset")) return &compare_boxes_subset;
         if (!std::strcmp(name, "update_box_subset")) return &update_box_subset;
         if (!std::strcmp(name, "decode_slabs_joint")) return &decode_slabs_joint;
         if (!std::strcmp(name, "decode_batch_joint")) return &decode_batch_joint;
@@ -3741,6 +3743,201 @@ int compare_batch_window_device(const void* d_src, const long* offsets, const lo
     return rc;
 }
 
+// ---- many boxes of one large blob compared with resident voxels (SQYAMD_Compare_Boxes_*) -----------------------------------
+// decode_boxes_on_device with loads where its stores were: ONE header fetch, the LZ4 frames of all boxes' z-ranges united
+// (DecodeCall::frames_subset on the ranges), a record of eight 64-bit words per box in Workspace::batch_records made ready on the stream,
+// ONE output launch that adds into the records, ONE copy of them behind it; sqy::compare_boxes_path says what runs.  The views are only
+// read and nothing outside the workspace is written.
+static_assert(sizeof(sqy::Bitswap1BoxCompareJob) == sqy::kBitswap1BoxCompareJobBytes && sizeof(sqy::Bitswap1BoxCompareJob) % 16 == 0, "the comparing box job's layout");
+
+// one window compare under `name`, a job per box: box i (ws[i]) of the dense volume at denses[i] against its view
+int launch_boxes_compare(Context& cx, hipStream_t stream, CompareLaunch& l, const char* name, int elem_size)
+{
+    std::vector<PendingEvent>* pend = &cx.pending;
+    const uint32_t* d_tiles = nullptr;
+    if (l.upload(stream, cx.ws.boxes_jobs, &d_tiles)) return 1;
+    SQY_TIMED(name, sqy::launch_batch_window_compare(static_cast<const sqy::BatchCompareJob*>(cx.ws.boxes_jobs.p), d_tiles, (uint32_t)l.jobs.size(), l.ntiles, elem_size, stream));
+    return 0;
+}
+
+// the compare's one launch behind DecodeCall::frames_subset: box i (ws[i], its view vs[i] at views[i]) of the united frames in c.range_buf
+// into the record at d_records + 8 i
+int boxes_range_compare(DecodeCall& c, CompareLaunch& l, TiledJobs<sqy::Bitswap1BoxCompareJob>& tj, const std::vector<sqy::BatchWindow>& ws, const std::vector<WindowView>& vs,
+                        const void* const* views, unsigned rank, unsigned long long* d_records)
+{
+    hipStream_t stream = c.stream;
+    std::vector<PendingEvent>* pend = c.pend;
+    const sqy::FrameRangesPlan& p = c.ranges_plan;
+    const size_t count = ws.size();
+    if (p.boxes.size() != count) return 1;
+    if (sqy::compare_boxes_path(true, c.range_form, true) == sqy::BoxPath::subset_transposer) {
+        const uint16_t* lut = nullptr;
+        if (c.range_lut(&lut)) return 1;
+        const uint32_t wpt = 128u / (8u * (uint32_t)p.we);
+        for (size_t i = 0; i < count; ++i) {
+            const sqy::BatchWindow& w = ws[i];
+            const sqy::FrameRangesBox& b = p.boxes[i];
+            sqy::Bitswap1BoxCompareJob j{};
+            j.view = views[i];
+            j.g = sqy::WindowGeometry{w.bY, w.bX, w.oz, w.oy, w.ox, w.Z, w.Y, w.X, vs[i].sz, vs[i].sy};
+            std::copy(b.plane, b.plane + 16, j.r.plane);
+            j.r.tail = b.tail; j.r.w0 = b.w0; j.r.w1 = b.w1; j.r.v0 = b.v0; j.r.v1 = b.v1; j.r.L = b.L;
+            j.t0 = sqy::range_first_thread(b.w0, wpt);
+            j.record = d_records + sqy::kCompareFields * i;
+            if (!sqy::bitswap1_box_compare_job_ok(j)) return 1;
+            tj.jobs.push_back(j);
+            tj.first_tile.push_back(tj.ntiles);
+            tj.ntiles += (uint32_t)sqy::range_job_groups(b.w0, b.w1, wpt);
+        }
+        const uint32_t* d_tiles = nullptr;
+        if (tj.upload(stream, c.cx.ws.boxes_jobs, &d_tiles)) return 1;
+        SQY_TIMED(lut ? "bitswap1_quantiser_compare_boxes" : "bitswap1_compare_boxes",
+                  sqy::launch_bitswap1_decode_range_windows_compare(c.range_buf, static_cast<const sqy::Bitswap1BoxCompareJob*>(c.cx.ws.boxes_jobs.p), d_tiles, (uint32_t)count,
+                                                                    tj.ntiles, p.we, lut, stream));
+        return 0;
+    }
+    // plain, shuffle: box i's range in the workspace is a blob of its frames, the box begins at its first one (boxes_range_out's geometry)
+    for (size_t i = 0; i < count; ++i) {
+        sqy::BatchWindow in_range = ws[i];
+        if (rank == 3) { in_range.bZ = in_range.Z; in_range.oz = 0; }
+        else if (rank == 2) { in_range.bY = in_range.Y; in_range.oy = 0; }
+        else { in_range.bX = in_range.X; in_range.ox = 0; }
+        l.add(views[i], c.range_buf + p.boxes[i].range_at, in_range, vs[i], false, d_records + sqy::kCompareFields * i);
+    }
+    return launch_boxes_compare(c.cx, stream, l, "boxes_window_compare", c.h.elem_size());
+}
+
+// Box i = [origins + i rank, .. + extents + i rank) of the blob against the view at d_views[i] (strides + i rank, or dense).  The checks
+// of decode_boxes_on_device -- all before anything runs on the device.  stats: count rows, zeroed by the caller; every row all ones where
+// the decode fails behind the admission (a damaged frame that some box needs)
+int compare_boxes_on_device(Context& cx, const void* d_src_v, uint64_t srclen, size_t count, const long* origins, const void* const* d_views, const long* extents,
+                            const long* strides, unsigned rank, int want_elem, hipStream_t stream, unsigned long long* stats)
+{
+    const uint8_t* d_src = static_cast<const uint8_t*>(d_src_v);
+    std::vector<PendingEvent>* pend = &cx.pending;
+    DrainOnExit drain{stream, &cx.pending, cx.side};
+    sqy::HeaderInfo h;
+    if (fetch_header(d_src, srclen, stream, h)) return 1;
+    uint64_t raw_bytes = 0;
+    if (!admit_blob(h, srclen, want_elem, &raw_bytes)) return 1;
+    std::vector<sqy::BatchWindow> ws(count);
+    std::vector<WindowView> vs(count);
+    std::vector<std::pair<uint64_t, uint64_t>> ranges(count);
+    const uint64_t frame_voxels = raw_bytes / (uint64_t)want_elem / h.shape[0];
+    uint64_t copy_tiles = 0, range_groups = 0;               // what the one output launch may hold, whichever it is
+    for (size_t i = 0; i < count; ++i) {
+        const long* o = origins + i * rank;
+        const long* e = extents + i * rank;
+        if (!sqy::admit_window(h.shape, o, e, rank, &ws[i])) {
+            std::fprintf(stderr, "[sqeazy]\t compare boxes: box %zu does not lie inside the blob's shape, or has another rank\n", i);
+            return 1;
+        }
+        vs[i] = window_view(ws[i], strides ? strides + i * rank : nullptr, rank);
+        ranges[i] = {(uint64_t)o[0], (uint64_t)e[0]};
+        copy_tiles += sqy::batch_bitswap1_tiles(ws[i].Z * ws[i].Y * ws[i].X);
+        range_groups += (uint64_t)e[0] * frame_voxels / sqy::kBatchTileVoxels + 2;      // (at least range_job_groups of the box's words)
+    }
+    if (std::max(copy_tiles, range_groups) > 0x7fffffffull) {
+        std::fprintf(stderr, "[sqeazy]\t compare boxes: too many workgroups for one launch\n");
+        return 1;
+    }
+    const size_t words = count * sqy::kCompareFields;
+    if (cx.ws.batch_records.ensure(words * 8)) return 1;
+    unsigned long long* d_records = static_cast<unsigned long long*>(cx.ws.batch_records.p);
+    std::vector<unsigned long long> host(words);
+    CompareLaunch l;                                                    // (both wait for the stream before their tables go)
+    TiledJobs<sqy::Bitswap1BoxCompareJob> tj;
+    // the rows behind the call's last synchronisation: the records with VOXELS filled in, or all ones where the decode failed (rc)
+    auto rows = [&](int rc) {
+        for (size_t i = 0; i < count; ++i) {
+            unsigned long long* row = stats + i * sqy::kCompareFields;
+            if (rc) { std::fill(row, row + sqy::kCompareFields, ~0ull); continue; }
+            std::copy(host.begin() + i * sqy::kCompareFields, host.begin() + (i + 1) * sqy::kCompareFields, row);
+            row[0] = ws[i].Z * ws[i].Y * ws[i].X;
+        }
+        return rc;
+    };
+    if (g_opt.compare_boxes_subset.load()) {
+        DecodeCall c(cx, stream, nullptr, h, Pipeline::from_string(h.pipename), raw_bytes / (uint64_t)want_elem, d_src + h.size);
+        bool taken = false;
+        if (const int rc = c.frames_subset(ranges, false, &taken)) return rc;
+        if (taken) {
+            SQY_TIMED("batch_compare_init", sqy::launch_batch_compare_init(d_records, (uint32_t)count, stream));
+            if (const int rc = boxes_range_compare(c, l, tj, ws, vs, d_views, rank, d_records)) return rc;
+            SQY_HIP(hipMemcpyAsync(host.data(), d_records, words * 8, hipMemcpyDeviceToHost, stream));
+            return rows(c.finish());
+        }
+    }
+    // sqy::BoxPath::whole_copy: the whole volume ONCE, then all boxes in one launch
+    if (cx.ws.range_full.ensure(std::max<uint64_t>(raw_bytes, 16))) return 1;
+    if (const int rc = decode_on_device(cx, d_src_v, srclen, cx.ws.range_full.p, raw_bytes, want_elem, stream)) return rows(rc);
+    SQY_TIMED("batch_compare_init", sqy::launch_batch_compare_init(d_records, (uint32_t)count, stream));
+    for (size_t i = 0; i < count; ++i) l.add(d_views[i], cx.ws.range_full.p, ws[i], vs[i], false, d_records + sqy::kCompareFields * i);
+    if (launch_boxes_compare(cx, stream, l, "boxes_window_compare", want_elem)) return 1;
+    SQY_HIP(hipMemcpyAsync(host.data(), d_records, words * 8, hipMemcpyDeviceToHost, stream));
+    SQY_HIP(hipStreamSynchronize(stream));
+    if (g_prof_on.load()) prof_collect(cx.pending);
+    return rows(0);
+}
+
+// SQYAMD_Compare_Boxes_*_Device: decode_boxes_device's checks with the views read-only; stats zeroed on every refusal
+int compare_boxes_device(const void* d_src, long srclength, long count, const long* origins, const void* const* d_views, const long* view_shapes, const long* view_strides,
+                         unsigned rank, unsigned long long* stats, int elem_size, void* hip_stream)
+{
+    if (stats && count > 0 && count <= INT_MAX) std::fill(stats, stats + (size_t)count * sqy::kCompareFields, 0ull);
+    if (!stats || !d_views || !boxes_arguments_ok(d_src, srclength, count, origins, d_views, view_shapes, rank)) {
+        std::fprintf(stderr, "[sqeazy]\t compare boxes: bad arguments\n");
+        return 1;
+    }
+    std::vector<sqy::BatchView> views;
+    if (admit_views("compare boxes", d_views, view_shapes, view_strides, rank, (int)count, elem_size, &views)) return 1;
+    ContextLease lease;
+    if (!lease.ctx) { std::fprintf(stderr, "[sqeazy]\t no usable HIP device\n"); return 1; }
+    return compare_boxes_on_device(*lease.ctx, d_src, (uint64_t)srclength, (size_t)count, origins, d_views, view_shapes, view_strides, rank, elem_size,
+                                   static_cast<hipStream_t>(hip_stream), stats);
+}
+
+// host pointers: the header and every box are checked here, before anything is staged; views: the boxes' voxels dense, back to back in
+// box order, exactly views_bytes of them.  The blob and the views are staged once each
+int compare_boxes_from_host(const char* src, long srclength, long count, const long* origins, const long* extents, unsigned rank, const char* views, long views_bytes,
+                            unsigned long long* stats, int elem_size)
+{
+    if (stats && count > 0 && count <= INT_MAX) std::fill(stats, stats + (size_t)count * sqy::kCompareFields, 0ull);
+    if (!stats || !views || !boxes_arguments_ok(src, srclength, count, origins, nullptr, extents, rank)) { std::fprintf(stderr, "[sqeazy]\t compare boxes: bad arguments\n"); return 1; }
+    const sqy::HeaderInfo h = sqy::header_unpack(src, src + srclength);
+    if (!h.valid) { std::fprintf(stderr, "[sqeazy]\t unable to find a sqy header in the blob\n"); return 1; }
+    uint64_t raw = 0;
+    if (!header_shape_ok(h, (uint64_t)srclength, &raw)) return 1;
+    if (h.elem_size() != elem_size) { std::fprintf(stderr, "[sqeazy]\t blob holds %s voxels\n", h.type.c_str()); return 1; }
+    std::vector<uint64_t> at((size_t)count + 1, 0);                    // (a box is no larger than the volume, count fits an int: no wrap)
+    for (long i = 0; i < count; ++i) {
+        sqy::BatchWindow w;
+        if (!sqy::admit_window(h.shape, origins + (size_t)i * rank, extents + (size_t)i * rank, rank, &w)) {
+            std::fprintf(stderr, "[sqeazy]\t compare boxes: box %ld does not lie inside the blob's shape\n", i);
+            return 1;
+        }
+        at[(size_t)i + 1] = at[(size_t)i] + w.Z * w.Y * w.X * (uint64_t)elem_size;
+    }
+    if (views_bytes < 0 || at.back() != (uint64_t)views_bytes) { std::fprintf(stderr, "[sqeazy]\t compare boxes: the views hold another number of bytes than the boxes\n"); return 1; }
+    if (!device_present()) { std::fprintf(stderr, "[sqeazy]\t no MI355X (HIP device) visible: sqeazy_amd has no CPU path\n"); return 1; }
+    ContextLease lease;
+    if (!lease.ctx) { std::fprintf(stderr, "[sqeazy]\t no usable HIP device\n"); return 1; }
+    Context& cx = *lease.ctx;
+    hipStream_t stream = cx.own_stream();
+    if (!stream) { std::fprintf(stderr, "[sqeazy]\t no HIP stream\n"); return 1; }
+    if (cx.ws.io_src.ensure(std::max<uint64_t>((uint64_t)srclength, 16)) || cx.ws.io_dst.ensure(std::max<uint64_t>(at.back(), 16))) return 1;
+    int dev_id = 0;
+    SQY_HIP(hipGetDevice(&dev_id));
+    if (!cx.stager.copy(cx.ws.io_src.p, const_cast<char*>(src), (size_t)srclength, true, dev_id) ||
+        !cx.stager.copy(cx.ws.io_dst.p, const_cast<char*>(views), (size_t)at.back(), true, dev_id)) {
+        std::fprintf(stderr, "[sqeazy]\t host to device transfer failed\n");
+        return 1;
+    }
+    std::vector<const void*> ptrs((size_t)count);
+    for (long i = 0; i < count; ++i) ptrs[(size_t)i] = static_cast<const uint8_t*>(cx.ws.io_dst.p) + at[(size_t)i];
+    return compare_boxes_on_device(cx, cx.ws.io_src.p, (uint64_t)srclength, (size_t)count, origins, ptrs.data(), extents, nullptr, rank, elem_size, stream, stats);
+}
+
 int decode_batch_device(const void* d_src, const BatchDecodeArgs& a, int elem_size, void* hip_stream)
 {
     if (admit_decode_batch(d_src, a)) return 1;
@@ -5193,6 +5390,30 @@ int SQYAMD_Decode_Boxes_UI16(const char* src, long srclength, long count, const 
 int SQYAMD_Decode_Boxes_UI8(const char* src, long srclength, long count, const long* origins, const long* extents, unsigned rank, char* dst, long dst_capacity)
 {
     return guarded([&]() -> int { return decode_boxes_from_host(src, srclength, count, origins, extents, rank, dst, dst_capacity, 1); });
+}
+
+int SQYAMD_Compare_Boxes_UI16_Device(const void* d_src, long srclength, long count, const long* origins, const void* const* d_views, const long* view_shapes,
+                                     const long* view_strides, unsigned rank, unsigned long long* stats, void* hip_stream)
+{
+    return guarded([&]() -> int { return compare_boxes_device(d_src, srclength, count, origins, d_views, view_shapes, view_strides, rank, stats, 2, hip_stream); });
+}
+
+int SQYAMD_Compare_Boxes_UI8_Device(const void* d_src, long srclength, long count, const long* origins, const void* const* d_views, const long* view_shapes,
+                                    const long* view_strides, unsigned rank, unsigned long long* stats, void* hip_stream)
+{
+    return guarded([&]() -> int { return compare_boxes_device(d_src, srclength, count, origins, d_views, view_shapes, view_strides, rank, stats, 1, hip_stream); });
+}
+
+int SQYAMD_Compare_Boxes_UI16(const char* src, long srclength, long count, const long* origins, const long* extents, unsigned rank, const char* views, long views_bytes,
+                              unsigned long long* stats)
+{
+    return guarded([&]() -> int { return compare_boxes_from_host(src, srclength, count, origins, extents, rank, views, views_bytes, stats, 2); });
+}
+
+int SQYAMD_Compare_Boxes_UI8(const char* src, long srclength, long count, const long* origins, const long* extents, unsigned rank, const char* views, long views_bytes,
+                             unsigned long long* stats)
+{
+    return guarded([&]() -> int { return compare_boxes_from_host(src, srclength, count, origins, extents, rank, views, views_bytes, stats, 1); });
 }
 
 int SQYAMD_Decode_Slabs_UI16_Device(const void* d_src, const long* offsets, const long* lengths, int nslabs, void* d_dst, long dst_capacity,

@@ -429,6 +429,24 @@ struct Bitswap1BoxJob {
 bool bitswap1_box_job_ok(const Bitswap1BoxJob& j);
 hipError_t launch_bitswap1_decode_range_windows(const uint8_t* in, const Bitswap1BoxJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ngroups,
                                                 int elem_size, const uint16_t* lut, hipStream_t stream);
+// ---- many boxes of one large blob compared with resident voxels (SQYAMD_Compare_Boxes_*) ----
+// launch_bitswap1_decode_range_windows with loads where its stores were: job j's view is only READ, and the sums over its box's voxels
+// (a = the decoded voxel -- behind the look-up the 16-bit voxel out of the table --, b = the view's) go into its record, eight 64-bit words
+// made ready by launch_batch_compare_init, with ONE set of integer atomics per workgroup that holds a voxel of the box.  The job is
+// Bitswap1BoxJob's fields and the record; the tables, the groups and bitswap1_box_compare_job_ok as there.  Nothing but the records is
+// written.
+struct Bitswap1BoxCompareJob {
+    const void* view;
+    WindowGeometry g;
+    Bitswap1Range r;
+    uint64_t t0;
+    unsigned long long* record;
+    uint64_t pad;
+};
+constexpr uint64_t kBitswap1BoxCompareJobBytes = 288;     // (a multiple of 16: the tile table behind the jobs stays on the 16-byte grid)
+bool bitswap1_box_compare_job_ok(const Bitswap1BoxCompareJob& j);
+hipError_t launch_bitswap1_decode_range_windows_compare(const uint8_t* in, const Bitswap1BoxCompareJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs,
+                                                        uint32_t ngroups, int elem_size, const uint16_t* lut, hipStream_t stream);
 // ---- a box written into one large blob (SQYAMD_Update_Box_*) ----
 // launch_bitswap1_decode_range_window the other way round, in place: the box's voxels are read from the view (box.view; `dense` and tile0
 // are not read) and merged into the plane words [w0, w1) and the tail of the range r inside the compaction at buf (launch_bitswap1_batch_patch's

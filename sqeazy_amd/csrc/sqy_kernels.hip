@@ -8766,6 +8766,143 @@ void bitswap1_decode_batch_window_compare_kernel(const BatchCompareJob* __restri
     compare_publish(s, job.record);
 }
 
+// ---- many boxes of one large blob compared with resident voxels (SQYAMD_Compare_Boxes_*) ------------------------------------------------
+// bitswap1_decode_range_windows_kernel with window_compare16 where range_window_body scatters: the same job walk, absolute-word grid
+// (sqy::range_run), clip, plane loads (sixteen bytes on the stream's grid, word by word elsewhere), transposes and look-up.  Where that body
+// returns -- a thread without a word, a run with nothing inside the box, the end of the tail -- this one goes on to compare_publish with
+// what it has, the neutral element where that is nothing: the reduction's cross-lane steps and barrier need every thread.  LUT: a is the
+// 16-bit voxel out of the decode table, the view holds 16-bit voxels.  Nothing but the job's record is written.
+template <int ELEM, bool LUT>
+__global__ __launch_bounds__(256)
+void bitswap1_decode_range_windows_compare_kernel(const uint8_t* __restrict__ in, const Bitswap1BoxCompareJob* __restrict__ jobs, const uint32_t* __restrict__ first_tile,
+                                                  uint32_t njobs, const uint16_t* __restrict__ lut)
+{
+    static_assert(!LUT || ELEM == 1, "the look-up follows 8-bit planes");
+    constexpr uint32_t W = 8 * ELEM, WPT = BSWB_THREAD_VOX / W;        // voxels per word, words per thread
+    constexpr int OUT = LUT ? 2 : ELEM;                                // bytes of a voxel in the view
+    __shared__ uint16_t sl[LUT ? 256 : 1];
+    if constexpr (LUT) { sl[threadIdx.x] = lut[threadIdx.x]; __syncthreads(); }
+    const uint32_t j = batch_job_of_tile(first_tile, njobs);
+    const Bitswap1BoxCompareJob* __restrict__ job = jobs + j;           // (uniform: its fields live in scalar registers)
+    const uint32_t own = blockIdx.x - first_tile[j], tid = threadIdx.x;
+    const Bitswap1Range& a = job->r;
+    const WindowGeometry& g = job->g;
+    const uint8_t* __restrict__ view = static_cast<const uint8_t*>(job->view);
+    CompareSums s = compare_sums_neutral();
+    WindowPiece cur;
+    const uint64_t tail0 = a.v0 > a.L ? a.v0 : a.L;
+    if (own == 0 && tail0 + tid < a.v1) {                            // tail voxels: verbatim in the stream (or looked up), those of the box
+        WindowClip ct = window_clip_start(g, tail0 + tid, 1);
+        if (window_clip_next(g, &ct, &cur)) {
+            const uint32_t x = view_voxel_load<ELEM>(in + a.tail, tid);
+            compare_voxel(&s, LUT ? (uint32_t)sl[x & 0xffu] : x, view_voxel_load<OUT>(view, cur.dst_off));
+        }
+    }
+    const RangeRun run = range_run(job->t0 + (uint64_t)own * 256u + tid, WPT, a.w0, a.w1);
+    const bool owns = run.lo != run.hi;
+    WindowClip c = window_clip_start(g, owns ? run.first * W : 0, owns ? (uint64_t)run.hi * W : 0);
+    bool have = owns && window_clip_next(g, &c, &cur);
+    if (have) {                                                       // (else: nothing of the run inside the box, no plane word is loaded)
+        const uint64_t at = (run.first - a.w0) * ELEM;                // the thread's 16 bytes behind plane[s] (in front of it: a first thread's words not owned, never read)
+        bool wide = run.lo == 0 && run.hi == WPT;
+        if (wide) {
+            uint32_t off_grid = 0;                                    // (uniform: first ELEM is a multiple of 16)
+#pragma unroll
+            for (uint32_t p = 0; p < W; ++p) off_grid |= (uint32_t)(reinterpret_cast<uintptr_t>(in) + a.plane[p] + at);
+            wide = (off_grid & 15u) == 0;
+        }
+        if constexpr (ELEM == 2) {
+            uint32_t pl[16][4];                                       // pl[b] = eight words of the plane that carries bit b
+            if (wide) {
+#pragma unroll
+                for (int b = 0; b < 16; ++b) {
+                    const uint4 t = *reinterpret_cast<const uint4*>(in + a.plane[15 - b] + at);
+                    pl[b][0] = t.x; pl[b][1] = t.y; pl[b][2] = t.z; pl[b][3] = t.w;
+                }
+            } else {
+#pragma unroll
+                for (int b = 0; b < 16; ++b) { pl[b][0] = 0; pl[b][1] = 0; pl[b][2] = 0; pl[b][3] = 0; }
+#pragma unroll
+                for (uint32_t i = 0; i < WPT; ++i)
+                    if (i >= run.lo && i < run.hi)
+#pragma unroll
+                        for (int b = 0; b < 16; ++b)
+                            pl[b][i >> 1] |= (uint32_t)*reinterpret_cast<const uint16_t*>(in + a.plane[15 - b] + at + 2u * i) << (16u * (i & 1u));
+            }
+#pragma unroll
+            for (uint32_t q = 0; q < 4; ++q) {                        // words first + 2 q (group A, low halves) and first + 2 q + 1 (group B)
+                if (2 * q >= run.hi || !have) break;
+                uint32_t r[16];
+#pragma unroll
+                for (int b = 0; b < 16; ++b) r[b] = pl[b][q];
+                transpose16x16_pairs(r);                              // r[i] = voxel 15 - i of group A | of group B << 16
+                uint32_t ga[8], gb[8];
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    ga[k] = __builtin_amdgcn_perm(r[14 - 2 * k], r[15 - 2 * k], 0x05040100u);
+                    gb[k] = __builtin_amdgcn_perm(r[14 - 2 * k], r[15 - 2 * k], 0x07060302u);
+                }
+                window_compare16<2>(view, g, c, cur, have, ga, 32u * q, 8, &s);
+                window_compare16<2>(view, g, c, cur, have, ga + 4, 32u * q + 8u, 8, &s);
+                if (2 * q + 1 >= run.hi) break;
+                window_compare16<2>(view, g, c, cur, have, gb, 32u * q + 16u, 8, &s);
+                window_compare16<2>(view, g, c, cur, have, gb + 4, 32u * q + 24u, 8, &s);
+            }
+        } else {
+            uint32_t pw[8][4];                                        // pw[b] = 16 bytes of the plane that carries bit b
+            if (wide) {
+#pragma unroll
+                for (int b = 0; b < 8; ++b) {
+                    const uint4 t = *reinterpret_cast<const uint4*>(in + a.plane[7 - b] + at);
+                    pw[b][0] = t.x; pw[b][1] = t.y; pw[b][2] = t.z; pw[b][3] = t.w;
+                }
+            } else {
+#pragma unroll
+                for (int b = 0; b < 8; ++b) { pw[b][0] = 0; pw[b][1] = 0; pw[b][2] = 0; pw[b][3] = 0; }
+#pragma unroll
+                for (uint32_t i = 0; i < WPT; ++i)
+                    if (i >= run.lo && i < run.hi)
+#pragma unroll
+                        for (int b = 0; b < 8; ++b) pw[b][i >> 2] |= (uint32_t)in[a.plane[7 - b] + at + i] << (8u * (i & 3u));
+            }
+#pragma unroll
+            for (uint32_t gq = 0; gq < 16; gq += 2) {
+                if (gq >= run.hi || !have) break;
+                uint32_t d[4];
+#pragma unroll
+                for (uint32_t u = 0; u < 2; ++u) {
+                    // (bitswap1_decode_batch_strided_kernel's gather and transpose: afterwards byte i of hi:lo = voxel 7 - i)
+                    constexpr uint32_t Zs = 0x0c;                     // v_perm selector: a zero byte
+                    const uint32_t cc = (gq + u) & 3u, wdx = (gq + u) >> 2;
+                    const uint32_t s01 = cc | ((4u + cc) << 8) | (Zs << 16) | (Zs << 24), s23 = Zs | (Zs << 8) | (cc << 16) | ((4u + cc) << 24);
+                    uint32_t lo_ = __builtin_amdgcn_perm(pw[1][wdx], pw[0][wdx], s01) | __builtin_amdgcn_perm(pw[3][wdx], pw[2][wdx], s23);
+                    uint32_t hi_ = __builtin_amdgcn_perm(pw[5][wdx], pw[4][wdx], s01) | __builtin_amdgcn_perm(pw[7][wdx], pw[6][wdx], s23);
+                    uint32_t y;
+                    y = (lo_ ^ (lo_ >> 7)) & 0x00AA00AAu; lo_ ^= y ^ (y << 7);
+                    y = (hi_ ^ (hi_ >> 7)) & 0x00AA00AAu; hi_ ^= y ^ (y << 7);
+                    y = (lo_ ^ (lo_ >> 14)) & 0x0000CCCCu; lo_ ^= y ^ (y << 14);
+                    y = (hi_ ^ (hi_ >> 14)) & 0x0000CCCCu; hi_ ^= y ^ (y << 14);
+                    y = (lo_ ^ (hi_ << 4)) & 0xF0F0F0F0u; lo_ ^= y; hi_ ^= y >> 4;
+                    d[2 * u] = __builtin_bswap32(hi_);                // voxels 0..3 of the word
+                    d[2 * u + 1] = __builtin_bswap32(lo_);            // voxels 4..7
+                }
+                if constexpr (LUT) {
+#pragma unroll
+                    for (uint32_t u = 0; u < 2; ++u) {                // word gq + u: eight 16-bit voxels, one piece
+                        if (gq + u >= run.hi) break;
+                        const uint32_t h4 = d[2 * u], l4 = d[2 * u + 1];      // (voxel k of four at byte k)
+                        const uint32_t v16[4] = {(uint32_t)sl[h4 & 0xffu] | ((uint32_t)sl[(h4 >> 8) & 0xffu] << 16), (uint32_t)sl[(h4 >> 16) & 0xffu] | ((uint32_t)sl[h4 >> 24] << 16),
+                                                 (uint32_t)sl[l4 & 0xffu] | ((uint32_t)sl[(l4 >> 8) & 0xffu] << 16), (uint32_t)sl[(l4 >> 16) & 0xffu] | ((uint32_t)sl[l4 >> 24] << 16)};
+                        window_compare16<2>(view, g, c, cur, have, v16, 8u * (gq + u), 8, &s);
+                    }
+                } else
+                    window_compare16<1>(view, g, c, cur, have, d, 8u * gq, run.hi - gq >= 2u ? 16u : 8u, &s);
+            }
+        }
+    }
+    compare_publish(s, job->record);
+}
+
 hipError_t launch_batch_compare_init(unsigned long long* d_records, uint32_t nrecords, hipStream_t stream)
 {
     if (nrecords == 0) return hipSuccess;
@@ -9133,6 +9270,30 @@ bool bitswap1_box_job_ok(const Bitswap1BoxJob& j)
     const Bitswap1Range& r = j.r;
     const WindowGeometry& g = j.g;
     if (r.v1 <= r.v0 || r.w1 < r.w0 || !j.view || g.Z == 0 || g.Y == 0 || g.X == 0) return false;
+    return ((g.oz * g.bY + g.oy) * g.bX + g.ox) >= r.v0 && ((g.oz + g.Z - 1) * g.bY + g.oy + g.Y - 1) * g.bX + g.ox + g.X <= r.v1;
+}
+
+static_assert(sizeof(Bitswap1BoxCompareJob) == kBitswap1BoxCompareJobBytes && sizeof(Bitswap1BoxCompareJob) % 16 == 0 &&
+                  offsetof(Bitswap1BoxCompareJob, record) == sizeof(Bitswap1BoxJob),
+              "the comparing box job: Bitswap1BoxJob's fields, the record behind them");
+
+hipError_t launch_bitswap1_decode_range_windows_compare(const uint8_t* in, const Bitswap1BoxCompareJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs,
+                                                        uint32_t ngroups, int elem_size, const uint16_t* lut, hipStream_t stream)
+{
+    if (njobs == 0 || ngroups < njobs || (elem_size != 1 && elem_size != 2) || (lut && elem_size != 1)) return hipErrorInvalidValue;
+    const dim3 grid(ngroups);
+    if (elem_size == 2) hipLaunchKernelGGL((bitswap1_decode_range_windows_compare_kernel<2, false>), grid, dim3(256), 0, stream, in, d_jobs, d_first_tile, njobs, lut);
+    else if (lut) hipLaunchKernelGGL((bitswap1_decode_range_windows_compare_kernel<1, true>), grid, dim3(256), 0, stream, in, d_jobs, d_first_tile, njobs, lut);
+    else hipLaunchKernelGGL((bitswap1_decode_range_windows_compare_kernel<1, false>), grid, dim3(256), 0, stream, in, d_jobs, d_first_tile, njobs, lut);
+    return hipGetLastError();
+}
+
+// bitswap1_box_job_ok for the comparing job, and a record to add into
+bool bitswap1_box_compare_job_ok(const Bitswap1BoxCompareJob& j)
+{
+    const Bitswap1Range& r = j.r;
+    const WindowGeometry& g = j.g;
+    if (r.v1 <= r.v0 || r.w1 < r.w0 || !j.view || !j.record || g.Z == 0 || g.Y == 0 || g.X == 0) return false;
     return ((g.oz * g.bY + g.oy) * g.bX + g.ox) >= r.v0 && ((g.oz + g.Z - 1) * g.bY + g.oy + g.Y - 1) * g.bX + g.ox + g.X <= r.v1;
 }
 

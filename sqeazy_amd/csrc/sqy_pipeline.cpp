@@ -888,6 +888,18 @@ BoxesPath decode_boxes_path(bool subset_form, RangeForm form, bool subset_option
     }
 }
 
+BoxPath compare_boxes_path(bool subset_form, RangeForm form, bool option_on)
+{
+    if (!subset_form || !option_on) return BoxPath::whole_copy;
+    switch (form) {
+    case RangeForm::planes:
+    case RangeForm::planes_lut: return BoxPath::subset_transposer;
+    case RangeForm::plain:
+    case RangeForm::shuffle: return BoxPath::subset_copy;
+    }
+    return BoxPath::whole_copy;
+}
+
 // ---- a box written into one large blob (SQYAMD_Update_Box_*) ----
 UpdateBoxPath update_box_path(const UpdateBoxFacts& f)
 {

@@ -502,6 +502,12 @@ BoxPath decode_box_path(bool subset_form, RangeForm form, bool option_on);
 //   whole_copy         the whole blob decoded ONCE into the workspace, ONE window copy with a job per box
 enum class BoxesPath { box_by_box, subset_transposer, subset_copy, whole_copy };
 BoxesPath decode_boxes_path(bool subset_form, RangeForm form, bool subset_option, bool joint_option);
+// Many boxes of one blob compared with resident voxels (SQYAMD_Compare_Boxes_*).  option_on: compare_boxes_subset; the rest as for
+// decode_box_path.  One record per box, ONE output launch on every path:
+//   subset_transposer  planes, planes_lut: the LZ4 frames of all boxes' z-ranges united, then the comparing job-table range transposer
+//   subset_copy        plain, shuffle: .. then ONE window compare with a job per box in the compaction
+//   whole_copy         every other blob, and every blob with the option off: decoded whole ONCE, ONE window compare with a job per box
+BoxPath compare_boxes_path(bool subset_form, RangeForm form, bool option_on);
 
 struct Stage {
     std::string name;
