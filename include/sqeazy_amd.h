@@ -525,6 +525,38 @@ SQY_FUNCTION_PREFIX int SQYAMD_Update_Box_UI16_Device(const char* pipeline, cons
 SQY_FUNCTION_PREFIX int SQYAMD_Update_Box_UI8_Device(const char* pipeline, const void* d_src, long srclength, const long* origin, const void* d_view,
                                                      const long* view_shape, const long* view_strides, unsigned rank, void* d_dst, long dst_capacity,
                                                      long* dstlength, int nthreads, void* hip_stream);
+/* MANY boxes written into ONE large blob in one call: SQYAMD_Update_Box_* for a table of `count` boxes (the table layout of
+ * SQYAMD_Decode_Boxes_* and SQYAMD_Compare_Boxes_*: `count` rows of `rank` longs in origins, view_shapes and view_strides; d_views a
+ * HOST array of `count` device pointers; view_strides NULL: every view dense).  Let V = what SQYAMD_Decode_*_Device gives for the old
+ * blob and V' = V with box 0, then box 1, .. then box count - 1 replaced by their views, in that order: boxes may overlap, and where
+ * they do the box with the higher index holds.  The new blob decodes to V' under `pipeline`; whenever the old blob is what the single
+ * call gives for V, the new blob is BYTE FOR BYTE what the single call gives for V' -- exactly what a chain of `count`
+ * SQYAMD_Update_Box_*_Device calls gives; count = 1 is SQYAMD_Update_Box_*.  A lossy old blob is re-quantised from its decoded voxels.
+ * Admission, all before a byte is written; every refusal returns 1 with *dstlength = 0.  Per box SQYAMD_Update_Box_*'s rules; in
+ * addition count < 1, a NULL entry of d_views, more workgroups than one launch takes.  Whatever needs no header is checked before a
+ * device is looked for.
+ * Errors are SQYAMD_Update_Box_*'s: a damaged LZ4 frame that SOME box's range needs gives SQY_Decode's composite code with d_dst
+ * untouched, one that no box needs is carried over unnoticed; a blob that does not fit returns 1 with *dstlength set to the exact
+ * bytes a retry needs, nothing at or behind d_dst + dst_capacity is written.
+ * How: where SQYAMD_Update_Box_* would take its subset path, its stages run ONCE each for all boxes -- one header
+ * fetch, one frame index, one decode of the LZ4 frames the boxes' ranges need (each once), one patch launch (`lz4`: one paste per
+ * layer of pairwise disjoint consecutive boxes, usually one), one parse, one splice.  Every other blob, and every blob with
+ * "update_boxes_subset" = 0 (SQY_NO_UPDATE_BOXES_SUBSET=1), is decoded whole once, pasted and encoded by the single call -- same bytes.
+ * Stream, context, ordering and thread safety are SQYAMD_Update_Box_*_Device's. */
+SQY_FUNCTION_PREFIX int SQYAMD_Update_Boxes_UI16_Device(const char* pipeline, const void* d_src, long srclength, long count, const long* origins,
+                                                        const void* const* d_views, const long* view_shapes, const long* view_strides, unsigned rank,
+                                                        void* d_dst, long dst_capacity, long* dstlength, int nthreads, void* hip_stream);
+SQY_FUNCTION_PREFIX int SQYAMD_Update_Boxes_UI8_Device(const char* pipeline, const void* d_src, long srclength, long count, const long* origins,
+                                                       const void* const* d_views, const long* view_shapes, const long* view_strides, unsigned rank,
+                                                       void* d_dst, long dst_capacity, long* dstlength, int nthreads, void* hip_stream);
+/* host-pointer variants: the blob staged once, the views dense and back to back in box order -- exactly views_bytes bytes of them, the
+ * boxes' summed bytes (checked, like the arguments, before a device is looked for); the new blob comes back to dst */
+SQY_FUNCTION_PREFIX int SQYAMD_Update_Boxes_UI16(const char* pipeline, const char* src, long srclength, long count, const long* origins, const long* extents,
+                                                 unsigned rank, const char* views, long views_bytes, char* dst, long dst_capacity, long* dstlength,
+                                                 int nthreads);
+SQY_FUNCTION_PREFIX int SQYAMD_Update_Boxes_UI8(const char* pipeline, const char* src, long srclength, long count, const long* origins, const long* extents,
+                                                unsigned rank, const char* views, long views_bytes, char* dst, long dst_capacity, long* dstlength,
+                                                int nthreads);
 /* host-pointer variants: blobs in host memory at src + offsets[i], dsts[i] host pointers (any alignment); arguments and headers are checked
  * on the host before any device is looked for */
 SQY_FUNCTION_PREFIX int SQYAMD_Decode_Batch_UI16(const char* src, const long* offsets, const long* lengths, int nblobs,
@@ -615,6 +647,8 @@ SQY_FUNCTION_PREFIX void SQYAMD_Release_Workspace(void);
  *   "compare_boxes_subset"            1 [SQY_NO_COMPARE_BOXES_SUBSET=1 -> 0]  SQYAMD_Compare_Boxes_*: only the LZ4 frames the boxes' z-ranges need, the
  *                                     comparing range transposer or one compare in the compaction, where the pipeline allows (0: every blob
  *                                     decoded whole once and one window compare -- same statistics)
+ *   "update_boxes_subset"             1 [SQY_NO_UPDATE_BOXES_SUBSET=1 -> 0]  SQYAMD_Update_Boxes_*: SQYAMD_Update_Box_*'s subset path, every stage once for
+ *                                     all boxes (0: the blob decoded whole once, the pastes layer by layer, the single call's encode -- same bytes)
  *   "decode_slabs_joint"              1 [SQY_NO_DECODE_SLABS_JOINT=1 -> 0]  SQYAMD_Decode_Slabs_*: the chunked LZ4 blobs of a group indexed and
  *                                     decoded by one launch each (0: every blob on its own, as by SQYAMD_Decode_*_Device -- same bytes)
  *   "decode_batch_joint"              1 [SQY_NO_DECODE_BATCH_JOINT=1 -> 0]  SQYAMD_Decode_Batch_*: the joint-eligible blobs of a group ranked, decoded and

@@ -34,6 +34,7 @@ EXPORTED_SYMBOLS = (
     "SQYAMD_Decode_BatchStrided_UI16_Device", "SQYAMD_Decode_BatchStrided_UI8_Device",
     "SQYAMD_Decode_BatchWindow_UI16_Device", "SQYAMD_Decode_BatchWindow_UI8_Device",
     "SQYAMD_Update_BatchWindow_UI16_Device", "SQYAMD_Update_BatchWindow_UI8_Device", "SQYAMD_Update_Box_UI16_Device", "SQYAMD_Update_Box_UI8_Device",
+    "SQYAMD_Update_Boxes_UI16_Device", "SQYAMD_Update_Boxes_UI8_Device", "SQYAMD_Update_Boxes_UI16", "SQYAMD_Update_Boxes_UI8",
     "SQYAMD_Compare_BatchWindow_UI16_Device", "SQYAMD_Compare_BatchWindow_UI8_Device",
     "SQYAMD_PipelineEncode_UI16_Cap", "SQYAMD_PipelineEncode_UI8_Cap",
     "SQYAMD_Decode_UI16_Device", "SQYAMD_Decode_UI8_Device",
@@ -117,6 +118,12 @@ def lib():
         for f in ("SQYAMD_Update_Box_UI8_Device", "SQYAMD_Update_Box_UI16_Device"):
             getattr(L, f).argtypes = [ctypes.c_char_p, ctypes.c_void_p, ctypes.c_long, c_long_p, ctypes.c_void_p, c_long_p, c_long_p, ctypes.c_uint, ctypes.c_void_p,
                                       ctypes.c_long, c_long_p, ctypes.c_int, ctypes.c_void_p]
+        for f in ("SQYAMD_Update_Boxes_UI8_Device", "SQYAMD_Update_Boxes_UI16_Device"):
+            getattr(L, f).argtypes = [ctypes.c_char_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_long, c_long_p, ctypes.POINTER(ctypes.c_void_p), c_long_p, c_long_p,
+                                      ctypes.c_uint, ctypes.c_void_p, ctypes.c_long, c_long_p, ctypes.c_int, ctypes.c_void_p]
+        for f in ("SQYAMD_Update_Boxes_UI8", "SQYAMD_Update_Boxes_UI16"):
+            getattr(L, f).argtypes = [ctypes.c_char_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_long, c_long_p, c_long_p, ctypes.c_uint, ctypes.c_void_p, ctypes.c_long,
+                                      ctypes.c_void_p, ctypes.c_long, c_long_p, ctypes.c_int]
         for f in ("SQYAMD_PipelineEncode_Batch_UI8", "SQYAMD_PipelineEncode_Batch_UI16"):
             getattr(L, f).argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_void_p), c_long_p, ctypes.c_uint, ctypes.c_int, ctypes.c_void_p, ctypes.c_long,
                                       c_long_p, c_long_p, ctypes.c_int]
@@ -711,6 +718,42 @@ def update_box_device(pipeline, d_src, srclength, origin, d_view, shape, strides
         None if strides is None else _longs(strides), ctypes.c_uint(len(shape) if shape is not None else len(origin or ())),
         ctypes.c_void_p(None if d_dst is None else int(d_dst)), ctypes.c_long(int(dst_capacity)), ctypes.byref(n), ctypes.c_int(nthreads), ctypes.c_void_p(stream or 0))
     return rc, n.value
+
+
+def update_boxes_device(pipeline, d_src, srclength, origins, d_views, shapes, strides, dtype, d_dst, dst_capacity, nthreads=0, stream=None, count=None):
+    """SQYAMD_Update_Boxes_*_Device on raw device pointers (ints): the old blob at d_src with box 0, then box 1, .. replaced by their views --
+    box i of extent shapes[i] begins at voxel origins[i], its new voxels are the view at d_views[i] with strides[i] in voxels (strides
+    None: every view dense); where boxes overlap the one with the higher index holds.  The new blob goes to d_dst (dst_capacity bytes),
+    byte for byte what a chain of update_box_device calls gives.  count: the number of boxes (default: as many as there are shapes).
+    Returns (rc, dstlength); rc 1 with a dstlength above 0: the bytes a retry needs."""
+    k = len(shapes) if shapes is not None else len(origins or ())
+    first = (shapes or origins or [()])[0] if k else ()
+    ptrs = None if d_views is None else (ctypes.c_void_p * max(len(d_views), 1))(*[None if p is None else int(p) for p in d_views])
+    n = ctypes.c_long(0)
+    rc = getattr(lib(), "SQYAMD_Update_Boxes_%s_Device" % _suffix(dtype))(
+        None if pipeline is None else pipeline.encode(), ctypes.c_void_p(None if d_src is None else int(d_src)), ctypes.c_long(int(srclength)),
+        ctypes.c_long(k if count is None else int(count)), _long_rows(origins), ptrs, _long_rows(shapes), _long_rows(strides), ctypes.c_uint(len(first)),
+        ctypes.c_void_p(None if d_dst is None else int(d_dst)), ctypes.c_long(int(dst_capacity)), ctypes.byref(n), ctypes.c_int(nthreads), ctypes.c_void_p(stream or 0))
+    return rc, n.value
+
+
+def update_boxes(pipeline, blob, origins, views, nthreads=0):
+    """SQYAMD_Update_Boxes_UI8/UI16: the blob (bytes) with the boxes that begin at origins[i] and have the shape of the ndarray views[i]
+    replaced by those arrays, in box order, with one call; returns (rc, new blob as bytes or None)."""
+    blob = bytes(blob)
+    size, shape = decompressed_sizeof(blob), decompressed_shape(blob)
+    n = len(views)
+    if size not in (1, 2) or not shape or len(origins) != n or not n:
+        return 1, None
+    dtype = np.uint16 if size == 2 else np.uint8
+    dense = np.concatenate([np.ascontiguousarray(v, dtype=dtype).reshape(-1) for v in views])
+    src = np.frombuffer(blob, dtype=np.uint8)
+    out = np.empty(max_compressed_length(pipeline, shape, dtype), dtype=np.uint8)
+    got = ctypes.c_long(0)
+    rc = getattr(lib(), "SQYAMD_Update_Boxes_" + _suffix(dtype))(
+        pipeline.encode(), src.ctypes.data, ctypes.c_long(len(blob)), ctypes.c_long(n), _long_rows(origins), _long_rows([np.shape(v) for v in views]),
+        ctypes.c_uint(np.ndim(views[0])), dense.ctypes.data, ctypes.c_long(dense.nbytes), out.ctypes.data, ctypes.c_long(out.nbytes), ctypes.byref(got), ctypes.c_int(nthreads))
+    return (rc, None) if rc else (0, out[:got.value].tobytes())
 
 
 def box_windows(shape, tile, box_origin, box_extent, dst_ptr, dst_strides, itemsize):

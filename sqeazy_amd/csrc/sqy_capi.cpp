@@ -15,6 +15,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <atomic>
+#include <functional>
 #include <condition_variable>
 #include <memory>
 #include <mutex>
@@ -82,6 +83,7 @@ struct Options {
     std::atomic<long> decode_boxes_joint;               // many boxes of one blob: the frames united, one output launch for all boxes (0: the single-box driver box by box)
     std::atomic<long> compare_boxes_subset;             // compare of many boxes of one blob: only the LZ4 frames the boxes' z-ranges need, the comparing range transposer or one compare in the compaction, where sqy::compare_boxes_path allows (0: the blob decoded whole once, one window compare)
     std::atomic<long> update_box_subset;                // box update of one blob: only the LZ4 frames the box's z-range needs are decoded, patched, parsed again and spliced between the old ones, where sqy::update_box_path allows (0: whole decode, one paste, the single call's encode)
+    std::atomic<long> update_boxes_subset;              // update of many boxes of one blob: update_box_subset's stages, each once for all boxes (0: the blob decoded whole once, the pastes layer by layer, the single call's encode)
     std::atomic<long> decode_slabs_joint;               // slab-set decode: the chunked LZ4 blobs of a group indexed and decoded by one launch each (0: blob by blob)
     std::atomic<long> decode_batch_joint;               // batch decode: the joint-eligible blobs of a group indexed, decoded and transposed back by one launch each (0: blob by blob)
     std::atomic<long> decode_batch_group_bytes;         // .. the LZ4 output one group holds at most (a group holds at least one blob)
@@ -108,6 +110,7 @@ struct Options {
           host_l2_bytes((long)sqy::host_l2_cache_bytes()), decode_frames_subset(env_flag("SQY_NO_DECODE_FRAMES_SUBSET") ? 0 : 1),
           decode_box_subset(env_flag("SQY_NO_DECODE_BOX_SUBSET") ? 0 : 1), decode_boxes_joint(env_flag("SQY_NO_DECODE_BOXES_JOINT") ? 0 : 1),
           compare_boxes_subset(env_flag("SQY_NO_COMPARE_BOXES_SUBSET") ? 0 : 1), update_box_subset(env_flag("SQY_NO_UPDATE_BOX_SUBSET") ? 0 : 1),
+          update_boxes_subset(env_flag("SQY_NO_UPDATE_BOXES_SUBSET") ? 0 : 1),
           decode_slabs_joint(env_flag("SQY_NO_DECODE_SLABS_JOINT") ? 0 : 1), decode_batch_joint(env_flag("SQY_NO_DECODE_BATCH_JOINT") ? 0 : 1),
           decode_batch_group_bytes(env_number("SQY_DECODE_BATCH_GROUP_BYTES", (long)kSlabsGroupBytes, 1, (long)kSlabsGroupBytes)), encode_batch_joint(env_flag("SQY_NO_ENCODE_BATCH_JOINT") ? 0 : 1),
           encode_batch_group_bytes(env_number("SQY_ENCODE_BATCH_GROUP_BYTES", kBatchGroupBytesDefault, 1, kBatchBytesMax)),
@@ -134,6 +137,7 @@ struct Options {
         if (!std::strcmp(name, "decode_boxes_joint")) return &decode_boxes_joint;
         if (!std::strcmp(name, "compare_boxes_subset")) return &compare_boxes_subset;
         if (!std::strcmp(name, "update_box_subset")) return &update_box_subset;
+        if (!std::strcmp(name, "update_boxes_subset")) return &update_boxes_subset;
         if (!std::strcmp(name, "decode_slabs_joint")) return &decode_slabs_joint;
         if (!std::strcmp(name, "decode_batch_joint")) return &decode_batch_joint;
         if (!std::strcmp(name, "decode_batch_group_bytes")) return &decode_batch_group_bytes;
@@ -4645,13 +4649,18 @@ int update_box_splice(DecodeCall& c, const UpdateBoxCall& u, const SpliceTables&
 
 // every other blob: whole decode, one paste, the single call's encode -- into the workspace first, so that a blob that does not fit leaves
 // d_dst untouched and its exact length known
-int update_box_whole(const UpdateBoxCall& u)
+// (boxes: SQYAMD_Update_Boxes_*' table, pasted layer by layer; nullptr: the one box of u)
+struct UpdateBoxesTable;
+int update_boxes_whole_paste(const UpdateBoxCall& u, const UpdateBoxesTable& t);
+int update_box_whole(const UpdateBoxCall& u, const UpdateBoxesTable* boxes = nullptr)
 {
     Context& cx = u.cx;
     hipStream_t stream = u.stream;
     if (cx.ws.range_full.ensure(std::max<uint64_t>(u.raw_bytes, 16))) return 1;
     if (const int rc = decode_on_device(cx, u.d_src, u.srclen, cx.ws.range_full.p, u.raw_bytes, u.elem, stream)) return rc;
-    {
+    if (boxes) {
+        if (const int rc = update_boxes_whole_paste(u, *boxes)) return rc;
+    } else {
         DrainOnExit drain{stream, &cx.pending, cx.side};
         WindowLaunch paste;
         paste.add(u.d_view, cx.ws.range_full.p, u.w, u.v, false);
@@ -4676,14 +4685,17 @@ int update_box_whole(const UpdateBoxCall& u)
 }
 
 // the subset path where sqy::update_box_path allows it; *taken = false: nothing was written, the caller takes the whole path
-int update_box_subset(const UpdateBoxCall& u, bool* taken)
+// ranges: the frames to decode (the box's z-range; SQYAMD_Update_Boxes_*: its segments); patch: stage 2, the box or boxes into the
+// compaction; option_on: the caller's option
+int update_box_subset(const UpdateBoxCall& u, bool option_on, const std::vector<std::pair<uint64_t, uint64_t>>& ranges, const std::function<int(DecodeCall&)>& patch,
+                      bool* taken)
 {
     *taken = false;
     Context& cx = u.cx;
     hipStream_t stream = u.stream;
     const uint64_t n = u.raw_bytes / (uint64_t)u.elem;
     sqy::UpdateBoxFacts facts;
-    facts.option_on = g_opt.update_box_subset.load() != 0;
+    facts.option_on = option_on;
     Pipeline held = Pipeline::from_string(u.h.pipename, u.elem);
     facts.same_stages = sqy::pipelines_same_stages(u.pipe, held);
     facts.form_ok = sqy::update_box_form_ok(u.pipe);
@@ -4694,11 +4706,13 @@ int update_box_subset(const UpdateBoxCall& u, bool* taken)
     if (sqy::update_box_path(facts) != sqy::UpdateBoxPath::subset_patch) return 0;
 
     DrainOnExit drain{stream, &cx.pending, cx.side};
-    WindowLaunch l;                                                     // (waits for the stream before its tables go)
     DecodeCall c(cx, stream, nullptr, u.h, std::move(held), n, u.d_src + u.h.size);
-    // 1. the frame index and the frames of the box's z-range, each a whole chunk of the compaction
+    // 1. the frame index and the frames of the ranges, each a whole chunk of the compaction (range_plan: the first range's, and the
+    // frames and offsets of all of them)
     bool subset = false;
-    if (const int rc = c.frames_subset(u.z0, u.nz, false, &subset)) return rc;
+    if (const int rc = c.frames_subset(ranges, false, &subset)) return rc;
+    if (subset) c.range_plan = sqy::frame_range_plan_of(c.ranges_plan, 0);
+    c.range_plan.direct = false;
     facts.subset_taken = subset && (c.range_form == sqy::RangeForm::plain || c.range_form == sqy::RangeForm::planes);
     facts.frames = c.range_ix.hc[0]; facts.blocks = c.range_ix.hc[1]; facts.frame_chunk = c.range_ix.chunk;
     if (sqy::update_box_path(facts) != sqy::UpdateBoxPath::subset_patch) return 0;      // (a subset decode already launched is drained; the whole path decides)
@@ -4716,7 +4730,7 @@ int update_box_subset(const UpdateBoxCall& u, bool* taken)
     std::memcpy(T.host.data() + T.text_at + prefix.size(), suffix.data(), suffix.size());
     *taken = true;
     // 2. the box into the compaction
-    if (const int rc = update_box_patch(c, u, l)) return rc;
+    if (const int rc = patch(c)) return rc;
     // 3. the selected chunks parsed again; the old frames' verdict
     if (const int rc = update_box_parse(c, T, chunk, stride)) return rc;
     // 4., 5. the splice and its record
@@ -4769,8 +4783,264 @@ int update_box_device(const char* pipeline, const void* d_src, long srclength, c
     const WindowView v = window_view(w, view_strides, rank);
     const UpdateBoxCall u{cx, stream, pipeline, pipe, src, (uint64_t)srclength, h, raw_bytes, w, v, (uint64_t)origin[0], (uint64_t)view_shape[0], rank, d_view, elem_size, d_dst, (uint64_t)dst_capacity, dstlength, nthreads};
     bool taken = false;
-    if (const int rc = update_box_subset(u, &taken)) return rc;
+    WindowLaunch l;                                                     // (waits for the stream before its tables go)
+    if (const int rc = update_box_subset(u, g_opt.update_box_subset.load() != 0, {{u.z0, u.nz}}, [&](DecodeCall& c) { return update_box_patch(c, u, l); }, &taken)) return rc;
     return taken ? 0 : update_box_whole(u);
+}
+
+// ---- many boxes written into one large blob (SQYAMD_Update_Boxes_*) --------------------------------------------------------------
+// SQYAMD_Update_Box_*'s stages for a table of boxes, each stage ONCE: one header fetch, one frame index, one frames_subset over the
+// SEGMENTS of sqy::update_boxes_plan (every LZ4 frame decoded once), one patch launch (bitswap1_range_patches_kernel; `lz4`: one window
+// paste per layer), one parse of all selected chunks with the old frames' verdict at its round trip, one splice.  The whole path: one
+// decode into Workspace::range_full, the pastes layer by layer, one single-call encode.  New blob = what a chain of SQYAMD_Update_Box_*
+// calls gives: box 0, then box 1, .. pasted in that order.
+struct UpdateBoxesTable {
+    std::vector<sqy::BatchWindow> ws;
+    std::vector<WindowView> vs;
+    const void* const* d_views = nullptr;
+    std::vector<std::pair<uint64_t, uint64_t>> ranges;                  // box i's range along the header's first dimension
+    sqy::UpdateBoxesPlan plan;                                          // (ok only where the subset path may run)
+    std::vector<uint32_t> layer_first;                                  // the layers of the paste launches, whichever path
+};
+// the device tables of bitswap1_range_patches_kernel in Workspace::boxes_jobs: segments | boxes | first workgroups; alive until the stream
+// has been waited for
+struct PatchTables {
+    std::vector<unsigned char> host;
+    hipStream_t queued_on = nullptr;
+    bool queued = false;
+    PatchTables() = default;
+    PatchTables(const PatchTables&) = delete;
+    PatchTables& operator=(const PatchTables&) = delete;
+    ~PatchTables() { if (queued) (void)hipStreamSynchronize(queued_on); }
+};
+
+// the whole path's pastes into Workspace::range_full, layer by layer in stream order
+int update_boxes_whole_paste(const UpdateBoxCall& u, const UpdateBoxesTable& t)
+{
+    Context& cx = u.cx;
+    DrainOnExit drain{u.stream, &cx.pending, cx.side};
+    for (size_t l = 0; l + 1 < t.layer_first.size(); ++l) {
+        WindowLaunch paste;
+        for (uint32_t i = t.layer_first[l]; i < t.layer_first[l + 1]; ++i) paste.add(t.d_views[i], cx.ws.range_full.p, t.ws[i], t.vs[i], false);
+        if (launch_windows(cx, u.stream, paste, WindowLaunch::paste, u.elem)) return 1;
+        paste.wait();                                                   // (the next layer's table goes to the same buffer)
+    }
+    return 0;
+}
+
+// subset path, stage 2 for a table of boxes: ONE launch of the patch kernel over the plan's segments, or (plain) one paste per layer
+int update_boxes_patch(DecodeCall& c, const UpdateBoxCall& u, const UpdateBoxesTable& t, PatchTables& pt)
+{
+    hipStream_t stream = c.stream;
+    std::vector<PendingEvent>* pend = c.pend;
+    const sqy::FrameRangesPlan& p = c.ranges_plan;
+    const std::vector<sqy::UpdateBoxesSegment>& segs = t.plan.segments;
+    if (p.boxes.size() != segs.size()) { std::fprintf(stderr, "[sqeazy]\t internal error: update boxes: the frame plan does not hold the segments\n"); return 1; }
+    if (c.range_form == sqy::RangeForm::planes) {
+        const uint32_t wpt = 128u / (8u * (uint32_t)p.we), nsegs = (uint32_t)segs.size(), nboxes = (uint32_t)t.ws.size();
+        const uint64_t boxes_at = (uint64_t)nsegs * sizeof(sqy::Bitswap1PatchSegment), tiles_at = boxes_at + (uint64_t)nboxes * sizeof(sqy::Bitswap1PatchBox);
+        pt.host.assign(tiles_at + ((uint64_t)nsegs + 1) * 4, 0);
+        sqy::Bitswap1PatchSegment* hs = reinterpret_cast<sqy::Bitswap1PatchSegment*>(pt.host.data());
+        sqy::Bitswap1PatchBox* hb = reinterpret_cast<sqy::Bitswap1PatchBox*>(pt.host.data() + boxes_at);
+        uint32_t* ht = reinterpret_cast<uint32_t*>(pt.host.data() + tiles_at);
+        uint64_t groups = 0;
+        uint32_t named = 0;
+        for (uint32_t s = 0; s < nsegs; ++s) {
+            const sqy::FrameRangesBox& b = p.boxes[s];
+            std::copy(b.plane, b.plane + 16, hs[s].r.plane);
+            hs[s].r.tail = b.tail; hs[s].r.w0 = b.w0; hs[s].r.w1 = b.w1; hs[s].r.v0 = b.v0; hs[s].r.v1 = b.v1; hs[s].r.L = b.L;
+            hs[s].t0 = sqy::range_first_thread(b.w0, wpt);
+            hs[s].box0 = named;
+            hs[s].nbox = (uint32_t)segs[s].boxes.size();
+            for (uint32_t i : segs[s].boxes) {
+                const sqy::BatchWindow& w = t.ws[i];
+                hb[named].view = t.d_views[i];
+                hb[named].g = sqy::WindowGeometry{w.bY, w.bX, w.oz, w.oy, w.ox, w.Z, w.Y, w.X, t.vs[i].sz, t.vs[i].sy};
+                ++named;
+            }
+            ht[s] = (uint32_t)groups;
+            groups += sqy::range_job_groups(b.w0, b.w1, wpt);
+            if (groups > 0x7fffffffull) { std::fprintf(stderr, "[sqeazy]\t update boxes: too many workgroups for one launch\n"); return 1; }
+        }
+        ht[nsegs] = (uint32_t)groups;
+        if (!sqy::bitswap1_patch_tables_ok(hs, nsegs, hb, nboxes, p.we)) { std::fprintf(stderr, "[sqeazy]\t internal error: the segments do not hold the boxes\n"); return 1; }
+        if (c.cx.ws.boxes_jobs.ensure(pt.host.size())) return 1;
+        uint8_t* d_tab = static_cast<uint8_t*>(c.cx.ws.boxes_jobs.p);
+        pt.queued_on = stream;
+        pt.queued = true;
+        SQY_HIP(hipMemcpyAsync(d_tab, pt.host.data(), pt.host.size(), hipMemcpyHostToDevice, stream));
+        SQY_TIMED("bitswap1_range_patches",
+                  sqy::launch_bitswap1_range_patches(c.range_buf, reinterpret_cast<const sqy::Bitswap1PatchSegment*>(d_tab),
+                                                     reinterpret_cast<const sqy::Bitswap1PatchBox*>(d_tab + boxes_at), reinterpret_cast<const uint32_t*>(d_tab + tiles_at), nsegs,
+                                                     (uint32_t)groups, p.we, stream));
+        return 0;
+    }
+    // plain: a segment's range in the workspace is a blob of its frames (box_range_out's rule); one launch per layer, in stream order
+    std::vector<uint32_t> seg_of(t.ws.size(), 0);
+    for (size_t s = 0; s < segs.size(); ++s) for (uint32_t i : segs[s].boxes) seg_of[i] = (uint32_t)s;
+    for (size_t l = 0; l + 1 < t.layer_first.size(); ++l) {
+        WindowLaunch paste;
+        for (uint32_t i = t.layer_first[l]; i < t.layer_first[l + 1]; ++i) {
+            const sqy::UpdateBoxesSegment& sg = segs[seg_of[i]];
+            sqy::BatchWindow in_range = t.ws[i];
+            if (u.rank == 3) { in_range.bZ = sg.nz; in_range.oz -= sg.z0; }
+            else if (u.rank == 2) { in_range.bY = sg.nz; in_range.oy -= sg.z0; }
+            else { in_range.bX = sg.nz; in_range.ox -= sg.z0; }
+            paste.add(t.d_views[i], c.range_buf + p.boxes[seg_of[i]].range_at, in_range, t.vs[i], false);
+        }
+        const uint32_t* d_tiles = nullptr;
+        if (paste.upload(stream, c.cx.ws.boxes_jobs, &d_tiles)) return 1;
+        SQY_TIMED("boxes_window_paste", sqy::launch_batch_window_paste(static_cast<const sqy::BatchWindowJob*>(c.cx.ws.boxes_jobs.p), d_tiles, (uint32_t)paste.jobs.size(),
+                                                                       paste.ntiles, u.elem, stream));
+        paste.wait();                                                   // (the next layer's table goes to the same buffer)
+    }
+    return 0;
+}
+
+// Box i = [origins + i rank, .. + view_shapes + i rank) of the old blob replaced by the view at d_views[i].  What needs the header: the
+// voxel type, the rank and every box, the single call's refusals for the blob's shape under `pipeline`, the launches' sizes -- all
+// before a byte is written
+int update_boxes_on_device(Context& cx, const char* pipeline, const Pipeline& pipe, const void* d_src, uint64_t srclen, size_t count, const long* origins,
+                           const void* const* d_views, const long* view_shapes, const long* view_strides, unsigned rank, int elem_size, void* d_dst, uint64_t capacity,
+                           long* dstlength, int nthreads, hipStream_t stream)
+{
+    const uint8_t* src = static_cast<const uint8_t*>(d_src);
+    sqy::HeaderInfo h;
+    uint64_t raw_bytes = 0;
+    UpdateBoxesTable t;
+    t.ws.resize(count); t.vs.resize(count); t.ranges.resize(count);
+    t.d_views = d_views;
+    Pipeline admitted = pipe;
+    {
+        DrainOnExit drain{stream, &cx.pending, cx.side};
+        if (fetch_header(src, srclen, stream, h)) return 1;
+        if (!admit_blob(h, srclen, elem_size, &raw_bytes)) return 1;
+        const uint64_t frame_voxels = raw_bytes / (uint64_t)elem_size / h.shape[0];
+        uint64_t paste_tiles = 0, range_groups = 0;          // what one launch may hold, whichever it is
+        for (size_t i = 0; i < count; ++i) {
+            const long* o = origins + i * rank;
+            const long* e = view_shapes + i * rank;
+            if (!sqy::admit_window(h.shape, o, e, rank, &t.ws[i])) {
+                std::fprintf(stderr, "[sqeazy]\t update boxes: box %zu does not lie inside the blob's shape, or has another rank\n", i);
+                return 1;
+            }
+            t.vs[i] = window_view(t.ws[i], view_strides ? view_strides + i * rank : nullptr, rank);
+            t.ranges[i] = {(uint64_t)o[0], (uint64_t)e[0]};
+            paste_tiles += sqy::batch_bitswap1_tiles(t.ws[i].Z * t.ws[i].Y * t.ws[i].X);
+            range_groups += (uint64_t)e[0] * frame_voxels / sqy::kBatchTileVoxels + 2;      // (at least range_job_groups of the box's words)
+        }
+        if (std::max(paste_tiles, range_groups) > 0x7fffffffull) {
+            std::fprintf(stderr, "[sqeazy]\t update boxes: too many workgroups for one launch\n");
+            return 1;
+        }
+        std::vector<long> shape(h.shape.begin(), h.shape.end());
+        std::vector<uint64_t> dims;
+        uint64_t len = 0;
+        if (admit_shape(&admitted, shape.data(), rank, &dims, &len)) return 1;
+    }
+    t.layer_first = sqy::update_boxes_layers(t.ws);
+    const UpdateBoxCall u{cx, stream, pipeline, admitted, src, srclen, h, raw_bytes, t.ws[0], t.vs[0], t.ranges[0].first, t.ranges[0].second, rank, d_views[0], elem_size, d_dst,
+                          capacity, dstlength, nthreads};
+    bool taken = false;
+    const bool option_on = g_opt.update_boxes_subset.load() != 0;
+    if (option_on && sqy::update_box_form_ok(admitted)) {
+        t.plan = sqy::update_boxes_plan(admitted.stages.size() == 1 ? sqy::RangeForm::plain : sqy::RangeForm::planes, raw_bytes / (uint64_t)elem_size, elem_size, h.shape[0],
+                                        t.ranges, t.ws);
+        if (!t.plan.ok) { std::fprintf(stderr, "[sqeazy]\t internal error: update boxes: no plan\n"); return 1; }
+        std::vector<std::pair<uint64_t, uint64_t>> segments;
+        for (const sqy::UpdateBoxesSegment& s : t.plan.segments) segments.push_back({s.z0, s.nz});
+        PatchTables pt;                                                 // (waits for the stream before its tables go)
+        if (const int rc = update_box_subset(u, option_on, segments, [&](DecodeCall& c) { return update_boxes_patch(c, u, t, pt); }, &taken)) return rc;
+    }
+    return taken ? 0 : update_box_whole(u, &t);
+}
+
+// what needs no header, before a device is looked for: the arguments, the pipeline, the view rules
+int update_boxes_admit(const char* who, const char* pipeline, const void* src, long srclength, long count, const long* origins, const void* const* views, const long* extents,
+                       unsigned rank, const void* dst, long dst_capacity, long* dstlength, int elem_size, int nthreads, Pipeline* pipe)
+{
+    if (!dstlength) return 1;
+    *dstlength = 0;
+    if (!pipeline || !dst || dst_capacity <= 0 || !boxes_arguments_ok(src, srclength, count, origins, views, extents, rank)) {
+        std::fprintf(stderr, "[sqeazy]\t %s: bad arguments\n", who);
+        return 1;
+    }
+    return admit_pipeline(pipeline, elem_size, nthreads, pipe);
+}
+
+int update_boxes_device(const char* pipeline, const void* d_src, long srclength, long count, const long* origins, const void* const* d_views, const long* view_shapes,
+                        const long* view_strides, unsigned rank, int elem_size, void* d_dst, long dst_capacity, long* dstlength, int nthreads, void* hip_stream)
+{
+    Pipeline pipe;
+    if (!d_views) { if (dstlength) *dstlength = 0; std::fprintf(stderr, "[sqeazy]\t update boxes: bad arguments\n"); return 1; }
+    if (update_boxes_admit("update boxes", pipeline, d_src, srclength, count, origins, d_views, view_shapes, rank, d_dst, dst_capacity, dstlength, elem_size, nthreads, &pipe)) return 1;
+    std::vector<sqy::BatchView> views;
+    if (admit_views("update boxes", d_views, view_shapes, view_strides, rank, (int)count, elem_size, &views)) return 1;
+    ContextLease lease;
+    if (!lease.ctx) { std::fprintf(stderr, "[sqeazy]\t no usable HIP device\n"); return 1; }
+    return update_boxes_on_device(*lease.ctx, pipeline, pipe, d_src, (uint64_t)srclength, (size_t)count, origins, d_views, view_shapes, view_strides, rank, elem_size, d_dst,
+                                  (uint64_t)dst_capacity, dstlength, nthreads, static_cast<hipStream_t>(hip_stream));
+}
+
+// host pointers: the header and every box are checked here, before anything is staged; views: the boxes' new voxels dense, back to back
+// in box order, exactly views_bytes of them.  The blob and the views are staged once, the new blob comes back
+int update_boxes_from_host(const char* pipeline, const char* src, long srclength, long count, const long* origins, const long* extents, unsigned rank, const char* views,
+                           long views_bytes, char* dst, long dst_capacity, long* dstlength, int elem_size, int nthreads)
+{
+    Pipeline pipe;
+    if (!views) { if (dstlength) *dstlength = 0; std::fprintf(stderr, "[sqeazy]\t update boxes: bad arguments\n"); return 1; }
+    if (update_boxes_admit("update boxes", pipeline, src, srclength, count, origins, nullptr, extents, rank, dst, dst_capacity, dstlength, elem_size, nthreads, &pipe)) return 1;
+    // (without a header: every extent positive, the views' bytes their sum; a product that does not fit 63 bits is no such sum)
+    uint64_t sum = 0;
+    for (long i = 0; i < count; ++i) {
+        uint64_t vox = 1;
+        for (unsigned k = 0; k < rank; ++k) {
+            const long e = extents[(size_t)i * rank + k];
+            if (e <= 0 || vox > (uint64_t)LONG_MAX / (uint64_t)e) { std::fprintf(stderr, "[sqeazy]\t update boxes: box %ld has no such extent\n", i); return 1; }
+            vox *= (uint64_t)e;
+        }
+        if (vox > ((uint64_t)LONG_MAX - sum) / (uint64_t)elem_size) { sum = (uint64_t)LONG_MAX; break; }
+        sum += vox * (uint64_t)elem_size;
+    }
+    if (views_bytes < 0 || sum != (uint64_t)views_bytes) { std::fprintf(stderr, "[sqeazy]\t update boxes: the views hold another number of bytes than the boxes\n"); return 1; }
+    const sqy::HeaderInfo h = sqy::header_unpack(src, src + srclength);
+    if (!h.valid) { std::fprintf(stderr, "[sqeazy]\t unable to find a sqy header in the blob\n"); return 1; }
+    uint64_t raw = 0;
+    if (!header_shape_ok(h, (uint64_t)srclength, &raw)) return 1;
+    if (h.elem_size() != elem_size) { std::fprintf(stderr, "[sqeazy]\t blob holds %s voxels\n", h.type.c_str()); return 1; }
+    std::vector<uint64_t> at((size_t)count + 1, 0);
+    for (long i = 0; i < count; ++i) {
+        sqy::BatchWindow w;
+        if (!sqy::admit_window(h.shape, origins + (size_t)i * rank, extents + (size_t)i * rank, rank, &w)) {
+            std::fprintf(stderr, "[sqeazy]\t update boxes: box %ld does not lie inside the blob's shape\n", i);
+            return 1;
+        }
+        at[(size_t)i + 1] = at[(size_t)i] + w.Z * w.Y * w.X * (uint64_t)elem_size;
+    }
+    if (!device_present()) { std::fprintf(stderr, "[sqeazy]\t no MI355X (HIP device) visible: sqeazy_amd has no CPU path\n"); return 1; }
+    ContextLease lease;
+    if (!lease.ctx) { std::fprintf(stderr, "[sqeazy]\t no usable HIP device\n"); return 1; }
+    Context& cx = *lease.ctx;
+    hipStream_t stream = cx.own_stream();
+    if (!stream) { std::fprintf(stderr, "[sqeazy]\t no HIP stream\n"); return 1; }
+    // the blob and, on the 16-byte grid behind it, the views in one staging buffer; the destination no larger than a blob can get
+    const uint64_t views_at = ((uint64_t)srclength + 15) & ~(uint64_t)15;
+    const uint64_t room = std::min<uint64_t>((uint64_t)dst_capacity, std::max(Pipeline::from_string(pipeline, elem_size).max_encoded_size(raw, elem_size), pipe.max_encoded_size(raw, elem_size)));
+    if (cx.ws.io_src.ensure(std::max<uint64_t>(views_at + at.back(), 16)) || cx.ws.io_dst.ensure(std::max<uint64_t>(room, 16))) return 1;
+    int dev_id = 0;
+    SQY_HIP(hipGetDevice(&dev_id));
+    uint8_t* d_io = static_cast<uint8_t*>(cx.ws.io_src.p);
+    if (!cx.stager.copy(d_io, const_cast<char*>(src), (size_t)srclength, true, dev_id) || !cx.stager.copy(d_io + views_at, const_cast<char*>(views), (size_t)at.back(), true, dev_id)) {
+        std::fprintf(stderr, "[sqeazy]\t host to device transfer failed\n");
+        return 1;
+    }
+    std::vector<const void*> ptrs((size_t)count);
+    for (long i = 0; i < count; ++i) ptrs[(size_t)i] = d_io + views_at + at[(size_t)i];
+    if (const int rc = update_boxes_on_device(cx, pipeline, pipe, d_io, (uint64_t)srclength, (size_t)count, origins, ptrs.data(), extents, nullptr, rank, elem_size,
+                                              cx.ws.io_dst.p, room, dstlength, nthreads, stream))
+        return rc;
+    if (!cx.stager.copy(cx.ws.io_dst.p, dst, (size_t)*dstlength, false, dev_id)) { *dstlength = 0; std::fprintf(stderr, "[sqeazy]\t device to host transfer failed\n"); return 1; }
+    return 0;
 }
 
 // the host-pointer variant (not tuned): every volume staged up, one call of the device driver, the blobs brought back
@@ -5538,6 +5808,36 @@ int SQYAMD_Update_Box_UI8_Device(const char* pipeline, const void* d_src, long s
     return guarded([&]() -> int {
         return update_box_device(pipeline, d_src, srclength, origin, d_view, view_shape, view_strides, rank, 1, d_dst, dst_capacity, dstlength, nthreads, hip_stream);
     });
+}
+
+int SQYAMD_Update_Boxes_UI16_Device(const char* pipeline, const void* d_src, long srclength, long count, const long* origins, const void* const* d_views,
+                                    const long* view_shapes, const long* view_strides, unsigned rank, void* d_dst, long dst_capacity, long* dstlength, int nthreads,
+                                    void* hip_stream)
+{
+    return guarded([&]() -> int {
+        return update_boxes_device(pipeline, d_src, srclength, count, origins, d_views, view_shapes, view_strides, rank, 2, d_dst, dst_capacity, dstlength, nthreads, hip_stream);
+    });
+}
+
+int SQYAMD_Update_Boxes_UI8_Device(const char* pipeline, const void* d_src, long srclength, long count, const long* origins, const void* const* d_views,
+                                   const long* view_shapes, const long* view_strides, unsigned rank, void* d_dst, long dst_capacity, long* dstlength, int nthreads,
+                                   void* hip_stream)
+{
+    return guarded([&]() -> int {
+        return update_boxes_device(pipeline, d_src, srclength, count, origins, d_views, view_shapes, view_strides, rank, 1, d_dst, dst_capacity, dstlength, nthreads, hip_stream);
+    });
+}
+
+int SQYAMD_Update_Boxes_UI16(const char* pipeline, const char* src, long srclength, long count, const long* origins, const long* extents, unsigned rank, const char* views,
+                             long views_bytes, char* dst, long dst_capacity, long* dstlength, int nthreads)
+{
+    return guarded([&]() -> int { return update_boxes_from_host(pipeline, src, srclength, count, origins, extents, rank, views, views_bytes, dst, dst_capacity, dstlength, 2, nthreads); });
+}
+
+int SQYAMD_Update_Boxes_UI8(const char* pipeline, const char* src, long srclength, long count, const long* origins, const long* extents, unsigned rank, const char* views,
+                            long views_bytes, char* dst, long dst_capacity, long* dstlength, int nthreads)
+{
+    return guarded([&]() -> int { return update_boxes_from_host(pipeline, src, srclength, count, origins, extents, rank, views, views_bytes, dst, dst_capacity, dstlength, 1, nthreads); });
 }
 
 int SQYAMD_Decode_Batch_UI16(const char* src, const long* offsets, const long* lengths, int nblobs, char* const* dsts, const long* dst_capacities, long* decoded_bytes)

@@ -454,6 +454,28 @@ hipError_t launch_bitswap1_decode_range_windows_compare(const uint8_t* in, const
 // 128-voxel run, and only where the box has a voxel in them; nothing else of buf and nothing of the view is written.
 bool bitswap1_range_patch_ok(const Bitswap1Range& r, const BatchWindowJob& box, int elem_size);
 hipError_t launch_bitswap1_range_patch(uint8_t* buf, const Bitswap1Range& r, const BatchWindowJob& box, int elem_size, hipStream_t stream);
+// ---- many boxes written into one large blob (SQYAMD_Update_Boxes_*) ----
+// launch_bitswap1_range_patch for a table of SEGMENTS (sqy::update_boxes_plan: no plane word and no tail voxel belongs to two of them)
+// in ONE launch.  Segment s has its range r inside the one compaction at buf, t0 = sqy::range_first_thread(r.w0, words per thread) and
+// the boxes d_boxes[box0 .. box0 + nbox) in ascending box order, every one inside the range (bitswap1_patch_tables_ok; refused
+// otherwise).  d_first_tile: nsegs + 1 words, the prefix sums of sqy::range_job_groups(r.w0, r.w1, words per thread); ngroups their sum.
+// A thread owns the words of its 128-voxel run as in the single-box kernel and walks its segment's boxes in that order, a later box
+// over an earlier one, so every word is read and written by one thread: boxes that overlap, and disjoint boxes that share a word, need
+// no atomics and no second launch.  Nothing else of buf and nothing of the views is written.
+struct Bitswap1PatchSegment {
+    Bitswap1Range r;
+    uint64_t t0;
+    uint32_t box0, nbox;
+};
+struct Bitswap1PatchBox {
+    const void* view;
+    WindowGeometry g;
+    uint64_t pad;
+};
+constexpr uint64_t kBitswap1PatchSegmentBytes = 192, kBitswap1PatchBoxBytes = 96;       // (multiples of 16: the tables behind one another stay on the 16-byte grid)
+bool bitswap1_patch_tables_ok(const Bitswap1PatchSegment* segs, uint32_t nsegs, const Bitswap1PatchBox* boxes, uint32_t nboxes, int elem_size);
+hipError_t launch_bitswap1_range_patches(uint8_t* buf, const Bitswap1PatchSegment* d_segs, const Bitswap1PatchBox* d_boxes, const uint32_t* d_first_tile, uint32_t nsegs,
+                                         uint32_t ngroups, int elem_size, hipStream_t stream);
 // ---- batch decode (SQYAMD_Decode_Batch_*): the blobs of a group share one launch of every kernel ----
 // The inverse of launch_bitswap1_batch on the same tables: job j's planes + tail at `in` (16-byte aligned) become its `len` voxels at
 // `out` (any voxel-aligned address; sixteen-byte stores where it and the plane size allow, word by word where not).  first_tile: njobs + 1

@@ -9206,6 +9206,178 @@ hipError_t launch_bitswap1_range_patch(uint8_t* buf, const Bitswap1Range& r, con
     return hipGetLastError();
 }
 
+// ---- many boxes written into one large blob (SQYAMD_Update_Boxes_*) --------------------------------------------------------------------------
+// window_gather16 for one piece on its own: the n voxels (n <= 16 / ELEM) of the blob's dense order that begin at the voxel with the
+// coordinates (z, y, x); those inside the window replace what d holds, the others stay -- a later box over an earlier one.  No division:
+// the clip begins where the caller stands.
+template <int ELEM>
+__device__ __forceinline__ void window_gather16_over(uint32_t (&d)[4], const uint8_t* __restrict__ view, const WindowGeometry& g, uint64_t z, uint64_t y, uint64_t x, uint32_t n)
+{
+    constexpr uint32_t G = 16 / ELEM, M = ELEM == 2 ? 0xffffu : 0xffu;
+    WindowClip c{z, y, x, 0, n};
+    WindowPiece cur;
+    while (window_clip_next(g, &c, &cur)) {
+        const uint32_t lo = (uint32_t)cur.run_off, hi = lo + (uint32_t)cur.len;
+        const uint8_t* q = view + cur.dst_off * ELEM;
+        if (lo == 0 && hi == G && (reinterpret_cast<uintptr_t>(q) & 15u) == 0) {
+            const uint4 r = *reinterpret_cast<const uint4*>(q);
+            d[0] = r.x; d[1] = r.y; d[2] = r.z; d[3] = r.w;
+        } else {
+#pragma unroll
+            for (uint32_t k = 0; k < G; ++k)
+                if (k >= lo && k < hi) {
+                    const uint32_t sh = 8u * ((k * ELEM) & 3u);
+                    d[k * ELEM / 4] = (d[k * ELEM / 4] & ~(M << sh)) | (view_voxel_load<ELEM>(view, cur.dst_off + (k - lo)) << sh);
+                }
+        }
+    }
+}
+
+// bitswap1_range_patch_kernel's merge, driven by a device table of segments and boxes.  The grid runs over the 128-voxel runs of all
+// segments; workgroups map to segments through the first-workgroup table (batch_job_of_tile), segment and boxes are uniform per
+// workgroup.  OWNERSHIP DECIDES THE ORDER: a thread owns its run's words exactly as in the single-box kernel (range_run against its
+// segment's [w0, w1)) and walks ITS SEGMENT'S BOXES IN ASCENDING INDEX -- first their clips against the run, which give the run's mask
+// (the boxes' masks or-ed) and which boxes touch it, before anything is loaded: a thread whose run no box touches loads and stores
+// nothing.  Then the merge in the voxel domain: for sixteen bytes of voxels at a time the touching boxes are walked, a later box writes
+// over an earlier one; ONE transpose; every plane stored as (old & ~mask) | new, sixteen bytes at a time where the single-box kernel
+// stores wide.  Every word is read and written by one thread only, and no two segments share a word or a tail voxel
+// (sqy::update_boxes_plan), so boxes that overlap and disjoint boxes that share a word need no atomics and no second launch.  A
+// segment's tail voxels are moved by its first workgroup, the last box that holds one winning.
+template <int ELEM>
+__global__ __launch_bounds__(256)
+void bitswap1_range_patches_kernel(uint8_t* __restrict__ buf, const Bitswap1PatchSegment* __restrict__ segs, const Bitswap1PatchBox* __restrict__ boxes,
+                                   const uint32_t* __restrict__ first_tile, uint32_t nsegs)
+{
+    constexpr uint32_t W = 8 * ELEM, WPT = BSWB_THREAD_VOX / W;        // voxels per word (= planes), words per thread
+    typedef typename std::conditional<ELEM == 2, uint16_t, uint8_t>::type word_t;
+    const uint32_t tid = threadIdx.x;
+    const uint32_t sj = batch_job_of_tile(first_tile, nsegs);
+    const Bitswap1PatchSegment* __restrict__ seg = segs + sj;
+    const uint32_t own = blockIdx.x - first_tile[sj];
+    const Bitswap1Range& a = seg->r;
+    const Bitswap1PatchBox* __restrict__ bx = boxes + seg->box0;
+    const uint32_t nbox = seg->nbox;
+    WindowPiece cur;
+    const uint64_t tail0 = a.v0 > a.L ? a.v0 : a.L;
+    if (own == 0 && tail0 + tid < a.v1) {                              // tail voxels: the last box that has this one
+        bool found = false;
+        uint32_t v = 0;
+        for (uint32_t k = 0; k < nbox; ++k) {
+            const WindowGeometry& g = bx[k].g;
+            WindowClip ct = window_clip_start(g, tail0 + tid, 1);
+            if (window_clip_next(g, &ct, &cur)) { v = view_voxel_load<ELEM>(static_cast<const uint8_t*>(bx[k].view), cur.dst_off); found = true; }
+        }
+        if (found) view_voxel_store<ELEM>(buf + a.tail, tid, v);
+    }
+    const RangeRun run = range_run(seg->t0 + (uint64_t)own * 256u + tid, WPT, a.w0, a.w1);
+    if (run.lo == run.hi) return;
+    // where the run begins in the blob (the rows are the same for every box), once
+    const WindowClip at0 = window_clip_start(bx[0].g, run.first * W, (uint64_t)run.hi * W);
+    uint32_t mask[4] = {0, 0, 0, 0};
+    uint64_t touch = 0;                                                // bit min(k, 63): box k has a voxel in the run
+    for (uint32_t k = 0; k < nbox; ++k) {
+        const WindowGeometry& g = bx[k].g;
+        WindowClip c = at0;
+        bool any = false;
+        while (window_clip_next(g, &c, &cur)) {
+            window_run_mask(W, (uint32_t)cur.run_off, (uint32_t)cur.len, mask);
+            any = true;
+        }
+        if (any) touch |= 1ull << (k < 63u ? k : 63u);
+    }
+    if (touch == 0) return;                                            // nothing of the run inside any box: no word is loaded or stored
+    const uint64_t at = (run.first - a.w0) * ELEM;                    // the thread's 16 bytes behind plane[s]
+    bool wide = run.lo == 0 && run.hi == WPT;
+    if (wide) {
+        uint32_t off_grid = 0;
+#pragma unroll
+        for (uint32_t s = 0; s < W; ++s) off_grid |= (uint32_t)(reinterpret_cast<uintptr_t>(buf) + a.plane[s] + at);
+        wide = (off_grid & 15u) == 0;
+    }
+    const bool all = (mask[0] & mask[1] & mask[2] & mask[3]) == 0xffffffffu;      // (then the thread owns all its words)
+    uint32_t res[W][4];                                               // res[b]: the thread's 16 bytes of the plane that carries bit b
+#pragma unroll
+    for (uint32_t b = 0; b < W; ++b) { res[b][0] = 0; res[b][1] = 0; res[b][2] = 0; res[b][3] = 0; }
+    const uint64_t bY = bx[0].g.bY, bX = bx[0].g.bX;
+    uint64_t z = at0.z, y = at0.y, x = at0.x;                          // the coordinates of voxel `pos` of the run
+    uint32_t pos = 0;
+    window_patch_transpose<ELEM>(res, run.hi, [&](uint32_t p, uint32_t n) {
+        x += p - pos;                                                  // (pieces come in ascending p)
+        pos = p;
+        while (x >= bX) {
+            x -= bX;
+            if (++y == bY) { y = 0; ++z; }
+        }
+        uint32_t d[4] = {0, 0, 0, 0};
+        for (uint32_t k = 0; k < nbox; ++k)
+            if ((touch >> (k < 63u ? k : 63u)) & 1u) window_gather16_over<ELEM>(d, static_cast<const uint8_t*>(bx[k].view), bx[k].g, z, y, x, n);
+        return make_uint4(d[0], d[1], d[2], d[3]);
+    });
+    if (wide) {
+#pragma unroll
+        for (uint32_t b = 0; b < W; ++b) {
+            uint8_t* q = buf + a.plane[W - 1 - b] + at;
+            uint4 r = make_uint4(res[b][0], res[b][1], res[b][2], res[b][3]);
+            if (!all) {
+                const uint4 o = *reinterpret_cast<const uint4*>(q);
+                r = make_uint4(window_merge_word(o.x, r.x, mask[0]), window_merge_word(o.y, r.y, mask[1]), window_merge_word(o.z, r.z, mask[2]),
+                               window_merge_word(o.w, r.w, mask[3]));
+            }
+            *reinterpret_cast<uint4*>(q) = r;
+        }
+    } else {
+        constexpr uint32_t PER = 4 / ELEM;                            // plane words in 32 bits
+#pragma unroll
+        for (uint32_t i = 0; i < WPT; ++i)
+            if (i >= run.lo && i < run.hi) {
+                const word_t m = (word_t)(mask[i / PER] >> (W * (i % PER)));
+                if (m == 0) continue;                                 // (no voxel of any box in this word)
+#pragma unroll
+                for (uint32_t b = 0; b < W; ++b) {
+                    word_t* q = reinterpret_cast<word_t*>(buf + a.plane[W - 1 - b] + at + (uint64_t)i * ELEM);
+                    const word_t r = (word_t)(res[b][i / PER] >> (W * (i % PER)));
+                    *q = window_merge_word(*q, r, m);
+                }
+            }
+    }
+}
+
+static_assert(sizeof(Bitswap1PatchSegment) == kBitswap1PatchSegmentBytes && sizeof(Bitswap1PatchBox) == kBitswap1PatchBoxBytes, "the patch tables' layout");
+
+bool bitswap1_patch_tables_ok(const Bitswap1PatchSegment* segs, uint32_t nsegs, const Bitswap1PatchBox* boxes, uint32_t nboxes, int elem_size)
+{
+    if (!segs || !boxes || nsegs == 0 || nboxes == 0 || (elem_size != 1 && elem_size != 2)) return false;
+    const uint32_t wpt = BSWB_THREAD_VOX / (8u * (uint32_t)elem_size);
+    uint64_t groups = 0, named = 0;
+    for (uint32_t s = 0; s < nsegs; ++s) {
+        const Bitswap1PatchSegment& sg = segs[s];
+        const Bitswap1Range& r = sg.r;
+        if (r.v1 <= r.v0 || r.w1 < r.w0 || sg.nbox == 0 || sg.box0 != named || sg.nbox > nboxes - sg.box0 || sg.t0 != range_first_thread(r.w0, wpt)) return false;
+        // ascending and disjoint: no word and no tail voxel in two segments
+        if (s && (r.v0 < segs[s - 1].r.v1 || r.w0 < segs[s - 1].r.w1)) return false;
+        for (uint32_t k = sg.box0; k < sg.box0 + sg.nbox; ++k) {
+            const WindowGeometry& g = boxes[k].g;
+            // the same rows for every box, and the range holds the box
+            if (!boxes[k].view || g.Z == 0 || g.Y == 0 || g.X == 0 || g.bY == 0 || g.bX == 0 || g.bY != boxes[0].g.bY || g.bX != boxes[0].g.bX || g.oy + g.Y > g.bY ||
+                g.ox + g.X > g.bX || ((g.oz * g.bY + g.oy) * g.bX + g.ox) < r.v0 || ((g.oz + g.Z - 1) * g.bY + g.oy + g.Y - 1) * g.bX + g.ox + g.X > r.v1)
+                return false;
+        }
+        named += sg.nbox;
+        groups += range_job_groups(r.w0, r.w1, wpt);
+    }
+    return named == nboxes && groups <= 0x7fffffffull;
+}
+
+hipError_t launch_bitswap1_range_patches(uint8_t* buf, const Bitswap1PatchSegment* d_segs, const Bitswap1PatchBox* d_boxes, const uint32_t* d_first_tile, uint32_t nsegs,
+                                         uint32_t ngroups, int elem_size, hipStream_t stream)
+{
+    if (!buf || !d_segs || !d_boxes || !d_first_tile || nsegs == 0 || ngroups < nsegs || ngroups > 0x7fffffffu || (elem_size != 1 && elem_size != 2)) return hipErrorInvalidValue;
+    const dim3 grid(ngroups);
+    if (elem_size == 2) hipLaunchKernelGGL(bitswap1_range_patches_kernel<2>, grid, dim3(256), 0, stream, buf, d_segs, d_boxes, d_first_tile, nsegs);
+    else hipLaunchKernelGGL(bitswap1_range_patches_kernel<1>, grid, dim3(256), 0, stream, buf, d_segs, d_boxes, d_first_tile, nsegs);
+    return hipGetLastError();
+}
+
 hipError_t launch_batch_window_copy(const BatchWindowJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ntiles, int elem_size, hipStream_t stream)
 {
     if (njobs == 0 || ntiles == 0) return hipSuccess;

@@ -927,6 +927,59 @@ bool update_box_form_ok(const Pipeline& p)
     return ns == 1 || p.stages[0].kind == StageKind::bitswap1;
 }
 
+// ---- many boxes written into one large blob (SQYAMD_Update_Boxes_*) ----
+UpdateBoxesPlan update_boxes_plan(RangeForm form, uint64_t n, int elem, uint64_t shape0, const std::vector<std::pair<uint64_t, uint64_t>>& ranges,
+                                  const std::vector<BatchWindow>& windows)
+{
+    UpdateBoxesPlan p;
+    if (shape0 == 0 || n == 0 || n % shape0 != 0 || ranges.empty() || ranges.size() > 0xffffffffull || windows.size() != ranges.size() || (elem != 1 && elem != 2) ||
+        (form != RangeForm::plain && form != RangeForm::planes))
+        return p;
+    for (const auto& r : ranges)
+        if (r.second == 0 || r.first >= shape0 || r.second > shape0 - r.first) return p;
+    const bool planes = form == RangeForm::planes;
+    const uint64_t vpf = n / shape0, W = 8 * (uint64_t)elem, seg = n / W, L = seg * W;
+    std::vector<uint32_t> order(ranges.size());
+    for (size_t i = 0; i < order.size(); ++i) order[i] = (uint32_t)i;
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return ranges[a].first != ranges[b].first ? ranges[a].first < ranges[b].first : a < b; });
+    uint64_t z1 = 0;                                                    // the open segment ends in front of frame z1
+    for (uint32_t i : order) {
+        const uint64_t a = ranges[i].first, b = a + ranges[i].second;
+        bool join = false;
+        if (!p.segments.empty()) {
+            // (ascending first frames: the open segment's last word is the one its last voxel lies in)
+            const uint64_t open_w1 = std::min((z1 * vpf + W - 1) / W, seg), w0 = std::min(a * vpf / W, seg);
+            if (a < z1) { join = true; ++(planes && a * vpf >= L ? p.merged_tail : p.merged_overlap); }
+            else if (a == z1) { join = true; ++p.merged_overlap; }
+            else if (planes && w0 < open_w1) { join = true; ++p.merged_word; }
+        }
+        if (!join) {
+            p.segments.push_back(UpdateBoxesSegment{a, 0, {}});
+            z1 = b;
+        }
+        UpdateBoxesSegment& s = p.segments.back();
+        z1 = std::max(z1, b);
+        s.nz = z1 - s.z0;
+        s.boxes.push_back(i);
+    }
+    for (UpdateBoxesSegment& s : p.segments) std::sort(s.boxes.begin(), s.boxes.end());
+    if (form == RangeForm::plain) p.layer_first = update_boxes_layers(windows);
+    p.ok = true;
+    return p;
+}
+
+std::vector<uint32_t> update_boxes_layers(const std::vector<BatchWindow>& windows)
+{
+    std::vector<uint32_t> first;
+    if (windows.empty()) return first;
+    first.push_back(0);
+    for (size_t i = 1; i < windows.size(); ++i)
+        for (size_t j = first.back(); j < i; ++j)
+            if (windows_overlap(windows[i], windows[j])) { first.push_back((uint32_t)i); break; }
+    first.push_back((uint32_t)windows.size());
+    return first;
+}
+
 bool lz4_splice_ok(const std::vector<uint32_t>& slot_of, size_t nselected)
 {
     if (slot_of.empty() || slot_of.size() > 0x7fffffffull || nselected > slot_of.size()) return false;

@@ -415,6 +415,38 @@ struct Pipeline;
 bool pipelines_same_stages(const Pipeline& a, const Pipeline& b);
 bool update_box_form_ok(const Pipeline& p);
 
+// ---- many boxes written into one large blob (SQYAMD_Update_Boxes_*) ----
+// update_box_path decides for the whole call (pipeline, header, layout and frame index are the same for every box).  The plan turns the
+// boxes' ranges (z0, nz) along the header's first dimension into SEGMENTS: ranges [z0, z0 + nz) of frames, ascending and pairwise
+// disjoint, each the hull of the ranges that went into it, with the indices of its boxes in ascending box order.  Two ranges go into
+// one segment when they overlap or abut, or (planes) when their plane-word intervals [w0, w1) intersect -- across a gap of frames where
+// a frame has fewer voxels than a plane word, or where a word straddles a frame boundary.  Ranges that share a tail voxel share a voxel,
+// so they overlap: that rule needs no test of its own, the plan only counts where the shared voxels were tail voxels alone.
+// THE INVARIANT (tests/sanitize/update_boxes_test.cpp checks it by brute force): no plane word, no tail voxel and no byte of the
+// stream in front of lz4 belongs to two segments.  So one thread of bitswap1_range_patches_kernel owns every word it writes, whatever
+// boxes meet in it, and the segments are the `ranges` of DecodeCall::frames_subset: FrameRangesPlan::boxes[s] is segment s's addressing.
+// plain: the box list is also cut into LAYERS, maximal runs of consecutive boxes [layer_first[l], layer_first[l + 1]) that are pairwise
+// voxel-disjoint; one paste launch per layer in stream order gives "the box with the higher index holds" (the cut costs the layer's
+// size squared in box comparisons; the usual call has one layer).  windows[i]: box i as admit_window gives it (its z-range is ranges[i]).
+enum class RangeForm;                       // (below: plain, planes, ..)
+struct UpdateBoxesSegment { uint64_t z0 = 0, nz = 0; std::vector<uint32_t> boxes; };
+struct UpdateBoxesPlan {
+    bool ok = false;                        // false: no box, ranges outside shape0 or a table of another length (nothing else is filled in)
+    std::vector<UpdateBoxesSegment> segments;
+    std::vector<uint32_t> layer_first;      // plain: nlayers + 1 entries
+    uint64_t merged_overlap = 0, merged_word = 0, merged_tail = 0;       // ranges joined to the one in front: overlapping or abutting |
+                                                                        // by a shared plane word alone | overlapping in tail voxels alone
+};
+UpdateBoxesPlan update_boxes_plan(RangeForm form, uint64_t n, int elem, uint64_t shape0, const std::vector<std::pair<uint64_t, uint64_t>>& ranges,
+                                  const std::vector<BatchWindow>& windows);
+// the layers alone, for any form (the whole path pastes by them too): nlayers + 1 entries, empty for no window
+std::vector<uint32_t> update_boxes_layers(const std::vector<BatchWindow>& windows);
+// two admitted windows of one blob share a voxel
+inline bool windows_overlap(const BatchWindow& a, const BatchWindow& b)
+{
+    return a.oz < b.oz + b.Z && b.oz < a.oz + a.Z && a.oy < b.oy + b.Y && b.oy < a.oy + a.Y && a.ox < b.ox + b.X && b.ox < a.ox + a.X;
+}
+
 // The block-parallel parse of block-linked frames (sqy_kernels.h: Lz4SpecArgs).  Worth it for few long frames: the frame walks would
 // leave the chip empty
 bool lz4_spec_wanted(const Lz4Plan& plan);
