@@ -465,6 +465,42 @@ SQY_FUNCTION_PREFIX int SQYAMD_Compare_Boxes_UI16(const char* src, long srclengt
                                                   const char* views, long views_bytes, unsigned long long* stats);
 SQY_FUNCTION_PREFIX int SQYAMD_Compare_Boxes_UI8(const char* src, long srclength, long count, const long* origins, const long* extents, unsigned rank,
                                                  const char* views, long views_bytes, unsigned long long* stats);
+/* The quick look at a stack stored as ONE blob: MANY boxes of one blob projected along an axis in one call -- maximum, minimum or sum --,
+ * the decoded voxels never stored.  Box i is [origins + i rank, .. + extents + i rank) of the volume SQYAMD_Decode_*_Device gives for the
+ * blob (count rows of `rank` longs each; ranks 1 to 3 mapped as by SQYAMD_Decode_Boxes_*: frames are the first dimension).  axis lies in
+ * [0, rank) and is the same for all boxes; op is one of SQYAMD_PROJECT_MAX, _MIN, _SUM.  Image i has the box's extent with `axis` removed
+ * -- rank - 1 dimensions, ONE element for rank 1 -- and its elements are uint32_t for every op and both voxel types: element (u, v) is the
+ * max, min or sum of the box's voxels along `axis`, exact (behind the quantiser's look-up: of the 16-bit voxels out of the table).  The
+ * mean is the caller's division.  d_outs[i] is 4-byte aligned; out_strides + i (rank - 1) gives image i's pitches in ELEMENTS under the
+ * view rules of SQYAMD_Decode_Boxes_*_Device (innermost 1, no dimension reaches into the next; NULL: every image dense).  Every element of
+ * every image is written and nothing else: not the gaps between pitched rows, not d_src.  Images that overlap each other are the caller's
+ * error.
+ * Checked before a byte is written (else 1, every image untouched): what SQYAMD_Decode_Boxes_* checks for every box; axis or op out of
+ * range; a NULL or misaligned image; the stride rules; more workgroups than one launch takes; and SQYAMD_PROJECT_SUM where the sum might
+ * not fit: maxvoxel x extent[axis] >= 2^32 with maxvoxel 255 for 8-bit voxels (extents up to 16843009 are taken), and for 16-bit voxels
+ * every extent above 65536.  Whatever needs no header is checked before a device is looked for.  A damaged LZ4 frame that SOME box's
+ * z-range needs gives SQY_Decode's composite code; the images may then hold anything, and nothing outside them is written.  A damaged
+ * frame that no box needs goes unnoticed.
+ * How: one header fetch, the LZ4 frames the boxes' z-ranges need united and decoded by one launch, ONE output launch -- for
+ * `bitswap1->lz4` and `quantiser->bitswap1->lz4` the range transposer of SQYAMD_Decode_Boxes_* with a 32-bit integer atomic on the image
+ * where it stores (the images get the op's neutral element by one small launch in front of it; along axis 0, where every frame is a
+ * whole number of 32-voxel runs, a thread walks z over the box's frames instead, reduces in registers and stores once:
+ * "project_boxes_walk"), for `lz4` and `frame_shuffle->lz4` one launch with a thread per image element in the compaction.  Every other blob is decoded whole ONCE into the workspace and the same
+ * per-element launch takes all boxes ("project_boxes_subset" = 0: every blob -- the same images).  Stream, context, ordering and thread
+ * safety as SQYAMD_Decode_Boxes_*_Device. */
+#define SQYAMD_PROJECT_MAX 0
+#define SQYAMD_PROJECT_MIN 1
+#define SQYAMD_PROJECT_SUM 2
+SQY_FUNCTION_PREFIX int SQYAMD_Project_Boxes_UI16_Device(const void* d_src, long srclength, long count, const long* origins, const long* extents, unsigned rank,
+                                                         int axis, int op, void* const* d_outs, const long* out_strides, void* hip_stream);
+SQY_FUNCTION_PREFIX int SQYAMD_Project_Boxes_UI8_Device(const void* d_src, long srclength, long count, const long* origins, const long* extents, unsigned rank,
+                                                        int axis, int op, void* const* d_outs, const long* out_strides, void* hip_stream);
+/* host-pointer variants: the blob is staged ONCE; the images come back dense and back to back in box order, as uint32_t (1 where
+ * out_capacity, in bytes, is too small) */
+SQY_FUNCTION_PREFIX int SQYAMD_Project_Boxes_UI16(const char* src, long srclength, long count, const long* origins, const long* extents, unsigned rank, int axis,
+                                                  int op, char* out, long out_capacity);
+SQY_FUNCTION_PREFIX int SQYAMD_Project_Boxes_UI8(const char* src, long srclength, long count, const long* origins, const long* extents, unsigned rank, int axis,
+                                                 int op, char* out, long out_capacity);
 /* The write of a box into a tiled store, whose border cuts through tiles: every tile under the box is read, modified and written again
  * with ONE call.  Old blob i lies at d_src + src_offsets[i], src_lengths[i] bytes (host arrays; any alignment): a complete sqeazy blob of
  * the entry point's voxel type, any pipeline, any layout.  Window i is the box [origins row i, + win_shapes row i) of that blob's volume
@@ -649,6 +685,12 @@ SQY_FUNCTION_PREFIX void SQYAMD_Release_Workspace(void);
  *                                     decoded whole once and one window compare -- same statistics)
  *   "update_boxes_subset"             1 [SQY_NO_UPDATE_BOXES_SUBSET=1 -> 0]  SQYAMD_Update_Boxes_*: SQYAMD_Update_Box_*'s subset path, every stage once for
  *                                     all boxes (0: the blob decoded whole once, the pastes layer by layer, the single call's encode -- same bytes)
+ *   "project_boxes_subset"            1 [SQY_NO_PROJECT_BOXES_SUBSET=1 -> 0]  SQYAMD_Project_Boxes_*: only the LZ4 frames the boxes' z-ranges need, the
+ *                                     projecting range transposer or one projection in the compaction, where the pipeline allows (0: every blob
+ *                                     decoded whole once and one projection launch -- same images)
+ *   "project_boxes_walk"              1 [SQY_NO_PROJECT_BOXES_WALK=1 -> 0]  SQYAMD_Project_Boxes_* along axis 0 on the transposer path: a thread walks z over
+ *                                     the box's frames, reduces in registers and stores once, where every box's frames are whole 32-voxel runs on the
+ *                                     4-byte grid (0: always the integer atomics -- same images)
  *   "decode_slabs_joint"              1 [SQY_NO_DECODE_SLABS_JOINT=1 -> 0]  SQYAMD_Decode_Slabs_*: the chunked LZ4 blobs of a group indexed and
  *                                     decoded by one launch each (0: every blob on its own, as by SQYAMD_Decode_*_Device -- same bytes)
  *   "decode_batch_joint"              1 [SQY_NO_DECODE_BATCH_JOINT=1 -> 0]  SQYAMD_Decode_Batch_*: the joint-eligible blobs of a group ranked, decoded and

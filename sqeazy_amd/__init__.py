@@ -42,6 +42,7 @@ EXPORTED_SYMBOLS = (
     "SQYAMD_Decode_Box_UI16_Device", "SQYAMD_Decode_Box_UI8_Device", "SQYAMD_Decode_Box_UI16", "SQYAMD_Decode_Box_UI8",
     "SQYAMD_Decode_Boxes_UI16_Device", "SQYAMD_Decode_Boxes_UI8_Device", "SQYAMD_Decode_Boxes_UI16", "SQYAMD_Decode_Boxes_UI8",
     "SQYAMD_Compare_Boxes_UI16_Device", "SQYAMD_Compare_Boxes_UI8_Device", "SQYAMD_Compare_Boxes_UI16", "SQYAMD_Compare_Boxes_UI8",
+    "SQYAMD_Project_Boxes_UI16_Device", "SQYAMD_Project_Boxes_UI8_Device", "SQYAMD_Project_Boxes_UI16", "SQYAMD_Project_Boxes_UI8",
     "SQYAMD_Decode_Slabs_UI16_Device", "SQYAMD_Decode_Slabs_UI8_Device", "SQYAMD_Decode_Slabs_UI16", "SQYAMD_Decode_Slabs_UI8",
     "SQYAMD_Decode_Batch_UI16_Device", "SQYAMD_Decode_Batch_UI8_Device", "SQYAMD_Decode_Batch_UI16", "SQYAMD_Decode_Batch_UI8",
     "SQYAMD_Profile_Enable", "SQYAMD_Profile_Reset", "SQYAMD_Profile_Get",
@@ -153,6 +154,12 @@ def lib():
         for f in ("SQYAMD_Compare_Boxes_UI8", "SQYAMD_Compare_Boxes_UI16"):
             getattr(L, f).argtypes = [ctypes.c_void_p, ctypes.c_long, ctypes.c_long, c_long_p, c_long_p, ctypes.c_uint, ctypes.c_void_p, ctypes.c_long,
                                       ctypes.POINTER(ctypes.c_ulonglong)]
+        for f in ("SQYAMD_Project_Boxes_UI8_Device", "SQYAMD_Project_Boxes_UI16_Device"):
+            getattr(L, f).argtypes = [ctypes.c_void_p, ctypes.c_long, ctypes.c_long, c_long_p, c_long_p, ctypes.c_uint, ctypes.c_int, ctypes.c_int,
+                                      ctypes.POINTER(ctypes.c_void_p), c_long_p, ctypes.c_void_p]
+        for f in ("SQYAMD_Project_Boxes_UI8", "SQYAMD_Project_Boxes_UI16"):
+            getattr(L, f).argtypes = [ctypes.c_void_p, ctypes.c_long, ctypes.c_long, c_long_p, c_long_p, ctypes.c_uint, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                      ctypes.c_long]
         for f in ("SQYAMD_Decode_Slabs_UI8_Device", "SQYAMD_Decode_Slabs_UI16_Device"):
             getattr(L, f).argtypes = [ctypes.c_void_p, c_long_p, c_long_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_long, c_long_p, ctypes.c_int,
                                       ctypes.c_void_p]
@@ -686,6 +693,59 @@ def compare_boxes(blob, origins, views):
         src.ctypes.data, ctypes.c_long(len(blob)), ctypes.c_long(n), _long_rows(origins), _long_rows([np.shape(v) for v in views]), ctypes.c_uint(np.ndim(views[0])),
         dense.ctypes.data, ctypes.c_long(dense.nbytes), stats.ctypes.data_as(ctypes.POINTER(ctypes.c_ulonglong)))
     return rc, stats
+
+
+PROJECT_MAX, PROJECT_MIN, PROJECT_SUM = 0, 1, 2
+_PROJECT_OPS = {"max": PROJECT_MAX, "min": PROJECT_MIN, "sum": PROJECT_SUM}
+
+
+def _project_op(op):
+    """the op as SQYAMD_PROJECT_*: a name ("max", "min", "sum") or the constant itself"""
+    return _PROJECT_OPS[op] if isinstance(op, str) else int(op)
+
+
+def project_boxes_device(d_src, srclength, origins, extents, axis, op, d_outs, out_strides, dtype, stream=None, count=None):
+    """SQYAMD_Project_Boxes_*_Device on raw device pointers (ints): box i of extent extents[i] that begins at voxel origins[i] of the ONE blob
+    at d_src, projected along `axis` with op ("max", "min", "sum" or PROJECT_*) into the uint32 image at d_outs[i], whose shape is the
+    extent with `axis` removed and whose pitches in elements are out_strides[i] (None: every image dense).  count: the number of boxes
+    (default: as many as there are extents).  Returns rc."""
+    n = len(extents) if extents is not None else len(origins or ())
+    first = (extents or origins or [()])[0] if n else ()
+    ptrs = None if d_outs is None else (ctypes.c_void_p * max(len(d_outs), 1))(*[None if p is None else int(p) for p in d_outs])
+    strides = None if out_strides is None or len(first) < 2 else _long_rows(out_strides)
+    return getattr(lib(), "SQYAMD_Project_Boxes_%s_Device" % _suffix(dtype))(
+        ctypes.c_void_p(None if d_src is None else int(d_src)), ctypes.c_long(int(srclength)), ctypes.c_long(n if count is None else int(count)), _long_rows(origins),
+        _long_rows(extents), ctypes.c_uint(len(first)), ctypes.c_int(int(axis)), ctypes.c_int(_project_op(op)), ptrs, strides, ctypes.c_void_p(stream or 0))
+
+
+def project_boxes(blob, origins, extents, axis, op="max"):
+    """SQYAMD_Project_Boxes_UI8/UI16: the boxes [origins[i], origins[i] + extents[i]) of the blob's volume projected along `axis` with one
+    call; op "max", "min", "sum" (or PROJECT_*) gives uint32 images, "mean" the sum divided by extents[i][axis] in float64.  Returns
+    (rc, [ndarray of the extent with `axis` removed, ..] or None)."""
+    blob = bytes(blob)
+    size = decompressed_sizeof(blob)
+    if size not in (1, 2) or not decompressed_shape(blob) or len(origins) != len(extents) or not len(extents):
+        return 1, None
+    mean = op == "mean"
+    code = PROJECT_SUM if mean else _project_op(op)
+    dtype = np.uint16 if size == 2 else np.uint8
+    rank = len(extents[0])
+    if not 0 <= int(axis) < rank:
+        return 1, None
+    shapes = [tuple(max(int(e), 0) for k, e in enumerate(ext) if k != int(axis)) for ext in extents]
+    counts = [int(np.prod(sh, dtype=np.int64)) for sh in shapes]
+    out = np.empty(sum(counts), dtype=np.uint32)
+    src = np.frombuffer(blob, dtype=np.uint8)
+    rc = getattr(lib(), "SQYAMD_Project_Boxes_" + _suffix(dtype))(src.ctypes.data, ctypes.c_long(len(blob)), ctypes.c_long(len(extents)), _long_rows(origins),
+                                                                  _long_rows(extents), ctypes.c_uint(rank), ctypes.c_int(int(axis)), ctypes.c_int(code),
+                                                                  out.ctypes.data, ctypes.c_long(out.nbytes))
+    if rc:
+        return rc, None
+    ends = np.cumsum(counts)
+    images = [out[e - c:e].reshape(sh) for e, c, sh in zip(ends, counts, shapes)]
+    if mean:
+        images = [im.astype(np.float64) / np.float64(int(ext[int(axis)])) for im, ext in zip(images, extents)]
+    return 0, images
 
 
 def update_batch_window_device(pipeline, d_src, offsets, lengths, origins, d_wins, shapes, strides, dtype, d_dst, slot_capacity, nthreads=0, stream=None):

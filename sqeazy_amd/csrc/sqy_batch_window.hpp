@@ -9,6 +9,8 @@
 // Behind the clip: the mask and the merge of a window's update in the bit-plane layout (SQYAMD_Update_BatchWindow_*), and the sums of a
 // window's compare with a view (SQYAMD_Compare_BatchWindow_*; tests/sanitize/batch_compare_test.cpp holds them against a triple loop;
 // SQYAMD_Compare_Boxes_* gathers the same sums over the range transposer's runs: tests/sanitize/compare_boxes_test.cpp).
+// And the projection of a box along an axis (SQYAMD_Project_Boxes_*): a combine into an image where the scatter stores
+// (tests/sanitize/project_boxes_test.cpp).
 #ifndef SQY_BATCH_WINDOW_HPP_
 #define SQY_BATCH_WINDOW_HPP_
 
@@ -227,6 +229,59 @@ SQY_VIEW_HD inline void window_compare16(const uint8_t* view, const WindowGeomet
         }
         compare_piece<ELEM>(s, a, b, lo, hi);
         if (end > (uint64_t)p + n) break;                             // the sub-run goes on in the next piece
+        have = window_clip_next(g, &c, &cur);
+    }
+}
+
+// ---- the projection of a box along an axis (SQYAMD_Project_Boxes_*) ----
+// The range transposer's scatter with a combine where its stores were: every decoded voxel of the box is combined -- max, min or sum in
+// 32 unsigned bits -- into the element of the output image that its place with the projected axis removed names.  The clip computes that
+// element: the job's WindowGeometry is filled (sqy::admit_projection) so that dst_off drops the projected axis --
+//   axis 0 (frames):  sz = 0, sy = the image's row pitch:   element = cur.dst_off + (p + k - cur.run_off)
+//   axis 1 (rows):    sy = 0, sz = the image's row pitch:   the same expression
+//   axis 2 (columns): sy = K, sz = K x the image's row pitch, K the power of two >= X: a sub-run lies within one row of the box, so ALL
+//                     its voxels go to the one element cur.dst_off >> log2(K) (the bits below hold x - ox); the thread reduces them
+//                     itself and sends ONE combine per sub-run -- rows longer than a thread's 128 voxels and rows that straddle two
+//                     threads' runs meet in the sink.
+// tests/sanitize/project_boxes_test.cpp holds it against a triple loop with an array for the sink.
+constexpr uint32_t kProjectMax = 0, kProjectMin = 1, kProjectSum = 2, kProjectOps = 3;
+
+SQY_VIEW_HD inline uint32_t project_neutral(uint32_t op) { return op == kProjectMin ? 0xffffffffu : 0u; }
+SQY_VIEW_HD inline uint32_t project_combine(uint32_t op, uint32_t a, uint32_t b)
+{
+    return op == kProjectMax ? (a > b ? a : b) : op == kProjectMin ? (a < b ? a : b) : a + b;
+}
+// log2 of the power of two K that axis 2's geometry holds in sy
+SQY_VIEW_HD inline uint32_t project_row_shift(const WindowGeometry& g) { return (uint32_t)__builtin_ctzll(g.sy | (1ull << 63)); }
+
+// what a thread has reduced of the sub-run it stands in (axis 2): `any` false, nothing
+struct ProjectPending { uint64_t off; uint32_t v; bool any; };
+
+// The piece `a` holds the n decoded voxels (n <= 16 / ELEM, packed as in a dense copy) at offset p of the thread's run; those inside the
+// current sub-run `cur` -- and the ones behind it that the piece reaches, have: there is one -- are combined into `sink`
+// (sink.combine(element, value)).  Pieces come in ascending p; what `pend` still holds behind the run's last piece is the caller's to send.
+template <int ELEM, class Sink>
+SQY_VIEW_HD inline void window_project16(Sink& sink, const WindowGeometry& g, WindowClip& c, WindowPiece& cur, bool& have, const uint32_t a[4], uint32_t p, uint32_t n,
+                                         uint32_t op, uint32_t axis, ProjectPending* pend)
+{
+    constexpr uint32_t G = 16 / ELEM, M = ELEM == 2 ? 0xffffu : 0xffu;
+    const uint32_t shift = axis == 2 ? project_row_shift(g) : 0u;
+    while (have && cur.run_off < (uint64_t)p + n) {
+        const uint64_t end = cur.run_off + cur.len;                  // (> p: a sub-run that ends in front of the piece has been left)
+        const uint32_t lo = cur.run_off > p ? (uint32_t)(cur.run_off - p) : 0u, hi = end < (uint64_t)p + n ? (uint32_t)(end - p) : n;
+        const uint64_t off = cur.dst_off + ((uint64_t)p + lo - cur.run_off);          // axes 0, 1: the element of voxel lo of the piece
+        if (axis == 2 && !pend->any) *pend = ProjectPending{cur.dst_off >> shift, project_neutral(op), true};
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+        for (uint32_t k = 0; k < G; ++k)
+            if (k >= lo && k < hi) {
+                const uint32_t v = (a[k * ELEM / 4] >> (8u * ((k * ELEM) & 3u))) & M;
+                if (axis == 2) pend->v = project_combine(op, pend->v, v);
+                else sink.combine(off + (k - lo), v);
+            }
+        if (end > (uint64_t)p + n) break;                             // the sub-run goes on in the next piece
+        if (axis == 2) { sink.combine(pend->off, pend->v); pend->any = false; }
         have = window_clip_next(g, &c, &cur);
     }
 }

@@ -82,6 +82,8 @@ struct Options {
     std::atomic<long> decode_box_subset;                // box decode: only the LZ4 frames the box's z-range needs, where the pipeline allows (0: full decode + window copy)
     std::atomic<long> decode_boxes_joint;               // many boxes of one blob: the frames united, one output launch for all boxes (0: the single-box driver box by box)
     std::atomic<long> compare_boxes_subset;             // compare of many boxes of one blob: only the LZ4 frames the boxes' z-ranges need, the comparing range transposer or one compare in the compaction, where sqy::compare_boxes_path allows (0: the blob decoded whole once, one window compare)
+    std::atomic<long> project_boxes_walk;               // projection along axis 0 on the transposer path: the z-walking form (registers, plain stores) where every box is on the 32-voxel grid (0: always the atomics -- same images)
+    std::atomic<long> project_boxes_subset;             // projection of many boxes of one blob: only the LZ4 frames the boxes' z-ranges need, the projecting range transposer or one projection in the compaction, where sqy::project_boxes_path allows (0: the blob decoded whole once, one projection launch)
     std::atomic<long> update_box_subset;                // box update of one blob: only the LZ4 frames the box's z-range needs are decoded, patched, parsed again and spliced between the old ones, where sqy::update_box_path allows (0: whole decode, one paste, the single call's encode)
     std::atomic<long> update_boxes_subset;              // update of many boxes of one blob: update_box_subset's stages, each once for all boxes (0: the blob decoded whole once, the pastes layer by layer, the single call's encode)
     std::atomic<long> decode_slabs_joint;               // slab-set decode: the chunked LZ4 blobs of a group indexed and decoded by one launch each (0: blob by blob)
@@ -109,7 +111,8 @@ struct Options {
           transpose_tiles_per_wave(env_number("SQY_TRANSPOSE_TILES_PER_WAVE", sqy::kBitswap1TilesPerWave, 1, 64)), stored_tail_index(env_flag("SQY_NO_STORED_TAIL_INDEX") ? 0 : 1),
           host_l2_bytes((long)sqy::host_l2_cache_bytes()), decode_frames_subset(env_flag("SQY_NO_DECODE_FRAMES_SUBSET") ? 0 : 1),
           decode_box_subset(env_flag("SQY_NO_DECODE_BOX_SUBSET") ? 0 : 1), decode_boxes_joint(env_flag("SQY_NO_DECODE_BOXES_JOINT") ? 0 : 1),
-          compare_boxes_subset(env_flag("SQY_NO_COMPARE_BOXES_SUBSET") ? 0 : 1), update_box_subset(env_flag("SQY_NO_UPDATE_BOX_SUBSET") ? 0 : 1),
+          compare_boxes_subset(env_flag("SQY_NO_COMPARE_BOXES_SUBSET") ? 0 : 1),
+          project_boxes_walk(env_flag("SQY_NO_PROJECT_BOXES_WALK") ? 0 : 1), project_boxes_subset(env_flag("SQY_NO_PROJECT_BOXES_SUBSET") ? 0 : 1), update_box_subset(env_flag("SQY_NO_UPDATE_BOX_SUBSET") ? 0 : 1),
           update_boxes_subset(env_flag("SQY_NO_UPDATE_BOXES_SUBSET") ? 0 : 1),
           decode_slabs_joint(env_flag("SQY_NO_DECODE_SLABS_JOINT") ? 0 : 1), decode_batch_joint(env_flag("SQY_NO_DECODE_BATCH_JOINT") ? 0 : 1),
           decode_batch_group_bytes(env_number("SQY_DECODE_BATCH_GROUP_BYTES", (long)kSlabsGroupBytes, 1, (long)kSlabsGroupBytes)), encode_batch_joint(env_flag("SQY_NO_ENCODE_BATCH_JOINT") ? 0 : 1),
@@ -136,6 +139,8 @@ struct Options {
         if (!std::strcmp(name, "decode_box_subset")) return &decode_box_subset;
         if (!std::strcmp(name, "decode_boxes_joint")) return &decode_boxes_joint;
         if (!std::strcmp(name, "compare_boxes_subset")) return &compare_boxes_subset;
+        if (!std::strcmp(name, "project_boxes_subset")) return &project_boxes_subset;
+        if (!std::strcmp(name, "project_boxes_walk")) return &project_boxes_walk;
         if (!std::strcmp(name, "update_box_subset")) return &update_box_subset;
         if (!std::strcmp(name, "update_boxes_subset")) return &update_boxes_subset;
         if (!std::strcmp(name, "decode_slabs_joint")) return &decode_slabs_joint;
@@ -3942,6 +3947,213 @@ int compare_boxes_from_host(const char* src, long srclength, long count, const l
     return compare_boxes_on_device(cx, cx.ws.io_src.p, (uint64_t)srclength, (size_t)count, origins, ptrs.data(), extents, nullptr, rank, elem_size, stream, stats);
 }
 
+// ---- many boxes of one large blob projected along an axis (SQYAMD_Project_Boxes_*) -----------------------------------------
+// compare_boxes_on_device with another sink: ONE header fetch, the LZ4 frames of all boxes' z-ranges united (DecodeCall::frames_subset on
+// the ranges), ONE output launch that combines into the images; sqy::project_boxes_path says what runs and sqy::admit_projection what is
+// admitted.  Nothing but the images' elements is written outside the workspace.
+static_assert(sizeof(sqy::Bitswap1BoxProjectJob) == sqy::kBitswap1BoxProjectJobBytes && sizeof(sqy::BoxProjectJob) == sqy::kBoxProjectJobBytes, "the projecting jobs' layout");
+
+// the thread-per-element projection's jobs: box i (w, its projection q) of the dense volume at `dense` into the image at `out`
+struct ProjectLaunch : TiledJobs<sqy::BoxProjectJob> {
+    void add(void* out, const void* dense, const sqy::BatchWindow& w, const sqy::Projection& q, int op)
+    {
+        jobs.push_back(sqy::BoxProjectJob{dense, out, (w.oz * w.bY + w.oy) * w.bX + w.ox, q.E0, q.E1, q.p0, q.su, q.sv, q.sa, q.n, (uint32_t)op, 0, 0});
+        first_tile.push_back(ntiles);
+        ntiles += (uint32_t)((q.E0 * q.E1 + 255) / 256);
+    }
+};
+int launch_boxes_project(Context& cx, hipStream_t stream, ProjectLaunch& l, int elem_size)
+{
+    std::vector<PendingEvent>* pend = &cx.pending;
+    const uint32_t* d_tiles = nullptr;
+    if (l.upload(stream, cx.ws.boxes_jobs, &d_tiles)) return 1;
+    SQY_TIMED("boxes_window_project", sqy::launch_boxes_window_project(static_cast<const sqy::BoxProjectJob*>(cx.ws.boxes_jobs.p), d_tiles, (uint32_t)l.jobs.size(), l.ntiles,
+                                                                        elem_size, stream));
+    return 0;
+}
+
+// the projection's launches behind DecodeCall::frames_subset: box i (ws[i], qs[i]) of the united frames in c.range_buf into outs[i]
+int boxes_range_project(DecodeCall& c, ProjectLaunch& l, TiledJobs<sqy::Bitswap1BoxProjectJob>& tj, const std::vector<sqy::BatchWindow>& ws,
+                        const std::vector<sqy::Projection>& qs, void* const* outs, unsigned rank, int op)
+{
+    hipStream_t stream = c.stream;
+    std::vector<PendingEvent>* pend = c.pend;
+    const sqy::FrameRangesPlan& p = c.ranges_plan;
+    const size_t count = ws.size();
+    if (p.boxes.size() != count) return 1;
+    if (sqy::project_boxes_path(true, c.range_form, true) == sqy::BoxPath::subset_transposer) {
+        const uint16_t* lut = nullptr;
+        if (c.range_lut(&lut)) return 1;
+        const uint32_t wpt = 128u / (8u * (uint32_t)p.we);
+        for (size_t i = 0; i < count; ++i) {
+            const sqy::BatchWindow& w = ws[i];
+            const sqy::Projection& q = qs[i];
+            const sqy::FrameRangesBox& b = p.boxes[i];
+            sqy::Bitswap1BoxProjectJob j{};
+            j.out = outs[i];
+            j.g = sqy::WindowGeometry{w.bY, w.bX, w.oz, w.oy, w.ox, w.Z, w.Y, w.X, q.sz, q.sy};
+            std::copy(b.plane, b.plane + 16, j.r.plane);
+            j.r.tail = b.tail; j.r.w0 = b.w0; j.r.w1 = b.w1; j.r.v0 = b.v0; j.r.v1 = b.v1; j.r.L = b.L;
+            j.t0 = sqy::range_first_thread(b.w0, wpt);
+            j.op = (uint32_t)op; j.axis = q.axis3;
+            j.E0 = q.E0; j.E1 = q.E1; j.p0 = q.p0;
+            if (!sqy::bitswap1_box_project_job_ok(j)) return 1;
+            tj.jobs.push_back(j);
+        }
+        // the form: axis 0 with every job on the 32-voxel grid walks z in registers and stores once; else the atomics
+        bool walk = g_opt.project_boxes_walk.load() != 0 && reinterpret_cast<uintptr_t>(c.range_buf) % 4u == 0;
+        uint64_t walk_groups = 0;
+        for (size_t i = 0; walk && i < count; ++i) {
+            walk = sqy::bitswap1_box_project_walk_ok(tj.jobs[i], p.we);
+            walk_groups += sqy::project_walk_groups(tj.jobs[i].g);
+        }
+        walk = walk && walk_groups <= 0x7fffffffull;
+        for (size_t i = 0; i < count; ++i) {
+            tj.first_tile.push_back(tj.ntiles);
+            tj.ntiles += (uint32_t)(walk ? sqy::project_walk_groups(tj.jobs[i].g) : sqy::range_job_groups(p.boxes[i].w0, p.boxes[i].w1, wpt));
+        }
+        const uint32_t* d_tiles = nullptr;
+        if (tj.upload(stream, c.cx.ws.boxes_jobs, &d_tiles)) return 1;
+        const sqy::Bitswap1BoxProjectJob* d_jobs = static_cast<const sqy::Bitswap1BoxProjectJob*>(c.cx.ws.boxes_jobs.p);
+        if (walk) {
+            SQY_TIMED(lut ? "bitswap1_quantiser_project_boxes" : "bitswap1_project_boxes",
+                      sqy::launch_bitswap1_decode_range_windows_project_walk(c.range_buf, d_jobs, d_tiles, (uint32_t)count, tj.ntiles, p.we, lut, stream));
+            return 0;
+        }
+        SQY_TIMED("boxes_project_init", sqy::launch_boxes_project_init(d_jobs, d_tiles, (uint32_t)count, tj.ntiles, stream));
+        SQY_TIMED(lut ? "bitswap1_quantiser_project_boxes" : "bitswap1_project_boxes",
+                  sqy::launch_bitswap1_decode_range_windows_project(c.range_buf, d_jobs, d_tiles, (uint32_t)count, tj.ntiles, p.we, lut, stream));
+        return 0;
+    }
+    // plain, shuffle: box i's range in the workspace is a blob of its frames, the box begins at its first one (boxes_range_out's geometry)
+    for (size_t i = 0; i < count; ++i) {
+        sqy::BatchWindow in_range = ws[i];
+        if (rank == 3) { in_range.bZ = in_range.Z; in_range.oz = 0; }
+        else if (rank == 2) { in_range.bY = in_range.Y; in_range.oy = 0; }
+        else { in_range.bX = in_range.X; in_range.ox = 0; }
+        l.add(outs[i], c.range_buf + p.boxes[i].range_at, in_range, qs[i], op);
+    }
+    return launch_boxes_project(c.cx, stream, l, c.h.elem_size());
+}
+
+// Box i = [origins + i rank, .. + extents + i rank) of the blob projected along `axis` into the image at d_outs[i] (out_strides +
+// i (rank - 1), or dense).  sqy::admit_projection for every box and the launches' sizes -- all before anything is written
+int project_boxes_on_device(Context& cx, const void* d_src_v, uint64_t srclen, size_t count, const long* origins, const long* extents, unsigned rank, int axis, int op,
+                            void* const* d_outs, const long* out_strides, int want_elem, hipStream_t stream)
+{
+    const uint8_t* d_src = static_cast<const uint8_t*>(d_src_v);
+    DrainOnExit drain{stream, &cx.pending, cx.side};
+    sqy::HeaderInfo h;
+    if (fetch_header(d_src, srclen, stream, h)) return 1;
+    uint64_t raw_bytes = 0;
+    if (!admit_blob(h, srclen, want_elem, &raw_bytes)) return 1;
+    std::vector<sqy::BatchWindow> ws(count);
+    std::vector<sqy::Projection> qs(count);
+    std::vector<std::pair<uint64_t, uint64_t>> ranges(count);
+    const uint64_t frame_voxels = raw_bytes / (uint64_t)want_elem / h.shape[0];
+    uint64_t element_groups = 0, range_groups = 0;           // what the one output launch may hold, whichever it is
+    for (size_t i = 0; i < count; ++i) {
+        const long* o = origins + i * rank;
+        const long* e = extents + i * rank;
+        if (!sqy::admit_projection(h.shape, o, e, rank, axis, op, want_elem == 2 ? 65535u : 255u, d_outs[i], out_strides ? out_strides + i * (rank - 1) : nullptr, &ws[i],
+                                   &qs[i])) {
+            std::fprintf(stderr, "[sqeazy]\t project boxes: box %zu does not lie inside the blob's shape or has another rank, or its sum might not fit 32 bits\n", i);
+            return 1;
+        }
+        ranges[i] = {(uint64_t)o[0], (uint64_t)e[0]};
+        element_groups += (qs[i].E0 * qs[i].E1 + 255) / 256;
+        range_groups += (uint64_t)e[0] * frame_voxels / sqy::kBatchTileVoxels + 2;      // (at least range_job_groups of the box's words)
+    }
+    if (std::max(element_groups, range_groups) > 0x7fffffffull) {
+        std::fprintf(stderr, "[sqeazy]\t project boxes: too many workgroups for one launch\n");
+        return 1;
+    }
+    ProjectLaunch l;                                                    // (both wait for the stream before their tables go)
+    TiledJobs<sqy::Bitswap1BoxProjectJob> tj;
+    if (g_opt.project_boxes_subset.load()) {
+        DecodeCall c(cx, stream, nullptr, h, Pipeline::from_string(h.pipename), raw_bytes / (uint64_t)want_elem, d_src + h.size);
+        bool taken = false;
+        if (const int rc = c.frames_subset(ranges, false, &taken)) return rc;
+        if (taken) {
+            if (const int rc = boxes_range_project(c, l, tj, ws, qs, d_outs, rank, op)) return rc;
+            return c.finish();
+        }
+    }
+    // sqy::BoxPath::whole_copy: the whole volume ONCE, then all boxes in one launch
+    if (cx.ws.range_full.ensure(std::max<uint64_t>(raw_bytes, 16))) return 1;
+    if (const int rc = decode_on_device(cx, d_src_v, srclen, cx.ws.range_full.p, raw_bytes, want_elem, stream)) return rc;
+    for (size_t i = 0; i < count; ++i) l.add(d_outs[i], cx.ws.range_full.p, ws[i], qs[i], op);
+    if (launch_boxes_project(cx, stream, l, want_elem)) return 1;
+    SQY_HIP(hipStreamSynchronize(stream));
+    if (g_prof_on.load()) prof_collect(cx.pending);
+    return 0;
+}
+
+// what SQYAMD_Project_Boxes_* checks without a header, before a device is looked for: boxes_arguments_ok, and sqy::admit_projection of
+// every box against the smallest shape that holds it -- the axis, the op, the image's pointer and pitches, the sum bound
+bool project_arguments_ok(const void* src, long srclength, long count, const long* origins, const long* extents, unsigned rank, int axis, int op, void* const* outs,
+                          const long* out_strides, int elem_size)
+{
+    if (!boxes_arguments_ok(src, srclength, count, origins, outs, extents, rank)) return false;
+    for (long i = 0; i < count; ++i) {
+        const long* o = origins + (size_t)i * rank;
+        const long* e = extents + (size_t)i * rank;
+        std::vector<uint64_t> shape(rank);
+        for (unsigned k = 0; k < rank; ++k) shape[k] = (uint64_t)o[k] + (uint64_t)std::max(e[k], 0l);     // (both below 2^63: no wrap)
+        sqy::BatchWindow w;
+        sqy::Projection q;
+        const void* out = outs ? outs[i] : static_cast<const void*>(&q);                                   // (host variant: the images are the library's)
+        if (!sqy::admit_projection(shape, o, e, rank, axis, op, elem_size == 2 ? 65535u : 255u, out, outs && out_strides ? out_strides + (size_t)i * (rank - 1) : nullptr, &w, &q))
+            return false;
+    }
+    return true;
+}
+
+int project_boxes_device(const void* d_src, long srclength, long count, const long* origins, const long* extents, unsigned rank, int axis, int op, void* const* d_outs,
+                         const long* out_strides, int elem_size, void* hip_stream)
+{
+    if (!d_outs || !project_arguments_ok(d_src, srclength, count, origins, extents, rank, axis, op, d_outs, out_strides, elem_size)) {
+        std::fprintf(stderr, "[sqeazy]\t project boxes: bad arguments\n");
+        return 1;
+    }
+    ContextLease lease;
+    if (!lease.ctx) { std::fprintf(stderr, "[sqeazy]\t no usable HIP device\n"); return 1; }
+    return project_boxes_on_device(*lease.ctx, d_src, (uint64_t)srclength, (size_t)count, origins, extents, rank, axis, op, d_outs, out_strides, elem_size,
+                                   static_cast<hipStream_t>(hip_stream));
+}
+
+// host pointers: the header and every box are checked here, before anything is staged; the images come back dense, back to back in box
+// order, 32-bit elements
+int project_boxes_from_host(const char* src, long srclength, long count, const long* origins, const long* extents, unsigned rank, int axis, int op, char* out,
+                            long out_capacity, int elem_size)
+{
+    if (!out || !project_arguments_ok(src, srclength, count, origins, extents, rank, axis, op, nullptr, nullptr, elem_size)) {
+        std::fprintf(stderr, "[sqeazy]\t project boxes: bad arguments\n");
+        return 1;
+    }
+    const sqy::HeaderInfo h = sqy::header_unpack(src, src + srclength);
+    if (!h.valid) { std::fprintf(stderr, "[sqeazy]\t unable to find a sqy header in the blob\n"); return 1; }
+    uint64_t raw = 0;
+    if (!header_shape_ok(h, (uint64_t)srclength, &raw)) return 1;
+    if (h.elem_size() != elem_size) { std::fprintf(stderr, "[sqeazy]\t blob holds %s voxels\n", h.type.c_str()); return 1; }
+    std::vector<uint64_t> at((size_t)count + 1, 0);                    // (an image is no larger than the volume, count fits an int: no wrap)
+    for (long i = 0; i < count; ++i) {
+        sqy::BatchWindow w;
+        sqy::Projection q;
+        if (!sqy::admit_projection(h.shape, origins + (size_t)i * rank, extents + (size_t)i * rank, rank, axis, op, elem_size == 2 ? 65535u : 255u, &q, nullptr, &w, &q)) {
+            std::fprintf(stderr, "[sqeazy]\t project boxes: box %ld does not lie inside the blob's shape, or its sum might not fit 32 bits\n", i);
+            return 1;
+        }
+        at[(size_t)i + 1] = at[(size_t)i] + q.E0 * q.E1 * 4u;
+    }
+    if (at.back() > (uint64_t)std::max(out_capacity, 0l)) { std::fprintf(stderr, "[sqeazy]\t project boxes: buffer too small\n"); return 1; }
+    return decode_staged(src, (uint64_t)srclength, out, at.back(), [&](Context& cx, void* d_src, void* d_dst, hipStream_t stream) {
+        std::vector<void*> ptrs((size_t)count);
+        for (long i = 0; i < count; ++i) ptrs[(size_t)i] = static_cast<uint8_t*>(d_dst) + at[(size_t)i];
+        return project_boxes_on_device(cx, d_src, (uint64_t)srclength, (size_t)count, origins, extents, rank, axis, op, ptrs.data(), nullptr, elem_size, stream);
+    });
+}
+
 int decode_batch_device(const void* d_src, const BatchDecodeArgs& a, int elem_size, void* hip_stream)
 {
     if (admit_decode_batch(d_src, a)) return 1;
@@ -5684,6 +5896,30 @@ int SQYAMD_Compare_Boxes_UI8(const char* src, long srclength, long count, const 
                              unsigned long long* stats)
 {
     return guarded([&]() -> int { return compare_boxes_from_host(src, srclength, count, origins, extents, rank, views, views_bytes, stats, 1); });
+}
+
+int SQYAMD_Project_Boxes_UI16_Device(const void* d_src, long srclength, long count, const long* origins, const long* extents, unsigned rank, int axis, int op,
+                                     void* const* d_outs, const long* out_strides, void* hip_stream)
+{
+    return guarded([&]() -> int { return project_boxes_device(d_src, srclength, count, origins, extents, rank, axis, op, d_outs, out_strides, 2, hip_stream); });
+}
+
+int SQYAMD_Project_Boxes_UI8_Device(const void* d_src, long srclength, long count, const long* origins, const long* extents, unsigned rank, int axis, int op,
+                                    void* const* d_outs, const long* out_strides, void* hip_stream)
+{
+    return guarded([&]() -> int { return project_boxes_device(d_src, srclength, count, origins, extents, rank, axis, op, d_outs, out_strides, 1, hip_stream); });
+}
+
+int SQYAMD_Project_Boxes_UI16(const char* src, long srclength, long count, const long* origins, const long* extents, unsigned rank, int axis, int op, char* out,
+                              long out_capacity)
+{
+    return guarded([&]() -> int { return project_boxes_from_host(src, srclength, count, origins, extents, rank, axis, op, out, out_capacity, 2); });
+}
+
+int SQYAMD_Project_Boxes_UI8(const char* src, long srclength, long count, const long* origins, const long* extents, unsigned rank, int axis, int op, char* out,
+                             long out_capacity)
+{
+    return guarded([&]() -> int { return project_boxes_from_host(src, srclength, count, origins, extents, rank, axis, op, out, out_capacity, 1); });
 }
 
 int SQYAMD_Decode_Slabs_UI16_Device(const void* d_src, const long* offsets, const long* lengths, int nslabs, void* d_dst, long dst_capacity,

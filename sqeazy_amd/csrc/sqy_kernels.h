@@ -447,6 +447,65 @@ constexpr uint64_t kBitswap1BoxCompareJobBytes = 288;     // (a multiple of 16: 
 bool bitswap1_box_compare_job_ok(const Bitswap1BoxCompareJob& j);
 hipError_t launch_bitswap1_decode_range_windows_compare(const uint8_t* in, const Bitswap1BoxCompareJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs,
                                                         uint32_t ngroups, int elem_size, const uint16_t* lut, hipStream_t stream);
+// ---- many boxes of one large blob projected along an axis (SQYAMD_Project_Boxes_*) ----
+// launch_bitswap1_decode_range_windows with a combine where its stores were: job j's decoded voxels (behind the look-up the 16-bit voxels
+// out of the table) go into its image of 32-bit elements at `out` with no-return integer atomics at device scope -- max, min or add, so
+// the result does not depend on the order the threads finish in --, the element being the clip's dst_off under the geometry
+// sqy::admit_projection fills (sqy_batch_window.hpp: window_project16; axis 2 reduced per sub-run in the thread first).  The images hold
+// their neutral elements beforehand: launch_boxes_project_init over the SAME tables, in front on the stream -- workgroup `own` of a job's
+// groups fills the elements own 256 + tid, + groups 256, .. of the job's image (E0 rows of E1 elements, p0 apart).  The job is
+// Bitswap1BoxJob's fields and the image's; the tables, the groups and bitswap1_box_project_job_ok as there.  Nothing but the images'
+// elements is written.
+struct Bitswap1BoxProjectJob {
+    void* out;
+    WindowGeometry g;
+    Bitswap1Range r;
+    uint64_t t0;
+    uint32_t op, axis;       // sqy::kProjectMax .. ; the axis among (z, y, x)
+    uint64_t E0, E1, p0;
+};
+constexpr uint64_t kBitswap1BoxProjectJobBytes = 304;    // (a multiple of 16: the tile table behind the jobs stays on the 16-byte grid)
+bool bitswap1_box_project_job_ok(const Bitswap1BoxProjectJob& j);
+hipError_t launch_boxes_project_init(const Bitswap1BoxProjectJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ngroups, hipStream_t stream);
+hipError_t launch_bitswap1_decode_range_windows_project(const uint8_t* in, const Bitswap1BoxProjectJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs,
+                                                        uint32_t ngroups, int elem_size, const uint16_t* lut, hipStream_t stream);
+// The second form for axis 0 (frames), where a frame is a whole number of 32-voxel runs: no atomics, no neutral elements beforehand.  A
+// thread owns ONE frame-local run of 32 voxels -- four bytes of every plane per frame, on the 4-byte grid -- and walks z over the box's
+// frames: it loads the plane pieces of each frame, transposes them and reduces by position in registers; the clip of its run in the box's
+// first frame (the same in every frame) says which positions are image elements, and it stores those once.  Job j owns
+// project_walk_groups(g) workgroups: the runs [first, last] that hold a voxel of the box's footprint in a frame; a run with nothing
+// inside loads no plane word.  Every job of a launch must pass bitswap1_box_project_walk_ok (and bitswap1_box_project_job_ok); `in` is on
+// the 4-byte grid.
+SQY_VIEW_HD inline uint64_t project_walk_first_run(const WindowGeometry& g) { return (g.oy * g.bX + g.ox) / 32; }
+SQY_VIEW_HD inline uint64_t project_walk_groups(const WindowGeometry& g)
+{
+    return (((g.oy + g.Y - 1) * g.bX + g.ox + g.X - 1) / 32 - project_walk_first_run(g)) / 256 + 1;
+}
+// elem_size: of a STORED voxel (1 behind the look-up)
+inline bool bitswap1_box_project_walk_ok(const Bitswap1BoxProjectJob& j, int elem_size)
+{
+    const uint64_t W = 8u * (uint64_t)elem_size, frame = j.g.bY * j.g.bX;
+    if (j.axis != 0 || frame == 0 || frame % 32 != 0) return false;
+    // every word of the box's frames lies in the range's plane words, none of its voxels in the tail
+    if (j.r.w0 * W > j.g.oz * frame || (j.g.oz + j.g.Z) * frame > j.r.w1 * W || (j.g.oz + j.g.Z) * frame > j.r.L) return false;
+    for (uint64_t p = 0; p < W; ++p)                                  // a run's four bytes of plane p: on the 4-byte grid
+        if ((j.r.plane[p] % 4 + 4 - (j.r.w0 * (uint64_t)elem_size) % 4) % 4 != 0) return false;
+    return true;
+}
+hipError_t launch_bitswap1_decode_range_windows_project_walk(const uint8_t* in, const Bitswap1BoxProjectJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs,
+                                                             uint32_t ngroups, int elem_size, const uint16_t* lut, hipStream_t stream);
+// The projection of boxes of a DENSE volume (the compaction of `lz4` and `frame_shuffle->lz4` blobs, the whole decode): a thread per image
+// element walks the axis -- element (u, v) reads dense[base + u su + v sv + k sa], k < n, and stores out[u p0 + v] once: no atomics, and
+// no neutral elements beforehand.  Job j owns ceil(E0 E1 / 256) workgroups; d_first_tile their prefix sums.
+struct BoxProjectJob {
+    const void* dense;
+    void* out;
+    uint64_t base, E0, E1, p0, su, sv, sa, n;
+    uint32_t op, pad0;
+    uint64_t pad1;
+};
+constexpr uint64_t kBoxProjectJobBytes = 96;
+hipError_t launch_boxes_window_project(const BoxProjectJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ngroups, int elem_size, hipStream_t stream);
 // ---- a box written into one large blob (SQYAMD_Update_Box_*) ----
 // launch_bitswap1_decode_range_window the other way round, in place: the box's voxels are read from the view (box.view; `dense` and tile0
 // are not read) and merged into the plane words [w0, w1) and the tail of the range r inside the compaction at buf (launch_bitswap1_batch_patch's

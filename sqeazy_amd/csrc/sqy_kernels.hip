@@ -9469,6 +9469,320 @@ bool bitswap1_box_compare_job_ok(const Bitswap1BoxCompareJob& j)
     return ((g.oz * g.bY + g.oy) * g.bX + g.ox) >= r.v0 && ((g.oz + g.Z - 1) * g.bY + g.oy + g.Y - 1) * g.bX + g.ox + g.X <= r.v1;
 }
 
+// ---- many boxes of one large blob projected along an axis (SQYAMD_Project_Boxes_*) ------------------------------------------------------
+// the sink of window_project16 on the device: one no-return 32-bit integer atomic at device scope per combine.  A value that is the
+// op's neutral element changes nothing and is not sent (dark voxels under max and sum)
+struct ProjectAtomicSink {
+    uint32_t* __restrict__ out;
+    uint32_t op;
+    __device__ __forceinline__ void combine(uint64_t off, uint32_t v) const
+    {
+        if (op == kProjectMax) { if (v) (void)atomicMax(out + off, v); }
+        else if (op == kProjectMin) (void)atomicMin(out + off, v);
+        else if (v) (void)atomicAdd(out + off, v);
+    }
+};
+
+// the images' neutral elements, over the projecting launch's own tables: workgroup `own` of job j's groups fills every groups-th run of
+// 256 elements of the image, rows p0 apart -- the gaps between pitched rows are not touched
+__global__ __launch_bounds__(256)
+void boxes_project_init_kernel(const Bitswap1BoxProjectJob* __restrict__ jobs, const uint32_t* __restrict__ first_tile, uint32_t njobs)
+{
+    const uint32_t j = batch_job_of_tile(first_tile, njobs);
+    const Bitswap1BoxProjectJob* __restrict__ job = jobs + j;
+    const uint64_t own = blockIdx.x - first_tile[j], groups = first_tile[j + 1] - first_tile[j];
+    const uint64_t E1 = job->E1, n = job->E0 * E1, p0 = job->p0;
+    uint32_t* __restrict__ out = static_cast<uint32_t*>(job->out);
+    const uint32_t neutral = project_neutral(job->op);
+    for (uint64_t e = own * 256u + threadIdx.x; e < n; e += groups * 256u) {
+        const uint64_t u = e / E1;
+        out[u * p0 + (e - u * E1)] = neutral;
+    }
+}
+
+// bitswap1_decode_range_windows_compare_kernel with window_project16 where it compares: the same job walk, absolute-word grid
+// (sqy::range_run), clip, plane loads (sixteen bytes on the stream's grid, word by word elsewhere), transposes and look-up.  A thread
+// without a word, or whose run has nothing inside the box, loads no plane word and sends nothing; every thread has passed the look-up's
+// barrier by then.  The job's first workgroup also takes the tail voxels.  Nothing but the job's image is written, by atomics alone.
+template <int ELEM, bool LUT>
+__global__ __launch_bounds__(256)
+void bitswap1_decode_range_windows_project_kernel(const uint8_t* __restrict__ in, const Bitswap1BoxProjectJob* __restrict__ jobs, const uint32_t* __restrict__ first_tile,
+                                                  uint32_t njobs, const uint16_t* __restrict__ lut)
+{
+    static_assert(!LUT || ELEM == 1, "the look-up follows 8-bit planes");
+    constexpr uint32_t W = 8 * ELEM, WPT = BSWB_THREAD_VOX / W;        // voxels per word, words per thread
+    __shared__ uint16_t sl[LUT ? 256 : 1];
+    if constexpr (LUT) { sl[threadIdx.x] = lut[threadIdx.x]; __syncthreads(); }
+    const uint32_t j = batch_job_of_tile(first_tile, njobs);
+    const Bitswap1BoxProjectJob* __restrict__ job = jobs + j;           // (uniform: its fields live in scalar registers)
+    const uint32_t own = blockIdx.x - first_tile[j], tid = threadIdx.x;
+    const Bitswap1Range& a = job->r;
+    const WindowGeometry& g = job->g;
+    const uint32_t op = job->op, axis = job->axis;
+    ProjectAtomicSink sink{static_cast<uint32_t*>(job->out), op};
+    WindowPiece cur;
+    const uint64_t tail0 = a.v0 > a.L ? a.v0 : a.L;
+    if (own == 0 && tail0 + tid < a.v1) {                            // tail voxels: verbatim in the stream (or looked up), those of the box
+        WindowClip ct = window_clip_start(g, tail0 + tid, 1);
+        if (window_clip_next(g, &ct, &cur)) {
+            const uint32_t x = view_voxel_load<ELEM>(in + a.tail, tid);
+            sink.combine(axis == 2 ? cur.dst_off >> project_row_shift(g) : cur.dst_off, LUT ? (uint32_t)sl[x & 0xffu] : x);
+        }
+    }
+    const RangeRun run = range_run(job->t0 + (uint64_t)own * 256u + tid, WPT, a.w0, a.w1);
+    const bool owns = run.lo != run.hi;
+    WindowClip c = window_clip_start(g, owns ? run.first * W : 0, owns ? (uint64_t)run.hi * W : 0);
+    bool have = owns && window_clip_next(g, &c, &cur);
+    if (!have) return;                                                // (nothing of the run inside the box: no plane word is loaded)
+    ProjectPending pend{0, 0, false};
+    const uint64_t at = (run.first - a.w0) * ELEM;                    // the thread's 16 bytes behind plane[s] (in front of it: a first thread's words not owned, never read)
+    bool wide = run.lo == 0 && run.hi == WPT;
+    if (wide) {
+        uint32_t off_grid = 0;                                        // (uniform: first ELEM is a multiple of 16)
+#pragma unroll
+        for (uint32_t p = 0; p < W; ++p) off_grid |= (uint32_t)(reinterpret_cast<uintptr_t>(in) + a.plane[p] + at);
+        wide = (off_grid & 15u) == 0;
+    }
+    if constexpr (ELEM == 2) {
+        uint32_t pl[16][4];                                           // pl[b] = eight words of the plane that carries bit b
+        if (wide) {
+#pragma unroll
+            for (int b = 0; b < 16; ++b) {
+                const uint4 t = *reinterpret_cast<const uint4*>(in + a.plane[15 - b] + at);
+                pl[b][0] = t.x; pl[b][1] = t.y; pl[b][2] = t.z; pl[b][3] = t.w;
+            }
+        } else {
+#pragma unroll
+            for (int b = 0; b < 16; ++b) { pl[b][0] = 0; pl[b][1] = 0; pl[b][2] = 0; pl[b][3] = 0; }
+#pragma unroll
+            for (uint32_t i = 0; i < WPT; ++i)
+                if (i >= run.lo && i < run.hi)
+#pragma unroll
+                    for (int b = 0; b < 16; ++b)
+                        pl[b][i >> 1] |= (uint32_t)*reinterpret_cast<const uint16_t*>(in + a.plane[15 - b] + at + 2u * i) << (16u * (i & 1u));
+        }
+#pragma unroll
+        for (uint32_t q = 0; q < 4; ++q) {                            // words first + 2 q (group A, low halves) and first + 2 q + 1 (group B)
+            if (2 * q >= run.hi || !have) break;
+            uint32_t r[16];
+#pragma unroll
+            for (int b = 0; b < 16; ++b) r[b] = pl[b][q];
+            transpose16x16_pairs(r);                                  // r[i] = voxel 15 - i of group A | of group B << 16
+            uint32_t ga[8], gb[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                ga[k] = __builtin_amdgcn_perm(r[14 - 2 * k], r[15 - 2 * k], 0x05040100u);
+                gb[k] = __builtin_amdgcn_perm(r[14 - 2 * k], r[15 - 2 * k], 0x07060302u);
+            }
+            window_project16<2>(sink, g, c, cur, have, ga, 32u * q, 8, op, axis, &pend);
+            window_project16<2>(sink, g, c, cur, have, ga + 4, 32u * q + 8u, 8, op, axis, &pend);
+            if (2 * q + 1 >= run.hi) break;
+            window_project16<2>(sink, g, c, cur, have, gb, 32u * q + 16u, 8, op, axis, &pend);
+            window_project16<2>(sink, g, c, cur, have, gb + 4, 32u * q + 24u, 8, op, axis, &pend);
+        }
+    } else {
+        uint32_t pw[8][4];                                            // pw[b] = 16 bytes of the plane that carries bit b
+        if (wide) {
+#pragma unroll
+            for (int b = 0; b < 8; ++b) {
+                const uint4 t = *reinterpret_cast<const uint4*>(in + a.plane[7 - b] + at);
+                pw[b][0] = t.x; pw[b][1] = t.y; pw[b][2] = t.z; pw[b][3] = t.w;
+            }
+        } else {
+#pragma unroll
+            for (int b = 0; b < 8; ++b) { pw[b][0] = 0; pw[b][1] = 0; pw[b][2] = 0; pw[b][3] = 0; }
+#pragma unroll
+            for (uint32_t i = 0; i < WPT; ++i)
+                if (i >= run.lo && i < run.hi)
+#pragma unroll
+                    for (int b = 0; b < 8; ++b) pw[b][i >> 2] |= (uint32_t)in[a.plane[7 - b] + at + i] << (8u * (i & 3u));
+        }
+#pragma unroll
+        for (uint32_t gq = 0; gq < 16; gq += 2) {
+            if (gq >= run.hi || !have) break;
+            uint32_t d[4];
+#pragma unroll
+            for (uint32_t u = 0; u < 2; ++u) {
+                // (bitswap1_decode_batch_strided_kernel's gather and transpose: afterwards byte i of hi:lo = voxel 7 - i)
+                constexpr uint32_t Zs = 0x0c;                         // v_perm selector: a zero byte
+                const uint32_t cc = (gq + u) & 3u, wdx = (gq + u) >> 2;
+                const uint32_t s01 = cc | ((4u + cc) << 8) | (Zs << 16) | (Zs << 24), s23 = Zs | (Zs << 8) | (cc << 16) | ((4u + cc) << 24);
+                uint32_t lo_ = __builtin_amdgcn_perm(pw[1][wdx], pw[0][wdx], s01) | __builtin_amdgcn_perm(pw[3][wdx], pw[2][wdx], s23);
+                uint32_t hi_ = __builtin_amdgcn_perm(pw[5][wdx], pw[4][wdx], s01) | __builtin_amdgcn_perm(pw[7][wdx], pw[6][wdx], s23);
+                uint32_t y;
+                y = (lo_ ^ (lo_ >> 7)) & 0x00AA00AAu; lo_ ^= y ^ (y << 7);
+                y = (hi_ ^ (hi_ >> 7)) & 0x00AA00AAu; hi_ ^= y ^ (y << 7);
+                y = (lo_ ^ (lo_ >> 14)) & 0x0000CCCCu; lo_ ^= y ^ (y << 14);
+                y = (hi_ ^ (hi_ >> 14)) & 0x0000CCCCu; hi_ ^= y ^ (y << 14);
+                y = (lo_ ^ (hi_ << 4)) & 0xF0F0F0F0u; lo_ ^= y; hi_ ^= y >> 4;
+                d[2 * u] = __builtin_bswap32(hi_);                    // voxels 0..3 of the word
+                d[2 * u + 1] = __builtin_bswap32(lo_);                // voxels 4..7
+            }
+            if constexpr (LUT) {
+#pragma unroll
+                for (uint32_t u = 0; u < 2; ++u) {                    // word gq + u: eight 16-bit voxels, one piece
+                    if (gq + u >= run.hi) break;
+                    const uint32_t h4 = d[2 * u], l4 = d[2 * u + 1];          // (voxel k of four at byte k)
+                    const uint32_t v16[4] = {(uint32_t)sl[h4 & 0xffu] | ((uint32_t)sl[(h4 >> 8) & 0xffu] << 16), (uint32_t)sl[(h4 >> 16) & 0xffu] | ((uint32_t)sl[h4 >> 24] << 16),
+                                             (uint32_t)sl[l4 & 0xffu] | ((uint32_t)sl[(l4 >> 8) & 0xffu] << 16), (uint32_t)sl[(l4 >> 16) & 0xffu] | ((uint32_t)sl[l4 >> 24] << 16)};
+                    window_project16<2>(sink, g, c, cur, have, v16, 8u * (gq + u), 8, op, axis, &pend);
+                }
+            } else
+                window_project16<1>(sink, g, c, cur, have, d, 8u * gq, run.hi - gq >= 2u ? 16u : 8u, op, axis, &pend);
+        }
+    }
+    if (pend.any) sink.combine(pend.off, pend.v);                     // (a sub-run that ends with the run is sent where it ends: nothing is left)
+}
+
+// The second form for axis 0 (sqy_kernels.h): a thread owns the frame-local run of 32 voxels `run` and walks z.  acc[i] is the reduction of
+// position i of the run over the box's frames; the clip of the run in the box's first frame names the positions that are image elements.
+// Plain stores, once per element: an element belongs to exactly one run.
+template <int ELEM, bool LUT>
+__global__ __launch_bounds__(256)
+void bitswap1_decode_range_windows_project_walk_kernel(const uint8_t* __restrict__ in, const Bitswap1BoxProjectJob* __restrict__ jobs,
+                                                       const uint32_t* __restrict__ first_tile, uint32_t njobs, const uint16_t* __restrict__ lut)
+{
+    static_assert(!LUT || ELEM == 1, "the look-up follows 8-bit planes");
+    constexpr uint32_t W = 8 * ELEM;                                   // voxels per word; a run is 32 / W words, four bytes of a plane
+    __shared__ uint16_t sl[LUT ? 256 : 1];
+    if constexpr (LUT) { sl[threadIdx.x] = lut[threadIdx.x]; __syncthreads(); }
+    const uint32_t j = batch_job_of_tile(first_tile, njobs);
+    const Bitswap1BoxProjectJob* __restrict__ job = jobs + j;           // (uniform: its fields live in scalar registers)
+    const Bitswap1Range& a = job->r;
+    const WindowGeometry& g = job->g;
+    const uint32_t op = job->op;
+    const uint64_t frame = g.bY * g.bX;
+    const uint64_t run = project_walk_first_run(g) + (uint64_t)(blockIdx.x - first_tile[j]) * 256u + threadIdx.x;
+    if ((run + 1) * 32 > frame) return;                                // (behind the frame: the last workgroup's spare threads)
+    WindowClip c = window_clip_start(g, g.oz * frame + run * 32, 32);
+    WindowPiece cur;
+    bool have = window_clip_next(g, &c, &cur);
+    if (!have) return;                                                // (nothing of the run inside the box's footprint: no plane word is loaded)
+    uint32_t acc[32];
+#pragma unroll
+    for (int i = 0; i < 32; ++i) acc[i] = project_neutral(op);
+    for (uint64_t z = 0; z < g.Z; ++z) {
+        const uint64_t at = (((g.oz + z) * frame + run * 32) / W - a.w0) * ELEM;      // the run's four bytes behind plane[s]
+        uint32_t v[32];
+        if constexpr (ELEM == 2) {
+            uint32_t r[16];                                            // r[b] = the run's two words of the plane that carries bit b
+#pragma unroll
+            for (int b = 0; b < 16; ++b) r[b] = *reinterpret_cast<const uint32_t*>(in + a.plane[15 - b] + at);
+            transpose16x16_pairs(r);                                  // r[i] = voxel 15 - i of the first word | of the second << 16
+#pragma unroll
+            for (int i = 0; i < 16; ++i) { v[i] = r[15 - i] & 0xffffu; v[16 + i] = r[15 - i] >> 16; }
+        } else {
+            uint32_t pw[8];                                            // pw[b] = the run's four words of the plane that carries bit b
+#pragma unroll
+            for (int b = 0; b < 8; ++b) pw[b] = *reinterpret_cast<const uint32_t*>(in + a.plane[7 - b] + at);
+#pragma unroll
+            for (uint32_t u = 0; u < 4; ++u) {
+                // (bitswap1_decode_batch_strided_kernel's gather and transpose: afterwards byte i of hi:lo = voxel 7 - i)
+                constexpr uint32_t Zs = 0x0c;                         // v_perm selector: a zero byte
+                const uint32_t s01 = u | ((4u + u) << 8) | (Zs << 16) | (Zs << 24), s23 = Zs | (Zs << 8) | (u << 16) | ((4u + u) << 24);
+                uint32_t lo_ = __builtin_amdgcn_perm(pw[1], pw[0], s01) | __builtin_amdgcn_perm(pw[3], pw[2], s23);
+                uint32_t hi_ = __builtin_amdgcn_perm(pw[5], pw[4], s01) | __builtin_amdgcn_perm(pw[7], pw[6], s23);
+                uint32_t y;
+                y = (lo_ ^ (lo_ >> 7)) & 0x00AA00AAu; lo_ ^= y ^ (y << 7);
+                y = (hi_ ^ (hi_ >> 7)) & 0x00AA00AAu; hi_ ^= y ^ (y << 7);
+                y = (lo_ ^ (lo_ >> 14)) & 0x0000CCCCu; lo_ ^= y ^ (y << 14);
+                y = (hi_ ^ (hi_ >> 14)) & 0x0000CCCCu; hi_ ^= y ^ (y << 14);
+                y = (lo_ ^ (hi_ << 4)) & 0xF0F0F0F0u; lo_ ^= y; hi_ ^= y >> 4;
+                const uint32_t h4 = __builtin_bswap32(hi_), l4 = __builtin_bswap32(lo_);      // voxels 0..3 and 4..7 of word u, voxel k at byte k
+#pragma unroll
+                for (uint32_t k = 0; k < 4; ++k) {
+                    const uint32_t x0 = (h4 >> (8u * k)) & 0xffu, x1 = (l4 >> (8u * k)) & 0xffu;
+                    v[8 * u + k] = LUT ? (uint32_t)sl[x0] : x0;
+                    v[8 * u + 4 + k] = LUT ? (uint32_t)sl[x1] : x1;
+                }
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 32; ++i) acc[i] = project_combine(op, acc[i], v[i]);
+    }
+    uint32_t* __restrict__ out = static_cast<uint32_t*>(job->out);
+#pragma unroll
+    for (uint32_t i = 0; i < 32; ++i)
+        if (have && i >= cur.run_off) {                                // (sub-runs in ascending order: i is inside `cur` or in front of it)
+            out[cur.dst_off + (i - cur.run_off)] = acc[i];
+            if (i + 1 == cur.run_off + cur.len) have = window_clip_next(g, &c, &cur);
+        }
+}
+
+// a thread per image element of a dense volume's box: it walks the axis and stores its element once
+template <int ELEM>
+__global__ __launch_bounds__(256)
+void boxes_window_project_kernel(const BoxProjectJob* __restrict__ jobs, const uint32_t* __restrict__ first_tile, uint32_t njobs)
+{
+    const uint32_t j = batch_job_of_tile(first_tile, njobs);
+    const BoxProjectJob* __restrict__ job = jobs + j;
+    const uint64_t e = (uint64_t)(blockIdx.x - first_tile[j]) * 256u + threadIdx.x, E1 = job->E1;
+    if (e >= job->E0 * E1) return;
+    const uint64_t u = e / E1, v = e - u * E1, sa = job->sa, n = job->n;
+    const uint8_t* __restrict__ dense = static_cast<const uint8_t*>(job->dense);
+    const uint32_t op = job->op;
+    uint64_t at = job->base + u * job->su + v * job->sv;
+    uint32_t acc = project_neutral(op);
+    for (uint64_t k = 0; k < n; ++k, at += sa) acc = project_combine(op, acc, view_voxel_load<ELEM>(dense, at));
+    static_cast<uint32_t*>(job->out)[u * job->p0 + v] = acc;
+}
+
+static_assert(sizeof(Bitswap1BoxProjectJob) == kBitswap1BoxProjectJobBytes && sizeof(Bitswap1BoxProjectJob) % 16 == 0 &&
+                  offsetof(Bitswap1BoxProjectJob, op) == sizeof(Bitswap1BoxJob) && sizeof(BoxProjectJob) == kBoxProjectJobBytes,
+              "the projecting box job: Bitswap1BoxJob's fields, the image's behind them");
+
+hipError_t launch_boxes_project_init(const Bitswap1BoxProjectJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ngroups, hipStream_t stream)
+{
+    if (njobs == 0 || ngroups < njobs) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(boxes_project_init_kernel, dim3(ngroups), dim3(256), 0, stream, d_jobs, d_first_tile, njobs);
+    return hipGetLastError();
+}
+
+hipError_t launch_bitswap1_decode_range_windows_project(const uint8_t* in, const Bitswap1BoxProjectJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs,
+                                                        uint32_t ngroups, int elem_size, const uint16_t* lut, hipStream_t stream)
+{
+    if (njobs == 0 || ngroups < njobs || (elem_size != 1 && elem_size != 2) || (lut && elem_size != 1)) return hipErrorInvalidValue;
+    const dim3 grid(ngroups);
+    if (elem_size == 2) hipLaunchKernelGGL((bitswap1_decode_range_windows_project_kernel<2, false>), grid, dim3(256), 0, stream, in, d_jobs, d_first_tile, njobs, lut);
+    else if (lut) hipLaunchKernelGGL((bitswap1_decode_range_windows_project_kernel<1, true>), grid, dim3(256), 0, stream, in, d_jobs, d_first_tile, njobs, lut);
+    else hipLaunchKernelGGL((bitswap1_decode_range_windows_project_kernel<1, false>), grid, dim3(256), 0, stream, in, d_jobs, d_first_tile, njobs, lut);
+    return hipGetLastError();
+}
+
+hipError_t launch_bitswap1_decode_range_windows_project_walk(const uint8_t* in, const Bitswap1BoxProjectJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs,
+                                                             uint32_t ngroups, int elem_size, const uint16_t* lut, hipStream_t stream)
+{
+    if (njobs == 0 || ngroups < njobs || (elem_size != 1 && elem_size != 2) || (lut && elem_size != 1) || reinterpret_cast<uintptr_t>(in) % 4u) return hipErrorInvalidValue;
+    const dim3 grid(ngroups);
+    if (elem_size == 2) hipLaunchKernelGGL((bitswap1_decode_range_windows_project_walk_kernel<2, false>), grid, dim3(256), 0, stream, in, d_jobs, d_first_tile, njobs, lut);
+    else if (lut) hipLaunchKernelGGL((bitswap1_decode_range_windows_project_walk_kernel<1, true>), grid, dim3(256), 0, stream, in, d_jobs, d_first_tile, njobs, lut);
+    else hipLaunchKernelGGL((bitswap1_decode_range_windows_project_walk_kernel<1, false>), grid, dim3(256), 0, stream, in, d_jobs, d_first_tile, njobs, lut);
+    return hipGetLastError();
+}
+
+// bitswap1_box_job_ok for the projecting job; an image to combine into whose addressing matches the geometry's
+bool bitswap1_box_project_job_ok(const Bitswap1BoxProjectJob& j)
+{
+    const Bitswap1Range& r = j.r;
+    const WindowGeometry& g = j.g;
+    if (r.v1 <= r.v0 || r.w1 < r.w0 || !j.out || reinterpret_cast<uintptr_t>(j.out) % 4u || g.Z == 0 || g.Y == 0 || g.X == 0) return false;
+    if (j.op >= kProjectOps || j.axis > 2 || j.E0 == 0 || j.E1 == 0 || j.p0 < j.E1) return false;
+    // the clip's largest dst_off must name the image's last element
+    const uint64_t last = (g.Z - 1) * g.sz + (g.Y - 1) * g.sy + (g.X - 1);
+    const uint64_t elem = j.axis == 2 ? last >> project_row_shift(g) : last;
+    if (elem != (j.E0 - 1) * j.p0 + (j.E1 - 1)) return false;
+    if (j.axis == 2 && ((g.sy & (g.sy - 1)) != 0 || g.sy < g.X)) return false;
+    return ((g.oz * g.bY + g.oy) * g.bX + g.ox) >= r.v0 && ((g.oz + g.Z - 1) * g.bY + g.oy + g.Y - 1) * g.bX + g.ox + g.X <= r.v1;
+}
+
+hipError_t launch_boxes_window_project(const BoxProjectJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ngroups, int elem_size, hipStream_t stream)
+{
+    if (njobs == 0 || ngroups < njobs || (elem_size != 1 && elem_size != 2)) return hipErrorInvalidValue;
+    if (elem_size == 2) hipLaunchKernelGGL(boxes_window_project_kernel<2>, dim3(ngroups), dim3(256), 0, stream, d_jobs, d_first_tile, njobs);
+    else hipLaunchKernelGGL(boxes_window_project_kernel<1>, dim3(ngroups), dim3(256), 0, stream, d_jobs, d_first_tile, njobs);
+    return hipGetLastError();
+}
+
 hipError_t launch_batch_view_copy(const BatchViewJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ntiles, int elem_size, bool to_view,
                                   hipStream_t stream)
 {

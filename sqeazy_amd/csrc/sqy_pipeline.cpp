@@ -900,6 +900,57 @@ BoxPath compare_boxes_path(bool subset_form, RangeForm form, bool option_on)
     return BoxPath::whole_copy;
 }
 
+BoxPath project_boxes_path(bool subset_form, RangeForm form, bool option_on)
+{
+    if (!subset_form || !option_on) return BoxPath::whole_copy;
+    switch (form) {
+    case RangeForm::planes:
+    case RangeForm::planes_lut: return BoxPath::subset_transposer;
+    case RangeForm::plain:
+    case RangeForm::shuffle: return BoxPath::subset_copy;
+    }
+    return BoxPath::whole_copy;
+}
+
+bool admit_projection(const std::vector<uint64_t>& header_shape, const long* origin, const long* extent, unsigned rank, int axis, int op, uint64_t maxvoxel,
+                      const void* out, const long* out_strides, BatchWindow* w, Projection* p)
+{
+    if (!w || !p || !admit_window(header_shape, origin, extent, rank, w)) return false;
+    if (axis < 0 || (unsigned)axis >= rank || op < 0 || op > 2) return false;
+    if (!out || reinterpret_cast<uintptr_t>(out) % 4u) return false;
+    const uint64_t e[3] = {w->Z, w->Y, w->X};
+    Projection q;
+    q.axis3 = (uint32_t)axis + 3u - rank;
+    q.n = e[q.axis3];
+    // the sum bound: maxvoxel n >= 2^32 is refused -- and the 16-bit extent 65537 with it (65535 x 65537 = 2^32 - 1 would still fit; the
+    // stated bound for 16-bit voxels is 65536 | 65537, the stricter one, and it is kept)
+    if (op == 2 && q.n > (maxvoxel > 255 ? (uint64_t)65536 : 0xffffffffull / maxvoxel)) return false;
+    if (rank > 1) {
+        long shape[2];
+        unsigned k2 = 0;
+        for (unsigned k = 0; k < rank; ++k) if (k != (unsigned)axis) shape[k2++] = extent[k];
+        BatchView v;
+        if (!admit_view(shape, out_strides, rank - 1, &v)) return false;
+    }
+    // the image padded to two dimensions: what is left of (Z, Y, X)
+    const uint64_t plane = w->bY * w->bX;
+    const uint64_t step[3] = {plane, w->bX, 1};
+    const unsigned u = q.axis3 == 0 ? 1 : 0, v = q.axis3 == 2 ? 1 : 2;
+    q.E0 = e[u]; q.E1 = e[v];
+    q.su = step[u]; q.sv = step[v]; q.sa = step[q.axis3];
+    q.p0 = rank == 3 && out_strides ? (uint64_t)out_strides[0] : q.E1;     // (ranks 1 and 2: E0 = 1, the pitch is never stepped over)
+    if (q.axis3 == 0) { q.sz = 0; q.sy = q.p0; }
+    else if (q.axis3 == 1) { q.sz = q.p0; q.sy = 0; }
+    else {
+        uint64_t K = 1;
+        while (K < w->X) K <<= 1;                                       // (X <= the blob's row, below 2^62: no wrap)
+        if (q.p0 >= ((uint64_t)1 << 62) / K) return false;
+        q.sy = K; q.sz = K * q.p0;
+    }
+    *p = q;
+    return true;
+}
+
 // ---- a box written into one large blob (SQYAMD_Update_Box_*) ----
 UpdateBoxPath update_box_path(const UpdateBoxFacts& f)
 {

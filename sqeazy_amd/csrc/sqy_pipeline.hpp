@@ -540,6 +540,27 @@ BoxesPath decode_boxes_path(bool subset_form, RangeForm form, bool subset_option
 //   subset_copy        plain, shuffle: .. then ONE window compare with a job per box in the compaction
 //   whole_copy         every other blob, and every blob with the option off: decoded whole ONCE, ONE window compare with a job per box
 BoxPath compare_boxes_path(bool subset_form, RangeForm form, bool option_on);
+// Many boxes of one blob projected along an axis (SQYAMD_Project_Boxes_*).  option_on: project_boxes_subset; the rest as for
+// compare_boxes_path.  One job per box, ONE output launch on every path:
+//   subset_transposer  planes, planes_lut: the LZ4 frames of all boxes' z-ranges united, the outputs' neutral elements, then the projecting
+//                      job-table range transposer (integer atomics on the images; the box's voxels never exist in memory)
+//   subset_copy        plain, shuffle: .. then ONE projection launch with a job per box in the compaction (a thread per image element: it
+//                      stores every element itself, no neutral elements first)
+//   whole_copy         every other blob, and every blob with the option off: decoded whole ONCE, the same projection launch
+BoxPath project_boxes_path(bool subset_form, RangeForm form, bool option_on);
+// The admission of one box's projection, stated once (SQYAMD_Project_Boxes_*).  The box as admit_window admits it; `axis` in
+// [0, rank) and the same for every box; op 0 .. 2 (max, min, sum); the image at `out` (not NULL, 4-byte aligned) has the box's extent with
+// `axis` removed -- rank - 1 dimensions, ONE element for rank 1 -- and out_strides (rank - 1 pitches in elements, nullptr: dense) under
+// admit_view's rules.  The sum is refused where it might not fit 32 bits: maxvoxel x extent[axis] >= 2^32 (maxvoxel: 65535 for 16-bit
+// voxels, 255 for 8-bit ones).  On success: the window, and how the kernels address the image --
+//   axis3   the axis among the window's three padded dimensions (axis + 3 - rank)
+//   E0, E1  the image's extent padded to two dimensions, p0 its row pitch in elements
+//   sz, sy  the WindowGeometry pitches that make the clip's dst_off the image's element (sqy_batch_window.hpp states the rule)
+//   n       the box's extent along the axis; su, sv, sa: the steps in the BLOB's dense order from image row to row, column to column, and
+//           along the axis (the thread-per-element projection of a dense volume)
+struct Projection { uint32_t axis3 = 0; uint64_t E0 = 1, E1 = 1, p0 = 1, sz = 0, sy = 0, n = 1, su = 0, sv = 0, sa = 0; };
+bool admit_projection(const std::vector<uint64_t>& header_shape, const long* origin, const long* extent, unsigned rank, int axis, int op, uint64_t maxvoxel,
+                      const void* out, const long* out_strides, BatchWindow* w, Projection* p);
 
 struct Stage {
     std::string name;
