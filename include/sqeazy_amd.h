@@ -501,6 +501,39 @@ SQY_FUNCTION_PREFIX int SQYAMD_Project_Boxes_UI16(const char* src, long srclengt
                                                   int op, char* out, long out_capacity);
 SQY_FUNCTION_PREFIX int SQYAMD_Project_Boxes_UI8(const char* src, long srclength, long count, const long* origins, const long* extents, unsigned rank, int axis,
                                                  int op, char* out, long out_capacity);
+/* The same boxes at a coarser resolution: MANY boxes of one blob binned in one call -- an overview, a pyramid level, binned crops --, the
+ * full-resolution voxels never stored.  Boxes, rank, device, stream and thread rules are SQYAMD_Decode_Boxes_*'s (ranks 1 to 3, frames the
+ * first dimension).  bins: `rank` longs, each >= 1, the same for every box; op is one of SQYAMD_PROJECT_MAX, _MIN, _SUM.  Output i keeps
+ * the rank; its extent in dimension d is ceil(extent[d] / bins[d]).  Cell c covers the box's voxels [c bins, min((c + 1) bins, extent))
+ * per dimension: a partial cell at the box's far edge reduces the voxels it has, a bin larger than the extent is one cell.  Elements are
+ * uint32_t for every op and both voxel types, exact (behind the quantiser's look-up: of the 16-bit voxels out of the table); the mean is
+ * the caller's division by the cell's voxel count.  d_outs[i] is 4-byte aligned; out_strides + i rank gives output i's pitches in ELEMENTS
+ * under the view rules of SQYAMD_Decode_Boxes_*_Device (innermost 1, no dimension reaches into the next; NULL: every output dense).  Every
+ * element of every output is written once and nothing else: not the gaps between pitched rows, not d_src.  bins of all ones give
+ * SQYAMD_Decode_Boxes_*'s voxels, widened; bins[axis] >= extent[axis] with ones elsewhere SQYAMD_Project_Boxes_*'s image with a kept
+ * dimension of 1 -- correct, but such a box has few cells and so few workgroups: a projection is SQYAMD_Project_Boxes_*'s to do.
+ * Checked before a byte is written (else 1, every output untouched): what SQYAMD_Decode_Boxes_* checks for every box; bins NULL or an
+ * entry < 1; op out of range; a NULL or misaligned output; the stride rules; more workgroups than one launch takes; and SQYAMD_PROJECT_SUM
+ * where a cell might not fit: with V the product of min(bins[d], extent[d]) of the box, 16-bit voxels at V > 65536, 8-bit voxels at
+ * 255 V >= 2^32.  Whatever needs no header is checked before a device is looked for.  A damaged LZ4 frame that SOME box's z-range needs
+ * gives SQY_Decode's composite code; the outputs may then hold anything, and nothing outside them is written.  A damaged frame that no
+ * box needs goes unnoticed.
+ * How: one header fetch, the LZ4 frames the boxes' z-ranges need united and decoded by one launch, ONE output launch -- for
+ * `bitswap1->lz4` and `quantiser->bitswap1->lz4` a workgroup per block of one box's cells (one cell layer, a band of cell rows, a strip of
+ * cell columns): accumulators in LDS, the plane words of the block's footprint transposed and reduced in registers, LDS integer atomics,
+ * every cell stored once -- no global atomic, no neutral-element launch; for `lz4` and `frame_shuffle->lz4` one launch with a thread per
+ * output cell in the compaction.  Every other blob is decoded whole ONCE into the workspace and the same per-cell launch takes all boxes
+ * ("bin_boxes_subset" = 0: every blob -- the same outputs). */
+SQY_FUNCTION_PREFIX int SQYAMD_Bin_Boxes_UI16_Device(const void* d_src, long srclength, long count, const long* origins, const long* extents, unsigned rank,
+                                                     const long* bins, int op, void* const* d_outs, const long* out_strides, void* hip_stream);
+SQY_FUNCTION_PREFIX int SQYAMD_Bin_Boxes_UI8_Device(const void* d_src, long srclength, long count, const long* origins, const long* extents, unsigned rank,
+                                                    const long* bins, int op, void* const* d_outs, const long* out_strides, void* hip_stream);
+/* host-pointer variants: the blob is staged ONCE; the outputs come back dense and back to back in box order, as uint32_t (1 where
+ * out_capacity, in bytes, is too small) */
+SQY_FUNCTION_PREFIX int SQYAMD_Bin_Boxes_UI16(const char* src, long srclength, long count, const long* origins, const long* extents, unsigned rank,
+                                              const long* bins, int op, char* out, long out_capacity);
+SQY_FUNCTION_PREFIX int SQYAMD_Bin_Boxes_UI8(const char* src, long srclength, long count, const long* origins, const long* extents, unsigned rank,
+                                             const long* bins, int op, char* out, long out_capacity);
 /* The write of a box into a tiled store, whose border cuts through tiles: every tile under the box is read, modified and written again
  * with ONE call.  Old blob i lies at d_src + src_offsets[i], src_lengths[i] bytes (host arrays; any alignment): a complete sqeazy blob of
  * the entry point's voxel type, any pipeline, any layout.  Window i is the box [origins row i, + win_shapes row i) of that blob's volume
@@ -691,6 +724,9 @@ SQY_FUNCTION_PREFIX void SQYAMD_Release_Workspace(void);
  *   "project_boxes_walk"              1 [SQY_NO_PROJECT_BOXES_WALK=1 -> 0]  SQYAMD_Project_Boxes_* along axis 0 on the transposer path: a thread walks z over
  *                                     the box's frames, reduces in registers and stores once, where every box's frames are whole 32-voxel runs on the
  *                                     4-byte grid (0: always the integer atomics -- same images)
+ *   "bin_boxes_subset"                1 [SQY_NO_BIN_BOXES_SUBSET=1 -> 0]  SQYAMD_Bin_Boxes_*: only the LZ4 frames the boxes' z-ranges need, the binning
+ *                                     kernel (a workgroup per block of cells, LDS accumulators) or one per-cell launch in the compaction, where the
+ *                                     pipeline allows (0: every blob decoded whole once and one per-cell launch -- same outputs)
  *   "decode_slabs_joint"              1 [SQY_NO_DECODE_SLABS_JOINT=1 -> 0]  SQYAMD_Decode_Slabs_*: the chunked LZ4 blobs of a group indexed and
  *                                     decoded by one launch each (0: every blob on its own, as by SQYAMD_Decode_*_Device -- same bytes)
  *   "decode_batch_joint"              1 [SQY_NO_DECODE_BATCH_JOINT=1 -> 0]  SQYAMD_Decode_Batch_*: the joint-eligible blobs of a group ranked, decoded and

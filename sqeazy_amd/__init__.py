@@ -43,6 +43,7 @@ EXPORTED_SYMBOLS = (
     "SQYAMD_Decode_Boxes_UI16_Device", "SQYAMD_Decode_Boxes_UI8_Device", "SQYAMD_Decode_Boxes_UI16", "SQYAMD_Decode_Boxes_UI8",
     "SQYAMD_Compare_Boxes_UI16_Device", "SQYAMD_Compare_Boxes_UI8_Device", "SQYAMD_Compare_Boxes_UI16", "SQYAMD_Compare_Boxes_UI8",
     "SQYAMD_Project_Boxes_UI16_Device", "SQYAMD_Project_Boxes_UI8_Device", "SQYAMD_Project_Boxes_UI16", "SQYAMD_Project_Boxes_UI8",
+    "SQYAMD_Bin_Boxes_UI16_Device", "SQYAMD_Bin_Boxes_UI8_Device", "SQYAMD_Bin_Boxes_UI16", "SQYAMD_Bin_Boxes_UI8",
     "SQYAMD_Decode_Slabs_UI16_Device", "SQYAMD_Decode_Slabs_UI8_Device", "SQYAMD_Decode_Slabs_UI16", "SQYAMD_Decode_Slabs_UI8",
     "SQYAMD_Decode_Batch_UI16_Device", "SQYAMD_Decode_Batch_UI8_Device", "SQYAMD_Decode_Batch_UI16", "SQYAMD_Decode_Batch_UI8",
     "SQYAMD_Profile_Enable", "SQYAMD_Profile_Reset", "SQYAMD_Profile_Get",
@@ -159,6 +160,12 @@ def lib():
                                       ctypes.POINTER(ctypes.c_void_p), c_long_p, ctypes.c_void_p]
         for f in ("SQYAMD_Project_Boxes_UI8", "SQYAMD_Project_Boxes_UI16"):
             getattr(L, f).argtypes = [ctypes.c_void_p, ctypes.c_long, ctypes.c_long, c_long_p, c_long_p, ctypes.c_uint, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                      ctypes.c_long]
+        for f in ("SQYAMD_Bin_Boxes_UI8_Device", "SQYAMD_Bin_Boxes_UI16_Device"):
+            getattr(L, f).argtypes = [ctypes.c_void_p, ctypes.c_long, ctypes.c_long, c_long_p, c_long_p, ctypes.c_uint, c_long_p, ctypes.c_int,
+                                      ctypes.POINTER(ctypes.c_void_p), c_long_p, ctypes.c_void_p]
+        for f in ("SQYAMD_Bin_Boxes_UI8", "SQYAMD_Bin_Boxes_UI16"):
+            getattr(L, f).argtypes = [ctypes.c_void_p, ctypes.c_long, ctypes.c_long, c_long_p, c_long_p, ctypes.c_uint, c_long_p, ctypes.c_int, ctypes.c_void_p,
                                       ctypes.c_long]
         for f in ("SQYAMD_Decode_Slabs_UI8_Device", "SQYAMD_Decode_Slabs_UI16_Device"):
             getattr(L, f).argtypes = [ctypes.c_void_p, c_long_p, c_long_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_long, c_long_p, ctypes.c_int,
@@ -746,6 +753,65 @@ def project_boxes(blob, origins, extents, axis, op="max"):
     if mean:
         images = [im.astype(np.float64) / np.float64(int(ext[int(axis)])) for im, ext in zip(images, extents)]
     return 0, images
+
+
+def bin_boxes_device(d_src, srclength, origins, extents, bins, op, d_outs, out_strides, dtype, stream=None, count=None):
+    """SQYAMD_Bin_Boxes_*_Device on raw device pointers (ints): box i of extent extents[i] that begins at voxel origins[i] of the ONE blob at
+    d_src, read at a coarser resolution -- cells of `bins` voxels (one entry per dimension, the same for all boxes) reduced with op ("max",
+    "min", "sum" or PROJECT_*) -- into the uint32 output at d_outs[i], whose shape is ceil(extents[i] / bins) and whose pitches in elements
+    are out_strides[i] (None: every output dense).  count: the number of boxes (default: as many as there are extents).  Returns rc."""
+    n = len(extents) if extents is not None else len(origins or ())
+    first = (extents or origins or [()])[0] if n else ()
+    ptrs = None if d_outs is None else (ctypes.c_void_p * max(len(d_outs), 1))(*[None if p is None else int(p) for p in d_outs])
+    return getattr(lib(), "SQYAMD_Bin_Boxes_%s_Device" % _suffix(dtype))(
+        ctypes.c_void_p(None if d_src is None else int(d_src)), ctypes.c_long(int(srclength)), ctypes.c_long(n if count is None else int(count)), _long_rows(origins),
+        _long_rows(extents), ctypes.c_uint(len(first)), None if bins is None else _long_rows([bins]), ctypes.c_int(_project_op(op)), ptrs,
+        None if out_strides is None else _long_rows(out_strides), ctypes.c_void_p(stream or 0))
+
+
+def bin_shape(extent, bins):
+    """the shape of a box's binned output: ceil(extent / bins) per dimension"""
+    return tuple(-(-max(int(e), 0) // max(int(b), 1)) for e, b in zip(extent, bins))
+
+
+def bin_counts(extent, bins):
+    """the number of voxels in every cell of a box's binned output (partial cells at the far edges hold fewer), as float64"""
+    n = np.ones((), np.float64)
+    for e, b in zip(extent, bins):
+        e, b = int(e), min(int(b), int(e))
+        edge = np.minimum(np.arange(b, e + b, b), e) - np.arange(0, e, b)
+        n = np.multiply.outer(n, edge.astype(np.float64))
+    return n
+
+
+def bin_boxes(blob, origins, extents, bins, op="max"):
+    """SQYAMD_Bin_Boxes_UI8/UI16: the boxes [origins[i], origins[i] + extents[i]) of the blob's volume read at a coarser resolution with one
+    call; op "max", "min", "sum" (or PROJECT_*) gives uint32 arrays, "mean" the sum divided by each cell's actual voxel count in float64 (a
+    partial cell by fewer).  Returns (rc, [ndarray of shape ceil(extents[i] / bins), ..] or None)."""
+    blob = bytes(blob)
+    size = decompressed_sizeof(blob)
+    if size not in (1, 2) or not decompressed_shape(blob) or len(origins) != len(extents) or not len(extents):
+        return 1, None
+    mean = op == "mean"
+    code = PROJECT_SUM if mean else _project_op(op)
+    dtype = np.uint16 if size == 2 else np.uint8
+    rank = len(extents[0])
+    if bins is None or len(bins) != rank or any(int(b) < 1 for b in bins):
+        return 1, None
+    shapes = [bin_shape(ext, bins) for ext in extents]
+    counts = [int(np.prod(sh, dtype=np.int64)) for sh in shapes]
+    out = np.empty(sum(counts), dtype=np.uint32)
+    src = np.frombuffer(blob, dtype=np.uint8)
+    rc = getattr(lib(), "SQYAMD_Bin_Boxes_" + _suffix(dtype))(src.ctypes.data, ctypes.c_long(len(blob)), ctypes.c_long(len(extents)), _long_rows(origins),
+                                                              _long_rows(extents), ctypes.c_uint(rank), _long_rows([bins]), ctypes.c_int(code), out.ctypes.data,
+                                                              ctypes.c_long(out.nbytes))
+    if rc:
+        return rc, None
+    ends = np.cumsum(counts)
+    cells = [out[e - c:e].reshape(sh) for e, c, sh in zip(ends, counts, shapes)]
+    if mean:
+        cells = [a.astype(np.float64) / bin_counts(ext, bins) for a, ext in zip(cells, extents)]
+    return 0, cells
 
 
 def update_batch_window_device(pipeline, d_src, offsets, lengths, origins, d_wins, shapes, strides, dtype, d_dst, slot_capacity, nthreads=0, stream=None):

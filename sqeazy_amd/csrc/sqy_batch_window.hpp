@@ -286,5 +286,90 @@ SQY_VIEW_HD inline void window_project16(Sink& sink, const WindowGeometry& g, Wi
     }
 }
 
+// ---- boxes read at a coarser resolution (SQYAMD_Bin_Boxes_*) ----
+// A box of extent (Z, Y, X) under bins (bz, by, bx) -- clamped to the extent by sqy::admit_binning, so a bin never exceeds its dimension --
+// has the cell grid C = ceil(extent / bins); cell c reduces the box's voxels [c bins, min((c + 1) bins, extent)).  The bit-plane kernel
+// gives every workgroup a BLOCK of cells (sqy::bin_boxes_plan states the tiling): ONE cell layer cz, the cell rows [cy0, cy0 + ncy), the
+// cell columns [cx0, cx0 + ncx) -- at most kBinBlockCells accumulators in LDS, and a footprint in a frame that is a band of rows of the
+// blob cut to the strip's columns.  Block `own` of a box is layer own / (nbands nstrips), band .. / nstrips, strip .. % nstrips.
+// The workgroup's threads share the ITEMS of the block: item t is one 32-voxel run of the blob's dense order on the absolute grid
+// (run r holds the voxels [32 r, 32 r + 32): four bytes of every plane) in one frame of the footprint; where a frame is a whole number
+// of runs (`zreg`) an item is the run in the layer's FIRST frame and the thread reduces the same positions of the layer's other frames
+// into it in registers first.  The clip (window_clip_*, the footprint's geometry with Z = 1 at the item's frame, sy = K the power of
+// two >= the footprint's width, sz = 0) names the run's voxels inside the footprint: dst_off = (y - oy) K + (x - ox).  bin_run_cells
+// reduces the neighbouring voxels of one cell in registers and sends ONE combine per piece of a cell's row to the sink -- the kernel's
+// sink is an LDS atomic on the block's accumulators, the host test's an array (tests/sanitize/bin_boxes_test.cpp holds the whole walk
+// against a triple loop).
+constexpr uint32_t kBinBlockCells = 8192;               // the accumulators of a block: 32 KiB of LDS, well under the CU's 160 KiB
+constexpr uint64_t kBinBlockVoxels = 1u << 16;          // the footprint a block is sized for (256 threads x 8 runs) where the cells allow it
+
+struct BinPlan { uint64_t C[3]; uint64_t band, strip, nbands, nstrips, blocks; };
+struct BinBlock { uint64_t cz, cy0, ncy, cx0, ncx; };
+SQY_VIEW_HD inline BinBlock bin_block_of(const BinPlan& p, uint64_t own)
+{
+    const uint64_t per_layer = p.nbands * p.nstrips, cz = own / per_layer, r = own - cz * per_layer, b = r / p.nstrips, s = r - b * p.nstrips;
+    const uint64_t cy0 = b * p.band, cx0 = s * p.strip;
+    return BinBlock{cz, cy0, p.C[1] - cy0 < p.band ? p.C[1] - cy0 : p.band, cx0, p.C[2] - cx0 < p.strip ? p.C[2] - cx0 : p.strip};
+}
+
+// a block's footprint: the frames [z0, z0 + nz) of its cell layer and, in each, the clip's geometry (g.oz is the caller's to step)
+struct BinFootprint { WindowGeometry g; uint64_t z0, nz; };
+SQY_VIEW_HD inline BinFootprint bin_block_footprint(const WindowGeometry& box, const uint64_t bins[3], const BinBlock& b)
+{
+    const uint64_t z = b.cz * bins[0], y = b.cy0 * bins[1], x = b.cx0 * bins[2];
+    const uint64_t nz = box.Z - z < bins[0] ? box.Z - z : bins[0];
+    const uint64_t Y = box.Y - y < b.ncy * bins[1] ? box.Y - y : b.ncy * bins[1], X = box.X - x < b.ncx * bins[2] ? box.X - x : b.ncx * bins[2];
+    uint64_t K = 1;
+    while (K < X) K <<= 1;
+    return BinFootprint{WindowGeometry{box.bY, box.bX, box.oz + z, box.oy + y, box.ox + x, 1, Y, X, 0, K}, box.oz + z, nz};
+}
+// the runs that hold a voxel of the footprint in frame z, and a bound on their number that holds for every frame
+SQY_VIEW_HD inline uint64_t bin_frame_first_run(const WindowGeometry& g, uint64_t z) { return ((z * g.bY + g.oy) * g.bX + g.ox) / 32; }
+SQY_VIEW_HD inline uint64_t bin_frame_last_run(const WindowGeometry& g, uint64_t z) { return ((z * g.bY + g.oy + g.Y - 1) * g.bX + g.ox + g.X - 1) / 32; }
+SQY_VIEW_HD inline uint64_t bin_frame_runs(const WindowGeometry& g) { return ((g.Y - 1) * g.bX + g.X + 31) / 32 + 1; }
+SQY_VIEW_HD inline uint64_t bin_block_items(const BinFootprint& f, bool zreg) { return (zreg ? 1 : f.nz) * bin_frame_runs(f.g); }
+// item t of a block: its frame and run (false: the frame has no such run)
+SQY_VIEW_HD inline bool bin_block_item(const BinFootprint& f, bool zreg, uint64_t t, uint64_t* z, uint64_t* run)
+{
+    const uint64_t nr = bin_frame_runs(f.g), zi = zreg ? 0 : t / nr, k = t - zi * nr;
+    *z = f.z0 + zi;
+    *run = bin_frame_first_run(f.g, *z) + k;
+    return *run <= bin_frame_last_run(f.g, *z);
+}
+
+SQY_VIEW_HD inline uint64_t bin_div(uint64_t a, uint64_t b) { return ((a | b) >> 32) == 0 ? (uint64_t)((uint32_t)a / (uint32_t)b) : a / b; }
+
+// The 32 values v of a run whose clip stands at its first sub-run `cur` (`have`: there is one): every piece of a cell's row inside the
+// run is reduced here and sent once -- sink.combine(cell, value), cell = (cy - cy0) ncx + (cx - cx0) within the block.  by, bx: the
+// bins along y and x; ncx: the block's cell columns.
+template <class Sink>
+SQY_VIEW_HD inline void bin_run_cells(Sink& sink, const WindowGeometry& g, WindowClip& c, WindowPiece& cur, bool& have, const uint32_t (&v)[32], uint64_t by, uint64_t bx,
+                                      uint64_t ncx, uint32_t op)
+{
+    const uint32_t shift = project_row_shift(g);
+    uint64_t cell = 0, left = 0;                                        // the cell the walk stands in, what is left of its row piece
+    uint32_t acc = project_neutral(op);
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (uint32_t i = 0; i < 32; ++i)
+        if (have && i >= cur.run_off) {                                 // (sub-runs in ascending order: i is inside `cur` or in front of it)
+            if (i == cur.run_off) {
+                const uint64_t y = cur.dst_off >> shift, x = cur.dst_off & (g.sy - 1), cx = bin_div(x, bx);
+                cell = bin_div(y, by) * ncx + cx;
+                left = bx - (x - cx * bx);
+            }
+            acc = project_combine(op, acc, v[i]);
+            const bool last = i + 1 == cur.run_off + cur.len;
+            if (--left == 0 || last) {
+                sink.combine(cell, acc);
+                acc = project_neutral(op);
+                ++cell;
+                left = bx;
+            }
+            if (last) have = window_clip_next(g, &c, &cur);
+        }
+}
+
 } // namespace sqy
 #endif

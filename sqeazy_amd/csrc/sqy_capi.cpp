@@ -84,6 +84,7 @@ struct Options {
     std::atomic<long> compare_boxes_subset;             // compare of many boxes of one blob: only the LZ4 frames the boxes' z-ranges need, the comparing range transposer or one compare in the compaction, where sqy::compare_boxes_path allows (0: the blob decoded whole once, one window compare)
     std::atomic<long> project_boxes_walk;               // projection along axis 0 on the transposer path: the z-walking form (registers, plain stores) where every box is on the 32-voxel grid (0: always the atomics -- same images)
     std::atomic<long> project_boxes_subset;             // projection of many boxes of one blob: only the LZ4 frames the boxes' z-ranges need, the projecting range transposer or one projection in the compaction, where sqy::project_boxes_path allows (0: the blob decoded whole once, one projection launch)
+    std::atomic<long> bin_boxes_subset;                 // binned read of many boxes of one blob: only the LZ4 frames the boxes' z-ranges need, the binning job-table kernel (a workgroup per block of cells, LDS accumulators) or one per-cell launch in the compaction, where sqy::bin_boxes_path allows (0: the blob decoded whole once, one per-cell launch)
     std::atomic<long> update_box_subset;                // box update of one blob: only the LZ4 frames the box's z-range needs are decoded, patched, parsed again and spliced between the old ones, where sqy::update_box_path allows (0: whole decode, one paste, the single call's encode)
     std::atomic<long> update_boxes_subset;              // update of many boxes of one blob: update_box_subset's stages, each once for all boxes (0: the blob decoded whole once, the pastes layer by layer, the single call's encode)
     std::atomic<long> decode_slabs_joint;               // slab-set decode: the chunked LZ4 blobs of a group indexed and decoded by one launch each (0: blob by blob)
@@ -112,7 +113,8 @@ struct Options {
           host_l2_bytes((long)sqy::host_l2_cache_bytes()), decode_frames_subset(env_flag("SQY_NO_DECODE_FRAMES_SUBSET") ? 0 : 1),
           decode_box_subset(env_flag("SQY_NO_DECODE_BOX_SUBSET") ? 0 : 1), decode_boxes_joint(env_flag("SQY_NO_DECODE_BOXES_JOINT") ? 0 : 1),
           compare_boxes_subset(env_flag("SQY_NO_COMPARE_BOXES_SUBSET") ? 0 : 1),
-          project_boxes_walk(env_flag("SQY_NO_PROJECT_BOXES_WALK") ? 0 : 1), project_boxes_subset(env_flag("SQY_NO_PROJECT_BOXES_SUBSET") ? 0 : 1), update_box_subset(env_flag("SQY_NO_UPDATE_BOX_SUBSET") ? 0 : 1),
+          project_boxes_walk(env_flag("SQY_NO_PROJECT_BOXES_WALK") ? 0 : 1), project_boxes_subset(env_flag("SQY_NO_PROJECT_BOXES_SUBSET") ? 0 : 1),
+          bin_boxes_subset(env_flag("SQY_NO_BIN_BOXES_SUBSET") ? 0 : 1), update_box_subset(env_flag("SQY_NO_UPDATE_BOX_SUBSET") ? 0 : 1),
           update_boxes_subset(env_flag("SQY_NO_UPDATE_BOXES_SUBSET") ? 0 : 1),
           decode_slabs_joint(env_flag("SQY_NO_DECODE_SLABS_JOINT") ? 0 : 1), decode_batch_joint(env_flag("SQY_NO_DECODE_BATCH_JOINT") ? 0 : 1),
           decode_batch_group_bytes(env_number("SQY_DECODE_BATCH_GROUP_BYTES", (long)kSlabsGroupBytes, 1, (long)kSlabsGroupBytes)), encode_batch_joint(env_flag("SQY_NO_ENCODE_BATCH_JOINT") ? 0 : 1),
@@ -141,6 +143,7 @@ struct Options {
         if (!std::strcmp(name, "compare_boxes_subset")) return &compare_boxes_subset;
         if (!std::strcmp(name, "project_boxes_subset")) return &project_boxes_subset;
         if (!std::strcmp(name, "project_boxes_walk")) return &project_boxes_walk;
+        if (!std::strcmp(name, "bin_boxes_subset")) return &bin_boxes_subset;
         if (!std::strcmp(name, "update_box_subset")) return &update_box_subset;
         if (!std::strcmp(name, "update_boxes_subset")) return &update_boxes_subset;
         if (!std::strcmp(name, "decode_slabs_joint")) return &decode_slabs_joint;
@@ -4154,6 +4157,197 @@ int project_boxes_from_host(const char* src, long srclength, long count, const l
     });
 }
 
+// ---- many boxes of one large blob read at a coarser resolution (SQYAMD_Bin_Boxes_*) -----------------------------------------
+// project_boxes_on_device with cells for image elements: ONE header fetch, the LZ4 frames of all boxes' z-ranges united, ONE output
+// launch; sqy::bin_boxes_path says what runs, sqy::admit_binning what is admitted and sqy::bin_boxes_plan how the bit-plane kernel's
+// workgroups share a box's cells.  No neutral-element launch, no global atomics.  Nothing but the outputs' cells is written outside
+// the workspace.
+static_assert(sizeof(sqy::Bitswap1BoxBinJob) == sqy::kBitswap1BoxBinJobBytes && sizeof(sqy::BoxBinJob) == sqy::kBoxBinJobBytes, "the binning jobs' layout");
+
+// the thread-per-cell launch's jobs: box i (w, its binning q) of the dense volume at `dense` into the output at `out`
+struct BinLaunch : TiledJobs<sqy::BoxBinJob> {
+    void add(void* out, const void* dense, const sqy::BatchWindow& w, const sqy::Binning& q, int op)
+    {
+        jobs.push_back(sqy::BoxBinJob{dense, out, (w.oz * w.bY + w.oy) * w.bX + w.ox, w.bY * w.bX, w.bX, {w.Z, w.Y, w.X}, {q.bins[0], q.bins[1], q.bins[2]},
+                                      {q.C[0], q.C[1], q.C[2]}, q.pz, q.py, (uint32_t)op, 0, 0});
+        first_tile.push_back(ntiles);
+        ntiles += (uint32_t)((q.C[0] * q.C[1] * q.C[2] + 255) / 256);
+    }
+};
+int launch_boxes_bin(Context& cx, hipStream_t stream, BinLaunch& l, int elem_size)
+{
+    std::vector<PendingEvent>* pend = &cx.pending;
+    const uint32_t* d_tiles = nullptr;
+    if (l.upload(stream, cx.ws.boxes_jobs, &d_tiles)) return 1;
+    SQY_TIMED("boxes_window_bin", sqy::launch_boxes_window_bin(static_cast<const sqy::BoxBinJob*>(cx.ws.boxes_jobs.p), d_tiles, (uint32_t)l.jobs.size(), l.ntiles, elem_size, stream));
+    return 0;
+}
+
+// the binning's launch behind DecodeCall::frames_subset: box i (ws[i], qs[i]) of the united frames in c.range_buf into outs[i]
+int boxes_range_bin(DecodeCall& c, BinLaunch& l, TiledJobs<sqy::Bitswap1BoxBinJob>& tj, const std::vector<sqy::BatchWindow>& ws, const std::vector<sqy::Binning>& qs,
+                    void* const* outs, unsigned rank, int op)
+{
+    hipStream_t stream = c.stream;
+    std::vector<PendingEvent>* pend = c.pend;
+    const sqy::FrameRangesPlan& p = c.ranges_plan;
+    const size_t count = ws.size();
+    if (p.boxes.size() != count) return 1;
+    if (sqy::bin_boxes_path(true, c.range_form, true) == sqy::BoxPath::subset_transposer) {
+        const uint16_t* lut = nullptr;
+        if (c.range_lut(&lut)) return 1;
+        for (size_t i = 0; i < count; ++i) {
+            const sqy::BatchWindow& w = ws[i];
+            const sqy::Binning& q = qs[i];
+            const sqy::FrameRangesBox& b = p.boxes[i];
+            sqy::Bitswap1BoxBinJob j{};
+            j.out = outs[i];
+            j.g = sqy::WindowGeometry{w.bY, w.bX, w.oz, w.oy, w.ox, w.Z, w.Y, w.X, q.pz, q.py};
+            std::copy(b.plane, b.plane + 16, j.r.plane);
+            j.r.tail = b.tail; j.r.w0 = b.w0; j.r.w1 = b.w1; j.r.v0 = b.v0; j.r.v1 = b.v1; j.r.L = b.L;
+            j.t0 = sqy::range_first_thread(b.w0, 128u / (8u * (uint32_t)p.we));
+            std::copy(q.bins, q.bins + 3, j.bins);
+            j.plan = sqy::bin_boxes_plan(q.C, q.bins, w.X);
+            j.op = (uint32_t)op;
+            j.zreg = sqy::bitswap1_box_bin_zreg_ok(j) ? 1u : 0u;
+            if (!sqy::bitswap1_box_bin_job_ok(j) || (uint64_t)tj.ntiles + j.plan.blocks > 0x7fffffffull) return 1;
+            tj.jobs.push_back(j);
+            tj.first_tile.push_back(tj.ntiles);
+            tj.ntiles += (uint32_t)j.plan.blocks;
+        }
+        const uint32_t* d_tiles = nullptr;
+        if (tj.upload(stream, c.cx.ws.boxes_jobs, &d_tiles)) return 1;
+        SQY_TIMED(lut ? "bitswap1_quantiser_bin_boxes" : "bitswap1_bin_boxes",
+                  sqy::launch_bitswap1_decode_range_windows_bin(c.range_buf, static_cast<const sqy::Bitswap1BoxBinJob*>(c.cx.ws.boxes_jobs.p), d_tiles, (uint32_t)count, tj.ntiles,
+                                                                p.we, lut, stream));
+        return 0;
+    }
+    // plain, shuffle: box i's range in the workspace is a blob of its frames, the box begins at its first one (boxes_range_out's geometry)
+    for (size_t i = 0; i < count; ++i) {
+        sqy::BatchWindow in_range = ws[i];
+        if (rank == 3) { in_range.bZ = in_range.Z; in_range.oz = 0; }
+        else if (rank == 2) { in_range.bY = in_range.Y; in_range.oy = 0; }
+        else { in_range.bX = in_range.X; in_range.ox = 0; }
+        l.add(outs[i], c.range_buf + p.boxes[i].range_at, in_range, qs[i], op);
+    }
+    return launch_boxes_bin(c.cx, stream, l, c.h.elem_size());
+}
+
+// Box i = [origins + i rank, .. + extents + i rank) of the blob binned into the output at d_outs[i] (out_strides + i rank, or dense).
+// sqy::admit_binning for every box and the launches' sizes -- all before anything is written
+int bin_boxes_on_device(Context& cx, const void* d_src_v, uint64_t srclen, size_t count, const long* origins, const long* extents, unsigned rank, const long* bins, int op,
+                        void* const* d_outs, const long* out_strides, int want_elem, hipStream_t stream)
+{
+    const uint8_t* d_src = static_cast<const uint8_t*>(d_src_v);
+    DrainOnExit drain{stream, &cx.pending, cx.side};
+    sqy::HeaderInfo h;
+    if (fetch_header(d_src, srclen, stream, h)) return 1;
+    uint64_t raw_bytes = 0;
+    if (!admit_blob(h, srclen, want_elem, &raw_bytes)) return 1;
+    std::vector<sqy::BatchWindow> ws(count);
+    std::vector<sqy::Binning> qs(count);
+    std::vector<std::pair<uint64_t, uint64_t>> ranges(count);
+    uint64_t cell_groups = 0, blocks = 0;                    // what the one output launch may hold, whichever it is
+    for (size_t i = 0; i < count; ++i) {
+        const long* o = origins + i * rank;
+        const long* e = extents + i * rank;
+        if (!sqy::admit_binning(h.shape, o, e, rank, bins, op, want_elem == 2 ? 65535u : 255u, d_outs[i], out_strides ? out_strides + i * rank : nullptr, &ws[i], &qs[i])) {
+            std::fprintf(stderr, "[sqeazy]\t bin boxes: box %zu does not lie inside the blob's shape or has another rank, or a cell's sum might not fit 32 bits\n", i);
+            return 1;
+        }
+        ranges[i] = {(uint64_t)o[0], (uint64_t)e[0]};
+        cell_groups += (qs[i].C[0] * qs[i].C[1] * qs[i].C[2] + 255) / 256;           // (the cells are no more than the blob's voxels: no wrap)
+        blocks += sqy::bin_boxes_plan(qs[i].C, qs[i].bins, ws[i].X).blocks;
+        if (std::max(cell_groups, blocks) > 0x7fffffffull) {             // (checked box by box: the sums stay far below 2^64)
+            std::fprintf(stderr, "[sqeazy]\t bin boxes: too many workgroups for one launch\n");
+            return 1;
+        }
+    }
+    BinLaunch l;                                                        // (both wait for the stream before their tables go)
+    TiledJobs<sqy::Bitswap1BoxBinJob> tj;
+    if (g_opt.bin_boxes_subset.load()) {
+        DecodeCall c(cx, stream, nullptr, h, Pipeline::from_string(h.pipename), raw_bytes / (uint64_t)want_elem, d_src + h.size);
+        bool taken = false;
+        if (const int rc = c.frames_subset(ranges, false, &taken)) return rc;
+        if (taken) {
+            if (const int rc = boxes_range_bin(c, l, tj, ws, qs, d_outs, rank, op)) return rc;
+            return c.finish();
+        }
+    }
+    // sqy::BoxPath::whole_copy: the whole volume ONCE, then all boxes in one launch
+    if (cx.ws.range_full.ensure(std::max<uint64_t>(raw_bytes, 16))) return 1;
+    if (const int rc = decode_on_device(cx, d_src_v, srclen, cx.ws.range_full.p, raw_bytes, want_elem, stream)) return rc;
+    for (size_t i = 0; i < count; ++i) l.add(d_outs[i], cx.ws.range_full.p, ws[i], qs[i], op);
+    if (launch_boxes_bin(cx, stream, l, want_elem)) return 1;
+    SQY_HIP(hipStreamSynchronize(stream));
+    if (g_prof_on.load()) prof_collect(cx.pending);
+    return 0;
+}
+
+// what SQYAMD_Bin_Boxes_* checks without a header, before a device is looked for: boxes_arguments_ok, and sqy::admit_binning of every box
+// against the smallest shape that holds it -- the bins, the op, the output's pointer and pitches, the sum bound
+bool bin_arguments_ok(const void* src, long srclength, long count, const long* origins, const long* extents, unsigned rank, const long* bins, int op, void* const* outs,
+                      const long* out_strides, int elem_size)
+{
+    if (!bins || !boxes_arguments_ok(src, srclength, count, origins, outs, extents, rank)) return false;
+    for (long i = 0; i < count; ++i) {
+        const long* o = origins + (size_t)i * rank;
+        const long* e = extents + (size_t)i * rank;
+        std::vector<uint64_t> shape(rank);
+        for (unsigned k = 0; k < rank; ++k) shape[k] = (uint64_t)o[k] + (uint64_t)std::max(e[k], 0l);     // (both below 2^63: no wrap)
+        sqy::BatchWindow w;
+        sqy::Binning q;
+        const void* out = outs ? outs[i] : static_cast<const void*>(&q);                                   // (host variant: the outputs are the library's)
+        if (!sqy::admit_binning(shape, o, e, rank, bins, op, elem_size == 2 ? 65535u : 255u, out, outs && out_strides ? out_strides + (size_t)i * rank : nullptr, &w, &q))
+            return false;
+    }
+    return true;
+}
+
+int bin_boxes_device(const void* d_src, long srclength, long count, const long* origins, const long* extents, unsigned rank, const long* bins, int op, void* const* d_outs,
+                     const long* out_strides, int elem_size, void* hip_stream)
+{
+    if (!d_outs || !bin_arguments_ok(d_src, srclength, count, origins, extents, rank, bins, op, d_outs, out_strides, elem_size)) {
+        std::fprintf(stderr, "[sqeazy]\t bin boxes: bad arguments\n");
+        return 1;
+    }
+    ContextLease lease;
+    if (!lease.ctx) { std::fprintf(stderr, "[sqeazy]\t no usable HIP device\n"); return 1; }
+    return bin_boxes_on_device(*lease.ctx, d_src, (uint64_t)srclength, (size_t)count, origins, extents, rank, bins, op, d_outs, out_strides, elem_size,
+                               static_cast<hipStream_t>(hip_stream));
+}
+
+// host pointers: the header and every box are checked here, before anything is staged; the outputs come back dense, back to back in box
+// order, 32-bit elements
+int bin_boxes_from_host(const char* src, long srclength, long count, const long* origins, const long* extents, unsigned rank, const long* bins, int op, char* out,
+                        long out_capacity, int elem_size)
+{
+    if (!out || !bin_arguments_ok(src, srclength, count, origins, extents, rank, bins, op, nullptr, nullptr, elem_size)) {
+        std::fprintf(stderr, "[sqeazy]\t bin boxes: bad arguments\n");
+        return 1;
+    }
+    const sqy::HeaderInfo h = sqy::header_unpack(src, src + srclength);
+    if (!h.valid) { std::fprintf(stderr, "[sqeazy]\t unable to find a sqy header in the blob\n"); return 1; }
+    uint64_t raw = 0;
+    if (!header_shape_ok(h, (uint64_t)srclength, &raw)) return 1;
+    if (h.elem_size() != elem_size) { std::fprintf(stderr, "[sqeazy]\t blob holds %s voxels\n", h.type.c_str()); return 1; }
+    std::vector<uint64_t> at((size_t)count + 1, 0);                    // (an output is no larger than the volume, count fits an int: no wrap)
+    for (long i = 0; i < count; ++i) {
+        sqy::BatchWindow w;
+        sqy::Binning q;
+        if (!sqy::admit_binning(h.shape, origins + (size_t)i * rank, extents + (size_t)i * rank, rank, bins, op, elem_size == 2 ? 65535u : 255u, &q, nullptr, &w, &q)) {
+            std::fprintf(stderr, "[sqeazy]\t bin boxes: box %ld does not lie inside the blob's shape, or a cell's sum might not fit 32 bits\n", i);
+            return 1;
+        }
+        at[(size_t)i + 1] = at[(size_t)i] + q.C[0] * q.C[1] * q.C[2] * 4u;
+    }
+    if (at.back() > (uint64_t)std::max(out_capacity, 0l)) { std::fprintf(stderr, "[sqeazy]\t bin boxes: buffer too small\n"); return 1; }
+    return decode_staged(src, (uint64_t)srclength, out, at.back(), [&](Context& cx, void* d_src, void* d_dst, hipStream_t stream) {
+        std::vector<void*> ptrs((size_t)count);
+        for (long i = 0; i < count; ++i) ptrs[(size_t)i] = static_cast<uint8_t*>(d_dst) + at[(size_t)i];
+        return bin_boxes_on_device(cx, d_src, (uint64_t)srclength, (size_t)count, origins, extents, rank, bins, op, ptrs.data(), nullptr, elem_size, stream);
+    });
+}
+
 int decode_batch_device(const void* d_src, const BatchDecodeArgs& a, int elem_size, void* hip_stream)
 {
     if (admit_decode_batch(d_src, a)) return 1;
@@ -5920,6 +6114,30 @@ int SQYAMD_Project_Boxes_UI8(const char* src, long srclength, long count, const 
                              long out_capacity)
 {
     return guarded([&]() -> int { return project_boxes_from_host(src, srclength, count, origins, extents, rank, axis, op, out, out_capacity, 1); });
+}
+
+int SQYAMD_Bin_Boxes_UI16_Device(const void* d_src, long srclength, long count, const long* origins, const long* extents, unsigned rank, const long* bins, int op,
+                                 void* const* d_outs, const long* out_strides, void* hip_stream)
+{
+    return guarded([&]() -> int { return bin_boxes_device(d_src, srclength, count, origins, extents, rank, bins, op, d_outs, out_strides, 2, hip_stream); });
+}
+
+int SQYAMD_Bin_Boxes_UI8_Device(const void* d_src, long srclength, long count, const long* origins, const long* extents, unsigned rank, const long* bins, int op,
+                                void* const* d_outs, const long* out_strides, void* hip_stream)
+{
+    return guarded([&]() -> int { return bin_boxes_device(d_src, srclength, count, origins, extents, rank, bins, op, d_outs, out_strides, 1, hip_stream); });
+}
+
+int SQYAMD_Bin_Boxes_UI16(const char* src, long srclength, long count, const long* origins, const long* extents, unsigned rank, const long* bins, int op, char* out,
+                          long out_capacity)
+{
+    return guarded([&]() -> int { return bin_boxes_from_host(src, srclength, count, origins, extents, rank, bins, op, out, out_capacity, 2); });
+}
+
+int SQYAMD_Bin_Boxes_UI8(const char* src, long srclength, long count, const long* origins, const long* extents, unsigned rank, const long* bins, int op, char* out,
+                         long out_capacity)
+{
+    return guarded([&]() -> int { return bin_boxes_from_host(src, srclength, count, origins, extents, rank, bins, op, out, out_capacity, 1); });
 }
 
 int SQYAMD_Decode_Slabs_UI16_Device(const void* d_src, const long* offsets, const long* lengths, int nslabs, void* d_dst, long dst_capacity,

@@ -506,6 +506,46 @@ struct BoxProjectJob {
 };
 constexpr uint64_t kBoxProjectJobBytes = 96;
 hipError_t launch_boxes_window_project(const BoxProjectJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ngroups, int elem_size, hipStream_t stream);
+// ---- many boxes of one large blob read at a coarser resolution (SQYAMD_Bin_Boxes_*) ----
+// No global atomics, no neutral elements beforehand, every output cell stored once.  Job j is a box (g: the blob's rows and the box; g.sz,
+// g.sy the OUTPUT's pitches in elements from cell layer to layer and cell row to row), its range, its clamped bins and the tiling of its
+// cell grid (sqy::bin_boxes_plan); it owns plan.blocks workgroups, d_first_tile their prefix sums.  Workgroup `own` takes the block
+// sqy::bin_block_of(plan, own): it sets the block's accumulators in LDS to the op's neutral element, its threads share the block's items
+// (sqy_batch_window.hpp: a 32-voxel run of a footprint frame each; zreg != 0: the run's positions reduced over the layer's frames in
+// registers first -- only where bitswap1_box_bin_zreg_ok), load the run's owned plane words -- four bytes of a plane at once where that
+// lies on the 4-byte grid and the run's words all belong to the range, word by word elsewhere; tail voxels verbatim --, transpose, look
+// up, reduce each cell's row piece in registers (sqy::bin_run_cells) and combine it into LDS with an LDS integer atomic; behind a barrier
+// the cells go out with plain 32-bit stores, a cell row's columns in consecutive threads.  A run with no voxel of the footprint loads no
+// plane word.  Every job must pass bitswap1_box_bin_job_ok.  Nothing but the outputs' cells is written.
+struct Bitswap1BoxBinJob {
+    void* out;
+    WindowGeometry g;
+    Bitswap1Range r;
+    uint64_t t0;             // (Bitswap1BoxJob's field; not used: a block finds its words from its footprint)
+    uint64_t bins[3];
+    BinPlan plan;
+    uint32_t op, zreg;
+};
+constexpr uint64_t kBitswap1BoxBinJobBytes = 368;       // (a multiple of 16: the tile table behind the jobs stays on the 16-byte grid)
+bool bitswap1_box_bin_job_ok(const Bitswap1BoxBinJob& j);
+// a frame is a whole number of 32-voxel runs (so the blob has no tail and every run of the box's frames lies in the range's words)
+inline bool bitswap1_box_bin_zreg_ok(const Bitswap1BoxBinJob& j) { const uint64_t frame = j.g.bY * j.g.bX; return frame != 0 && frame % 32 == 0; }
+hipError_t launch_bitswap1_decode_range_windows_bin(const uint8_t* in, const Bitswap1BoxBinJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ngroups,
+                                                    int elem_size, const uint16_t* lut, hipStream_t stream);
+// The binning of boxes of a DENSE volume (the compaction of `lz4` and `frame_shuffle->lz4` blobs, the whole decode): a thread per output
+// cell walks the cell's voxels -- cell (cz, cy, cx) reads dense[base + z plane + y row + x] over [c bins, min((c + 1) bins, extent)) --
+// and stores out[cz pz + cy py + cx] once.  Job j owns ceil(C[0] C[1] C[2] / 256) workgroups; d_first_tile their prefix sums.
+struct BoxBinJob {
+    const void* dense;
+    void* out;
+    uint64_t base, plane, row;
+    uint64_t E[3], bins[3], C[3];
+    uint64_t pz, py;
+    uint32_t op, pad0;
+    uint64_t pad1;
+};
+constexpr uint64_t kBoxBinJobBytes = 144;
+hipError_t launch_boxes_window_bin(const BoxBinJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ngroups, int elem_size, hipStream_t stream);
 // ---- a box written into one large blob (SQYAMD_Update_Box_*) ----
 // launch_bitswap1_decode_range_window the other way round, in place: the box's voxels are read from the view (box.view; `dense` and tile0
 // are not read) and merged into the plane words [w0, w1) and the tail of the range r inside the compaction at buf (launch_bitswap1_batch_patch's

@@ -9783,6 +9783,221 @@ hipError_t launch_boxes_window_project(const BoxProjectJob* d_jobs, const uint32
     return hipGetLastError();
 }
 
+// ---- many boxes of one large blob read at a coarser resolution (SQYAMD_Bin_Boxes_*) ------------------------------------------------------
+// the sink of bin_run_cells on the device: one no-return LDS integer atomic per piece of a cell's row.  A value that is the op's neutral
+// element changes nothing and is not sent
+struct BinLdsSink {
+    uint32_t* acc;
+    uint32_t op;
+    __device__ __forceinline__ void combine(uint64_t cell, uint32_t v) const
+    {
+        if (op == kProjectMax) { if (v) (void)atomicMax(acc + cell, v); }
+        else if (op == kProjectMin) (void)atomicMin(acc + cell, v);
+        else if (v) (void)atomicAdd(acc + cell, v);
+    }
+};
+
+// The 32 voxels of the run that begins at voxel i0 (a multiple of 32) out of the range `a`: v[i] = voxel i0 + i (behind the look-up the
+// 16-bit voxel out of the table), 0 where its plane word is not one of the range's [w0, w1) -- such a voxel lies outside every box of the
+// range -- or it lies behind the range's last voxel.  Four bytes of a plane at once where the run's words all belong to the range and
+// `grid4` says that they lie on the 4-byte grid, word by word elsewhere; the voxels behind the planes (a blob's last n % W) verbatim.
+template <int ELEM, bool LUT>
+__device__ __forceinline__ void bin_load_run(const uint8_t* __restrict__ in, const Bitswap1Range& a, uint64_t i0, bool grid4, const uint16_t* sl, uint32_t v[32])
+{
+    constexpr uint32_t W = 8 * ELEM, NW = 32 / W;                      // voxels per word; a run is NW words, four bytes of a plane
+    const uint64_t word0 = i0 / W;
+    const bool whole = grid4 && word0 >= a.w0 && word0 + NW <= a.w1;
+    if constexpr (ELEM == 2) {
+        uint32_t r[16];                                                // r[b] = the run's two words of the plane that carries bit b
+        if (whole) {
+            const uint64_t at = (word0 - a.w0) * 2u;
+#pragma unroll
+            for (int b = 0; b < 16; ++b) r[b] = *reinterpret_cast<const uint32_t*>(in + a.plane[15 - b] + at);
+        } else {
+#pragma unroll
+            for (int b = 0; b < 16; ++b) r[b] = 0;
+#pragma unroll
+            for (uint32_t i = 0; i < NW; ++i) {
+                const uint64_t w = word0 + i;
+                if (w >= a.w0 && w < a.w1)
+#pragma unroll
+                    for (int b = 0; b < 16; ++b) r[b] |= (uint32_t)*reinterpret_cast<const uint16_t*>(in + a.plane[15 - b] + (w - a.w0) * 2u) << (16u * i);
+            }
+        }
+        transpose16x16_pairs(r);                                      // r[i] = voxel 15 - i of the first word | of the second << 16
+#pragma unroll
+        for (int i = 0; i < 16; ++i) { v[i] = r[15 - i] & 0xffffu; v[16 + i] = r[15 - i] >> 16; }
+    } else {
+        uint32_t pw[8];                                                // pw[b] = the run's four words of the plane that carries bit b
+        if (whole) {
+            const uint64_t at = word0 - a.w0;
+#pragma unroll
+            for (int b = 0; b < 8; ++b) pw[b] = *reinterpret_cast<const uint32_t*>(in + a.plane[7 - b] + at);
+        } else {
+#pragma unroll
+            for (int b = 0; b < 8; ++b) pw[b] = 0;
+#pragma unroll
+            for (uint32_t i = 0; i < NW; ++i) {
+                const uint64_t w = word0 + i;
+                if (w >= a.w0 && w < a.w1)
+#pragma unroll
+                    for (int b = 0; b < 8; ++b) pw[b] |= (uint32_t)in[a.plane[7 - b] + (w - a.w0)] << (8u * i);
+            }
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < 4; ++u) {
+            // (bitswap1_decode_batch_strided_kernel's gather and transpose: afterwards byte i of hi:lo = voxel 7 - i)
+            constexpr uint32_t Zs = 0x0c;                             // v_perm selector: a zero byte
+            const uint32_t s01 = u | ((4u + u) << 8) | (Zs << 16) | (Zs << 24), s23 = Zs | (Zs << 8) | (u << 16) | ((4u + u) << 24);
+            uint32_t lo_ = __builtin_amdgcn_perm(pw[1], pw[0], s01) | __builtin_amdgcn_perm(pw[3], pw[2], s23);
+            uint32_t hi_ = __builtin_amdgcn_perm(pw[5], pw[4], s01) | __builtin_amdgcn_perm(pw[7], pw[6], s23);
+            uint32_t y;
+            y = (lo_ ^ (lo_ >> 7)) & 0x00AA00AAu; lo_ ^= y ^ (y << 7);
+            y = (hi_ ^ (hi_ >> 7)) & 0x00AA00AAu; hi_ ^= y ^ (y << 7);
+            y = (lo_ ^ (lo_ >> 14)) & 0x0000CCCCu; lo_ ^= y ^ (y << 14);
+            y = (hi_ ^ (hi_ >> 14)) & 0x0000CCCCu; hi_ ^= y ^ (y << 14);
+            y = (lo_ ^ (hi_ << 4)) & 0xF0F0F0F0u; lo_ ^= y; hi_ ^= y >> 4;
+            const uint32_t h4 = __builtin_bswap32(hi_), l4 = __builtin_bswap32(lo_);      // voxels 0..3 and 4..7 of word u, voxel k at byte k
+#pragma unroll
+            for (uint32_t k = 0; k < 4; ++k) {
+                const uint32_t x0 = (h4 >> (8u * k)) & 0xffu, x1 = (l4 >> (8u * k)) & 0xffu;
+                v[8 * u + k] = LUT ? (uint32_t)sl[x0] : x0;
+                v[8 * u + 4 + k] = LUT ? (uint32_t)sl[x1] : x1;
+            }
+        }
+    }
+    if (i0 + 32 > a.L) {                                               // (the blob's last run at most)
+        const uint64_t tail0 = a.v0 > a.L ? a.v0 : a.L;
+#pragma unroll
+        for (uint32_t i = 0; i < 32; ++i)
+            if (i0 + i >= tail0 && i0 + i < a.v1) {
+                const uint32_t x = view_voxel_load<ELEM>(in + a.tail, i0 + i - tail0);
+                v[i] = LUT ? (uint32_t)sl[x & 0xffu] : x;
+            }
+    }
+}
+
+// A workgroup per block of one box's cells (sqy_kernels.h, sqy_batch_window.hpp): accumulators in LDS, the items shared by the threads,
+// plain stores behind the barrier.  Every thread reaches both barriers: a thread without an item skips the loop's body only.
+template <int ELEM, bool LUT>
+__global__ __launch_bounds__(256)
+void bitswap1_decode_range_windows_bin_kernel(const uint8_t* __restrict__ in, const Bitswap1BoxBinJob* __restrict__ jobs, const uint32_t* __restrict__ first_tile,
+                                              uint32_t njobs, const uint16_t* __restrict__ lut)
+{
+    static_assert(!LUT || ELEM == 1, "the look-up follows 8-bit planes");
+    constexpr uint32_t W = 8 * ELEM;
+    __shared__ uint16_t sl[LUT ? 256 : 1];
+    __shared__ uint32_t acc[kBinBlockCells];
+    if constexpr (LUT) sl[threadIdx.x] = lut[threadIdx.x];
+    const uint32_t j = batch_job_of_tile(first_tile, njobs);
+    const Bitswap1BoxBinJob* __restrict__ job = jobs + j;               // (uniform: its fields live in scalar registers)
+    const Bitswap1Range& a = job->r;
+    const uint32_t op = job->op, tid = threadIdx.x;
+    const BinBlock blk = bin_block_of(job->plan, blockIdx.x - first_tile[j]);
+    const uint32_t ncx = (uint32_t)blk.ncx, ncells = (uint32_t)blk.ncy * ncx;          // (<= kBinBlockCells: bitswap1_box_bin_job_ok)
+    for (uint32_t c = tid; c < ncells; c += 256u) acc[c] = project_neutral(op);
+    __syncthreads();
+    const BinFootprint f = bin_block_footprint(job->g, job->bins, blk);
+    const bool zreg = job->zreg != 0;
+    const uint64_t items = bin_block_items(f, zreg), frame = job->g.bY * job->g.bX;
+    uint32_t off_grid = 0;                                            // (uniform) a run's four bytes of every plane: on the 4-byte grid?
+#pragma unroll
+    for (uint32_t p = 0; p < W; ++p) off_grid |= (uint32_t)(reinterpret_cast<uintptr_t>(in) + a.plane[p] - a.w0 * ELEM);
+    const bool grid4 = a.w0 < a.w1 && (off_grid & 3u) == 0;
+    BinLdsSink sink{acc, op};
+    for (uint64_t t = tid; t < items; t += 256u) {
+        uint64_t z, run;
+        if (!bin_block_item(f, zreg, t, &z, &run)) continue;
+        WindowGeometry g = f.g;
+        g.oz = z;
+        WindowClip c = window_clip_start(g, run * 32u, 32);
+        WindowPiece cur;
+        bool have = window_clip_next(g, &c, &cur);
+        if (!have) continue;                                          // (nothing of the run inside the footprint: no plane word is loaded)
+        uint32_t red[32];
+        bin_load_run<ELEM, LUT>(in, a, run * 32u, grid4, sl, red);
+        if (zreg)
+            for (uint64_t zz = 1; zz < f.nz; ++zz) {                  // the same positions of the layer's other frames
+                uint32_t v[32];
+                bin_load_run<ELEM, LUT>(in, a, run * 32u + zz * frame, grid4, sl, v);
+#pragma unroll
+                for (int i = 0; i < 32; ++i) red[i] = project_combine(op, red[i], v[i]);
+            }
+        bin_run_cells(sink, g, c, cur, have, red, job->bins[1], job->bins[2], blk.ncx, op);
+    }
+    __syncthreads();
+    uint32_t* __restrict__ out = static_cast<uint32_t*>(job->out);
+    const uint64_t py = job->g.sy, base = blk.cz * job->g.sz + blk.cy0 * py + blk.cx0;
+    for (uint32_t c = tid; c < ncells; c += 256u) {
+        const uint32_t cy = c / ncx;
+        out[base + cy * py + (c - cy * ncx)] = acc[c];
+    }
+}
+
+// a thread per output cell of a dense volume's box: it walks the cell's voxels and stores its cell once
+template <int ELEM>
+__global__ __launch_bounds__(256)
+void boxes_window_bin_kernel(const BoxBinJob* __restrict__ jobs, const uint32_t* __restrict__ first_tile, uint32_t njobs)
+{
+    const uint32_t j = batch_job_of_tile(first_tile, njobs);
+    const BoxBinJob* __restrict__ job = jobs + j;
+    const uint64_t e = (uint64_t)(blockIdx.x - first_tile[j]) * 256u + threadIdx.x, C1 = job->C[1], C2 = job->C[2], layer = C1 * C2;
+    if (e >= job->C[0] * layer) return;
+    const uint64_t cz = e / layer, r = e - cz * layer, cy = r / C2, cx = r - cy * C2;
+    const uint64_t bz = job->bins[0], by = job->bins[1], bx = job->bins[2];
+    const uint64_t z1 = (cz + 1) * bz < job->E[0] ? (cz + 1) * bz : job->E[0], y1 = (cy + 1) * by < job->E[1] ? (cy + 1) * by : job->E[1];
+    const uint64_t x1 = (cx + 1) * bx < job->E[2] ? (cx + 1) * bx : job->E[2];
+    const uint8_t* __restrict__ dense = static_cast<const uint8_t*>(job->dense);
+    const uint32_t op = job->op;
+    uint32_t acc = project_neutral(op);
+    for (uint64_t z = cz * bz; z < z1; ++z)
+        for (uint64_t y = cy * by; y < y1; ++y) {
+            const uint64_t at = job->base + z * job->plane + y * job->row;
+            for (uint64_t x = cx * bx; x < x1; ++x) acc = project_combine(op, acc, view_voxel_load<ELEM>(dense, at + x));
+        }
+    static_cast<uint32_t*>(job->out)[cz * job->pz + cy * job->py + cx] = acc;
+}
+
+static_assert(sizeof(Bitswap1BoxBinJob) == kBitswap1BoxBinJobBytes && sizeof(Bitswap1BoxBinJob) % 16 == 0 && offsetof(Bitswap1BoxBinJob, bins) == sizeof(Bitswap1BoxJob) &&
+                  sizeof(BoxBinJob) == kBoxBinJobBytes && sizeof(BoxBinJob) % 16 == 0,
+              "the binning jobs: Bitswap1BoxJob's fields, the bins and the tiling behind them");
+
+// bitswap1_box_job_ok for the binning job; bins inside the extent, the tiling that of the cell grid and within the LDS accumulators
+bool bitswap1_box_bin_job_ok(const Bitswap1BoxBinJob& j)
+{
+    const Bitswap1Range& r = j.r;
+    const WindowGeometry& g = j.g;
+    const BinPlan& p = j.plan;
+    if (r.v1 <= r.v0 || r.w1 < r.w0 || !j.out || reinterpret_cast<uintptr_t>(j.out) % 4u || g.Z == 0 || g.Y == 0 || g.X == 0 || g.bY == 0 || g.bX == 0) return false;
+    if (j.op >= kProjectOps || (j.zreg && !bitswap1_box_bin_zreg_ok(j))) return false;
+    const uint64_t e[3] = {g.Z, g.Y, g.X};
+    for (int d = 0; d < 3; ++d)
+        if (j.bins[d] == 0 || j.bins[d] > e[d] || p.C[d] != (e[d] + j.bins[d] - 1) / j.bins[d]) return false;
+    if (p.band == 0 || p.strip == 0 || p.band > kBinBlockCells || p.strip > kBinBlockCells || p.band * p.strip > kBinBlockCells) return false;
+    if (p.nbands != (p.C[1] + p.band - 1) / p.band || p.nstrips != (p.C[2] + p.strip - 1) / p.strip || p.blocks != p.C[0] * p.nbands * p.nstrips) return false;
+    if (g.sy < p.C[2] || (p.C[0] > 1 && g.sz < p.C[1] * g.sy)) return false;
+    return ((g.oz * g.bY + g.oy) * g.bX + g.ox) >= r.v0 && ((g.oz + g.Z - 1) * g.bY + g.oy + g.Y - 1) * g.bX + g.ox + g.X <= r.v1;
+}
+
+hipError_t launch_bitswap1_decode_range_windows_bin(const uint8_t* in, const Bitswap1BoxBinJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ngroups,
+                                                    int elem_size, const uint16_t* lut, hipStream_t stream)
+{
+    if (njobs == 0 || ngroups < njobs || (elem_size != 1 && elem_size != 2) || (lut && elem_size != 1)) return hipErrorInvalidValue;
+    const dim3 grid(ngroups);
+    if (elem_size == 2) hipLaunchKernelGGL((bitswap1_decode_range_windows_bin_kernel<2, false>), grid, dim3(256), 0, stream, in, d_jobs, d_first_tile, njobs, lut);
+    else if (lut) hipLaunchKernelGGL((bitswap1_decode_range_windows_bin_kernel<1, true>), grid, dim3(256), 0, stream, in, d_jobs, d_first_tile, njobs, lut);
+    else hipLaunchKernelGGL((bitswap1_decode_range_windows_bin_kernel<1, false>), grid, dim3(256), 0, stream, in, d_jobs, d_first_tile, njobs, lut);
+    return hipGetLastError();
+}
+
+hipError_t launch_boxes_window_bin(const BoxBinJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ngroups, int elem_size, hipStream_t stream)
+{
+    if (njobs == 0 || ngroups < njobs || (elem_size != 1 && elem_size != 2)) return hipErrorInvalidValue;
+    if (elem_size == 2) hipLaunchKernelGGL(boxes_window_bin_kernel<2>, dim3(ngroups), dim3(256), 0, stream, d_jobs, d_first_tile, njobs);
+    else hipLaunchKernelGGL(boxes_window_bin_kernel<1>, dim3(ngroups), dim3(256), 0, stream, d_jobs, d_first_tile, njobs);
+    return hipGetLastError();
+}
+
 hipError_t launch_batch_view_copy(const BatchViewJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ntiles, int elem_size, bool to_view,
                                   hipStream_t stream)
 {

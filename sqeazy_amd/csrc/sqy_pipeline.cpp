@@ -951,6 +951,68 @@ bool admit_projection(const std::vector<uint64_t>& header_shape, const long* ori
     return true;
 }
 
+BoxPath bin_boxes_path(bool subset_form, RangeForm form, bool option_on)
+{
+    if (!subset_form || !option_on) return BoxPath::whole_copy;
+    switch (form) {
+    case RangeForm::planes:
+    case RangeForm::planes_lut: return BoxPath::subset_transposer;
+    case RangeForm::plain:
+    case RangeForm::shuffle: return BoxPath::subset_copy;
+    }
+    return BoxPath::whole_copy;
+}
+
+bool admit_binning(const std::vector<uint64_t>& header_shape, const long* origin, const long* extent, unsigned rank, const long* bins, int op, uint64_t maxvoxel,
+                   const void* out, const long* out_strides, BatchWindow* w, Binning* b)
+{
+    if (!w || !b || !admit_window(header_shape, origin, extent, rank, w)) return false;
+    if (!bins || op < 0 || op > 2) return false;
+    if (!out || reinterpret_cast<uintptr_t>(out) % 4u) return false;
+    const uint64_t e[3] = {w->Z, w->Y, w->X};
+    Binning q;
+    long cells[3] = {1, 1, 1};
+    constexpr uint64_t kSat = (uint64_t)1 << 33;                          // (above both bounds; a factor is clamped to it before it multiplies)
+    uint64_t V = 1;
+    for (unsigned k = 0; k < rank; ++k) {
+        if (bins[k] < 1) return false;
+        const unsigned d = 3 - rank + k;
+        q.bins[d] = std::min((uint64_t)bins[k], e[d]);
+        q.C[d] = (e[d] + q.bins[d] - 1) / q.bins[d];
+        cells[k] = (long)q.C[d];
+        V = std::min(V * std::min(q.bins[d], kSat), kSat);                // (both factors <= 2^33: no wrap)
+    }
+    // the projection's bound applied to the cell: 16-bit voxels up to 65536 of them, 8-bit ones while 255 V < 2^32
+    if (op == 2 && V > (maxvoxel > 255 ? (uint64_t)65536 : 0xffffffffull / maxvoxel)) return false;
+    BatchView v;
+    if (!admit_view(cells, out_strides, rank, &v)) return false;
+    q.py = rank >= 2 && out_strides ? (uint64_t)out_strides[rank - 2] : q.C[2];
+    q.pz = rank == 3 && out_strides ? (uint64_t)out_strides[0] : q.C[1] * q.py;     // (ranks 1 and 2: one layer, the pitch is never stepped over)
+    *b = q;
+    return true;
+}
+
+BinPlan bin_boxes_plan(const uint64_t C[3], const uint64_t bins[3], uint64_t X, uint64_t budget_cells, uint64_t cap_voxels)
+{
+    BinPlan p{};
+    p.C[0] = C[0]; p.C[1] = C[1]; p.C[2] = C[2];
+    if (budget_cells == 0) budget_cells = 1;
+    if (C[2] > budget_cells) {                                          // a cell row does not fit: ONE row, in strips
+        p.band = 1;
+        p.strip = budget_cells;
+    } else {
+        p.strip = C[2];
+        // a cell row's footprint over the layer's frames, saturating
+        constexpr uint64_t lim = (uint64_t)1 << 20;                      // (far above any cap: each factor is clamped to it first)
+        const uint64_t row = std::min(std::min(bins[0], lim) * std::min(bins[1], lim), lim) * std::min(std::max<uint64_t>(X, 1), lim);
+        p.band = std::max<uint64_t>(1, std::min({budget_cells / C[2], cap_voxels / row, C[1]}));
+    }
+    p.nbands = (C[1] + p.band - 1) / p.band;
+    p.nstrips = (C[2] + p.strip - 1) / p.strip;
+    p.blocks = C[0] * p.nbands * p.nstrips;                             // (the caller bounds the sum over the boxes: each factor is below 2^62 / the others for an admitted box)
+    return p;
+}
+
 // ---- a box written into one large blob (SQYAMD_Update_Box_*) ----
 UpdateBoxPath update_box_path(const UpdateBoxFacts& f)
 {

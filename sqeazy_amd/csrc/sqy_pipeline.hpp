@@ -18,6 +18,8 @@
 #include <utility>
 #include <vector>
 
+#include "sqy_batch_window.hpp"
+
 namespace sqy {
 
 typedef std::vector<std::pair<std::string, std::string>> pairs_t;
@@ -561,6 +563,28 @@ BoxPath project_boxes_path(bool subset_form, RangeForm form, bool option_on);
 struct Projection { uint32_t axis3 = 0; uint64_t E0 = 1, E1 = 1, p0 = 1, sz = 0, sy = 0, n = 1, su = 0, sv = 0, sa = 0; };
 bool admit_projection(const std::vector<uint64_t>& header_shape, const long* origin, const long* extent, unsigned rank, int axis, int op, uint64_t maxvoxel,
                       const void* out, const long* out_strides, BatchWindow* w, Projection* p);
+// Many boxes of one blob read at a coarser resolution (SQYAMD_Bin_Boxes_*).  option_on: bin_boxes_subset; the rest as for
+// project_boxes_path.  One job per box, ONE output launch on every path, no neutral-element launch on any:
+//   subset_transposer  planes, planes_lut: the LZ4 frames of all boxes' z-ranges united, then the binning job-table kernel -- a workgroup
+//                      per block of cells (bin_boxes_plan), accumulators in LDS, every cell stored once
+//   subset_copy        plain, shuffle: .. then ONE launch with a thread per output cell in the compaction
+//   whole_copy         every other blob, and every blob with the option off: decoded whole ONCE, the same per-cell launch
+BoxPath bin_boxes_path(bool subset_form, RangeForm form, bool option_on);
+// The admission of one box's binning, stated once (SQYAMD_Bin_Boxes_*).  The box as admit_window admits it; bins: `rank`
+// longs, each >= 1; op 0 .. 2 (max, min, sum); the output at `out` (not NULL, 4-byte aligned) keeps the rank, its extent ceil(extent /
+// bins) per dimension, and out_strides (rank pitches in elements, nullptr: dense) under admit_view's rules.  The sum is refused where a
+// cell might not fit 32 bits: with V = the product of min(bins[d], extent[d]) -- each factor clamped first, the product saturating --,
+// V > 65536 for 16-bit voxels (maxvoxel 65535) and maxvoxel V >= 2^32 for 8-bit ones (maxvoxel 255).  On success: the window, and
+//   bins    padded to (z, y, x) and clamped to the extent (the same cells: a bin larger than the extent is one cell)
+//   C       the cell grid, padded;  pz, py: the output's pitches in elements from cell layer to layer and cell row to row
+struct Binning { uint64_t bins[3] = {1, 1, 1}, C[3] = {1, 1, 1}, pz = 1, py = 1; };
+bool admit_binning(const std::vector<uint64_t>& header_shape, const long* origin, const long* extent, unsigned rank, const long* bins, int op, uint64_t maxvoxel,
+                   const void* out, const long* out_strides, BatchWindow* w, Binning* b);
+// The tiling of one box's cell grid C into the blocks a workgroup of the bit-plane kernel owns (sqy_batch_window.hpp states what a block
+// is), stated once.  `bins` as admit_binning clamps them, X the box's width.  A block holds at most budget_cells cells: whole cell rows
+// where a row fits (as many as the budget takes, but no more than keep the block's footprint near cap_voxels voxels: small blocks fill
+// the device), else ONE cell row cut into strips of budget_cells columns.  blocks = C[0] nbands nstrips.
+BinPlan bin_boxes_plan(const uint64_t C[3], const uint64_t bins[3], uint64_t X, uint64_t budget_cells = kBinBlockCells, uint64_t cap_voxels = kBinBlockVoxels);
 
 struct Stage {
     std::string name;
