@@ -534,6 +534,35 @@ SQY_FUNCTION_PREFIX int SQYAMD_Bin_Boxes_UI16(const char* src, long srclength, l
                                               const long* bins, int op, char* out, long out_capacity);
 SQY_FUNCTION_PREFIX int SQYAMD_Bin_Boxes_UI8(const char* src, long srclength, long count, const long* origins, const long* extents, unsigned rank,
                                              const long* bins, int op, char* out, long out_capacity);
+/* The intensity distribution of the same boxes: MANY boxes of one blob counted in one call -- display range and percentiles, an Otsu or
+ * background threshold per crop, saturation checks, the 65536-bin histogram a re-quantisation starts from --, the decoded voxels never
+ * stored.  Boxes, rank, device, stream and thread rules are SQYAMD_Decode_Boxes_*'s (ranks 1 to 3, frames the first dimension).  Voxel v
+ * of box i falls into bin v >> shift; histogram i is nbins = R >> shift counters of uint32_t, dense, at d_hists[i] (4-byte aligned), with
+ * R = 65536 for the 16-bit entry points and 256 for the 8-bit ones and shift in [0, 16) resp. [0, 8).  Behind the quantiser's look-up the
+ * counted voxel is the 16-bit one out of the table, as for SQYAMD_Compare_Boxes_*.  Counts are exact: a blob has fewer than 2^31 voxels,
+ * so no counter wraps.  Every counter of every histogram is written, zeros included, and nothing else: not d_src, not a byte around the
+ * histograms.  Boxes may overlap in the blob; histograms that overlap each other are the caller's error.
+ * Checked before a byte is written (else 1, every histogram untouched): what SQYAMD_Decode_Boxes_* checks for every box; shift out of
+ * range; d_hists NULL, a NULL entry in it or one off the 4-byte grid.  Whatever needs no header is checked before a device is looked for.
+ * A damaged LZ4 frame that SOME box's z-range needs gives SQY_Decode's composite code; the histograms may then hold anything, and nothing
+ * outside them is written.  A damaged frame that no box needs goes unnoticed.
+ * How: one header fetch, the LZ4 frames the boxes' z-ranges need united and decoded by one launch, one launch that zeroes all histograms,
+ * ONE counting launch -- for `bitswap1->lz4` and `quantiser->bitswap1->lz4` the range transposer driven by a job table, a workgroup per
+ * 32768 voxels of a box's word range: it counts the box's voxels into a private histogram in LDS (up to 16384 bins whole; above, a window
+ * of 16384 bins voted from its first voxels, the bins outside it by global atomics) and adds its non-zero counters into the output with
+ * no-return 32-bit atomics; for `lz4` and `frame_shuffle->lz4` one launch over the boxes' rows in the compaction with the same LDS
+ * histogram.  Every other blob is decoded whole ONCE into the workspace and the same launch takes all boxes ("histogram_boxes_subset" = 0:
+ * every blob -- the same histograms). */
+SQY_FUNCTION_PREFIX int SQYAMD_Histogram_Boxes_UI16_Device(const void* d_src, long srclength, long count, const long* origins, const long* extents, unsigned rank,
+                                                           int shift, void* const* d_hists, void* hip_stream);
+SQY_FUNCTION_PREFIX int SQYAMD_Histogram_Boxes_UI8_Device(const void* d_src, long srclength, long count, const long* origins, const long* extents, unsigned rank,
+                                                          int shift, void* const* d_hists, void* hip_stream);
+/* host-pointer variants: the blob is staged ONCE; the histograms come back dense and back to back in box order, nbins uint32_t each (1
+ * where out_capacity, in bytes, is below count nbins 4) */
+SQY_FUNCTION_PREFIX int SQYAMD_Histogram_Boxes_UI16(const char* src, long srclength, long count, const long* origins, const long* extents, unsigned rank,
+                                                    int shift, char* out, long out_capacity);
+SQY_FUNCTION_PREFIX int SQYAMD_Histogram_Boxes_UI8(const char* src, long srclength, long count, const long* origins, const long* extents, unsigned rank,
+                                                   int shift, char* out, long out_capacity);
 /* The write of a box into a tiled store, whose border cuts through tiles: every tile under the box is read, modified and written again
  * with ONE call.  Old blob i lies at d_src + src_offsets[i], src_lengths[i] bytes (host arrays; any alignment): a complete sqeazy blob of
  * the entry point's voxel type, any pipeline, any layout.  Window i is the box [origins row i, + win_shapes row i) of that blob's volume
@@ -727,6 +756,12 @@ SQY_FUNCTION_PREFIX void SQYAMD_Release_Workspace(void);
  *   "bin_boxes_subset"                1 [SQY_NO_BIN_BOXES_SUBSET=1 -> 0]  SQYAMD_Bin_Boxes_*: only the LZ4 frames the boxes' z-ranges need, the binning
  *                                     kernel (a workgroup per block of cells, LDS accumulators) or one per-cell launch in the compaction, where the
  *                                     pipeline allows (0: every blob decoded whole once and one per-cell launch -- same outputs)
+ *   "histogram_boxes_subset"          1 [SQY_NO_HISTOGRAM_BOXES_SUBSET=1 -> 0]  SQYAMD_Histogram_Boxes_*: only the LZ4 frames the boxes' z-ranges need,
+ *                                     the counting range transposer or one window histogram in the compaction, where the pipeline allows (0: every
+ *                                     blob decoded whole once and one window histogram -- same histograms)
+ *   "histogram_boxes_merge"           2 [SQY_NO_HISTOGRAM_BOXES_MERGE=1 -> 0]  SQYAMD_Histogram_Boxes_*: how a thread adds equal neighbours into LDS -- 2: a
+ *                                     piece of sixteen bytes whose bins are all equal with one atomic; 1: equal consecutive voxels of its whole run
+ *                                     with one; 0: one LDS atomic per voxel -- same histograms
  *   "decode_slabs_joint"              1 [SQY_NO_DECODE_SLABS_JOINT=1 -> 0]  SQYAMD_Decode_Slabs_*: the chunked LZ4 blobs of a group indexed and
  *                                     decoded by one launch each (0: every blob on its own, as by SQYAMD_Decode_*_Device -- same bytes)
  *   "decode_batch_joint"              1 [SQY_NO_DECODE_BATCH_JOINT=1 -> 0]  SQYAMD_Decode_Batch_*: the joint-eligible blobs of a group ranked, decoded and

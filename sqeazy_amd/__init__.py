@@ -44,6 +44,7 @@ EXPORTED_SYMBOLS = (
     "SQYAMD_Compare_Boxes_UI16_Device", "SQYAMD_Compare_Boxes_UI8_Device", "SQYAMD_Compare_Boxes_UI16", "SQYAMD_Compare_Boxes_UI8",
     "SQYAMD_Project_Boxes_UI16_Device", "SQYAMD_Project_Boxes_UI8_Device", "SQYAMD_Project_Boxes_UI16", "SQYAMD_Project_Boxes_UI8",
     "SQYAMD_Bin_Boxes_UI16_Device", "SQYAMD_Bin_Boxes_UI8_Device", "SQYAMD_Bin_Boxes_UI16", "SQYAMD_Bin_Boxes_UI8",
+    "SQYAMD_Histogram_Boxes_UI16_Device", "SQYAMD_Histogram_Boxes_UI8_Device", "SQYAMD_Histogram_Boxes_UI16", "SQYAMD_Histogram_Boxes_UI8",
     "SQYAMD_Decode_Slabs_UI16_Device", "SQYAMD_Decode_Slabs_UI8_Device", "SQYAMD_Decode_Slabs_UI16", "SQYAMD_Decode_Slabs_UI8",
     "SQYAMD_Decode_Batch_UI16_Device", "SQYAMD_Decode_Batch_UI8_Device", "SQYAMD_Decode_Batch_UI16", "SQYAMD_Decode_Batch_UI8",
     "SQYAMD_Profile_Enable", "SQYAMD_Profile_Reset", "SQYAMD_Profile_Get",
@@ -167,6 +168,11 @@ def lib():
         for f in ("SQYAMD_Bin_Boxes_UI8", "SQYAMD_Bin_Boxes_UI16"):
             getattr(L, f).argtypes = [ctypes.c_void_p, ctypes.c_long, ctypes.c_long, c_long_p, c_long_p, ctypes.c_uint, c_long_p, ctypes.c_int, ctypes.c_void_p,
                                       ctypes.c_long]
+        for f in ("SQYAMD_Histogram_Boxes_UI8_Device", "SQYAMD_Histogram_Boxes_UI16_Device"):
+            getattr(L, f).argtypes = [ctypes.c_void_p, ctypes.c_long, ctypes.c_long, c_long_p, c_long_p, ctypes.c_uint, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p),
+                                      ctypes.c_void_p]
+        for f in ("SQYAMD_Histogram_Boxes_UI8", "SQYAMD_Histogram_Boxes_UI16"):
+            getattr(L, f).argtypes = [ctypes.c_void_p, ctypes.c_long, ctypes.c_long, c_long_p, c_long_p, ctypes.c_uint, ctypes.c_int, ctypes.c_void_p, ctypes.c_long]
         for f in ("SQYAMD_Decode_Slabs_UI8_Device", "SQYAMD_Decode_Slabs_UI16_Device"):
             getattr(L, f).argtypes = [ctypes.c_void_p, c_long_p, c_long_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_long, c_long_p, ctypes.c_int,
                                       ctypes.c_void_p]
@@ -812,6 +818,59 @@ def bin_boxes(blob, origins, extents, bins, op="max"):
     if mean:
         cells = [a.astype(np.float64) / bin_counts(ext, bins) for a, ext in zip(cells, extents)]
     return 0, cells
+
+
+def histogram_bins(dtype, shift):
+    """the number of bins of a histogram of SQYAMD_Histogram_Boxes_*: 65536 >> shift for 16-bit voxels, 256 >> shift for 8-bit ones"""
+    bits = 8 * np.dtype(dtype).itemsize
+    if bits not in (8, 16) or not 0 <= int(shift) < bits:
+        raise ValueError("shift %r out of range for %s" % (shift, np.dtype(dtype)))
+    return (1 << bits) >> int(shift)
+
+
+def histogram_boxes_device(d_src, srclength, origins, extents, shift, d_hists, dtype, stream=None, count=None):
+    """SQYAMD_Histogram_Boxes_*_Device on raw device pointers (ints): the voxels of box i -- extent extents[i], first voxel origins[i] of the
+    ONE blob at d_src -- counted into the histogram at d_hists[i]: histogram_bins(dtype, shift) uint32 counters, voxel v in bin v >> shift.
+    count: the number of boxes (default: as many as there are extents).  Returns rc."""
+    n = len(extents) if extents is not None else len(origins or ())
+    first = (extents or origins or [()])[0] if n else ()
+    ptrs = None if d_hists is None else (ctypes.c_void_p * max(len(d_hists), 1))(*[None if p is None else int(p) for p in d_hists])
+    return getattr(lib(), "SQYAMD_Histogram_Boxes_%s_Device" % _suffix(dtype))(
+        ctypes.c_void_p(None if d_src is None else int(d_src)), ctypes.c_long(int(srclength)), ctypes.c_long(n if count is None else int(count)), _long_rows(origins),
+        _long_rows(extents), ctypes.c_uint(len(first)), ctypes.c_int(int(shift)), ptrs, ctypes.c_void_p(stream or 0))
+
+
+def histogram_boxes(blob, origins, extents, shift=0):
+    """SQYAMD_Histogram_Boxes_UI8/UI16: the intensity histograms of the boxes [origins[i], origins[i] + extents[i]) of the blob's volume with
+    one call, voxel v in bin v >> shift.  Returns (rc, [uint32 ndarray of histogram_bins(dtype, shift) counters, ..] or None)."""
+    blob = bytes(blob)
+    size = decompressed_sizeof(blob)
+    if size not in (1, 2) or not decompressed_shape(blob) or len(origins) != len(extents) or not len(extents) or not 0 <= int(shift) < 8 * size:
+        return 1, None
+    dtype = np.uint16 if size == 2 else np.uint8
+    nbins = histogram_bins(dtype, shift)
+    out = np.empty(len(extents) * nbins, dtype=np.uint32)
+    src = np.frombuffer(blob, dtype=np.uint8)
+    rc = getattr(lib(), "SQYAMD_Histogram_Boxes_" + _suffix(dtype))(src.ctypes.data, ctypes.c_long(len(blob)), ctypes.c_long(len(extents)), _long_rows(origins),
+                                                                    _long_rows(extents), ctypes.c_uint(len(extents[0])), ctypes.c_int(int(shift)), out.ctypes.data,
+                                                                    ctypes.c_long(out.nbytes))
+    if rc:
+        return rc, None
+    return 0, [out[i * nbins:(i + 1) * nbins] for i in range(len(extents))]
+
+
+def histogram_quantile(hist, q, shift=0):
+    """The nearest-rank quantile of a histogram of SQYAMD_Histogram_Boxes_*: the lower edge b << shift of the smallest bin b whose cumulative
+    count reaches max(1, ceil(q N)), N the histogram's total.  ValueError for an empty histogram or q outside [0, 1]."""
+    hist = np.asarray(hist)
+    if not 0.0 <= q <= 1.0:
+        raise ValueError("q outside [0, 1]")
+    cum = np.cumsum(hist.astype(np.uint64))
+    total = int(cum[-1]) if cum.size else 0
+    if total == 0:
+        raise ValueError("empty histogram")
+    rank = max(1, int(np.ceil(q * total)))
+    return int(np.searchsorted(cum, rank, side="left")) << int(shift)
 
 
 def update_batch_window_device(pipeline, d_src, offsets, lengths, origins, d_wins, shapes, strides, dtype, d_dst, slot_capacity, nthreads=0, stream=None):

@@ -10,7 +10,8 @@
 // window's compare with a view (SQYAMD_Compare_BatchWindow_*; tests/sanitize/batch_compare_test.cpp holds them against a triple loop;
 // SQYAMD_Compare_Boxes_* gathers the same sums over the range transposer's runs: tests/sanitize/compare_boxes_test.cpp).
 // And the projection of a box along an axis (SQYAMD_Project_Boxes_*): a combine into an image where the scatter stores
-// (tests/sanitize/project_boxes_test.cpp).
+// (tests/sanitize/project_boxes_test.cpp).  And the intensity histogram of a box (SQYAMD_Histogram_Boxes_*): a count into a window of
+// bins where the scatter stores (tests/sanitize/histogram_boxes_test.cpp).
 #ifndef SQY_BATCH_WINDOW_HPP_
 #define SQY_BATCH_WINDOW_HPP_
 
@@ -369,6 +370,99 @@ SQY_VIEW_HD inline void bin_run_cells(Sink& sink, const WindowGeometry& g, Windo
             }
             if (last) have = window_clip_next(g, &c, &cur);
         }
+}
+
+// ---- the intensity histograms of boxes (SQYAMD_Histogram_Boxes_*) ----
+// Voxel v of a box falls into bin v >> shift of the box's nbins = R >> shift counters (R = 65536 for 16-bit voxels, 256 for 8-bit ones).
+// A workgroup counts into a private array of hist_window_bins(nbins) counters in LDS: the whole histogram up to kHistWindowBins bins
+// (64 KiB), else ONE window of that many bins -- window k holds the bins [k kHistWindowBins, (k + 1) kHistWindowBins) -- voted from the
+// first voxel each thread counts (hist_vote_window, hist_best_window: the first of the windows with the most votes); a bin outside the
+// window goes straight to the output.  Whatever window wins, the counts are the same.  Stacks have long constant runs, and 64 lanes
+// adding 1 to one LDS address serialise, so equal neighbours can go in one add (MERGE, below): hist_count merges equal consecutive bins
+// of a thread's whole walk -- what `run` still holds behind the walk's last voxel is the caller's to send with hist_flush --, hist_piece
+// a full piece of sixteen bytes whose bins are all equal.  The sink: sink.add(bin, n) -- the kernels' routes a
+// bin with hist_window_slot to an LDS atomic or a global one, the host test's (tests/sanitize/histogram_boxes_test.cpp, which holds the
+// whole walk against a triple loop) to two arrays.
+constexpr uint32_t kHistWindowBins = 16384;
+
+SQY_VIEW_HD inline uint32_t hist_bin(uint32_t v, uint32_t shift) { return v >> shift; }
+SQY_VIEW_HD inline uint32_t hist_window_bins(uint32_t nbins) { return nbins < kHistWindowBins ? nbins : kHistWindowBins; }
+SQY_VIEW_HD inline uint32_t hist_windows(uint32_t nbins) { return nbins / hist_window_bins(nbins ? nbins : 1u); }
+SQY_VIEW_HD inline uint32_t hist_vote_window(uint32_t bin) { return bin / kHistWindowBins; }
+// the first of the nwin (<= 4) windows with the most votes
+SQY_VIEW_HD inline uint32_t hist_best_window(const uint32_t votes[4], uint32_t nwin)
+{
+    uint32_t best = 0;
+    for (uint32_t q = 1; q < 4; ++q)
+        if (q < nwin && votes[q] > votes[best]) best = q;
+    return best;
+}
+// true: `bin` is counter *slot of the window that begins at bin wbase and holds wbins bins
+SQY_VIEW_HD inline bool hist_window_slot(uint32_t bin, uint32_t wbase, uint32_t wbins, uint32_t* slot)
+{
+    *slot = bin - wbase;
+    return *slot < wbins;                                               // (bin < wbase wraps far above wbins)
+}
+
+// the equal bins a thread has seen in a row and not sent yet (n == 0: none)
+struct HistRun { uint32_t bin, n; };
+
+// MERGE: kHistMergeNone, one add per voxel; kHistMergeRuns, equal consecutive bins of the thread's whole walk in one add;
+// kHistMergePieces, a full piece of sixteen bytes whose bins are all equal in one add, voxel by voxel otherwise (hist_piece)
+constexpr int kHistMergeNone = 0, kHistMergeRuns = 1, kHistMergePieces = 2;
+
+template <int MERGE, class Sink>
+SQY_VIEW_HD inline void hist_count(Sink& sink, HistRun* run, uint32_t bin)
+{
+    if constexpr (MERGE != kHistMergeRuns) sink.add(bin, 1u);
+    else {
+        if (run->n != 0 && run->bin == bin) { ++run->n; return; }
+        if (run->n != 0) sink.add(run->bin, run->n);
+        run->bin = bin;
+        run->n = 1;
+    }
+}
+template <class Sink>
+SQY_VIEW_HD inline void hist_flush(Sink& sink, HistRun* run)
+{
+    if (run->n != 0) sink.add(run->bin, run->n);
+    run->n = 0;
+}
+
+// voxels [lo, hi) of a piece of sixteen bytes packed as in a dense copy (hi <= 16 / ELEM), counted
+template <int ELEM, int MERGE, class Sink>
+SQY_VIEW_HD inline void hist_piece(Sink& sink, HistRun* run, const uint32_t a[4], uint32_t lo, uint32_t hi, uint32_t shift)
+{
+    constexpr uint32_t G = 16 / ELEM, M = ELEM == 2 ? 0xffffu : 0xffu;
+    if constexpr (MERGE == kHistMergePieces) {
+        if (lo == 0 && hi == G) {                                       // the bins of all G voxels at once: each voxel's field shifted in place
+            const uint32_t m = (M >> shift) * (ELEM == 2 ? 0x00010001u : 0x01010101u);
+            const uint32_t b0 = (a[0] >> shift) & m, b1 = (a[1] >> shift) & m, b2 = (a[2] >> shift) & m, b3 = (a[3] >> shift) & m;
+            const uint32_t turned = (b0 >> (8u * ELEM)) | (b0 << (32u - 8u * ELEM));      // (equal to b0: all its fields are equal)
+            if (b0 == b1 && b0 == b2 && b0 == b3 && b0 == turned) { sink.add(b0 & M, G); return; }
+        }
+    }
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (uint32_t k = 0; k < G; ++k)
+        if (k >= lo && k < hi) hist_count<MERGE>(sink, run, hist_bin((a[k * ELEM / 4] >> (8u * ((k * ELEM) & 3u))) & M, shift));
+}
+
+// window_compare16 with a count where it compares: the piece `a` holds the n decoded voxels (n <= 16 / ELEM) at offset p of the thread's
+// run; those inside the current sub-run `cur` -- and the ones behind it that the piece reaches, have: there is one -- are counted.
+// Pieces come in ascending p.
+template <int ELEM, int MERGE, class Sink>
+SQY_VIEW_HD inline void window_histogram16(Sink& sink, const WindowGeometry& g, WindowClip& c, WindowPiece& cur, bool& have, const uint32_t a[4], uint32_t p, uint32_t n,
+                                           uint32_t shift, HistRun* run)
+{
+    while (have && cur.run_off < (uint64_t)p + n) {
+        const uint64_t end = cur.run_off + cur.len;                  // (> p: a sub-run that ends in front of the piece has been left)
+        const uint32_t lo = cur.run_off > p ? (uint32_t)(cur.run_off - p) : 0u, hi = end < (uint64_t)p + n ? (uint32_t)(end - p) : n;
+        hist_piece<ELEM, MERGE>(sink, run, a, lo, hi, shift);
+        if (end > (uint64_t)p + n) break;                             // the sub-run goes on in the next piece
+        have = window_clip_next(g, &c, &cur);
+    }
 }
 
 } // namespace sqy

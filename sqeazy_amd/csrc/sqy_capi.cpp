@@ -85,6 +85,8 @@ struct Options {
     std::atomic<long> project_boxes_walk;               // projection along axis 0 on the transposer path: the z-walking form (registers, plain stores) where every box is on the 32-voxel grid (0: always the atomics -- same images)
     std::atomic<long> project_boxes_subset;             // projection of many boxes of one blob: only the LZ4 frames the boxes' z-ranges need, the projecting range transposer or one projection in the compaction, where sqy::project_boxes_path allows (0: the blob decoded whole once, one projection launch)
     std::atomic<long> bin_boxes_subset;                 // binned read of many boxes of one blob: only the LZ4 frames the boxes' z-ranges need, the binning job-table kernel (a workgroup per block of cells, LDS accumulators) or one per-cell launch in the compaction, where sqy::bin_boxes_path allows (0: the blob decoded whole once, one per-cell launch)
+    std::atomic<long> histogram_boxes_subset;           // histograms of many boxes of one blob: only the LZ4 frames the boxes' z-ranges need, the counting range transposer or one window histogram in the compaction, where sqy::histogram_boxes_path allows (0: the blob decoded whole once, one window histogram)
+    std::atomic<long> histogram_boxes_merge;            // how the histogram kernels add equal neighbours: 2 a piece of sixteen bytes whose bins are all equal in one LDS atomic, 1 equal consecutive voxels of a thread's whole run in one, 0 one per voxel -- same counts
     std::atomic<long> update_box_subset;                // box update of one blob: only the LZ4 frames the box's z-range needs are decoded, patched, parsed again and spliced between the old ones, where sqy::update_box_path allows (0: whole decode, one paste, the single call's encode)
     std::atomic<long> update_boxes_subset;              // update of many boxes of one blob: update_box_subset's stages, each once for all boxes (0: the blob decoded whole once, the pastes layer by layer, the single call's encode)
     std::atomic<long> decode_slabs_joint;               // slab-set decode: the chunked LZ4 blobs of a group indexed and decoded by one launch each (0: blob by blob)
@@ -114,7 +116,8 @@ struct Options {
           decode_box_subset(env_flag("SQY_NO_DECODE_BOX_SUBSET") ? 0 : 1), decode_boxes_joint(env_flag("SQY_NO_DECODE_BOXES_JOINT") ? 0 : 1),
           compare_boxes_subset(env_flag("SQY_NO_COMPARE_BOXES_SUBSET") ? 0 : 1),
           project_boxes_walk(env_flag("SQY_NO_PROJECT_BOXES_WALK") ? 0 : 1), project_boxes_subset(env_flag("SQY_NO_PROJECT_BOXES_SUBSET") ? 0 : 1),
-          bin_boxes_subset(env_flag("SQY_NO_BIN_BOXES_SUBSET") ? 0 : 1), update_box_subset(env_flag("SQY_NO_UPDATE_BOX_SUBSET") ? 0 : 1),
+          bin_boxes_subset(env_flag("SQY_NO_BIN_BOXES_SUBSET") ? 0 : 1), histogram_boxes_subset(env_flag("SQY_NO_HISTOGRAM_BOXES_SUBSET") ? 0 : 1),
+          histogram_boxes_merge(env_flag("SQY_NO_HISTOGRAM_BOXES_MERGE") ? 0 : 2), update_box_subset(env_flag("SQY_NO_UPDATE_BOX_SUBSET") ? 0 : 1),
           update_boxes_subset(env_flag("SQY_NO_UPDATE_BOXES_SUBSET") ? 0 : 1),
           decode_slabs_joint(env_flag("SQY_NO_DECODE_SLABS_JOINT") ? 0 : 1), decode_batch_joint(env_flag("SQY_NO_DECODE_BATCH_JOINT") ? 0 : 1),
           decode_batch_group_bytes(env_number("SQY_DECODE_BATCH_GROUP_BYTES", (long)kSlabsGroupBytes, 1, (long)kSlabsGroupBytes)), encode_batch_joint(env_flag("SQY_NO_ENCODE_BATCH_JOINT") ? 0 : 1),
@@ -144,6 +147,8 @@ struct Options {
         if (!std::strcmp(name, "project_boxes_subset")) return &project_boxes_subset;
         if (!std::strcmp(name, "project_boxes_walk")) return &project_boxes_walk;
         if (!std::strcmp(name, "bin_boxes_subset")) return &bin_boxes_subset;
+        if (!std::strcmp(name, "histogram_boxes_subset")) return &histogram_boxes_subset;
+        if (!std::strcmp(name, "histogram_boxes_merge")) return &histogram_boxes_merge;
         if (!std::strcmp(name, "update_box_subset")) return &update_box_subset;
         if (!std::strcmp(name, "update_boxes_subset")) return &update_boxes_subset;
         if (!std::strcmp(name, "decode_slabs_joint")) return &decode_slabs_joint;
@@ -4348,6 +4353,184 @@ int bin_boxes_from_host(const char* src, long srclength, long count, const long*
     });
 }
 
+// ---- the intensity histograms of many boxes of one large blob (SQYAMD_Histogram_Boxes_*) ------------------------------------
+// compare_boxes_on_device with a count for the compare: ONE header fetch, the LZ4 frames of all boxes' z-ranges united, ONE launch that
+// zeroes every histogram over the counting launch's own tables, ONE counting launch; sqy::histogram_boxes_path says what runs and
+// sqy::admit_histogram what is admitted.  Nothing but the histograms' counters is written outside the workspace.
+
+// zeroes and one window histogram under the name "boxes_window_histogram", a job per box (its `view` the histogram)
+int launch_boxes_histogram(Context& cx, hipStream_t stream, WindowLaunch& l, int elem_size, int shift)
+{
+    std::vector<PendingEvent>* pend = &cx.pending;
+    const uint32_t* d_tiles = nullptr;
+    if (l.upload(stream, cx.ws.boxes_jobs, &d_tiles)) return 1;
+    const sqy::BatchWindowJob* d_jobs = static_cast<const sqy::BatchWindowJob*>(cx.ws.boxes_jobs.p);
+    SQY_TIMED("boxes_histogram_init", sqy::launch_boxes_histogram_init(d_jobs, d_tiles, (uint32_t)l.jobs.size(), l.ntiles, sqy::histogram_bins(elem_size, shift), stream));
+    SQY_TIMED("boxes_window_histogram", sqy::launch_boxes_window_histogram(d_jobs, d_tiles, (uint32_t)l.jobs.size(), l.ntiles, elem_size, (uint32_t)shift,
+                                                                            (int)g_opt.histogram_boxes_merge.load(), stream));
+    return 0;
+}
+
+// the histograms' launches behind DecodeCall::frames_subset: box i (ws[i]) of the united frames in c.range_buf into hists[i]
+int boxes_range_histogram(DecodeCall& c, WindowLaunch& l, TiledJobs<sqy::Bitswap1BoxJob>& tj, const std::vector<sqy::BatchWindow>& ws, void* const* hists, unsigned rank,
+                          int shift, int want_elem)
+{
+    hipStream_t stream = c.stream;
+    std::vector<PendingEvent>* pend = c.pend;
+    const sqy::FrameRangesPlan& p = c.ranges_plan;
+    const size_t count = ws.size();
+    if (p.boxes.size() != count) return 1;
+    if (sqy::histogram_boxes_path(true, c.range_form, true) == sqy::BoxPath::subset_transposer) {
+        const uint16_t* lut = nullptr;
+        if (c.range_lut(&lut)) return 1;
+        if (sqy::histogram_bins(lut ? 2 : p.we, shift) != sqy::histogram_bins(want_elem, shift)) return 1;      // (the counted voxel is the entry point's)
+        const uint32_t wpt = 128u / (8u * (uint32_t)p.we);
+        for (size_t i = 0; i < count; ++i) {
+            const sqy::BatchWindow& w = ws[i];
+            const sqy::FrameRangesBox& b = p.boxes[i];
+            sqy::Bitswap1BoxJob j;
+            j.view = hists[i];
+            j.g = sqy::WindowGeometry{w.bY, w.bX, w.oz, w.oy, w.ox, w.Z, w.Y, w.X, w.Y * w.X, w.X};      // (the pitches are not used: nothing is stored by place)
+            std::copy(b.plane, b.plane + 16, j.r.plane);
+            j.r.tail = b.tail; j.r.w0 = b.w0; j.r.w1 = b.w1; j.r.v0 = b.v0; j.r.v1 = b.v1; j.r.L = b.L;
+            j.t0 = sqy::range_first_thread(b.w0, wpt);
+            if (!sqy::bitswap1_box_job_ok(j)) return 1;
+            tj.jobs.push_back(j);
+            tj.first_tile.push_back(tj.ntiles);
+            tj.ntiles += (uint32_t)sqy::range_job_groups(b.w0, b.w1, wpt);
+        }
+        const uint32_t* d_tiles = nullptr;
+        if (tj.upload(stream, c.cx.ws.boxes_jobs, &d_tiles)) return 1;
+        const sqy::Bitswap1BoxJob* d_jobs = static_cast<const sqy::Bitswap1BoxJob*>(c.cx.ws.boxes_jobs.p);
+        SQY_TIMED("boxes_histogram_init", sqy::launch_boxes_histogram_init(d_jobs, d_tiles, (uint32_t)count, tj.ntiles, sqy::histogram_bins(want_elem, shift), stream));
+        SQY_TIMED(lut ? "bitswap1_quantiser_histogram_boxes" : "bitswap1_histogram_boxes",
+                  sqy::launch_bitswap1_decode_range_windows_histogram(c.range_buf, d_jobs, d_tiles, (uint32_t)count, tj.ntiles, p.we, lut, (uint32_t)shift,
+                                                                      (int)g_opt.histogram_boxes_merge.load(), stream));
+        return 0;
+    }
+    // plain, shuffle: box i's range in the workspace is a blob of its frames, the box begins at its first one (boxes_range_out's geometry)
+    for (size_t i = 0; i < count; ++i) {
+        sqy::BatchWindow in_range = ws[i];
+        if (rank == 3) { in_range.bZ = in_range.Z; in_range.oz = 0; }
+        else if (rank == 2) { in_range.bY = in_range.Y; in_range.oy = 0; }
+        else { in_range.bX = in_range.X; in_range.ox = 0; }
+        l.add(hists[i], c.range_buf + p.boxes[i].range_at, in_range, WindowView{in_range.Y * in_range.X, in_range.X}, false);
+    }
+    return launch_boxes_histogram(c.cx, stream, l, c.h.elem_size(), shift);
+}
+
+// Box i = [origins + i rank, .. + extents + i rank) of the blob counted into the histogram at d_hists[i].  sqy::admit_histogram for
+// every box and the launches' sizes -- all before anything is written
+int histogram_boxes_on_device(Context& cx, const void* d_src_v, uint64_t srclen, size_t count, const long* origins, const long* extents, unsigned rank, int shift,
+                              void* const* d_hists, int want_elem, hipStream_t stream)
+{
+    const uint8_t* d_src = static_cast<const uint8_t*>(d_src_v);
+    DrainOnExit drain{stream, &cx.pending, cx.side};
+    sqy::HeaderInfo h;
+    if (fetch_header(d_src, srclen, stream, h)) return 1;
+    uint64_t raw_bytes = 0;
+    if (!admit_blob(h, srclen, want_elem, &raw_bytes)) return 1;
+    std::vector<sqy::BatchWindow> ws(count);
+    std::vector<std::pair<uint64_t, uint64_t>> ranges(count);
+    const uint64_t frame_voxels = raw_bytes / (uint64_t)want_elem / h.shape[0];
+    uint64_t copy_tiles = 0, range_groups = 0;               // what the one counting launch may hold, whichever it is
+    for (size_t i = 0; i < count; ++i) {
+        const long* o = origins + i * rank;
+        const long* e = extents + i * rank;
+        if (!sqy::admit_histogram(h.shape, o, e, rank, shift, want_elem, d_hists[i], &ws[i])) {
+            std::fprintf(stderr, "[sqeazy]\t histogram boxes: box %zu does not lie inside the blob's shape, or has another rank\n", i);
+            return 1;
+        }
+        ranges[i] = {(uint64_t)o[0], (uint64_t)e[0]};
+        copy_tiles += sqy::batch_bitswap1_tiles(ws[i].Z * ws[i].Y * ws[i].X);
+        range_groups += (uint64_t)e[0] * frame_voxels / sqy::kBatchTileVoxels + 2;      // (at least range_job_groups of the box's words)
+    }
+    if (std::max(copy_tiles, range_groups) > 0x7fffffffull) {
+        std::fprintf(stderr, "[sqeazy]\t histogram boxes: too many workgroups for one launch\n");
+        return 1;
+    }
+    WindowLaunch l;                                                     // (both wait for the stream before their tables go)
+    TiledJobs<sqy::Bitswap1BoxJob> tj;
+    if (g_opt.histogram_boxes_subset.load()) {
+        DecodeCall c(cx, stream, nullptr, h, Pipeline::from_string(h.pipename), raw_bytes / (uint64_t)want_elem, d_src + h.size);
+        bool taken = false;
+        if (const int rc = c.frames_subset(ranges, false, &taken)) return rc;
+        if (taken) {
+            if (const int rc = boxes_range_histogram(c, l, tj, ws, d_hists, rank, shift, want_elem)) return rc;
+            return c.finish();
+        }
+    }
+    // sqy::BoxPath::whole_copy: the whole volume ONCE, then all boxes in one launch
+    if (cx.ws.range_full.ensure(std::max<uint64_t>(raw_bytes, 16))) return 1;
+    if (const int rc = decode_on_device(cx, d_src_v, srclen, cx.ws.range_full.p, raw_bytes, want_elem, stream)) return rc;
+    for (size_t i = 0; i < count; ++i) l.add(d_hists[i], cx.ws.range_full.p, ws[i], WindowView{ws[i].Y * ws[i].X, ws[i].X}, false);
+    if (launch_boxes_histogram(cx, stream, l, want_elem, shift)) return 1;
+    SQY_HIP(hipStreamSynchronize(stream));
+    if (g_prof_on.load()) prof_collect(cx.pending);
+    return 0;
+}
+
+// what SQYAMD_Histogram_Boxes_* checks without a header, before a device is looked for: boxes_arguments_ok, and sqy::admit_histogram of
+// every box against the smallest shape that holds it -- the shift, the histogram's pointer
+bool histogram_arguments_ok(const void* src, long srclength, long count, const long* origins, const long* extents, unsigned rank, int shift, void* const* hists,
+                            int elem_size)
+{
+    if (!boxes_arguments_ok(src, srclength, count, origins, hists, extents, rank)) return false;
+    for (long i = 0; i < count; ++i) {
+        const long* o = origins + (size_t)i * rank;
+        const long* e = extents + (size_t)i * rank;
+        std::vector<uint64_t> shape(rank);
+        for (unsigned k = 0; k < rank; ++k) shape[k] = (uint64_t)o[k] + (uint64_t)std::max(e[k], 0l);     // (both below 2^63: no wrap)
+        sqy::BatchWindow w;
+        const void* out = hists ? hists[i] : static_cast<const void*>(&w);                                 // (host variant: the histograms are the library's)
+        if (!sqy::admit_histogram(shape, o, e, rank, shift, elem_size, out, &w)) return false;
+    }
+    return true;
+}
+
+int histogram_boxes_device(const void* d_src, long srclength, long count, const long* origins, const long* extents, unsigned rank, int shift, void* const* d_hists,
+                           int elem_size, void* hip_stream)
+{
+    if (!d_hists || !histogram_arguments_ok(d_src, srclength, count, origins, extents, rank, shift, d_hists, elem_size)) {
+        std::fprintf(stderr, "[sqeazy]\t histogram boxes: bad arguments\n");
+        return 1;
+    }
+    ContextLease lease;
+    if (!lease.ctx) { std::fprintf(stderr, "[sqeazy]\t no usable HIP device\n"); return 1; }
+    return histogram_boxes_on_device(*lease.ctx, d_src, (uint64_t)srclength, (size_t)count, origins, extents, rank, shift, d_hists, elem_size,
+                                     static_cast<hipStream_t>(hip_stream));
+}
+
+// host pointers: the header and every box are checked here, before anything is staged; the histograms come back dense, back to back in
+// box order, nbins 32-bit counters each
+int histogram_boxes_from_host(const char* src, long srclength, long count, const long* origins, const long* extents, unsigned rank, int shift, char* out,
+                              long out_capacity, int elem_size)
+{
+    if (!out || !histogram_arguments_ok(src, srclength, count, origins, extents, rank, shift, nullptr, elem_size)) {
+        std::fprintf(stderr, "[sqeazy]\t histogram boxes: bad arguments\n");
+        return 1;
+    }
+    const uint64_t hist_bytes = (uint64_t)sqy::histogram_bins(elem_size, shift) * 4u, total = (uint64_t)count * hist_bytes;      // (count fits an int: no wrap)
+    if (total > (uint64_t)std::max(out_capacity, 0l)) { std::fprintf(stderr, "[sqeazy]\t histogram boxes: buffer too small\n"); return 1; }
+    const sqy::HeaderInfo h = sqy::header_unpack(src, src + srclength);
+    if (!h.valid) { std::fprintf(stderr, "[sqeazy]\t unable to find a sqy header in the blob\n"); return 1; }
+    uint64_t raw = 0;
+    if (!header_shape_ok(h, (uint64_t)srclength, &raw)) return 1;
+    if (h.elem_size() != elem_size) { std::fprintf(stderr, "[sqeazy]\t blob holds %s voxels\n", h.type.c_str()); return 1; }
+    for (long i = 0; i < count; ++i) {
+        sqy::BatchWindow w;
+        if (!sqy::admit_histogram(h.shape, origins + (size_t)i * rank, extents + (size_t)i * rank, rank, shift, elem_size, &w, &w)) {
+            std::fprintf(stderr, "[sqeazy]\t histogram boxes: box %ld does not lie inside the blob's shape\n", i);
+            return 1;
+        }
+    }
+    return decode_staged(src, (uint64_t)srclength, out, total, [&](Context& cx, void* d_src, void* d_dst, hipStream_t stream) {
+        std::vector<void*> ptrs((size_t)count);
+        for (long i = 0; i < count; ++i) ptrs[(size_t)i] = static_cast<uint8_t*>(d_dst) + (uint64_t)i * hist_bytes;
+        return histogram_boxes_on_device(cx, d_src, (uint64_t)srclength, (size_t)count, origins, extents, rank, shift, ptrs.data(), elem_size, stream);
+    });
+}
+
 int decode_batch_device(const void* d_src, const BatchDecodeArgs& a, int elem_size, void* hip_stream)
 {
     if (admit_decode_batch(d_src, a)) return 1;
@@ -6140,6 +6323,30 @@ int SQYAMD_Bin_Boxes_UI8(const char* src, long srclength, long count, const long
     return guarded([&]() -> int { return bin_boxes_from_host(src, srclength, count, origins, extents, rank, bins, op, out, out_capacity, 1); });
 }
 
+int SQYAMD_Histogram_Boxes_UI16_Device(const void* d_src, long srclength, long count, const long* origins, const long* extents, unsigned rank, int shift,
+                                       void* const* d_hists, void* hip_stream)
+{
+    return guarded([&]() -> int { return histogram_boxes_device(d_src, srclength, count, origins, extents, rank, shift, d_hists, 2, hip_stream); });
+}
+
+int SQYAMD_Histogram_Boxes_UI8_Device(const void* d_src, long srclength, long count, const long* origins, const long* extents, unsigned rank, int shift,
+                                      void* const* d_hists, void* hip_stream)
+{
+    return guarded([&]() -> int { return histogram_boxes_device(d_src, srclength, count, origins, extents, rank, shift, d_hists, 1, hip_stream); });
+}
+
+int SQYAMD_Histogram_Boxes_UI16(const char* src, long srclength, long count, const long* origins, const long* extents, unsigned rank, int shift, char* out,
+                                long out_capacity)
+{
+    return guarded([&]() -> int { return histogram_boxes_from_host(src, srclength, count, origins, extents, rank, shift, out, out_capacity, 2); });
+}
+
+int SQYAMD_Histogram_Boxes_UI8(const char* src, long srclength, long count, const long* origins, const long* extents, unsigned rank, int shift, char* out,
+                               long out_capacity)
+{
+    return guarded([&]() -> int { return histogram_boxes_from_host(src, srclength, count, origins, extents, rank, shift, out, out_capacity, 1); });
+}
+
 int SQYAMD_Decode_Slabs_UI16_Device(const void* d_src, const long* offsets, const long* lengths, int nslabs, void* d_dst, long dst_capacity,
                                     long* frames, int inflight, void* hip_stream)
 {
@@ -6344,7 +6551,7 @@ int SQYAMD_Set_Option(const char* name, long value)
     if (o == &g_opt.block_parallel_warmup) { if (value < 0 || value > kWarmupMax) return 1; }
     else if (o == &g_opt.transpose_tiles_per_wave) { if (value < 1 || value > 64) return 1; sqy::set_bitswap1_tiles_per_wave(value); }
     else if (o == &g_opt.host_l2_bytes) { if (value < 0 || value > (long)UINT32_MAX) return 1; }
-    else if (o == &g_opt.stage_lanes) { if (value < 0 || value > 2) return 1; }
+    else if (o == &g_opt.stage_lanes || o == &g_opt.histogram_boxes_merge) { if (value < 0 || value > 2) return 1; }
     else if (o == &g_opt.encode_batch_group_bytes) { if (value < 1 || value > kBatchBytesMax) return 1; }
     else if (o == &g_opt.decode_batch_group_bytes) { if (value < 1 || value > (long)kSlabsGroupBytes) return 1; }
     else if (o == &g_opt.encode_batch_joint_max_bytes) { if (value < 0 || value > kBatchBytesMax) return 1; }

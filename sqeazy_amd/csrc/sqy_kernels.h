@@ -546,6 +546,27 @@ struct BoxBinJob {
 };
 constexpr uint64_t kBoxBinJobBytes = 144;
 hipError_t launch_boxes_window_bin(const BoxBinJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ngroups, int elem_size, hipStream_t stream);
+// ---- the intensity histograms of many boxes of one large blob (SQYAMD_Histogram_Boxes_*) ----
+// launch_bitswap1_decode_range_windows_compare with a count where it compares: job j is a Bitswap1BoxJob whose `view` is the box's
+// histogram -- nbins = (65536 or 256) >> shift counters of uint32_t, dense; the 16-bit range behind the look-up --, the tables, the
+// groups and bitswap1_box_job_ok as there.  A workgroup counts the box's voxels of its 32768 into a private LDS array of
+// sqy::hist_window_bins(nbins) counters (sqy_batch_window.hpp: the whole histogram up to 16384 bins, else a window voted from the first
+// voxel each thread counts; bins outside it go to the output by a no-return global atomic), and behind a barrier adds its non-zero
+// counters into the output with no-return 32-bit atomics at device scope; zero counters issue nothing.  merge: how equal
+// neighbours are added, sqy::kHistMergeNone, kHistMergeRuns or kHistMergePieces.  A thread whose run holds nothing of the box loads no
+// plane word but reaches every barrier; a workgroup in which no thread holds a voxel of the box returns before it zeroes anything.  The histograms hold zeros beforehand: launch_boxes_histogram_init over the SAME tables, in front on the stream --
+// workgroup `own` of a job's groups zeroes the counters own 256 + tid, + groups 256, ...  Nothing but the histograms is written.
+hipError_t launch_boxes_histogram_init(const Bitswap1BoxJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ngroups, uint32_t nbins, hipStream_t stream);
+hipError_t launch_bitswap1_decode_range_windows_histogram(const uint8_t* in, const Bitswap1BoxJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ngroups,
+                                                          int elem_size, const uint16_t* lut, uint32_t shift, int merge, hipStream_t stream);
+// The histograms of boxes of a DENSE volume (the compaction of `lz4` and `frame_shuffle->lz4` blobs, the whole decode): the grid of
+// launch_batch_window_compare -- job j is a BatchWindowJob whose `view` is the box's histogram and whose `dense` is the volume (sz, sy,
+// tile0 are not read), a workgroup per 32768 voxels of the box, its rows gathered sixteen bytes at a time -- with the same LDS
+// histogram, vote and flush.  elem_size: of a voxel of the dense volume (2 behind the quantiser's whole decode).  The init launch takes
+// these tables too.
+hipError_t launch_boxes_histogram_init(const BatchWindowJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ngroups, uint32_t nbins, hipStream_t stream);
+hipError_t launch_boxes_window_histogram(const BatchWindowJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ngroups, int elem_size, uint32_t shift,
+                                         int merge, hipStream_t stream);
 // ---- a box written into one large blob (SQYAMD_Update_Box_*) ----
 // launch_bitswap1_decode_range_window the other way round, in place: the box's voxels are read from the view (box.view; `dense` and tile0
 // are not read) and merged into the plane words [w0, w1) and the tail of the range r inside the compaction at buf (launch_bitswap1_batch_patch's

@@ -8929,6 +8929,329 @@ hipError_t launch_bitswap1_decode_batch_window_compare(const BatchCompareJob* d_
     return hipGetLastError();
 }
 
+// ---- the intensity histograms of many boxes of one large blob (SQYAMD_Histogram_Boxes_*) ------------------------------------------------
+// The workgroup-private histogram both kernels count into (sqy_batch_window.hpp states the window and the vote): hist_window_bins(nbins)
+// counters of dynamic LDS -- 64 KiB at most, so two workgroups share a CU's 160 KiB.
+// the sink of hist_count on the device: an LDS atomic inside the workgroup's window, a no-return global one outside it
+struct HistLdsSink {
+    uint32_t* lds;
+    uint32_t* __restrict__ out;
+    uint32_t wbase, wbins;
+    __device__ __forceinline__ void add(uint32_t bin, uint32_t n) const
+    {
+        uint32_t slot;
+        if (hist_window_slot(bin, wbase, wbins, &slot)) (void)atomicAdd(lds + slot, n);
+        else (void)atomicAdd(out + bin, n);
+    }
+};
+
+// the window's counters and the votes to zero; the caller's barrier follows
+__device__ __forceinline__ void hist_lds_clear(uint32_t* lds, uint32_t* votes, uint32_t wbins)
+{
+    const uint32_t tid = threadIdx.x;
+    if (wbins >= 4u)
+        for (uint32_t i = tid; i < wbins / 4u; i += 256u) reinterpret_cast<uint4*>(lds)[i] = make_uint4(0, 0, 0, 0);
+    else if (tid < wbins) lds[tid] = 0;
+    if (tid < 4u) votes[tid] = 0;
+}
+
+// The first bin of the workgroup's window.  nwin is uniform: with one window nobody votes and there is no barrier; else every thread of
+// the workgroup comes here, those with a voxel to count (any) vote with its bin.
+__device__ __forceinline__ uint32_t hist_lds_vote(uint32_t* votes, uint32_t nwin, bool any, uint32_t bin)
+{
+    if (nwin <= 1u) return 0u;
+    if (any) (void)atomicAdd(votes + hist_vote_window(bin), 1u);
+    __syncthreads();
+    const uint32_t v[4] = {votes[0], votes[1], votes[2], votes[3]};
+    return hist_best_window(v, nwin) * kHistWindowBins;
+}
+
+// behind the workgroup's last count: its non-zero counters into the output, one no-return atomic each
+__device__ __forceinline__ void hist_lds_publish(const uint32_t* lds, uint32_t* __restrict__ out, uint32_t wbase, uint32_t wbins)
+{
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < wbins; i += 256u) {
+        const uint32_t n = lds[i];
+        if (n) (void)atomicAdd(out + wbase + i, n);
+    }
+}
+
+// voxel k (< 128) of a thread's run out of its sixteen bytes of every plane: pl[b] carries bit b, plane word i of the run lies at bit
+// W i of pl[b][0..3], and bit W - 1 - k' of a word is voxel W i + k' (the vote needs ONE voxel in front of the transposes)
+template <int ELEM>
+__device__ __forceinline__ uint32_t plane_run_voxel(const uint32_t (&pl)[8 * ELEM][4], uint32_t k)
+{
+    const uint32_t q = k >> 5;
+    const uint32_t bit = ELEM == 2 ? 16u * ((k >> 4) & 1u) + 15u - (k & 15u) : 8u * ((k >> 3) & 3u) + 7u - (k & 7u);
+    // the candidate of each of the four dwords, then ONE choice among four values: a choice among pl[b][0..3] themselves would index
+    // the register array at run time and send it to scratch
+    uint32_t v0 = 0, v1 = 0, v2 = 0, v3 = 0;
+#pragma unroll
+    for (int b = 0; b < 8 * ELEM; ++b) {
+        v0 |= ((pl[b][0] >> bit) & 1u) << b;
+        v1 |= ((pl[b][1] >> bit) & 1u) << b;
+        v2 |= ((pl[b][2] >> bit) & 1u) << b;
+        v3 |= ((pl[b][3] >> bit) & 1u) << b;
+    }
+    return q == 0u ? v0 : q == 1u ? v1 : q == 2u ? v2 : v3;
+}
+
+// every histogram's counters zeroed, over the counting launch's own tables (Job: its `view` is the histogram): workgroup `own` of job
+// j's groups zeroes every groups-th run of 256 counters
+template <class Job>
+__global__ __launch_bounds__(256)
+void boxes_histogram_init_kernel(const Job* __restrict__ jobs, const uint32_t* __restrict__ first_tile, uint32_t njobs, uint32_t nbins)
+{
+    const uint32_t j = batch_job_of_tile(first_tile, njobs);
+    const uint32_t own = blockIdx.x - first_tile[j], groups = first_tile[j + 1] - first_tile[j];
+    uint32_t* __restrict__ out = static_cast<uint32_t*>(jobs[j].view);
+    for (uint64_t e = (uint64_t)own * 256u + threadIdx.x; e < nbins; e += (uint64_t)groups * 256u) out[e] = 0;
+}
+
+// bitswap1_decode_range_windows_compare_kernel with window_histogram16 where it compares: the same job walk, absolute-word grid
+// (sqy::range_run), clip, plane loads (sixteen bytes on the stream's grid, word by word elsewhere), transposes and look-up.  The plane
+// words are loaded in front of the vote, which takes the thread's first voxel inside the box out of them (plane_run_voxel); a thread
+// without a word, or whose run has nothing inside the box, loads no plane word, does not vote and counts nothing, but reaches the vote's
+// barrier and the flush.  The job's first workgroup sends the tail voxels straight to the output.  LUT: the counted voxel is the 16-bit
+// one out of the decode table.  Nothing but the job's histogram is written, by atomics alone.
+template <int ELEM, bool LUT, int MERGE>
+__global__ __launch_bounds__(256)
+void bitswap1_decode_range_windows_histogram_kernel(const uint8_t* __restrict__ in, const Bitswap1BoxJob* __restrict__ jobs, const uint32_t* __restrict__ first_tile,
+                                                    uint32_t njobs, const uint16_t* __restrict__ lut, uint32_t shift)
+{
+    static_assert(!LUT || ELEM == 1, "the look-up follows 8-bit planes");
+    constexpr uint32_t W = 8 * ELEM, WPT = BSWB_THREAD_VOX / W;        // voxels per word, words per thread
+    extern __shared__ __align__(16) uint32_t hist_lds[];              // hist_window_bins(nbins) counters
+    __shared__ uint32_t votes[4];
+    __shared__ uint16_t sl[LUT ? 256 : 1];
+    const uint32_t nbins = ((LUT || ELEM == 2) ? 65536u : 256u) >> shift, wbins = hist_window_bins(nbins), nwin = hist_windows(nbins);
+    if constexpr (LUT) { sl[threadIdx.x] = lut[threadIdx.x]; __syncthreads(); }
+    const uint32_t j = batch_job_of_tile(first_tile, njobs);
+    const Bitswap1BoxJob* __restrict__ job = jobs + j;                  // (uniform: its fields live in scalar registers)
+    const uint32_t own = blockIdx.x - first_tile[j], tid = threadIdx.x;
+    const Bitswap1Range& a = job->r;
+    const WindowGeometry& g = job->g;
+    uint32_t* __restrict__ out = static_cast<uint32_t*>(job->view);
+    WindowPiece cur;
+    const uint64_t tail0 = a.v0 > a.L ? a.v0 : a.L;
+    if (own == 0 && tail0 + tid < a.v1) {                            // tail voxels: verbatim in the stream (or looked up), those of the box
+        WindowClip ct = window_clip_start(g, tail0 + tid, 1);
+        if (window_clip_next(g, &ct, &cur)) {
+            const uint32_t x = view_voxel_load<ELEM>(in + a.tail, tid);
+            (void)atomicAdd(out + hist_bin(LUT ? (uint32_t)sl[x & 0xffu] : x, shift), 1u);
+        }
+    }
+    const RangeRun run = range_run(job->t0 + (uint64_t)own * 256u + tid, WPT, a.w0, a.w1);
+    const bool owns = run.lo != run.hi;
+    WindowClip c = window_clip_start(g, owns ? run.first * W : 0, owns ? (uint64_t)run.hi * W : 0);
+    bool have = owns && window_clip_next(g, &c, &cur);
+    // a workgroup whose 32768 voxels hold nothing of the box (most of them where the box is a small crop of large frames) is done: it
+    // zeroes, counts and flushes nothing
+    if (!__syncthreads_or(have ? 1 : 0)) return;
+    hist_lds_clear(hist_lds, votes, wbins);
+    uint32_t pl[W][4];                                                // pl[b] = the thread's 16 bytes of the plane that carries bit b
+    if (have) {                                                       // (else: nothing of the run inside the box, no plane word is loaded)
+        const uint64_t at = (run.first - a.w0) * ELEM;                // the thread's 16 bytes behind plane[s] (in front of it: a first thread's words not owned, never read)
+        bool wide = run.lo == 0 && run.hi == WPT;
+        if (wide) {
+            uint32_t off_grid = 0;                                    // (uniform: first ELEM is a multiple of 16)
+#pragma unroll
+            for (uint32_t p = 0; p < W; ++p) off_grid |= (uint32_t)(reinterpret_cast<uintptr_t>(in) + a.plane[p] + at);
+            wide = (off_grid & 15u) == 0;
+        }
+        if (wide) {
+#pragma unroll
+            for (int b = 0; b < (int)W; ++b) {
+                const uint4 t = *reinterpret_cast<const uint4*>(in + a.plane[W - 1 - b] + at);
+                pl[b][0] = t.x; pl[b][1] = t.y; pl[b][2] = t.z; pl[b][3] = t.w;
+            }
+        } else {
+#pragma unroll
+            for (int b = 0; b < (int)W; ++b) { pl[b][0] = 0; pl[b][1] = 0; pl[b][2] = 0; pl[b][3] = 0; }
+#pragma unroll
+            for (uint32_t i = 0; i < WPT; ++i)
+                if (i >= run.lo && i < run.hi) {
+#pragma unroll
+                    for (int b = 0; b < (int)W; ++b) {
+                        if constexpr (ELEM == 2) pl[b][i >> 1] |= (uint32_t)*reinterpret_cast<const uint16_t*>(in + a.plane[15 - b] + at + 2u * i) << (16u * (i & 1u));
+                        else pl[b][i >> 2] |= (uint32_t)in[a.plane[7 - b] + at + i] << (8u * (i & 3u));
+                    }
+                }
+        }
+    }
+    __syncthreads();                                                  // (the counters and the votes are zero)
+    uint32_t first_bin = 0;
+    if (nwin > 1u && have) {                                          // (cur.run_off: the thread's first voxel inside the box)
+        const uint32_t v = plane_run_voxel<ELEM>(pl, (uint32_t)cur.run_off);
+        first_bin = hist_bin(LUT ? (uint32_t)sl[v & 0xffu] : v, shift);
+    }
+    const uint32_t wbase = hist_lds_vote(votes, nwin, have, first_bin);
+    const HistLdsSink sink{hist_lds, out, wbase, wbins};
+    HistRun hr{0, 0};
+    if (have) {
+        if constexpr (ELEM == 2) {
+#pragma unroll
+            for (uint32_t q = 0; q < 4; ++q) {                        // words first + 2 q (group A, low halves) and first + 2 q + 1 (group B)
+                if (2 * q >= run.hi || !have) break;
+                uint32_t r[16];
+#pragma unroll
+                for (int b = 0; b < 16; ++b) r[b] = pl[b][q];
+                transpose16x16_pairs(r);                              // r[i] = voxel 15 - i of group A | of group B << 16
+                uint32_t ga[8], gb[8];
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    ga[k] = __builtin_amdgcn_perm(r[14 - 2 * k], r[15 - 2 * k], 0x05040100u);
+                    gb[k] = __builtin_amdgcn_perm(r[14 - 2 * k], r[15 - 2 * k], 0x07060302u);
+                }
+                window_histogram16<2, MERGE>(sink, g, c, cur, have, ga, 32u * q, 8, shift, &hr);
+                window_histogram16<2, MERGE>(sink, g, c, cur, have, ga + 4, 32u * q + 8u, 8, shift, &hr);
+                if (2 * q + 1 >= run.hi) break;
+                window_histogram16<2, MERGE>(sink, g, c, cur, have, gb, 32u * q + 16u, 8, shift, &hr);
+                window_histogram16<2, MERGE>(sink, g, c, cur, have, gb + 4, 32u * q + 24u, 8, shift, &hr);
+            }
+        } else {
+#pragma unroll
+            for (uint32_t gq = 0; gq < 16; gq += 2) {
+                if (gq >= run.hi || !have) break;
+                uint32_t d[4];
+#pragma unroll
+                for (uint32_t u = 0; u < 2; ++u) {
+                    // (bitswap1_decode_batch_strided_kernel's gather and transpose: afterwards byte i of hi:lo = voxel 7 - i)
+                    constexpr uint32_t Zs = 0x0c;                     // v_perm selector: a zero byte
+                    const uint32_t cc = (gq + u) & 3u, wdx = (gq + u) >> 2;
+                    const uint32_t s01 = cc | ((4u + cc) << 8) | (Zs << 16) | (Zs << 24), s23 = Zs | (Zs << 8) | (cc << 16) | ((4u + cc) << 24);
+                    uint32_t lo_ = __builtin_amdgcn_perm(pl[1][wdx], pl[0][wdx], s01) | __builtin_amdgcn_perm(pl[3][wdx], pl[2][wdx], s23);
+                    uint32_t hi_ = __builtin_amdgcn_perm(pl[5][wdx], pl[4][wdx], s01) | __builtin_amdgcn_perm(pl[7][wdx], pl[6][wdx], s23);
+                    uint32_t y;
+                    y = (lo_ ^ (lo_ >> 7)) & 0x00AA00AAu; lo_ ^= y ^ (y << 7);
+                    y = (hi_ ^ (hi_ >> 7)) & 0x00AA00AAu; hi_ ^= y ^ (y << 7);
+                    y = (lo_ ^ (lo_ >> 14)) & 0x0000CCCCu; lo_ ^= y ^ (y << 14);
+                    y = (hi_ ^ (hi_ >> 14)) & 0x0000CCCCu; hi_ ^= y ^ (y << 14);
+                    y = (lo_ ^ (hi_ << 4)) & 0xF0F0F0F0u; lo_ ^= y; hi_ ^= y >> 4;
+                    d[2 * u] = __builtin_bswap32(hi_);                // voxels 0..3 of the word
+                    d[2 * u + 1] = __builtin_bswap32(lo_);            // voxels 4..7
+                }
+                if constexpr (LUT) {
+#pragma unroll
+                    for (uint32_t u = 0; u < 2; ++u) {                // word gq + u: eight 16-bit voxels, one piece
+                        if (gq + u >= run.hi) break;
+                        const uint32_t h4 = d[2 * u], l4 = d[2 * u + 1];      // (voxel k of four at byte k)
+                        const uint32_t v16[4] = {(uint32_t)sl[h4 & 0xffu] | ((uint32_t)sl[(h4 >> 8) & 0xffu] << 16), (uint32_t)sl[(h4 >> 16) & 0xffu] | ((uint32_t)sl[h4 >> 24] << 16),
+                                                 (uint32_t)sl[l4 & 0xffu] | ((uint32_t)sl[(l4 >> 8) & 0xffu] << 16), (uint32_t)sl[(l4 >> 16) & 0xffu] | ((uint32_t)sl[l4 >> 24] << 16)};
+                        window_histogram16<2, MERGE>(sink, g, c, cur, have, v16, 8u * (gq + u), 8, shift, &hr);
+                    }
+                } else
+                    window_histogram16<1, MERGE>(sink, g, c, cur, have, d, 8u * gq, run.hi - gq >= 2u ? 16u : 8u, shift, &hr);
+            }
+        }
+    }
+    hist_flush(sink, &hr);
+    hist_lds_publish(hist_lds, out, wbase, wbins);
+}
+
+// batch_window_compare_kernel's walk over the box inside the dense volume at job.dense with a count where it compares: tiles and
+// pieces are those of the BOX's dense order, piece p of a tile goes to thread p % 256.  A thread's first piece is gathered in front of
+// the vote, whose voxel is the piece's first.
+template <int ELEM, int MERGE>
+__global__ __launch_bounds__(256)
+void boxes_window_histogram_kernel(const BatchWindowJob* __restrict__ jobs, const uint32_t* __restrict__ first_tile, uint32_t njobs, uint32_t shift)
+{
+    constexpr uint32_t G = 16 / ELEM, PIECES = BSWB_TILE_VOX / G / 256u, M = ELEM == 2 ? 0xffffu : 0xffu;      // voxels per piece, pieces per thread (128 voxels)
+    extern __shared__ __align__(16) uint32_t hist_lds[];              // hist_window_bins(nbins) counters
+    __shared__ uint32_t votes[4];
+    const uint32_t nbins = (ELEM == 2 ? 65536u : 256u) >> shift, wbins = hist_window_bins(nbins), nwin = hist_windows(nbins);
+    hist_lds_clear(hist_lds, votes, wbins);
+    __syncthreads();
+    const uint32_t j = batch_job_of_tile(first_tile, njobs);
+    const BatchWindowJob job = jobs[j];
+    const uint64_t len = job.Z * job.Y * job.X;
+    const uint64_t base = (uint64_t)(blockIdx.x - first_tile[j]) * BSWB_TILE_VOX;
+    const ViewGeometry gs{job.Y, job.X, job.bY * job.bX, job.bX};
+    const uint8_t* __restrict__ src = static_cast<const uint8_t*>(job.dense) + ((job.oz * job.bY + job.oy) * job.bX + job.ox) * ELEM;
+    uint32_t* __restrict__ out = static_cast<uint32_t*>(job.view);
+    uint4 x0 = make_uint4(0, 0, 0, 0);
+    uint32_t n0 = 0;
+    const uint64_t i00 = base + (uint64_t)threadIdx.x * G;
+    if (i00 < len) {
+        n0 = (uint32_t)(len - i00 < G ? len - i00 : G);
+        ViewWalk ws = view_walk_start(gs, i00);
+        x0 = view_gather16<ELEM>(src, gs, ws, n0);
+    }
+    const uint32_t wbase = hist_lds_vote(votes, nwin, n0 != 0u, hist_bin(x0.x & M, shift));
+    const HistLdsSink sink{hist_lds, out, wbase, wbins};
+    HistRun hr{0, 0};
+    if (n0 != 0u) {
+        const uint32_t a[4] = {x0.x, x0.y, x0.z, x0.w};
+        hist_piece<ELEM, MERGE>(sink, &hr, a, 0u, n0, shift);
+        for (uint32_t k = 1; k < PIECES; ++k) {
+            const uint64_t i0 = base + ((uint64_t)k * 256u + threadIdx.x) * G;
+            if (i0 >= len) break;
+            const uint32_t n = (uint32_t)(len - i0 < G ? len - i0 : G);
+            ViewWalk ws = view_walk_start(gs, i0);
+            const uint4 x = view_gather16<ELEM>(src, gs, ws, n);
+            const uint32_t b[4] = {x.x, x.y, x.z, x.w};
+            hist_piece<ELEM, MERGE>(sink, &hr, b, 0u, n, shift);
+        }
+    }
+    hist_flush(sink, &hr);
+    hist_lds_publish(hist_lds, out, wbase, wbins);
+}
+
+template <class Job>
+static hipError_t boxes_histogram_init(const Job* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ngroups, uint32_t nbins, hipStream_t stream)
+{
+    if (njobs == 0 || ngroups < njobs || nbins == 0 || nbins > 65536u) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(boxes_histogram_init_kernel<Job>, dim3(ngroups), dim3(256), 0, stream, d_jobs, d_first_tile, njobs, nbins);
+    return hipGetLastError();
+}
+hipError_t launch_boxes_histogram_init(const Bitswap1BoxJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ngroups, uint32_t nbins, hipStream_t stream)
+{
+    return boxes_histogram_init(d_jobs, d_first_tile, njobs, ngroups, nbins, stream);
+}
+hipError_t launch_boxes_histogram_init(const BatchWindowJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ngroups, uint32_t nbins, hipStream_t stream)
+{
+    return boxes_histogram_init(d_jobs, d_first_tile, njobs, ngroups, nbins, stream);
+}
+
+hipError_t launch_bitswap1_decode_range_windows_histogram(const uint8_t* in, const Bitswap1BoxJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ngroups,
+                                                          int elem_size, const uint16_t* lut, uint32_t shift, int merge, hipStream_t stream)
+{
+    if (njobs == 0 || ngroups < njobs || (elem_size != 1 && elem_size != 2) || (lut && elem_size != 1)) return hipErrorInvalidValue;
+    const uint32_t range_bits = (lut || elem_size == 2) ? 16u : 8u;   // of a COUNTED voxel
+    if (shift >= range_bits) return hipErrorInvalidValue;
+    const dim3 grid(ngroups);
+    const size_t lds = (size_t)hist_window_bins((1u << range_bits) >> shift) * sizeof(uint32_t);
+#define SQY_HIST_LAUNCH(E, L)                                                                                                                                   \
+    do {                                                                                                                                                        \
+        if (merge == 1) hipLaunchKernelGGL((bitswap1_decode_range_windows_histogram_kernel<E, L, 1>), grid, dim3(256), lds, stream, in, d_jobs, d_first_tile, njobs, lut, shift); \
+        else if (merge == 2) hipLaunchKernelGGL((bitswap1_decode_range_windows_histogram_kernel<E, L, 2>), grid, dim3(256), lds, stream, in, d_jobs, d_first_tile, njobs, lut, shift); \
+        else hipLaunchKernelGGL((bitswap1_decode_range_windows_histogram_kernel<E, L, 0>), grid, dim3(256), lds, stream, in, d_jobs, d_first_tile, njobs, lut, shift);     \
+    } while (0)
+    if (elem_size == 2) SQY_HIST_LAUNCH(2, false);
+    else if (lut) SQY_HIST_LAUNCH(1, true);
+    else SQY_HIST_LAUNCH(1, false);
+#undef SQY_HIST_LAUNCH
+    return hipGetLastError();
+}
+
+hipError_t launch_boxes_window_histogram(const BatchWindowJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ngroups, int elem_size, uint32_t shift,
+                                         int merge, hipStream_t stream)
+{
+    if (njobs == 0 || ngroups < njobs || (elem_size != 1 && elem_size != 2) || shift >= 8u * (uint32_t)elem_size) return hipErrorInvalidValue;
+    const dim3 grid(ngroups);
+    const size_t lds = (size_t)hist_window_bins((elem_size == 2 ? 65536u : 256u) >> shift) * sizeof(uint32_t);
+#define SQY_HIST_LAUNCH(E)                                                                                                                        \
+    do {                                                                                                                                          \
+        if (merge == 1) hipLaunchKernelGGL((boxes_window_histogram_kernel<E, 1>), grid, dim3(256), lds, stream, d_jobs, d_first_tile, njobs, shift);      \
+        else if (merge == 2) hipLaunchKernelGGL((boxes_window_histogram_kernel<E, 2>), grid, dim3(256), lds, stream, d_jobs, d_first_tile, njobs, shift); \
+        else hipLaunchKernelGGL((boxes_window_histogram_kernel<E, 0>), grid, dim3(256), lds, stream, d_jobs, d_first_tile, njobs, shift);                 \
+    } while (0)
+    if (elem_size == 2) SQY_HIST_LAUNCH(2);
+    else SQY_HIST_LAUNCH(1);
+#undef SQY_HIST_LAUNCH
+    return hipGetLastError();
+}
+
 // ---- the update of a window (SQYAMD_Update_BatchWindow_*) ----------------------------------------------------------------------------------
 // window_scatter16's mirror image: the n voxels (n <= 16 / ELEM) at offset p of the thread's run, packed as they lie in a dense copy; those
 // inside the window come from the view, the others are zero.  Pieces come in ascending p.

@@ -1013,6 +1013,26 @@ BinPlan bin_boxes_plan(const uint64_t C[3], const uint64_t bins[3], uint64_t X, 
     return p;
 }
 
+BoxPath histogram_boxes_path(bool subset_form, RangeForm form, bool option_on)
+{
+    if (!subset_form || !option_on) return BoxPath::whole_copy;
+    switch (form) {
+    case RangeForm::planes:
+    case RangeForm::planes_lut: return BoxPath::subset_transposer;
+    case RangeForm::plain:
+    case RangeForm::shuffle: return BoxPath::subset_copy;
+    }
+    return BoxPath::whole_copy;
+}
+
+bool admit_histogram(const std::vector<uint64_t>& header_shape, const long* origin, const long* extent, unsigned rank, int shift, int elem_size, const void* out,
+                     BatchWindow* w)
+{
+    if (!w || !admit_window(header_shape, origin, extent, rank, w)) return false;
+    if (histogram_bins(elem_size, shift) == 0) return false;
+    return out && reinterpret_cast<uintptr_t>(out) % 4u == 0;
+}
+
 // ---- a box written into one large blob (SQYAMD_Update_Box_*) ----
 UpdateBoxPath update_box_path(const UpdateBoxFacts& f)
 {

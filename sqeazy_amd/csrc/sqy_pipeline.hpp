@@ -585,6 +585,23 @@ bool admit_binning(const std::vector<uint64_t>& header_shape, const long* origin
 // where a row fits (as many as the budget takes, but no more than keep the block's footprint near cap_voxels voxels: small blocks fill
 // the device), else ONE cell row cut into strips of budget_cells columns.  blocks = C[0] nbands nstrips.
 BinPlan bin_boxes_plan(const uint64_t C[3], const uint64_t bins[3], uint64_t X, uint64_t budget_cells = kBinBlockCells, uint64_t cap_voxels = kBinBlockVoxels);
+// The intensity histograms of many boxes of one blob (SQYAMD_Histogram_Boxes_*).  option_on: histogram_boxes_subset; the rest as for
+// project_boxes_path.  One job per box; on every path ONE launch that zeroes all histograms, then ONE counting launch that adds into them:
+//   subset_transposer  planes, planes_lut: the LZ4 frames of all boxes' z-ranges united, then the counting job-table range transposer --
+//                      a workgroup-private histogram (or a voted window of it) in LDS, flushed with no-return global atomics
+//   subset_copy        plain, shuffle: .. then ONE window histogram with a job per box in the compaction
+//   whole_copy         every other blob, and every blob with the option off: decoded whole ONCE, the same window histogram
+BoxPath histogram_boxes_path(bool subset_form, RangeForm form, bool option_on);
+// The admission of one box's histogram, stated once (SQYAMD_Histogram_Boxes_*).  The box as admit_window admits it; shift
+// in [0, 8 elem_size) -- voxel v falls into bin v >> shift of (256^elem_size) >> shift bins --; the histogram at `out` not NULL and on
+// the 4-byte grid.  On success the window.  A blob has fewer than 2^31 voxels, so no 32-bit counter can wrap: there is no bound on the box.
+bool admit_histogram(const std::vector<uint64_t>& header_shape, const long* origin, const long* extent, unsigned rank, int shift, int elem_size, const void* out,
+                     BatchWindow* w);
+// the bins of a histogram (0: shift or elem_size out of range)
+inline uint32_t histogram_bins(int elem_size, int shift)
+{
+    return (elem_size == 1 || elem_size == 2) && shift >= 0 && shift < 8 * elem_size ? (elem_size == 2 ? 65536u : 256u) >> shift : 0u;
+}
 
 struct Stage {
     std::string name;
