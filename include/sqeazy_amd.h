@@ -534,6 +534,41 @@ SQY_FUNCTION_PREFIX int SQYAMD_Bin_Boxes_UI16(const char* src, long srclength, l
                                               const long* bins, int op, char* out, long out_capacity);
 SQY_FUNCTION_PREFIX int SQYAMD_Bin_Boxes_UI8(const char* src, long srclength, long count, const long* origins, const long* extents, unsigned rank,
                                              const long* bins, int op, char* out, long out_capacity);
+/* A whole resolution pyramid of the same boxes in one call: SQYAMD_Bin_Boxes_* at `levels` sets of bins -- a viewer's multiscale overview,
+ * the pyramid levels of a chunked store, crops at 1x / 2x / 4x --, the header fetched, the frames indexed and the LZ4 frames of the boxes'
+ * z-ranges decoded ONCE for all levels.  Boxes, rank, device, stream and thread rules are SQYAMD_Bin_Boxes_*'s.  levels: 1 to
+ * SQYAMD_PYRAMID_MAX_LEVELS; bins: levels x rank longs, row l for level l, the same for every box; op is one of SQYAMD_PROJECT_MAX, _MIN,
+ * _SUM.  Level l of box i is exactly what SQYAMD_Bin_Boxes_* gives for row l: uint32_t, of the box's rank, its extent in dimension d
+ * ceil(extent[d] / min(bins[l][d], extent[d])); it lies at d_outs[i levels + l] (4-byte aligned) with the pitches out_strides +
+ * (i levels + l) rank in ELEMENTS under SQYAMD_Bin_Boxes_*'s rules (NULL: every output dense).  The levels must NEST: bins[l + 1][d] is
+ * a whole multiple of bins[l][d] for every d, on the values as given (a multiple of 1, a repeated level, is allowed).  Cells begin at the
+ * box's origin, so a cell of level l + 1 is the union of whole cells of level l -- partial cells at the far edge and bins beyond the
+ * extent included -- and max, min and sum of it are those of their results: every level is exact.  Every element of every output is
+ * written once and nothing else.
+ * Checked before a byte is written (else 1, every output untouched): what SQYAMD_Bin_Boxes_* checks, for every level of every box;
+ * levels out of range; a row that is no multiple of the row before; a NULL or misaligned output or the stride rules, for every output;
+ * more workgroups than one launch takes; and SQYAMD_PROJECT_SUM where a cell of the coarsest level might not fit (V of that level: 16-bit
+ * voxels at V > 65536, 8-bit voxels at 255 V >= 2^32).  Whatever needs no header is checked before a device is looked for.  Damaged LZ4
+ * frames: as SQYAMD_Bin_Boxes_*.
+ * How: for `bitswap1->lz4` and `quantiser->bitswap1->lz4` ONE launch in which a workgroup owns a block of cells of the box's top fused
+ * level T -- the highest level of which a cell fits the accumulators in LDS --, walks the level-0 cell layers under it as
+ * SQYAMD_Bin_Boxes_*'s kernel walks its one, stores each and folds it LDS to LDS into level 1, a completed layer of level 1 into level 2,
+ * and so on: no plane word is loaded twice, no global atomic, every cell stored once.  Levels above T -- their cells span workgroups --
+ * come from ONE further small launch with a thread per cell over the stored level-T cells.  For `lz4`, `frame_shuffle->lz4` and every
+ * blob decoded whole: level 0 by SQYAMD_Bin_Boxes_*'s per-cell launch, every further level by that same small launch straight from level
+ * 0.  "pyramid_boxes_subset" = 0: every blob decoded whole once; "pyramid_boxes_fused" = 0: level 0 by SQYAMD_Bin_Boxes_*'s launch and
+ * every further level by a launch of its own from the level below -- the same outputs both. */
+#define SQYAMD_PYRAMID_MAX_LEVELS 8
+SQY_FUNCTION_PREFIX int SQYAMD_Pyramid_Boxes_UI16_Device(const void* d_src, long srclength, long count, const long* origins, const long* extents, unsigned rank,
+                                                         long levels, const long* bins, int op, void* const* d_outs, const long* out_strides, void* hip_stream);
+SQY_FUNCTION_PREFIX int SQYAMD_Pyramid_Boxes_UI8_Device(const void* d_src, long srclength, long count, const long* origins, const long* extents, unsigned rank,
+                                                        long levels, const long* bins, int op, void* const* d_outs, const long* out_strides, void* hip_stream);
+/* host-pointer variants: the blob is staged ONCE; the outputs come back dense and back to back, box by box and levels ascending within a
+ * box, as uint32_t (1 where out_capacity, in bytes, is too small) */
+SQY_FUNCTION_PREFIX int SQYAMD_Pyramid_Boxes_UI16(const char* src, long srclength, long count, const long* origins, const long* extents, unsigned rank,
+                                                  long levels, const long* bins, int op, char* out, long out_capacity);
+SQY_FUNCTION_PREFIX int SQYAMD_Pyramid_Boxes_UI8(const char* src, long srclength, long count, const long* origins, const long* extents, unsigned rank,
+                                                 long levels, const long* bins, int op, char* out, long out_capacity);
 /* The intensity distribution of the same boxes: MANY boxes of one blob counted in one call -- display range and percentiles, an Otsu or
  * background threshold per crop, saturation checks, the 65536-bin histogram a re-quantisation starts from --, the decoded voxels never
  * stored.  Boxes, rank, device, stream and thread rules are SQYAMD_Decode_Boxes_*'s (ranks 1 to 3, frames the first dimension).  Voxel v
@@ -756,6 +791,11 @@ SQY_FUNCTION_PREFIX void SQYAMD_Release_Workspace(void);
  *   "bin_boxes_subset"                1 [SQY_NO_BIN_BOXES_SUBSET=1 -> 0]  SQYAMD_Bin_Boxes_*: only the LZ4 frames the boxes' z-ranges need, the binning
  *                                     kernel (a workgroup per block of cells, LDS accumulators) or one per-cell launch in the compaction, where the
  *                                     pipeline allows (0: every blob decoded whole once and one per-cell launch -- same outputs)
+ *   "pyramid_boxes_subset"            1 [SQY_NO_PYRAMID_BOXES_SUBSET=1 -> 0]  SQYAMD_Pyramid_Boxes_*: only the LZ4 frames the boxes' z-ranges need, decoded
+ *                                     once for all levels, where the pipeline allows (0: every blob decoded whole once -- same outputs)
+ *   "pyramid_boxes_fused"             1 [SQY_NO_PYRAMID_BOXES_FUSED=1 -> 0]  SQYAMD_Pyramid_Boxes_*: all fused levels from one pass over the planes and ONE
+ *                                     small launch for the rest (0: level 0 by SQYAMD_Bin_Boxes_*'s launch, every further level by a launch of its
+ *                                     own from the level below -- same outputs; the in-call baseline)
  *   "histogram_boxes_subset"          1 [SQY_NO_HISTOGRAM_BOXES_SUBSET=1 -> 0]  SQYAMD_Histogram_Boxes_*: only the LZ4 frames the boxes' z-ranges need,
  *                                     the counting range transposer or one window histogram in the compaction, where the pipeline allows (0: every
  *                                     blob decoded whole once and one window histogram -- same histograms)

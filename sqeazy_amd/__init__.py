@@ -44,6 +44,7 @@ EXPORTED_SYMBOLS = (
     "SQYAMD_Compare_Boxes_UI16_Device", "SQYAMD_Compare_Boxes_UI8_Device", "SQYAMD_Compare_Boxes_UI16", "SQYAMD_Compare_Boxes_UI8",
     "SQYAMD_Project_Boxes_UI16_Device", "SQYAMD_Project_Boxes_UI8_Device", "SQYAMD_Project_Boxes_UI16", "SQYAMD_Project_Boxes_UI8",
     "SQYAMD_Bin_Boxes_UI16_Device", "SQYAMD_Bin_Boxes_UI8_Device", "SQYAMD_Bin_Boxes_UI16", "SQYAMD_Bin_Boxes_UI8",
+    "SQYAMD_Pyramid_Boxes_UI16_Device", "SQYAMD_Pyramid_Boxes_UI8_Device", "SQYAMD_Pyramid_Boxes_UI16", "SQYAMD_Pyramid_Boxes_UI8",
     "SQYAMD_Histogram_Boxes_UI16_Device", "SQYAMD_Histogram_Boxes_UI8_Device", "SQYAMD_Histogram_Boxes_UI16", "SQYAMD_Histogram_Boxes_UI8",
     "SQYAMD_Decode_Slabs_UI16_Device", "SQYAMD_Decode_Slabs_UI8_Device", "SQYAMD_Decode_Slabs_UI16", "SQYAMD_Decode_Slabs_UI8",
     "SQYAMD_Decode_Batch_UI16_Device", "SQYAMD_Decode_Batch_UI8_Device", "SQYAMD_Decode_Batch_UI16", "SQYAMD_Decode_Batch_UI8",
@@ -168,6 +169,12 @@ def lib():
         for f in ("SQYAMD_Bin_Boxes_UI8", "SQYAMD_Bin_Boxes_UI16"):
             getattr(L, f).argtypes = [ctypes.c_void_p, ctypes.c_long, ctypes.c_long, c_long_p, c_long_p, ctypes.c_uint, c_long_p, ctypes.c_int, ctypes.c_void_p,
                                       ctypes.c_long]
+        for f in ("SQYAMD_Pyramid_Boxes_UI8_Device", "SQYAMD_Pyramid_Boxes_UI16_Device"):
+            getattr(L, f).argtypes = [ctypes.c_void_p, ctypes.c_long, ctypes.c_long, c_long_p, c_long_p, ctypes.c_uint, ctypes.c_long, c_long_p, ctypes.c_int,
+                                      ctypes.POINTER(ctypes.c_void_p), c_long_p, ctypes.c_void_p]
+        for f in ("SQYAMD_Pyramid_Boxes_UI8", "SQYAMD_Pyramid_Boxes_UI16"):
+            getattr(L, f).argtypes = [ctypes.c_void_p, ctypes.c_long, ctypes.c_long, c_long_p, c_long_p, ctypes.c_uint, ctypes.c_long, c_long_p, ctypes.c_int,
+                                      ctypes.c_void_p, ctypes.c_long]
         for f in ("SQYAMD_Histogram_Boxes_UI8_Device", "SQYAMD_Histogram_Boxes_UI16_Device"):
             getattr(L, f).argtypes = [ctypes.c_void_p, ctypes.c_long, ctypes.c_long, c_long_p, c_long_p, ctypes.c_uint, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p),
                                       ctypes.c_void_p]
@@ -871,6 +878,52 @@ def histogram_quantile(hist, q, shift=0):
         raise ValueError("empty histogram")
     rank = max(1, int(np.ceil(q * total)))
     return int(np.searchsorted(cum, rank, side="left")) << int(shift)
+
+
+def pyramid_boxes_device(d_src, srclength, origins, extents, bins_per_level, op, d_outs, out_strides, dtype, stream=None, count=None, levels=None):
+    """SQYAMD_Pyramid_Boxes_*_Device on raw device pointers (ints): bin_boxes_device at every row of bins_per_level (one row of bins per
+    level, the rows nesting) with one call.  d_outs[i][l] is the uint32 output of level l of box i, out_strides[i][l] its pitches in
+    elements (None: every output dense).  count: the number of boxes, levels: the number of rows (defaults: as given).  Returns rc."""
+    n = len(extents) if extents is not None else len(origins or ())
+    first = (extents or origins or [()])[0] if n else ()
+    nlev = len(bins_per_level) if bins_per_level is not None else 0
+    flat = None if d_outs is None else [p for row in d_outs for p in row]
+    ptrs = None if flat is None else (ctypes.c_void_p * max(len(flat), 1))(*[None if p is None else int(p) for p in flat])
+    return getattr(lib(), "SQYAMD_Pyramid_Boxes_%s_Device" % _suffix(dtype))(
+        ctypes.c_void_p(None if d_src is None else int(d_src)), ctypes.c_long(int(srclength)), ctypes.c_long(n if count is None else int(count)), _long_rows(origins),
+        _long_rows(extents), ctypes.c_uint(len(first)), ctypes.c_long(nlev if levels is None else int(levels)), None if not nlev else _long_rows(bins_per_level),
+        ctypes.c_int(_project_op(op)), ptrs, None if out_strides is None else _long_rows([s for row in out_strides for s in row]), ctypes.c_void_p(stream or 0))
+
+
+def pyramid_boxes(blob, origins, extents, bins_per_level, op="max"):
+    """SQYAMD_Pyramid_Boxes_UI8/UI16: the boxes [origins[i], origins[i] + extents[i]) of the blob's volume read at every resolution of
+    bins_per_level (rows of bins, each a whole multiple of the row before per dimension) with one call; op as for bin_boxes, "mean" the
+    sum divided by each cell's actual voxel count in float64.  Returns (rc, [[level arrays] per box] or None)."""
+    blob = bytes(blob)
+    size = decompressed_sizeof(blob)
+    if size not in (1, 2) or not decompressed_shape(blob) or len(origins) != len(extents) or not len(extents):
+        return 1, None
+    mean = op == "mean"
+    code = PROJECT_SUM if mean else _project_op(op)
+    dtype = np.uint16 if size == 2 else np.uint8
+    rank = len(extents[0])
+    if not bins_per_level or any(len(row) != rank or any(int(b) < 1 for b in row) for row in bins_per_level):
+        return 1, None
+    shapes = [bin_shape(ext, row) for ext in extents for row in bins_per_level]
+    counts = [int(np.prod(sh, dtype=np.int64)) for sh in shapes]
+    out = np.empty(sum(counts), dtype=np.uint32)
+    src = np.frombuffer(blob, dtype=np.uint8)
+    rc = getattr(lib(), "SQYAMD_Pyramid_Boxes_" + _suffix(dtype))(src.ctypes.data, ctypes.c_long(len(blob)), ctypes.c_long(len(extents)), _long_rows(origins),
+                                                                  _long_rows(extents), ctypes.c_uint(rank), ctypes.c_long(len(bins_per_level)),
+                                                                  _long_rows(bins_per_level), ctypes.c_int(code), out.ctypes.data, ctypes.c_long(out.nbytes))
+    if rc:
+        return rc, None
+    ends = np.cumsum(counts)
+    cells = [out[e - c:e].reshape(sh) for e, c, sh in zip(ends, counts, shapes)]
+    nlev = len(bins_per_level)
+    if mean:
+        cells = [a.astype(np.float64) / bin_counts(extents[k // nlev], bins_per_level[k % nlev]) for k, a in enumerate(cells)]
+    return 0, [cells[i * nlev:(i + 1) * nlev] for i in range(len(extents))]
 
 
 def update_batch_window_device(pipeline, d_src, offsets, lengths, origins, d_wins, shapes, strides, dtype, d_dst, slot_capacity, nthreads=0, stream=None):

@@ -465,5 +465,63 @@ SQY_VIEW_HD inline void window_histogram16(Sink& sink, const WindowGeometry& g, 
     }
 }
 
+// ---- a resolution pyramid of boxes (SQYAMD_Pyramid_Boxes_*) ----
+// Level l of a box is its binning under the bins of row l; the rows nest (sqy::admit_pyramid), so with r = bins[l] / bins[l - 1] a cell c
+// of level l is the reduction of the level-(l - 1) cells [c r, min((c + 1) r, C[l - 1])) per dimension -- partial cells at the far edge
+// and bins beyond the extent included, for C[l] = ceil(C[l - 1] / min(r, C[l - 1])).  The bit-plane kernel gives every workgroup a BLOCK
+// of cells of the top fused level T (sqy::pyramid_boxes_plan states T and the tiling): ONE level-T cell layer, a band of level-T cell
+// rows, a strip of level-T cell columns.  Below it lie, per level l <= T, q[l] cells of level l per level-T cell and dimension; the
+// block's accumulators of level l -- ONE layer of its level-l cells -- stand at off[l] in LDS.  The workgroup walks the level-0 cell
+// layers of the block one after another (the walk of a Bin_Boxes block: bin_block_footprint, bin_block_item, bin_run_cells); behind a
+// barrier it stores the layer and folds it into level 1 (pyramid_fold_cell, a thread per level-1 cell), a completed level-1 layer is
+// stored and folded into level 2, and so on.  tests/sanitize/pyramid_boxes_test.cpp holds the whole walk against a triple loop per level.
+constexpr uint32_t kPyramidMaxLevels = 8;
+constexpr uint32_t kPyramidLdsCells = 10240;            // all fused levels' accumulators of a block: 40 KiB -- level 0's 8192 and a quarter more; four workgroups fit a CU
+constexpr uint64_t kPyramidBlockVoxels = 1u << 15;      // the voxels a block is sized for where the cells allow it (DESIGN.md 5 says against what)
+
+struct PyramidPlan {
+    uint32_t levels, T;                                 // the call's levels; the top fused one
+    uint32_t off[kPyramidMaxLevels];                    // level l's accumulators in LDS (l <= T)
+    uint64_t C[kPyramidMaxLevels][3];                   // the cell grids
+    uint64_t r[kPyramidMaxLevels][3];                   // level-(l - 1) cells per level-l cell, clamped to C[l - 1] (r[0]: ones)
+    uint64_t q[kPyramidMaxLevels][3];                   // level-l cells per level-T cell, clamped to C[l] (l <= T); above T: level-T cells per level-l cell, clamped to C[T]
+    uint64_t band, strip, nbands, nstrips, blocks;      // the tiling of the level-T grid (BinPlan's fields)
+};
+SQY_VIEW_HD inline BinPlan pyramid_top_plan(const PyramidPlan& p)
+{
+    return BinPlan{{p.C[p.T][0], p.C[p.T][1], p.C[p.T][2]}, p.band, p.strip, p.nbands, p.nstrips, p.blocks};
+}
+// the level-l cells (l <= T) of dimension d under the level-T cells [c0, c0 + n)
+SQY_VIEW_HD inline void pyramid_level_span(const PyramidPlan& p, uint32_t l, int d, uint64_t c0, uint64_t n, uint64_t* first, uint64_t* count)
+{
+    const uint64_t q = p.q[l][d], f = c0 * q, rest = p.C[l][d] - f;      // (c0 q < C[l]: C[T] = ceil(C[l] / q))
+    *first = f;
+    *count = n * q < rest ? n * q : rest;
+}
+// cell (ly, lx) of a level's layer from the layer below it, ncy x ncx cells at `lo`: its children [l r, min((l + 1) r, nc)) reduced
+SQY_VIEW_HD inline uint32_t pyramid_fold_cell(const uint32_t* lo, uint64_t ncy, uint64_t ncx, uint64_t ry, uint64_t rx, uint64_t ly, uint64_t lx, uint32_t op)
+{
+    const uint64_t y0 = ly * ry, x0 = lx * rx, y1 = ncy - y0 < ry ? ncy : y0 + ry, x1 = ncx - x0 < rx ? ncx : x0 + rx;
+    uint32_t acc = project_neutral(op);
+    for (uint64_t y = y0; y < y1; ++y)
+        for (uint64_t x = x0; x < x1; ++x) acc = project_combine(op, acc, lo[y * ncx + x]);
+    return acc;
+}
+// cell (cz, cy, cx) of a level above T from the STORED cells of a finer level (grid Cs, pitches spz, spy in elements): the cells
+// [c r, min((c + 1) r, Cs)) per dimension reduced -- what a thread of pyramid_reduce_kernel computes
+SQY_VIEW_HD inline uint32_t pyramid_reduce_cell(const uint32_t* src, const uint64_t Cs[3], uint64_t spz, uint64_t spy, const uint64_t r[3], uint64_t cz, uint64_t cy,
+                                                uint64_t cx, uint32_t op)
+{
+    const uint64_t z1 = (cz + 1) * r[0] < Cs[0] ? (cz + 1) * r[0] : Cs[0], y1 = (cy + 1) * r[1] < Cs[1] ? (cy + 1) * r[1] : Cs[1];
+    const uint64_t x1 = (cx + 1) * r[2] < Cs[2] ? (cx + 1) * r[2] : Cs[2];
+    uint32_t acc = project_neutral(op);
+    for (uint64_t z = cz * r[0]; z < z1; ++z)
+        for (uint64_t y = cy * r[1]; y < y1; ++y) {
+            const uint64_t at = z * spz + y * spy;
+            for (uint64_t x = cx * r[2]; x < x1; ++x) acc = project_combine(op, acc, src[at + x]);
+        }
+    return acc;
+}
+
 } // namespace sqy
 #endif

@@ -85,6 +85,8 @@ struct Options {
     std::atomic<long> project_boxes_walk;               // projection along axis 0 on the transposer path: the z-walking form (registers, plain stores) where every box is on the 32-voxel grid (0: always the atomics -- same images)
     std::atomic<long> project_boxes_subset;             // projection of many boxes of one blob: only the LZ4 frames the boxes' z-ranges need, the projecting range transposer or one projection in the compaction, where sqy::project_boxes_path allows (0: the blob decoded whole once, one projection launch)
     std::atomic<long> bin_boxes_subset;                 // binned read of many boxes of one blob: only the LZ4 frames the boxes' z-ranges need, the binning job-table kernel (a workgroup per block of cells, LDS accumulators) or one per-cell launch in the compaction, where sqy::bin_boxes_path allows (0: the blob decoded whole once, one per-cell launch)
+    std::atomic<long> pyramid_boxes_subset;             // pyramid of many boxes of one blob: only the LZ4 frames the boxes' z-ranges need, decoded once for all levels, where sqy::pyramid_boxes_path allows (0: the blob decoded whole once)
+    std::atomic<long> pyramid_boxes_fused;              // .. all fused levels from one pass over the planes, the levels above them (and every further level of the copy forms) by ONE pyramid_reduce launch (0: level 0 by Bin_Boxes' launch, every further level by a pyramid_reduce launch from the level below -- same outputs)
     std::atomic<long> histogram_boxes_subset;           // histograms of many boxes of one blob: only the LZ4 frames the boxes' z-ranges need, the counting range transposer or one window histogram in the compaction, where sqy::histogram_boxes_path allows (0: the blob decoded whole once, one window histogram)
     std::atomic<long> histogram_boxes_merge;            // how the histogram kernels add equal neighbours: 2 a piece of sixteen bytes whose bins are all equal in one LDS atomic, 1 equal consecutive voxels of a thread's whole run in one, 0 one per voxel -- same counts
     std::atomic<long> update_box_subset;                // box update of one blob: only the LZ4 frames the box's z-range needs are decoded, patched, parsed again and spliced between the old ones, where sqy::update_box_path allows (0: whole decode, one paste, the single call's encode)
@@ -116,7 +118,8 @@ struct Options {
           decode_box_subset(env_flag("SQY_NO_DECODE_BOX_SUBSET") ? 0 : 1), decode_boxes_joint(env_flag("SQY_NO_DECODE_BOXES_JOINT") ? 0 : 1),
           compare_boxes_subset(env_flag("SQY_NO_COMPARE_BOXES_SUBSET") ? 0 : 1),
           project_boxes_walk(env_flag("SQY_NO_PROJECT_BOXES_WALK") ? 0 : 1), project_boxes_subset(env_flag("SQY_NO_PROJECT_BOXES_SUBSET") ? 0 : 1),
-          bin_boxes_subset(env_flag("SQY_NO_BIN_BOXES_SUBSET") ? 0 : 1), histogram_boxes_subset(env_flag("SQY_NO_HISTOGRAM_BOXES_SUBSET") ? 0 : 1),
+          bin_boxes_subset(env_flag("SQY_NO_BIN_BOXES_SUBSET") ? 0 : 1), pyramid_boxes_subset(env_flag("SQY_NO_PYRAMID_BOXES_SUBSET") ? 0 : 1),
+          pyramid_boxes_fused(env_flag("SQY_NO_PYRAMID_BOXES_FUSED") ? 0 : 1), histogram_boxes_subset(env_flag("SQY_NO_HISTOGRAM_BOXES_SUBSET") ? 0 : 1),
           histogram_boxes_merge(env_flag("SQY_NO_HISTOGRAM_BOXES_MERGE") ? 0 : 2), update_box_subset(env_flag("SQY_NO_UPDATE_BOX_SUBSET") ? 0 : 1),
           update_boxes_subset(env_flag("SQY_NO_UPDATE_BOXES_SUBSET") ? 0 : 1),
           decode_slabs_joint(env_flag("SQY_NO_DECODE_SLABS_JOINT") ? 0 : 1), decode_batch_joint(env_flag("SQY_NO_DECODE_BATCH_JOINT") ? 0 : 1),
@@ -147,6 +150,8 @@ struct Options {
         if (!std::strcmp(name, "project_boxes_subset")) return &project_boxes_subset;
         if (!std::strcmp(name, "project_boxes_walk")) return &project_boxes_walk;
         if (!std::strcmp(name, "bin_boxes_subset")) return &bin_boxes_subset;
+        if (!std::strcmp(name, "pyramid_boxes_subset")) return &pyramid_boxes_subset;
+        if (!std::strcmp(name, "pyramid_boxes_fused")) return &pyramid_boxes_fused;
         if (!std::strcmp(name, "histogram_boxes_subset")) return &histogram_boxes_subset;
         if (!std::strcmp(name, "histogram_boxes_merge")) return &histogram_boxes_merge;
         if (!std::strcmp(name, "update_box_subset")) return &update_box_subset;
@@ -365,6 +370,7 @@ struct Workspace {
     DevBuf box_window;        // box decode: the job and tile table of the window copy (one job)
     DevBuf update_box;        // box update, the whole path: the single call's new blob before it is held against the caller's capacity and copied out
     DevBuf boxes_jobs;        // decode of many boxes of one blob: the job and tile table of its one output launch
+    DevBuf pyramid_jobs[sqy::kPyramidMaxLevels];      // pyramid of many boxes of one blob: the job and tile tables of its pyramid_reduce launches (the first launch's are in boxes_jobs)
     DevBuf slabs_index;       // slab-set decode: every blob's frame ranking (scratch, block index, counts) of a group
     DevBuf slabs_joint;       // .. the group's joint block index, frame output table, part descriptors and frame_shuffle maps
     DevBuf slabs_out;         // .. the group's LZ4 output (when it does not go straight to the volume)
@@ -389,7 +395,7 @@ struct Workspace {
     {
         ping.release(); pong.release(); lz4_scratch.release(); csize.release(); frame_off.release();
         io_src.release(); io_dst.release(); small.release(); plan.release(); dedupe.release(); diff_side.release(); spec.release(); digest.release(); bkrd.release();
-        subset.release(); range_full.release(); box_window.release(); update_box.release(); boxes_jobs.release(); slabs_index.release(); slabs_joint.release(); slabs_out.release(); slabs_host.release();
+        subset.release(); range_full.release(); box_window.release(); update_box.release(); boxes_jobs.release(); for (DevBuf& b : pyramid_jobs) b.release(); slabs_index.release(); slabs_joint.release(); slabs_out.release(); slabs_host.release();
         batch_stream.release(); batch_scratch.release(); batch_tables.release(); batch_quant.release(); batch_host.release();
         batch_pack.release(); batch_pack_one.release(); for (DevBuf& b : batch_views) b.release(); for (DevBuf& b : batch_windows) b.release();
         for (DevBuf& b : batch_compares) b.release();
@@ -4353,6 +4359,234 @@ int bin_boxes_from_host(const char* src, long srclength, long count, const long*
     });
 }
 
+// ---- a whole resolution pyramid of many boxes of one large blob (SQYAMD_Pyramid_Boxes_*) ------------------------------------
+// bin_boxes_on_device with a table of bins: ONE header fetch, ONE frame index, the LZ4 frames of all boxes' z-ranges united and decoded
+// ONCE for all levels; sqy::pyramid_boxes_path says what runs, sqy::admit_pyramid what is admitted and sqy::pyramid_boxes_plan which
+// levels the bit-plane kernel fuses and how its workgroups share a box's cells.  No neutral-element launch, no global atomics.  Nothing
+// but the outputs' cells is written outside the workspace.
+static_assert(sizeof(sqy::Bitswap1BoxPyramidJob) == sqy::kBitswap1BoxPyramidJobBytes && sizeof(sqy::PyramidReduceJob) == sqy::kPyramidReduceJobBytes,
+              "the pyramid jobs' layout");
+
+// a pyramid_reduce launch's jobs: level `to` of a box out of its stored level `from`
+struct ReduceLaunch : TiledJobs<sqy::PyramidReduceJob> {
+    void add(const sqy::Pyramid& y, void* const* outs, uint32_t from, uint32_t to, int op)
+    {
+        const sqy::Binning& s = y.q[from];
+        const sqy::Binning& d = y.q[to];
+        sqy::PyramidReduceJob j{};
+        j.src = outs[from];
+        j.out = outs[to];
+        for (int k = 0; k < 3; ++k) {
+            j.Cs[k] = s.C[k];
+            j.C[k] = d.C[k];
+            j.r[k] = std::min(y.raw[to][k] / y.raw[from][k], s.C[k]);     // (the rows nest: a whole ratio; clamped, the same cells)
+        }
+        j.spz = s.pz; j.spy = s.py; j.pz = d.pz; j.py = d.py;
+        j.op = (uint32_t)op;
+        jobs.push_back(j);
+        first_tile.push_back(ntiles);
+        ntiles += (uint32_t)((d.C[0] * d.C[1] * d.C[2] + 255) / 256);
+    }
+};
+int launch_pyramid_reduce_jobs(Context& cx, hipStream_t stream, ReduceLaunch& l, DevBuf& buf)
+{
+    if (l.jobs.empty()) return 0;
+    std::vector<PendingEvent>* pend = &cx.pending;
+    const uint32_t* d_tiles = nullptr;
+    if (l.upload(stream, buf, &d_tiles)) return 1;
+    SQY_TIMED("pyramid_reduce", sqy::launch_pyramid_reduce(static_cast<const sqy::PyramidReduceJob*>(buf.p), d_tiles, (uint32_t)l.jobs.size(), l.ntiles, stream));
+    return 0;
+}
+
+// everything behind level 0 where no kernel fuses it: with `fused` ONE launch that takes every further level straight from level 0, else
+// a launch per level from the level below
+int pyramid_tail_from_level0(Context& cx, hipStream_t stream, ReduceLaunch (&rl)[sqy::kPyramidMaxLevels], const std::vector<sqy::Pyramid>& ys, void* const* outs, long levels,
+                             int op, bool fused)
+{
+    for (long l = 1; l < levels; ++l) {
+        ReduceLaunch& r = rl[fused ? 0 : l - 1];
+        for (size_t i = 0; i < ys.size(); ++i) r.add(ys[i], outs + i * (size_t)levels, fused ? 0u : (uint32_t)(l - 1), (uint32_t)l, op);
+    }
+    for (long l = 0; l + 1 < levels; ++l)
+        if (launch_pyramid_reduce_jobs(cx, stream, rl[l], cx.ws.pyramid_jobs[l])) return 1;
+    return 0;
+}
+
+// the launches behind DecodeCall::frames_subset: box i (ws[i], ys[i]) of the united frames in c.range_buf into its outputs outs + i levels
+int boxes_range_pyramid(DecodeCall& c, BinLaunch& l, TiledJobs<sqy::Bitswap1BoxBinJob>& tj, TiledJobs<sqy::Bitswap1BoxPyramidJob>& pj,
+                        ReduceLaunch (&rl)[sqy::kPyramidMaxLevels], const std::vector<sqy::BatchWindow>& ws, const std::vector<sqy::Pyramid>& ys, void* const* outs,
+                        unsigned rank, long levels, int op, bool fused)
+{
+    hipStream_t stream = c.stream;
+    std::vector<PendingEvent>* pend = c.pend;
+    const sqy::FrameRangesPlan& p = c.ranges_plan;
+    const size_t count = ws.size();
+    if (p.boxes.size() != count) return 1;
+    std::vector<void*> level0(count);
+    std::vector<sqy::Binning> q0(count);
+    for (size_t i = 0; i < count; ++i) { level0[i] = outs[i * (size_t)levels]; q0[i] = ys[i].q[0]; }
+    const sqy::PyramidPath path = sqy::pyramid_boxes_path(true, c.range_form, true, fused);
+    if (path.path != sqy::BoxPath::subset_transposer || !path.fused) {
+        // level 0 is Bin_Boxes' launch of the path, the rest pyramid_reduce's
+        if (const int rc = boxes_range_bin(c, l, tj, ws, q0, level0.data(), rank, op)) return rc;
+        return pyramid_tail_from_level0(c.cx, stream, rl, ys, outs, levels, op, path.fused);
+    }
+    const uint16_t* lut = nullptr;
+    if (c.range_lut(&lut)) return 1;
+    for (size_t i = 0; i < count; ++i) {
+        const sqy::BatchWindow& w = ws[i];
+        const sqy::Pyramid& y = ys[i];
+        const sqy::FrameRangesBox& b = p.boxes[i];
+        sqy::Bitswap1BoxPyramidJob j{};
+        for (long k = 0; k < levels; ++k) { j.out[k] = outs[i * (size_t)levels + (size_t)k]; j.pz[k] = y.q[k].pz; j.py[k] = y.q[k].py; }
+        j.g = sqy::WindowGeometry{w.bY, w.bX, w.oz, w.oy, w.ox, w.Z, w.Y, w.X, y.q[0].pz, y.q[0].py};
+        std::copy(b.plane, b.plane + 16, j.r.plane);
+        j.r.tail = b.tail; j.r.w0 = b.w0; j.r.w1 = b.w1; j.r.v0 = b.v0; j.r.v1 = b.v1; j.r.L = b.L;
+        j.t0 = sqy::range_first_thread(b.w0, 128u / (8u * (uint32_t)p.we));
+        std::copy(y.q[0].bins, y.q[0].bins + 3, j.bins);
+        const uint64_t E[3] = {w.Z, w.Y, w.X};
+        j.plan = sqy::pyramid_boxes_plan(y, E);
+        j.op = (uint32_t)op;
+        j.zreg = (w.bY * w.bX) % 32 == 0 ? 1u : 0u;
+        if (!sqy::bitswap1_box_pyramid_job_ok(j) || (uint64_t)pj.ntiles + j.plan.blocks > 0x7fffffffull) return 1;
+        pj.jobs.push_back(j);
+        pj.first_tile.push_back(pj.ntiles);
+        pj.ntiles += (uint32_t)j.plan.blocks;
+        for (uint32_t k = j.plan.T + 1; k < (uint32_t)levels; ++k) rl[0].add(y, outs + i * (size_t)levels, j.plan.T, k, op);      // the levels above T: from the stored level T
+    }
+    const uint32_t* d_tiles = nullptr;
+    if (pj.upload(stream, c.cx.ws.boxes_jobs, &d_tiles)) return 1;
+    SQY_TIMED(lut ? "bitswap1_quantiser_pyramid_boxes" : "bitswap1_pyramid_boxes",
+              sqy::launch_bitswap1_decode_range_windows_pyramid(c.range_buf, static_cast<const sqy::Bitswap1BoxPyramidJob*>(c.cx.ws.boxes_jobs.p), d_tiles, (uint32_t)count,
+                                                                pj.ntiles, p.we, lut, stream));
+    return launch_pyramid_reduce_jobs(c.cx, stream, rl[0], c.cx.ws.pyramid_jobs[0]);
+}
+
+// Level l of box i = [origins + i rank, .. + extents + i rank) into d_outs[i levels + l] (out_strides + (i levels + l) rank, or dense).
+// sqy::admit_pyramid for every box, the launches' sizes with it -- all before anything is written
+int pyramid_boxes_on_device(Context& cx, const void* d_src_v, uint64_t srclen, size_t count, const long* origins, const long* extents, unsigned rank, long levels,
+                            const long* bins, int op, void* const* d_outs, const long* out_strides, int want_elem, hipStream_t stream)
+{
+    const uint8_t* d_src = static_cast<const uint8_t*>(d_src_v);
+    DrainOnExit drain{stream, &cx.pending, cx.side};
+    sqy::HeaderInfo h;
+    if (fetch_header(d_src, srclen, stream, h)) return 1;
+    uint64_t raw_bytes = 0;
+    if (!admit_blob(h, srclen, want_elem, &raw_bytes)) return 1;
+    std::vector<sqy::BatchWindow> ws(count);
+    std::vector<sqy::Pyramid> ys(count);
+    std::vector<std::pair<uint64_t, uint64_t>> ranges(count);
+    sqy::PyramidSizes sizes;
+    for (size_t i = 0; i < count; ++i) {
+        const long* o = origins + i * rank;
+        const long* e = extents + i * rank;
+        if (!sqy::admit_pyramid(h.shape, o, e, rank, levels, bins, op, want_elem == 2 ? 65535u : 255u, d_outs + i * (size_t)levels,
+                                out_strides ? out_strides + i * (size_t)levels * rank : nullptr, &ws[i], &ys[i], &sizes)) {
+            std::fprintf(stderr, "[sqeazy]\t pyramid boxes: box %zu does not lie inside the blob's shape or has another rank, a cell's sum might not fit 32 bits, or the "
+                                 "call takes too many workgroups for one launch\n", i);
+            return 1;
+        }
+        ranges[i] = {(uint64_t)o[0], (uint64_t)e[0]};
+    }
+    const bool fused = g_opt.pyramid_boxes_fused.load() != 0;
+    BinLaunch l;                                                        // (all wait for the stream before their tables go)
+    TiledJobs<sqy::Bitswap1BoxBinJob> tj;
+    TiledJobs<sqy::Bitswap1BoxPyramidJob> pj;
+    ReduceLaunch rl[sqy::kPyramidMaxLevels];
+    if (g_opt.pyramid_boxes_subset.load()) {
+        DecodeCall c(cx, stream, nullptr, h, Pipeline::from_string(h.pipename), raw_bytes / (uint64_t)want_elem, d_src + h.size);
+        bool taken = false;
+        if (const int rc = c.frames_subset(ranges, false, &taken)) return rc;
+        if (taken) {
+            if (const int rc = boxes_range_pyramid(c, l, tj, pj, rl, ws, ys, d_outs, rank, levels, op, fused)) return rc;
+            return c.finish();
+        }
+    }
+    // sqy::BoxPath::whole_copy: the whole volume ONCE, level 0 of all boxes in one launch, the rest pyramid_reduce's
+    if (cx.ws.range_full.ensure(std::max<uint64_t>(raw_bytes, 16))) return 1;
+    if (const int rc = decode_on_device(cx, d_src_v, srclen, cx.ws.range_full.p, raw_bytes, want_elem, stream)) return rc;
+    for (size_t i = 0; i < count; ++i) l.add(d_outs[i * (size_t)levels], cx.ws.range_full.p, ws[i], ys[i].q[0], op);
+    if (launch_boxes_bin(cx, stream, l, want_elem)) return 1;
+    if (pyramid_tail_from_level0(cx, stream, rl, ys, d_outs, levels, op, fused)) return 1;
+    SQY_HIP(hipStreamSynchronize(stream));
+    if (g_prof_on.load()) prof_collect(cx.pending);
+    return 0;
+}
+
+// what SQYAMD_Pyramid_Boxes_* checks without a header, before a device is looked for: boxes_arguments_ok, and sqy::admit_pyramid of every
+// box against the smallest shape that holds it -- the levels, the nesting, the op, every output's pointer and pitches, the sum bound
+bool pyramid_arguments_ok(const void* src, long srclength, long count, const long* origins, const long* extents, unsigned rank, long levels, const long* bins, int op,
+                          void* const* outs, const long* out_strides, int elem_size)
+{
+    if (!bins || levels < 1 || levels > (long)sqy::kPyramidMaxLevels || !boxes_arguments_ok(src, srclength, count, origins, nullptr, extents, rank)) return false;
+    for (long i = 0; i < count; ++i) {
+        const long* o = origins + (size_t)i * rank;
+        const long* e = extents + (size_t)i * rank;
+        std::vector<uint64_t> shape(rank);
+        for (unsigned k = 0; k < rank; ++k) shape[k] = (uint64_t)o[k] + (uint64_t)std::max(e[k], 0l);     // (both below 2^63: no wrap)
+        sqy::BatchWindow w;
+        sqy::Pyramid y;
+        const void* own[sqy::kPyramidMaxLevels];                                                           // (host variant: the outputs are the library's)
+        for (long l = 0; l < levels; ++l) own[l] = outs ? outs[(size_t)i * (size_t)levels + (size_t)l] : static_cast<const void*>(&w);
+        if (!sqy::admit_pyramid(shape, o, e, rank, levels, bins, op, elem_size == 2 ? 65535u : 255u, own,
+                                outs && out_strides ? out_strides + (size_t)i * (size_t)levels * rank : nullptr, &w, &y))
+            return false;
+    }
+    return true;
+}
+
+int pyramid_boxes_device(const void* d_src, long srclength, long count, const long* origins, const long* extents, unsigned rank, long levels, const long* bins, int op,
+                         void* const* d_outs, const long* out_strides, int elem_size, void* hip_stream)
+{
+    if (!d_outs || !pyramid_arguments_ok(d_src, srclength, count, origins, extents, rank, levels, bins, op, d_outs, out_strides, elem_size)) {
+        std::fprintf(stderr, "[sqeazy]\t pyramid boxes: bad arguments\n");
+        return 1;
+    }
+    ContextLease lease;
+    if (!lease.ctx) { std::fprintf(stderr, "[sqeazy]\t no usable HIP device\n"); return 1; }
+    return pyramid_boxes_on_device(*lease.ctx, d_src, (uint64_t)srclength, (size_t)count, origins, extents, rank, levels, bins, op, d_outs, out_strides, elem_size,
+                                   static_cast<hipStream_t>(hip_stream));
+}
+
+// host pointers: the header and every box are checked here, before anything is staged; the outputs come back dense and back to back, box
+// by box and levels ascending within a box, 32-bit elements
+int pyramid_boxes_from_host(const char* src, long srclength, long count, const long* origins, const long* extents, unsigned rank, long levels, const long* bins, int op,
+                            char* out, long out_capacity, int elem_size)
+{
+    if (!out || !pyramid_arguments_ok(src, srclength, count, origins, extents, rank, levels, bins, op, nullptr, nullptr, elem_size)) {
+        std::fprintf(stderr, "[sqeazy]\t pyramid boxes: bad arguments\n");
+        return 1;
+    }
+    const sqy::HeaderInfo h = sqy::header_unpack(src, src + srclength);
+    if (!h.valid) { std::fprintf(stderr, "[sqeazy]\t unable to find a sqy header in the blob\n"); return 1; }
+    uint64_t raw = 0;
+    if (!header_shape_ok(h, (uint64_t)srclength, &raw)) return 1;
+    if (h.elem_size() != elem_size) { std::fprintf(stderr, "[sqeazy]\t blob holds %s voxels\n", h.type.c_str()); return 1; }
+    const size_t nouts = (size_t)count * (size_t)levels;
+    std::vector<uint64_t> at(nouts + 1, 0);                             // (an output is no larger than the volume, count fits an int: no wrap)
+    for (long i = 0; i < count; ++i) {
+        sqy::BatchWindow w;
+        sqy::Pyramid y;
+        const void* own[sqy::kPyramidMaxLevels];
+        for (long l = 0; l < levels; ++l) own[l] = &w;
+        if (!sqy::admit_pyramid(h.shape, origins + (size_t)i * rank, extents + (size_t)i * rank, rank, levels, bins, op, elem_size == 2 ? 65535u : 255u, own, nullptr, &w,
+                                &y)) {
+            std::fprintf(stderr, "[sqeazy]\t pyramid boxes: box %ld does not lie inside the blob's shape, or a cell's sum might not fit 32 bits\n", i);
+            return 1;
+        }
+        for (long l = 0; l < levels; ++l) {
+            const size_t k = (size_t)i * (size_t)levels + (size_t)l;
+            at[k + 1] = at[k] + y.q[l].C[0] * y.q[l].C[1] * y.q[l].C[2] * 4u;
+        }
+    }
+    if (at.back() > (uint64_t)std::max(out_capacity, 0l)) { std::fprintf(stderr, "[sqeazy]\t pyramid boxes: buffer too small\n"); return 1; }
+    return decode_staged(src, (uint64_t)srclength, out, at.back(), [&](Context& cx, void* d_src, void* d_dst, hipStream_t stream) {
+        std::vector<void*> ptrs(nouts);
+        for (size_t k = 0; k < nouts; ++k) ptrs[k] = static_cast<uint8_t*>(d_dst) + at[k];
+        return pyramid_boxes_on_device(cx, d_src, (uint64_t)srclength, (size_t)count, origins, extents, rank, levels, bins, op, ptrs.data(), nullptr, elem_size, stream);
+    });
+}
+
 // ---- the intensity histograms of many boxes of one large blob (SQYAMD_Histogram_Boxes_*) ------------------------------------
 // compare_boxes_on_device with a count for the compare: ONE header fetch, the LZ4 frames of all boxes' z-ranges united, ONE launch that
 // zeroes every histogram over the counting launch's own tables, ONE counting launch; sqy::histogram_boxes_path says what runs and
@@ -6321,6 +6555,30 @@ int SQYAMD_Bin_Boxes_UI8(const char* src, long srclength, long count, const long
                          long out_capacity)
 {
     return guarded([&]() -> int { return bin_boxes_from_host(src, srclength, count, origins, extents, rank, bins, op, out, out_capacity, 1); });
+}
+
+int SQYAMD_Pyramid_Boxes_UI16_Device(const void* d_src, long srclength, long count, const long* origins, const long* extents, unsigned rank, long levels, const long* bins,
+                                     int op, void* const* d_outs, const long* out_strides, void* hip_stream)
+{
+    return guarded([&]() -> int { return pyramid_boxes_device(d_src, srclength, count, origins, extents, rank, levels, bins, op, d_outs, out_strides, 2, hip_stream); });
+}
+
+int SQYAMD_Pyramid_Boxes_UI8_Device(const void* d_src, long srclength, long count, const long* origins, const long* extents, unsigned rank, long levels, const long* bins,
+                                     int op, void* const* d_outs, const long* out_strides, void* hip_stream)
+{
+    return guarded([&]() -> int { return pyramid_boxes_device(d_src, srclength, count, origins, extents, rank, levels, bins, op, d_outs, out_strides, 1, hip_stream); });
+}
+
+int SQYAMD_Pyramid_Boxes_UI16(const char* src, long srclength, long count, const long* origins, const long* extents, unsigned rank, long levels, const long* bins, int op,
+                              char* out, long out_capacity)
+{
+    return guarded([&]() -> int { return pyramid_boxes_from_host(src, srclength, count, origins, extents, rank, levels, bins, op, out, out_capacity, 2); });
+}
+
+int SQYAMD_Pyramid_Boxes_UI8(const char* src, long srclength, long count, const long* origins, const long* extents, unsigned rank, long levels, const long* bins, int op,
+                              char* out, long out_capacity)
+{
+    return guarded([&]() -> int { return pyramid_boxes_from_host(src, srclength, count, origins, extents, rank, levels, bins, op, out, out_capacity, 1); });
 }
 
 int SQYAMD_Histogram_Boxes_UI16_Device(const void* d_src, long srclength, long count, const long* origins, const long* extents, unsigned rank, int shift,

@@ -546,6 +546,44 @@ struct BoxBinJob {
 };
 constexpr uint64_t kBoxBinJobBytes = 144;
 hipError_t launch_boxes_window_bin(const BoxBinJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ngroups, int elem_size, hipStream_t stream);
+// ---- a whole resolution pyramid of many boxes of one large blob (SQYAMD_Pyramid_Boxes_*) ----
+// Bitswap1BoxBinJob with an output, its pitches and a cell grid per level: job j is a box, its range, its level-0 bins (clamped) and its
+// sqy::PyramidPlan; it owns plan.blocks workgroups, d_first_tile their prefix sums.  Workgroup `own` takes the block
+// sqy::bin_block_of(pyramid_top_plan(plan), own) of level-T cells and walks the level-0 cell layers under it one after another: the
+// accumulators of the layer set to the op's neutral element, the layer's items shared by the threads exactly as in
+// launch_bitswap1_decode_range_windows_bin (the same device functions; zreg the same), behind a barrier the layer stored with plain
+// stores and folded LDS to LDS into the level-1 accumulators at plan.off[1] (a thread per level-1 cell: sqy::pyramid_fold_cell), a
+// level-1 layer that is complete stored and folded into level 2, and so on up to T.  Every cell of the levels 0 .. T is stored once; no
+// global atomic, no neutral-element launch; no plane word is loaded twice within a block.  Static LDS: sqy::kPyramidLdsCells
+// accumulators (40 KiB) and the look-up, under 64 KiB.  Every job must pass bitswap1_box_pyramid_job_ok.  Nothing but the outputs' cells is
+// written.  The levels above T are launch_pyramid_reduce's.
+struct Bitswap1BoxPyramidJob {
+    void* out[kPyramidMaxLevels];
+    uint64_t pz[kPyramidMaxLevels], py[kPyramidMaxLevels];         // level l's pitches in elements from cell layer to layer and cell row to row
+    WindowGeometry g;                                               // (sz, sy not used: the pitches stand per level)
+    Bitswap1Range r;
+    uint64_t t0;             // (Bitswap1BoxJob's field; not used)
+    uint64_t bins[3];        // level 0's, clamped to the extent
+    PyramidPlan plan;
+    uint32_t op, zreg;
+    uint64_t pad;
+};
+constexpr uint64_t kBitswap1BoxPyramidJobBytes = 1152;  // (a multiple of 16: the tile table behind the jobs stays on the 16-byte grid)
+bool bitswap1_box_pyramid_job_ok(const Bitswap1BoxPyramidJob& j);
+hipError_t launch_bitswap1_decode_range_windows_pyramid(const uint8_t* in, const Bitswap1BoxPyramidJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs,
+                                                        uint32_t ngroups, int elem_size, const uint16_t* lut, hipStream_t stream);
+// A level of a pyramid from a stored finer one: a thread per cell of `out` (grid C, pitches pz, py) reduces the cells
+// [c r, min((c + 1) r, Cs)) per dimension of `src` (grid Cs, pitches spz, spy; uint32_t both) and stores its cell once.  No atomics.  Job
+// j owns ceil(C[0] C[1] C[2] / 256) workgroups; d_first_tile their prefix sums.  `src` is written by a launch in front on the stream.
+struct PyramidReduceJob {
+    const void* src;
+    void* out;
+    uint64_t Cs[3], C[3], r[3];
+    uint64_t spz, spy, pz, py;
+    uint32_t op, pad0;
+};
+constexpr uint64_t kPyramidReduceJobBytes = 128;
+hipError_t launch_pyramid_reduce(const PyramidReduceJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ngroups, hipStream_t stream);
 // ---- the intensity histograms of many boxes of one large blob (SQYAMD_Histogram_Boxes_*) ----
 // launch_bitswap1_decode_range_windows_compare with a count where it compares: job j is a Bitswap1BoxJob whose `view` is the box's
 // histogram -- nbins = (65536 or 256) >> shift counters of uint32_t, dense; the 16-bit range behind the look-up --, the tables, the

@@ -10321,6 +10321,176 @@ hipError_t launch_boxes_window_bin(const BoxBinJob* d_jobs, const uint32_t* d_fi
     return hipGetLastError();
 }
 
+// ---- a whole resolution pyramid of many boxes of one large blob (SQYAMD_Pyramid_Boxes_*) -------------------------------------------------
+// A workgroup per block of level-T cells (sqy_kernels.h, sqy_batch_window.hpp): the level-0 cell layers under the block walked one after
+// another as bitswap1_decode_range_windows_bin_kernel walks its one, each stored and folded upwards LDS to LDS behind a barrier.  Every
+// branch around a barrier depends on the job and the block alone: all threads reach all barriers.
+template <int ELEM, bool LUT>
+__global__ __launch_bounds__(256)
+void bitswap1_decode_range_windows_pyramid_kernel(const uint8_t* __restrict__ in, const Bitswap1BoxPyramidJob* __restrict__ jobs, const uint32_t* __restrict__ first_tile,
+                                                  uint32_t njobs, const uint16_t* __restrict__ lut)
+{
+    static_assert(!LUT || ELEM == 1, "the look-up follows 8-bit planes");
+    constexpr uint32_t W = 8 * ELEM;
+    __shared__ uint16_t sl[LUT ? 256 : 1];
+    __shared__ uint32_t acc[kPyramidLdsCells];
+    if constexpr (LUT) sl[threadIdx.x] = lut[threadIdx.x];
+    const uint32_t j = batch_job_of_tile(first_tile, njobs);
+    const Bitswap1BoxPyramidJob* __restrict__ job = jobs + j;           // (uniform: its fields live in scalar registers)
+    const Bitswap1Range& a = job->r;
+    const PyramidPlan& P = job->plan;
+    const uint32_t op = job->op, tid = threadIdx.x, T = P.T;
+    const BinBlock top = bin_block_of(pyramid_top_plan(P), blockIdx.x - first_tile[j]);
+    uint64_t z0, nz0, cy0, ncy, cx0, ncx;                               // the block in level-0 cells
+    pyramid_level_span(P, 0, 0, top.cz, 1, &z0, &nz0);
+    pyramid_level_span(P, 0, 1, top.cy0, top.ncy, &cy0, &ncy);
+    pyramid_level_span(P, 0, 2, top.cx0, top.ncx, &cx0, &ncx);
+    const uint32_t ncells = (uint32_t)ncy * (uint32_t)ncx;             // (<= kBinBlockCells: bitswap1_box_pyramid_job_ok)
+    const bool zreg = job->zreg != 0;
+    const uint64_t frame = job->g.bY * job->g.bX;
+    uint32_t off_grid = 0;                                            // (uniform) a run's four bytes of every plane: on the 4-byte grid?
+#pragma unroll
+    for (uint32_t p = 0; p < W; ++p) off_grid |= (uint32_t)(reinterpret_cast<uintptr_t>(in) + a.plane[p] - a.w0 * ELEM);
+    const bool grid4 = a.w0 < a.w1 && (off_grid & 3u) == 0;
+    BinLdsSink sink{acc, op};
+    uint32_t* __restrict__ out0 = static_cast<uint32_t*>(job->out[0]);
+    for (uint64_t k = 0; k < nz0; ++k) {
+        const BinBlock blk{z0 + k, cy0, ncy, cx0, ncx};
+        for (uint32_t c = tid; c < ncells; c += 256u) acc[c] = project_neutral(op);
+        __syncthreads();
+        const BinFootprint f = bin_block_footprint(job->g, job->bins, blk);
+        const uint64_t items = bin_block_items(f, zreg);
+        for (uint64_t t = tid; t < items; t += 256u) {
+            uint64_t z, run;
+            if (!bin_block_item(f, zreg, t, &z, &run)) continue;
+            WindowGeometry g = f.g;
+            g.oz = z;
+            WindowClip c = window_clip_start(g, run * 32u, 32);
+            WindowPiece cur;
+            bool have = window_clip_next(g, &c, &cur);
+            if (!have) continue;                                      // (nothing of the run inside the footprint: no plane word is loaded)
+            uint32_t red[32];
+            bin_load_run<ELEM, LUT>(in, a, run * 32u, grid4, sl, red);
+            if (zreg)
+                for (uint64_t zz = 1; zz < f.nz; ++zz) {              // the same positions of the layer's other frames
+                    uint32_t v[32];
+                    bin_load_run<ELEM, LUT>(in, a, run * 32u + zz * frame, grid4, sl, v);
+#pragma unroll
+                    for (int i = 0; i < 32; ++i) red[i] = project_combine(op, red[i], v[i]);
+                }
+            bin_run_cells(sink, g, c, cur, have, red, job->bins[1], job->bins[2], ncx, op);
+        }
+        __syncthreads();
+        {
+            const uint64_t py = job->py[0], base = blk.cz * job->pz[0] + cy0 * py + cx0;
+            const uint32_t w = (uint32_t)ncx;
+            for (uint32_t c = tid; c < ncells; c += 256u) {
+                const uint32_t cy = c / w;
+                out0[base + cy * py + (c - cy * w)] = acc[c];
+            }
+        }
+        // the layer folded upwards: `done` is the layer of level l - 1 that has just been completed
+        uint64_t done = blk.cz, mcy = ncy, mcx = ncx;                   // (the block's cells of the level below)
+        for (uint32_t l = 1; l <= T; ++l) {
+            const uint64_t rz = P.r[l][0], cz = done / rz, last = (cz + 1) * rz < P.C[l - 1][0] ? (cz + 1) * rz : P.C[l - 1][0];
+            const bool first = done == cz * rz, complete = done + 1 == last;
+            uint64_t ly0, lcy, lx0, lcx;
+            pyramid_level_span(P, l, 1, top.cy0, top.ncy, &ly0, &lcy);
+            pyramid_level_span(P, l, 2, top.cx0, top.ncx, &lx0, &lcx);
+            const uint32_t* lo = acc + P.off[l - 1];
+            uint32_t* hi = acc + P.off[l];
+            uint32_t* __restrict__ outl = static_cast<uint32_t*>(job->out[l]);
+            const uint64_t py = job->py[l], base = cz * job->pz[l] + ly0 * py + lx0, ry = P.r[l][1], rx = P.r[l][2];
+            const uint32_t n = (uint32_t)lcy * (uint32_t)lcx, w = (uint32_t)lcx;
+            for (uint32_t c = tid; c < n; c += 256u) {
+                const uint32_t y = c / w, x = c - y * w;
+                uint32_t v = pyramid_fold_cell(lo, mcy, mcx, ry, rx, y, x, op);
+                if (!first) v = project_combine(op, hi[c], v);
+                hi[c] = v;
+                if (complete) outl[base + y * py + x] = v;
+            }
+            if (!complete) break;
+            __syncthreads();                                          // level l's layer stands: the next fold reads it
+            done = cz; mcy = lcy; mcx = lcx;
+        }
+        __syncthreads();                                              // the folds have read what the next layer's walk sets anew
+    }
+}
+
+// a thread per cell of a pyramid level: the cells of the stored finer level under it reduced, the cell stored once
+__global__ __launch_bounds__(256)
+void pyramid_reduce_kernel(const PyramidReduceJob* __restrict__ jobs, const uint32_t* __restrict__ first_tile, uint32_t njobs)
+{
+    const uint32_t j = batch_job_of_tile(first_tile, njobs);
+    const PyramidReduceJob* __restrict__ job = jobs + j;
+    const uint64_t e = (uint64_t)(blockIdx.x - first_tile[j]) * 256u + threadIdx.x, C1 = job->C[1], C2 = job->C[2], layer = C1 * C2;
+    if (e >= job->C[0] * layer) return;
+    const uint64_t cz = e / layer, r = e - cz * layer, cy = r / C2, cx = r - cy * C2;
+    const uint32_t* src = static_cast<const uint32_t*>(job->src);       // (written by the launch in front: not __restrict__)
+    const uint32_t acc = pyramid_reduce_cell(src, job->Cs, job->spz, job->spy, job->r, cz, cy, cx, job->op);
+    static_cast<uint32_t*>(job->out)[cz * job->pz + cy * job->py + cx] = acc;
+}
+
+static_assert(sizeof(Bitswap1BoxPyramidJob) == kBitswap1BoxPyramidJobBytes && sizeof(Bitswap1BoxPyramidJob) % 16 == 0 && sizeof(PyramidReduceJob) == kPyramidReduceJobBytes &&
+                  sizeof(PyramidReduceJob) % 16 == 0 && kPyramidLdsCells * 4u + 512u <= 65536u && kBinBlockCells <= kPyramidLdsCells,
+              "the pyramid jobs' layout; the accumulators and the look-up within 64 KiB of LDS");
+
+// bitswap1_box_bin_job_ok for the pyramid job: level 0's bins inside the extent, the grids nested as the ratios say, the tiling that of
+// the level-T grid, every fused level's accumulators inside LDS, every output there and behind its grid's pitches
+bool bitswap1_box_pyramid_job_ok(const Bitswap1BoxPyramidJob& j)
+{
+    const Bitswap1Range& r = j.r;
+    const WindowGeometry& g = j.g;
+    const PyramidPlan& p = j.plan;
+    if (r.v1 <= r.v0 || r.w1 < r.w0 || g.Z == 0 || g.Y == 0 || g.X == 0 || g.bY == 0 || g.bX == 0) return false;
+    if (j.op >= kProjectOps || (j.zreg && (g.bY * g.bX) % 32 != 0)) return false;
+    if (p.levels < 1 || p.levels > kPyramidMaxLevels || p.T >= p.levels) return false;
+    const uint64_t e[3] = {g.Z, g.Y, g.X};
+    for (int d = 0; d < 3; ++d) {
+        if (j.bins[d] == 0 || j.bins[d] > e[d] || p.C[0][d] != (e[d] + j.bins[d] - 1) / j.bins[d] || p.q[p.T][d] != 1) return false;
+        for (uint32_t l = 1; l < p.levels; ++l)
+            if (p.r[l][d] == 0 || p.r[l][d] > p.C[l - 1][d] || p.C[l][d] != (p.C[l - 1][d] + p.r[l][d] - 1) / p.r[l][d]) return false;
+        for (uint32_t l = p.T; l >= 1; --l) {                           // (products of two grid sizes of an admitted box: no wrap)
+            const uint64_t want = p.q[l][d] * p.r[l][d] < p.C[l - 1][d] ? p.q[l][d] * p.r[l][d] : p.C[l - 1][d];
+            if (p.q[l - 1][d] != want) return false;
+        }
+    }
+    for (uint32_t l = 0; l < p.levels; ++l) {
+        if (!j.out[l] || reinterpret_cast<uintptr_t>(j.out[l]) % 4u) return false;
+        if (j.py[l] < p.C[l][2] || (p.C[l][0] > 1 && j.pz[l] < p.C[l][1] * j.py[l])) return false;
+    }
+    const uint64_t CT1 = p.C[p.T][1], CT2 = p.C[p.T][2];
+    if (p.band == 0 || p.strip == 0 || p.band > CT1 || p.strip > CT2) return false;
+    if (p.nbands != (CT1 + p.band - 1) / p.band || p.nstrips != (CT2 + p.strip - 1) / p.strip || p.blocks != p.C[p.T][0] * p.nbands * p.nstrips) return false;
+    uint64_t at = 0;
+    for (uint32_t l = 0; l <= p.T; ++l) {
+        const uint64_t ny = p.band * p.q[l][1] < p.C[l][1] ? p.band * p.q[l][1] : p.C[l][1], nx = p.strip * p.q[l][2] < p.C[l][2] ? p.strip * p.q[l][2] : p.C[l][2];
+        if (ny > kPyramidLdsCells || nx > kPyramidLdsCells || ny * nx > (l == 0 ? kBinBlockCells : kPyramidLdsCells)) return false;
+        if (p.off[l] != at) return false;
+        at += ny * nx;
+        if (at > kPyramidLdsCells) return false;
+    }
+    return ((g.oz * g.bY + g.oy) * g.bX + g.ox) >= r.v0 && ((g.oz + g.Z - 1) * g.bY + g.oy + g.Y - 1) * g.bX + g.ox + g.X <= r.v1;
+}
+
+hipError_t launch_bitswap1_decode_range_windows_pyramid(const uint8_t* in, const Bitswap1BoxPyramidJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs,
+                                                        uint32_t ngroups, int elem_size, const uint16_t* lut, hipStream_t stream)
+{
+    if (njobs == 0 || ngroups < njobs || (elem_size != 1 && elem_size != 2) || (lut && elem_size != 1)) return hipErrorInvalidValue;
+    const dim3 grid(ngroups);
+    if (elem_size == 2) hipLaunchKernelGGL((bitswap1_decode_range_windows_pyramid_kernel<2, false>), grid, dim3(256), 0, stream, in, d_jobs, d_first_tile, njobs, lut);
+    else if (lut) hipLaunchKernelGGL((bitswap1_decode_range_windows_pyramid_kernel<1, true>), grid, dim3(256), 0, stream, in, d_jobs, d_first_tile, njobs, lut);
+    else hipLaunchKernelGGL((bitswap1_decode_range_windows_pyramid_kernel<1, false>), grid, dim3(256), 0, stream, in, d_jobs, d_first_tile, njobs, lut);
+    return hipGetLastError();
+}
+
+hipError_t launch_pyramid_reduce(const PyramidReduceJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ngroups, hipStream_t stream)
+{
+    if (njobs == 0 || ngroups < njobs) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(pyramid_reduce_kernel, dim3(ngroups), dim3(256), 0, stream, d_jobs, d_first_tile, njobs);
+    return hipGetLastError();
+}
+
 hipError_t launch_batch_view_copy(const BatchViewJob* d_jobs, const uint32_t* d_first_tile, uint32_t njobs, uint32_t ntiles, int elem_size, bool to_view,
                                   hipStream_t stream)
 {

@@ -1033,6 +1033,121 @@ bool admit_histogram(const std::vector<uint64_t>& header_shape, const long* orig
     return out && reinterpret_cast<uintptr_t>(out) % 4u == 0;
 }
 
+// ---- a resolution pyramid of boxes (SQYAMD_Pyramid_Boxes_*) ----
+PyramidPath pyramid_boxes_path(bool subset_form, RangeForm form, bool subset_option, bool fused_option)
+{
+    return PyramidPath{bin_boxes_path(subset_form, form, subset_option), fused_option};
+}
+
+bool admit_pyramid(const std::vector<uint64_t>& header_shape, const long* origin, const long* extent, unsigned rank, long levels, const long* bins, int op,
+                   uint64_t maxvoxel, const void* const* outs, const long* out_strides, BatchWindow* w, Pyramid* p, PyramidSizes* sizes)
+{
+    if (!w || !p || !bins || !outs || levels < 1 || levels > (long)kPyramidMaxLevels || rank < 1 || rank > 3) return false;
+    for (long l = 0; l < levels; ++l)
+        for (unsigned k = 0; k < rank; ++k) {
+            const long b = bins[(size_t)l * rank + k];
+            if (b < 1 || (l > 0 && b % bins[(size_t)(l - 1) * rank + k] != 0)) return false;      // (the level below is >= 1: checked first)
+        }
+    Pyramid y;
+    y.levels = (uint32_t)levels;
+    for (long l = 0; l < levels; ++l) {
+        if (!admit_binning(header_shape, origin, extent, rank, bins + (size_t)l * rank, op, maxvoxel, outs[l], out_strides ? out_strides + (size_t)l * rank : nullptr, w,
+                           &y.q[l]))
+            return false;
+        for (unsigned d = 0; d < 3; ++d) y.raw[l][d] = d < 3 - rank ? 1u : (uint64_t)bins[(size_t)l * rank + (d - (3 - rank))];
+    }
+    for (uint32_t l = levels; l < kPyramidMaxLevels; ++l)
+        for (unsigned d = 0; d < 3; ++d) y.raw[l][d] = 1;
+    if (sizes) {
+        const uint64_t E[3] = {w->Z, w->Y, w->X};
+        const uint64_t lim = 0x7fffffffull;
+        sizes->cell_groups += (y.q[0].C[0] * y.q[0].C[1] * y.q[0].C[2] + 255) / 256;      // (the cells are no more than the blob's voxels: no wrap)
+        sizes->bin_blocks += bin_boxes_plan(y.q[0].C, y.q[0].bins, w->X).blocks;
+        sizes->blocks += pyramid_boxes_plan(y, E).blocks;
+        for (long l = 1; l < levels; ++l) sizes->reduce_groups += (y.q[l].C[0] * y.q[l].C[1] * y.q[l].C[2] + 255) / 256;
+        if (sizes->cell_groups > lim || sizes->bin_blocks > lim || sizes->blocks > lim || sizes->reduce_groups > lim) return false;
+    }
+    *p = y;
+    return true;
+}
+
+static uint64_t pyramid_sat_mul(uint64_t a, uint64_t b)
+{
+    constexpr uint64_t lim = (uint64_t)1 << 40;                         // (far above every budget and cap: each factor is clamped to it first)
+    return std::min(std::min(a, lim) * std::min(b, lim), lim);
+}
+
+uint64_t pyramid_level_cells(const PyramidPlan& p, uint32_t l, uint64_t band, uint64_t strip)
+{
+    return pyramid_sat_mul(std::min(pyramid_sat_mul(band, p.q[l][1]), p.C[l][1]), std::min(pyramid_sat_mul(strip, p.q[l][2]), p.C[l][2]));
+}
+
+PyramidPlan pyramid_boxes_plan(const Pyramid& y, const uint64_t E[3], uint64_t budget_level0, uint64_t budget_cells, uint64_t cap_voxels)
+{
+    PyramidPlan p{};
+    const uint32_t levels = std::min(std::max<uint32_t>(y.levels, 1), kPyramidMaxLevels);
+    p.levels = levels;
+    budget_level0 = std::max<uint64_t>(budget_level0, 1);
+    budget_cells = std::max(budget_cells, budget_level0);
+    for (uint32_t l = 0; l < kPyramidMaxLevels; ++l)
+        for (int d = 0; d < 3; ++d) {
+            p.C[l][d] = l < levels ? y.q[l].C[d] : 1;
+            p.r[l][d] = l && l < levels ? std::min(y.raw[l][d] / y.raw[l - 1][d], p.C[l - 1][d]) : 1;
+            p.q[l][d] = 1;
+        }
+    // level-`from` cells under one level-`to` cell (from <= to), clamped to the grid
+    const auto under = [&](uint32_t to, uint32_t from, int d) { return std::min(y.raw[to][d] / y.raw[from][d], p.C[from][d]); };
+    uint32_t T = 0;
+    for (uint32_t t = levels - 1; t >= 1; --t) {
+        if (pyramid_sat_mul(under(t, 0, 1), under(t, 0, 2)) > budget_level0) continue;
+        uint64_t all = 0, voxels = 1;
+        for (uint32_t l = 0; l <= t; ++l) all += pyramid_sat_mul(under(t, l, 1), under(t, l, 2));
+        // (a row of level-t cells over the box's width and all its frames: the least a block walks)
+        for (int d = 0; d < 3; ++d) voxels = pyramid_sat_mul(voxels, d == 2 ? std::max<uint64_t>(E[d], 1) : std::min(y.raw[t][d], std::max<uint64_t>(E[d], 1)));
+        if (all > budget_cells || voxels > cap_voxels) continue;
+        T = t;
+        break;
+    }
+    p.T = T;
+    for (uint32_t l = 0; l < levels; ++l)
+        for (int d = 0; d < 3; ++d) p.q[l][d] = l <= T ? under(T, l, d) : std::min(y.raw[l][d] / y.raw[T][d], p.C[T][d]);
+    const auto fits = [&](uint64_t band, uint64_t strip) {
+        if (pyramid_level_cells(p, 0, band, strip) > budget_level0) return false;
+        uint64_t all = 0;
+        for (uint32_t l = 0; l <= T; ++l) all += pyramid_level_cells(p, l, band, strip);
+        return all <= budget_cells;
+    };
+    // the largest n in [1, hi] with ok(n), ok monotone and ok(1) true
+    const auto largest = [](uint64_t hi, const auto& ok) {
+        uint64_t lo = 1;
+        while (lo < hi) {
+            const uint64_t mid = lo + (hi - lo + 1) / 2;
+            if (ok(mid)) lo = mid; else hi = mid - 1;
+        }
+        return lo;
+    };
+    const uint64_t CT1 = p.C[T][1], CT2 = p.C[T][2];
+    if (!fits(1, CT2)) {                                                // a row of level-T cells does not fit: ONE row, in strips
+        p.band = 1;
+        p.strip = largest(CT2, [&](uint64_t s) { return fits(1, s); });
+    } else {
+        p.strip = CT2;
+        // a row of level-T cells over all its frames, saturating: a block walks band rows of it, layer by layer
+        const uint64_t row = pyramid_sat_mul(pyramid_sat_mul(std::min(y.raw[T][0], std::max<uint64_t>(E[0], 1)), std::min(y.raw[T][1], std::max<uint64_t>(E[1], 1))),
+                                             std::max<uint64_t>(E[2], 1));
+        p.band = largest(std::min(CT1, std::max<uint64_t>(1, cap_voxels / row)), [&](uint64_t b) { return fits(b, CT2); });
+    }
+    p.nbands = (CT1 + p.band - 1) / p.band;
+    p.nstrips = (CT2 + p.strip - 1) / p.strip;
+    p.blocks = p.C[T][0] * p.nbands * p.nstrips;                        // (the caller bounds the sum over the boxes, as for bin_boxes_plan)
+    uint64_t at = 0;
+    for (uint32_t l = 0; l <= T; ++l) {
+        p.off[l] = (uint32_t)at;
+        at += pyramid_level_cells(p, l, p.band, p.strip);
+    }
+    return p;
+}
+
 // ---- a box written into one large blob (SQYAMD_Update_Box_*) ----
 UpdateBoxPath update_box_path(const UpdateBoxFacts& f)
 {

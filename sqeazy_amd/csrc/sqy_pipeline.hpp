@@ -585,6 +585,41 @@ bool admit_binning(const std::vector<uint64_t>& header_shape, const long* origin
 // where a row fits (as many as the budget takes, but no more than keep the block's footprint near cap_voxels voxels: small blocks fill
 // the device), else ONE cell row cut into strips of budget_cells columns.  blocks = C[0] nbands nstrips.
 BinPlan bin_boxes_plan(const uint64_t C[3], const uint64_t bins[3], uint64_t X, uint64_t budget_cells = kBinBlockCells, uint64_t cap_voxels = kBinBlockVoxels);
+// A whole resolution pyramid of many boxes of one blob (SQYAMD_Pyramid_Boxes_*).  subset_option: pyramid_boxes_subset, fused_option:
+// pyramid_boxes_fused; the rest as for bin_boxes_path.  ONE header fetch, ONE frame index, the LZ4 frames of all boxes' z-ranges united and
+// decoded ONCE on the subset paths (the blob decoded whole ONCE on whole_copy); then, with `fused`:
+//   subset_transposer  planes, planes_lut: ONE launch of the pyramid job-table kernel -- a workgroup per block of level-T cells
+//                      (pyramid_boxes_plan), all fused levels' accumulators in LDS, every cell of every fused level stored once --, and where
+//                      some box has levels above its T ONE pyramid_reduce launch that takes them all from the stored level-T cells
+//   subset_copy        plain, shuffle: level 0 by Bin_Boxes' launch with a thread per cell in the compaction, then ONE pyramid_reduce
+//                      launch that takes every further level straight from level 0
+//   whole_copy         every other blob, and every blob with the subset option off: the same two launches on the whole volume
+// and without: level 0 by Bin_Boxes' launch of the path, every further level by a pyramid_reduce launch of its own from the level below
+// -- the same outputs, the layer to fall back on.
+struct PyramidPath { BoxPath path; bool fused; };
+PyramidPath pyramid_boxes_path(bool subset_form, RangeForm form, bool subset_option, bool fused_option);
+// The admission of one box's pyramid, stated once (SQYAMD_Pyramid_Boxes_*), on admit_binning.  levels in [1,
+// kPyramidMaxLevels]; bins: levels x rank longs, row l for level l; the rows nest: bins[l + 1][d] is a whole multiple of bins[l][d] for
+// every d, on the caller's unclamped values (a multiple of 1 -- a repeated level -- included).  outs: the box's `levels` outputs, each as
+// admit_binning wants it; out_strides: levels x rank pitches, or nullptr: all dense.  Every level is admitted by admit_binning -- the sum
+// bound binds on the coarsest level's cell, the largest --, and where `sizes` is given the box's workgroups are added to each launch's
+// count and the box refused where one passes 2^31 - 1.  On success: the window, every level's Binning, and the caller's bins padded to
+// (z, y, x) with ones (`raw`: the ratios are taken on them).
+struct Pyramid { uint32_t levels = 0; Binning q[kPyramidMaxLevels]; uint64_t raw[kPyramidMaxLevels][3]; };
+struct PyramidSizes { uint64_t cell_groups = 0, blocks = 0, bin_blocks = 0, reduce_groups = 0; };
+bool admit_pyramid(const std::vector<uint64_t>& header_shape, const long* origin, const long* extent, unsigned rank, long levels, const long* bins, int op,
+                   uint64_t maxvoxel, const void* const* outs, const long* out_strides, BatchWindow* w, Pyramid* p, PyramidSizes* sizes = nullptr);
+// What a workgroup of the pyramid kernel owns, per box, stated once (sqy_batch_window.hpp states what a block is).  E: the box's extent
+// padded to (z, y, x).  T is the highest level of which ONE cell, counted in level-0 cells of one layer after clamping to the grid, fits
+// budget_level0 accumulators, whose fused levels' accumulators for ONE level-T cell fit budget_cells together, and of which ONE row of
+// cells over the box's width and all its frames -- the least a block walks, layer after layer -- holds no more than cap_voxels voxels
+// (level 0 is always fused).  The level-T grid is tiled as bin_boxes_plan tiles: whole rows of level-T cells where one fits both budgets
+// (as many as fit, but no more than keep the block's footprint near cap_voxels: small blocks fill the device), else ONE row cut into the
+// widest strips that fit.  off[l]: level l's accumulators in LDS for a block of the full band and strip.
+PyramidPlan pyramid_boxes_plan(const Pyramid& p, const uint64_t E[3], uint64_t budget_level0 = kBinBlockCells, uint64_t budget_cells = kPyramidLdsCells,
+                               uint64_t cap_voxels = kPyramidBlockVoxels);
+// the accumulators that the level-l cells (l <= T) under band x strip level-T cells take: one layer of them
+uint64_t pyramid_level_cells(const PyramidPlan& p, uint32_t l, uint64_t band, uint64_t strip);
 // The intensity histograms of many boxes of one blob (SQYAMD_Histogram_Boxes_*).  option_on: histogram_boxes_subset; the rest as for
 // project_boxes_path.  One job per box; on every path ONE launch that zeroes all histograms, then ONE counting launch that adds into them:
 //   subset_transposer  planes, planes_lut: the LZ4 frames of all boxes' z-ranges united, then the counting job-table range transposer --
