@@ -384,6 +384,22 @@ def lz4_planted():
     print("wrote", os.path.join(GOLD, "lz4_planted.json"), "with", len(L["cases"]), "cases")
 
 
+def lz4_linked_planted():
+    """tests/golden/lz4_linked_planted.json: the streams of tests/lz4_linked_planted.py -- per case its length and sha256 and the size and sha256
+    of the oracle's frame under the case's configuration (no bytes); asserts oracle == liblz4 on the way where the reference driver is built"""
+    import lz4_linked_planted as LP
+    L = {"_meta": {"generator": "oracle/gen_golden.py --lz4-linked-planted", "frame": "lz4_linked_planted.oracle_frame(sqy_oracle, case)",
+                   "liblz4": "1.9.3 (LZ4_versionNumber 10903)" if ref.available() else "not compared"}, "cases": {}}
+    for c in LP.cases():
+        fr = LP.oracle_frame(o, c)
+        if ref.available():
+            assert fr == LP.liblz4_frame(ref, o, c), c["name"]
+        L["cases"][c["name"]] = {"n": len(c["data"]), "sha256": sha(c["data"]), "frame_bytes": len(fr), "frame_sha256": sha(fr)}
+    with open(os.path.join(GOLD, "lz4_linked_planted.json"), "w") as f:
+        json.dump(L, f, indent=1, sort_keys=True)
+    print("wrote", os.path.join(GOLD, "lz4_linked_planted.json"), "with", len(L["cases"]), "cases")
+
+
 # ------------------------------------------------------------------------------------------------------------------------------------
 # Filter stages against the reference's own templates (oracle/ref_driver.cpp): ONE table of cases, tests/golden/ref_stages.json
 # ------------------------------------------------------------------------------------------------------------------------------------
@@ -899,6 +915,8 @@ if __name__ == "__main__":
         accel()
     elif "--lz4-planted" in sys.argv:
         lz4_planted()
+    elif "--lz4-linked-planted" in sys.argv:
+        lz4_linked_planted()
     elif "--headline-slabs" in sys.argv:
         headline_slabs()
     elif "--headline-serial" in sys.argv:
@@ -914,5 +932,6 @@ if __name__ == "__main__":
         quantiser()
         accel()
         lz4_planted()
+        lz4_linked_planted()
         headline()
         headline_serial()
