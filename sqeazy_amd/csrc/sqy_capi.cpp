@@ -2467,15 +2467,24 @@ int decode_staged(const char* src, uint64_t src_bytes, char* dst, uint64_t dst_b
     return 0;
 }
 
+// The header front of the host variants that name a part of ONE blob (frames, a box, boxes), before anything is staged: the header found,
+// its shape sound (header_shape_ok; *raw: the volume's bytes) and its voxels the entry point's
+bool host_header_ok(const char* src, long srclength, int elem_size, sqy::HeaderInfo* h, uint64_t* raw)
+{
+    *h = sqy::header_unpack(src, src + srclength);
+    if (!h->valid) { std::fprintf(stderr, "[sqeazy]\t unable to find a sqy header in the blob\n"); return false; }
+    if (!header_shape_ok(*h, (uint64_t)srclength, raw)) return false;
+    if (h->elem_size() != elem_size) { std::fprintf(stderr, "[sqeazy]\t blob holds %s voxels\n", h->type.c_str()); return false; }
+    return true;
+}
+
 // host-pointer frame-range decode: only the range comes back
 int decode_frames_from_host(const char* src, long srclength, long z0, long nz, char* dst, long dst_capacity, int elem_size)
 {
     if (!src || !dst || srclength <= 0) return 1;
-    const sqy::HeaderInfo h = sqy::header_unpack(src, src + srclength);
-    if (!h.valid) { std::fprintf(stderr, "[sqeazy]\t unable to find a sqy header in the blob\n"); return 1; }
+    sqy::HeaderInfo h;
     uint64_t raw = 0;
-    if (!header_shape_ok(h, (uint64_t)srclength, &raw)) return 1;
-    if (h.elem_size() != elem_size) { std::fprintf(stderr, "[sqeazy]\t blob holds %s voxels\n", h.type.c_str()); return 1; }
+    if (!host_header_ok(src, srclength, elem_size, &h, &raw)) return 1;
     const uint64_t Z = h.shape[0], fb = raw / Z;
     if (z0 < 0 || nz <= 0 || (uint64_t)z0 + (uint64_t)nz > Z || (uint64_t)nz * fb > (uint64_t)std::max(dst_capacity, 0l)) {
         std::fprintf(stderr, "[sqeazy]\t decode frames: range [%ld, %ld + %ld) outside the blob's %llu frames, or buffer too small\n", z0, z0, nz,
@@ -2614,6 +2623,8 @@ struct TiledJobs {
     ~TiledJobs() { wait(); }
     void wait() { if (queued) (void)hipStreamSynchronize(queued_on); queued = false; }
     void clear() { wait(); jobs.clear(); first_tile.clear(); ntiles = 0; host.clear(); }
+    // a job that owns the next `tiles` workgroups of the launch
+    void push(const Job& j, uint32_t tiles) { jobs.push_back(j); first_tile.push_back(ntiles); ntiles += tiles; }
     // the tables to buf: the jobs at its start, *d_tiles the prefix sums behind them
     int upload(hipStream_t stream, DevBuf& buf, const uint32_t** d_tiles)
     {
@@ -2631,18 +2642,23 @@ struct TiledJobs {
         return 0;
     }
 };
+// A window job's workgroups.  blob_tiles: the job is a windowed transposer's -- the blob's tiles that reach into the window's frames, from
+// tile0 on --, else a copy's or a compare's: the window's own tiles
+struct WindowTiles { uint64_t tile0; uint32_t count; };
+WindowTiles window_tiles(const sqy::BatchWindow& w, const WindowView& v, bool blob_tiles)
+{
+    if (!blob_tiles) return WindowTiles{0, sqy::batch_bitswap1_tiles(w.Z * w.Y * w.X)};
+    const sqy::WindowGeometry g = sqy::window_geometry(w, v.sz, v.sy);
+    return WindowTiles{sqy::window_first_tile(g, sqy::kBatchTileVoxels), (uint32_t)sqy::window_tile_count(g, sqy::kBatchTileVoxels)};
+}
 struct WindowLaunch : TiledJobs<sqy::BatchWindowJob> {
     // paste (SQYAMD_Update_BatchWindow_*): the copy the other way round, the job's `dense` is written
     enum Kind { copy, bitswap1_decode, copy_from_lz4, paste };
-    // blob_tiles: the job is the windowed transposer's (the blob's tiles that reach into the window's frames), else the copy's (the
-    // window's own tiles)
+    // blob_tiles: window_tiles
     void add(const void* view, const void* dense, const sqy::BatchWindow& w, const WindowView& v, bool blob_tiles)
     {
-        const sqy::WindowGeometry g{w.bY, w.bX, w.oz, w.oy, w.ox, w.Z, w.Y, w.X, v.sz, v.sy};
-        const uint64_t tile0 = blob_tiles ? sqy::window_first_tile(g, sqy::kBatchTileVoxels) : 0;
-        jobs.push_back(sqy::BatchWindowJob{const_cast<void*>(view), dense, w.Z, w.Y, w.X, v.sz, v.sy, w.bZ, w.bY, w.bX, w.oz, w.oy, w.ox, tile0});
-        first_tile.push_back(ntiles);
-        ntiles += blob_tiles ? (uint32_t)sqy::window_tile_count(g, sqy::kBatchTileVoxels) : sqy::batch_bitswap1_tiles(w.Z * w.Y * w.X);
+        const WindowTiles t = window_tiles(w, v, blob_tiles);
+        push(sqy::BatchWindowJob{const_cast<void*>(view), dense, w.Z, w.Y, w.X, v.sz, v.sy, w.bZ, w.bY, w.bX, w.oz, w.oy, w.ox, t.tile0}, t.count);
     }
 };
 // the tables to Workspace::batch_windows[kind], the launch behind them under its profile name; no jobs: nothing
@@ -2699,11 +2715,7 @@ int box_range_out(DecodeCall& c, WindowLaunch& l, const sqy::BatchWindow& w, con
         return 0;
     }
     // plain, shuffle: the range in the workspace is a blob of the box's frames, the box begins at its first one
-    sqy::BatchWindow in_range = w;
-    if (rank == 3) { in_range.bZ = w.Z; in_range.oz = 0; }             // (the frames are the header's first dimension:
-    else if (rank == 2) { in_range.bY = w.Y; in_range.oy = 0; }        //  of a header of rank 2 the rows,
-    else { in_range.bX = w.X; in_range.ox = 0; }                       //  of rank 1 the voxels)
-    return launch_box_copy(c.cx, stream, l, c.d_dst, c.range_buf + p.range_at, in_range, v, e);
+    return launch_box_copy(c.cx, stream, l, c.d_dst, c.range_buf + p.range_at, sqy::window_in_own_frames(w, rank), v, e);
 }
 
 // The box [origin, origin + extent) of the blob into the view at d_dst.  Same checks as decode_on_device, plus the window against the
@@ -2766,11 +2778,9 @@ int decode_box_device(const void* d_src, long srclength, const long* origin, voi
 int decode_box_from_host(const char* src, long srclength, const long* origin, const long* extent, unsigned rank, char* dst, long dst_capacity, int elem_size)
 {
     if (!box_arguments_ok(src, srclength, origin, dst, extent, rank)) { std::fprintf(stderr, "[sqeazy]\t decode box: bad arguments\n"); return 1; }
-    const sqy::HeaderInfo h = sqy::header_unpack(src, src + srclength);
-    if (!h.valid) { std::fprintf(stderr, "[sqeazy]\t unable to find a sqy header in the blob\n"); return 1; }
+    sqy::HeaderInfo h;
     uint64_t raw = 0;
-    if (!header_shape_ok(h, (uint64_t)srclength, &raw)) return 1;
-    if (h.elem_size() != elem_size) { std::fprintf(stderr, "[sqeazy]\t blob holds %s voxels\n", h.type.c_str()); return 1; }
+    if (!host_header_ok(src, srclength, elem_size, &h, &raw)) return 1;
     sqy::BatchWindow w;
     if (!sqy::admit_window(h.shape, origin, extent, rank, &w) || w.Z * w.Y * w.X * (uint64_t)elem_size > (uint64_t)std::max(dst_capacity, 0l)) {
         std::fprintf(stderr, "[sqeazy]\t decode box: the box does not lie inside the blob's shape, or buffer too small\n");
@@ -2782,10 +2792,165 @@ int decode_box_from_host(const char* src, long srclength, const long* origin, co
     });
 }
 
+// ---- boxes of one large blob: what every SQYAMD_*_Boxes_* driver shares -------------------------------------------------------
+// A family is an admission per box (sqy::admit_window, admit_projection, ..) and an output: ONE launch behind DecodeCall::frames_subset on
+// the boxes' z-ranges united -- ONE header fetch, frame index and pruned LZ4 launch for all boxes --, and the same output out of the whole
+// volume, decoded ONCE into Workspace::range_full, for every other blob.  BoxesCall holds that flow; the families below say what is theirs.
+
+// the refusal of box i in the words of the family `who`
+bool box_refused(const char* who, size_t i, const char* why) { std::fprintf(stderr, "[sqeazy]\t %s: box %zu %s\n", who, i, why); return false; }
+
+// f(i, origin, extent) for every box of the tables, until one says false
+template <class F>
+bool every_box(size_t count, const long* origins, const long* extents, unsigned rank, F&& f)
+{
+    for (size_t i = 0; i < count; ++i)
+        if (!f(i, origins + i * rank, extents + i * rank)) return false;
+    return true;
+}
+
+// what a family's *_arguments_ok checks of the boxes without a header, before a device is looked for: admit(i, shape, origin, extent) -- the
+// family's sqy::admit_* -- of every box against the smallest shape that holds it
+template <class F>
+bool every_box_in_its_own_shape(long count, const long* origins, const long* extents, unsigned rank, F&& admit)
+{
+    return every_box((size_t)count, origins, extents, rank, [&](size_t i, const long* o, const long* e) { return admit(i, sqy::smallest_holding_shape(o, e, rank), o, e); });
+}
+
+// the largest voxel of the entry point's type (the sum bounds of the admissions)
+uint64_t voxel_max(int elem_size) { return elem_size == 2 ? 65535u : 255u; }
+
+// the common prefix of the range transposers' jobs (sqy::Bitswap1BoxJob, ..CompareJob, ..ProjectJob, ..BinJob, ..PyramidJob): the window w
+// with the sink's two pitches, the box's range b of the united frames and its first thread; we: the bytes of a stored voxel
+template <class Job>
+void fill_range_job(Job& j, const sqy::BatchWindow& w, uint64_t sz, uint64_t sy, const sqy::FrameRangesBox& b, int we)
+{
+    j.g = sqy::window_geometry(w, sz, sy);
+    j.r = sqy::bitswap1_range_of<sqy::Bitswap1Range>(b);
+    j.t0 = sqy::range_first_thread(b.w0, 128u / (8u * (uint32_t)we));
+}
+// the workgroups of such a job where they share the range's words
+uint32_t range_job_groups_of(const sqy::FrameRangesBox& b, int we) { return (uint32_t)sqy::range_job_groups(b.w0, b.w1, 128u / (8u * (uint32_t)we)); }
+
+struct BoxesCall {
+    Context& cx;
+    const char* who;                        // the family in the messages: "decode boxes", ..
+    const void* d_src_v;
+    uint64_t srclen;
+    int want_elem;
+    hipStream_t stream;
+    DrainOnExit drain;
+    sqy::HeaderInfo h;
+    uint64_t raw_bytes = 0;
+    std::vector<sqy::BatchWindow> ws;                       // box i in the blob
+    std::vector<std::pair<uint64_t, uint64_t>> ranges;      // .. and its frames
+    // what the one output launch may hold, whichever it is: the family's own sum and a bound of the range transposer's groups
+    uint64_t groups = 0, range_groups = 0;
+    bool verdict = false;                   // run() got as far as the decode's verdict: its return is the decode's (SQYAMD_Compare_Boxes_*'s rows)
+
+    BoxesCall(Context& cx_, const char* who_, const void* d_src, uint64_t srclen_, int want_elem_, hipStream_t stream_)
+        : cx(cx_), who(who_), d_src_v(d_src), srclen(srclen_), want_elem(want_elem_), stream(stream_), drain{stream_, &cx_.pending, cx_.side} {}
+
+    // decode_on_device's checks of the blob, then per_box(i, origin, extent, &ws[i], &own) for every box: the family's admission, which
+    // says its refusal itself (box_refused) and leaves in `own` the box's share of the family's launch
+    template <class F>
+    int admit(size_t count, const long* origins, const long* extents, unsigned rank, F&& per_box)
+    {
+        if (fetch_header(static_cast<const uint8_t*>(d_src_v), srclen, stream, h)) return 1;
+        if (!admit_blob(h, srclen, want_elem, &raw_bytes)) return 1;
+        ws.resize(count);
+        ranges.resize(count);
+        const uint64_t frame_voxels = raw_bytes / (uint64_t)want_elem / h.shape[0];
+        return every_box(count, origins, extents, rank, [&](size_t i, const long* o, const long* e) {
+            uint64_t own = 0;
+            if (!per_box(i, o, e, &ws[i], &own)) return false;
+            ranges[i] = {(uint64_t)o[0], (uint64_t)e[0]};
+            groups += own;
+            range_groups += (uint64_t)e[0] * frame_voxels / sqy::kBatchTileVoxels + 2;      // (at least range_job_groups of the box's words)
+            return true;
+        }) ? 0 : 1;
+    }
+    bool launch_holds(uint64_t n) const
+    {
+        if (n > 0x7fffffffull) std::fprintf(stderr, "[sqeazy]\t %s: too many workgroups for one launch\n", who);
+        return n <= 0x7fffffffull;
+    }
+    bool one_launch_holds() const { return launch_holds(std::max(groups, range_groups)); }
+
+    // All checks are behind: nothing has been written so far.  With the family's option on and a blob DecodeCall::frames_subset takes,
+    // range_launch(c) behind the pruned LZ4 decode (d_dst: DecodeCall's destination); else the whole volume, then whole_launch(volume)
+    template <class R, class W>
+    int run(bool subset_option, void* d_dst, R&& range_launch, W&& whole_launch)
+    {
+        if (subset_option) {
+            DecodeCall c(cx, stream, d_dst, h, Pipeline::from_string(h.pipename), raw_bytes / (uint64_t)want_elem, static_cast<const uint8_t*>(d_src_v) + h.size);
+            bool taken = false;
+            if (const int rc = c.frames_subset(ranges, false, &taken)) return rc;
+            if (taken) {
+                if (c.ranges_plan.boxes.size() != ws.size()) return 1;
+                if (const int rc = range_launch(c)) return rc;
+                verdict = true;
+                return c.finish();
+            }
+        }
+        // sqy::BoxPath::whole_copy: the whole volume ONCE, then all boxes in the family's dense launch
+        if (cx.ws.range_full.ensure(std::max<uint64_t>(raw_bytes, 16))) return 1;
+        if (const int rc = decode_on_device(cx, d_src_v, srclen, cx.ws.range_full.p, raw_bytes, want_elem, stream)) { verdict = true; return rc; }
+        if (whole_launch(cx.ws.range_full.p)) return 1;
+        SQY_HIP(hipStreamSynchronize(stream));
+        if (g_prof_on.load()) prof_collect(cx.pending);
+        verdict = true;
+        return 0;
+    }
+};
+
+// SQYAMD_Decode_Boxes_*'s and SQYAMD_Compare_Boxes_*'s admission: sqy::admit_window, the view (strides + i rank, or dense), the copy's tiles
+int admit_box_windows(BoxesCall& b, size_t count, const long* origins, const long* extents, const long* strides, unsigned rank, std::vector<WindowView>* vs)
+{
+    vs->resize(count);
+    const int refused = b.admit(count, origins, extents, rank, [&](size_t i, const long* o, const long* e, sqy::BatchWindow* w, uint64_t* tiles) {
+        if (!sqy::admit_window(b.h.shape, o, e, rank, w)) return box_refused(b.who, i, "does not lie inside the blob's shape, or has another rank");
+        (*vs)[i] = window_view(*w, strides ? strides + i * rank : nullptr, rank);
+        *tiles = sqy::batch_bitswap1_tiles(w->Z * w->Y * w->X);
+        return true;
+    });
+    return refused || !b.one_launch_holds() ? 1 : 0;
+}
+
+// ---- the host variants of the box families: host_header_ok in front, then the boxes against the header, then ------------------------------
+// the outputs of `bytes` each dense and back to back in the caller's buffer: sqy::output_offsets, said where the buffer is too small
+bool host_outputs_fit(const char* who, const std::vector<uint64_t>& bytes, long capacity, std::vector<uint64_t>* at)
+{
+    if (sqy::output_offsets(bytes, capacity, at)) return true;
+    std::fprintf(stderr, "[sqeazy]\t %s: buffer too small\n", who);
+    return false;
+}
+// decode_staged with the outputs' places in the staged buffer: call(context, d_src, ptrs, stream), ptrs[i] = its start + at[i]
+template <class F>
+int boxes_staged(const char* src, long srclength, char* out, const std::vector<uint64_t>& at, F&& call)
+{
+    return decode_staged(src, (uint64_t)srclength, out, at.back(), [&](Context& cx, void* d_src, void* d_dst, hipStream_t stream) {
+        std::vector<void*> ptrs(at.size() - 1);
+        for (size_t i = 0; i < ptrs.size(); ++i) ptrs[i] = static_cast<uint8_t*>(d_dst) + at[i];
+        return call(cx, d_src, ptrs.data(), stream);
+    });
+}
+
 // ---- many boxes of one large blob (SQYAMD_Decode_Boxes_*) ------------------------------------------------------------------------
-// SQYAMD_Decode_Box_*'s driver for a table of boxes: ONE header fetch, frame index, pruned LZ4 launch over the frames of all boxes' z-ranges
-// united (DecodeCall::frames_subset on the ranges) and ONE output launch for all boxes; sqy::decode_boxes_path says what runs.
+// BoxesCall with stores into the boxes' views; sqy::decode_boxes_path says what runs.  Its own: the box_by_box route, and DecodeCall's
+// destination is the first view.
 static_assert(sizeof(sqy::Bitswap1BoxJob) % 16 == 0, "the box job's layout");
+
+// one window copy under the name "boxes_window_copy", a job per box
+int launch_boxes_copy(Context& cx, hipStream_t stream, WindowLaunch& l, int elem_size)
+{
+    std::vector<PendingEvent>* pend = &cx.pending;
+    const uint32_t* d_tiles = nullptr;
+    if (l.upload(stream, cx.ws.boxes_jobs, &d_tiles)) return 1;
+    SQY_TIMED("boxes_window_copy", sqy::launch_batch_window_copy(static_cast<const sqy::BatchWindowJob*>(cx.ws.boxes_jobs.p), d_tiles, (uint32_t)l.jobs.size(), l.ntiles,
+                                                                  elem_size, stream));
+    return 0;
+}
 
 // the boxes' last launch behind DecodeCall::frames_subset: box i (ws[i], its view vs[i] at dsts[i]) out of the united frames in c.range_buf
 int boxes_range_out(DecodeCall& c, WindowLaunch& l, TiledJobs<sqy::Bitswap1BoxJob>& tj, const std::vector<sqy::BatchWindow>& ws, const std::vector<WindowView>& vs,
@@ -2795,26 +2960,17 @@ int boxes_range_out(DecodeCall& c, WindowLaunch& l, TiledJobs<sqy::Bitswap1BoxJo
     std::vector<PendingEvent>* pend = c.pend;
     const sqy::FrameRangesPlan& p = c.ranges_plan;
     const size_t count = ws.size();
-    if (p.boxes.size() != count) return 1;
-    const uint32_t* d_tiles = nullptr;
     if (sqy::decode_boxes_path(true, c.range_form, true, true) == sqy::BoxesPath::subset_transposer) {
         const uint16_t* lut = nullptr;
         if (c.range_lut(&lut)) return 1;
-        const uint32_t wpt = 128u / (8u * (uint32_t)p.we);
         for (size_t i = 0; i < count; ++i) {
-            const sqy::BatchWindow& w = ws[i];
-            const sqy::FrameRangesBox& b = p.boxes[i];
-            sqy::Bitswap1BoxJob j;
+            sqy::Bitswap1BoxJob j{};
             j.view = dsts[i];
-            j.g = sqy::WindowGeometry{w.bY, w.bX, w.oz, w.oy, w.ox, w.Z, w.Y, w.X, vs[i].sz, vs[i].sy};
-            std::copy(b.plane, b.plane + 16, j.r.plane);
-            j.r.tail = b.tail; j.r.w0 = b.w0; j.r.w1 = b.w1; j.r.v0 = b.v0; j.r.v1 = b.v1; j.r.L = b.L;
-            j.t0 = sqy::range_first_thread(b.w0, wpt);
+            fill_range_job(j, ws[i], vs[i].sz, vs[i].sy, p.boxes[i], p.we);
             if (!sqy::bitswap1_box_job_ok(j)) return 1;
-            tj.jobs.push_back(j);
-            tj.first_tile.push_back(tj.ntiles);
-            tj.ntiles += (uint32_t)sqy::range_job_groups(b.w0, b.w1, wpt);
+            tj.push(j, range_job_groups_of(p.boxes[i], p.we));
         }
+        const uint32_t* d_tiles = nullptr;
         if (tj.upload(stream, c.cx.ws.boxes_jobs, &d_tiles)) return 1;
         SQY_TIMED(lut ? "bitswap1_quantiser_decode_boxes" : "bitswap1_decode_boxes",
                   sqy::launch_bitswap1_decode_range_windows(c.range_buf, static_cast<const sqy::Bitswap1BoxJob*>(c.cx.ws.boxes_jobs.p), d_tiles, (uint32_t)count, tj.ntiles,
@@ -2822,17 +2978,8 @@ int boxes_range_out(DecodeCall& c, WindowLaunch& l, TiledJobs<sqy::Bitswap1BoxJo
         return 0;
     }
     // plain, shuffle: box i's range in the workspace is a blob of its frames, the box begins at its first one
-    for (size_t i = 0; i < count; ++i) {
-        sqy::BatchWindow in_range = ws[i];
-        if (rank == 3) { in_range.bZ = in_range.Z; in_range.oz = 0; }
-        else if (rank == 2) { in_range.bY = in_range.Y; in_range.oy = 0; }
-        else { in_range.bX = in_range.X; in_range.ox = 0; }
-        l.add(dsts[i], c.range_buf + p.boxes[i].range_at, in_range, vs[i], false);
-    }
-    if (l.upload(stream, c.cx.ws.boxes_jobs, &d_tiles)) return 1;
-    SQY_TIMED("boxes_window_copy", sqy::launch_batch_window_copy(static_cast<const sqy::BatchWindowJob*>(c.cx.ws.boxes_jobs.p), d_tiles, (uint32_t)count, l.ntiles,
-                                                                  c.h.elem_size(), stream));
-    return 0;
+    for (size_t i = 0; i < count; ++i) l.add(dsts[i], c.range_buf + p.boxes[i].range_at, sqy::window_in_own_frames(ws[i], rank), vs[i], false);
+    return launch_boxes_copy(c.cx, stream, l, c.h.elem_size());
 }
 
 // Box i = [origins + i rank, .. + extents + i rank) of the blob into the view at d_dsts[i] (strides + i rank, or dense).  The checks of
@@ -2840,34 +2987,9 @@ int boxes_range_out(DecodeCall& c, WindowLaunch& l, TiledJobs<sqy::Bitswap1BoxJo
 int decode_boxes_on_device(Context& cx, const void* d_src_v, uint64_t srclen, size_t count, const long* origins, void* const* d_dsts, const long* extents,
                            const long* strides, unsigned rank, int want_elem, hipStream_t stream)
 {
-    const uint8_t* d_src = static_cast<const uint8_t*>(d_src_v);
-    std::vector<PendingEvent>* pend = &cx.pending;
-    DrainOnExit drain{stream, &cx.pending, cx.side};
-    sqy::HeaderInfo h;
-    if (fetch_header(d_src, srclen, stream, h)) return 1;
-    uint64_t raw_bytes = 0;
-    if (!admit_blob(h, srclen, want_elem, &raw_bytes)) return 1;
-    std::vector<sqy::BatchWindow> ws(count);
-    std::vector<WindowView> vs(count);
-    std::vector<std::pair<uint64_t, uint64_t>> ranges(count);
-    const uint64_t frame_voxels = raw_bytes / (uint64_t)want_elem / h.shape[0];
-    uint64_t copy_tiles = 0, range_groups = 0;               // what the one output launch may hold, whichever it is
-    for (size_t i = 0; i < count; ++i) {
-        const long* o = origins + i * rank;
-        const long* e = extents + i * rank;
-        if (!sqy::admit_window(h.shape, o, e, rank, &ws[i])) {
-            std::fprintf(stderr, "[sqeazy]\t decode boxes: box %zu does not lie inside the blob's shape, or has another rank\n", i);
-            return 1;
-        }
-        vs[i] = window_view(ws[i], strides ? strides + i * rank : nullptr, rank);
-        ranges[i] = {(uint64_t)o[0], (uint64_t)e[0]};
-        copy_tiles += sqy::batch_bitswap1_tiles(ws[i].Z * ws[i].Y * ws[i].X);
-        range_groups += (uint64_t)e[0] * frame_voxels / sqy::kBatchTileVoxels + 2;      // (at least range_job_groups of the box's words)
-    }
-    if (std::max(copy_tiles, range_groups) > 0x7fffffffull) {
-        std::fprintf(stderr, "[sqeazy]\t decode boxes: too many workgroups for one launch\n");
-        return 1;
-    }
+    BoxesCall b(cx, "decode boxes", d_src_v, srclen, want_elem, stream);
+    std::vector<WindowView> vs;
+    if (admit_box_windows(b, count, origins, extents, strides, rank, &vs)) return 1;
     if (sqy::decode_boxes_path(false, sqy::RangeForm::plain, false, g_opt.decode_boxes_joint.load() != 0) == sqy::BoxesPath::box_by_box) {
         for (size_t i = 0; i < count; ++i)
             if (const int rc = decode_box_on_device(cx, d_src_v, srclen, origins + i * rank, extents + i * rank, strides ? strides + i * rank : nullptr, rank, d_dsts[i],
@@ -2877,26 +2999,11 @@ int decode_boxes_on_device(Context& cx, const void* d_src_v, uint64_t srclen, si
     }
     WindowLaunch l;                                                     // (both wait for the stream before their tables go)
     TiledJobs<sqy::Bitswap1BoxJob> tj;
-    if (g_opt.decode_box_subset.load()) {
-        DecodeCall c(cx, stream, d_dsts[0], h, Pipeline::from_string(h.pipename), raw_bytes / (uint64_t)want_elem, d_src + h.size);
-        bool taken = false;
-        if (const int rc = c.frames_subset(ranges, false, &taken)) return rc;
-        if (taken) {
-            if (const int rc = boxes_range_out(c, l, tj, ws, vs, d_dsts, rank)) return rc;
-            return c.finish();
-        }
-    }
-    // sqy::BoxesPath::whole_copy: the whole volume ONCE, then all boxes in one launch
-    if (cx.ws.range_full.ensure(std::max<uint64_t>(raw_bytes, 16))) return 1;
-    if (const int rc = decode_on_device(cx, d_src_v, srclen, cx.ws.range_full.p, raw_bytes, want_elem, stream)) return rc;
-    for (size_t i = 0; i < count; ++i) l.add(d_dsts[i], cx.ws.range_full.p, ws[i], vs[i], false);
-    const uint32_t* d_tiles = nullptr;
-    if (l.upload(stream, cx.ws.boxes_jobs, &d_tiles)) return 1;
-    SQY_TIMED("boxes_window_copy", sqy::launch_batch_window_copy(static_cast<const sqy::BatchWindowJob*>(cx.ws.boxes_jobs.p), d_tiles, (uint32_t)count, l.ntiles, want_elem,
-                                                                  stream));
-    SQY_HIP(hipStreamSynchronize(stream));
-    if (g_prof_on.load()) prof_collect(cx.pending);
-    return 0;
+    return b.run(g_opt.decode_box_subset.load() != 0, d_dsts[0], [&](DecodeCall& c) { return boxes_range_out(c, l, tj, b.ws, vs, d_dsts, rank); },
+                 [&](const void* volume) {
+                     for (size_t i = 0; i < count; ++i) l.add(d_dsts[i], volume, b.ws[i], vs[i], false);
+                     return launch_boxes_copy(cx, stream, l, want_elem);
+                 });
 }
 
 // what SQYAMD_Decode_Boxes_* checks without a header, before a device is looked for: box_arguments_ok for every box
@@ -2920,29 +3027,30 @@ int decode_boxes_device(const void* d_src, long srclength, long count, const lon
                                   static_cast<hipStream_t>(hip_stream));
 }
 
+// the bytes of every box of a host variant that takes or gives the boxes' voxels dense: sqy::admit_window against the header
+bool host_box_bytes(const char* who, const sqy::HeaderInfo& h, long count, const long* origins, const long* extents, unsigned rank, int elem_size, std::vector<uint64_t>* bytes)
+{
+    bytes->resize((size_t)count);
+    return every_box((size_t)count, origins, extents, rank, [&](size_t i, const long* o, const long* e) {
+        sqy::BatchWindow w;
+        if (!sqy::admit_window(h.shape, o, e, rank, &w)) return box_refused(who, i, "does not lie inside the blob's shape");
+        (*bytes)[i] = w.Z * w.Y * w.X * (uint64_t)elem_size;
+        return true;
+    });
+}
+
 // host pointers: the header and every box are checked here, before anything is staged; the boxes come back dense, back to back in box order
 int decode_boxes_from_host(const char* src, long srclength, long count, const long* origins, const long* extents, unsigned rank, char* dst, long dst_capacity, int elem_size)
 {
     if (!dst || !boxes_arguments_ok(src, srclength, count, origins, nullptr, extents, rank)) { std::fprintf(stderr, "[sqeazy]\t decode boxes: bad arguments\n"); return 1; }
-    const sqy::HeaderInfo h = sqy::header_unpack(src, src + srclength);
-    if (!h.valid) { std::fprintf(stderr, "[sqeazy]\t unable to find a sqy header in the blob\n"); return 1; }
+    sqy::HeaderInfo h;
     uint64_t raw = 0;
-    if (!header_shape_ok(h, (uint64_t)srclength, &raw)) return 1;
-    if (h.elem_size() != elem_size) { std::fprintf(stderr, "[sqeazy]\t blob holds %s voxels\n", h.type.c_str()); return 1; }
-    std::vector<uint64_t> at((size_t)count + 1, 0);                    // (a box is no larger than the volume, count fits an int: no wrap)
-    for (long i = 0; i < count; ++i) {
-        sqy::BatchWindow w;
-        if (!sqy::admit_window(h.shape, origins + (size_t)i * rank, extents + (size_t)i * rank, rank, &w)) {
-            std::fprintf(stderr, "[sqeazy]\t decode boxes: box %ld does not lie inside the blob's shape\n", i);
-            return 1;
-        }
-        at[(size_t)i + 1] = at[(size_t)i] + w.Z * w.Y * w.X * (uint64_t)elem_size;
-    }
-    if (at.back() > (uint64_t)std::max(dst_capacity, 0l)) { std::fprintf(stderr, "[sqeazy]\t decode boxes: buffer too small\n"); return 1; }
-    return decode_staged(src, (uint64_t)srclength, dst, at.back(), [&](Context& cx, void* d_src, void* d_dst, hipStream_t stream) {
-        std::vector<void*> ptrs((size_t)count);
-        for (long i = 0; i < count; ++i) ptrs[(size_t)i] = static_cast<uint8_t*>(d_dst) + at[(size_t)i];
-        return decode_boxes_on_device(cx, d_src, (uint64_t)srclength, (size_t)count, origins, ptrs.data(), extents, nullptr, rank, elem_size, stream);
+    std::vector<uint64_t> bytes, at;
+    if (!host_header_ok(src, srclength, elem_size, &h, &raw) || !host_box_bytes("decode boxes", h, count, origins, extents, rank, elem_size, &bytes) ||
+        !host_outputs_fit("decode boxes", bytes, dst_capacity, &at))
+        return 1;
+    return boxes_staged(src, srclength, dst, at, [&](Context& cx, void* d_src, void* const* ptrs, hipStream_t stream) {
+        return decode_boxes_on_device(cx, d_src, (uint64_t)srclength, (size_t)count, origins, ptrs, extents, nullptr, rank, elem_size, stream);
     });
 }
 
@@ -2957,11 +3065,8 @@ struct CompareLaunch : TiledJobs<sqy::BatchCompareJob> {
     // blob_tiles: as WindowLaunch::add
     void add(const void* view, const void* dense, const sqy::BatchWindow& w, const WindowView& v, bool blob_tiles, unsigned long long* record)
     {
-        const sqy::WindowGeometry g{w.bY, w.bX, w.oz, w.oy, w.ox, w.Z, w.Y, w.X, v.sz, v.sy};
-        const uint64_t tile0 = blob_tiles ? sqy::window_first_tile(g, sqy::kBatchTileVoxels) : 0;
-        jobs.push_back(sqy::BatchCompareJob{view, dense, w.Z, w.Y, w.X, v.sz, v.sy, w.bZ, w.bY, w.bX, w.oz, w.oy, w.ox, tile0, record, 0});
-        first_tile.push_back(ntiles);
-        ntiles += blob_tiles ? (uint32_t)sqy::window_tile_count(g, sqy::kBatchTileVoxels) : sqy::batch_bitswap1_tiles(w.Z * w.Y * w.X);
+        const WindowTiles t = window_tiles(w, v, blob_tiles);
+        push(sqy::BatchCompareJob{view, dense, w.Z, w.Y, w.X, v.sz, v.sy, w.bZ, w.bY, w.bX, w.oz, w.oy, w.ox, t.tile0, record, 0}, t.count);
     }
 };
 // the tables to Workspace::batch_compares[kind], the launch behind them under its profile name; no jobs: nothing
@@ -2989,9 +3094,7 @@ static_assert(sizeof(sqy::BatchPatchJob) == sqy::kBatchPatchJobBytes, "the patch
 struct PatchLaunch : TiledJobs<sqy::BatchPatchJob> {
     void add(const void* view, const void* old_stream, void* new_stream, const sqy::BatchWindow& w, const WindowView& v)
     {
-        jobs.push_back(sqy::BatchPatchJob{view, old_stream, new_stream, w.Z, w.Y, w.X, v.sz, v.sy, w.bZ, w.bY, w.bX, w.oz, w.oy, w.ox});
-        first_tile.push_back(ntiles);
-        ntiles += sqy::batch_bitswap1_tiles(w.bZ * w.bY * w.bX);
+        push(sqy::BatchPatchJob{view, old_stream, new_stream, w.Z, w.Y, w.X, v.sz, v.sy, w.bZ, w.bY, w.bX, w.oz, w.oy, w.ox}, sqy::batch_bitswap1_tiles(w.bZ * w.bY * w.bX));
     }
 };
 int launch_patches(Context& cx, hipStream_t stream, PatchLaunch& l, int elem_size)
@@ -3767,10 +3870,9 @@ int compare_batch_window_device(const void* d_src, const long* offsets, const lo
 }
 
 // ---- many boxes of one large blob compared with resident voxels (SQYAMD_Compare_Boxes_*) -----------------------------------
-// decode_boxes_on_device with loads where its stores were: ONE header fetch, the LZ4 frames of all boxes' z-ranges united
-// (DecodeCall::frames_subset on the ranges), a record of eight 64-bit words per box in Workspace::batch_records made ready on the stream,
-// ONE output launch that adds into the records, ONE copy of them behind it; sqy::compare_boxes_path says what runs.  The views are only
-// read and nothing outside the workspace is written.
+// BoxesCall with loads where Decode_Boxes stores: a record of eight 64-bit words per box in Workspace::batch_records made ready on the
+// stream in front of the ONE output launch that adds into the records, ONE copy of them behind it; sqy::compare_boxes_path says what
+// runs.  The views are only read and nothing outside the workspace is written.
 static_assert(sizeof(sqy::Bitswap1BoxCompareJob) == sqy::kBitswap1BoxCompareJobBytes && sizeof(sqy::Bitswap1BoxCompareJob) % 16 == 0, "the comparing box job's layout");
 
 // one window compare under `name`, a job per box: box i (ws[i]) of the dense volume at denses[i] against its view
@@ -3792,25 +3894,16 @@ int boxes_range_compare(DecodeCall& c, CompareLaunch& l, TiledJobs<sqy::Bitswap1
     std::vector<PendingEvent>* pend = c.pend;
     const sqy::FrameRangesPlan& p = c.ranges_plan;
     const size_t count = ws.size();
-    if (p.boxes.size() != count) return 1;
     if (sqy::compare_boxes_path(true, c.range_form, true) == sqy::BoxPath::subset_transposer) {
         const uint16_t* lut = nullptr;
         if (c.range_lut(&lut)) return 1;
-        const uint32_t wpt = 128u / (8u * (uint32_t)p.we);
         for (size_t i = 0; i < count; ++i) {
-            const sqy::BatchWindow& w = ws[i];
-            const sqy::FrameRangesBox& b = p.boxes[i];
             sqy::Bitswap1BoxCompareJob j{};
             j.view = views[i];
-            j.g = sqy::WindowGeometry{w.bY, w.bX, w.oz, w.oy, w.ox, w.Z, w.Y, w.X, vs[i].sz, vs[i].sy};
-            std::copy(b.plane, b.plane + 16, j.r.plane);
-            j.r.tail = b.tail; j.r.w0 = b.w0; j.r.w1 = b.w1; j.r.v0 = b.v0; j.r.v1 = b.v1; j.r.L = b.L;
-            j.t0 = sqy::range_first_thread(b.w0, wpt);
+            fill_range_job(j, ws[i], vs[i].sz, vs[i].sy, p.boxes[i], p.we);
             j.record = d_records + sqy::kCompareFields * i;
             if (!sqy::bitswap1_box_compare_job_ok(j)) return 1;
-            tj.jobs.push_back(j);
-            tj.first_tile.push_back(tj.ntiles);
-            tj.ntiles += (uint32_t)sqy::range_job_groups(b.w0, b.w1, wpt);
+            tj.push(j, range_job_groups_of(p.boxes[i], p.we));
         }
         const uint32_t* d_tiles = nullptr;
         if (tj.upload(stream, c.cx.ws.boxes_jobs, &d_tiles)) return 1;
@@ -3819,14 +3912,9 @@ int boxes_range_compare(DecodeCall& c, CompareLaunch& l, TiledJobs<sqy::Bitswap1
                                                                     tj.ntiles, p.we, lut, stream));
         return 0;
     }
-    // plain, shuffle: box i's range in the workspace is a blob of its frames, the box begins at its first one (boxes_range_out's geometry)
-    for (size_t i = 0; i < count; ++i) {
-        sqy::BatchWindow in_range = ws[i];
-        if (rank == 3) { in_range.bZ = in_range.Z; in_range.oz = 0; }
-        else if (rank == 2) { in_range.bY = in_range.Y; in_range.oy = 0; }
-        else { in_range.bX = in_range.X; in_range.ox = 0; }
-        l.add(views[i], c.range_buf + p.boxes[i].range_at, in_range, vs[i], false, d_records + sqy::kCompareFields * i);
-    }
+    // plain, shuffle: boxes_range_out's geometry
+    for (size_t i = 0; i < count; ++i)
+        l.add(views[i], c.range_buf + p.boxes[i].range_at, sqy::window_in_own_frames(ws[i], rank), vs[i], false, d_records + sqy::kCompareFields * i);
     return launch_boxes_compare(c.cx, stream, l, "boxes_window_compare", c.h.elem_size());
 }
 
@@ -3836,71 +3924,40 @@ int boxes_range_compare(DecodeCall& c, CompareLaunch& l, TiledJobs<sqy::Bitswap1
 int compare_boxes_on_device(Context& cx, const void* d_src_v, uint64_t srclen, size_t count, const long* origins, const void* const* d_views, const long* extents,
                             const long* strides, unsigned rank, int want_elem, hipStream_t stream, unsigned long long* stats)
 {
-    const uint8_t* d_src = static_cast<const uint8_t*>(d_src_v);
     std::vector<PendingEvent>* pend = &cx.pending;
-    DrainOnExit drain{stream, &cx.pending, cx.side};
-    sqy::HeaderInfo h;
-    if (fetch_header(d_src, srclen, stream, h)) return 1;
-    uint64_t raw_bytes = 0;
-    if (!admit_blob(h, srclen, want_elem, &raw_bytes)) return 1;
-    std::vector<sqy::BatchWindow> ws(count);
-    std::vector<WindowView> vs(count);
-    std::vector<std::pair<uint64_t, uint64_t>> ranges(count);
-    const uint64_t frame_voxels = raw_bytes / (uint64_t)want_elem / h.shape[0];
-    uint64_t copy_tiles = 0, range_groups = 0;               // what the one output launch may hold, whichever it is
-    for (size_t i = 0; i < count; ++i) {
-        const long* o = origins + i * rank;
-        const long* e = extents + i * rank;
-        if (!sqy::admit_window(h.shape, o, e, rank, &ws[i])) {
-            std::fprintf(stderr, "[sqeazy]\t compare boxes: box %zu does not lie inside the blob's shape, or has another rank\n", i);
-            return 1;
-        }
-        vs[i] = window_view(ws[i], strides ? strides + i * rank : nullptr, rank);
-        ranges[i] = {(uint64_t)o[0], (uint64_t)e[0]};
-        copy_tiles += sqy::batch_bitswap1_tiles(ws[i].Z * ws[i].Y * ws[i].X);
-        range_groups += (uint64_t)e[0] * frame_voxels / sqy::kBatchTileVoxels + 2;      // (at least range_job_groups of the box's words)
-    }
-    if (std::max(copy_tiles, range_groups) > 0x7fffffffull) {
-        std::fprintf(stderr, "[sqeazy]\t compare boxes: too many workgroups for one launch\n");
-        return 1;
-    }
+    BoxesCall b(cx, "compare boxes", d_src_v, srclen, want_elem, stream);
+    std::vector<WindowView> vs;
+    if (admit_box_windows(b, count, origins, extents, strides, rank, &vs)) return 1;
     const size_t words = count * sqy::kCompareFields;
     if (cx.ws.batch_records.ensure(words * 8)) return 1;
     unsigned long long* d_records = static_cast<unsigned long long*>(cx.ws.batch_records.p);
     std::vector<unsigned long long> host(words);
     CompareLaunch l;                                                    // (both wait for the stream before their tables go)
     TiledJobs<sqy::Bitswap1BoxCompareJob> tj;
-    // the rows behind the call's last synchronisation: the records with VOXELS filled in, or all ones where the decode failed (rc)
-    auto rows = [&](int rc) {
-        for (size_t i = 0; i < count; ++i) {
-            unsigned long long* row = stats + i * sqy::kCompareFields;
-            if (rc) { std::fill(row, row + sqy::kCompareFields, ~0ull); continue; }
-            std::copy(host.begin() + i * sqy::kCompareFields, host.begin() + (i + 1) * sqy::kCompareFields, row);
-            row[0] = ws[i].Z * ws[i].Y * ws[i].X;
-        }
-        return rc;
+    // the records made ready in front of `compare`, their copy to the host behind it -- in front of the call's last synchronisation
+    auto records_around = [&](auto&& compare) -> int {
+        SQY_TIMED("batch_compare_init", sqy::launch_batch_compare_init(d_records, (uint32_t)count, stream));
+        if (const int rc = compare()) return rc;
+        SQY_HIP(hipMemcpyAsync(host.data(), d_records, words * 8, hipMemcpyDeviceToHost, stream));
+        return 0;
     };
-    if (g_opt.compare_boxes_subset.load()) {
-        DecodeCall c(cx, stream, nullptr, h, Pipeline::from_string(h.pipename), raw_bytes / (uint64_t)want_elem, d_src + h.size);
-        bool taken = false;
-        if (const int rc = c.frames_subset(ranges, false, &taken)) return rc;
-        if (taken) {
-            SQY_TIMED("batch_compare_init", sqy::launch_batch_compare_init(d_records, (uint32_t)count, stream));
-            if (const int rc = boxes_range_compare(c, l, tj, ws, vs, d_views, rank, d_records)) return rc;
-            SQY_HIP(hipMemcpyAsync(host.data(), d_records, words * 8, hipMemcpyDeviceToHost, stream));
-            return rows(c.finish());
-        }
+    const int rc = b.run(g_opt.compare_boxes_subset.load() != 0, nullptr,
+                         [&](DecodeCall& c) { return records_around([&] { return boxes_range_compare(c, l, tj, b.ws, vs, d_views, rank, d_records); }); },
+                         [&](const void* volume) {
+                             return records_around([&] {
+                                 for (size_t i = 0; i < count; ++i) l.add(d_views[i], volume, b.ws[i], vs[i], false, d_records + sqy::kCompareFields * i);
+                                 return launch_boxes_compare(cx, stream, l, "boxes_window_compare", want_elem);
+                             });
+                         });
+    if (!b.verdict) return rc;
+    // the rows behind the call's last synchronisation: the records with VOXELS filled in, or all ones where the decode failed
+    for (size_t i = 0; i < count; ++i) {
+        unsigned long long* row = stats + i * sqy::kCompareFields;
+        if (rc) { std::fill(row, row + sqy::kCompareFields, ~0ull); continue; }
+        std::copy(host.begin() + i * sqy::kCompareFields, host.begin() + (i + 1) * sqy::kCompareFields, row);
+        row[0] = b.ws[i].Z * b.ws[i].Y * b.ws[i].X;
     }
-    // sqy::BoxPath::whole_copy: the whole volume ONCE, then all boxes in one launch
-    if (cx.ws.range_full.ensure(std::max<uint64_t>(raw_bytes, 16))) return 1;
-    if (const int rc = decode_on_device(cx, d_src_v, srclen, cx.ws.range_full.p, raw_bytes, want_elem, stream)) return rows(rc);
-    SQY_TIMED("batch_compare_init", sqy::launch_batch_compare_init(d_records, (uint32_t)count, stream));
-    for (size_t i = 0; i < count; ++i) l.add(d_views[i], cx.ws.range_full.p, ws[i], vs[i], false, d_records + sqy::kCompareFields * i);
-    if (launch_boxes_compare(cx, stream, l, "boxes_window_compare", want_elem)) return 1;
-    SQY_HIP(hipMemcpyAsync(host.data(), d_records, words * 8, hipMemcpyDeviceToHost, stream));
-    SQY_HIP(hipStreamSynchronize(stream));
-    if (g_prof_on.load()) prof_collect(cx.pending);
-    return rows(0);
+    return rc;
 }
 
 // SQYAMD_Compare_Boxes_*_Device: decode_boxes_device's checks with the views read-only; stats zeroed on every refusal
@@ -3921,27 +3978,20 @@ int compare_boxes_device(const void* d_src, long srclength, long count, const lo
 }
 
 // host pointers: the header and every box are checked here, before anything is staged; views: the boxes' voxels dense, back to back in
-// box order, exactly views_bytes of them.  The blob and the views are staged once each
+// box order, exactly views_bytes of them.  The blob and the views are staged once each: two inputs, so the staging is its own
 int compare_boxes_from_host(const char* src, long srclength, long count, const long* origins, const long* extents, unsigned rank, const char* views, long views_bytes,
                             unsigned long long* stats, int elem_size)
 {
     if (stats && count > 0 && count <= INT_MAX) std::fill(stats, stats + (size_t)count * sqy::kCompareFields, 0ull);
     if (!stats || !views || !boxes_arguments_ok(src, srclength, count, origins, nullptr, extents, rank)) { std::fprintf(stderr, "[sqeazy]\t compare boxes: bad arguments\n"); return 1; }
-    const sqy::HeaderInfo h = sqy::header_unpack(src, src + srclength);
-    if (!h.valid) { std::fprintf(stderr, "[sqeazy]\t unable to find a sqy header in the blob\n"); return 1; }
+    sqy::HeaderInfo h;
     uint64_t raw = 0;
-    if (!header_shape_ok(h, (uint64_t)srclength, &raw)) return 1;
-    if (h.elem_size() != elem_size) { std::fprintf(stderr, "[sqeazy]\t blob holds %s voxels\n", h.type.c_str()); return 1; }
-    std::vector<uint64_t> at((size_t)count + 1, 0);                    // (a box is no larger than the volume, count fits an int: no wrap)
-    for (long i = 0; i < count; ++i) {
-        sqy::BatchWindow w;
-        if (!sqy::admit_window(h.shape, origins + (size_t)i * rank, extents + (size_t)i * rank, rank, &w)) {
-            std::fprintf(stderr, "[sqeazy]\t compare boxes: box %ld does not lie inside the blob's shape\n", i);
-            return 1;
-        }
-        at[(size_t)i + 1] = at[(size_t)i] + w.Z * w.Y * w.X * (uint64_t)elem_size;
+    std::vector<uint64_t> bytes, at;
+    if (!host_header_ok(src, srclength, elem_size, &h, &raw) || !host_box_bytes("compare boxes", h, count, origins, extents, rank, elem_size, &bytes)) return 1;
+    if (!sqy::output_offsets(bytes, views_bytes, &at) || at.back() != (uint64_t)views_bytes) {
+        std::fprintf(stderr, "[sqeazy]\t compare boxes: the views hold another number of bytes than the boxes\n");
+        return 1;
     }
-    if (views_bytes < 0 || at.back() != (uint64_t)views_bytes) { std::fprintf(stderr, "[sqeazy]\t compare boxes: the views hold another number of bytes than the boxes\n"); return 1; }
     if (!device_present()) { std::fprintf(stderr, "[sqeazy]\t no MI355X (HIP device) visible: sqeazy_amd has no CPU path\n"); return 1; }
     ContextLease lease;
     if (!lease.ctx) { std::fprintf(stderr, "[sqeazy]\t no usable HIP device\n"); return 1; }
@@ -3962,18 +4012,17 @@ int compare_boxes_from_host(const char* src, long srclength, long count, const l
 }
 
 // ---- many boxes of one large blob projected along an axis (SQYAMD_Project_Boxes_*) -----------------------------------------
-// compare_boxes_on_device with another sink: ONE header fetch, the LZ4 frames of all boxes' z-ranges united (DecodeCall::frames_subset on
-// the ranges), ONE output launch that combines into the images; sqy::project_boxes_path says what runs and sqy::admit_projection what is
-// admitted.  Nothing but the images' elements is written outside the workspace.
+// BoxesCall with a combine into images of rank - 1 as its sink; sqy::project_boxes_path says what runs and sqy::admit_projection what is
+// admitted.  Its own: the neutral-element launch in front of the atomics, and the walk form without either.  Nothing but the images'
+// elements is written outside the workspace.
 static_assert(sizeof(sqy::Bitswap1BoxProjectJob) == sqy::kBitswap1BoxProjectJobBytes && sizeof(sqy::BoxProjectJob) == sqy::kBoxProjectJobBytes, "the projecting jobs' layout");
 
 // the thread-per-element projection's jobs: box i (w, its projection q) of the dense volume at `dense` into the image at `out`
 struct ProjectLaunch : TiledJobs<sqy::BoxProjectJob> {
     void add(void* out, const void* dense, const sqy::BatchWindow& w, const sqy::Projection& q, int op)
     {
-        jobs.push_back(sqy::BoxProjectJob{dense, out, (w.oz * w.bY + w.oy) * w.bX + w.ox, q.E0, q.E1, q.p0, q.su, q.sv, q.sa, q.n, (uint32_t)op, 0, 0});
-        first_tile.push_back(ntiles);
-        ntiles += (uint32_t)((q.E0 * q.E1 + 255) / 256);
+        push(sqy::BoxProjectJob{dense, out, (w.oz * w.bY + w.oy) * w.bX + w.ox, q.E0, q.E1, q.p0, q.su, q.sv, q.sa, q.n, (uint32_t)op, 0, 0},
+             (uint32_t)((q.E0 * q.E1 + 255) / 256));
     }
 };
 int launch_boxes_project(Context& cx, hipStream_t stream, ProjectLaunch& l, int elem_size)
@@ -3994,27 +4043,21 @@ int boxes_range_project(DecodeCall& c, ProjectLaunch& l, TiledJobs<sqy::Bitswap1
     std::vector<PendingEvent>* pend = c.pend;
     const sqy::FrameRangesPlan& p = c.ranges_plan;
     const size_t count = ws.size();
-    if (p.boxes.size() != count) return 1;
     if (sqy::project_boxes_path(true, c.range_form, true) == sqy::BoxPath::subset_transposer) {
         const uint16_t* lut = nullptr;
         if (c.range_lut(&lut)) return 1;
-        const uint32_t wpt = 128u / (8u * (uint32_t)p.we);
         for (size_t i = 0; i < count; ++i) {
-            const sqy::BatchWindow& w = ws[i];
             const sqy::Projection& q = qs[i];
-            const sqy::FrameRangesBox& b = p.boxes[i];
             sqy::Bitswap1BoxProjectJob j{};
             j.out = outs[i];
-            j.g = sqy::WindowGeometry{w.bY, w.bX, w.oz, w.oy, w.ox, w.Z, w.Y, w.X, q.sz, q.sy};
-            std::copy(b.plane, b.plane + 16, j.r.plane);
-            j.r.tail = b.tail; j.r.w0 = b.w0; j.r.w1 = b.w1; j.r.v0 = b.v0; j.r.v1 = b.v1; j.r.L = b.L;
-            j.t0 = sqy::range_first_thread(b.w0, wpt);
+            fill_range_job(j, ws[i], q.sz, q.sy, p.boxes[i], p.we);
             j.op = (uint32_t)op; j.axis = q.axis3;
             j.E0 = q.E0; j.E1 = q.E1; j.p0 = q.p0;
             if (!sqy::bitswap1_box_project_job_ok(j)) return 1;
             tj.jobs.push_back(j);
         }
-        // the form: axis 0 with every job on the 32-voxel grid walks z in registers and stores once; else the atomics
+        // the form: axis 0 with every job on the 32-voxel grid walks z in registers and stores once; else the atomics.  The
+        // jobs' workgroups depend on it: counted behind the decision
         bool walk = g_opt.project_boxes_walk.load() != 0 && reinterpret_cast<uintptr_t>(c.range_buf) % 4u == 0;
         uint64_t walk_groups = 0;
         for (size_t i = 0; walk && i < count; ++i) {
@@ -4024,7 +4067,7 @@ int boxes_range_project(DecodeCall& c, ProjectLaunch& l, TiledJobs<sqy::Bitswap1
         walk = walk && walk_groups <= 0x7fffffffull;
         for (size_t i = 0; i < count; ++i) {
             tj.first_tile.push_back(tj.ntiles);
-            tj.ntiles += (uint32_t)(walk ? sqy::project_walk_groups(tj.jobs[i].g) : sqy::range_job_groups(p.boxes[i].w0, p.boxes[i].w1, wpt));
+            tj.ntiles += walk ? (uint32_t)sqy::project_walk_groups(tj.jobs[i].g) : range_job_groups_of(p.boxes[i], p.we);
         }
         const uint32_t* d_tiles = nullptr;
         if (tj.upload(stream, c.cx.ws.boxes_jobs, &d_tiles)) return 1;
@@ -4039,14 +4082,8 @@ int boxes_range_project(DecodeCall& c, ProjectLaunch& l, TiledJobs<sqy::Bitswap1
                   sqy::launch_bitswap1_decode_range_windows_project(c.range_buf, d_jobs, d_tiles, (uint32_t)count, tj.ntiles, p.we, lut, stream));
         return 0;
     }
-    // plain, shuffle: box i's range in the workspace is a blob of its frames, the box begins at its first one (boxes_range_out's geometry)
-    for (size_t i = 0; i < count; ++i) {
-        sqy::BatchWindow in_range = ws[i];
-        if (rank == 3) { in_range.bZ = in_range.Z; in_range.oz = 0; }
-        else if (rank == 2) { in_range.bY = in_range.Y; in_range.oy = 0; }
-        else { in_range.bX = in_range.X; in_range.ox = 0; }
-        l.add(outs[i], c.range_buf + p.boxes[i].range_at, in_range, qs[i], op);
-    }
+    // plain, shuffle: boxes_range_out's geometry
+    for (size_t i = 0; i < count; ++i) l.add(outs[i], c.range_buf + p.boxes[i].range_at, sqy::window_in_own_frames(ws[i], rank), qs[i], op);
     return launch_boxes_project(c.cx, stream, l, c.h.elem_size());
 }
 
@@ -4055,72 +4092,36 @@ int boxes_range_project(DecodeCall& c, ProjectLaunch& l, TiledJobs<sqy::Bitswap1
 int project_boxes_on_device(Context& cx, const void* d_src_v, uint64_t srclen, size_t count, const long* origins, const long* extents, unsigned rank, int axis, int op,
                             void* const* d_outs, const long* out_strides, int want_elem, hipStream_t stream)
 {
-    const uint8_t* d_src = static_cast<const uint8_t*>(d_src_v);
-    DrainOnExit drain{stream, &cx.pending, cx.side};
-    sqy::HeaderInfo h;
-    if (fetch_header(d_src, srclen, stream, h)) return 1;
-    uint64_t raw_bytes = 0;
-    if (!admit_blob(h, srclen, want_elem, &raw_bytes)) return 1;
-    std::vector<sqy::BatchWindow> ws(count);
+    BoxesCall b(cx, "project boxes", d_src_v, srclen, want_elem, stream);
     std::vector<sqy::Projection> qs(count);
-    std::vector<std::pair<uint64_t, uint64_t>> ranges(count);
-    const uint64_t frame_voxels = raw_bytes / (uint64_t)want_elem / h.shape[0];
-    uint64_t element_groups = 0, range_groups = 0;           // what the one output launch may hold, whichever it is
-    for (size_t i = 0; i < count; ++i) {
-        const long* o = origins + i * rank;
-        const long* e = extents + i * rank;
-        if (!sqy::admit_projection(h.shape, o, e, rank, axis, op, want_elem == 2 ? 65535u : 255u, d_outs[i], out_strides ? out_strides + i * (rank - 1) : nullptr, &ws[i],
-                                   &qs[i])) {
-            std::fprintf(stderr, "[sqeazy]\t project boxes: box %zu does not lie inside the blob's shape or has another rank, or its sum might not fit 32 bits\n", i);
-            return 1;
-        }
-        ranges[i] = {(uint64_t)o[0], (uint64_t)e[0]};
-        element_groups += (qs[i].E0 * qs[i].E1 + 255) / 256;
-        range_groups += (uint64_t)e[0] * frame_voxels / sqy::kBatchTileVoxels + 2;      // (at least range_job_groups of the box's words)
-    }
-    if (std::max(element_groups, range_groups) > 0x7fffffffull) {
-        std::fprintf(stderr, "[sqeazy]\t project boxes: too many workgroups for one launch\n");
-        return 1;
-    }
+    const int refused = b.admit(count, origins, extents, rank, [&](size_t i, const long* o, const long* e, sqy::BatchWindow* w, uint64_t* element_groups) {
+        if (!sqy::admit_projection(b.h.shape, o, e, rank, axis, op, voxel_max(want_elem), d_outs[i], out_strides ? out_strides + i * (rank - 1) : nullptr, w, &qs[i]))
+            return box_refused(b.who, i, "does not lie inside the blob's shape or has another rank, or its sum might not fit 32 bits");
+        *element_groups = (qs[i].E0 * qs[i].E1 + 255) / 256;
+        return true;
+    });
+    if (refused || !b.one_launch_holds()) return 1;
     ProjectLaunch l;                                                    // (both wait for the stream before their tables go)
     TiledJobs<sqy::Bitswap1BoxProjectJob> tj;
-    if (g_opt.project_boxes_subset.load()) {
-        DecodeCall c(cx, stream, nullptr, h, Pipeline::from_string(h.pipename), raw_bytes / (uint64_t)want_elem, d_src + h.size);
-        bool taken = false;
-        if (const int rc = c.frames_subset(ranges, false, &taken)) return rc;
-        if (taken) {
-            if (const int rc = boxes_range_project(c, l, tj, ws, qs, d_outs, rank, op)) return rc;
-            return c.finish();
-        }
-    }
-    // sqy::BoxPath::whole_copy: the whole volume ONCE, then all boxes in one launch
-    if (cx.ws.range_full.ensure(std::max<uint64_t>(raw_bytes, 16))) return 1;
-    if (const int rc = decode_on_device(cx, d_src_v, srclen, cx.ws.range_full.p, raw_bytes, want_elem, stream)) return rc;
-    for (size_t i = 0; i < count; ++i) l.add(d_outs[i], cx.ws.range_full.p, ws[i], qs[i], op);
-    if (launch_boxes_project(cx, stream, l, want_elem)) return 1;
-    SQY_HIP(hipStreamSynchronize(stream));
-    if (g_prof_on.load()) prof_collect(cx.pending);
-    return 0;
+    return b.run(g_opt.project_boxes_subset.load() != 0, nullptr, [&](DecodeCall& c) { return boxes_range_project(c, l, tj, b.ws, qs, d_outs, rank, op); },
+                 [&](const void* volume) {
+                     for (size_t i = 0; i < count; ++i) l.add(d_outs[i], volume, b.ws[i], qs[i], op);
+                     return launch_boxes_project(cx, stream, l, want_elem);
+                 });
 }
 
 // what SQYAMD_Project_Boxes_* checks without a header, before a device is looked for: boxes_arguments_ok, and sqy::admit_projection of
-// every box against the smallest shape that holds it -- the axis, the op, the image's pointer and pitches, the sum bound
+// every box in its own shape -- the axis, the op, the image's pointer and pitches, the sum bound
 bool project_arguments_ok(const void* src, long srclength, long count, const long* origins, const long* extents, unsigned rank, int axis, int op, void* const* outs,
                           const long* out_strides, int elem_size)
 {
     if (!boxes_arguments_ok(src, srclength, count, origins, outs, extents, rank)) return false;
-    for (long i = 0; i < count; ++i) {
-        const long* o = origins + (size_t)i * rank;
-        const long* e = extents + (size_t)i * rank;
-        std::vector<uint64_t> shape(rank);
-        for (unsigned k = 0; k < rank; ++k) shape[k] = (uint64_t)o[k] + (uint64_t)std::max(e[k], 0l);     // (both below 2^63: no wrap)
+    return every_box_in_its_own_shape(count, origins, extents, rank, [&](size_t i, const std::vector<uint64_t>& shape, const long* o, const long* e) {
         sqy::BatchWindow w;
         sqy::Projection q;
         const void* out = outs ? outs[i] : static_cast<const void*>(&q);                                   // (host variant: the images are the library's)
-        if (!sqy::admit_projection(shape, o, e, rank, axis, op, elem_size == 2 ? 65535u : 255u, out, outs && out_strides ? out_strides + (size_t)i * (rank - 1) : nullptr, &w, &q))
-            return false;
-    }
-    return true;
+        return sqy::admit_projection(shape, o, e, rank, axis, op, voxel_max(elem_size), out, outs && out_strides ? out_strides + i * (rank - 1) : nullptr, &w, &q);
+    });
 }
 
 int project_boxes_device(const void* d_src, long srclength, long count, const long* origins, const long* extents, unsigned rank, int axis, int op, void* const* d_outs,
@@ -4145,44 +4146,37 @@ int project_boxes_from_host(const char* src, long srclength, long count, const l
         std::fprintf(stderr, "[sqeazy]\t project boxes: bad arguments\n");
         return 1;
     }
-    const sqy::HeaderInfo h = sqy::header_unpack(src, src + srclength);
-    if (!h.valid) { std::fprintf(stderr, "[sqeazy]\t unable to find a sqy header in the blob\n"); return 1; }
+    sqy::HeaderInfo h;
     uint64_t raw = 0;
-    if (!header_shape_ok(h, (uint64_t)srclength, &raw)) return 1;
-    if (h.elem_size() != elem_size) { std::fprintf(stderr, "[sqeazy]\t blob holds %s voxels\n", h.type.c_str()); return 1; }
-    std::vector<uint64_t> at((size_t)count + 1, 0);                    // (an image is no larger than the volume, count fits an int: no wrap)
-    for (long i = 0; i < count; ++i) {
+    if (!host_header_ok(src, srclength, elem_size, &h, &raw)) return 1;
+    std::vector<uint64_t> bytes((size_t)count), at;
+    const bool admitted = every_box((size_t)count, origins, extents, rank, [&](size_t i, const long* o, const long* e) {
         sqy::BatchWindow w;
         sqy::Projection q;
-        if (!sqy::admit_projection(h.shape, origins + (size_t)i * rank, extents + (size_t)i * rank, rank, axis, op, elem_size == 2 ? 65535u : 255u, &q, nullptr, &w, &q)) {
-            std::fprintf(stderr, "[sqeazy]\t project boxes: box %ld does not lie inside the blob's shape, or its sum might not fit 32 bits\n", i);
-            return 1;
-        }
-        at[(size_t)i + 1] = at[(size_t)i] + q.E0 * q.E1 * 4u;
-    }
-    if (at.back() > (uint64_t)std::max(out_capacity, 0l)) { std::fprintf(stderr, "[sqeazy]\t project boxes: buffer too small\n"); return 1; }
-    return decode_staged(src, (uint64_t)srclength, out, at.back(), [&](Context& cx, void* d_src, void* d_dst, hipStream_t stream) {
-        std::vector<void*> ptrs((size_t)count);
-        for (long i = 0; i < count; ++i) ptrs[(size_t)i] = static_cast<uint8_t*>(d_dst) + at[(size_t)i];
-        return project_boxes_on_device(cx, d_src, (uint64_t)srclength, (size_t)count, origins, extents, rank, axis, op, ptrs.data(), nullptr, elem_size, stream);
+        if (!sqy::admit_projection(h.shape, o, e, rank, axis, op, voxel_max(elem_size), &q, nullptr, &w, &q))
+            return box_refused("project boxes", i, "does not lie inside the blob's shape, or its sum might not fit 32 bits");
+        bytes[i] = q.E0 * q.E1 * 4u;
+        return true;
+    });
+    if (!admitted || !host_outputs_fit("project boxes", bytes, out_capacity, &at)) return 1;
+    return boxes_staged(src, srclength, out, at, [&](Context& cx, void* d_src, void* const* ptrs, hipStream_t stream) {
+        return project_boxes_on_device(cx, d_src, (uint64_t)srclength, (size_t)count, origins, extents, rank, axis, op, ptrs, nullptr, elem_size, stream);
     });
 }
 
 // ---- many boxes of one large blob read at a coarser resolution (SQYAMD_Bin_Boxes_*) -----------------------------------------
-// project_boxes_on_device with cells for image elements: ONE header fetch, the LZ4 frames of all boxes' z-ranges united, ONE output
-// launch; sqy::bin_boxes_path says what runs, sqy::admit_binning what is admitted and sqy::bin_boxes_plan how the bit-plane kernel's
-// workgroups share a box's cells.  No neutral-element launch, no global atomics.  Nothing but the outputs' cells is written outside
-// the workspace.
+// BoxesCall with cells as its sink; sqy::bin_boxes_path says what runs, sqy::admit_binning what is admitted and sqy::bin_boxes_plan how
+// the bit-plane kernel's workgroups share a box's cells.  Its own: the launches' sizes are the cells' and the plan's blocks, checked box
+// by box.  No neutral-element launch, no global atomics.  Nothing but the outputs' cells is written outside the workspace.
 static_assert(sizeof(sqy::Bitswap1BoxBinJob) == sqy::kBitswap1BoxBinJobBytes && sizeof(sqy::BoxBinJob) == sqy::kBoxBinJobBytes, "the binning jobs' layout");
 
 // the thread-per-cell launch's jobs: box i (w, its binning q) of the dense volume at `dense` into the output at `out`
 struct BinLaunch : TiledJobs<sqy::BoxBinJob> {
     void add(void* out, const void* dense, const sqy::BatchWindow& w, const sqy::Binning& q, int op)
     {
-        jobs.push_back(sqy::BoxBinJob{dense, out, (w.oz * w.bY + w.oy) * w.bX + w.ox, w.bY * w.bX, w.bX, {w.Z, w.Y, w.X}, {q.bins[0], q.bins[1], q.bins[2]},
-                                      {q.C[0], q.C[1], q.C[2]}, q.pz, q.py, (uint32_t)op, 0, 0});
-        first_tile.push_back(ntiles);
-        ntiles += (uint32_t)((q.C[0] * q.C[1] * q.C[2] + 255) / 256);
+        push(sqy::BoxBinJob{dense, out, (w.oz * w.bY + w.oy) * w.bX + w.ox, w.bY * w.bX, w.bX, {w.Z, w.Y, w.X}, {q.bins[0], q.bins[1], q.bins[2]},
+                            {q.C[0], q.C[1], q.C[2]}, q.pz, q.py, (uint32_t)op, 0, 0},
+             (uint32_t)((q.C[0] * q.C[1] * q.C[2] + 255) / 256));
     }
 };
 int launch_boxes_bin(Context& cx, hipStream_t stream, BinLaunch& l, int elem_size)
@@ -4202,28 +4196,20 @@ int boxes_range_bin(DecodeCall& c, BinLaunch& l, TiledJobs<sqy::Bitswap1BoxBinJo
     std::vector<PendingEvent>* pend = c.pend;
     const sqy::FrameRangesPlan& p = c.ranges_plan;
     const size_t count = ws.size();
-    if (p.boxes.size() != count) return 1;
     if (sqy::bin_boxes_path(true, c.range_form, true) == sqy::BoxPath::subset_transposer) {
         const uint16_t* lut = nullptr;
         if (c.range_lut(&lut)) return 1;
         for (size_t i = 0; i < count; ++i) {
-            const sqy::BatchWindow& w = ws[i];
             const sqy::Binning& q = qs[i];
-            const sqy::FrameRangesBox& b = p.boxes[i];
             sqy::Bitswap1BoxBinJob j{};
             j.out = outs[i];
-            j.g = sqy::WindowGeometry{w.bY, w.bX, w.oz, w.oy, w.ox, w.Z, w.Y, w.X, q.pz, q.py};
-            std::copy(b.plane, b.plane + 16, j.r.plane);
-            j.r.tail = b.tail; j.r.w0 = b.w0; j.r.w1 = b.w1; j.r.v0 = b.v0; j.r.v1 = b.v1; j.r.L = b.L;
-            j.t0 = sqy::range_first_thread(b.w0, 128u / (8u * (uint32_t)p.we));
+            fill_range_job(j, ws[i], q.pz, q.py, p.boxes[i], p.we);
             std::copy(q.bins, q.bins + 3, j.bins);
-            j.plan = sqy::bin_boxes_plan(q.C, q.bins, w.X);
+            j.plan = sqy::bin_boxes_plan(q.C, q.bins, ws[i].X);
             j.op = (uint32_t)op;
             j.zreg = sqy::bitswap1_box_bin_zreg_ok(j) ? 1u : 0u;
             if (!sqy::bitswap1_box_bin_job_ok(j) || (uint64_t)tj.ntiles + j.plan.blocks > 0x7fffffffull) return 1;
-            tj.jobs.push_back(j);
-            tj.first_tile.push_back(tj.ntiles);
-            tj.ntiles += (uint32_t)j.plan.blocks;
+            tj.push(j, (uint32_t)j.plan.blocks);
         }
         const uint32_t* d_tiles = nullptr;
         if (tj.upload(stream, c.cx.ws.boxes_jobs, &d_tiles)) return 1;
@@ -4232,14 +4218,8 @@ int boxes_range_bin(DecodeCall& c, BinLaunch& l, TiledJobs<sqy::Bitswap1BoxBinJo
                                                                 p.we, lut, stream));
         return 0;
     }
-    // plain, shuffle: box i's range in the workspace is a blob of its frames, the box begins at its first one (boxes_range_out's geometry)
-    for (size_t i = 0; i < count; ++i) {
-        sqy::BatchWindow in_range = ws[i];
-        if (rank == 3) { in_range.bZ = in_range.Z; in_range.oz = 0; }
-        else if (rank == 2) { in_range.bY = in_range.Y; in_range.oy = 0; }
-        else { in_range.bX = in_range.X; in_range.ox = 0; }
-        l.add(outs[i], c.range_buf + p.boxes[i].range_at, in_range, qs[i], op);
-    }
+    // plain, shuffle: boxes_range_out's geometry
+    for (size_t i = 0; i < count; ++i) l.add(outs[i], c.range_buf + p.boxes[i].range_at, sqy::window_in_own_frames(ws[i], rank), qs[i], op);
     return launch_boxes_bin(c.cx, stream, l, c.h.elem_size());
 }
 
@@ -4248,70 +4228,38 @@ int boxes_range_bin(DecodeCall& c, BinLaunch& l, TiledJobs<sqy::Bitswap1BoxBinJo
 int bin_boxes_on_device(Context& cx, const void* d_src_v, uint64_t srclen, size_t count, const long* origins, const long* extents, unsigned rank, const long* bins, int op,
                         void* const* d_outs, const long* out_strides, int want_elem, hipStream_t stream)
 {
-    const uint8_t* d_src = static_cast<const uint8_t*>(d_src_v);
-    DrainOnExit drain{stream, &cx.pending, cx.side};
-    sqy::HeaderInfo h;
-    if (fetch_header(d_src, srclen, stream, h)) return 1;
-    uint64_t raw_bytes = 0;
-    if (!admit_blob(h, srclen, want_elem, &raw_bytes)) return 1;
-    std::vector<sqy::BatchWindow> ws(count);
+    BoxesCall b(cx, "bin boxes", d_src_v, srclen, want_elem, stream);
     std::vector<sqy::Binning> qs(count);
-    std::vector<std::pair<uint64_t, uint64_t>> ranges(count);
     uint64_t cell_groups = 0, blocks = 0;                    // what the one output launch may hold, whichever it is
-    for (size_t i = 0; i < count; ++i) {
-        const long* o = origins + i * rank;
-        const long* e = extents + i * rank;
-        if (!sqy::admit_binning(h.shape, o, e, rank, bins, op, want_elem == 2 ? 65535u : 255u, d_outs[i], out_strides ? out_strides + i * rank : nullptr, &ws[i], &qs[i])) {
-            std::fprintf(stderr, "[sqeazy]\t bin boxes: box %zu does not lie inside the blob's shape or has another rank, or a cell's sum might not fit 32 bits\n", i);
-            return 1;
-        }
-        ranges[i] = {(uint64_t)o[0], (uint64_t)e[0]};
+    const int refused = b.admit(count, origins, extents, rank, [&](size_t i, const long* o, const long* e, sqy::BatchWindow* w, uint64_t*) {
+        if (!sqy::admit_binning(b.h.shape, o, e, rank, bins, op, voxel_max(want_elem), d_outs[i], out_strides ? out_strides + i * rank : nullptr, w, &qs[i]))
+            return box_refused(b.who, i, "does not lie inside the blob's shape or has another rank, or a cell's sum might not fit 32 bits");
         cell_groups += (qs[i].C[0] * qs[i].C[1] * qs[i].C[2] + 255) / 256;           // (the cells are no more than the blob's voxels: no wrap)
-        blocks += sqy::bin_boxes_plan(qs[i].C, qs[i].bins, ws[i].X).blocks;
-        if (std::max(cell_groups, blocks) > 0x7fffffffull) {             // (checked box by box: the sums stay far below 2^64)
-            std::fprintf(stderr, "[sqeazy]\t bin boxes: too many workgroups for one launch\n");
-            return 1;
-        }
-    }
+        blocks += sqy::bin_boxes_plan(qs[i].C, qs[i].bins, w->X).blocks;
+        return b.launch_holds(std::max(cell_groups, blocks));             // (checked box by box: the sums stay far below 2^64)
+    });
+    if (refused) return 1;
     BinLaunch l;                                                        // (both wait for the stream before their tables go)
     TiledJobs<sqy::Bitswap1BoxBinJob> tj;
-    if (g_opt.bin_boxes_subset.load()) {
-        DecodeCall c(cx, stream, nullptr, h, Pipeline::from_string(h.pipename), raw_bytes / (uint64_t)want_elem, d_src + h.size);
-        bool taken = false;
-        if (const int rc = c.frames_subset(ranges, false, &taken)) return rc;
-        if (taken) {
-            if (const int rc = boxes_range_bin(c, l, tj, ws, qs, d_outs, rank, op)) return rc;
-            return c.finish();
-        }
-    }
-    // sqy::BoxPath::whole_copy: the whole volume ONCE, then all boxes in one launch
-    if (cx.ws.range_full.ensure(std::max<uint64_t>(raw_bytes, 16))) return 1;
-    if (const int rc = decode_on_device(cx, d_src_v, srclen, cx.ws.range_full.p, raw_bytes, want_elem, stream)) return rc;
-    for (size_t i = 0; i < count; ++i) l.add(d_outs[i], cx.ws.range_full.p, ws[i], qs[i], op);
-    if (launch_boxes_bin(cx, stream, l, want_elem)) return 1;
-    SQY_HIP(hipStreamSynchronize(stream));
-    if (g_prof_on.load()) prof_collect(cx.pending);
-    return 0;
+    return b.run(g_opt.bin_boxes_subset.load() != 0, nullptr, [&](DecodeCall& c) { return boxes_range_bin(c, l, tj, b.ws, qs, d_outs, rank, op); },
+                 [&](const void* volume) {
+                     for (size_t i = 0; i < count; ++i) l.add(d_outs[i], volume, b.ws[i], qs[i], op);
+                     return launch_boxes_bin(cx, stream, l, want_elem);
+                 });
 }
 
 // what SQYAMD_Bin_Boxes_* checks without a header, before a device is looked for: boxes_arguments_ok, and sqy::admit_binning of every box
-// against the smallest shape that holds it -- the bins, the op, the output's pointer and pitches, the sum bound
+// in its own shape -- the bins, the op, the output's pointer and pitches, the sum bound
 bool bin_arguments_ok(const void* src, long srclength, long count, const long* origins, const long* extents, unsigned rank, const long* bins, int op, void* const* outs,
                       const long* out_strides, int elem_size)
 {
     if (!bins || !boxes_arguments_ok(src, srclength, count, origins, outs, extents, rank)) return false;
-    for (long i = 0; i < count; ++i) {
-        const long* o = origins + (size_t)i * rank;
-        const long* e = extents + (size_t)i * rank;
-        std::vector<uint64_t> shape(rank);
-        for (unsigned k = 0; k < rank; ++k) shape[k] = (uint64_t)o[k] + (uint64_t)std::max(e[k], 0l);     // (both below 2^63: no wrap)
+    return every_box_in_its_own_shape(count, origins, extents, rank, [&](size_t i, const std::vector<uint64_t>& shape, const long* o, const long* e) {
         sqy::BatchWindow w;
         sqy::Binning q;
         const void* out = outs ? outs[i] : static_cast<const void*>(&q);                                   // (host variant: the outputs are the library's)
-        if (!sqy::admit_binning(shape, o, e, rank, bins, op, elem_size == 2 ? 65535u : 255u, out, outs && out_strides ? out_strides + (size_t)i * rank : nullptr, &w, &q))
-            return false;
-    }
-    return true;
+        return sqy::admit_binning(shape, o, e, rank, bins, op, voxel_max(elem_size), out, outs && out_strides ? out_strides + i * rank : nullptr, &w, &q);
+    });
 }
 
 int bin_boxes_device(const void* d_src, long srclength, long count, const long* origins, const long* extents, unsigned rank, const long* bins, int op, void* const* d_outs,
@@ -4336,34 +4284,29 @@ int bin_boxes_from_host(const char* src, long srclength, long count, const long*
         std::fprintf(stderr, "[sqeazy]\t bin boxes: bad arguments\n");
         return 1;
     }
-    const sqy::HeaderInfo h = sqy::header_unpack(src, src + srclength);
-    if (!h.valid) { std::fprintf(stderr, "[sqeazy]\t unable to find a sqy header in the blob\n"); return 1; }
+    sqy::HeaderInfo h;
     uint64_t raw = 0;
-    if (!header_shape_ok(h, (uint64_t)srclength, &raw)) return 1;
-    if (h.elem_size() != elem_size) { std::fprintf(stderr, "[sqeazy]\t blob holds %s voxels\n", h.type.c_str()); return 1; }
-    std::vector<uint64_t> at((size_t)count + 1, 0);                    // (an output is no larger than the volume, count fits an int: no wrap)
-    for (long i = 0; i < count; ++i) {
+    if (!host_header_ok(src, srclength, elem_size, &h, &raw)) return 1;
+    std::vector<uint64_t> bytes((size_t)count), at;
+    const bool admitted = every_box((size_t)count, origins, extents, rank, [&](size_t i, const long* o, const long* e) {
         sqy::BatchWindow w;
         sqy::Binning q;
-        if (!sqy::admit_binning(h.shape, origins + (size_t)i * rank, extents + (size_t)i * rank, rank, bins, op, elem_size == 2 ? 65535u : 255u, &q, nullptr, &w, &q)) {
-            std::fprintf(stderr, "[sqeazy]\t bin boxes: box %ld does not lie inside the blob's shape, or a cell's sum might not fit 32 bits\n", i);
-            return 1;
-        }
-        at[(size_t)i + 1] = at[(size_t)i] + q.C[0] * q.C[1] * q.C[2] * 4u;
-    }
-    if (at.back() > (uint64_t)std::max(out_capacity, 0l)) { std::fprintf(stderr, "[sqeazy]\t bin boxes: buffer too small\n"); return 1; }
-    return decode_staged(src, (uint64_t)srclength, out, at.back(), [&](Context& cx, void* d_src, void* d_dst, hipStream_t stream) {
-        std::vector<void*> ptrs((size_t)count);
-        for (long i = 0; i < count; ++i) ptrs[(size_t)i] = static_cast<uint8_t*>(d_dst) + at[(size_t)i];
-        return bin_boxes_on_device(cx, d_src, (uint64_t)srclength, (size_t)count, origins, extents, rank, bins, op, ptrs.data(), nullptr, elem_size, stream);
+        if (!sqy::admit_binning(h.shape, o, e, rank, bins, op, voxel_max(elem_size), &q, nullptr, &w, &q))
+            return box_refused("bin boxes", i, "does not lie inside the blob's shape, or a cell's sum might not fit 32 bits");
+        bytes[i] = q.C[0] * q.C[1] * q.C[2] * 4u;
+        return true;
+    });
+    if (!admitted || !host_outputs_fit("bin boxes", bytes, out_capacity, &at)) return 1;
+    return boxes_staged(src, srclength, out, at, [&](Context& cx, void* d_src, void* const* ptrs, hipStream_t stream) {
+        return bin_boxes_on_device(cx, d_src, (uint64_t)srclength, (size_t)count, origins, extents, rank, bins, op, ptrs, nullptr, elem_size, stream);
     });
 }
 
 // ---- a whole resolution pyramid of many boxes of one large blob (SQYAMD_Pyramid_Boxes_*) ------------------------------------
-// bin_boxes_on_device with a table of bins: ONE header fetch, ONE frame index, the LZ4 frames of all boxes' z-ranges united and decoded
-// ONCE for all levels; sqy::pyramid_boxes_path says what runs, sqy::admit_pyramid what is admitted and sqy::pyramid_boxes_plan which
-// levels the bit-plane kernel fuses and how its workgroups share a box's cells.  No neutral-element launch, no global atomics.  Nothing
-// but the outputs' cells is written outside the workspace.
+// BoxesCall with a table of cell grids per box as its sink, the united frames decoded ONCE for all levels; sqy::pyramid_boxes_path says
+// what runs, sqy::admit_pyramid what is admitted -- the launches' sizes with it (sqy::PyramidSizes) -- and sqy::pyramid_boxes_plan which
+// levels the bit-plane kernel fuses and how its workgroups share a box's cells.  Its own: the pyramid_reduce launches behind level 0 or
+// behind the fused levels.  No neutral-element launch, no global atomics.  Nothing but the outputs' cells is written outside the workspace.
 static_assert(sizeof(sqy::Bitswap1BoxPyramidJob) == sqy::kBitswap1BoxPyramidJobBytes && sizeof(sqy::PyramidReduceJob) == sqy::kPyramidReduceJobBytes,
               "the pyramid jobs' layout");
 
@@ -4383,9 +4326,7 @@ struct ReduceLaunch : TiledJobs<sqy::PyramidReduceJob> {
         }
         j.spz = s.pz; j.spy = s.py; j.pz = d.pz; j.py = d.py;
         j.op = (uint32_t)op;
-        jobs.push_back(j);
-        first_tile.push_back(ntiles);
-        ntiles += (uint32_t)((d.C[0] * d.C[1] * d.C[2] + 255) / 256);
+        push(j, (uint32_t)((d.C[0] * d.C[1] * d.C[2] + 255) / 256));
     }
 };
 int launch_pyramid_reduce_jobs(Context& cx, hipStream_t stream, ReduceLaunch& l, DevBuf& buf)
@@ -4421,13 +4362,12 @@ int boxes_range_pyramid(DecodeCall& c, BinLaunch& l, TiledJobs<sqy::Bitswap1BoxB
     std::vector<PendingEvent>* pend = c.pend;
     const sqy::FrameRangesPlan& p = c.ranges_plan;
     const size_t count = ws.size();
-    if (p.boxes.size() != count) return 1;
-    std::vector<void*> level0(count);
-    std::vector<sqy::Binning> q0(count);
-    for (size_t i = 0; i < count; ++i) { level0[i] = outs[i * (size_t)levels]; q0[i] = ys[i].q[0]; }
     const sqy::PyramidPath path = sqy::pyramid_boxes_path(true, c.range_form, true, fused);
     if (path.path != sqy::BoxPath::subset_transposer || !path.fused) {
         // level 0 is Bin_Boxes' launch of the path, the rest pyramid_reduce's
+        std::vector<void*> level0(count);
+        std::vector<sqy::Binning> q0(count);
+        for (size_t i = 0; i < count; ++i) { level0[i] = outs[i * (size_t)levels]; q0[i] = ys[i].q[0]; }
         if (const int rc = boxes_range_bin(c, l, tj, ws, q0, level0.data(), rank, op)) return rc;
         return pyramid_tail_from_level0(c.cx, stream, rl, ys, outs, levels, op, path.fused);
     }
@@ -4436,22 +4376,16 @@ int boxes_range_pyramid(DecodeCall& c, BinLaunch& l, TiledJobs<sqy::Bitswap1BoxB
     for (size_t i = 0; i < count; ++i) {
         const sqy::BatchWindow& w = ws[i];
         const sqy::Pyramid& y = ys[i];
-        const sqy::FrameRangesBox& b = p.boxes[i];
         sqy::Bitswap1BoxPyramidJob j{};
         for (long k = 0; k < levels; ++k) { j.out[k] = outs[i * (size_t)levels + (size_t)k]; j.pz[k] = y.q[k].pz; j.py[k] = y.q[k].py; }
-        j.g = sqy::WindowGeometry{w.bY, w.bX, w.oz, w.oy, w.ox, w.Z, w.Y, w.X, y.q[0].pz, y.q[0].py};
-        std::copy(b.plane, b.plane + 16, j.r.plane);
-        j.r.tail = b.tail; j.r.w0 = b.w0; j.r.w1 = b.w1; j.r.v0 = b.v0; j.r.v1 = b.v1; j.r.L = b.L;
-        j.t0 = sqy::range_first_thread(b.w0, 128u / (8u * (uint32_t)p.we));
+        fill_range_job(j, w, y.q[0].pz, y.q[0].py, p.boxes[i], p.we);
         std::copy(y.q[0].bins, y.q[0].bins + 3, j.bins);
         const uint64_t E[3] = {w.Z, w.Y, w.X};
         j.plan = sqy::pyramid_boxes_plan(y, E);
         j.op = (uint32_t)op;
         j.zreg = (w.bY * w.bX) % 32 == 0 ? 1u : 0u;
         if (!sqy::bitswap1_box_pyramid_job_ok(j) || (uint64_t)pj.ntiles + j.plan.blocks > 0x7fffffffull) return 1;
-        pj.jobs.push_back(j);
-        pj.first_tile.push_back(pj.ntiles);
-        pj.ntiles += (uint32_t)j.plan.blocks;
+        pj.push(j, (uint32_t)j.plan.blocks);
         for (uint32_t k = j.plan.T + 1; k < (uint32_t)levels; ++k) rl[0].add(y, outs + i * (size_t)levels, j.plan.T, k, op);      // the levels above T: from the stored level T
     }
     const uint32_t* d_tiles = nullptr;
@@ -4467,72 +4401,42 @@ int boxes_range_pyramid(DecodeCall& c, BinLaunch& l, TiledJobs<sqy::Bitswap1BoxB
 int pyramid_boxes_on_device(Context& cx, const void* d_src_v, uint64_t srclen, size_t count, const long* origins, const long* extents, unsigned rank, long levels,
                             const long* bins, int op, void* const* d_outs, const long* out_strides, int want_elem, hipStream_t stream)
 {
-    const uint8_t* d_src = static_cast<const uint8_t*>(d_src_v);
-    DrainOnExit drain{stream, &cx.pending, cx.side};
-    sqy::HeaderInfo h;
-    if (fetch_header(d_src, srclen, stream, h)) return 1;
-    uint64_t raw_bytes = 0;
-    if (!admit_blob(h, srclen, want_elem, &raw_bytes)) return 1;
-    std::vector<sqy::BatchWindow> ws(count);
+    BoxesCall b(cx, "pyramid boxes", d_src_v, srclen, want_elem, stream);
     std::vector<sqy::Pyramid> ys(count);
-    std::vector<std::pair<uint64_t, uint64_t>> ranges(count);
     sqy::PyramidSizes sizes;
-    for (size_t i = 0; i < count; ++i) {
-        const long* o = origins + i * rank;
-        const long* e = extents + i * rank;
-        if (!sqy::admit_pyramid(h.shape, o, e, rank, levels, bins, op, want_elem == 2 ? 65535u : 255u, d_outs + i * (size_t)levels,
-                                out_strides ? out_strides + i * (size_t)levels * rank : nullptr, &ws[i], &ys[i], &sizes)) {
-            std::fprintf(stderr, "[sqeazy]\t pyramid boxes: box %zu does not lie inside the blob's shape or has another rank, a cell's sum might not fit 32 bits, or the "
-                                 "call takes too many workgroups for one launch\n", i);
-            return 1;
-        }
-        ranges[i] = {(uint64_t)o[0], (uint64_t)e[0]};
-    }
+    const int refused = b.admit(count, origins, extents, rank, [&](size_t i, const long* o, const long* e, sqy::BatchWindow* w, uint64_t*) {
+        return sqy::admit_pyramid(b.h.shape, o, e, rank, levels, bins, op, voxel_max(want_elem), d_outs + i * (size_t)levels,
+                                  out_strides ? out_strides + i * (size_t)levels * rank : nullptr, w, &ys[i], &sizes) ||
+               box_refused(b.who, i, "does not lie inside the blob's shape or has another rank, a cell's sum might not fit 32 bits, or the call takes too many workgroups "
+                                     "for one launch");
+    });
+    if (refused) return 1;
     const bool fused = g_opt.pyramid_boxes_fused.load() != 0;
     BinLaunch l;                                                        // (all wait for the stream before their tables go)
     TiledJobs<sqy::Bitswap1BoxBinJob> tj;
     TiledJobs<sqy::Bitswap1BoxPyramidJob> pj;
     ReduceLaunch rl[sqy::kPyramidMaxLevels];
-    if (g_opt.pyramid_boxes_subset.load()) {
-        DecodeCall c(cx, stream, nullptr, h, Pipeline::from_string(h.pipename), raw_bytes / (uint64_t)want_elem, d_src + h.size);
-        bool taken = false;
-        if (const int rc = c.frames_subset(ranges, false, &taken)) return rc;
-        if (taken) {
-            if (const int rc = boxes_range_pyramid(c, l, tj, pj, rl, ws, ys, d_outs, rank, levels, op, fused)) return rc;
-            return c.finish();
-        }
-    }
-    // sqy::BoxPath::whole_copy: the whole volume ONCE, level 0 of all boxes in one launch, the rest pyramid_reduce's
-    if (cx.ws.range_full.ensure(std::max<uint64_t>(raw_bytes, 16))) return 1;
-    if (const int rc = decode_on_device(cx, d_src_v, srclen, cx.ws.range_full.p, raw_bytes, want_elem, stream)) return rc;
-    for (size_t i = 0; i < count; ++i) l.add(d_outs[i * (size_t)levels], cx.ws.range_full.p, ws[i], ys[i].q[0], op);
-    if (launch_boxes_bin(cx, stream, l, want_elem)) return 1;
-    if (pyramid_tail_from_level0(cx, stream, rl, ys, d_outs, levels, op, fused)) return 1;
-    SQY_HIP(hipStreamSynchronize(stream));
-    if (g_prof_on.load()) prof_collect(cx.pending);
-    return 0;
+    return b.run(g_opt.pyramid_boxes_subset.load() != 0, nullptr,
+                 [&](DecodeCall& c) { return boxes_range_pyramid(c, l, tj, pj, rl, b.ws, ys, d_outs, rank, levels, op, fused); },
+                 [&](const void* volume) {      // level 0 of all boxes in one launch, the rest pyramid_reduce's
+                     for (size_t i = 0; i < count; ++i) l.add(d_outs[i * (size_t)levels], volume, b.ws[i], ys[i].q[0], op);
+                     return launch_boxes_bin(cx, stream, l, want_elem) || pyramid_tail_from_level0(cx, stream, rl, ys, d_outs, levels, op, fused);
+                 });
 }
 
 // what SQYAMD_Pyramid_Boxes_* checks without a header, before a device is looked for: boxes_arguments_ok, and sqy::admit_pyramid of every
-// box against the smallest shape that holds it -- the levels, the nesting, the op, every output's pointer and pitches, the sum bound
+// box in its own shape -- the levels, the nesting, the op, every output's pointer and pitches, the sum bound
 bool pyramid_arguments_ok(const void* src, long srclength, long count, const long* origins, const long* extents, unsigned rank, long levels, const long* bins, int op,
                           void* const* outs, const long* out_strides, int elem_size)
 {
     if (!bins || levels < 1 || levels > (long)sqy::kPyramidMaxLevels || !boxes_arguments_ok(src, srclength, count, origins, nullptr, extents, rank)) return false;
-    for (long i = 0; i < count; ++i) {
-        const long* o = origins + (size_t)i * rank;
-        const long* e = extents + (size_t)i * rank;
-        std::vector<uint64_t> shape(rank);
-        for (unsigned k = 0; k < rank; ++k) shape[k] = (uint64_t)o[k] + (uint64_t)std::max(e[k], 0l);     // (both below 2^63: no wrap)
+    return every_box_in_its_own_shape(count, origins, extents, rank, [&](size_t i, const std::vector<uint64_t>& shape, const long* o, const long* e) {
         sqy::BatchWindow w;
         sqy::Pyramid y;
         const void* own[sqy::kPyramidMaxLevels];                                                           // (host variant: the outputs are the library's)
-        for (long l = 0; l < levels; ++l) own[l] = outs ? outs[(size_t)i * (size_t)levels + (size_t)l] : static_cast<const void*>(&w);
-        if (!sqy::admit_pyramid(shape, o, e, rank, levels, bins, op, elem_size == 2 ? 65535u : 255u, own,
-                                outs && out_strides ? out_strides + (size_t)i * (size_t)levels * rank : nullptr, &w, &y))
-            return false;
-    }
-    return true;
+        for (long l = 0; l < levels; ++l) own[l] = outs ? outs[i * (size_t)levels + (size_t)l] : static_cast<const void*>(&w);
+        return sqy::admit_pyramid(shape, o, e, rank, levels, bins, op, voxel_max(elem_size), own, outs && out_strides ? out_strides + i * (size_t)levels * rank : nullptr, &w, &y);
+    });
 }
 
 int pyramid_boxes_device(const void* d_src, long srclength, long count, const long* origins, const long* extents, unsigned rank, long levels, const long* bins, int op,
@@ -4557,40 +4461,30 @@ int pyramid_boxes_from_host(const char* src, long srclength, long count, const l
         std::fprintf(stderr, "[sqeazy]\t pyramid boxes: bad arguments\n");
         return 1;
     }
-    const sqy::HeaderInfo h = sqy::header_unpack(src, src + srclength);
-    if (!h.valid) { std::fprintf(stderr, "[sqeazy]\t unable to find a sqy header in the blob\n"); return 1; }
+    sqy::HeaderInfo h;
     uint64_t raw = 0;
-    if (!header_shape_ok(h, (uint64_t)srclength, &raw)) return 1;
-    if (h.elem_size() != elem_size) { std::fprintf(stderr, "[sqeazy]\t blob holds %s voxels\n", h.type.c_str()); return 1; }
-    const size_t nouts = (size_t)count * (size_t)levels;
-    std::vector<uint64_t> at(nouts + 1, 0);                             // (an output is no larger than the volume, count fits an int: no wrap)
-    for (long i = 0; i < count; ++i) {
+    if (!host_header_ok(src, srclength, elem_size, &h, &raw)) return 1;
+    std::vector<uint64_t> bytes((size_t)count * (size_t)levels), at;
+    const bool admitted = every_box((size_t)count, origins, extents, rank, [&](size_t i, const long* o, const long* e) {
         sqy::BatchWindow w;
         sqy::Pyramid y;
         const void* own[sqy::kPyramidMaxLevels];
         for (long l = 0; l < levels; ++l) own[l] = &w;
-        if (!sqy::admit_pyramid(h.shape, origins + (size_t)i * rank, extents + (size_t)i * rank, rank, levels, bins, op, elem_size == 2 ? 65535u : 255u, own, nullptr, &w,
-                                &y)) {
-            std::fprintf(stderr, "[sqeazy]\t pyramid boxes: box %ld does not lie inside the blob's shape, or a cell's sum might not fit 32 bits\n", i);
-            return 1;
-        }
-        for (long l = 0; l < levels; ++l) {
-            const size_t k = (size_t)i * (size_t)levels + (size_t)l;
-            at[k + 1] = at[k] + y.q[l].C[0] * y.q[l].C[1] * y.q[l].C[2] * 4u;
-        }
-    }
-    if (at.back() > (uint64_t)std::max(out_capacity, 0l)) { std::fprintf(stderr, "[sqeazy]\t pyramid boxes: buffer too small\n"); return 1; }
-    return decode_staged(src, (uint64_t)srclength, out, at.back(), [&](Context& cx, void* d_src, void* d_dst, hipStream_t stream) {
-        std::vector<void*> ptrs(nouts);
-        for (size_t k = 0; k < nouts; ++k) ptrs[k] = static_cast<uint8_t*>(d_dst) + at[k];
-        return pyramid_boxes_on_device(cx, d_src, (uint64_t)srclength, (size_t)count, origins, extents, rank, levels, bins, op, ptrs.data(), nullptr, elem_size, stream);
+        if (!sqy::admit_pyramid(h.shape, o, e, rank, levels, bins, op, voxel_max(elem_size), own, nullptr, &w, &y))
+            return box_refused("pyramid boxes", i, "does not lie inside the blob's shape, or a cell's sum might not fit 32 bits");
+        for (long l = 0; l < levels; ++l) bytes[i * (size_t)levels + (size_t)l] = y.q[l].C[0] * y.q[l].C[1] * y.q[l].C[2] * 4u;
+        return true;
+    });
+    if (!admitted || !host_outputs_fit("pyramid boxes", bytes, out_capacity, &at)) return 1;
+    return boxes_staged(src, srclength, out, at, [&](Context& cx, void* d_src, void* const* ptrs, hipStream_t stream) {
+        return pyramid_boxes_on_device(cx, d_src, (uint64_t)srclength, (size_t)count, origins, extents, rank, levels, bins, op, ptrs, nullptr, elem_size, stream);
     });
 }
 
 // ---- the intensity histograms of many boxes of one large blob (SQYAMD_Histogram_Boxes_*) ------------------------------------
-// compare_boxes_on_device with a count for the compare: ONE header fetch, the LZ4 frames of all boxes' z-ranges united, ONE launch that
-// zeroes every histogram over the counting launch's own tables, ONE counting launch; sqy::histogram_boxes_path says what runs and
-// sqy::admit_histogram what is admitted.  Nothing but the histograms' counters is written outside the workspace.
+// BoxesCall with a count as its sink; sqy::histogram_boxes_path says what runs and sqy::admit_histogram what is admitted.  Its own: ONE
+// launch that zeroes every histogram over the counting launch's own tables in front of it, and no view -- a job's pitches are the box's.
+// Nothing but the histograms' counters is written outside the workspace.
 
 // zeroes and one window histogram under the name "boxes_window_histogram", a job per box (its `view` the histogram)
 int launch_boxes_histogram(Context& cx, hipStream_t stream, WindowLaunch& l, int elem_size, int shift)
@@ -4604,6 +4498,8 @@ int launch_boxes_histogram(Context& cx, hipStream_t stream, WindowLaunch& l, int
                                                                             (int)g_opt.histogram_boxes_merge.load(), stream));
     return 0;
 }
+// the pitches of a box that is counted, not stored by place
+WindowView counted_view(const sqy::BatchWindow& w) { return WindowView{w.Y * w.X, w.X}; }
 
 // the histograms' launches behind DecodeCall::frames_subset: box i (ws[i]) of the united frames in c.range_buf into hists[i]
 int boxes_range_histogram(DecodeCall& c, WindowLaunch& l, TiledJobs<sqy::Bitswap1BoxJob>& tj, const std::vector<sqy::BatchWindow>& ws, void* const* hists, unsigned rank,
@@ -4613,25 +4509,16 @@ int boxes_range_histogram(DecodeCall& c, WindowLaunch& l, TiledJobs<sqy::Bitswap
     std::vector<PendingEvent>* pend = c.pend;
     const sqy::FrameRangesPlan& p = c.ranges_plan;
     const size_t count = ws.size();
-    if (p.boxes.size() != count) return 1;
     if (sqy::histogram_boxes_path(true, c.range_form, true) == sqy::BoxPath::subset_transposer) {
         const uint16_t* lut = nullptr;
         if (c.range_lut(&lut)) return 1;
         if (sqy::histogram_bins(lut ? 2 : p.we, shift) != sqy::histogram_bins(want_elem, shift)) return 1;      // (the counted voxel is the entry point's)
-        const uint32_t wpt = 128u / (8u * (uint32_t)p.we);
         for (size_t i = 0; i < count; ++i) {
-            const sqy::BatchWindow& w = ws[i];
-            const sqy::FrameRangesBox& b = p.boxes[i];
-            sqy::Bitswap1BoxJob j;
+            sqy::Bitswap1BoxJob j{};
             j.view = hists[i];
-            j.g = sqy::WindowGeometry{w.bY, w.bX, w.oz, w.oy, w.ox, w.Z, w.Y, w.X, w.Y * w.X, w.X};      // (the pitches are not used: nothing is stored by place)
-            std::copy(b.plane, b.plane + 16, j.r.plane);
-            j.r.tail = b.tail; j.r.w0 = b.w0; j.r.w1 = b.w1; j.r.v0 = b.v0; j.r.v1 = b.v1; j.r.L = b.L;
-            j.t0 = sqy::range_first_thread(b.w0, wpt);
+            fill_range_job(j, ws[i], counted_view(ws[i]).sz, counted_view(ws[i]).sy, p.boxes[i], p.we);      // (the pitches are not used)
             if (!sqy::bitswap1_box_job_ok(j)) return 1;
-            tj.jobs.push_back(j);
-            tj.first_tile.push_back(tj.ntiles);
-            tj.ntiles += (uint32_t)sqy::range_job_groups(b.w0, b.w1, wpt);
+            tj.push(j, range_job_groups_of(p.boxes[i], p.we));
         }
         const uint32_t* d_tiles = nullptr;
         if (tj.upload(stream, c.cx.ws.boxes_jobs, &d_tiles)) return 1;
@@ -4642,14 +4529,8 @@ int boxes_range_histogram(DecodeCall& c, WindowLaunch& l, TiledJobs<sqy::Bitswap
                                                                       (int)g_opt.histogram_boxes_merge.load(), stream));
         return 0;
     }
-    // plain, shuffle: box i's range in the workspace is a blob of its frames, the box begins at its first one (boxes_range_out's geometry)
-    for (size_t i = 0; i < count; ++i) {
-        sqy::BatchWindow in_range = ws[i];
-        if (rank == 3) { in_range.bZ = in_range.Z; in_range.oz = 0; }
-        else if (rank == 2) { in_range.bY = in_range.Y; in_range.oy = 0; }
-        else { in_range.bX = in_range.X; in_range.ox = 0; }
-        l.add(hists[i], c.range_buf + p.boxes[i].range_at, in_range, WindowView{in_range.Y * in_range.X, in_range.X}, false);
-    }
+    // plain, shuffle: boxes_range_out's geometry
+    for (size_t i = 0; i < count; ++i) l.add(hists[i], c.range_buf + p.boxes[i].range_at, sqy::window_in_own_frames(ws[i], rank), counted_view(ws[i]), false);
     return launch_boxes_histogram(c.cx, stream, l, c.h.elem_size(), shift);
 }
 
@@ -4658,68 +4539,33 @@ int boxes_range_histogram(DecodeCall& c, WindowLaunch& l, TiledJobs<sqy::Bitswap
 int histogram_boxes_on_device(Context& cx, const void* d_src_v, uint64_t srclen, size_t count, const long* origins, const long* extents, unsigned rank, int shift,
                               void* const* d_hists, int want_elem, hipStream_t stream)
 {
-    const uint8_t* d_src = static_cast<const uint8_t*>(d_src_v);
-    DrainOnExit drain{stream, &cx.pending, cx.side};
-    sqy::HeaderInfo h;
-    if (fetch_header(d_src, srclen, stream, h)) return 1;
-    uint64_t raw_bytes = 0;
-    if (!admit_blob(h, srclen, want_elem, &raw_bytes)) return 1;
-    std::vector<sqy::BatchWindow> ws(count);
-    std::vector<std::pair<uint64_t, uint64_t>> ranges(count);
-    const uint64_t frame_voxels = raw_bytes / (uint64_t)want_elem / h.shape[0];
-    uint64_t copy_tiles = 0, range_groups = 0;               // what the one counting launch may hold, whichever it is
-    for (size_t i = 0; i < count; ++i) {
-        const long* o = origins + i * rank;
-        const long* e = extents + i * rank;
-        if (!sqy::admit_histogram(h.shape, o, e, rank, shift, want_elem, d_hists[i], &ws[i])) {
-            std::fprintf(stderr, "[sqeazy]\t histogram boxes: box %zu does not lie inside the blob's shape, or has another rank\n", i);
-            return 1;
-        }
-        ranges[i] = {(uint64_t)o[0], (uint64_t)e[0]};
-        copy_tiles += sqy::batch_bitswap1_tiles(ws[i].Z * ws[i].Y * ws[i].X);
-        range_groups += (uint64_t)e[0] * frame_voxels / sqy::kBatchTileVoxels + 2;      // (at least range_job_groups of the box's words)
-    }
-    if (std::max(copy_tiles, range_groups) > 0x7fffffffull) {
-        std::fprintf(stderr, "[sqeazy]\t histogram boxes: too many workgroups for one launch\n");
-        return 1;
-    }
+    BoxesCall b(cx, "histogram boxes", d_src_v, srclen, want_elem, stream);
+    const int refused = b.admit(count, origins, extents, rank, [&](size_t i, const long* o, const long* e, sqy::BatchWindow* w, uint64_t* copy_tiles) {
+        if (!sqy::admit_histogram(b.h.shape, o, e, rank, shift, want_elem, d_hists[i], w)) return box_refused(b.who, i, "does not lie inside the blob's shape, or has another rank");
+        *copy_tiles = sqy::batch_bitswap1_tiles(w->Z * w->Y * w->X);
+        return true;
+    });
+    if (refused || !b.one_launch_holds()) return 1;
     WindowLaunch l;                                                     // (both wait for the stream before their tables go)
     TiledJobs<sqy::Bitswap1BoxJob> tj;
-    if (g_opt.histogram_boxes_subset.load()) {
-        DecodeCall c(cx, stream, nullptr, h, Pipeline::from_string(h.pipename), raw_bytes / (uint64_t)want_elem, d_src + h.size);
-        bool taken = false;
-        if (const int rc = c.frames_subset(ranges, false, &taken)) return rc;
-        if (taken) {
-            if (const int rc = boxes_range_histogram(c, l, tj, ws, d_hists, rank, shift, want_elem)) return rc;
-            return c.finish();
-        }
-    }
-    // sqy::BoxPath::whole_copy: the whole volume ONCE, then all boxes in one launch
-    if (cx.ws.range_full.ensure(std::max<uint64_t>(raw_bytes, 16))) return 1;
-    if (const int rc = decode_on_device(cx, d_src_v, srclen, cx.ws.range_full.p, raw_bytes, want_elem, stream)) return rc;
-    for (size_t i = 0; i < count; ++i) l.add(d_hists[i], cx.ws.range_full.p, ws[i], WindowView{ws[i].Y * ws[i].X, ws[i].X}, false);
-    if (launch_boxes_histogram(cx, stream, l, want_elem, shift)) return 1;
-    SQY_HIP(hipStreamSynchronize(stream));
-    if (g_prof_on.load()) prof_collect(cx.pending);
-    return 0;
+    return b.run(g_opt.histogram_boxes_subset.load() != 0, nullptr, [&](DecodeCall& c) { return boxes_range_histogram(c, l, tj, b.ws, d_hists, rank, shift, want_elem); },
+                 [&](const void* volume) {
+                     for (size_t i = 0; i < count; ++i) l.add(d_hists[i], volume, b.ws[i], counted_view(b.ws[i]), false);
+                     return launch_boxes_histogram(cx, stream, l, want_elem, shift);
+                 });
 }
 
 // what SQYAMD_Histogram_Boxes_* checks without a header, before a device is looked for: boxes_arguments_ok, and sqy::admit_histogram of
-// every box against the smallest shape that holds it -- the shift, the histogram's pointer
+// every box in its own shape -- the shift, the histogram's pointer
 bool histogram_arguments_ok(const void* src, long srclength, long count, const long* origins, const long* extents, unsigned rank, int shift, void* const* hists,
                             int elem_size)
 {
     if (!boxes_arguments_ok(src, srclength, count, origins, hists, extents, rank)) return false;
-    for (long i = 0; i < count; ++i) {
-        const long* o = origins + (size_t)i * rank;
-        const long* e = extents + (size_t)i * rank;
-        std::vector<uint64_t> shape(rank);
-        for (unsigned k = 0; k < rank; ++k) shape[k] = (uint64_t)o[k] + (uint64_t)std::max(e[k], 0l);     // (both below 2^63: no wrap)
+    return every_box_in_its_own_shape(count, origins, extents, rank, [&](size_t i, const std::vector<uint64_t>& shape, const long* o, const long* e) {
         sqy::BatchWindow w;
         const void* out = hists ? hists[i] : static_cast<const void*>(&w);                                 // (host variant: the histograms are the library's)
-        if (!sqy::admit_histogram(shape, o, e, rank, shift, elem_size, out, &w)) return false;
-    }
-    return true;
+        return sqy::admit_histogram(shape, o, e, rank, shift, elem_size, out, &w);
+    });
 }
 
 int histogram_boxes_device(const void* d_src, long srclength, long count, const long* origins, const long* extents, unsigned rank, int shift, void* const* d_hists,
@@ -4735,8 +4581,8 @@ int histogram_boxes_device(const void* d_src, long srclength, long count, const 
                                      static_cast<hipStream_t>(hip_stream));
 }
 
-// host pointers: the header and every box are checked here, before anything is staged; the histograms come back dense, back to back in
-// box order, nbins 32-bit counters each
+// host pointers: the buffer, then the header and every box are checked here, before anything is staged; the histograms come back dense,
+// back to back in box order, nbins 32-bit counters each
 int histogram_boxes_from_host(const char* src, long srclength, long count, const long* origins, const long* extents, unsigned rank, int shift, char* out,
                               long out_capacity, int elem_size)
 {
@@ -4744,24 +4590,18 @@ int histogram_boxes_from_host(const char* src, long srclength, long count, const
         std::fprintf(stderr, "[sqeazy]\t histogram boxes: bad arguments\n");
         return 1;
     }
-    const uint64_t hist_bytes = (uint64_t)sqy::histogram_bins(elem_size, shift) * 4u, total = (uint64_t)count * hist_bytes;      // (count fits an int: no wrap)
-    if (total > (uint64_t)std::max(out_capacity, 0l)) { std::fprintf(stderr, "[sqeazy]\t histogram boxes: buffer too small\n"); return 1; }
-    const sqy::HeaderInfo h = sqy::header_unpack(src, src + srclength);
-    if (!h.valid) { std::fprintf(stderr, "[sqeazy]\t unable to find a sqy header in the blob\n"); return 1; }
+    std::vector<uint64_t> at;                                           // (count fits an int: no wrap)
+    if (!host_outputs_fit("histogram boxes", std::vector<uint64_t>((size_t)count, (uint64_t)sqy::histogram_bins(elem_size, shift) * 4u), out_capacity, &at)) return 1;
+    sqy::HeaderInfo h;
     uint64_t raw = 0;
-    if (!header_shape_ok(h, (uint64_t)srclength, &raw)) return 1;
-    if (h.elem_size() != elem_size) { std::fprintf(stderr, "[sqeazy]\t blob holds %s voxels\n", h.type.c_str()); return 1; }
-    for (long i = 0; i < count; ++i) {
+    if (!host_header_ok(src, srclength, elem_size, &h, &raw)) return 1;
+    const bool admitted = every_box((size_t)count, origins, extents, rank, [&](size_t i, const long* o, const long* e) {
         sqy::BatchWindow w;
-        if (!sqy::admit_histogram(h.shape, origins + (size_t)i * rank, extents + (size_t)i * rank, rank, shift, elem_size, &w, &w)) {
-            std::fprintf(stderr, "[sqeazy]\t histogram boxes: box %ld does not lie inside the blob's shape\n", i);
-            return 1;
-        }
-    }
-    return decode_staged(src, (uint64_t)srclength, out, total, [&](Context& cx, void* d_src, void* d_dst, hipStream_t stream) {
-        std::vector<void*> ptrs((size_t)count);
-        for (long i = 0; i < count; ++i) ptrs[(size_t)i] = static_cast<uint8_t*>(d_dst) + (uint64_t)i * hist_bytes;
-        return histogram_boxes_on_device(cx, d_src, (uint64_t)srclength, (size_t)count, origins, extents, rank, shift, ptrs.data(), elem_size, stream);
+        return sqy::admit_histogram(h.shape, o, e, rank, shift, elem_size, &w, &w) || box_refused("histogram boxes", i, "does not lie inside the blob's shape");
+    });
+    if (!admitted) return 1;
+    return boxes_staged(src, srclength, out, at, [&](Context& cx, void* d_src, void* const* ptrs, hipStream_t stream) {
+        return histogram_boxes_on_device(cx, d_src, (uint64_t)srclength, (size_t)count, origins, extents, rank, shift, ptrs, elem_size, stream);
     });
 }
 
@@ -5397,11 +5237,7 @@ int update_box_patch(DecodeCall& c, const UpdateBoxCall& u, WindowLaunch& l)
         return 0;
     }
     // plain: the range in the workspace is a blob of the box's frames, the box begins at its first one (box_range_out's rule)
-    sqy::BatchWindow in_range = u.w;
-    if (u.rank == 3) { in_range.bZ = u.w.Z; in_range.oz = 0; }
-    else if (u.rank == 2) { in_range.bY = u.w.Y; in_range.oy = 0; }
-    else { in_range.bX = u.w.X; in_range.ox = 0; }
-    l.add(u.d_view, c.range_buf + p.range_at, in_range, u.v, false);
+    l.add(u.d_view, c.range_buf + p.range_at, sqy::window_in_own_frames(u.w, u.rank), u.v, false);
     const uint32_t* d_tiles = nullptr;
     if (l.upload(stream, c.cx.ws.box_window, &d_tiles)) return 1;
     SQY_TIMED("box_window_paste", sqy::launch_batch_window_paste(static_cast<const sqy::BatchWindowJob*>(c.cx.ws.box_window.p), d_tiles, 1, l.ntiles, u.elem, stream));
@@ -5678,7 +5514,7 @@ int update_boxes_patch(DecodeCall& c, const UpdateBoxCall& u, const UpdateBoxesT
             for (uint32_t i : segs[s].boxes) {
                 const sqy::BatchWindow& w = t.ws[i];
                 hb[named].view = t.d_views[i];
-                hb[named].g = sqy::WindowGeometry{w.bY, w.bX, w.oz, w.oy, w.ox, w.Z, w.Y, w.X, t.vs[i].sz, t.vs[i].sy};
+                hb[named].g = sqy::window_geometry(w, t.vs[i].sz, t.vs[i].sy);
                 ++named;
             }
             ht[s] = (uint32_t)groups;
@@ -5826,20 +5662,11 @@ int update_boxes_from_host(const char* pipeline, const char* src, long srclength
         sum += vox * (uint64_t)elem_size;
     }
     if (views_bytes < 0 || sum != (uint64_t)views_bytes) { std::fprintf(stderr, "[sqeazy]\t update boxes: the views hold another number of bytes than the boxes\n"); return 1; }
-    const sqy::HeaderInfo h = sqy::header_unpack(src, src + srclength);
-    if (!h.valid) { std::fprintf(stderr, "[sqeazy]\t unable to find a sqy header in the blob\n"); return 1; }
+    sqy::HeaderInfo h;
     uint64_t raw = 0;
-    if (!header_shape_ok(h, (uint64_t)srclength, &raw)) return 1;
-    if (h.elem_size() != elem_size) { std::fprintf(stderr, "[sqeazy]\t blob holds %s voxels\n", h.type.c_str()); return 1; }
-    std::vector<uint64_t> at((size_t)count + 1, 0);
-    for (long i = 0; i < count; ++i) {
-        sqy::BatchWindow w;
-        if (!sqy::admit_window(h.shape, origins + (size_t)i * rank, extents + (size_t)i * rank, rank, &w)) {
-            std::fprintf(stderr, "[sqeazy]\t update boxes: box %ld does not lie inside the blob's shape\n", i);
-            return 1;
-        }
-        at[(size_t)i + 1] = at[(size_t)i] + w.Z * w.Y * w.X * (uint64_t)elem_size;
-    }
+    std::vector<uint64_t> bytes, at;
+    if (!host_header_ok(src, srclength, elem_size, &h, &raw) || !host_box_bytes("update boxes", h, count, origins, extents, rank, elem_size, &bytes)) return 1;
+    (void)sqy::output_offsets(bytes, views_bytes, &at);               // (the views' bytes are the boxes': checked above)
     if (!device_present()) { std::fprintf(stderr, "[sqeazy]\t no MI355X (HIP device) visible: sqeazy_amd has no CPU path\n"); return 1; }
     ContextLease lease;
     if (!lease.ctx) { std::fprintf(stderr, "[sqeazy]\t no usable HIP device\n"); return 1; }

@@ -160,6 +160,33 @@ struct BatchWindow { uint64_t bZ, bY, bX, oz, oy, ox, Z, Y, X; bool whole; };
 // false: rank 0 or above 3, a header of another rank, an origin below 0, an extent below 1, or origin + extent past the header's shape
 // (a sum that overflows `long` is past it)
 bool admit_window(const std::vector<uint64_t>& header_shape, const long* origin, const long* extent, unsigned rank, BatchWindow* out);
+// the clip's geometry of a window and the destination's two pitches
+inline WindowGeometry window_geometry(const BatchWindow& w, uint64_t sz, uint64_t sy) { return WindowGeometry{w.bY, w.bX, w.oz, w.oy, w.ox, w.Z, w.Y, w.X, sz, sy}; }
+// A window rebased onto a buffer that holds only its own frames: the blob's first dimension shrinks to the window's and the window begins
+// at its first frame.  The frames are the HEADER's first dimension: of a header of rank 2 the rows, of rank 1 the voxels
+inline BatchWindow window_in_own_frames(BatchWindow w, unsigned rank)
+{
+    if (rank == 3) { w.bZ = w.Z; w.oz = 0; }
+    else if (rank == 2) { w.bY = w.Y; w.oy = 0; }
+    else { w.bX = w.X; w.ox = 0; }
+    return w;
+}
+// the smallest shape that holds the box [origin, origin + extent): what an admit_* is given where there is no header yet (origins not
+// below 0; an extent below 1 counts as 0 and is refused by the admit_*; both below 2^63: no wrap)
+inline std::vector<uint64_t> smallest_holding_shape(const long* origin, const long* extent, unsigned rank)
+{
+    std::vector<uint64_t> shape(rank);
+    for (unsigned k = 0; k < rank; ++k) shape[k] = (uint64_t)origin[k] + (uint64_t)(extent[k] > 0 ? extent[k] : 0);
+    return shape;
+}
+// Outputs back to back in one buffer: at[i] the first byte of output i, at.back() the bytes of all (bytes.size() + 1 entries; the callers'
+// outputs are no larger than a volume and fewer than 2^31: no wrap).  false: more than `capacity` bytes (a capacity below 0 holds nothing)
+inline bool output_offsets(const std::vector<uint64_t>& bytes, long capacity, std::vector<uint64_t>* at)
+{
+    at->assign(bytes.size() + 1, 0);
+    for (size_t i = 0; i < bytes.size(); ++i) (*at)[i + 1] = (*at)[i] + bytes[i];
+    return at->back() <= (uint64_t)(capacity > 0 ? capacity : 0);
+}
 // a window job of the window copy and the windowed transposer (sqy::BatchWindowJob, sqy_kernels.h)
 constexpr uint64_t kBatchWindowJobBytes = 112;
 // The tables of one window launch, one upload: njobs jobs at 0 | tiles_at (16-byte aligned): njobs + 1 words of prefix sums | total
@@ -507,6 +534,15 @@ struct FrameRangesBox {
     uint64_t pa = 0, pb = 0;                // shuffle: the range's places
     bool direct = false;                    // shuffle: the compaction IS the range
 };
+// planes: the box's range as the range transposers take it (Range: sqy::Bitswap1Range of sqy_kernels.h, whose fields these are)
+template <class Range>
+Range bitswap1_range_of(const FrameRangesBox& b)
+{
+    Range r;
+    for (int s = 0; s < 16; ++s) r.plane[s] = b.plane[s];
+    r.tail = b.tail; r.w0 = b.w0; r.w1 = b.w1; r.v0 = b.v0; r.v1 = b.v1; r.L = b.L;
+    return r;
+}
 struct FrameRangesPlan {
     bool ok = false;
     std::vector<uint32_t> ids;

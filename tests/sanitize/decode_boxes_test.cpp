@@ -3,7 +3,8 @@
 // on its own, for every form, over all pairs and triples of z-ranges of small streams (disjoint, touching, nested, identical): the ids are
 // the union, and every range reads the same bytes out of the union's compaction as out of its own; and the workgroup -> job mapping of
 // bitswap1_decode_range_windows_kernel, walked over first_tile as the kernel walks it, with sqy::range_run per job: every word of every
-// job exactly once.  Prints "decode_boxes ok" and returns 0.
+// job exactly once; and the pure helpers every boxes driver shares (a box's range for the transposers, a window in its own frames, the
+// outputs' offsets table, the smallest shape that holds a box).  Prints "decode_boxes ok" and returns 0.
 #include "../../sqeazy_amd/csrc/sqy_batch_window.hpp"
 #include "../../sqeazy_amd/csrc/sqy_pipeline.hpp"
 
@@ -284,11 +285,64 @@ int test_groups()
     return 0;
 }
 
+// the fields of sqy::Bitswap1Range (sqy_kernels.h, which this program does not need): what sqy::bitswap1_range_of fills
+struct PlaneRange { uint64_t plane[16]; uint64_t tail; uint64_t w0, w1, v0, v1, L; };
+
+// the pure helpers of the boxes drivers (sqy_pipeline.hpp)
+int test_driver_helpers()
+{
+    // a box's range: every value to the field of its name, nothing else of the box
+    sqy::FrameRangesBox b;
+    for (int s = 0; s < 16; ++s) b.plane[s] = 1000 + 7 * (uint64_t)s;
+    b.range_at = 1; b.tail = 2; b.v0 = 3; b.v1 = 4; b.w0 = 5; b.w1 = 6; b.L = 7; b.pa = 8; b.pb = 9; b.direct = true;
+    const PlaneRange r = sqy::bitswap1_range_of<PlaneRange>(b);
+    for (int s = 0; s < 16; ++s) CHECK(r.plane[s] == 1000 + 7 * (uint64_t)s);
+    CHECK(r.tail == 2 && r.v0 == 3 && r.v1 == 4 && r.w0 == 5 && r.w1 == 6 && r.L == 7);
+
+    // a window in its own frames, ranks 1 to 3: every voxel lies where it lay in the blob, less the frames in front of the window
+    const std::vector<uint64_t> shapes[3] = {{40}, {9, 11}, {5, 6, 7}};
+    const long origins[3][3] = {{13}, {4, 3}, {2, 1, 3}}, extents[3][3] = {{20}, {5, 7}, {3, 4, 2}};
+    for (unsigned rank = 1; rank <= 3; ++rank) {
+        sqy::BatchWindow w;
+        CHECK(sqy::admit_window(shapes[rank - 1], origins[rank - 1], extents[rank - 1], rank, &w));
+        uint64_t frame = 1;
+        for (unsigned k = 1; k < rank; ++k) frame *= shapes[rank - 1][k];
+        const uint64_t in_front = (uint64_t)origins[rank - 1][0] * frame, own = (uint64_t)extents[rank - 1][0] * frame;
+        const sqy::BatchWindow f = sqy::window_in_own_frames(w, rank);
+        CHECK(f.Z == w.Z && f.Y == w.Y && f.X == w.X && f.bZ * f.bY * f.bX == own);
+        for (uint64_t z = 0; z < w.Z; ++z)
+            for (uint64_t y = 0; y < w.Y; ++y)
+                for (uint64_t x = 0; x < w.X; ++x) {
+                    const uint64_t in_blob = ((w.oz + z) * w.bY + w.oy + y) * w.bX + w.ox + x, in_frames = ((f.oz + z) * f.bY + f.oy + y) * f.bX + f.ox + x;
+                    CHECK(in_blob >= in_front && in_frames == in_blob - in_front && in_frames < own);
+                }
+        const sqy::WindowGeometry g = sqy::window_geometry(f, 77, 5);
+        CHECK(g.bY == f.bY && g.bX == f.bX && g.oz == f.oz && g.oy == f.oy && g.ox == f.ox && g.Z == f.Z && g.Y == f.Y && g.X == f.X && g.sz == 77 && g.sy == 5);
+    }
+
+    // the outputs' offsets: prefix sums; a total that exceeds the capacity by one byte is refused, the same total fits; no room below 0
+    std::vector<uint64_t> at;
+    CHECK(sqy::output_offsets({3, 0, 5}, 8, &at) && at == (std::vector<uint64_t>{0, 3, 3, 8}));
+    CHECK(!sqy::output_offsets({3, 0, 5}, 7, &at) && at.back() == 8);
+    CHECK(!sqy::output_offsets({1}, 0, &at) && !sqy::output_offsets({1}, -1, &at) && !sqy::output_offsets({1}, -0x7fffffffffffffffl - 1, &at));
+    CHECK(sqy::output_offsets({}, -1, &at) && at == std::vector<uint64_t>{0});
+    CHECK(sqy::output_offsets({0x7fffffffffffffffull}, 0x7fffffffffffffffl, &at) && !sqy::output_offsets({0x7fffffffffffffffull, 1}, 0x7fffffffffffffffl, &at));
+
+    // the smallest shape that holds a box: origin + extent; an extent below 1 adds nothing (and no admission takes the box); no wrap
+    const long o[3] = {2, 0, 5}, e[3] = {3, -4, 1}, good[3] = {3, 4, 1}, far[1] = {0x7fffffffffffffffl};
+    CHECK(sqy::smallest_holding_shape(o, e, 3) == (std::vector<uint64_t>{5, 0, 6}));
+    CHECK(sqy::smallest_holding_shape(far, far, 1) == std::vector<uint64_t>{0xfffffffffffffffeull});
+    sqy::BatchWindow w;
+    CHECK(!sqy::admit_window(sqy::smallest_holding_shape(o, e, 3), o, e, 3, &w));
+    CHECK(sqy::admit_window(sqy::smallest_holding_shape(o, good, 3), o, good, 3, &w) && w.bZ == 5 && w.bY == 4 && w.bX == 6 && w.oz + w.Z == w.bZ && w.ox + w.X == w.bX);
+    return 0;
+}
+
 } // namespace
 
 int main()
 {
-    if (test_path() || test_groups() || test_shuffle()) return 1;
+    if (test_path() || test_groups() || test_shuffle() || test_driver_helpers()) return 1;
     // n = 7 * 33 * 31 in chunks of 4096: tails of 9 voxels (16-bit planes) and of 1 (8-bit planes); 6 * 384 voxels in chunks of 256: no tail,
     // many frames between two ranges' words; 5 * 63 in chunks of 48: plane segments that straddle chunks
     const struct { uint64_t shape0, frame_voxels, chunk; } streams[] = {{7, 33 * 31, 4096}, {6, 16 * 24, 256}, {5, 7 * 9, 48}};
